@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: agent opt-steps/sec, DQN Atari 84x84x4, batch 256 (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2]
+    python bench.py --gpus N --steps K --warmup W [--config c2] [--dump-outputs DIR] [--full]
 
 A "step" is one Agent::opt() -- on-device ChaCha12 index draw + gather from the 1M-transition HBM
 ring + online/target forward + Huber TD loss + backward + Adam (+ target sync when due) -- exactly
@@ -20,10 +20,20 @@ to host staging), and the line carries "rccl_ranks": N.
 c1/c4/c5 are parity-test configurations; their lines use the same schema and exist so that their
 rates and per-kernel rooflines are backed by tracked files under profiles/.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live: per-kernel HIP-event timing on the
-agent's own stream (bdr_agent_profile_*), algorithmic FLOPs / bytes from SURVEY.md section 8(d).
-`cpu_baseline` times oracle/torch_ref.py (the ATen op sequence tch 0.16 binds) on the host cores:
+Prints ONE JSON line (rank 0).  A plain run sets up, runs W untimed and K timed steps, writes the outputs of the last
+timed step when --dump-outputs is given, and prints the line: `value` (opt-steps/s) and `ms_per_step` are of those K
+steps.  --full adds everything else, as the default run did before it existed: for windows under 500 steps the cold
+window and the steady-state leg in front of the timed window (PROTOCOL_VERSION / WINDOW_ORDER below), the finite-loss
+check, the exact-f32 twin of c2 / c4, the per-kernel `roofline` and the `cpu_baseline`.  `roofline` is measured live:
+per-kernel HIP-event timing on the agent's own stream (bdr_agent_profile_*), algorithmic FLOPs / bytes from SURVEY.md
+section 8(d).  `cpu_baseline` times oracle/torch_ref.py (the ATen op sequence tch 0.16 binds) on the host cores:
 1 thread, a thread-count sweep, and the best count for >= 100 steps or the time budget.
+
+--dump-outputs DIR writes, after the timed steps, what they computed: the parameters of the trained networks (online
+and target) and, for c1 / c2 / c4, Adam's first moment, one float32 DIR/<name>.npy each (a few MB to ~30 MB).  Every
+input is seeded (replay contents, parameter init, index stream), so two runs with the same arguments start from the
+same state; in a plain run the step count is W + K, so two builds can be compared output for output.  (--full with
+K < 500 runs a steady-state leg of about half a second first, whose length depends on the measured rate.)
 """
 import argparse
 import json
@@ -509,6 +519,35 @@ def cpu_baseline(config, batch, loss, budget_s):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(config, agent):
+    """{name: float32 array}: what the opt steps computed, read back through the agent's public accessors - the online and
+    target networks' parameters and (DQN / IQN) Adam's first moment, the running mean of the gradients the backward pass made."""
+    if config in ("c1", "c2"):
+        return {k: agent.get_params(k) for k in ("qnet", "qnet_tgt", "exp_avg")}
+    if config == "c4":
+        return {k: agent.get_params(k) for k in ("iqn", "iqn_tgt", "exp_avg")}
+    nc = agent.config.n_critics
+    names = ["pi", "log_alpha"] + [f"qnet_{i}" for i in range(nc)] + [f"qnet_tgt_{i}" for i in range(nc)]
+    return {k: agent.get_params(k) for k in names}
+
+
+def dump_outputs(config, agent, out_dir):
+    """--dump-outputs: one DIR/<name>.npy (float32) per array of output_arrays, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    agent.sync()
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in output_arrays(config, agent).items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ launcher
 def self_launch(n_gpus: int, argv=None, python=None) -> int:
     """Re-executes this script as n_gpus ranks of one node through torch.distributed.run (rendezvous on 127.0.0.1, a free port) and
@@ -556,11 +595,16 @@ def main():
     ap.add_argument("--frame-ring", action="store_true", help="c2 / c4: single-frame store (8.8 GB instead of 56.6 GB for 1M transitions)")
     ap.add_argument("--arithmetic", default="bf16x3_6", choices=["bf16x3_6", "f32_exact"],
                     help="bdr_{dqn,iqn}_config::arithmetic of the measured agent (c2 / c4): the library default (split-operand bf16 products in the large forward "
-                         "layers) or exact f32 products everywhere; with the default, N=1 runs time an exact-f32 twin as well (`value_exact_f32`)")
-    ap.add_argument("--no-exact-leg", action="store_true", help="skip the exact-f32 twin of the c2 / c4 agent (value_exact_f32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "layers) or exact f32 products everywhere; with the default, N=1 --full runs time an exact-f32 twin as well (`value_exact_f32`)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: cold-window / steady-state legs (K < 500), finite-loss check, exact-f32 twin, roofline, "
+                         "CPU baseline. Without it a run does setup, W untimed + K timed steps, --dump-outputs and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the trained parameters (and Adam's first moment) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-exact-leg", action="store_true", help="--full: skip the exact-f32 twin of the c2 / c4 agent (value_exact_f32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
-    ap.add_argument("--profile-steps", type=int, default=30)
+    ap.add_argument("--profile-steps", type=int, default=30, help="--full: steps of the per-kernel roofline leg (0: none)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / control-plane check without a GPU (tests/test_bench_launcher.py): "
                     "ranks rendezvous, barrier, agree on a MAX-reduced time; rank 0 prints one line with \"dry_run\": true and no value")
     args = ap.parse_args()
@@ -699,8 +743,10 @@ def main():
     # Everything is in the line (`cold_window`, `steady_state`, `untimed_steps_before_window`, `window_order`); nothing is taken out
     # of the timed steps.  The same order at every N (the scaling curve compares like with like; the loop length is agreed on over the
     # control plane so that every rank runs the same number of exchanges); long windows (--steps >= 500) keep the plain protocol.
+    # A plain run (no --full) times the window alone: W untimed + K timed steps right after setup, the protocol long windows
+    # (--steps >= 500) have always used, and a step count that does not depend on any measured time (--dump-outputs).
     cold, steady, untimed_before = None, None, args.warmup
-    if args.steps < 500:
+    if args.full and args.steps < 500:
         dt_c = window(0)
         if dist:
             t = torch.tensor([dt_c], dtype=torch.float64)
@@ -729,19 +775,23 @@ def main():
         dt = float(t[0])
 
     result = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.config, agent, args.dump_outputs)
     if rank == 0:
         ms = 1000.0 * dt / args.steps
         value = world * args.steps / dt
-        # the timed steps trained a real network: one more step with its Record, which must be finite
-        rec = agent.opt_with_record(rb)
-        final_loss = float(rec[conf["loss_key"]])
-        if not (final_loss == final_loss and abs(final_loss) != float("inf")):
-            sys.exit(f"bench.py: non-finite loss {final_loss} after the timed steps")
+        final_loss = None
+        if args.full:
+            # the timed steps trained a real network: one more step with its Record, which must be finite
+            rec = agent.opt_with_record(rb)
+            final_loss = float(rec[conf["loss_key"]])
+            if not (final_loss == final_loss and abs(final_loss) != float("inf")):
+                sys.exit(f"bench.py: non-finite loss {final_loss} after the timed steps")
         # roofline leg: per-kernel HIP-event timing on the agent's stream.  An empty event bracket measures TWO marker
         # packets back to back; a bracket around a kernel contains the kernel plus ONE marker's processing time, so half of
         # the empty bracket is subtracted (reproduces rocprofv3's kernel durations to ~0.4 us, profiles/).
         roof = None
-        if args.profile_steps > 0:   # (0: under rocprofv3, whose own kernel trace is the measurement)
+        if args.full and args.profile_steps > 0:   # (0: under rocprofv3, whose own kernel trace is the measurement)
             prof, cnt, null_ms = profile(agent, rb, args.profile_steps)
             if any(v <= 0.0 for v in prof.values()):   # an outlier empty bracket: measure again
                 prof, cnt, null_ms = profile(agent, rb, max(30, args.profile_steps))
@@ -753,7 +803,9 @@ def main():
         par += ")"
         cfgd = {"workload": conf["workload"], "name": args.config, "batch_size": conf["batch"], "replay_capacity": conf["capacity"]}
         cfgd.update(conf["cfg_extra"])
-        cfgd.update({"parallelism": par, "final_loss": round(final_loss, 6), "samples_per_sec": round(value * conf["batch"], 1)})
+        cfgd.update({"parallelism": par, "samples_per_sec": round(value * conf["batch"], 1)})
+        if final_loss is not None:
+            cfgd["final_loss"] = round(final_loss, 6)
         result = {"metric": conf["metric"], "value": round(value, 2),
                   "unit": "opt-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                   "ms_per_step": round(ms, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -764,6 +816,9 @@ def main():
                                  "sync_interval": args.sync_interval, "data_plane": "rccl" if rccl_ranks else "host-transport test build of csrc/comm.hip (BDR_BENCH_SHARE_GPU=1: ranks share one device, which RCCL refuses)"}
         if steady is not None:
             result["steady_state"] = steady
+        if not args.full:
+            result["window"] = (f"W = {args.warmup} untimed + K = {args.steps} timed steps right after setup; cold-window / steady-state legs, "
+                                "exact-f32 twin, roofline and CPU baseline: bench.py --full")
         if cold is not None:
             result["cold_window"] = cold
             result["untimed_steps_before_window"] = untimed_before
@@ -774,7 +829,8 @@ def main():
             result["value_steady"] = steady["value"]
             result["warmup_note"] = (f"`warmup` = the W = {args.warmup} untimed steps directly in front of the K timed ones (the contract's window); "
                                      f"{untimed_before} untimed steps ran in this process before the timed ones in total (cold window + steady-state leg + W)")
-        result["protocol_version"] = PROTOCOL_VERSION
+        if args.full:
+            result["protocol_version"] = PROTOCOL_VERSION
     agent.close()
     # The exact-f32 twin (round 6): the default agent of c2 / c4 computes split-operand bf16 products in its large forward layers
     # (bdr_{dqn,iqn}_config::arithmetic = BDR_ARITH_BF16X3_6).  A second agent built with BDR_ARITH_F32_EXACT on the same ring runs
@@ -782,7 +838,7 @@ def main():
     # arithmetics' rates from one box.  N = 1 only; after the headline's legs, so `value` is untouched (protocol version unchanged); after
     # the headline agent is CLOSED: one DQN agent per process orders its two queues with device flags, a second one alive beside it falls
     # back to event ordering (~10 % slower) and would not be the same schedule.
-    if (rank == 0 and world == 1 and args.config in ("c2", "c4") and not args.no_exact_leg and cold is not None
+    if (rank == 0 and world == 1 and args.full and args.config in ("c2", "c4") and not args.no_exact_leg and cold is not None
             and not arithmetic_is_exact(args.arithmetic, {"c2": "BDR_DQN_F32_EXACT", "c4": "BDR_IQN_F32_EXACT"}[args.config])):
         saved_issue = dict(BF16_ISSUE)
         conf_x = build_config(B, args.config, args, rank, local_rank, arithmetic="f32_exact", rb=rb)
@@ -815,7 +871,7 @@ def main():
         result["exact_f32"] = ex
     rb.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.config, conf["batch"], args.loss, args.cpu_seconds)
         result["cpu_baseline"]["gpu_over_cpu"] = round(result["value"] / max(result["cpu_baseline"]["value"], 1e-9), 1)
     if rank == 0:

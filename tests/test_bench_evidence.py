@@ -154,3 +154,29 @@ def test_c4_step_work_counts_every_layer_once(tmp_path, monkeypatch):
         bench.BF16_ISSUE.update(saved)
     assert abs(r["step"]["gflop"] - step_flops / 1e9) < 1e-2
     assert r["step"]["frac"] <= 1.0 + 1e-3 and abs(r["step"]["fp32_mfma"]["gflop"] - r["step"]["gflop"]) < 1e-2
+
+
+def test_dump_outputs_writes_what_the_steps_computed_as_float32(tmp_path):
+    """--dump-outputs: one float32 DIR/<name>.npy per array the agent's accessors return after the timed steps (online / target
+    parameters, and Adam's first moment for DQN / IQN); SAC names every network."""
+    import types
+    import numpy as np
+
+    class Agent:
+        def __init__(self, n_critics=0):
+            self.config = types.SimpleNamespace(n_critics=n_critics)
+
+        def sync(self):
+            pass
+
+        def get_params(self, name="qnet"):
+            return np.full(7, len(name), np.float64)
+
+    for config, names in (("c2", ["exp_avg", "qnet", "qnet_tgt"]), ("c1", ["exp_avg", "qnet", "qnet_tgt"]), ("c4", ["exp_avg", "iqn", "iqn_tgt"]),
+                          ("c5", ["log_alpha", "pi", "qnet_0", "qnet_1", "qnet_tgt_0", "qnet_tgt_1"])):
+        out = tmp_path / config
+        bench.dump_outputs(config, Agent(n_critics=2), str(out))
+        assert sorted(os.listdir(out)) == [n + ".npy" for n in names]
+        for n in names:
+            a = np.load(out / (n + ".npy"))
+            assert a.dtype == np.float32 and a.shape == (7,) and (a == len(n)).all()

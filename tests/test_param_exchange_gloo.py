@@ -105,9 +105,19 @@ def test_world_size_2_gloo():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=420) for _ in range(2))
+    # the ranks run without a GPU, as (v) requires: on a machine with one they would reach ncclCommInitRank with rank 1 holding
+    # an all-zero unique id and wait there, so the devices are hidden from them (the spawned processes inherit the environment)
+    saved = os.environ.get("HIP_VISIBLE_DEVICES")
+    os.environ["HIP_VISIBLE_DEVICES"] = "-1"
+    try:
+        for p in procs:
+            p.start()
+    finally:
+        if saved is None:
+            os.environ.pop("HIP_VISIBLE_DEVICES", None)
+        else:
+            os.environ["HIP_VISIBLE_DEVICES"] = saved
+    res =sorted(q.get(timeout=420) for _ in range(2))
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

@@ -28,10 +28,12 @@ def candidate(tmp_path_factory):
 def test_cargo_project_pins_the_crates_border_pins():
     toml = open(os.path.join(KAT, "Cargo.toml")).read()
     assert re.search(r'rand\s*=\s*\{\s*version\s*=\s*"=0\.8\.5"', toml) and 'tch = "0.16.0"' in toml and 'image = "0.23.14"' in toml
-    ref = "/root/reference/Cargo.toml"
-    if os.path.exists(ref):   # (this container only)
-        r = open(ref).read()
-        assert 'rand = { version = "=0.8.5"' in r and 'tch = "0.16.0"' in r and 'image = "0.23.14"' in r
+    # the versions the upstream workspace pins (tests/golden/upstream_crate_pins.json): the KAT project must build against the same ones
+    pins = json.load(open(os.path.join(ROOT, "tests", "golden", "upstream_crate_pins.json")))
+    assert (pins["rand"], pins["tch"], pins["image"]) == ("=0.8.5", "0.16.0", "0.23.14")
+    for crate in ("rand", "tch", "image"):
+        m = re.search(r'^' + crate + r'\s*=\s*(?:"([^"]+)"|\{\s*version\s*=\s*"([^"]+)")', toml, re.M)
+        assert m and (m.group(1) or m.group(2)) == pins[crate], (crate, m and m.groups())
     rs = open(os.path.join(KAT, "src", "main.rs")).read()
     for needle in ("StdRng::seed_from_u64", "next_u32", "next_u64", "fill_bytes", "VarStore::new", "vs.save(", "resize(&img, 84, 84, Triangle)",
                    "upstream_kat.json"):

@@ -10,7 +10,7 @@ for rep in range(2):
         env = dict(os.environ)
         if ch:
             env["BDR_DW_CHUNKS"] = ch
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2000", "--warmup", "200", "--no-cpu-baseline", "--profile-steps", "60",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2000", "--warmup", "200", "--no-cpu-baseline", "--profile-steps", "60",
                             "--capacity", "100000"], capture_output=True, text=True, env=env, cwd=ROOT)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])

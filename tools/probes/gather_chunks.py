@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for ch in ("0", "1", "2", "3", "4", "6", "8"):
     env = dict(os.environ, BDR_GATHER_CHUNKS=ch)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "50", "--no-cpu-baseline", "--profile-steps", "60"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "300", "--warmup", "50", "--no-cpu-baseline", "--profile-steps", "60"],
                        capture_output=True, text=True, env=env, cwd=ROOT)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])
