@@ -78,6 +78,22 @@ class SacConfigC(C.Structure):
                 ("seed", C.c_uint64), ("opt_actor", AdamWConfigC), ("opt_critic", AdamWConfigC)]
 
 
+class MlpConfigC(C.Structure):
+    """bdr_mlp_config: border-candle-agent's MlpConfig (mlp/config.rs:6-11) without in/out dims"""
+    _fields_ = [("n_units", C.c_int32), ("units", C.c_int32 * BDR_MAX_UNITS), ("activation_out", C.c_int32)]
+
+
+class IqlConfigC(C.Structure):
+    _fields_ = [("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("value", MlpConfigC), ("actor", MlpConfigC), ("critic", MlpConfigC),
+                ("n_critics", C.c_int32), ("critic_tau", C.c_double), ("lr_value", C.c_double), ("lr_actor", C.c_double),
+                ("lr_critic", C.c_double), ("opt_value", AdamWConfigC), ("opt_actor", AdamWConfigC), ("opt_critic", AdamWConfigC),
+                ("min_log_std", C.c_double), ("max_log_std", C.c_double), ("action_limit", C.c_int32), ("action_min", C.c_double),
+                ("action_max", C.c_double), ("action_scale", C.c_double), ("gamma", C.c_double), ("tau_iql", C.c_double),
+                ("inv_lambda", C.c_double), ("exp_adv_max", C.c_double), ("adv_softmax", C.c_int32), ("critic_loss", C.c_int32),
+                ("n_updates_per_opt", C.c_uint64), ("batch_size", C.c_uint64), ("train", C.c_int32), ("device", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class DqnRecordC(C.Structure):
     _fields_ = [("loss", C.c_float), ("pred_mean", C.c_float), ("reward_mean", C.c_float),
                 ("tgt_mean", C.c_float), ("tgt_minus_pred_mean", C.c_float), ("has_verbose", C.c_int32)]
@@ -167,6 +183,7 @@ ABI_SYMBOLS = [
     "bdr_agent_profile_enable", "bdr_agent_profile_read",
     "bdr_iqn_config_default", "bdr_iqn_create", "bdr_iqn_update_on_batch", "bdr_iqn_forward", "bdr_iqn_qvalues",
     "bdr_sac_config_default", "bdr_sac_create", "bdr_sac_update_on_batch", "bdr_sac_sample", "bdr_sac_sample_device",
+    "bdr_iql_config_default", "bdr_iql_create", "bdr_iql_update_on_batch", "bdr_iql_probe", "bdr_iql_sample", "bdr_iql_sample_device",
     "bdr_comm_get_unique_id", "bdr_comm_init_rank", "bdr_comm_destroy", "bdr_comm_agree", "bdr_sac_probe", "bdr_agent_allreduce_params",
     "bdr_agent_broadcast_params", "bdr_agent_set_grad_comm", "bdr_dqn_grads_on_batch", "bdr_agent_apply_grads",
     "bdr_atari_prep_create", "bdr_atari_prep_destroy", "bdr_atari_prep_reset", "bdr_atari_prep_step", "bdr_atari_prep_obs",
@@ -196,7 +213,7 @@ def lib() -> C.CDLL:
     L.bdr_version.restype = C.c_char_p
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)  # AttributeError here == ABI drift
-        if name not in ("bdr_last_error", "bdr_version", "bdr_dqn_config_default", "bdr_sac_config_default", "bdr_iqn_config_default",
+        if name not in ("bdr_last_error", "bdr_version", "bdr_dqn_config_default", "bdr_sac_config_default", "bdr_iqn_config_default", "bdr_iql_config_default",
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
                         "bdr_trainer_ops_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default"):
             fn.restype = C.c_int32
@@ -265,6 +282,13 @@ def lib() -> C.CDLL:
     L.bdr_sac_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.bdr_sac_sample.argtypes = [vp, u64, vp, vp]
     L.bdr_sac_probe.argtypes = [vp, i32, vp, u64]
+    L.bdr_iql_config_default.restype = None
+    L.bdr_iql_config_default.argtypes = [C.POINTER(IqlConfigC)]
+    L.bdr_iql_create.argtypes = [C.POINTER(IqlConfigC), C.POINTER(vp)]
+    L.bdr_iql_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.bdr_iql_probe.argtypes = [vp, i32, vp, u64]
+    L.bdr_iql_sample.argtypes = [vp, u64, vp, vp]
+    L.bdr_iql_sample_device.argtypes = [vp, u64, vp, u64, vp]
     L.bdr_comm_get_unique_id.argtypes = [vp]
     L.bdr_comm_init_rank.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.bdr_comm_destroy.argtypes = [vp]

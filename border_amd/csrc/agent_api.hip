@@ -200,6 +200,17 @@ int32_t load_named(const std::string& path, const std::vector<NamedTensor>& meta
     return is_safetensors_path(path) ? load_safetensors(path, meta, data, n) : load_archive(path, meta, data, n);
 }
 
+// the safetensors container whatever the file name (candle's VarMap::save / load: IQL's "<stem>.pt" files)
+int32_t save_safetensors_named(const std::string& path, const std::vector<NamedTensor>& meta, const float* data, size_t n)
+{
+    return save_safetensors(path, meta, data, n);
+}
+
+int32_t load_safetensors_named(const std::string& path, const std::vector<NamedTensor>& meta, float* data, size_t n)
+{
+    return load_safetensors(path, meta, data, n);
+}
+
 std::string ckpt_save_path(const bdr_agent* a, const char* dir, const std::string& stem)
 {
     return std::string(dir) + "/" + stem + (a->ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt.tch");
@@ -799,6 +810,7 @@ float* agent_arena(bdr_agent* a, int which, size_t* n_floats, hipStream_t* strea
 }
 int32_t agent_scale(bdr_agent* a, float* p, size_t n, float s) { return launch_scale(a->stream, p, n, s); }
 void agent_set_grad_comm(bdr_agent* a, void* comm, int32_t (*reduce)(bdr_agent*, void*)) { a->grad_comm = comm; a->grad_reduce = reduce; }
+const char* agent_kind(const bdr_agent* a) { return a->kind(); }
 struct XSeg { size_t off, n; };
 int agent_exchange_plan(bdr_agent* a, int which, XSeg* segs, int cap, hipStream_t* comm)
 {

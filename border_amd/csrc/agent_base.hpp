@@ -416,6 +416,8 @@ inline void param_stat_keys(const std::vector<NamedTensor>& meta, std::vector<st
 }
 int32_t save_named(const std::string& path, const std::vector<NamedTensor>& meta, const float* data, size_t n);
 int32_t load_named(const std::string& path, const std::vector<NamedTensor>& meta, float* data, size_t n);
+int32_t save_safetensors_named(const std::string& path, const std::vector<NamedTensor>& meta, const float* data, size_t n);
+int32_t load_safetensors_named(const std::string& path, const std::vector<NamedTensor>& meta, float* data, size_t n);
 // "<dir>/<stem>.pt.tch" (the reference's names) or "<dir>/<stem>.safetensors" by bdr_agent_set_checkpoint_format; the load
 // path falls back to the other container when only that one exists
 std::string ckpt_save_path(const bdr_agent* a, const char* dir, const std::string& stem);

@@ -495,6 +495,7 @@ int32_t d_sample(void* a, uint64_t n, const void* obs, void* act)
 {
     bdr_agent* ag = (bdr_agent*)a;
     if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample(ag, n, (const float*)obs, (float*)act);
+    if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample(ag, n, (const float*)obs, (float*)act);   // util/actor.rs:226-241
     return bdr_agent_sample(ag, n, obs, (int64_t*)act, nullptr);
 }
 int32_t d_opt(void* a, void* b) { return bdr_agent_opt((bdr_agent*)a, (bdr_replay*)b); }
@@ -518,6 +519,7 @@ int32_t d_sample_dev(void* a, uint64_t n, const void* obs_dev, uint64_t stride, 
 {
     bdr_agent* ag = (bdr_agent*)a;
     if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample_device(ag, n, obs_dev, stride, (float*)act);
+    if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample_device(ag, n, obs_dev, stride, (float*)act);
     return bdr_agent_sample_device(ag, n, obs_dev, stride, (int64_t*)act, nullptr);
 }
 }  // namespace

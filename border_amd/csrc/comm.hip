@@ -19,6 +19,7 @@ int32_t agent_exchange_begin(bdr_agent* a, int seg);
 int32_t agent_exchange_end(bdr_agent* a, int seg);
 int32_t scale_on(hipStream_t st, float* p, size_t n, float s);
 void agent_set_grad_comm(bdr_agent* a, void* comm, int32_t (*reduce)(bdr_agent*, void*));
+const char* agent_kind(const bdr_agent* a);
 }
 
 namespace {
@@ -212,6 +213,7 @@ int32_t bdr_agent_set_grad_comm(bdr_agent* a, bdr_comm* c)
 {
     BDR_REQUIRE(a, "null agent");
     if (c) {
+        BDR_REQUIRE(strcmp(agent_kind(a), "iql") != 0, "synchronous data-parallel gradient exchange is not available for IQL agents");
         int dev = 0;
         BDR_REQUIRE(agent_arena(a, 4, nullptr, nullptr, &dev), "agent has no gradient arena");
         BDR_REQUIRE(dev == c->device, "agent and communicator live on different devices");

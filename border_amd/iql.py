@@ -1,0 +1,275 @@
+"""Host-side mirror of border-candle-agent's Iql agent over the C ABI (offline RL).
+
+  IqlConfig            border-candle-agent/src/iql/config.rs (defaults :109-125; `.lambda(v)` sets inv_lambda = 1 / v)
+  ValueConfig          iql/value.rs (value_config: MlpConfig, opt_config)
+  MultiCriticConfig    util/critic.rs:35-43 (n_nets 2, q_config, opt_config, tau 0.005)
+  GaussianActorConfig  util/actor.rs:36-55 (policy_config: Mlp3's MlpConfig, opt_config, min/max_log_std, action_limit)
+  ActionLimit          util/actor.rs:29-32 (Tanh{action_scale} | Clamp{action_min, action_max})
+  CandleMlpConfig      mlp/config.rs:6-11 (activation_out: "None" | "ReLU")
+  Iql                  iql/base.rs (Agent, Policy::sample, SyncModel ships the actor)
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass, field
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _lib
+from .dqn import OptimizerConfig
+from .replay import SimpleReplayBuffer
+
+ACTIVATIONS = {"None": 0, "ReLU": 1, "Tanh": 2, "Sigmoid": 3}   # lib.rs:58-63 (Tanh / Sigmoid are rejected by the library)
+
+
+@dataclass
+class CandleMlpConfig:
+    units: Tuple[int, ...] = (256, 256)
+    activation_out: str = "None"
+
+    def fill(self, m: "_lib.MlpConfigC") -> None:
+        m.n_units = len(self.units)
+        for i, u in enumerate(self.units):
+            m.units[i] = u
+        m.activation_out = ACTIVATIONS[self.activation_out]
+
+
+@dataclass
+class ActionLimit:
+    kind: str = "Clamp"          # "Clamp" | "Tanh"
+    action_min: float = -1.0
+    action_max: float = 1.0
+    action_scale: float = 1.0
+
+    @classmethod
+    def Clamp(cls, action_min: float = -1.0, action_max: float = 1.0) -> "ActionLimit":
+        return cls("Clamp", action_min, action_max)
+
+    @classmethod
+    def Tanh(cls, action_scale: float = 1.0) -> "ActionLimit":
+        return cls("Tanh", action_scale=action_scale)
+
+
+@dataclass
+class ValueConfig:
+    value_config: CandleMlpConfig = field(default_factory=CandleMlpConfig)
+    opt_config: OptimizerConfig = field(default_factory=lambda: OptimizerConfig.Adam(3e-4))
+
+
+@dataclass
+class MultiCriticConfig:
+    n_nets: int = 2
+    q_config: CandleMlpConfig = field(default_factory=CandleMlpConfig)
+    opt_config: OptimizerConfig = field(default_factory=lambda: OptimizerConfig.Adam(3e-4))
+    tau: float = 0.005
+
+
+@dataclass
+class GaussianActorConfig:
+    policy_config: CandleMlpConfig = field(default_factory=CandleMlpConfig)
+    opt_config: OptimizerConfig = field(default_factory=lambda: OptimizerConfig.Adam(3e-4))
+    min_log_std: float = -20.0
+    max_log_std: float = 2.0
+    action_limit: ActionLimit = field(default_factory=ActionLimit.Clamp)
+
+
+@dataclass
+class IqlConfig:
+    obs_dim: int = 0
+    act_dim: int = 0
+    value_config: ValueConfig = field(default_factory=ValueConfig)
+    critic_config: MultiCriticConfig = field(default_factory=MultiCriticConfig)
+    actor_config: GaussianActorConfig = field(default_factory=GaussianActorConfig)
+    gamma: float = 0.99
+    tau_iql: float = 0.7
+    inv_lambda: float = 10.0
+    n_updates_per_opt: int = 1
+    batch_size: int = 1
+    adv_softmax: bool = False
+    critic_loss: str = "Mse"
+    exp_adv_max: float = 100.0
+    train: bool = False
+    seed: int = 0
+    device: Optional[int] = None
+
+    def lambda_(self, v: float) -> "IqlConfig":
+        """IqlConfig::lambda (iql/config.rs): inv_lambda = 1 / v"""
+        self.inv_lambda = 1.0 / v
+        return self
+
+    def to_c(self) -> _lib.IqlConfigC:
+        c = _lib.IqlConfigC()
+        _lib.lib().bdr_iql_config_default(C.byref(c))
+        c.obs_dim, c.act_dim = self.obs_dim, self.act_dim
+        self.value_config.value_config.fill(c.value)
+        self.actor_config.policy_config.fill(c.actor)
+        self.critic_config.q_config.fill(c.critic)
+        c.n_critics, c.critic_tau = self.critic_config.n_nets, self.critic_config.tau
+        for name, o in (("value", self.value_config.opt_config), ("actor", self.actor_config.opt_config), ("critic", self.critic_config.opt_config)):
+            setattr(c, "lr_" + name, o.lr)
+            getattr(c, "opt_" + name).fill(o)
+        ac = self.actor_config
+        c.min_log_std, c.max_log_std = ac.min_log_std, ac.max_log_std
+        lim = ac.action_limit
+        c.action_limit = {"Clamp": 0, "Tanh": 1}[lim.kind]
+        c.action_min, c.action_max, c.action_scale = lim.action_min, lim.action_max, lim.action_scale
+        c.gamma, c.tau_iql, c.inv_lambda, c.exp_adv_max = self.gamma, self.tau_iql, self.inv_lambda, self.exp_adv_max
+        c.adv_softmax = int(self.adv_softmax)
+        c.critic_loss = {"Mse": 0, "SmoothL1": 1}[self.critic_loss]
+        c.n_updates_per_opt, c.batch_size, c.train, c.seed = self.n_updates_per_opt, self.batch_size, int(self.train), self.seed
+        c.device = -1 if self.device is None else self.device
+        return c
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class Iql:
+    def __init__(self, config: IqlConfig):
+        self.config = config
+        h = C.c_void_p()
+        c = config.to_c()
+        _lib.check(_lib.lib().bdr_iql_create(C.byref(c), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def build(cls, config: IqlConfig) -> "Iql":
+        return cls(config)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().bdr_agent_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def n_critics(self) -> int:
+        return self.config.critic_config.n_nets
+
+    # model ids (bdr_agent_get_params `which`)
+    def which(self, name: str, role: str = "param") -> int:
+        nc = self.n_critics
+        if name.startswith("critic_tgt_"):
+            i = 1 + nc + int(name[len("critic_tgt_"):])
+        elif name.startswith("critic_"):
+            i = 1 + int(name[len("critic_"):])
+        else:
+            i = {"actor": 0, "value": 1 + 2 * nc}[name]
+        return i + {"param": 0, "grad": 100, "exp_avg": 200, "exp_avg_sq": 300}[role]
+
+    WHICH = {"actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the actor == model 0
+
+    def arena_device_ptr(self, which="actor"):
+        ptr, n = C.c_void_p(), C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
+        return ptr.value, n.value
+
+    def train(self):
+        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 1))
+
+    def eval(self):
+        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 0))
+
+    def opt(self, buffer: SimpleReplayBuffer) -> None:
+        _lib.check(_lib.lib().bdr_agent_opt(self._h, buffer.handle))
+
+    def opt_with_record(self, buffer: SimpleReplayBuffer) -> dict:
+        from .dqn import opt_with_named_record
+        return opt_with_named_record(self._h, buffer)
+
+    def profile_enable(self, on: bool = True):
+        _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
+
+    def draw_noise(self, n: int) -> np.ndarray:
+        """n draws of the agent's device noise stream (bdr_agent_draw_noise): the N(0,1) numbers of Policy::sample in train mode."""
+        from .dqn import draw_noise
+        return draw_noise(self._h, n)
+
+    def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated) -> dict:
+        f = lambda x: np.ascontiguousarray(x, dtype=np.float32)
+        obs, act, next_obs, reward = map(f, (obs, act, next_obs, reward))
+        term = np.ascontiguousarray(is_terminated, dtype=np.int8)
+        trunc = np.ascontiguousarray(is_truncated, dtype=np.int8)
+        rec = np.zeros(3, np.float32)
+        _lib.check(_lib.lib().bdr_iql_update_on_batch(self._h, len(reward), _p(obs), _p(act), _p(next_obs), _p(reward), _p(term),
+                                                      _p(trunc), _p(rec)))
+        return dict(loss_value=float(rec[0]), loss_critic=float(rec[1]), loss_actor=float(rec[2]))
+
+    PROBES = {"q_tgt_min_value": 0, "v": 1, "u": 2, "tgt": 3, "q_pred": 4, "q_tgt_min_actor": 5, "w": 6, "logp": 7, "v_next": 8, "v_obs": 9}
+
+    def probe(self, what: str, batch: int) -> np.ndarray:
+        """Intermediates of the last update (bdr_iql_probe): q_pred [n_critics, B], every other one [B]."""
+        shape = (self.n_critics, batch) if what == "q_pred" else (batch,)
+        out = np.empty(shape, np.float32)
+        _lib.check(_lib.lib().bdr_iql_probe(self._h, self.PROBES[what], _p(out), out.size))
+        return out
+
+    def sample(self, obs) -> np.ndarray:
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        out = np.empty((obs.shape[0], self.config.act_dim), np.float32)
+        _lib.check(_lib.lib().bdr_iql_sample(self._h, obs.shape[0], _p(obs), _p(out)))
+        return out
+
+    def sample_device(self, obs_dev: int, n: int, row_stride: int) -> np.ndarray:
+        out = np.empty((n, self.config.act_dim), np.float32)
+        _lib.check(_lib.lib().bdr_iql_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(out)))
+        return out
+
+    def sync(self):
+        _lib.check(_lib.lib().bdr_agent_sync(self._h))
+
+    @property
+    def n_opts(self) -> int:
+        n = C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
+        return n.value
+
+    def param_count(self, name="actor") -> int:
+        n = C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_param_count_of(self._h, self.which(name), C.byref(n)))
+        return n.value
+
+    def get_params(self, name="actor", role="param") -> np.ndarray:
+        out = np.empty(self.param_count(name), np.float32)
+        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.which(name, role), _p(out), out.size))
+        return out
+
+    def set_params(self, params, name="actor", role="param") -> None:
+        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.which(name, role), _p(p), p.size))
+
+    def model_info(self):
+        """SyncModel::model_info: the actor's parameters."""
+        return self.n_opts, self.get_params("actor")
+
+    def sync_model(self, model_info) -> None:
+        self.set_params(model_info, "actor")
+
+    def set_checkpoint_format(self, fmt: str) -> None:
+        """"tch" (default): the reference's `<stem>.pt` files (safetensors, as candle's VarMap writes them); "safetensors":
+        `<stem>.safetensors`."""
+        from .checkpoint import FORMATS
+        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
+        self._ckpt_ext = {"tch": ".pt", "safetensors": ".safetensors"}[fmt]
+
+    def save_params(self, path: str):
+        """iql/base.rs:292-302: actor, critic, critic.tgt (the ONLINE critics, util/critic.rs:272-285), value."""
+        os.makedirs(path, exist_ok=True)
+        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
+        ext = getattr(self, "_ckpt_ext", ".pt")
+        return [os.path.join(path, stem + ext) for stem in ("actor", "critic", "critic.tgt", "value")]
+
+    def load_params(self, path: str):
+        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))

@@ -295,7 +295,8 @@ BDR_API int32_t bdr_agent_opt_with_scalars(bdr_agent* a, bdr_replay* buffer, flo
  *        then qnet.param_stats() - "<var>_mean", "<var>_std" (population) for c1.weight ... l2.bias / mlp.ln{i}.* in the
  *        variables' order (util.rs:64-80) - and "ratio_best_act" = n_samples_best_act / n_samples_act, which resets both
  *        counters (dqn/base.rs:316-342);
- *   IQN  "loss_critic" (iqn/base.rs:190);   SAC  "loss_critic", "loss_actor", "ent_coef" (sac/base.rs:187-196). */
+ *   IQN  "loss_critic" (iqn/base.rs:190);   SAC  "loss_critic", "loss_actor", "ent_coef" (sac/base.rs:187-196);
+ *   IQL  "loss_value", "loss_critic", "loss_actor", each averaged over n_updates_per_opt (iql/base.rs:177-185). */
 BDR_API int32_t bdr_agent_record_keys(bdr_agent* a, char* names_out, uint64_t names_cap, int32_t* n_keys);
 
 /* Test helper: n draws of the agent's own device noise stream copied to the host - SAC: the N(0,1) draws of action_logp
@@ -407,7 +408,10 @@ BDR_API int32_t bdr_agent_arena_release(bdr_agent* a, int32_t which);
 
 /* Agent::save_params / load_params (dqn/base.rs:345-371; iqn/base.rs:303-317; sac/base.rs:313-345): writes / reads
  * `qnet.pt.tch`, `qnet_tgt.pt.tch` (IQN: iqn, iqn_tgt; SAC: pi, qnet_{i}, qnet_tgt_{i}, ent_coef) under dir - the
- * reference's file names.  The container follows the file name exactly as tch's VarStore::{save,load} do:
+ * reference's file names.  IQL (iql/base.rs:292-309): `actor.pt`, `critic.pt`, `critic.tgt.pt`, `value.pt` - candle VarMaps, which
+ * are safetensors whatever the extension, so BDR_CKPT_TCH writes safetensors there and BDR_CKPT_SAFETENSORS `<stem>.safetensors`;
+ * critic.tgt.pt holds the ONLINE critics and loading reads both critic files into the online critics, leaving the targets
+ * untouched (util/critic.rs:272-298).  The container follows the file name exactly as tch's VarStore::{save,load} do:
  *   BDR_CKPT_TCH          "<stem>.pt.tch": the libtorch named-tensor archive (TorchScript module zip) that tch writes
  *                         through torch-sys at_save_multi and reads with torch::jit::load (default, = the reference);
  *   BDR_CKPT_SAFETENSORS  "<stem>.safetensors".
@@ -713,6 +717,73 @@ BDR_API int32_t bdr_sac_sample(bdr_agent* a, uint64_t n, const float* obs, float
 BDR_API int32_t bdr_sac_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
 
 /* ------------------------------------------------------------------------------------------
+ * IQL agent  (border-candle-agent/src/iql/{base.rs,config.rs,value.rs}; offline RL)
+ * Value = Mlp (mlp.rs:14-24, iql/value.rs), critics = MultiCritic of Mlp on cat(obs, act) (util/critic.rs),
+ * actor = GaussianActor (util/actor.rs) over Mlp3 (mlp/mlp3.rs): mean = Mlp(obs) without output activation and a
+ * state-independent log-std `head2` [1, act_dim] initialised to 0.
+ * ---------------------------------------------------------------------------------------- */
+enum { BDR_ACTIVATION_NONE = 0, BDR_ACTIVATION_RELU = 1, BDR_ACTIVATION_TANH = 2, BDR_ACTIVATION_SIGMOID = 3 };   /* lib.rs:58-63 Activation */
+enum { BDR_ACTION_LIMIT_CLAMP = 0, BDR_ACTION_LIMIT_TANH = 1 };                                                /* util/actor.rs:29-32 ActionLimit */
+
+/* MlpConfig of border-candle-agent (mlp/config.rs:6-11).  activation_out: BDR_ACTIVATION_NONE / _RELU (Tanh / Sigmoid: BDR_ERR_INVALID).
+ * The actor's Mlp3 ignores activation_out, as the reference does (mlp3.rs: mlp_forward(.., &Activation::None)). */
+typedef struct {
+    int32_t n_units;
+    int32_t units[BDR_MAX_UNITS];
+    int32_t activation_out; /* BDR_ACTIVATION_* */
+} bdr_mlp_config;
+
+/* IqlConfig (iql/config.rs:109-125) with its ValueConfig, MultiCriticConfig (util/critic.rs:35-43) and GaussianActorConfig
+ * (util/actor.rs:44-55).  Each model's OptimizerConfig is `lr` plus a bdr_adamw_config: Adam{lr} is candle-optimisers' Adam with
+ * PyTorch's defaults, AdamW is candle-nn's (weight_decay 0.01 by default); amsgrad does not exist there and is rejected. */
+typedef struct {
+    int32_t obs_dim, act_dim;
+    bdr_mlp_config value;         /* ValueConfig.value_config                 */
+    bdr_mlp_config actor;         /* GaussianActorConfig.policy_config (Mlp3) */
+    bdr_mlp_config critic;        /* MultiCriticConfig.q_config               */
+    int32_t n_critics;            /* MultiCriticConfig.n_nets (default 2)     */
+    double critic_tau;            /* MultiCriticConfig.tau (default 0.005)    */
+    double lr_value, lr_actor, lr_critic;
+    bdr_adamw_config opt_value, opt_actor, opt_critic;
+    double min_log_std, max_log_std;  /* GaussianActorConfig (-20, 2)     */
+    int32_t action_limit;             /* BDR_ACTION_LIMIT_* (default Clamp{-1, 1}) */
+    double action_min, action_max, action_scale;
+    double gamma;                 /* 0.99 (f32 in the reference) */
+    double tau_iql;               /* 0.7                          */
+    double inv_lambda;            /* 10 (= 1 / lambda)            */
+    double exp_adv_max;           /* 100                          */
+    int32_t adv_softmax;          /* false                        */
+    int32_t critic_loss;          /* BDR_LOSS_* (Mse)             */
+    uint64_t n_updates_per_opt, batch_size;   /* 1, 1 */
+    int32_t train;
+    int32_t device;               /* -1: none given */
+    uint64_t seed;                /* the library's parameter initialiser and the device noise stream of Policy::sample */
+} bdr_iql_config;
+BDR_API void bdr_iql_config_default(bdr_iql_config* cfg);                    /* iql/config.rs:109-125 */
+BDR_API int32_t bdr_iql_create(const bdr_iql_config* cfg, bdr_agent** out);  /* iql/base.rs:226-270 (Configurable::build) */
+/* One Iql::opt_ loop iteration (iql/base.rs:157-188) on a host minibatch: update_value (:75-86), update_critic (:88-121) with the
+ * soft update of every target critic, update_actor (:123-155).  gamma_not_done counts is_truncated (util.rs:235-255).
+ * rec3: loss_value, loss_critic, loss_actor.
+ * Parameter models for bdr_agent_{get,set}_params / param_count_of: 0 actor (mlp.ln{k}.weight/bias ..., then head2), 1+i critic_i,
+ * 1+n_critics+i critic_tgt_i, 1+2*n_critics value; +100 gradient, +200 exp_avg, +300 exp_avg_sq.  SyncModel ships model 0. */
+BDR_API int32_t bdr_iql_update_on_batch(bdr_agent* a, uint64_t n, const float* obs, const float* act, const float* next_obs,
+                                        const float* reward, const int8_t* is_terminated, const int8_t* is_truncated, float* rec3);
+/* Parity probes: intermediates of the LAST IQL update, to the host.  what:
+ *   0 q_tgt_min [B]     min_i Qtgt_i(obs, act) of update_value (:77; util/critic.rs:205-218)
+ *   1 v [B]             V(obs) before the value step (:78)          2 u [B]     q - v (:79)
+ *   3 tgt [B]           r + gamma_not_done * V'(next_obs) (:99-101)
+ *   4 q_pred [n_critics][B]  Q_i(obs, act) of update_critic (:97)
+ *   5 q_tgt_min [B]     min_i Qtgt_i(obs, act) of update_actor, after the soft update (:127)
+ *   6 w [B]             the advantage weights (:129-136)            7 logp [B]  log pi(act | obs) (:141)
+ *   8 v_next [B]        V'(next_obs) (:100)                          9 v_obs [B]  V'(obs) of update_actor (:128) */
+BDR_API int32_t bdr_iql_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* Policy::sample (util/actor.rs:226-241): train: mean + std * N(0,1) (the agent's device noise stream, bdr_agent_draw_noise),
+ * eval: mean; then clamp(action_min, action_max) or action_scale * tanh. */
+BDR_API int32_t bdr_iql_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out);
+/* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
+BDR_API int32_t bdr_iql_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU parameter exchange (replaces the learner->actors NamedTensors channel of
  * border-async-trainer/src/async_trainer/base.rs:268-272 with RCCL over xGMI).
  * ---------------------------------------------------------------------------------------- */
@@ -727,7 +798,7 @@ BDR_API int32_t bdr_comm_agree(bdr_comm* c, int32_t local_ok, int32_t* all_ok);
 /* params <- mean over ranks (ncclAllReduce sum on the flat arena, then 1/nranks), on the
  * agent's stream; which as in bdr_agent_get_params (0 qnet, 1 qnet_tgt, 2/3 Adam moments). */
 BDR_API int32_t bdr_agent_allreduce_params(bdr_agent* a, bdr_comm* c, int32_t which);
-/* Synchronous data-parallel mode for DQN agents: from now on every Agent::opt of `a` runs backward, all-reduces the gradient
+/* Synchronous data-parallel mode for DQN agents (an IQL agent returns BDR_ERR_INVALID): from now on every Agent::opt of `a` runs backward, all-reduces the gradient
  * arena over `c` (ncclAllReduce sum, then 1/nranks, on the agent's stream) and then takes the optimizer step, so the ranks
  * stay bit-for-bit in lock step and N x batch B/N equals one step on batch B.  c == NULL: back to independent steps. */
 BDR_API int32_t bdr_agent_set_grad_comm(bdr_agent* a, bdr_comm* c);

@@ -828,3 +828,286 @@ impl SacConfig {
         Ok(c)
     }
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// IQL: border-candle-agent's configs (`iql/config.rs:22-125`, `iql/value.rs:19-35`, `util/critic.rs:20-43`, `util/actor.rs:29-55`,
+// `mlp/config.rs:6-11`, `opt.rs:8-40`, `lib.rs:58-63`), with candle's field names so the d4rl example YAML files load unchanged.
+
+/// `border_candle_agent::Activation`.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone, Copy)]
+pub enum Activation {
+    None,
+    ReLU,
+    Tanh,
+    Sigmoid,
+}
+
+impl Activation {
+    /// Tanh / Sigmoid have no kernel here: `bdr_iql_create` rejects them with `BDR_ERR_INVALID`.
+    pub fn code(&self) -> i32 {
+        match self {
+            Activation::None => ffi::BDR_ACTIVATION_NONE,
+            Activation::ReLU => ffi::BDR_ACTIVATION_RELU,
+            Activation::Tanh => ffi::BDR_ACTIVATION_TANH,
+            Activation::Sigmoid => ffi::BDR_ACTIVATION_SIGMOID,
+        }
+    }
+}
+
+/// `border_candle_agent::mlp::MlpConfig`.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct CandleMlpConfig {
+    pub in_dim: i64,
+    pub units: Vec<i64>,
+    pub out_dim: i64,
+    pub activation_out: Activation,
+}
+
+impl CandleMlpConfig {
+    pub fn new(in_dim: i64, units: Vec<i64>, out_dim: i64, activation_out: Activation) -> Self {
+        Self { in_dim, units, out_dim, activation_out }
+    }
+
+    pub(crate) fn fill(&self, m: &mut ffi::bdr_mlp_config, what: &str) -> Result<()> {
+        fill_units(&self.units, &mut m.n_units, &mut m.units, what)?;
+        m.activation_out = self.activation_out.code();
+        Ok(())
+    }
+}
+
+fn candle_adamw_beta1() -> f64 {
+    0.9
+}
+fn candle_adamw_beta2() -> f64 {
+    0.999
+}
+fn candle_adamw_eps() -> f64 {
+    1e-8
+}
+fn candle_adamw_weight_decay() -> f64 {
+    0.01
+}
+
+/// `border_candle_agent::opt::OptimizerConfig`: candle-nn's AdamW (defaults of `ParamsAdamW`) or candle-optimisers' Adam.
+#[derive(Debug, Clone, Deserialize, Serialize, PartialEq)]
+pub enum CandleOptimizerConfig {
+    AdamW {
+        lr: f64,
+        #[serde(default = "candle_adamw_beta1")]
+        beta1: f64,
+        #[serde(default = "candle_adamw_beta2")]
+        beta2: f64,
+        #[serde(default = "candle_adamw_eps")]
+        eps: f64,
+        #[serde(default = "candle_adamw_weight_decay")]
+        weight_decay: f64,
+    },
+    Adam {
+        lr: f64,
+    },
+}
+
+impl CandleOptimizerConfig {
+    pub fn lr(&self) -> f64 {
+        match self {
+            CandleOptimizerConfig::Adam { lr } => *lr,
+            CandleOptimizerConfig::AdamW { lr, .. } => *lr,
+        }
+    }
+
+    pub(crate) fn fill(&self, c: &mut ffi::bdr_adamw_config) {
+        match self {
+            CandleOptimizerConfig::Adam { .. } => c.opt_kind = ffi::BDR_OPT_ADAM,
+            CandleOptimizerConfig::AdamW { lr: _, beta1, beta2, eps, weight_decay } => {
+                c.opt_kind = ffi::BDR_OPT_ADAMW;
+                c.beta1 = *beta1;
+                c.beta2 = *beta2;
+                c.eps = *eps;
+                c.weight_decay = *weight_decay;
+                c.amsgrad = 0;
+            }
+        }
+    }
+}
+
+/// `iql::ValueConfig`.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct ValueConfig {
+    pub value_config: Option<CandleMlpConfig>,
+    pub opt_config: CandleOptimizerConfig,
+}
+
+impl Default for ValueConfig {
+    fn default() -> Self {
+        Self { value_config: None, opt_config: CandleOptimizerConfig::Adam { lr: 0.0003 } }
+    }
+}
+
+/// `util::critic::MultiCriticConfig` (defaults `util/critic.rs:35-43`).
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct MultiCriticConfig {
+    pub n_nets: usize,
+    pub q_config: Option<CandleMlpConfig>,
+    pub opt_config: CandleOptimizerConfig,
+    pub tau: f64,
+}
+
+impl Default for MultiCriticConfig {
+    fn default() -> Self {
+        Self { n_nets: 2, q_config: None, opt_config: CandleOptimizerConfig::Adam { lr: 0.0003 }, tau: 0.005 }
+    }
+}
+
+/// `util::actor::ActionLimit`.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub enum ActionLimit {
+    Tanh { action_scale: f32 },
+    Clamp { action_min: f32, action_max: f32 },
+}
+
+/// `util::actor::GaussianActorConfig` (defaults `util/actor.rs:44-55`).  `policy_config` is Mlp3's MlpConfig.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct GaussianActorConfig {
+    pub policy_config: Option<CandleMlpConfig>,
+    pub opt_config: CandleOptimizerConfig,
+    pub min_log_std: f32,
+    pub max_log_std: f32,
+    pub action_limit: ActionLimit,
+}
+
+impl Default for GaussianActorConfig {
+    fn default() -> Self {
+        Self {
+            policy_config: None,
+            opt_config: CandleOptimizerConfig::Adam { lr: 0.0003 },
+            min_log_std: -20.0,
+            max_log_std: 2.0,
+            action_limit: ActionLimit::Clamp { action_min: -1.0, action_max: 1.0 },
+        }
+    }
+}
+
+/// `iql::IqlConfig<Q, P, V>` (`iql/config.rs:22-80`, defaults `:109-125`).  `seed` is not a reference field: it seeds the library's
+/// parameter initialiser and the device noise stream of `Policy::sample`.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct IqlConfig {
+    pub value_config: ValueConfig,
+    pub critic_config: MultiCriticConfig,
+    pub actor_config: GaussianActorConfig,
+    pub gamma: f32,
+    pub tau_iql: f64,
+    pub inv_lambda: f64,
+    pub n_updates_per_opt: usize,
+    pub batch_size: usize,
+    pub adv_softmax: bool,
+    pub critic_loss: CriticLoss,
+    pub exp_adv_max: f64,
+    #[serde(default)]
+    pub train: bool,
+    #[serde(default)]
+    pub seed: Option<i64>,
+    pub device: Option<Device>,
+}
+
+impl Default for IqlConfig {
+    fn default() -> Self {
+        Self {
+            value_config: Default::default(),
+            critic_config: Default::default(),
+            actor_config: Default::default(),
+            gamma: 0.99,
+            tau_iql: 0.7,
+            inv_lambda: 10.0,
+            n_updates_per_opt: 1,
+            batch_size: 1,
+            adv_softmax: false,
+            critic_loss: CriticLoss::Mse,
+            exp_adv_max: 100.0,
+            train: false,
+            seed: None,
+            device: None,
+        }
+    }
+}
+
+impl IqlConfig {
+    setter!(value_config, ValueConfig);
+    setter!(critic_config, MultiCriticConfig);
+    setter!(actor_config, GaussianActorConfig);
+    setter!(gamma, f32);
+    setter!(tau_iql, f64);
+    setter!(n_updates_per_opt, usize);
+    setter!(batch_size, usize);
+    setter!(adv_softmax, bool);
+    setter!(critic_loss, CriticLoss);
+    setter!(exp_adv_max, f64);
+    yaml_io!();
+
+    /// `IqlConfig::lambda`: inv_lambda = 1 / lambda.
+    pub fn lambda(mut self, v: f64) -> Self {
+        self.inv_lambda = 1.0 / v;
+        self
+    }
+
+    pub fn seed(mut self, v: i64) -> Self {
+        self.seed = Some(v);
+        self
+    }
+
+    pub fn device(mut self, device: Device) -> Self {
+        self.device = Some(device);
+        self
+    }
+
+    pub(crate) fn to_c(&self) -> Result<ffi::bdr_iql_config> {
+        let mut c: ffi::bdr_iql_config = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_iql_config_default(&mut c) };
+        let v = self.value_config.value_config.as_ref().ok_or_else(|| anyhow!("value_config is not set."))?;
+        let p = self.actor_config.policy_config.as_ref().ok_or_else(|| anyhow!("policy_config is not set."))?;
+        let q = self.critic_config.q_config.as_ref().ok_or_else(|| anyhow!("q_config is not set."))?;
+        c.obs_dim = p.in_dim as i32;
+        c.act_dim = p.out_dim as i32;
+        if v.in_dim != p.in_dim || v.out_dim != 1 {
+            return Err(anyhow!("value_config must map obs_dim = {} inputs to 1 output", p.in_dim));
+        }
+        if q.in_dim != p.in_dim + p.out_dim || q.out_dim != 1 {
+            return Err(anyhow!("critic q_config must map obs_dim + act_dim = {} inputs to 1 output", p.in_dim + p.out_dim));
+        }
+        v.fill(&mut c.value, "value_config")?;
+        p.fill(&mut c.actor, "policy_config")?;
+        q.fill(&mut c.critic, "q_config")?;
+        c.n_critics = self.critic_config.n_nets as i32;
+        c.critic_tau = self.critic_config.tau;
+        c.lr_value = self.value_config.opt_config.lr();
+        c.lr_actor = self.actor_config.opt_config.lr();
+        c.lr_critic = self.critic_config.opt_config.lr();
+        self.value_config.opt_config.fill(&mut c.opt_value);
+        self.actor_config.opt_config.fill(&mut c.opt_actor);
+        self.critic_config.opt_config.fill(&mut c.opt_critic);
+        c.min_log_std = self.actor_config.min_log_std as f64;
+        c.max_log_std = self.actor_config.max_log_std as f64;
+        match self.actor_config.action_limit {
+            ActionLimit::Clamp { action_min, action_max } => {
+                c.action_limit = ffi::BDR_ACTION_LIMIT_CLAMP;
+                c.action_min = action_min as f64;
+                c.action_max = action_max as f64;
+            }
+            ActionLimit::Tanh { action_scale } => {
+                c.action_limit = ffi::BDR_ACTION_LIMIT_TANH;
+                c.action_scale = action_scale as f64;
+            }
+        }
+        c.gamma = self.gamma as f64;
+        c.tau_iql = self.tau_iql;
+        c.inv_lambda = self.inv_lambda;
+        c.exp_adv_max = self.exp_adv_max;
+        c.adv_softmax = self.adv_softmax as i32;
+        c.critic_loss = self.critic_loss.code();
+        c.n_updates_per_opt = self.n_updates_per_opt as u64;
+        c.batch_size = self.batch_size as u64;
+        c.train = self.train as i32;
+        c.seed = self.seed.unwrap_or(0) as u64;
+        c.device = Device::ordinal(&self.device, "IQL");
+        Ok(c)
+    }
+}

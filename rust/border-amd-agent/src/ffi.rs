@@ -25,6 +25,12 @@ pub const BDR_OPT_ADAM: i32 = 0;
 pub const BDR_OPT_ADAMW: i32 = 1;
 pub const BDR_ARITH_BF16X3_6: i32 = 0;
 pub const BDR_ARITH_F32_EXACT: i32 = 1;
+pub const BDR_ACTIVATION_NONE: i32 = 0;
+pub const BDR_ACTIVATION_RELU: i32 = 1;
+pub const BDR_ACTIVATION_TANH: i32 = 2;
+pub const BDR_ACTIVATION_SIGMOID: i32 = 3;
+pub const BDR_ACTION_LIMIT_CLAMP: i32 = 0;
+pub const BDR_ACTION_LIMIT_TANH: i32 = 1;
 pub const BDR_MAX_UNITS: usize = 8;
 pub const BDR_EXPLORER_SOFTMAX: i32 = 0;
 pub const BDR_EXPLORER_EPS_GREEDY: i32 = 1;
@@ -423,6 +429,51 @@ pub struct bdr_sac_config {
     pub opt_critic: bdr_adamw_config,
 }
 
+/// border-candle-agent's MlpConfig (mlp/config.rs:6-11) without in/out dims
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bdr_mlp_config {
+    pub n_units: i32,
+    pub units: [i32; 8],
+    pub activation_out: i32,
+}
+
+/// IqlConfig (iql/config.rs:109-125) + ValueConfig, MultiCriticConfig, GaussianActorConfig
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bdr_iql_config {
+    pub obs_dim: i32,
+    pub act_dim: i32,
+    pub value: bdr_mlp_config,
+    pub actor: bdr_mlp_config,
+    pub critic: bdr_mlp_config,
+    pub n_critics: i32,
+    pub critic_tau: f64,
+    pub lr_value: f64,
+    pub lr_actor: f64,
+    pub lr_critic: f64,
+    pub opt_value: bdr_adamw_config,
+    pub opt_actor: bdr_adamw_config,
+    pub opt_critic: bdr_adamw_config,
+    pub min_log_std: f64,
+    pub max_log_std: f64,
+    pub action_limit: i32,
+    pub action_min: f64,
+    pub action_max: f64,
+    pub action_scale: f64,
+    pub gamma: f64,
+    pub tau_iql: f64,
+    pub inv_lambda: f64,
+    pub exp_adv_max: f64,
+    pub adv_softmax: i32,
+    pub critic_loss: i32,
+    pub n_updates_per_opt: u64,
+    pub batch_size: u64,
+    pub train: i32,
+    pub device: i32,
+    pub seed: u64,
+}
+
 #[link(name = "border_amd")]
 extern "C" {
     pub fn bdr_last_error() -> *const c_char;
@@ -658,6 +709,24 @@ extern "C" {
     ) -> i32;
     pub fn bdr_sac_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
     pub fn bdr_sac_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
+
+    // ---- IQL (border-candle-agent/src/iql)
+    pub fn bdr_iql_config_default(cfg: *mut bdr_iql_config);
+    pub fn bdr_iql_create(cfg: *const bdr_iql_config, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_iql_update_on_batch(
+        a: *mut bdr_agent,
+        n: u64,
+        obs: *const f32,
+        act: *const f32,
+        next_obs: *const f32,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+        rec3: *mut f32,
+    ) -> i32;
+    pub fn bdr_iql_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
+    pub fn bdr_iql_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
+    pub fn bdr_iql_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
 
     // ---- multi-GPU parameter exchange (RCCL over xGMI)
     pub fn bdr_comm_get_unique_id(id: *mut u8) -> i32;

@@ -179,6 +179,13 @@ impl AgentHandle {
         Ok(stems.iter().map(|f| path.join(format!("{f}.{ext}"))).collect())
     }
 
+    /// `save_params` of an agent whose reference files are candle VarMaps (IQL): `<stem>.pt` (safetensors inside) by default.
+    pub(crate) fn save_params_candle(&self, path: &Path, stems: &[String]) -> Result<Vec<PathBuf>> {
+        self.save_params(path, stems)?;
+        let ext = if self.safetensors { "safetensors" } else { "pt" };
+        Ok(stems.iter().map(|f| path.join(format!("{f}.{ext}"))).collect())
+    }
+
     /// A report kept from an earlier `opt` does not stop a checkpoint from loading (the parameters it concerned are being replaced):
     /// it is logged and dropped.
     pub(crate) fn load_params(&mut self, path: &Path) -> Result<()> {

@@ -10,6 +10,7 @@
 //!   `batch()` are those of `StdRng::seed_from_u64(seed)`, bit for bit.
 //! * [`AmdDqn`], [`AmdIqn`], [`AmdSac`] - `border-tch-agent/src/{dqn,iqn,sac}/base.rs`; configs keep the reference's field names
 //!   and serde layout ([`config`]), so the example YAML files load unchanged.
+//! * [`AmdIql`] - `border-candle-agent/src/iql/base.rs` (offline RL; [`IqlConfig`] deserialises the candle YAML names).
 //! * [`train_async`] - `border-async-trainer/src/util.rs:31-92` on one GPU (learner + actors + device mailbox), with the
 //!   optional cross-GPU exchange over RCCL ([`Comm`]).
 //!
@@ -24,6 +25,7 @@ pub mod dqn;
 pub mod error;
 pub mod ffi;
 mod handle;
+pub mod iql;
 pub mod iqn;
 pub mod replay;
 pub mod sac;
@@ -32,10 +34,12 @@ pub use async_trainer::{train_async, AmdAsyncTrainStat};
 pub use bytes::{ActFromRows, DiscreteAct, FloatAct, ObsRows, RowBatch};
 pub use comm::Comm;
 pub use config::{
+    ActionLimit, Activation, CandleMlpConfig, CandleOptimizerConfig, GaussianActorConfig, MultiCriticConfig, ValueConfig,
     ActorConfig, AtariCnnConfig, CriticConfig, CriticLoss, Device, DqnConfig, DqnExplorer, DqnModelConfig, EntCoefMode, EpsilonGreedy,
-    Arithmetic, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
+    Arithmetic, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
 };
 pub use dqn::AmdDqn;
+pub use iql::AmdIql;
 pub use iqn::AmdIqn;
 pub use replay::AmdReplayBuffer;
 pub use sac::AmdSac;
