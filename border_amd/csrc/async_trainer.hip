@@ -496,6 +496,7 @@ int32_t d_sample(void* a, uint64_t n, const void* obs, void* act)
     bdr_agent* ag = (bdr_agent*)a;
     if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample(ag, n, (const float*)obs, (float*)act);
     if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample(ag, n, (const float*)obs, (float*)act);   // util/actor.rs:226-241
+    if (ag && !strcmp(ag->kind(), "awac")) return bdr_awac_sample(ag, n, (const float*)obs, (float*)act);
     return bdr_agent_sample(ag, n, obs, (int64_t*)act, nullptr);
 }
 int32_t d_opt(void* a, void* b) { return bdr_agent_opt((bdr_agent*)a, (bdr_replay*)b); }
@@ -520,6 +521,7 @@ int32_t d_sample_dev(void* a, uint64_t n, const void* obs_dev, uint64_t stride, 
     bdr_agent* ag = (bdr_agent*)a;
     if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample_device(ag, n, obs_dev, stride, (float*)act);
     if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample_device(ag, n, obs_dev, stride, (float*)act);
+    if (ag && !strcmp(ag->kind(), "awac")) return bdr_awac_sample_device(ag, n, obs_dev, stride, (float*)act);
     return bdr_agent_sample_device(ag, n, obs_dev, stride, (int64_t*)act, nullptr);
 }
 }  // namespace

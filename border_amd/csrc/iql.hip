@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "candle_actor.hpp"
 #include "dense.hpp"
 
 using namespace bdr;
@@ -19,68 +20,11 @@ int32_t bdr_iql_sample(bdr_agent* base, uint64_t n, const float* obs, float* act
 
 namespace {
 
-// counter-based N(0,1) of the agent's noise stream (the same generator as SAC's: splitmix64 hash -> Box-Muller)
-__device__ __forceinline__ float iql_randn_at(uint64_t seed, uint64_t counter, size_t i)
-{
-    uint64_t x = (seed + 0x9E3779B97F4A7C15ull) ^ ((counter + i + 1) * 0xBF58476D1CE4E5B9ull);
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    const float u1 = ((float)(x >> 40) + 1.0f) * (1.0f / 16777217.0f);
-    const float u2 = (float)((x >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
-
 __global__ void k_iql_randn(float* __restrict__ out, size_t n, uint64_t seed, uint64_t counter)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    out[i] = iql_randn_at(seed, counter, i);
-}
-
-// ---- fixed-order batch sums (one 1024-thread workgroup) ----------------------------------------------------------------------
-__device__ __forceinline__ float iql_butterfly32(float v)
-{
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-// sum over b < B of value(b): rows in blocks of 32, each block's butterfly, the partials added in block order
-template <class F>
-__device__ __forceinline__ float iql_row_sum(int B, F&& value, float* red32)
-{
-    float total = 0.f;
-    for (int base = 0; base < B; base += 1024) {
-        const int b = base + (int)threadIdx.x;
-        const float part = iql_butterfly32(b < B ? value(b) : 0.f);
-        if ((threadIdx.x & 31) == 0) red32[threadIdx.x >> 5] = part;
-        __syncthreads();
-        const int nb = min(32, (B - base + 31) / 32);
-        for (int k = 0; k < nb; ++k) total += red32[k];
-        __syncthreads();
-    }
-    return total;
-}
-template <class F>
-__device__ __forceinline__ float iql_row_max(int B, F&& value, float* red32)
-{
-    float m = -INFINITY;
-    for (int base = 0; base < B; base += 1024) {
-        const int b = base + (int)threadIdx.x;
-        float v = b < B ? value(b) : -INFINITY;
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-        if ((threadIdx.x & 31) == 0) red32[threadIdx.x >> 5] = v;
-        __syncthreads();
-        const int nb = min(32, (B - base + 31) / 32);
-        for (int k = 0; k < nb; ++k) m = fmaxf(m, red32[k]);
-        __syncthreads();
-    }
-    return m;
-}
-__device__ __forceinline__ float iql_acc(float base, float s, float scale)   // base + s * scale, rounded step by step
-{
-#pragma clang fp contract(off)
-    const float t = s * scale;
-    return base + t;
+    out[i] = candle::randn_at(seed, counter, i);
 }
 
 // obs / next_obs / act rows -> the zero-padded inputs of the value + actor ([B][Kp], obs and next_obs) and of the critics ([B][Kq], obs | act)
@@ -116,7 +60,7 @@ __global__ __launch_bounds__(1024) void k_iql_value_loss(IqlValueArgs p)
 {
     __shared__ float red[32];
     const float invB = 1.0f / (float)p.B;
-    const float s = iql_row_sum(p.B, [&](int b) {
+    const float s = candle::row_sum(p.B, [&](int b) {
 #pragma clang fp contract(off)
         float qm = p.qt[0][(size_t)b * p.ldq];
         for (int i = 1; i < p.NC; ++i) qm = fminf(qm, p.qt[i][(size_t)b * p.ldq]);
@@ -132,7 +76,7 @@ __global__ __launch_bounds__(1024) void k_iql_value_loss(IqlValueArgs p)
         p.q_min[b] = qm; p.v_out[b] = v; p.u_out[b] = u;
         return l;
     }, red);
-    if (threadIdx.x == 0) p.loss[0] = iql_acc(p.accumulate ? p.loss[0] : 0.f, s, invB);
+    if (threadIdx.x == 0) p.loss[0] = candle::acc(p.accumulate ? p.loss[0] : 0.f, s, invB);
 }
 
 // (b) update_critic (iql/base.rs:88-121): tgt = r + gamma_not_done * V'(next_obs), gamma_not_done = (1 - (term | trunc)) * gamma in f32
@@ -159,7 +103,7 @@ __global__ __launch_bounds__(1024) void k_iql_critic_loss(IqlCriticArgs p)
     const float scale = 1.0f / ((float)p.B * (float)p.NC);
     float total = p.accumulate ? p.loss[0] : 0.f;
     for (int i = 0; i < p.NC; ++i) {   // critic by critic; a thread reads back only the targets it wrote itself
-        const float si = iql_row_sum(p.B, [&](int b) {
+        const float si = candle::row_sum(p.B, [&](int b) {
 #pragma clang fp contract(off)
             const float q = p.q[i][(size_t)b * p.ldq];
             const float d = q - p.tgt[b];
@@ -171,7 +115,7 @@ __global__ __launch_bounds__(1024) void k_iql_critic_loss(IqlCriticArgs p)
             p.dq[i][(size_t)b * p.ldq] = gq;
             return l;
         }, red);
-        total = iql_acc(total, si, scale);
+        total = candle::acc(total, si, scale);
     }
     if (threadIdx.x == 0) p.loss[0] = total;
 }
@@ -213,12 +157,12 @@ __global__ __launch_bounds__(1024) void k_iql_actor_loss(IqlActorArgs p)
         p.w[b] = p.softmax ? z : fminf(fmaxf(expf(z), 0.0f), p.exp_adv_max);
     }
     if (p.softmax) {   // softmax(z, 0): exp(z - max) / sum(exp(z - max))
-        const float mx = iql_row_max(p.B, [&](int b) { return p.w[b]; }, red);
-        const float s = iql_row_sum(p.B, [&](int b) { const float e = expf(p.w[b] - mx); p.w[b] = e; return e; }, red);
+        const float mx = candle::row_max(p.B, [&](int b) { return p.w[b]; }, red);
+        const float s = candle::row_sum(p.B, [&](int b) { const float e = expf(p.w[b] - mx); p.w[b] = e; return e; }, red);
         for (int b = threadIdx.x; b < p.B; b += 1024) p.w[b] = p.w[b] / s;
     }
     // per row: logp and dL/dmean
-    const float s_wl = iql_row_sum(p.B, [&](int b) {
+    const float s_wl = candle::row_sum(p.B, [&](int b) {
 #pragma clang fp contract(off)
         const float wb = p.w[b];
         const float gl = -wb * invB;   // dL/dlogp_b
@@ -242,14 +186,14 @@ __global__ __launch_bounds__(1024) void k_iql_actor_loss(IqlActorArgs p)
         p.logp[b] = l;
         return wb * l;
     }, red);
-    if (threadIdx.x == 0) p.loss[0] = iql_acc(p.accumulate ? p.loss[0] : 0.f, -s_wl, invB);
+    if (threadIdx.x == 0) p.loss[0] = candle::acc(p.accumulate ? p.loss[0] : 0.f, -s_wl, invB);
     // dL/dhead2_j: one fixed-order batch sum per action dimension
     for (int j = 0; j < p.A; ++j) {
         const float h = p.head2[j];
         const float ls = fminf(fmaxf(h, p.lo), p.hi);
         const float sd = expf(ls);
         const float var = sd * sd;
-        const float s = iql_row_sum(p.B, [&](int b) {
+        const float s = candle::row_sum(p.B, [&](int b) {
 #pragma clang fp contract(off)
             const float d = iql_x(p, p.act[(size_t)b * p.A + j]) - p.mean[(size_t)b * p.ldm + j];
             const float r = (d * d) / var - 1.0f;
@@ -275,7 +219,7 @@ __global__ __launch_bounds__(256) void k_iql_sample(IqlSampleArgs p)
     float a = p.mean[(size_t)b * p.ldm + j];
     if (p.train) {
         const float sd = expf(fminf(fmaxf(p.head2[j], p.lo), p.hi));
-        const float e = sd * iql_randn_at(p.seed, p.counter, (size_t)t);
+        const float e = sd * candle::randn_at(p.seed, p.counter, (size_t)t);
         a = e + a;
     }
     if (p.tanh_limit) { const float th = tanhf(a); a = p.scale * th; }

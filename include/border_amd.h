@@ -296,7 +296,9 @@ BDR_API int32_t bdr_agent_opt_with_scalars(bdr_agent* a, bdr_replay* buffer, flo
  *        variables' order (util.rs:64-80) - and "ratio_best_act" = n_samples_best_act / n_samples_act, which resets both
  *        counters (dqn/base.rs:316-342);
  *   IQN  "loss_critic" (iqn/base.rs:190);   SAC  "loss_critic", "loss_actor", "ent_coef" (sac/base.rs:187-196);
- *   IQL  "loss_value", "loss_critic", "loss_actor", each averaged over n_updates_per_opt (iql/base.rs:177-185). */
+ *   IQL  "loss_value", "loss_critic", "loss_actor", each averaged over n_updates_per_opt (iql/base.rs:177-185);
+ *   AWAC "loss_critic", "loss_actor", "q_tgt_abs_mean", "adv_mean", "adv_abs_mean" averaged over n_updates_per_opt, then
+ *        "logp_mean", "reward_mean", "next_q_mean" summed over them (awac/base.rs:197-212). */
 BDR_API int32_t bdr_agent_record_keys(bdr_agent* a, char* names_out, uint64_t names_cap, int32_t* n_keys);
 
 /* Test helper: n draws of the agent's own device noise stream copied to the host - SAC: the N(0,1) draws of action_logp
@@ -411,7 +413,8 @@ BDR_API int32_t bdr_agent_arena_release(bdr_agent* a, int32_t which);
  * reference's file names.  IQL (iql/base.rs:292-309): `actor.pt`, `critic.pt`, `critic.tgt.pt`, `value.pt` - candle VarMaps, which
  * are safetensors whatever the extension, so BDR_CKPT_TCH writes safetensors there and BDR_CKPT_SAFETENSORS `<stem>.safetensors`;
  * critic.tgt.pt holds the ONLINE critics and loading reads both critic files into the online critics, leaving the targets
- * untouched (util/critic.rs:272-298).  The container follows the file name exactly as tch's VarStore::{save,load} do:
+ * untouched (util/critic.rs:272-298).  AWAC (awac/base.rs:311-333): `actor.pt`, `critic.pt`, `critic.tgt.pt`, with the same
+ * containers and both critic.tgt quirks.  The container follows the file name exactly as tch's VarStore::{save,load} do:
  *   BDR_CKPT_TCH          "<stem>.pt.tch": the libtorch named-tensor archive (TorchScript module zip) that tch writes
  *                         through torch-sys at_save_multi and reads with torch::jit::load (default, = the reference);
  *   BDR_CKPT_SAFETENSORS  "<stem>.safetensors".
@@ -784,6 +787,70 @@ BDR_API int32_t bdr_iql_sample(bdr_agent* a, uint64_t n, const float* obs, float
 BDR_API int32_t bdr_iql_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
 
 /* ------------------------------------------------------------------------------------------
+ * AWAC agent  (border-candle-agent/src/awac/{base.rs,config.rs}; offline and online RL)
+ * Critics = MultiCritic of Mlp on cat(obs, act) (util/critic.rs), actor = GaussianActor (util/actor.rs) over Mlp3, as for IQL;
+ * there is no value network.
+ * ---------------------------------------------------------------------------------------- */
+/* AwacConfig (awac/config.rs:120-141) with its MultiCriticConfig (util/critic.rs:35-43) and GaussianActorConfig (util/actor.rs:44-55).
+ * AwacConfig's tau, min_lstd, max_lstd, reward_scale, n_critics and seed are not read by the reference agent (awac/base.rs:249-280)
+ * and have no field here: the soft-update rate is MultiCriticConfig.tau (critic_tau), the critic count MultiCriticConfig.n_nets
+ * (n_critics) and the log-std bounds GaussianActorConfig's (min_log_std, max_log_std).  amsgrad is rejected, as for IQL.
+ * batch_size must be >= 2: at one row the reference's squeeze(D::Minus1) (awac/base.rs:88; util/critic.rs:197-218) turns the
+ * critic minima and the TD target into scalars while each prediction keeps shape [1], and candle's same-shape tensor ops reject
+ * that pair, so the reference cannot run a one-row batch (BDR_ERR_INVALID). */
+typedef struct {
+    int32_t obs_dim, act_dim;
+    bdr_mlp_config actor;         /* GaussianActorConfig.policy_config (Mlp3) */
+    bdr_mlp_config critic;        /* MultiCriticConfig.q_config               */
+    int32_t n_critics;            /* MultiCriticConfig.n_nets (default 2)     */
+    double critic_tau;            /* MultiCriticConfig.tau (default 0.005)    */
+    double lr_actor, lr_critic;
+    bdr_adamw_config opt_actor, opt_critic;
+    double min_log_std, max_log_std;  /* GaussianActorConfig (-20, 2)     */
+    int32_t action_limit;             /* BDR_ACTION_LIMIT_* (default Clamp{-1, 1}) */
+    double action_min, action_max, action_scale;
+    double gamma;                 /* 0.99 (f32 in the reference) */
+    double inv_lambda;            /* 10 (= 1 / lambda)            */
+    double exp_adv_max;           /* 100                          */
+    int32_t adv_softmax;          /* false                        */
+    int32_t critic_loss;          /* BDR_LOSS_* (Mse)             */
+    uint64_t n_updates_per_opt, batch_size;   /* 1, 1 (batch_size 1 is rejected, see above) */
+    int32_t train;                /* false: the agent is built in eval mode (awac/base.rs:272) */
+    int32_t device;               /* -1: none given */
+    uint64_t seed;                /* the library's parameter initialiser and the device noise stream of Policy::sample */
+} bdr_awac_config;
+BDR_API void bdr_awac_config_default(bdr_awac_config* cfg);                    /* awac/config.rs:120-141 */
+BDR_API int32_t bdr_awac_create(const bdr_awac_config* cfg, bdr_agent** out);  /* awac/base.rs:249-280 (Configurable::build) */
+/* One Awac::opt_ loop iteration (awac/base.rs:170-215) on a host minibatch: update_actor (:127-168), then update_critic (:66-125) on
+ * the same batch with next_act drawn from the UPDATED actor, then the soft update of every target critic.  The advantage uses the
+ * ONLINE critics (qvals_min, util/critic.rs:197-202); the critic loss is the SUM over critics of mse / smooth_l1; gamma_not_done
+ * counts is_truncated (util.rs:235-255).
+ * Noise: in train mode act_ = mean + std z_pi and next_act = mean' + std' z_next.  z_pi / z_next: n * act_dim host N(0,1) draws,
+ * or NULL for the agent's device stream (the one bdr_agent_draw_noise reads); each NULL set takes n * act_dim draws, z_pi's first,
+ * row-major [n][act_dim].  Host draws take nothing from the stream.  Eval mode uses the means and no draws.
+ * rec8: loss_critic, loss_actor, q_tgt_abs_mean, adv_mean, adv_abs_mean, logp_mean, reward_mean, next_q_mean of this update.
+ * Parameter models for bdr_agent_{get,set}_params / param_count_of: 0 actor (mlp.ln{k}.weight/bias ..., then head2), 1+i critic_i,
+ * 1+n_critics+i critic_tgt_i; +100 gradient, +200 exp_avg, +300 exp_avg_sq.  SyncModel ships model 0.
+ * Record of bdr_agent_opt_with_scalars: the 8 keys above; the first five averaged over n_updates_per_opt, logp_mean, reward_mean
+ * and next_q_mean summed over the updates, as the reference does (awac/base.rs:197-212). */
+BDR_API int32_t bdr_awac_update_on_batch(bdr_agent* a, uint64_t n, const float* obs, const float* act, const float* next_obs,
+                                         const float* reward, const int8_t* is_terminated, const int8_t* is_truncated,
+                                         const float* z_pi, const float* z_next, float* rec8);
+/* Parity probes: intermediates of the LAST AWAC update, to the host.  what:
+ *   0 q_data_min [B]    min_i Q_i(obs, act) (:134-136)           1 q_pi_min [B]   min_i Q_i(obs, act_) (:137)
+ *   2 adv [B]           q - v (:138)                             3 w [B]          the advantage weights (:141-148)
+ *   4 logp [B]          log pi(act | obs) (:153)                 5 act_ [B][act_dim]    actor.sample(obs) (:133)
+ *   6 next_act [B][act_dim]  actor.sample(next_obs) of the updated actor (:85)
+ *   7 next_q [B]        min_i Qtgt_i(next_obs, next_act) (:86-88)  8 tgt [B]      r + gamma_not_done * next_q (:88)
+ *   9 q_pred [n_critics][B]  Q_i(obs, act) (:76) */
+BDR_API int32_t bdr_awac_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* Policy::sample (util/actor.rs:226-241): train: mean + std * N(0,1) (the agent's device noise stream, bdr_agent_draw_noise),
+ * eval: mean; then clamp(action_min, action_max) or action_scale * tanh. */
+BDR_API int32_t bdr_awac_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out);
+/* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
+BDR_API int32_t bdr_awac_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU parameter exchange (replaces the learner->actors NamedTensors channel of
  * border-async-trainer/src/async_trainer/base.rs:268-272 with RCCL over xGMI).
  * ---------------------------------------------------------------------------------------- */
@@ -798,7 +865,7 @@ BDR_API int32_t bdr_comm_agree(bdr_comm* c, int32_t local_ok, int32_t* all_ok);
 /* params <- mean over ranks (ncclAllReduce sum on the flat arena, then 1/nranks), on the
  * agent's stream; which as in bdr_agent_get_params (0 qnet, 1 qnet_tgt, 2/3 Adam moments). */
 BDR_API int32_t bdr_agent_allreduce_params(bdr_agent* a, bdr_comm* c, int32_t which);
-/* Synchronous data-parallel mode for DQN agents (an IQL agent returns BDR_ERR_INVALID): from now on every Agent::opt of `a` runs backward, all-reduces the gradient
+/* Synchronous data-parallel mode for DQN agents (an IQL or AWAC agent returns BDR_ERR_INVALID): from now on every Agent::opt of `a` runs backward, all-reduces the gradient
  * arena over `c` (ncclAllReduce sum, then 1/nranks, on the agent's stream) and then takes the optimizer step, so the ranks
  * stay bit-for-bit in lock step and N x batch B/N equals one step on batch B.  c == NULL: back to independent steps. */
 BDR_API int32_t bdr_agent_set_grad_comm(bdr_agent* a, bdr_comm* c);

@@ -1111,3 +1111,131 @@ impl IqlConfig {
         Ok(c)
     }
 }
+
+/// `awac::AwacConfig<Q, P>` (`awac/config.rs:20-73`, defaults `:120-141`), with the reference's field names.  `tau`, `min_lstd`,
+/// `max_lstd`, `reward_scale`, `n_critics` and `seed` are deserialised and ignored, as the reference agent ignores them
+/// (`awac/base.rs:249-280`): the soft-update rate is `critic_config.tau`, the critic count `critic_config.n_nets`, the log-std
+/// bounds `actor_config`'s.  `engine_seed` is not a reference field: it seeds the library's parameter initialiser and the device
+/// noise stream of `Policy::sample`.  `batch_size` must be >= 2 (`bdr_awac_create` says why).
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct AwacConfig {
+    pub actor_config: GaussianActorConfig,
+    pub critic_config: MultiCriticConfig,
+    pub gamma: f64,
+    pub inv_lambda: f64,
+    pub tau: f64,
+    pub min_lstd: f64,
+    pub max_lstd: f64,
+    pub n_updates_per_opt: usize,
+    pub batch_size: usize,
+    pub critic_loss: CriticLoss,
+    pub reward_scale: f32,
+    pub n_critics: usize,
+    pub exp_adv_max: f64,
+    pub seed: Option<i64>,
+    pub device: Option<Device>,
+    pub adv_softmax: bool,
+    #[serde(default)]
+    pub train: bool,
+    #[serde(default)]
+    pub engine_seed: u64,
+}
+
+impl Default for AwacConfig {
+    fn default() -> Self {
+        Self {
+            actor_config: Default::default(),
+            critic_config: Default::default(),
+            gamma: 0.99,
+            inv_lambda: 10.0,
+            tau: 0.005,
+            min_lstd: -20.0,
+            max_lstd: 2.0,
+            n_updates_per_opt: 1,
+            batch_size: 1,
+            critic_loss: CriticLoss::Mse,
+            reward_scale: 1.0,
+            n_critics: 2,
+            exp_adv_max: 100.0,
+            seed: None,
+            device: None,
+            adv_softmax: false,
+            train: false,
+            engine_seed: 0,
+        }
+    }
+}
+
+impl AwacConfig {
+    setter!(actor_config, GaussianActorConfig);
+    setter!(critic_config, MultiCriticConfig);
+    setter!(n_updates_per_opt, usize);
+    setter!(batch_size, usize);
+    setter!(tau, f64);
+    setter!(reward_scale, f32);
+    setter!(critic_loss, CriticLoss);
+    setter!(exp_adv_max, f64);
+    setter!(adv_softmax, bool);
+    yaml_io!();
+
+    /// `AwacConfig::lambda`: inv_lambda = 1 / lambda.
+    pub fn lambda(mut self, v: f64) -> Self {
+        self.inv_lambda = 1.0 / v;
+        self
+    }
+
+    /// `AwacConfig::discount_factor`: sets `gamma`.
+    pub fn discount_factor(mut self, v: f64) -> Self {
+        self.gamma = v;
+        self
+    }
+
+    pub fn device(mut self, device: Device) -> Self {
+        self.device = Some(device);
+        self
+    }
+
+    pub(crate) fn to_c(&self) -> Result<ffi::bdr_awac_config> {
+        let mut c: ffi::bdr_awac_config = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_awac_config_default(&mut c) };
+        let p = self.actor_config.policy_config.as_ref().ok_or_else(|| anyhow!("policy_config is not set."))?;
+        let q = self.critic_config.q_config.as_ref().ok_or_else(|| anyhow!("q_config is not set."))?;
+        c.obs_dim = p.in_dim as i32;
+        c.act_dim = p.out_dim as i32;
+        if q.in_dim != p.in_dim + p.out_dim || q.out_dim != 1 {
+            return Err(anyhow!("critic q_config must map obs_dim + act_dim = {} inputs to 1 output", p.in_dim + p.out_dim));
+        }
+        p.fill(&mut c.actor, "policy_config")?;
+        q.fill(&mut c.critic, "q_config")?;
+        c.n_critics = self.critic_config.n_nets as i32;
+        c.critic_tau = self.critic_config.tau;
+        c.lr_actor = self.actor_config.opt_config.lr();
+        c.lr_critic = self.critic_config.opt_config.lr();
+        self.actor_config.opt_config.fill(&mut c.opt_actor);
+        self.critic_config.opt_config.fill(&mut c.opt_critic);
+        c.min_log_std = self.actor_config.min_log_std as f64;
+        c.max_log_std = self.actor_config.max_log_std as f64;
+        match self.actor_config.action_limit {
+            ActionLimit::Clamp { action_min, action_max } => {
+                c.action_limit = ffi::BDR_ACTION_LIMIT_CLAMP;
+                c.action_min = action_min as f64;
+                c.action_max = action_max as f64;
+            }
+            ActionLimit::Tanh { action_scale } => {
+                c.action_limit = ffi::BDR_ACTION_LIMIT_TANH;
+                c.action_scale = action_scale as f64;
+            }
+        }
+        c.gamma = self.gamma;
+        c.inv_lambda = self.inv_lambda;
+        c.exp_adv_max = self.exp_adv_max;
+        c.adv_softmax = self.adv_softmax as i32;
+        c.critic_loss = self.critic_loss.code();
+        c.n_updates_per_opt = self.n_updates_per_opt as u64;
+        c.batch_size = self.batch_size as u64;
+        c.train = self.train as i32;
+        c.seed = self.engine_seed;
+        c.device = Device::ordinal(&self.device, "AWAC");
+        Ok(c)
+    }
+}

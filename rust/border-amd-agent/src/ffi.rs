@@ -474,6 +474,38 @@ pub struct bdr_iql_config {
     pub seed: u64,
 }
 
+/// AwacConfig (awac/config.rs:120-141) + MultiCriticConfig, GaussianActorConfig
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bdr_awac_config {
+    pub obs_dim: i32,
+    pub act_dim: i32,
+    pub actor: bdr_mlp_config,
+    pub critic: bdr_mlp_config,
+    pub n_critics: i32,
+    pub critic_tau: f64,
+    pub lr_actor: f64,
+    pub lr_critic: f64,
+    pub opt_actor: bdr_adamw_config,
+    pub opt_critic: bdr_adamw_config,
+    pub min_log_std: f64,
+    pub max_log_std: f64,
+    pub action_limit: i32,
+    pub action_min: f64,
+    pub action_max: f64,
+    pub action_scale: f64,
+    pub gamma: f64,
+    pub inv_lambda: f64,
+    pub exp_adv_max: f64,
+    pub adv_softmax: i32,
+    pub critic_loss: i32,
+    pub n_updates_per_opt: u64,
+    pub batch_size: u64,
+    pub train: i32,
+    pub device: i32,
+    pub seed: u64,
+}
+
 #[link(name = "border_amd")]
 extern "C" {
     pub fn bdr_last_error() -> *const c_char;
@@ -727,6 +759,26 @@ extern "C" {
     pub fn bdr_iql_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_iql_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
     pub fn bdr_iql_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
+
+    // ---- AWAC (border-candle-agent/src/awac)
+    pub fn bdr_awac_config_default(cfg: *mut bdr_awac_config);
+    pub fn bdr_awac_create(cfg: *const bdr_awac_config, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_awac_update_on_batch(
+        a: *mut bdr_agent,
+        n: u64,
+        obs: *const f32,
+        act: *const f32,
+        next_obs: *const f32,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+        z_pi: *const f32,
+        z_next: *const f32,
+        rec8: *mut f32,
+    ) -> i32;
+    pub fn bdr_awac_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
+    pub fn bdr_awac_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
+    pub fn bdr_awac_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
 
     // ---- multi-GPU parameter exchange (RCCL over xGMI)
     pub fn bdr_comm_get_unique_id(id: *mut u8) -> i32;

@@ -11,6 +11,7 @@
 //! * [`AmdDqn`], [`AmdIqn`], [`AmdSac`] - `border-tch-agent/src/{dqn,iqn,sac}/base.rs`; configs keep the reference's field names
 //!   and serde layout ([`config`]), so the example YAML files load unchanged.
 //! * [`AmdIql`] - `border-candle-agent/src/iql/base.rs` (offline RL; [`IqlConfig`] deserialises the candle YAML names).
+//! * [`AmdAwac`] - `border-candle-agent/src/awac/base.rs` (offline and online RL; [`AwacConfig`] likewise).
 //! * [`train_async`] - `border-async-trainer/src/util.rs:31-92` on one GPU (learner + actors + device mailbox), with the
 //!   optional cross-GPU exchange over RCCL ([`Comm`]).
 //!
@@ -18,6 +19,7 @@
 //! `type Agent_ = AmdDqn<Env, ObsBatch, ActBatch>; type ReplayBuffer_ = AmdReplayBuffer<ObsBatch, ActBatch>;`
 //! and keeps its `Trainer::build(config).train(env, step_proc, &mut agent, &mut buffer, ...)` call.
 pub mod async_trainer;
+pub mod awac;
 pub mod bytes;
 pub mod comm;
 pub mod config;
@@ -36,8 +38,9 @@ pub use comm::Comm;
 pub use config::{
     ActionLimit, Activation, CandleMlpConfig, CandleOptimizerConfig, GaussianActorConfig, MultiCriticConfig, ValueConfig,
     ActorConfig, AtariCnnConfig, CriticConfig, CriticLoss, Device, DqnConfig, DqnExplorer, DqnModelConfig, EntCoefMode, EpsilonGreedy,
-    Arithmetic, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
+    Arithmetic, AwacConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
 };
+pub use awac::AmdAwac;
 pub use dqn::AmdDqn;
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;
