@@ -5,21 +5,20 @@
                soft-update rate is critic_config.tau, the critic count critic_config.n_nets, the log-std bounds actor_config's.
   Awac         awac/base.rs (Agent, Policy::sample, SyncModel ships the actor)
 
-The model configs are IQL's: CandleMlpConfig, ActionLimit, GaussianActorConfig and MultiCriticConfig of border_amd.iql.
+The model configs are IQL's: CandleMlpConfig, ActionLimit, GaussianActorConfig and MultiCriticConfig of border_amd.iql, and so is
+CandleAgent, what the two agents' handles share.
 batch_size must be >= 2 (include/border_amd.h says why the reference cannot run a one-row batch).
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass, field
 from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from .iql import GaussianActorConfig, MultiCriticConfig
-from .replay import SimpleReplayBuffer
+from .iql import CandleAgent, GaussianActorConfig, MultiCriticConfig, _p
 
 RECORD_KEYS = ("loss_critic", "loss_actor", "q_tgt_abs_mean", "adv_mean", "adv_abs_mean", "logp_mean", "reward_mean", "next_q_mean")
 
@@ -69,79 +68,10 @@ class AwacConfig:
         return c
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class Awac:
-    def __init__(self, config: AwacConfig):
-        self.config = config
-        h = C.c_void_p()
-        c = config.to_c()
-        _lib.check(_lib.lib().bdr_awac_create(C.byref(c), C.byref(h)))
-        self._h = h
-
-    @classmethod
-    def build(cls, config: AwacConfig) -> "Awac":
-        return cls(config)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().bdr_agent_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def n_critics(self) -> int:
-        return self.config.critic_config.n_nets
-
-    # model ids (bdr_agent_get_params `which`)
-    def which(self, name: str, role: str = "param") -> int:
-        nc = self.n_critics
-        if name.startswith("critic_tgt_"):
-            i = 1 + nc + int(name[len("critic_tgt_"):])
-        elif name.startswith("critic_"):
-            i = 1 + int(name[len("critic_"):])
-        else:
-            i = {"actor": 0}[name]
-        return i + {"param": 0, "grad": 100, "exp_avg": 200, "exp_avg_sq": 300}[role]
-
-    WHICH = {"actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the actor == model 0
-
-    def arena_device_ptr(self, which="actor"):
-        ptr, n = C.c_void_p(), C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
-        return ptr.value, n.value
-
-    def train(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 1))
-
-    def eval(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 0))
-
-    def opt(self, buffer: SimpleReplayBuffer) -> None:
-        _lib.check(_lib.lib().bdr_agent_opt(self._h, buffer.handle))
-
-    def opt_with_record(self, buffer: SimpleReplayBuffer) -> dict:
-        from .dqn import opt_with_named_record
-        return opt_with_named_record(self._h, buffer)
-
-    def profile_enable(self, on: bool = True):
-        _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
-
-    def draw_noise(self, n: int) -> np.ndarray:
-        """n draws of the agent's device noise stream (bdr_agent_draw_noise): the N(0,1) numbers of Policy::sample in train mode."""
-        from .dqn import draw_noise
-        return draw_noise(self._h, n)
+class Awac(CandleAgent):
+    """awac/base.rs; checkpoints (awac/base.rs:311-320): actor, critic, critic.tgt."""
+    KIND = "awac"
+    CKPT_STEMS = ("actor", "critic", "critic.tgt")
 
     def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated, z_pi=None, z_next=None) -> dict:
         """One Awac::opt_ iteration.  z_pi / z_next: [n, act_dim] N(0,1) draws for act_ and next_act in train mode (None: the
@@ -167,61 +97,3 @@ class Awac:
         out = np.empty(shape, np.float32)
         _lib.check(_lib.lib().bdr_awac_probe(self._h, self.PROBES[what], _p(out), out.size))
         return out
-
-    def sample(self, obs) -> np.ndarray:
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        out = np.empty((obs.shape[0], self.config.act_dim), np.float32)
-        _lib.check(_lib.lib().bdr_awac_sample(self._h, obs.shape[0], _p(obs), _p(out)))
-        return out
-
-    def sample_device(self, obs_dev: int, n: int, row_stride: int) -> np.ndarray:
-        out = np.empty((n, self.config.act_dim), np.float32)
-        _lib.check(_lib.lib().bdr_awac_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(out)))
-        return out
-
-    def sync(self):
-        _lib.check(_lib.lib().bdr_agent_sync(self._h))
-
-    @property
-    def n_opts(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
-        return n.value
-
-    def param_count(self, name="actor") -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_param_count_of(self._h, self.which(name), C.byref(n)))
-        return n.value
-
-    def get_params(self, name="actor", role="param") -> np.ndarray:
-        out = np.empty(self.param_count(name), np.float32)
-        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.which(name, role), _p(out), out.size))
-        return out
-
-    def set_params(self, params, name="actor", role="param") -> None:
-        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
-        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.which(name, role), _p(p), p.size))
-
-    def model_info(self):
-        """SyncModel::model_info: the actor's parameters."""
-        return self.n_opts, self.get_params("actor")
-
-    def sync_model(self, model_info) -> None:
-        self.set_params(model_info, "actor")
-
-    def set_checkpoint_format(self, fmt: str) -> None:
-        """"tch" (default): the reference's `<stem>.pt` files (safetensors, as candle's VarMap writes them); "safetensors":
-        `<stem>.safetensors`."""
-        from .checkpoint import FORMATS
-        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
-        self._ckpt_ext = {"tch": ".pt", "safetensors": ".safetensors"}[fmt]
-
-    def save_params(self, path: str):
-        """awac/base.rs:311-320: actor, critic, critic.tgt (the ONLINE critics, util/critic.rs:272-285)."""
-        os.makedirs(path, exist_ok=True)
-        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
-        ext = getattr(self, "_ckpt_ext", ".pt")
-        return [os.path.join(path, stem + ext) for stem in ("actor", "critic", "critic.tgt")]
-
-    def load_params(self, path: str):
-        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))

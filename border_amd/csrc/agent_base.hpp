@@ -294,6 +294,9 @@ struct bdr_agent {
     virtual void record_keys(std::vector<std::string>& keys) = 0; // names of those scalars, in order
     // n draws of the agent's own device noise stream (SAC: N(0,1) of action_logp; IQN: U[0,1) percent points), advancing it
     virtual int32_t noise(float*, size_t) { return ::bdr::fail(BDR_ERR_INVALID, "this agent draws no device noise"); }
+    // Policy::sample with f32 action rows, where the handle itself implements it (the candle-family agents: CandleAgent,
+    // candle_actor.hpp).  obs: host rows, or device rows `stride` bytes apart when on_device.  false: not such an agent, nothing done.
+    virtual bool sample_f32(uint64_t, const void*, bool /*on_device*/, uint64_t /*stride*/, float*, int32_t* /*status*/) { return false; }
     virtual uint64_t param_count(int which) = 0;                  // reference-layout element count
     virtual int32_t get_params(int which, float* out, uint64_t n) = 0;
     virtual int32_t set_params(int which, const float* in, uint64_t n) = 0;
@@ -305,6 +308,27 @@ struct bdr_agent {
 };
 
 namespace bdr {
+
+// Policy::sample of the handle's kind for the default function tables of the compiled loops (trainer.hip, async_trainer.hip):
+// discrete agents return i64 actions (dqn/base.rs:211-242, iqn/base.rs:204-228), SAC (sac/base.rs:215-225) and the candle-family
+// agents (util/actor.rs:226-241) f32 action rows
+inline int32_t default_sample(void* a, uint64_t n, const void* obs, void* act)
+{
+    bdr_agent* ag = (bdr_agent*)a;
+    int32_t st = BDR_OK;
+    if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample(ag, n, (const float*)obs, (float*)act);
+    if (ag && ag->sample_f32(n, obs, false, 0, (float*)act, &st)) return st;
+    return bdr_agent_sample(ag, n, obs, (int64_t*)act, nullptr);
+}
+// the same for device-resident observations (bdr_env_vtable::obs_on_device)
+inline int32_t default_sample_device(void* a, uint64_t n, const void* obs_dev, uint64_t stride, void* act)
+{
+    bdr_agent* ag = (bdr_agent*)a;
+    int32_t st = BDR_OK;
+    if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample_device(ag, n, obs_dev, stride, (float*)act);
+    if (ag && ag->sample_f32(n, obs_dev, true, stride, (float*)act, &st)) return st;
+    return bdr_agent_sample_device(ag, n, obs_dev, stride, (int64_t*)act, nullptr);
+}
 
 // TD loss of one row (dqn/base.rs:123-151).  Without importance weights: smooth_l1 / mse of (pred, tgt).
 // With weights (PER): td = |pred - tgt| (clipped to [cmin, cmax] when clip_td_err is set), x = w * td,

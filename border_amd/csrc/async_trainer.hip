@@ -489,16 +489,6 @@ int32_t bdr_async_train(const bdr_async_trainer_config* c, const bdr_learner_ops
 namespace {
 struct DefaultCtx { int32_t which; };
 int32_t d_set_train(void* a, int32_t on) { return bdr_agent_set_train((bdr_agent*)a, on); }
-// Policy::sample of the handle's kind: discrete agents return i64 actions (dqn/base.rs:211-242, iqn/base.rs:204-228), SAC f32 rows
-// (sac/base.rs:215-225)
-int32_t d_sample(void* a, uint64_t n, const void* obs, void* act)
-{
-    bdr_agent* ag = (bdr_agent*)a;
-    if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample(ag, n, (const float*)obs, (float*)act);
-    if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample(ag, n, (const float*)obs, (float*)act);   // util/actor.rs:226-241
-    if (ag && !strcmp(ag->kind(), "awac")) return bdr_awac_sample(ag, n, (const float*)obs, (float*)act);
-    return bdr_agent_sample(ag, n, obs, (int64_t*)act, nullptr);
-}
 int32_t d_opt(void* a, void* b) { return bdr_agent_opt((bdr_agent*)a, (bdr_replay*)b); }
 int32_t d_opt_rec(void* a, void* b, float* out, int32_t cap, int32_t* n) { return bdr_agent_opt_with_scalars((bdr_agent*)a, (bdr_replay*)b, out, cap, n); }
 int32_t d_push(void* b, uint64_t n, const void* obs, const void* act, const void* next_obs, const float* rew, const int8_t* term, const int8_t* trunc)
@@ -515,17 +505,6 @@ int32_t d_sync(void* a, void* mailbox, uint32_t reader, int32_t first, uint64_t*
 
 extern "C" {
 
-namespace {
-int32_t d_sample_dev(void* a, uint64_t n, const void* obs_dev, uint64_t stride, void* act)
-{
-    bdr_agent* ag = (bdr_agent*)a;
-    if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample_device(ag, n, obs_dev, stride, (float*)act);
-    if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample_device(ag, n, obs_dev, stride, (float*)act);
-    if (ag && !strcmp(ag->kind(), "awac")) return bdr_awac_sample_device(ag, n, obs_dev, stride, (float*)act);
-    return bdr_agent_sample_device(ag, n, obs_dev, stride, (int64_t*)act, nullptr);
-}
-}  // namespace
-
 void bdr_learner_ops_default(bdr_learner_ops* ops, bdr_agent* agent, bdr_replay* buffer, bdr_model_mailbox* mailbox)
 {
     if (!ops) return;
@@ -539,8 +518,8 @@ void bdr_actor_ops_default(bdr_actor_ops* ops, bdr_agent* agent, bdr_model_mailb
     if (!ops) return;
     memset(ops, 0, sizeof *ops);
     ops->agent = agent; ops->mailbox = mailbox;
-    ops->agent_set_train = d_set_train; ops->agent_sample = d_sample; ops->sync_model = d_sync;
-    ops->agent_sample_device = d_sample_dev;
+    ops->agent_set_train = d_set_train; ops->agent_sample = default_sample; ops->sync_model = d_sync;
+    ops->agent_sample_device = default_sample_device;
     if (env) ops->env = *env;
 }
 

@@ -1,10 +1,19 @@
-// Device helpers shared by the candle-family agents (IQL, AWAC): the counter-based N(0,1) noise stream of Policy::sample and the
-// fixed-order batch sums.  Every batch-wide sum is formed in one order (rows in blocks of 32, a 32-lane butterfly per block, the
-// block partials added in block order), so an update gives the same bits run to run.
+// The candle-family agents (IQL: iql.hip, AWAC: awac.hip) share a GaussianActor over Mlp3 (util/actor.rs, mlp/mlp3.rs) and a
+// MultiCritic of Mlp on cat(obs, act) with soft-updated targets (util/critic.rs), trained on the FP32-MFMA kernels of dense.hpp.
+// This header holds what they share.  Device: the counter-based N(0,1) noise stream of Policy::sample, the fixed-order batch sums and
+// the sample kernel.  Host: CandleAgent, the core each agent derives from; an agent adds its update schedule, its loss kernels, its
+// records and probes, and any model of its own.  Every batch-wide sum is formed in one order (rows in blocks of 32, a 32-lane
+// butterfly per block, the block partials added in block order), so an update gives the same bits run to run.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstddef>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "dense.hpp"
 
 namespace bdr {
 namespace candle {
@@ -68,3 +77,498 @@ __device__ __forceinline__ float acc(float base, float s, float scale)   // base
 
 }  // namespace candle
 }  // namespace bdr
+
+namespace {
+using namespace bdr;
+
+__global__ void k_candle_randn(float* __restrict__ out, size_t n, uint64_t seed, uint64_t counter)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = candle::randn_at(seed, counter, i);
+}
+
+// Policy::sample (util/actor.rs:226-241): train: mean + std z, eval: mean; then clamp or scale * tanh.  z = the host draws z[t] when
+// given, else the device stream at counter + t (t = b * A + j).  out [n][A]; xq (optional): the action columns O.. of a critic input.
+struct CandleSampleArgs {
+    const float* mean; int ldm; const float* head2; int A, n;
+    float lo, hi; int tanh_limit; float amin, amax, scale;
+    int train; uint64_t seed, counter; const float* z;
+    float* out; float* xq; int ldq; int O;
+};
+__global__ __launch_bounds__(256) void k_candle_sample(CandleSampleArgs p)
+{
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.n * p.A) return;
+    const int b = t / p.A, j = t % p.A;
+    float a = p.mean[(size_t)b * p.ldm + j];
+    if (p.train) {
+        const float sd = expf(fminf(fmaxf(p.head2[j], p.lo), p.hi));
+        const float zz = p.z ? p.z[t] : candle::randn_at(p.seed, p.counter, (size_t)t);
+        const float e = sd * zz;
+        a = e + a;
+    }
+    if (p.tanh_limit) { const float th = tanhf(a); a = p.scale * th; }
+    else a = fminf(fmaxf(a, p.amin), p.amax);
+    p.out[t] = a;
+    if (p.xq) p.xq[(size_t)b * p.ldq + p.O + j] = a;
+}
+
+int32_t check_mlp(const bdr_mlp_config& m, const char* what, bool actor)
+{
+    BDR_REQUIRE(m.n_units >= (actor ? 1 : 0) && m.n_units <= BDR_MAX_UNITS, "%s: bad layer count", what);
+    for (int i = 0; i < m.n_units; ++i) BDR_REQUIRE(m.units[i] >= 1 && m.units[i] <= 4096, "%s: bad layer width", what);
+    BDR_REQUIRE(m.activation_out == BDR_ACTIVATION_NONE || m.activation_out == BDR_ACTIVATION_RELU,
+                "%s: activation_out must be None or ReLU (Tanh / Sigmoid are not supported)", what);
+    return BDR_OK;
+}
+int32_t check_opt(const bdr_adamw_config& o, const char* what)
+{
+    BDR_REQUIRE(o.opt_kind == BDR_OPT_ADAM || o.opt_kind == BDR_OPT_ADAMW, "%s: unknown optimizer", what);
+    BDR_REQUIRE(!(o.opt_kind == BDR_OPT_ADAMW && o.amsgrad), "%s: candle's AdamW has no amsgrad", what);
+    return BDR_OK;
+}
+
+// ================================================================================================
+// The host core.  Self is the agent (CRTP): it supplies NAME (in messages), N_RECORD (its record values), kind(), record(),
+// record_keys(), update(Bn, obs, act, next_obs, reward, term, trunc, first) and alloc_batch(Bn), and may replace the hooks
+// init_own, alloc_staging and own_slot below.  Cfg is its bdr_*_config; the fields named here are common to all of them.
+template <class Self, class Cfg>
+struct CandleAgent : bdr_agent {
+    Cfg cfg;
+    int O = 0, A = 0, NC = 2;
+    MlpLayout pn, qn;                  // actor mean (head2 follows pn in the actor arena), critic
+    size_t h2_off = 0, pi_total = 0;   // head2 at h2_off (= pn.total) in the actor arena; pi_total = pn.total + pad64(A)
+    // arenas: parameters, gradients, exp_avg, exp_avg_sq (+ the critics' targets)
+    float *pi_p = nullptr, *pi_g = nullptr, *pi_m = nullptr, *pi_v = nullptr;
+    float* q_p[4] = {nullptr}; float* q_t[4] = {nullptr}; float* q_g[4] = {nullptr}; float* q_m[4] = {nullptr}; float* q_v[4] = {nullptr};
+    uint64_t step_pi = 0, step_q = 0;
+    uint64_t noise_counter = 0;
+    // batch buffers (ensure_batch)
+    int B = 0;
+    float *x_o = nullptr, *x_no = nullptr, *xq = nullptr;    // actor inputs [B][Kp] (obs, next_obs), critic input [B][Kq] (obs | act)
+    std::vector<float*> p_act, p_dy;                         // actor on obs, its gradients
+    std::vector<float*> c_act[4], t_act[4], c_dy[4];         // online critics, target critics, critic gradients
+    float *pr_w = nullptr, *pr_logp = nullptr, *pr_tgt = nullptr;                                 // probes [B]
+    float *pi_part = nullptr, *q_part = nullptr, *h2_part = nullptr; size_t q_part_stride = 0;   // dW partials, head2's gradient
+    std::vector<size_t> pi_off, q_off;
+    float* scal = nullptr;    // the record values, summed over the updates of one opt
+    float* samp = nullptr;    // Policy::sample rows [B][A]
+    // host staging of update_on_batch (stage_batch)
+    float *u_obs = nullptr, *u_next = nullptr, *u_act = nullptr, *u_rew = nullptr; int8_t *u_term = nullptr, *u_trunc = nullptr; uint64_t u_cap = 0;
+    int last_B = 0;
+
+    Self& self() { return static_cast<Self&>(*this); }
+
+    // Every device buffer is registered by its lifetime when it is allocated and freed here: the agent's (arenas, scal), those of
+    // one batch size (ensure_batch) and the staging rows (stage_batch)
+    enum Life { AGENT, BATCH, STAGING };
+    std::vector<void*> owned[3];
+    template <class T>
+    int32_t alloc(T** p, size_t n, Life life, bool zero = true)
+    {
+        const size_t bytes = std::max<size_t>(n, 4) * sizeof(T);
+        BDR_HIP(hipMalloc((void**)p, bytes));
+        owned[life].push_back(*p);
+        if (zero) BDR_HIP(hipMemsetAsync(*p, 0, bytes, stream));
+        return BDR_OK;
+    }
+    void release(Life life)
+    {
+        for (void* p : owned[life]) (void)hipFree(p);
+        owned[life].clear();
+    }
+    ~CandleAgent() override
+    {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+        for (Life l : {AGENT, BATCH, STAGING}) release(l);
+    }
+    int32_t layer_bufs(const MlpLayout& net, int Bn, std::vector<float*>& out)
+    {
+        out.assign(net.L.size(), nullptr);
+        for (size_t l = 0; l < net.L.size(); ++l) BDR_TRY(alloc(&out[l], (size_t)Bn * net.L[l].Np, BATCH));
+        return BDR_OK;
+    }
+    // row chunks of the grouped dW launch (k_dense_dw_small_group: 256 rows per workgroup, at most 16 chunks)
+    static int chunks_for(int Bn) { return std::max(1, std::min(16, Bn / 256)); }
+    // per-layer offsets of one network's dW partials; returns their size
+    static size_t plan(const MlpLayout& net, int Bn, std::vector<size_t>& off)
+    {
+        off.clear();
+        size_t o = 0;
+        for (const auto& l : net.L) { off.push_back(o); o += (size_t)chunks_for(Bn) * ((size_t)l.Kp * l.Np + l.Np); }
+        return o;
+    }
+    int32_t ensure_batch(int Bn)
+    {
+        if (Bn <= B) return BDR_OK;
+        BDR_HIP(hipStreamSynchronize(stream));
+        release(BATCH);
+        B = 0;
+        const int Kp = pn.L[0].Kp, Kq = qn.L[0].Kp;
+        BDR_TRY(alloc(&x_o, (size_t)Bn * Kp, BATCH)); BDR_TRY(alloc(&x_no, (size_t)Bn * Kp, BATCH)); BDR_TRY(alloc(&xq, (size_t)Bn * Kq, BATCH));
+        for (auto* vec : {&p_act, &p_dy}) BDR_TRY(layer_bufs(pn, Bn, *vec));
+        for (int i = 0; i < NC; ++i) for (auto* vec : {&c_act[i], &t_act[i], &c_dy[i]}) BDR_TRY(layer_bufs(qn, Bn, *vec));
+        for (auto p : {&pr_w, &pr_logp, &pr_tgt}) BDR_TRY(alloc(p, Bn, BATCH));
+        BDR_TRY(alloc(&pi_part, plan(pn, Bn, pi_off), BATCH));
+        q_part_stride = plan(qn, Bn, q_off);
+        BDR_TRY(alloc(&q_part, q_part_stride * NC, BATCH));
+        BDR_TRY(alloc(&h2_part, (size_t)pad64(A), BATCH));
+        BDR_TRY(alloc(&samp, (size_t)Bn * A, BATCH));
+        BDR_TRY(self().alloc_batch(Bn));
+        B = Bn;
+        return BDR_OK;
+    }
+
+    // forward of n (parameters, input) pairs of one architecture, up to 4 per launch: pass j runs params[j] on x[j] into (*acts[j])[layer]
+    int32_t mlp_forward(const MlpLayout& net, int n, const float* const* params, const float* const* x, std::vector<float*>* const* acts, int Bn, const char* name)
+    {
+        for (int j0 = 0; j0 < n; j0 += 4) {
+            const int nz = std::min(4, n - j0);
+            DenseSrc in[4]; float* out[4];
+            for (int j = 0; j < nz; ++j) in[j] = DenseSrc{x[j0 + j], net.L[0].Kp};
+            for (size_t l = 0; l < net.L.size(); ++l) {
+                for (int j = 0; j < nz; ++j) out[j] = (*acts[j0 + j])[l];
+                Bracket br(this, name);
+                BDR_TRY(dense_forward_z(stream, net.L[l], nz, params + j0, in, out, Bn, true));
+                for (int j = 0; j < nz; ++j) in[j] = DenseSrc{out[j], net.L[l].Np};
+            }
+        }
+        return BDR_OK;
+    }
+    // the actor's mean of Bn rows x ([Bn][Kp]) into acts
+    int32_t actor_forward(const float* x, std::vector<float*>& acts, int Bn)
+    {
+        const float* pp[1] = {pi_p}; const float* xs[1] = {x}; std::vector<float*>* as[1] = {&acts};
+        return mlp_forward(pn, 1, pp, xs, as, Bn, "pi_fwd");
+    }
+    static AdamScalars opt_scalars(const bdr_adamw_config& o, double lr, uint64_t step)
+    {
+        return adam_scalars_for(o.opt_kind == BDR_OPT_ADAMW, lr, o.beta1, o.beta2, o.eps, o.weight_decay, step);
+    }
+    // backward of nz networks of one layout from the last layer's output gradient dy[z][L-1]: input gradients down to layer 1 (one
+    // launch per layer for all nz), every weight gradient in one grouped launch, then the fused reduce + Adam (+ tracking into tgt)
+    int32_t mlp_backward_step(const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
+                              const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
+                              const std::vector<size_t>& off, const AdamScalars* sc, int Bn, const char* name, size_t total, const DenseReduceSeg* extra = nullptr)
+    {
+        const int L = (int)net.L.size();
+        for (int l = L - 1; l >= 1; --l) {
+            const float* pb[4]; const float* dy[4]; float* dx[4]; const float* mask[4];
+            for (int z = 0; z < nz; ++z) { pb[z] = p[z]; dy[z] = (*dys[z])[l]; dx[z] = (*dys[z])[l - 1]; mask[z] = (*acts[z])[l - 1]; }
+            Bracket br(this, name);
+            BDR_TRY(dense_dx_z(stream, net.L[l], nz, pb, dy, dx, mask, Bn, true));
+        }
+        std::vector<DenseDwJob> jobs;
+        const int c = chunks_for(Bn);
+        for (int z = 0; z < nz; ++z)
+            for (int l = 0; l < L; ++l)
+                jobs.push_back(DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*dys[z])[l],
+                                          part + (size_t)z * part_stride + off[l], c});
+        { Bracket br(this, name); BDR_TRY(dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
+        ReduceAdamArgs ra{};
+        ra.nseg = L; ra.inst_part_stride = part_stride;
+        for (int l = 0; l < L; ++l) {
+            const DenseLayer& ly = net.L[l];
+            const size_t nfl = (size_t)ly.Kp * ly.Np + ly.Np;
+            ra.seg[l] = DenseReduceSeg{part + off[l], nfl, c, (unsigned)(ly.w / 4), (unsigned)(nfl / 4)};
+        }
+        if (extra) ra.seg[ra.nseg++] = *extra;
+        for (int z = 0; z < nz; ++z) { ra.p[z] = p[z]; ra.g[z] = g[z]; ra.m[z] = m[z]; ra.v[z] = v[z]; ra.tgt[z] = tgt ? tgt[z] : nullptr; ra.s[z] = sc[z]; ra.vmax[z] = nullptr; }
+        ra.n4 = (unsigned)(total / 4); ra.track = tgt ? 1 : 0; ra.tau = (float)cfg.critic_tau; ra.omt = (float)(1.0 - cfg.critic_tau);
+        Bracket br(this, name);
+        BDR_HIP(step_launch(stream, true, k_dense_reduce_adam, dim3((ra.n4 + 255) / 256, nz), dim3(256), ra));
+        return BDR_OK;
+    }
+    // the actor's step from dL/dmean (p_dy's last layer) and dL/dhead2 (h2_part): backward and Adam, head2 as one more segment
+    int32_t actor_step(int Bn)
+    {
+        step_pi += 1;
+        const AdamScalars sc = opt_scalars(cfg.opt_actor, cfg.lr_actor, step_pi);
+        std::vector<float*>* acts[1] = {&p_act}; std::vector<float*>* dys[1] = {&p_dy};
+        const DenseReduceSeg h2seg{h2_part, (size_t)pad64(A), 1, (unsigned)(h2_off / 4), (unsigned)(pad64(A) / 4)};
+        return mlp_backward_step(pn, 1, &pi_p, &pi_g, &pi_m, &pi_v, nullptr, x_o, acts, dys, pi_part, 0, pi_off, &sc, Bn, "pi_bwd_adam", pi_total, &h2seg);
+    }
+    // the critics' step from dL/dQ_i (c_dy's last layers): backward, Adam and the soft update of the targets
+    int32_t critic_step(int Bn)
+    {
+        step_q += 1;
+        AdamScalars sc[4];
+        std::vector<float*>* acts[4]; std::vector<float*>* dys[4];
+        for (int i = 0; i < NC; ++i) { sc[i] = opt_scalars(cfg.opt_critic, cfg.lr_critic, step_q); acts[i] = &c_act[i]; dys[i] = &c_dy[i]; }
+        return mlp_backward_step(qn, NC, q_p, q_g, q_m, q_v, q_t, xq, acts, dys, q_part, q_part_stride, q_off, sc, Bn, "q_bwd_adam_track", qn.total);
+    }
+    // Policy::sample of n rows from the actor's last layer (mean) into out, and into the action columns of the critic input xqd when
+    // given: host draws z, else in train mode the device stream
+    int32_t sample_pack(const float* mean, int n, const float* z, float* out, float* xqd, const char* name)
+    {
+        CandleSampleArgs p{};
+        p.mean = mean; p.ldm = pn.L.back().Np; p.head2 = pi_p + h2_off; p.A = A; p.n = n;
+        p.lo = (float)cfg.min_log_std; p.hi = (float)cfg.max_log_std; p.tanh_limit = cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
+        p.amin = (float)cfg.action_min; p.amax = (float)cfg.action_max; p.scale = (float)cfg.action_scale;
+        p.train = train ? 1 : 0; p.seed = cfg.seed;
+        p.z = z; p.out = out; p.xq = xqd; p.ldq = qn.L[0].Kp; p.O = O;
+        if (train && !z) { p.counter = noise_counter; noise_counter += (uint64_t)n * A; }
+        const int tot = n * A;
+        Bracket br(this, name);
+        BDR_HIP(step_launch(stream, true, k_candle_sample, dim3((tot + 255) / 256), dim3(256), p));
+        return BDR_OK;
+    }
+
+    // ---- update_on_batch ----
+    // host rows -> the staging buffers, grown on demand (with the agent's own: alloc_staging)
+    int32_t stage_batch(uint64_t n, const float* obs, const float* act, const float* next_obs, const float* reward, const int8_t* term, const int8_t* trunc)
+    {
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(ensure_batch((int)n));
+        if (n > u_cap) {
+            BDR_HIP(hipStreamSynchronize(stream));
+            release(STAGING);
+            u_cap = 0;
+            BDR_TRY(alloc(&u_obs, n * O, STAGING, false)); BDR_TRY(alloc(&u_next, n * O, STAGING, false));
+            BDR_TRY(alloc(&u_act, n * A, STAGING, false)); BDR_TRY(alloc(&u_rew, n, STAGING, false));
+            BDR_TRY(alloc(&u_term, round_up(n, 16), STAGING, false)); BDR_TRY(alloc(&u_trunc, round_up(n, 16), STAGING, false));
+            BDR_TRY(self().alloc_staging(n));
+            u_cap = n;
+        }
+        BDR_HIP(hipMemcpyAsync(u_obs, obs, n * O * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipMemcpyAsync(u_next, next_obs, n * O * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipMemcpyAsync(u_act, act, n * A * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipMemcpyAsync(u_rew, reward, n * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipMemcpyAsync(u_term, term, n, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipMemcpyAsync(u_trunc, trunc, n, hipMemcpyHostToDevice, stream));
+        return BDR_OK;
+    }
+    // after the update: the profile, the record values (rec: N_RECORD floats, or null) and the device's error words
+    int32_t batch_done(float* rec)
+    {
+        prof_collect(this);
+        if (rec) BDR_HIP(hipMemcpyAsync(rec, scal, Self::N_RECORD * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        return err_check();
+    }
+
+    // ---- agent plumbing ----
+    int32_t opt(bdr_replay* r) override
+    {
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)O * 4 && r->act_bytes == (uint64_t)A * 4, "replay rows do not match %s obs/act dims (f32 rows)", Self::NAME);
+        BDR_REQUIRE(r->device == device, "agent and replay buffer live on different devices");
+        BDR_REQUIRE(!r->frame_stack, "%s reads f32 observation rows, not a frame-stack store", Self::NAME);
+        const int Bn = (int)cfg.batch_size;
+        BDR_TRY(ensure_batch(Bn));
+        for (uint64_t u = 0; u < cfg.n_updates_per_opt; ++u) {
+            { Bracket br(this, "sample"); BDR_TRY(replay_sample_on_stream(r, Bn, stream)); }
+            BDR_TRY(self().update(Bn, (const float*)r->b_obs, (const float*)r->b_act, (const float*)r->b_next, r->b_reward, r->b_term, r->b_trunc, u == 0));
+        }
+        return BDR_OK;
+    }
+    int32_t noise(float* dev, size_t n) override   // the N(0,1) stream of Policy::sample in train mode
+    {
+        BDR_HIP(step_launch(stream, true, k_candle_randn, dim3((unsigned)((n + 255) / 256)), dim3(256), dev, n, cfg.seed, noise_counter));
+        noise_counter += n;
+        return BDR_OK;
+    }
+
+    // Policy::sample (util/actor.rs:226-241) of n observation rows (host rows, or device rows inside sample_device); out: [n][A]
+    int32_t sample(uint64_t n, const float* obs, float* act_out)
+    {
+        BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(ensure_batch((int)n));
+        const float* d = nullptr;
+        int32_t st = BDR_OK;
+        if (!obs_rows_on_device && n * O * 4 <= HOST_ROWS_PINNED_MAX) {   // host rows: read in place from pinned memory by the packing kernel
+            const uint8_t* pd = nullptr;
+            BDR_TRY(host_rows_pinned(obs, n * O * 4, &pd));
+            d = reinterpret_cast<const float*>(pd);
+        } else {
+            float* stage = nullptr;
+            BDR_TRY(act_buffer(n * O * 4, (void**)&stage));
+            st = stage_obs(stage, obs, (size_t)O * 4, n, stream);
+            d = stage;
+        }
+        if (st == BDR_OK) st = pack_rows(stream, d, O, O, x_o, pn.L[0].Kp, 0, (int)n);
+        if (st == BDR_OK) st = actor_forward(x_o, p_act, (int)n);
+        if (st == BDR_OK) st = sample_pack(p_act.back(), (int)n, nullptr, samp, nullptr, "sample_pack");
+        if (st == BDR_OK) st = rows_to_host(samp, act_out, n * A);
+        slot_cursor = 0;
+        return st;
+    }
+    int32_t sample_device(uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out)
+    {
+        BDR_REQUIRE(row_stride >= (uint64_t)O * 4 && row_stride % 4 == 0, "row_stride must be >= the row size and a multiple of 4");
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(check_device_rows(obs_dev, row_stride));
+        DeviceRowsScope rows(this, row_stride);
+        return sample(n, static_cast<const float*>(obs_dev), act_out);
+    }
+    bool sample_f32(uint64_t n, const void* obs, bool on_device, uint64_t stride, float* act, int32_t* st) override
+    {
+        *st = !obs || !act ? fail(BDR_ERR_INVALID, "null argument")
+            : on_device ? sample_device(n, obs, stride, act) : sample(n, static_cast<const float*>(obs), act);
+        return true;
+    }
+
+    // ---- parameter views ----
+    // which: 0 actor, 1+i critic_i, 1+NC+i critic_tgt_i, then the agent's own models from 1+2NC (own_slot);  +100 grad, +200 exp_avg,
+    // +300 exp_avg_sq
+    struct Slot { float* p = nullptr; const MlpLayout* net = nullptr; size_t n = 0; };   // net == &pn: the actor, head2 included
+    Slot slot(int which)
+    {
+        const int role = which / 100, id = which % 100;
+        if (role > 3 || which < 0) return Slot{};
+        if (id == 0) { float* r[4] = {pi_p, pi_g, pi_m, pi_v}; return Slot{r[role], &pn, pi_total}; }
+        if (id >= 1 && id <= NC) { const int i = id - 1; float* r[4] = {q_p[i], q_g[i], q_m[i], q_v[i]}; return Slot{r[role], &qn, qn.total}; }
+        if (id >= 1 + NC && id <= 2 * NC) return role == 0 ? Slot{q_t[id - 1 - NC], &qn, qn.total} : Slot{};
+        return self().own_slot(id - 1 - 2 * NC, role);
+    }
+    uint64_t param_count(int which) override
+    {
+        Slot s = slot(which);
+        if (!s.p) return 0;
+        return s.net == &pn ? pn.ref_total + (uint64_t)A : s.net->ref_total;
+    }
+    int32_t get_params(int which, float* out, uint64_t n) override
+    {
+        Slot s = slot(which);
+        BDR_REQUIRE(s.p, "unknown %s model %d", Self::NAME, which);
+        BDR_REQUIRE(n == param_count(which), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)param_count(which));
+        std::vector<float> in(s.n);
+        BDR_HIP(hipMemcpyAsync(in.data(), s.p, s.n * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        mlp_to_reference(*s.net, 0, in.data(), out);
+        if (s.net == &pn) for (int j = 0; j < A; ++j) out[pn.ref_total + j] = in[h2_off + j];
+        return BDR_OK;
+    }
+    int32_t set_params(int which, const float* inp, uint64_t n) override
+    {
+        Slot s = slot(which);
+        BDR_REQUIRE(s.p, "unknown %s model %d", Self::NAME, which);
+        BDR_REQUIRE(n == param_count(which), "parameter count mismatch");
+        std::vector<float> in(s.n, 0.f);
+        mlp_to_internal(*s.net, 0, inp, in.data());
+        if (s.net == &pn) for (int j = 0; j < A; ++j) in[h2_off + j] = inp[pn.ref_total + j];
+        BDR_HIP(hipMemcpyAsync(s.p, in.data(), s.n * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        return BDR_OK;
+    }
+    // SyncModel ships the actor (model 0)
+    float* arena(int which, size_t* n) override { Slot s = slot(which); if (n) *n = s.n; return s.p; }
+
+    // ---- checkpoints: actor.pt, critic.pt, critic.tgt.pt ----
+    static void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt)
+    {
+        for (size_t i = 0; i < net.L.size(); ++i) {
+            mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)net.L[i].out, (uint64_t)net.L[i].in}});
+            mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)net.L[i].out}});
+        }
+    }
+    std::vector<NamedTensor> actor_meta() const
+    {
+        std::vector<NamedTensor> mt;
+        mlp_meta(pn, "actor.", mt);
+        mt.push_back({"actor.head2", {1, (uint64_t)A}});
+        return mt;
+    }
+    std::vector<NamedTensor> critic_meta() const   // one VarMap holds every critic: critic{i}.mlp.ln{k}.* (util/critic.rs:155-170)
+    {
+        std::vector<NamedTensor> mt;
+        for (int i = 0; i < NC; ++i) mlp_meta(qn, "critic" + std::to_string(i) + ".", mt);
+        return mt;
+    }
+    // candle's VarMap::save writes safetensors whatever the extension: "<stem>.pt" (default, the reference's files) or "<stem>.safetensors"
+    std::string save_path(const char* dir, const char* stem) const { return std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt"); }
+    std::string load_path(const char* dir, const char* stem) const
+    {
+        const std::string first = save_path(dir, stem);
+        const std::string second = std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".pt" : ".safetensors");
+        FILE* f = fopen(first.c_str(), "rb");
+        if (f) { fclose(f); return first; }
+        f = fopen(second.c_str(), "rb");
+        if (f) { fclose(f); return second; }
+        return first;
+    }
+    int32_t save(const char* dir) override
+    {
+        std::vector<float> v(param_count(0));
+        BDR_TRY(get_params(0, v.data(), v.size()));
+        BDR_TRY(save_safetensors_named(save_path(dir, "actor"), actor_meta(), v.data(), v.size()));
+        const size_t nq = qn.ref_total;
+        v.assign((size_t)NC * nq, 0.f);
+        for (int i = 0; i < NC; ++i) BDR_TRY(get_params(1 + i, v.data() + (size_t)i * nq, nq));
+        BDR_TRY(save_safetensors_named(save_path(dir, "critic"), critic_meta(), v.data(), v.size()));
+        return save_safetensors_named(save_path(dir, "critic.tgt"), critic_meta(), v.data(), v.size());   // the ONLINE critics (util/critic.rs:272-285)
+    }
+    int32_t load(const char* dir) override
+    {
+        std::vector<float> v(param_count(0));
+        BDR_TRY(load_safetensors_named(load_path(dir, "actor"), actor_meta(), v.data(), v.size()));
+        BDR_TRY(set_params(0, v.data(), v.size()));
+        const size_t nq = qn.ref_total;
+        v.assign((size_t)NC * nq, 0.f);
+        // MultiCritic::load (util/critic.rs:287-298): both files into the ONLINE critics' VarMap - the second load wins - and the
+        // targets stay as they are
+        BDR_TRY(load_safetensors_named(load_path(dir, "critic"), critic_meta(), v.data(), v.size()));
+        BDR_TRY(load_safetensors_named(load_path(dir, "critic.tgt"), critic_meta(), v.data(), v.size()));
+        for (int i = 0; i < NC; ++i) BDR_TRY(set_params(1 + i, v.data() + (size_t)i * nq, nq));
+        return BDR_OK;
+    }
+
+    // ---- hooks an agent may replace ----
+    int32_t init_own() { return BDR_OK; }                       // create: the agent's own models, after the actor's and critics'
+    int32_t alloc_staging(uint64_t) { return BDR_OK; }          // stage_batch: the agent's own staging rows (alloc(..., STAGING))
+    Slot own_slot(int /*k*/, int /*role*/) { return Slot{}; }   // model 1 + 2NC + k
+
+    // bdr_*_create after its null check: the checks in their order, the device, then the agent with its initial parameters.
+    // value / opt_value: IQL's value model, checked before the actor's; one_row: why a one-row batch is refused (AWAC), null where one
+    // row is allowed.
+    static int32_t create(const Cfg& c, bdr_agent** out, const bdr_mlp_config* value, const bdr_adamw_config* opt_value, const char* one_row)
+    {
+        BDR_REQUIRE(c.device >= 0, "No device is given for %s agent", Self::NAME);
+        BDR_REQUIRE(c.obs_dim >= 1 && c.obs_dim <= 4096 && c.act_dim >= 1 && c.act_dim <= 256, "bad obs/act dims");
+        if (value) BDR_TRY(check_mlp(*value, "value", false));
+        BDR_TRY(check_mlp(c.actor, "actor (Mlp3)", true));
+        BDR_TRY(check_mlp(c.critic, "critic", false));
+        BDR_REQUIRE(c.n_critics >= 1 && c.n_critics <= 4, "n_critics must be in [1,4]");
+        if (one_row) BDR_REQUIRE(c.batch_size != 1, "%s", one_row);
+        BDR_REQUIRE(c.batch_size >= 1 && c.batch_size <= 65536 && c.n_updates_per_opt >= 1, "bad batch / update counts");
+        BDR_REQUIRE(c.action_limit == BDR_ACTION_LIMIT_CLAMP || c.action_limit == BDR_ACTION_LIMIT_TANH, "unknown action limit");
+        BDR_REQUIRE(c.critic_loss == BDR_LOSS_MSE || c.critic_loss == BDR_LOSS_SMOOTH_L1, "unknown critic loss");
+        if (opt_value) BDR_TRY(check_opt(*opt_value, "value"));
+        BDR_TRY(check_opt(c.opt_actor, "actor")); BDR_TRY(check_opt(c.opt_critic, "critic"));
+        BDR_TRY(ensure_device(c.device));
+        Self* a = new Self();
+        a->cfg = c; a->device = c.device; a->train = c.train != 0;
+        a->O = c.obs_dim; a->A = c.act_dim; a->NC = c.n_critics;
+        a->pn = make_mlp(a->O, c.actor.units, c.actor.n_units, a->A, false);   // Mlp3: no output activation
+        a->qn = make_mlp(a->O + a->A, c.critic.units, c.critic.n_units, 1, c.critic.activation_out == BDR_ACTIVATION_RELU);
+        a->h2_off = a->pn.total; a->pi_total = a->pn.total + (size_t)pad64(a->A);
+        const int32_t st = [&]() -> int32_t {
+            BDR_HIP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
+            BDR_TRY(a->err_init());
+            for (auto p : {&a->pi_p, &a->pi_g, &a->pi_m, &a->pi_v}) BDR_TRY(a->alloc(p, a->pi_total, AGENT));
+            for (int i = 0; i < a->NC; ++i)
+                for (auto p : {&a->q_p[i], &a->q_t[i], &a->q_g[i], &a->q_m[i], &a->q_v[i]}) BDR_TRY(a->alloc(p, a->qn.total, AGENT));
+            BDR_TRY(a->alloc(&a->scal, Self::N_RECORD, AGENT));
+            // initial parameters: the library's initialiser, head2 = 0 (mlp3.rs: Init::Const(0.)); targets are copies of the critics
+            std::vector<float> ref(a->param_count(0), 0.f);
+            mlp_init_reference(a->pn, c.seed * 7 + 1, ref.data());
+            BDR_TRY(a->set_params(0, ref.data(), ref.size()));
+            ref.assign(a->qn.ref_total, 0.f);
+            for (int i = 0; i < a->NC; ++i) {
+                mlp_init_reference(a->qn, c.seed * 7 + 2 + i, ref.data());
+                BDR_TRY(a->set_params(1 + i, ref.data(), ref.size()));
+                BDR_TRY(a->set_params(1 + a->NC + i, ref.data(), ref.size()));
+            }
+            BDR_TRY(a->init_own());
+            return a->ensure_batch((int)c.batch_size);
+        }();
+        if (st != BDR_OK) { delete a; return st; }
+        *out = a;
+        return BDR_OK;
+    }
+};
+
+}  // namespace

@@ -82,30 +82,13 @@ int32_t check(const bdr_trainer_config* c, const bdr_trainer_ops* ops)
 
 // defaults: the library's own handles
 int32_t d_set_train(void* a, int32_t on) { return bdr_agent_set_train((bdr_agent*)a, on); }
-// Policy::sample of the handle's kind: i64 actions for DQN / IQN, f32 action rows for SAC (sac/base.rs:215-225)
-int32_t d_sample(void* a, uint64_t n, const void* obs, void* act)
-{
-    bdr_agent* ag = (bdr_agent*)a;
-    if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample(ag, n, (const float*)obs, (float*)act);
-    if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample(ag, n, (const float*)obs, (float*)act);   // util/actor.rs:226-241
-    if (ag && !strcmp(ag->kind(), "awac")) return bdr_awac_sample(ag, n, (const float*)obs, (float*)act);
-    return bdr_agent_sample(ag, n, obs, (int64_t*)act, nullptr);
-}
 int32_t d_opt(void* a, void* b) { return bdr_agent_opt((bdr_agent*)a, (bdr_replay*)b); }
 int32_t d_opt_rec(void* a, void* b, float* out, int32_t cap, int32_t* n) { return bdr_agent_opt_with_scalars((bdr_agent*)a, (bdr_replay*)b, out, cap, n); }
 int32_t d_push(void* b, uint64_t n, const void* obs, const void* act, const void* next_obs, const float* rew, const int8_t* term, const int8_t* trunc)
 {
     return bdr_replay_push((bdr_replay*)b, n, obs, act, next_obs, rew, term, trunc);
 }
-// the same two for device-resident observations (bdr_env_vtable::obs_on_device)
-int32_t d_sample_dev(void* a, uint64_t n, const void* obs_dev, uint64_t stride, void* act)
-{
-    bdr_agent* ag = (bdr_agent*)a;
-    if (ag && !strcmp(ag->kind(), "sac")) return bdr_sac_sample_device(ag, n, obs_dev, stride, (float*)act);
-    if (ag && !strcmp(ag->kind(), "iql")) return bdr_iql_sample_device(ag, n, obs_dev, stride, (float*)act);
-    if (ag && !strcmp(ag->kind(), "awac")) return bdr_awac_sample_device(ag, n, obs_dev, stride, (float*)act);
-    return bdr_agent_sample_device(ag, n, obs_dev, stride, (int64_t*)act, nullptr);
-}
+// bdr_replay_push for device-resident observations (bdr_env_vtable::obs_on_device)
 int32_t d_push_dev(void* b, uint64_t n, const void* obs_dev, uint64_t os, const void* act, const void* next_dev, uint64_t ns, const float* rew,
                    const int8_t* term, const int8_t* trunc)
 {
@@ -137,9 +120,9 @@ void bdr_trainer_ops_default(bdr_trainer_ops* ops, bdr_agent* agent, bdr_replay*
 {
     if (!ops) return;
     ops->agent = agent; ops->buffer = buffer;
-    ops->agent_set_train = d_set_train; ops->agent_sample = d_sample; ops->agent_opt = d_opt;
+    ops->agent_set_train = d_set_train; ops->agent_sample = default_sample; ops->agent_opt = d_opt;
     ops->agent_opt_with_record = d_opt_rec; ops->buffer_push = d_push;
-    ops->agent_sample_device = d_sample_dev; ops->buffer_push_device = d_push_dev;
+    ops->agent_sample_device = default_sample_device; ops->buffer_push_device = d_push_dev;
 }
 
 int32_t bdr_trainer_train(const bdr_trainer_config* c, const bdr_trainer_ops* ops, const bdr_env_vtable* env,

@@ -6,6 +6,7 @@
   GaussianActorConfig  util/actor.rs:36-55 (policy_config: Mlp3's MlpConfig, opt_config, min/max_log_std, action_limit)
   ActionLimit          util/actor.rs:29-32 (Tanh{action_scale} | Clamp{action_min, action_max})
   CandleMlpConfig      mlp/config.rs:6-11 (activation_out: "None" | "ReLU")
+  CandleAgent          what Iql and Awac (border_amd.awac) share over the C ABI
   Iql                  iql/base.rs (Agent, Policy::sample, SyncModel ships the actor)
 """
 from __future__ import annotations
@@ -127,16 +128,24 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-class Iql:
-    def __init__(self, config: IqlConfig):
+ROLES = {"param": 0, "grad": 100, "exp_avg": 200, "exp_avg_sq": 300}
+
+
+class CandleAgent:
+    """The handle of a candle-family agent (csrc/candle_actor.hpp): its lifecycle, Agent::opt, Policy::sample (bdr_<KIND>_sample*),
+    the parameter views of the actor and the critics, SyncModel (the actor) and the checkpoint files CKPT_STEMS."""
+    KIND = ""                        # "iql" | "awac": the bdr_<KIND>_* entry points
+    CKPT_STEMS: Tuple[str, ...] = ()
+
+    def __init__(self, config):
         self.config = config
         h = C.c_void_p()
         c = config.to_c()
-        _lib.check(_lib.lib().bdr_iql_create(C.byref(c), C.byref(h)))
+        _lib.check(getattr(_lib.lib(), f"bdr_{self.KIND}_create")(C.byref(c), C.byref(h)))
         self._h = h
 
     @classmethod
-    def build(cls, config: IqlConfig) -> "Iql":
+    def build(cls, config):
         return cls(config)
 
     def close(self):
@@ -158,16 +167,18 @@ class Iql:
     def n_critics(self) -> int:
         return self.config.critic_config.n_nets
 
-    # model ids (bdr_agent_get_params `which`)
-    def which(self, name: str, role: str = "param") -> int:
+    def _model_id(self, name: str) -> int:
+        """actor 0, critic_i 1 + i, critic_tgt_i 1 + n_critics + i; an agent's own models follow"""
         nc = self.n_critics
         if name.startswith("critic_tgt_"):
-            i = 1 + nc + int(name[len("critic_tgt_"):])
-        elif name.startswith("critic_"):
-            i = 1 + int(name[len("critic_"):])
-        else:
-            i = {"actor": 0, "value": 1 + 2 * nc}[name]
-        return i + {"param": 0, "grad": 100, "exp_avg": 200, "exp_avg_sq": 300}[role]
+            return 1 + nc + int(name[len("critic_tgt_"):])
+        if name.startswith("critic_"):
+            return 1 + int(name[len("critic_"):])
+        return {"actor": 0}[name]
+
+    # model ids (bdr_agent_get_params `which`)
+    def which(self, name: str, role: str = "param") -> int:
+        return self._model_id(name) + ROLES[role]
 
     WHICH = {"actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the actor == model 0
 
@@ -197,34 +208,15 @@ class Iql:
         from .dqn import draw_noise
         return draw_noise(self._h, n)
 
-    def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated) -> dict:
-        f = lambda x: np.ascontiguousarray(x, dtype=np.float32)
-        obs, act, next_obs, reward = map(f, (obs, act, next_obs, reward))
-        term = np.ascontiguousarray(is_terminated, dtype=np.int8)
-        trunc = np.ascontiguousarray(is_truncated, dtype=np.int8)
-        rec = np.zeros(3, np.float32)
-        _lib.check(_lib.lib().bdr_iql_update_on_batch(self._h, len(reward), _p(obs), _p(act), _p(next_obs), _p(reward), _p(term),
-                                                      _p(trunc), _p(rec)))
-        return dict(loss_value=float(rec[0]), loss_critic=float(rec[1]), loss_actor=float(rec[2]))
-
-    PROBES = {"q_tgt_min_value": 0, "v": 1, "u": 2, "tgt": 3, "q_pred": 4, "q_tgt_min_actor": 5, "w": 6, "logp": 7, "v_next": 8, "v_obs": 9}
-
-    def probe(self, what: str, batch: int) -> np.ndarray:
-        """Intermediates of the last update (bdr_iql_probe): q_pred [n_critics, B], every other one [B]."""
-        shape = (self.n_critics, batch) if what == "q_pred" else (batch,)
-        out = np.empty(shape, np.float32)
-        _lib.check(_lib.lib().bdr_iql_probe(self._h, self.PROBES[what], _p(out), out.size))
-        return out
-
     def sample(self, obs) -> np.ndarray:
         obs = np.ascontiguousarray(obs, dtype=np.float32)
         out = np.empty((obs.shape[0], self.config.act_dim), np.float32)
-        _lib.check(_lib.lib().bdr_iql_sample(self._h, obs.shape[0], _p(obs), _p(out)))
+        _lib.check(getattr(_lib.lib(), f"bdr_{self.KIND}_sample")(self._h, obs.shape[0], _p(obs), _p(out)))
         return out
 
     def sample_device(self, obs_dev: int, n: int, row_stride: int) -> np.ndarray:
         out = np.empty((n, self.config.act_dim), np.float32)
-        _lib.check(_lib.lib().bdr_iql_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(out)))
+        _lib.check(getattr(_lib.lib(), f"bdr_{self.KIND}_sample_device")(self._h, n, C.c_void_p(obs_dev), row_stride, _p(out)))
         return out
 
     def sync(self):
@@ -265,11 +257,39 @@ class Iql:
         self._ckpt_ext = {"tch": ".pt", "safetensors": ".safetensors"}[fmt]
 
     def save_params(self, path: str):
-        """iql/base.rs:292-302: actor, critic, critic.tgt (the ONLINE critics, util/critic.rs:272-285), value."""
+        """The files of CKPT_STEMS; critic.tgt holds the ONLINE critics (util/critic.rs:272-285)."""
         os.makedirs(path, exist_ok=True)
         _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
         ext = getattr(self, "_ckpt_ext", ".pt")
-        return [os.path.join(path, stem + ext) for stem in ("actor", "critic", "critic.tgt", "value")]
+        return [os.path.join(path, stem + ext) for stem in self.CKPT_STEMS]
 
     def load_params(self, path: str):
         _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))
+
+
+class Iql(CandleAgent):
+    """iql/base.rs; checkpoints (iql/base.rs:292-302): actor, critic, critic.tgt, value."""
+    KIND = "iql"
+    CKPT_STEMS = ("actor", "critic", "critic.tgt", "value")
+
+    def _model_id(self, name: str) -> int:
+        return 1 + 2 * self.n_critics if name == "value" else super()._model_id(name)
+
+    def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated) -> dict:
+        f = lambda x: np.ascontiguousarray(x, dtype=np.float32)
+        obs, act, next_obs, reward = map(f, (obs, act, next_obs, reward))
+        term = np.ascontiguousarray(is_terminated, dtype=np.int8)
+        trunc = np.ascontiguousarray(is_truncated, dtype=np.int8)
+        rec = np.zeros(3, np.float32)
+        _lib.check(_lib.lib().bdr_iql_update_on_batch(self._h, len(reward), _p(obs), _p(act), _p(next_obs), _p(reward), _p(term),
+                                                      _p(trunc), _p(rec)))
+        return dict(loss_value=float(rec[0]), loss_critic=float(rec[1]), loss_actor=float(rec[2]))
+
+    PROBES = {"q_tgt_min_value": 0, "v": 1, "u": 2, "tgt": 3, "q_pred": 4, "q_tgt_min_actor": 5, "w": 6, "logp": 7, "v_next": 8, "v_obs": 9}
+
+    def probe(self, what: str, batch: int) -> np.ndarray:
+        """Intermediates of the last update (bdr_iql_probe): q_pred [n_critics, B], every other one [B]."""
+        shape = (self.n_critics, batch) if what == "q_pred" else (batch,)
+        out = np.empty(shape, np.float32)
+        _lib.check(_lib.lib().bdr_iql_probe(self._h, self.PROBES[what], _p(out), out.size))
+        return out
