@@ -1,0 +1,213 @@
+"""Host-side mirror of border-candle-agent's Bc agent (behaviour cloning) over the C ABI.
+
+  BcConfig        border-candle-agent/src/bc/config.rs (defaults :66-75: batch_size 1, action_type Discrete, device None,
+                  record_verbose_level 0)
+  BcModelConfig   bc/model.rs (policy_model_config: the Mlp's MlpConfig, opt_config: OptimizerConfig::default() = AdamW)
+  BcActionType    bc/config.rs (Discrete | Continuous)
+  Bc              bc/base.rs (Agent, Policy::sample, SyncModel ships the policy; train() / eval() do nothing, is_train() is false)
+
+The policy is a plain Mlp whose activation_out may be any of "None", "ReLU", "Tanh", "Sigmoid" (CandleMlpConfig of border_amd.iql).
+kernel_form picks how one update is launched: "default", "general" (three launches for the last layer, any act_dim) or "fused"
+(k_bc_head, act_dim <= 64, the last layer's weights staged in LDS; head_rows is its row block, 0: the measured default) or "fused_mfma"
+(k_bc_head_mfma, the same launch on the FP32 MFMA, 32 rows per workgroup).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass, field
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from .dqn import OptimizerConfig
+from .iql import ROLES, CandleMlpConfig, _p
+from .replay import SimpleReplayBuffer
+
+
+class BcActionType:
+    Discrete = "Discrete"
+    Continuous = "Continuous"
+
+
+ACTION_TYPES = {BcActionType.Discrete: 0, BcActionType.Continuous: 1}   # BDR_BC_ACTION_*
+KERNEL_FORMS = {"default": 0, "general": 1, "fused": 2, "fused_mfma": 3}   # BDR_BC_KERNEL_*
+
+
+@dataclass
+class BcModelConfig:
+    policy_model_config: CandleMlpConfig = field(default_factory=CandleMlpConfig)
+    opt_config: OptimizerConfig = field(default_factory=lambda: OptimizerConfig.AdamW(1e-3))
+
+
+@dataclass
+class BcConfig:
+    obs_dim: int = 0
+    act_dim: int = 0
+    policy_model_config: BcModelConfig = field(default_factory=BcModelConfig)
+    batch_size: int = 1
+    action_type: str = BcActionType.Discrete
+    device: Optional[int] = None
+    record_verbose_level: int = 0
+    seed: int = 0
+    kernel_form: str = "default"
+    head_rows: int = 0
+
+    def to_c(self) -> _lib.BcConfigC:
+        c = _lib.BcConfigC()
+        _lib.lib().bdr_bc_config_default(C.byref(c))
+        c.obs_dim, c.act_dim = self.obs_dim, self.act_dim
+        self.policy_model_config.policy_model_config.fill(c.policy)
+        c.opt.fill(self.policy_model_config.opt_config)
+        c.lr = self.policy_model_config.opt_config.lr
+        c.batch_size, c.action_type = self.batch_size, ACTION_TYPES[self.action_type]
+        c.device = -1 if self.device is None else self.device
+        c.record_verbose_level, c.seed = self.record_verbose_level, self.seed
+        c.kernel_form, c.head_rows = KERNEL_FORMS[self.kernel_form], self.head_rows
+        return c
+
+
+class Bc:
+    """bc/base.rs; checkpoint (bc/base.rs:138-153): policy_model."""
+    KIND = "bc"
+    CKPT_STEMS = ("policy_model",)
+    WHICH = {"policy": 0, "actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the policy == model 0
+    PROBES = {"pred": 0, "dz": 1}
+
+    def __init__(self, config: BcConfig):
+        self.config = config
+        h = C.c_void_p()
+        c = config.to_c()
+        _lib.check(_lib.lib().bdr_bc_create(C.byref(c), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def build(cls, config):
+        return cls(config)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().bdr_agent_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def which(self, name: str = "policy", role: str = "param") -> int:
+        return self.WHICH[name] + ROLES[role]
+
+    def arena_device_ptr(self, which="policy"):
+        ptr, n = C.c_void_p(), C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
+        return ptr.value, n.value
+
+    def train(self):
+        """bc/base.rs:104-106: nothing to switch"""
+        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 1))
+
+    def eval(self):
+        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 0))
+
+    def is_train(self) -> bool:
+        """bc/base.rs:110-112: always False"""
+        out = C.c_int32()
+        _lib.check(_lib.lib().bdr_agent_is_train(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def opt(self, buffer: SimpleReplayBuffer) -> None:
+        _lib.check(_lib.lib().bdr_agent_opt(self._h, buffer.handle))
+
+    def opt_with_record(self, buffer: SimpleReplayBuffer) -> dict:
+        from .dqn import opt_with_named_record
+        return opt_with_named_record(self._h, buffer)
+
+    def update_on_batch(self, obs, act) -> dict:
+        """One Bc::opt_ (bc/base.rs:167-198) on host rows; the record's one key is "loss"."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        act = np.ascontiguousarray(act, dtype=np.float32)
+        n = obs.shape[0]
+        if obs.size != n * self.config.obs_dim or act.size != n * self.config.act_dim:
+            raise ValueError(f"rows must hold {n} x {self.config.obs_dim} observations and {n} x {self.config.act_dim} actions")
+        rec = np.zeros(1, np.float32)
+        _lib.check(_lib.lib().bdr_bc_update_on_batch(self._h, n, _p(obs), _p(act), _p(rec)))
+        return {"loss": float(rec[0])}
+
+    def probe(self, what: str, batch: int) -> np.ndarray:
+        """Intermediates of the last update (bdr_bc_probe): pred, dz [B, act_dim]."""
+        out = np.empty((batch, self.config.act_dim), np.float32)
+        _lib.check(_lib.lib().bdr_bc_probe(self._h, self.PROBES[what], _p(out), out.size))
+        return out
+
+    def profile_enable(self, on: bool = True):
+        _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
+
+    def _out(self, n: int):
+        if self.config.action_type == BcActionType.Discrete:
+            return np.empty(n, np.int64), True
+        return np.empty((n, self.config.act_dim), np.float32), False
+
+    def sample(self, obs) -> np.ndarray:
+        """Policy::sample (bc/base.rs:49-59): [n, act_dim] f32 (Continuous) or [n] i64 argmax indices (Discrete)"""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        out, disc = self._out(obs.shape[0])
+        _lib.check(_lib.lib().bdr_bc_sample(self._h, obs.shape[0], _p(obs), None if disc else _p(out), _p(out) if disc else None))
+        return out
+
+    def sample_device(self, obs_dev: int, n: int, row_stride: int) -> np.ndarray:
+        out, disc = self._out(n)
+        _lib.check(_lib.lib().bdr_bc_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, None if disc else _p(out),
+                                                   _p(out) if disc else None))
+        return out
+
+    def sync(self):
+        _lib.check(_lib.lib().bdr_agent_sync(self._h))
+
+    @property
+    def n_opts(self) -> int:
+        n = C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
+        return n.value
+
+    def param_count(self, name="policy") -> int:
+        n = C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_param_count_of(self._h, self.which(name), C.byref(n)))
+        return n.value
+
+    def get_params(self, name="policy", role="param") -> np.ndarray:
+        out = np.empty(self.param_count(name), np.float32)
+        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.which(name, role), _p(out), out.size))
+        return out
+
+    def set_params(self, params, name="policy", role="param") -> None:
+        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.which(name, role), _p(p), p.size))
+
+    def model_info(self):
+        """SyncModel::model_info: the policy's parameters."""
+        return self.n_opts, self.get_params()
+
+    def sync_model(self, model_info) -> None:
+        self.set_params(model_info)
+
+    def set_checkpoint_format(self, fmt: str) -> None:
+        """"tch" (default): `policy_model.pt` (safetensors, as candle's VarMap writes it); "safetensors": `policy_model.safetensors`."""
+        from .checkpoint import FORMATS
+        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
+        self._ckpt_ext = {"tch": ".pt", "safetensors": ".safetensors"}[fmt]
+
+    def save_params(self, path: str):
+        os.makedirs(path, exist_ok=True)
+        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
+        ext = getattr(self, "_ckpt_ext", ".pt")
+        return [os.path.join(path, stem + ext) for stem in self.CKPT_STEMS]
+
+    def load_params(self, path: str):
+        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))

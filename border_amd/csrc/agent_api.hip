@@ -348,7 +348,7 @@ int32_t bdr_agent_destroy(bdr_agent* a)
     return BDR_OK;
 }
 
-int32_t bdr_agent_set_train(bdr_agent* a, int32_t train) { BDR_REQUIRE(a, "null agent"); a->train = train != 0; return BDR_OK; }
+int32_t bdr_agent_set_train(bdr_agent* a, int32_t train) { BDR_REQUIRE(a, "null agent"); a->train = train != 0 && a->has_train_mode(); return BDR_OK; }
 int32_t bdr_agent_is_train(const bdr_agent* a, int32_t* out) { BDR_REQUIRE(a && out, "null argument"); *out = a->train; return BDR_OK; }
 int32_t bdr_agent_n_opts(const bdr_agent* a, uint64_t* n) { BDR_REQUIRE(a && n, "null argument"); *n = a->n_opts; return BDR_OK; }
 

@@ -288,6 +288,7 @@ struct bdr_agent {
     // the rows can be read in place (device rows that are already contiguous)
     bool obs_in_place(size_t row_bytes) const { return obs_rows_on_device && obs_row_stride == row_bytes; }
     virtual const char* kind() const = 0;
+    virtual bool has_train_mode() const { return true; }          // false: train() / eval() are accepted and is_train() stays false (BC)
     virtual int32_t opt(bdr_replay* r) = 0;                       // Agent::opt, asynchronous
     virtual int32_t after_sync() { return BDR_OK; }               // device-side error flags, checked by bdr_agent_sync
     virtual int32_t record(float* out, int cap, int* n) = 0;      // scalars of the last update (syncs)

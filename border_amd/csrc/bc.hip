@@ -1,0 +1,707 @@
+// BC (behaviour cloning) agent on MI355X: Bc::opt_ (border-candle-agent/src/bc/base.rs:167-198): loss = mse(policy(obs), act) - the mean of
+// the squared differences over all B x A elements - backward and one optimizer step on the policy, a plain Mlp (mlp/base.rs,
+// mlp.rs:14-24: ReLU after every layer but the last, activation_out after the last; lib.rs:58-74 None | ReLU | Tanh | Sigmoid).  No
+// critic, no target, no noise; the record holds "loss" (:191-193).  Policy::sample (:49-59): Continuous returns the network output,
+// Discrete the argmax over the last dimension as i64; the Discrete update is a panic in the reference (:174) and an error here.
+// train() / eval() do nothing and is_train() is false (:104-112).
+// Hidden layers, the grouped weight gradient and the fused reduce + Adam are dense.hpp's FP32-MFMA kernels, unchanged.  BC's own:
+//   k_bc_loss   (general form) y = act_out(z), the loss, dL/dz from the last layer's pre-activation z [B][Np]
+//   k_bc_head   (fused form, out_dim <= 64) the last layer's forward, y, the loss, dL/dz and the last layer's input gradient in one
+//               row-block launch, the layer's weights staged in LDS once per workgroup
+//   k_bc_head_mfma  the same on the FP32 MFMA: 32 rows per workgroup, dense.hpp's 32 x 32 tiles, the weights read from L2
+//   k_bc_act    Policy::sample: the output activation (Continuous) or the row-wise argmax (Discrete)
+// One update, general form: pack, L forwards, k_bc_loss, L-1 input gradients, the grouped dW, reduce + Adam (3L + 2 launches);
+// fused form: pack, L-1 forwards, k_bc_head, L-2 input gradients, the grouped dW, reduce + Adam (3L - 1 launches).
+// Every sum has one order, so an update gives the same bits run to run and agent to agent.  The loss: per row the squared
+// differences added in column order; then candle_actor.hpp's batch order (rows in blocks of 32, a butterfly per block, the block
+// partials added in block order), formed by the launch's last workgroup from per-row sums - no workgroup waits for another, and no
+// float atomics.  The two forms form the last layer's dot products in different orders and need not agree bitwise.
+#include <algorithm>
+#include <cstdlib>
+
+#include "candle_actor.hpp"
+
+using namespace bdr;
+
+namespace {
+
+// one output element: y = act_out(z), d = y - a; sq = d^2; dz = 2 d inv_n * act_out'(z)
+__device__ __forceinline__ void bc_elem(int kind, float z, float a, float inv_n, float& y, float& dz, float& sq)
+{
+#pragma clang fp contract(off)
+    float gp = 1.f;
+    y = z;
+    if (kind == BDR_ACTIVATION_RELU) { y = z > 0.f ? z : 0.f; gp = z > 0.f ? 1.f : 0.f; }
+    else if (kind == BDR_ACTIVATION_TANH) { y = tanhf(z); const float yy = y * y; gp = 1.f - yy; }
+    else if (kind == BDR_ACTIVATION_SIGMOID) { const float e = expf(-z); y = 1.f / (1.f + e); gp = y * (1.f - y); }
+    const float d = y - a;
+    sq = d * d;
+    const float g = 2.f * d;
+    const float gs = g * inv_n;
+    dz = gs * gp;
+}
+__device__ __forceinline__ float bc_act_out(int kind, float z)
+{
+    if (kind == BDR_ACTIVATION_RELU) return z > 0.f ? z : 0.f;
+    if (kind == BDR_ACTIVATION_TANH) return tanhf(z);
+    if (kind == BDR_ACTIVATION_SIGMOID) return 1.f / (1.f + expf(-z));
+    return z;
+}
+
+// The launch's last workgroup (256 threads): the per-row sums in candle::row_sum's order - blocks of 32 rows, a butterfly per
+// block, the partials added in block order (the order does not depend on the workgroup's size) - into the record slot.
+// rowsq was written with agent-scope stores by every workgroup before its ticket (dense.hpp last_workgroup).
+__device__ __forceinline__ void bc_finish_loss(const float* rowsq, int B, float* scal, int accumulate, float inv_n, float* red8)
+{
+    float total = 0.f;
+    for (int base = 0; base < B; base += 256) {
+        const int b = base + (int)threadIdx.x;
+        const float part = candle::butterfly32(b < B ? ld_agent(rowsq + b) : 0.f);
+        if ((threadIdx.x & 31) == 0) red8[threadIdx.x >> 5] = part;
+        __syncthreads();
+        const int nb = min(8, (B - base + 31) / 32);
+        for (int k = 0; k < nb; ++k) total += red8[k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) scal[0] = candle::acc(accumulate ? scal[0] : 0.f, total, inv_n);
+}
+
+// ---- general form -----------------------------------------------------------------------------------------------------------------
+// z [B][ld] (ld = pad64(A)), act [B][A].  Workgroup w owns rows [32 w, 32 w + 32): y -> pred, dL/dz -> dz (both [B][ld], padding
+// columns zero), the row sums -> rowsq.  Bounds: rows b < B and columns j < ld only; sq holds 32 x (ld + 1) floats, ld <= 256.
+struct BcLossArgs {
+    const float* z; int ld; const float* act; int A, B, kind;
+    float* pred; float* dz; float* rowsq; unsigned* ticket; float* scal; int accumulate; float inv_n;
+};
+__global__ __launch_bounds__(256) void k_bc_loss(BcLossArgs p)
+{
+    __shared__ float sq[32 * 257];
+    __shared__ float red8[8];
+    __shared__ unsigned s_flag;
+    const int r0 = (int)blockIdx.x * 32, ls = p.ld + 1;
+    for (int t = threadIdx.x; t < 32 * p.ld; t += 256) {
+        const int r = t / p.ld, j = t % p.ld, b = r0 + r;
+        float y = 0.f, g = 0.f, s = 0.f;
+        if (b < p.B && j < p.A) bc_elem(p.kind, p.z[(size_t)b * p.ld + j], p.act[(size_t)b * p.A + j], p.inv_n, y, g, s);
+        sq[r * ls + j] = s;
+        if (b < p.B) { p.pred[(size_t)b * p.ld + j] = y; p.dz[(size_t)b * p.ld + j] = g; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && r0 + (int)threadIdx.x < p.B) {
+        float s = 0.f;
+        for (int j = 0; j < p.A; ++j) s += sq[threadIdx.x * ls + j];
+        st_agent(p.rowsq + r0 + threadIdx.x, s);
+    }
+    if (last_workgroup(p.ticket, gridDim.x, &s_flag)) bc_finish_loss(p.rowsq, p.B, p.scal, p.accumulate, p.inv_n, red8);
+}
+
+// ---- fused form -------------------------------------------------------------------------------------------------------------------
+// h [B][K] the last hidden activation (post-ReLU, K = its padded width), w [K][64] + bias [64] the last layer (out_dim <= 64).
+// Workgroup g owns rows [R g, R g + R):  z = h w + bias (k ascending, then the bias), y, dL/dz, the row sums, and
+// dL/dh[b][k] = [h > 0] sum_n dz[b][n] w[k][n] (n ascending).  y -> pred, dL/dz -> dz ([B][64], padding columns zero: the grouped
+// dW launch reads them), dL/dh -> dx [B][K].
+// LDS (dynamic, floats): ws [K][65] the weights (row stride 65: the forward reads a row across lanes, dX a column across lanes, both
+// without bank conflicts) | hs [R][K] | dzt [64][R] | sq [R][65] | red8 [8] | flag.  bc_head_lds() is the size; the host refuses
+// shapes beyond 160 KB.  Bounds: rows are clamped to B - 1 when loaded and stored only for b < B; k < K; n < 64.
+struct BcHeadArgs {
+    const float* h; int K; const float* w; const float* bias; const float* act; int A, B, kind;
+    float* pred; float* dz; float* dx; float* rowsq; unsigned* ticket; float* scal; int accumulate; float inv_n;
+};
+constexpr int BC_HEAD_ROWS_DEFAULT = 8;   // measured at the bc_pen shape: 8 rows 22.9k updates/s, 16 rows 21.1k, 32 rows 17.1k (profiles/bench_bc_pen.json)
+// BDR_BC_KERNEL_DEFAULT: the MFMA head where it applies and the update is launch-bound.  Measured at the bc_pen shape (B = 256,
+// profiles/bench_bc_pen.json): 23 200-23 600 updates/s against 21 800-22 000 (general) and 22 600-23 000 (k_bc_head, 8 rows) in five
+// alternating rounds.  Nothing was measured above a few hundred rows, where the launches stop being the bound: the general form there.
+inline int bc_default_form(int batch, bool can_mfma) { return can_mfma && batch <= 1024 ? BDR_BC_KERNEL_FUSED_MFMA : BDR_BC_KERNEL_GENERAL; }
+inline size_t bc_head_lds(int K, int R) { return ((size_t)K * 65 + (size_t)R * K + 64 * (size_t)R + (size_t)R * 65 + 8 + 4) * sizeof(float) + 64; }
+template <int R>
+__global__ __launch_bounds__(256) void k_bc_head(BcHeadArgs p)
+{
+    extern __shared__ __attribute__((aligned(16))) float bc_lds[];
+    const int K = p.K, tid = threadIdx.x;
+    // carve: hs first (16-byte aligned rows for the b128 broadcast reads), then dzt (also read as b128), then the scalar-read parts
+    float* hs = bc_lds;
+    float* dzt = hs + (size_t)R * K;
+    float* ws = dzt + 64 * R;
+    float* sq = ws + (size_t)K * 65;
+    float* red8 = sq + R * 65;
+    unsigned* s_flag = reinterpret_cast<unsigned*>(red8 + 8);
+    const int r0 = (int)blockIdx.x * R;
+    for (int i = tid; i < K * 16; i += 256) {   // K x 64 weights, four columns per load
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p.w + (size_t)i * 4);
+        float* d = ws + (i >> 4) * 65 + (i & 15) * 4;
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    }
+    const int K4 = K / 4;
+    for (int i = tid; i < R * K4; i += 256) {
+        const int r = i / K4, q = i % K4;
+        *reinterpret_cast<f32x4*>(hs + (size_t)r * K + q * 4) = *reinterpret_cast<const f32x4*>(p.h + (size_t)min(r0 + r, p.B - 1) * K + q * 4);
+    }
+    __syncthreads();
+    // forward: lane -> column n, wave -> RW rows
+    constexpr int RW = R / 4;
+    const int n = tid & 63, rw0 = (tid >> 6) * RW;
+    float acc[RW];
+#pragma unroll
+    for (int i = 0; i < RW; ++i) acc[i] = 0.f;
+    for (int k = 0; k < K; k += 4) {
+        const float w0 = ws[(k + 0) * 65 + n], w1 = ws[(k + 1) * 65 + n], w2 = ws[(k + 2) * 65 + n], w3 = ws[(k + 3) * 65 + n];
+#pragma unroll
+        for (int i = 0; i < RW; ++i) {
+            const f32x4 hv = *reinterpret_cast<const f32x4*>(hs + (size_t)(rw0 + i) * K + k);
+            acc[i] = fmaf(hv[0], w0, acc[i]); acc[i] = fmaf(hv[1], w1, acc[i]); acc[i] = fmaf(hv[2], w2, acc[i]); acc[i] = fmaf(hv[3], w3, acc[i]);
+        }
+    }
+    const float bias = p.bias[n];
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const int r = rw0 + i, b = r0 + r;
+        float y = 0.f, g = 0.f, s = 0.f;
+        if (b < p.B && n < p.A) bc_elem(p.kind, acc[i] + bias, p.act[(size_t)b * p.A + n], p.inv_n, y, g, s);
+        dzt[n * R + r] = g;
+        sq[r * 65 + n] = s;
+        if (b < p.B) { p.pred[(size_t)b * 64 + n] = y; p.dz[(size_t)b * 64 + n] = g; }
+    }
+    __syncthreads();
+    if (tid < R && r0 + tid < p.B) {
+        float s = 0.f;
+        for (int j = 0; j < p.A; ++j) s += sq[tid * 65 + j];
+        st_agent(p.rowsq + r0 + tid, s);
+    }
+    ticket_take(p.ticket, gridDim.x, s_flag);   // the answer is read after the input gradient: the ticket's round trip hides behind it
+    // input gradient: thread -> column k of the hidden layer, all R rows
+    for (int k = tid; k < K; k += 256) {
+        float dxv[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) dxv[r] = 0.f;
+        for (int j = 0; j < p.A; ++j) {
+            const float wv = ws[k * 65 + j];
+#pragma unroll
+            for (int r4 = 0; r4 < R; r4 += 4) {
+                const f32x4 g4 = *reinterpret_cast<const f32x4*>(dzt + j * R + r4);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) dxv[r4 + u] = fmaf(g4[u], wv, dxv[r4 + u]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (r0 + r < p.B) p.dx[(size_t)(r0 + r) * K + k] = hs[(size_t)r * K + k] > 0.f ? dxv[r] : 0.f;
+    }
+    if (ticket_last(s_flag)) bc_finish_loss(p.rowsq, p.B, p.scal, p.accumulate, p.inv_n, red8);
+}
+
+// ---- fused form on the FP32 MFMA ----------------------------------------------------------------------------------------------------
+// The same work as k_bc_head for a block of 32 rows, both products as dense.hpp's 32 x 32 MFMA tiles and the weights read from
+// global memory (L2) instead of staged in LDS.  Forward: NT column tiles (NT = 1 for act_dim <= 32, else 2) through
+// dense_small_tile / dense_small_sum - the tile k_dense_small forms, so z has the general form's bits - then the bias.  Input
+// gradient: wave w owns the 32-column tiles w, w + 4, ... of the hidden layer; A = dz rows from LDS, B = weight rows (contiguous
+// in n), reduced over n ascending in quads, the two lane halves taking alternate quads.
+// Bounds: rows clamped to B - 1 when loaded, stored for b < B only; k < K (K % 64 == 0); n < 32 NT <= 64.
+template <int NT>
+__global__ __launch_bounds__(256) void k_bc_head_mfma(BcHeadArgs p)
+{
+    constexpr int NC = NT * 32;
+    __shared__ float red[4][32][33];
+    __shared__ __attribute__((aligned(16))) float dzs[32][NC + 4];
+    __shared__ float sq[32][NC + 1];
+    __shared__ float red8[8];
+    __shared__ unsigned s_flag;
+    const int K = p.K, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, h = lane >> 5;
+    const int r0 = (int)blockIdx.x * 32;
+    const float* arow = p.h + (size_t)min(r0 + i, p.B - 1) * K;
+    const int r = tid >> 3, c4 = (tid & 7) * 4, b = r0 + r;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        dense_small_tile<false>([&](int k) { return *reinterpret_cast<const f32x4*>(arow + k); }, p.w, 64, t * 32, K, wave, lane, red);
+        __syncthreads();
+        f32x4 y4 = {0.f, 0.f, 0.f, 0.f}, g4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int n = t * 32 + c4 + q;
+            const float z = dense_small_sum(red, r, c4 + q) + p.bias[n];
+            float y = 0.f, g = 0.f, s = 0.f;
+            if (b < p.B && n < p.A) bc_elem(p.kind, z, p.act[(size_t)b * p.A + n], p.inv_n, y, g, s);
+            dzs[r][n] = g; sq[r][n] = s; y4[q] = y; g4[q] = g;
+        }
+        if (b < p.B) {
+            *reinterpret_cast<f32x4*>(p.pred + (size_t)b * 64 + t * 32 + c4) = y4;
+            *reinterpret_cast<f32x4*>(p.dz + (size_t)b * 64 + t * 32 + c4) = g4;
+            if (NT == 1) {   // columns 32 .. 63 of the padded rows: zero (the grouped dW launch reads them)
+                const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+                *reinterpret_cast<f32x4*>(p.pred + (size_t)b * 64 + 32 + c4) = z4;
+                *reinterpret_cast<f32x4*>(p.dz + (size_t)b * 64 + 32 + c4) = z4;
+            }
+        }
+        __syncthreads();   // red is the next tile's
+    }
+    if (tid < 32 && r0 + tid < p.B) {
+        float s = 0.f;
+        for (int j = 0; j < p.A; ++j) s += sq[tid][j];
+        st_agent(p.rowsq + r0 + tid, s);
+    }
+    ticket_take(p.ticket, gridDim.x, &s_flag);   // the answer is read after the input gradient
+    for (int kt = wave; kt < K / 32; kt += 4) {
+        const float* wrow = p.w + (size_t)(kt * 32 + i) * 64;
+        f32x4 av[NC / 8], bv[NC / 8];
+#pragma unroll
+        for (int c = 0; c < NC / 8; ++c) {
+            bv[c] = *reinterpret_cast<const f32x4*>(wrow + 8 * c + 4 * h);
+            av[c] = *reinterpret_cast<const f32x4*>(&dzs[i][8 * c + 4 * h]);
+        }
+        f32x16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC / 8; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c][q], bv[c][q], acc, 0, 0, 0);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int bb = r0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            if (bb < p.B) {
+                const size_t o = (size_t)bb * K + kt * 32 + i;
+                p.dx[o] = p.h[o] > 0.f ? acc[e] : 0.f;
+            }
+        }
+    }
+    if (ticket_last(&s_flag)) bc_finish_loss(p.rowsq, p.B, p.scal, p.accumulate, p.inv_n, red8);
+}
+
+// Policy::sample (bc/base.rs:49-59) from the last layer's pre-activation z [n][ld].  Continuous: out [n][A] = act_out(z).  Discrete:
+// idx [n] = argmax_j act_out(z[b][j]), the lowest index among equal values (candle's tie order is not pinned by anything that can be
+// run against; ReLU outputs tie at 0).
+struct BcActArgs { const float* z; int ld, A, n, kind, discrete; float* out; long long* idx; };
+__global__ __launch_bounds__(256) void k_bc_act(BcActArgs p)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (p.discrete) {
+        if (t >= p.n) return;
+        int best = 0;
+        float bv = bc_act_out(p.kind, p.z[(size_t)t * p.ld]);
+        for (int j = 1; j < p.A; ++j) {
+            const float v = bc_act_out(p.kind, p.z[(size_t)t * p.ld + j]);
+            if (v > bv) { bv = v; best = j; }
+        }
+        p.idx[t] = best;
+        return;
+    }
+    if (t >= p.n * p.A) return;
+    const int b = t / p.A, j = t % p.A;
+    p.out[t] = bc_act_out(p.kind, p.z[(size_t)b * p.ld + j]);
+}
+
+}  // namespace
+
+// ================================================================================================
+struct Bc : bdr_agent {
+    bdr_bc_config cfg;
+    int O = 0, A = 0;
+    MlpLayout net;                     // the policy; its last layer is built without activation (z), act_out is applied by BC's kernels
+    float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;   // arenas: parameters, gradients, exp_avg, exp_avg_sq
+    uint64_t step = 0;
+    int form = BDR_BC_KERNEL_GENERAL; bool head_attr = false; int head_rows = 0; size_t head_lds = 0;
+    // batch buffers
+    int B = 0;
+    float* x0 = nullptr;                        // [B][Kp] padded observations
+    std::vector<float*> act, dy;                // activations (the last: z) and gradients per layer
+    float *pred = nullptr, *rowsq = nullptr, *part = nullptr, *samp = nullptr; long long* samp_idx = nullptr;
+    std::vector<size_t> off;
+    unsigned* ticket = nullptr;
+    float* scal = nullptr;                      // [0] loss
+    float *u_obs = nullptr, *u_act = nullptr; uint64_t u_cap = 0;
+    int last_B = 0;
+
+    enum Life { AGENT, BATCH, STAGING };
+    std::vector<void*> owned[3];
+    template <class T>
+    int32_t alloc(T** q, size_t n, Life life)
+    {
+        const size_t bytes = std::max<size_t>(n, 4) * sizeof(T);
+        BDR_HIP(hipMalloc((void**)q, bytes));
+        owned[life].push_back(*q);
+        BDR_HIP(hipMemsetAsync(*q, 0, bytes, stream));
+        return BDR_OK;
+    }
+    void release(Life life)
+    {
+        for (void* q : owned[life]) (void)hipFree(q);
+        owned[life].clear();
+    }
+    ~Bc() override
+    {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+        for (Life l : {AGENT, BATCH, STAGING}) release(l);
+    }
+    static int chunks_for(int Bn) { return std::max(1, std::min(16, Bn / 256)); }   // rows per dW chunk: k_dense_dw_small_group
+    int32_t ensure_batch(int Bn)
+    {
+        if (Bn <= B) return BDR_OK;
+        BDR_HIP(hipStreamSynchronize(stream));
+        release(BATCH);
+        B = 0;
+        const size_t L = net.L.size();
+        BDR_TRY(alloc(&x0, (size_t)Bn * net.L[0].Kp, BATCH));
+        act.assign(L, nullptr); dy.assign(L, nullptr);
+        for (size_t l = 0; l < L; ++l) { BDR_TRY(alloc(&act[l], (size_t)Bn * net.L[l].Np, BATCH)); BDR_TRY(alloc(&dy[l], (size_t)Bn * net.L[l].Np, BATCH)); }
+        BDR_TRY(alloc(&pred, (size_t)Bn * net.L.back().Np, BATCH));
+        BDR_TRY(alloc(&rowsq, Bn, BATCH));
+        off.clear();
+        size_t o = 0;
+        for (const auto& l : net.L) { off.push_back(o); o += (size_t)chunks_for(Bn) * ((size_t)l.Kp * l.Np + l.Np); }
+        BDR_TRY(alloc(&part, o, BATCH));
+        BDR_TRY(alloc(&samp, (size_t)Bn * A, BATCH));
+        BDR_TRY(alloc(&samp_idx, Bn, BATCH));
+        B = Bn;
+        return BDR_OK;
+    }
+    // layers [0, upto) of Bn rows of x0
+    int32_t forward(int upto, int Bn, const char* name)
+    {
+        DenseSrc in{x0, net.L[0].Kp};
+        const float* pp[1] = {p};
+        for (int l = 0; l < upto; ++l) {
+            float* out[1] = {act[l]};
+            Bracket br(this, name);
+            BDR_TRY(dense_forward_z(stream, net.L[l], 1, pp, &in, out, Bn, true));
+            in = DenseSrc{act[l], net.L[l].Np};
+        }
+        return BDR_OK;
+    }
+    template <int R>
+    int32_t launch_head(const BcHeadArgs& a, int Bn)
+    {
+        if (!head_attr) {   // more than 64 KB of dynamic LDS has to be asked for, once per agent (and so per device)
+            BDR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bc_head<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)head_lds));
+            head_attr = true;
+        }
+        hipLaunchKernelGGL(k_bc_head<R>, dim3((Bn + R - 1) / R), dim3(256), head_lds, stream, a);
+        BDR_HIP(hipGetLastError());
+        return BDR_OK;
+    }
+    // Bc::opt_ (bc/base.rs:167-198) on device-resident rows: obs [Bn][O], data [Bn][A]
+    int32_t update(int Bn, const float* obs, const float* data)
+    {
+        BDR_TRY(ensure_batch(Bn));
+        const int L = (int)net.L.size();
+        const DenseLayer& last = net.L[L - 1];
+        const float inv_n = (float)(1.0 / ((double)Bn * (double)A));
+        { Bracket br(this, "pack"); BDR_TRY(pack_rows(stream, obs, O, O, x0, net.L[0].Kp, 0, Bn)); }
+        int lo;   // input gradients still to form: layers lo .. 1
+        if (form != BDR_BC_KERNEL_GENERAL) {
+            BDR_TRY(forward(L - 1, Bn, "fwd"));
+            BcHeadArgs a{act[L - 2], last.Kp, p + last.w, p + last.b, data, A, Bn, cfg.policy.activation_out,
+                         pred, dy[L - 1], dy[L - 2], rowsq, ticket, scal, 0, inv_n};
+            Bracket br(this, "bc_head");
+            if (form == BDR_BC_KERNEL_FUSED_MFMA) {
+                if (A <= 32) BDR_HIP(step_launch(stream, false, k_bc_head_mfma<1>, dim3((Bn + 31) / 32), dim3(256), a));
+                else BDR_HIP(step_launch(stream, false, k_bc_head_mfma<2>, dim3((Bn + 31) / 32), dim3(256), a));
+            } else {
+                BDR_TRY(head_rows == 8 ? launch_head<8>(a, Bn) : head_rows == 32 ? launch_head<32>(a, Bn) : launch_head<16>(a, Bn));
+            }
+            lo = L - 2;
+        } else {
+            BDR_TRY(forward(L, Bn, "fwd"));
+            BcLossArgs a{act[L - 1], last.Np, data, A, Bn, cfg.policy.activation_out, pred, dy[L - 1], rowsq, ticket, scal, 0, inv_n};
+            Bracket br(this, "bc_loss");
+            BDR_HIP(step_launch(stream, false, k_bc_loss, dim3((Bn + 31) / 32), dim3(256), a));
+            lo = L - 1;
+        }
+        const float* pb[1] = {p};
+        for (int l = lo; l >= 1; --l) {
+            const float* dyl[1] = {dy[l]}; float* dxl[1] = {dy[l - 1]}; const float* mask[1] = {act[l - 1]};
+            Bracket br(this, "dx");
+            BDR_TRY(dense_dx_z(stream, net.L[l], 1, pb, dyl, dxl, mask, Bn, true));
+        }
+        std::vector<DenseDwJob> jobs;
+        const int c = chunks_for(Bn);
+        for (int l = 0; l < L; ++l)
+            jobs.push_back(DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{act[l - 1], net.L[l - 1].Np}, dy[l], part + off[l], c});
+        { Bracket br(this, "dw"); BDR_TRY(dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
+        step += 1;
+        ReduceAdamArgs ra{};
+        ra.nseg = L;
+        for (int l = 0; l < L; ++l) {
+            const DenseLayer& ly = net.L[l];
+            const size_t nfl = (size_t)ly.Kp * ly.Np + ly.Np;
+            ra.seg[l] = DenseReduceSeg{part + off[l], nfl, c, (unsigned)(ly.w / 4), (unsigned)(nfl / 4)};
+        }
+        ra.p[0] = p; ra.g[0] = g; ra.m[0] = m; ra.v[0] = v;
+        ra.s[0] = adam_scalars_for(cfg.opt.opt_kind == BDR_OPT_ADAMW, cfg.lr, cfg.opt.beta1, cfg.opt.beta2, cfg.opt.eps, cfg.opt.weight_decay, step);
+        ra.n4 = (unsigned)(net.total / 4);
+        {
+            Bracket br(this, "reduce_adam");
+            BDR_HIP(step_launch(stream, true, k_dense_reduce_adam, dim3((ra.n4 + 255) / 256, 1), dim3(256), ra));
+        }
+        n_opts += 1;
+        last_B = Bn;
+        return BDR_OK;
+    }
+    int32_t refuse_discrete() const
+    {
+        return cfg.action_type == BDR_BC_ACTION_DISCRETE
+                   ? fail(BDR_ERR_INVALID, "BC has no update for BcActionType::Discrete: the reference's opt_ panics there (bc/base.rs:174)")
+                   : BDR_OK;
+    }
+
+    bool has_train_mode() const override { return false; }   // bc/base.rs:104-112
+    const char* kind() const override { return "bc"; }
+    int32_t opt(bdr_replay* r) override
+    {
+        BDR_TRY(refuse_discrete());
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)O * 4 && r->act_bytes == (uint64_t)A * 4, "replay rows do not match BC obs/act dims (f32 rows)");
+        BDR_REQUIRE(r->device == device, "agent and replay buffer live on different devices");
+        BDR_REQUIRE(!r->frame_stack, "BC reads f32 observation rows, not a frame-stack store");
+        const int Bn = (int)cfg.batch_size;
+        BDR_TRY(ensure_batch(Bn));
+        { Bracket br(this, "sample"); BDR_TRY(replay_sample_on_stream(r, Bn, stream)); }
+        return update(Bn, (const float*)r->b_obs, (const float*)r->b_act);
+    }
+    void record_keys(std::vector<std::string>& keys) override { keys = {"loss"}; }
+    int32_t record(float* out, int cap, int* n) override
+    {
+        if (cap < 1) return fail(BDR_ERR_INVALID, "BC record needs 1 slot");
+        BDR_HIP(hipMemcpyAsync(out, scal, 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        *n = 1;
+        return BDR_OK;
+    }
+
+    // Policy::sample of n observation rows (host rows, or device rows inside sample_device)
+    int32_t sample(uint64_t n, const float* obs, float* act_out, int64_t* idx_out)
+    {
+        const bool disc = cfg.action_type == BDR_BC_ACTION_DISCRETE;
+        BDR_REQUIRE(disc ? idx_out != nullptr : act_out != nullptr, "BC sample: a %s agent writes %s", disc ? "Discrete" : "Continuous", disc ? "idx_out" : "act_out");
+        BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(ensure_batch((int)n));
+        const float* d = nullptr;
+        int32_t st = BDR_OK;
+        if (!obs_rows_on_device && n * O * 4 <= HOST_ROWS_PINNED_MAX) {
+            const uint8_t* pd = nullptr;
+            BDR_TRY(host_rows_pinned(obs, n * O * 4, &pd));
+            d = reinterpret_cast<const float*>(pd);
+        } else {
+            float* stage = nullptr;
+            BDR_TRY(act_buffer(n * O * 4, (void**)&stage));
+            st = stage_obs(stage, obs, (size_t)O * 4, n, stream);
+            d = stage;
+        }
+        if (st == BDR_OK) st = pack_rows(stream, d, O, O, x0, net.L[0].Kp, 0, (int)n);
+        if (st == BDR_OK) st = forward((int)net.L.size(), (int)n, "sample_fwd");
+        if (st == BDR_OK) {
+            BcActArgs a{act.back(), net.L.back().Np, A, (int)n, cfg.policy.activation_out, disc ? 1 : 0, samp, samp_idx};
+            const int tot = disc ? (int)n : (int)n * A;
+            Bracket br(this, "bc_act");
+            const hipError_t e = step_launch(stream, false, k_bc_act, dim3((tot + 255) / 256), dim3(256), a);
+            if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_bc_act: %s", hipGetErrorString(e));
+        }
+        // (an i64 row travels as two f32 words: the copy moves bits)
+        if (st == BDR_OK) st = disc ? rows_to_host(reinterpret_cast<const float*>(samp_idx), reinterpret_cast<float*>(idx_out), n * 2) : rows_to_host(samp, act_out, n * A);
+        slot_cursor = 0;
+        return st;
+    }
+    int32_t sample_device(uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out)
+    {
+        BDR_REQUIRE(row_stride >= (uint64_t)O * 4 && row_stride % 4 == 0, "row_stride must be >= the row size and a multiple of 4");
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(check_device_rows(obs_dev, row_stride));
+        DeviceRowsScope rows(this, row_stride);
+        return sample(n, static_cast<const float*>(obs_dev), act_out, idx_out);
+    }
+    // the compiled trainers take f32 action rows: Continuous only
+    bool sample_f32(uint64_t n, const void* obs, bool on_device, uint64_t stride, float* out, int32_t* st) override
+    {
+        *st = !obs || !out ? fail(BDR_ERR_INVALID, "null argument")
+            : cfg.action_type != BDR_BC_ACTION_CONTINUOUS ? fail(BDR_ERR_INVALID, "the compiled trainers take f32 action rows: a Discrete BC agent is sampled through bdr_bc_sample")
+            : on_device ? sample_device(n, obs, stride, out, nullptr) : sample(n, static_cast<const float*>(obs), out, nullptr);
+        return true;
+    }
+
+    // ---- parameter views: model 0; +100 grad, +200 exp_avg, +300 exp_avg_sq ----
+    float* slot(int which) const
+    {
+        if (which < 0 || which % 100 != 0 || which / 100 > 3) return nullptr;
+        float* r[4] = {p, g, m, v};
+        return r[which / 100];
+    }
+    uint64_t param_count(int which) override { return slot(which) ? net.ref_total : 0; }
+    int32_t get_params(int which, float* out, uint64_t n) override
+    {
+        float* s = slot(which);
+        BDR_REQUIRE(s, "unknown BC model %d", which);
+        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)net.ref_total);
+        std::vector<float> in(net.total);
+        BDR_HIP(hipMemcpyAsync(in.data(), s, net.total * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        mlp_to_reference(net, 0, in.data(), out);
+        return BDR_OK;
+    }
+    int32_t set_params(int which, const float* inp, uint64_t n) override
+    {
+        float* s = slot(which);
+        BDR_REQUIRE(s, "unknown BC model %d", which);
+        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch");
+        std::vector<float> in(net.total, 0.f);
+        mlp_to_internal(net, 0, inp, in.data());
+        BDR_HIP(hipMemcpyAsync(s, in.data(), net.total * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        return BDR_OK;
+    }
+    float* arena(int which, size_t* n) override { float* s = slot(which); if (n) *n = s ? net.total : 0; return s; }
+
+    // ---- checkpoint: policy_model.pt (bc/base.rs:138-153), variables mlp.ln{i}.weight / .bias from the VarMap's root (bc/model.rs:130-133)
+    std::vector<NamedTensor> meta() const
+    {
+        std::vector<NamedTensor> mt;
+        candle::mlp_meta(net, "", mt);
+        return mt;
+    }
+    int32_t save(const char* dir) override
+    {
+        std::vector<float> w(net.ref_total);
+        BDR_TRY(get_params(0, w.data(), w.size()));
+        return save_safetensors_named(candle::ckpt_save_path(ckpt_format, dir, "policy_model"), meta(), w.data(), w.size());
+    }
+    int32_t load(const char* dir) override
+    {
+        std::vector<float> w(net.ref_total);
+        BDR_TRY(load_safetensors_named(candle::ckpt_load_path(ckpt_format, dir, "policy_model"), meta(), w.data(), w.size()));
+        return set_params(0, w.data(), w.size());
+    }
+};
+
+namespace {
+
+constexpr size_t BC_LDS_MAX = 160 * 1024;
+
+int32_t bc_check(const bdr_bc_config& c)
+{
+    BDR_REQUIRE(c.device >= 0, "No device is given for BC agent");
+    BDR_REQUIRE(c.obs_dim >= 1 && c.obs_dim <= 4096 && c.act_dim >= 1 && c.act_dim <= 256, "bad obs/act dims");
+    const bdr_mlp_config& m = c.policy;
+    BDR_REQUIRE(m.n_units >= 0 && m.n_units <= BDR_MAX_UNITS, "policy: bad layer count");
+    for (int i = 0; i < m.n_units; ++i) BDR_REQUIRE(m.units[i] >= 1 && m.units[i] <= 4096, "policy: bad layer width");
+    BDR_REQUIRE(m.activation_out >= BDR_ACTIVATION_NONE && m.activation_out <= BDR_ACTIVATION_SIGMOID, "policy: unknown activation_out %d", m.activation_out);
+    BDR_REQUIRE(c.action_type == BDR_BC_ACTION_DISCRETE || c.action_type == BDR_BC_ACTION_CONTINUOUS, "unknown BC action type %d", c.action_type);
+    BDR_REQUIRE(c.batch_size >= 1 && c.batch_size <= 65536, "bad batch size");
+    BDR_TRY(check_opt(c.opt, "policy"));
+    BDR_REQUIRE(c.kernel_form >= BDR_BC_KERNEL_DEFAULT && c.kernel_form <= BDR_BC_KERNEL_FUSED_MFMA, "unknown BC kernel form %d", c.kernel_form);
+    BDR_REQUIRE(c.head_rows == 0 || c.head_rows == 8 || c.head_rows == 16 || c.head_rows == 32, "head_rows must be 0, 8, 16 or 32");
+    return BDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void bdr_bc_config_default(bdr_bc_config* c)
+{
+    if (!c) return;
+    memset(c, 0, sizeof *c);
+    // bc/config.rs:66-75
+    c->batch_size = 1; c->action_type = BDR_BC_ACTION_DISCRETE; c->device = -1; c->record_verbose_level = 0;
+    c->policy.activation_out = BDR_ACTIVATION_NONE;
+    // BcModelConfig (bc/model.rs:33-43): opt_config = OptimizerConfig::default() = AdamW with candle's ParamsAdamW defaults (opt.rs:100-111)
+    c->lr = 1e-3;
+    c->opt.opt_kind = BDR_OPT_ADAMW; c->opt.beta1 = 0.9; c->opt.beta2 = 0.999; c->opt.weight_decay = 0.01; c->opt.eps = 1e-8;
+    c->kernel_form = BDR_BC_KERNEL_DEFAULT;
+}
+
+int32_t bdr_bc_create(const bdr_bc_config* cfg, bdr_agent** out)
+{
+    BDR_REQUIRE(cfg && out, "null argument");
+    const bdr_bc_config& c = *cfg;
+    BDR_TRY(bc_check(c));
+    MlpLayout net = make_mlp(c.obs_dim, c.policy.units, c.policy.n_units, c.act_dim, false);
+    // the fused head: one padded column block, a hidden layer under it, and its LDS plan within the CU's 160 KB
+    const int R = c.head_rows ? c.head_rows : BC_HEAD_ROWS_DEFAULT;
+    const bool can_fuse = c.act_dim <= 64 && c.policy.n_units >= 1 && bc_head_lds(net.L.back().Kp, R) <= BC_LDS_MAX;
+    BDR_REQUIRE(c.kernel_form != BDR_BC_KERNEL_FUSED || can_fuse,
+                "the fused BC head needs act_dim <= 64, a hidden layer, and the last layer's weights plus %d rows within 160 KB of LDS "
+                "(act_dim %d, %d hidden layers, last hidden width %d): use BDR_BC_KERNEL_GENERAL", R, c.act_dim, c.policy.n_units,
+                c.policy.n_units ? c.policy.units[c.policy.n_units - 1] : 0);
+    const bool can_mfma = c.act_dim <= 64 && c.policy.n_units >= 1;
+    BDR_REQUIRE(c.kernel_form != BDR_BC_KERNEL_FUSED_MFMA || can_mfma,
+                "the fused BC head needs act_dim <= 64 and a hidden layer (act_dim %d, %d hidden layers): use BDR_BC_KERNEL_GENERAL", c.act_dim, c.policy.n_units);
+    BDR_TRY(ensure_device(c.device));
+    Bc* a = new Bc();
+    a->cfg = c; a->device = c.device; a->train = false;
+    a->O = c.obs_dim; a->A = c.act_dim; a->net = net;
+    a->form = c.kernel_form != BDR_BC_KERNEL_DEFAULT ? c.kernel_form : bc_default_form((int)c.batch_size, can_mfma);
+    a->head_rows = R; a->head_lds = bc_head_lds(net.L.back().Kp, R);
+    const int32_t st = [&]() -> int32_t {
+        BDR_HIP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
+        BDR_TRY(a->err_init());
+        for (auto q : {&a->p, &a->g, &a->m, &a->v}) BDR_TRY(a->alloc(q, net.total, Bc::AGENT));
+        BDR_TRY(a->alloc(&a->scal, 4, Bc::AGENT));
+        BDR_TRY(a->alloc(&a->ticket, 4, Bc::AGENT));
+        std::vector<float> ref(net.ref_total, 0.f);
+        mlp_init_reference(net, c.seed * 7 + 1, ref.data());
+        BDR_TRY(a->set_params(0, ref.data(), ref.size()));
+        return a->ensure_batch((int)c.batch_size);
+    }();
+    if (st != BDR_OK) { delete a; return st; }
+    *out = a;
+    return BDR_OK;
+}
+
+int32_t bdr_bc_update_on_batch(bdr_agent* base, uint64_t n, const float* obs, const float* act, float* rec_out)
+{
+    BDR_REQUIRE(base && obs && act, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "bc"), "not a BC agent");
+    Bc* a = static_cast<Bc*>(base);
+    BDR_TRY(a->refuse_discrete());
+    BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+    BDR_HIP(hipSetDevice(a->device));
+    BDR_TRY(a->ensure_batch((int)n));
+    if (n > a->u_cap) {
+        BDR_HIP(hipStreamSynchronize(a->stream));
+        a->release(Bc::STAGING);
+        a->u_cap = 0;
+        BDR_TRY(a->alloc(&a->u_obs, n * a->O, Bc::STAGING)); BDR_TRY(a->alloc(&a->u_act, n * a->A, Bc::STAGING));
+        a->u_cap = n;
+    }
+    BDR_HIP(hipMemcpyAsync(a->u_obs, obs, n * a->O * 4, hipMemcpyHostToDevice, a->stream));
+    BDR_HIP(hipMemcpyAsync(a->u_act, act, n * a->A * 4, hipMemcpyHostToDevice, a->stream));
+    BDR_TRY(a->update((int)n, a->u_obs, a->u_act));
+    prof_collect(a);
+    if (rec_out) BDR_HIP(hipMemcpyAsync(rec_out, a->scal, 4, hipMemcpyDeviceToHost, a->stream));
+    BDR_HIP(hipStreamSynchronize(a->stream));
+    return a->err_check();
+}
+
+// Parity probes of the LAST update (see include/border_amd.h)
+int32_t bdr_bc_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
+{
+    BDR_REQUIRE(base && out, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "bc"), "not a BC agent");
+    Bc* a = static_cast<Bc*>(base);
+    BDR_HIP(hipSetDevice(a->device));
+    const int Bn = a->last_B;
+    BDR_REQUIRE(Bn > 0, "no update has run yet");
+    BDR_REQUIRE(what == 0 || what == 1, "unknown BC probe %d", what);
+    BDR_REQUIRE(n == (uint64_t)Bn * a->A, "this probe holds batch x act_dim values");
+    BDR_HIP(hipStreamSynchronize(a->stream));
+    const int ld = a->net.L.back().Np;
+    std::vector<float> h((size_t)Bn * ld);
+    BDR_HIP(hipMemcpy(h.data(), what == 0 ? a->pred : a->dy.back(), h.size() * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < Bn; ++b) memcpy(out + (size_t)b * a->A, h.data() + (size_t)b * ld, (size_t)a->A * 4);
+    return BDR_OK;
+}
+
+int32_t bdr_bc_sample(bdr_agent* base, uint64_t n, const float* obs, float* act_out, int64_t* idx_out)
+{
+    BDR_REQUIRE(base && obs, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "bc"), "not a BC agent");
+    return static_cast<Bc*>(base)->sample(n, obs, act_out, idx_out);
+}
+
+int32_t bdr_bc_sample_device(bdr_agent* base, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out)
+{
+    BDR_REQUIRE(base && obs_dev, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "bc"), "not a BC agent");
+    return static_cast<Bc*>(base)->sample_device(n, obs_dev, row_stride, act_out, idx_out);
+}
+
+}  // extern "C"

@@ -75,6 +75,33 @@ __device__ __forceinline__ float acc(float base, float s, float scale)   // base
     return base + t;
 }
 
+
+// ---- checkpoints of candle VarMaps (host) ----
+// the variables of an Mlp under `prefix`: mlp.ln{i}.weight [out][in], mlp.ln{i}.bias [out]
+inline void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt)
+{
+    for (size_t i = 0; i < net.L.size(); ++i) {
+        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)net.L[i].out, (uint64_t)net.L[i].in}});
+        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)net.L[i].out}});
+    }
+}
+// candle's VarMap::save writes safetensors whatever the extension: "<stem>.pt" (default, the reference's files) or "<stem>.safetensors"
+inline std::string ckpt_save_path(int32_t ckpt_format, const char* dir, const char* stem)
+{
+    return std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt");
+}
+// ... and the load path falls back to the other extension when only that file exists
+inline std::string ckpt_load_path(int32_t ckpt_format, const char* dir, const char* stem)
+{
+    const std::string first = ckpt_save_path(ckpt_format, dir, stem);
+    const std::string second = std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".pt" : ".safetensors");
+    FILE* f = fopen(first.c_str(), "rb");
+    if (f) { fclose(f); return first; }
+    f = fopen(second.c_str(), "rb");
+    if (f) { fclose(f); return second; }
+    return first;
+}
+
 }  // namespace candle
 }  // namespace bdr
 
@@ -458,13 +485,7 @@ struct CandleAgent : bdr_agent {
     float* arena(int which, size_t* n) override { Slot s = slot(which); if (n) *n = s.n; return s.p; }
 
     // ---- checkpoints: actor.pt, critic.pt, critic.tgt.pt ----
-    static void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt)
-    {
-        for (size_t i = 0; i < net.L.size(); ++i) {
-            mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)net.L[i].out, (uint64_t)net.L[i].in}});
-            mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)net.L[i].out}});
-        }
-    }
+    static void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt) { candle::mlp_meta(net, prefix, mt); }
     std::vector<NamedTensor> actor_meta() const
     {
         std::vector<NamedTensor> mt;
@@ -478,18 +499,8 @@ struct CandleAgent : bdr_agent {
         for (int i = 0; i < NC; ++i) mlp_meta(qn, "critic" + std::to_string(i) + ".", mt);
         return mt;
     }
-    // candle's VarMap::save writes safetensors whatever the extension: "<stem>.pt" (default, the reference's files) or "<stem>.safetensors"
-    std::string save_path(const char* dir, const char* stem) const { return std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt"); }
-    std::string load_path(const char* dir, const char* stem) const
-    {
-        const std::string first = save_path(dir, stem);
-        const std::string second = std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".pt" : ".safetensors");
-        FILE* f = fopen(first.c_str(), "rb");
-        if (f) { fclose(f); return first; }
-        f = fopen(second.c_str(), "rb");
-        if (f) { fclose(f); return second; }
-        return first;
-    }
+    std::string save_path(const char* dir, const char* stem) const { return candle::ckpt_save_path(ckpt_format, dir, stem); }
+    std::string load_path(const char* dir, const char* stem) const { return candle::ckpt_load_path(ckpt_format, dir, stem); }
     int32_t save(const char* dir) override
     {
         std::vector<float> v(param_count(0));

@@ -22,7 +22,7 @@ from . import _lib
 from .dqn import OptimizerConfig
 from .replay import SimpleReplayBuffer
 
-ACTIVATIONS = {"None": 0, "ReLU": 1, "Tanh": 2, "Sigmoid": 3}   # lib.rs:58-63 (Tanh / Sigmoid are rejected by the library)
+ACTIVATIONS = {"None": 0, "ReLU": 1, "Tanh": 2, "Sigmoid": 3}   # lib.rs:58-63 (Tanh / Sigmoid: BC only; IQL and AWAC reject them)
 
 
 @dataclass

@@ -728,7 +728,7 @@ BDR_API int32_t bdr_sac_sample_device(bdr_agent* a, uint64_t n, const void* obs_
 enum { BDR_ACTIVATION_NONE = 0, BDR_ACTIVATION_RELU = 1, BDR_ACTIVATION_TANH = 2, BDR_ACTIVATION_SIGMOID = 3 };   /* lib.rs:58-63 Activation */
 enum { BDR_ACTION_LIMIT_CLAMP = 0, BDR_ACTION_LIMIT_TANH = 1 };                                                /* util/actor.rs:29-32 ActionLimit */
 
-/* MlpConfig of border-candle-agent (mlp/config.rs:6-11).  activation_out: BDR_ACTIVATION_NONE / _RELU (Tanh / Sigmoid: BDR_ERR_INVALID).
+/* MlpConfig of border-candle-agent (mlp/config.rs:6-11).  activation_out: BDR_ACTIVATION_NONE / _RELU (Tanh / Sigmoid: BDR_ERR_INVALID); BC: all four.
  * The actor's Mlp3 ignores activation_out, as the reference does (mlp3.rs: mlp_forward(.., &Activation::None)). */
 typedef struct {
     int32_t n_units;
@@ -851,6 +851,53 @@ BDR_API int32_t bdr_awac_sample(bdr_agent* a, uint64_t n, const float* obs, floa
 BDR_API int32_t bdr_awac_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
 
 /* ------------------------------------------------------------------------------------------
+ * BC agent  (border-candle-agent/src/bc/{base.rs,config.rs,model.rs}; behaviour cloning, offline)
+ * Policy = Mlp (mlp/base.rs, mlp.rs:14-24): ReLU after every layer but the last, activation_out (all four BDR_ACTIVATION_*)
+ * after the last.  No critic, no target, no noise.
+ * ---------------------------------------------------------------------------------------- */
+enum { BDR_BC_ACTION_DISCRETE = 0, BDR_BC_ACTION_CONTINUOUS = 1 };   /* bc/config.rs BcActionType */
+/* How one update is launched.  GENERAL: the last layer's forward, k_bc_loss and the last layer's input gradient as three launches
+ * (any out_dim).  FUSED: k_bc_head does the three in one row-block launch; it needs act_dim <= 64, at least one hidden layer and a
+ * last hidden layer of at most 384 units (its weights are staged in LDS), else bdr_bc_create returns BDR_ERR_INVALID.  FUSED_MFMA:
+ * the same launch with both products on the FP32 MFMA and the weights read from L2 (k_bc_head_mfma; act_dim <= 64, a hidden layer).  DEFAULT:
+ * FUSED_MFMA where it applies and batch_size <= 1024 (measured at the bc_pen shape: profiles/bench_bc_pen.json), GENERAL elsewhere. */
+enum { BDR_BC_KERNEL_DEFAULT = 0, BDR_BC_KERNEL_GENERAL = 1, BDR_BC_KERNEL_FUSED = 2, BDR_BC_KERNEL_FUSED_MFMA = 3 };
+/* BcConfig (bc/config.rs:66-75) with BcModelConfig (bc/model.rs): policy_model_config.{policy_model_config, opt_config}.
+ * amsgrad is rejected, as for IQL. */
+typedef struct {
+    int32_t obs_dim, act_dim;
+    bdr_mlp_config policy;        /* BcModelConfig.policy_model_config; activation_out: None / ReLU / Tanh / Sigmoid */
+    bdr_adamw_config opt;         /* BcModelConfig.opt_config */
+    double lr;
+    uint64_t batch_size;          /* 1 */
+    int32_t action_type;          /* BDR_BC_ACTION_* (Discrete) */
+    int32_t device;               /* -1: none given */
+    int32_t record_verbose_level; /* 0 */
+    int32_t kernel_form;          /* BDR_BC_KERNEL_* (Default) */
+    int32_t head_rows;            /* rows per workgroup of k_bc_head: 0 (the measured default), 8, 16 or 32 */
+    int32_t reserved;
+    uint64_t seed;                /* the library's parameter initialiser */
+} bdr_bc_config;
+BDR_API void bdr_bc_config_default(bdr_bc_config* cfg);                    /* bc/config.rs:66-75 */
+BDR_API int32_t bdr_bc_create(const bdr_bc_config* cfg, bdr_agent** out);  /* bc/base.rs:126-136 (Configurable::build) */
+/* One Bc::opt_ (bc/base.rs:167-198) on a host minibatch: loss = mean over all n x act_dim elements of (policy(obs) - act)^2,
+ * backward, one optimizer step.  rec_out (may be NULL): 1 float, "loss".  A Discrete agent returns BDR_ERR_INVALID (the reference
+ * panics, bc/base.rs:174).
+ * Parameter models for bdr_agent_{get,set}_params / param_count_of: 0 the policy (mlp.ln{k}.weight, mlp.ln{k}.bias ...); +100
+ * gradient, +200 exp_avg, +300 exp_avg_sq.  SyncModel ships model 0.  Checkpoint: policy_model.pt (safetensors, as candle writes it).
+ * bdr_agent_set_train is accepted and bdr_agent_is_train answers false (bc/base.rs:104-112). */
+BDR_API int32_t bdr_bc_update_on_batch(bdr_agent* a, uint64_t n, const float* obs, const float* act, float* rec_out);
+/* Parity probes: intermediates of the LAST BC update, to the host.  what:
+ *   0 pred [B][act_dim]   the network output, output activation applied     1 dz [B][act_dim]   dLoss / d(last pre-activation) */
+BDR_API int32_t bdr_bc_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* Policy::sample (bc/base.rs:49-59).  Continuous: act_out [n][act_dim] = the network output, idx_out NULL.  Discrete: idx_out [n] =
+ * argmax over the last dimension (the lowest index among equal values; candle's tie order is not pinned by anything that can be
+ * run against), act_out NULL. */
+BDR_API int32_t bdr_bc_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out, int64_t* idx_out);
+/* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
+BDR_API int32_t bdr_bc_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU parameter exchange (replaces the learner->actors NamedTensors channel of
  * border-async-trainer/src/async_trainer/base.rs:268-272 with RCCL over xGMI).
  * ---------------------------------------------------------------------------------------- */
@@ -865,7 +912,7 @@ BDR_API int32_t bdr_comm_agree(bdr_comm* c, int32_t local_ok, int32_t* all_ok);
 /* params <- mean over ranks (ncclAllReduce sum on the flat arena, then 1/nranks), on the
  * agent's stream; which as in bdr_agent_get_params (0 qnet, 1 qnet_tgt, 2/3 Adam moments). */
 BDR_API int32_t bdr_agent_allreduce_params(bdr_agent* a, bdr_comm* c, int32_t which);
-/* Synchronous data-parallel mode for DQN agents (an IQL or AWAC agent returns BDR_ERR_INVALID): from now on every Agent::opt of `a` runs backward, all-reduces the gradient
+/* Synchronous data-parallel mode for DQN agents (an IQL, AWAC or BC agent returns BDR_ERR_INVALID): from now on every Agent::opt of `a` runs backward, all-reduces the gradient
  * arena over `c` (ncclAllReduce sum, then 1/nranks, on the agent's stream) and then takes the optimizer step, so the ranks
  * stay bit-for-bit in lock step and N x batch B/N equals one step on batch B.  c == NULL: back to independent steps. */
 BDR_API int32_t bdr_agent_set_grad_comm(bdr_agent* a, bdr_comm* c);

@@ -1239,3 +1239,142 @@ impl AwacConfig {
         Ok(c)
     }
 }
+
+/// `bc::BcActionType` (`bc/config.rs`).
+#[derive(Clone, Copy, Debug, Deserialize, Serialize, PartialEq)]
+pub enum BcActionType {
+    Discrete,
+    Continuous,
+}
+
+/// How one BC update is launched (`BDR_BC_KERNEL_*`, include/border_amd.h).  NOT a reference field; absent in a reference YAML
+/// (-> the library default).
+#[derive(Clone, Copy, Debug, Deserialize, Serialize, PartialEq, Default)]
+pub enum BcKernelForm {
+    #[default]
+    Default,
+    General,
+    Fused,
+    FusedMfma,
+}
+
+/// `bc::BcModelConfig<MlpConfig>` (`bc/model.rs:24-43`): the policy Mlp and its optimizer (default: `OptimizerConfig::default()`,
+/// AdamW with candle's `ParamsAdamW` defaults, `opt.rs:100-111`).
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct BcModelConfig {
+    pub policy_model_config: Option<CandleMlpConfig>,
+    #[serde(default = "bc_opt_default")]
+    pub opt_config: CandleOptimizerConfig,
+}
+
+fn bc_opt_default() -> CandleOptimizerConfig {
+    CandleOptimizerConfig::AdamW { lr: 0.001, beta1: 0.9, beta2: 0.999, eps: 1e-8, weight_decay: 0.01 }
+}
+
+impl Default for BcModelConfig {
+    fn default() -> Self {
+        Self { policy_model_config: None, opt_config: bc_opt_default() }
+    }
+}
+
+impl BcModelConfig {
+    pub fn policy_model_config(mut self, v: CandleMlpConfig) -> Self {
+        self.policy_model_config = Some(v);
+        self
+    }
+
+    pub fn opt_config(mut self, v: CandleOptimizerConfig) -> Self {
+        self.opt_config = v;
+        self
+    }
+
+    /// `BcModelConfig::out_dim` (`bc/model.rs:56-62`).
+    pub fn out_dim(mut self, v: i64) -> Self {
+        if let Some(c) = &mut self.policy_model_config {
+            c.out_dim = v;
+        }
+        self
+    }
+}
+
+/// `bc::BcConfig<P>` (`bc/config.rs:20-75`) with the reference's field names; `phantom` is accepted and ignored.  `engine_seed`,
+/// `kernel_form` and `head_rows` are not reference fields: the library's parameter initialiser, the launch form of one update and
+/// the row block of the fused head (0: the measured default).
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct BcConfig {
+    pub policy_model_config: BcModelConfig,
+    pub batch_size: usize,
+    pub action_type: BcActionType,
+    pub device: Option<Device>,
+    pub record_verbose_level: usize,
+    #[serde(default, skip_serializing)]
+    pub phantom: Option<()>,
+    #[serde(default)]
+    pub engine_seed: u64,
+    #[serde(default)]
+    pub kernel_form: BcKernelForm,
+    #[serde(default)]
+    pub head_rows: usize,
+}
+
+impl Default for BcConfig {
+    fn default() -> Self {
+        Self {
+            policy_model_config: Default::default(),
+            batch_size: 1,
+            action_type: BcActionType::Discrete,
+            device: None,
+            record_verbose_level: 0,
+            phantom: None,
+            engine_seed: 0,
+            kernel_form: BcKernelForm::Default,
+            head_rows: 0,
+        }
+    }
+}
+
+impl BcConfig {
+    setter!(batch_size, usize);
+    setter!(policy_model_config, BcModelConfig);
+    setter!(action_type, BcActionType);
+    setter!(record_verbose_level, usize);
+    yaml_io!();
+
+    /// `BcConfig::out_dim` (`bc/config.rs`): the policy's output dimension.
+    pub fn out_dim(mut self, v: i64) -> Self {
+        self.policy_model_config = self.policy_model_config.out_dim(v);
+        self
+    }
+
+    pub fn device(mut self, device: Device) -> Self {
+        self.device = Some(device);
+        self
+    }
+
+    pub(crate) fn to_c(&self) -> Result<ffi::bdr_bc_config> {
+        let mut c: ffi::bdr_bc_config = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_bc_config_default(&mut c) };
+        let p = self.policy_model_config.policy_model_config.as_ref().ok_or_else(|| anyhow!("policy_model_config is not set."))?;
+        c.obs_dim = p.in_dim as i32;
+        c.act_dim = p.out_dim as i32;
+        p.fill(&mut c.policy, "policy_model_config")?;
+        c.lr = self.policy_model_config.opt_config.lr();
+        self.policy_model_config.opt_config.fill(&mut c.opt);
+        c.batch_size = self.batch_size as u64;
+        c.action_type = match self.action_type {
+            BcActionType::Discrete => ffi::BDR_BC_ACTION_DISCRETE,
+            BcActionType::Continuous => ffi::BDR_BC_ACTION_CONTINUOUS,
+        };
+        c.record_verbose_level = self.record_verbose_level as i32;
+        c.kernel_form = match self.kernel_form {
+            BcKernelForm::Default => ffi::BDR_BC_KERNEL_DEFAULT,
+            BcKernelForm::General => ffi::BDR_BC_KERNEL_GENERAL,
+            BcKernelForm::Fused => ffi::BDR_BC_KERNEL_FUSED,
+            BcKernelForm::FusedMfma => ffi::BDR_BC_KERNEL_FUSED_MFMA,
+        };
+        c.head_rows = self.head_rows as i32;
+        c.seed = self.engine_seed;
+        c.device = Device::ordinal(&self.device, "BC");
+        Ok(c)
+    }
+}

@@ -31,6 +31,12 @@ pub const BDR_ACTIVATION_TANH: i32 = 2;
 pub const BDR_ACTIVATION_SIGMOID: i32 = 3;
 pub const BDR_ACTION_LIMIT_CLAMP: i32 = 0;
 pub const BDR_ACTION_LIMIT_TANH: i32 = 1;
+pub const BDR_BC_ACTION_DISCRETE: i32 = 0;
+pub const BDR_BC_ACTION_CONTINUOUS: i32 = 1;
+pub const BDR_BC_KERNEL_DEFAULT: i32 = 0;
+pub const BDR_BC_KERNEL_GENERAL: i32 = 1;
+pub const BDR_BC_KERNEL_FUSED: i32 = 2;
+pub const BDR_BC_KERNEL_FUSED_MFMA: i32 = 3;
 pub const BDR_MAX_UNITS: usize = 8;
 pub const BDR_EXPLORER_SOFTMAX: i32 = 0;
 pub const BDR_EXPLORER_EPS_GREEDY: i32 = 1;
@@ -506,6 +512,25 @@ pub struct bdr_awac_config {
     pub seed: u64,
 }
 
+/// BcConfig (bc/config.rs:66-75) + BcModelConfig (bc/model.rs)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bdr_bc_config {
+    pub obs_dim: i32,
+    pub act_dim: i32,
+    pub policy: bdr_mlp_config,
+    pub opt: bdr_adamw_config,
+    pub lr: f64,
+    pub batch_size: u64,
+    pub action_type: i32,
+    pub device: i32,
+    pub record_verbose_level: i32,
+    pub kernel_form: i32,
+    pub head_rows: i32,
+    pub reserved: i32,
+    pub seed: u64,
+}
+
 #[link(name = "border_amd")]
 extern "C" {
     pub fn bdr_last_error() -> *const c_char;
@@ -779,6 +804,21 @@ extern "C" {
     pub fn bdr_awac_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_awac_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
     pub fn bdr_awac_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
+
+    // ---- BC (border-candle-agent/src/bc)
+    pub fn bdr_bc_config_default(cfg: *mut bdr_bc_config);
+    pub fn bdr_bc_create(cfg: *const bdr_bc_config, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_bc_update_on_batch(a: *mut bdr_agent, n: u64, obs: *const f32, act: *const f32, rec_out: *mut f32) -> i32;
+    pub fn bdr_bc_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
+    pub fn bdr_bc_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32, idx_out: *mut i64) -> i32;
+    pub fn bdr_bc_sample_device(
+        a: *mut bdr_agent,
+        n: u64,
+        obs_dev: *const c_void,
+        row_stride: u64,
+        act_out: *mut f32,
+        idx_out: *mut i64,
+    ) -> i32;
 
     // ---- multi-GPU parameter exchange (RCCL over xGMI)
     pub fn bdr_comm_get_unique_id(id: *mut u8) -> i32;

@@ -12,6 +12,7 @@
 //!   and serde layout ([`config`]), so the example YAML files load unchanged.
 //! * [`AmdIql`] - `border-candle-agent/src/iql/base.rs` (offline RL; [`IqlConfig`] deserialises the candle YAML names).
 //! * [`AmdAwac`] - `border-candle-agent/src/awac/base.rs` (offline and online RL; [`AwacConfig`] likewise).
+//! * [`AmdBc`] - `border-candle-agent/src/bc/base.rs` (behaviour cloning; [`BcConfig`] likewise).
 //! * [`train_async`] - `border-async-trainer/src/util.rs:31-92` on one GPU (learner + actors + device mailbox), with the
 //!   optional cross-GPU exchange over RCCL ([`Comm`]).
 //!
@@ -20,6 +21,7 @@
 //! and keeps its `Trainer::build(config).train(env, step_proc, &mut agent, &mut buffer, ...)` call.
 pub mod async_trainer;
 pub mod awac;
+pub mod bc;
 pub mod bytes;
 pub mod comm;
 pub mod config;
@@ -38,9 +40,10 @@ pub use comm::Comm;
 pub use config::{
     ActionLimit, Activation, CandleMlpConfig, CandleOptimizerConfig, GaussianActorConfig, MultiCriticConfig, ValueConfig,
     ActorConfig, AtariCnnConfig, CriticConfig, CriticLoss, Device, DqnConfig, DqnExplorer, DqnModelConfig, EntCoefMode, EpsilonGreedy,
-    Arithmetic, AwacConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
+    Arithmetic, AwacConfig, BcActionType, BcConfig, BcKernelForm, BcModelConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
 };
 pub use awac::AmdAwac;
+pub use bc::AmdBc;
 pub use dqn::AmdDqn;
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;
