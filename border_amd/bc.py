@@ -14,7 +14,6 @@ kernel_form picks how one update is launched: "default", "general" (three launch
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -22,8 +21,7 @@ import numpy as np
 
 from . import _lib
 from .dqn import OptimizerConfig
-from .iql import ROLES, CandleMlpConfig, _p
-from .replay import SimpleReplayBuffer
+from .iql import ROLES, AgentHandle, CandleMlpConfig, _p  # noqa: F401  (ROLES: importable from here as before)
 
 
 class BcActionType:
@@ -68,66 +66,20 @@ class BcConfig:
         return c
 
 
-class Bc:
-    """bc/base.rs; checkpoint (bc/base.rs:138-153): policy_model."""
+class Bc(AgentHandle):
+    """bc/base.rs; checkpoint (bc/base.rs:138-153): policy_model.pt, or policy_model.safetensors (set_checkpoint_format).
+    train() / eval() switch nothing (bc/base.rs:104-106)."""
     KIND = "bc"
     CKPT_STEMS = ("policy_model",)
+    SYNC_MODEL = "policy"
     WHICH = {"policy": 0, "actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the policy == model 0
     PROBES = {"pred": 0, "dz": 1}
-
-    def __init__(self, config: BcConfig):
-        self.config = config
-        h = C.c_void_p()
-        c = config.to_c()
-        _lib.check(_lib.lib().bdr_bc_create(C.byref(c), C.byref(h)))
-        self._h = h
-
-    @classmethod
-    def build(cls, config):
-        return cls(config)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().bdr_agent_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    def which(self, name: str = "policy", role: str = "param") -> int:
-        return self.WHICH[name] + ROLES[role]
-
-    def arena_device_ptr(self, which="policy"):
-        ptr, n = C.c_void_p(), C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
-        return ptr.value, n.value
-
-    def train(self):
-        """bc/base.rs:104-106: nothing to switch"""
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 1))
-
-    def eval(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 0))
 
     def is_train(self) -> bool:
         """bc/base.rs:110-112: always False"""
         out = C.c_int32()
         _lib.check(_lib.lib().bdr_agent_is_train(self._h, C.byref(out)))
         return bool(out.value)
-
-    def opt(self, buffer: SimpleReplayBuffer) -> None:
-        _lib.check(_lib.lib().bdr_agent_opt(self._h, buffer.handle))
-
-    def opt_with_record(self, buffer: SimpleReplayBuffer) -> dict:
-        from .dqn import opt_with_named_record
-        return opt_with_named_record(self._h, buffer)
 
     def update_on_batch(self, obs, act) -> dict:
         """One Bc::opt_ (bc/base.rs:167-198) on host rows; the record's one key is "loss"."""
@@ -146,9 +98,6 @@ class Bc:
         _lib.check(_lib.lib().bdr_bc_probe(self._h, self.PROBES[what], _p(out), out.size))
         return out
 
-    def profile_enable(self, on: bool = True):
-        _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
-
     def _out(self, n: int):
         if self.config.action_type == BcActionType.Discrete:
             return np.empty(n, np.int64), True
@@ -166,48 +115,3 @@ class Bc:
         _lib.check(_lib.lib().bdr_bc_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, None if disc else _p(out),
                                                    _p(out) if disc else None))
         return out
-
-    def sync(self):
-        _lib.check(_lib.lib().bdr_agent_sync(self._h))
-
-    @property
-    def n_opts(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
-        return n.value
-
-    def param_count(self, name="policy") -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_param_count_of(self._h, self.which(name), C.byref(n)))
-        return n.value
-
-    def get_params(self, name="policy", role="param") -> np.ndarray:
-        out = np.empty(self.param_count(name), np.float32)
-        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.which(name, role), _p(out), out.size))
-        return out
-
-    def set_params(self, params, name="policy", role="param") -> None:
-        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
-        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.which(name, role), _p(p), p.size))
-
-    def model_info(self):
-        """SyncModel::model_info: the policy's parameters."""
-        return self.n_opts, self.get_params()
-
-    def sync_model(self, model_info) -> None:
-        self.set_params(model_info)
-
-    def set_checkpoint_format(self, fmt: str) -> None:
-        """"tch" (default): `policy_model.pt` (safetensors, as candle's VarMap writes it); "safetensors": `policy_model.safetensors`."""
-        from .checkpoint import FORMATS
-        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
-        self._ckpt_ext = {"tch": ".pt", "safetensors": ".safetensors"}[fmt]
-
-    def save_params(self, path: str):
-        os.makedirs(path, exist_ok=True)
-        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
-        ext = getattr(self, "_ckpt_ext", ".pt")
-        return [os.path.join(path, stem + ext) for stem in self.CKPT_STEMS]
-
-    def load_params(self, path: str):
-        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))

@@ -285,6 +285,16 @@ struct bdr_agent {
         else BDR_HIP(hipMemcpy2DAsync(dst, row_bytes, src, obs_row_stride, row_bytes, n, hipMemcpyDeviceToDevice, st));
         return BDR_OK;
     }
+    // The n observation rows of an acting call as contiguous device-readable memory: host rows of up to HOST_ROWS_PINNED_MAX bytes
+    // through the pinned area (read in place by the packing kernel), anything else through the staging buffer on the agent's stream
+    int32_t acting_rows(const void* rows, size_t row_bytes, uint64_t n, const uint8_t** dev)
+    {
+        if (!obs_rows_on_device && n * row_bytes <= HOST_ROWS_PINNED_MAX) return host_rows_pinned(rows, n * row_bytes, dev);
+        void* stage = nullptr;
+        BDR_TRY(act_buffer(n * row_bytes, &stage));
+        *dev = static_cast<const uint8_t*>(stage);
+        return stage_obs(stage, rows, row_bytes, n, stream);
+    }
     // the rows can be read in place (device rows that are already contiguous)
     bool obs_in_place(size_t row_bytes) const { return obs_rows_on_device && obs_row_stride == row_bytes; }
     virtual const char* kind() const = 0;

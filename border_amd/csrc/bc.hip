@@ -4,7 +4,9 @@
 // critic, no target, no noise; the record holds "loss" (:191-193).  Policy::sample (:49-59): Continuous returns the network output,
 // Discrete the argmax over the last dimension as i64; the Discrete update is a panic in the reference (:174) and an error here.
 // train() / eval() do nothing and is_train() is false (:104-112).
-// Hidden layers, the grouped weight gradient and the fused reduce + Adam are dense.hpp's FP32-MFMA kernels, unchanged.  BC's own:
+// Hidden layers, the grouped weight gradient and the fused reduce + Adam are dense.hpp's FP32-MFMA kernels, unchanged, driven by
+// DenseAgent (dense_agent.hpp), the host core BC shares with IQL and AWAC: this file holds BC's kernels, the dispatch of its three
+// kernel forms, its record, its sample and its entry points.  BC's own kernels:
 //   k_bc_loss   (general form) y = act_out(z), the loss, dL/dz from the last layer's pre-activation z [B][Np]
 //   k_bc_head   (fused form, out_dim <= 64) the last layer's forward, y, the loss, dL/dz and the last layer's input gradient in one
 //               row-block launch, the layer's weights staged in LDS once per workgroup
@@ -293,9 +295,10 @@ __global__ __launch_bounds__(256) void k_bc_act(BcActArgs p)
 }  // namespace
 
 // ================================================================================================
-struct Bc : bdr_agent {
+// The buffer lifetimes, the layer-by-layer forward, the backward step, the observation rows of an acting call and the reference
+// layout are DenseAgent's (dense_agent.hpp); BC adds its one model, the loss / head kernels' dispatch, its record and its sample.
+struct Bc : DenseAgent {
     bdr_bc_config cfg;
-    int O = 0, A = 0;
     MlpLayout net;                     // the policy; its last layer is built without activation (z), act_out is applied by BC's kernels
     float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;   // arenas: parameters, gradients, exp_avg, exp_avg_sq
     uint64_t step = 0;
@@ -311,45 +314,17 @@ struct Bc : bdr_agent {
     float *u_obs = nullptr, *u_act = nullptr; uint64_t u_cap = 0;
     int last_B = 0;
 
-    enum Life { AGENT, BATCH, STAGING };
-    std::vector<void*> owned[3];
-    template <class T>
-    int32_t alloc(T** q, size_t n, Life life)
-    {
-        const size_t bytes = std::max<size_t>(n, 4) * sizeof(T);
-        BDR_HIP(hipMalloc((void**)q, bytes));
-        owned[life].push_back(*q);
-        BDR_HIP(hipMemsetAsync(*q, 0, bytes, stream));
-        return BDR_OK;
-    }
-    void release(Life life)
-    {
-        for (void* q : owned[life]) (void)hipFree(q);
-        owned[life].clear();
-    }
-    ~Bc() override
-    {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(stream);
-        for (Life l : {AGENT, BATCH, STAGING}) release(l);
-    }
-    static int chunks_for(int Bn) { return std::max(1, std::min(16, Bn / 256)); }   // rows per dW chunk: k_dense_dw_small_group
     int32_t ensure_batch(int Bn)
     {
         if (Bn <= B) return BDR_OK;
         BDR_HIP(hipStreamSynchronize(stream));
         release(BATCH);
         B = 0;
-        const size_t L = net.L.size();
         BDR_TRY(alloc(&x0, (size_t)Bn * net.L[0].Kp, BATCH));
-        act.assign(L, nullptr); dy.assign(L, nullptr);
-        for (size_t l = 0; l < L; ++l) { BDR_TRY(alloc(&act[l], (size_t)Bn * net.L[l].Np, BATCH)); BDR_TRY(alloc(&dy[l], (size_t)Bn * net.L[l].Np, BATCH)); }
+        BDR_TRY(layer_bufs(net, Bn, act)); BDR_TRY(layer_bufs(net, Bn, dy));
         BDR_TRY(alloc(&pred, (size_t)Bn * net.L.back().Np, BATCH));
         BDR_TRY(alloc(&rowsq, Bn, BATCH));
-        off.clear();
-        size_t o = 0;
-        for (const auto& l : net.L) { off.push_back(o); o += (size_t)chunks_for(Bn) * ((size_t)l.Kp * l.Np + l.Np); }
-        BDR_TRY(alloc(&part, o, BATCH));
+        BDR_TRY(alloc(&part, plan(net, Bn, off), BATCH));
         BDR_TRY(alloc(&samp, (size_t)Bn * A, BATCH));
         BDR_TRY(alloc(&samp_idx, Bn, BATCH));
         B = Bn;
@@ -358,15 +333,8 @@ struct Bc : bdr_agent {
     // layers [0, upto) of Bn rows of x0
     int32_t forward(int upto, int Bn, const char* name)
     {
-        DenseSrc in{x0, net.L[0].Kp};
-        const float* pp[1] = {p};
-        for (int l = 0; l < upto; ++l) {
-            float* out[1] = {act[l]};
-            Bracket br(this, name);
-            BDR_TRY(dense_forward_z(stream, net.L[l], 1, pp, &in, out, Bn, true));
-            in = DenseSrc{act[l], net.L[l].Np};
-        }
-        return BDR_OK;
+        const float* pp[1] = {p}; const float* xs[1] = {x0}; std::vector<float*>* as[1] = {&act};
+        return mlp_forward(net, 1, pp, xs, as, Bn, name, upto);
     }
     template <int R>
     int32_t launch_head(const BcHeadArgs& a, int Bn)
@@ -407,32 +375,11 @@ struct Bc : bdr_agent {
             BDR_HIP(step_launch(stream, false, k_bc_loss, dim3((Bn + 31) / 32), dim3(256), a));
             lo = L - 1;
         }
-        const float* pb[1] = {p};
-        for (int l = lo; l >= 1; --l) {
-            const float* dyl[1] = {dy[l]}; float* dxl[1] = {dy[l - 1]}; const float* mask[1] = {act[l - 1]};
-            Bracket br(this, "dx");
-            BDR_TRY(dense_dx_z(stream, net.L[l], 1, pb, dyl, dxl, mask, Bn, true));
-        }
-        std::vector<DenseDwJob> jobs;
-        const int c = chunks_for(Bn);
-        for (int l = 0; l < L; ++l)
-            jobs.push_back(DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{act[l - 1], net.L[l - 1].Np}, dy[l], part + off[l], c});
-        { Bracket br(this, "dw"); BDR_TRY(dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
         step += 1;
-        ReduceAdamArgs ra{};
-        ra.nseg = L;
-        for (int l = 0; l < L; ++l) {
-            const DenseLayer& ly = net.L[l];
-            const size_t nfl = (size_t)ly.Kp * ly.Np + ly.Np;
-            ra.seg[l] = DenseReduceSeg{part + off[l], nfl, c, (unsigned)(ly.w / 4), (unsigned)(nfl / 4)};
-        }
-        ra.p[0] = p; ra.g[0] = g; ra.m[0] = m; ra.v[0] = v;
-        ra.s[0] = adam_scalars_for(cfg.opt.opt_kind == BDR_OPT_ADAMW, cfg.lr, cfg.opt.beta1, cfg.opt.beta2, cfg.opt.eps, cfg.opt.weight_decay, step);
-        ra.n4 = (unsigned)(net.total / 4);
-        {
-            Bracket br(this, "reduce_adam");
-            BDR_HIP(step_launch(stream, true, k_dense_reduce_adam, dim3((ra.n4 + 255) / 256, 1), dim3(256), ra));
-        }
+        const AdamScalars sc = opt_scalars(cfg.opt, cfg.lr, step);
+        std::vector<float*>* acts[1] = {&act}; std::vector<float*>* dys[1] = {&dy};
+        // no targets: nz = 1, no instance stride, track == 0, and a tau the kernel does not read (dense.hpp k_dense_reduce_adam)
+        BDR_TRY(mlp_backward_step(net, 1, &p, &g, &m, &v, nullptr, x0, acts, dys, part, 0, off, &sc, Bn, {"dx", "dw", "reduce_adam"}, net.total, 0.0, lo));
         n_opts += 1;
         last_B = Bn;
         return BDR_OK;
@@ -449,9 +396,7 @@ struct Bc : bdr_agent {
     int32_t opt(bdr_replay* r) override
     {
         BDR_TRY(refuse_discrete());
-        BDR_REQUIRE(r->obs_bytes == (uint64_t)O * 4 && r->act_bytes == (uint64_t)A * 4, "replay rows do not match BC obs/act dims (f32 rows)");
-        BDR_REQUIRE(r->device == device, "agent and replay buffer live on different devices");
-        BDR_REQUIRE(!r->frame_stack, "BC reads f32 observation rows, not a frame-stack store");
+        BDR_TRY(check_replay(r, "BC"));
         const int Bn = (int)cfg.batch_size;
         BDR_TRY(ensure_batch(Bn));
         { Bracket br(this, "sample"); BDR_TRY(replay_sample_on_stream(r, Bn, stream)); }
@@ -475,19 +420,7 @@ struct Bc : bdr_agent {
         BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
         BDR_HIP(hipSetDevice(device));
         BDR_TRY(ensure_batch((int)n));
-        const float* d = nullptr;
-        int32_t st = BDR_OK;
-        if (!obs_rows_on_device && n * O * 4 <= HOST_ROWS_PINNED_MAX) {
-            const uint8_t* pd = nullptr;
-            BDR_TRY(host_rows_pinned(obs, n * O * 4, &pd));
-            d = reinterpret_cast<const float*>(pd);
-        } else {
-            float* stage = nullptr;
-            BDR_TRY(act_buffer(n * O * 4, (void**)&stage));
-            st = stage_obs(stage, obs, (size_t)O * 4, n, stream);
-            d = stage;
-        }
-        if (st == BDR_OK) st = pack_rows(stream, d, O, O, x0, net.L[0].Kp, 0, (int)n);
+        int32_t st = pack_acting_obs(obs, n, x0, net.L[0].Kp);
         if (st == BDR_OK) st = forward((int)net.L.size(), (int)n, "sample_fwd");
         if (st == BDR_OK) {
             BcActArgs a{act.back(), net.L.back().Np, A, (int)n, cfg.policy.activation_out, disc ? 1 : 0, samp, samp_idx};
@@ -503,11 +436,7 @@ struct Bc : bdr_agent {
     }
     int32_t sample_device(uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out)
     {
-        BDR_REQUIRE(row_stride >= (uint64_t)O * 4 && row_stride % 4 == 0, "row_stride must be >= the row size and a multiple of 4");
-        BDR_HIP(hipSetDevice(device));
-        BDR_TRY(check_device_rows(obs_dev, row_stride));
-        DeviceRowsScope rows(this, row_stride);
-        return sample(n, static_cast<const float*>(obs_dev), act_out, idx_out);
+        return with_device_rows(obs_dev, row_stride, [&](const float* rows) { return sample(n, rows, act_out, idx_out); });
     }
     // the compiled trainers take f32 action rows: Continuous only
     bool sample_f32(uint64_t n, const void* obs, bool on_device, uint64_t stride, float* out, int32_t* st) override
@@ -532,10 +461,7 @@ struct Bc : bdr_agent {
         BDR_REQUIRE(s, "unknown BC model %d", which);
         BDR_REQUIRE(n == net.ref_total, "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)net.ref_total);
         std::vector<float> in(net.total);
-        BDR_HIP(hipMemcpyAsync(in.data(), s, net.total * 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        mlp_to_reference(net, 0, in.data(), out);
-        return BDR_OK;
+        return arena_to_reference(net, s, in, out);
     }
     int32_t set_params(int which, const float* inp, uint64_t n) override
     {
@@ -543,10 +469,7 @@ struct Bc : bdr_agent {
         BDR_REQUIRE(s, "unknown BC model %d", which);
         BDR_REQUIRE(n == net.ref_total, "parameter count mismatch");
         std::vector<float> in(net.total, 0.f);
-        mlp_to_internal(net, 0, inp, in.data());
-        BDR_HIP(hipMemcpyAsync(s, in.data(), net.total * 4, hipMemcpyHostToDevice, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
+        return arena_from_reference(net, inp, in, s);
     }
     float* arena(int which, size_t* n) override { float* s = slot(which); if (n) *n = s ? net.total : 0; return s; }
 

@@ -1,19 +1,13 @@
 // The candle-family agents (IQL: iql.hip, AWAC: awac.hip) share a GaussianActor over Mlp3 (util/actor.rs, mlp/mlp3.rs) and a
 // MultiCritic of Mlp on cat(obs, act) with soft-updated targets (util/critic.rs), trained on the FP32-MFMA kernels of dense.hpp.
-// This header holds what they share.  Device: the counter-based N(0,1) noise stream of Policy::sample, the fixed-order batch sums and
-// the sample kernel.  Host: CandleAgent, the core each agent derives from; an agent adds its update schedule, its loss kernels, its
-// records and probes, and any model of its own.  Every batch-wide sum is formed in one order (rows in blocks of 32, a 32-lane
-// butterfly per block, the block partials added in block order), so an update gives the same bits run to run.
+// This header holds what they share.  Device: the counter-based N(0,1) noise stream of Policy::sample, the fixed-order batch sums
+// (BC's loss, bc.hip, uses their butterfly and acc too) and the sample kernel.  Host: CandleAgent, the actor + critics + targets
+// core each of the two derives from, itself on DenseAgent (dense_agent.hpp: buffer lifetimes, the Mlp forward and backward step,
+// the observation rows of an acting call, the reference layout); an agent adds its update schedule, its loss kernels, its records
+// and probes, and any model of its own.  Every batch-wide sum is formed in one order (rows in blocks of 32, a 32-lane butterfly per
+// block, the block partials added in block order), so an update gives the same bits run to run.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <algorithm>
-#include <cstdint>
-#include <cstddef>
-#include <cstdio>
-#include <string>
-#include <vector>
-
-#include "dense.hpp"
+#include "dense_agent.hpp"
 
 namespace bdr {
 namespace candle {
@@ -75,33 +69,6 @@ __device__ __forceinline__ float acc(float base, float s, float scale)   // base
     return base + t;
 }
 
-
-// ---- checkpoints of candle VarMaps (host) ----
-// the variables of an Mlp under `prefix`: mlp.ln{i}.weight [out][in], mlp.ln{i}.bias [out]
-inline void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt)
-{
-    for (size_t i = 0; i < net.L.size(); ++i) {
-        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)net.L[i].out, (uint64_t)net.L[i].in}});
-        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)net.L[i].out}});
-    }
-}
-// candle's VarMap::save writes safetensors whatever the extension: "<stem>.pt" (default, the reference's files) or "<stem>.safetensors"
-inline std::string ckpt_save_path(int32_t ckpt_format, const char* dir, const char* stem)
-{
-    return std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt");
-}
-// ... and the load path falls back to the other extension when only that file exists
-inline std::string ckpt_load_path(int32_t ckpt_format, const char* dir, const char* stem)
-{
-    const std::string first = ckpt_save_path(ckpt_format, dir, stem);
-    const std::string second = std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".pt" : ".safetensors");
-    FILE* f = fopen(first.c_str(), "rb");
-    if (f) { fclose(f); return first; }
-    f = fopen(second.c_str(), "rb");
-    if (f) { fclose(f); return second; }
-    return first;
-}
-
 }  // namespace candle
 }  // namespace bdr
 
@@ -150,21 +117,15 @@ int32_t check_mlp(const bdr_mlp_config& m, const char* what, bool actor)
                 "%s: activation_out must be None or ReLU (Tanh / Sigmoid are not supported)", what);
     return BDR_OK;
 }
-int32_t check_opt(const bdr_adamw_config& o, const char* what)
-{
-    BDR_REQUIRE(o.opt_kind == BDR_OPT_ADAM || o.opt_kind == BDR_OPT_ADAMW, "%s: unknown optimizer", what);
-    BDR_REQUIRE(!(o.opt_kind == BDR_OPT_ADAMW && o.amsgrad), "%s: candle's AdamW has no amsgrad", what);
-    return BDR_OK;
-}
 
 // ================================================================================================
 // The host core.  Self is the agent (CRTP): it supplies NAME (in messages), N_RECORD (its record values), kind(), record(),
 // record_keys(), update(Bn, obs, act, next_obs, reward, term, trunc, first) and alloc_batch(Bn), and may replace the hooks
 // init_own, alloc_staging and own_slot below.  Cfg is its bdr_*_config; the fields named here are common to all of them.
 template <class Self, class Cfg>
-struct CandleAgent : bdr_agent {
+struct CandleAgent : DenseAgent {
     Cfg cfg;
-    int O = 0, A = 0, NC = 2;
+    int NC = 2;
     MlpLayout pn, qn;                  // actor mean (head2 follows pn in the actor arena), critic
     size_t h2_off = 0, pi_total = 0;   // head2 at h2_off (= pn.total) in the actor arena; pi_total = pn.total + pad64(A)
     // arenas: parameters, gradients, exp_avg, exp_avg_sq (+ the critics' targets)
@@ -188,46 +149,6 @@ struct CandleAgent : bdr_agent {
 
     Self& self() { return static_cast<Self&>(*this); }
 
-    // Every device buffer is registered by its lifetime when it is allocated and freed here: the agent's (arenas, scal), those of
-    // one batch size (ensure_batch) and the staging rows (stage_batch)
-    enum Life { AGENT, BATCH, STAGING };
-    std::vector<void*> owned[3];
-    template <class T>
-    int32_t alloc(T** p, size_t n, Life life, bool zero = true)
-    {
-        const size_t bytes = std::max<size_t>(n, 4) * sizeof(T);
-        BDR_HIP(hipMalloc((void**)p, bytes));
-        owned[life].push_back(*p);
-        if (zero) BDR_HIP(hipMemsetAsync(*p, 0, bytes, stream));
-        return BDR_OK;
-    }
-    void release(Life life)
-    {
-        for (void* p : owned[life]) (void)hipFree(p);
-        owned[life].clear();
-    }
-    ~CandleAgent() override
-    {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(stream);
-        for (Life l : {AGENT, BATCH, STAGING}) release(l);
-    }
-    int32_t layer_bufs(const MlpLayout& net, int Bn, std::vector<float*>& out)
-    {
-        out.assign(net.L.size(), nullptr);
-        for (size_t l = 0; l < net.L.size(); ++l) BDR_TRY(alloc(&out[l], (size_t)Bn * net.L[l].Np, BATCH));
-        return BDR_OK;
-    }
-    // row chunks of the grouped dW launch (k_dense_dw_small_group: 256 rows per workgroup, at most 16 chunks)
-    static int chunks_for(int Bn) { return std::max(1, std::min(16, Bn / 256)); }
-    // per-layer offsets of one network's dW partials; returns their size
-    static size_t plan(const MlpLayout& net, int Bn, std::vector<size_t>& off)
-    {
-        off.clear();
-        size_t o = 0;
-        for (const auto& l : net.L) { off.push_back(o); o += (size_t)chunks_for(Bn) * ((size_t)l.Kp * l.Np + l.Np); }
-        return o;
-    }
     int32_t ensure_batch(int Bn)
     {
         if (Bn <= B) return BDR_OK;
@@ -249,65 +170,20 @@ struct CandleAgent : bdr_agent {
         return BDR_OK;
     }
 
-    // forward of n (parameters, input) pairs of one architecture, up to 4 per launch: pass j runs params[j] on x[j] into (*acts[j])[layer]
-    int32_t mlp_forward(const MlpLayout& net, int n, const float* const* params, const float* const* x, std::vector<float*>* const* acts, int Bn, const char* name)
-    {
-        for (int j0 = 0; j0 < n; j0 += 4) {
-            const int nz = std::min(4, n - j0);
-            DenseSrc in[4]; float* out[4];
-            for (int j = 0; j < nz; ++j) in[j] = DenseSrc{x[j0 + j], net.L[0].Kp};
-            for (size_t l = 0; l < net.L.size(); ++l) {
-                for (int j = 0; j < nz; ++j) out[j] = (*acts[j0 + j])[l];
-                Bracket br(this, name);
-                BDR_TRY(dense_forward_z(stream, net.L[l], nz, params + j0, in, out, Bn, true));
-                for (int j = 0; j < nz; ++j) in[j] = DenseSrc{out[j], net.L[l].Np};
-            }
-        }
-        return BDR_OK;
-    }
     // the actor's mean of Bn rows x ([Bn][Kp]) into acts
     int32_t actor_forward(const float* x, std::vector<float*>& acts, int Bn)
     {
         const float* pp[1] = {pi_p}; const float* xs[1] = {x}; std::vector<float*>* as[1] = {&acts};
         return mlp_forward(pn, 1, pp, xs, as, Bn, "pi_fwd");
     }
-    static AdamScalars opt_scalars(const bdr_adamw_config& o, double lr, uint64_t step)
-    {
-        return adam_scalars_for(o.opt_kind == BDR_OPT_ADAMW, lr, o.beta1, o.beta2, o.eps, o.weight_decay, step);
-    }
-    // backward of nz networks of one layout from the last layer's output gradient dy[z][L-1]: input gradients down to layer 1 (one
-    // launch per layer for all nz), every weight gradient in one grouped launch, then the fused reduce + Adam (+ tracking into tgt)
+    // DenseAgent's step from the last layer, under one bracket name, with the critics' tau (the kernel reads it only where targets
+    // are tracked)
     int32_t mlp_backward_step(const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
                               const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
                               const std::vector<size_t>& off, const AdamScalars* sc, int Bn, const char* name, size_t total, const DenseReduceSeg* extra = nullptr)
     {
-        const int L = (int)net.L.size();
-        for (int l = L - 1; l >= 1; --l) {
-            const float* pb[4]; const float* dy[4]; float* dx[4]; const float* mask[4];
-            for (int z = 0; z < nz; ++z) { pb[z] = p[z]; dy[z] = (*dys[z])[l]; dx[z] = (*dys[z])[l - 1]; mask[z] = (*acts[z])[l - 1]; }
-            Bracket br(this, name);
-            BDR_TRY(dense_dx_z(stream, net.L[l], nz, pb, dy, dx, mask, Bn, true));
-        }
-        std::vector<DenseDwJob> jobs;
-        const int c = chunks_for(Bn);
-        for (int z = 0; z < nz; ++z)
-            for (int l = 0; l < L; ++l)
-                jobs.push_back(DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*dys[z])[l],
-                                          part + (size_t)z * part_stride + off[l], c});
-        { Bracket br(this, name); BDR_TRY(dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
-        ReduceAdamArgs ra{};
-        ra.nseg = L; ra.inst_part_stride = part_stride;
-        for (int l = 0; l < L; ++l) {
-            const DenseLayer& ly = net.L[l];
-            const size_t nfl = (size_t)ly.Kp * ly.Np + ly.Np;
-            ra.seg[l] = DenseReduceSeg{part + off[l], nfl, c, (unsigned)(ly.w / 4), (unsigned)(nfl / 4)};
-        }
-        if (extra) ra.seg[ra.nseg++] = *extra;
-        for (int z = 0; z < nz; ++z) { ra.p[z] = p[z]; ra.g[z] = g[z]; ra.m[z] = m[z]; ra.v[z] = v[z]; ra.tgt[z] = tgt ? tgt[z] : nullptr; ra.s[z] = sc[z]; ra.vmax[z] = nullptr; }
-        ra.n4 = (unsigned)(total / 4); ra.track = tgt ? 1 : 0; ra.tau = (float)cfg.critic_tau; ra.omt = (float)(1.0 - cfg.critic_tau);
-        Bracket br(this, name);
-        BDR_HIP(step_launch(stream, true, k_dense_reduce_adam, dim3((ra.n4 + 255) / 256, nz), dim3(256), ra));
-        return BDR_OK;
+        return DenseAgent::mlp_backward_step(net, nz, p, g, m, v, tgt, x0, acts, dys, part, part_stride, off, sc, Bn, name, total, cfg.critic_tau,
+                                             (int)net.L.size() - 1, extra);
     }
     // the actor's step from dL/dmean (p_dy's last layer) and dL/dhead2 (h2_part): backward and Adam, head2 as one more segment
     int32_t actor_step(int Bn)
@@ -380,9 +256,7 @@ struct CandleAgent : bdr_agent {
     // ---- agent plumbing ----
     int32_t opt(bdr_replay* r) override
     {
-        BDR_REQUIRE(r->obs_bytes == (uint64_t)O * 4 && r->act_bytes == (uint64_t)A * 4, "replay rows do not match %s obs/act dims (f32 rows)", Self::NAME);
-        BDR_REQUIRE(r->device == device, "agent and replay buffer live on different devices");
-        BDR_REQUIRE(!r->frame_stack, "%s reads f32 observation rows, not a frame-stack store", Self::NAME);
+        BDR_TRY(check_replay(r, Self::NAME));
         const int Bn = (int)cfg.batch_size;
         BDR_TRY(ensure_batch(Bn));
         for (uint64_t u = 0; u < cfg.n_updates_per_opt; ++u) {
@@ -404,19 +278,7 @@ struct CandleAgent : bdr_agent {
         BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
         BDR_HIP(hipSetDevice(device));
         BDR_TRY(ensure_batch((int)n));
-        const float* d = nullptr;
-        int32_t st = BDR_OK;
-        if (!obs_rows_on_device && n * O * 4 <= HOST_ROWS_PINNED_MAX) {   // host rows: read in place from pinned memory by the packing kernel
-            const uint8_t* pd = nullptr;
-            BDR_TRY(host_rows_pinned(obs, n * O * 4, &pd));
-            d = reinterpret_cast<const float*>(pd);
-        } else {
-            float* stage = nullptr;
-            BDR_TRY(act_buffer(n * O * 4, (void**)&stage));
-            st = stage_obs(stage, obs, (size_t)O * 4, n, stream);
-            d = stage;
-        }
-        if (st == BDR_OK) st = pack_rows(stream, d, O, O, x_o, pn.L[0].Kp, 0, (int)n);
+        int32_t st = pack_acting_obs(obs, n, x_o, pn.L[0].Kp);
         if (st == BDR_OK) st = actor_forward(x_o, p_act, (int)n);
         if (st == BDR_OK) st = sample_pack(p_act.back(), (int)n, nullptr, samp, nullptr, "sample_pack");
         if (st == BDR_OK) st = rows_to_host(samp, act_out, n * A);
@@ -425,11 +287,7 @@ struct CandleAgent : bdr_agent {
     }
     int32_t sample_device(uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out)
     {
-        BDR_REQUIRE(row_stride >= (uint64_t)O * 4 && row_stride % 4 == 0, "row_stride must be >= the row size and a multiple of 4");
-        BDR_HIP(hipSetDevice(device));
-        BDR_TRY(check_device_rows(obs_dev, row_stride));
-        DeviceRowsScope rows(this, row_stride);
-        return sample(n, static_cast<const float*>(obs_dev), act_out);
+        return with_device_rows(obs_dev, row_stride, [&](const float* rows) { return sample(n, rows, act_out); });
     }
     bool sample_f32(uint64_t n, const void* obs, bool on_device, uint64_t stride, float* act, int32_t* st) override
     {
@@ -463,9 +321,7 @@ struct CandleAgent : bdr_agent {
         BDR_REQUIRE(s.p, "unknown %s model %d", Self::NAME, which);
         BDR_REQUIRE(n == param_count(which), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)param_count(which));
         std::vector<float> in(s.n);
-        BDR_HIP(hipMemcpyAsync(in.data(), s.p, s.n * 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        mlp_to_reference(*s.net, 0, in.data(), out);
+        BDR_TRY(arena_to_reference(*s.net, s.p, in, out));
         if (s.net == &pn) for (int j = 0; j < A; ++j) out[pn.ref_total + j] = in[h2_off + j];
         return BDR_OK;
     }
@@ -475,11 +331,8 @@ struct CandleAgent : bdr_agent {
         BDR_REQUIRE(s.p, "unknown %s model %d", Self::NAME, which);
         BDR_REQUIRE(n == param_count(which), "parameter count mismatch");
         std::vector<float> in(s.n, 0.f);
-        mlp_to_internal(*s.net, 0, inp, in.data());
         if (s.net == &pn) for (int j = 0; j < A; ++j) in[h2_off + j] = inp[pn.ref_total + j];
-        BDR_HIP(hipMemcpyAsync(s.p, in.data(), s.n * 4, hipMemcpyHostToDevice, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
+        return arena_from_reference(*s.net, inp, in, s.p);
     }
     // SyncModel ships the actor (model 0)
     float* arena(int which, size_t* n) override { Slot s = slot(which); if (n) *n = s.n; return s.p; }

@@ -1,0 +1,220 @@
+// DenseAgent: the host core under every agent whose models are Mlps trained on dense.hpp's FP32-MFMA kernels (BC: bc.hip; IQL and
+// AWAC through CandleAgent, candle_actor.hpp).  It knows how such a network is allocated, run forward, stepped (input gradients,
+// the grouped dW, the fused reduce + Adam), fed the observation rows of an acting call, and copied to and from the reference
+// layout - and nothing about which models an agent has: an agent brings its arenas, its batch buffers, its loss kernels and its
+// update schedule.  Host code only; with it the checkpoint helpers of candle VarMaps and the optimizer check the agents share.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdint>
+#include <cstddef>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "dense.hpp"
+
+namespace bdr {
+namespace candle {
+
+// ---- checkpoints of candle VarMaps (host) ----
+// the variables of an Mlp under `prefix`: mlp.ln{i}.weight [out][in], mlp.ln{i}.bias [out]
+inline void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt)
+{
+    for (size_t i = 0; i < net.L.size(); ++i) {
+        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)net.L[i].out, (uint64_t)net.L[i].in}});
+        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)net.L[i].out}});
+    }
+}
+// candle's VarMap::save writes safetensors whatever the extension: "<stem>.pt" (default, the reference's files) or "<stem>.safetensors"
+inline std::string ckpt_save_path(int32_t ckpt_format, const char* dir, const char* stem)
+{
+    return std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt");
+}
+// ... and the load path falls back to the other extension when only that file exists
+inline std::string ckpt_load_path(int32_t ckpt_format, const char* dir, const char* stem)
+{
+    const std::string first = ckpt_save_path(ckpt_format, dir, stem);
+    const std::string second = std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".pt" : ".safetensors");
+    FILE* f = fopen(first.c_str(), "rb");
+    if (f) { fclose(f); return first; }
+    f = fopen(second.c_str(), "rb");
+    if (f) { fclose(f); return second; }
+    return first;
+}
+
+}  // namespace candle
+}  // namespace bdr
+
+namespace {
+using namespace bdr;
+
+int32_t check_opt(const bdr_adamw_config& o, const char* what)
+{
+    BDR_REQUIRE(o.opt_kind == BDR_OPT_ADAM || o.opt_kind == BDR_OPT_ADAMW, "%s: unknown optimizer", what);
+    BDR_REQUIRE(!(o.opt_kind == BDR_OPT_ADAMW && o.amsgrad), "%s: candle's AdamW has no amsgrad", what);
+    return BDR_OK;
+}
+
+struct DenseAgent : bdr_agent {
+    int O = 0, A = 0;   // f32 observation and action row widths
+
+    // Every device buffer is registered by its lifetime when it is allocated and freed here: the agent's (arenas, record values),
+    // those of one batch size (the agent's ensure_batch) and the staging rows of update_on_batch
+    enum Life { AGENT, BATCH, STAGING };
+    std::vector<void*> owned[3];
+    template <class T>
+    int32_t alloc(T** p, size_t n, Life life, bool zero = true)
+    {
+        const size_t bytes = std::max<size_t>(n, 4) * sizeof(T);
+        BDR_HIP(hipMalloc((void**)p, bytes));
+        owned[life].push_back(*p);
+        if (zero) BDR_HIP(hipMemsetAsync(*p, 0, bytes, stream));
+        return BDR_OK;
+    }
+    void release(Life life)
+    {
+        for (void* p : owned[life]) (void)hipFree(p);
+        owned[life].clear();
+    }
+    ~DenseAgent() override
+    {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+        for (Life l : {AGENT, BATCH, STAGING}) release(l);
+    }
+    int32_t layer_bufs(const MlpLayout& net, int Bn, std::vector<float*>& out)
+    {
+        out.assign(net.L.size(), nullptr);
+        for (size_t l = 0; l < net.L.size(); ++l) BDR_TRY(alloc(&out[l], (size_t)Bn * net.L[l].Np, BATCH));
+        return BDR_OK;
+    }
+    // row chunks of the grouped dW launch (k_dense_dw_small_group: 256 rows per workgroup, at most 16 chunks)
+    static int chunks_for(int Bn) { return std::max(1, std::min(16, Bn / 256)); }
+    // per-layer offsets of one network's dW partials; returns their size
+    static size_t plan(const MlpLayout& net, int Bn, std::vector<size_t>& off)
+    {
+        off.clear();
+        size_t o = 0;
+        for (const auto& l : net.L) { off.push_back(o); o += (size_t)chunks_for(Bn) * ((size_t)l.Kp * l.Np + l.Np); }
+        return o;
+    }
+
+    // forward of n (parameters, input) pairs of one architecture, up to 4 per launch: pass j runs params[j] on x[j] into
+    // (*acts[j])[layer]; layers [0, upto), all of them by default.  One profile bracket `name` per launch.
+    int32_t mlp_forward(const MlpLayout& net, int n, const float* const* params, const float* const* x, std::vector<float*>* const* acts, int Bn, const char* name,
+                        int upto = -1)
+    {
+        const size_t layers = upto < 0 ? net.L.size() : (size_t)upto;
+        for (int j0 = 0; j0 < n; j0 += 4) {
+            const int nz = std::min(4, n - j0);
+            DenseSrc in[4]; float* out[4];
+            for (int j = 0; j < nz; ++j) in[j] = DenseSrc{x[j0 + j], net.L[0].Kp};
+            for (size_t l = 0; l < layers; ++l) {
+                for (int j = 0; j < nz; ++j) out[j] = (*acts[j0 + j])[l];
+                Bracket br(this, name);
+                BDR_TRY(dense_forward_z(stream, net.L[l], nz, params + j0, in, out, Bn, true));
+                for (int j = 0; j < nz; ++j) in[j] = DenseSrc{out[j], net.L[l].Np};
+            }
+        }
+        return BDR_OK;
+    }
+    static AdamScalars opt_scalars(const bdr_adamw_config& o, double lr, uint64_t step)
+    {
+        return adam_scalars_for(o.opt_kind == BDR_OPT_ADAMW, lr, o.beta1, o.beta2, o.eps, o.weight_decay, step);
+    }
+    // the profile brackets of mlp_backward_step, one per launch: the input gradients, the grouped dW, the reduce + Adam
+    struct StepNames {
+        const char *dx, *dw, *adam;
+        StepNames(const char* one) : dx(one), dw(one), adam(one) {}
+        StepNames(const char* dx_, const char* dw_, const char* adam_) : dx(dx_), dw(dw_), adam(adam_) {}
+    };
+    // backward of nz networks of one layout from the output gradient dy[z][lo] of layer lo (the last layer, or below it where the
+    // agent's own kernel has already formed the gradients above: BC's fused head): input gradients down to layer 1 (one launch per
+    // layer for all nz), every weight gradient in one grouped launch, then the fused reduce + Adam (+ tracking into tgt at rate tau)
+    int32_t mlp_backward_step(const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
+                              const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
+                              const std::vector<size_t>& off, const AdamScalars* sc, int Bn, const StepNames& names, size_t total, double tau, int lo,
+                              const DenseReduceSeg* extra = nullptr)
+    {
+        const int L = (int)net.L.size();
+        for (int l = lo; l >= 1; --l) {
+            const float* pb[4]; const float* dy[4]; float* dx[4]; const float* mask[4];
+            for (int z = 0; z < nz; ++z) { pb[z] = p[z]; dy[z] = (*dys[z])[l]; dx[z] = (*dys[z])[l - 1]; mask[z] = (*acts[z])[l - 1]; }
+            Bracket br(this, names.dx);
+            BDR_TRY(dense_dx_z(stream, net.L[l], nz, pb, dy, dx, mask, Bn, true));
+        }
+        std::vector<DenseDwJob> jobs;
+        const int c = chunks_for(Bn);
+        for (int z = 0; z < nz; ++z)
+            for (int l = 0; l < L; ++l)
+                jobs.push_back(DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*dys[z])[l],
+                                          part + (size_t)z * part_stride + off[l], c});
+        { Bracket br(this, names.dw); BDR_TRY(dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
+        ReduceAdamArgs ra{};
+        ra.nseg = L; ra.inst_part_stride = part_stride;
+        for (int l = 0; l < L; ++l) {
+            const DenseLayer& ly = net.L[l];
+            const size_t nfl = (size_t)ly.Kp * ly.Np + ly.Np;
+            ra.seg[l] = DenseReduceSeg{part + off[l], nfl, c, (unsigned)(ly.w / 4), (unsigned)(nfl / 4)};
+        }
+        if (extra) ra.seg[ra.nseg++] = *extra;
+        for (int z = 0; z < nz; ++z) { ra.p[z] = p[z]; ra.g[z] = g[z]; ra.m[z] = m[z]; ra.v[z] = v[z]; ra.tgt[z] = tgt ? tgt[z] : nullptr; ra.s[z] = sc[z]; ra.vmax[z] = nullptr; }
+        // without targets (track == 0) k_dense_reduce_adam reads neither tau nor omt: an agent that has none passes any tau
+        ra.n4 = (unsigned)(total / 4); ra.track = tgt ? 1 : 0; ra.tau = (float)tau; ra.omt = (float)(1.0 - tau);
+        Bracket br(this, names.adam);
+        BDR_HIP(step_launch(stream, true, k_dense_reduce_adam, dim3((ra.n4 + 255) / 256, nz), dim3(256), ra));
+        return BDR_OK;
+    }
+
+    // Agent::opt's checks of the replay buffer: f32 rows of the agent's widths on the agent's device
+    int32_t check_replay(const bdr_replay* r, const char* name) const
+    {
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)O * 4 && r->act_bytes == (uint64_t)A * 4, "replay rows do not match %s obs/act dims (f32 rows)", name);
+        BDR_REQUIRE(r->device == device, "agent and replay buffer live on different devices");
+        BDR_REQUIRE(!r->frame_stack, "%s reads f32 observation rows, not a frame-stack store", name);
+        return BDR_OK;
+    }
+
+    // ---- acting calls (Policy::sample) ----
+    // n observation rows (host rows, or device rows inside with_device_rows) -> the zero-padded first-layer input x [n][Kp].  On an
+    // error the profile's slot cursor is reset, as the caller does when the call ends, and the status returned.
+    int32_t pack_acting_obs(const float* obs, uint64_t n, float* x, int Kp)
+    {
+        const uint8_t* d = nullptr;
+        int32_t st = acting_rows(obs, (size_t)O * 4, n, &d);
+        if (st == BDR_OK) st = pack_rows(stream, reinterpret_cast<const float*>(d), O, O, x, Kp, 0, (int)n);
+        if (st != BDR_OK) slot_cursor = 0;
+        return st;
+    }
+    // an acting call on rows that already live in HBM, row_stride bytes apart: sample(rows) is the agent's host-row call
+    template <class F>
+    int32_t with_device_rows(const void* obs_dev, uint64_t row_stride, F&& sample)
+    {
+        BDR_REQUIRE(row_stride >= (uint64_t)O * 4 && row_stride % 4 == 0, "row_stride must be >= the row size and a multiple of 4");
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(check_device_rows(obs_dev, row_stride));
+        DeviceRowsScope rows(this, row_stride);
+        return sample(static_cast<const float*>(obs_dev));
+    }
+
+    // ---- parameter views ----
+    // a device arena of `host.size()` floats with `net` at its start -> the host copy and net's parameters in the reference layout
+    int32_t arena_to_reference(const MlpLayout& net, const float* dev, std::vector<float>& host, float* out)
+    {
+        BDR_HIP(hipMemcpyAsync(host.data(), dev, host.size() * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        mlp_to_reference(net, 0, host.data(), out);
+        return BDR_OK;
+    }
+    // ... and back: net's parameters from the reference layout into `host` (what follows net in the arena is the caller's), then up
+    int32_t arena_from_reference(const MlpLayout& net, const float* inp, std::vector<float>& host, float* dev)
+    {
+        mlp_to_internal(net, 0, inp, host.data());
+        BDR_HIP(hipMemcpyAsync(dev, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        return BDR_OK;
+    }
+};
+
+}  // namespace

@@ -6,7 +6,8 @@
   GaussianActorConfig  util/actor.rs:36-55 (policy_config: Mlp3's MlpConfig, opt_config, min/max_log_std, action_limit)
   ActionLimit          util/actor.rs:29-32 (Tanh{action_scale} | Clamp{action_min, action_max})
   CandleMlpConfig      mlp/config.rs:6-11 (activation_out: "None" | "ReLU")
-  CandleAgent          what Iql and Awac (border_amd.awac) share over the C ABI
+  AgentHandle          what the handles of Iql, Awac (border_amd.awac) and Bc (border_amd.bc) share over the C ABI
+  CandleAgent          on it, what Iql and Awac share: actor + critics + targets, the noise stream, the f32 Policy::sample
   Iql                  iql/base.rs (Agent, Policy::sample, SyncModel ships the actor)
 """
 from __future__ import annotations
@@ -131,11 +132,14 @@ def _p(a):
 ROLES = {"param": 0, "grad": 100, "exp_avg": 200, "exp_avg_sq": 300}
 
 
-class CandleAgent:
-    """The handle of a candle-family agent (csrc/candle_actor.hpp): its lifecycle, Agent::opt, Policy::sample (bdr_<KIND>_sample*),
-    the parameter views of the actor and the critics, SyncModel (the actor) and the checkpoint files CKPT_STEMS."""
-    KIND = ""                        # "iql" | "awac": the bdr_<KIND>_* entry points
+class AgentHandle:
+    """The handle of an agent on the dense-agent core (csrc/dense_agent.hpp): its lifecycle, Agent::opt, the parameter views,
+    SyncModel (the model SYNC_MODEL) and the checkpoint files CKPT_STEMS.  A subclass names its entry points (KIND), its models
+    (WHICH, or _model_id) and adds its update_on_batch, probes and Policy::sample."""
+    KIND = ""                        # "iql" | "awac" | "bc": the bdr_<KIND>_* entry points
     CKPT_STEMS: Tuple[str, ...] = ()
+    SYNC_MODEL = ""                  # the model SyncModel ships (model 0) and the default of the parameter views
+    WHICH: dict = {}                 # ParamExchange / ModelMailbox names of model 0
 
     def __init__(self, config):
         self.config = config
@@ -163,28 +167,16 @@ class CandleAgent:
     def handle(self):
         return self._h
 
-    @property
-    def n_critics(self) -> int:
-        return self.config.critic_config.n_nets
-
     def _model_id(self, name: str) -> int:
-        """actor 0, critic_i 1 + i, critic_tgt_i 1 + n_critics + i; an agent's own models follow"""
-        nc = self.n_critics
-        if name.startswith("critic_tgt_"):
-            return 1 + nc + int(name[len("critic_tgt_"):])
-        if name.startswith("critic_"):
-            return 1 + int(name[len("critic_"):])
-        return {"actor": 0}[name]
+        return self.WHICH[name]
 
     # model ids (bdr_agent_get_params `which`)
-    def which(self, name: str, role: str = "param") -> int:
-        return self._model_id(name) + ROLES[role]
+    def which(self, name: Optional[str] = None, role: str = "param") -> int:
+        return self._model_id(name or self.SYNC_MODEL) + ROLES[role]
 
-    WHICH = {"actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the actor == model 0
-
-    def arena_device_ptr(self, which="actor"):
+    def arena_device_ptr(self, which: Optional[str] = None):
         ptr, n = C.c_void_p(), C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
+        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which or self.SYNC_MODEL], C.byref(ptr), C.byref(n)))
         return ptr.value, n.value
 
     def train(self):
@@ -203,6 +195,73 @@ class CandleAgent:
     def profile_enable(self, on: bool = True):
         _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
 
+    def sync(self):
+        _lib.check(_lib.lib().bdr_agent_sync(self._h))
+
+    @property
+    def n_opts(self) -> int:
+        n = C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
+        return n.value
+
+    def param_count(self, name: Optional[str] = None) -> int:
+        n = C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_param_count_of(self._h, self.which(name), C.byref(n)))
+        return n.value
+
+    def get_params(self, name: Optional[str] = None, role="param") -> np.ndarray:
+        out = np.empty(self.param_count(name), np.float32)
+        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.which(name, role), _p(out), out.size))
+        return out
+
+    def set_params(self, params, name: Optional[str] = None, role="param") -> None:
+        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.which(name, role), _p(p), p.size))
+
+    def model_info(self):
+        """SyncModel::model_info: the parameters of SYNC_MODEL."""
+        return self.n_opts, self.get_params()
+
+    def sync_model(self, model_info) -> None:
+        self.set_params(model_info)
+
+    def set_checkpoint_format(self, fmt: str) -> None:
+        """"tch" (default): the reference's `<stem>.pt` files (safetensors, as candle's VarMap writes them); "safetensors":
+        `<stem>.safetensors`."""
+        from .checkpoint import FORMATS
+        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
+        self._ckpt_ext = {"tch": ".pt", "safetensors": ".safetensors"}[fmt]
+
+    def save_params(self, path: str):
+        """The files of CKPT_STEMS (the candle agents' critic.tgt holds the ONLINE critics, util/critic.rs:272-285)."""
+        os.makedirs(path, exist_ok=True)
+        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
+        ext = getattr(self, "_ckpt_ext", ".pt")
+        return [os.path.join(path, stem + ext) for stem in self.CKPT_STEMS]
+
+    def load_params(self, path: str):
+        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))
+
+
+class CandleAgent(AgentHandle):
+    """The handle of a candle-family agent (csrc/candle_actor.hpp): the models of an actor with critics and their targets, the
+    device noise stream and the f32 Policy::sample (bdr_<KIND>_sample*); SyncModel ships the actor."""
+    SYNC_MODEL = "actor"
+    WHICH = {"actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the actor == model 0
+
+    @property
+    def n_critics(self) -> int:
+        return self.config.critic_config.n_nets
+
+    def _model_id(self, name: str) -> int:
+        """actor 0, critic_i 1 + i, critic_tgt_i 1 + n_critics + i; an agent's own models follow"""
+        nc = self.n_critics
+        if name.startswith("critic_tgt_"):
+            return 1 + nc + int(name[len("critic_tgt_"):])
+        if name.startswith("critic_"):
+            return 1 + int(name[len("critic_"):])
+        return {"actor": 0}[name]
+
     def draw_noise(self, n: int) -> np.ndarray:
         """n draws of the agent's device noise stream (bdr_agent_draw_noise): the N(0,1) numbers of Policy::sample in train mode."""
         from .dqn import draw_noise
@@ -218,53 +277,6 @@ class CandleAgent:
         out = np.empty((n, self.config.act_dim), np.float32)
         _lib.check(getattr(_lib.lib(), f"bdr_{self.KIND}_sample_device")(self._h, n, C.c_void_p(obs_dev), row_stride, _p(out)))
         return out
-
-    def sync(self):
-        _lib.check(_lib.lib().bdr_agent_sync(self._h))
-
-    @property
-    def n_opts(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
-        return n.value
-
-    def param_count(self, name="actor") -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_param_count_of(self._h, self.which(name), C.byref(n)))
-        return n.value
-
-    def get_params(self, name="actor", role="param") -> np.ndarray:
-        out = np.empty(self.param_count(name), np.float32)
-        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.which(name, role), _p(out), out.size))
-        return out
-
-    def set_params(self, params, name="actor", role="param") -> None:
-        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
-        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.which(name, role), _p(p), p.size))
-
-    def model_info(self):
-        """SyncModel::model_info: the actor's parameters."""
-        return self.n_opts, self.get_params("actor")
-
-    def sync_model(self, model_info) -> None:
-        self.set_params(model_info, "actor")
-
-    def set_checkpoint_format(self, fmt: str) -> None:
-        """"tch" (default): the reference's `<stem>.pt` files (safetensors, as candle's VarMap writes them); "safetensors":
-        `<stem>.safetensors`."""
-        from .checkpoint import FORMATS
-        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
-        self._ckpt_ext = {"tch": ".pt", "safetensors": ".safetensors"}[fmt]
-
-    def save_params(self, path: str):
-        """The files of CKPT_STEMS; critic.tgt holds the ONLINE critics (util/critic.rs:272-285)."""
-        os.makedirs(path, exist_ok=True)
-        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
-        ext = getattr(self, "_ckpt_ext", ".pt")
-        return [os.path.join(path, stem + ext) for stem in self.CKPT_STEMS]
-
-    def load_params(self, path: str):
-        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))
 
 
 class Iql(CandleAgent):
