@@ -183,12 +183,21 @@ class DeviceBatch(C.Structure):
                 ("ixs", C.c_void_p), ("weight", C.c_void_p)]
 
 
+BDR_DTYPE_F32, BDR_DTYPE_F64 = 0, 1
+
+
+class ReplaySummaryC(C.Structure):
+    _fields_ = [("n_terminated", C.c_uint64), ("n_truncated", C.c_uint64), ("sum_rewards", C.c_float), ("reserved", C.c_int32)]
+
+
 # every symbol include/border_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "bdr_last_error", "bdr_last_error_is_deferred", "bdr_device_count", "bdr_version",
     "bdr_replay_create", "bdr_replay_destroy", "bdr_replay_push", "bdr_replay_push_device", "bdr_replay_len", "bdr_replay_head", "bdr_replay_frames_used",
     "bdr_replay_sample_indices", "bdr_replay_batch", "bdr_replay_last_batch", "bdr_replay_fill_synthetic",
     "bdr_replay_read_rows",
+    "bdr_obs_norm_create", "bdr_obs_norm_destroy", "bdr_obs_norm_accumulate", "bdr_obs_norm_finish", "bdr_obs_norm_set", "bdr_obs_norm_get",
+    "bdr_obs_norm_apply", "bdr_obs_norm_apply_device", "bdr_replay_push_episode", "bdr_replay_summarize",
     "bdr_per_config_default", "bdr_replay_enable_per", "bdr_replay_update_priority", "bdr_replay_batch_weights",
     "bdr_replay_per_info", "bdr_replay_per_read", "bdr_replay_per_get", "bdr_dqn_update_on_batch_weighted",
     "bdr_dqn_config_default", "bdr_dqn_create", "bdr_agent_destroy", "bdr_agent_set_train", "bdr_agent_is_train",
@@ -264,6 +273,16 @@ def lib() -> C.CDLL:
     L.bdr_replay_last_batch.argtypes = [vp, C.POINTER(DeviceBatch)]
     L.bdr_replay_fill_synthetic.argtypes = [vp, u64, u64, i32, i32]
     L.bdr_replay_read_rows.argtypes = [vp, u64, u64, vp, vp, vp, vp, vp, vp]
+    L.bdr_obs_norm_create.argtypes = [i32, u64, C.POINTER(vp)]
+    L.bdr_obs_norm_destroy.argtypes = [vp]
+    L.bdr_obs_norm_accumulate.argtypes = [vp, u64, vp, i32]
+    L.bdr_obs_norm_finish.argtypes = [vp]
+    L.bdr_obs_norm_set.argtypes = [vp, vp, vp]
+    L.bdr_obs_norm_get.argtypes = [vp, vp, vp, C.POINTER(u64)]
+    L.bdr_obs_norm_apply.argtypes = [vp, u64, vp, i32, vp]
+    L.bdr_obs_norm_apply_device.argtypes = [vp, u64, vp, u64, i32, vp, u64]
+    L.bdr_replay_push_episode.argtypes = [vp, u64, vp, i32, vp, vp, vp, vp, vp]
+    L.bdr_replay_summarize.argtypes = [vp, C.POINTER(ReplaySummaryC)]
     L.bdr_dqn_config_default.argtypes = [C.POINTER(DqnConfigC)]
     L.bdr_dqn_create.argtypes = [C.POINTER(DqnConfigC), C.POINTER(vp)]
     L.bdr_agent_destroy.argtypes = [vp]

@@ -102,6 +102,8 @@ struct bdr_replay {
     unsigned* done_ticket = nullptr;                        // device: records of the current small push that are finished
     unsigned dev_rows_checks = 0;                            // counts cache hits of dev_rows_ok (every 1024th one re-validates)
     const void* dev_rows_ok[2] = {nullptr, nullptr};       // bdr_replay_push_device: the obs / next_obs base addresses that passed the device-pointer check last
+    // bdr_replay_push_episode: pinned staging (two halves of ep_half bytes: raw rows | act / reward / flags) and its device twin
+    uint8_t* ep_stage = nullptr; uint8_t* d_ep = nullptr; uint64_t ep_half = 0; hipEvent_t ep_free[2] = {nullptr, nullptr};
     uint8_t* d_tails = nullptr; uint64_t tails_cap = 0;   // bdr_replay_push_device: device copy of a run's act / reward / flags
     // device batch buffers (lazily sized)
     uint64_t batch_cap = 0, batch_n = 0;
@@ -128,6 +130,40 @@ struct bdr_replay {
     uint8_t* fstage = nullptr;             // pinned staging for new frames
     uint64_t fstage_frames = 0;
 };
+
+// Observation normaliser (dataset.hip): per-column mean / std of a dataset and the element contract
+//   z = ((float)x - mean) / std     (two separately rounded f32 operations, the division correctly rounded)
+// that bdr_obs_norm_apply[_device] and bdr_replay_push_episode (replay.hip, k_push_episode) share.
+struct bdr_obs_norm {
+    int32_t device = 0;
+    uint64_t dim = 0;
+    bool ready = false;                    // finish() or set() happened: mean / std are valid, accumulate is refused
+    uint64_t count = 0;                    // rows accumulated so far
+    uint64_t merged = 0, fill_rows = 0;    // of them: folded into d_mean / d_m2; waiting in the current staging half
+    int32_t fill_dtype = 0; int half = 0;  // dtype of the waiting rows; the half being filled
+    hipStream_t stream = nullptr;
+    double *d_mean = nullptr, *d_m2 = nullptr;   // [dim] running mean and sum of squared deviations (float64, device)
+    double* d_part = nullptr;              // [chunk_rows / 64][2][dim] per-block (mean, M2) of the chunk in flight
+    float *d_meanf = nullptr, *d_stdf = nullptr; // [dim] the f32 statistics the kernels read
+    std::vector<float> mean, std;          // host copies (the host path of apply, get)
+    uint8_t* stage = nullptr;              // pinned: two halves of stage_half bytes
+    uint8_t* d_raw = nullptr;              // device twin of the staging halves
+    uint64_t stage_half = 0, chunk_rows = 0;
+    hipEvent_t half_free[2] = {nullptr, nullptr};
+};
+
+namespace bdr {
+// z of one element, shared by every kernel that normalises (the statement of the contract in code)
+__host__ __device__ __forceinline__ float obs_norm_z(float x, float mean, float std)
+{
+#pragma clang fp contract(off)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(x - mean, std);
+#else
+    return (x - mean) / std;
+#endif
+}
+}  // namespace bdr
 
 namespace bdr {
 // Enqueue "draw n indices + gather" on `stream` (the consumer's stream).  Handles the

@@ -581,6 +581,9 @@ int32_t bdr_replay_destroy(bdr_replay* r)
     (void)hipFree(r->alt.obs); (void)hipFree(r->alt.next); (void)hipFree(r->alt.act); (void)hipFree(r->alt.reward);
     (void)hipFree(r->alt.term); (void)hipFree(r->alt.trunc); (void)hipFree(r->alt.ixs);
     (void)hipFree(r->d_tails); (void)hipFree(r->xo_state);
+    if (r->ep_stage) (void)hipHostFree(r->ep_stage);
+    (void)hipFree(r->d_ep);
+    for (hipEvent_t ev : r->ep_free) if (ev) (void)hipEventDestroy(ev);
     per_destroy(r->per);
     (void)hipEventDestroy(r->written); (void)hipEventDestroy(r->read);
     (void)hipStreamDestroy(r->stream);
@@ -820,6 +823,177 @@ int32_t bdr_replay_push_device(bdr_replay* r, uint64_t n, const void* obs_dev, u
     r->i = (r->i + n) % r->capacity;
     r->size += n;
     if (r->size >= r->capacity) r->size = r->capacity;
+    return BDR_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// One episode -> ring (MinariDataset::create_replay_buffer, border-minari/src/dataset.rs:80-100, with PenConverter's
+// convert_observation_batch[_next], d4rl/pen/candle.rs:104-161): the T + 1 raw observation rows are staged once, in their own
+// dtype; record k takes obs from row k and next_obs from row k + 1.
+// k_push_episode: one wave per record, four records per workgroup.  Rows k and k + 1 are one contiguous span of 2 * dim elements
+// starting at element k * dim of the staged block; a lane loads 16-byte vectors (2 float64 / 4 f32) from the 16-byte grid under
+// that span - whatever the parity of k * dim, a float64 row of 45 elements is only 8-byte aligned - converts to f32, normalises
+// (obs_norm_z, common.hpp) and stores each element into its half of the record; neighbouring lanes store neighbouring words.
+// Bounds: reads elements [floor_V(k * dim), ceil_V((k + 2) * dim)) - at most V - 1 elements in front of the span (>= element 0) and
+// behind it (the staged block carries 16 spare bytes); writes columns < dim of records pos + k < pos + m <= capacity.
+// ------------------------------------------------------------------------------------------------
+constexpr uint64_t EPISODE_STAGE_BYTES = 4ull << 20;   // one staging half of bdr_replay_push_episode: raw rows | act / reward / flags
+struct PushEpArgs {
+    uint8_t* ring; uint64_t stride, act_bytes, next_off, act_off, tail_off, pos;
+    const uint8_t* raw;      // [m + 1][dim] of T, 16-byte aligned, 16 readable bytes behind the last row
+    const uint8_t* tails;    // [m][act_bytes + 8]: act | reward f32 | is_terminated | is_truncated | 2 pad   (4-byte aligned)
+    const float* mean; const float* std;   // nullptr: conversion to f32 alone
+    uint64_t dim, m;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_push_episode(PushEpArgs a)
+{
+    constexpr uint32_t V = 16 / sizeof(T);
+    typedef T vec __attribute__((ext_vector_type(V)));
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t k = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= a.m) return;
+    uint8_t* rec = a.ring + (a.pos + k) * a.stride;
+    float* obs = reinterpret_cast<float*>(rec);
+    float* next = reinterpret_cast<float*>(rec + a.next_off);
+    const T* raw = reinterpret_cast<const T*>(a.raw);
+    const uint64_t s = k * a.dim, e1 = s + 2 * a.dim;
+    for (uint64_t e = (s & ~(uint64_t)(V - 1)) + (uint64_t)lane * V; e < e1; e += 64 * V) {
+        const vec x = *reinterpret_cast<const vec*>(raw + e);
+#pragma unroll
+        for (uint32_t i = 0; i < V; ++i) {
+            const uint64_t ee = e + i;
+            if (ee < s || ee >= e1) continue;
+            uint64_t c = ee - s;
+            const bool second = c >= a.dim;
+            if (second) c -= a.dim;
+            float z = (float)x[i];   // float64 -> f32: round to nearest even (`as f32`)
+            if (a.mean) z = obs_norm_z(z, a.mean[c], a.std[c]);
+            (second ? next : obs)[c] = z;
+        }
+    }
+    const uint32_t* t = reinterpret_cast<const uint32_t*>(a.tails + k * (a.act_bytes + 8));
+    uint32_t* act = reinterpret_cast<uint32_t*>(rec + a.act_off);
+    const uint64_t aw = a.act_bytes / 4;
+    for (uint64_t i = lane; i < aw; i += 64) act[i] = t[i];
+    if (lane == 0) *reinterpret_cast<uint32_t*>(rec + a.tail_off) = t[aw];                 // reward
+    if (lane == 1) *reinterpret_cast<uint16_t*>(rec + a.tail_off + 4) = (uint16_t)t[aw + 1];   // is_terminated | is_truncated
+}
+
+extern "C" {
+
+int32_t bdr_replay_push_episode(bdr_replay* r, uint64_t T, const void* observations, int32_t obs_dtype, const void* act, const float* reward,
+                                const int8_t* term, const int8_t* trunc, const bdr_obs_norm* norm)
+{
+    BDR_REQUIRE(r, "null replay handle");
+    BDR_REQUIRE(obs_dtype == BDR_DTYPE_F32 || obs_dtype == BDR_DTYPE_F64, "obs_dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64");
+    BDR_REQUIRE(!r->frame_stack, "bdr_replay_push_episode writes f32 rows: not for a buffer with frame_stack > 0 (push stacked host rows with bdr_replay_push)");
+    const uint64_t dim = r->obs_bytes / 4;
+    if (norm) {
+        BDR_REQUIRE(norm->ready, "the normaliser has no statistics yet (bdr_obs_norm_finish / bdr_obs_norm_set)");
+        BDR_REQUIRE(norm->dim * 4 == r->obs_bytes, "dim mismatch: the normaliser has %llu columns, the buffer's observation row is %llu bytes (dim * 4 must equal obs_row_bytes)",
+                    (unsigned long long)norm->dim, (unsigned long long)r->obs_bytes);
+        BDR_REQUIRE(norm->device == r->device, "the normaliser lives on device %d, the buffer on device %d", norm->device, r->device);
+    }
+    if (T == 0) return BDR_OK;
+    BDR_REQUIRE(observations && act && reward && term && trunc, "null episode field");
+    BDR_HIP(hipSetDevice(r->device));
+    const uint64_t tw = r->act_bytes + 8, rb = dim * (obs_dtype == BDR_DTYPE_F64 ? 8 : 4);
+    if (!r->ep_stage) {   // sized for float64 rows: a pass holds at least one record (two rows)
+        r->ep_half = std::max<uint64_t>(EPISODE_STAGE_BYTES, round_up(2 * dim * 8 + 48 + tw, 16));
+        BDR_HIP(hipHostMalloc((void**)&r->ep_stage, 2 * r->ep_half, hipHostMallocDefault));
+        BDR_HIP(hipMalloc((void**)&r->d_ep, 2 * r->ep_half));
+        for (hipEvent_t& ev : r->ep_free) BDR_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    BDR_TRY(wait_for_reader(r, r->stream));  // WAR: do not overwrite rows a consumer's gather may still be reading
+    // a pass of m records stages round_up((m + 1) * rb, 16) + 16 bytes of rows and m * tw bytes of small fields
+    const uint64_t fit = (r->ep_half - rb - 32) / (rb + tw);
+    const uint8_t* o = (const uint8_t*)observations; const uint8_t* a = (const uint8_t*)act;
+    uint64_t done = 0;
+    for (int half = 0; done < T; half ^= 1) {
+        const uint64_t pos = (r->i + done) % r->capacity;
+        const uint64_t m = std::min(std::min(T - done, fit), r->capacity - pos);   // consecutive passes overlap by one row
+        const uint64_t tails_off = round_up((m + 1) * rb, 16) + 16;
+        uint8_t* st = r->ep_stage + half * r->ep_half;
+        uint8_t* dv = r->d_ep + half * r->ep_half;
+        BDR_HIP(hipEventSynchronize(r->ep_free[half]));   // the copy out of this half (two passes ago) has finished
+        memcpy(st, o + done * rb, (m + 1) * rb);
+        memset(st + (m + 1) * rb, 0, tails_off - (m + 1) * rb);
+        for (uint64_t k = 0; k < m; ++k) {
+            uint8_t* t = st + tails_off + k * tw;
+            const uint64_t s = done + k;
+            memcpy(t, a + s * r->act_bytes, r->act_bytes);
+            memcpy(t + r->act_bytes, &reward[s], 4);
+            t[r->act_bytes + 4] = (uint8_t)term[s]; t[r->act_bytes + 5] = (uint8_t)trunc[s]; t[r->act_bytes + 6] = t[r->act_bytes + 7] = 0;
+        }
+        BDR_HIP(hipMemcpyAsync(dv, st, tails_off + m * tw, hipMemcpyHostToDevice, r->stream));
+        BDR_HIP(hipEventRecord(r->ep_free[half], r->stream));
+        PushEpArgs pa{r->ring, r->stride, r->act_bytes, r->next_off, r->act_off, r->tail_off, pos, dv, dv + tails_off,
+                      norm ? norm->d_meanf : nullptr, norm ? norm->d_stdf : nullptr, dim, m};
+        const dim3 grid((uint32_t)((m + 3) / 4));
+        if (obs_dtype == BDR_DTYPE_F64) hipLaunchKernelGGL(k_push_episode<double>, grid, dim3(256), 0, r->stream, pa);
+        else hipLaunchKernelGGL(k_push_episode<float>, grid, dim3(256), 0, r->stream, pa);
+        BDR_HIP(hipGetLastError());
+        done += m;
+    }
+    if (r->per) {   // base.rs:304-306 set_priority(len), as bdr_replay_push
+        if (r->written_lazy) { r->written_lazy = false; BDR_HIP(hipEventRecord(r->written, r->stream)); }
+        BDR_HIP(hipStreamWaitEvent(r->stream, r->written, 0));
+        BDR_TRY(per_push(r->per, r->i, T, r->stream));
+        BDR_HIP(hipEventRecord(r->written, r->stream)); mark_written(r);
+    } else {
+        r->written_lazy = true; mark_written(r);   // `written` is recorded when a consumer on another stream asks for it (wait_for_writer)
+    }
+    // as bdr_replay_push: the caller's arrays are in the pinned staging area, the copies and kernels are in flight on the buffer's stream
+    r->i = (r->i + T) % r->capacity;
+    r->size = std::min(r->size + T, r->capacity);
+    return BDR_OK;
+}
+
+}  // extern "C"
+
+// num_terminated_flags / num_truncated_flags / sum_rewards (base.rs:243-267).  The kernel packs reward and flags of rows [0, len)
+// into dense arrays; the host counts and folds the rewards left to right in f32 (Iterator::sum, :265) - once per dataset.
+__global__ __launch_bounds__(256) void k_pack_tails(const uint8_t* __restrict__ ring, uint64_t stride, uint64_t tail_off, uint64_t n,
+                                                    float* __restrict__ reward, int8_t* __restrict__ term, int8_t* __restrict__ trunc)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const uint8_t* t = ring + k * stride + tail_off;
+    reward[k] = *reinterpret_cast<const float*>(t);
+    term[k] = (int8_t)t[4];
+    trunc[k] = (int8_t)t[5];
+}
+
+extern "C" {
+
+int32_t bdr_replay_summarize(bdr_replay* r, bdr_replay_summary* out)
+{
+    BDR_REQUIRE(r && out, "null argument");
+    *out = bdr_replay_summary{0, 0, 0.f, 0};
+    const uint64_t n = r->size;
+    if (n == 0) return BDR_OK;
+    BDR_HIP(hipSetDevice(r->device));
+    uint8_t* d = nullptr;
+    BDR_HIP(hipMalloc((void**)&d, n * 6));
+    std::vector<uint8_t> hbuf(n * 6);
+    hipLaunchKernelGGL(k_pack_tails, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, r->stream, r->ring, r->stride,
+                       r->frame_stack ? r->rec_tail_off : r->tail_off, n, (float*)d, (int8_t*)(d + n * 4), (int8_t*)(d + n * 5));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(hbuf.data(), d, n * 6, hipMemcpyDeviceToHost, r->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(BDR_ERR_HIP, "bdr_replay_summarize: %s", hipGetErrorString(e));
+    const float* rew = reinterpret_cast<const float*>(hbuf.data());
+    float sum = 0.f;
+    for (uint64_t k = 0; k < n; ++k) {
+        sum += rew[k];
+        out->n_terminated += hbuf[n * 4 + k] != 0;
+        out->n_truncated += hbuf[n * 5 + k] != 0;
+    }
+    out->sum_rewards = sum;
     return BDR_OK;
 }
 

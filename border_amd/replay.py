@@ -145,6 +145,43 @@ class SimpleReplayBuffer:
         _lib.check(_lib.lib().bdr_replay_push_device(self._h, n, C.c_void_p(obs_dev), obs_stride, _p(act), C.c_void_p(next_obs_dev), next_obs_stride,
                                                      _p(reward), _p(term), _p(trunc)))
 
+    def push_episode(self, observations, act, reward, is_terminated, is_truncated, normalizer=None) -> None:
+        """One episode (`bdr_replay_push_episode`; dataset.rs:80-100): `observations` has T + 1 rows (float64 as Minari stores them, or
+        float32), the other arrays T.  The result is that of push(N(observations[:-1]), act, N(observations[1:]), ...) with N the
+        normalizer's (x.astype(f32) - mean) / std (`dataset.ObsNormalizer`; None: the conversion alone) - the raw rows cross PCIe once
+        and are converted, normalised and written into both halves of every record on the device."""
+        reward = np.ascontiguousarray(reward, dtype=np.float32).reshape(-1)
+        n = reward.shape[0]
+        observations = np.asarray(observations)
+        if observations.dtype != np.float32:
+            observations = observations.astype(np.float64, copy=False)
+        observations = np.ascontiguousarray(observations).reshape(observations.shape[0], -1)
+        if self.obs_dtype != np.float32 or observations.shape[1] * 4 != self.obs_bytes:
+            raise _lib.BdrError(1, f"dim mismatch: push_episode writes float32 rows of {observations.shape[1]} columns, the buffer's rows are "
+                                   f"{self.obs_bytes} bytes of {self.obs_dtype}")
+        if observations.shape[0] != n + 1:
+            raise _lib.BdrError(1, f"an episode of {n} transitions has {n + 1} observation rows, not {observations.shape[0]}")
+        act = np.ascontiguousarray(act, dtype=self.act_dtype).reshape(n, self.act_bytes // self.act_dtype.itemsize)   # (n may be 0)
+        term = np.ascontiguousarray(is_terminated, dtype=np.int8).reshape(n)
+        trunc = np.ascontiguousarray(is_truncated, dtype=np.int8).reshape(n)
+        dtype = _lib.BDR_DTYPE_F32 if observations.dtype == np.float32 else _lib.BDR_DTYPE_F64
+        _lib.check(_lib.lib().bdr_replay_push_episode(self._h, n, _p(observations), dtype, _p(act), _p(reward), _p(term), _p(trunc),
+                                                      None if normalizer is None else normalizer.handle))
+
+    def summary(self) -> dict:
+        """num_terminated_flags / num_truncated_flags / sum_rewards (base.rs:248-267) over rows [0, len); sum_rewards is the
+        left-to-right f32 sum."""
+        o = _lib.ReplaySummaryC()
+        _lib.check(_lib.lib().bdr_replay_summarize(self._h, C.byref(o)))
+        return {"num_terminated_flags": o.n_terminated, "num_truncated_flags": o.n_truncated, "sum_rewards": np.float32(o.sum_rewards)}
+
+    def whole_actions(self) -> np.ndarray:
+        """base.rs:243-246: the actions of rows [0, len)."""
+        n = self.len()
+        act = np.empty((n,) + self.act_shape, self.act_dtype)
+        _lib.check(_lib.lib().bdr_replay_read_rows(self._h, 0, n, None, _p(act), None, None, None, None))
+        return act
+
     def len(self) -> int:
         n = C.c_uint64()
         _lib.check(_lib.lib().bdr_replay_len(self._h, C.byref(n)))

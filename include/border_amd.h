@@ -163,6 +163,59 @@ BDR_API int32_t bdr_replay_read_rows(bdr_replay* r, uint64_t first, uint64_t n, 
                                      void* next_obs, float* reward, int8_t* term, int8_t* trunc);
 
 /* ------------------------------------------------------------------------------------------
+ * Episode datasets and observation normalisation  (border-minari/src/dataset.rs:64-109 MinariDataset::create_replay_buffer,
+ * border-minari/src/d4rl/pen/candle.rs:42-161 PenConverter)
+ * ---------------------------------------------------------------------------------------- */
+#define BDR_DTYPE_F32 0
+#define BDR_DTYPE_F64 1          /* Minari stores observations as float64 (pyobj_to_arrayd::<f64, f32>, border-minari/src/util.rs) */
+
+/* PenConverter's per-column mean / std (pen/candle.rs:42-69) and the normalisation it applies to every observation, in the
+ * replay buffer (:104-124) and at acting time (:83-87).  Element contract, for every input dtype: a float64 element is first
+ * rounded to f32 (round to nearest even, Rust's `as f32`), then z = (x - mean) / std in f32 - two separately rounded operations,
+ * the division correctly rounded (ndarray's `(&obs.0 - &self.mean) / &self.std`, :71-74).  The host path and the device kernels
+ * give the same bits: those of numpy's (x.astype(float32) - mean32) / std32. */
+typedef struct bdr_obs_norm bdr_obs_norm;
+BDR_API int32_t bdr_obs_norm_create(int32_t device, uint64_t dim, bdr_obs_norm** out);
+BDR_API int32_t bdr_obs_norm_destroy(bdr_obs_norm* h);
+/* Statistics (pen/candle.rs:48-66): the caller passes the rows that count - the reference drops the last row of every episode
+ * before it concatenates (:56, :146-152).  rows: host [n_rows][dim] of `dtype`.  Accumulation runs on the device in float64 over
+ * the f32-rounded elements, in a fixed order (count / mean / M2 per block of 64 rows, blocks merged in row order: Chan et al.),
+ * so the same sequence of calls gives the same bits.  finish: mean = sum / n, std = sqrt(sum (x - mean)^2 / (n - 1))
+ * (`std_axis(Axis(0), 1.0)`), each rounded to f32 once.  The statement of record is "the float64 result, rounded": the reference
+ * accumulates in f32 in ndarray's own order.  finish fails with BDR_ERR_INVALID when n < 2 or when a column's std is zero or not
+ * finite (the message names the first such column; the reference would fill the buffer with NaN).  accumulate after finish or
+ * after set: BDR_ERR_INVALID. */
+BDR_API int32_t bdr_obs_norm_accumulate(bdr_obs_norm* h, uint64_t n_rows, const void* rows, int32_t dtype);
+BDR_API int32_t bdr_obs_norm_finish(bdr_obs_norm* h);
+/* Statistics computed elsewhere (a saved converter): dim floats each; a zero or non-finite std is BDR_ERR_INVALID.  get: the
+ * statistics in use and the number of rows they were computed from (0 after set); any pointer may be NULL. */
+BDR_API int32_t bdr_obs_norm_set(bdr_obs_norm* h, const float* mean, const float* std);
+BDR_API int32_t bdr_obs_norm_get(const bdr_obs_norm* h, float* mean_out, float* std_out, uint64_t* count_out);
+/* convert_observation (pen/candle.rs:83-87): n rows of `dtype` -> normalised f32 rows.  apply: host [n][dim] -> host [n][dim],
+ * computed on the host.  apply_device: rows in HBM of the normaliser's GPU, row k at rows_dev + k * row_stride bytes, written to
+ * out_dev + k * out_stride bytes - what bdr_*_sample_device takes, so an observation that lives on the device is normalised there. */
+BDR_API int32_t bdr_obs_norm_apply(const bdr_obs_norm* h, uint64_t n, const void* rows, int32_t dtype, float* out);
+BDR_API int32_t bdr_obs_norm_apply_device(const bdr_obs_norm* h, uint64_t n, const void* rows_dev, uint64_t row_stride,
+                                          int32_t dtype, float* out_dev, uint64_t out_stride);
+
+/* One episode into the ring (dataset.rs:80-100 + pen/candle.rs:104-161): `observations` is host [T+1][dim] of `obs_dtype`, the
+ * other arrays have T rows.  By definition the result is that of
+ *   bdr_replay_push(r, T, N(observations[0:T]), act, N(observations[1:T+1]), reward, is_terminated, is_truncated)
+ * with N = the normaliser's element contract (norm == NULL: the conversion to f32 alone) - ring bytes, cursor, size and PER
+ * priorities are identical; T may need several staging passes and may wrap the ring.  It differs in cost only: the T+1 raw rows
+ * cross PCIe once, in their own dtype, and a kernel converts, normalises and writes both halves of every record; no normalised
+ * copy exists on the host.  The ring's rows must be f32 (dim * 4 == obs_row_bytes), `norm` of the same dim and device; a
+ * frame_stack > 0 ring is refused (BDR_ERR_INVALID); T == 0 is a no-op.  Returns when the caller's arrays are free. */
+BDR_API int32_t bdr_replay_push_episode(bdr_replay* r, uint64_t T, const void* observations, int32_t obs_dtype,
+                                        const void* act, const float* reward, const int8_t* is_terminated,
+                                        const int8_t* is_truncated, const bdr_obs_norm* norm);
+
+/* num_terminated_flags / num_truncated_flags / sum_rewards (generic_replay_buffer/base.rs:243-267) over rows [0, len): the counts
+ * are exact, sum_rewards is the LEFT-TO-RIGHT f32 sum (`Iterator::sum` is a sequential fold, :265) - the order is the contract. */
+typedef struct { uint64_t n_terminated, n_truncated; float sum_rewards; int32_t reserved; } bdr_replay_summary;
+BDR_API int32_t bdr_replay_summarize(bdr_replay* r, bdr_replay_summary* out);
+
+/* ------------------------------------------------------------------------------------------
  * Prioritized experience replay  (SimpleReplayBufferConfig::per_config, config.rs:45-83;
  * generic_replay_buffer/base/sum_tree.rs; base/iw_scheduler.rs)
  * ---------------------------------------------------------------------------------------- */

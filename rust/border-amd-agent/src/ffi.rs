@@ -15,6 +15,8 @@ pub const BDR_ERR_COMM: i32 = 6;
 
 pub const BDR_RNG_STDRNG: i32 = 0;
 pub const BDR_RNG_XOSHIRO256PP: i32 = 1;
+pub const BDR_DTYPE_F32: i32 = 0;
+pub const BDR_DTYPE_F64: i32 = 1;
 pub const BDR_PER_NORMALIZE_ALL: i32 = 0;
 pub const BDR_PER_NORMALIZE_BATCH: i32 = 1;
 pub const BDR_NET_ATARI_CNN: i32 = 0;
@@ -82,6 +84,18 @@ pub struct bdr_model_mailbox {
 #[repr(C)]
 pub struct bdr_atari_prep {
     _private: [u8; 0],
+}
+
+/// Opaque handle of an observation normaliser (`bdr_obs_norm_*`): an uninhabited type, only ever used behind a pointer.
+pub enum bdr_obs_norm {}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bdr_replay_summary {
+    pub n_terminated: u64,
+    pub n_truncated: u64,
+    pub sum_rewards: f32,
+    pub reserved: i32,
 }
 
 #[repr(C)]
@@ -594,6 +608,34 @@ extern "C" {
 
     // ---- prioritized replay
     pub fn bdr_per_config_default(c: *mut bdr_per_config);
+    pub fn bdr_obs_norm_create(device: i32, dim: u64, out: *mut *mut bdr_obs_norm) -> i32;
+    pub fn bdr_obs_norm_destroy(h: *mut bdr_obs_norm) -> i32;
+    pub fn bdr_obs_norm_accumulate(h: *mut bdr_obs_norm, n_rows: u64, rows: *const c_void, dtype: i32) -> i32;
+    pub fn bdr_obs_norm_finish(h: *mut bdr_obs_norm) -> i32;
+    pub fn bdr_obs_norm_set(h: *mut bdr_obs_norm, mean: *const f32, std: *const f32) -> i32;
+    pub fn bdr_obs_norm_get(h: *const bdr_obs_norm, mean_out: *mut f32, std_out: *mut f32, count_out: *mut u64) -> i32;
+    pub fn bdr_obs_norm_apply(h: *const bdr_obs_norm, n: u64, rows: *const c_void, dtype: i32, out: *mut f32) -> i32;
+    pub fn bdr_obs_norm_apply_device(
+        h: *const bdr_obs_norm,
+        n: u64,
+        rows_dev: *const c_void,
+        row_stride: u64,
+        dtype: i32,
+        out_dev: *mut f32,
+        out_stride: u64,
+    ) -> i32;
+    pub fn bdr_replay_push_episode(
+        r: *mut bdr_replay,
+        t: u64,
+        observations: *const c_void,
+        obs_dtype: i32,
+        act: *const c_void,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+        norm: *const bdr_obs_norm,
+    ) -> i32;
+    pub fn bdr_replay_summarize(r: *mut bdr_replay, out: *mut bdr_replay_summary) -> i32;
     pub fn bdr_replay_enable_per(r: *mut bdr_replay, c: *const bdr_per_config) -> i32;
     pub fn bdr_replay_update_priority(r: *mut bdr_replay, n: u64, ixs: *const u64, td_errs: *const f32) -> i32;
     pub fn bdr_replay_batch_weights(r: *mut bdr_replay, n: u64, w_out: *mut f32) -> i32;

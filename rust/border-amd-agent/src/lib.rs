@@ -13,6 +13,8 @@
 //! * [`AmdIql`] - `border-candle-agent/src/iql/base.rs` (offline RL; [`IqlConfig`] deserialises the candle YAML names).
 //! * [`AmdAwac`] - `border-candle-agent/src/awac/base.rs` (offline and online RL; [`AwacConfig`] likewise).
 //! * [`AmdBc`] - `border-candle-agent/src/bc/base.rs` (behaviour cloning; [`BcConfig`] likewise).
+//! * [`AmdObsNorm`], [`AmdReplayBuffer::push_episode`] - `border-minari`'s `PenConverter` statistics / normalisation and
+//!   `MinariDataset::create_replay_buffer`'s episode push, on the device.
 //! * [`train_async`] - `border-async-trainer/src/util.rs:31-92` on one GPU (learner + actors + device mailbox), with the
 //!   optional cross-GPU exchange over RCCL ([`Comm`]).
 //!
@@ -25,6 +27,7 @@ pub mod bc;
 pub mod bytes;
 pub mod comm;
 pub mod config;
+pub mod dataset;
 pub mod dqn;
 pub mod error;
 pub mod ffi;
@@ -44,6 +47,7 @@ pub use config::{
 };
 pub use awac::AmdAwac;
 pub use bc::AmdBc;
+pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;

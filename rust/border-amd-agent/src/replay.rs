@@ -6,6 +6,7 @@
 //! handle to the library, which draws and gathers on the device; `batch()` exists for callers that want the host copy.
 use crate::{
     bytes::RowBatch,
+    dataset::{AmdObsNorm, ObsElem},
     error::{check, expect},
     ffi,
 };
@@ -103,6 +104,66 @@ where
 
     pub fn capacity(&self) -> usize {
         self.capacity
+    }
+
+    /// One episode (`border-minari/src/dataset.rs:80-100`, `d4rl/pen/candle.rs:104-161`): `observations` holds the `T + 1` raw
+    /// rows (`[T + 1][dim]`, `f64` as Minari stores them, or `f32`), `act` the `T` action rows.  The result is that of `push` with
+    /// `obs = N(observations[..T])`, `next_obs = N(observations[1..])`, `N` = `norm`'s `(x as f32 - mean) / std` (`None`: the
+    /// conversion alone); the raw rows cross PCIe once and are converted, normalised and written on the device.
+    pub fn push_episode<X: ObsElem>(
+        &mut self,
+        observations: &[X],
+        act: &A,
+        reward: &[f32],
+        is_terminated: &[i8],
+        is_truncated: &[i8],
+        norm: Option<&AmdObsNorm>,
+    ) -> Result<()> {
+        let t = reward.len();
+        let dim = O::ROW_BYTES / 4;
+        anyhow::ensure!(observations.len() == (t + 1) * dim, "an episode of {} transitions has {} observation rows of {} columns", t, t + 1, dim);
+        anyhow::ensure!(act.n_rows() == t && is_terminated.len() == t && is_truncated.len() == t, "episode fields differ in length");
+        check(unsafe {
+            ffi::bdr_replay_push_episode(
+                self.h,
+                t as u64,
+                observations.as_ptr() as *const c_void,
+                X::DTYPE,
+                act.as_bytes().as_ptr() as *const c_void,
+                reward.as_ptr(),
+                is_terminated.as_ptr(),
+                is_truncated.as_ptr(),
+                norm.map_or(std::ptr::null(), |n| n.handle() as *const ffi::bdr_obs_norm),
+            )
+        })
+    }
+
+    /// `(num_terminated_flags, num_truncated_flags, sum_rewards)` over rows `[0, len)` (`base.rs:248-267`); `sum_rewards` is the
+    /// left-to-right `f32` sum of `Iterator::sum`.
+    pub fn summary(&mut self) -> Result<(usize, usize, f32)> {
+        let mut s = ffi::bdr_replay_summary::default();
+        check(unsafe { ffi::bdr_replay_summarize(self.h, &mut s) })?;
+        Ok((s.n_terminated as usize, s.n_truncated as usize, s.sum_rewards))
+    }
+
+    /// `base.rs:243-246`: the actions of rows `[0, len)`.
+    pub fn whole_actions(&mut self) -> Result<A> {
+        let n = self.len();
+        let mut act = vec![0u8; n * A::ROW_BYTES];
+        check(unsafe {
+            ffi::bdr_replay_read_rows(
+                self.h,
+                0,
+                n as u64,
+                std::ptr::null_mut(),
+                act.as_mut_ptr() as *mut c_void,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        })?;
+        Ok(A::from_bytes(act, n))
     }
 
     /// The write cursor `i` of the reference's struct.
