@@ -16,5 +16,6 @@ from . import checkpoint  # noqa: F401
 from .atari import AtariDeviceEnv, AtariPreprocessor  # noqa: F401
 from .trainer import (NativeTrainer, ParamExchange, Sampler, SimpleStepProcessor, Step, SyntheticEnv, Trainer, TrainerConfig,  # noqa: F401
                       shard_seed)
+from .evaluator import EvalResult, Evaluator  # noqa: F401
 from .async_trainer import (ActorManagerConfig, ActorStat, AsyncTrainer, AsyncTrainerConfig, AsyncTrainStat, ModelMailbox,  # noqa: F401
                             actor_stats_fmt)

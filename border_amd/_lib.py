@@ -166,6 +166,35 @@ class TrainerOps(C.Structure):
                 ("agent_sample_device", SAMPLE_DEV_FN), ("buffer_push_device", PUSH_DEV_FN)]
 
 
+EVAL_RESET_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p)
+EVAL_STEP_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int8), C.POINTER(C.c_int8))
+SAMPLE_RAW_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p)
+SAVE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_char_p)
+
+
+class EvalEnvVtable(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("reset_with_index", EVAL_RESET_FN), ("step", EVAL_STEP_FN), ("obs_on_device", C.c_int32), ("device", C.c_int32)]
+
+
+class EvaluatorC(C.Structure):
+    _fields_ = [("n_episodes", C.c_uint64), ("obs_row_bytes", C.c_uint64), ("act_row_bytes", C.c_uint64), ("obs_dtype", C.c_int32),
+                ("norm", C.c_void_p), ("has_ref_scores", C.c_int32), ("ref_min_score", C.c_float), ("ref_max_score", C.c_float),
+                ("env", EvalEnvVtable), ("agent_sample", SAMPLE_FN), ("agent_sample_raw", SAMPLE_RAW_FN)]
+
+
+class EvalResultC(C.Structure):
+    _fields_ = [("score", C.c_float), ("has_normalized", C.c_int32), ("normalized", C.c_float), ("n_steps", C.c_uint64), ("n_episodes", C.c_uint64)]
+
+
+class TrainerPostC(C.Structure):
+    _fields_ = [("eval_interval", C.c_uint64), ("save_interval", C.c_uint64), ("evaluator", C.POINTER(EvaluatorC)), ("model_dir", C.c_char_p),
+                ("save_params", SAVE_FN)]
+
+
+BDR_ACT_PATH_DEFAULT, BDR_ACT_PATH_LAYERS, BDR_ACT_PATH_FUSED = 0, 1, 2
+BDR_TRAINER_EVENT_EVAL = 4
+
+
 class TrainerConfigC(C.Structure):
     _fields_ = [("max_opts", C.c_uint64), ("opt_interval", C.c_uint64), ("warmup_period", C.c_uint64),
                 ("record_agent_info_interval", C.c_uint64), ("record_compute_cost_interval", C.c_uint64),
@@ -217,6 +246,8 @@ ABI_SYMBOLS = [
     "bdr_atari_prep_create", "bdr_atari_prep_destroy", "bdr_atari_prep_reset", "bdr_atari_prep_step", "bdr_atari_prep_obs",
     "bdr_atari_prep_device_stacks", "bdr_atari_prep_device_prev_stacks", "bdr_atari_prep_copy_stack", "bdr_atari_clip_reward",
     "bdr_trainer_config_default", "bdr_trainer_ops_default", "bdr_trainer_train", "bdr_trainer_train_offline",
+    "bdr_evaluator_default", "bdr_evaluate", "bdr_trainer_post_default", "bdr_trainer_train_post", "bdr_trainer_train_offline_post",
+    "bdr_agent_set_act_path", "bdr_agent_sample_raw",
     "bdr_model_mailbox_create", "bdr_model_mailbox_destroy", "bdr_agent_publish_model", "bdr_agent_sync_model_from",
     "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default", "bdr_async_train",
 ]
@@ -244,7 +275,7 @@ def lib() -> C.CDLL:
         if name not in ("bdr_last_error", "bdr_version", "bdr_dqn_config_default", "bdr_sac_config_default", "bdr_iqn_config_default", "bdr_iql_config_default",
                         "bdr_awac_config_default", "bdr_bc_config_default",
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
-                        "bdr_trainer_ops_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default"):
+                        "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -253,6 +284,17 @@ def lib() -> C.CDLL:
                                     C.POINTER(TrainerStatsC)]
     L.bdr_trainer_train_offline.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(TrainerOps), OBSERVER_FN, C.c_void_p,
                                             C.POINTER(TrainerStatsC)]
+    L.bdr_evaluator_default.restype = None
+    L.bdr_evaluator_default.argtypes = [C.POINTER(EvaluatorC), C.c_void_p]
+    L.bdr_trainer_post_default.restype = None
+    L.bdr_trainer_post_default.argtypes = [C.POINTER(TrainerPostC)]
+    L.bdr_evaluate.argtypes = [C.POINTER(EvaluatorC), C.c_void_p, C.POINTER(EvalResultC)]
+    L.bdr_trainer_train_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(TrainerOps), C.POINTER(EnvVtable), C.POINTER(TrainerPostC), OBSERVER_FN,
+                                         C.c_void_p, C.POINTER(TrainerStatsC)]
+    L.bdr_trainer_train_offline_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(TrainerOps), C.POINTER(TrainerPostC), OBSERVER_FN, C.c_void_p,
+                                                 C.POINTER(TrainerStatsC)]
+    L.bdr_agent_set_act_path.argtypes = [C.c_void_p, C.c_int32]
+    L.bdr_agent_sample_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.bdr_atari_clip_reward.restype = C.c_float
     L.bdr_atari_clip_reward.argtypes = [C.c_float, C.c_int32]
     L.bdr_dqn_config_default.restype = None

@@ -103,6 +103,8 @@ class Bc(AgentHandle):
             return np.empty(n, np.int64), True
         return np.empty((n, self.config.act_dim), np.float32), False
 
+    _raw_out = _out   # AgentHandle.sample_raw / sample_raw_device: Discrete agents return indices
+
     def sample(self, obs) -> np.ndarray:
         """Policy::sample (bc/base.rs:49-59): [n, act_dim] f32 (Continuous) or [n] i64 argmax indices (Discrete)"""
         obs = np.ascontiguousarray(obs, dtype=np.float32)

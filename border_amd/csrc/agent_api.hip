@@ -772,6 +772,19 @@ int32_t bdr_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n)
     return !strcmp(a->kind(), "dqn_cnn") ? dqn_cnn_probe(a, what, out, n) : dqn_mlp_probe(a, what, out, n);
 }
 
+int32_t bdr_agent_set_act_path(bdr_agent* a, int32_t path)
+{
+    BDR_REQUIRE(a, "null agent");
+    return a->set_act_path(path);
+}
+
+int32_t bdr_agent_sample_raw(bdr_agent* a, const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype, int32_t on_device, uint64_t row_stride,
+                             float* act_out, int64_t* idx_out)
+{
+    BDR_REQUIRE(a, "null agent");
+    return a->sample_raw(norm, n, rows, dtype, on_device != 0, row_stride, act_out, idx_out);
+}
+
 int32_t bdr_agent_profile_enable(bdr_agent* a, int32_t on)
 {
     BDR_REQUIRE(a, "null agent");

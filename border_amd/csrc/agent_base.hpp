@@ -308,6 +308,16 @@ struct bdr_agent {
     // Policy::sample with f32 action rows, where the handle itself implements it (the candle-family agents: CandleAgent,
     // candle_actor.hpp).  obs: host rows, or device rows `stride` bytes apart when on_device.  false: not such an agent, nothing done.
     virtual bool sample_f32(uint64_t, const void*, bool /*on_device*/, uint64_t /*stride*/, float*, int32_t* /*status*/) { return false; }
+    // bdr_agent_set_act_path / bdr_agent_sample_raw: the DenseAgent agents (dense_agent.hpp: IQL, AWAC, BC) implement them
+    virtual int32_t set_act_path(int32_t path)
+    {
+        if (path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS) return BDR_OK;
+        return ::bdr::fail(BDR_ERR_INVALID, path == BDR_ACT_PATH_FUSED ? "this agent kind has no fused acting kernel (IQL, AWAC and BC have one)" : "unknown act path");
+    }
+    virtual int32_t sample_raw(const bdr_obs_norm*, uint64_t, const void*, int32_t, bool, uint64_t, float*, int64_t*)
+    {
+        return ::bdr::fail(BDR_ERR_INVALID, "bdr_agent_sample_raw serves IQL, AWAC and BC agents (the others sample through their own entry points)");
+    }
     virtual uint64_t param_count(int which) = 0;                  // reference-layout element count
     virtual int32_t get_params(int which, float* out, uint64_t n) = 0;
     virtual int32_t set_params(int which, const float* in, uint64_t n) = 0;

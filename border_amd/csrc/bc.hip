@@ -42,13 +42,7 @@ __device__ __forceinline__ void bc_elem(int kind, float z, float a, float inv_n,
     const float gs = g * inv_n;
     dz = gs * gp;
 }
-__device__ __forceinline__ float bc_act_out(int kind, float z)
-{
-    if (kind == BDR_ACTIVATION_RELU) return z > 0.f ? z : 0.f;
-    if (kind == BDR_ACTIVATION_TANH) return tanhf(z);
-    if (kind == BDR_ACTIVATION_SIGMOID) return 1.f / (1.f + expf(-z));
-    return z;
-}
+// (bc_act_out and bc_argmax, the element code of Policy::sample, live in dense_act.hpp: k_dense_act calls them too)
 
 // The launch's last workgroup (256 threads): the per-row sums in candle::row_sum's order - blocks of 32 rows, a butterfly per
 // block, the partials added in block order (the order does not depend on the workgroup's size) - into the record slot.
@@ -278,13 +272,7 @@ __global__ __launch_bounds__(256) void k_bc_act(BcActArgs p)
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (p.discrete) {
         if (t >= p.n) return;
-        int best = 0;
-        float bv = bc_act_out(p.kind, p.z[(size_t)t * p.ld]);
-        for (int j = 1; j < p.A; ++j) {
-            const float v = bc_act_out(p.kind, p.z[(size_t)t * p.ld + j]);
-            if (v > bv) { bv = v; best = j; }
-        }
-        p.idx[t] = best;
+        p.idx[t] = bc_argmax(p.kind, p.z + (size_t)t * p.ld, p.A);
         return;
     }
     if (t >= p.n * p.A) return;
@@ -418,6 +406,7 @@ struct Bc : DenseAgent {
         const bool disc = cfg.action_type == BDR_BC_ACTION_DISCRETE;
         BDR_REQUIRE(disc ? idx_out != nullptr : act_out != nullptr, "BC sample: a %s agent writes %s", disc ? "Discrete" : "Continuous", disc ? "idx_out" : "act_out");
         BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+        if (act_fused_on()) return act_fused(nullptr, n, obs, BDR_DTYPE_F32, obs_rows_on_device, obs_rows_on_device ? obs_row_stride : (uint64_t)O * 4, act_out, idx_out);
         BDR_HIP(hipSetDevice(device));
         BDR_TRY(ensure_batch((int)n));
         int32_t st = pack_acting_obs(obs, n, x0, net.L[0].Kp);
@@ -437,6 +426,32 @@ struct Bc : DenseAgent {
     int32_t sample_device(uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out)
     {
         return with_device_rows(obs_dev, row_stride, [&](const float* rows) { return sample(n, rows, act_out, idx_out); });
+    }
+    // ---- DenseAgent's acting hooks (dense_agent.hpp) ----
+    const MlpLayout& act_net() const override { return net; }
+    const float* act_params() const override { return p; }
+    int32_t act_check_out(const float* act_out, const int64_t* idx_out) const override
+    {
+        const bool disc = cfg.action_type == BDR_BC_ACTION_DISCRETE;
+        BDR_REQUIRE(disc ? idx_out != nullptr : act_out != nullptr, "BC sample: a %s agent writes %s", disc ? "Discrete" : "Continuous", disc ? "idx_out" : "act_out");
+        return BDR_OK;
+    }
+    int32_t act_epilogue(DenseActArgs& a, uint64_t n) override
+    {
+        BDR_TRY(ensure_batch((int)n));
+        a.mode = cfg.action_type == BDR_BC_ACTION_DISCRETE ? DA_BC_DISCRETE : DA_BC; a.kind = cfg.policy.activation_out;
+        a.out = samp; a.idx = samp_idx;
+        return BDR_OK;
+    }
+    int32_t act_results(uint64_t n, float* act_out, int64_t* idx_out) override
+    {
+        // (an i64 row travels as two f32 words: the copy moves bits)
+        return cfg.action_type == BDR_BC_ACTION_DISCRETE ? rows_to_host(reinterpret_cast<const float*>(samp_idx), reinterpret_cast<float*>(idx_out), n * 2)
+                                                         : rows_to_host(samp, act_out, n * A);
+    }
+    int32_t act_layers(uint64_t n, const void* rows, bool on_device, uint64_t stride, float* act_out, int64_t* idx_out) override
+    {
+        return on_device ? sample_device(n, rows, stride, act_out, idx_out) : sample(n, static_cast<const float*>(rows), act_out, idx_out);
     }
     // the compiled trainers take f32 action rows: Continuous only
     bool sample_f32(uint64_t n, const void* obs, bool on_device, uint64_t stride, float* out, int32_t* st) override

@@ -12,15 +12,7 @@
 namespace bdr {
 namespace candle {
 
-// counter-based N(0,1) of the agent's noise stream (the same generator as SAC's: splitmix64 hash -> Box-Muller)
-__device__ __forceinline__ float randn_at(uint64_t seed, uint64_t counter, size_t i)
-{
-    uint64_t x = (seed + 0x9E3779B97F4A7C15ull) ^ ((counter + i + 1) * 0xBF58476D1CE4E5B9ull);
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    const float u1 = ((float)(x >> 40) + 1.0f) * (1.0f / 16777217.0f);
-    const float u2 = (float)((x >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
+// (the counter-based N(0,1) of the agent's noise stream, randn_at, lives in dense_act.hpp beside the element code of Policy::sample)
 
 // ---- fixed-order batch sums (one 1024-thread workgroup) ----------------------------------------------------------------------
 __device__ __forceinline__ float butterfly32(float v)
@@ -85,26 +77,16 @@ __global__ void k_candle_randn(float* __restrict__ out, size_t n, uint64_t seed,
 // Policy::sample (util/actor.rs:226-241): train: mean + std z, eval: mean; then clamp or scale * tanh.  z = the host draws z[t] when
 // given, else the device stream at counter + t (t = b * A + j).  out [n][A]; xq (optional): the action columns O.. of a critic input.
 struct CandleSampleArgs {
-    const float* mean; int ldm; const float* head2; int A, n;
-    float lo, hi; int tanh_limit; float amin, amax, scale;
-    int train; uint64_t seed, counter; const float* z;
+    const float* mean; int ldm; int A, n;
+    SampleElem e;   // the element code and its operands (dense_act.hpp: shared with k_dense_act)
     float* out; float* xq; int ldq; int O;
 };
 __global__ __launch_bounds__(256) void k_candle_sample(CandleSampleArgs p)
 {
-#pragma clang fp contract(off)
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.n * p.A) return;
     const int b = t / p.A, j = t % p.A;
-    float a = p.mean[(size_t)b * p.ldm + j];
-    if (p.train) {
-        const float sd = expf(fminf(fmaxf(p.head2[j], p.lo), p.hi));
-        const float zz = p.z ? p.z[t] : candle::randn_at(p.seed, p.counter, (size_t)t);
-        const float e = sd * zz;
-        a = e + a;
-    }
-    if (p.tanh_limit) { const float th = tanhf(a); a = p.scale * th; }
-    else a = fminf(fmaxf(a, p.amin), p.amax);
+    const float a = candle_sample_elem(p.e, p.mean[(size_t)b * p.ldm + j], j, (size_t)t);
     p.out[t] = a;
     if (p.xq) p.xq[(size_t)b * p.ldq + p.O + j] = a;
 }
@@ -203,17 +185,26 @@ struct CandleAgent : DenseAgent {
         for (int i = 0; i < NC; ++i) { sc[i] = opt_scalars(cfg.opt_critic, cfg.lr_critic, step_q); acts[i] = &c_act[i]; dys[i] = &c_dy[i]; }
         return mlp_backward_step(qn, NC, q_p, q_g, q_m, q_v, q_t, xq, acts, dys, q_part, q_part_stride, q_off, sc, Bn, "q_bwd_adam_track", qn.total);
     }
+    // the operands of Policy::sample's element code for n rows; in train mode without host draws it takes the next n * A draws of the
+    // device stream (the layer path and the fused kernel advance the same counter: their calls can be interleaved)
+    SampleElem sample_elem(int n, const float* z)
+    {
+        SampleElem e{};
+        e.head2 = pi_p + h2_off;
+        e.lo = (float)cfg.min_log_std; e.hi = (float)cfg.max_log_std; e.tanh_limit = cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
+        e.amin = (float)cfg.action_min; e.amax = (float)cfg.action_max; e.scale = (float)cfg.action_scale;
+        e.train = train ? 1 : 0; e.seed = cfg.seed; e.z = z;
+        if (train && !z) { e.counter = noise_counter; noise_counter += (uint64_t)n * A; }
+        return e;
+    }
     // Policy::sample of n rows from the actor's last layer (mean) into out, and into the action columns of the critic input xqd when
     // given: host draws z, else in train mode the device stream
     int32_t sample_pack(const float* mean, int n, const float* z, float* out, float* xqd, const char* name)
     {
         CandleSampleArgs p{};
-        p.mean = mean; p.ldm = pn.L.back().Np; p.head2 = pi_p + h2_off; p.A = A; p.n = n;
-        p.lo = (float)cfg.min_log_std; p.hi = (float)cfg.max_log_std; p.tanh_limit = cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
-        p.amin = (float)cfg.action_min; p.amax = (float)cfg.action_max; p.scale = (float)cfg.action_scale;
-        p.train = train ? 1 : 0; p.seed = cfg.seed;
-        p.z = z; p.out = out; p.xq = xqd; p.ldq = qn.L[0].Kp; p.O = O;
-        if (train && !z) { p.counter = noise_counter; noise_counter += (uint64_t)n * A; }
+        p.mean = mean; p.ldm = pn.L.back().Np; p.A = A; p.n = n;
+        p.e = sample_elem(n, z);
+        p.out = out; p.xq = xqd; p.ldq = qn.L[0].Kp; p.O = O;
         const int tot = n * A;
         Bracket br(this, name);
         BDR_HIP(step_launch(stream, true, k_candle_sample, dim3((tot + 255) / 256), dim3(256), p));
@@ -276,6 +267,7 @@ struct CandleAgent : DenseAgent {
     int32_t sample(uint64_t n, const float* obs, float* act_out)
     {
         BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+        if (act_fused_on()) return act_fused(nullptr, n, obs, BDR_DTYPE_F32, obs_rows_on_device, obs_rows_on_device ? obs_row_stride : (uint64_t)O * 4, act_out, nullptr);
         BDR_HIP(hipSetDevice(device));
         BDR_TRY(ensure_batch((int)n));
         int32_t st = pack_acting_obs(obs, n, x_o, pn.L[0].Kp);
@@ -288,6 +280,25 @@ struct CandleAgent : DenseAgent {
     int32_t sample_device(uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out)
     {
         return with_device_rows(obs_dev, row_stride, [&](const float* rows) { return sample(n, rows, act_out); });
+    }
+    // ---- DenseAgent's acting hooks (dense_agent.hpp) ----
+    const MlpLayout& act_net() const override { return pn; }
+    const float* act_params() const override { return pi_p; }
+    int32_t act_check_out(const float* act_out, const int64_t*) const override
+    {
+        BDR_REQUIRE(act_out, "null argument");
+        return BDR_OK;
+    }
+    int32_t act_epilogue(DenseActArgs& a, uint64_t n) override
+    {
+        BDR_TRY(ensure_batch((int)n));
+        a.mode = DA_CANDLE; a.e = sample_elem((int)n, nullptr); a.out = samp;
+        return BDR_OK;
+    }
+    int32_t act_results(uint64_t n, float* act_out, int64_t*) override { return rows_to_host(samp, act_out, n * A); }
+    int32_t act_layers(uint64_t n, const void* rows, bool on_device, uint64_t stride, float* act_out, int64_t*) override
+    {
+        return on_device ? sample_device(n, rows, stride, act_out) : sample(n, static_cast<const float*>(rows), act_out);
     }
     bool sample_f32(uint64_t n, const void* obs, bool on_device, uint64_t stride, float* act, int32_t* st) override
     {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "dense.hpp"
+#include "dense_act.hpp"
 
 namespace bdr {
 namespace candle {
@@ -82,6 +83,7 @@ struct DenseAgent : bdr_agent {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
         for (Life l : {AGENT, BATCH, STAGING}) release(l);
+        (void)hipFree(raw_f32);
     }
     int32_t layer_bufs(const MlpLayout& net, int Bn, std::vector<float*>& out)
     {
@@ -196,6 +198,137 @@ struct DenseAgent : bdr_agent {
         BDR_TRY(check_device_rows(obs_dev, row_stride));
         DeviceRowsScope rows(this, row_stride);
         return sample(static_cast<const float*>(obs_dev));
+    }
+
+    // ---- the acting path (bdr_agent_set_act_path) and raw rows (bdr_agent_sample_raw) ----
+    // An agent names the network it acts with (act_net / act_params), checks its output pointers (act_check_out), fills the epilogue
+    // of k_dense_act for n rows (act_epilogue: its result buffers, the element code's operands, the draws it takes), copies the
+    // results out (act_results) and runs its layer-by-layer call on f32 rows (act_layers).
+    virtual const MlpLayout& act_net() const = 0;
+    virtual const float* act_params() const = 0;
+    virtual int32_t act_check_out(const float* act_out, const int64_t* idx_out) const = 0;
+    virtual int32_t act_epilogue(DenseActArgs& a, uint64_t n) = 0;
+    virtual int32_t act_results(uint64_t n, float* act_out, int64_t* idx_out) = 0;
+    virtual int32_t act_layers(uint64_t n, const void* rows, bool on_device, uint64_t stride, float* act_out, int64_t* idx_out) = 0;
+
+    int32_t act_path = BDR_ACT_PATH_DEFAULT;
+    bool act_attr[2] = {false, false};   // k_dense_act<1>, <2>: the dynamic LDS size was asked for (once per agent, and so per device)
+    float* raw_f32 = nullptr; size_t raw_cap = 0;   // the layer path's f32 rows of a raw call
+    // widest padded layer input / output of the acting network
+    int act_width() const
+    {
+        int W = 0;
+        for (const auto& l : act_net().L) W = std::max(W, std::max(l.Kp, l.Np));
+        return W;
+    }
+    // BDR_ACT_PATH_DEFAULT is the layer path: nothing has shown the fused kernel faster in every round for any shape class yet
+    // (DESIGN.md 14); BDR_ACT_PATH_FUSED asks for it
+    bool act_fused_on() const { return act_path == BDR_ACT_PATH_FUSED; }
+    int32_t set_act_path(int32_t path) override
+    {
+        BDR_REQUIRE(path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS || path == BDR_ACT_PATH_FUSED, "unknown act path %d", path);
+        const int W = act_width();
+        BDR_REQUIRE(path != BDR_ACT_PATH_FUSED || (W <= DA_MAX_W && dense_act_lds(W, 1) <= DA_LDS_MAX),
+                    "the fused acting kernel keeps two [32][W + 4] activation buffers and its reduction block in 160 KB of LDS: W <= %d, "
+                    "this agent's widest padded layer is %d: use BDR_ACT_PATH_LAYERS", DA_MAX_W, W);
+        act_path = path;
+        return BDR_OK;
+    }
+    // one launch: raw rows -> (normalise) -> every layer -> the action, then the results to the host
+    int32_t act_fused(const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype, bool on_device, uint64_t stride, float* act_out, int64_t* idx_out)
+    {
+        BDR_TRY(act_check_out(act_out, idx_out));
+        BDR_HIP(hipSetDevice(device));
+        const MlpLayout& net = act_net();
+        const uint64_t eb = dtype == BDR_DTYPE_F64 ? 8 : 4;
+        DenseActArgs a{};
+        const uint8_t* src = static_cast<const uint8_t*>(rows);
+        uint64_t rs = stride;
+        if (!on_device) {   // host rows: the pinned area the kernel reads in place, or (large) the staging buffer
+            rs = (uint64_t)O * eb;
+            if (n * rs <= HOST_ROWS_PINNED_MAX) BDR_TRY(host_rows_pinned(rows, n * rs, &src));
+            else {
+                void* stage = nullptr;
+                BDR_TRY(act_buffer(n * rs, &stage));
+                BDR_HIP(hipMemcpyAsync(stage, rows, n * rs, hipMemcpyHostToDevice, stream));
+                src = static_cast<const uint8_t*>(stage);
+            }
+        }
+        a.rows = src; a.row_stride = rs; a.f64 = dtype == BDR_DTYPE_F64 ? 1 : 0;
+        a.n = (int)n; a.O = O; a.A = A; a.nl = (int)net.L.size(); a.W = act_width();
+        a.mean = norm ? norm->d_meanf : nullptr; a.std = norm ? norm->d_stdf : nullptr;
+        const float* pb = act_params();
+        for (int l = 0; l < a.nl; ++l) a.L[l] = DenseActLayer{pb + net.L[l].w, pb + net.L[l].b, net.L[l].Kp, net.L[l].Np, net.L[l].relu};
+        BDR_TRY(act_epilogue(a, n));
+        const int teams = dense_act_lds(a.W, 2) <= DA_LDS_MAX ? 2 : 1;
+        const size_t lds = dense_act_lds(a.W, teams);
+        int32_t st = BDR_OK;
+        {
+            Bracket br(this, "dense_act");
+            hipError_t e = hipSuccess;
+            if (!act_attr[teams - 1]) {   // more than 64 KB of dynamic LDS has to be asked for
+                e = teams == 2 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_act<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX)
+                               : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_act<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX);
+                act_attr[teams - 1] = e == hipSuccess;
+            }
+            if (e == hipSuccess) {
+                const dim3 grid((unsigned)((n + 31) / 32));
+                if (teams == 2) hipLaunchKernelGGL(k_dense_act<2>, grid, dim3(512), lds, stream, a);
+                else hipLaunchKernelGGL(k_dense_act<1>, grid, dim3(256), lds, stream, a);
+                e = hipGetLastError();
+            }
+            if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_dense_act: %s", hipGetErrorString(e));
+        }
+        if (st == BDR_OK) st = act_results(n, act_out, idx_out);
+        if (st == BDR_OK) prof_collect(this);
+        slot_cursor = 0;
+        return st;
+    }
+    // Policy::sample on raw environment rows (bdr_agent_sample_raw): fused, one launch; layers, the rows' f32 / z form into
+    // contiguous device rows (obs_norm_z, the expression of bdr_obs_norm_apply) followed by the agent's call on those
+    int32_t sample_raw(const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype, bool on_device, uint64_t stride, float* act_out,
+                       int64_t* idx_out) override
+    {
+        BDR_REQUIRE(rows, "null argument");
+        BDR_TRY(act_check_out(act_out, idx_out));
+        BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+        BDR_REQUIRE(dtype == BDR_DTYPE_F32 || dtype == BDR_DTYPE_F64, "dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64");
+        const uint64_t eb = dtype == BDR_DTYPE_F64 ? 8 : 4;
+        if (norm) {
+            BDR_REQUIRE(norm->ready, "the normaliser has no statistics yet (bdr_obs_norm_finish / bdr_obs_norm_set)");
+            BDR_REQUIRE(norm->dim == (uint64_t)O, "the normaliser's dim (%llu) is not the agent's obs dim (%d)", (unsigned long long)norm->dim, O);
+            BDR_REQUIRE(norm->device == device, "agent and normaliser live on different devices");
+        }
+        BDR_HIP(hipSetDevice(device));
+        if (on_device) {
+            BDR_REQUIRE(stride >= (uint64_t)O * eb && stride % eb == 0 && (uintptr_t)rows % eb == 0,
+                        "row_stride must be a multiple of the element size and >= the row size, rows aligned to the element size");
+            BDR_TRY(check_device_rows(rows, stride));
+        }
+        if (act_fused_on()) return act_fused(norm, n, rows, dtype, on_device, stride, act_out, idx_out);
+        if (!norm && dtype == BDR_DTYPE_F32) return act_layers(n, rows, on_device, stride, act_out, idx_out);
+        const uint8_t* src = static_cast<const uint8_t*>(rows);
+        uint64_t rs = stride;
+        if (!on_device) {
+            rs = (uint64_t)O * eb;
+            BDR_TRY(acting_rows(rows, (size_t)rs, n, &src));
+        }
+        if (n * O > raw_cap) {
+            BDR_HIP(hipStreamSynchronize(stream));
+            (void)hipFree(raw_f32); raw_f32 = nullptr; raw_cap = 0;
+            const size_t cap = std::max<size_t>(n * O, 4096);
+            BDR_HIP(hipMalloc((void**)&raw_f32, cap * 4));
+            raw_cap = cap;
+        }
+        const dim3 grid((unsigned)((n * O + 255) / 256));
+        const float* mean = norm ? norm->d_meanf : nullptr; const float* sd = norm ? norm->d_stdf : nullptr;
+        {
+            Bracket br(this, "raw_rows");
+            if (dtype == BDR_DTYPE_F64) hipLaunchKernelGGL(k_act_raw_rows<double>, grid, dim3(256), 0, stream, src, (unsigned long long)rs, (unsigned long long)n, O, mean, sd, raw_f32);
+            else hipLaunchKernelGGL(k_act_raw_rows<float>, grid, dim3(256), 0, stream, src, (unsigned long long)rs, (unsigned long long)n, O, mean, sd, raw_f32);
+        }
+        BDR_HIP(hipGetLastError());
+        return act_layers(n, raw_f32, true, (uint64_t)O * 4, act_out, idx_out);
     }
 
     // ---- parameter views ----

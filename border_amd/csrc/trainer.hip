@@ -5,11 +5,17 @@
 //   Trainer::train_offline   trainer.rs:330-384                   warmup_period = 0, opt_interval = 1
 //   Sampler::sample_and_push trainer/sampler.rs:99-144            reset on first use, Policy::sample, step_with_reset, push
 //   SimpleStepProcessor      generic_replay_buffer/step_proc.rs:62-137   (prev_obs, act, obs, ...) transitions
-// Recorder / evaluator sinks are out of scope: an observer callback receives what the reference would
-// store.  Pure host code: the agent, buffer and environment are reached through function tables, so the loop itself runs
+//   Trainer::post_process   trainer.rs:231-264                   evaluate every eval_interval opt steps, keep the best model, save
+//   DefaultEvaluator        evaluator/default_evaluator.rs:64-88  (MinariEvaluator, border-minari/src/evaluator.rs:25-62, is the same loop)
+// Recorders are out of scope: an observer callback receives what the reference would store.  Pure host code: the agent, buffer and environment are reached through function tables, so the loop itself runs
 // (and is tested) without a GPU.
+#include <sys/stat.h>
+
+#include <cerrno>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "agent_base.hpp"
@@ -27,6 +33,7 @@ struct State {
     double timer_for_opt_steps = 0, timer_for_samples = 0, total_opt = 0, total_sample = 0;
     float scalars[128];
     int32_t n_scalars = 0;
+    float max_eval_reward = -FLT_MAX;   // f32::MIN (trainer.rs: max_eval_reward)
 };
 
 // trainer.rs:197-228
@@ -94,6 +101,69 @@ int32_t d_push_dev(void* b, uint64_t n, const void* obs_dev, uint64_t os, const 
 {
     return bdr_replay_push_device((bdr_replay*)b, n, obs_dev, os, act, next_dev, ns, rew, term, trunc);
 }
+// defaults of the evaluator and the post-processing
+int32_t d_sample_raw(void* a, const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype, int32_t on_device, uint64_t row_stride, void* act)
+{
+    // one buffer for both result kinds: a Discrete BC agent writes i64 indices, every other agent f32 rows
+    return bdr_agent_sample_raw((bdr_agent*)a, norm, n, rows, dtype, on_device, row_stride, (float*)act, (int64_t*)act);
+}
+int32_t mkdir_p(const std::string& dir)
+{
+    for (size_t i = 1; i <= dir.size(); ++i) {
+        if (i != dir.size() && dir[i] != '/') continue;
+        const std::string part = dir.substr(0, i);
+        if (mkdir(part.c_str(), 0777) != 0 && errno != EEXIST) return fail(BDR_ERR_IO, "cannot create directory %s: %s", part.c_str(), strerror(errno));
+    }
+    return BDR_OK;
+}
+int32_t d_save(void* a, const char* dir)
+{
+    BDR_TRY(mkdir_p(dir));
+    return bdr_agent_save_params((bdr_agent*)a, dir);
+}
+
+int32_t check_post(const bdr_trainer_post* post)
+{
+    if (!post) return BDR_OK;
+    BDR_REQUIRE(!post->eval_interval || post->evaluator, "eval_interval is set: post-processing needs an evaluator");
+    BDR_REQUIRE(!(post->eval_interval || post->save_interval) || post->model_dir, "post-processing saves models: model_dir must be set");
+    return BDR_OK;
+}
+
+// trainer.rs:231-264, after an iteration that took an opt step
+int32_t post_process(State& s, const bdr_trainer_post* post, bdr_trainer_observer obs, void* ctx)
+{
+    if (!post) return BDR_OK;
+    const auto save = post->save_params ? post->save_params : d_save;
+    if (post->eval_interval && s.opt_steps % post->eval_interval == 0) {
+        BDR_TRY(s.ops->agent_set_train(s.ops->agent, 0));
+        bdr_eval_result r{};
+        BDR_TRY(bdr_evaluate(post->evaluator, s.ops->agent, &r));
+        BDR_TRY(s.ops->agent_set_train(s.ops->agent, 1));
+        const float sc[2] = {r.score, r.normalized};
+        if (obs) obs(ctx, s.env_steps, s.opt_steps, BDR_TRAINER_EVENT_EVAL, sc, r.has_normalized ? 2 : 1);
+        if (r.score > s.max_eval_reward) {
+            s.max_eval_reward = r.score;
+            BDR_TRY(save(s.ops->agent, (std::string(post->model_dir) + "/best").c_str()));
+        }
+    }
+    if (post->save_interval > 0 && s.opt_steps % post->save_interval == 0)
+        BDR_TRY(save(s.ops->agent, (std::string(post->model_dir) + "/" + std::to_string(s.opt_steps)).c_str()));
+    return BDR_OK;
+}
+
+// what follows the sampling of an iteration in both loops: train_step, its event, post_process, the cost record; *stop: max_opts reached
+int32_t step_and_records(State& s, const bdr_trainer_post* post, bdr_trainer_observer obs, void* obs_ctx, bool* stop)
+{
+    bool is_opt = false, with_record = false;
+    BDR_TRY(train_step(s, &is_opt, &with_record));
+    if (obs) obs(obs_ctx, s.env_steps, s.opt_steps, is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP,
+                 s.scalars, s.n_scalars);
+    if (is_opt) BDR_TRY(post_process(s, post, obs, obs_ctx));
+    cost_record(s, obs, obs_ctx);
+    *stop = s.opt_steps == s.c->max_opts;   // trainer.rs:323-325
+    return BDR_OK;
+}
 }  // namespace
 
 namespace bdr {
@@ -125,10 +195,69 @@ void bdr_trainer_ops_default(bdr_trainer_ops* ops, bdr_agent* agent, bdr_replay*
     ops->agent_sample_device = default_sample_device; ops->buffer_push_device = d_push_dev;
 }
 
+void bdr_evaluator_default(bdr_evaluator* ev, bdr_agent*)
+{
+    if (!ev) return;
+    memset(ev, 0, sizeof *ev);
+    ev->obs_dtype = BDR_DTYPE_F32;
+    ev->agent_sample = default_sample; ev->agent_sample_raw = d_sample_raw;
+}
+
+void bdr_trainer_post_default(bdr_trainer_post* post)
+{
+    if (!post) return;
+    memset(post, 0, sizeof *post);
+    post->save_params = d_save;
+}
+
+// default_evaluator.rs:64-88
+int32_t bdr_evaluate(const bdr_evaluator* ev, void* agent, bdr_eval_result* out)
+{
+    BDR_REQUIRE(ev && out, "null argument");
+    BDR_REQUIRE(ev->env.reset_with_index && ev->env.step, "the evaluator's environment function table is incomplete");
+    BDR_REQUIRE(ev->n_episodes >= 1, "n_episodes must be >= 1");
+    BDR_REQUIRE(ev->obs_row_bytes > 0 && ev->act_row_bytes > 0, "obs_row_bytes / act_row_bytes must be set");
+    BDR_REQUIRE(ev->obs_dtype == BDR_DTYPE_F32 || ev->obs_dtype == BDR_DTYPE_F64, "obs_dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64");
+    const bool dev = ev->env.obs_on_device != 0;
+    const bool raw = ev->norm != nullptr || ev->obs_dtype != BDR_DTYPE_F32 || dev;
+    BDR_REQUIRE(raw ? ev->agent_sample_raw != nullptr : ev->agent_sample != nullptr,
+                raw ? "normalised, float64 or device-resident rows need agent_sample_raw" : "agent_sample is not set");
+    ObsRow prev, next;
+    BDR_TRY(prev.init(dev, ev->env.device, ev->obs_row_bytes)); BDR_TRY(next.init(dev, ev->env.device, ev->obs_row_bytes));
+    std::vector<uint8_t> act(std::max<uint64_t>(ev->act_row_bytes, 8));
+    float r_total = 0.f;
+    uint64_t n_steps = 0;
+    for (uint64_t ix = 0; ix < ev->n_episodes; ++ix) {
+        BDR_TRY(ev->env.reset_with_index(ev->env.ctx, ix, prev.p()));
+        for (;;) {
+            if (raw) BDR_TRY(ev->agent_sample_raw(agent, ev->norm, 1, prev.p(), ev->obs_dtype, dev ? 1 : 0, ev->obs_row_bytes, act.data()));
+            else BDR_TRY(ev->agent_sample(agent, 1, prev.p(), act.data()));
+            float reward = 0; int8_t term = 0, trunc = 0;
+            BDR_TRY(ev->env.step(ev->env.ctx, act.data(), next.p(), &reward, &term, &trunc));
+            r_total += reward;
+            n_steps += 1;
+            if (term == 1 || trunc == 1) break;   // step.rs:136-138
+            prev.swap(next);                      // prev_obs = step.obs
+        }
+    }
+    out->score = r_total / (float)ev->n_episodes;
+    out->has_normalized = ev->has_ref_scores ? 1 : 0;
+    out->normalized = ev->has_ref_scores ? (out->score - ev->ref_min_score) / (ev->ref_max_score - ev->ref_min_score) : 0.f;   // border-minari/src/env.rs:162-168
+    out->n_steps = n_steps; out->n_episodes = ev->n_episodes;
+    return BDR_OK;
+}
+
 int32_t bdr_trainer_train(const bdr_trainer_config* c, const bdr_trainer_ops* ops, const bdr_env_vtable* env,
                           bdr_trainer_observer obs, void* obs_ctx, bdr_trainer_stats* out)
 {
+    return bdr_trainer_train_post(c, ops, env, nullptr, obs, obs_ctx, out);
+}
+
+int32_t bdr_trainer_train_post(const bdr_trainer_config* c, const bdr_trainer_ops* ops, const bdr_env_vtable* env, const bdr_trainer_post* post,
+                               bdr_trainer_observer obs, void* obs_ctx, bdr_trainer_stats* out)
+{
     BDR_TRY(check(c, ops));
+    BDR_TRY(check_post(post));
     BDR_REQUIRE(env && env->reset && env->step_with_reset, "environment function table is incomplete");
     BDR_REQUIRE(ops->agent_sample && ops->buffer_push, "the online loop needs agent_sample and buffer_push");
     BDR_REQUIRE(c->obs_row_bytes > 0 && c->act_row_bytes > 0, "obs_row_bytes / act_row_bytes must be set");
@@ -165,13 +294,10 @@ int32_t bdr_trainer_train(const bdr_trainer_config* c, const bdr_trainer_ops* op
         s.timer_for_samples += dt; s.total_sample += dt;
         s.samples_counter += 1;
         s.env_steps += 1;
-        // ---- train_step + records
-        bool is_opt = false, with_record = false;
-        BDR_TRY(train_step(s, &is_opt, &with_record));
-        if (obs) obs(obs_ctx, s.env_steps, s.opt_steps, is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP,
-                     s.scalars, s.n_scalars);
-        cost_record(s, obs, obs_ctx);
-        if (s.opt_steps == c->max_opts) break;           // trainer.rs:323-325
+        // ---- train_step + post_process + records
+        bool stop = false;
+        BDR_TRY(step_and_records(s, post, obs, obs_ctx, &stop));
+        if (stop) break;
     }
     fill_stats(s, out);
     return BDR_OK;
@@ -180,19 +306,23 @@ int32_t bdr_trainer_train(const bdr_trainer_config* c, const bdr_trainer_ops* op
 int32_t bdr_trainer_train_offline(const bdr_trainer_config* c_in, const bdr_trainer_ops* ops, bdr_trainer_observer obs, void* obs_ctx,
                                   bdr_trainer_stats* out)
 {
+    return bdr_trainer_train_offline_post(c_in, ops, nullptr, obs, obs_ctx, out);
+}
+
+int32_t bdr_trainer_train_offline_post(const bdr_trainer_config* c_in, const bdr_trainer_ops* ops, const bdr_trainer_post* post, bdr_trainer_observer obs,
+                                       void* obs_ctx, bdr_trainer_stats* out)
+{
     BDR_TRY(check(c_in, ops));
+    BDR_TRY(check_post(post));
     bdr_trainer_config c = *c_in;
     c.warmup_period = 0; c.opt_interval = 1;            // trainer.rs:345-346
     State s; s.c = &c; s.ops = ops;
     BDR_TRY(ops->agent_set_train(ops->agent, 1));
     for (;;) {
         s.env_steps += 1;
-        bool is_opt = false, with_record = false;
-        BDR_TRY(train_step(s, &is_opt, &with_record));
-        if (obs) obs(obs_ctx, s.env_steps, s.opt_steps, is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP,
-                     s.scalars, s.n_scalars);
-        cost_record(s, obs, obs_ctx);
-        if (s.opt_steps == c.max_opts) break;
+        bool stop = false;
+        BDR_TRY(step_and_records(s, post, obs, obs_ctx, &stop));
+        if (stop) break;
     }
     fill_stats(s, out);
     return BDR_OK;

@@ -192,6 +192,46 @@ class AgentHandle:
         from .dqn import opt_with_named_record
         return opt_with_named_record(self._h, buffer)
 
+    ACT_PATHS = {"default": 0, "layers": 1, "fused": 2}   # BDR_ACT_PATH_*
+
+    def set_act_path(self, path: str) -> None:
+        """How Policy::sample runs: "layers" (pack, one launch per layer, the sample kernel), "fused" (k_dense_act: one launch from the
+        raw rows to the action; same bits) or "default".  "fused" on a network it does not cover raises BdrError."""
+        _lib.check(_lib.lib().bdr_agent_set_act_path(self._h, self.ACT_PATHS[path]))
+
+    def _raw_out(self, n: int):
+        """(result array, is it an index array) of a sample of n rows"""
+        return np.empty((n, self.config.act_dim), np.float32), False
+
+    def sample_raw(self, rows, obs_norm=None) -> np.ndarray:
+        """Policy::sample on raw environment rows (bdr_agent_sample_raw): float32 or float64 host rows [n, obs_dim], rounded to
+        float32 and - with `obs_norm`, an ObsNormalizer - normalised on the device with the bits of ObsNormalizer.apply."""
+        rows = np.asarray(rows)
+        if rows.dtype != np.float32:
+            rows = rows.astype(np.float64, copy=False)
+        rows = np.ascontiguousarray(rows).reshape(-1, self.config.obs_dim)
+        out, disc = self._raw_out(rows.shape[0])
+        code = _lib.BDR_DTYPE_F32 if rows.dtype == np.float32 else _lib.BDR_DTYPE_F64
+        _lib.check(_lib.lib().bdr_agent_sample_raw(self._h, obs_norm.handle if obs_norm is not None else None, rows.shape[0], _p(rows), code, 0, 0,
+                                                   None if disc else _p(out), _p(out) if disc else None))
+        return out
+
+    def sample_raw_device(self, ptr: int, n: int, row_stride: int, dtype=np.float32, obs_norm=None) -> np.ndarray:
+        """The same for rows in HBM: row k at ptr + k * row_stride bytes, obs_dim elements of `dtype`."""
+        out, disc = self._raw_out(n)
+        code = _lib.BDR_DTYPE_F32 if np.dtype(dtype) == np.float32 else _lib.BDR_DTYPE_F64
+        _lib.check(_lib.lib().bdr_agent_sample_raw(self._h, obs_norm.handle if obs_norm is not None else None, n, C.c_void_p(ptr), code, 1, row_stride,
+                                                   None if disc else _p(out), _p(out) if disc else None))
+        return out
+
+    def profile_read(self) -> list:
+        """[(bracket name, mean milliseconds)] of the launches recorded since profile_enable (bdr_agent_profile_read), in launch order."""
+        n = C.c_uint64(256)
+        names, ms = C.create_string_buffer(16384), np.zeros(256, np.float32)
+        _lib.check(_lib.lib().bdr_agent_profile_read(self._h, names, len(names), _p(ms), C.byref(n)))
+        keys = [k for k in names.value.decode().split("\n") if k]
+        return [(k, float(ms[i])) for i, k in enumerate(keys[:n.value])]
+
     def profile_enable(self, on: bool = True):
         _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
 

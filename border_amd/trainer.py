@@ -124,6 +124,8 @@ class Trainer:
         self.timer_for_opt_steps = 0.0
         self.opt_steps_counter = 0
         self.records = []
+        self.evals = []                                  # (opt_steps, EvalResult) of post_process
+        self.max_eval_reward = -np.finfo(np.float32).max   # f32::MIN
 
     def train_step(self, agent, buffer):
         """trainer.rs:197-228."""
@@ -145,8 +147,22 @@ class Trainer:
         """trainer.rs:164-174 (host-side enqueue time unless the step synchronised)."""
         return 1000.0 * self.timer_for_opt_steps / max(1, self.opt_steps_counter)
 
-    def train(self, env, step_proc, agent, buffer, on_step=None):
-        """trainer.rs:267-327 without recorder / evaluator sinks: sample_and_push, then train_step, until max_opts.
+    def post_process(self, agent, evaluator, eval_interval, save_interval, model_dir):
+        """trainer.rs:231-264 (an interval of 0: never).  evaluator: a border_amd.evaluator.Evaluator."""
+        import os
+        if eval_interval and self.opt_steps % eval_interval == 0:
+            agent.eval()
+            res = evaluator.evaluate(agent)
+            agent.train()
+            self.evals.append((self.opt_steps, res))
+            if res.score > self.max_eval_reward:
+                self.max_eval_reward = res.score
+                agent.save_params(os.path.join(model_dir, "best"))
+        if save_interval and self.opt_steps % save_interval == 0:
+            agent.save_params(os.path.join(model_dir, str(self.opt_steps)))
+
+    def train(self, env, step_proc, agent, buffer, on_step=None, evaluator=None, eval_interval=0, save_interval=0, model_dir=None):
+        """trainer.rs:267-327 without recorder sinks: sample_and_push, then train_step and post_process, until max_opts.
         `on_step(step, record, is_opt)` observes every iteration (tests)."""
         sampler = Sampler(env, step_proc)
         agent.train()
@@ -159,13 +175,15 @@ class Trainer:
             rec, is_opt = self.train_step(agent, buffer)
             if rec is not None:
                 self.records.append((self.opt_steps, rec))
+            if is_opt and (eval_interval or save_interval):
+                self.post_process(agent, evaluator, eval_interval, save_interval, model_dir)
             if on_step is not None:
                 on_step(step, rec, is_opt)
             if self.opt_steps == self.config.max_opts:
                 return
 
-    def train_offline(self, agent, buffer, exchange=None):
-        """trainer.rs:330-384 without recorder / evaluator sinks (out of scope: SURVEY.md 2.1 #4)."""
+    def train_offline(self, agent, buffer, exchange=None, evaluator=None, eval_interval=0, save_interval=0, model_dir=None):
+        """trainer.rs:330-384 without recorder sinks (out of scope: SURVEY.md 2.1 #4)."""
         self.config.warmup_period = 0
         self.config.opt_interval = 1
         agent.train()
@@ -174,6 +192,8 @@ class Trainer:
             rec, is_opt = self.train_step(agent, buffer)
             if rec is not None:
                 self.records.append((self.opt_steps, rec))
+            if is_opt and (eval_interval or save_interval):
+                self.post_process(agent, evaluator, eval_interval, save_interval, model_dir)
             if is_opt and exchange is not None:
                 exchange.after_opt(agent, self.opt_steps)
             if self.opt_steps == self.config.max_opts:
@@ -184,7 +204,7 @@ class NativeTrainer:
     """The compiled driver (csrc/trainer.hip: bdr_trainer_train / bdr_trainer_train_offline) - the loops above run in C++;
     Python only supplies the environment callbacks and, optionally, an observer."""
 
-    EVENTS = {0: "skip", 1: "opt", 2: "opt_record", 3: "cost"}
+    EVENTS = {0: "skip", 1: "opt", 2: "opt_record", 3: "cost", 4: "eval"}
 
     def __init__(self, config: TrainerConfig):
         self.config = config
@@ -210,17 +230,45 @@ class NativeTrainer:
         self.stats = {k: getattr(st, k) for k, _ in _lib.TrainerStatsC._fields_}
         return self.stats
 
-    def train_offline(self, agent, buffer, on_event=None, ops=None):
+    @staticmethod
+    def _post(evaluator, eval_interval, save_interval, model_dir, save_params=None):
+        """Trainer::post_process (trainer.rs:231-264) as a bdr_trainer_post, or None when nothing of it is asked for: then the
+        call is exactly the one without post-processing.  evaluator: a border_amd.evaluator.Evaluator (or a ready EvaluatorC)."""
+        if evaluator is None and not eval_interval and not save_interval and model_dir is None:
+            return None, None
+        post = _lib.TrainerPostC()
+        _lib.lib().bdr_trainer_post_default(C.byref(post))
+        post.eval_interval, post.save_interval = int(eval_interval or 0), int(save_interval or 0)
+        ev = None
+        if evaluator is not None:
+            ev = evaluator if isinstance(evaluator, _lib.EvaluatorC) else evaluator.c_struct()
+            post.evaluator = C.pointer(ev)
+        if model_dir is not None:
+            post.model_dir = str(model_dir).encode()
+        if save_params is not None:
+            post.save_params = save_params
+        return post, (ev, save_params)
+
+    def train_offline(self, agent, buffer, on_event=None, ops=None, evaluator=None, eval_interval=0, save_interval=0, model_dir=None, save_params=None):
+        """evaluator / eval_interval / save_interval / model_dir: Trainer::post_process after every opt step (bdr_trainer_train_offline_post);
+        the observer then also gets "eval" events with [score] or [score, normalized].  Leaving them out gives bdr_trainer_train_offline."""
         if ops is None:
             ops = _lib.TrainerOps()
             _lib.lib().bdr_trainer_ops_default(C.byref(ops), agent.handle, buffer.handle)
         c, st, obs = self._config(), _lib.TrainerStatsC(), self._observer(on_event)
-        _lib.check(_lib.lib().bdr_trainer_train_offline(C.byref(c), C.byref(ops), obs, None, C.byref(st)))
+        post, _keep = self._post(evaluator, eval_interval, save_interval, model_dir, save_params)
+        if post is None:
+            _lib.check(_lib.lib().bdr_trainer_train_offline(C.byref(c), C.byref(ops), obs, None, C.byref(st)))
+        else:
+            rc = _lib.lib().bdr_trainer_train_offline_post(C.byref(c), C.byref(ops), C.byref(post), obs, None, C.byref(st))
+            (evaluator._raise if hasattr(evaluator, "_raise") else _lib.check)(rc)
         return self._finish(st)
 
-    def train(self, env, agent, buffer, obs_shape, obs_dtype, act_row_bytes=8, on_event=None, ops=None, act_dtype=np.int64):
+    def train(self, env, agent, buffer, obs_shape, obs_dtype, act_row_bytes=8, on_event=None, ops=None, act_dtype=np.int64,
+              evaluator=None, eval_interval=0, save_interval=0, model_dir=None, save_params=None):
         """`env` has reset(None) -> obs[1, ...] and step_with_reset(act) -> Step (as SyntheticEnv).  Continuous-action agents
-        (SAC): act_row_bytes = 4 * act_dim, act_dtype = np.float32."""
+        (SAC): act_row_bytes = 4 * act_dim, act_dtype = np.float32.  evaluator / eval_interval / save_interval / model_dir: as
+        train_offline (bdr_trainer_train_post)."""
         obs_dtype = np.dtype(obs_dtype)
         row = int(np.prod(obs_shape)) * obs_dtype.itemsize
 
@@ -249,7 +297,12 @@ class NativeTrainer:
             ops = _lib.TrainerOps()
             _lib.lib().bdr_trainer_ops_default(C.byref(ops), agent.handle, buffer.handle)
         c, st, obs = self._config(row, act_row_bytes), _lib.TrainerStatsC(), self._observer(on_event)
-        _lib.check(_lib.lib().bdr_trainer_train(C.byref(c), C.byref(ops), C.byref(vt), obs, None, C.byref(st)))
+        post, _keep = self._post(evaluator, eval_interval, save_interval, model_dir, save_params)
+        if post is None:
+            _lib.check(_lib.lib().bdr_trainer_train(C.byref(c), C.byref(ops), C.byref(vt), obs, None, C.byref(st)))
+        else:
+            rc = _lib.lib().bdr_trainer_train_post(C.byref(c), C.byref(ops), C.byref(vt), C.byref(post), obs, None, C.byref(st))
+            (evaluator._raise if hasattr(evaluator, "_raise") else _lib.check)(rc)
         return self._finish(st)
 
 

@@ -490,7 +490,9 @@ BDR_API int32_t bdr_agent_load_params(bdr_agent* a, const char* dir);
  *                              (opt_steps + 1) % record_agent_info_interval == 0; the timer wraps opt*() only; stop at
  *                              opt_steps == max_opts
  *   bdr_trainer_train_offline  Trainer::train_offline (:330-384): warmup_period = 0, opt_interval = 1, no sampling
- * Recorder / evaluator sinks are out of scope; `observer` receives what the reference would store. */
+ * Recorders (TensorBoard, MLflow) are out of scope: `observer` receives what the reference would store.  The Evaluator and the
+ * post-processing of every opt step (Trainer::post_process, trainer.rs:231-264: evaluate every eval_interval opt steps, keep the
+ * best model, save every save_interval opt steps) are bdr_evaluate and the *_post entries below. */
 typedef struct bdr_env_vtable {             /* single-process Env (border-core/src/base/env.rs:45-181) */
     void* ctx;
     int32_t (*reset)(void* ctx, void* obs_out);                                  /* Env::reset(None) */
@@ -550,6 +552,73 @@ BDR_API int32_t bdr_trainer_train(const bdr_trainer_config* c, const bdr_trainer
                                   bdr_trainer_observer observer, void* observer_ctx, bdr_trainer_stats* out);
 BDR_API int32_t bdr_trainer_train_offline(const bdr_trainer_config* c, const bdr_trainer_ops* ops, bdr_trainer_observer observer,
                                           void* observer_ctx, bdr_trainer_stats* out);
+
+/* ---- Evaluator (border-core/src/evaluator/default_evaluator.rs:64-88, border-minari/src/evaluator.rs:25-62) and
+ * Trainer::post_process (trainer.rs:231-264) ---------------------------------------------------------------------------------
+ * bdr_evaluate is the reference's loop, literally: for ix in 0..n_episodes: reset_with_index(ix), then sample -> step ->
+ * r_total += reward until is_terminated | is_truncated; r_total is one f32 accumulator and the additions happen in call order;
+ * score = r_total / (float)n_episodes; normalized = (score - ref_min_score) / (ref_max_score - ref_min_score) when the
+ * reference scores are present (border-minari/src/env.rs:162-168).  It does not change the agent's train / eval mode: the
+ * Trainer does that. */
+typedef struct bdr_eval_env_vtable {        /* the evaluator's view of an Env */
+    void* ctx;
+    int32_t (*reset_with_index)(void* ctx, uint64_t ix, void* obs_out);          /* Env::reset_with_index (env.rs:180) */
+    /* Env::step (no reset): writes obs, reward and the flags */
+    int32_t (*step)(void* ctx, const void* act, void* obs_out, float* reward, int8_t* is_terminated, int8_t* is_truncated);
+    int32_t obs_on_device;                  /* as bdr_env_vtable: obs_out is a DEVICE buffer of obs_row_bytes on GPU `device` */
+    int32_t device;
+} bdr_eval_env_vtable;
+
+typedef struct bdr_evaluator {
+    uint64_t n_episodes;
+    uint64_t obs_row_bytes;                 /* one observation row as the environment writes it (obs_dtype elements) */
+    uint64_t act_row_bytes;
+    int32_t obs_dtype;                      /* BDR_DTYPE_F32 / BDR_DTYPE_F64 (Minari environments produce float64 rows) */
+    const bdr_obs_norm* norm;               /* NULL: the rows are the agent's input as they are */
+    int32_t has_ref_scores;
+    float ref_min_score;
+    float ref_max_score;
+    bdr_eval_env_vtable env;
+    /* Policy::sample on one row.  agent_sample (every agent kind; the signature of bdr_trainer_ops) is used when norm is NULL and
+     * the rows are f32 in host memory; agent_sample_raw (bdr_agent_sample_raw: IQL, AWAC, BC) otherwise. */
+    int32_t (*agent_sample)(void* agent, uint64_t n_procs, const void* obs, void* act_out);
+    int32_t (*agent_sample_raw)(void* agent, const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype, int32_t on_device,
+                                uint64_t row_stride, void* act_out);
+} bdr_evaluator;
+
+typedef struct bdr_eval_result {
+    float score;                            /* r_total / n_episodes */
+    int32_t has_normalized;
+    float normalized;
+    uint64_t n_steps;                       /* environment steps of the evaluation */
+    uint64_t n_episodes;
+} bdr_eval_result;
+
+/* Trainer::post_process after every iteration that took an opt step.  An interval of 0 means never (this header's convention; the
+ * reference would divide by zero).  When opt_steps % eval_interval == 0: agent_set_train(0), evaluate, agent_set_train(1) -
+ * unconditionally, as trainer.rs:246-248 - the observer gets BDR_TRAINER_EVENT_EVAL, and when score > max_eval_reward (which
+ * starts at -FLT_MAX = f32::MIN; a strict >) the model is saved to model_dir/best.  When save_interval > 0 and
+ * opt_steps % save_interval == 0 the model is saved to model_dir/<opt_steps>.  The evaluator's time is in neither Trainer timer. */
+typedef struct bdr_trainer_post {
+    uint64_t eval_interval;
+    uint64_t save_interval;
+    const bdr_evaluator* evaluator;         /* needed when eval_interval > 0 */
+    const char* model_dir;                  /* needed when something is saved */
+    int32_t (*save_params)(void* agent, const char* dir);   /* NULL: bdr_agent_save_params after creating the directory */
+} bdr_trainer_post;
+
+#define BDR_TRAINER_EVENT_EVAL 4            /* scalars = {score} or {score, normalized} (with reference scores) */
+
+/* zeroes *ev and fills both acting hooks from the library's handles (agent may be NULL: it is not read) */
+BDR_API void bdr_evaluator_default(bdr_evaluator* ev, bdr_agent* agent);
+BDR_API int32_t bdr_evaluate(const bdr_evaluator* ev, void* agent, bdr_eval_result* out);
+BDR_API void bdr_trainer_post_default(bdr_trainer_post* post);
+/* bdr_trainer_train / bdr_trainer_train_offline plus post_process; with post == NULL they are those functions (one loop body). */
+BDR_API int32_t bdr_trainer_train_post(const bdr_trainer_config* c, const bdr_trainer_ops* ops, const bdr_env_vtable* env,
+                                       const bdr_trainer_post* post, bdr_trainer_observer observer, void* observer_ctx,
+                                       bdr_trainer_stats* out);
+BDR_API int32_t bdr_trainer_train_offline_post(const bdr_trainer_config* c, const bdr_trainer_ops* ops, const bdr_trainer_post* post,
+                                               bdr_trainer_observer observer, void* observer_ctx, bdr_trainer_stats* out);
 
 /* ---- border-async-trainer (border-async-trainer/src) -----------------------------------------------------------------------
  * The reference runs one learner thread (AsyncTrainer::train, async_trainer/base.rs:299-388) and n actor threads (Actor::run,
@@ -949,6 +1018,22 @@ BDR_API int32_t bdr_bc_probe(bdr_agent* a, int32_t what, float* out, uint64_t n)
 BDR_API int32_t bdr_bc_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out, int64_t* idx_out);
 /* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
 BDR_API int32_t bdr_bc_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out);
+
+/* ---- acting of the dense-agent agents (IQL, AWAC, BC) ----------------------------------------------------------------------
+ * Their Policy::sample has two forms that produce the same bits: the layer-by-layer path (pack, one launch per layer, the sample
+ * kernel) and k_dense_act (csrc/dense_act.hpp), one launch from the raw rows to the action.  bdr_{iql,awac,bc}_sample[_device] and
+ * bdr_agent_sample_raw obey the setting.  FUSED on an agent kind or a network it does not cover (a padded layer wider than 512)
+ * returns BDR_ERR_INVALID with the reason.  DEFAULT is the layer path. */
+#define BDR_ACT_PATH_DEFAULT 0
+#define BDR_ACT_PATH_LAYERS 1
+#define BDR_ACT_PATH_FUSED 2
+BDR_API int32_t bdr_agent_set_act_path(bdr_agent* a, int32_t path);
+/* Policy::sample on n raw environment rows of `dtype` (BDR_DTYPE_F32 / _F64): host rows, contiguous, or (on_device != 0) device rows
+ * row_stride bytes apart.  float64 is rounded to f32; with a normaliser (finished or set, dim = the agent's obs dim, on the agent's
+ * device) the value that enters the first layer has the bits of bdr_obs_norm_apply.  act_out [n][act_dim]; idx_out [n] for a
+ * Discrete BC agent (then act_out may be NULL), else NULL.  IQL, AWAC and BC; other agent kinds return BDR_ERR_INVALID. */
+BDR_API int32_t bdr_agent_sample_raw(bdr_agent* a, const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype,
+                                     int32_t on_device, uint64_t row_stride, float* act_out, int64_t* idx_out);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU parameter exchange (replaces the learner->actors NamedTensors channel of

@@ -63,6 +63,10 @@ pub const BDR_TRAINER_EVENT_SKIP: i32 = 0;
 pub const BDR_TRAINER_EVENT_OPT: i32 = 1;
 pub const BDR_TRAINER_EVENT_OPT_RECORD: i32 = 2;
 pub const BDR_TRAINER_EVENT_COST: i32 = 3;
+pub const BDR_TRAINER_EVENT_EVAL: i32 = 4;
+pub const BDR_ACT_PATH_DEFAULT: i32 = 0;
+pub const BDR_ACT_PATH_LAYERS: i32 = 1;
+pub const BDR_ACT_PATH_FUSED: i32 = 2;
 
 // opaque handles
 #[repr(C)]
@@ -312,6 +316,72 @@ pub struct bdr_trainer_stats {
     pub n_episodes: u64,
     pub opt_seconds: f64,
     pub sample_seconds: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_eval_env_vtable {
+    pub ctx: *mut c_void,
+    pub reset_with_index: Option<unsafe extern "C" fn(ctx: *mut c_void, ix: u64, obs_out: *mut c_void) -> i32>,
+    pub step: Option<
+        unsafe extern "C" fn(
+            ctx: *mut c_void,
+            act: *const c_void,
+            obs_out: *mut c_void,
+            reward: *mut f32,
+            is_terminated: *mut i8,
+            is_truncated: *mut i8,
+        ) -> i32,
+    >,
+    pub obs_on_device: i32,
+    pub device: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_evaluator {
+    pub n_episodes: u64,
+    pub obs_row_bytes: u64,
+    pub act_row_bytes: u64,
+    pub obs_dtype: i32,
+    pub norm: *const bdr_obs_norm,
+    pub has_ref_scores: i32,
+    pub ref_min_score: f32,
+    pub ref_max_score: f32,
+    pub env: bdr_eval_env_vtable,
+    pub agent_sample: Option<unsafe extern "C" fn(agent: *mut c_void, n_procs: u64, obs: *const c_void, act_out: *mut c_void) -> i32>,
+    pub agent_sample_raw: Option<
+        unsafe extern "C" fn(
+            agent: *mut c_void,
+            norm: *const bdr_obs_norm,
+            n: u64,
+            rows: *const c_void,
+            dtype: i32,
+            on_device: i32,
+            row_stride: u64,
+            act_out: *mut c_void,
+        ) -> i32,
+    >,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bdr_eval_result {
+    pub score: f32,
+    pub has_normalized: i32,
+    pub normalized: f32,
+    pub n_steps: u64,
+    pub n_episodes: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_trainer_post {
+    pub eval_interval: u64,
+    pub save_interval: u64,
+    pub evaluator: *const bdr_evaluator,
+    pub model_dir: *const c_char,
+    pub save_params: Option<unsafe extern "C" fn(agent: *mut c_void, dir: *const c_char) -> i32>,
 }
 
 pub type bdr_trainer_observer =
@@ -716,6 +786,38 @@ extern "C" {
         observer: bdr_trainer_observer,
         observer_ctx: *mut c_void,
         out: *mut bdr_trainer_stats,
+    ) -> i32;
+    pub fn bdr_evaluator_default(ev: *mut bdr_evaluator, agent: *mut bdr_agent);
+    pub fn bdr_evaluate(ev: *const bdr_evaluator, agent: *mut c_void, out: *mut bdr_eval_result) -> i32;
+    pub fn bdr_trainer_post_default(post: *mut bdr_trainer_post);
+    pub fn bdr_trainer_train_post(
+        c: *const bdr_trainer_config,
+        ops: *const bdr_trainer_ops,
+        env: *const bdr_env_vtable,
+        post: *const bdr_trainer_post,
+        observer: bdr_trainer_observer,
+        observer_ctx: *mut c_void,
+        out: *mut bdr_trainer_stats,
+    ) -> i32;
+    pub fn bdr_trainer_train_offline_post(
+        c: *const bdr_trainer_config,
+        ops: *const bdr_trainer_ops,
+        post: *const bdr_trainer_post,
+        observer: bdr_trainer_observer,
+        observer_ctx: *mut c_void,
+        out: *mut bdr_trainer_stats,
+    ) -> i32;
+    pub fn bdr_agent_set_act_path(a: *mut bdr_agent, path: i32) -> i32;
+    pub fn bdr_agent_sample_raw(
+        a: *mut bdr_agent,
+        norm: *const bdr_obs_norm,
+        n: u64,
+        rows: *const c_void,
+        dtype: i32,
+        on_device: i32,
+        row_stride: u64,
+        act_out: *mut f32,
+        idx_out: *mut i64,
     ) -> i32;
     pub fn bdr_trainer_train_offline(
         c: *const bdr_trainer_config,

@@ -60,6 +60,11 @@ where
         self.a.n_opts()
     }
 
+    /// Width of one action row (`Policy::sample` on raw rows: [`crate::evaluator::SampleRaw`]).
+    pub fn act_dim(&self) -> usize {
+        self.act_dim
+    }
+
     pub fn sync(&mut self) -> Result<()> {
         self.a.sync()
     }

@@ -15,6 +15,8 @@
 //! * [`AmdBc`] - `border-candle-agent/src/bc/base.rs` (behaviour cloning; [`BcConfig`] likewise).
 //! * [`AmdObsNorm`], [`AmdReplayBuffer::push_episode`] - `border-minari`'s `PenConverter` statistics / normalisation and
 //!   `MinariDataset::create_replay_buffer`'s episode push, on the device.
+//! * [`AmdEvaluator`], [`TrainerPost`], [`SampleRaw`] - `DefaultEvaluator` / `MinariEvaluator` and `Trainer::post_process` behind
+//!   `bdr_evaluate` and the `*_post` Trainer loops; `sample_raw` / `set_act_path` on the dense-agent agents (one-launch acting).
 //! * [`train_async`] - `border-async-trainer/src/util.rs:31-92` on one GPU (learner + actors + device mailbox), with the
 //!   optional cross-GPU exchange over RCCL ([`Comm`]).
 //!
@@ -30,6 +32,7 @@ pub mod config;
 pub mod dataset;
 pub mod dqn;
 pub mod error;
+pub mod evaluator;
 pub mod ffi;
 mod handle;
 pub mod iql;
@@ -49,6 +52,7 @@ pub use awac::AmdAwac;
 pub use bc::AmdBc;
 pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;
+pub use evaluator::{ActPath, AmdEvaluator, EvalResult, SampleRaw, TrainerPost};
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;
 pub use replay::AmdReplayBuffer;
