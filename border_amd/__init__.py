@@ -11,6 +11,7 @@ from .sac import Sac, SacConfig  # noqa: F401
 from .iqn import Iqn, IqnConfig  # noqa: F401
 from .iql import ActionLimit, CandleMlpConfig, GaussianActorConfig, Iql, IqlConfig, MultiCriticConfig, ValueConfig  # noqa: F401
 from .awac import Awac, AwacConfig  # noqa: F401
+from .candle_sac import CandleSac, CandleSacConfig, EntCoefMode  # noqa: F401
 from .bc import Bc, BcActionType, BcConfig, BcModelConfig  # noqa: F401
 from . import checkpoint  # noqa: F401
 from .atari import AtariDeviceEnv, AtariPreprocessor  # noqa: F401

@@ -105,6 +105,18 @@ class AwacConfigC(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class CandleSacConfigC(C.Structure):
+    _fields_ = [("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("actor", MlpConfigC), ("critic", MlpConfigC),
+                ("n_critics", C.c_int32), ("critic_tau", C.c_double), ("lr_actor", C.c_double), ("lr_critic", C.c_double),
+                ("opt_actor", AdamWConfigC), ("opt_critic", AdamWConfigC),
+                ("min_log_std", C.c_double), ("max_log_std", C.c_double), ("action_limit", C.c_int32), ("action_min", C.c_double),
+                ("action_max", C.c_double), ("action_scale", C.c_double), ("gamma", C.c_double),
+                ("ent_coef_mode", C.c_int32), ("ent_coef_alpha", C.c_double), ("target_entropy", C.c_double), ("ent_coef_lr", C.c_double),
+                ("actor_kind", C.c_int32), ("critic_loss", C.c_int32),
+                ("n_updates_per_opt", C.c_uint64), ("batch_size", C.c_uint64), ("train", C.c_int32), ("device", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class BcConfigC(C.Structure):
     _fields_ = [("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("policy", MlpConfigC), ("opt", AdamWConfigC), ("lr", C.c_double),
                 ("batch_size", C.c_uint64), ("action_type", C.c_int32), ("device", C.c_int32), ("record_verbose_level", C.c_int32),
@@ -240,6 +252,8 @@ ABI_SYMBOLS = [
     "bdr_sac_config_default", "bdr_sac_create", "bdr_sac_update_on_batch", "bdr_sac_sample", "bdr_sac_sample_device",
     "bdr_iql_config_default", "bdr_iql_create", "bdr_iql_update_on_batch", "bdr_iql_probe", "bdr_iql_sample", "bdr_iql_sample_device",
     "bdr_awac_config_default", "bdr_awac_create", "bdr_awac_update_on_batch", "bdr_awac_probe", "bdr_awac_sample", "bdr_awac_sample_device",
+    "bdr_candle_sac_config_default", "bdr_candle_sac_create", "bdr_candle_sac_update_on_batch", "bdr_candle_sac_probe", "bdr_candle_sac_sample",
+    "bdr_candle_sac_sample_device",
     "bdr_bc_config_default", "bdr_bc_create", "bdr_bc_update_on_batch", "bdr_bc_probe", "bdr_bc_sample", "bdr_bc_sample_device",
     "bdr_comm_get_unique_id", "bdr_comm_init_rank", "bdr_comm_destroy", "bdr_comm_agree", "bdr_sac_probe", "bdr_agent_allreduce_params",
     "bdr_agent_broadcast_params", "bdr_agent_set_grad_comm", "bdr_dqn_grads_on_batch", "bdr_agent_apply_grads",
@@ -273,7 +287,7 @@ def lib() -> C.CDLL:
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)  # AttributeError here == ABI drift
         if name not in ("bdr_last_error", "bdr_version", "bdr_dqn_config_default", "bdr_sac_config_default", "bdr_iqn_config_default", "bdr_iql_config_default",
-                        "bdr_awac_config_default", "bdr_bc_config_default",
+                        "bdr_awac_config_default", "bdr_bc_config_default", "bdr_candle_sac_config_default",
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
                         "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default"):
             fn.restype = C.c_int32
@@ -377,6 +391,13 @@ def lib() -> C.CDLL:
     L.bdr_awac_probe.argtypes = [vp, i32, vp, u64]
     L.bdr_awac_sample.argtypes = [vp, u64, vp, vp]
     L.bdr_awac_sample_device.argtypes = [vp, u64, vp, u64, vp]
+    L.bdr_candle_sac_config_default.restype = None
+    L.bdr_candle_sac_config_default.argtypes = [C.POINTER(CandleSacConfigC)]
+    L.bdr_candle_sac_create.argtypes = [C.POINTER(CandleSacConfigC), C.POINTER(vp)]
+    L.bdr_candle_sac_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.bdr_candle_sac_probe.argtypes = [vp, i32, vp, u64]
+    L.bdr_candle_sac_sample.argtypes = [vp, u64, vp, vp]
+    L.bdr_candle_sac_sample_device.argtypes = [vp, u64, vp, u64, vp]
     L.bdr_bc_config_default.restype = None
     L.bdr_bc_config_default.argtypes = [C.POINTER(BcConfigC)]
     L.bdr_bc_create.argtypes = [C.POINTER(BcConfigC), C.POINTER(vp)]

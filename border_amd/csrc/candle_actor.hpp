@@ -1,4 +1,5 @@
-// The candle-family agents (IQL: iql.hip, AWAC: awac.hip) share a GaussianActor over Mlp3 (util/actor.rs, mlp/mlp3.rs) and a
+// The candle-family agents (IQL: iql.hip, AWAC: awac.hip, SAC: candle_sac.hip) share a GaussianActor (util/actor.rs) over Mlp3
+// (mlp/mlp3.rs; SAC also over Mlp2, mlp/mlp2.rs: the two heads are one last layer of width 2 A, mean columns then s columns) and a
 // MultiCritic of Mlp on cat(obs, act) with soft-updated targets (util/critic.rs), trained on the FP32-MFMA kernels of dense.hpp.
 // This header holds what they share.  Device: the counter-based N(0,1) noise stream of Policy::sample, the fixed-order batch sums
 // (BC's loss, bc.hip, uses their butterfly and acc too) and the sample kernel.  Host: CandleAgent, the actor + critics + targets
@@ -86,7 +87,8 @@ __global__ __launch_bounds__(256) void k_candle_sample(CandleSampleArgs p)
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.n * p.A) return;
     const int b = t / p.A, j = t % p.A;
-    const float a = candle_sample_elem(p.e, p.mean[(size_t)b * p.ldm + j], j, (size_t)t);
+    const float* row = p.mean + (size_t)b * p.ldm;
+    const float a = candle_sample_elem(p.e, row[j], j, (size_t)t, p.e.mlp2 ? row[p.A + j] : 0.f);
     p.out[t] = a;
     if (p.xq) p.xq[(size_t)b * p.ldq + p.O + j] = a;
 }
@@ -108,8 +110,10 @@ template <class Self, class Cfg>
 struct CandleAgent : DenseAgent {
     Cfg cfg;
     int NC = 2;
+    int actor_kind = BDR_ACTOR_MLP3;   // BDR_ACTOR_MLP2: pn's last layer is [mean | s] (2 A columns) and there is no head2
     MlpLayout pn, qn;                  // actor mean (head2 follows pn in the actor arena), critic
-    size_t h2_off = 0, pi_total = 0;   // head2 at h2_off (= pn.total) in the actor arena; pi_total = pn.total + pad64(A)
+    size_t h2_off = 0, pi_total = 0;   // head2 at h2_off (= pn.total) in the actor arena; pi_total = pn.total + pad64(A) (Mlp2: pn.total)
+    bool mlp2() const { return actor_kind == BDR_ACTOR_MLP2; }
     // arenas: parameters, gradients, exp_avg, exp_avg_sq (+ the critics' targets)
     float *pi_p = nullptr, *pi_g = nullptr, *pi_m = nullptr, *pi_v = nullptr;
     float* q_p[4] = {nullptr}; float* q_t[4] = {nullptr}; float* q_g[4] = {nullptr}; float* q_m[4] = {nullptr}; float* q_v[4] = {nullptr};
@@ -174,7 +178,7 @@ struct CandleAgent : DenseAgent {
         const AdamScalars sc = opt_scalars(cfg.opt_actor, cfg.lr_actor, step_pi);
         std::vector<float*>* acts[1] = {&p_act}; std::vector<float*>* dys[1] = {&p_dy};
         const DenseReduceSeg h2seg{h2_part, (size_t)pad64(A), 1, (unsigned)(h2_off / 4), (unsigned)(pad64(A) / 4)};
-        return mlp_backward_step(pn, 1, &pi_p, &pi_g, &pi_m, &pi_v, nullptr, x_o, acts, dys, pi_part, 0, pi_off, &sc, Bn, "pi_bwd_adam", pi_total, &h2seg);
+        return mlp_backward_step(pn, 1, &pi_p, &pi_g, &pi_m, &pi_v, nullptr, x_o, acts, dys, pi_part, 0, pi_off, &sc, Bn, "pi_bwd_adam", pi_total, mlp2() ? nullptr : &h2seg);
     }
     // the critics' step from dL/dQ_i (c_dy's last layers): backward, Adam and the soft update of the targets
     int32_t critic_step(int Bn)
@@ -190,7 +194,7 @@ struct CandleAgent : DenseAgent {
     SampleElem sample_elem(int n, const float* z)
     {
         SampleElem e{};
-        e.head2 = pi_p + h2_off;
+        e.head2 = pi_p + h2_off; e.mlp2 = mlp2() ? 1 : 0;
         e.lo = (float)cfg.min_log_std; e.hi = (float)cfg.max_log_std; e.tanh_limit = cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
         e.amin = (float)cfg.action_min; e.amax = (float)cfg.action_max; e.scale = (float)cfg.action_scale;
         e.train = train ? 1 : 0; e.seed = cfg.seed; e.z = z;
@@ -324,7 +328,18 @@ struct CandleAgent : DenseAgent {
     {
         Slot s = slot(which);
         if (!s.p) return 0;
-        return s.net == &pn ? pn.ref_total + (uint64_t)A : s.net->ref_total;
+        return s.net == &pn && !mlp2() ? pn.ref_total + (uint64_t)A : s.net->ref_total;
+    }
+    // Mlp2's heads in the actor's reference view: the last layer's [weight [2A][H] | bias [2A]] (mean rows, then std rows) <->
+    // mean.weight [A][H], mean.bias [A], std.weight [A][H], std.bias [A] (mlp2.rs:47-52)
+    void mlp2_heads(float* ref, bool to_reference) const
+    {
+        const size_t H = (size_t)pn.L.back().in, a = (size_t)A, nw = a * H;
+        float* t = ref + pn.ref_total - (2 * nw + 2 * a);
+        std::vector<float> o(t, t + 2 * nw + 2 * a);
+        // layer order: Wm Ws bm bs; reference order: Wm bm Ws bs - the two middle blocks change places
+        if (to_reference) { std::copy(o.begin() + 2 * nw, o.begin() + 2 * nw + a, t + nw); std::copy(o.begin() + nw, o.begin() + 2 * nw, t + nw + a); }
+        else { std::copy(o.begin() + nw + a, o.begin() + 2 * nw + a, t + nw); std::copy(o.begin() + nw, o.begin() + nw + a, t + 2 * nw); }
     }
     int32_t get_params(int which, float* out, uint64_t n) override
     {
@@ -333,7 +348,8 @@ struct CandleAgent : DenseAgent {
         BDR_REQUIRE(n == param_count(which), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)param_count(which));
         std::vector<float> in(s.n);
         BDR_TRY(arena_to_reference(*s.net, s.p, in, out));
-        if (s.net == &pn) for (int j = 0; j < A; ++j) out[pn.ref_total + j] = in[h2_off + j];
+        if (s.net == &pn && mlp2()) mlp2_heads(out, true);
+        else if (s.net == &pn) for (int j = 0; j < A; ++j) out[pn.ref_total + j] = in[h2_off + j];
         return BDR_OK;
     }
     int32_t set_params(int which, const float* inp, uint64_t n) override
@@ -342,6 +358,11 @@ struct CandleAgent : DenseAgent {
         BDR_REQUIRE(s.p, "unknown %s model %d", Self::NAME, which);
         BDR_REQUIRE(n == param_count(which), "parameter count mismatch");
         std::vector<float> in(s.n, 0.f);
+        if (s.net == &pn && mlp2()) {
+            std::vector<float> ref(inp, inp + n);
+            mlp2_heads(ref.data(), false);
+            return arena_from_reference(*s.net, ref.data(), in, s.p);
+        }
         if (s.net == &pn) for (int j = 0; j < A; ++j) in[h2_off + j] = inp[pn.ref_total + j];
         return arena_from_reference(*s.net, inp, in, s.p);
     }
@@ -354,7 +375,14 @@ struct CandleAgent : DenseAgent {
     {
         std::vector<NamedTensor> mt;
         mlp_meta(pn, "actor.", mt);
-        mt.push_back({"actor.head2", {1, (uint64_t)A}});
+        if (mlp2()) {   // mlp2.rs:47-52: the trunk's ln{i}, then the heads `mean` and `std`
+            mt.resize(mt.size() - 2);
+            const uint64_t H = (uint64_t)pn.L.back().in;
+            for (const char* h : {"mean", "std"}) {
+                mt.push_back({std::string("actor.") + h + ".weight", {(uint64_t)A, H}});
+                mt.push_back({std::string("actor.") + h + ".bias", {(uint64_t)A}});
+            }
+        } else mt.push_back({"actor.head2", {1, (uint64_t)A}});
         return mt;
     }
     std::vector<NamedTensor> critic_meta() const   // one VarMap holds every critic: critic{i}.mlp.ln{k}.* (util/critic.rs:155-170)
@@ -399,12 +427,18 @@ struct CandleAgent : DenseAgent {
     // bdr_*_create after its null check: the checks in their order, the device, then the agent with its initial parameters.
     // value / opt_value: IQL's value model, checked before the actor's; one_row: why a one-row batch is refused (AWAC), null where one
     // row is allowed.
-    static int32_t create(const Cfg& c, bdr_agent** out, const bdr_mlp_config* value, const bdr_adamw_config* opt_value, const char* one_row)
+    // actor_kind: BDR_ACTOR_MLP3 for IQL and AWAC; SAC passes its config's.
+    static int32_t create(const Cfg& c, bdr_agent** out, const bdr_mlp_config* value, const bdr_adamw_config* opt_value, const char* one_row,
+                          int32_t actor_kind = BDR_ACTOR_MLP3)
     {
         BDR_REQUIRE(c.device >= 0, "No device is given for %s agent", Self::NAME);
         BDR_REQUIRE(c.obs_dim >= 1 && c.obs_dim <= 4096 && c.act_dim >= 1 && c.act_dim <= 256, "bad obs/act dims");
         if (value) BDR_TRY(check_mlp(*value, "value", false));
-        BDR_TRY(check_mlp(c.actor, "actor (Mlp3)", true));
+        BDR_REQUIRE(actor_kind == BDR_ACTOR_MLP3 || actor_kind == BDR_ACTOR_MLP2, "unknown actor_kind %d (BDR_ACTOR_MLP3 or BDR_ACTOR_MLP2)", actor_kind);
+        const bool two = actor_kind == BDR_ACTOR_MLP2;
+        BDR_TRY(check_mlp(c.actor, two ? "actor (Mlp2)" : "actor (Mlp3)", true));
+        // mlp.rs:14-24: mlp_forward's loop bound 0..=n_layers-2 underflows (usize) with a single trunk layer
+        BDR_REQUIRE(!two || c.actor.n_units >= 2, "actor (Mlp2): the reference's trunk needs at least 2 layers (units), got %d", c.actor.n_units);
         BDR_TRY(check_mlp(c.critic, "critic", false));
         BDR_REQUIRE(c.n_critics >= 1 && c.n_critics <= 4, "n_critics must be in [1,4]");
         if (one_row) BDR_REQUIRE(c.batch_size != 1, "%s", one_row);
@@ -417,9 +451,11 @@ struct CandleAgent : DenseAgent {
         Self* a = new Self();
         a->cfg = c; a->device = c.device; a->train = c.train != 0;
         a->O = c.obs_dim; a->A = c.act_dim; a->NC = c.n_critics;
-        a->pn = make_mlp(a->O, c.actor.units, c.actor.n_units, a->A, false);   // Mlp3: no output activation
+        a->actor_kind = actor_kind;
+        // Mlp3: no output activation.  Mlp2: ReLU after every trunk layer, then the two heads as one layer [mean | s] without one
+        a->pn = make_mlp(a->O, c.actor.units, c.actor.n_units, two ? 2 * a->A : a->A, false);
         a->qn = make_mlp(a->O + a->A, c.critic.units, c.critic.n_units, 1, c.critic.activation_out == BDR_ACTIVATION_RELU);
-        a->h2_off = a->pn.total; a->pi_total = a->pn.total + (size_t)pad64(a->A);
+        a->h2_off = a->pn.total; a->pi_total = a->pn.total + (two ? 0 : (size_t)pad64(a->A));
         const int32_t st = [&]() -> int32_t {
             BDR_HIP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
             BDR_TRY(a->err_init());

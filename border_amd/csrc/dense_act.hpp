@@ -46,17 +46,20 @@ namespace {
 using namespace bdr;
 
 // ---- the element code of Policy::sample, shared by the layer path's kernels and k_dense_act -----------------------------------
-// GaussianActor (util/actor.rs:226-241): train: mean + exp(clamp(head2)) z, eval: mean; then clamp or scale * tanh.  z = the host
+// GaussianActor (util/actor.rs:226-241): train: mean + exp(clamp(l)) z, eval: mean; then clamp or scale * tanh.  l = head2[j]
+// (Mlp3) or, with mlp2 set, exp(s) of the row's own s (Mlp2, mlp2.rs:41: the double exponential is the reference's).  z = the host
 // draw z[t] when given, else the device stream at counter + t (t = b * A + j).
 struct SampleElem {
     const float* head2; float lo, hi; int tanh_limit; float amin, amax, scale;
     int train; uint64_t seed, counter; const float* z;
+    int mlp2;
 };
-__device__ __forceinline__ float candle_sample_elem(const SampleElem& p, float a, int j, size_t t)
+__device__ __forceinline__ float candle_sample_elem(const SampleElem& p, float a, int j, size_t t, float s = 0.f)
 {
 #pragma clang fp contract(off)
     if (p.train) {
-        const float sd = expf(fminf(fmaxf(p.head2[j], p.lo), p.hi));
+        const float l = p.mlp2 ? expf(s) : p.head2[j];
+        const float sd = expf(fminf(fmaxf(l, p.lo), p.hi));
         const float zz = p.z ? p.z[t] : candle::randn_at(p.seed, p.counter, t);
         const float e = sd * zz;
         a = e + a;
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
         const int rr = e / a.A, j = e % a.A;
         const size_t t = (size_t)(m0 + rr) * a.A + j;
         const float z = cur[rr * ldz + j];
-        a.out[t] = a.mode == DA_CANDLE ? candle_sample_elem(a.e, z, j, t) : bc_act_out(a.kind, z);
+        a.out[t] = a.mode == DA_CANDLE ? candle_sample_elem(a.e, z, j, t, a.e.mlp2 ? cur[rr * ldz + a.A + j] : 0.f) : bc_act_out(a.kind, z);
     }
 }
 

@@ -75,6 +75,7 @@ class GaussianActorConfig:
     min_log_std: float = -20.0
     max_log_std: float = 2.0
     action_limit: ActionLimit = field(default_factory=ActionLimit.Clamp)
+    kind: str = "Mlp3"   # "Mlp3" | "Mlp2" (mlp/mlp2.rs): read by CandleSacConfig only; IQL and AWAC build Mlp3
 
 
 @dataclass

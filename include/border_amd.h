@@ -973,6 +973,81 @@ BDR_API int32_t bdr_awac_sample(bdr_agent* a, uint64_t n, const float* obs, floa
 BDR_API int32_t bdr_awac_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
 
 /* ------------------------------------------------------------------------------------------
+ * SAC agent of border-candle-agent  (border-candle-agent/src/sac/{base.rs,config.rs,ent_coef.rs}; online RL)
+ * Not the bdr_sac_* agent above, which restates border-tch-agent/src/sac.  Critics = MultiCritic of Mlp on cat(obs, act)
+ * (util/critic.rs), actor = GaussianActor (util/actor.rs) over Mlp3, as for IQL and AWAC, or over Mlp2 (mlp/mlp2.rs), the form the
+ * reference's examples build (examples/gym/sac_pendulum, sac_fetch_reach, convert_policy: SacConfig<Mlp, Mlp2>).
+ * ---------------------------------------------------------------------------------------- */
+/* The actor's policy model.  BDR_ACTOR_MLP3 (mlp/mlp3.rs): mean = Mlp(obs) and a state-independent `head2` [1, act_dim] as the
+ * log-std.  BDR_ACTOR_MLP2 (mlp/mlp2.rs:33-44): a trunk of `units` with ReLU after EVERY layer (mlp.rs:14-24 with Activation::ReLU),
+ * then mean = W_m h + b_m and the second output exp(W_s h + b_s), which GaussianActor clamps and exponentiates once more
+ * (util/actor.rs:199-201, 228-229): std = exp(clamp(exp(s), min_log_std, max_log_std)).  Mlp2 needs n_units >= 2: the reference's
+ * loop bound 0..=n_layers-2 underflows with one trunk layer (BDR_ERR_INVALID). */
+enum { BDR_ACTOR_MLP3 = 0, BDR_ACTOR_MLP2 = 1 };
+enum { BDR_ENT_COEF_FIX = 0, BDR_ENT_COEF_AUTO = 1 };   /* sac/ent_coef.rs:13-19 EntCoefMode::Fix(alpha) | Auto(target_entropy, lr) */
+
+/* SacConfig (sac/config.rs:82-93) with its MultiCriticConfig (util/critic.rs:35-43) and GaussianActorConfig (util/actor.rs:44-55).
+ * There is no reward_scale and there are no log-std bounds of the agent's own: the bounds are GaussianActorConfig's.  amsgrad is
+ * rejected, as for IQL.  batch_size must be >= 2: at one row the squeeze(D::Minus1) of sac/base.rs:83 turns the TD target into a
+ * scalar while each prediction keeps shape [1], and candle's same-shape tensor ops reject that pair (BDR_ERR_INVALID). */
+typedef struct {
+    int32_t obs_dim, act_dim;
+    bdr_mlp_config actor;         /* GaussianActorConfig.policy_config (Mlp3 or Mlp2: actor_kind) */
+    bdr_mlp_config critic;        /* MultiCriticConfig.q_config               */
+    int32_t n_critics;            /* MultiCriticConfig.n_nets (default 2)     */
+    double critic_tau;            /* MultiCriticConfig.tau (default 0.005)    */
+    double lr_actor, lr_critic;
+    bdr_adamw_config opt_actor, opt_critic;
+    double min_log_std, max_log_std;  /* GaussianActorConfig (-20, 2)     */
+    int32_t action_limit;             /* BDR_ACTION_LIMIT_* (default Clamp{-1, 1}) */
+    double action_min, action_max, action_scale;
+    double gamma;                 /* 0.99 (f32 in the reference) */
+    int32_t ent_coef_mode;        /* BDR_ENT_COEF_* (default Fix(1.0), sac/config.rs:90) */
+    double ent_coef_alpha;        /* Fix(alpha): log_alpha = (float)ln(alpha), never stepped */
+    double target_entropy;        /* Auto(target_entropy, _), used as f32 (ent_coef.rs:73-74) */
+    double ent_coef_lr;           /* Auto(_, lr): candle-nn AdamW defaults (weight decay 0.01) with this learning rate */
+    int32_t actor_kind;           /* BDR_ACTOR_* (default Mlp3) */
+    int32_t critic_loss;          /* BDR_LOSS_* (Mse)             */
+    uint64_t n_updates_per_opt, batch_size;   /* 1, 1 (batch_size 1 is rejected, see above) */
+    int32_t train;                /* false: the agent is built in eval mode (sac/base.rs:204) */
+    int32_t device;               /* -1: none given */
+    uint64_t seed;                /* the library's parameter initialiser and the device noise stream of Policy::sample */
+} bdr_candle_sac_config;
+BDR_API void bdr_candle_sac_config_default(bdr_candle_sac_config* cfg);                    /* sac/config.rs:82-93 */
+BDR_API int32_t bdr_candle_sac_create(const bdr_candle_sac_config* cfg, bdr_agent** out);  /* sac/base.rs:183-210 (Configurable::build) */
+/* One Sac::opt_ loop iteration (sac/base.rs:124-134) on a host minibatch: update_actor (:104-122), then update_critic (:63-102) on
+ * the same batch with the already updated actor and alpha, then the soft update of every target critic (:132).
+ *   update_actor: a = actor.sample(obs), logp = actor.logp(obs, a) (evaluated on the limited action: atanh(clamp(a / scale)) plus the
+ *     log-Jacobian of `a` itself, util/actor.rs:196-223); EntCoef::update(logp.detach()) (ent_coef.rs:71-84; Auto only) BEFORE alpha
+ *     is read; loss = mean(alpha logp - min_i Q_i(obs, a)) over the ONLINE critics.  The gradient reaches the actor through `a` (z
+ *     fixed) and through the mean and std logp reads; the minimum passes it to every critic whose value equals it.
+ *   update_critic: tgt = r + gamma_not_done (min_i Qtgt_i(next_obs, next_a) - alpha next_logp), gamma_not_done = (1 - is_terminated)
+ *     gamma; is_truncated is NOT counted (gamma_not_done(.., None, ..), :75-76); loss = mean over critics of mse / smooth_l1.
+ * Noise: in train mode z_pi / z_next are n * act_dim host N(0,1) draws for a and next_a, or NULL for the agent's device stream (the
+ * one bdr_agent_draw_noise reads); each NULL set takes n * act_dim draws, z_pi's first, row-major [n][act_dim].  Host draws take
+ * nothing from the stream.  Eval mode uses the means and no draws; the EntCoef steps in both modes.
+ * rec3: loss_critic, loss_actor, ent_coef (alpha after this update) - the record keys of :136-146, the two losses averaged over
+ * n_updates_per_opt by bdr_agent_opt_with_scalars.
+ * Parameter models for bdr_agent_{get,set}_params / param_count_of: 0 actor (Mlp3: mlp.ln{k}.weight/bias ..., then head2; Mlp2: the
+ * trunk's mlp.ln{k}.weight/bias, then mean.weight, mean.bias, std.weight, std.bias), 1+i critic_i, 1+n_critics+i critic_tgt_i,
+ * 1+2*n_critics log_alpha [1]; +100 gradient, +200 exp_avg, +300 exp_avg_sq.  SyncModel ships model 0 (the reference has no
+ * SyncModel for this agent).  Checkpoints (:244-270): actor.pt, critic.pt, critic.tgt.pt as for IQL, and ent_coef.pt (log_alpha [1]). */
+BDR_API int32_t bdr_candle_sac_update_on_batch(bdr_agent* a, uint64_t n, const float* obs, const float* act, const float* next_obs,
+                                               const float* reward, const int8_t* is_terminated, const int8_t* is_truncated,
+                                               const float* z_pi, const float* z_next, float* rec3);
+/* Parity probes: intermediates of the LAST update, to the host.  what:
+ *   0 a [B][act_dim]       actor.sample(obs) (:107)                  1 logp [B]       actor.logp(obs, a) (:108)
+ *   2 q_min [B]            min_i Q_i(obs, a) (:114)                  3 next_a [B][act_dim]  of the updated actor (:77)
+ *   4 next_logp [B]        (:78)                                     5 tgt [B]        the TD target (:79-83)
+ *   6 q_pred [n_critics][B]  Q_i(obs, act) (:71)                     7 dq_da [B][act_dim]   d q_min / d a */
+BDR_API int32_t bdr_candle_sac_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* Policy::sample (sac/base.rs:152-167 -> util/actor.rs:226-241): train: mean + std * N(0,1) (the agent's device noise stream,
+ * bdr_agent_draw_noise), eval: mean; then clamp(action_min, action_max) or action_scale * tanh. */
+BDR_API int32_t bdr_candle_sac_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out);
+/* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
+BDR_API int32_t bdr_candle_sac_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
+
+/* ------------------------------------------------------------------------------------------
  * BC agent  (border-candle-agent/src/bc/{base.rs,config.rs,model.rs}; behaviour cloning, offline)
  * Policy = Mlp (mlp/base.rs, mlp.rs:14-24): ReLU after every layer but the last, activation_out (all four BDR_ACTIVATION_*)
  * after the last.  No critic, no target, no noise.

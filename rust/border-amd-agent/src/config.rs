@@ -1240,6 +1240,134 @@ impl AwacConfig {
     }
 }
 
+/// The policy model of a candle [`GaussianActorConfig`] for SAC: `Mlp3` (`mlp/mlp3.rs`) or `Mlp2` (`mlp/mlp2.rs`), which the
+/// reference chooses by a type parameter (`SacConfig<Mlp, Mlp2>` in its examples), not in the YAML.
+#[derive(Clone, Copy, Debug, Deserialize, Serialize, PartialEq, Default)]
+pub enum ActorKind {
+    Mlp3,
+    #[default]
+    Mlp2,
+}
+
+/// `sac::SacConfig<Q, P>` of border-candle-agent (`sac/config.rs:22-52`, defaults `:82-93`), with the reference's field names:
+/// `actor_config`, `critic_config`, `gamma`, `ent_coef_mode`, `n_updates_per_opt`, `batch_size`, `critic_loss`, `device`.
+/// `actor_kind`, `train` and `engine_seed` are not reference fields: the policy model is the reference's type parameter `P` (its
+/// examples build `Mlp2`, the default here), `engine_seed` seeds the library's parameter initialiser and the device noise stream
+/// of `Policy::sample`.  `batch_size` must be >= 2 (`bdr_candle_sac_create` says why).
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct CandleSacConfig {
+    pub actor_config: GaussianActorConfig,
+    pub critic_config: MultiCriticConfig,
+    pub gamma: f64,
+    pub ent_coef_mode: EntCoefMode,
+    pub n_updates_per_opt: usize,
+    pub batch_size: usize,
+    pub critic_loss: CriticLoss,
+    pub device: Option<Device>,
+    #[serde(default)]
+    pub actor_kind: ActorKind,
+    #[serde(default)]
+    pub train: bool,
+    #[serde(default)]
+    pub engine_seed: u64,
+}
+
+impl Default for CandleSacConfig {
+    fn default() -> Self {
+        Self {
+            actor_config: Default::default(),
+            critic_config: Default::default(),
+            gamma: 0.99,
+            ent_coef_mode: EntCoefMode::Fix(1.0),
+            n_updates_per_opt: 1,
+            batch_size: 1,
+            critic_loss: CriticLoss::Mse,
+            device: None,
+            actor_kind: ActorKind::Mlp2,
+            train: false,
+            engine_seed: 0,
+        }
+    }
+}
+
+impl CandleSacConfig {
+    setter!(actor_config, GaussianActorConfig);
+    setter!(critic_config, MultiCriticConfig);
+    setter!(n_updates_per_opt, usize);
+    setter!(batch_size, usize);
+    setter!(ent_coef_mode, EntCoefMode);
+    setter!(critic_loss, CriticLoss);
+    setter!(actor_kind, ActorKind);
+    yaml_io!();
+
+    /// `SacConfig::discount_factor`: sets `gamma`.
+    pub fn discount_factor(mut self, v: f64) -> Self {
+        self.gamma = v;
+        self
+    }
+
+    pub fn device(mut self, device: Device) -> Self {
+        self.device = Some(device);
+        self
+    }
+
+    pub(crate) fn to_c(&self) -> Result<ffi::bdr_candle_sac_config> {
+        let mut c: ffi::bdr_candle_sac_config = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_sac_config_default(&mut c) };
+        let p = self.actor_config.policy_config.as_ref().ok_or_else(|| anyhow!("policy_config is not set."))?;
+        let q = self.critic_config.q_config.as_ref().ok_or_else(|| anyhow!("q_config is not set."))?;
+        c.obs_dim = p.in_dim as i32;
+        c.act_dim = p.out_dim as i32;
+        if q.in_dim != p.in_dim + p.out_dim || q.out_dim != 1 {
+            return Err(anyhow!("critic q_config must map obs_dim + act_dim = {} inputs to 1 output", p.in_dim + p.out_dim));
+        }
+        p.fill(&mut c.actor, "policy_config")?;
+        q.fill(&mut c.critic, "q_config")?;
+        c.actor_kind = match self.actor_kind {
+            ActorKind::Mlp3 => ffi::BDR_ACTOR_MLP3,
+            ActorKind::Mlp2 => ffi::BDR_ACTOR_MLP2,
+        };
+        c.n_critics = self.critic_config.n_nets as i32;
+        c.critic_tau = self.critic_config.tau;
+        c.lr_actor = self.actor_config.opt_config.lr();
+        c.lr_critic = self.critic_config.opt_config.lr();
+        self.actor_config.opt_config.fill(&mut c.opt_actor);
+        self.critic_config.opt_config.fill(&mut c.opt_critic);
+        c.min_log_std = self.actor_config.min_log_std as f64;
+        c.max_log_std = self.actor_config.max_log_std as f64;
+        match self.actor_config.action_limit {
+            ActionLimit::Clamp { action_min, action_max } => {
+                c.action_limit = ffi::BDR_ACTION_LIMIT_CLAMP;
+                c.action_min = action_min as f64;
+                c.action_max = action_max as f64;
+            }
+            ActionLimit::Tanh { action_scale } => {
+                c.action_limit = ffi::BDR_ACTION_LIMIT_TANH;
+                c.action_scale = action_scale as f64;
+            }
+        }
+        c.gamma = self.gamma;
+        match self.ent_coef_mode {
+            EntCoefMode::Fix(alpha) => {
+                c.ent_coef_mode = ffi::BDR_ENT_COEF_FIX;
+                c.ent_coef_alpha = alpha;
+            }
+            EntCoefMode::Auto(target_entropy, lr) => {
+                c.ent_coef_mode = ffi::BDR_ENT_COEF_AUTO;
+                c.target_entropy = target_entropy;
+                c.ent_coef_lr = lr;
+            }
+        }
+        c.critic_loss = self.critic_loss.code();
+        c.n_updates_per_opt = self.n_updates_per_opt as u64;
+        c.batch_size = self.batch_size as u64;
+        c.train = self.train as i32;
+        c.seed = self.engine_seed;
+        c.device = Device::ordinal(&self.device, "SAC");
+        Ok(c)
+    }
+}
+
 /// `bc::BcActionType` (`bc/config.rs`).
 #[derive(Clone, Copy, Debug, Deserialize, Serialize, PartialEq)]
 pub enum BcActionType {

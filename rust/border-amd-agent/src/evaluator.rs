@@ -8,11 +8,12 @@
 //! * [`TrainerPost`] - `Trainer::post_process` (`trainer.rs:231-264`) for `bdr_trainer_train_post` /
 //!   `bdr_trainer_train_offline_post`: evaluate every `eval_interval` opt steps between `eval()` and `train()`, keep the best
 //!   model under `model_dir/best`, save every `save_interval` opt steps under `model_dir/<opt_steps>`; 0 means never.
-//! * [`SampleRaw`] - `sample_raw` / `set_act_path` on [`AmdIql`], [`AmdAwac`] and [`AmdBc`].
+//! * [`SampleRaw`] - `sample_raw` / `set_act_path` on [`AmdIql`], [`AmdAwac`], [`AmdCandleSac`] and [`AmdBc`].
 use crate::{
     awac::AmdAwac,
     bc::AmdBc,
     bytes::{ActFromRows, ObsRows, RowBatch},
+    candle_sac::AmdCandleSac,
     dataset::{AmdObsNorm, ObsElem},
     error::check,
     ffi,
@@ -97,6 +98,7 @@ macro_rules! impl_sample_raw {
 }
 impl_sample_raw!(AmdIql);
 impl_sample_raw!(AmdAwac);
+impl_sample_raw!(AmdCandleSac);
 impl_sample_raw!(AmdBc);
 
 /// What one evaluation returns (`bdr_eval_result`).

@@ -33,6 +33,10 @@ pub const BDR_ACTIVATION_TANH: i32 = 2;
 pub const BDR_ACTIVATION_SIGMOID: i32 = 3;
 pub const BDR_ACTION_LIMIT_CLAMP: i32 = 0;
 pub const BDR_ACTION_LIMIT_TANH: i32 = 1;
+pub const BDR_ACTOR_MLP3: i32 = 0;
+pub const BDR_ACTOR_MLP2: i32 = 1;
+pub const BDR_ENT_COEF_FIX: i32 = 0;
+pub const BDR_ENT_COEF_AUTO: i32 = 1;
 pub const BDR_BC_ACTION_DISCRETE: i32 = 0;
 pub const BDR_BC_ACTION_CONTINUOUS: i32 = 1;
 pub const BDR_BC_KERNEL_DEFAULT: i32 = 0;
@@ -596,6 +600,40 @@ pub struct bdr_awac_config {
     pub seed: u64,
 }
 
+/// SacConfig of border-candle-agent (sac/config.rs:82-93) + MultiCriticConfig, GaussianActorConfig, EntCoefMode
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bdr_candle_sac_config {
+    pub obs_dim: i32,
+    pub act_dim: i32,
+    pub actor: bdr_mlp_config,
+    pub critic: bdr_mlp_config,
+    pub n_critics: i32,
+    pub critic_tau: f64,
+    pub lr_actor: f64,
+    pub lr_critic: f64,
+    pub opt_actor: bdr_adamw_config,
+    pub opt_critic: bdr_adamw_config,
+    pub min_log_std: f64,
+    pub max_log_std: f64,
+    pub action_limit: i32,
+    pub action_min: f64,
+    pub action_max: f64,
+    pub action_scale: f64,
+    pub gamma: f64,
+    pub ent_coef_mode: i32,
+    pub ent_coef_alpha: f64,
+    pub target_entropy: f64,
+    pub ent_coef_lr: f64,
+    pub actor_kind: i32,
+    pub critic_loss: i32,
+    pub n_updates_per_opt: u64,
+    pub batch_size: u64,
+    pub train: i32,
+    pub device: i32,
+    pub seed: u64,
+}
+
 /// BcConfig (bc/config.rs:66-75) + BcModelConfig (bc/model.rs)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -948,6 +986,26 @@ extern "C" {
     pub fn bdr_awac_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_awac_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
     pub fn bdr_awac_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
+
+    // ---- SAC of border-candle-agent (border-candle-agent/src/sac)
+    pub fn bdr_candle_sac_config_default(cfg: *mut bdr_candle_sac_config);
+    pub fn bdr_candle_sac_create(cfg: *const bdr_candle_sac_config, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_candle_sac_update_on_batch(
+        a: *mut bdr_agent,
+        n: u64,
+        obs: *const f32,
+        act: *const f32,
+        next_obs: *const f32,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+        z_pi: *const f32,
+        z_next: *const f32,
+        rec3: *mut f32,
+    ) -> i32;
+    pub fn bdr_candle_sac_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
+    pub fn bdr_candle_sac_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
+    pub fn bdr_candle_sac_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
 
     // ---- BC (border-candle-agent/src/bc)
     pub fn bdr_bc_config_default(cfg: *mut bdr_bc_config);

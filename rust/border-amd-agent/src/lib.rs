@@ -12,6 +12,8 @@
 //!   and serde layout ([`config`]), so the example YAML files load unchanged.
 //! * [`AmdIql`] - `border-candle-agent/src/iql/base.rs` (offline RL; [`IqlConfig`] deserialises the candle YAML names).
 //! * [`AmdAwac`] - `border-candle-agent/src/awac/base.rs` (offline and online RL; [`AwacConfig`] likewise).
+//! * [`AmdCandleSac`] - `border-candle-agent/src/sac/base.rs` (the candle SAC with its `Mlp2` Gaussian actor; [`CandleSacConfig`]
+//!   likewise).
 //! * [`AmdBc`] - `border-candle-agent/src/bc/base.rs` (behaviour cloning; [`BcConfig`] likewise).
 //! * [`AmdObsNorm`], [`AmdReplayBuffer::push_episode`] - `border-minari`'s `PenConverter` statistics / normalisation and
 //!   `MinariDataset::create_replay_buffer`'s episode push, on the device.
@@ -27,6 +29,7 @@ pub mod async_trainer;
 pub mod awac;
 pub mod bc;
 pub mod bytes;
+pub mod candle_sac;
 pub mod comm;
 pub mod config;
 pub mod dataset;
@@ -46,10 +49,11 @@ pub use comm::Comm;
 pub use config::{
     ActionLimit, Activation, CandleMlpConfig, CandleOptimizerConfig, GaussianActorConfig, MultiCriticConfig, ValueConfig,
     ActorConfig, AtariCnnConfig, CriticConfig, CriticLoss, Device, DqnConfig, DqnExplorer, DqnModelConfig, EntCoefMode, EpsilonGreedy,
-    Arithmetic, AwacConfig, BcActionType, BcConfig, BcKernelForm, BcModelConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
+    ActorKind, Arithmetic, AwacConfig, CandleSacConfig, BcActionType, BcConfig, BcKernelForm, BcModelConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
 };
 pub use awac::AmdAwac;
 pub use bc::AmdBc;
+pub use candle_sac::AmdCandleSac;
 pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;
 pub use evaluator::{ActPath, AmdEvaluator, EvalResult, SampleRaw, TrainerPost};
