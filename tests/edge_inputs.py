@@ -536,8 +536,9 @@ class Check:
     bar: object = 0.0   # rel / abs: the bar; elem: (rel, abs)
     sl: object = None   # a slice or index array of the flattened quantity
     how: str = ""       # where the bar comes from
-    against: str = "f64"   # parameters and targets keep their existing reference, the f32 restatement (the Adam step is not under test:
-                           # on gradients of 1e-20 an f32 and a float64 Adam legitimately differ by more than 0.3 lr)
+    against: str = "f64"   # parameters and targets keep their existing reference, the f32 restatement (the Adam step is under test in
+                           # tests/optimizer_inputs.py, element by element from the device's own gradient, not here: on gradients of
+                           # 1e-20 an f32 and a float64 Adam of the WHOLE update legitimately differ by more than 0.3 lr)
 
     def _pick(self, x):
         x = np.asarray(x, np.float64).reshape(-1)
