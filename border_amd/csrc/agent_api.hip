@@ -246,6 +246,7 @@ int32_t bdr_agent::err_report(const unsigned* w)
         g_err_deferred = 1;
         return st__;
     }
+    if (act) on_action_error();
     const int32_t st__ = act ? fail(BDR_ERR_INVALID, "an action index outside [0, n_actions) reached the TD step (the reference's gather raises "
                                                       "an index error); it was clamped")
                              : fail(BDR_ERR_INVALID, "non-finite value flagged on the device (%u)", nonf);
@@ -304,6 +305,8 @@ static int32_t err_check_after_step(bdr_agent* a)
 }
 
 static bool is_dqn(const bdr_agent* a) { return a && (!strcmp(a->kind(), "dqn_cnn") || !strcmp(a->kind(), "dqn_mlp")); }
+// the agents whose record starts with the five values of bdr_dqn_record: the tch DQN and the candle DQN (candle_dqn.hip)
+static bool has_dqn_record(const bdr_agent* a) { return is_dqn(a) || (a && !strcmp(a->kind(), "candle_dqn")); }
 
 extern "C" {
 
@@ -375,7 +378,7 @@ int32_t bdr_agent_opt(bdr_agent* a, bdr_replay* r)
 int32_t bdr_agent_opt_with_record(bdr_agent* a, bdr_replay* r, bdr_dqn_record* rec)
 {
     BDR_REQUIRE(a && r && rec, "null argument");
-    BDR_REQUIRE(is_dqn(a), "bdr_agent_opt_with_record(bdr_dqn_record) needs a DQN agent; use bdr_agent_opt_with_scalars");
+    BDR_REQUIRE(has_dqn_record(a), "bdr_agent_opt_with_record(bdr_dqn_record) needs a DQN agent; use bdr_agent_opt_with_scalars");
     BDR_HIP(hipSetDevice(a->device));
     BDR_TRY(a->err_poll());   // as bdr_agent_opt: a failure of an earlier step is reported before this one is enqueued
     a->last_replay_uid = r->uid;
@@ -509,7 +512,9 @@ static int32_t action_values(bdr_agent* a, uint64_t n, const void* obs, std::vec
     BDR_HIP(hipSetDevice(a->device));
     const int A = (int)a->param_count(-1);   // number of actions (every value agent reports it as which = -1)
     q.resize(n * A);
-    if (!strcmp(a->kind(), "dqn_cnn")) BDR_TRY(dqn_cnn_qvalues(a, n, obs, q.data()));
+    int32_t st = BDR_OK;
+    if (a->qvalues_f32(n, obs, q.data(), &st)) BDR_TRY(st);
+    else if (!strcmp(a->kind(), "dqn_cnn")) BDR_TRY(dqn_cnn_qvalues(a, n, obs, q.data()));
     else if (!strcmp(a->kind(), "dqn_mlp")) BDR_TRY(dqn_mlp_qvalues(a, n, obs, q.data()));
     else if (!strcmp(a->kind(), "iqn")) BDR_TRY(bdr_iqn_qvalues(a, n, obs, q.data(), nullptr));
     else return fail(BDR_ERR_INVALID, "agent kind '%s' has no discrete action values", a->kind());
@@ -554,6 +559,7 @@ int32_t bdr_agent_set_explorer(bdr_agent* a, const bdr_explorer_config* e)
     x.n_calls = e->n_calls;
     seed_from_u64(e->seed, x.key.k);
     x.word_pos = 0;
+    a->explorer_reseed(e->seed);
     return BDR_OK;
 }
 
@@ -570,6 +576,10 @@ int32_t bdr_agent_get_explorer(const bdr_agent* a, bdr_explorer_config* e)
 int32_t bdr_agent_sample(bdr_agent* a, uint64_t n, const void* obs, int64_t* act_out, bdr_sample_info* info)
 {
     BDR_REQUIRE(a && obs && act_out, "null argument");
+    {   // an agent with a Policy::sample and an exploration stream of its own (the candle DQN)
+        int32_t st = BDR_OK;
+        if (a->sample_i64(n, obs, act_out, info, &st)) return st;
+    }
     std::vector<float> q;
     int A = 0;
     a->err_fresh = false;   // (set again only by THIS call's own pinned read-back: a flag left by an earlier qvalues call must not send this one down the poll on old words)

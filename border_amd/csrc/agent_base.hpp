@@ -65,7 +65,8 @@ struct ObsRow {
     void swap(ObsRow& o) { std::swap(h, o.h); std::swap(d, o.d); }   // `a = b` of the reference where b is dead afterwards
 };
 
-// rows -> pinned host memory, then the sequence number the host waits for (system-scope release: the rows are visible before it); the
+// rows -> pinned host memory as 32-bit WORDS (the rows are moved, never read as numbers: i64 indices travel as two words each,
+// bdr_agent::words_to_host), then the sequence number the host waits for (system-scope release: the rows are visible before it); the
 // device-side error words ride along (bdr_agent::err_poll reads them)
 constexpr size_t ROWS_PINNED_MAX_FLOATS = 4096;
 // the device's error words -> their pinned host mirror (bdr_agent::err_poll, every ERR_POLL_INTERVAL opts): a one-wave kernel in the
@@ -78,7 +79,9 @@ static __global__ __launch_bounds__(64) void k_err_mirror(const unsigned* dev_er
 
 static __global__ __launch_bounds__(256) void k_publish_rows(const float* src, float* dst_host, unsigned n, unsigned* seq_host, unsigned seq, const unsigned* dev_err, int n_err)
 {
-    for (unsigned i = threadIdx.x; i < n; i += 256) dst_host[i] = src[i];
+    const unsigned* s = reinterpret_cast<const unsigned*>(src);
+    unsigned* d = reinterpret_cast<unsigned*>(dst_host);
+    for (unsigned i = threadIdx.x; i < n; i += 256) d[i] = s[i];
     if (dev_err && (int)threadIdx.x < n_err) seq_host[4 + threadIdx.x] = dev_err[threadIdx.x];
     __threadfence_system();
     __syncthreads();
@@ -176,6 +179,12 @@ struct bdr_agent {
         BDR_HIP(hipGetLastError());
         return rows_wait(seq, out, n_floats);
     }
+    // the same for results that are not floats (i64 action indices): n_words 32-bit words, moved as bytes on every leg (k_publish_rows
+    // copies words, rows_wait and the large-result path use memcpy / a copy command)
+    int32_t words_to_host(const void* dev_words, void* out, size_t n_words)
+    {
+        return rows_to_host(static_cast<const float*>(dev_words), static_cast<float*>(out), n_words);
+    }
     // wait for sequence number `seq` in the pinned area, then copy the rows (and this call's view of the error words) out
     int32_t rows_wait(unsigned seq, float* out, size_t n_floats)
     {
@@ -218,6 +227,9 @@ struct bdr_agent {
     }
     bool err_fresh = false;   // host_err was refreshed by the call in progress (an acting call's Q rows brought the words along): poll, do not copy again
     virtual void on_gate_timeout() {}   // DqnCnn: fall back to event ordering
+    // Called by err_report when an out-of-range action is reported, after the stream has been synchronised and the words cleared:
+    // an agent whose device skipped the flagged updates (the candle DQN) puts its host counters back to what was applied
+    virtual void on_action_error() {}
     // Called by err_report BEFORE it clears the error words: every queue of the agent must be idle by then.  While the words are up
     // the waits queued on the other queues return at once (poison); cleared under them they would start a fresh time limit and
     // could poison the agent a second time, and kernels still queued there would write the batch sets the fallback schedule reads.
@@ -308,11 +320,17 @@ struct bdr_agent {
     // Policy::sample with f32 action rows, where the handle itself implements it (the candle-family agents: CandleAgent,
     // candle_actor.hpp).  obs: host rows, or device rows `stride` bytes apart when on_device.  false: not such an agent, nothing done.
     virtual bool sample_f32(uint64_t, const void*, bool /*on_device*/, uint64_t /*stride*/, float*, int32_t* /*status*/) { return false; }
+    // Policy::sample with i64 action indices and the action values [n][A], where the handle itself implements them with an
+    // exploration stream of its own (the candle DQN, candle_dqn.hip: SmallRng instead of `explorer`'s ChaCha stream).  obs: host
+    // rows, or device rows inside a DeviceRowsScope.  false: not such an agent, nothing done (bdr_agent_sample / bdr_agent_qvalues).
+    virtual bool sample_i64(uint64_t, const void*, int64_t*, bdr_sample_info*, int32_t* /*status*/) { return false; }
+    virtual bool qvalues_f32(uint64_t, const void*, float*, int32_t* /*status*/) { return false; }
+    virtual void explorer_reseed(uint64_t /*seed*/) {}   // bdr_agent_set_explorer: the stream starts again from `seed`
     // bdr_agent_set_act_path / bdr_agent_sample_raw: the DenseAgent agents (dense_agent.hpp: IQL, AWAC, BC) implement them
     virtual int32_t set_act_path(int32_t path)
     {
         if (path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS) return BDR_OK;
-        return ::bdr::fail(BDR_ERR_INVALID, path == BDR_ACT_PATH_FUSED ? "this agent kind has no fused acting kernel (IQL, AWAC and BC have one)" : "unknown act path");
+        return ::bdr::fail(BDR_ERR_INVALID, path == BDR_ACT_PATH_FUSED ? "this agent kind has no fused acting kernel (IQL, AWAC, BC and the candle SAC and DQN have one)" : "unknown act path");
     }
     virtual int32_t sample_raw(const bdr_obs_norm*, uint64_t, const void*, int32_t, bool, uint64_t, float*, int64_t*)
     {

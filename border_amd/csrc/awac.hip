@@ -182,8 +182,7 @@ __global__ __launch_bounds__(1024) void k_awac_critic_loss(AwacCriticArgs p)
             const float q = p.q[i][(size_t)b * p.ldq];
             const float d = q - p.tgt[b];
             float l, g;
-            if (p.loss_kind == 1) { const float z = fabsf(d); const float hz = 0.5f * z; l = z < 1.f ? hz * z : z - 0.5f; g = z < 1.f ? d : (d > 0.f ? 1.f : -1.f); }
-            else { l = d * d; g = 2.f * d; }
+            candle::critic_loss_elem(p.loss_kind, d, l, g);
             float gq = g * invB;
             if (p.relu_out && !(q > 0.f)) gq = 0.f;
             p.dq[i][(size_t)b * p.ldq] = gq;

@@ -55,6 +55,14 @@ __device__ __forceinline__ float row_max(int B, F&& value, float* red32)
     }
     return m;
 }
+// The critic-loss element of every candle agent's update_critic (candle_nn::loss::mse, util.rs:144-152 smooth_l1_loss with beta 1):
+// d = pred - tgt -> the loss element l and dl/dpred g, before the mean's scale.  One definition for IQL, AWAC, SAC and DQN.
+__device__ __forceinline__ void critic_loss_elem(int loss_kind, float d, float& l, float& g)
+{
+#pragma clang fp contract(off)
+    if (loss_kind == 1) { const float z = fabsf(d); const float hz = 0.5f * z; l = z < 1.f ? hz * z : z - 0.5f; g = z < 1.f ? d : (d > 0.f ? 1.f : -1.f); }
+    else { l = d * d; g = 2.f * d; }
+}
 __device__ __forceinline__ float acc(float base, float s, float scale)   // base + s * scale, rounded step by step
 {
 #pragma clang fp contract(off)

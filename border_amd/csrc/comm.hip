@@ -217,6 +217,7 @@ int32_t bdr_agent_set_grad_comm(bdr_agent* a, bdr_comm* c)
         BDR_REQUIRE(strcmp(agent_kind(a), "awac") != 0, "synchronous data-parallel gradient exchange is not available for AWAC agents");
         BDR_REQUIRE(strcmp(agent_kind(a), "bc") != 0, "synchronous data-parallel gradient exchange is not available for BC agents");
         BDR_REQUIRE(strcmp(agent_kind(a), "candle_sac") != 0, "synchronous data-parallel gradient exchange is not available for candle SAC agents");
+        BDR_REQUIRE(strcmp(agent_kind(a), "candle_dqn") != 0, "synchronous data-parallel gradient exchange is not available for candle DQN agents");
         int dev = 0;
         BDR_REQUIRE(agent_arena(a, 4, nullptr, nullptr, &dev), "agent has no gradient arena");
         BDR_REQUIRE(dev == c->device, "agent and communicator live on different devices");

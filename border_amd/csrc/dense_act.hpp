@@ -11,7 +11,7 @@
 //   (dense.hpp) with the LDS rows as the A operand, then bias and ReLU in dense_small_body's order: the tile k_dense_small forms.
 //   DenseAgent's forward always takes k_dense_small (dense_forward_z(..., true)), so the actions have the bits of the
 //   layer-by-layer path at every n (tests/test_gpu_dense_act.py asserts == on the raw bits).  The element code of the two
-//   epilogues (candle_sample_elem, bc_act_out / bc_argmax) is shared with k_candle_sample and k_bc_act.
+//   epilogues (candle_sample_elem, bc_act_out / bc_argmax, dqn_q_argmax) is shared with k_candle_sample, k_bc_act and k_cdqn_act.
 //   Latency.  A tile's weight loads depend on nothing the kernel computes.  TEAMS four-wave teams take TEAMS tiles of a layer per
 //   round (wave w of a team: k-slice w of its tile), and each wave fetches the weights and the bias of its NEXT round - also across
 //   the layer boundary - before the MFMAs of the current one (dense_small_load_b; layers with a reduction over 256 load inside
@@ -23,7 +23,7 @@
 //   input / output.  TEAMS = 2 when that fits 160 KB (W <= 448), else 1 (W <= 512: 148 992 bytes); wider networks keep the layer path.
 //   Bounds.  rows: block row r is read from memory only for m0 + r < n and column c < O, and stored (out / idx) only for
 //   m0 + r < n; LDS rows r >= n - m0 are zero.  LDS: r < 32, c < Kp or Np <= W.  Weights: k < Kp, column < Np of the layer
-//   (t < Np / 32).  out: (m0 + r) * A + j < n * A.  mean / std: c < O = the normaliser's dim (checked by the host).
+//   (t < Np / 32).  out: (m0 + r) * A + j < n * A; idx: m0 + r < n.  mean / std: c < O = the normaliser's dim (checked by the host).
 #pragma once
 
 namespace bdr {
@@ -87,6 +87,11 @@ __device__ __forceinline__ int bc_argmax(int kind, const float* z, int A)
     return best;
 }
 
+// the candle DQN (dqn/base.rs:103, :108, :226): argmax over a row of action values, the output activation already applied by the
+// last layer.  bc_argmax's rule: the lowest index among equal values; a NaN never wins a comparison, so a row whose first value is
+// NaN answers 0 and a NaN elsewhere is passed over.
+__device__ __forceinline__ int dqn_q_argmax(const float* q, int A) { return bc_argmax(BDR_ACTIVATION_NONE, q, A); }
+
 // ---- the layer path's prologue for raw rows: out[k][c] = z((float)rows[k][c]) (norm given) or (float)rows[k][c], contiguous f32 rows
 template <typename T>
 __global__ __launch_bounds__(256) void k_act_raw_rows(const uint8_t* __restrict__ rows, unsigned long long row_stride, unsigned long long n, int O,
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(256) void k_act_raw_rows(const uint8_t* __restrict_
 constexpr int DA_MAX_LAYERS = BDR_MAX_UNITS + 1;
 constexpr int DA_MAX_W = 512;
 constexpr size_t DA_LDS_MAX = 160 * 1024;
-enum { DA_CANDLE = 0, DA_BC = 1, DA_BC_DISCRETE = 2 };
+enum { DA_CANDLE = 0, DA_BC = 1, DA_BC_DISCRETE = 2, DA_DQN = 3 };
 inline size_t dense_act_lds(int W, int teams) { return ((size_t)2 * 32 * (W + 4) + (size_t)teams * 4 * 32 * 33) * sizeof(float); }
 
 struct DenseActLayer { const float* w; const float* b; int Kp, Np, relu; };
@@ -115,7 +120,7 @@ struct DenseActArgs {
     DenseActLayer L[DA_MAX_LAYERS];
     int mode, kind;                                                // DA_*; BC: activation_out
     SampleElem e;                                                  // DA_CANDLE
-    float* out; long long* idx;                                    // [n][A] actions (DA_CANDLE, DA_BC); [n] (DA_BC_DISCRETE)
+    float* out; long long* idx;                                    // [n][A] actions (DA_CANDLE, DA_BC); [n] (DA_BC_DISCRETE); both (DA_DQN)
 };
 
 // "these loaded registers have landed": the wait is HERE, before the next round's loads are issued behind them (dense_chain.hpp chain_land)
@@ -213,6 +218,14 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
     const int ldz = a.L[a.nl - 1].Np + 4;
     if (a.mode == DA_BC_DISCRETE) {
         if (tid < rows_here) a.idx[m0 + tid] = bc_argmax(a.kind, cur + tid * ldz, a.A);
+        return;
+    }
+    if (a.mode == DA_DQN) {   // the candle DQN (dqn/base.rs:203): the Q rows themselves and each row's first maximum (dqn_q_argmax)
+        for (int e = tid; e < rows_here * a.A; e += NTHR) {
+            const int rr = e / a.A, j = e % a.A;
+            a.out[(size_t)(m0 + rr) * a.A + j] = cur[rr * ldz + j];
+        }
+        if (tid < rows_here) a.idx[m0 + tid] = dqn_q_argmax(cur + tid * ldz, a.A);
         return;
     }
     for (int e = tid; e < rows_here * a.A; e += NTHR) {

@@ -1,5 +1,5 @@
-// DenseAgent: the host core under every agent whose models are Mlps trained on dense.hpp's FP32-MFMA kernels (BC: bc.hip; IQL and
-// AWAC through CandleAgent, candle_actor.hpp).  It knows how such a network is allocated, run forward, stepped (input gradients,
+// DenseAgent: the host core under every agent whose models are Mlps trained on dense.hpp's FP32-MFMA kernels (BC: bc.hip; the candle
+// DQN: candle_dqn.hip; IQL, AWAC and the candle SAC through CandleAgent, candle_actor.hpp).  It knows how such a network is allocated, run forward, stepped (input gradients,
 // the grouped dW, the fused reduce + Adam), fed the observation rows of an acting call, and copied to and from the reference
 // layout - and nothing about which models an agent has: an agent brings its arenas, its batch buffers, its loss kernels and its
 // update schedule.  Host code only; with it the checkpoint helpers of candle VarMaps and the optimizer check the agents share.
@@ -133,11 +133,14 @@ struct DenseAgent : bdr_agent {
     };
     // backward of nz networks of one layout from the output gradient dy[z][lo] of layer lo (the last layer, or below it where the
     // agent's own kernel has already formed the gradients above: BC's fused head): input gradients down to layer 1 (one launch per
-    // layer for all nz), every weight gradient in one grouped launch, then the fused reduce + Adam (+ tracking into tgt at rate tau)
+    // layer for all nz), every weight gradient in one grouped launch, then the fused reduce + Adam (+ tracking into tgt at rate tau).
+    // poison (optional): a device word that, when non-zero, makes the reduce + Adam launch leave everything alone (the candle DQN's
+    // out-of-range action flag); applied / step: *applied = step by a launch that was not skipped.
     int32_t mlp_backward_step(const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
                               const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
                               const std::vector<size_t>& off, const AdamScalars* sc, int Bn, const StepNames& names, size_t total, double tau, int lo,
-                              const DenseReduceSeg* extra = nullptr)
+                              const DenseReduceSeg* extra = nullptr, const unsigned* poison = nullptr, unsigned long long* applied = nullptr,
+                              unsigned long long step = 0)
     {
         const int L = (int)net.L.size();
         for (int l = lo; l >= 1; --l) {
@@ -164,6 +167,7 @@ struct DenseAgent : bdr_agent {
         for (int z = 0; z < nz; ++z) { ra.p[z] = p[z]; ra.g[z] = g[z]; ra.m[z] = m[z]; ra.v[z] = v[z]; ra.tgt[z] = tgt ? tgt[z] : nullptr; ra.s[z] = sc[z]; ra.vmax[z] = nullptr; }
         // without targets (track == 0) k_dense_reduce_adam reads neither tau nor omt: an agent that has none passes any tau
         ra.n4 = (unsigned)(total / 4); ra.track = tgt ? 1 : 0; ra.tau = (float)tau; ra.omt = (float)(1.0 - tau);
+        ra.poison = poison; ra.applied = applied; ra.step = step;
         Bracket br(this, names.adam);
         BDR_HIP(step_launch(stream, true, k_dense_reduce_adam, dim3((ra.n4 + 255) / 256, nz), dim3(256), ra));
         return BDR_OK;

@@ -1094,7 +1094,74 @@ BDR_API int32_t bdr_bc_sample(bdr_agent* a, uint64_t n, const float* obs, float*
 /* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
 BDR_API int32_t bdr_bc_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out);
 
-/* ---- acting of the dense-agent agents (IQL, AWAC, BC) ----------------------------------------------------------------------
+/* ------------------------------------------------------------------------------------------
+ * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)
+ * Not the bdr_dqn_* agent above, which restates border-tch-agent/src/dqn.  Q-network = Mlp (mlp/base.rs, mlp.rs:14-24): ReLU after
+ * every layer but the last, activation_out after the last; variables mlp.ln{i}.weight [out][in] / .bias.  The AtariCnn Q-network of
+ * the candle crate is not built here.
+ * ---------------------------------------------------------------------------------------- */
+/* DqnConfig (dqn/config.rs:25-47; defaults :75-102) with DqnModelConfig (dqn/model.rs:20-39: q_config, opt_config) plus obs_dim,
+ * n_actions and record_verbose_level's integer.  clip_reward and clip_td_err are carried and unused: nothing in dqn/base.rs reads
+ * them (`_clip_reward`, :40; clip_td_err only inside the commented-out prioritized loss, :138-152), and is_truncated is dropped when
+ * the batch is unpacked (:62).  amsgrad is rejected, as for IQL.  explorer: DqnExplorer (dqn/explorer.rs), default Softmax; its seed
+ * is the seed of the agent's SmallRng, 42 in the reference (dqn/base.rs:274) and by default here. */
+typedef struct {
+    int32_t obs_dim, n_actions;
+    bdr_mlp_config qnet;            /* DqnModelConfig.q_config (MlpConfig); activation_out None / ReLU */
+    bdr_adamw_config opt;           /* DqnModelConfig.opt_config */
+    double lr;
+    uint64_t soft_update_interval;  /* 1 */
+    uint64_t n_updates_per_opt;     /* 1 */
+    uint64_t batch_size;            /* 1 */
+    double discount_factor;         /* 0.99, used as f32 (dqn/base.rs:113) */
+    double tau;                     /* 0.005 */
+    int32_t train;                  /* false */
+    int32_t double_dqn;             /* false */
+    bdr_explorer_config explorer;   /* Softmax; seed 42 */
+    int32_t has_clip_reward;        /* clip_reward: None - carried, unused */
+    int32_t has_clip_td_err;        /* clip_td_err: None - carried, unused */
+    double clip_reward;
+    double clip_td_err_min, clip_td_err_max;
+    int32_t critic_loss;            /* BDR_LOSS_* (Mse) */
+    int32_t record_verbose_level;   /* 0 */
+    int32_t device;                 /* -1: none given ("No device is given for DQN agent", dqn/base.rs:245-248) */
+    int32_t ckpt_format;            /* BDR_CKPT_TCH: qnet.pt / qnet_tgt.pt (safetensors, as candle writes them); BDR_CKPT_SAFETENSORS: *.safetensors */
+    uint64_t seed;                  /* the library's parameter initialiser */
+} bdr_candle_dqn_config;
+BDR_API void bdr_candle_dqn_config_default(bdr_candle_dqn_config* cfg);                    /* dqn/config.rs:75-102 */
+BDR_API int32_t bdr_candle_dqn_create(const bdr_candle_dqn_config* cfg, bdr_agent** out);  /* dqn/base.rs:244-276 (Configurable::build): track(tau = 1) once */
+/* One Dqn::update_critic (dqn/base.rs:59-170) on a host minibatch, then the bookkeeping of opt_ (:180-186: the soft update when the
+ * counter of OPTS reaches soft_update_interval, n_opts += 1).  pred = Q(obs)[act]; q = Q_tgt(next_obs)[argmax Q(next_obs)] (double_dqn,
+ * the ONLINE net's first maximum) or max_j Q_tgt(next_obs)[j]; tgt = reward + (((1 - is_terminated) * (f32)gamma) * q); loss = mse or
+ * smooth_l1 (util.rs:144-152).  act: int64 [n], one action index per row; an index outside [0, n_actions) touches nothing out of
+ * bounds and is reported by this call, by bdr_agent_sync and by the poll of bdr_agent_opt; the flagged update and every update enqueued
+ * until the report take no optimizer step and no soft update, and n_opts, the Adam step number and the soft-update counter go back
+ * to what was applied (an opt counts when all its updates were applied).  is_truncated may be NULL: it is read by nothing (:62).
+ * rec (may be NULL): loss and, with record_verbose_level >= 2, pred_mean, reward_mean, tgt_mean, tgt_minus_pred_mean (:88-133).
+ * Parameter models for bdr_agent_{get,set}_params / param_count_of: 0 qnet, 1 qnet_tgt, 2 exp_avg, 3 exp_avg_sq, 4 the last gradient
+ * (also +100 gradient, +200 exp_avg, +300 exp_avg_sq of model 0, as for the other dense agents).  SyncModel is unimplemented!() in the
+ * reference (:380-392); the generic arena path ships model 0.  Checkpoints (:337-351): qnet.pt, qnet_tgt.pt.
+ * bdr_agent_opt on a prioritized ring returns BDR_ERR_INVALID: the reference panics on a weighted batch (dqn/base.rs:135-137).
+ * Record of bdr_agent_opt_with_scalars (:307-331): the keys above of the LAST update of the opt (Record::merge), with
+ * record_verbose_level >= 2 `<var>_mean` / `<var>_std` of every qnet variable, then ratio_best_act, which resets both counters. */
+BDR_API int32_t bdr_candle_dqn_update_on_batch(bdr_agent* a, uint64_t n, const float* obs, const int64_t* act, const float* next_obs,
+                                               const float* reward, const int8_t* is_terminated, const int8_t* is_truncated,
+                                               bdr_dqn_record* rec);
+/* Parity probes: intermediates of the LAST update, to the host, each [B] floats.  what:
+ *   0 pred   Q(obs)[act] (:80-86)                    1 q_next  the gathered target value (:101-111)
+ *   2 y      the argmax index as a float (:103, :108)  3 tgt   the TD target (:113)
+ *   4 dpred  dLoss / dpred, 1/B included (the gradient of the output itself: an output ReLU's mask is applied behind it) */
+BDR_API int32_t bdr_candle_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* Policy::sample (dqn/base.rs:202-230) goes through bdr_agent_sample / _sample_device / _sample_raw (idx_out) and the action values
+ * through bdr_agent_qvalues / _qvalues_device.  The exploration stream of this kind is the reference's SmallRng (xoshiro256++ seeded
+ * by rand_core's seed_from_u64; DESIGN.md 17 states the rules, which nothing here can pin against rand itself):
+ *   train, Softmax (explorer.rs:31-40):        per row WeightedIndex<f32> over softmax(q_row); a NaN row returns BDR_ERR_INVALID
+ *   train, EpsilonGreedy (explorer.rs:79-133): eps in f64, r = gen::<f32>(), random iff r < (f32)eps, n_calls += 1; random: per row
+ *                                              gen::<u64>() % A; n_samples_best_act counts only with record_verbose_level >= 2
+ *   eval (dqn/base.rs:221-227):                gen::<f32>() < 0.01 ? ONE gen_range(0..A), written to every row : argmax per row
+ * bdr_agent_set_explorer rewinds the stream to its seed. */
+
+/* ---- acting of the dense-agent agents (IQL, AWAC, the candle SAC, BC, the candle DQN) ----------------------------------------------------------------------
  * Their Policy::sample has two forms that produce the same bits: the layer-by-layer path (pack, one launch per layer, the sample
  * kernel) and k_dense_act (csrc/dense_act.hpp), one launch from the raw rows to the action.  bdr_{iql,awac,bc}_sample[_device] and
  * bdr_agent_sample_raw obey the setting.  FUSED on an agent kind or a network it does not cover (a padded layer wider than 512)
@@ -1106,7 +1173,8 @@ BDR_API int32_t bdr_agent_set_act_path(bdr_agent* a, int32_t path);
 /* Policy::sample on n raw environment rows of `dtype` (BDR_DTYPE_F32 / _F64): host rows, contiguous, or (on_device != 0) device rows
  * row_stride bytes apart.  float64 is rounded to f32; with a normaliser (finished or set, dim = the agent's obs dim, on the agent's
  * device) the value that enters the first layer has the bits of bdr_obs_norm_apply.  act_out [n][act_dim]; idx_out [n] for a
- * Discrete BC agent (then act_out may be NULL), else NULL.  IQL, AWAC and BC; other agent kinds return BDR_ERR_INVALID. */
+ * Discrete BC agent and for the candle DQN (the explored i64 actions; then act_out may be NULL), else NULL.  IQL, AWAC, the candle
+ * SAC, BC and the candle DQN; other agent kinds return BDR_ERR_INVALID. */
 BDR_API int32_t bdr_agent_sample_raw(bdr_agent* a, const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype,
                                      int32_t on_device, uint64_t row_stride, float* act_out, int64_t* idx_out);
 

@@ -1506,3 +1506,170 @@ impl BcConfig {
         Ok(c)
     }
 }
+
+// ---------------------------------------------------------------------------------------------- DQN of border-candle-agent
+/// `dqn::DqnModelConfig<MlpConfig>` of border-candle-agent (`dqn/model.rs:20-39`): the Q-network's Mlp and its optimizer (default:
+/// `OptimizerConfig::default()`, AdamW with candle's `ParamsAdamW` defaults).
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct CandleDqnModelConfig {
+    pub q_config: Option<CandleMlpConfig>,
+    #[serde(default = "bc_opt_default")]
+    pub opt_config: CandleOptimizerConfig,
+}
+
+impl Default for CandleDqnModelConfig {
+    fn default() -> Self {
+        Self { q_config: None, opt_config: bc_opt_default() }
+    }
+}
+
+impl CandleDqnModelConfig {
+    pub fn q_config(mut self, v: CandleMlpConfig) -> Self {
+        self.q_config = Some(v);
+        self
+    }
+
+    pub fn opt_config(mut self, v: CandleOptimizerConfig) -> Self {
+        self.opt_config = v;
+        self
+    }
+
+    /// `DqnModelConfig::out_dim` (`dqn/model.rs`): the number of actions.
+    pub fn out_dim(mut self, v: i64) -> Self {
+        if let Some(c) = &mut self.q_config {
+            c.out_dim = v;
+        }
+        self
+    }
+}
+
+fn candle_dqn_rng_seed() -> u64 {
+    42 // dqn/base.rs:274: SmallRng::seed_from_u64(42)
+}
+
+/// `dqn::DqnConfig<Mlp>` of border-candle-agent (`dqn/config.rs:25-102`) with the reference's field names; `phantom` is accepted and
+/// ignored.  `clip_reward` and `clip_td_err` are carried and read by nothing, as in the reference (`dqn/base.rs:40`, `:138-152`).
+/// `rng_seed`, `engine_seed` and `safetensors_ext` are not reference fields: the seed of the exploration stream (the reference's
+/// fixed 42), the library's parameter initialiser, and `*.safetensors` instead of `*.pt` file names.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct CandleDqnConfig {
+    pub model_config: CandleDqnModelConfig,
+    pub soft_update_interval: usize,
+    pub n_updates_per_opt: usize,
+    pub batch_size: usize,
+    pub discount_factor: f64,
+    pub tau: f64,
+    pub train: bool,
+    pub explorer: DqnExplorer,
+    #[serde(default)]
+    pub clip_reward: Option<f64>,
+    #[serde(default)]
+    pub double_dqn: bool,
+    pub clip_td_err: Option<(f64, f64)>,
+    pub device: Option<Device>,
+    pub critic_loss: CriticLoss,
+    pub record_verbose_level: usize,
+    #[serde(default, skip_serializing)]
+    pub phantom: Option<()>,
+    #[serde(default = "candle_dqn_rng_seed")]
+    pub rng_seed: u64,
+    #[serde(default)]
+    pub engine_seed: u64,
+    #[serde(default)]
+    pub safetensors_ext: bool,
+}
+
+impl Default for CandleDqnConfig {
+    /// `dqn/config.rs:75-102`
+    fn default() -> Self {
+        Self {
+            model_config: Default::default(),
+            soft_update_interval: 1,
+            n_updates_per_opt: 1,
+            batch_size: 1,
+            discount_factor: 0.99,
+            tau: 0.005,
+            train: false,
+            explorer: DqnExplorer::Softmax(Softmax::new()),
+            clip_reward: None,
+            double_dqn: false,
+            clip_td_err: None,
+            device: None,
+            critic_loss: CriticLoss::Mse,
+            record_verbose_level: 0,
+            phantom: None,
+            rng_seed: candle_dqn_rng_seed(),
+            engine_seed: 0,
+            safetensors_ext: false,
+        }
+    }
+}
+
+impl CandleDqnConfig {
+    setter!(soft_update_interval, usize);
+    setter!(n_updates_per_opt, usize);
+    setter!(batch_size, usize);
+    setter!(discount_factor, f64);
+    setter!(tau, f64);
+    setter!(explorer, DqnExplorer);
+    setter!(model_config, CandleDqnModelConfig);
+    setter!(double_dqn, bool);
+    setter!(critic_loss, CriticLoss);
+    setter!(record_verbose_level, usize);
+    yaml_io!();
+
+    /// `DqnConfig::out_dim` (`dqn/config.rs`): the number of actions.
+    pub fn out_dim(mut self, v: i64) -> Self {
+        self.model_config = self.model_config.out_dim(v);
+        self
+    }
+
+    pub fn clip_reward(mut self, v: Option<f64>) -> Self {
+        self.clip_reward = v;
+        self
+    }
+
+    pub fn clip_td_err(mut self, v: Option<(f64, f64)>) -> Self {
+        self.clip_td_err = v;
+        self
+    }
+
+    pub fn device(mut self, device: Device) -> Self {
+        self.device = Some(device);
+        self
+    }
+
+    pub(crate) fn to_c(&self) -> Result<ffi::bdr_candle_dqn_config> {
+        let mut c: ffi::bdr_candle_dqn_config = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_dqn_config_default(&mut c) };
+        let q = self.model_config.q_config.as_ref().ok_or_else(|| anyhow!("q_config is not set."))?;
+        c.obs_dim = q.in_dim as i32;
+        c.n_actions = q.out_dim as i32;
+        q.fill(&mut c.qnet, "q_config")?;
+        c.lr = self.model_config.opt_config.lr();
+        self.model_config.opt_config.fill(&mut c.opt);
+        c.soft_update_interval = self.soft_update_interval as u64;
+        c.n_updates_per_opt = self.n_updates_per_opt as u64;
+        c.batch_size = self.batch_size as u64;
+        c.discount_factor = self.discount_factor;
+        c.tau = self.tau;
+        c.train = self.train as i32;
+        c.double_dqn = self.double_dqn as i32;
+        c.explorer = self.explorer.to_c(self.rng_seed);
+        if let Some(v) = self.clip_reward {
+            c.has_clip_reward = 1;
+            c.clip_reward = v;
+        }
+        if let Some((lo, hi)) = self.clip_td_err {
+            c.has_clip_td_err = 1;
+            c.clip_td_err_min = lo;
+            c.clip_td_err_max = hi;
+        }
+        c.critic_loss = self.critic_loss.code();
+        c.record_verbose_level = self.record_verbose_level as i32;
+        c.ckpt_format = if self.safetensors_ext { ffi::BDR_CKPT_SAFETENSORS } else { ffi::BDR_CKPT_TCH };
+        c.seed = self.engine_seed;
+        c.device = Device::ordinal(&self.device, "DQN");
+        Ok(c)
+    }
+}

@@ -8,10 +8,11 @@
 //! * [`TrainerPost`] - `Trainer::post_process` (`trainer.rs:231-264`) for `bdr_trainer_train_post` /
 //!   `bdr_trainer_train_offline_post`: evaluate every `eval_interval` opt steps between `eval()` and `train()`, keep the best
 //!   model under `model_dir/best`, save every `save_interval` opt steps under `model_dir/<opt_steps>`; 0 means never.
-//! * [`SampleRaw`] - `sample_raw` / `set_act_path` on [`AmdIql`], [`AmdAwac`], [`AmdCandleSac`] and [`AmdBc`].
+//! * [`SampleRaw`] - `sample_raw` / `set_act_path` on [`AmdIql`], [`AmdAwac`], [`AmdCandleSac`], [`AmdBc`] and [`AmdCandleDqn`].
 use crate::{
     awac::AmdAwac,
     bc::AmdBc,
+    candle_dqn::AmdCandleDqn,
     bytes::{ActFromRows, ObsRows, RowBatch},
     candle_sac::AmdCandleSac,
     dataset::{AmdObsNorm, ObsElem},
@@ -68,7 +69,7 @@ pub trait SampleRaw {
         Ok(act)
     }
 
-    /// The same for a Discrete BC agent: `[n]` argmax indices.
+    /// The same for a Discrete BC agent (`[n]` argmax indices) and the candle DQN (`[n]` explored actions).
     fn sample_raw_index<X: ObsElem>(&mut self, norm: Option<&AmdObsNorm>, n: usize, rows: &[X]) -> Result<Vec<i64>> {
         let mut idx = vec![0i64; n];
         let np = norm.map_or(std::ptr::null(), |m| m.handle() as *const ffi::bdr_obs_norm);
@@ -100,6 +101,7 @@ impl_sample_raw!(AmdIql);
 impl_sample_raw!(AmdAwac);
 impl_sample_raw!(AmdCandleSac);
 impl_sample_raw!(AmdBc);
+impl_sample_raw!(AmdCandleDqn);   // one i64 index per row: sample_raw_index
 
 /// What one evaluation returns (`bdr_eval_result`).
 #[derive(Clone, Copy, Debug)]

@@ -653,6 +653,35 @@ pub struct bdr_bc_config {
     pub seed: u64,
 }
 
+/// DqnConfig of border-candle-agent (dqn/config.rs:75-102) + DqnModelConfig (dqn/model.rs) + the explorer and its SmallRng seed
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bdr_candle_dqn_config {
+    pub obs_dim: i32,
+    pub n_actions: i32,
+    pub qnet: bdr_mlp_config,
+    pub opt: bdr_adamw_config,
+    pub lr: f64,
+    pub soft_update_interval: u64,
+    pub n_updates_per_opt: u64,
+    pub batch_size: u64,
+    pub discount_factor: f64,
+    pub tau: f64,
+    pub train: i32,
+    pub double_dqn: i32,
+    pub explorer: bdr_explorer_config,
+    pub has_clip_reward: i32,
+    pub has_clip_td_err: i32,
+    pub clip_reward: f64,
+    pub clip_td_err_min: f64,
+    pub clip_td_err_max: f64,
+    pub critic_loss: i32,
+    pub record_verbose_level: i32,
+    pub device: i32,
+    pub ckpt_format: i32,
+    pub seed: u64,
+}
+
 #[link(name = "border_amd")]
 extern "C" {
     pub fn bdr_last_error() -> *const c_char;
@@ -1006,6 +1035,22 @@ extern "C" {
     pub fn bdr_candle_sac_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_candle_sac_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
     pub fn bdr_candle_sac_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
+
+    // ---- DQN of border-candle-agent (border-candle-agent/src/dqn), Mlp Q-network
+    pub fn bdr_candle_dqn_config_default(cfg: *mut bdr_candle_dqn_config);
+    pub fn bdr_candle_dqn_create(cfg: *const bdr_candle_dqn_config, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_candle_dqn_update_on_batch(
+        a: *mut bdr_agent,
+        n: u64,
+        obs: *const f32,
+        act: *const i64,
+        next_obs: *const f32,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+        rec: *mut bdr_dqn_record,
+    ) -> i32;
+    pub fn bdr_candle_dqn_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
 
     // ---- BC (border-candle-agent/src/bc)
     pub fn bdr_bc_config_default(cfg: *mut bdr_bc_config);

@@ -14,6 +14,8 @@
 //! * [`AmdAwac`] - `border-candle-agent/src/awac/base.rs` (offline and online RL; [`AwacConfig`] likewise).
 //! * [`AmdCandleSac`] - `border-candle-agent/src/sac/base.rs` (the candle SAC with its `Mlp2` Gaussian actor; [`CandleSacConfig`]
 //!   likewise).
+//! * [`AmdCandleDqn`] - `border-candle-agent/src/dqn/base.rs` (the candle DQN with an `Mlp` Q-network and the reference's
+//!   `SmallRng` exploration stream; [`CandleDqnConfig`] likewise).
 //! * [`AmdBc`] - `border-candle-agent/src/bc/base.rs` (behaviour cloning; [`BcConfig`] likewise).
 //! * [`AmdObsNorm`], [`AmdReplayBuffer::push_episode`] - `border-minari`'s `PenConverter` statistics / normalisation and
 //!   `MinariDataset::create_replay_buffer`'s episode push, on the device.
@@ -29,6 +31,7 @@ pub mod async_trainer;
 pub mod awac;
 pub mod bc;
 pub mod bytes;
+pub mod candle_dqn;
 pub mod candle_sac;
 pub mod comm;
 pub mod config;
@@ -49,10 +52,11 @@ pub use comm::Comm;
 pub use config::{
     ActionLimit, Activation, CandleMlpConfig, CandleOptimizerConfig, GaussianActorConfig, MultiCriticConfig, ValueConfig,
     ActorConfig, AtariCnnConfig, CriticConfig, CriticLoss, Device, DqnConfig, DqnExplorer, DqnModelConfig, EntCoefMode, EpsilonGreedy,
-    ActorKind, Arithmetic, AwacConfig, CandleSacConfig, BcActionType, BcConfig, BcKernelForm, BcModelConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
+    ActorKind, Arithmetic, AwacConfig, CandleDqnConfig, CandleDqnModelConfig, CandleSacConfig, BcActionType, BcConfig, BcKernelForm, BcModelConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
 };
 pub use awac::AmdAwac;
 pub use bc::AmdBc;
+pub use candle_dqn::AmdCandleDqn;
 pub use candle_sac::AmdCandleSac;
 pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;

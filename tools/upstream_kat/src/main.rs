@@ -9,10 +9,18 @@
 //!  3. `image::imageops::resize(.., 84, 84, Triangle)` + the luma expression of `BorderAtariEnv::warp_and_grayscale`
 //!     (`border-atari-env/src/env.rs:171-195`) on a 210x160 frame both sides generate from the same integer formula.
 //!
+//!  4. `SmallRng::seed_from_u64(42)`, the exploration stream of border-candle-agent's `Dqn` (`dqn/base.rs:274`, `dqn/explorer.rs`):
+//!     its first `next_u64` words, `gen::<f32>()`, `gen_range(0..6i64)` and `WeightedIndex<f32>` draws - the vectors that pin the
+//!     SmallRng contract of `csrc/candle_dqn.hip` / `tests/candle_dqn_restatement.py`, each from a fresh generator.
+//!
 //! Usage:  cargo run --release [-- <out dir>]      (default ./out)
 //! Then:   python tests/golden/ingest_upstream.py <out dir> [--accept]     in the border_amd repository.
 use image::{imageops::resize, imageops::FilterType::Triangle, ImageBuffer, Rgb};
-use rand::{rngs::StdRng, RngCore, SeedableRng};
+use rand::{
+    distributions::WeightedIndex,
+    rngs::{SmallRng, StdRng},
+    Rng, RngCore, SeedableRng,
+};
 use std::{fmt::Write as _, fs, path::PathBuf};
 use tch::{nn, Device, Kind, Tensor};
 
@@ -98,6 +106,32 @@ fn main() -> Result<(), Box<dyn std::error::Error>> {
         )?;
     }
     writeln!(j, "  ],")?;
+
+    // ---- 1b. SmallRng (rand 0.8.5 with `small_rng`: xoshiro256++ on 64-bit targets), each vector from a fresh seed_from_u64(42) ------
+    {
+        let weights: [f32; 5] = [0.125, 0.25, 0.0625, 0.5, 0.0625];
+        let mut r = SmallRng::seed_from_u64(42);
+        let u64s: Vec<u64> = (0..8).map(|_| r.next_u64()).collect();
+        let mut r = SmallRng::seed_from_u64(42);
+        let f32_bits: Vec<u32> = (0..4).map(|_| r.gen::<f32>().to_bits()).collect();
+        let mut r = SmallRng::seed_from_u64(42);
+        let ranges: Vec<i64> = (0..4).map(|_| r.gen_range(0..6i64)).collect();
+        let mut r = SmallRng::seed_from_u64(42);
+        let dist = WeightedIndex::new(&weights)?;
+        let picks: Vec<usize> = (0..4).map(|_| r.sample(&dist)).collect();
+        let mut r = SmallRng::seed_from_u64(42);
+        let mods: Vec<u64> = (0..4).map(|_| r.gen::<u64>() % 6).collect();
+        writeln!(
+            j,
+            "  \"small_rng\": {{\"seed\": 42, \"next_u64\": {}, \"gen_f32_bits\": {}, \"gen_range_0_6_i64\": {}, \"weights_f32\": {}, \"weighted_index\": {}, \"gen_u64_mod_6\": {}}},",
+            json_list(&u64s),
+            json_list(&f32_bits),
+            json_list(&ranges),
+            json_list(&weights.to_vec()),
+            json_list(&picks),
+            json_list(&mods)
+        )?;
+    }
 
     // ---- 2. VarStore files ---------------------------------------------------------------------------------------------------
     // three variables with the reference's naming scheme (sub-path / name -> "c1.weight"), values = index * 0.25 - 3 (exact in f32)
