@@ -35,6 +35,8 @@ struct Conv1DwArgs {
     float* part;          // [gridDim.x][part_stride]
     size_t part_stride;   // floats (64*n_stack*32 + 32)
     int B;
+    unsigned* sig_flag;   // optional: the launch's first workgroup publishes "everything queued before me on my stream is complete" (igemm.hpp start_signal)
+    unsigned sig_epoch;
 };
 
 constexpr int C1DW_LDM = 408;   // bf16 per plane row (400 + 8)
@@ -117,6 +119,7 @@ __device__ __forceinline__ void c1dw_steps(const uint8_t* const (&src)[TPW], U32
 template <int NS>
 static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NS <= 4 ? C1DW_WAVES_PER_EU : 2, NS <= 4 ? C1DW_WAVES_PER_EU : 2))) void k_conv1_dw_bf16(Conv1DwArgs a)
 {
+    start_signal(a.sig_flag, a.sig_epoch);
     C1DW_TP(0);
     constexpr int TASKS = 4 * ((NS + 1) / 2), TPW = (TASKS + 7) / 8;
     // LDS, dynamic (c1dw_lds_bytes): with a static size hipcc sees that only one workgroup fits a CU and spends the whole register file on

@@ -25,6 +25,7 @@
 #include "cnn_layers.hpp"
 #include "igemm_b3.hpp"
 #include "act_small.hpp"
+#include "dqn_rollback.hpp"
 
 using namespace bdr;
 
@@ -57,6 +58,12 @@ namespace {
 #endif
 #ifndef BDR_TEAMS_DX_C2
 #define BDR_TEAMS_DX_C2 1
+#endif
+// Schedule 3: the weight-gradient tail of an update (conv2 dW, the conv2 / conv3 optimizer pass) on the weight-gradient queue, beside conv1 dW,
+// conv1's optimizer pass and the NEXT update's gather gate and conv1 forward on the dX queue (update_critic).  0: the
+// round-6 order - conv2 dW and conv1 dW in sequence on the dX queue, then the join and one optimizer pass over the three conv layers.
+#ifndef BDR_TAIL_OVERLAP
+#define BDR_TAIL_OVERLAP 1
 #endif
 #ifndef BDR_DXC2_MERGED
 #define BDR_DXC2_MERGED 2   // conv2 input gradient: 2 = the four parity classes as one GEMM over position-class tiles (DxC2MPos, valid taps only); 1 = the same GEMM over flat row tiles (DxC2M); 0 = one launch slice per class (DxC2)
@@ -388,7 +395,7 @@ struct DqnCnn : bdr_agent {
     hipStream_t aux = nullptr;           // prioritized-replay tree updates
     hipEvent_t ev_fork[4] = {nullptr}, ev_join = nullptr;
     bool kev = true;
-    unsigned* sig = nullptr;   // [8] device progress flags of schedule 3
+    unsigned* sig = nullptr;   // [16] device progress flags of schedule 3
     unsigned sig_epoch = 0;
     unsigned test_epoch = 0;
     bool aux_gated = true;     // the PER queue may wait through gates (queues_independent at its creation)
@@ -428,7 +435,15 @@ struct DqnCnn : bdr_agent {
     const float* last_reward = nullptr; int last_B = 0;
     // bookkeeping (dqn/base.rs:26-48)
     uint64_t adam_step = 0, soft_update_counter = 0;
-    int64_t conv_step_lag = 0;   // the conv segment's optimizer step number is adam_step - conv_step_lag: 0 unless a gate time-out fell between the step's two optimizer passes (on_gate_timeout)
+    int64_t conv_lag[2] = {0, 0};   // optimizer step number of conv1 ([0]) and of conv2 + conv3 ([1]): adam_step - conv_lag[k]; 0 unless a gate time-out fell between the step's optimizer passes (on_gate_timeout, dqn_rollback.hpp)
+    // Overlapped tail (BDR_TAIL_OVERLAP): the last update left conv2 dW and the conv2 / conv3 optimizer pass running on the weight-gradient
+    // queue.  "The agent's stream has drained" then does not mean "the parameters are final": whatever touches q, grad, m, v or the planes on
+    // the agent's stream first waits for that queue's CONV23 flag (join_conv23) - the next forward between conv1 and conv2, everything else
+    // before its first kernel.
+    bool conv23_join_pending = false;
+    unsigned conv23_epoch = 0;
+    float* a1_alt = nullptr;        // second buffer of a1[0]: the next update's conv1 forward runs while conv2 dW still reads this update's a1[0]
+    int32_t join_conv23();
     // conv2 / conv3 on the bf16 matrix cores with split f32 operands (igemm_b3.hpp): bf16 planes of W2 / W3 beside each parameter set
     // ([0] online, [1] target).  k_reduce_adam writes the online set's planes with the parameters; every other writer of conv
     // parameters marks the set stale (planes_stale) and the next forward re-splits it on its own queue, behind whatever orders
@@ -441,7 +456,7 @@ struct DqnCnn : bdr_agent {
     void arena_escaped(int which) override { if (which == 0 || which == 1) cpl_escaped[which] = true; }
     void arena_released(int which) override { if (which == 0 || which == 1) { cpl_escaped[which] = false; cpl_fresh[which] = false; } }
     float* act_part = nullptr; unsigned* act_tickets = nullptr;   // scratch of the acting kernels (act_small.hpp)
-    unsigned long long* applied_step = nullptr;   // device words: the Adam step number of the last pass that was not skipped - [0] l1 / l2 (k_adam, or the whole arena), [1] the conv segment (k_reduce_adam)
+    unsigned long long* applied_step = nullptr;   // device words: the Adam step number of the last pass that was not skipped - [0] l1 / l2 (k_adam, or the whole arena), [1] conv1, [2] conv2 + conv3 (k_reduce_adam)
 
     ~DqnCnn() override;
     const char* kind() const override { return "dqn_cnn"; }
@@ -456,7 +471,8 @@ struct DqnCnn : bdr_agent {
     }
     int32_t after_sync() override
     {
-        if (!(xchg_pending_conv || xchg_pending_fc)) return BDR_OK;
+        if (!(xchg_pending_conv || xchg_pending_fc || conv23_join_pending)) return BDR_OK;
+        BDR_TRY(join_conv23());
         BDR_TRY(join_exchange(true, true));
         BDR_HIP(hipStreamSynchronize(stream));
         return BDR_OK;
@@ -489,13 +505,14 @@ void free_batch_buffers(DqnCnn* a)
     }
     (void)hipFree(a->dh1); (void)hipFree(a->dy3); (void)hipFree(a->dy2); (void)hipFree(a->dy1);
     (void)hipFree(a->dq); (void)hipFree(a->pred); (void)hipFree(a->tgt); (void)hipFree(a->loss_row);
-    (void)hipFree(a->part);
-    a->dh1 = a->dy3 = a->dy2 = a->dy1 = a->dq = a->pred = a->tgt = a->loss_row = a->part = nullptr;
+    (void)hipFree(a->part); (void)hipFree(a->a1_alt);
+    a->dh1 = a->dy3 = a->dy2 = a->dy1 = a->dq = a->pred = a->tgt = a->loss_row = a->part = a->a1_alt = nullptr;
 }
 
 int32_t ensure_batch(DqnCnn* a, int B)
 {
     if (B <= a->B) return BDR_OK;
+    BDR_TRY(a->join_conv23());   // (conv2 dW on the other queue reads a1[0] and dy2)
     BDR_HIP(hipStreamSynchronize(a->stream));
     free_batch_buffers(a);
     const int A = a->ar.A;
@@ -507,6 +524,7 @@ int32_t ensure_batch(DqnCnn* a, int B)
         BDR_TRY(alloc_f(&a->h1[z], (size_t)B * 512));
         BDR_TRY(alloc_f(&a->qv[z], (size_t)B * A));
     }
+    BDR_TRY(alloc_f(&a->a1_alt, (size_t)B * 400 * 32));
     BDR_TRY(alloc_f(&a->dh1, (size_t)B * 512));
     BDR_TRY(alloc_f(&a->dy3, (size_t)B * 49 * 64));
     BDR_TRY(alloc_f(&a->dy2, (size_t)B * 81 * 64));
@@ -534,7 +552,9 @@ struct ConvReduceAdamArgs {
     int reduce_blocks;
     const unsigned* poison;  // sig + SIG_ERR: a gate timed out, leave the parameters alone
     int reduce_only;         // gradients only (the optimizer step follows an all-reduce: synchronous data-parallel mode)
-    unsigned long long* applied; unsigned long long step;   // *applied = step by a launch that was not skipped (on_gate_timeout rolls the conv segment's step number back to it)
+    unsigned long long* applied; unsigned long long step;   // *applied = step by a launch that was not skipped (on_gate_timeout rolls the segment's step number back to it)
+    unsigned long long* applied2;   // a launch over all three segments stands for both conv words (null otherwise)
+    int wg_base;             // the launch covers a sub-range of the segments: its block 0 is block seg[first].wg0 of the whole walk
     uint16_t* cpl;           // the parameter set's bf16 planes of W2 / W3 (segments 1, 2), written with the parameters; null: none
 };
 // Schedule 3 cross-queue ordering without barrier packets (igemm.hpp start_signal).
@@ -542,6 +562,10 @@ struct ConvReduceAdamArgs {
 // it cannot starve the producer; a producer that never arrives trips the time limit instead of hanging the queue
 // (sig[SIG_ERR] is checked at the next synchronisation).
 constexpr int SIG_HEAD = 0, SIG_DXL1 = 1, SIG_DXC3 = 2, SIG_SIDE = 3, SIG_GATHER = 4, SIG_TEST = 5, SIG_TEST_ERR = 6, SIG_ERR = 7, SIG_TGT = 8, SIG_TRACK = 9, SIG_MAIN_END = 10, SIG_XCONV = 11, SIG_XFC = 14;   // (12, 13: trace timestamp)
+// Overlapped tail: DXC2 = "conv2 dX complete" (published by conv1 dW's first workgroup); CONV23 = "the weight-gradient queue has finished the
+// update" (behind the conv2 / conv3 optimizer pass).  CONV23 is SIDE's word: the l1 / l2 pass is earlier on the same queue, so the later
+// signal stands for both, and the join keeps its trace site.
+constexpr int SIG_DXC2 = 15, SIG_CONV23 = SIG_SIDE;
 // A gate that times out POISONS the agent: sig[SIG_ERR] (and dev_err[ERR_GATE], the word the host polls) is set, every later
 // gate returns at once instead of waiting another 10 s, and the kernels that write parameters (k_reduce_adam, the l1 / l2
 // k_adam) skip their update while the flag is up - kernels behind a failed gate run unordered, so their gradients may be
@@ -588,7 +612,7 @@ __global__ void k_copy_word_unless(unsigned long long* dst, const unsigned long 
 __global__ __launch_bounds__(256) void k_reduce_adam(ConvReduceAdamArgs a)
 {
     const bool poisoned = a.reduce_only || (a.poison && *a.poison != 0);
-    if (a.applied && !poisoned && blockIdx.x == 0 && threadIdx.x == 0) *a.applied = a.step;
+    if (a.applied && !poisoned && blockIdx.x == 0 && threadIdx.x == 0) { *a.applied = a.step; if (a.applied2) *a.applied2 = a.step; }
     if ((int)blockIdx.x >= a.reduce_blocks) {
         if (poisoned) return;
         const size_t i = a.rest0_4 + (size_t)(blockIdx.x - a.reduce_blocks) * 256 + threadIdx.x;
@@ -607,10 +631,11 @@ __global__ __launch_bounds__(256) void k_reduce_adam(ConvReduceAdamArgs a)
         return;
     }
     __shared__ float red[8][32];
-    const int s_id = (int)blockIdx.x >= a.r.seg[2].wg0 ? 2 : ((int)blockIdx.x >= a.r.seg[1].wg0 ? 1 : 0);
+    const int bx = (int)blockIdx.x + a.wg_base;   // block index in the walk over all three segments
+    const int s_id = bx >= a.r.seg[2].wg0 ? 2 : (bx >= a.r.seg[1].wg0 ? 1 : 0);
     const ReduceSeg& sg = a.r.seg[s_id];
     const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = ((int)blockIdx.x - sg.wg0) * 32 + o;
+    const int i = (bx - sg.wg0) * 32 + o;
     float s = 0.f;
     if (i < sg.n) {
         int c = grp;
@@ -662,6 +687,8 @@ int32_t forward(DqnCnn* a, const NetInst* inst, int nz, int B, const TdArgs* td 
         Bracket br(a, "fwd_conv1");
         BDR_HIP(conv1_forward(ar.ns, B, st, c));
     }
+    // conv1 reads W1 / b1 only, stepped by this queue's own conv1 pass; W2, W3, their planes and l1 / l2 are final behind CONV23
+    if (uses_q && st == a->stream) BDR_TRY(a->join_conv23());
     f.M = B * 81;
     for (int z = 0; z < nz; ++z) { f.x[z] = a->a1[inst[z].slot]; f.w[z] = inst[z].params + ar.w2; f.bias[z] = inst[z].params + ar.b2; f.out[z] = a->a2[inst[z].slot]; }
     bool b3 = a->conv_b3;
@@ -794,6 +821,9 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
     a->last_reward = reward; a->last_B = B;
     const Arena& ar = a->ar;
     const bdr_dqn_config& c = a->cfg;
+    // the previous update's conv2 dW may still be reading its a1[0] on the other queue when this update's conv1 forward runs (it is
+    // in front of the CONV23 join): this update writes the other buffer
+    if (a->conv23_join_pending) std::swap(a->a1[0], a->a1_alt);
     // :71-74 + :91-103  slot 0 = qnet(obs), slot 1 = qnet_tgt(next_obs), slot 2 = qnet(next_obs) for double DQN
     NetInst inst[3] = {{obs, a->q, 0}, {next_obs, a->q_tgt, 1}, {next_obs, a->q, 2}};
 
@@ -828,7 +858,8 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
     //      may run beside it follow as hipExtAnyOrderLaunch dispatches (no barrier bit; ignored by this runtime on gfx9);
     //   3  two streams ordered through device flags instead of events: the next dX kernel's first workgroup publishes
     //      "my predecessor is complete" (start_signal), one-wave k_gate kernels on the consuming queue wait for it.  No
-    //      packet is added to the dX queue except the join gate before the reduction.
+    //      packet is added to the dX queue except the join gate (before the reduction; with the overlapped tail, BDR_TAIL_OVERLAP,
+    //      in the NEXT forward between conv1 and conv2).
     const int sched = effective_sched(a);
     const bool ov = sched == 1;
     const bool gated = sched == 3;
@@ -848,6 +879,7 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
     };
     const DwPlan pl = dw_plan(a->B, ar.ns);   // buffer layout follows the allocated batch capacity
     const bool defer = a->defer_adam;  // backward only: the optimizer step is apply_grads()
+    const bool tail = gated && BDR_TAIL_OVERLAP != 0 && !defer;   // overlapped tail, see the gated branch below
     if (!defer) a->adam_step += 1;
     const AdamScalars adam_s = adam_scalars(c, std::max<uint64_t>(a->adam_step, 1));
 
@@ -914,9 +946,41 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
     };
     auto c1_dw = [&]() -> int32_t {   // conv1 has no input gradient
         const int chunks = std::min(pl.chunks_c1, B);
-        Conv1DwArgs d{obs, a->dy1, a->part + pl.off_c1, pl.stride_c1, B};
+        Conv1DwArgs d{obs, a->dy1, a->part + pl.off_c1, pl.stride_c1, B, tail ? sigf(SIG_DXC2) : nullptr, epoch};   // tail: its start publishes "conv2 dX done"
         Bracket br(a, "bwd_conv1_dw");
         BDR_HIP(launch_conv1_dw_bf16(ar.ns, dim3(chunks), a->stream, d));
+        return BDR_OK;
+    };
+
+    // conv partials -> gradient arena + the conv layers' Adam step (k_reduce_adam) for the segments [lo, hi) of {conv1, conv2, conv3} on queue st;
+    // l1 / l2: adam_l1_l2 above.  A launch over a sub-range runs the same blocks of the same walk (wg_base), so every element sees the same code.
+    auto reduce_adam = [&](hipStream_t st, int lo, int hi) -> int32_t {
+        Reduce3Args r{};
+        const int Ms[3] = {B * 400, B * 81, B * 49};
+        const int plc[3] = {pl.chunks_c1, pl.chunks_c2, pl.chunks_c3};
+        const size_t offs[3] = {pl.off_c1, pl.off_c2, pl.off_c3}, strides[3] = {pl.stride_c1, pl.stride_c2, pl.stride_c3};
+        const size_t gw[3] = {ar.w1, ar.w2, ar.w3};
+        const int nw[3] = {(int)ar.n_w1(), 512 * 64, 576 * 64}, nb[3] = {32, 64, 64};
+        int wg = 0, wg0[4];
+        for (int k = 0; k < 3; ++k) {
+            const int nchunks = k == 0 ? std::min(plc[0], B) : std::min(plc[k], (Ms[k] + 31) / 32);   // conv1: one partial per workgroup
+            r.seg[k] = ReduceSeg{a->part + offs[k], strides[k], nchunks, a->grad + gw[k], nw[k] + nb[k], nw[k],
+                                 k == 0 ? INV255 : 1.0f, wg};
+            wg0[k] = wg;
+            wg += (nw[k] + nb[k] + 31) / 32;
+        }
+        wg0[3] = wg;
+        const int64_t lag = a->conv_lag[lo == 0 ? 0 : 1];   // (a launch over all three segments: both lags are equal, see below)
+        ConvReduceAdamArgs ra{};
+        ra.r = r; ra.p = a->q; ra.g = a->grad; ra.m = a->m; ra.v = a->v; ra.gbase = a->grad;
+        ra.rest0_4 = ra.n4 = ar.w4 / 4; ra.s = lag ? adam_scalars(c, (uint64_t)std::max<int64_t>((int64_t)a->adam_step - lag, 1)) : adam_s;
+        ra.applied = defer ? nullptr : a->applied_step + (lo == 0 ? 1 : 2); ra.step = (unsigned long long)((int64_t)a->adam_step - lag);
+        ra.applied2 = !defer && lo == 0 && hi == 3 ? a->applied_step + 2 : nullptr;
+        ra.wg_base = wg0[lo]; ra.reduce_blocks = wg0[hi] - wg0[lo]; ra.poison = a->sig + SIG_ERR; ra.reduce_only = defer ? 1 : 0;
+        ra.cpl = a->conv_b3 && !defer ? a->cpl[0] : nullptr;
+        hipLaunchKernelGGL(k_reduce_adam, dim3(ra.reduce_blocks), dim3(256), 0, st, ra);
+        BDR_HIP(hipGetLastError());
+        if (ra.cpl && hi > 1) a->cpl_fresh[0] = true;   // (a poisoned launch skips parameters and planes alike; on_gate_timeout marks them stale anyway)
         return BDR_OK;
     };
 
@@ -950,13 +1014,38 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
         BDR_TRY(head_bwd()); BDR_TRY(l1_dw());
         BDR_TRY(l1_dx());
         BDR_TRY(gate(sd, SIG_DXL1)); BDR_TRY(c3_dw()); BDR_TRY(adam_l1_l2());
-        hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, sd, a->sig, SIG_SIDE, epoch);
-        BDR_HIP(hipGetLastError());
+        if (!tail) {
+            hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, sd, a->sig, SIG_SIDE, epoch);
+            BDR_HIP(hipGetLastError());
+        }
         BDR_TRY(c3_dx());
         BDR_TRY(c2_dx());
-        { hipStream_t side = sd; sd = a->stream; BDR_TRY(c2_dw()); sd = side; }
-        BDR_TRY(c1_dw());
-        BDR_TRY(gate(a->stream, SIG_SIDE));   // join: all weight-gradient partials complete
+        if (tail) {
+            // Overlapped tail.  Nothing in the data orders conv2 dW (needs dy2), conv1 dW (needs dy1) and the conv optimizer passes one after
+            // the other, and the weight-gradient queue is idle from its l1 / l2 pass on:
+            //   dX queue      conv1 dW (its start publishes DXC2) -> reduce + Adam {conv1}   | next update: [gate GATHER] conv1 -> [gate CONV23] conv2 ...
+            //   other queue   [gate DXC2] -> conv2 dW -> reduce + Adam {conv2, conv3} -> signal CONV23
+            // The gate keeps conv2 dW from running beside conv2 dX (measured slower: profiles/ab_r06_conv2_dw_queue.txt).  Hazards:
+            //   W2, W3 and their planes are written on the other queue behind DXC2, i.e. after conv3 dX and conv2 dX - their last readers of
+            //     this update - have completed; they are read next by the following forward's conv2, behind CONV23 (join_conv23);
+            //   W1 / b1 are written and read on the dX queue only; l1 / l2 are stepped earlier on the other queue, so CONV23 covers them too;
+            //   grad, m, v and the partials of a conv segment are touched only by that segment's dW and reduce launch, on one queue each;
+            //   conv2 dW reads dy2 (rewritten by the next conv3 dX, behind CONV23) and a1[0] (rewritten by the next conv1 forward IN FRONT of
+            //     CONV23: consecutive updates alternate between two buffers, a1_alt).
+            // Everything else that touches the parameters on the agent's stream waits for CONV23 first (conv23_join_pending).
+            BDR_TRY(c1_dw());
+            BDR_TRY(reduce_adam(a->stream, 0, 1));
+            BDR_TRY(gate(sd, SIG_DXC2));
+            BDR_TRY(c2_dw());
+            BDR_TRY(reduce_adam(sd, 1, 3));
+            hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, sd, a->sig, SIG_CONV23, epoch);
+            BDR_HIP(hipGetLastError());
+            a->conv23_join_pending = true; a->conv23_epoch = epoch;
+        } else {
+            { hipStream_t side = sd; sd = a->stream; BDR_TRY(c2_dw()); sd = side; }
+            BDR_TRY(c1_dw());
+            BDR_TRY(gate(a->stream, SIG_SIDE));   // join: all weight-gradient partials complete
+        }
     } else if (sched == 2) {
         BDR_TRY(l1_dx());  BDR_TRY(head_bwd()); BDR_TRY(l1_dw());        // barrier, any-order, any-order
         BDR_TRY(c3_dx());  BDR_TRY(adam_l1_l2()); BDR_TRY(c3_dw());
@@ -977,31 +1066,10 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
             BDR_HIP(hipStreamWaitEvent(a->stream, a->ev_join, 0));
         }
     }
-    {   // conv1..conv3 partials -> gradient arena, one launch
-        Reduce3Args r{};
-        const int Ms[3] = {B * 400, B * 81, B * 49};
-        const int plc[3] = {pl.chunks_c1, pl.chunks_c2, pl.chunks_c3};
-        const size_t offs[3] = {pl.off_c1, pl.off_c2, pl.off_c3}, strides[3] = {pl.stride_c1, pl.stride_c2, pl.stride_c3};
-        const size_t gw[3] = {ar.w1, ar.w2, ar.w3};
-        const int nw[3] = {(int)ar.n_w1(), 512 * 64, 576 * 64}, nb[3] = {32, 64, 64};
-        int wg = 0;
-        for (int k = 0; k < 3; ++k) {
-            const int nchunks = k == 0 ? std::min(plc[0], B) : std::min(plc[k], (Ms[k] + 31) / 32);   // conv1: one partial per workgroup
-            r.seg[k] = ReduceSeg{a->part + offs[k], strides[k], nchunks, a->grad + gw[k], nw[k] + nb[k], nw[k],
-                                 k == 0 ? INV255 : 1.0f, wg};
-            wg += (nw[k] + nb[k] + 31) / 32;
-        }
-        // the conv layers' Adam step rides on their partial reduction (k_reduce_adam); l1 / l2: adam_l1_l2 above
-        ConvReduceAdamArgs ra{};
-        ra.r = r; ra.p = a->q; ra.g = a->grad; ra.m = a->m; ra.v = a->v; ra.gbase = a->grad;
-        ra.rest0_4 = ra.n4 = ar.w4 / 4; ra.s = a->conv_step_lag ? adam_scalars(c, (uint64_t)std::max<int64_t>((int64_t)a->adam_step - a->conv_step_lag, 1)) : adam_s;
-        ra.applied = defer ? nullptr : a->applied_step + 1; ra.step = (unsigned long long)((int64_t)a->adam_step - a->conv_step_lag);
-        ra.reduce_blocks = wg; ra.poison = a->sig + SIG_ERR; ra.reduce_only = defer ? 1 : 0;
-        ra.cpl = a->conv_b3 && !defer ? a->cpl[0] : nullptr;
+    if (!tail) {
         Bracket br(a, "reduce_adam");
-        hipLaunchKernelGGL(k_reduce_adam, dim3(wg), dim3(256), 0, a->stream, ra);
-        BDR_HIP(hipGetLastError());
-        if (ra.cpl) a->cpl_fresh[0] = true;   // (a poisoned launch skips parameters and planes alike; on_gate_timeout marks them stale anyway)
+        if (a->conv_lag[0] == a->conv_lag[1]) BDR_TRY(reduce_adam(a->stream, 0, 3));   // one launch
+        else { BDR_TRY(reduce_adam(a->stream, 0, 1)); BDR_TRY(reduce_adam(a->stream, 1, 3)); }   // after a time-out between the passes: a step number per launch
     }
     return BDR_OK;
 }
@@ -1010,6 +1078,7 @@ int32_t soft_update(DqnCnn* a)
 {
     const size_t n4 = a->ar.total / 4;
     const float tau = (float)a->cfg.tau, omt = (float)(1.0 - a->cfg.tau);
+    BDR_TRY(a->join_conv23());
     Bracket br(a, "track");
     a->planes_stale(1);
     hipLaunchKernelGGL(k_track, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, a->stream, a->q_tgt, a->q, n4, tau, omt, (const unsigned*)(a->sig + SIG_ERR));
@@ -1038,18 +1107,19 @@ int32_t after_updates(DqnCnn* a)
 // the optimizer step over the whole arena (the fused path splits it between k_reduce_adam and the l1 / l2 k_adam)
 int32_t adam_all(DqnCnn* a)
 {
+    BDR_TRY(a->join_conv23());
     a->adam_step += 1;
     a->planes_stale(0);
     Bracket br(a, "adam_all");
     const size_t n4 = a->ar.total / 4;
     const unsigned* poison = (const unsigned*)(a->sig + SIG_ERR);
     // ranges of the arena with their own optimizer step number: one (the whole arena) unless a gate time-out once fell between the fused
-    // path's two passes - then the conv segment [0, w4) continues from the step number ITS moments are at
-    struct Range { size_t off, n; uint64_t step; int slot; } rg[2] = {{0, a->ar.total, a->adam_step, 0}, {0, 0, 0, 1}};
+    // path's passes - then conv1 [0, w2) and conv2 + conv3 [w2, w4) each continue from the step number THEIR moments are at
+    struct Range { size_t off, n; uint64_t step; int slot; } rg[3] = {{0, a->ar.total, a->adam_step, 0}, {0, 0, 0, 1}, {0, 0, 0, 2}};
     int nr = 1;
-    if (a->conv_step_lag) {
-        const uint64_t cs = (uint64_t)std::max<int64_t>((int64_t)a->adam_step - a->conv_step_lag, 1);
-        rg[0] = Range{a->ar.w4, a->ar.total - a->ar.w4, a->adam_step, 0}; rg[1] = Range{0, a->ar.w4, cs, 1}; nr = 2;
+    if (a->conv_lag[0] || a->conv_lag[1]) {
+        const uint64_t c1s = (uint64_t)std::max<int64_t>((int64_t)a->adam_step - a->conv_lag[0], 1), c23s = (uint64_t)std::max<int64_t>((int64_t)a->adam_step - a->conv_lag[1], 1);
+        rg[0] = Range{a->ar.w4, a->ar.total - a->ar.w4, a->adam_step, 0}; rg[1] = Range{0, a->ar.w2, c1s, 1}; rg[2] = Range{a->ar.w2, a->ar.w4 - a->ar.w2, c23s, 2}; nr = 3;
     }
     for (int k = 0; k < nr; ++k) {
         const Range& g = rg[k];
@@ -1059,9 +1129,11 @@ int32_t adam_all(DqnCnn* a)
                            sc, poison, a->applied_step + g.slot, (unsigned long long)g.step);
         BDR_HIP(hipGetLastError());
     }
-    if (nr == 1) {   // the whole-arena pass stands for both segments
-        hipLaunchKernelGGL(k_copy_word_unless, dim3(1), dim3(1), 0, a->stream, a->applied_step + 1, (const unsigned long long*)a->applied_step, poison);
-        BDR_HIP(hipGetLastError());
+    if (nr == 1) {   // the whole-arena pass stands for every segment
+        for (int k = 1; k <= 2; ++k) {
+            hipLaunchKernelGGL(k_copy_word_unless, dim3(1), dim3(1), 0, a->stream, a->applied_step + k, (const unsigned long long*)a->applied_step, poison);
+            BDR_HIP(hipGetLastError());
+        }
     }
     (void)n4;
     return BDR_OK;
@@ -1143,6 +1215,7 @@ int32_t opt_inner(DqnCnn* a, bdr_replay* r)
 
 int32_t fill_record(DqnCnn* a, int B, const float* reward_dev, bdr_dqn_record* rec)
 {
+    BDR_TRY(a->join_conv23());   // the caller continues on finished parameters
     BDR_HIP(hipMemcpyAsync(&rec->loss, a->loss, 4, hipMemcpyDeviceToHost, a->stream));
     BDR_HIP(hipStreamSynchronize(a->stream));
     rec->has_verbose = 0;
@@ -1252,26 +1325,24 @@ void DqnCnn::on_gate_timeout()
         // Updates whose parameter-writing kernels ran while the poison word was up were skipped on the device: the host's step numbers go
         // back to the last update that was applied, so Adam's bias corrections continue from the state the parameters are in
         // (the l1 / l2 pass, 95 % of the arena, records the step number it applied; opt.rs:74-83).
-        // The two optimizer passes of the fused path (l1 / l2 on the weight-gradient queue, the conv segment at the end of the dX queue)
-        // each record the step number they applied; a time-out that fell BETWEEN them leaves the conv segment one step behind: it keeps
-        // its own step number from then on (conv_step_lag), so every segment's bias corrections match the moments it holds.
-        unsigned long long applied[2] = {0, 0};
+        // The optimizer passes of the fused path (l1 / l2 and conv2 + conv3 on the weight-gradient queue, conv1 on the dX queue) each
+        // record the step number they applied; a time-out that fell BETWEEN them leaves a conv segment a step away from l1 / l2: it keeps
+        // its own step number from then on (conv_lag), so every segment's bias corrections match the moments it holds.
+        unsigned long long applied[3] = {0, 0, 0};
         if (hipMemcpy(applied, applied_step, sizeof applied, hipMemcpyDeviceToHost) == hipSuccess) {
-            const int64_t conv_now = (int64_t)adam_step - conv_step_lag;
-            if (applied[0] < adam_step || (int64_t)applied[1] < conv_now) {
-                const uint64_t skipped = adam_step - std::min<uint64_t>(applied[0], adam_step);
-                adam_step -= skipped;
-                conv_step_lag = (int64_t)adam_step - (int64_t)std::min<uint64_t>(applied[1], (uint64_t)std::max<int64_t>(conv_now, 0));
-                const uint64_t opts_back = std::min(n_opts, skipped / std::max<uint64_t>(1, cfg.n_updates_per_opt));
-                n_opts -= opts_back;
-                // the soft updates of the skipped opts were skipped on the device with them (k_track is poison-gated): their counter goes back too
-                const uint64_t iv = std::max<uint64_t>(1, cfg.soft_update_interval);
-                soft_update_counter = (soft_update_counter + iv - opts_back % iv) % iv;
-                fprintf(stderr, "border_amd: %llu update(s) behind the failed gate were skipped on the device; the step counters were rolled back with them%s\n",
-                        (unsigned long long)skipped, conv_step_lag ? " (the conv segment is one optimizer step behind l1 / l2 and keeps its own step number)" : "");
+            const bdr::DqnRollback rb = bdr::dqn_rollback(applied, bdr::DqnStepCounters{adam_step, {conv_lag[0], conv_lag[1]}, n_opts, soft_update_counter},
+                                                          cfg.n_updates_per_opt, cfg.soft_update_interval);   // (dqn_rollback.hpp)
+            if (rb.changed) {
+                adam_step = rb.c.adam_step; conv_lag[0] = rb.c.lag[0]; conv_lag[1] = rb.c.lag[1];
+                n_opts = rb.c.n_opts; soft_update_counter = rb.c.soft_update_counter;
+                fprintf(stderr, "border_amd: %llu update(s) behind the failed gate were skipped on the device; the step counters were rolled back with them", (unsigned long long)rb.skipped);
+                if (conv_lag[0] || conv_lag[1])
+                    fprintf(stderr, " (optimizer steps behind l1 / l2: conv1 %lld, conv2 + conv3 %lld - each segment keeps its own step number)", (long long)conv_lag[0], (long long)conv_lag[1]);
+                fprintf(stderr, "\n");
             }
         }
     }
+    conv23_join_pending = false;   // (every queue has drained)
     sig_epoch = 0; head_gate_enqueued = false;
     if (sched == 3) {
         fprintf(stderr, "border_amd: a cross-queue gate timed out; this agent continues with event ordering (schedule 1)\n");
@@ -1314,7 +1385,10 @@ int DqnCnn::exchange_plan(int which, ExchangeSeg* segs, int cap, hipStream_t* co
 int32_t DqnCnn::exchange_begin(int seg)
 {
     const int flag = (seg == 0 && !xchg_tracked) ? SIG_SIDE : SIG_MAIN_END;
-    return launch_gate(this, comm_st, flag, xchg_epoch, -1);
+    BDR_TRY(launch_gate(this, comm_st, flag, xchg_epoch, -1));
+    // the conv2 / conv3 pass of the overlapped tail ends on the weight-gradient queue: "the dX queue has finished" does not cover it
+    if (flag == SIG_MAIN_END) BDR_TRY(launch_gate(this, comm_st, SIG_CONV23, xchg_epoch, -1));
+    return BDR_OK;
 }
 
 int32_t DqnCnn::exchange_end(int seg)
@@ -1323,6 +1397,13 @@ int32_t DqnCnn::exchange_end(int seg)
     BDR_HIP(hipGetLastError());
     if (seg == 0) xchg_pending_fc = true; else xchg_pending_conv = true;
     return BDR_OK;
+}
+
+int32_t DqnCnn::join_conv23()
+{
+    if (!conv23_join_pending) return BDR_OK;
+    conv23_join_pending = false;
+    return launch_gate(this, stream, SIG_CONV23, conv23_epoch, -1);
 }
 
 int32_t DqnCnn::join_exchange(bool conv, bool fc)
@@ -1338,7 +1419,8 @@ DqnCnn::~DqnCnn()
     if (comm_st) { (void)hipStreamSynchronize(comm_st); (void)hipStreamDestroy(comm_st); }
     if (holds_gate_token) { DqnCnn* me = this; g_gate_owner.compare_exchange_strong(me, nullptr); holds_gate_token = false; }
     (void)hipStreamSynchronize(stream);
-    if (side) (void)hipStreamSynchronize(side);
+    if (side) (void)hipStreamSynchronize(side);   // (a pending CONV23 join included: the weight-gradient queue is drained itself)
+    conv23_join_pending = false;
     free_batch_buffers(this);
     (void)hipFree(q); (void)hipFree(q_tgt); (void)hipFree(grad); (void)hipFree(m); (void)hipFree(v); (void)hipFree(vmax);
     (void)hipFree(loss); (void)hipFree(cpl[0]); (void)hipFree(cpl[1]);
@@ -1408,6 +1490,7 @@ uint64_t DqnCnn::param_count(int which) { return which == -1 ? (uint64_t)ar.A : 
 
 int32_t DqnCnn::get_params(int which, float* out, uint64_t n)
 {
+    BDR_TRY(join_conv23());
     BDR_TRY(join_exchange(true, true));
     float* src = arena_ptr(this, which);
     BDR_REQUIRE(src, "which must be 0..4");
@@ -1422,6 +1505,7 @@ int32_t DqnCnn::get_params(int which, float* out, uint64_t n)
 
 int32_t DqnCnn::set_params(int which, const float* inp, uint64_t n)
 {
+    BDR_TRY(join_conv23());
     BDR_TRY(join_exchange(true, true));
     float* dst = arena_ptr(this, which);
     BDR_REQUIRE(dst, "which must be 0..4");
@@ -1436,6 +1520,7 @@ int32_t DqnCnn::set_params(int which, const float* inp, uint64_t n)
 
 float* DqnCnn::arena(int which, size_t* n)
 {
+    (void)join_conv23();
     (void)join_exchange(true, true);   // whoever asks for the arena is about to enqueue work on it behind this queue
     planes_stale(which);               // ... possibly a write
     if (n) *n = ar.total;
@@ -1483,8 +1568,8 @@ int32_t dqn_cnn_create(const bdr_dqn_config* cfg, bdr_agent** out)
     BDR_HIP(hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming | hipEventDisableSystemFence));
     if (const char* e = getenv("BDR_SCHED")) a->sched = std::max(0, std::min(3, atoi(e)));
     BDR_HIP(hipMalloc((void**)&a->sig, 16 * sizeof(unsigned)));
-    BDR_HIP(hipMalloc((void**)&a->applied_step, 2 * sizeof(unsigned long long)));
-    BDR_HIP(hipMemsetAsync(a->applied_step, 0, 2 * sizeof(unsigned long long), a->stream));
+    BDR_HIP(hipMalloc((void**)&a->applied_step, 3 * sizeof(unsigned long long)));
+    BDR_HIP(hipMemsetAsync(a->applied_step, 0, 3 * sizeof(unsigned long long), a->stream));
     BDR_HIP(hipMemsetAsync(a->sig, 0, 16 * sizeof(unsigned), a->stream));   // synchronised with the parameter upload below
     if (getenv("BDR_GATE_TRACE")) {
         BDR_HIP(hipMalloc((void**)&a->gate_trace, 32 * sizeof(unsigned long long)));
@@ -1535,6 +1620,7 @@ int32_t dqn_cnn_update_on_batch(bdr_agent* base, uint64_t n, const void* obs, co
 {
     DqnCnn* a = static_cast<DqnCnn*>(base);
     const size_t ob = (size_t)a->cfg.net.n_stack * 84 * 84;
+    BDR_TRY(a->join_conv23());   // this update starts from the finished parameters of the one before it
     if (n > a->u_cap) {
         BDR_HIP(hipStreamSynchronize(a->stream));
         (void)hipFree(a->u_obs); (void)hipFree(a->u_next); (void)hipFree(a->u_act); (void)hipFree(a->u_rew); (void)hipFree(a->u_term);
@@ -1559,6 +1645,7 @@ int32_t dqn_cnn_update_on_batch(bdr_agent* base, uint64_t n, const void* obs, co
         BDR_TRY(after_updates(a));
     }
     BDR_TRY(st);
+    BDR_TRY(a->join_conv23());                  // the call returns with the update complete on both queues
     BDR_HIP(hipStreamSynchronize(a->stream));   // host buffers may be reused by the caller
     return BDR_OK;
 }
@@ -1587,6 +1674,7 @@ static int32_t act_small_forward(DqnCnn* a, const uint8_t* d, int n, float* q_ou
 {
     const Arena& ar = a->ar;
     hipStream_t st = a->stream;
+    BDR_TRY(a->join_conv23());
     BDR_TRY(a->join_exchange(true, true));   // an overlapped parameter exchange of the online network may still be in flight
     if (!a->act_part) {
         BDR_HIP(hipMalloc((void**)&a->act_part, act_small_part_floats() * sizeof(float)));
@@ -1622,6 +1710,7 @@ static int32_t act_small_forward(DqnCnn* a, const uint8_t* d, int n, float* q_ou
 int32_t dqn_cnn_qvalues(bdr_agent* base, uint64_t n, const void* obs, float* q_out)
 {
     DqnCnn* a = static_cast<DqnCnn*>(base);
+    BDR_TRY(a->join_conv23());   // in front of conv1: it writes a1[0], which conv2 dW of the last update may still be reading
     BDR_TRY(ensure_batch(a, (int)n));
     const size_t ob = (size_t)a->cfg.net.n_stack * 84 * 84;
     const uint8_t* d = static_cast<const uint8_t*>(obs);
