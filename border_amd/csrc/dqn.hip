@@ -1750,9 +1750,23 @@ int32_t dqn_cnn_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
         case 5: src = a->a1[0]; break;   // the online network's activations on `obs`, position-major: [B][20*20][32], [B][9*9][64], [B][7*7][64]
         case 6: src = a->a2[0]; break;
         case 7: src = a->a3[0]; break;
+        // the backward pass's inputs and intermediates: the online instance's h1 [B][512], dL/dQ(s,a) [B], and the gradients w.r.t. the
+        // pre-activations of l1 [B][512], conv3 [B*49][64], conv2 [B*81][64], conv1 [B*400][32]
+        case 8: src = a->h1[0]; break;
+        case 9: src = a->dq; break;
+        case 10: src = a->dh1; break;
+        case 11: src = a->dy3; break;
+        case 12: src = a->dy2; break;
+        case 13: src = a->dy1; break;
         default: return fail(BDR_ERR_INVALID, "unknown probe %d", what);
     }
     BDR_REQUIRE(src, "nothing to probe yet (no update has run)");
+    // Every probed buffer is written on, or ordered in front of, the agent's stream in every schedule: forward, head and the dX chain run
+    // on it, and with the split forward the target instance's Q values (probe 1) come from the other queue in front of k_head's wait on
+    // SIG_TGT.  Otherwise the other queue only reads them.  a1[0] is the buffer this update's conv2 dW read until the NEXT update swaps it
+    // with a1_alt.  With the overlapped tail the last update's conv2 dW / conv optimizer pass may still be running on the other queue:
+    // the copy goes behind its CONV23 flag, so a probe after opt() returns with that update complete, as one after update_on_batch does.
+    BDR_TRY(a->join_conv23());
     BDR_HIP(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, a->stream));
     BDR_HIP(hipStreamSynchronize(a->stream));
     return BDR_OK;

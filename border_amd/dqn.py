@@ -381,7 +381,8 @@ class Dqn:
 
     # probes / profiling ----------------------------------------------------------------------
     def probe(self, what: str, n: int) -> np.ndarray:
-        idx = {"q_pred_all": 0, "q_next_all": 1, "pred": 2, "tgt": 3, "loss": 4, "act_conv1": 5, "act_conv2": 6, "act_conv3": 7}[what]
+        idx = {"q_pred_all": 0, "q_next_all": 1, "pred": 2, "tgt": 3, "loss": 4, "act_conv1": 5, "act_conv2": 6, "act_conv3": 7,
+               "h1": 8, "dq": 9, "dh1": 10, "dy3": 11, "dy2": 12, "dy1": 13}[what]   # 8-13 AtariCnn only: the backward pass's inputs and intermediates
         out = np.empty(n, np.float32)
         _lib.check(_lib.lib().bdr_dqn_probe(self._h, idx, _p(out), n))
         return out

@@ -750,7 +750,9 @@ BDR_API int32_t bdr_checkpoint_read(const char* path, const bdr_named_tensor* me
 
 /* Parity probes: copy intermediates of the LAST update to the host.
  * what: 0 q_pred_all [B][A], 1 q_next_all [B][A], 2 pred [B], 3 tgt [B], 4 loss [1];
- * AtariCnn only, the online network's activations on `obs`, position-major (NHWC): 5 conv1 [B][400][32], 6 conv2 [B][81][64], 7 conv3 [B][49][64]. */
+ * AtariCnn only, the online network's activations on `obs`, position-major (NHWC): 5 conv1 [B][400][32], 6 conv2 [B][81][64], 7 conv3 [B][49][64];
+ * AtariCnn only, the backward pass: 8 h1 [B][512] (online instance on `obs`), 9 dq [B] (dL/dQ(s,a)), 10 dh1 [B][512], and the gradients
+ * w.r.t. the conv layers' pre-activations, position-major: 11 dy3 [B*49][64], 12 dy2 [B*81][64], 13 dy1 [B*400][32]. */
 BDR_API int32_t bdr_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
 
 /* Per-kernel device timing of the opt step (bench.py roofline leg): when enabled the step is
