@@ -158,6 +158,18 @@ class CandleDqnConfigC(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class CandleDqnCnnConfigC(C.Structure):
+    """bdr_candle_dqn_cnn_config: the candle DQN with the AtariCnn Q-network"""
+    _fields_ = [("n_stack", C.c_int32), ("out_dim", C.c_int32), ("skip_linear", C.c_int32), ("arithmetic", C.c_int32),
+                ("opt", AdamWConfigC), ("lr", C.c_double),
+                ("soft_update_interval", C.c_uint64), ("n_updates_per_opt", C.c_uint64), ("batch_size", C.c_uint64),
+                ("discount_factor", C.c_double), ("tau", C.c_double), ("train", C.c_int32), ("double_dqn", C.c_int32),
+                ("explorer", ExplorerConfigC), ("has_clip_reward", C.c_int32), ("has_clip_td_err", C.c_int32),
+                ("clip_reward", C.c_double), ("clip_td_err_min", C.c_double), ("clip_td_err_max", C.c_double),
+                ("critic_loss", C.c_int32), ("record_verbose_level", C.c_int32), ("device", C.c_int32), ("ckpt_format", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class NamedTensorC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("dims", C.POINTER(C.c_uint64)), ("ndim", C.c_uint32)]
 
@@ -266,6 +278,7 @@ ABI_SYMBOLS = [
     "bdr_candle_sac_sample_device",
     "bdr_bc_config_default", "bdr_bc_create", "bdr_bc_update_on_batch", "bdr_bc_probe", "bdr_bc_sample", "bdr_bc_sample_device",
     "bdr_candle_dqn_config_default", "bdr_candle_dqn_create", "bdr_candle_dqn_update_on_batch", "bdr_candle_dqn_probe",
+    "bdr_candle_dqn_cnn_config_default", "bdr_candle_dqn_cnn_create", "bdr_candle_dqn_cnn_update_on_batch",
     "bdr_comm_get_unique_id", "bdr_comm_init_rank", "bdr_comm_destroy", "bdr_comm_agree", "bdr_sac_probe", "bdr_agent_allreduce_params",
     "bdr_agent_broadcast_params", "bdr_agent_set_grad_comm", "bdr_dqn_grads_on_batch", "bdr_agent_apply_grads",
     "bdr_atari_prep_create", "bdr_atari_prep_destroy", "bdr_atari_prep_reset", "bdr_atari_prep_step", "bdr_atari_prep_obs",
@@ -299,6 +312,7 @@ def lib() -> C.CDLL:
         fn = getattr(L, name)  # AttributeError here == ABI drift
         if name not in ("bdr_last_error", "bdr_version", "bdr_dqn_config_default", "bdr_sac_config_default", "bdr_iqn_config_default", "bdr_iql_config_default",
                         "bdr_awac_config_default", "bdr_bc_config_default", "bdr_candle_sac_config_default", "bdr_candle_dqn_config_default",
+                        "bdr_candle_dqn_cnn_config_default",
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
                         "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default"):
             fn.restype = C.c_int32
@@ -414,6 +428,10 @@ def lib() -> C.CDLL:
     L.bdr_candle_dqn_create.argtypes = [C.POINTER(CandleDqnConfigC), C.POINTER(vp)]
     L.bdr_candle_dqn_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(DqnRecordC)]
     L.bdr_candle_dqn_probe.argtypes = [vp, i32, vp, u64]
+    L.bdr_candle_dqn_cnn_config_default.restype = None
+    L.bdr_candle_dqn_cnn_config_default.argtypes = [C.POINTER(CandleDqnCnnConfigC)]
+    L.bdr_candle_dqn_cnn_create.argtypes = [C.POINTER(CandleDqnCnnConfigC), C.POINTER(vp)]
+    L.bdr_candle_dqn_cnn_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(DqnRecordC)]
     L.bdr_bc_config_default.restype = None
     L.bdr_bc_config_default.argtypes = [C.POINTER(BcConfigC)]
     L.bdr_bc_create.argtypes = [C.POINTER(BcConfigC), C.POINTER(vp)]

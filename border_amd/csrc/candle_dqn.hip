@@ -13,11 +13,15 @@
 // k_cdqn_td, L - 1 input gradients, the grouped dW, reduce + Adam: 2 L + 3 launches, 9 at the CartPole shape (L = 3), plus the
 // ring's gather.  The soft update rides in the reduce + Adam launch of the opt's last update on the opts that track (dqn/base.rs:180-184).
 // Every sum has one order (candle::row_sum), so an update gives the same bits run to run and agent to agent.
+// The AtariCnn Q-network (atari_cnn/base.rs) is the second form, CandleDqnCnn below: the shared conv layers of cnn_layers.hpp in front
+// of the same head and TD step, and k_cdqn_conv_reduce_adam, the candle optimizer step over the conv gradients' partial sums.
 #include <algorithm>
 #include <cstdlib>
 #include <deque>
 
 #include "candle_actor.hpp"
+#include "conv1_bf16_img.hpp"
+#include "cnn_layers.hpp"
 
 using namespace bdr;
 
@@ -128,6 +132,73 @@ __global__ __launch_bounds__(256) void k_cdqn_act(CdqnActArgs p)
     if (t < p.n) p.idx[t] = dqn_q_argmax(p.z + (size_t)t * p.ld, p.A);
 }
 
+// ---- k_cdqn_conv_reduce_adam ------------------------------------------------------------------------------------------------------
+// The optimizer step of the AtariCnn form's conv parameters.  The conv weight-gradient kernels (DwC3, DwC2, conv1_dw_bf16) leave
+// row-chunk partials [chunks][K N + N] (weights, then bias) per layer.  A workgroup owns 32 float4 of the conv arena W1 b1 W2 b2 W3 b3 -
+// the segments follow one another without slack, each a multiple of four floats - and eight threads share a float4 i:
+//   thread group q = 0 ... 7 sums the float4 of the chunks c = q, q + 8, ... in ascending order; the eight sums meet in LDS and
+//   group 0 adds them as ((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7: ONE order, whatever the grid (conv1 leaves up to 256
+//   chunks: one thread per float4 walked them in 82 us at B = 256); it scales conv1's WEIGHT elements by 1/255 (the kernel multiplied
+//   raw u8 operands; the bias gradient is the plain column sum), stores the gradient arena,
+//   applies adam_element (candle AdamW / candle-optimisers Adam through AdamScalars) and, on the opts that track, track_element -
+//   exactly what k_dense_reduce_adam applies to the head's parameters.
+// It reads the same poison word (err[ERR_ACTION], raised by k_cdqn_td earlier in the same update) and writes the same `applied`
+// word as the head's launch: the word does not change between the two launches of an update (only the host clears it, with the
+// stream idle), so either every parameter of an update steps or none does, and settle() holds for the whole set.
+// Bounds.  i = 32 blockIdx.x + (threadIdx.x & 31) < n4 = conv floats / 4 for every access but the LDS store (red[8][32], indexed by
+// the thread's group and slot); segment k = the last one with off4 <= i, so j = i - off4 < seg.n4 and the reads
+// part[c * stride + 4 j .. + 3], c < chunks, stay below chunks * stride (stride = 4 seg.n4 = the segment's floats).  p, g, m, v, tgt
+// are arenas of at least n4 float4.
+struct CdqnConvSeg { const float* part; size_t stride; int chunks; unsigned off4, n4, nw4; float wscale; };   // float4s [off4, off4 + n4); the first nw4 scaled
+struct CdqnConvAdamArgs {
+    CdqnConvSeg seg[3];
+    float *p, *g, *m, *v, *tgt;
+    AdamScalars s; unsigned n4; float tau, omt; int track;
+    const unsigned* poison; unsigned long long* applied; unsigned long long step;
+};
+__global__ __launch_bounds__(256) void k_cdqn_conv_reduce_adam(CdqnConvAdamArgs a)
+{
+#pragma clang fp contract(off)
+    __shared__ f32x4 red[8][32];
+    if (*a.poison) return;   // (the whole grid reads the same word: no thread of a workgroup is left at the barrier)
+    const unsigned o = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const unsigned i = blockIdx.x * 32 + o;
+    const bool in = i < a.n4;
+    const int k = (i >= a.seg[1].off4 ? 1 : 0) + (i >= a.seg[2].off4 ? 1 : 0);
+    const CdqnConvSeg sg = a.seg[k];
+    const unsigned j = i - sg.off4;
+    f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (in) {
+        const float* part = sg.part + (size_t)j * 4;
+        for (int c = (int)grp; c < sg.chunks; c += 8) sum += *reinterpret_cast<const f32x4*>(part + (size_t)c * sg.stride);
+    }
+    red[grp][o] = sum;
+    __syncthreads();
+    if (grp != 0 || !in) return;
+    if (i == 0) *a.applied = a.step;
+    f32x4 gg = red[0][o];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) gg += red[q][o];
+    if (j < sg.nw4) gg *= sg.wscale;
+    reinterpret_cast<f32x4*>(a.g)[i] = gg;
+    f32x4 pp = reinterpret_cast<f32x4*>(a.p)[i], mm = reinterpret_cast<f32x4*>(a.m)[i], vv = reinterpret_cast<f32x4*>(a.v)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        adam_element(pe, gg[e], me, ve, a.s);
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+    }
+    reinterpret_cast<f32x4*>(a.p)[i] = pp;
+    reinterpret_cast<f32x4*>(a.m)[i] = mm;
+    reinterpret_cast<f32x4*>(a.v)[i] = vv;
+    if (a.track) {
+        f32x4 d = reinterpret_cast<f32x4*>(a.tgt)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = track_element(pp[e], d[e], a.tau, a.omt);
+        reinterpret_cast<f32x4*>(a.tgt)[i] = d;
+    }
+}
+
 // ---- the exploration stream -------------------------------------------------------------------------------------------------------
 // rand 0.8.5's SmallRng on 64-bit targets as Dqn uses it (dqn/base.rs:274 `SmallRng::seed_from_u64(42)`, explorer.rs), restated from
 // rand's source; nothing here can run rand, so every rule below is unpinned until tools/upstream_kat has run.  The
@@ -234,6 +305,16 @@ struct CandleDqn : DenseAgent {
     std::vector<float> h_q; std::vector<int64_t> h_idx;
 
     bool verbose() const { return cfg.record_verbose_level >= 2; }
+    // The AtariCnn form (CandleDqnCnn below) keeps a conv trunk in front of `net`: it brings the trunk's batch buffers in place of
+    // the packed f32 inputs, its own forward of an acting call, and the sizes and names of the whole parameter set
+    virtual bool cnn_form() const { return false; }
+    virtual int32_t alloc_inputs(int Bn)
+    {
+        BDR_TRY(alloc(&x_o, (size_t)Bn * net.L[0].Kp, BATCH));
+        return alloc(&x_no, (size_t)Bn * net.L[0].Kp, BATCH);
+    }
+    virtual uint64_t ref_count() const { return net.ref_total; }
+    virtual size_t arena_floats() const { return net.total; }
 
     int32_t ensure_batch(int Bn)
     {
@@ -241,7 +322,7 @@ struct CandleDqn : DenseAgent {
         BDR_HIP(hipStreamSynchronize(stream));
         release(BATCH);
         B = 0;
-        BDR_TRY(alloc(&x_o, (size_t)Bn * net.L[0].Kp, BATCH)); BDR_TRY(alloc(&x_no, (size_t)Bn * net.L[0].Kp, BATCH));
+        BDR_TRY(alloc_inputs(Bn));
         for (auto* vec : {&a_on, &a_tg, &a_onn, &dy}) BDR_TRY(layer_bufs(net, Bn, *vec));
         for (auto q : {&pr_pred, &pr_qn, &pr_y, &pr_tgt, &pr_dpred, &lrow}) BDR_TRY(alloc(q, Bn, BATCH));
         BDR_TRY(alloc(&part, plan(net, Bn, off), BATCH));
@@ -337,7 +418,7 @@ struct CandleDqn : DenseAgent {
         n_opts += 1;
         return BDR_OK;
     }
-    std::vector<NamedTensor> meta() const
+    virtual std::vector<NamedTensor> meta() const
     {
         std::vector<NamedTensor> mt;
         candle::mlp_meta(net, "", mt);
@@ -363,7 +444,7 @@ struct CandleDqn : DenseAgent {
         BDR_TRY(settle());
         if (rec_opt) {
             if (verbose()) {
-                std::vector<float> ref(net.ref_total);
+                std::vector<float> ref(ref_count());
                 BDR_TRY(get_params(0, ref.data(), ref.size()));
                 param_stats(meta(), ref.data(), r);
             }
@@ -386,7 +467,7 @@ struct CandleDqn : DenseAgent {
         return words_to_host(samp_idx, h_idx.data(), n * 2);   // an i64 index is two 32-bit words
     }
     // the forward of n f32 rows (host rows, or device rows inside with_device_rows) on the agent's acting path
-    int32_t run_net(uint64_t n, const float* obs)
+    virtual int32_t run_net(uint64_t n, const float* obs)
     {
         BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
         if (act_fused_on()) return act_fused(nullptr, n, obs, BDR_DTYPE_F32, obs_rows_on_device, obs_rows_on_device ? obs_row_stride : (uint64_t)O * 4, nullptr, nullptr);
@@ -522,7 +603,7 @@ struct CandleDqn : DenseAgent {
             default: return nullptr;
         }
     }
-    uint64_t param_count(int which) override { return which == -1 ? (uint64_t)A : slot(which) ? net.ref_total : 0; }
+    uint64_t param_count(int which) override { return which == -1 ? (uint64_t)A : slot(which) ? ref_count() : 0; }
     int32_t get_params(int which, float* out, uint64_t n) override
     {
         float* s = slot(which);
@@ -539,12 +620,12 @@ struct CandleDqn : DenseAgent {
         std::vector<float> in(net.total, 0.f);
         return arena_from_reference(net, inp, in, s);
     }
-    float* arena(int which, size_t* n) override { float* s = slot(which); if (n) *n = s ? net.total : 0; return s; }
+    float* arena(int which, size_t* n) override { float* s = slot(which); if (n) *n = s ? arena_floats() : 0; return s; }
 
     // ---- checkpoints: qnet.pt, qnet_tgt.pt (dqn/base.rs:337-351), VarMaps with mlp.ln{i}.weight / .bias at their root ----
     int32_t save(const char* dir) override
     {
-        std::vector<float> w(net.ref_total);
+        std::vector<float> w(ref_count());
         const char* stems[2] = {"qnet", "qnet_tgt"};
         for (int i = 0; i < 2; ++i) {
             BDR_TRY(get_params(i, w.data(), w.size()));
@@ -554,12 +635,261 @@ struct CandleDqn : DenseAgent {
     }
     int32_t load(const char* dir) override
     {
-        std::vector<float> w(net.ref_total);
+        std::vector<float> w(ref_count());
         const char* stems[2] = {"qnet", "qnet_tgt"};
         for (int i = 0; i < 2; ++i) {
             BDR_TRY(load_safetensors_named(candle::ckpt_load_path(ckpt_format, dir, stems[i]), meta(), w.data(), w.size()));
             BDR_TRY(set_params(i, w.data(), w.size()));
         }
+        return BDR_OK;
+    }
+};
+
+// ================================================================================================
+// The AtariCnn form (border-candle-agent/src/atari_cnn/base.rs:31-45): conv1 8x8/4, conv2 4x4/2, conv3 3x3/1 with ReLU after each -
+// the shared layer policies of cnn_layers.hpp, driven as iqn.hip drives them - then `net` = [3136 -> 512 -> A] on DenseAgent's
+// kernels.  Every arena is  W1 b1 W2 b2 W3 b3 (cnn_layers.hpp's layouts) | net's arena;  conv3's output [B][7][7][64] is net's first
+// input as it stands, and l1.weight's 3136 columns, (c, h, w) in the reference, are permuted once in to_internal / to_reference.
+// Arithmetic: conv1 on the bf16 MFMA with exact u8 operands and the 1/255 in its epilogue, everything else f32 x f32 on the FP32
+// MFMA (BDR_ARITH_F32_EXACT of the tch agent).  One queue, eager launches.  One update is
+//   3 trunk forwards (conv1, conv2, conv3: the passes (p, obs), (p_tgt, next_obs) and - double_dqn - (p, next_obs) share a launch)
+//   2 head forwards, k_cdqn_td, 2 head input gradients (l2, then d(features) under conv3's ReLU mask), the grouped dW of l1 and l2,
+//   the head's reduce + Adam, conv3 dW, conv3 dX, conv2 dW, conv2 dX, conv1 dW, k_cdqn_conv_reduce_adam
+// = 16 launches plus the ring's gather.  The head steps before the trunk's backward runs; nothing behind it reads l1 or l2.
+struct CandleDqnCnn : CandleDqn {
+    bdr_candle_dqn_cnn_config ccfg;
+    Arena conv;                      // offsets of W1 ... b3 (w4 = the conv floats = where net's arena begins)
+    float *a1[3] = {}, *a2[3] = {}, *a3[3] = {};    // trunk activations of the three passes
+    float *dy3 = nullptr, *dy2 = nullptr, *dy1 = nullptr, *part_conv = nullptr;
+    uint8_t *u_obs8 = nullptr, *u_next8 = nullptr; uint64_t u_cap8 = 0;
+
+    bool cnn_form() const override { return true; }
+    size_t conv_floats() const { return conv.w4; }
+    size_t row_bytes() const { return (size_t)7056 * conv.ns; }
+    uint64_t ref_count() const override { return (uint64_t)conv_floats() + net.ref_total; }
+    size_t arena_floats() const override { return conv_floats() + net.total; }
+    float* head(float* arena_base) const { return arena_base + conv_floats(); }
+
+    int32_t alloc_inputs(int Bn) override
+    {
+        for (int z = 0; z < 3; ++z) {
+            BDR_TRY(alloc(&a1[z], (size_t)Bn * 400 * 32, BATCH)); BDR_TRY(alloc(&a2[z], (size_t)Bn * 81 * 64, BATCH)); BDR_TRY(alloc(&a3[z], (size_t)Bn * 49 * 64, BATCH));
+        }
+        BDR_TRY(alloc(&dy3, (size_t)Bn * 49 * 64, BATCH)); BDR_TRY(alloc(&dy2, (size_t)Bn * 81 * 64, BATCH)); BDR_TRY(alloc(&dy1, (size_t)Bn * 400 * 32, BATCH));
+        return alloc(&part_conv, dw_plan(Bn, conv.ns).total, BATCH);
+    }
+    // the trunk of nz (parameters, u8 rows) pairs into a1 / a2 / a3 [0, nz): one launch per layer
+    int32_t trunk_forward(int nz, const float* const* pp, const uint8_t* const* rows, int Bn, const char* name)
+    {
+        Conv1Args c{}; c.M = Bn * 400; c.nz = nz;
+        FwdArgs f2{}, f3{}; f2.M = Bn * 81; f3.M = Bn * 49;
+        for (int z = 0; z < nz; ++z) {
+            c.x[z] = rows[z]; c.w1[z] = pp[z] + conv.w1; c.bias[z] = pp[z] + conv.b1; c.out[z] = a1[z];
+            f2.x[z] = a1[z]; f2.w[z] = pp[z] + conv.w2; f2.bias[z] = pp[z] + conv.b2; f2.out[z] = a2[z];
+            f3.x[z] = a2[z]; f3.w[z] = pp[z] + conv.w3; f3.bias[z] = pp[z] + conv.b3; f3.out[z] = a3[z];
+        }
+        bdr_agent* a = this;
+        { Bracket br(this, name); BDR_HIP(conv1_forward(conv.ns, Bn, stream, c)); }
+        { Bracket br(this, name); LAUNCH(k_igemm<FwdC2>, dim3((f2.M + 63) / 64, 1, nz), f2); }
+        { Bracket br(this, name); LAUNCH(k_igemm<FwdC3>, dim3((f3.M + 63) / 64, 1, nz), f3); }
+        return BDR_OK;
+    }
+    int32_t update_cnn(int Bn, const uint8_t* obs, const uint8_t* act, int act_bytes, const uint8_t* next_obs, const float* reward, const int8_t* term, bool track)
+    {
+        BDR_TRY(ensure_batch(Bn));
+        bdr_agent* a = this;
+        const int L = (int)net.L.size(), nz = cfg.double_dqn ? 3 : 2;
+        const DenseLayer& last = net.L[L - 1];
+        {
+            const float* pp[3] = {p, p_tgt, p}; const uint8_t* rows[3] = {obs, next_obs, next_obs};
+            BDR_TRY(trunk_forward(nz, pp, rows, Bn, "fwd_conv"));
+            const float* hp[3] = {head(p), head(p_tgt), head(p)}; const float* xs[3] = {a3[0], a3[1], a3[2]}; std::vector<float*>* as[3] = {&a_on, &a_tg, &a_onn};
+            BDR_TRY(mlp_forward(net, nz, hp, xs, as, Bn, "fwd"));
+        }
+        {
+            CdqnTdArgs t{};
+            t.q_on = a_on[L - 1]; t.q_tg = a_tg[L - 1]; t.q_on_next = cfg.double_dqn ? a_onn[L - 1] : nullptr;
+            t.Np = last.Np; t.A = A; t.B = Bn; t.act = act; t.act_bytes = act_bytes; t.reward = reward; t.term = term;
+            t.gamma = (float)cfg.discount_factor; t.loss_kind = cfg.critic_loss; t.relu_out = 0; t.verbose = verbose() ? 1 : 0;
+            t.dy = dy[L - 1]; t.pred = pr_pred; t.q_next = pr_qn; t.y = pr_y; t.tgt = pr_tgt; t.dpred = pr_dpred; t.lrow = lrow;
+            t.scal = scal; t.err = dev_err;
+            Bracket br(this, "cdqn_td");
+            BDR_HIP(step_launch(stream, false, k_cdqn_td, dim3(1), dim3(1024), t));
+        }
+        step += 1;
+        marks.push_back(Mark{step, opt_n0, opt_s0});
+        if (marks.size() > 4096) marks.pop_front();
+        const AdamScalars sc = opt_scalars(cfg.opt, cfg.lr, step);
+        {   // the head: l2's and l1's input gradients (the second one is d(features) under conv3's ReLU mask), dW, reduce + Adam
+            std::vector<float*>* acts[1] = {&a_on}; std::vector<float*>* dys[1] = {&dy};
+            float *hp = head(p), *hg = head(g), *hm = head(m), *hv = head(v), *ht[1] = {head(p_tgt)};
+            float* dx0[1] = {dy3}; const float* mask0[1] = {a3[0]};
+            BDR_TRY(mlp_backward_step(net, 1, &hp, &hg, &hm, &hv, track ? ht : nullptr, a3[0], acts, dys, part, 0, off, &sc, Bn, {"dx", "dw", "reduce_adam"}, net.total,
+                                      cfg.tau, L - 1, nullptr, dev_err + ERR_ACTION, applied, step, dx0, mask0));
+        }
+        const DwPlan pl = dw_plan(B, conv.ns);
+        CdqnConvAdamArgs ra{};
+        {
+            const int Mr = Bn * 49, chunks = std::min(pl.chunks_c3, (Mr + 31) / 32);
+            DwArgs d{a2[0], dy3, part_conv + pl.off_c3, pl.stride_c3, Mr};
+            { Bracket br(this, "conv3_dw"); LAUNCH(k_igemm_red<DwC3>, dim3(9 * chunks), d); }
+            ra.seg[2] = CdqnConvSeg{part_conv + pl.off_c3, pl.stride_c3, chunks, (unsigned)(conv.w3 / 4), (unsigned)(pl.stride_c3 / 4), 0u, 1.0f};
+        }
+        {
+            DxArgs d{dy3, p + conv.w3, a2[0], dy2, Bn * 81, nullptr, 0};
+            Bracket br(this, "conv3_dx");
+            BDR_HIP((launch_igemm<DxC3Pos, 2>(stream, dim3(((Bn + DxC3Pos::WM * DxC3Pos::TM * 32 - 1) / (DxC3Pos::WM * DxC3Pos::TM * 32)) * n_tiles<DxC3Pos>(), 81, 1), d)));
+        }
+        {
+            const int Mr = Bn * 81, chunks = std::min(pl.chunks_c2, (Mr + 31) / 32);
+            DwArgs d{a1[0], dy2, part_conv + pl.off_c2, pl.stride_c2, Mr};
+            { Bracket br(this, "conv2_dw"); LAUNCH(k_igemm_red<DwC2>, dim3(8 * chunks), d); }
+            ra.seg[1] = CdqnConvSeg{part_conv + pl.off_c2, pl.stride_c2, chunks, (unsigned)(conv.w2 / 4), (unsigned)(pl.stride_c2 / 4), 0u, 1.0f};
+        }
+        {
+            DxArgs d{dy2, p + conv.w2, a1[0], dy1, Bn * 100, nullptr, 0};
+            Bracket br(this, "conv2_dx");
+            BDR_HIP((launch_igemm<DxC2MPos, 1>(stream, dxc2_pos_grid<DxC2MPos>(Bn), d)));
+        }
+        {
+            const int chunks = std::min(pl.chunks_c1, Bn);
+            Conv1DwArgs d{obs, dy1, part_conv + pl.off_c1, pl.stride_c1, Bn};
+            { Bracket br(this, "conv1_dw"); BDR_HIP(launch_conv1_dw_bf16(conv.ns, dim3(chunks), stream, d)); }
+            ra.seg[0] = CdqnConvSeg{part_conv + pl.off_c1, pl.stride_c1, chunks, (unsigned)(conv.w1 / 4), (unsigned)(pl.stride_c1 / 4), (unsigned)(conv.n_w1() / 4), INV255};
+        }
+        {
+            ra.p = p; ra.g = g; ra.m = m; ra.v = v; ra.tgt = p_tgt; ra.s = sc; ra.n4 = (unsigned)(conv_floats() / 4);
+            ra.track = track ? 1 : 0; ra.tau = (float)cfg.tau; ra.omt = (float)(1.0 - cfg.tau);
+            ra.poison = dev_err + ERR_ACTION; ra.applied = applied; ra.step = step;
+            Bracket br(this, "conv_reduce_adam");
+            BDR_HIP(step_launch(stream, true, k_cdqn_conv_reduce_adam, dim3((ra.n4 + 31) / 32), dim3(256), ra));
+        }
+        last_B = Bn;
+        return BDR_OK;
+    }
+    int32_t opt(bdr_replay* r) override
+    {
+        BDR_REQUIRE(!r->per, "the candle DQN has no prioritized update: the reference panics on a batch that carries importance weights "
+                             "(border-candle-agent/src/dqn/base.rs:135-137); use a uniform ring");
+        BDR_REQUIRE(r->obs_bytes != (uint64_t)row_bytes() * 4, "DQN (candle, AtariCnn) reads u8 observation rows of 84 x 84 x n_stack bytes, not an f32 ring");
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)row_bytes(), "replay rows of %llu bytes do not match DQN (candle, AtariCnn) u8 rows of 84 x 84 x %d = %llu bytes",
+                    (unsigned long long)r->obs_bytes, conv.ns, (unsigned long long)row_bytes());
+        BDR_REQUIRE(r->act_bytes == 8, "DQN (candle) reads ONE i64 action per row: the ring's action rows must be 8 bytes, not %llu",
+                    (unsigned long long)r->act_bytes);
+        BDR_REQUIRE(r->device == device, "agent and replay buffer live on different devices");
+        const int Bn = (int)cfg.batch_size;
+        BDR_TRY(ensure_batch(Bn));
+        const bool track = opt_tracks();
+        for (uint64_t u = 0; u < cfg.n_updates_per_opt; ++u) {
+            { Bracket br(this, "sample"); BDR_TRY(replay_sample_on_stream(r, Bn, stream)); }
+            BDR_TRY(update_cnn(Bn, r->b_obs, r->b_act, 8, r->b_next, r->b_reward, r->b_term, track && u + 1 == cfg.n_updates_per_opt));
+        }
+        n_opts += 1;
+        return BDR_OK;
+    }
+    std::vector<NamedTensor> meta() const override
+    {
+        return {{"c1.weight", {32, (uint64_t)conv.ns, 8, 8}}, {"c1.bias", {32}}, {"c2.weight", {64, 32, 4, 4}}, {"c2.bias", {64}},
+                {"c3.weight", {64, 64, 3, 3}}, {"c3.bias", {64}}, {"l1.weight", {512, 3136}}, {"l1.bias", {512}},
+                {"l2.weight", {(uint64_t)A, 512}}, {"l2.bias", {(uint64_t)A}}};
+    }
+    // Policy::sample's forward: u8 rows (host rows, or device rows inside a DeviceRowsScope) through the batch forward of the update
+    int32_t run_net(uint64_t n, const float* obs) override
+    {
+        BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(ensure_batch((int)n));
+        const uint8_t* d = nullptr;
+        int32_t st = acting_rows(obs, row_bytes(), n, &d);
+        if (st == BDR_OK) { const float* pp[1] = {p}; const uint8_t* rows[1] = {d}; st = trunk_forward(1, pp, rows, (int)n, "sample_conv"); }
+        if (st == BDR_OK) {
+            const float* hp[1] = {head(p)}; const float* xs[1] = {a3[0]}; std::vector<float*>* as[1] = {&a_on};
+            st = mlp_forward(net, 1, hp, xs, as, (int)n, "sample_fwd");
+        }
+        if (st == BDR_OK) {
+            CdqnActArgs a{a_on.back(), net.L.back().Np, A, (int)n, samp, samp_idx};
+            Bracket br(this, "cdqn_act");
+            const hipError_t e = step_launch(stream, false, k_cdqn_act, dim3((unsigned)((n * A + 255) / 256)), dim3(256), a);
+            if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_cdqn_act: %s", hipGetErrorString(e));
+        }
+        if (st == BDR_OK) st = results_to_host(n);
+        if (st == BDR_OK) prof_collect(this);
+        slot_cursor = 0;
+        return st;
+    }
+    int32_t set_act_path(int32_t path) override
+    {
+        BDR_REQUIRE(path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS || path == BDR_ACT_PATH_FUSED, "unknown act path %d", path);
+        BDR_REQUIRE(path != BDR_ACT_PATH_FUSED, "the fused acting kernel runs Mlp networks on f32 rows: the AtariCnn Q-network of this DQN (candle) agent acts "
+                                                "through its layer launches (BDR_ACT_PATH_LAYERS)");
+        return BDR_OK;
+    }
+    int32_t sample_raw(const bdr_obs_norm*, uint64_t, const void*, int32_t, bool, uint64_t, float*, int64_t*) override
+    {
+        return fail(BDR_ERR_INVALID, "bdr_agent_sample_raw takes f32 / f64 rows: the AtariCnn Q-network of this DQN (candle) agent reads u8 frame stacks "
+                                     "(bdr_agent_sample, bdr_agent_sample_device)");
+    }
+
+    // ---- reference <-> internal layouts: the conv layers as iqn.hip has them, l1's input columns (c, h, w) -> (h, w, c) ----
+    void to_internal(const float* ref, float* in) const
+    {
+        std::fill(in, in + arena_floats(), 0.f);
+        const float* q = ref;
+        const int K1 = 64 * conv.ns;
+        for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) in[conv.w1 + (size_t)k * 32 + o] = q[(size_t)o * K1 + k];
+        q += (size_t)32 * K1; std::copy(q, q + 32, in + conv.b1); q += 32;
+        for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
+            in[conv.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o] = q[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw];
+        q += 32768; std::copy(q, q + 64, in + conv.b2); q += 64;
+        for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
+            in[conv.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o] = q[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw];
+        q += 36864; std::copy(q, q + 64, in + conv.b3); q += 64;
+        float* h = in + conv_floats();
+        const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
+        for (int o = 0; o < 512; ++o) for (int j = 0; j < 3136; ++j) h[l1.w + (size_t)((j % 49) * 64 + j / 49) * l1.Np + o] = q[(size_t)o * 3136 + j];
+        q += (size_t)512 * 3136; std::copy(q, q + 512, h + l1.b); q += 512;
+        for (int o = 0; o < A; ++o) for (int k = 0; k < 512; ++k) h[l2.w + (size_t)k * l2.Np + o] = q[(size_t)o * 512 + k];
+        q += (size_t)A * 512; std::copy(q, q + A, h + l2.b);
+    }
+    void to_reference(const float* in, float* ref) const
+    {
+        float* q = ref;
+        const int K1 = 64 * conv.ns;
+        for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) q[(size_t)o * K1 + k] = in[conv.w1 + (size_t)k * 32 + o];
+        q += (size_t)32 * K1; std::copy(in + conv.b1, in + conv.b1 + 32, q); q += 32;
+        for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
+            q[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw] = in[conv.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o];
+        q += 32768; std::copy(in + conv.b2, in + conv.b2 + 64, q); q += 64;
+        for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
+            q[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw] = in[conv.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o];
+        q += 36864; std::copy(in + conv.b3, in + conv.b3 + 64, q); q += 64;
+        const float* h = in + conv_floats();
+        const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
+        for (int o = 0; o < 512; ++o) for (int j = 0; j < 3136; ++j) q[(size_t)o * 3136 + j] = h[l1.w + (size_t)((j % 49) * 64 + j / 49) * l1.Np + o];
+        q += (size_t)512 * 3136; std::copy(h + l1.b, h + l1.b + 512, q); q += 512;
+        for (int o = 0; o < A; ++o) for (int k = 0; k < 512; ++k) q[(size_t)o * 512 + k] = h[l2.w + (size_t)k * l2.Np + o];
+        q += (size_t)A * 512; std::copy(h + l2.b, h + l2.b + A, q);
+    }
+    int32_t get_params(int which, float* out, uint64_t n) override
+    {
+        float* s = slot(which);
+        BDR_REQUIRE(s, "unknown DQN (candle) model %d", which);
+        BDR_REQUIRE(n == ref_count(), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)ref_count());
+        std::vector<float> in(arena_floats());
+        BDR_HIP(hipMemcpyAsync(in.data(), s, in.size() * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        to_reference(in.data(), out);
+        return BDR_OK;
+    }
+    int32_t set_params(int which, const float* inp, uint64_t n) override
+    {
+        float* s = slot(which);
+        BDR_REQUIRE(s, "unknown DQN (candle) model %d", which);
+        BDR_REQUIRE(n == ref_count(), "parameter count mismatch");
+        std::vector<float> in(arena_floats());
+        to_internal(inp, in.data());
+        BDR_HIP(hipMemcpyAsync(s, in.data(), in.size() * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
         return BDR_OK;
     }
 };
@@ -582,9 +912,125 @@ int32_t cdqn_check(const bdr_candle_dqn_config& c)
     return BDR_OK;
 }
 
+// the AtariCnn form's config as the shared one (the Mlp fields stay zero), after the checks of its own fields
+int32_t cdqn_cnn_check(const bdr_candle_dqn_cnn_config& c, bdr_candle_dqn_config* out)
+{
+    BDR_REQUIRE(c.skip_linear == 0, "AtariCnnConfig::skip_linear = true leaves the 3136 features of conv3 as the output: Dqn needs out_dim action values (l1, l2)");
+    BDR_REQUIRE(c.arithmetic == BDR_ARITH_F32_EXACT, "DQN (candle, AtariCnn) computes exact f32 products in conv2 / conv3 (BDR_ARITH_F32_EXACT): the split-operand "
+                                                     "forward (BDR_ARITH_BF16X3_6) is the tch agent's (bdr_dqn_config)");
+    BDR_REQUIRE(c.n_stack >= 1 && c.n_stack <= bdr::C1_MAX_STACK, "AtariCnnConfig::n_stack must be in [1, %d] (conv1's kernels are instantiated per depth), got %d",
+                bdr::C1_MAX_STACK, c.n_stack);
+    bdr_candle_dqn_config d;
+    memset(&d, 0, sizeof d);
+    d.obs_dim = 1; d.n_actions = c.out_dim; d.qnet.n_units = 1; d.qnet.units[0] = 512; d.qnet.activation_out = BDR_ACTIVATION_NONE;
+    d.opt = c.opt; d.lr = c.lr; d.soft_update_interval = c.soft_update_interval; d.n_updates_per_opt = c.n_updates_per_opt; d.batch_size = c.batch_size;
+    d.discount_factor = c.discount_factor; d.tau = c.tau; d.train = c.train; d.double_dqn = c.double_dqn; d.explorer = c.explorer;
+    d.has_clip_reward = c.has_clip_reward; d.has_clip_td_err = c.has_clip_td_err; d.clip_reward = c.clip_reward;
+    d.clip_td_err_min = c.clip_td_err_min; d.clip_td_err_max = c.clip_td_err_max; d.critic_loss = c.critic_loss;
+    d.record_verbose_level = c.record_verbose_level; d.device = c.device; d.ckpt_format = c.ckpt_format; d.seed = c.seed;
+    BDR_TRY(check_opt(c.opt, "qnet"));   // (amsgrad) before the device is looked at, like the other refusals here
+    BDR_REQUIRE(c.batch_size >= 1 && c.batch_size <= 65536, "bad batch size");
+    BDR_REQUIRE(c.device >= 0, "No device is given for DQN agent");
+    BDR_TRY(cdqn_check(d));
+    *out = d;
+    return BDR_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void bdr_candle_dqn_cnn_config_default(bdr_candle_dqn_cnn_config* c)
+{
+    if (!c) return;
+    bdr_candle_dqn_config d;
+    bdr_candle_dqn_config_default(&d);
+    memset(c, 0, sizeof *c);
+    c->n_stack = 4; c->out_dim = 0; c->skip_linear = 0; c->arithmetic = BDR_ARITH_F32_EXACT;   // atari_cnn/config.rs; the arithmetic is this library's
+    c->opt = d.opt; c->lr = d.lr; c->soft_update_interval = d.soft_update_interval; c->n_updates_per_opt = d.n_updates_per_opt; c->batch_size = d.batch_size;
+    c->discount_factor = d.discount_factor; c->tau = d.tau; c->train = d.train; c->double_dqn = d.double_dqn; c->explorer = d.explorer;
+    c->critic_loss = d.critic_loss; c->record_verbose_level = d.record_verbose_level; c->device = d.device; c->ckpt_format = d.ckpt_format;
+}
+
+int32_t bdr_candle_dqn_cnn_create(const bdr_candle_dqn_cnn_config* cfg, bdr_agent** out)
+{
+    BDR_REQUIRE(cfg && out, "null argument");
+    bdr_candle_dqn_config c;
+    BDR_TRY(cdqn_cnn_check(*cfg, &c));
+    BDR_TRY(ensure_device(c.device));
+    CandleDqnCnn* a = new CandleDqnCnn();
+    a->ccfg = *cfg; a->cfg = c; a->device = c.device; a->train = c.train != 0; a->ckpt_format = c.ckpt_format;
+    a->O = 0; a->A = c.n_actions;
+    a->conv = make_arena(1, cfg->n_stack);
+    const int units[1] = {512};
+    a->net = make_mlp(3136, units, 1, c.n_actions, false);
+    Explorer& x = a->explorer;
+    x.kind = c.explorer.kind; x.eps_start = c.explorer.eps_start; x.eps_final = c.explorer.eps_final; x.final_step = c.explorer.final_step;
+    x.n_calls = c.explorer.n_calls;
+    a->rng.seed_from_u64(c.explorer.seed);
+    const int32_t st = [&]() -> int32_t {
+        BDR_HIP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
+        BDR_TRY(a->err_init());
+        for (auto q : {&a->p, &a->p_tgt, &a->g, &a->m, &a->v}) BDR_TRY(a->alloc(q, a->arena_floats(), CandleDqn::AGENT));
+        BDR_TRY(a->alloc(&a->scal, 8, CandleDqn::AGENT));
+        BDR_TRY(a->alloc(&a->applied, 1, CandleDqn::AGENT));
+        // the library's own seeded initialiser, uniform(+-1/sqrt(fan_in)) per layer (tests set parameters)
+        std::vector<float> ref(a->ref_count(), 0.f);
+        const int fan[5] = {64 * cfg->n_stack, 512, 576, 3136, 512}, outs[5] = {32, 64, 64, 512, c.n_actions};
+        float* q = ref.data();
+        for (int l = 0; l < 5; ++l) {
+            const int u[1] = {1};
+            const MlpLayout one = make_mlp(fan[l], u, 0, outs[l], false);
+            mlp_init_reference(one, c.seed * 7 + 1 + (uint64_t)l, q);
+            q += one.ref_total;
+        }
+        BDR_TRY(a->set_params(0, ref.data(), ref.size()));
+        BDR_TRY(a->set_params(1, ref.data(), ref.size()));   // track(qnet_tgt, qnet, 1.0) (dqn/base.rs:251)
+        return a->ensure_batch((int)c.batch_size);
+    }();
+    if (st != BDR_OK) { delete a; return st; }
+    *out = a;
+    return BDR_OK;
+}
+
+int32_t bdr_candle_dqn_cnn_update_on_batch(bdr_agent* base, uint64_t n, const uint8_t* obs, const int64_t* act, const uint8_t* next_obs, const float* reward,
+                                           const int8_t* term, const int8_t* /*is_truncated: read by nothing, dqn/base.rs:62*/, bdr_dqn_record* rec)
+{
+    BDR_REQUIRE(base && obs && act && next_obs && reward && term, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn") && static_cast<CandleDqn*>(base)->cnn_form(), "not a DQN (candle) agent with the AtariCnn Q-network");
+    CandleDqnCnn* a = static_cast<CandleDqnCnn*>(base);
+    BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+    BDR_HIP(hipSetDevice(a->device));
+    BDR_TRY(a->ensure_batch((int)n));
+    const size_t rb = a->row_bytes();
+    if (n > a->u_cap8) {
+        BDR_HIP(hipStreamSynchronize(a->stream));
+        a->release(CandleDqn::STAGING);
+        a->u_cap8 = 0;
+        BDR_TRY(a->alloc(&a->u_obs8, n * rb, CandleDqn::STAGING, false)); BDR_TRY(a->alloc(&a->u_next8, n * rb, CandleDqn::STAGING, false));
+        BDR_TRY(a->alloc(&a->u_act, n, CandleDqn::STAGING, false)); BDR_TRY(a->alloc(&a->u_rew, n, CandleDqn::STAGING, false));
+        BDR_TRY(a->alloc(&a->u_term, round_up(n, 16), CandleDqn::STAGING, false));
+        a->u_cap8 = n;
+    }
+    BDR_HIP(hipMemcpyAsync(a->u_obs8, obs, n * rb, hipMemcpyHostToDevice, a->stream));
+    BDR_HIP(hipMemcpyAsync(a->u_next8, next_obs, n * rb, hipMemcpyHostToDevice, a->stream));
+    BDR_HIP(hipMemcpyAsync(a->u_act, act, n * 8, hipMemcpyHostToDevice, a->stream));
+    BDR_HIP(hipMemcpyAsync(a->u_rew, reward, n * 4, hipMemcpyHostToDevice, a->stream));
+    BDR_HIP(hipMemcpyAsync(a->u_term, term, n, hipMemcpyHostToDevice, a->stream));
+    const bool track = a->opt_tracks();
+    BDR_TRY(a->update_cnn((int)n, a->u_obs8, reinterpret_cast<const uint8_t*>(a->u_act), 8, a->u_next8, a->u_rew, a->u_term, track));
+    a->n_opts += 1;
+    prof_collect(a);
+    float r5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    BDR_HIP(hipMemcpyAsync(r5, a->scal, sizeof r5, hipMemcpyDeviceToHost, a->stream));
+    BDR_HIP(hipStreamSynchronize(a->stream));
+    BDR_TRY(a->settle());
+    if (rec) {
+        rec->loss = r5[0]; rec->has_verbose = a->verbose() ? 1 : 0;
+        if (a->verbose()) { rec->pred_mean = r5[1]; rec->reward_mean = r5[2]; rec->tgt_mean = r5[3]; rec->tgt_minus_pred_mean = r5[4]; }
+    }
+    return a->err_check();
+}
 
 void bdr_candle_dqn_config_default(bdr_candle_dqn_config* c)
 {
@@ -642,6 +1088,7 @@ int32_t bdr_candle_dqn_update_on_batch(bdr_agent* base, uint64_t n, const float*
     BDR_REQUIRE(base && obs && act && next_obs && reward && term, "null argument");
     BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn"), "not a DQN (candle) agent");
     CandleDqn* a = static_cast<CandleDqn*>(base);
+    BDR_REQUIRE(!a->cnn_form(), "this DQN (candle) agent has the AtariCnn Q-network: its rows are u8 (bdr_candle_dqn_cnn_update_on_batch)");
     BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
     BDR_HIP(hipSetDevice(a->device));
     BDR_TRY(a->ensure_batch((int)n));

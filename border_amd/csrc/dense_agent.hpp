@@ -136,11 +136,13 @@ struct DenseAgent : bdr_agent {
     // layer for all nz), every weight gradient in one grouped launch, then the fused reduce + Adam (+ tracking into tgt at rate tau).
     // poison (optional): a device word that, when non-zero, makes the reduce + Adam launch leave everything alone (the candle DQN's
     // out-of-range action flag); applied / step: *applied = step by a launch that was not skipped.
+    // dx0 / mask0 (optional): one more input-gradient launch below layer 0, d(x0) of network z into dx0[z] ([Bn][Kp of layer 0]),
+    // zero where mask0[z] - the post-ReLU activation that produced x0 - is not positive (the candle DQN's conv trunk feeds layer 0).
     int32_t mlp_backward_step(const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
                               const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
                               const std::vector<size_t>& off, const AdamScalars* sc, int Bn, const StepNames& names, size_t total, double tau, int lo,
                               const DenseReduceSeg* extra = nullptr, const unsigned* poison = nullptr, unsigned long long* applied = nullptr,
-                              unsigned long long step = 0)
+                              unsigned long long step = 0, float* const* dx0 = nullptr, const float* const* mask0 = nullptr)
     {
         const int L = (int)net.L.size();
         for (int l = lo; l >= 1; --l) {
@@ -148,6 +150,12 @@ struct DenseAgent : bdr_agent {
             for (int z = 0; z < nz; ++z) { pb[z] = p[z]; dy[z] = (*dys[z])[l]; dx[z] = (*dys[z])[l - 1]; mask[z] = (*acts[z])[l - 1]; }
             Bracket br(this, names.dx);
             BDR_TRY(dense_dx_z(stream, net.L[l], nz, pb, dy, dx, mask, Bn, true));
+        }
+        if (dx0) {
+            const float* pb[4]; const float* dy[4];
+            for (int z = 0; z < nz; ++z) { pb[z] = p[z]; dy[z] = (*dys[z])[0]; }
+            Bracket br(this, names.dx);
+            BDR_TRY(dense_dx_z(stream, net.L[0], nz, pb, dy, dx0, mask0, Bn, true));
         }
         std::vector<DenseDwJob> jobs;
         const int c = chunks_for(Bn);

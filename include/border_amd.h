@@ -1100,7 +1100,7 @@ BDR_API int32_t bdr_bc_sample_device(bdr_agent* a, uint64_t n, const void* obs_d
  * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)
  * Not the bdr_dqn_* agent above, which restates border-tch-agent/src/dqn.  Q-network = Mlp (mlp/base.rs, mlp.rs:14-24): ReLU after
  * every layer but the last, activation_out after the last; variables mlp.ln{i}.weight [out][in] / .bias.  The AtariCnn Q-network of
- * the candle crate is not built here.
+ * the candle crate (atari_cnn/base.rs) is the second form of this agent: bdr_candle_dqn_cnn_config below.
  * ---------------------------------------------------------------------------------------- */
 /* DqnConfig (dqn/config.rs:25-47; defaults :75-102) with DqnModelConfig (dqn/model.rs:20-39: q_config, opt_config) plus obs_dim,
  * n_actions and record_verbose_level's integer.  clip_reward and clip_td_err are carried and unused: nothing in dqn/base.rs reads
@@ -1154,6 +1154,52 @@ BDR_API int32_t bdr_candle_dqn_update_on_batch(bdr_agent* a, uint64_t n, const f
  *   2 y      the argmax index as a float (:103, :108)  3 tgt   the TD target (:113)
  *   4 dpred  dLoss / dpred, 1/B included (the gradient of the output itself: an output ReLU's mask is applied behind it) */
 BDR_API int32_t bdr_candle_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* ---- the same agent with the candle crate's AtariCnn Q-network (border-candle-agent/src/atari_cnn/base.rs:31-45) ----
+ * conv1 8x8/4 (n_stack -> 32), conv2 4x4/2 (-> 64), conv3 3x3/1 (-> 64), ReLU after each, flatten (c, h, w), l1 3136 -> 512, ReLU,
+ * l2 512 -> out_dim.  Observation rows are u8, 84 * 84 * n_stack bytes ([n_stack][84][84]; the reference's [B, n_stack, 1, 84, 84]
+ * squeezed), scaled by 1/255 inside conv1.  Variables at the root of qnet.pt / qnet_tgt.pt: c1.weight [32][n_stack][8][8], c1.bias,
+ * c2.weight [64][32][4][4], c2.bias, c3.weight [64][64][3][3], c3.bias, l1.weight [512][3136], l1.bias, l2.weight [out_dim][512],
+ * l2.bias - also the order of the parameter models (0 qnet, 1 qnet_tgt, 2 exp_avg, 3 exp_avg_sq, 4 gradient; +100 / +200 / +300).
+ * The fields are those of bdr_candle_dqn_config with AtariCnnConfig's n_stack / out_dim / skip_linear in place of obs_dim / qnet.
+ * skip_linear != 0 is refused (Dqn needs out_dim action values).  arithmetic: BDR_ARITH_F32_EXACT only (conv1 on the bf16 MFMA with
+ * exact u8 operands, every other product f32 x f32); BDR_ARITH_BF16X3_6 is refused - the split-operand forward belongs to the tch
+ * agent.  Everything said about bdr_candle_dqn_config's agent holds: update order, records, explorers on the SmallRng, the
+ * out-of-range action rule (no parameter of the update steps, conv layers included), checkpoints.  bdr_agent_opt reads a u8 ring
+ * (obs_bytes = 84 * 84 * n_stack, act_bytes = 8; a frame-stack store is accepted); an f32 ring, another row size, another device or
+ * a prioritized ring returns BDR_ERR_INVALID.  bdr_agent_sample / _qvalues take u8 host rows, the _device forms rows such as
+ * bdr_atari_prep_device_stacks'; BDR_ACT_PATH_FUSED and bdr_agent_sample_raw return BDR_ERR_INVALID for this network. */
+typedef struct {
+    int32_t n_stack;                /* AtariCnnConfig.n_stack: 1 ... 8 */
+    int32_t out_dim;                /* AtariCnnConfig.out_dim = the number of actions */
+    int32_t skip_linear;            /* AtariCnnConfig.skip_linear: must be 0 */
+    int32_t arithmetic;             /* BDR_ARITH_F32_EXACT */
+    bdr_adamw_config opt;           /* DqnModelConfig.opt_config */
+    double lr;
+    uint64_t soft_update_interval;  /* 1 */
+    uint64_t n_updates_per_opt;     /* 1 */
+    uint64_t batch_size;            /* 1 */
+    double discount_factor;         /* 0.99, used as f32 */
+    double tau;                     /* 0.005 */
+    int32_t train;                  /* false */
+    int32_t double_dqn;             /* false */
+    bdr_explorer_config explorer;   /* Softmax; seed 42 */
+    int32_t has_clip_reward;        /* carried, unused */
+    int32_t has_clip_td_err;        /* carried, unused */
+    double clip_reward;
+    double clip_td_err_min, clip_td_err_max;
+    int32_t critic_loss;            /* BDR_LOSS_* (Mse) */
+    int32_t record_verbose_level;   /* 0 */
+    int32_t device;                 /* -1: none given */
+    int32_t ckpt_format;            /* BDR_CKPT_TCH: qnet.pt / qnet_tgt.pt (safetensors); BDR_CKPT_SAFETENSORS: *.safetensors */
+    uint64_t seed;                  /* the library's parameter initialiser */
+} bdr_candle_dqn_cnn_config;
+BDR_API void bdr_candle_dqn_cnn_config_default(bdr_candle_dqn_cnn_config* cfg);   /* n_stack 4, out_dim 0, F32_EXACT; the rest as bdr_candle_dqn_config_default */
+BDR_API int32_t bdr_candle_dqn_cnn_create(const bdr_candle_dqn_cnn_config* cfg, bdr_agent** out);
+/* bdr_candle_dqn_update_on_batch for this form: obs / next_obs are u8 rows [n][84 * 84 * n_stack].  bdr_candle_dqn_probe serves both
+ * forms; bdr_candle_dqn_update_on_batch (f32 rows) returns BDR_ERR_INVALID on this one and this call on the Mlp form. */
+BDR_API int32_t bdr_candle_dqn_cnn_update_on_batch(bdr_agent* a, uint64_t n, const uint8_t* obs, const int64_t* act, const uint8_t* next_obs,
+                                                   const float* reward, const int8_t* is_terminated, const int8_t* is_truncated,
+                                                   bdr_dqn_record* rec);
 /* Policy::sample (dqn/base.rs:202-230) goes through bdr_agent_sample / _sample_device / _sample_raw (idx_out) and the action values
  * through bdr_agent_qvalues / _qvalues_device.  The exploration stream of this kind is the reference's SmallRng (xoshiro256++ seeded
  * by rand_core's seed_from_u64; DESIGN.md 17 states the rules, which nothing here can pin against rand itself):

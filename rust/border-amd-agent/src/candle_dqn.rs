@@ -130,6 +130,22 @@ where
     }
 }
 
+impl<E, O, A> AmdCandleDqn<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    /// `Dqn<E, AtariCnn, R>::build` of border-candle-agent (the network of `examples/atari/dqn_atari`): conv1-conv3, l1, l2 on u8
+    /// frame stacks.  Everything else - `opt`, `sample`, the records, `qnet.pt` / `qnet_tgt.pt` - is this type's, unchanged.
+    pub fn build_atari_cnn(config: crate::config::CandleDqnAtariCnnConfig) -> Self {
+        let c = config.to_c().expect("CandleDqnAtariCnnConfig");
+        let mut h = std::ptr::null_mut();
+        expect(unsafe { ffi::bdr_candle_dqn_cnn_create(&c, &mut h) }, "Dqn::build");
+        Self { a: AgentHandle::new(h), train: config.dqn.train, n_actions: c.out_dim as usize, phantom: PhantomData }
+    }
+}
+
 impl<E, O, A> Agent<E, AmdReplayBuffer<O, A>> for AmdCandleDqn<E, O, A>
 where
     E: Env + 'static,

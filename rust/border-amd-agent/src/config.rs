@@ -1673,3 +1673,64 @@ impl CandleDqnConfig {
         Ok(c)
     }
 }
+
+/// `dqn::DqnConfig<AtariCnn>` of border-candle-agent: the fields of [`CandleDqnConfig`] (`dqn`; its `model_config.q_config` is not
+/// read, its `model_config.opt_config` is) with `atari_cnn::AtariCnnConfig` (`atari_cnn/config.rs`: `n_stack`, `out_dim`,
+/// `skip_linear`) as the Q-network.  `skip_linear = true` is refused by the library: `Dqn` needs `out_dim` action values.
+/// Observation rows are u8 frame stacks of `84 * 84 * n_stack` bytes; checkpoints hold `c1.weight ... l2.bias`.
+#[derive(Debug, Deserialize, Serialize, PartialEq, Clone)]
+pub struct CandleDqnAtariCnnConfig {
+    pub n_stack: i64,
+    pub out_dim: i64,
+    #[serde(default)]
+    pub skip_linear: bool,
+    pub dqn: CandleDqnConfig,
+}
+
+impl Default for CandleDqnAtariCnnConfig {
+    fn default() -> Self {
+        Self { n_stack: 4, out_dim: 0, skip_linear: false, dqn: Default::default() }
+    }
+}
+
+impl CandleDqnAtariCnnConfig {
+    setter!(n_stack, i64);
+    setter!(out_dim, i64);
+    setter!(skip_linear, bool);
+    setter!(dqn, CandleDqnConfig);
+    yaml_io!();
+
+    pub(crate) fn to_c(&self) -> Result<ffi::bdr_candle_dqn_cnn_config> {
+        let mut c: ffi::bdr_candle_dqn_cnn_config = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_dqn_cnn_config_default(&mut c) };
+        let d = &self.dqn;
+        c.n_stack = self.n_stack as i32;
+        c.out_dim = self.out_dim as i32;
+        c.skip_linear = self.skip_linear as i32;
+        c.lr = d.model_config.opt_config.lr();
+        d.model_config.opt_config.fill(&mut c.opt);
+        c.soft_update_interval = d.soft_update_interval as u64;
+        c.n_updates_per_opt = d.n_updates_per_opt as u64;
+        c.batch_size = d.batch_size as u64;
+        c.discount_factor = d.discount_factor;
+        c.tau = d.tau;
+        c.train = d.train as i32;
+        c.double_dqn = d.double_dqn as i32;
+        c.explorer = d.explorer.to_c(d.rng_seed);
+        if let Some(v) = d.clip_reward {
+            c.has_clip_reward = 1;
+            c.clip_reward = v;
+        }
+        if let Some((lo, hi)) = d.clip_td_err {
+            c.has_clip_td_err = 1;
+            c.clip_td_err_min = lo;
+            c.clip_td_err_max = hi;
+        }
+        c.critic_loss = d.critic_loss.code();
+        c.record_verbose_level = d.record_verbose_level as i32;
+        c.ckpt_format = if d.safetensors_ext { ffi::BDR_CKPT_SAFETENSORS } else { ffi::BDR_CKPT_TCH };
+        c.seed = d.engine_seed;
+        c.device = Device::ordinal(&d.device, "DQN");
+        Ok(c)
+    }
+}

@@ -682,6 +682,37 @@ pub struct bdr_candle_dqn_config {
     pub seed: u64,
 }
 
+/// The same agent with the candle crate's AtariCnn Q-network (atari_cnn/base.rs): AtariCnnConfig's n_stack / out_dim / skip_linear
+/// in place of obs_dim / qnet, plus the library's `arithmetic` (BDR_ARITH_F32_EXACT only)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bdr_candle_dqn_cnn_config {
+    pub n_stack: i32,
+    pub out_dim: i32,
+    pub skip_linear: i32,
+    pub arithmetic: i32,
+    pub opt: bdr_adamw_config,
+    pub lr: f64,
+    pub soft_update_interval: u64,
+    pub n_updates_per_opt: u64,
+    pub batch_size: u64,
+    pub discount_factor: f64,
+    pub tau: f64,
+    pub train: i32,
+    pub double_dqn: i32,
+    pub explorer: bdr_explorer_config,
+    pub has_clip_reward: i32,
+    pub has_clip_td_err: i32,
+    pub clip_reward: f64,
+    pub clip_td_err_min: f64,
+    pub clip_td_err_max: f64,
+    pub critic_loss: i32,
+    pub record_verbose_level: i32,
+    pub device: i32,
+    pub ckpt_format: i32,
+    pub seed: u64,
+}
+
 #[link(name = "border_amd")]
 extern "C" {
     pub fn bdr_last_error() -> *const c_char;
@@ -1051,6 +1082,19 @@ extern "C" {
         rec: *mut bdr_dqn_record,
     ) -> i32;
     pub fn bdr_candle_dqn_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
+    pub fn bdr_candle_dqn_cnn_config_default(cfg: *mut bdr_candle_dqn_cnn_config);
+    pub fn bdr_candle_dqn_cnn_create(cfg: *const bdr_candle_dqn_cnn_config, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_candle_dqn_cnn_update_on_batch(
+        a: *mut bdr_agent,
+        n: u64,
+        obs: *const u8,
+        act: *const i64,
+        next_obs: *const u8,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+        rec: *mut bdr_dqn_record,
+    ) -> i32;
 
     // ---- BC (border-candle-agent/src/bc)
     pub fn bdr_bc_config_default(cfg: *mut bdr_bc_config);

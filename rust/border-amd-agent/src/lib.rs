@@ -52,7 +52,7 @@ pub use comm::Comm;
 pub use config::{
     ActionLimit, Activation, CandleMlpConfig, CandleOptimizerConfig, GaussianActorConfig, MultiCriticConfig, ValueConfig,
     ActorConfig, AtariCnnConfig, CriticConfig, CriticLoss, Device, DqnConfig, DqnExplorer, DqnModelConfig, EntCoefMode, EpsilonGreedy,
-    ActorKind, Arithmetic, AwacConfig, CandleDqnConfig, CandleDqnModelConfig, CandleSacConfig, BcActionType, BcConfig, BcKernelForm, BcModelConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
+    ActorKind, Arithmetic, AwacConfig, CandleDqnAtariCnnConfig, CandleDqnConfig, CandleDqnModelConfig, CandleSacConfig, BcActionType, BcConfig, BcKernelForm, BcModelConfig, IqlConfig, IqnConfig, IqnExplorer, IqnModelConfig, IqnSample, MlpConfig, OptimizerConfig, QNetConfig, SacConfig, Softmax,
 };
 pub use awac::AmdAwac;
 pub use bc::AmdBc;

@@ -7,6 +7,11 @@ device, for comparison.  Prints ONE JSON line and writes it to profiles/bench_ca
   No speed threshold is set here: the figures go to README.md and DESIGN.md 17.
 
   python tools/bench_candle_dqn.py --steps 300 --warmup 30 [--double-dqn]
+
+--cnn: the AtariCnn form at the shape of examples/atari/dqn_atari (n_stack 4, 6 actions, B = 32; --batch 256 is the C2 batch) over a
+u8 ring, against the tch Dqn CNN agent built with arithmetic = "f32_exact" (the same products), legs alternating in the same
+process; writes profiles/bench_candle_dqn_cnn.json (B = 32) or profiles/bench_candle_dqn_cnn_b256.json.  --no-tch runs the candle
+agent alone (the kernel-trace run).
 """
 from __future__ import annotations
 
@@ -30,6 +35,16 @@ def ring(B, n=50_000):
     rb = B.SimpleReplayBuffer(B.SimpleReplayBufferConfig(capacity=n, seed=42), (O,), np.float32, (1,), np.int64)
     rb.push(rng.standard_normal((n, O)).astype(np.float32), rng.integers(0, A, (n, 1)).astype(np.int64),
             rng.standard_normal((n, O)).astype(np.float32), rng.standard_normal(n).astype(np.float32),
+            (rng.random(n) < 0.01).astype(np.int8), np.zeros(n, np.int8))
+    return rb
+
+
+def ring_u8(B, n_stack, n=2048):
+    rng = np.random.default_rng(0)
+    w = 84 * 84 * n_stack
+    rb = B.SimpleReplayBuffer(B.SimpleReplayBufferConfig(capacity=n, seed=42), (w,), np.uint8, (1,), np.int64)
+    rb.push(rng.integers(0, 256, (n, w), dtype=np.uint8), rng.integers(0, 6, (n, 1)).astype(np.int64),
+            rng.integers(0, 256, (n, w), dtype=np.uint8), rng.standard_normal(n).astype(np.float32),
             (rng.random(n) < 0.01).astype(np.int8), np.zeros(n, np.int8))
     return rb
 
@@ -76,8 +91,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--legs", type=int, default=5)
     ap.add_argument("--double-dqn", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_candle_dqn.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--cnn", action="store_true")
+    ap.add_argument("--batch", type=int, default=32, help="--cnn: 32 (dqn_atari) or 256 (the C2 batch)")
+    ap.add_argument("--no-tch", action="store_true")
     args = ap.parse_args()
+    if args.out is None:
+        stem = "bench_candle_dqn" if not args.cnn else "bench_candle_dqn_cnn" + ("" if args.batch == 32 else f"_b{args.batch}")
+        args.out = os.path.join(ROOT, "profiles", stem + ".json")
+    if args.cnn:
+        return main_cnn(args)
 
     import border_amd as B
     import candle_dqn_restatement as R
@@ -111,6 +134,46 @@ def main():
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         f.write(line + "\n")
+    print(line)
+
+
+def main_cnn(args):
+    import border_amd as B
+    import candle_dqn_cnn_restatement as RC
+    NS, NA = 4, 6
+    spec = RC.CandleDqnCnnSpec(NS, NA, lr=1e-3, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01), double_dqn=args.double_dqn)
+    pairs = [("candle_dqn_cnn", B.CandleDqn.build(spec.to_config(B, args.batch, device=0, seed=1)), ring_u8(B, NS))]
+    if not args.no_tch:
+        tch = B.Dqn.build(B.DqnConfig(model_config=B.DqnModelConfig(B.AtariCnnConfig(NS, NA), B.OptimizerConfig.AdamW(1e-3, wd=0.01)),
+                                      batch_size=args.batch, double_dqn=args.double_dqn, device=0, param_seed=1, arithmetic="f32_exact"))
+        pairs.append(("tch_dqn_cnn_f32_exact", tch, ring_u8(B, NS)))
+    res = {}
+    for name, agent, rb in pairs:
+        res[name] = {"value": round(window(agent, rb, args.warmup, args.steps), 1), "legs": []}
+    for _ in range(args.legs):
+        for name, agent, rb in pairs:
+            res[name]["legs"].append(leg(agent, rb))
+    for name, agent, rb in pairs:
+        r, legs = res[name], sorted(res[name]["legs"])
+        r["ms_per_update"] = round(1e3 / r["value"], 4)
+        r["steady_legs_updates_per_s"] = [round(x, 1) for x in r.pop("legs")]
+        if legs:
+            r["steady_median"] = round(legs[len(legs) // 2], 1)
+            r["steady_spread_pct"] = round(100.0 * (legs[-1] - legs[0]) / legs[len(legs) // 2], 2)
+        if name == "candle_dqn_cnn":
+            r.update(launches(agent, rb))
+    for _, agent, rb in pairs:
+        agent.close(); rb.close()
+    out = {"metric": "dqn_atari_candle_updates_per_s", "shape": {"n_stack": NS, "n_actions": NA, "batch": args.batch, "opt": "AdamW", "loss": "Mse",
+                                                                  "double_dqn": bool(args.double_dqn)},
+           "warmup": args.warmup, "steps": args.steps, "value": res["candle_dqn_cnn"]["value"], **res}
+    if not args.no_tch:
+        out["candle_over_tch_steady_median"] = round(res["candle_dqn_cnn"]["steady_median"] / res["tch_dqn_cnn_f32_exact"]["steady_median"], 4)
+    line = json.dumps(out)
+    if not args.no_tch:
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
     print(line)
 
 
