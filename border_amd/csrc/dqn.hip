@@ -24,6 +24,7 @@
 #include "conv1_bf16_img.hpp"
 #include "cnn_layers.hpp"
 #include "igemm_b3.hpp"
+#include "fwd_c23_b3.hpp"
 #include "act_small.hpp"
 #include "dqn_rollback.hpp"
 
@@ -74,50 +75,17 @@ namespace {
 #define BDR_FWDC3_SHAPE 1, 2, 1, 1
 #endif
 using FwdC3D = FwdConvP<GeomC3, BDR_FWDC3_SHAPE>;
-constexpr size_t PL2_U16 = (size_t)3 * 64 * 512, PL3_U16 = (size_t)3 * 64 * 576;   // W2's / W3's three planes
-// One parameter set's planes: W2 then W3, each [3 planes][K / 32][64 cout][32 k]: the B tile of k-tile kt (64 columns x 32 k of one plane) is
-// 4 KB contiguous, so a wave of staging threads (16 columns x four 16-byte chunks) fetches 1 KB in one piece.  Measured against [cout][K] rows
-// (+0.8 % on the step) and [K / 8][cout][8] (-1.8 %); k_reduce_adam's 32 consecutive cout of one k land 64 bytes apart.
-constexpr size_t CPL_W2 = 0, CPL_W3 = PL2_U16, CPL_U16 = PL2_U16 + PL3_U16;
-__device__ __forceinline__ size_t cpl_index(int k, int n) { return ((size_t)(k >> 5) * 64 + n) * 32 + (k & 31); }
-
-// element e = k * 64 + n of W2 (layer 0) or W3 (layer 1) -> its three bf16 terms
-__device__ __forceinline__ void conv_plane_store(uint16_t* __restrict__ pl, int layer, int e, float x)
-{
-    uint16_t v[3];
-    split3_rn(x, v);                                            // (igemm_b3.hpp: round-to-nearest terms, exact sum)
-    const size_t n = (size_t)(layer ? 576 : 512) * 64, o = cpl_index(e >> 6, e & 63);
-    uint16_t* d = pl + (layer ? CPL_W3 : CPL_W2);
-    d[o] = v[0]; d[n + o] = v[1]; d[2 * n + o] = v[2];
-}
-
-// the planes of one parameter set from its f32 weights (every writer of conv parameters other than k_reduce_adam leaves them stale:
-// DqnCnn::cpl_fresh; the forward re-splits before it reads them)
-__global__ __launch_bounds__(256) void k_conv_planes(const float* __restrict__ w2, const float* __restrict__ w3, uint16_t* __restrict__ pl)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 512 * 64) conv_plane_store(pl, 0, i, w2[i]);
-    else if (i < 512 * 64 + 576 * 64) conv_plane_store(pl, 1, i - 512 * 64, w3[i - 512 * 64]);
-}
-// conv2 / conv3 forward on the bf16 matrix cores with split operands (igemm_b3.hpp, six of the nine partial products): the A rows are the
-// f32 activations, split on their way into LDS; the weights are read from bf16 planes kept beside each parameter set (cpl_index)
-#ifndef BDR_FWDC2_B3_SHAPE
-#define BDR_FWDC2_B3_SHAPE 2, 2
+// conv2 + conv3 forward of the split-arithmetic step (fwd_c23_b3.hpp).  0 = one k_igemm_b3 launch per layer.  1 = one fused per-image launch (a1 and
+// a2 staged and split once per image, a2 handed to conv3 through LDS) for every forward on the agent's OWN queue: the online network of an update, which
+// runs alone on the chip behind the CONV23 join - a microsecond saved there is a microsecond off the step - and acting / qvalues / update_on_batch.  A forward
+// launched on another queue (the target network beside the previous update's backward) keeps the two launches: a fused workgroup holds 137 KB of LDS, so
+// nothing else that stages through LDS fits on its CU while it runs, and the backward kernels beside it lose what the forward gains (measured:
+// profiles/ab_fused_conv23.txt, variant C).  2 = the fused launch on every queue (that variant).  Same bits in all three
+// (tests/test_gpu_dqn_fused_conv23.py); the two launches also run while the per-kernel profile is enabled, whose fwd_conv2 / fwd_conv3 rows carry their
+// own work models.
+#ifndef BDR_FUSED_CONV23
+#define BDR_FUSED_CONV23 1
 #endif
-#ifndef BDR_FWDC3_B3_SHAPE
-#define BDR_FWDC3_B3_SHAPE 2, 2
-#endif
-struct FwdB3Args : FwdArgs { const uint16_t* wpl[MAXZ]; };
-template <class G, int WM_, int WN_, int TM_ = 1, int TN_ = 1>
-struct FwdB3 : FwdP<G, AFwd<G>, WM_, WN_, false, 0, TM_, TN_> {
-    using Args = FwdB3Args;
-    __device__ static const uint4* b_chunk(const Args& a, int z, int, int pl, int kt, int n, int kq)
-    {
-        return reinterpret_cast<const uint4*>(a.wpl[z] + (size_t)pl * G::COUT * G::K + cpl_index(kt * 32 + kq * 8, n));
-    }
-};
-using FwdC2B3 = FwdB3<GeomC2, BDR_FWDC2_B3_SHAPE>;
-using FwdC3B3 = FwdB3<GeomC3, BDR_FWDC3_B3_SHAPE>;
 constexpr int TEAMS_FWD_C2 = BDR_TEAMS_FWD_C2, TEAMS_FWD_C3 = BDR_TEAMS_FWD_C3, TEAMS_FWD_L1 = BDR_TEAMS_FWD_L1, TEAMS_DX_L1 = BDR_TEAMS_DX_L1,
               TEAMS_DX_C3 = BDR_TEAMS_DX_C3, TEAMS_DX_C2 = BDR_TEAMS_DX_C2;
 
@@ -701,20 +669,31 @@ int32_t forward(DqnCnn* a, const NetInst* inst, int nz, int B, const TdArgs* td 
         BDR_HIP(hipGetLastError());
         a->cpl_fresh[set] = true;
     }
-    if (b3) {
-        static_cast<FwdArgs&>(fb) = f;
-        for (int z = 0; z < nz; ++z) fb.wpl[z] = a->cpl[inst[z].params == a->q ? 0 : 1] + CPL_W2;
-        Bracket br(a, "fwd_conv2");
-        BDR_HIP((launch_igemm_b3<FwdC2B3, 6>(st, dim3(m_tiles<FwdC2B3>(f.M) * n_tiles<FwdC2B3>(), 1, nz), fb)));
-    } else { Bracket br(a, "fwd_conv2"); BDR_HIP((launch_igemm<FwdC2, TEAMS_FWD_C2>(st, dim3(m_tiles<FwdC2>(f.M) * n_tiles<FwdC2>(), 1, nz), f))); }
-    f.M = B * 49;
-    for (int z = 0; z < nz; ++z) { f.x[z] = a->a2[inst[z].slot]; f.w[z] = inst[z].params + ar.w3; f.bias[z] = inst[z].params + ar.b3; f.out[z] = a->a3[inst[z].slot]; }
-    if (b3) {
-        static_cast<FwdArgs&>(fb) = f;
-        for (int z = 0; z < nz; ++z) fb.wpl[z] = a->cpl[inst[z].params == a->q ? 0 : 1] + CPL_W3;
-        Bracket br(a, "fwd_conv3");
-        BDR_HIP((launch_igemm_b3<FwdC3B3, 6>(st, dim3(m_tiles<FwdC3B3>(f.M) * n_tiles<FwdC3B3>(), 1, nz), fb)));
-    } else { Bracket br(a, "fwd_conv3"); BDR_HIP((launch_igemm<FwdC3D, TEAMS_FWD_C3>(st, dim3(m_tiles<FwdC3D>(f.M) * n_tiles<FwdC3D>(), 1, nz), f))); }
+    if (b3 && BDR_FUSED_CONV23 != 0 && !a->prof && (BDR_FUSED_CONV23 == 2 || st == a->stream)) {
+        // one launch for the pair (fwd_c23_b3.hpp), behind the same gate and the same plane refresh as conv2 alone
+        FwdC23Args c{};
+        for (int z = 0; z < nz; ++z) {
+            c.a1[z] = a->a1[inst[z].slot]; c.cpl[z] = a->cpl[inst[z].params == a->q ? 0 : 1];
+            c.b2[z] = inst[z].params + ar.b2; c.b3[z] = inst[z].params + ar.b3;
+            c.a2[z] = a->a2[inst[z].slot]; c.a3[z] = a->a3[inst[z].slot];
+        }
+        BDR_HIP(launch_fwd_c23_b3(st, B, nz, c));
+    } else {
+        if (b3) {
+            static_cast<FwdArgs&>(fb) = f;
+            for (int z = 0; z < nz; ++z) fb.wpl[z] = a->cpl[inst[z].params == a->q ? 0 : 1] + CPL_W2;
+            Bracket br(a, "fwd_conv2");
+            BDR_HIP((launch_igemm_b3<FwdC2B3, 6>(st, dim3(m_tiles<FwdC2B3>(f.M) * n_tiles<FwdC2B3>(), 1, nz), fb)));
+        } else { Bracket br(a, "fwd_conv2"); BDR_HIP((launch_igemm<FwdC2, TEAMS_FWD_C2>(st, dim3(m_tiles<FwdC2>(f.M) * n_tiles<FwdC2>(), 1, nz), f))); }
+        f.M = B * 49;
+        for (int z = 0; z < nz; ++z) { f.x[z] = a->a2[inst[z].slot]; f.w[z] = inst[z].params + ar.w3; f.bias[z] = inst[z].params + ar.b3; f.out[z] = a->a3[inst[z].slot]; }
+        if (b3) {
+            static_cast<FwdArgs&>(fb) = f;
+            for (int z = 0; z < nz; ++z) fb.wpl[z] = a->cpl[inst[z].params == a->q ? 0 : 1] + CPL_W3;
+            Bracket br(a, "fwd_conv3");
+            BDR_HIP((launch_igemm_b3<FwdC3B3, 6>(st, dim3(m_tiles<FwdC3B3>(f.M) * n_tiles<FwdC3B3>(), 1, nz), fb)));
+        } else { Bracket br(a, "fwd_conv3"); BDR_HIP((launch_igemm<FwdC3D, TEAMS_FWD_C3>(st, dim3(m_tiles<FwdC3D>(f.M) * n_tiles<FwdC3D>(), 1, nz), f))); }
+    }
     f.M = B; f.nkt_per_split = (98 + L1_SPLIT - 1) / L1_SPLIT;
     for (int z = 0; z < nz; ++z) { f.x[z] = a->a3[inst[z].slot]; f.w[z] = inst[z].params + ar.w4; f.bias[z] = nullptr; f.out[z] = a->p1[inst[z].slot]; }
     if (uses_q) BDR_TRY(a->join_exchange(false, true));
