@@ -13,15 +13,14 @@
 // k_cdqn_td, L - 1 input gradients, the grouped dW, reduce + Adam: 2 L + 3 launches, 9 at the CartPole shape (L = 3), plus the
 // ring's gather.  The soft update rides in the reduce + Adam launch of the opt's last update on the opts that track (dqn/base.rs:180-184).
 // Every sum has one order (candle::row_sum), so an update gives the same bits run to run and agent to agent.
-// The AtariCnn Q-network (atari_cnn/base.rs) is the second form, CandleDqnCnn below: the shared conv layers of cnn_layers.hpp in front
+// The AtariCnn Q-network (atari_cnn/base.rs) is the second form, CandleDqnCnn below: the shared conv trunk (conv_trunk.hpp) in front
 // of the same head and TD step, and k_cdqn_conv_reduce_adam, the candle optimizer step over the conv gradients' partial sums.
 #include <algorithm>
 #include <cstdlib>
 #include <deque>
 
 #include "candle_actor.hpp"
-#include "conv1_bf16_img.hpp"
-#include "cnn_layers.hpp"
+#include "conv_trunk.hpp"
 
 using namespace bdr;
 
@@ -647,8 +646,8 @@ struct CandleDqn : DenseAgent {
 
 // ================================================================================================
 // The AtariCnn form (border-candle-agent/src/atari_cnn/base.rs:31-45): conv1 8x8/4, conv2 4x4/2, conv3 3x3/1 with ReLU after each -
-// the shared layer policies of cnn_layers.hpp, driven as iqn.hip drives them - then `net` = [3136 -> 512 -> A] on DenseAgent's
-// kernels.  Every arena is  W1 b1 W2 b2 W3 b3 (cnn_layers.hpp's layouts) | net's arena;  conv3's output [B][7][7][64] is net's first
+// the shared layer policies of cnn_layers.hpp, driven by conv_trunk.hpp as IQN's psi is - then `net` = [3136 -> 512 -> A] on DenseAgent's
+// kernels.  Every arena is  W1 b1 W2 b2 W3 b3 (conv_layout.hpp's layouts) | net's arena;  conv3's output [B][7][7][64] is net's first
 // input as it stands, and l1.weight's 3136 columns, (c, h, w) in the reference, are permuted once in to_internal / to_reference.
 // Arithmetic: conv1 on the bf16 MFMA with exact u8 operands and the 1/255 in its epilogue, everything else f32 x f32 on the FP32
 // MFMA (BDR_ARITH_F32_EXACT of the tch agent).  One queue, eager launches.  One update is
@@ -673,31 +672,20 @@ struct CandleDqnCnn : CandleDqn {
     int32_t alloc_inputs(int Bn) override
     {
         for (int z = 0; z < 3; ++z) {
-            BDR_TRY(alloc(&a1[z], (size_t)Bn * 400 * 32, BATCH)); BDR_TRY(alloc(&a2[z], (size_t)Bn * 81 * 64, BATCH)); BDR_TRY(alloc(&a3[z], (size_t)Bn * 49 * 64, BATCH));
+            BDR_TRY(alloc(&a1[z], Bn * CONV_A1_ROW, BATCH)); BDR_TRY(alloc(&a2[z], Bn * CONV_A2_ROW, BATCH)); BDR_TRY(alloc(&a3[z], Bn * CONV_A3_ROW, BATCH));
         }
-        BDR_TRY(alloc(&dy3, (size_t)Bn * 49 * 64, BATCH)); BDR_TRY(alloc(&dy2, (size_t)Bn * 81 * 64, BATCH)); BDR_TRY(alloc(&dy1, (size_t)Bn * 400 * 32, BATCH));
+        BDR_TRY(alloc(&dy3, Bn * CONV_A3_ROW, BATCH)); BDR_TRY(alloc(&dy2, Bn * CONV_A2_ROW, BATCH)); BDR_TRY(alloc(&dy1, Bn * CONV_A1_ROW, BATCH));
         return alloc(&part_conv, dw_plan(Bn, conv.ns).total, BATCH);
     }
     // the trunk of nz (parameters, u8 rows) pairs into a1 / a2 / a3 [0, nz): one launch per layer
     int32_t trunk_forward(int nz, const float* const* pp, const uint8_t* const* rows, int Bn, const char* name)
     {
-        Conv1Args c{}; c.M = Bn * 400; c.nz = nz;
-        FwdArgs f2{}, f3{}; f2.M = Bn * 81; f3.M = Bn * 49;
-        for (int z = 0; z < nz; ++z) {
-            c.x[z] = rows[z]; c.w1[z] = pp[z] + conv.w1; c.bias[z] = pp[z] + conv.b1; c.out[z] = a1[z];
-            f2.x[z] = a1[z]; f2.w[z] = pp[z] + conv.w2; f2.bias[z] = pp[z] + conv.b2; f2.out[z] = a2[z];
-            f3.x[z] = a2[z]; f3.w[z] = pp[z] + conv.w3; f3.bias[z] = pp[z] + conv.b3; f3.out[z] = a3[z];
-        }
-        bdr_agent* a = this;
-        { Bracket br(this, name); BDR_HIP(conv1_forward(conv.ns, Bn, stream, c)); }
-        { Bracket br(this, name); LAUNCH(k_igemm<FwdC2>, dim3((f2.M + 63) / 64, 1, nz), f2); }
-        { Bracket br(this, name); LAUNCH(k_igemm<FwdC3>, dim3((f3.M + 63) / 64, 1, nz), f3); }
-        return BDR_OK;
+        BDR_TRY(trunk_conv1(this, conv, nz, pp, rows, a1, Bn, name));
+        return trunk_conv23(this, conv, nz, pp, a1, a2, a3, Bn, name, name);
     }
     int32_t update_cnn(int Bn, const uint8_t* obs, const uint8_t* act, int act_bytes, const uint8_t* next_obs, const float* reward, const int8_t* term, bool track)
     {
         BDR_TRY(ensure_batch(Bn));
-        bdr_agent* a = this;
         const int L = (int)net.L.size(), nz = cfg.double_dqn ? 3 : 2;
         const DenseLayer& last = net.L[L - 1];
         {
@@ -727,36 +715,12 @@ struct CandleDqnCnn : CandleDqn {
             BDR_TRY(mlp_backward_step(net, 1, &hp, &hg, &hm, &hv, track ? ht : nullptr, a3[0], acts, dys, part, 0, off, &sc, Bn, {"dx", "dw", "reduce_adam"}, net.total,
                                       cfg.tau, L - 1, nullptr, dev_err + ERR_ACTION, applied, step, dx0, mask0));
         }
-        const DwPlan pl = dw_plan(B, conv.ns);
         CdqnConvAdamArgs ra{};
-        {
-            const int Mr = Bn * 49, chunks = std::min(pl.chunks_c3, (Mr + 31) / 32);
-            DwArgs d{a2[0], dy3, part_conv + pl.off_c3, pl.stride_c3, Mr};
-            { Bracket br(this, "conv3_dw"); LAUNCH(k_igemm_red<DwC3>, dim3(9 * chunks), d); }
-            ra.seg[2] = CdqnConvSeg{part_conv + pl.off_c3, pl.stride_c3, chunks, (unsigned)(conv.w3 / 4), (unsigned)(pl.stride_c3 / 4), 0u, 1.0f};
-        }
-        {
-            DxArgs d{dy3, p + conv.w3, a2[0], dy2, Bn * 81, nullptr, 0};
-            Bracket br(this, "conv3_dx");
-            BDR_HIP((launch_igemm<DxC3Pos, 2>(stream, dim3(((Bn + DxC3Pos::WM * DxC3Pos::TM * 32 - 1) / (DxC3Pos::WM * DxC3Pos::TM * 32)) * n_tiles<DxC3Pos>(), 81, 1), d)));
-        }
-        {
-            const int Mr = Bn * 81, chunks = std::min(pl.chunks_c2, (Mr + 31) / 32);
-            DwArgs d{a1[0], dy2, part_conv + pl.off_c2, pl.stride_c2, Mr};
-            { Bracket br(this, "conv2_dw"); LAUNCH(k_igemm_red<DwC2>, dim3(8 * chunks), d); }
-            ra.seg[1] = CdqnConvSeg{part_conv + pl.off_c2, pl.stride_c2, chunks, (unsigned)(conv.w2 / 4), (unsigned)(pl.stride_c2 / 4), 0u, 1.0f};
-        }
-        {
-            DxArgs d{dy2, p + conv.w2, a1[0], dy1, Bn * 100, nullptr, 0};
-            Bracket br(this, "conv2_dx");
-            BDR_HIP((launch_igemm<DxC2MPos, 1>(stream, dxc2_pos_grid<DxC2MPos>(Bn), d)));
-        }
-        {
-            const int chunks = std::min(pl.chunks_c1, Bn);
-            Conv1DwArgs d{obs, dy1, part_conv + pl.off_c1, pl.stride_c1, Bn};
-            { Bracket br(this, "conv1_dw"); BDR_HIP(launch_conv1_dw_bf16(conv.ns, dim3(chunks), stream, d)); }
-            ra.seg[0] = CdqnConvSeg{part_conv + pl.off_c1, pl.stride_c1, chunks, (unsigned)(conv.w1 / 4), (unsigned)(pl.stride_c1 / 4), (unsigned)(conv.n_w1() / 4), INV255};
-        }
+        BDR_TRY(trunk_backward(this, conv, p, obs, a1[0], a2[0], dy3, dy2, dy1, part_conv, Bn, B, "", [&](int k, int chunks, const float* lp, size_t stride) {
+            const size_t w[3] = {conv.w1, conv.w2, conv.w3};   // conv1's weights carry the 1 / 255 of its u8 operand
+            ra.seg[k] = CdqnConvSeg{lp, stride, chunks, (unsigned)(w[k] / 4), (unsigned)(stride / 4), k == 0 ? (unsigned)(conv.n_w1() / 4) : 0u, k == 0 ? INV255 : 1.0f};
+            return (int32_t)BDR_OK;
+        }));
         {
             ra.p = p; ra.g = g; ra.m = m; ra.v = v; ra.tgt = p_tgt; ra.s = sc; ra.n4 = (unsigned)(conv_floats() / 4);
             ra.track = track ? 1 : 0; ra.tau = (float)cfg.tau; ra.omt = (float)(1.0 - cfg.tau);
@@ -830,20 +794,11 @@ struct CandleDqnCnn : CandleDqn {
                                      "(bdr_agent_sample, bdr_agent_sample_device)");
     }
 
-    // ---- reference <-> internal layouts: the conv layers as iqn.hip has them, l1's input columns (c, h, w) -> (h, w, c) ----
+    // ---- reference <-> internal layouts: the conv layers by conv_layout.hpp, l1's input columns (c, h, w) -> (h, w, c) ----
     void to_internal(const float* ref, float* in) const
     {
         std::fill(in, in + arena_floats(), 0.f);
-        const float* q = ref;
-        const int K1 = 64 * conv.ns;
-        for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) in[conv.w1 + (size_t)k * 32 + o] = q[(size_t)o * K1 + k];
-        q += (size_t)32 * K1; std::copy(q, q + 32, in + conv.b1); q += 32;
-        for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
-            in[conv.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o] = q[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw];
-        q += 32768; std::copy(q, q + 64, in + conv.b2); q += 64;
-        for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
-            in[conv.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o] = q[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw];
-        q += 36864; std::copy(q, q + 64, in + conv.b3); q += 64;
+        const float* q = ref + conv_to_internal(conv, ref, in);
         float* h = in + conv_floats();
         const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
         for (int o = 0; o < 512; ++o) for (int j = 0; j < 3136; ++j) h[l1.w + (size_t)((j % 49) * 64 + j / 49) * l1.Np + o] = q[(size_t)o * 3136 + j];
@@ -853,16 +808,7 @@ struct CandleDqnCnn : CandleDqn {
     }
     void to_reference(const float* in, float* ref) const
     {
-        float* q = ref;
-        const int K1 = 64 * conv.ns;
-        for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) q[(size_t)o * K1 + k] = in[conv.w1 + (size_t)k * 32 + o];
-        q += (size_t)32 * K1; std::copy(in + conv.b1, in + conv.b1 + 32, q); q += 32;
-        for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
-            q[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw] = in[conv.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o];
-        q += 32768; std::copy(in + conv.b2, in + conv.b2 + 64, q); q += 64;
-        for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
-            q[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw] = in[conv.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o];
-        q += 36864; std::copy(in + conv.b3, in + conv.b3 + 64, q); q += 64;
+        float* q = ref + conv_to_reference(conv, in, ref);
         const float* h = in + conv_floats();
         const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
         for (int o = 0; o < 512; ++o) for (int j = 0; j < 3136; ++j) q[(size_t)o * 3136 + j] = h[l1.w + (size_t)((j % 49) * 64 + j / 49) * l1.Np + o];

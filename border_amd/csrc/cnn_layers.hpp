@@ -1,10 +1,13 @@
-// Nature-CNN layer policies shared by the DQN and IQN agents (border-tch-agent/src/cnn/base.rs:23-36):
-// parameter arena layout, forward / input-gradient / weight-gradient policies for the implicit-GEMM
-// kernels of igemm.hpp, the deterministic partial reduction, and the dW chunk plan.
+// Nature-CNN layer policies shared by the tch DQN, IQN and candle DQN agents (border-tch-agent/src/cnn/base.rs:23-36):
+// forward / input-gradient / weight-gradient policies for the implicit-GEMM kernels of igemm.hpp, the deterministic
+// partial reduction, and the dW chunk plan.  The parameter arena and its reference <-> internal conversion are in
+// conv_layout.hpp (no HIP); the host code that drives these kernels layer by layer on one stream is conv_trunk.hpp
+// (IQN, candle DQN; the tch DQN's multi-queue step in dqn.hip launches them itself).
 #pragma once
 #include <algorithm>
 
 #include "agent_base.hpp"
+#include "conv_layout.hpp"
 #include "conv1_dw_bf16.hpp"
 #include "igemm.hpp"
 
@@ -19,33 +22,6 @@ constexpr int MAXZ = 3;       // network instances per forward launch
 #endif
 constexpr int L1_SPLIT = BDR_L1_SPLIT;   // split-K of the 3136-deep l1 contraction (98 k-tiles)
 constexpr float INV255 = 1.0f / 255.0f;
-
-// ---- flat parameter arena (internal layouts; every segment 16-byte aligned) ----------------------
-//   W1 [64 * n_stack][32]  k=(c,kh,kw)      b1[32]      (n_stack = 4: [256][32])
-//   W2 [512][64]  k=(kh,kw,c)      b2[64]
-//   W3 [576][64]  k=(kh,kw,c)      b3[64]
-//   W4 [3136][512] k=(h,w,c)       b4[512]      (NHWC flatten of conv3's output)
-//   W5 [A][512]  (= the reference's [out][in]: k_head reads a lane's 8 columns of an action as two f32x4)   b5[A]
-struct Arena {
-    size_t w1, b1, w2, b2, w3, b3, w4, b4, w5, b5, total;  // offsets in floats
-    int A;
-    int ns;        // AtariCnnConfig::n_stack (cnn/config.rs:14-24): conv1 has 64 * ns rows
-    size_t n_w1() const { return (size_t)64 * ns * 32; }
-};
-Arena make_arena(int A, int ns = 4)
-{
-    Arena a{};
-    size_t o = 0;
-    auto seg = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-    a.ns = ns;
-    a.w1 = seg((size_t)64 * ns * 32); a.b1 = seg(32);
-    a.w2 = seg(512 * 64); a.b2 = seg(64);
-    a.w3 = seg(576 * 64); a.b3 = seg(64);
-    a.w4 = seg((size_t)3136 * 512); a.b4 = seg(512);
-    a.w5 = seg((size_t)512 * A); a.b5 = seg(A);
-    a.total = o; a.A = A;
-    return a;
-}
 
 // ================================================================================================
 // forward policies
@@ -275,6 +251,7 @@ struct DxC3PosP {
 };
 
 using DxC3Pos = DxC3PosP<BDR_DXC3_SHAPE>;
+template <class P> inline dim3 dxc3_pos_grid(int B) { return dim3((unsigned)((B + P::WM * P::TM * 32 - 1) / (P::WM * P::TM * 32)) * n_tiles<P>(), P::G::IH * P::G::IW, 1); }
 
 // conv2 (4x4, stride 2): blockIdx.y = parity class (ph,pw); rows (b, ih/2, iw/2); K' = 4 taps * 64
 template <int WM_, int WN_, int RPIP_ = 0, int TM_ = 1, int TN_ = 1>

@@ -485,18 +485,18 @@ int32_t ensure_batch(DqnCnn* a, int B)
     free_batch_buffers(a);
     const int A = a->ar.A;
     for (int z = 0; z < MAXZ; ++z) {
-        BDR_TRY(alloc_f(&a->a1[z], (size_t)B * 400 * 32));
-        BDR_TRY(alloc_f(&a->a2[z], (size_t)B * 81 * 64));
-        BDR_TRY(alloc_f(&a->a3[z], (size_t)B * 49 * 64));
+        BDR_TRY(alloc_f(&a->a1[z], B * CONV_A1_ROW));
+        BDR_TRY(alloc_f(&a->a2[z], B * CONV_A2_ROW));
+        BDR_TRY(alloc_f(&a->a3[z], B * CONV_A3_ROW));
         BDR_TRY(alloc_f(&a->p1[z], (size_t)L1_SPLIT * B * 512));
         BDR_TRY(alloc_f(&a->h1[z], (size_t)B * 512));
         BDR_TRY(alloc_f(&a->qv[z], (size_t)B * A));
     }
-    BDR_TRY(alloc_f(&a->a1_alt, (size_t)B * 400 * 32));
+    BDR_TRY(alloc_f(&a->a1_alt, B * CONV_A1_ROW));
     BDR_TRY(alloc_f(&a->dh1, (size_t)B * 512));
-    BDR_TRY(alloc_f(&a->dy3, (size_t)B * 49 * 64));
-    BDR_TRY(alloc_f(&a->dy2, (size_t)B * 81 * 64));
-    BDR_TRY(alloc_f(&a->dy1, (size_t)B * 400 * 32));
+    BDR_TRY(alloc_f(&a->dy3, B * CONV_A3_ROW));
+    BDR_TRY(alloc_f(&a->dy2, B * CONV_A2_ROW));
+    BDR_TRY(alloc_f(&a->dy1, B * CONV_A1_ROW));
     BDR_TRY(alloc_f(&a->dq, B)); BDR_TRY(alloc_f(&a->pred, B)); BDR_TRY(alloc_f(&a->tgt, B));
     BDR_TRY(alloc_f(&a->loss_row, B));
     const DwPlan p = dw_plan(B, a->ar.ns);
@@ -901,7 +901,7 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
     auto c3_dx = [&]() -> int32_t {
         DxArgs d{a->dy3, a->q + ar.w3, a->a2[0], a->dy2, B * 81, sigf(SIG_DXL1), epoch};
         Bracket br(a, "bwd_conv3_dx");
-        BDR_HIP((launch_igemm<DxC3Pos, TEAMS_DX_C3>(a->stream, dim3(((B + DxC3Pos::WM * DxC3Pos::TM * 32 - 1) / (DxC3Pos::WM * DxC3Pos::TM * 32)) * n_tiles<DxC3Pos>(), 81, 1), d, 0, kev(2))));
+        BDR_HIP((launch_igemm<DxC3Pos, TEAMS_DX_C3>(a->stream, dxc3_pos_grid<DxC3Pos>(B), d, 0, kev(2))));
         return BDR_OK;
     };
     auto c2_dw = [&]() -> int32_t {
@@ -1220,16 +1220,7 @@ size_t ref_param_count(int A, int ns) { return (size_t)2048 * ns + 32 + 32768 + 
 void to_internal(const Arena& ar, const float* ref, float* in)
 {
     std::fill(in, in + ar.total, 0.f);
-    const float* p = ref;
-    const int K1 = 64 * ar.ns;   // (c, kh, kw) of c1.weight[o] is the internal k order
-    for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) in[ar.w1 + (size_t)k * 32 + o] = p[(size_t)o * K1 + k];
-    p += (size_t)32 * K1; std::copy(p, p + 32, in + ar.b1); p += 32;
-    for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
-        in[ar.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o] = p[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw];
-    p += 32768; std::copy(p, p + 64, in + ar.b2); p += 64;
-    for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
-        in[ar.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o] = p[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw];
-    p += 36864; std::copy(p, p + 64, in + ar.b3); p += 64;
+    const float* p = ref + conv_to_internal(ar, ref, in);
     for (int o = 0; o < 512; ++o) for (int c = 0; c < 64; ++c) for (int hw = 0; hw < 49; ++hw)
         in[ar.w4 + (size_t)(hw * 64 + c) * 512 + o] = p[(size_t)o * 3136 + c * 49 + hw];
     p += (size_t)512 * 3136; std::copy(p, p + 512, in + ar.b4); p += 512;
@@ -1239,16 +1230,7 @@ void to_internal(const Arena& ar, const float* ref, float* in)
 
 void to_reference(const Arena& ar, const float* in, float* ref)
 {
-    float* p = ref;
-    const int K1 = 64 * ar.ns;
-    for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) p[(size_t)o * K1 + k] = in[ar.w1 + (size_t)k * 32 + o];
-    p += (size_t)32 * K1; std::copy(in + ar.b1, in + ar.b1 + 32, p); p += 32;
-    for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
-        p[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw] = in[ar.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o];
-    p += 32768; std::copy(in + ar.b2, in + ar.b2 + 64, p); p += 64;
-    for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
-        p[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw] = in[ar.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o];
-    p += 36864; std::copy(in + ar.b3, in + ar.b3 + 64, p); p += 64;
+    float* p = ref + conv_to_reference(ar, in, ref);
     for (int o = 0; o < 512; ++o) for (int c = 0; c < 64; ++c) for (int hw = 0; hw < 49; ++hw)
         p[(size_t)o * 3136 + c * 49 + hw] = in[ar.w4 + (size_t)(hw * 64 + c) * 512 + o];
     p += (size_t)512 * 3136; std::copy(in + ar.b4, in + ar.b4 + 512, p); p += 512;

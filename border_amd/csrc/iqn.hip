@@ -12,8 +12,7 @@
 #include <cstdlib>
 
 #include "dense.hpp"
-#include "conv1_bf16_img.hpp"
-#include "cnn_layers.hpp"
+#include "conv_trunk.hpp"
 #include "act_small.hpp"
 
 using namespace bdr;
@@ -147,8 +146,6 @@ void sample_const(int mode, std::vector<float>& t)
     else t.push_back(0.5f);
 }
 
-inline size_t conv_floats(int ns) { return (size_t)2048 * ns + 32 + 32768 + 64 + 36864 + 64; }   // c1 [32][ns][8][8] .. c3.bias (cnn/base.rs:27-31)
-
 }  // namespace
 
 // ================================================================================================
@@ -248,8 +245,8 @@ struct Iqn : bdr_agent {
         const size_t M = (size_t)Bn * N;
         const int Fp = hd.L[0].Np, Ep = hd.L[0].Kp;
         if (cnn) {
-            BDR_TRY(zalloc(&a1, (size_t)Bn * 400 * 32)); BDR_TRY(zalloc(&a2, (size_t)Bn * 81 * 64)); BDR_TRY(zalloc(&a3, (size_t)Bn * 49 * 64));
-            BDR_TRY(zalloc(&dy3, (size_t)Bn * 49 * 64)); BDR_TRY(zalloc(&dy2, (size_t)Bn * 81 * 64)); BDR_TRY(zalloc(&dy1, (size_t)Bn * 400 * 32));
+            BDR_TRY(zalloc(&a1, Bn * CONV_A1_ROW)); BDR_TRY(zalloc(&a2, Bn * CONV_A2_ROW)); BDR_TRY(zalloc(&a3, Bn * CONV_A3_ROW));
+            BDR_TRY(zalloc(&dy3, Bn * CONV_A3_ROW)); BDR_TRY(zalloc(&dy2, Bn * CONV_A2_ROW)); BDR_TRY(zalloc(&dy1, Bn * CONV_A1_ROW));
             BDR_TRY(zalloc(&part_conv, dw_plan(Bn, conv.ns).total));
         } else {
             BDR_TRY(zalloc(&x_in, (size_t)Bn * psi_mlp.L[0].Kp));
@@ -275,9 +272,7 @@ struct Iqn : bdr_agent {
     {
         bdr_agent* a = this;
         if (cnn) {
-            Conv1Args c{}; c.M = Bn * 400; c.nz = 1;
-            c.x[0] = obs; c.w1[0] = params + conv.w1; c.bias[0] = params + conv.b1; c.out[0] = a1;
-            { Bracket br(a, "psi_conv1"); BDR_HIP(conv1_forward(conv.ns, Bn, stream, c)); }
+            BDR_TRY(trunk_conv1(a, conv, 1, &params, &obs, &a1, Bn, "psi_conv1"));
             if (acting && Bn <= ACT_SMALL_MAX) {
                 auto pad32 = [](int m) { return (m + 31) / 32 * 32; };
                 BDR_TRY(act_scratch(act_small_part_floats()));
@@ -290,11 +285,7 @@ struct Iqn : bdr_agent {
                 *feat = a3; *ld = 3136;
                 return BDR_OK;
             }
-            FwdArgs f{};
-            f.M = Bn * 81; f.x[0] = a1; f.w[0] = params + conv.w2; f.bias[0] = params + conv.b2; f.out[0] = a2;
-            { Bracket br(a, "psi_conv2"); LAUNCH(k_igemm<FwdC2>, dim3((f.M + 63) / 64, 1, 1), f); }
-            f.M = Bn * 49; f.x[0] = a2; f.w[0] = params + conv.w3; f.bias[0] = params + conv.b3; f.out[0] = a3;
-            { Bracket br(a, "psi_conv3"); LAUNCH(k_igemm<FwdC3>, dim3((f.M + 63) / 64, 1, 1), f); }
+            BDR_TRY(trunk_conv23(a, conv, 1, &params, &a1, &a2, &a3, Bn, "psi_conv2", "psi_conv3"));
             *feat = a3; *ld = 3136;
         } else {
             BDR_TRY(pack_rows(stream, reinterpret_cast<const float*>(obs), in_dim, in_dim, x_in, psi_mlp.L[0].Kp, 0, Bn));
@@ -416,41 +407,15 @@ struct Iqn : bdr_agent {
         { Bracket br(a, "iqn_cos_dw"); BDR_TRY(dense_dw(stream, hd.L[0], grad, DenseSrc{cosv, Ep}, mrg, M, part, ch)); }
         // psi backward
         if (cnn) {
-            const DwPlan pl = dw_plan(B, conv.ns);
-            {
-                const int Mr = Bn * 49, chunks = std::min(pl.chunks_c3, (Mr + 31) / 32);
-                DwArgs d{a2, dy3, part_conv + pl.off_c3, pl.stride_c3, Mr};
-                { Bracket br(a, "psi_conv3_dw"); LAUNCH(k_igemm_red<DwC3>, dim3(9 * chunks), d); }
-                const int n = 576 * 64 + 64;
-                hipLaunchKernelGGL(k_reduce_partials, dim3((n + 63) / 64), dim3(256), 0, stream, part_conv + pl.off_c3, pl.stride_c3, chunks, grad + conv.w3, n, 576 * 64, 1.0f);
+            // each layer's partial sums are reduced into grad right behind its dW launch (a chunk = the layer's weights, then its bias)
+            auto reduce = [&](int k, int chunks, const float* lp, size_t stride) -> int32_t {
+                const size_t w[3] = {conv.w1, conv.w2, conv.w3};
+                const int n = (int)stride, nw = n - (k == 0 ? 32 : 64);
+                hipLaunchKernelGGL(k_reduce_partials, dim3((n + 63) / 64), dim3(256), 0, stream, lp, stride, chunks, grad + w[k], n, nw, k == 0 ? INV255 : 1.0f);
                 BDR_HIP(hipGetLastError());
-            }
-            {   // position-class tiles (cnn_layers.hpp DxC3PosP: only the taps that reach a valid output; bit-identical to the flat row tiles)
-                DxArgs d{dy3, p + conv.w3, a2, dy2, Bn * 81, nullptr, 0};
-                Bracket br(a, "psi_conv3_dx");
-                BDR_HIP((launch_igemm<DxC3Pos, 2>(stream, dim3(((Bn + DxC3Pos::WM * DxC3Pos::TM * 32 - 1) / (DxC3Pos::WM * DxC3Pos::TM * 32)) * n_tiles<DxC3Pos>(), 81, 1), d)));
-            }
-            {
-                const int Mr = Bn * 81, chunks = std::min(pl.chunks_c2, (Mr + 31) / 32);
-                DwArgs d{a1, dy2, part_conv + pl.off_c2, pl.stride_c2, Mr};
-                { Bracket br(a, "psi_conv2_dw"); LAUNCH(k_igemm_red<DwC2>, dim3(8 * chunks), d); }
-                const int n = 512 * 64 + 64;
-                hipLaunchKernelGGL(k_reduce_partials, dim3((n + 63) / 64), dim3(256), 0, stream, part_conv + pl.off_c2, pl.stride_c2, chunks, grad + conv.w2, n, 512 * 64, 1.0f);
-                BDR_HIP(hipGetLastError());
-            }
-            {   // the four parity classes as one GEMM over position-class tiles (DxC2MPosP), as the DQN step
-                DxArgs d{dy2, p + conv.w2, a1, dy1, Bn * 100, nullptr, 0};
-                Bracket br(a, "psi_conv2_dx");
-                BDR_HIP((launch_igemm<DxC2MPos, 1>(stream, dxc2_pos_grid<DxC2MPos>(Bn), d)));
-            }
-            {
-                const int chunks = std::min(pl.chunks_c1, Bn);
-                Conv1DwArgs d{obs, dy1, part_conv + pl.off_c1, pl.stride_c1, Bn};
-                { Bracket br(a, "psi_conv1_dw"); BDR_HIP(launch_conv1_dw_bf16(conv.ns, dim3(chunks), a->stream, d)); }
-                const int nw = (int)conv.n_w1(), n = nw + 32;
-                hipLaunchKernelGGL(k_reduce_partials, dim3((n + 63) / 64), dim3(256), 0, stream, part_conv + pl.off_c1, pl.stride_c1, chunks, grad + conv.w1, n, nw, INV255);
-                BDR_HIP(hipGetLastError());
-            }
+                return BDR_OK;
+            };
+            BDR_TRY(trunk_backward(a, conv, p, obs, a1, a2, dy3, dy2, dy1, part_conv, Bn, B, "psi_", reduce));
         } else {
             const int PL = (int)psi_mlp.L.size();
             for (int i = PL - 1; i >= 0; --i) {
@@ -542,15 +507,7 @@ struct Iqn : bdr_agent {
         std::fill(in, in + total, 0.f);
         const float* q = ref;
         if (cnn) {
-            const int K1 = 64 * conv.ns;
-            for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) in[conv.w1 + (size_t)k * 32 + o] = q[(size_t)o * K1 + k];
-            q += (size_t)32 * K1; std::copy(q, q + 32, in + conv.b1); q += 32;
-            for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
-                in[conv.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o] = q[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw];
-            q += 32768; std::copy(q, q + 64, in + conv.b2); q += 64;
-            for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
-                in[conv.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o] = q[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw];
-            q += 36864; std::copy(q, q + 64, in + conv.b3); q += 64;
+            q += conv_to_internal(conv, q, in);
         } else {
             mlp_to_internal(psi_mlp, 0, q, in);
             q += psi_mlp.ref_total;
@@ -574,15 +531,7 @@ struct Iqn : bdr_agent {
     {
         float* q = ref;
         if (cnn) {
-            const int K1 = 64 * conv.ns;
-            for (int o = 0; o < 32; ++o) for (int k = 0; k < K1; ++k) q[(size_t)o * K1 + k] = in[conv.w1 + (size_t)k * 32 + o];
-            q += (size_t)32 * K1; std::copy(in + conv.b1, in + conv.b1 + 32, q); q += 32;
-            for (int o = 0; o < 64; ++o) for (int c = 0; c < 32; ++c) for (int kh = 0; kh < 4; ++kh) for (int kw = 0; kw < 4; ++kw)
-                q[((size_t)(o * 32 + c) * 4 + kh) * 4 + kw] = in[conv.w2 + (size_t)((kh * 4 + kw) * 32 + c) * 64 + o];
-            q += 32768; std::copy(in + conv.b2, in + conv.b2 + 64, q); q += 64;
-            for (int o = 0; o < 64; ++o) for (int c = 0; c < 64; ++c) for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw)
-                q[((size_t)(o * 64 + c) * 3 + kh) * 3 + kw] = in[conv.w3 + (size_t)((kh * 3 + kw) * 64 + c) * 64 + o];
-            q += 36864; std::copy(in + conv.b3, in + conv.b3 + 64, q); q += 64;
+            q += conv_to_reference(conv, in, q);
         } else {
             mlp_to_reference(psi_mlp, 0, in, q);
             q += psi_mlp.ref_total;
@@ -723,7 +672,7 @@ int32_t bdr_iqn_create(const bdr_iqn_config* cfg, bdr_agent** out)
         BDR_REQUIRE(cfg->feature_dim == 3136, "the AtariCnn{skip_linear} trunk yields 64 x 7 x 7 = 3136 features (cnn/base.rs:38-45)");
         BDR_REQUIRE(cfg->psi.n_stack >= 1 && cfg->psi.n_stack <= bdr::C1_MAX_STACK, "AtariCnnConfig::n_stack must be in [1, %d] (conv1's kernels are instantiated per depth)", bdr::C1_MAX_STACK);
         a->conv = make_arena(1, cfg->psi.n_stack);
-        o = a->ref_total = conv_floats(cfg->psi.n_stack);
+        o = a->ref_total = conv_ref_floats(cfg->psi.n_stack);
     } else {
         BDR_REQUIRE(cfg->psi.out_dim == cfg->feature_dim, "psi.out_dim must equal feature_dim");
         a->in_dim = cfg->psi.in_dim;

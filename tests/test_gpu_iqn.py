@@ -81,6 +81,24 @@ def test_iqn_golden_cnn_b2(B, golden_dir):
     _run(B, "iqn_cnn_b2", golden_dir)
 
 
+def test_one_update_runs_the_psi_trunk_in_its_fixed_launch_order(B):
+    """From the profile brackets of one update at the iqn_cnn_b2 shapes: the trunk's three forward launches once for the target network
+    and once for the online one, later the backward chain conv3 dW, conv3 dX, conv2 dW, conv2 dX, conv1 dW (csrc/conv_trunk.hpp).
+    B = 2 is the smallest batch and sits under every chunk clamp of the weight gradients: conv1 has fewer images than its chunk cap,
+    conv2 / conv3 have (M + 31) / 32 = 6 / 4 row tiles against dw_plan's caps of 64 / 56."""
+    import bench
+    kind, F_, E, fu, A, pin, pu, Bsz, n_p, n_t, steps, lr, sh, p0, seed = MG.iqn_case("iqn_cnn_b2")
+    assert kind == "cnn" and Bsz == 2
+    a = _agent(B, kind, F_, E, fu, A, pin, pu, Bsz, lr, p0, tau=0.01, soft_update_interval=2)
+    a.profile_enable(True)
+    a.update_on_batch(*MG.iqn_case_batch("iqn_cnn_b2", 0))
+    psi = [l for l, _ in bench.read_profile(a) if l.startswith("psi_")]
+    a.profile_enable(False)
+    a.close()
+    assert psi == ["psi_conv1", "psi_conv2", "psi_conv3", "psi_conv1", "psi_conv2", "psi_conv3",
+                   "psi_conv3_dw", "psi_conv3_dx", "psi_conv2_dw", "psi_conv2_dx", "psi_conv1_dw"], psi
+
+
 @pytest.mark.parametrize("A", [6, 4, 9, 18, 33])
 def test_iqn_cnn_64_quantiles_vs_oracle(B, A):
     """BASELINE config 4 shape at a reduced batch (B=16, 64 pred/tgt quantiles, Nature trunk): one update vs the C oracle, at
