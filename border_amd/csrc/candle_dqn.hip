@@ -134,7 +134,8 @@ __global__ __launch_bounds__(256) void k_cdqn_act(CdqnActArgs p)
 // ---- k_cdqn_conv_reduce_adam ------------------------------------------------------------------------------------------------------
 // The optimizer step of the AtariCnn form's conv parameters.  The conv weight-gradient kernels (DwC3, DwC2, conv1_dw_bf16) leave
 // row-chunk partials [chunks][K N + N] (weights, then bias) per layer.  A workgroup owns 32 float4 of the conv arena W1 b1 W2 b2 W3 b3 -
-// the segments follow one another without slack, each a multiple of four floats - and eight threads share a float4 i:
+// the segments follow one another without slack, each a multiple of four floats - and eight threads share a float4 i
+// (cnn_layers.hpp reduce_partials_8x32, the sum the tch DQN's k_reduce_adam runs over floats):
 //   thread group q = 0 ... 7 sums the float4 of the chunks c = q, q + 8, ... in ascending order; the eight sums meet in LDS and
 //   group 0 adds them as ((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7: ONE order, whatever the grid (conv1 leaves up to 256
 //   chunks: one thread per float4 walked them in 82 us at B = 256); it scales conv1's WEIGHT elements by 1/255 (the kernel multiplied
@@ -160,42 +161,32 @@ __global__ __launch_bounds__(256) void k_cdqn_conv_reduce_adam(CdqnConvAdamArgs 
 #pragma clang fp contract(off)
     __shared__ f32x4 red[8][32];
     if (*a.poison) return;   // (the whole grid reads the same word: no thread of a workgroup is left at the barrier)
-    const unsigned o = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const unsigned i = blockIdx.x * 32 + o;
-    const bool in = i < a.n4;
+    const unsigned i = blockIdx.x * 32 + (threadIdx.x & 31);
     const int k = (i >= a.seg[1].off4 ? 1 : 0) + (i >= a.seg[2].off4 ? 1 : 0);
     const CdqnConvSeg sg = a.seg[k];
     const unsigned j = i - sg.off4;
-    f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (in) {
-        const float* part = sg.part + (size_t)j * 4;
-        for (int c = (int)grp; c < sg.chunks; c += 8) sum += *reinterpret_cast<const f32x4*>(part + (size_t)c * sg.stride);
-    }
-    red[grp][o] = sum;
-    __syncthreads();
-    if (grp != 0 || !in) return;
-    if (i == 0) *a.applied = a.step;
-    f32x4 gg = red[0][o];
+    reduce_partials_8x32(red, sg, j, i < a.n4, [&](f32x4 gg) {
+#pragma clang fp contract(off)
+        if (i == 0) *a.applied = a.step;
+        if (j < sg.nw4) gg *= sg.wscale;
+        reinterpret_cast<f32x4*>(a.g)[i] = gg;
+        f32x4 pp = reinterpret_cast<f32x4*>(a.p)[i], mm = reinterpret_cast<f32x4*>(a.m)[i], vv = reinterpret_cast<f32x4*>(a.v)[i];
 #pragma unroll
-    for (int q = 1; q < 8; ++q) gg += red[q][o];
-    if (j < sg.nw4) gg *= sg.wscale;
-    reinterpret_cast<f32x4*>(a.g)[i] = gg;
-    f32x4 pp = reinterpret_cast<f32x4*>(a.p)[i], mm = reinterpret_cast<f32x4*>(a.m)[i], vv = reinterpret_cast<f32x4*>(a.v)[i];
+        for (int e = 0; e < 4; ++e) {
+            float pe = pp[e], me = mm[e], ve = vv[e];
+            adam_element(pe, gg[e], me, ve, a.s);
+            pp[e] = pe; mm[e] = me; vv[e] = ve;
+        }
+        reinterpret_cast<f32x4*>(a.p)[i] = pp;
+        reinterpret_cast<f32x4*>(a.m)[i] = mm;
+        reinterpret_cast<f32x4*>(a.v)[i] = vv;
+        if (a.track) {
+            f32x4 d = reinterpret_cast<f32x4*>(a.tgt)[i];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float pe = pp[e], me = mm[e], ve = vv[e];
-        adam_element(pe, gg[e], me, ve, a.s);
-        pp[e] = pe; mm[e] = me; vv[e] = ve;
-    }
-    reinterpret_cast<f32x4*>(a.p)[i] = pp;
-    reinterpret_cast<f32x4*>(a.m)[i] = mm;
-    reinterpret_cast<f32x4*>(a.v)[i] = vv;
-    if (a.track) {
-        f32x4 d = reinterpret_cast<f32x4*>(a.tgt)[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = track_element(pp[e], d[e], a.tau, a.omt);
-        reinterpret_cast<f32x4*>(a.tgt)[i] = d;
-    }
+            for (int e = 0; e < 4; ++e) d[e] = track_element(pp[e], d[e], a.tau, a.omt);
+            reinterpret_cast<f32x4*>(a.tgt)[i] = d;
+        }
+    });
 }
 
 // ---- the exploration stream -------------------------------------------------------------------------------------------------------
@@ -675,7 +666,7 @@ struct CandleDqnCnn : CandleDqn {
             BDR_TRY(alloc(&a1[z], Bn * CONV_A1_ROW, BATCH)); BDR_TRY(alloc(&a2[z], Bn * CONV_A2_ROW, BATCH)); BDR_TRY(alloc(&a3[z], Bn * CONV_A3_ROW, BATCH));
         }
         BDR_TRY(alloc(&dy3, Bn * CONV_A3_ROW, BATCH)); BDR_TRY(alloc(&dy2, Bn * CONV_A2_ROW, BATCH)); BDR_TRY(alloc(&dy1, Bn * CONV_A1_ROW, BATCH));
-        return alloc(&part_conv, dw_plan(Bn, conv.ns).total, BATCH);
+        return alloc(&part_conv, conv_dw_plan(conv, Bn).total, BATCH);
     }
     // the trunk of nz (parameters, u8 rows) pairs into a1 / a2 / a3 [0, nz): one launch per layer
     int32_t trunk_forward(int nz, const float* const* pp, const uint8_t* const* rows, int Bn, const char* name)
@@ -716,9 +707,9 @@ struct CandleDqnCnn : CandleDqn {
                                       cfg.tau, L - 1, nullptr, dev_err + ERR_ACTION, applied, step, dx0, mask0));
         }
         CdqnConvAdamArgs ra{};
-        BDR_TRY(trunk_backward(this, conv, p, obs, a1[0], a2[0], dy3, dy2, dy1, part_conv, Bn, B, "", [&](int k, int chunks, const float* lp, size_t stride) {
-            const size_t w[3] = {conv.w1, conv.w2, conv.w3};   // conv1's weights carry the 1 / 255 of its u8 operand
-            ra.seg[k] = CdqnConvSeg{lp, stride, chunks, (unsigned)(w[k] / 4), (unsigned)(stride / 4), k == 0 ? (unsigned)(conv.n_w1() / 4) : 0u, k == 0 ? INV255 : 1.0f};
+        int k = 3;   // the hook runs for conv3, conv2, conv1; the segments are in arena order
+        BDR_TRY(trunk_backward(this, conv, p, obs, a1[0], a2[0], dy3, dy2, dy1, part_conv, Bn, B, "", [&](const ConvDwLayer& l, int chunks, const float* lp) {
+            ra.seg[--k] = CdqnConvSeg{lp, l.stride, chunks, (unsigned)(l.w / 4), (unsigned)(l.n / 4), (unsigned)(l.n_weights / 4), l.wscale};
             return (int32_t)BDR_OK;
         }));
         {

@@ -1,7 +1,7 @@
 // Nature-CNN layer policies shared by the tch DQN, IQN and candle DQN agents (border-tch-agent/src/cnn/base.rs:23-36):
 // forward / input-gradient / weight-gradient policies for the implicit-GEMM kernels of igemm.hpp, the deterministic
-// partial reduction, and the dW chunk plan.  The parameter arena and its reference <-> internal conversion are in
-// conv_layout.hpp (no HIP); the host code that drives these kernels layer by layer on one stream is conv_trunk.hpp
+// partial reductions.  The parameter arena, its reference <-> internal conversion and the plan of the dW partials
+// (conv_dw_plan) are in conv_layout.hpp (no HIP); the host code that drives these kernels layer by layer on one stream is conv_trunk.hpp
 // (IQN, candle DQN; the tch DQN's multi-queue step in dqn.hip launches them itself).
 #pragma once
 #include <algorithm>
@@ -21,7 +21,6 @@ constexpr int MAXZ = 3;       // network instances per forward launch
 #define BDR_L1_SPLIT (BDR_L1_XSPLIT ? 8 : 7)
 #endif
 constexpr int L1_SPLIT = BDR_L1_SPLIT;   // split-K of the 3136-deep l1 contraction (98 k-tiles)
-constexpr float INV255 = 1.0f / 255.0f;
 
 // ================================================================================================
 // forward policies
@@ -460,8 +459,42 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const float* __restrict
     }
 }
 
-// All three conv layers' partial reductions in ONE launch: 32 outputs x 8 chunk groups per workgroup
-// (chunk c -> group c % 8), fixed-order combine => deterministic.
+// The conv layers' partial sums in 8 chunk groups x 32 elements per workgroup of 256 threads: the one statement of the order that
+// k_reduce_adam (dqn.hip, T = float) and k_cdqn_conv_reduce_adam (candle_dqn.hip, T = f32x4) share, so that their gradients are
+// reproducible and agree.  sg: the segment's partials, chunks of stride floats (const float* part; size_t stride; int chunks); element i of chunk c is the T at
+// sg.part[c * sg.stride + i * (floats of a T)]; `in`: i is inside the segment.
+// Group g = threadIdx.x >> 5 adds the chunks g, g + 8, g + 16, ... in ascending order, one add each (loads issued four chunks
+// ahead); the eight sums meet in red, and behind the barrier group 0 adds red[0 ... 7] in ascending order and hands the total to
+// done(t).  Every thread of the workgroup must call it (the barrier).
+template <class T, class Seg, class I, class F>
+__device__ __forceinline__ void reduce_partials_8x32(T (&red)[8][32], const Seg& sg, I i, bool in, F&& done)
+{
+    const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    constexpr size_t W = sizeof(T) / sizeof(float);
+    auto ld = [&](int c) { return *reinterpret_cast<const T*>(sg.part + ((size_t)c * sg.stride + i * W)); };
+    T s{};
+    if (in) {
+        int c = grp;
+        for (; c + 24 < sg.chunks; c += 32) {
+            const T v0 = ld(c), v1 = ld(c + 8), v2 = ld(c + 16), v3 = ld(c + 24);
+            s += v0; s += v1; s += v2; s += v3;
+        }
+        for (; c < sg.chunks; c += 8) s += ld(c);
+    }
+    red[grp][o] = s;
+    __syncthreads();
+    if (grp == 0 && in) {
+        T t = red[0][o];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) t += red[k][o];
+        done(t);
+    }
+}
+
+// All three conv layers' partial reductions in ONE launch, gradients only: the segment walk of k_reduce_adam (dqn.hip) without the
+// optimizer step.  Launched by nothing since k_reduce_adam took the step in; it stays for one measured reason: with this kernel
+// deleted and nothing else changed, the tch DQN's step ran 0.3 - 0.4 % slower (every later kernel of the code object moves;
+// profiles/ab_conv_dw_plan.txt).  Remove it together with a change that re-measures the step.
 struct ReduceSeg { const float* part; size_t stride; int chunks; float* g; int n, n_weights; float wscale; int wg0; };
 struct Reduce3Args { ReduceSeg seg[3]; };
 __global__ __launch_bounds__(256) void k_reduce_partials3(Reduce3Args a)
@@ -469,52 +502,8 @@ __global__ __launch_bounds__(256) void k_reduce_partials3(Reduce3Args a)
     __shared__ float red[8][32];
     const int s_id = (int)blockIdx.x >= a.seg[2].wg0 ? 2 : ((int)blockIdx.x >= a.seg[1].wg0 ? 1 : 0);
     const ReduceSeg& sg = a.seg[s_id];
-    const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = ((int)blockIdx.x - sg.wg0) * 32 + o;
-    float s = 0.f;
-    if (i < sg.n) {
-        int c = grp;
-        for (; c + 24 < sg.chunks; c += 32) {
-            const float v0 = sg.part[(size_t)c * sg.stride + i], v1 = sg.part[(size_t)(c + 8) * sg.stride + i];
-            const float v2 = sg.part[(size_t)(c + 16) * sg.stride + i], v3 = sg.part[(size_t)(c + 24) * sg.stride + i];
-            s += v0; s += v1; s += v2; s += v3;
-        }
-        for (; c < sg.chunks; c += 8) s += sg.part[(size_t)c * sg.stride + i];
-    }
-    red[grp][o] = s;
-    __syncthreads();
-    if (grp == 0 && i < sg.n) {
-        float t = red[0][o];
-#pragma unroll
-        for (int k = 1; k < 8; ++k) t += red[k][o];
-        sg.g[i] = i < sg.n_weights ? t * sg.wscale : t;
-    }
-}
-
-// chunk counts of the weight-gradient reductions (rows M split across workgroups)
-struct DwPlan { int chunks_c1, chunks_c2, chunks_c3; size_t stride_c1, stride_c2, stride_c3, off_c1, off_c2, off_c3, total; };
-DwPlan dw_plan(int B, int ns = 4)
-{
-    DwPlan p{};
-    auto mt = [](int M) { return (M + 31) / 32; };
-    p.chunks_c1 = std::min(256, B);           // conv1: one partial per workgroup, workgroups stride over the images
-    p.chunks_c2 = std::min(64, mt(B * 81));
-    p.chunks_c3 = std::min(56, mt(B * 49));
-    // diagnostics (A/B of the partial-sum traffic): BDR_DW_CHUNKS="c1,c2,c3" caps the three counts (c2 / c3: multiples of 8 keep the XCD map)
-    if (const char* e = getenv("BDR_DW_CHUNKS")) {
-        int c1 = 0, c2 = 0, c3 = 0;
-        if (sscanf(e, "%d,%d,%d", &c1, &c2, &c3) == 3) {
-            if (c1 > 0) p.chunks_c1 = std::min(p.chunks_c1, c1);
-            if (c2 > 0) p.chunks_c2 = std::min(p.chunks_c2, c2);
-            if (c3 > 0) p.chunks_c3 = std::min(p.chunks_c3, c3);
-        }
-    }
-    p.stride_c1 = (size_t)64 * ns * 32 + 32; p.stride_c2 = 512 * 64 + 64; p.stride_c3 = 576 * 64 + 64;
-    p.off_c1 = 0;
-    p.off_c2 = p.off_c1 + p.chunks_c1 * p.stride_c1;
-    p.off_c3 = p.off_c2 + p.chunks_c2 * p.stride_c2;
-    p.total = p.off_c3 + p.chunks_c3 * p.stride_c3;
-    return p;
+    const int i = ((int)blockIdx.x - sg.wg0) * 32 + (threadIdx.x & 31);
+    reduce_partials_8x32(red, sg, i, i < sg.n, [&](float t) { sg.g[i] = i < sg.n_weights ? t * sg.wscale : t; });
 }
 
 }  // namespace

@@ -1,9 +1,13 @@
 // Parameter arena of the Nature-CNN trunk (conv1 8x8/4, conv2 4x4/2, conv3 3x3/1; border-tch-agent/src/cnn/base.rs:23-36) and the
-// conversion of its six conv tensors between the reference's layout and the internal one.  No HIP in here: the three agents that run
+// conversion of its six conv tensors between the reference's layout and the internal one, and the plan of the conv layers'
+// weight-gradient partials (conv_dw_plan).  No HIP in here: the three agents that run
 // the trunk (dqn.hip, iqn.hip, candle_dqn.hip) share this one copy, and it is tested on its own with the host compiler
 // (tests/test_conv_layout_host.py).
 #pragma once
+#include <algorithm>
 #include <cstddef>
+#include <cstdio>
+#include <cstdlib>
 
 namespace bdr {
 
@@ -63,5 +67,43 @@ inline size_t conv_layout_walk(const Arena& ar, F f)
 // the caller's own tail (l1 / head / cos layer) continues at the returned count of reference floats
 inline size_t conv_to_internal(const Arena& ar, const float* ref, float* in) { return conv_layout_walk(ar, [&](size_t r, size_t i) { in[i] = ref[r]; }); }
 inline size_t conv_to_reference(const Arena& ar, const float* in, float* ref) { return conv_layout_walk(ar, [&](size_t r, size_t i) { ref[r] = in[i]; }); }
+
+// ---- weight-gradient partials of the three conv layers -------------------------------------------
+// A conv layer's dW kernel splits its rows across workgroups and leaves one partial sum per chunk: part[off + chunk * stride + i],
+// a chunk = the layer's weights, then its bias (the layer's gradient segment of the arena, n floats at w).  The buffer is laid out
+// for the batch CAPACITY; a batch of Bn <= capacity images fills the first chunks(Bn) chunks of each layer, and the reduction behind
+// the dW launch sums exactly those.  The one place that knows the split: the dW launches and every reduction read it from here.
+constexpr float INV255 = 1.0f / 255.0f;   // cnn/base.rs:26 "/ 255": conv1's kernels multiply raw u8 operands
+struct ConvDwLayer {
+    size_t off, stride;   // floats: the layer's partials in the partial buffer, and one chunk of them
+    int allocated;        // chunks the buffer holds
+    int rows;             // GEMM rows per image that 32-row tiles split into chunks (0: conv1, one partial per workgroup, workgroups stride over the images)
+    int n, n_weights;     // floats of the gradient segment (= stride), the weights among them
+    size_t w;             // arena offset of the segment
+    float wscale;         // applied to the weights' sums
+    int wgs;              // dW workgroups per chunk
+    int chunks(int Bn) const { return std::min(allocated, rows ? (Bn * rows + 31) / 32 : Bn); }
+};
+struct ConvDwPlan { ConvDwLayer layer[3]; size_t total; };   // [0] conv1, [1] conv2, [2] conv3; total floats of the partial buffer
+inline ConvDwPlan conv_dw_plan(const Arena& ar, int B)
+{
+    ConvDwPlan p{};
+    const int cap[3] = {256, 64, 56}, rows[3] = {0, 81, 49}, nw[3] = {(int)ar.n_w1(), 512 * 64, 576 * 64}, nb[3] = {32, 64, 64}, wgs[3] = {1, 8, 9};
+    const size_t seg[3] = {ar.w1, ar.w2, ar.w3};
+    // diagnostics (A/B of the partial-sum traffic): BDR_DW_CHUNKS="c1,c2,c3" caps the three counts (c2 / c3: multiples of 8 keep the XCD map)
+    int env[3] = {0, 0, 0};
+    if (const char* e = getenv("BDR_DW_CHUNKS")) { if (sscanf(e, "%d,%d,%d", &env[0], &env[1], &env[2]) != 3) env[0] = env[1] = env[2] = 0; }
+    for (int k = 0; k < 3; ++k) {
+        ConvDwLayer& l = p.layer[k];
+        l.rows = rows[k]; l.allocated = cap[k];
+        l.allocated = l.chunks(B);
+        if (env[k] > 0) l.allocated = std::min(l.allocated, env[k]);
+        l.n_weights = nw[k]; l.n = nw[k] + nb[k]; l.stride = (size_t)l.n;
+        l.w = seg[k]; l.wscale = k == 0 ? INV255 : 1.0f; l.wgs = wgs[k];
+        l.off = p.total;
+        p.total += l.allocated * l.stride;
+    }
+    return p;
+}
 
 }  // namespace bdr

@@ -499,20 +499,20 @@ int32_t ensure_batch(DqnCnn* a, int B)
     BDR_TRY(alloc_f(&a->dy1, B * CONV_A1_ROW));
     BDR_TRY(alloc_f(&a->dq, B)); BDR_TRY(alloc_f(&a->pred, B)); BDR_TRY(alloc_f(&a->tgt, B));
     BDR_TRY(alloc_f(&a->loss_row, B));
-    const DwPlan p = dw_plan(B, a->ar.ns);
-    BDR_TRY(alloc_f(&a->part, p.total));
-    a->part_floats = p.total;
+    a->part_floats = conv_dw_plan(a->ar, B).total;
+    BDR_TRY(alloc_f(&a->part, a->part_floats));
     a->B = B;
     return BDR_OK;
 }
 
 // Conv partial reduction and the Adam step in ONE launch (one launch boundary less on the critical path):
-//   blocks [0, reduce_blocks)  : k_reduce_partials3's job for 32 conv-gradient elements each, immediately followed by
+//   blocks [0, reduce_blocks)  : the fixed-order sum of the partials (cnn_layers.hpp reduce_partials_8x32) for 32 conv-gradient
+//                                elements each, one walk of blocks over the three segments (wg0), immediately followed by
 //                                the Adam update of those same elements (the conv layers: 78 k of the 1.69 M parameters);
 //   remaining blocks           : Adam over the rest of the arena (l1, l2), four elements per thread.
-// Element formulas are k_reduce_partials3's and k_adam's, unchanged.
+// Element formulas are reduce_partials_8x32's and k_adam's, unchanged.
 struct ConvReduceAdamArgs {
-    Reduce3Args r;
+    ReduceSeg seg[3];
     float* p; const float* g; float* m; float* v;
     float* gbase;            // start of the gradient arena (segment gradients live at seg.g = gbase + offset)
     size_t rest0_4, n4;      // Adam's f32x4 range [rest0_4, n4) = everything behind the conv segments
@@ -600,26 +600,10 @@ __global__ __launch_bounds__(256) void k_reduce_adam(ConvReduceAdamArgs a)
     }
     __shared__ float red[8][32];
     const int bx = (int)blockIdx.x + a.wg_base;   // block index in the walk over all three segments
-    const int s_id = bx >= a.r.seg[2].wg0 ? 2 : (bx >= a.r.seg[1].wg0 ? 1 : 0);
-    const ReduceSeg& sg = a.r.seg[s_id];
-    const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = (bx - sg.wg0) * 32 + o;
-    float s = 0.f;
-    if (i < sg.n) {
-        int c = grp;
-        for (; c + 24 < sg.chunks; c += 32) {
-            const float v0 = sg.part[(size_t)c * sg.stride + i], v1 = sg.part[(size_t)(c + 8) * sg.stride + i];
-            const float v2 = sg.part[(size_t)(c + 16) * sg.stride + i], v3 = sg.part[(size_t)(c + 24) * sg.stride + i];
-            s += v0; s += v1; s += v2; s += v3;
-        }
-        for (; c < sg.chunks; c += 8) s += sg.part[(size_t)c * sg.stride + i];
-    }
-    red[grp][o] = s;
-    __syncthreads();
-    if (grp == 0 && i < sg.n) {
-        float t = red[0][o];
-#pragma unroll
-        for (int k = 1; k < 8; ++k) t += red[k][o];
+    const int s_id = bx >= a.seg[2].wg0 ? 2 : (bx >= a.seg[1].wg0 ? 1 : 0);
+    const ReduceSeg& sg = a.seg[s_id];
+    const int i = (bx - sg.wg0) * 32 + (threadIdx.x & 31);
+    reduce_partials_8x32(red, sg, i, i < sg.n, [&](float t) {
         const float g = i < sg.n_weights ? t * sg.wscale : t;
         sg.g[i] = g;
         if (poisoned) return;
@@ -628,7 +612,7 @@ __global__ __launch_bounds__(256) void k_reduce_adam(ConvReduceAdamArgs a)
         adam_element(pe, g, me, ve, a.s);
         a.p[e] = pe; a.m[e] = me; a.v[e] = ve;
         if (a.cpl && s_id >= 1 && i < sg.n_weights) conv_plane_store(a.cpl, s_id - 1, i, pe);
-    }
+    });
 }
 
 int effective_sched(DqnCnn* a);   // (defined with update_critic)
@@ -856,7 +840,7 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
         BDR_HIP(hipStreamWaitEvent(a->side, a->ev_fork[k], 0));
         return BDR_OK;
     };
-    const DwPlan pl = dw_plan(a->B, ar.ns);   // buffer layout follows the allocated batch capacity
+    const ConvDwPlan pl = conv_dw_plan(ar, a->B);   // buffer layout follows the allocated batch capacity; chunk counts follow the batch
     const bool defer = a->defer_adam;  // backward only: the optimizer step is apply_grads()
     const bool tail = gated && BDR_TAIL_OVERLAP != 0 && !defer;   // overlapped tail, see the gated branch below
     if (!defer) a->adam_step += 1;
@@ -892,10 +876,10 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
         return BDR_OK;
     };
     auto c3_dw = [&]() -> int32_t {
-        const int M = B * 49, chunks = std::min(pl.chunks_c3, (M + 31) / 32);
-        DwArgs d{a->a2[0], a->dy3, a->part + pl.off_c3, pl.stride_c3, M};
+        const ConvDwLayer& l = pl.layer[2];
+        DwArgs d{a->a2[0], a->dy3, a->part + l.off, l.stride, B * 49};
         Bracket br(a, "bwd_conv3_dw");
-        LAUNCH_FL(sd, any, nullptr, k_igemm_red<DwC3>, dim3(9 * chunks), dim3(256), d);
+        LAUNCH_FL(sd, any, nullptr, k_igemm_red<DwC3>, dim3(l.wgs * l.chunks(B)), dim3(256), d);
         return BDR_OK;
     };
     auto c3_dx = [&]() -> int32_t {
@@ -905,10 +889,10 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
         return BDR_OK;
     };
     auto c2_dw = [&]() -> int32_t {
-        const int M = B * 81, chunks = std::min(pl.chunks_c2, (M + 31) / 32);
-        DwArgs d{a->a1[0], a->dy2, a->part + pl.off_c2, pl.stride_c2, M, nullptr, 0};
+        const ConvDwLayer& l = pl.layer[1];
+        DwArgs d{a->a1[0], a->dy2, a->part + l.off, l.stride, B * 81, nullptr, 0};
         Bracket br(a, "bwd_conv2_dw");
-        LAUNCH_FL(sd, any, ov && a->kev ? a->ev_join : nullptr, k_igemm_red<DwC2>, dim3(8 * chunks), dim3(256), d);
+        LAUNCH_FL(sd, any, ov && a->kev ? a->ev_join : nullptr, k_igemm_red<DwC2>, dim3(l.wgs * l.chunks(B)), dim3(256), d);
         return BDR_OK;
     };
     auto c2_dx = [&]() -> int32_t {
@@ -924,34 +908,25 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
         return BDR_OK;
     };
     auto c1_dw = [&]() -> int32_t {   // conv1 has no input gradient
-        const int chunks = std::min(pl.chunks_c1, B);
-        Conv1DwArgs d{obs, a->dy1, a->part + pl.off_c1, pl.stride_c1, B, tail ? sigf(SIG_DXC2) : nullptr, epoch};   // tail: its start publishes "conv2 dX done"
+        const ConvDwLayer& l = pl.layer[0];
+        Conv1DwArgs d{obs, a->dy1, a->part + l.off, l.stride, B, tail ? sigf(SIG_DXC2) : nullptr, epoch};   // tail: its start publishes "conv2 dX done"
         Bracket br(a, "bwd_conv1_dw");
-        BDR_HIP(launch_conv1_dw_bf16(ar.ns, dim3(chunks), a->stream, d));
+        BDR_HIP(launch_conv1_dw_bf16(ar.ns, dim3(l.wgs * l.chunks(B)), a->stream, d));
         return BDR_OK;
     };
 
     // conv partials -> gradient arena + the conv layers' Adam step (k_reduce_adam) for the segments [lo, hi) of {conv1, conv2, conv3} on queue st;
     // l1 / l2: adam_l1_l2 above.  A launch over a sub-range runs the same blocks of the same walk (wg_base), so every element sees the same code.
     auto reduce_adam = [&](hipStream_t st, int lo, int hi) -> int32_t {
-        Reduce3Args r{};
-        const int Ms[3] = {B * 400, B * 81, B * 49};
-        const int plc[3] = {pl.chunks_c1, pl.chunks_c2, pl.chunks_c3};
-        const size_t offs[3] = {pl.off_c1, pl.off_c2, pl.off_c3}, strides[3] = {pl.stride_c1, pl.stride_c2, pl.stride_c3};
-        const size_t gw[3] = {ar.w1, ar.w2, ar.w3};
-        const int nw[3] = {(int)ar.n_w1(), 512 * 64, 576 * 64}, nb[3] = {32, 64, 64};
-        int wg = 0, wg0[4];
-        for (int k = 0; k < 3; ++k) {
-            const int nchunks = k == 0 ? std::min(plc[0], B) : std::min(plc[k], (Ms[k] + 31) / 32);   // conv1: one partial per workgroup
-            r.seg[k] = ReduceSeg{a->part + offs[k], strides[k], nchunks, a->grad + gw[k], nw[k] + nb[k], nw[k],
-                                 k == 0 ? INV255 : 1.0f, wg};
-            wg0[k] = wg;
-            wg += (nw[k] + nb[k] + 31) / 32;
-        }
-        wg0[3] = wg;
-        const int64_t lag = a->conv_lag[lo == 0 ? 0 : 1];   // (a launch over all three segments: both lags are equal, see below)
         ConvReduceAdamArgs ra{};
-        ra.r = r; ra.p = a->q; ra.g = a->grad; ra.m = a->m; ra.v = a->v; ra.gbase = a->grad;
+        int wg0[4] = {0, 0, 0, 0};   // the walk of blocks over the three segments: 32 outputs per block
+        for (int k = 0; k < 3; ++k) {
+            const ConvDwLayer& l = pl.layer[k];
+            ra.seg[k] = ReduceSeg{a->part + l.off, l.stride, l.chunks(B), a->grad + l.w, l.n, l.n_weights, l.wscale, wg0[k]};
+            wg0[k + 1] = wg0[k] + (l.n + 31) / 32;
+        }
+        const int64_t lag = a->conv_lag[lo == 0 ? 0 : 1];   // (a launch over all three segments: both lags are equal, see below)
+        ra.p = a->q; ra.g = a->grad; ra.m = a->m; ra.v = a->v; ra.gbase = a->grad;
         ra.rest0_4 = ra.n4 = ar.w4 / 4; ra.s = lag ? adam_scalars(c, (uint64_t)std::max<int64_t>((int64_t)a->adam_step - lag, 1)) : adam_s;
         ra.applied = defer ? nullptr : a->applied_step + (lo == 0 ? 1 : 2); ra.step = (unsigned long long)((int64_t)a->adam_step - lag);
         ra.applied2 = !defer && lo == 0 && hi == 3 ? a->applied_step + 2 : nullptr;

@@ -247,7 +247,7 @@ struct Iqn : bdr_agent {
         if (cnn) {
             BDR_TRY(zalloc(&a1, Bn * CONV_A1_ROW)); BDR_TRY(zalloc(&a2, Bn * CONV_A2_ROW)); BDR_TRY(zalloc(&a3, Bn * CONV_A3_ROW));
             BDR_TRY(zalloc(&dy3, Bn * CONV_A3_ROW)); BDR_TRY(zalloc(&dy2, Bn * CONV_A2_ROW)); BDR_TRY(zalloc(&dy1, Bn * CONV_A1_ROW));
-            BDR_TRY(zalloc(&part_conv, dw_plan(Bn, conv.ns).total));
+            BDR_TRY(zalloc(&part_conv, conv_dw_plan(conv, Bn).total));
         } else {
             BDR_TRY(zalloc(&x_in, (size_t)Bn * psi_mlp.L[0].Kp));
             for (const auto& l : psi_mlp.L) { float *q = nullptr, *d = nullptr; BDR_TRY(zalloc(&q, (size_t)Bn * l.Np)); BDR_TRY(zalloc(&d, (size_t)Bn * l.Np)); psi_act.push_back(q); psi_dy.push_back(d); }
@@ -408,10 +408,8 @@ struct Iqn : bdr_agent {
         // psi backward
         if (cnn) {
             // each layer's partial sums are reduced into grad right behind its dW launch (a chunk = the layer's weights, then its bias)
-            auto reduce = [&](int k, int chunks, const float* lp, size_t stride) -> int32_t {
-                const size_t w[3] = {conv.w1, conv.w2, conv.w3};
-                const int n = (int)stride, nw = n - (k == 0 ? 32 : 64);
-                hipLaunchKernelGGL(k_reduce_partials, dim3((n + 63) / 64), dim3(256), 0, stream, lp, stride, chunks, grad + w[k], n, nw, k == 0 ? INV255 : 1.0f);
+            auto reduce = [&](const ConvDwLayer& l, int chunks, const float* lp) -> int32_t {
+                hipLaunchKernelGGL(k_reduce_partials, dim3((l.n + 63) / 64), dim3(256), 0, stream, lp, l.stride, chunks, grad + l.w, l.n, l.n_weights, l.wscale);
                 BDR_HIP(hipGetLastError());
                 return BDR_OK;
             };

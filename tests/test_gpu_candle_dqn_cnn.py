@@ -170,6 +170,29 @@ def test_a_ragged_batch_of_33(B):
     a.close(); b.close()
 
 
+def test_a_batch_below_the_capacity_takes_the_same_step_bit_for_bit(B):
+    """An agent built for 5 rows and one built for 2 take the same 2-row update: the weight-gradient partials are laid out for the
+    capacity (conv_layout.hpp's conv_dw_plan) - conv2's and conv3's sit at other offsets in the two agents - but the chunks a batch
+    fills follow the batch, 2, ceil(162 / 32) = 6 and ceil(98 / 32) = 4 in both, so k_cdqn_conv_reduce_adam sums the same sums:
+    parameters, target parameters and the gradient arena equal byte for byte."""
+    spec = R.CandleDqnCnnSpec(4, 6, lr=1e-4, tau=0.3, adamw=ADAMW, double_dqn=True)
+    params = spec.init_params(91)
+    assert (params[0] != params[1]).any()
+    batch = R.make_batch(spec, 2, 92)
+    got = []
+    for cap in (5, 2):
+        a = _agent(B, spec, cap, params)
+        rec = a.update_on_batch(*batch)
+        got.append((rec, a.get_params("qnet"), a.get_params("qnet_tgt"), a.get_params("qnet", "grad")))
+        a.close()
+    (ra, pa, ta, ga), (rb, pb, tb, gb) = got
+    assert ra == rb
+    assert pa.tobytes() == pb.tobytes() and ta.tobytes() == tb.tobytes() and ga.tobytes() == gb.tobytes()
+    sl = R.var_slices(4, 6)
+    for v in R.VAR_NAMES:   # the update ran: a gradient, a step and a soft update of every variable
+        assert np.abs(ga[sl[v]]).max() > 0 and (pa[sl[v]] != params[0][sl[v]]).any() and (ta[sl[v]] != params[1][sl[v]]).any(), v
+
+
 # ---------------------------------------------------------------------------------------------------------- the optimizer rule
 @pytest.mark.parametrize("kind", ("AdamW", "Adam"))
 def test_one_optimizer_step_and_the_soft_update_element_by_element(B, kind):

@@ -85,7 +85,7 @@ def test_one_update_runs_the_psi_trunk_in_its_fixed_launch_order(B):
     """From the profile brackets of one update at the iqn_cnn_b2 shapes: the trunk's three forward launches once for the target network
     and once for the online one, later the backward chain conv3 dW, conv3 dX, conv2 dW, conv2 dX, conv1 dW (csrc/conv_trunk.hpp).
     B = 2 is the smallest batch and sits under every chunk clamp of the weight gradients: conv1 has fewer images than its chunk cap,
-    conv2 / conv3 have (M + 31) / 32 = 6 / 4 row tiles against dw_plan's caps of 64 / 56."""
+    conv2 / conv3 have (M + 31) / 32 = 6 / 4 row tiles against conv_dw_plan's caps of 64 / 56."""
     import bench
     kind, F_, E, fu, A, pin, pu, Bsz, n_p, n_t, steps, lr, sh, p0, seed = MG.iqn_case("iqn_cnn_b2")
     assert kind == "cnn" and Bsz == 2
@@ -97,6 +97,31 @@ def test_one_update_runs_the_psi_trunk_in_its_fixed_launch_order(B):
     a.close()
     assert psi == ["psi_conv1", "psi_conv2", "psi_conv3", "psi_conv1", "psi_conv2", "psi_conv3",
                    "psi_conv3_dw", "psi_conv3_dx", "psi_conv2_dw", "psi_conv2_dx", "psi_conv1_dw"], psi
+
+
+def test_a_batch_below_the_capacity_takes_the_same_step_bit_for_bit(B):
+    """An agent built for 5 rows and one built for 2 take the same 2-row update (the iqn_cnn_b2 batch, online and target networks
+    different): the weight-gradient partials are laid out for the capacity (conv_layout.hpp's conv_dw_plan) - conv2's and conv3's
+    sit at other offsets in the two agents - but the chunks a batch fills follow the batch, 2, ceil(162 / 32) = 6 and
+    ceil(98 / 32) = 4 in both, so the sums are the same sums: parameters, target parameters and gradients equal byte for byte."""
+    from oracle import torch_ref as T
+    kind, F_, E, fu, A, pin, pu, Bsz, n_p, n_t, steps, lr, sh, p0, seed = MG.iqn_case("iqn_cnn_b2")
+    assert kind == "cnn" and Bsz == 2
+    p_tgt = T.init_params(sh[0] + sh[1] + sh[2], seed + 1)
+    assert p_tgt.shape == p0.shape and (p_tgt != p0).any()
+    batch = MG.iqn_case_batch("iqn_cnn_b2", 0)
+    got = []
+    for cap in (5, 2):
+        a = _agent(B, kind, F_, E, fu, A, pin, pu, cap, lr, p0, tau=0.01, soft_update_interval=1)
+        a.set_params(p_tgt, "iqn_tgt")
+        rec = a.update_on_batch(*batch)
+        got.append((rec["loss_critic"], a.get_params("iqn"), a.get_params("iqn_tgt"), a.get_params("grad")))
+        a.close()
+    (la, pa, ta, ga), (lb, pb, tb, gb) = got
+    assert la == lb
+    assert pa.tobytes() == pb.tobytes() and ta.tobytes() == tb.tobytes() and ga.tobytes() == gb.tobytes()
+    n_conv = 2048 * 4 + 32 + 32768 + 64 + 36864 + 64
+    assert np.abs(ga[:n_conv]).max() > 0 and (pa != p0).any() and (ta != p_tgt).any()   # the update ran: conv gradients, a step, a soft update
 
 
 @pytest.mark.parametrize("A", [6, 4, 9, 18, 33])
