@@ -270,7 +270,7 @@ ABI_SYMBOLS = [
     "bdr_agent_set_params", "bdr_agent_arena_device_ptr", "bdr_agent_arena_release", "bdr_agent_save_params", "bdr_agent_load_params", "bdr_agent_set_checkpoint_format",
     "bdr_checkpoint_write", "bdr_checkpoint_read", "bdr_dqn_probe",
     "bdr_agent_profile_enable", "bdr_agent_profile_read",
-    "bdr_iqn_config_default", "bdr_iqn_create", "bdr_iqn_update_on_batch", "bdr_iqn_forward", "bdr_iqn_qvalues",
+    "bdr_iqn_config_default", "bdr_iqn_create", "bdr_iqn_update_on_batch", "bdr_iqn_forward", "bdr_iqn_qvalues", "bdr_iqn_probe",
     "bdr_sac_config_default", "bdr_sac_create", "bdr_sac_update_on_batch", "bdr_sac_sample", "bdr_sac_sample_device",
     "bdr_iql_config_default", "bdr_iql_create", "bdr_iql_update_on_batch", "bdr_iql_probe", "bdr_iql_sample", "bdr_iql_sample_device",
     "bdr_awac_config_default", "bdr_awac_create", "bdr_awac_update_on_batch", "bdr_awac_probe", "bdr_awac_sample", "bdr_awac_sample_device",
@@ -397,6 +397,7 @@ def lib() -> C.CDLL:
     L.bdr_iqn_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     L.bdr_iqn_forward.argtypes = [vp, i32, u64, vp, vp, i32, vp]
     L.bdr_iqn_qvalues.argtypes = [vp, u64, vp, vp, vp]
+    L.bdr_iqn_probe.argtypes = [vp, i32, vp, u64]
     L.bdr_sac_config_default.argtypes = [C.POINTER(SacConfigC)]
     L.bdr_sac_create.argtypes = [C.POINTER(SacConfigC), C.POINTER(vp)]
     L.bdr_sac_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]

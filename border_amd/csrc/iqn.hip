@@ -170,6 +170,8 @@ struct Iqn : bdr_agent {
     uint8_t *u_obs = nullptr, *u_next = nullptr, *u_act = nullptr; float* u_rew = nullptr; int8_t* u_term = nullptr; uint64_t u_cap = 0;
     uint64_t adam_step = 0, soft_update_counter = 0, noise_counter = 0;
     int n_updates_done = 0;
+    // what the batch buffers hold, for bdr_iqn_probe: rows / percent points of the last model_forward, and of the last update_critic
+    int fwd_B = 0, fwd_N = 0, upd_B = 0, upd_Np = 0, upd_Nt = 0;
     // acting calls (bdr_iqn_qvalues on a handful of observations): the trunk's conv2 / conv3 and the merge layer take the acting kernels
     // (act_small.hpp): at 33 percent points per observation the merge layer is a [33 n][3136] x [3136][512] product that the training
     // kernel walks in 8 workgroups of 98 k-tiles (71 us of a 175 us call)
@@ -228,6 +230,7 @@ struct Iqn : bdr_agent {
         float** singles[] = {&a1, &a2, &a3, &dy3, &dy2, &dy1, &part_conv, &x_in, &tau_p, &tau_t, &cosv, &phi, &mrg, &tgt, &loss_row, &qavg, &part};
         for (auto q : singles) { (void)hipFree(*q); *q = nullptr; }
         for (auto v : {&psi_act, &psi_dy, &f_act, &f_dy}) { for (auto q : *v) (void)hipFree(q); v->clear(); }
+        fwd_B = fwd_N = upd_B = upd_Np = upd_Nt = 0;
     }
     int32_t zalloc(float** q, size_t n)
     {
@@ -307,6 +310,7 @@ struct Iqn : bdr_agent {
         const float* feat; int ldf;
         BDR_TRY(psi_forward(params, obs, Bn, &feat, &ldf));
         const int M = Bn * N, Ep = hd.L[0].Kp;
+        fwd_B = Bn; fwd_N = N;
         { Bracket br(a, "iqn_cos"); hipLaunchKernelGGL(k_iqn_cos, dim3((M * Ep + 255) / 256), dim3(256), 0, stream, tau, cosv, M, E, Ep); BDR_HIP(hipGetLastError()); }
         // phi = relu(cos-embedding * W + b); the merge m = phi * psi(x)[b] (iqn/model/base.rs) is the input of the next layer and of
         // its weight gradient and is formed inside those two GEMMs on the way into LDS: [B*N][F] floats that are never written
@@ -422,6 +426,7 @@ struct Iqn : bdr_agent {
                 if (i > 0) { Bracket br(a, "psi_dx"); BDR_TRY(dense_dx(stream, psi_mlp.L[i], p, psi_dy[i], psi_dy[i - 1], psi_act[i - 1], Bn)); }
             }
         }
+        upd_B = Bn; upd_Np = Np; upd_Nt = Nt;
         adam_step += 1;
         {   // IqnModel::backward_step (iqn/model/base.rs) -> opt.rs:74-83; OptimizerConfig::{Adam, AdamW} (opt.rs:30-57)
             const bdr_adamw_config& o = cfg.opt;
@@ -611,6 +616,52 @@ struct Iqn : bdr_agent {
         BDR_TRY(load_named(ckpt_load_path(this, dir, "iqn_tgt"), meta(), ref.data(), ref.size()));
         return set_params(1, ref.data(), ref.size());
     }
+    // bdr_iqn_probe: the raw buffer `what` names, with its padded leading dimension, as the last model_forward / update_critic left it.
+    // Forward buffers hold fwd_B x fwd_N rows (after an update: the online network's pass on `obs`), gradient buffers upd_B x upd_Np.
+    int32_t probe(int32_t what, float* out, uint64_t n)
+    {
+        const float* src = nullptr;
+        size_t want = 0;
+        bool grad_buf = false;
+        const size_t Mf = (size_t)fwd_B * fwd_N, Mu = (size_t)upd_B * upd_Np;
+        const int Fp = hd.L[0].Np, Ep = hd.L[0].Kp, ldf = cnn ? 3136 : psi_mlp.L.back().Np;
+        const int nf = (int)hd.L.size() - 1, np_ = (int)psi_mlp.L.size();
+        switch (what) {
+            case BDR_IQN_PROBE_COS: src = cosv; want = Mf * Ep; break;
+            case BDR_IQN_PROBE_PHI: src = phi; want = Mf * Fp; break;
+            case BDR_IQN_PROBE_PSI: src = cnn ? a3 : psi_act.back(); want = (size_t)fwd_B * ldf; break;
+            case BDR_IQN_PROBE_DLIN: src = mrg; want = Mu * Fp; grad_buf = true; break;
+            case BDR_IQN_PROBE_DPSI: src = cnn ? dy3 : psi_dy.back(); want = (size_t)upd_B * ldf; grad_buf = true; break;
+            case BDR_IQN_PROBE_TGT: src = tgt; want = (size_t)upd_B * upd_Nt; grad_buf = true; break;
+            case BDR_IQN_PROBE_LOSS_ROW: src = loss_row; want = upd_B; grad_buf = true; break;
+            case BDR_IQN_PROBE_A1: case BDR_IQN_PROBE_A2: case BDR_IQN_PROBE_DY2: case BDR_IQN_PROBE_DY1: {
+                BDR_REQUIRE(cnn, "probe %d needs the AtariCnn feature extractor", what);
+                grad_buf = what == BDR_IQN_PROBE_DY2 || what == BDR_IQN_PROBE_DY1;
+                const bool l1 = what == BDR_IQN_PROBE_A1 || what == BDR_IQN_PROBE_DY1;
+                src = what == BDR_IQN_PROBE_A1 ? a1 : what == BDR_IQN_PROBE_A2 ? a2 : what == BDR_IQN_PROBE_DY2 ? dy2 : dy1;
+                want = (size_t)(grad_buf ? upd_B : fwd_B) * (l1 ? CONV_A1_ROW : CONV_A2_ROW);
+                break;
+            }
+            default: {
+                const int base = what & ~15, i = what & 15;
+                if ((base == BDR_IQN_PROBE_F_ACT || base == BDR_IQN_PROBE_F_DY) && i < nf) {
+                    grad_buf = base == BDR_IQN_PROBE_F_DY;
+                    src = grad_buf ? f_dy[i] : f_act[i];
+                    want = (grad_buf ? Mu : Mf) * hd.L[i + 1].Np;
+                } else if (!cnn && (base == BDR_IQN_PROBE_PSI_ACT || base == BDR_IQN_PROBE_PSI_DY) && i < np_) {
+                    grad_buf = base == BDR_IQN_PROBE_PSI_DY;
+                    src = grad_buf ? psi_dy[i] : psi_act[i];
+                    want = (size_t)(grad_buf ? upd_B : fwd_B) * psi_mlp.L[i].Np;
+                } else return fail(BDR_ERR_INVALID, "unknown probe %d", what);
+            }
+        }
+        BDR_REQUIRE(fwd_B > 0 && src, "nothing to probe yet (no forward has run)");
+        BDR_REQUIRE(!grad_buf || upd_B > 0, "nothing to probe yet (no update has run on these buffers)");
+        BDR_REQUIRE(n == want, "probe %d holds %llu floats, not %llu", what, (unsigned long long)want, (unsigned long long)n);
+        BDR_HIP(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        return BDR_OK;
+    }
     int32_t stage(uint64_t n, const void* obs, const int64_t* act, const void* next_obs, const float* reward, const int8_t* term)
     {
         const size_t ob = cnn ? (size_t)7056 * conv.ns : (size_t)in_dim * 4;
@@ -783,6 +834,15 @@ int32_t bdr_iqn_qvalues(bdr_agent* base, uint64_t n, const void* obs, float* q_o
             argmax_out[i] = best;
         }
     return BDR_OK;
+}
+
+int32_t bdr_iqn_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
+{
+    BDR_REQUIRE(base && out, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "iqn"), "not an IQN agent");
+    Iqn* a = static_cast<Iqn*>(base);
+    BDR_HIP(hipSetDevice(a->device));
+    return a->probe(what, out, n);
 }
 
 }  // extern "C"

@@ -149,6 +149,31 @@ class Iqn:
         _lib.check(_lib.lib().bdr_iqn_forward(self._h, self.WHICH[which], n, _p(obs), _p(tau), nt, _p(z)))
         return z
 
+    PROBE = {"cos": 0, "phi": 1, "psi": 2, "dlin": 3, "dpsi": 4, "tgt": 5, "loss_row": 6, "a1": 7, "a2": 8, "dy2": 9, "dy1": 10,
+             "f_act": 16, "f_dy": 32, "psi_act": 48, "psi_dy": 64}   # BDR_IQN_PROBE_*
+
+    def probe(self, what: str, rows: int, i: int = 0, cols: Optional[int] = None) -> np.ndarray:
+        """bdr_iqn_probe: the raw buffer [rows][ld] that the last forward / update left behind, padding columns included (they must be
+        exactly 0, and a test can assert it).  rows: B * N for cos, phi, dlin, f_act, f_dy; B for the others.  i: the layer of f_act /
+        f_dy (merge net, the last one is z / dz) and psi_act / psi_dy (Mlp feature extractor).  cols: tgt's n_tgt.  A wrong row count
+        is an error of the library, never a short or long read.  forward() and qvalues() overwrite (or reallocate) these buffers."""
+        c, pad = self.config, lambda x: (x + 63) // 64 * 64
+        cnn = isinstance(c.f_config, AtariCnnConfig)
+        f_ld = [pad(u) for u in tuple(c.m_units) + (c.n_actions,)]
+        psi_ld = [] if cnn else [pad(u) for u in tuple(c.f_config.units) + (c.f_config.out_dim,)]
+        ldf = 3136 if cnn else pad(c.feature_dim)
+        ld = {"cos": pad(c.embed_dim), "phi": pad(c.feature_dim), "dlin": pad(c.feature_dim), "psi": ldf, "dpsi": ldf, "tgt": cols, "loss_row": 1,
+              "a1": 400 * 32, "dy1": 400 * 32, "a2": 81 * 64, "dy2": 81 * 64}.get(what)
+        if what in ("f_act", "f_dy"):
+            ld = f_ld[i]
+        elif what in ("psi_act", "psi_dy"):
+            ld = psi_ld[i]
+        if ld is None:
+            raise ValueError("unknown probe %r (or tgt without cols)" % (what,))
+        out = np.empty((rows, ld), np.float32)
+        _lib.check(_lib.lib().bdr_iqn_probe(self._h, self.PROBE[what] + (i if self.PROBE[what] >= 16 else 0), _p(out), out.size))
+        return out
+
     def sample_device(self, obs_dev: int, n: int, row_stride: int, return_info: bool = False):
         """Policy::sample for observation rows already in HBM (`bdr_agent_sample_device`): row i at obs_dev + i * row_stride bytes."""
         a = np.empty(n, np.int64)

@@ -797,6 +797,23 @@ BDR_API int32_t bdr_iqn_forward(bdr_agent* a, int32_t which, uint64_t n, const v
                                 int32_t n_tau, float* z_out);
 /* Policy::sample greedy part (iqn/base.rs:204-228): values averaged over sample_percents_act. */
 BDR_API int32_t bdr_iqn_qvalues(bdr_agent* a, uint64_t n, const void* obs, float* q_out, int64_t* argmax_out);
+/* Parity probes: the raw buffers, padded leading dimensions included, that the LAST model forward / update left behind, to the
+ * host.  M = B * N rows; Ep, Fp, Np_i = embed_dim, feature_dim, the i-th merge-net layer's width rounded up to 64 (padding columns
+ * are exactly 0); ldf = 3136 (AtariCnn) or Fp (Mlp).  Forward buffers (M = rows of the last forward; after an update that is the
+ * ONLINE network's pass on `obs` with n_pred points - the target pass went through the same buffers before it):
+ *   COS [M][Ep], PHI [M][Fp], PSI [B][ldf] (conv3's activation / the Mlp's output), F_ACT + i [M][Np_i] (hidden activations; the
+ *   last one is z), A1 [B][400][32], A2 [B][81][64] (AtariCnn), PSI_ACT + i [B][pad64(units_i)] (Mlp).
+ * Gradient buffers of the last update (M = B * n_pred):
+ *   F_DY + i [M][Np_i] (gradients at the merge net's pre-activations; the last one is dL/dz), DLIN [M][Fp] (the gradient at the
+ *   cosine layer's pre-activation), DPSI [B][ldf], TGT [B][n_tgt], LOSS_ROW [B], DY2 [B][81][64], DY1 [B][400][32] (AtariCnn),
+ *   PSI_DY + i (Mlp).
+ * n must be the buffer's float count (BDR_ERR_INVALID otherwise, as for an unknown `what` or when nothing has run yet).
+ * bdr_iqn_forward and bdr_iqn_qvalues overwrite the forward buffers, and with more rows or percent points than the agent has held
+ * so far they reallocate every buffer (the gradient buffers are then gone): probe before calling either. */
+enum { BDR_IQN_PROBE_COS = 0, BDR_IQN_PROBE_PHI = 1, BDR_IQN_PROBE_PSI = 2, BDR_IQN_PROBE_DLIN = 3, BDR_IQN_PROBE_DPSI = 4,
+       BDR_IQN_PROBE_TGT = 5, BDR_IQN_PROBE_LOSS_ROW = 6, BDR_IQN_PROBE_A1 = 7, BDR_IQN_PROBE_A2 = 8, BDR_IQN_PROBE_DY2 = 9,
+       BDR_IQN_PROBE_DY1 = 10, BDR_IQN_PROBE_F_ACT = 16, BDR_IQN_PROBE_F_DY = 32, BDR_IQN_PROBE_PSI_ACT = 48, BDR_IQN_PROBE_PSI_DY = 64 };
+BDR_API int32_t bdr_iqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
 
 /* ------------------------------------------------------------------------------------------
  * SAC agent  (border-tch-agent/src/sac/base.rs, sac/config.rs:85-105, sac/ent_coef.rs,

@@ -25,6 +25,21 @@ pub const BDR_LOSS_MSE: i32 = 0;
 pub const BDR_LOSS_SMOOTH_L1: i32 = 1;
 pub const BDR_OPT_ADAM: i32 = 0;
 pub const BDR_OPT_ADAMW: i32 = 1;
+pub const BDR_IQN_PROBE_COS: i32 = 0;
+pub const BDR_IQN_PROBE_PHI: i32 = 1;
+pub const BDR_IQN_PROBE_PSI: i32 = 2;
+pub const BDR_IQN_PROBE_DLIN: i32 = 3;
+pub const BDR_IQN_PROBE_DPSI: i32 = 4;
+pub const BDR_IQN_PROBE_TGT: i32 = 5;
+pub const BDR_IQN_PROBE_LOSS_ROW: i32 = 6;
+pub const BDR_IQN_PROBE_A1: i32 = 7;
+pub const BDR_IQN_PROBE_A2: i32 = 8;
+pub const BDR_IQN_PROBE_DY2: i32 = 9;
+pub const BDR_IQN_PROBE_DY1: i32 = 10;
+pub const BDR_IQN_PROBE_F_ACT: i32 = 16;
+pub const BDR_IQN_PROBE_F_DY: i32 = 32;
+pub const BDR_IQN_PROBE_PSI_ACT: i32 = 48;
+pub const BDR_IQN_PROBE_PSI_DY: i32 = 64;
 pub const BDR_ARITH_BF16X3_6: i32 = 0;
 pub const BDR_ARITH_F32_EXACT: i32 = 1;
 pub const BDR_ACTIVATION_NONE: i32 = 0;
@@ -990,6 +1005,7 @@ extern "C" {
     ) -> i32;
     pub fn bdr_iqn_forward(a: *mut bdr_agent, which: i32, n: u64, obs: *const c_void, tau: *const f32, n_tau: i32, z_out: *mut f32) -> i32;
     pub fn bdr_iqn_qvalues(a: *mut bdr_agent, n: u64, obs: *const c_void, q_out: *mut f32, argmax_out: *mut i64) -> i32;
+    pub fn bdr_iqn_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
 
     // ---- SAC
     pub fn bdr_sac_config_default(cfg: *mut bdr_sac_config);
