@@ -256,7 +256,7 @@ class ReplaySummaryC(C.Structure):
 # every symbol include/border_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "bdr_last_error", "bdr_last_error_is_deferred", "bdr_device_count", "bdr_version",
-    "bdr_replay_create", "bdr_replay_destroy", "bdr_replay_push", "bdr_replay_push_device", "bdr_replay_len", "bdr_replay_head", "bdr_replay_frames_used",
+    "bdr_replay_create", "bdr_replay_destroy", "bdr_replay_push", "bdr_replay_push_device", "bdr_replay_push_device_frames", "bdr_replay_len", "bdr_replay_head", "bdr_replay_frames_used",
     "bdr_replay_sample_indices", "bdr_replay_batch", "bdr_replay_last_batch", "bdr_replay_fill_synthetic",
     "bdr_replay_read_rows",
     "bdr_obs_norm_create", "bdr_obs_norm_destroy", "bdr_obs_norm_accumulate", "bdr_obs_norm_finish", "bdr_obs_norm_set", "bdr_obs_norm_get",
@@ -346,6 +346,7 @@ def lib() -> C.CDLL:
     L.bdr_replay_destroy.argtypes = [vp]
     L.bdr_replay_push.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
     L.bdr_replay_push_device.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
+    L.bdr_replay_push_device_frames.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
     L.bdr_replay_len.argtypes = [vp, C.POINTER(u64)]
     L.bdr_replay_head.argtypes = [vp, C.POINTER(u64)]
     L.bdr_replay_frames_used.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]

@@ -14,6 +14,7 @@
 
 #include "../../include/border_amd.h"
 #include "chacha.hpp"
+#include "frame_share.hpp"
 
 namespace bdr {
 
@@ -120,15 +121,15 @@ struct bdr_replay {
     //   [u32 frame slot x 2k (obs newest..oldest, next_obs newest..oldest) | act | reward f32 | is_terminated i8 | is_truncated i8]
     // and `frames` the frame store (frame_cap slots of frame_bytes, allocated in push order, slot = seq % frame_cap).
     int32_t frame_stack = 0;
-    uint64_t frame_bytes = 0, frame_cap = 0, frame_seq = 0;   // frame_seq: frames allocated so far
+    uint64_t frame_bytes = 0, frame_cap = 0;
     uint8_t* frames = nullptr;
     uint64_t rec_act_off = 0, rec_tail_off = 0;               // record layout (offsets of act / tail inside a record)
-    std::vector<uint64_t> first_ref;       // per transition slot: smallest frame sequence number it references
-    std::vector<uint8_t> last_next;        // host copy of the last pushed next_obs (episode continuation test)
-    std::vector<uint64_t> last_next_seq;   // ... and the sequence numbers of its k frames
-    bool have_last = false;
-    uint8_t* fstage = nullptr;             // pinned staging for new frames
+    bdr::FrameShare fs;                    // frames allocated so far, first_ref, the last next_obs' sequence numbers (frame_share.hpp)
+    std::vector<uint8_t> last_next;        // host copy of the last pushed next_obs (episode continuation test of the host push)
+    bool last_next_stale = false;          // a device push came last: `last_next` is fetched from the frame store when a host push needs it
+    uint8_t* fstage = nullptr;             // pinned staging: new frames (host push) / equality flags and scatter jobs (device push)
     uint64_t fstage_frames = 0;
+    uint8_t* d_fshare = nullptr; uint64_t fshare_bytes = 0;   // bdr_replay_push_device_frames: device twin of the flags and jobs of a run
 };
 
 // Observation normaliser (dataset.hip): per-column mean / std of a dataset and the element contract

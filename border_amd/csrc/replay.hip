@@ -362,6 +362,25 @@ static int32_t wait_for_writer(bdr_replay* r, hipStream_t s)
     return BDR_OK;
 }
 
+// the packed record of the transition frame_share_step placed last: [u32 slot x 2k | act | reward | flags], as common.hpp describes it
+static void stage_frame_record(const bdr_replay* r, uint8_t* rec, const uint8_t* act, float reward, int8_t term, int8_t trunc)
+{
+    const int k = r->frame_stack;
+    memset(rec, 0, r->stride);
+    uint32_t* slots = reinterpret_cast<uint32_t*>(rec);
+    for (int j = 0; j < k; ++j) {
+        slots[j] = (uint32_t)(r->fs.oseq[j] % r->frame_cap); slots[k + j] = (uint32_t)(r->fs.nseq[j] % r->frame_cap);
+    }
+    memcpy(rec + r->rec_act_off, act, r->act_bytes);
+    memcpy(rec + r->rec_tail_off, &reward, 4);
+    rec[r->rec_tail_off + 4] = (uint8_t)term; rec[r->rec_tail_off + 5] = (uint8_t)trunc;
+}
+static int32_t fail_store_exhausted(const bdr_replay* r)
+{
+    return fail(BDR_ERR_INVALID, "single-frame store exhausted: %llu frames cannot hold the frames of %llu live transitions "
+                                 "(raise bdr_replay_config::frame_capacity)", (unsigned long long)r->frame_cap, (unsigned long long)r->capacity);
+}
+
 // push() of the single-frame store.  Sharing is FOUND, not assumed: frame j of an incoming stack reuses an already stored frame
 // only when its bytes equal that frame's bytes -
 //   obs_t == the previous push's next_obs (episode continues)      -> obs costs nothing
@@ -374,8 +393,16 @@ static int32_t push_frames(bdr_replay* r, uint64_t n, const uint8_t* o, const ui
 {
     const int k = r->frame_stack;
     const uint64_t fb = r->frame_bytes;
-    std::vector<uint64_t> oseq(k), nseq(k);
-    uint64_t staged = 0, stage_first_seq = r->frame_seq, rec_done = 0;
+    FrameShare& f = r->fs;
+    if (r->last_next_stale) {   // a device push came last: its next_obs is in the frame store, not in the host copy
+        if (f.have_last) {
+            for (int j = 0; j < k; ++j)
+                BDR_HIP(hipMemcpyAsync(r->last_next.data() + (uint64_t)j * fb, r->frames + (f.last_next_seq[j] % r->frame_cap) * fb, fb, hipMemcpyDeviceToHost, r->stream));
+            BDR_HIP(hipStreamSynchronize(r->stream));
+        }
+        r->last_next_stale = false;
+    }
+    uint64_t staged = 0, stage_first_seq = f.frame_seq, rec_done = 0;
     auto flush_frames = [&]() -> int32_t {   // staged frames -> their slots (<= 2 runs: the store is a ring)
         uint64_t off = 0;
         while (off < staged) {
@@ -385,7 +412,7 @@ static int32_t push_frames(bdr_replay* r, uint64_t n, const uint8_t* o, const ui
             off += m;
         }
         if (staged) BDR_HIP(hipStreamSynchronize(r->stream));   // staging reusable
-        stage_first_seq = r->frame_seq; staged = 0;
+        stage_first_seq = f.frame_seq; staged = 0;
         return BDR_OK;
     };
     auto flush_records = [&](uint64_t upto) -> int32_t {       // packed records [rec_done, upto) -> ring (<= 2 runs)
@@ -400,71 +427,36 @@ static int32_t push_frames(bdr_replay* r, uint64_t n, const uint8_t* o, const ui
         rec_done = upto;
         return BDR_OK;
     };
-    auto alloc = [&](const uint8_t* frame, uint64_t oldest_live) -> int64_t {   // -> sequence number, or -1 (store exhausted)
-        if (r->frame_seq >= r->frame_cap && r->frame_seq - r->frame_cap >= oldest_live) return -1;   // would overwrite a live frame
-        memcpy(r->fstage + staged * fb, frame, fb);
-        staged += 1;
-        return (int64_t)r->frame_seq++;
-    };
     for (uint64_t s = 0; s < n; ++s) {
         if (staged + 2 * (uint64_t)k > r->fstage_frames) BDR_TRY(flush_frames());
         if (s - rec_done >= r->stage_records) BDR_TRY(flush_records(s));
         const uint64_t pos = (r->i + s) % r->capacity;
-        // the oldest frame any transition that stays live references: slot `pos` itself is being replaced
-        uint64_t oldest_live = UINT64_MAX;
-        const uint64_t live = std::min(r->size + s, r->capacity);
-        if (live > 0) {
-            const bool replacing = r->size + s >= r->capacity;
-            if (!replacing) oldest_live = r->first_ref[(r->i + s + r->capacity - live) % r->capacity];
-            else if (r->capacity > 1) oldest_live = r->first_ref[(pos + 1) % r->capacity];
-        }
-        if (r->have_last) oldest_live = std::min(oldest_live, *std::min_element(r->last_next_seq.begin(), r->last_next_seq.end()));
         const uint8_t* os = o + s * r->obs_bytes;
         const uint8_t* ns = x + s * r->obs_bytes;
-        bool ok = true;
-        if (r->have_last && memcmp(os, r->last_next.data(), r->obs_bytes) == 0) oseq = r->last_next_seq;
-        else {
-            for (int j = k - 1; j >= 0 && ok; --j) {   // oldest first, so that sequence numbers grow with time
-                if (j < k - 1 && memcmp(os + j * fb, os + (j + 1) * fb, fb) == 0) oseq[j] = oseq[j + 1];
-                else { const int64_t q = alloc(os + j * fb, oldest_live); ok = q >= 0; oseq[j] = (uint64_t)q; }
-            }
-        }
-        if (ok) {
-            if (k > 1 && memcmp(ns + fb, os, (k - 1) * fb) == 0) {
-                for (int j = 1; j < k; ++j) nseq[j] = oseq[j - 1];
-                if (memcmp(ns, ns + fb, fb) == 0) nseq[0] = nseq[1];
-                else { const int64_t q = alloc(ns, std::min(oldest_live, *std::min_element(oseq.begin(), oseq.end()))); ok = q >= 0; nseq[0] = (uint64_t)q; }
-            } else {
-                for (int j = k - 1; j >= 0 && ok; --j) {
-                    if (j < k - 1 && memcmp(ns + j * fb, ns + (j + 1) * fb, fb) == 0) nseq[j] = nseq[j + 1];
-                    else { const int64_t q = alloc(ns + j * fb, std::min(oldest_live, *std::min_element(oseq.begin(), oseq.end()))); ok = q >= 0; nseq[j] = (uint64_t)q; }
-                }
-            }
-        }
-        if (!ok) {
+        auto eq = [&](int q) -> bool {   // the questions of frame_share.hpp, answered on the caller's rows
+            const uint8_t *u, *v;
+            if (q < k) { u = os + (uint64_t)q * fb; v = r->last_next.data() + (uint64_t)q * fb; }
+            else if (q < 2 * k - 1) { const uint64_t j = q - k; u = os + j * fb; v = os + (j + 1) * fb; }
+            else if (q < 3 * k - 2) { const uint64_t j = q - (2 * k - 1); u = ns + (j + 1) * fb; v = os + j * fb; }
+            else { const uint64_t j = q - (3 * k - 2); u = ns + j * fb; v = ns + (j + 1) * fb; }
+            return memcmp(u, v, fb) == 0;
+        };
+        auto on_alloc = [&](int src, int j, uint64_t) {   // (sequence numbers are handed out in staging order)
+            memcpy(r->fstage + staged * fb, (src ? ns : os) + (uint64_t)j * fb, fb);
+            staged += 1;
+        };
+        if (!frame_share_step(f, pos, r->size + s, eq, on_alloc)) {
             // keep the buffer consistent: what was staged for the transitions already accepted is written, the rest is dropped
-            r->frame_seq = stage_first_seq + staged;   // (frames of the failed transition may have been staged: harmless)
+            // (frames of the failed transition may have been staged: harmless)
             BDR_TRY(flush_frames());
             BDR_TRY(flush_records(s));
             BDR_HIP(hipEventRecord(r->written, r->stream)); mark_written(r);
             if (r->per && s) BDR_TRY(per_push(r->per, r->i, s, r->stream));
             r->i = (r->i + s) % r->capacity; r->size = std::min(r->size + s, r->capacity);
-            return fail(BDR_ERR_INVALID, "single-frame store exhausted: %llu frames cannot hold the frames of %llu live transitions "
-                                         "(raise bdr_replay_config::frame_capacity)", (unsigned long long)r->frame_cap, (unsigned long long)r->capacity);
+            return fail_store_exhausted(r);
         }
-        uint8_t* rec = r->stage + (s - rec_done) * r->stride;
-        memset(rec, 0, r->stride);
-        uint32_t* slots = reinterpret_cast<uint32_t*>(rec);
-        uint64_t fr = UINT64_MAX;
-        for (int j = 0; j < k; ++j) {
-            slots[j] = (uint32_t)(oseq[j] % r->frame_cap); slots[k + j] = (uint32_t)(nseq[j] % r->frame_cap);
-            fr = std::min(fr, std::min(oseq[j], nseq[j]));
-        }
-        memcpy(rec + r->rec_act_off, a + s * r->act_bytes, r->act_bytes);
-        memcpy(rec + r->rec_tail_off, &reward[s], 4);
-        rec[r->rec_tail_off + 4] = (uint8_t)term[s]; rec[r->rec_tail_off + 5] = (uint8_t)trunc[s];
-        r->first_ref[pos] = fr;
-        memcpy(r->last_next.data(), ns, r->obs_bytes); r->last_next_seq = nseq; r->have_last = true;
+        stage_frame_record(r, r->stage + (s - rec_done) * r->stride, a + s * r->act_bytes, reward[s], term[s], trunc[s]);
+        memcpy(r->last_next.data(), ns, r->obs_bytes);
     }
     BDR_TRY(flush_frames());
     BDR_TRY(flush_records(n));
@@ -532,8 +524,8 @@ int32_t bdr_replay_create(const bdr_replay_config* cfg, bdr_replay** out)
             delete r;
             return fail(BDR_ERR_HIP, "hipMalloc of the %.2f GB frame store failed: %s", (double)(r->frame_cap * r->frame_bytes) / 1e9, hipGetErrorString(fe));
         }
-        r->first_ref.assign(r->capacity, 0);
-        r->last_next.resize(r->obs_bytes); r->last_next_seq.assign(k, 0);
+        r->fs.init(k, r->capacity, r->frame_cap);
+        r->last_next.resize(r->obs_bytes);
     }
     hipError_t e = hipMalloc((void**)&r->ring, r->capacity * r->stride);
     if (e != hipSuccess) {
@@ -573,6 +565,7 @@ int32_t bdr_replay_destroy(bdr_replay* r)
     (void)hipFree(r->ring);
     (void)hipFree(r->frames);
     if (r->fstage) (void)hipHostFree(r->fstage);
+    (void)hipFree(r->d_fshare);
     (void)hipHostFree(r->stage);
     if (r->done_host) (void)hipHostFree(r->done_host);
     (void)hipFree(r->done_ticket);
@@ -602,7 +595,7 @@ int32_t bdr_replay_frames_used(const bdr_replay* r, uint64_t* allocated, uint64_
 {
     BDR_REQUIRE(r, "null replay handle");
     BDR_REQUIRE(r->frame_stack > 0, "not a single-frame store (bdr_replay_config::frame_stack == 0)");
-    if (allocated) *allocated = r->frame_seq;
+    if (allocated) *allocated = r->fs.frame_seq;
     if (capacity) *capacity = r->frame_cap;
     return BDR_OK;
 }
@@ -658,6 +651,22 @@ int32_t bdr_replay_push(bdr_replay* r, uint64_t n, const void* obs, const void* 
     r->i = (r->i + n) % r->capacity;
     r->size += n;
     if (r->size >= r->capacity) r->size = r->capacity;
+    return BDR_OK;
+}
+
+// the observation rows of a device push must be device memory of the buffer's GPU
+static int32_t require_device_rows(bdr_replay* r, const void* obs_dev, const void* next_obs_dev)
+{
+    for (const void* p : {obs_dev, next_obs_dev}) {
+        // (the check is a driver call of ~2 us: an address that passed it last time - the environment's stacks, push after push - is not asked
+        //  again; every 1024th push asks anyway, so an allocation that was freed and whose address came back as host or another GPU's memory
+        //  is noticed within a bounded number of pushes instead of never)
+        if ((p == r->dev_rows_ok[0] || p == r->dev_rows_ok[1]) && (r->dev_rows_checks++ & 1023u) != 1023u) continue;
+        hipPointerAttribute_t at{};
+        BDR_REQUIRE(hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == r->device,
+                    "observation rows must be device memory of the buffer's GPU (host rows go through bdr_replay_push)");
+        r->dev_rows_ok[p == obs_dev ? 0 : 1] = p;
+    }
     return BDR_OK;
 }
 
@@ -736,16 +745,7 @@ int32_t bdr_replay_push_device(bdr_replay* r, uint64_t n, const void* obs_dev, u
     BDR_REQUIRE(!r->frame_stack, "the single-frame store finds shared frames by comparing host rows: push host rows (bdr_replay_push) into a "
                                  "buffer with frame_stack > 0");
     BDR_HIP(hipSetDevice(r->device));
-    for (const void* p : {obs_dev, next_obs_dev}) {
-        // (the check is a driver call of ~2 us: an address that passed it last time - the environment's stacks, push after push - is not asked
-        //  again; every 1024th push asks anyway, so an allocation that was freed and whose address came back as host or another GPU's memory
-        //  is noticed within a bounded number of pushes instead of never)
-        if ((p == r->dev_rows_ok[0] || p == r->dev_rows_ok[1]) && (r->dev_rows_checks++ & 1023u) != 1023u) continue;
-        hipPointerAttribute_t at{};
-        BDR_REQUIRE(hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == r->device,
-                    "observation rows must be device memory of the buffer's GPU (host rows go through bdr_replay_push)");
-        r->dev_rows_ok[p == obs_dev ? 0 : 1] = p;
-    }
+    BDR_TRY(require_device_rows(r, obs_dev, next_obs_dev));
     BDR_TRY(wait_for_reader(r, r->stream));  // WAR: do not overwrite rows a consumer's gather may still be reading
     if (n <= (uint64_t)PUSH_SMALL_N && r->act_bytes + 8 <= (uint64_t)PUSH_SMALL_TAIL && !r->per) {
         PushDevSmallArgs sa{};
@@ -824,6 +824,157 @@ int32_t bdr_replay_push_device(bdr_replay* r, uint64_t n, const void* obs_dev, u
     r->size += n;
     if (r->size >= r->capacity) r->size = r->capacity;
     return BDR_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// bdr_replay_push_device_frames: the device push of the single-frame store.  The sharing rule (frame_share.hpp) asks whether
+// frames are equal; here both sides of every question are in HBM - the caller's rows, and for the first transition of a call the
+// frames the store holds as the last next_obs - so the comparison runs there and only its answers cross to the host.
+// k_frame_eq: workgroup (transition s, question q) XORs the two frames in 16-byte vectors, ORs the lanes, reduces over the
+// workgroup (ballot per wave, 4 words of LDS) and thread 0 stores flags[s * (4k - 3) + q] = 1 (equal) / 0: one writer per flag.
+// Bounds: reads frame_bytes at rows s, s - 1 < n of the caller's arrays (frame j < k inside a row of >= k * frame_bytes) and at
+// slot last_slot[j] < frame_cap of the store; writes flag s * Q + q < n * Q.
+// ------------------------------------------------------------------------------------------------
+constexpr int FRAME_STACK_MAX = 64;   // bdr_replay_create's limit
+struct FrameEqArgs {
+    const uint8_t* obs; uint64_t obs_stride; const uint8_t* next; uint64_t next_stride;   // the call's rows (transition 0 of the call first)
+    const uint8_t* frames; uint64_t frame_bytes;
+    uint64_t s0;            // first transition of this launch
+    uint8_t* flags;         // [launch's transitions][4k - 3]
+    int k, have_last;       // have_last 0: the P answers of transition 0 are 0
+    uint32_t last_slot[FRAME_STACK_MAX];   // slots of the store's last next_obs (what transition 0 continues, if anything)
+};
+__global__ __launch_bounds__(256) void k_frame_eq(FrameEqArgs a)
+{
+    const int k = a.k, Q = 4 * k - 3;
+    const uint64_t local = blockIdx.x / Q, s = a.s0 + local;
+    const int q = blockIdx.x % Q;
+    const uint64_t fb = a.frame_bytes;
+    const uint8_t* os = a.obs + s * a.obs_stride;
+    const uint8_t* ns = a.next + s * a.next_stride;
+    const uint8_t *x, *y;
+    bool ask = true;
+    if (q < k) {
+        x = os + (uint64_t)q * fb;
+        if (s == 0) { ask = a.have_last != 0; y = a.frames + (uint64_t)a.last_slot[q] * fb; }
+        else y = a.next + (s - 1) * a.next_stride + (uint64_t)q * fb;
+    } else if (q < 2 * k - 1) { const uint64_t j = q - k; x = os + j * fb; y = os + (j + 1) * fb; }
+    else if (q < 3 * k - 2) { const uint64_t j = q - (2 * k - 1); x = ns + (j + 1) * fb; y = os + j * fb; }
+    else { const uint64_t j = q - (3 * k - 2); x = ns + j * fb; y = ns + (j + 1) * fb; }
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    if (ask) {
+        const u32x4* xv = reinterpret_cast<const u32x4*>(x); const u32x4* yv = reinterpret_cast<const u32x4*>(y);
+        for (uint64_t v = threadIdx.x; v < fb / 16; v += 256) acc |= xv[v] ^ yv[v];
+    }
+    __shared__ uint32_t differs[4];
+    const bool wave_differs = __ballot((acc.x | acc.y | acc.z | acc.w) != 0u) != 0ull;
+    if ((threadIdx.x & 63) == 0) differs[threadIdx.x >> 6] = wave_differs ? 1u : 0u;
+    __syncthreads();
+    if (threadIdx.x == 0) a.flags[local * Q + q] = (ask && !(differs[0] | differs[1] | differs[2] | differs[3])) ? 1 : 0;
+}
+
+// k_frame_scatter: workgroup j copies the frame job j names - frame `frame` of row `row` of the caller's obs (src 0) / next_obs
+// (src 1) array - into slot `slot` of the store, 16-byte vectors.  The host builds the jobs from frame_share_step's allocations:
+// slot = sequence number % frame_cap < frame_cap, row < n, frame < k.
+struct FrameJob { uint32_t src, row, frame, slot; };
+struct FrameScatterArgs {
+    const uint8_t* obs; uint64_t obs_stride; const uint8_t* next; uint64_t next_stride;
+    uint8_t* frames; uint64_t frame_bytes; const FrameJob* jobs;
+};
+__global__ __launch_bounds__(256) void k_frame_scatter(FrameScatterArgs a)
+{
+    const FrameJob j = a.jobs[blockIdx.x];
+    const uint8_t* src = (j.src ? a.next + (uint64_t)j.row * a.next_stride : a.obs + (uint64_t)j.row * a.obs_stride) + (uint64_t)j.frame * a.frame_bytes;
+    const u32x4* sv = reinterpret_cast<const u32x4*>(src);
+    u32x4* dv = reinterpret_cast<u32x4*>(a.frames + (uint64_t)j.slot * a.frame_bytes);
+    for (uint64_t v = threadIdx.x; v < a.frame_bytes / 16; v += 256) dv[v] = sv[v];
+}
+
+extern "C" {
+
+int32_t bdr_replay_push_device_frames(bdr_replay* r, uint64_t n, const void* obs_dev, uint64_t obs_stride, const void* act, const void* next_obs_dev,
+                                      uint64_t next_obs_stride, const float* reward, const int8_t* term, const int8_t* trunc)
+{
+    BDR_REQUIRE(r, "null replay handle");
+    if (n == 0) return BDR_OK;
+    BDR_REQUIRE(obs_dev && act && next_obs_dev && reward && term && trunc, "null transition field");
+    BDR_REQUIRE(r->frame_stack > 0, "not a single-frame store (bdr_replay_config::frame_stack == 0): push device rows into a plain ring with bdr_replay_push_device");
+    BDR_REQUIRE(obs_stride >= r->obs_bytes && next_obs_stride >= r->obs_bytes, "row strides must be >= the observation row size");
+    BDR_REQUIRE((((uintptr_t)obs_dev | (uintptr_t)next_obs_dev | obs_stride | next_obs_stride) & 15) == 0,
+                "observation rows and strides must be multiples of 16 bytes (the frames are compared and copied in 16-byte vectors)");
+    BDR_REQUIRE(n <= 0xFFFFFFFFull, "too many transitions in one push");
+    BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(require_device_rows(r, obs_dev, next_obs_dev));
+    BDR_TRY(wait_for_reader(r, r->stream));  // WAR: do not overwrite frames or records a consumer's gather may still be reading
+    const int k = r->frame_stack, Q = frame_q_count(k);
+    FrameShare& f = r->fs;
+    // a run of m transitions stages m * Q flags and <= 2k * m jobs in the pinned frame staging area, and m records in `stage`
+    const uint64_t fstage_bytes = r->fstage_frames * r->frame_bytes;
+    const uint64_t jobs_off_per = round_up((uint64_t)Q, 16);
+    const uint64_t m_max = std::max<uint64_t>(1, std::min(r->stage_records, fstage_bytes / (jobs_off_per + 2 * (uint64_t)k * sizeof(FrameJob))));
+    const uint64_t jobs_off = m_max * jobs_off_per;
+    if (!r->d_fshare) {
+        r->fshare_bytes = jobs_off + m_max * 2 * (uint64_t)k * sizeof(FrameJob);
+        BDR_HIP(hipMalloc((void**)&r->d_fshare, r->fshare_bytes));
+    }
+    const uint8_t* flags = r->fstage;
+    FrameJob* jobs = reinterpret_cast<FrameJob*>(r->fstage + jobs_off);
+    const uint8_t* a = (const uint8_t*)act;
+    // transitions [0, accepted) of the call are in the store: `written`, priorities, cursor and size move by them
+    auto finish = [&](uint64_t accepted) -> int32_t {
+        if (r->per && accepted) {   // base.rs:304-306 set_priority(len), as push_frames
+            BDR_HIP(hipStreamWaitEvent(r->stream, r->written, 0));
+            BDR_TRY(per_push(r->per, r->i, accepted, r->stream));
+        }
+        BDR_HIP(hipEventRecord(r->written, r->stream)); mark_written(r);
+        BDR_HIP(hipStreamSynchronize(r->stream));  // the caller's device rows may be overwritten by its next environment step
+        r->i = (r->i + accepted) % r->capacity;
+        r->size = std::min(r->size + accepted, r->capacity);
+        if (accepted) r->last_next_stale = true;   // the last next_obs is in the frame store alone: a host push fetches it from there
+        return BDR_OK;
+    };
+    uint64_t done = 0;
+    while (done < n) {
+        const uint64_t m = std::min(n - done, m_max);
+        FrameEqArgs ea{};
+        ea.obs = (const uint8_t*)obs_dev; ea.obs_stride = obs_stride; ea.next = (const uint8_t*)next_obs_dev; ea.next_stride = next_obs_stride;
+        ea.frames = r->frames; ea.frame_bytes = r->frame_bytes; ea.s0 = done; ea.flags = r->d_fshare; ea.k = k;
+        ea.have_last = done == 0 && f.have_last ? 1 : 0;
+        if (ea.have_last) for (int j = 0; j < k; ++j) ea.last_slot[j] = (uint32_t)(f.last_next_seq[j] % r->frame_cap);
+        hipLaunchKernelGGL(k_frame_eq, dim3((uint32_t)(m * Q)), dim3(256), 0, r->stream, ea);
+        BDR_HIP(hipGetLastError());
+        BDR_HIP(hipMemcpyAsync(r->fstage, r->d_fshare, m * Q, hipMemcpyDeviceToHost, r->stream));
+        BDR_HIP(hipStreamSynchronize(r->stream));   // the answers are on the host; the staging areas of the last run are free
+        uint64_t n_jobs = 0, ok_upto = m;
+        for (uint64_t t = 0; t < m; ++t) {
+            const uint64_t s = done + t;
+            auto eq = [&](int q) -> bool { return flags[t * Q + q] != 0; };
+            auto on_alloc = [&](int src, int j, uint64_t seq) { jobs[n_jobs++] = FrameJob{(uint32_t)src, (uint32_t)s, (uint32_t)j, (uint32_t)(seq % r->frame_cap)}; };
+            if (!frame_share_step(f, (r->i + s) % r->capacity, r->size + s, eq, on_alloc)) { ok_upto = t; break; }
+            stage_frame_record(r, r->stage + t * r->stride, a + s * r->act_bytes, reward[s], term[s], trunc[s]);
+        }
+        if (n_jobs) {   // (as push_frames: frames a failed transition had been given are written too - their slots hold no live frame)
+            BDR_HIP(hipMemcpyAsync(r->d_fshare + jobs_off, jobs, n_jobs * sizeof(FrameJob), hipMemcpyHostToDevice, r->stream));
+            FrameScatterArgs sa{(const uint8_t*)obs_dev, obs_stride, (const uint8_t*)next_obs_dev, next_obs_stride, r->frames, r->frame_bytes,
+                                reinterpret_cast<const FrameJob*>(r->d_fshare + jobs_off)};
+            hipLaunchKernelGGL(k_frame_scatter, dim3((uint32_t)n_jobs), dim3(256), 0, r->stream, sa);
+            BDR_HIP(hipGetLastError());
+        }
+        for (uint64_t t = 0; t < ok_upto;) {   // packed records -> ring (<= 2 runs)
+            const uint64_t pos = (r->i + done + t) % r->capacity;
+            const uint64_t c = std::min(ok_upto - t, r->capacity - pos);
+            BDR_HIP(hipMemcpyAsync(r->ring + pos * r->stride, r->stage + t * r->stride, c * r->stride, hipMemcpyHostToDevice, r->stream));
+            t += c;
+        }
+        if (ok_upto < m) {
+            BDR_TRY(finish(done + ok_upto));
+            return fail_store_exhausted(r);
+        }
+        done += m;
+    }
+    return finish(n);
 }
 
 }  // extern "C"
@@ -1010,7 +1161,7 @@ int32_t bdr_replay_fill_synthetic(bdr_replay* r, uint64_t n, uint64_t seed, int3
     BDR_TRY(wait_for_reader(r, r->stream));
     if (r->frame_stack) {   // one continuous episode of n transitions over n + k frames (see k_fill_frames)
         BDR_REQUIRE(kind == 0 && n_actions > 0, "the single-frame store is filled with Atari-like rows (kind 0, discrete actions)");
-        BDR_REQUIRE(r->size == 0 && r->frame_seq == 0, "synthetic fill of the single-frame store needs an empty buffer");
+        BDR_REQUIRE(r->size == 0 && r->fs.frame_seq == 0, "synthetic fill of the single-frame store needs an empty buffer");
         BDR_REQUIRE(n + (uint64_t)r->frame_stack <= r->frame_cap, "fill needs n + frame_stack frames");
         const int k = r->frame_stack;
         FillFramesArgs fa{r->ring, r->stride, r->rec_act_off, r->rec_tail_off, r->frames, r->frame_bytes, r->frame_cap, n, seed, r->capacity, k, n_actions};
@@ -1018,15 +1169,15 @@ int32_t bdr_replay_fill_synthetic(bdr_replay* r, uint64_t n, uint64_t seed, int3
         BDR_HIP(hipGetLastError());
         if (r->per) BDR_TRY(per_push(r->per, 0, n, r->stream));
         BDR_HIP(hipEventRecord(r->written, r->stream)); mark_written(r);
-        for (uint64_t t = 0; t < n; ++t) r->first_ref[t % r->capacity] = t;
-        r->frame_seq = n + k;
+        for (uint64_t t = 0; t < n; ++t) r->fs.first_ref[t % r->capacity] = t;
+        r->fs.frame_seq = n + k;
         // the last next_obs (frames n+k-1 .. n, newest first) as push() will compare against it
         for (int j = 0; j < k; ++j) {
-            r->last_next_seq[j] = n + k - 1 - j;
+            r->fs.last_next_seq[j] = n + k - 1 - j;
             uint64_t* dst = reinterpret_cast<uint64_t*>(r->last_next.data() + (uint64_t)j * r->frame_bytes);
             for (uint64_t w = 0; w < r->frame_bytes / 8; ++w) dst[w] = synth_hash(seed, n + k - 1 - j, 7, w);
         }
-        r->have_last = n > 0;
+        r->fs.have_last = n > 0;
         r->i = n % r->capacity; r->size = n;
         return BDR_OK;
     }

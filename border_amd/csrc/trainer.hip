@@ -95,10 +95,11 @@ int32_t d_push(void* b, uint64_t n, const void* obs, const void* act, const void
 {
     return bdr_replay_push((bdr_replay*)b, n, obs, act, next_obs, rew, term, trunc);
 }
-// bdr_replay_push for device-resident observations (bdr_env_vtable::obs_on_device)
+// bdr_replay_push for device-resident observations (bdr_env_vtable::obs_on_device); the single-frame store has its own device push
 int32_t d_push_dev(void* b, uint64_t n, const void* obs_dev, uint64_t os, const void* act, const void* next_dev, uint64_t ns, const float* rew,
                    const int8_t* term, const int8_t* trunc)
 {
+    if (((bdr_replay*)b)->frame_stack) return bdr_replay_push_device_frames((bdr_replay*)b, n, obs_dev, os, act, next_dev, ns, rew, term, trunc);
     return bdr_replay_push_device((bdr_replay*)b, n, obs_dev, os, act, next_dev, ns, rew, term, trunc);
 }
 // defaults of the evaluator and the post-processing

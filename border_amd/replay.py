@@ -145,6 +145,18 @@ class SimpleReplayBuffer:
         _lib.check(_lib.lib().bdr_replay_push_device(self._h, n, C.c_void_p(obs_dev), obs_stride, _p(act), C.c_void_p(next_obs_dev), next_obs_stride,
                                                      _p(reward), _p(term), _p(trunc)))
 
+    def push_device_frames(self, obs_dev: int, obs_stride: int, act, next_obs_dev: int, next_obs_stride: int, reward, is_terminated, is_truncated) -> None:
+        """`push_device` for a buffer with `frame_stack > 0` (`bdr_replay_push_device_frames`): the shared frames are found by comparing
+        the rows in HBM, the result is that of `push` on the same bytes.  Addresses and strides are multiples of 16 bytes."""
+        reward = np.ascontiguousarray(reward, dtype=np.float32).reshape(-1)
+        n = reward.shape[0]
+        act = np.ascontiguousarray(act, dtype=self.act_dtype).reshape(n, -1)
+        term = np.ascontiguousarray(is_terminated, dtype=np.int8).reshape(n)
+        trunc = np.ascontiguousarray(is_truncated, dtype=np.int8).reshape(n)
+        assert act.nbytes == n * self.act_bytes
+        _lib.check(_lib.lib().bdr_replay_push_device_frames(self._h, n, C.c_void_p(obs_dev), obs_stride, _p(act), C.c_void_p(next_obs_dev), next_obs_stride,
+                                                            _p(reward), _p(term), _p(trunc)))
+
     def push_episode(self, observations, act, reward, is_terminated, is_truncated, normalizer=None) -> None:
         """One episode (`bdr_replay_push_episode`; dataset.rs:80-100): `observations` has T + 1 rows (float64 as Minari stores them, or
         float32), the other arrays T.  The result is that of push(N(observations[:-1]), act, N(observations[1:]), ...) with N the

@@ -110,10 +110,23 @@ BDR_API int32_t bdr_replay_push(bdr_replay* r, uint64_t n, const void* obs, cons
  * rows `*_stride` bytes apart: trainer/sampler.rs:99-144 + border-atari-env/src/env.rs:197-209,312-324 without the HBM -> host ->
  * HBM round trip of the stacks.  act / reward / flags are host arrays (they come from the host side: exploration, the emulator).
  * Ring rows, cursor, size and PER priorities are exactly those of bdr_replay_push on the same bytes.  Not for frame_stack > 0
- * buffers (their push compares host rows): BDR_ERR_INVALID.  Returns when the rows have been copied. */
+ * buffers (bdr_replay_push_device_frames is their device push): BDR_ERR_INVALID.  Returns when the rows have been copied. */
 BDR_API int32_t bdr_replay_push_device(bdr_replay* r, uint64_t n, const void* obs_dev, uint64_t obs_stride, const void* act,
                                        const void* next_obs_dev, uint64_t next_obs_stride, const float* reward,
                                        const int8_t* is_terminated, const int8_t* is_truncated);
+
+/* bdr_replay_push_device for a buffer with frame_stack > 0 (same arguments): the frames an incoming stack shares with the previous
+ * next_obs, with its own transition and inside itself are found by comparing the rows in HBM (the previous next_obs is read from the
+ * frame store), only the answers cross to the host, and the frames that are new are copied from the caller's rows into the store.
+ * Ring records, cursor, size, PER priorities, bdr_replay_frames_used, the sharing state and every later batch / read are exactly
+ * what bdr_replay_push leaves after the same bytes as host rows; host and device pushes may alternate on one buffer in any order.
+ * BDR_ERR_INVALID before anything is written: frame_stack == 0; rows that are not device memory of the buffer's GPU; a stride
+ * below the row size; a base address or stride that is not a multiple of 16 bytes.  A store that runs out of frames behaves as in
+ * bdr_replay_push: the accepted prefix stays (cursor, size and priorities advance by it), BDR_ERR_INVALID, the buffer stays usable.
+ * Returns when the caller's device rows may be overwritten. */
+BDR_API int32_t bdr_replay_push_device_frames(bdr_replay* r, uint64_t n, const void* obs_dev, uint64_t obs_stride, const void* act,
+                                              const void* next_obs_dev, uint64_t next_obs_stride, const float* reward,
+                                              const int8_t* is_terminated, const int8_t* is_truncated);
 
 /* ExperienceBufferBase::len (base.rs:318-320) and the write cursor `i`. */
 BDR_API int32_t bdr_replay_len(const bdr_replay* r, uint64_t* len);

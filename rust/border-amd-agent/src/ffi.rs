@@ -760,6 +760,18 @@ extern "C" {
         is_terminated: *const i8,
         is_truncated: *const i8,
     ) -> i32;
+    pub fn bdr_replay_push_device_frames(
+        r: *mut bdr_replay,
+        n: u64,
+        obs_dev: *const c_void,
+        obs_stride: u64,
+        act: *const c_void,
+        next_obs_dev: *const c_void,
+        next_obs_stride: u64,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+    ) -> i32;
     pub fn bdr_replay_len(r: *const bdr_replay, len: *mut u64) -> i32;
     pub fn bdr_replay_head(r: *const bdr_replay, head: *mut u64) -> i32;
     pub fn bdr_replay_frames_used(r: *const bdr_replay, allocated: *mut u64, capacity: *mut u64) -> i32;

@@ -138,6 +138,41 @@ where
         })
     }
 
+    /// `push` for a buffer built with `frame_stack > 0` whose observation rows already live in HBM (the frame stacks of a
+    /// `bdr_atari_prep`): row `s` of `obs` / `next_obs` is at `*_dev + s * *_stride`.  The shared frames are found by comparing
+    /// the rows on the device; records, cursor, priorities and the frames used are exactly those of `push` on the same bytes,
+    /// and the two may alternate.  Returns when the device rows may be overwritten.
+    ///
+    /// # Safety
+    /// `obs_dev` / `next_obs_dev` must address `reward.len()` readable rows of `O::ROW_BYTES` bytes in the memory of the
+    /// buffer's GPU (addresses and strides multiples of 16 bytes); the library checks the memory kind, not the extent.
+    pub unsafe fn push_device_frames(
+        &mut self,
+        obs_dev: *const c_void,
+        obs_stride: u64,
+        act: &A,
+        next_obs_dev: *const c_void,
+        next_obs_stride: u64,
+        reward: &[f32],
+        is_terminated: &[i8],
+        is_truncated: &[i8],
+    ) -> Result<()> {
+        let n = reward.len();
+        anyhow::ensure!(act.n_rows() == n && is_terminated.len() == n && is_truncated.len() == n, "transition fields differ in length");
+        check(ffi::bdr_replay_push_device_frames(
+            self.h,
+            n as u64,
+            obs_dev,
+            obs_stride,
+            act.as_bytes().as_ptr() as *const c_void,
+            next_obs_dev,
+            next_obs_stride,
+            reward.as_ptr(),
+            is_terminated.as_ptr(),
+            is_truncated.as_ptr(),
+        ))
+    }
+
     /// `(num_terminated_flags, num_truncated_flags, sum_rewards)` over rows `[0, len)` (`base.rs:248-267`); `sum_rewards` is the
     /// left-to-right `f32` sum of `Iterator::sum`.
     pub fn summary(&mut self) -> Result<(usize, usize, f32)> {
