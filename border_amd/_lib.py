@@ -288,6 +288,8 @@ ABI_SYMBOLS = [
     "bdr_agent_set_act_path", "bdr_agent_sample_raw",
     "bdr_model_mailbox_create", "bdr_model_mailbox_destroy", "bdr_agent_publish_model", "bdr_agent_sync_model_from",
     "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default", "bdr_async_train",
+    "bdr_agent_group_create", "bdr_agent_group_destroy", "bdr_agent_group_size", "bdr_agent_group_member", "bdr_agent_group_opt",
+    "bdr_agent_group_opt_with_scalars", "bdr_agent_group_qvalues", "bdr_agent_group_sample", "bdr_agent_group_sync",
 ]
 
 _lib = None
@@ -450,6 +452,15 @@ def lib() -> C.CDLL:
     L.bdr_agent_set_grad_comm.argtypes = [vp, vp]
     L.bdr_dqn_grads_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(DqnRecordC)]
     L.bdr_agent_apply_grads.argtypes = [vp]
+    L.bdr_agent_group_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_agent_group_destroy.argtypes = [vp]
+    L.bdr_agent_group_size.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.bdr_agent_group_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_agent_group_opt.argtypes = [vp, vp]
+    L.bdr_agent_group_opt_with_scalars.argtypes = [vp, vp, vp, i32, vp]
+    L.bdr_agent_group_qvalues.argtypes = [vp, vp, vp]
+    L.bdr_agent_group_sample.argtypes = [vp, vp, vp, vp]
+    L.bdr_agent_group_sync.argtypes = [vp]
     _lib = L
     return L
 

@@ -308,6 +308,74 @@ static bool is_dqn(const bdr_agent* a) { return a && (!strcmp(a->kind(), "dqn_cn
 // the agents whose record starts with the five values of bdr_dqn_record: the tch DQN and the candle DQN (candle_dqn.hip)
 static bool has_dqn_record(const bdr_agent* a) { return is_dqn(a) || (a && !strcmp(a->kind(), "candle_dqn")); }
 
+static int argmax_row(const float* q, int A)   // first maximum, like Tensor::argmax
+{
+    int best = 0;
+    for (int k = 1; k < A; ++k) if (q[k] > q[best]) best = k;
+    return best;
+}
+
+// The exploration tail of Policy::sample (dqn/base.rs:215-241, explorer.rs) on the action values q[n][A] of one call: the agent's
+// host-side explorer stream, its counters and bdr_sample_info.  Shared by bdr_agent_sample and bdr_agent_group_sample.
+int32_t bdr::explore_actions(bdr_agent* a, uint64_t n, const float* q, int A, int64_t* act_out, bdr_sample_info* info)
+{
+    Explorer& x = a->explorer;
+    double eps = 0.0;
+    bool is_random = false;
+    if (a->train) {
+        a->n_samples_act += 1;                                            // dqn/base.rs:215
+        if (x.kind == BDR_EXPLORER_SOFTMAX) {                             // explorer.rs:29-31: softmax(-1).multinomial(1)
+            bool all_best = true;
+            for (uint64_t i = 0; i < n; ++i) {
+                const float* qi = &q[i * A];
+                float mx = qi[0];
+                for (int k = 1; k < A; ++k) mx = std::max(mx, qi[k]);
+                double z = 0.0;
+                for (int k = 0; k < A; ++k) z += std::exp((double)(qi[k] - mx));
+                const double u = x.f64() * z;
+                double c = 0.0;
+                int act = A - 1;
+                for (int k = 0; k < A; ++k) {
+                    c += std::exp((double)(qi[k] - mx));
+                    if (c > u) { act = k; break; }
+                }
+                act_out[i] = act;
+                all_best = all_best && act == argmax_row(qi, A);
+            }
+            if (all_best) a->n_samples_best_act += 1;
+        } else {                                                          // explorer.rs:68-90
+            const double d = (x.eps_start - x.eps_final) / (double)x.final_step;
+            eps = std::max(x.eps_start - d * (double)x.n_calls, x.eps_final);
+            is_random = x.f64() < eps;
+            x.n_calls += 1;
+            bool all_best = true;
+            for (uint64_t i = 0; i < n; ++i) {
+                const int best = argmax_row(&q[i * A], A);
+                const int act = is_random ? (int)x.below((uint32_t)A) : best;
+                act_out[i] = act;
+                all_best = all_best && act == best;
+            }
+            if (all_best) a->n_samples_best_act += 1;                     // action_with_best, dqn/base.rs:219-224
+        }
+    } else {
+        // eval: DQN takes a uniformly random action 1 % of the time (dqn/base.rs:231-234; the reference
+        // returns ONE scalar action for the call, applied to every row here); IQN is purely greedy
+        const bool dqn = !strncmp(a->kind(), "dqn", 3);
+        if (dqn && x.f32() < 0.01f) {
+            is_random = true;
+            const int act = (int)x.below((uint32_t)A);
+            for (uint64_t i = 0; i < n; ++i) act_out[i] = act;
+        } else {
+            for (uint64_t i = 0; i < n; ++i) act_out[i] = argmax_row(&q[i * A], A);
+        }
+    }
+    if (info) {
+        info->eps = eps; info->is_random = is_random ? 1 : 0;
+        info->n_samples_act = a->n_samples_act; info->n_samples_best_act = a->n_samples_best_act;
+    }
+    return BDR_OK;
+}
+
 extern "C" {
 
 void bdr_dqn_config_default(bdr_dqn_config* c)
@@ -342,6 +410,7 @@ int32_t bdr_dqn_create(const bdr_dqn_config* cfg, bdr_agent** out)
 int32_t bdr_agent_destroy(bdr_agent* a)
 {
     if (!a) return BDR_OK;
+    BDR_REQUIRE(!a->group, "the agent is a member of a live bdr_agent_group, which owns it: destroy the group");
     (void)hipSetDevice(a->device);
     for (auto& s : a->slots) { (void)hipEventDestroy(s.e0); (void)hipEventDestroy(s.e1); }
     hipStream_t st = a->stream;
@@ -522,12 +591,6 @@ static int32_t action_values(bdr_agent* a, uint64_t n, const void* obs, std::vec
     return BDR_OK;
 }
 
-static int argmax_row(const float* q, int A)   // first maximum, like Tensor::argmax
-{
-    int best = 0;
-    for (int k = 1; k < A; ++k) if (q[k] > q[best]) best = k;
-    return best;
-}
 
 int32_t bdr_agent_qvalues(bdr_agent* a, uint64_t n, const void* obs, float* q_out, int64_t* argmax_out)
 {
@@ -592,61 +655,7 @@ int32_t bdr_agent_sample(bdr_agent* a, uint64_t n, const void* obs, int64_t* act
         if (!alive) a->last_replay_uid = 0;
         BDR_TRY(st);
     } else BDR_TRY(a->err_check());
-    Explorer& x = a->explorer;
-    double eps = 0.0;
-    bool is_random = false;
-    if (a->train) {
-        a->n_samples_act += 1;                                            // dqn/base.rs:215
-        if (x.kind == BDR_EXPLORER_SOFTMAX) {                             // explorer.rs:29-31: softmax(-1).multinomial(1)
-            bool all_best = true;
-            for (uint64_t i = 0; i < n; ++i) {
-                const float* qi = &q[i * A];
-                float mx = qi[0];
-                for (int k = 1; k < A; ++k) mx = std::max(mx, qi[k]);
-                double z = 0.0;
-                for (int k = 0; k < A; ++k) z += std::exp((double)(qi[k] - mx));
-                const double u = x.f64() * z;
-                double c = 0.0;
-                int act = A - 1;
-                for (int k = 0; k < A; ++k) {
-                    c += std::exp((double)(qi[k] - mx));
-                    if (c > u) { act = k; break; }
-                }
-                act_out[i] = act;
-                all_best = all_best && act == argmax_row(qi, A);
-            }
-            if (all_best) a->n_samples_best_act += 1;
-        } else {                                                          // explorer.rs:68-90
-            const double d = (x.eps_start - x.eps_final) / (double)x.final_step;
-            eps = std::max(x.eps_start - d * (double)x.n_calls, x.eps_final);
-            is_random = x.f64() < eps;
-            x.n_calls += 1;
-            bool all_best = true;
-            for (uint64_t i = 0; i < n; ++i) {
-                const int best = argmax_row(&q[i * A], A);
-                const int act = is_random ? (int)x.below((uint32_t)A) : best;
-                act_out[i] = act;
-                all_best = all_best && act == best;
-            }
-            if (all_best) a->n_samples_best_act += 1;                     // action_with_best, dqn/base.rs:219-224
-        }
-    } else {
-        // eval: DQN takes a uniformly random action 1 % of the time (dqn/base.rs:231-234; the reference
-        // returns ONE scalar action for the call, applied to every row here); IQN is purely greedy
-        const bool dqn = !strncmp(a->kind(), "dqn", 3);
-        if (dqn && x.f32() < 0.01f) {
-            is_random = true;
-            const int act = (int)x.below((uint32_t)A);
-            for (uint64_t i = 0; i < n; ++i) act_out[i] = act;
-        } else {
-            for (uint64_t i = 0; i < n; ++i) act_out[i] = argmax_row(&q[i * A], A);
-        }
-    }
-    if (info) {
-        info->eps = eps; info->is_random = is_random ? 1 : 0;
-        info->n_samples_act = a->n_samples_act; info->n_samples_best_act = a->n_samples_best_act;
-    }
-    return BDR_OK;
+    return bdr::explore_actions(a, n, q.data(), A, act_out, info);
 }
 
 // Policy::sample / action values for observation rows that already live in HBM ("batched across many vectorised

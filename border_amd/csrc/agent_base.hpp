@@ -91,6 +91,7 @@ static __global__ __launch_bounds__(256) void k_publish_rows(const float* src, f
 struct bdr_agent {
     int32_t device = 0;
     hipStream_t stream = nullptr;
+    void* group = nullptr;          // the live bdr_agent_group that adopted this agent (`stream` is then the group's; mlp_agents.hip)
     bool train = false;
     uint64_t n_opts = 0;
     int32_t ckpt_format = BDR_CKPT_TCH;
@@ -347,6 +348,9 @@ struct bdr_agent {
 };
 
 namespace bdr {
+
+// exploration tail of Policy::sample on the action values q[n][A] of one call (agent_api.hip)
+int32_t explore_actions(bdr_agent* a, uint64_t n, const float* q, int A, int64_t* act_out, bdr_sample_info* info);
 
 // Policy::sample of the handle's kind for the default function tables of the compiled loops (trainer.hip, async_trainer.hip):
 // discrete agents return i64 actions (dqn/base.rs:211-242, iqn/base.rs:204-228), SAC (sac/base.rs:215-225) and the candle-family

@@ -3,6 +3,8 @@
 // Same FP32-MFMA kernels as the CNN path, driven with runtime (64-padded) dimensions (dense.hpp).
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
+#include <memory>
 
 #include "dense.hpp"
 #include "mlp_fused.hpp"
@@ -296,11 +298,14 @@ struct DqnMlp : bdr_agent {
         for (const auto& l : net.L) if (nz * RB * (l.Np / 32) > 8 || RB * (l.Kp / 32) * (l.Np / 32) > 8) return false;
         return true;
     }
-    // the whole update in one launch (mlp_fused.hpp)
-    int32_t update_critic_fused(int Bn, const uint8_t* obs, const uint8_t* next_obs, const uint8_t* act, int act_bytes,
-                                const float* reward, const int8_t* term, const float* weight, const GatherArgs* gather = nullptr)
+    // ---- the one-launch step (mlp_fused.hpp) in three parts, so that a group (DqnGroup below) can fill every member's arguments and
+    // launch once: fused_static = everything that changes only when buffers are reallocated; fused_step_advance = this step's words,
+    // advancing the host state (adam_step, track_with_next / track_done); the launch.
+    // Returns the LDS bytes of the member's plan (0: none - BDR_NO_MLP_LDS=1 or it does not fit)
+    size_t fused_static(MlpFusedArgs& f, int Bn, const uint8_t* obs, const uint8_t* next_obs, const uint8_t* act, int act_bytes,
+                        const float* reward, const int8_t* term, const float* weight, const GatherArgs* gather)
     {
-        MlpFusedArgs f{};
+        f = MlpFusedArgs{};
         if (gather) { f.do_gather = 1; f.g = *gather; }
         const int L = (int)net.L.size();
         f.L = L; f.nz = cfg.double_dqn ? 3 : 2; f.B = Bn; f.A = net.out_dim; f.in_dim = net.in_dim;
@@ -317,14 +322,31 @@ struct DqnMlp : bdr_agent {
         f.weight = weight; f.td_abs = td_abs; f.has_clip = cfg.has_clip_td_err; f.clip_min = (float)cfg.clip_td_err_min; f.clip_max = (float)cfg.clip_td_err_max;
         f.err = dev_err;
         f.q = q; f.grad = grad; f.m = m; f.v = v; f.q_tgt = q_tgt; f.total = net.total;
-        f.do_adam = defer_adam ? 0 : 1;
-        if (f.do_adam) {
-            adam_step += 1;
-            f.adam = adam_scalars_for(cfg.opt_kind == BDR_OPT_ADAMW, cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay, adam_step);
-        }
-        f.do_track = (track_with_next && f.do_adam) ? 1 : 0;
         f.tau = (float)cfg.tau; f.omt = (float)(1.0 - cfg.tau);
-        const size_t lds_bytes = lds_step ? mf_lds_plan(f) : 0;
+        return lds_step ? mf_lds_plan(f) : 0;
+    }
+    MfStep fused_step_advance(const GatherArgs* gather)
+    {
+        MfStep d{};
+        if (gather) { d.word_pos = gather->word_pos; d.size = gather->size; }
+        d.do_adam = defer_adam ? 0 : 1;
+        if (d.do_adam) {
+            adam_step += 1;
+            d.adam = adam_scalars_for(cfg.opt_kind == BDR_OPT_ADAMW, cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay, adam_step);
+        }
+        d.do_track = (track_with_next && d.do_adam) ? 1 : 0;
+        if (d.do_track) track_done = true;
+        track_with_next = false;
+        return d;
+    }
+    // the whole update in one launch
+    int32_t update_critic_fused(int Bn, const uint8_t* obs, const uint8_t* next_obs, const uint8_t* act, int act_bytes,
+                                const float* reward, const int8_t* term, const float* weight, const GatherArgs* gather = nullptr)
+    {
+        MlpFusedArgs f;
+        const size_t lds_bytes = fused_static(f, Bn, obs, next_obs, act, act_bytes, reward, term, weight, gather);
+        const MfStep d = fused_step_advance(gather);
+        f.g.word_pos = d.word_pos; f.g.size = d.size; f.adam = d.adam; f.do_adam = d.do_adam; f.do_track = d.do_track;
         Bracket br(this, "mlp_step");
         if (lds_bytes) {   // activations and gradients resident in LDS (mlp_fused.hpp)
             if (lds_bytes > lds_attr) {
@@ -336,8 +358,6 @@ struct DqnMlp : bdr_agent {
             hipLaunchKernelGGL(k_dqn_mlp_step, dim3(1), dim3(512), 0, stream, f);
         }
         BDR_HIP(hipGetLastError());
-        if (f.do_track) track_done = true;
-        track_with_next = false;
         return BDR_OK;
     }
 
@@ -735,3 +755,388 @@ int32_t dqn_mlp_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
 }
 
 }  // namespace bdr
+
+// ================================================================================================
+// A group of DqnMlp agents: Agent::opt of every member in ONE launch per update round (k_dqn_mlp_step[_lds]_group, workgroup p =
+// member p) and Policy::sample of every member in one launch (k_dqn_mlp_act_group).  A launch grouping, not an agent kind: the
+// members stay ordinary bdr_agents on the group's stream (DESIGN.md "Agent groups").
+//   static arguments   d_args[P] (MlpFusedArgs without its per-step words), rewritten only when a member's buffers or ring change
+//                      (`key` below) - synchronously, behind a stream synchronise: rare
+//   per-step words     MfStep[P] in slot (launch % STEP_SLOTS) of a pinned ring the kernel reads in place; a slot is rewritten only
+//                      after the launch that read it has published its sequence number (mf_group_done)
+// so one group step is one launch per update round and no copy command, whatever P is.
+struct bdr_agent_group {
+    enum { STEP_SLOTS = 8 };
+    int32_t device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<DqnMlp*> members;
+    uint64_t n_updates = 1;
+    // opt
+    struct StaticKey { bool valid = false; uint64_t batch_gen = 0; const void* td_abs = nullptr; uint64_t r_uid = 0, r_batch_gen = 0; };
+    std::vector<StaticKey> keys;
+    std::vector<MlpFusedArgs> h_args; MlpFusedArgs* d_args = nullptr;
+    std::vector<size_t> lds_bytes; size_t lds_attr = 0;
+    MfStep* steps_host = nullptr; MfStep* steps_dev = nullptr;          // [STEP_SLOTS][P] pinned, mapped
+    unsigned* seq_host = nullptr; unsigned* seq_dev = nullptr;          // pinned word: sequence number of the last finished group launch
+    unsigned* ticket = nullptr;
+    uint64_t launches = 0;                                              // group launches so far; launch k (1-based) reads slot k % STEP_SLOTS and publishes (unsigned)k
+    std::vector<bdr_replay*> last_buffers;                              // the buffers of the last accepted opt (distinctness checked once)
+    uint64_t poll_count = 0; MfErrRef* d_err_refs = nullptr;
+    // acting
+    MfActArgs* d_act = nullptr; std::vector<unsigned> obs_off; unsigned obs_floats = 0;
+    float* obs_pin = nullptr; float* obs_pin_dev = nullptr;
+    float* act_pin = nullptr; float* act_pin_dev = nullptr; unsigned act_seq = 0;
+    std::vector<float> qrow;
+};
+
+namespace {
+
+int32_t group_wait_seq(bdr_agent_group* g, unsigned seq)
+{
+    const volatile unsigned* done = g->seq_host;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0; (int)(*done - seq) < 0; ++spins) {
+        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {   // a lost kernel: let the stream report
+            BDR_HIP(hipStreamSynchronize(g->stream));
+            break;
+        }
+    }
+    return BDR_OK;
+}
+
+// why `a` cannot be a member (nullptr: it can)
+const char* group_ineligible(const bdr_agent* a, const DqnMlp** out)
+{
+    if (strcmp(a->kind(), "dqn_mlp") != 0) return "not an Mlp DQN agent (kind dqn_mlp)";
+    const DqnMlp* m = static_cast<const DqnMlp*>(a);
+    *out = m;
+    if (m->group) return "already a member of a group";
+    if (!m->fused) return "the one-workgroup step is switched off (BDR_NO_MLP_FUSED)";
+    if (!m->gather_in_step) return "the in-step sample is switched off (BDR_NO_STEP_GATHER)";
+    if (!m->fused_ok((int)m->cfg.batch_size)) return "its network / batch size does not take the one-workgroup step (at most 4 layers up to 256 wide, batch <= 128, at most 8 32x32 blocks per phase)";
+    if (m->amsgrad) return "amsgrad";
+    if (m->grad_comm) return "a gradient communicator is installed";
+    if (m->prof) return "profiling is on";
+    return nullptr;
+}
+
+// the in_kernel conditions of DqnMlp::opt_enqueue + the checks of DqnMlp::opt, without touching anything
+int32_t group_check_buffers(bdr_agent_group* g, bdr_replay* const* buffers)
+{
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {
+        const DqnMlp* m = g->members[p];
+        const bdr_replay* r = buffers[p];
+        BDR_REQUIRE(r, "member %u: null buffer", p);
+        BDR_REQUIRE(!m->prof && !m->grad_comm, "member %u: profiling or a gradient communicator was switched on after the group was created", p);
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->net.in_dim * 4, "member %u: replay obs rows (%llu B) do not match the Mlp input (%d f32)", p,
+                    (unsigned long long)r->obs_bytes, m->net.in_dim);
+        BDR_REQUIRE(r->act_bytes >= 8, "member %u: discrete actions are stored as i64", p);
+        BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
+        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot be stepped by a group (the in-step sample covers the uniform ring)", p);
+        BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by a group", p);
+        BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: the in-step sample draws the StdRng index stream only", p);
+        if (r->size == 0) return fail(BDR_ERR_EMPTY, "member %u: batch() on an empty replay buffer", p);
+    }
+    if (g->last_buffers.size() != P || memcmp(g->last_buffers.data(), buffers, P * sizeof(bdr_replay*)) != 0) {
+        std::vector<const bdr_replay*> s(buffers, buffers + P);   // workgroups run side by side: one ring (its batch arrays) per member
+        std::sort(s.begin(), s.end());
+        BDR_REQUIRE(std::adjacent_find(s.begin(), s.end()) == s.end(), "two members share one replay buffer: every member needs its own");
+        g->last_buffers.clear();   // (set again once the step is enqueued)
+    }
+    return BDR_OK;
+}
+
+// one update round of every member: fill, advance the host state, one launch
+int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_round)
+{
+    const uint32_t P = (uint32_t)g->members.size();
+    const uint64_t k = g->launches + 1;
+    const unsigned seq = (unsigned)k;
+    const int slot = (int)(k % bdr_agent_group::STEP_SLOTS);
+    if (k > bdr_agent_group::STEP_SLOTS) BDR_TRY(group_wait_seq(g, (unsigned)(k - bdr_agent_group::STEP_SLOTS)));   // the launch that read this slot last
+    MfStep* steps = g->steps_host + (size_t)slot * P;
+    bool dirty = false;
+    for (uint32_t p = 0; p < P; ++p) {
+        DqnMlp* m = g->members[p];
+        bdr_replay* r = buffers[p];
+        const int bs = (int)m->cfg.batch_size;
+        BDR_TRY(m->ensure_batch(bs));
+        BDR_TRY(m->td_buffer(bs));
+        GatherArgs plan{};
+        BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));
+        m->last_reward = r->b_reward; m->last_B = bs;
+        m->defer_adam = false;
+        m->track_with_next = last_round && m->soft_update_counter + 1 == m->cfg.soft_update_interval;
+        bdr_agent_group::StaticKey& key = g->keys[p];
+        if (!key.valid || key.batch_gen != m->batch_gen || key.td_abs != m->td_abs || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
+            g->lds_bytes[p] = m->fused_static(g->h_args[p], bs, r->b_obs, r->b_next, r->b_act, (int)r->act_bytes, r->b_reward, r->b_term, nullptr, &plan);
+            key.valid = true; key.batch_gen = m->batch_gen; key.td_abs = m->td_abs; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
+            dirty = true;
+        }
+        steps[p] = m->fused_step_advance(&plan);
+    }
+    if (dirty) {   // rare (first step, a reallocation, another ring): behind everything the stream still holds
+        BDR_HIP(hipStreamSynchronize(g->stream));
+        BDR_HIP(hipMemcpy(g->d_args, g->h_args.data(), P * sizeof(MlpFusedArgs), hipMemcpyHostToDevice));
+    }
+    // the LDS form only when every member has a plan: otherwise all take the global-memory form (same bits)
+    size_t lds = 0;
+    bool all_lds = true;
+    for (uint32_t p = 0; p < P; ++p) { all_lds = all_lds && g->lds_bytes[p] != 0; lds = std::max(lds, g->lds_bytes[p]); }
+    const auto* args = (const MF_CONST_AS MlpFusedArgs*)g->d_args;
+    const auto* st = (const MF_CONST_AS MfStep*)(g->steps_dev + (size_t)slot * P);
+    if (all_lds) {
+        if (lds > g->lds_attr) {
+            BDR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dqn_mlp_step_lds_group), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            g->lds_attr = lds;
+        }
+        hipLaunchKernelGGL(k_dqn_mlp_step_lds_group, dim3(P), dim3(512), lds, g->stream, args, st, g->ticket, g->seq_dev, seq);
+    } else {
+        hipLaunchKernelGGL(k_dqn_mlp_step_group, dim3(P), dim3(512), 0, g->stream, args, st, g->ticket, g->seq_dev, seq);
+    }
+    g->launches = k;
+    BDR_HIP(hipGetLastError());
+    return BDR_OK;
+}
+
+// what bdr_agent_opt does around opt(), for every member, then the rounds
+int32_t group_opt(bdr_agent_group* g, bdr_replay* const* buffers)
+{
+    BDR_HIP(hipSetDevice(g->device));
+    BDR_TRY(group_check_buffers(g, buffers));
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {   // asynchronous: a device-side failure of an earlier step surfaces here without a synchronisation
+        DqnMlp* m = g->members[p];
+        unsigned w[bdr_agent::ERR_WORDS];
+        for (int i = 0; i < bdr_agent::ERR_WORDS; ++i) w[i] = reinterpret_cast<volatile unsigned*>(m->host_err)[i];
+        BDR_TRY(m->err_report(w));
+    }
+    if (++g->poll_count % bdr_agent::ERR_POLL_INTERVAL == 0) {   // every member's error words -> its pinned mirror, one launch
+        hipLaunchKernelGGL(k_group_err_mirror, dim3(P), dim3(64), 0, g->stream, (const MfErrRef*)g->d_err_refs, (int)bdr_agent::ERR_WORDS);
+        BDR_HIP(hipGetLastError());
+    }
+    for (uint32_t p = 0; p < P; ++p) g->members[p]->last_replay_uid = buffers[p]->uid;
+    for (uint64_t u = 0; u < g->n_updates; ++u) BDR_TRY(group_round(g, buffers, u + 1 == g->n_updates));
+    for (uint32_t p = 0; p < P; ++p) BDR_TRY(g->members[p]->after_updates());   // (the soft update rode on the last round's launch: nothing is enqueued here)
+    g->last_buffers.assign(buffers, buffers + P);
+    return BDR_OK;
+}
+
+// one observation row per member -> the members' action values in the pinned result area (and each member's view of its error words)
+int32_t group_act(bdr_agent_group* g, const void* const* obs)
+{
+    BDR_HIP(hipSetDevice(g->device));
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {
+        BDR_REQUIRE(obs[p], "member %u: null observation row", p);
+        memcpy(g->obs_pin + g->obs_off[p], obs[p], (size_t)g->members[p]->net.in_dim * 4);
+    }
+    const unsigned seq = ++g->act_seq;
+    hipLaunchKernelGGL(k_dqn_mlp_act_group, dim3(P), dim3(512), 0, g->stream, (const MF_CONST_AS MfActArgs*)g->d_act, (const float*)g->obs_pin_dev, g->act_pin_dev, seq);
+    BDR_HIP(hipGetLastError());
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t p = 0; p < P; ++p) {
+        const volatile unsigned* done = reinterpret_cast<const volatile unsigned*>(g->act_pin + (size_t)p * MF_ACT_SLOT);
+        for (unsigned spins = 0; (int)(*done - seq) < 0; ++spins) {
+            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+                BDR_HIP(hipStreamSynchronize(g->stream));
+                if ((int)(*done - seq) < 0) return fail(BDR_ERR_HIP, "the action values of a group acting call never arrived in host memory");
+                break;
+            }
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (uint32_t p = 0; p < P; ++p) {
+        DqnMlp* m = g->members[p];
+        const unsigned* words = reinterpret_cast<const unsigned*>(g->act_pin + (size_t)p * MF_ACT_SLOT);
+        for (int i = 0; i < bdr_agent::ERR_WORDS; ++i) reinterpret_cast<volatile unsigned*>(m->host_err)[i] = words[4 + i];
+    }
+    return BDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr_agent_group** out)
+{
+    BDR_REQUIRE(agents && out, "null argument");
+    BDR_REQUIRE(n >= 1 && n <= 65535, "a group has 1 .. 65535 members");
+    std::vector<DqnMlp*> ms;
+    for (uint32_t p = 0; p < n; ++p) {
+        BDR_REQUIRE(agents[p], "member %u: null agent", p);
+        const DqnMlp* m = nullptr;
+        const char* why = group_ineligible(agents[p], &m);
+        BDR_REQUIRE(!why, "member %u cannot join a group: %s", p, why);
+        BDR_REQUIRE(m->device == agents[0]->device, "member %u lives on device %d, member 0 on device %d", p, m->device, agents[0]->device);
+        BDR_REQUIRE(m->cfg.n_updates_per_opt == static_cast<const DqnMlp*>(agents[0])->cfg.n_updates_per_opt,
+                    "member %u has n_updates_per_opt %llu, member 0 has %llu: one value per group", p, (unsigned long long)m->cfg.n_updates_per_opt,
+                    (unsigned long long)static_cast<const DqnMlp*>(agents[0])->cfg.n_updates_per_opt);
+        for (uint32_t o = 0; o < p; ++o) BDR_REQUIRE(agents[o] != agents[p], "member %u is member %u once more", p, o);
+        ms.push_back(static_cast<DqnMlp*>(agents[p]));
+    }
+    std::unique_ptr<bdr_agent_group> g(new bdr_agent_group());
+    g->device = ms[0]->device; g->n_updates = ms[0]->cfg.n_updates_per_opt;
+    BDR_HIP(hipSetDevice(g->device));
+    const size_t P = n;
+    // acting arguments: fixed for the members' lifetime (the arenas and the error words are never reallocated)
+    std::vector<MfActArgs> act(P);
+    std::vector<MfErrRef> refs(P);
+    g->obs_off.resize(P);
+    for (size_t p = 0; p < P; ++p) {
+        DqnMlp* m = ms[p];
+        MfActArgs& a = act[p];
+        memset(&a, 0, sizeof a);
+        a.L = (int)m->net.L.size(); a.A = m->net.out_dim; a.in_dim = m->net.in_dim;
+        for (int i = 0; i < a.L; ++i) { a.Kp[i] = m->net.L[i].Kp; a.Np[i] = m->net.L[i].Np; a.relu[i] = m->net.L[i].relu; a.w[i] = m->net.L[i].w; a.b[i] = m->net.L[i].b; }
+        a.params = m->q; a.dev_err = m->dev_err;
+        g->obs_off[p] = g->obs_floats; a.obs_off = g->obs_floats;
+        g->obs_floats += (unsigned)round_up((uint64_t)m->net.in_dim, 4);
+        if (!m->host_err_dev) BDR_HIP(hipHostGetDevicePointer((void**)&m->host_err_dev, m->host_err, 0));
+        refs[p] = MfErrRef{m->dev_err, m->host_err_dev};
+    }
+    // (a failure below leaves nothing adopted: the partially built group frees what it holds)
+    struct Guard { bdr_agent_group* g; bool armed = true; ~Guard() { if (armed) {
+        (void)hipFree(g->d_args); (void)hipFree(g->d_act); (void)hipFree(g->d_err_refs); (void)hipFree(g->ticket);
+        if (g->steps_host) (void)hipHostFree(g->steps_host); if (g->seq_host) (void)hipHostFree(g->seq_host);
+        if (g->obs_pin) (void)hipHostFree(g->obs_pin); if (g->act_pin) (void)hipHostFree(g->act_pin);
+        if (g->stream) (void)hipStreamDestroy(g->stream); } } } guard{g.get()};
+    BDR_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    BDR_HIP(hipMalloc((void**)&g->d_args, P * sizeof(MlpFusedArgs)));
+    BDR_HIP(hipMalloc((void**)&g->d_act, P * sizeof(MfActArgs)));
+    BDR_HIP(hipMalloc((void**)&g->d_err_refs, P * sizeof(MfErrRef)));
+    BDR_HIP(hipMalloc((void**)&g->ticket, sizeof(unsigned)));
+    BDR_HIP(hipMemset(g->ticket, 0, sizeof(unsigned)));
+    BDR_HIP(hipMemcpy(g->d_act, act.data(), P * sizeof(MfActArgs), hipMemcpyHostToDevice));
+    BDR_HIP(hipMemcpy(g->d_err_refs, refs.data(), P * sizeof(MfErrRef), hipMemcpyHostToDevice));
+    BDR_HIP(hipHostMalloc((void**)&g->steps_host, bdr_agent_group::STEP_SLOTS * P * sizeof(MfStep), hipHostMallocMapped));
+    memset(g->steps_host, 0, bdr_agent_group::STEP_SLOTS * P * sizeof(MfStep));
+    BDR_HIP(hipHostGetDevicePointer((void**)&g->steps_dev, g->steps_host, 0));
+    BDR_HIP(hipHostMalloc((void**)&g->seq_host, 64, hipHostMallocMapped));
+    memset(g->seq_host, 0, 64);
+    BDR_HIP(hipHostGetDevicePointer((void**)&g->seq_dev, g->seq_host, 0));
+    BDR_HIP(hipHostMalloc((void**)&g->obs_pin, (size_t)g->obs_floats * 4, hipHostMallocMapped));
+    memset(g->obs_pin, 0, (size_t)g->obs_floats * 4);
+    BDR_HIP(hipHostGetDevicePointer((void**)&g->obs_pin_dev, g->obs_pin, 0));
+    BDR_HIP(hipHostMalloc((void**)&g->act_pin, P * MF_ACT_SLOT * sizeof(float), hipHostMallocMapped));
+    memset(g->act_pin, 0, P * MF_ACT_SLOT * sizeof(float));
+    BDR_HIP(hipHostGetDevicePointer((void**)&g->act_pin_dev, g->act_pin, 0));
+    g->keys.resize(P); g->h_args.resize(P); g->lds_bytes.assign(P, 0);
+    // adopt: the member's own stream is drained, retired and destroyed; the member enqueues on the group's stream from now on
+    for (size_t p = 0; p < P; ++p) BDR_HIP(hipStreamSynchronize(ms[p]->stream));
+    for (size_t p = 0; p < P; ++p) {
+        DqnMlp* m = ms[p];
+        hipStream_t old = m->stream;
+        m->stream = g->stream; m->group = g.get();
+        if (old) { stream_retire(old); (void)hipStreamDestroy(old); }
+    }
+    g->members = std::move(ms);
+    guard.armed = false;
+    *out = g.release();
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_destroy(bdr_agent_group* g)
+{
+    if (!g) return BDR_OK;
+    (void)hipSetDevice(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    for (DqnMlp* m : g->members) {   // the group owns its members; their stream is the group's, destroyed once below
+        m->group = nullptr; m->stream = nullptr;
+        (void)bdr_agent_destroy(m);
+    }
+    stream_retire(g->stream);
+    (void)hipStreamDestroy(g->stream);
+    (void)hipFree(g->d_args); (void)hipFree(g->d_act); (void)hipFree(g->d_err_refs); (void)hipFree(g->ticket);
+    (void)hipHostFree(g->steps_host); (void)hipHostFree(g->seq_host); (void)hipHostFree(g->obs_pin); (void)hipHostFree(g->act_pin);
+    delete g;
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_size(const bdr_agent_group* g, uint32_t* n)
+{
+    BDR_REQUIRE(g && n, "null argument");
+    *n = (uint32_t)g->members.size();
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr_agent** out)
+{
+    BDR_REQUIRE(g && out, "null argument");
+    BDR_REQUIRE(i < g->members.size(), "member %u of a group of %u", i, (unsigned)g->members.size());
+    *out = g->members[i];
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_opt(bdr_agent_group* g, bdr_replay* const* buffers)
+{
+    BDR_REQUIRE(g && buffers, "null argument");
+    return group_opt(g, buffers);
+}
+
+int32_t bdr_agent_group_opt_with_scalars(bdr_agent_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out)
+{
+    BDR_REQUIRE(g && buffers && out && n_out, "null argument");
+    BDR_REQUIRE(cap_per_member >= 1, "cap_per_member must be positive");
+    BDR_TRY(group_opt(g, buffers));
+    BDR_HIP(hipStreamSynchronize(g->stream));   // the one synchronisation: every record() below finds the stream idle
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {
+        DqnMlp* m = g->members[p];
+        int n = 0;
+        m->rec_opt = true;
+        const int32_t st = m->record(out + (size_t)p * cap_per_member, cap_per_member, &n);
+        m->rec_opt = false;
+        BDR_TRY(st);
+        n_out[p] = n;
+    }
+    for (uint32_t p = 0; p < P; ++p) {   // the records are complete whatever the error words say about the step that produced them
+        const int32_t st = g->members[p]->err_check();
+        if (st != BDR_OK) { if (bdr::g_err_deferred) bdr::g_err_deferred = 2; return st; }
+    }
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_qvalues(bdr_agent_group* g, const void* const* obs, float* const* q_out)
+{
+    BDR_REQUIRE(g && obs && q_out, "null argument");
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) BDR_REQUIRE(q_out[p], "member %u: null output row", p);
+    BDR_TRY(group_act(g, obs));
+    for (uint32_t p = 0; p < P; ++p) memcpy(q_out[p], g->act_pin + (size_t)p * MF_ACT_SLOT + 16, (size_t)g->members[p]->net.out_dim * 4);
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_sample(bdr_agent_group* g, const void* const* obs, int64_t* act_out, bdr_sample_info* info)
+{
+    BDR_REQUIRE(g && obs && act_out, "null argument");
+    BDR_TRY(group_act(g, obs));
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {   // the forward brought each member's error words along: report from them, as bdr_agent_sample does
+        DqnMlp* m = g->members[p];
+        unsigned w[bdr_agent::ERR_WORDS];
+        for (int i = 0; i < bdr_agent::ERR_WORDS; ++i) w[i] = reinterpret_cast<volatile unsigned*>(m->host_err)[i];
+        BDR_TRY(m->err_report(w));
+        bool alive = false;
+        const int32_t st = replay_per_check(m->last_replay_uid, &alive);
+        if (!alive) m->last_replay_uid = 0;
+        BDR_TRY(st);
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        DqnMlp* m = g->members[p];
+        BDR_TRY(bdr::explore_actions(m, 1, g->act_pin + (size_t)p * MF_ACT_SLOT + 16, m->net.out_dim, act_out + p, info ? info + p : nullptr));
+    }
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_sync(bdr_agent_group* g)
+{
+    BDR_REQUIRE(g, "null group");
+    BDR_HIP(hipSetDevice(g->device));
+    BDR_HIP(hipStreamSynchronize(g->stream));
+    for (DqnMlp* m : g->members) { BDR_TRY(m->after_sync()); BDR_TRY(m->err_check()); }
+    return BDR_OK;
+}
+
+}  // extern "C"

@@ -148,7 +148,23 @@ __device__ __forceinline__ f32x16 mf_block_pre(int K, int lane, FA&& a4, const f
     return acc;
 }
 
-__global__ __launch_bounds__(512) void k_dqn_mlp_step(MlpFusedArgs a)
+// what changes from one step to the next (the rest of MlpFusedArgs changes only when buffers are reallocated): a group launch
+// (k_dqn_mlp_step_group) reads it per member from a staging slot, the single-agent entries take it from their MlpFusedArgs
+struct MfStep { unsigned long long word_pos, size; AdamScalars adam; int do_adam, do_track; };
+__device__ __forceinline__ MfStep mf_step_of(const MlpFusedArgs& a) { return MfStep{a.g.word_pos, a.g.size, a.adam, a.do_adam, a.do_track}; }
+
+// (Args: MlpFusedArgs in the kernel-argument segment, or the same struct behind a constant-address-space pointer - see the group entries)
+template <class Args>
+__device__ __forceinline__ ChaChaKey mf_key(const Args& a)
+{
+    ChaChaKey k;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k.k[i] = a.g.key.k[i];
+    return k;
+}
+
+template <class Args>
+__device__ __forceinline__ void mf_step_body(const Args& a, const MfStep& d)
 {
     __shared__ float red[512];
     // (wave index as a scalar: block -> (instance, tile) maps and the kernel-argument pointers they select stay in SGPRs; with a
@@ -160,7 +176,7 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step(MlpFusedArgs a)
     if (a.do_gather) {
         __shared__ uint64_t s_row[128];
         if (tid < B) {
-            const uint64_t row = (uint64_t)chacha12_word(a.g.key, a.g.word_pos + tid) % a.g.size;   // (StdRng::next_u32() as usize) % size
+            const uint64_t row = (uint64_t)chacha12_word(mf_key(a), d.word_pos + tid) % d.size;   // (StdRng::next_u32() as usize) % size
             s_row[tid] = row; a.g.ixs[tid] = row;
         }
         __syncthreads();
@@ -347,7 +363,7 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step(MlpFusedArgs a)
         MF_TP(7 + (L - 1 - l));
     }
     // ---- Adam (libtorch Adam::step, adam_element) and the soft update (track) in the same pass over the arena
-    if (a.do_adam || a.do_track) {
+    if (d.do_adam || d.do_track) {
         // 16-byte vectors, two per thread in flight: the arena is ~13 k floats, a scalar loop would be 25 dependent round trips
         const size_t n4 = a.total / 4;   // (arena segments are multiples of 64 floats)
         constexpr int V = 4;             // vectors per thread in flight (x up to 5 arrays)
@@ -360,19 +376,19 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step(MlpFusedArgs a)
                 ok[u] = e < n4;
                 const size_t ec = ok[u] ? e : 0;
                 p[u] = reinterpret_cast<const f32x4*>(a.q)[ec];
-                if (a.do_adam) { g[u] = reinterpret_cast<const f32x4*>(a.grad)[ec]; mm[u] = reinterpret_cast<const f32x4*>(a.m)[ec]; vv[u] = reinterpret_cast<const f32x4*>(a.v)[ec]; }
-                if (a.do_track) t[u] = reinterpret_cast<const f32x4*>(a.q_tgt)[ec];
+                if (d.do_adam) { g[u] = reinterpret_cast<const f32x4*>(a.grad)[ec]; mm[u] = reinterpret_cast<const f32x4*>(a.m)[ec]; vv[u] = reinterpret_cast<const f32x4*>(a.v)[ec]; }
+                if (d.do_track) t[u] = reinterpret_cast<const f32x4*>(a.q_tgt)[ec];
             }
 #pragma unroll
             for (int u = 0; u < V; ++u) {
                 if (!ok[u]) continue;
                 const size_t e = e0 + (size_t)u * 512;
-                if (a.do_adam) {
+                if (d.do_adam) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { float pe = p[u][j], me = mm[u][j], ve = vv[u][j]; adam_element(pe, g[u][j], me, ve, a.adam); p[u][j] = pe; mm[u][j] = me; vv[u][j] = ve; }
+                    for (int j = 0; j < 4; ++j) { float pe = p[u][j], me = mm[u][j], ve = vv[u][j]; adam_element(pe, g[u][j], me, ve, d.adam); p[u][j] = pe; mm[u][j] = me; vv[u][j] = ve; }
                     reinterpret_cast<f32x4*>(a.q)[e] = p[u]; reinterpret_cast<f32x4*>(a.m)[e] = mm[u]; reinterpret_cast<f32x4*>(a.v)[e] = vv[u];
                 }
-                if (a.do_track) {
+                if (d.do_track) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) t[u][j] = track_element(p[u][j], t[u][j], a.tau, a.omt);
                     reinterpret_cast<f32x4*>(a.q_tgt)[e] = t[u];
@@ -394,7 +410,8 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step(MlpFusedArgs a)
 // step).  Same MFMA blocks, same k order, same bits as k_dqn_mlp_step.
 __device__ __forceinline__ void mf_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__global__ __launch_bounds__(512) void k_dqn_mlp_step_lds(MlpFusedArgs a)
+template <class Args>
+__device__ __forceinline__ void mf_step_lds_body(const Args& a, const MfStep& d)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float red[512];
@@ -409,7 +426,7 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step_lds(MlpFusedArgs a)
     // ---- sample (see k_dqn_mlp_step) + the per-row scalars of the TD step
     if (a.do_gather) {
         if (tid < B) {
-            const uint64_t row = (uint64_t)chacha12_word(a.g.key, a.g.word_pos + tid) % a.g.size;
+            const uint64_t row = (uint64_t)chacha12_word(mf_key(a), d.word_pos + tid) % d.size;
             s_row[tid] = row; a.g.ixs[tid] = row;
         }
         mf_lds_sync();
@@ -683,7 +700,7 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step_lds(MlpFusedArgs a)
     // ---- Adam + soft update (see k_dqn_mlp_step).  The gradient arena is exchanged through global memory: one full release /
     // acquire barrier - placed AFTER the loads of the parameters and moments of the first pass are in flight (they do not depend
     // on the gradients), so that round trip overlaps the tail of the backward phases.
-    if (a.do_adam || a.do_track) {
+    if (d.do_adam || d.do_track) {
         // Only the rows of W_l below the layer's logical input width (and the biases) can be non-zero: the zero-padding rows have
         // zero gradients and moments, and Adam / track map (0, 0, 0, 0) to 0 exactly - they are skipped, not recomputed
         // (CartPole: 4 of layer 0's 64 rows are real; 2 160 vectors instead of 3 120, one pass of the loop below).
@@ -716,23 +733,23 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step_lds(MlpFusedArgs a)
                 ok[u] = e < T;
                 at[u] = locate(ok[u] ? e : 0u);
                 p[u] = reinterpret_cast<const f32x4*>(a.q)[at[u]];
-                if (a.do_adam) { mm[u] = reinterpret_cast<const f32x4*>(a.m)[at[u]]; vv[u] = reinterpret_cast<const f32x4*>(a.v)[at[u]]; }
-                if (a.do_track) t[u] = reinterpret_cast<const f32x4*>(a.q_tgt)[at[u]];
+                if (d.do_adam) { mm[u] = reinterpret_cast<const f32x4*>(a.m)[at[u]]; vv[u] = reinterpret_cast<const f32x4*>(a.v)[at[u]]; }
+                if (d.do_track) t[u] = reinterpret_cast<const f32x4*>(a.q_tgt)[at[u]];
             }
             if (base == 0) __syncthreads();
-            if (a.do_adam) {
+            if (d.do_adam) {
 #pragma unroll
                 for (int u = 0; u < V; ++u) g[u] = reinterpret_cast<const f32x4*>(a.grad)[at[u]];
             }
 #pragma unroll
             for (int u = 0; u < V; ++u) {
                 if (!ok[u]) continue;
-                if (a.do_adam) {
+                if (d.do_adam) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { float pe = p[u][j], me = mm[u][j], ve = vv[u][j]; adam_element(pe, g[u][j], me, ve, a.adam); p[u][j] = pe; mm[u][j] = me; vv[u][j] = ve; }
+                    for (int j = 0; j < 4; ++j) { float pe = p[u][j], me = mm[u][j], ve = vv[u][j]; adam_element(pe, g[u][j], me, ve, d.adam); p[u][j] = pe; mm[u][j] = me; vv[u][j] = ve; }
                     reinterpret_cast<f32x4*>(a.q)[at[u]] = p[u]; reinterpret_cast<f32x4*>(a.m)[at[u]] = mm[u]; reinterpret_cast<f32x4*>(a.v)[at[u]] = vv[u];
                 }
-                if (a.do_track) {
+                if (d.do_track) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) t[u][j] = track_element(p[u][j], t[u][j], a.tau, a.omt);
                     reinterpret_cast<f32x4*>(a.q_tgt)[at[u]] = t[u];
@@ -741,6 +758,105 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_step_lds(MlpFusedArgs a)
         }
     }
     MF_TP(11);
+}
+
+__global__ __launch_bounds__(512) void k_dqn_mlp_step(MlpFusedArgs a) { mf_step_body(a, mf_step_of(a)); }
+__global__ __launch_bounds__(512) void k_dqn_mlp_step_lds(MlpFusedArgs a) { mf_step_lds_body(a, mf_step_of(a)); }
+
+// ---- a group of agents in one launch: workgroup p is member p ------------------------------------------
+// The members' arguments live in memory instead of the kernel-argument segment.  The bodies read them IN PLACE through the
+// constant address space: blockIdx.x is uniform, so every field (and every pointer a block -> tile map selects) is a scalar
+// load into SGPRs exactly as in the single-agent entries.  (A private copy of MlpFusedArgs would live in scratch memory: the
+// bodies index its arrays dynamically.)  The few per-step words are copied field by field - static indices, registers.
+#define MF_CONST_AS __attribute__((address_space(4)))
+__device__ __forceinline__ MfStep mf_step_load(const MF_CONST_AS MfStep& s)
+{
+    MfStep d;
+    d.word_pos = s.word_pos; d.size = s.size; d.do_adam = s.do_adam; d.do_track = s.do_track;
+    d.adam.b1 = s.adam.b1; d.adam.omb1 = s.adam.omb1; d.adam.b2 = s.adam.b2; d.adam.omb2 = s.adam.omb2;
+    d.adam.sqrt_bc2 = s.adam.sqrt_bc2; d.adam.eps = s.adam.eps; d.adam.neg_step = s.adam.neg_step; d.adam.wd_mul = s.adam.wd_mul;
+    return d;
+}
+// The per-step words sit in a slot of a pinned staging ring that the host rewrites: once every workgroup has finished (each wave
+// loads its own scalars, hence the barrier) the last one publishes the launch's sequence number to the host, which rewrites a
+// slot only after the launch that read it has said so (k_publish_rows' protocol; no event, no barrier packet in the queue).
+__device__ __forceinline__ void mf_group_done(unsigned* ticket, unsigned* seq_host, unsigned seq)
+{
+    __syncthreads();
+    if (threadIdx.x == 0 && atomicAdd(ticket, 1u) == gridDim.x - 1) {
+        atomicExch(ticket, 0u);   // (the next launch is behind this one in the stream)
+        __hip_atomic_store(seq_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+__global__ __launch_bounds__(512) void k_dqn_mlp_step_group(const MF_CONST_AS MlpFusedArgs* args, const MF_CONST_AS MfStep* steps,
+                                                            unsigned* ticket, unsigned* seq_host, unsigned seq)
+{
+    mf_step_body(args[blockIdx.x], mf_step_load(steps[blockIdx.x]));
+    mf_group_done(ticket, seq_host, seq);
+}
+__global__ __launch_bounds__(512) void k_dqn_mlp_step_lds_group(const MF_CONST_AS MlpFusedArgs* args, const MF_CONST_AS MfStep* steps,
+                                                                unsigned* ticket, unsigned* seq_host, unsigned seq)
+{
+    mf_step_lds_body(args[blockIdx.x], mf_step_load(steps[blockIdx.x]));
+    mf_group_done(ticket, seq_host, seq);
+}
+
+// ---- acting for a group: workgroup p runs member p's online network on ONE observation row --------------
+// Same mf_block phases as the step's forward (so the same k order as the tiled kernels DqnMlp::forward uses: the bits of
+// dqn_mlp_qvalues), activations in LDS, nothing of the member written.  The row is read in place from pinned host memory; the A
+// action values, the member's error words and then a sequence number go to the member's slot of a pinned result area
+// (k_publish_rows' protocol, one slot per member): the host waits on the P sequence words, no copy command, no synchronise.
+struct MfActArgs {
+    int L, A, in_dim;
+    int Kp[MF_MAXL], Np[MF_MAXL], relu[MF_MAXL];
+    size_t w[MF_MAXL], b[MF_MAXL];
+    const float* params;       // the online arena
+    const unsigned* dev_err;   // [ERR_WORDS]
+    unsigned obs_off;          // the member's row in the pinned observation area, in floats
+};
+constexpr int MF_ACT_SLOT = 128;   // floats per member of the result area: [0] sequence word, [4, 8) error words, [16, 16 + A) values
+__global__ __launch_bounds__(512) void k_dqn_mlp_act_group(const MF_CONST_AS MfActArgs* args, const float* obs_host, float* out_host, unsigned seq)
+{
+    __shared__ __attribute__((aligned(16))) float xs[2][256 + 4];   // (fused_ok: no layer wider than 256)
+    const MF_CONST_AS MfActArgs& a = args[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int c = tid; c < a.Kp[0]; c += 512) xs[0][c] = c < a.in_dim ? obs_host[a.obs_off + c] : 0.f;
+    __syncthreads();
+    for (int l = 0; l < a.L; ++l) {
+        const int Kp = a.Kp[l], Np = a.Np[l], NB = Np / 32;
+        const float* x = xs[l & 1];
+        float* o = xs[(l + 1) & 1];
+        const float* w = a.params + a.w[l];
+        const float* bias = a.params + a.b[l];
+        for (int nb = wave; nb < NB; nb += 8) {
+            const f32x16 acc = mf_block<true>(Kp, lane,
+                                        [&](int, int kq) { return *reinterpret_cast<const f32x4*>(x + kq); },   // B = 1: every row of the block aliases row 0
+                                        [&](int kq, int j) {
+                                            const float* p = w + (size_t)kq * Np + nb * 32 + j;
+                                            return f32x4{p[0], p[Np], p[2 * Np], p[3 * Np]};
+                                        });
+            if (lane < 32) {   // row 0 of the block: acc[0] of lanes 0..31 (mf_row)
+                const int col = nb * 32 + lane;
+                float v = acc[0] + bias[col];
+                if (a.relu[l]) v = v > 0.f ? v : 0.f;
+                o[col] = v;
+            }
+        }
+        __syncthreads();
+    }
+    float* slot = out_host + (size_t)blockIdx.x * MF_ACT_SLOT;
+    if (tid < a.A) slot[16 + tid] = xs[a.L & 1][tid];
+    if (tid < (int)bdr_agent::ERR_WORDS) reinterpret_cast<unsigned*>(slot)[4 + tid] = a.dev_err[tid];
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(reinterpret_cast<unsigned*>(slot), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// every member's error words -> its pinned mirror (k_err_mirror for a whole group, one launch)
+struct MfErrRef { const unsigned* dev_err; unsigned* host_err; };
+__global__ __launch_bounds__(64) void k_group_err_mirror(const MfErrRef* refs, int n)
+{
+    const MfErrRef r = refs[blockIdx.x];
+    if ((int)threadIdx.x < n) r.host_err[threadIdx.x] = r.dev_err[threadIdx.x];
 }
 
 }  // namespace

@@ -188,7 +188,7 @@ class Dqn:
 
     def close(self):
         if getattr(self, "_h", None):
-            _lib.lib().bdr_agent_destroy(self._h)
+            _lib.check(_lib.lib().bdr_agent_destroy(self._h))   # (refused for a member of a live DqnGroup: the group owns it)
             self._h = None
 
     def __del__(self):

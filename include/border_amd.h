@@ -456,6 +456,44 @@ BDR_API int32_t bdr_agent_qvalues_device(bdr_agent* a, uint64_t n, const void* o
 BDR_API int32_t bdr_agent_sync(bdr_agent* a);
 BDR_API int32_t bdr_agent_n_opts(const bdr_agent* a, uint64_t* n);
 
+/* ---- A group of small DQN agents stepped in one launch -----------------------------------------------------------------
+ * A launch grouping, not an agent kind: n Mlp DQN agents (bdr_dqn_create with BDR_NET_MLP) whose Agent::opt
+ * (border-core/src/base/agent.rs:62-64 -> dqn/base.rs:301-309) runs as ONE kernel launch per update round, one workgroup per member,
+ * and whose Policy::sample (dqn/base.rs:211-242) runs as one launch for all of them.  Every result - parameters, target
+ * parameters, Adam moments, gradients, the rings' index streams and batch arrays, records, counters, action sequences - is bit for
+ * bit what stepping the same agents one after the other gives.
+ * bdr_agent_group_create ADOPTS the agents: each member's own stream is synchronised and destroyed and the member enqueues on the
+ * group's stream from then on, so every bdr_agent_* call keeps working on a member (bdr_agent_group_member), means what it
+ * meant, and stays ordered with the group's calls.  The group owns its members: bdr_agent_group_destroy destroys them, and
+ * bdr_agent_destroy on a member of a live group is BDR_ERR_INVALID.
+ * Eligible (otherwise BDR_ERR_INVALID naming the member and the reason): every member is an Mlp DQN agent that takes the
+ * one-workgroup step for its batch size (no layer wider than 256, at most 4 layers, batch <= 128, every phase at most 8
+ * 32x32 blocks - Mlp[64, 64] up to batch 64), all on one device, no amsgrad, no gradient communicator, profiling off, and one
+ * n_updates_per_opt for all.  Widths, depth, in_dim, actions, batch size, loss, double DQN, gamma, tau, soft_update_interval,
+ * optimizer and its scalars and the seeds may differ per member. */
+typedef struct bdr_agent_group bdr_agent_group;
+BDR_API int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr_agent_group** out);
+BDR_API int32_t bdr_agent_group_destroy(bdr_agent_group* g);
+BDR_API int32_t bdr_agent_group_size(const bdr_agent_group* g, uint32_t* n);
+BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr_agent** out);
+/* Agent::opt of every member, member i on buffers[i] (n distinct buffers): n_updates_per_opt launches in all, asynchronous.
+ * Every buffer must be what the one-launch step samples itself - a uniform (non-prioritized) ring with the StdRng index stream,
+ * no single-frame store, f32 rows of the member's input width, on the group's device, not empty.  All buffers are checked BEFORE
+ * anything advances or is enqueued: a refused call leaves every member and every ring exactly where it was. */
+BDR_API int32_t bdr_agent_group_opt(bdr_agent_group* g, bdr_replay* const* buffers);
+/* Agent::opt_with_record (dqn/base.rs:311-343) of every member: the same step, ONE synchronisation, then member i's Record scalars
+ * (bdr_agent_opt_with_scalars' order) in out[i * cap_per_member ...] and their count in n_out[i]. */
+BDR_API int32_t bdr_agent_group_opt_with_scalars(bdr_agent_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member,
+                                                 int32_t* n_out);
+/* qnet.forward (dqn/base.rs:213) of ONE host observation row per member, one launch: obs[i] -> q_out[i][A_i], the bits of
+ * bdr_agent_qvalues(member i, 1, obs[i]). */
+BDR_API int32_t bdr_agent_group_qvalues(bdr_agent_group* g, const void* const* obs, float* const* q_out);
+/* Policy::sample (dqn/base.rs:211-242) of every member on one observation row each: one launch, then each member's own
+ * exploration stream and counters exactly as bdr_agent_sample(member i, 1, obs[i]) advances them.  act_out[n]; info[n] or NULL. */
+BDR_API int32_t bdr_agent_group_sample(bdr_agent_group* g, const void* const* obs, int64_t* act_out, bdr_sample_info* info);
+/* bdr_agent_sync for the group's stream; reports every member's device-side error flags. */
+BDR_API int32_t bdr_agent_group_sync(bdr_agent_group* g);
+
 /* SyncModel::model_info / sync_model (border-async-trainer/src/sync_model.rs:2-13,
  * dqn/base.rs:377-402) and checkpoint access.  Parameters cross the boundary in the
  * reference's variable order and layouts (c1.weight OIHW, c1.bias, ... l2.bias / mlp.ln{i}.*).

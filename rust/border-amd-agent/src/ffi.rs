@@ -88,6 +88,8 @@ pub const BDR_ACT_PATH_LAYERS: i32 = 1;
 pub const BDR_ACT_PATH_FUSED: i32 = 2;
 
 // opaque handles
+/// `bdr_agent_group` (a launch grouping of Mlp DQN agents): only ever behind a pointer.
+pub enum bdr_agent_group {}
 #[repr(C)]
 pub struct bdr_replay {
     _private: [u8; 0],
@@ -891,6 +893,17 @@ extern "C" {
     pub fn bdr_agent_qvalues_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, q_out: *mut f32, argmax_out: *mut i64) -> i32;
     pub fn bdr_agent_sync(a: *mut bdr_agent) -> i32;
     pub fn bdr_agent_n_opts(a: *const bdr_agent, n: *mut u64) -> i32;
+    // Agent groups.  The header's array parameters are `T* const*` (an array of handles the callee only reads); they are spelled here
+    // the way tests/test_rust_shim_layout.py canonicalises that declarator - same ABI, one pointer to an array of pointers.
+    pub fn bdr_agent_group_create(agents: *mut *const bdr_agent, n: u32, out: *mut *mut bdr_agent_group) -> i32;
+    pub fn bdr_agent_group_destroy(g: *mut bdr_agent_group) -> i32;
+    pub fn bdr_agent_group_size(g: *const bdr_agent_group, n: *mut u32) -> i32;
+    pub fn bdr_agent_group_member(g: *const bdr_agent_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_agent_group_opt(g: *mut bdr_agent_group, buffers: *mut *const bdr_replay) -> i32;
+    pub fn bdr_agent_group_opt_with_scalars(g: *mut bdr_agent_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
+    pub fn bdr_agent_group_qvalues(g: *mut bdr_agent_group, obs: *mut *const c_void, q_out: *mut *const f32) -> i32;
+    pub fn bdr_agent_group_sample(g: *mut bdr_agent_group, obs: *mut *const c_void, act_out: *mut i64, info: *mut bdr_sample_info) -> i32;
+    pub fn bdr_agent_group_sync(g: *mut bdr_agent_group) -> i32;
     pub fn bdr_agent_param_count(a: *const bdr_agent, n: *mut u64) -> i32;
     pub fn bdr_agent_param_count_of(a: *mut bdr_agent, which: i32, n: *mut u64) -> i32;
     pub fn bdr_agent_get_params(a: *mut bdr_agent, which: i32, out: *mut f32, n: u64) -> i32;

@@ -84,7 +84,7 @@ impl AgentHandle {
     }
 
     /// Names of the scalars `opt_with_record` returns, in order (the keys of the reference's `Record`).
-    fn record_keys(&mut self) -> &[String] {
+    pub(crate) fn record_keys(&mut self) -> &[String] {
         if self.keys.is_empty() {
             let mut buf = vec![0u8; 16384];
             let mut n = 0i32;

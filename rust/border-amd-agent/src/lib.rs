@@ -10,6 +10,8 @@
 //!   `batch()` are those of `StdRng::seed_from_u64(seed)`, bit for bit.
 //! * [`AmdDqn`], [`AmdIqn`], [`AmdSac`] - `border-tch-agent/src/{dqn,iqn,sac}/base.rs`; configs keep the reference's field names
 //!   and serde layout ([`config`]), so the example YAML files load unchanged.
+//! * [`AmdDqnGroup`] - a set of small `Mlp` [`AmdDqn`] agents whose `Agent::opt` runs as one kernel launch, one workgroup per member
+//!   (`bdr_agent_group_*`); the members stay ordinary agents.
 //! * [`AmdIql`] - `border-candle-agent/src/iql/base.rs` (offline RL; [`IqlConfig`] deserialises the candle YAML names).
 //! * [`AmdAwac`] - `border-candle-agent/src/awac/base.rs` (offline and online RL; [`AwacConfig`] likewise).
 //! * [`AmdCandleSac`] - `border-candle-agent/src/sac/base.rs` (the candle SAC with its `Mlp2` Gaussian actor; [`CandleSacConfig`]
@@ -40,6 +42,7 @@ pub mod dqn;
 pub mod error;
 pub mod evaluator;
 pub mod ffi;
+pub mod group;
 mod handle;
 pub mod iql;
 pub mod iqn;
@@ -60,6 +63,7 @@ pub use candle_dqn::AmdCandleDqn;
 pub use candle_sac::AmdCandleSac;
 pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;
+pub use group::AmdDqnGroup;
 pub use evaluator::{ActPath, AmdEvaluator, EvalResult, SampleRaw, TrainerPost};
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;
