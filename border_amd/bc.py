@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib
 from .dqn import OptimizerConfig
+from .handle import DenseHandle
 from .iql import ROLES, AgentHandle, CandleMlpConfig, _p  # noqa: F401  (ROLES: importable from here as before)
 
 
@@ -66,7 +67,7 @@ class BcConfig:
         return c
 
 
-class Bc(AgentHandle):
+class Bc(DenseHandle):
     """bc/base.rs; checkpoint (bc/base.rs:138-153): policy_model.pt, or policy_model.safetensors (set_checkpoint_format).
     train() / eval() switch nothing (bc/base.rs:104-106)."""
     KIND = "bc"
@@ -74,12 +75,6 @@ class Bc(AgentHandle):
     SYNC_MODEL = "policy"
     WHICH = {"policy": 0, "actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the policy == model 0
     PROBES = {"pred": 0, "dz": 1}
-
-    def is_train(self) -> bool:
-        """bc/base.rs:110-112: always False"""
-        out = C.c_int32()
-        _lib.check(_lib.lib().bdr_agent_is_train(self._h, C.byref(out)))
-        return bool(out.value)
 
     def update_on_batch(self, obs, act) -> dict:
         """One Bc::opt_ (bc/base.rs:167-198) on host rows; the record's one key is "loss"."""
@@ -103,7 +98,7 @@ class Bc(AgentHandle):
             return np.empty(n, np.int64), True
         return np.empty((n, self.config.act_dim), np.float32), False
 
-    _raw_out = _out   # AgentHandle.sample_raw / sample_raw_device: Discrete agents return indices
+    _raw_out = _out   # DenseHandle.sample_raw / sample_raw_device: Discrete agents return indices
 
     def sample(self, obs) -> np.ndarray:
         """Policy::sample (bc/base.rs:49-59): [n, act_dim] f32 (Continuous) or [n] i64 argmax indices (Discrete)"""

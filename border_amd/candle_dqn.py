@@ -21,7 +21,8 @@ import numpy as np
 
 from . import _lib
 from .dqn import AtariCnnConfig, EpsilonGreedy, OptimizerConfig, Softmax
-from .iql import AgentHandle, CandleMlpConfig, _p
+from .handle import DenseHandle
+from .iql import AgentHandle, CandleMlpConfig, _p  # noqa: F401  (AgentHandle: importable from here as before)
 
 
 @dataclass
@@ -68,7 +69,7 @@ class CandleDqnConfig:
 
     @property
     def act_dim(self) -> int:
-        """One int64 action index per row (the width AgentHandle's raw-row helpers ask for)."""
+        """One int64 action index per row (the width DenseHandle's raw-row helpers ask for)."""
         return 1
 
     def to_c(self):
@@ -106,7 +107,7 @@ def _info(info) -> dict:
     return {"eps": info.eps, "is_random": bool(info.is_random), "n_samples_act": info.n_samples_act, "n_samples_best_act": info.n_samples_best_act}
 
 
-class CandleDqn(AgentHandle):
+class CandleDqn(DenseHandle):
     """dqn/base.rs; checkpoints (dqn/base.rs:337-351): qnet.pt, qnet_tgt.pt, or *.safetensors (set_checkpoint_format)."""
     KIND = "candle_dqn"
     CKPT_STEMS = ("qnet", "qnet_tgt")
@@ -129,11 +130,6 @@ class CandleDqn(AgentHandle):
         self.n_actions = config.n_actions
         if config.ckpt_format != "tch":
             self._ckpt_ext = ".safetensors"
-
-    def is_train(self) -> bool:
-        out = C.c_int32()
-        _lib.check(_lib.lib().bdr_agent_is_train(self._h, C.byref(out)))
-        return bool(out.value)
 
     def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated=None) -> dict:
         """One Dqn::update_critic (dqn/base.rs:59-170) on host rows and opt_'s bookkeeping; act: int64 [n].  is_truncated is read by
@@ -187,7 +183,7 @@ class CandleDqn(AgentHandle):
         return (a, _info(info)) if return_info else a
 
     def _raw_out(self, n: int):
-        return np.empty(n, np.int64), True   # AgentHandle.sample_raw / sample_raw_device: indices
+        return np.empty(n, np.int64), True   # DenseHandle.sample_raw / sample_raw_device: indices
 
     def qvalues(self, obs) -> np.ndarray:
         obs = np.ascontiguousarray(obs, dtype=self._row_dtype).reshape(-1, self.config.obs_dim)

@@ -579,7 +579,7 @@ static int32_t action_values(bdr_agent* a, uint64_t n, const void* obs, std::vec
 {
     BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
     BDR_HIP(hipSetDevice(a->device));
-    const int A = (int)a->param_count(-1);   // number of actions (every value agent reports it as which = -1)
+    const int A = a->n_actions();
     q.resize(n * A);
     int32_t st = BDR_OK;
     if (a->qvalues_f32(n, obs, q.data(), &st)) BDR_TRY(st);
@@ -691,7 +691,7 @@ int32_t bdr_agent_param_count(const bdr_agent* a, uint64_t* n)
 int32_t bdr_agent_param_count_of(bdr_agent* a, int32_t which, uint64_t* n)
 {
     BDR_REQUIRE(a && n, "null argument");
-    *n = a->param_count(which);
+    *n = which == -1 ? (uint64_t)a->n_actions() : a->param_count(which);   // -1: the action count of a discrete agent
     return BDR_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "chacha.hpp"
 #include "common.hpp"
 #include "igemm.hpp"
+#include "param_table.hpp"
 #include "step_graph.hpp"
 
 // DqnExplorer / IqnExplorer state (dqn/explorer.rs:8-120, iqn/explorer.rs:9-108).  The reference draws from
@@ -88,7 +89,7 @@ static __global__ __launch_bounds__(256) void k_publish_rows(const float* src, f
     if (threadIdx.x == 0) __hip_atomic_store(seq_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-struct bdr_agent {
+struct bdr_agent : bdr::ParamTable {
     int32_t device = 0;
     hipStream_t stream = nullptr;
     void* group = nullptr;          // the live bdr_agent_group that adopted this agent (`stream` is then the group's; mlp_agents.hip)
@@ -337,14 +338,27 @@ struct bdr_agent {
     {
         return ::bdr::fail(BDR_ERR_INVALID, "bdr_agent_sample_raw serves IQL, AWAC and BC agents (the others sample through their own entry points)");
     }
-    virtual uint64_t param_count(int which) = 0;                  // reference-layout element count
-    virtual int32_t get_params(int which, float* out, uint64_t n) = 0;
-    virtual int32_t set_params(int which, const float* in, uint64_t n) = 0;
-    virtual float* arena(int which, size_t* n) = 0;               // flat device arena (kernel layout)
-    virtual void arena_released(int) {}                           // ... and the caller handed it back (bdr_agent_arena_release)
+    // ---- parameter views and checkpoints: param_table.hpp implements param_count / get_params / set_params / arena / save / load over
+    // the agent's param_view, checkpoint_files and hooks; here are the copies, the containers and the error channel it reaches them by
+    virtual bool candle_checkpoints() const { return false; }     // true: safetensors under candle's names (<stem>.pt), false: tch archives
+    virtual int n_actions() const { return 0; }                   // discrete agents: the action count (bdr_agent_param_count_of(a, -1))
+    int32_t arena_to_host(const float* dev, float* host, size_t n) final
+    {
+        BDR_HIP(hipMemcpyAsync(host, dev, n * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        return BDR_OK;
+    }
+    int32_t arena_from_host(float* dev, const float* host, size_t n) final
+    {
+        BDR_HIP(hipMemcpyAsync(dev, host, n * 4, hipMemcpyHostToDevice, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
+        return BDR_OK;
+    }
+    int32_t file_write(const bdr::CheckpointFile& f, const char* dir, const float* data, size_t n) final;
+    int32_t file_read(const bdr::CheckpointFile& f, const char* dir, float* data, size_t n) final;
+    int32_t param_error(const std::string& what) final { return ::bdr::fail(BDR_ERR_INVALID, "%s agent: %s", kind(), what.c_str()); }
+    virtual void arena_released(int) {}                           // the caller handed an arena back (bdr_agent_arena_release)
     virtual void arena_escaped(int) {}                            // the raw pointer of arena `which` left the library (bdr_agent_arena_device_ptr)
-    virtual int32_t save(const char* dir) = 0;
-    virtual int32_t load(const char* dir) = 0;
 };
 
 namespace bdr {
@@ -457,8 +471,6 @@ inline int32_t alloc_f(float** p, size_t n)
     return BDR_OK;
 }
 
-// named f32 tensor container used by every agent's save/load (reference variable names)
-struct NamedTensor { std::string name; std::vector<uint64_t> dims; };
 // util.rs:64-80 param_stats: `<var>_mean` = v.mean(), `<var>_std` = v.std(false) (population) of every variable, appended to
 // `out` in the variables' reference order (data: the reference-layout parameter vector described by meta)
 inline void param_stats(const std::vector<NamedTensor>& meta, const float* data, std::vector<float>& out)
@@ -489,8 +501,37 @@ int32_t load_safetensors_named(const std::string& path, const std::vector<NamedT
 // path falls back to the other container when only that one exists
 std::string ckpt_save_path(const bdr_agent* a, const char* dir, const std::string& stem);
 std::string ckpt_load_path(const bdr_agent* a, const char* dir, const std::string& stem);
+namespace candle {
+// candle's VarMap::save writes safetensors whatever the extension: "<stem>.pt" (default, the reference's files) or "<stem>.safetensors"
+inline std::string ckpt_save_path(int32_t ckpt_format, const char* dir, const char* stem)
+{
+    return std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt");
+}
+// ... and the load path falls back to the other extension when only that file exists
+inline std::string ckpt_load_path(int32_t ckpt_format, const char* dir, const char* stem)
+{
+    const std::string first = ckpt_save_path(ckpt_format, dir, stem);
+    const std::string second = std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".pt" : ".safetensors");
+    FILE* f = fopen(first.c_str(), "rb");
+    if (f) { fclose(f); return first; }
+    f = fopen(second.c_str(), "rb");
+    if (f) { fclose(f); return second; }
+    return first;
+}
+}  // namespace candle
 
 }  // namespace bdr
+
+inline int32_t bdr_agent::file_write(const bdr::CheckpointFile& f, const char* dir, const float* data, size_t n)
+{
+    if (candle_checkpoints()) return bdr::save_safetensors_named(bdr::candle::ckpt_save_path(ckpt_format, dir, f.stem.c_str()), f.tensors, data, n);
+    return bdr::save_named(bdr::ckpt_save_path(this, dir, f.stem), f.tensors, data, n);
+}
+inline int32_t bdr_agent::file_read(const bdr::CheckpointFile& f, const char* dir, float* data, size_t n)
+{
+    if (candle_checkpoints()) return bdr::load_safetensors_named(bdr::candle::ckpt_load_path(ckpt_format, dir, f.stem.c_str()), f.tensors, data, n);
+    return bdr::load_named(bdr::ckpt_load_path(this, dir, f.stem), f.tensors, data, n);
+}
 
 #define LAUNCH_ON(st, kernel, grid, args)                                                           \
     do {                                                                                           \

@@ -463,49 +463,19 @@ struct Bc : DenseAgent {
     }
 
     // ---- parameter views: model 0; +100 grad, +200 exp_avg, +300 exp_avg_sq ----
-    float* slot(int which) const
+    bool param_view(int which, ParamView* pv) override
     {
-        if (which < 0 || which % 100 != 0 || which / 100 > 3) return nullptr;
+        if (which < 0 || which % 100 != 0 || which / 100 > 3) return false;
         float* r[4] = {p, g, m, v};
-        return r[which / 100];
+        *pv = mlp_view(net, r[which / 100]);
+        return true;
     }
-    uint64_t param_count(int which) override { return slot(which) ? net.ref_total : 0; }
-    int32_t get_params(int which, float* out, uint64_t n) override
-    {
-        float* s = slot(which);
-        BDR_REQUIRE(s, "unknown BC model %d", which);
-        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)net.ref_total);
-        std::vector<float> in(net.total);
-        return arena_to_reference(net, s, in, out);
-    }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
-    {
-        float* s = slot(which);
-        BDR_REQUIRE(s, "unknown BC model %d", which);
-        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch");
-        std::vector<float> in(net.total, 0.f);
-        return arena_from_reference(net, inp, in, s);
-    }
-    float* arena(int which, size_t* n) override { float* s = slot(which); if (n) *n = s ? net.total : 0; return s; }
-
     // ---- checkpoint: policy_model.pt (bc/base.rs:138-153), variables mlp.ln{i}.weight / .bias from the VarMap's root (bc/model.rs:130-133)
-    std::vector<NamedTensor> meta() const
+    void checkpoint_files(std::vector<CheckpointFile>& files) override
     {
         std::vector<NamedTensor> mt;
         candle::mlp_meta(net, "", mt);
-        return mt;
-    }
-    int32_t save(const char* dir) override
-    {
-        std::vector<float> w(net.ref_total);
-        BDR_TRY(get_params(0, w.data(), w.size()));
-        return save_safetensors_named(candle::ckpt_save_path(ckpt_format, dir, "policy_model"), meta(), w.data(), w.size());
-    }
-    int32_t load(const char* dir) override
-    {
-        std::vector<float> w(net.ref_total);
-        BDR_TRY(load_safetensors_named(candle::ckpt_load_path(ckpt_format, dir, "policy_model"), meta(), w.data(), w.size()));
-        return set_params(0, w.data(), w.size());
+        files = {{"policy_model", mt, {0}, {0}}};
     }
 };
 

@@ -113,7 +113,7 @@ int32_t check_mlp(const bdr_mlp_config& m, const char* what, bool actor)
 // ================================================================================================
 // The host core.  Self is the agent (CRTP): it supplies NAME (in messages), N_RECORD (its record values), kind(), record(),
 // record_keys(), update(Bn, obs, act, next_obs, reward, term, trunc, first) and alloc_batch(Bn), and may replace the hooks
-// init_own, alloc_staging and own_slot below.  Cfg is its bdr_*_config; the fields named here are common to all of them.
+// init_own, alloc_staging, own_view and own_files below.  Cfg is its bdr_*_config; the fields named here are common to all of them.
 template <class Self, class Cfg>
 struct CandleAgent : DenseAgent {
     Cfg cfg;
@@ -320,23 +320,16 @@ struct CandleAgent : DenseAgent {
     }
 
     // ---- parameter views ----
-    // which: 0 actor, 1+i critic_i, 1+NC+i critic_tgt_i, then the agent's own models from 1+2NC (own_slot);  +100 grad, +200 exp_avg,
+    // which: 0 actor, 1+i critic_i, 1+NC+i critic_tgt_i, then the agent's own models from 1+2NC (own_view);  +100 grad, +200 exp_avg,
     // +300 exp_avg_sq
-    struct Slot { float* p = nullptr; const MlpLayout* net = nullptr; size_t n = 0; };   // net == &pn: the actor, head2 included
-    Slot slot(int which)
+    bool param_view(int which, ParamView* pv) override
     {
         const int role = which / 100, id = which % 100;
-        if (role > 3 || which < 0) return Slot{};
-        if (id == 0) { float* r[4] = {pi_p, pi_g, pi_m, pi_v}; return Slot{r[role], &pn, pi_total}; }
-        if (id >= 1 && id <= NC) { const int i = id - 1; float* r[4] = {q_p[i], q_g[i], q_m[i], q_v[i]}; return Slot{r[role], &qn, qn.total}; }
-        if (id >= 1 + NC && id <= 2 * NC) return role == 0 ? Slot{q_t[id - 1 - NC], &qn, qn.total} : Slot{};
-        return self().own_slot(id - 1 - 2 * NC, role);
-    }
-    uint64_t param_count(int which) override
-    {
-        Slot s = slot(which);
-        if (!s.p) return 0;
-        return s.net == &pn && !mlp2() ? pn.ref_total + (uint64_t)A : s.net->ref_total;
+        if (role > 3 || which < 0) return false;
+        if (id == 0) { float* r[4] = {pi_p, pi_g, pi_m, pi_v}; *pv = actor_view(r[role]); return true; }
+        if (id >= 1 && id <= NC) { const int i = id - 1; float* r[4] = {q_p[i], q_g[i], q_m[i], q_v[i]}; *pv = mlp_view(qn, r[role]); return true; }
+        if (id >= 1 + NC && id <= 2 * NC) { if (role == 0) *pv = mlp_view(qn, q_t[id - 1 - NC]); return role == 0; }
+        return self().own_view(id - 1 - 2 * NC, role, pv);
     }
     // Mlp2's heads in the actor's reference view: the last layer's [weight [2A][H] | bias [2A]] (mean rows, then std rows) <->
     // mean.weight [A][H], mean.bias [A], std.weight [A][H], std.bias [A] (mlp2.rs:47-52)
@@ -349,33 +342,24 @@ struct CandleAgent : DenseAgent {
         if (to_reference) { std::copy(o.begin() + 2 * nw, o.begin() + 2 * nw + a, t + nw); std::copy(o.begin() + nw, o.begin() + 2 * nw, t + nw + a); }
         else { std::copy(o.begin() + nw + a, o.begin() + 2 * nw + a, t + nw); std::copy(o.begin() + nw, o.begin() + nw + a, t + 2 * nw); }
     }
-    int32_t get_params(int which, float* out, uint64_t n) override
+    // the actor: pn's layers, then Mlp3's head2 [A] behind them (Mlp2: its two heads reordered, no head2)
+    ParamView actor_view(float* arena)
     {
-        Slot s = slot(which);
-        BDR_REQUIRE(s.p, "unknown %s model %d", Self::NAME, which);
-        BDR_REQUIRE(n == param_count(which), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)param_count(which));
-        std::vector<float> in(s.n);
-        BDR_TRY(arena_to_reference(*s.net, s.p, in, out));
-        if (s.net == &pn && mlp2()) mlp2_heads(out, true);
-        else if (s.net == &pn) for (int j = 0; j < A; ++j) out[pn.ref_total + j] = in[h2_off + j];
-        return BDR_OK;
-    }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
-    {
-        Slot s = slot(which);
-        BDR_REQUIRE(s.p, "unknown %s model %d", Self::NAME, which);
-        BDR_REQUIRE(n == param_count(which), "parameter count mismatch");
-        std::vector<float> in(s.n, 0.f);
-        if (s.net == &pn && mlp2()) {
-            std::vector<float> ref(inp, inp + n);
-            mlp2_heads(ref.data(), false);
-            return arena_from_reference(*s.net, ref.data(), in, s.p);
+        ParamView v = mlp_view(pn, arena, pi_total);
+        if (mlp2()) {
+            v.to_reference = [this](const float* in, float* ref) { mlp_to_reference(pn, 0, in, ref); mlp2_heads(ref, true); };
+            v.from_reference = [this](const float* ref, float* in) {
+                std::vector<float> r(ref, ref + pn.ref_total);
+                mlp2_heads(r.data(), false);
+                mlp_to_internal(pn, 0, r.data(), in);
+            };
+            return v;
         }
-        if (s.net == &pn) for (int j = 0; j < A; ++j) in[h2_off + j] = inp[pn.ref_total + j];
-        return arena_from_reference(*s.net, inp, in, s.p);
+        v.count = pn.ref_total + (uint64_t)A;
+        v.to_reference = [this](const float* in, float* ref) { mlp_to_reference(pn, 0, in, ref); std::copy(in + h2_off, in + h2_off + A, ref + pn.ref_total); };
+        v.from_reference = [this](const float* ref, float* in) { mlp_to_internal(pn, 0, ref, in); std::copy(ref + pn.ref_total, ref + pn.ref_total + A, in + h2_off); };
+        return v;
     }
-    // SyncModel ships the actor (model 0)
-    float* arena(int which, size_t* n) override { Slot s = slot(which); if (n) *n = s.n; return s.p; }
 
     // ---- checkpoints: actor.pt, critic.pt, critic.tgt.pt ----
     static void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt) { candle::mlp_meta(net, prefix, mt); }
@@ -399,38 +383,21 @@ struct CandleAgent : DenseAgent {
         for (int i = 0; i < NC; ++i) mlp_meta(qn, "critic" + std::to_string(i) + ".", mt);
         return mt;
     }
-    std::string save_path(const char* dir, const char* stem) const { return candle::ckpt_save_path(ckpt_format, dir, stem); }
-    std::string load_path(const char* dir, const char* stem) const { return candle::ckpt_load_path(ckpt_format, dir, stem); }
-    int32_t save(const char* dir) override
+    // actor, critic, critic.tgt - critic.tgt is saved from, and loaded into, the ONLINE critics: MultiCritic::save / load (util/critic.rs:272-298)
+    // put both files through the online critics' VarMap, the second load wins and the targets stay as they are - then the agent's own files
+    void checkpoint_files(std::vector<CheckpointFile>& files) override
     {
-        std::vector<float> v(param_count(0));
-        BDR_TRY(get_params(0, v.data(), v.size()));
-        BDR_TRY(save_safetensors_named(save_path(dir, "actor"), actor_meta(), v.data(), v.size()));
-        const size_t nq = qn.ref_total;
-        v.assign((size_t)NC * nq, 0.f);
-        for (int i = 0; i < NC; ++i) BDR_TRY(get_params(1 + i, v.data() + (size_t)i * nq, nq));
-        BDR_TRY(save_safetensors_named(save_path(dir, "critic"), critic_meta(), v.data(), v.size()));
-        return save_safetensors_named(save_path(dir, "critic.tgt"), critic_meta(), v.data(), v.size());   // the ONLINE critics (util/critic.rs:272-285)
-    }
-    int32_t load(const char* dir) override
-    {
-        std::vector<float> v(param_count(0));
-        BDR_TRY(load_safetensors_named(load_path(dir, "actor"), actor_meta(), v.data(), v.size()));
-        BDR_TRY(set_params(0, v.data(), v.size()));
-        const size_t nq = qn.ref_total;
-        v.assign((size_t)NC * nq, 0.f);
-        // MultiCritic::load (util/critic.rs:287-298): both files into the ONLINE critics' VarMap - the second load wins - and the
-        // targets stay as they are
-        BDR_TRY(load_safetensors_named(load_path(dir, "critic"), critic_meta(), v.data(), v.size()));
-        BDR_TRY(load_safetensors_named(load_path(dir, "critic.tgt"), critic_meta(), v.data(), v.size()));
-        for (int i = 0; i < NC; ++i) BDR_TRY(set_params(1 + i, v.data() + (size_t)i * nq, nq));
-        return BDR_OK;
+        std::vector<int> critics;
+        for (int i = 0; i < NC; ++i) critics.push_back(1 + i);
+        files = {{"actor", actor_meta(), {0}, {0}}, {"critic", critic_meta(), critics, critics}, {"critic.tgt", critic_meta(), critics, critics}};
+        self().own_files(files);
     }
 
     // ---- hooks an agent may replace ----
     int32_t init_own() { return BDR_OK; }                       // create: the agent's own models, after the actor's and critics'
     int32_t alloc_staging(uint64_t) { return BDR_OK; }          // stage_batch: the agent's own staging rows (alloc(..., STAGING))
-    Slot own_slot(int /*k*/, int /*role*/) { return Slot{}; }   // model 1 + 2NC + k
+    bool own_view(int /*k*/, int /*role*/, ParamView*) { return false; }   // model 1 + 2NC + k
+    void own_files(std::vector<CheckpointFile>&) {}             // checkpoint files behind the core's three
 
     // bdr_*_create after its null check: the checks in their order, the device, then the agent with its initial parameters.
     // value / opt_value: IQL's value model, checked before the actor's; one_row: why a one-row batch is refused (AWAC), null where one

@@ -593,46 +593,16 @@ struct CandleDqn : DenseAgent {
             default: return nullptr;
         }
     }
-    uint64_t param_count(int which) override { return which == -1 ? (uint64_t)A : slot(which) ? ref_count() : 0; }
-    int32_t get_params(int which, float* out, uint64_t n) override
+    bool param_view(int which, ParamView* pv) override
     {
-        float* s = slot(which);
-        BDR_REQUIRE(s, "unknown DQN (candle) model %d", which);
-        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)net.ref_total);
-        std::vector<float> in(net.total);
-        return arena_to_reference(net, s, in, out);
+        if (!slot(which)) return false;
+        *pv = net_view(slot(which));
+        return true;
     }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
-    {
-        float* s = slot(which);
-        BDR_REQUIRE(s, "unknown DQN (candle) model %d", which);
-        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch");
-        std::vector<float> in(net.total, 0.f);
-        return arena_from_reference(net, inp, in, s);
-    }
-    float* arena(int which, size_t* n) override { float* s = slot(which); if (n) *n = s ? arena_floats() : 0; return s; }
-
-    // ---- checkpoints: qnet.pt, qnet_tgt.pt (dqn/base.rs:337-351), VarMaps with mlp.ln{i}.weight / .bias at their root ----
-    int32_t save(const char* dir) override
-    {
-        std::vector<float> w(ref_count());
-        const char* stems[2] = {"qnet", "qnet_tgt"};
-        for (int i = 0; i < 2; ++i) {
-            BDR_TRY(get_params(i, w.data(), w.size()));
-            BDR_TRY(save_safetensors_named(candle::ckpt_save_path(ckpt_format, dir, stems[i]), meta(), w.data(), w.size()));
-        }
-        return BDR_OK;
-    }
-    int32_t load(const char* dir) override
-    {
-        std::vector<float> w(ref_count());
-        const char* stems[2] = {"qnet", "qnet_tgt"};
-        for (int i = 0; i < 2; ++i) {
-            BDR_TRY(load_safetensors_named(candle::ckpt_load_path(ckpt_format, dir, stems[i]), meta(), w.data(), w.size()));
-            BDR_TRY(set_params(i, w.data(), w.size()));
-        }
-        return BDR_OK;
-    }
+    virtual ParamView net_view(float* arena) { return mlp_view(net, arena); }
+    int n_actions() const override { return A; }
+    // ---- checkpoints: qnet.pt, qnet_tgt.pt (dqn/base.rs:337-351), VarMaps with the variables of meta() at their root ----
+    void checkpoint_files(std::vector<CheckpointFile>& files) override { files = {{"qnet", meta(), {0}, {0}}, {"qnet_tgt", meta(), {1}, {1}}}; }
 };
 
 // ================================================================================================
@@ -807,27 +777,9 @@ struct CandleDqnCnn : CandleDqn {
         for (int o = 0; o < A; ++o) for (int k = 0; k < 512; ++k) q[(size_t)o * 512 + k] = h[l2.w + (size_t)k * l2.Np + o];
         q += (size_t)A * 512; std::copy(h + l2.b, h + l2.b + A, q);
     }
-    int32_t get_params(int which, float* out, uint64_t n) override
+    ParamView net_view(float* arena) override
     {
-        float* s = slot(which);
-        BDR_REQUIRE(s, "unknown DQN (candle) model %d", which);
-        BDR_REQUIRE(n == ref_count(), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)ref_count());
-        std::vector<float> in(arena_floats());
-        BDR_HIP(hipMemcpyAsync(in.data(), s, in.size() * 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        to_reference(in.data(), out);
-        return BDR_OK;
-    }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
-    {
-        float* s = slot(which);
-        BDR_REQUIRE(s, "unknown DQN (candle) model %d", which);
-        BDR_REQUIRE(n == ref_count(), "parameter count mismatch");
-        std::vector<float> in(arena_floats());
-        to_internal(inp, in.data());
-        BDR_HIP(hipMemcpyAsync(s, in.data(), in.size() * 4, hipMemcpyHostToDevice, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
+        return {arena, arena_floats(), ref_count(), [this](const float* in, float* ref) { to_reference(in, ref); }, [this](const float* ref, float* in) { to_internal(ref, in); }};
     }
 };
 

@@ -419,42 +419,23 @@ struct CandleSac : CandleAgent<CandleSac, bdr_candle_sac_config> {
         return BDR_OK;
     }
 
-    // ---- log_alpha: model 1 + 2 NC (value, +100 grad, +200 exp_avg, +300 exp_avg_sq), one float each ----
-    bool is_ent(int which) const { return which >= 0 && which / 100 <= 3 && which % 100 == 1 + 2 * NC; }
-    uint64_t param_count(int which) override { return is_ent(which) ? 1 : CandleAgent::param_count(which); }
-    int32_t get_params(int which, float* out, uint64_t n) override
+    // ---- log_alpha: model 1 + 2 NC (value, +100 grad, +200 exp_avg, +300 exp_avg_sq), one float each of `ent` ----
+    bool own_view(int k, int role, ParamView* pv)
     {
-        if (!is_ent(which)) return CandleAgent::get_params(which, out, n);
-        BDR_REQUIRE(n == 1, "parameter count mismatch (log_alpha holds 1 value)");
-        BDR_HIP(hipMemcpyAsync(out, ent + which / 100, 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
+        if (k == 0) *pv = {ent + role, 1, 1, [](const float* in, float* ref) { ref[0] = in[0]; }, [](const float* ref, float* in) { in[0] = ref[0]; }};
+        return k == 0;
     }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
+    int32_t params_written(int which) override   // a new log_alpha: alpha = exp(log_alpha) is what the loss kernels read
     {
-        if (!is_ent(which)) return CandleAgent::set_params(which, inp, n);
-        BDR_REQUIRE(n == 1, "parameter count mismatch (log_alpha holds 1 value)");
-        BDR_HIP(hipMemcpyAsync(ent + which / 100, inp, 4, hipMemcpyHostToDevice, stream));
-        if (which / 100 == 0) { const float al = expf(inp[0]); BDR_HIP(hipMemcpyAsync(ent + 4, &al, 4, hipMemcpyHostToDevice, stream)); }
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
-    }
-
-    // ---- checkpoints (sac/base.rs:244-270): the core's three files and ent_coef.pt with log_alpha [1] ----
-    static std::vector<NamedTensor> ent_meta() { return {{"log_alpha", {1}}}; }
-    int32_t save(const char* dir) override
-    {
-        BDR_TRY(CandleAgent::save(dir));
+        if (which != 1 + 2 * NC) return BDR_OK;
         float la = 0.f;
-        BDR_TRY(get_params(1 + 2 * NC, &la, 1));
-        return save_safetensors_named(save_path(dir, "ent_coef"), ent_meta(), &la, 1);
+        BDR_TRY(arena_to_host(ent, &la, 1));
+        const float al = expf(la);
+        return arena_from_host(ent + 4, &al, 1);
     }
-    int32_t load(const char* dir) override
+    void own_files(std::vector<CheckpointFile>& files)   // sac/base.rs:244-270: the core's three files and ent_coef.pt with log_alpha [1]
     {
-        BDR_TRY(CandleAgent::load(dir));
-        float la = 0.f;
-        BDR_TRY(load_safetensors_named(load_path(dir, "ent_coef"), ent_meta(), &la, 1));
-        return set_params(1 + 2 * NC, &la, 1);
+        files.push_back({"ent_coef", {{"log_alpha", {1}}}, {1 + 2 * NC}, {1 + 2 * NC}});
     }
 };
 

@@ -76,6 +76,23 @@ inline void mlp_to_reference(const MlpLayout& m, size_t base, const float* in, f
         p += l.out;
     }
 }
+// the parameter view (param_table.hpp) of an arena of `arena_floats` floats with `m` at its start (m.total when 0).  m must outlive the view
+inline ParamView mlp_view(const MlpLayout& m, float* arena, size_t arena_floats = 0)
+{
+    const MlpLayout* net = &m;
+    return {arena, arena_floats ? arena_floats : m.total, m.ref_total,
+            [net](const float* in, float* ref) { mlp_to_reference(*net, 0, in, ref); },
+            [net](const float* ref, float* in) { mlp_to_internal(*net, 0, ref, in); }};
+}
+// the variables of an Mlp: <prefix>{i}.weight [out][in], <prefix>{i}.bias [out] for layers [first, first + count) (count < 0: to the last)
+inline void mlp_tensors(const MlpLayout& m, const std::string& prefix, std::vector<NamedTensor>& mt, size_t first = 0, int count = -1)
+{
+    const size_t end = count < 0 ? m.L.size() : first + (size_t)count;
+    for (size_t i = first; i < end; ++i) {
+        mt.push_back({prefix + std::to_string(i - first) + ".weight", {(uint64_t)m.L[i].out, (uint64_t)m.L[i].in}});
+        mt.push_back({prefix + std::to_string(i - first) + ".bias", {(uint64_t)m.L[i].out}});
+    }
+}
 
 // the library's own initialiser: uniform(+-1/sqrt(fan_in)) (tests inject weights through set_params)
 inline void mlp_init_reference(const MlpLayout& m, uint64_t seed, float* ref)

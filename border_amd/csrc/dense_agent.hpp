@@ -1,7 +1,7 @@
 // DenseAgent: the host core under every agent whose models are Mlps trained on dense.hpp's FP32-MFMA kernels (BC: bc.hip; the candle
 // DQN: candle_dqn.hip; IQL, AWAC and the candle SAC through CandleAgent, candle_actor.hpp).  It knows how such a network is allocated, run forward, stepped (input gradients,
 // the grouped dW, the fused reduce + Adam), fed the observation rows of an acting call, and copied to and from the reference
-// layout - and nothing about which models an agent has: an agent brings its arenas, its batch buffers, its loss kernels and its
+// layout (mlp_view, dense.hpp) - and nothing about which models an agent has: an agent brings its arenas, its batch buffers, its loss kernels and its
 // update schedule.  Host code only; with it the checkpoint helpers of candle VarMaps and the optimizer check the agents share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,30 +20,7 @@ namespace candle {
 
 // ---- checkpoints of candle VarMaps (host) ----
 // the variables of an Mlp under `prefix`: mlp.ln{i}.weight [out][in], mlp.ln{i}.bias [out]
-inline void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt)
-{
-    for (size_t i = 0; i < net.L.size(); ++i) {
-        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)net.L[i].out, (uint64_t)net.L[i].in}});
-        mt.push_back({prefix + "mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)net.L[i].out}});
-    }
-}
-// candle's VarMap::save writes safetensors whatever the extension: "<stem>.pt" (default, the reference's files) or "<stem>.safetensors"
-inline std::string ckpt_save_path(int32_t ckpt_format, const char* dir, const char* stem)
-{
-    return std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".safetensors" : ".pt");
-}
-// ... and the load path falls back to the other extension when only that file exists
-inline std::string ckpt_load_path(int32_t ckpt_format, const char* dir, const char* stem)
-{
-    const std::string first = ckpt_save_path(ckpt_format, dir, stem);
-    const std::string second = std::string(dir) + "/" + stem + (ckpt_format == BDR_CKPT_SAFETENSORS ? ".pt" : ".safetensors");
-    FILE* f = fopen(first.c_str(), "rb");
-    if (f) { fclose(f); return first; }
-    f = fopen(second.c_str(), "rb");
-    if (f) { fclose(f); return second; }
-    return first;
-}
-
+inline void mlp_meta(const MlpLayout& net, const std::string& prefix, std::vector<NamedTensor>& mt) { mlp_tensors(net, prefix + "mlp.ln", mt); }
 }  // namespace candle
 }  // namespace bdr
 
@@ -59,6 +36,7 @@ int32_t check_opt(const bdr_adamw_config& o, const char* what)
 
 struct DenseAgent : bdr_agent {
     int O = 0, A = 0;   // f32 observation and action row widths
+    bool candle_checkpoints() const override { return true; }   // every agent on this core mirrors a candle agent: VarMap files
 
     // Every device buffer is registered by its lifetime when it is allocated and freed here: the agent's (arenas, record values),
     // those of one batch size (the agent's ensure_batch) and the staging rows of update_on_batch
@@ -341,24 +319,6 @@ struct DenseAgent : bdr_agent {
         }
         BDR_HIP(hipGetLastError());
         return act_layers(n, raw_f32, true, (uint64_t)O * 4, act_out, idx_out);
-    }
-
-    // ---- parameter views ----
-    // a device arena of `host.size()` floats with `net` at its start -> the host copy and net's parameters in the reference layout
-    int32_t arena_to_reference(const MlpLayout& net, const float* dev, std::vector<float>& host, float* out)
-    {
-        BDR_HIP(hipMemcpyAsync(host.data(), dev, host.size() * 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        mlp_to_reference(net, 0, host.data(), out);
-        return BDR_OK;
-    }
-    // ... and back: net's parameters from the reference layout into `host` (what follows net in the arena is the caller's), then up
-    int32_t arena_from_reference(const MlpLayout& net, const float* inp, std::vector<float>& host, float* dev)
-    {
-        mlp_to_internal(net, 0, inp, host.data());
-        BDR_HIP(hipMemcpyAsync(dev, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
     }
 };
 

@@ -453,12 +453,12 @@ struct DqnCnn : bdr_agent {
     int32_t join_exchange(bool conv, bool fc);       // make the dX queue wait for pending exchanged segments
     int32_t record(float* out, int cap, int* n) override;
     void record_keys(std::vector<std::string>& keys) override;
-    uint64_t param_count(int which) override;
-    int32_t get_params(int which, float* out, uint64_t n) override;
-    int32_t set_params(int which, const float* in, uint64_t n) override;
-    float* arena(int which, size_t* n) override;
-    int32_t save(const char* dir) override;
-    int32_t load(const char* dir) override;
+    bool param_view(int which, ParamView* pv) override;
+    void checkpoint_files(std::vector<CheckpointFile>& files) override;
+    int n_actions() const override { return ar.A; }
+    int32_t params_quiesce() override;
+    int32_t params_written(int which) override { planes_stale(which); return BDR_OK; }
+    void arena_handed_out(int which) override { planes_stale(which); }   // whoever asks for the arena may be about to write it
 };
 
 namespace {
@@ -1213,15 +1213,6 @@ void to_reference(const Arena& ar, const float* in, float* ref)
     p += (size_t)ar.A * 512; std::copy(in + ar.b5, in + ar.b5 + ar.A, p);
 }
 
-float* arena_ptr(DqnCnn* a, int which)
-{
-    switch (which) {
-        case 0: return a->q; case 1: return a->q_tgt; case 2: return a->m; case 3: return a->v; case 4: return a->grad;
-        case 5: return a->vmax;   // AdamW amsgrad: max_exp_avg_sq (nullptr otherwise)
-        default: return nullptr;
-    }
-}
-
 // the library's own initialiser: uniform(+-1/sqrt(fan_in)) from splitmix64 (init scheme is irrelevant to
 // parity: tests inject weights through bdr_agent_set_params)
 void init_reference_params(int A, int ns, uint64_t seed, std::vector<float>& ref)
@@ -1386,8 +1377,6 @@ int32_t DqnCnn::apply_grads()
     return after_updates(this);
 }
 
-static std::vector<NamedTensor> cnn_meta(int A, int ns);
-
 // Agent::opt_with_record (dqn/base.rs:316-342): "loss"; with record_verbose_level >= 2 also pred_mean, reward_mean, tgt_mean,
 // tgt_minus_pred_mean (update_critic :107-121), then - only from opt_with_record - qnet.param_stats() (`<var>_mean`,
 // `<var>_std` of c1.weight ... l2.bias, util.rs:64-80) and ratio_best_act = n_samples_best_act / n_samples_act with both
@@ -1402,7 +1391,7 @@ int32_t DqnCnn::record(float* out, int cap, int* n)
         if (rec_opt) {
             std::vector<float> ref(ref_param_count(ar.A, ar.ns));
             BDR_TRY(get_params(0, ref.data(), ref.size()));
-            param_stats(cnn_meta(ar.A, ar.ns), ref.data(), v);
+            param_stats(file_tensors(0), ref.data(), v);
             v.push_back(n_samples_act == 0 ? 0.f : (float)n_samples_best_act / (float)n_samples_act);
             n_samples_act = 0; n_samples_best_act = 0;
         }
@@ -1417,76 +1406,36 @@ void DqnCnn::record_keys(std::vector<std::string>& keys)
     keys = {"loss"};
     if (cfg.record_verbose_level >= 2) {
         keys.insert(keys.end(), {"pred_mean", "reward_mean", "tgt_mean", "tgt_minus_pred_mean"});
-        param_stat_keys(cnn_meta(ar.A, ar.ns), keys);
+        param_stat_keys(file_tensors(0), keys);
         keys.push_back("ratio_best_act");
     }
 }
 
-uint64_t DqnCnn::param_count(int which) { return which == -1 ? (uint64_t)ar.A : ref_param_count(ar.A, ar.ns); }
-
-int32_t DqnCnn::get_params(int which, float* out, uint64_t n)
+// whoever reads or writes an arena, or asks for it, is about to enqueue work on it behind this queue
+int32_t DqnCnn::params_quiesce()
 {
     BDR_TRY(join_conv23());
-    BDR_TRY(join_exchange(true, true));
-    float* src = arena_ptr(this, which);
-    BDR_REQUIRE(src, "which must be 0..4");
-    BDR_REQUIRE(n == ref_param_count(ar.A, ar.ns), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n,
-                (unsigned long long)ref_param_count(ar.A, ar.ns));
-    std::vector<float> in(ar.total);
-    BDR_HIP(hipMemcpyAsync(in.data(), src, ar.total * 4, hipMemcpyDeviceToHost, stream));
-    BDR_HIP(hipStreamSynchronize(stream));
-    to_reference(ar, in.data(), out);
-    return BDR_OK;
+    return join_exchange(true, true);
 }
 
-int32_t DqnCnn::set_params(int which, const float* inp, uint64_t n)
+// which: 0 qnet, 1 qnet_tgt, 2 exp_avg, 3 exp_avg_sq, 4 grad, 5 max_exp_avg_sq (AdamW{amsgrad}, absent otherwise)
+bool DqnCnn::param_view(int which, ParamView* pv)
 {
-    BDR_TRY(join_conv23());
-    BDR_TRY(join_exchange(true, true));
-    float* dst = arena_ptr(this, which);
-    BDR_REQUIRE(dst, "which must be 0..4");
-    BDR_REQUIRE(n == ref_param_count(ar.A, ar.ns), "parameter count mismatch");
-    std::vector<float> in(ar.total);
-    to_internal(ar, inp, in.data());
-    BDR_HIP(hipMemcpyAsync(dst, in.data(), ar.total * 4, hipMemcpyHostToDevice, stream));
-    BDR_HIP(hipStreamSynchronize(stream));
-    planes_stale(which);
-    return BDR_OK;
+    float* r[6] = {q, q_tgt, m, v, grad, vmax};
+    if (which < 0 || which > 5 || !r[which]) return false;
+    const Arena* lay = &ar;
+    *pv = {r[which], ar.total, ref_param_count(ar.A, ar.ns), [lay](const float* in, float* ref) { to_reference(*lay, in, ref); },
+           [lay](const float* ref, float* in) { to_internal(*lay, ref, in); }};
+    return true;
 }
 
-float* DqnCnn::arena(int which, size_t* n)
+void DqnCnn::checkpoint_files(std::vector<CheckpointFile>& files)   // dqn/base.rs:348-356: qnet.pt.tch, qnet_tgt.pt.tch
 {
-    (void)join_conv23();
-    (void)join_exchange(true, true);   // whoever asks for the arena is about to enqueue work on it behind this queue
-    planes_stale(which);               // ... possibly a write
-    if (n) *n = ar.total;
-    return arena_ptr(this, which);
-}
-
-static std::vector<NamedTensor> cnn_meta(int A, int ns)
-{
-    return {{"c1.weight", {32, (uint64_t)ns, 8, 8}}, {"c1.bias", {32}}, {"c2.weight", {64, 32, 4, 4}}, {"c2.bias", {64}},
-            {"c3.weight", {64, 64, 3, 3}}, {"c3.bias", {64}}, {"l1.weight", {512, 3136}}, {"l1.bias", {512}},
-            {"l2.weight", {(uint64_t)A, 512}}, {"l2.bias", {(uint64_t)A}}};
-}
-
-int32_t DqnCnn::save(const char* dir)
-{
-    // dqn/base.rs:348-356: qnet.pt.tch, qnet_tgt.pt.tch
-    std::vector<float> ref(ref_param_count(ar.A, ar.ns));
-    BDR_TRY(get_params(0, ref.data(), ref.size()));
-    BDR_TRY(save_named(ckpt_save_path(this, dir, "qnet"), cnn_meta(ar.A, ar.ns), ref.data(), ref.size()));
-    BDR_TRY(get_params(1, ref.data(), ref.size()));
-    return save_named(ckpt_save_path(this, dir, "qnet_tgt"), cnn_meta(ar.A, ar.ns), ref.data(), ref.size());
-}
-
-int32_t DqnCnn::load(const char* dir)
-{
-    std::vector<float> ref(ref_param_count(ar.A, ar.ns));
-    BDR_TRY(load_named(ckpt_load_path(this, dir, "qnet"), cnn_meta(ar.A, ar.ns), ref.data(), ref.size()));
-    BDR_TRY(set_params(0, ref.data(), ref.size()));
-    BDR_TRY(load_named(ckpt_load_path(this, dir, "qnet_tgt"), cnn_meta(ar.A, ar.ns), ref.data(), ref.size()));
-    return set_params(1, ref.data(), ref.size());
+    const uint64_t A = (uint64_t)ar.A;
+    const std::vector<NamedTensor> mt = {{"c1.weight", {32, (uint64_t)ar.ns, 8, 8}}, {"c1.bias", {32}}, {"c2.weight", {64, 32, 4, 4}}, {"c2.bias", {64}},
+                                         {"c3.weight", {64, 64, 3, 3}}, {"c3.bias", {64}}, {"l1.weight", {512, 3136}}, {"l1.bias", {512}},
+                                         {"l2.weight", {A, 512}}, {"l2.bias", {A}}};
+    files = {{"qnet", mt, {0}, {0}}, {"qnet_tgt", mt, {1}, {1}}};
 }
 
 namespace bdr {

@@ -217,10 +217,17 @@ struct Iql : CandleAgent<Iql, bdr_iql_config> {
         mlp_init_reference(vn, cfg.seed * 7 + 6, ref.data());
         return set_params(1 + 2 * NC, ref.data(), ref.size());
     }
-    Slot own_slot(int k, int role)
+    bool own_view(int k, int role, ParamView* pv)
     {
         float* r[4] = {v_p, v_g, v_m, v_v};
-        return k == 0 ? Slot{r[role], &vn, vn.total} : Slot{};
+        if (k == 0) *pv = mlp_view(vn, r[role]);
+        return k == 0;
+    }
+    void own_files(std::vector<CheckpointFile>& files)   // iql/base.rs:292-309: actor, critic, critic.tgt, value
+    {
+        std::vector<NamedTensor> mt;
+        mlp_meta(vn, "value.", mt);
+        files.push_back({"value", mt, {1 + 2 * NC}, {1 + 2 * NC}});
     }
     int32_t alloc_batch(int Bn)
     {
@@ -320,22 +327,6 @@ struct Iql : CandleAgent<Iql, bdr_iql_config> {
         out[0] = h[0] / nu; out[1] = h[1] / nu; out[2] = h[2] / nu;   // loss_value, loss_critic, loss_actor (iql/base.rs:177-185)
         *n = 3;
         return BDR_OK;
-    }
-
-    std::vector<NamedTensor> value_meta() const { std::vector<NamedTensor> mt; mlp_meta(vn, "value.", mt); return mt; }
-    int32_t save(const char* dir) override   // iql/base.rs:292-302: actor, critic, critic.tgt, value
-    {
-        BDR_TRY(CandleAgent::save(dir));
-        std::vector<float> v(vn.ref_total);
-        BDR_TRY(get_params(1 + 2 * NC, v.data(), v.size()));
-        return save_safetensors_named(save_path(dir, "value"), value_meta(), v.data(), v.size());
-    }
-    int32_t load(const char* dir) override   // iql/base.rs:304-309
-    {
-        BDR_TRY(CandleAgent::load(dir));
-        std::vector<float> v(vn.ref_total);
-        BDR_TRY(load_safetensors_named(load_path(dir, "value"), value_meta(), v.data(), v.size()));
-        return set_params(1 + 2 * NC, v.data(), v.size());
     }
 };
 

@@ -553,68 +553,24 @@ struct Iqn : bdr_agent {
             q += l.out;
         }
     }
-    float* arena_ptr(int which)
+    // which: 0 iqn, 1 iqn_tgt, 2 exp_avg, 3 exp_avg_sq, 4 grad, 5 max_exp_avg_sq (AdamW{amsgrad})
+    bool param_view(int which, ParamView* pv) override
     {
-        switch (which) { case 0: return p; case 1: return p_tgt; case 2: return am; case 3: return av; case 4: return grad; case 5: return avmax; default: return nullptr; }
+        float* r[6] = {p, p_tgt, am, av, grad, avmax};
+        if (which < 0 || which > 5 || !r[which]) return false;
+        *pv = {r[which], total, ref_total, [this](const float* in, float* ref) { to_reference(in, ref); }, [this](const float* ref, float* in) { to_internal(ref, in); }};
+        return true;
     }
-    uint64_t param_count(int which) override { return which == -1 ? (uint64_t)A : ref_total; }
-    int32_t get_params(int which, float* out, uint64_t n) override
-    {
-        float* src = arena_ptr(which);
-        BDR_REQUIRE(src, "which must be 0..4 (5: max_exp_avg_sq of AdamW{amsgrad})");
-        BDR_REQUIRE(n == ref_total, "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)ref_total);
-        std::vector<float> in(total);
-        BDR_HIP(hipMemcpyAsync(in.data(), src, total * 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        to_reference(in.data(), out);
-        return BDR_OK;
-    }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
-    {
-        float* dst = arena_ptr(which);
-        BDR_REQUIRE(dst, "which must be 0..4 (5: max_exp_avg_sq of AdamW{amsgrad})");
-        BDR_REQUIRE(n == ref_total, "parameter count mismatch");
-        std::vector<float> in(total);
-        to_internal(inp, in.data());
-        BDR_HIP(hipMemcpyAsync(dst, in.data(), total * 4, hipMemcpyHostToDevice, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
-    }
-    float* arena(int which, size_t* n) override { if (n) *n = total; return arena_ptr(which); }
-    std::vector<NamedTensor> meta() const
+    int n_actions() const override { return A; }
+    void checkpoint_files(std::vector<CheckpointFile>& files) override   // iqn.pt.tch / iqn_tgt.pt.tch stems
     {
         std::vector<NamedTensor> mt;
-        if (cnn) {
-            mt = {{"c1.weight", {32, (uint64_t)conv.ns, 8, 8}}, {"c1.bias", {32}}, {"c2.weight", {64, 32, 4, 4}}, {"c2.bias", {64}}, {"c3.weight", {64, 64, 3, 3}}, {"c3.bias", {64}}};
-        } else {
-            for (size_t i = 0; i < psi_mlp.L.size(); ++i) {
-                mt.push_back({"psi.mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)psi_mlp.L[i].out, (uint64_t)psi_mlp.L[i].in}});
-                mt.push_back({"psi.mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)psi_mlp.L[i].out}});
-            }
-        }
+        if (cnn) mt = {{"c1.weight", {32, (uint64_t)conv.ns, 8, 8}}, {"c1.bias", {32}}, {"c2.weight", {64, 32, 4, 4}}, {"c2.bias", {64}}, {"c3.weight", {64, 64, 3, 3}}, {"c3.bias", {64}}};
+        else mlp_tensors(psi_mlp, "psi.mlp.ln", mt);
         mt.push_back({"iqn_cos_to_feature.weight", {(uint64_t)F, (uint64_t)E}});
         mt.push_back({"iqn_cos_to_feature.bias", {(uint64_t)F}});
-        for (size_t i = 1; i < hd.L.size(); ++i) {
-            mt.push_back({"mlp.ln" + std::to_string(i - 1) + ".weight", {(uint64_t)hd.L[i].out, (uint64_t)hd.L[i].in}});
-            mt.push_back({"mlp.ln" + std::to_string(i - 1) + ".bias", {(uint64_t)hd.L[i].out}});
-        }
-        return mt;
-    }
-    int32_t save(const char* dir) override   // iqn.pt.tch / iqn_tgt.pt.tch stems
-    {
-        std::vector<float> ref(ref_total);
-        BDR_TRY(get_params(0, ref.data(), ref.size()));
-        BDR_TRY(save_named(ckpt_save_path(this, dir, "iqn"), meta(), ref.data(), ref.size()));
-        BDR_TRY(get_params(1, ref.data(), ref.size()));
-        return save_named(ckpt_save_path(this, dir, "iqn_tgt"), meta(), ref.data(), ref.size());
-    }
-    int32_t load(const char* dir) override
-    {
-        std::vector<float> ref(ref_total);
-        BDR_TRY(load_named(ckpt_load_path(this, dir, "iqn"), meta(), ref.data(), ref.size()));
-        BDR_TRY(set_params(0, ref.data(), ref.size()));
-        BDR_TRY(load_named(ckpt_load_path(this, dir, "iqn_tgt"), meta(), ref.data(), ref.size()));
-        return set_params(1, ref.data(), ref.size());
+        mlp_tensors(hd, "mlp.ln", mt, 1);
+        files = {{"iqn", mt, {0}, {0}}, {"iqn_tgt", mt, {1}, {1}}};
     }
     // bdr_iqn_probe: the raw buffer `what` names, with its padded leading dimension, as the last model_forward / update_critic left it.
     // Forward buffers hold fwd_B x fwd_N rows (after an update: the online network's pass on `obs`), gradient buffers upd_B x upd_Np.

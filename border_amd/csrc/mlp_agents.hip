@@ -566,7 +566,7 @@ struct DqnMlp : bdr_agent {
             if (rec_opt) {
                 std::vector<float> ref(net.ref_total);
                 BDR_TRY(get_params(0, ref.data(), ref.size()));
-                param_stats(meta(), ref.data(), v);
+                param_stats(file_tensors(0), ref.data(), v);
                 v.push_back(n_samples_act == 0 ? 0.f : (float)n_samples_best_act / (float)n_samples_act);
                 n_samples_act = 0; n_samples_best_act = 0;
             }
@@ -580,62 +580,24 @@ struct DqnMlp : bdr_agent {
         keys = {"loss"};
         if (cfg.record_verbose_level >= 2) {
             keys.insert(keys.end(), {"pred_mean", "reward_mean", "tgt_mean", "tgt_minus_pred_mean"});
-            param_stat_keys(meta(), keys);
+            param_stat_keys(file_tensors(0), keys);
             keys.push_back("ratio_best_act");
         }
     }
-    float* arena_ptr(int which)
+    // which: 0 qnet, 1 qnet_tgt, 2 exp_avg, 3 exp_avg_sq, 4 grad, 5 max_exp_avg_sq (AdamW{amsgrad})
+    bool param_view(int which, ParamView* pv) override
     {
-        switch (which) { case 0: return q; case 1: return q_tgt; case 2: return m; case 3: return v; case 4: return grad; case 5: return vmax; default: return nullptr; }
+        float* r[6] = {q, q_tgt, m, v, grad, vmax};
+        if (which < 0 || which > 5 || !r[which]) return false;
+        *pv = mlp_view(net, r[which]);
+        return true;
     }
-    uint64_t param_count(int which) override { return which == -1 ? (uint64_t)net.out_dim : net.ref_total; }
-    int32_t get_params(int which, float* out, uint64_t n) override
-    {
-        float* src = arena_ptr(which);
-        BDR_REQUIRE(src, "which must be 0..4");
-        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)net.ref_total);
-        std::vector<float> in(net.total);
-        BDR_HIP(hipMemcpyAsync(in.data(), src, net.total * 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        mlp_to_reference(net, 0, in.data(), out);
-        return BDR_OK;
-    }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
-    {
-        float* dst = arena_ptr(which);
-        BDR_REQUIRE(dst, "which must be 0..4");
-        BDR_REQUIRE(n == net.ref_total, "parameter count mismatch");
-        std::vector<float> in(net.total, 0.f);
-        mlp_to_internal(net, 0, inp, in.data());
-        BDR_HIP(hipMemcpyAsync(dst, in.data(), net.total * 4, hipMemcpyHostToDevice, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
-    }
-    float* arena(int which, size_t* n) override { if (n) *n = net.total; return arena_ptr(which); }
-    std::vector<NamedTensor> meta() const
+    int n_actions() const override { return net.out_dim; }
+    void checkpoint_files(std::vector<CheckpointFile>& files) override   // dqn/base.rs:348-356: qnet.pt.tch, qnet_tgt.pt.tch
     {
         std::vector<NamedTensor> mt;
-        for (size_t i = 0; i < net.L.size(); ++i) {
-            mt.push_back({"mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)net.L[i].out, (uint64_t)net.L[i].in}});
-            mt.push_back({"mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)net.L[i].out}});
-        }
-        return mt;
-    }
-    int32_t save(const char* dir) override
-    {
-        std::vector<float> ref(net.ref_total);
-        BDR_TRY(get_params(0, ref.data(), ref.size()));
-        BDR_TRY(save_named(ckpt_save_path(this, dir, "qnet"), meta(), ref.data(), ref.size()));
-        BDR_TRY(get_params(1, ref.data(), ref.size()));
-        return save_named(ckpt_save_path(this, dir, "qnet_tgt"), meta(), ref.data(), ref.size());
-    }
-    int32_t load(const char* dir) override
-    {
-        std::vector<float> ref(net.ref_total);
-        BDR_TRY(load_named(ckpt_load_path(this, dir, "qnet"), meta(), ref.data(), ref.size()));
-        BDR_TRY(set_params(0, ref.data(), ref.size()));
-        BDR_TRY(load_named(ckpt_load_path(this, dir, "qnet_tgt"), meta(), ref.data(), ref.size()));
-        return set_params(1, ref.data(), ref.size());
+        mlp_tensors(net, "mlp.ln", mt);
+        files = {{"qnet", mt, {0}, {0}}, {"qnet_tgt", mt, {1}, {1}}};
     }
 };
 

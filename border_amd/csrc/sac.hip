@@ -947,103 +947,35 @@ struct Sac : bdr_agent, SacBatch {
     }
 
     // which: 0 pi, 1+i qnet_i, 1+NC+i qnet_tgt_i, 1+2NC log_alpha;  +100 grad, +200 exp_avg, +300 exp_avg_sq, +400 max_exp_avg_sq (AdamW{amsgrad})
-    struct Slot { float* p; const MlpLayout* lay; size_t n; };
-    Slot slot(int which)
+    bool param_view(int which, ParamView* pv) override
     {
         const int role = which / 100, id = which % 100;
-        if (id == 0) { float* r[5] = {pi_p, pi_g, pi_m, pi_v, pi_vmax}; return role < 5 && r[role] ? Slot{r[role], &pi, pi.total} : Slot{nullptr, nullptr, 0}; }
-        if (id >= 1 && id <= NC) { const int i = id - 1; float* r[5] = {q_p[i], q_g[i], q_m[i], q_v[i], q_vmax[i]}; return role < 5 && r[role] ? Slot{r[role], &qn, qn.total} : Slot{nullptr, nullptr, 0}; }
-        if (id >= 1 + NC && id <= 2 * NC && role == 0) return Slot{q_t[id - 1 - NC], &qn, qn.total};
-        if (id == 1 + 2 * NC) { float* r[4] = {log_alpha, nullptr, al_m, al_v}; return (role < 4 && r[role]) ? Slot{r[role], nullptr, 4} : Slot{nullptr, nullptr, 0}; }
-        return Slot{nullptr, nullptr, 0};
+        if (which < 0 || role > 4) return false;
+        float* a = nullptr; const MlpLayout* lay = nullptr;
+        if (id == 0) { float* r[5] = {pi_p, pi_g, pi_m, pi_v, pi_vmax}; a = r[role]; lay = &pi; }
+        else if (id >= 1 && id <= NC) { const int i = id - 1; float* r[5] = {q_p[i], q_g[i], q_m[i], q_v[i], q_vmax[i]}; a = r[role]; lay = &qn; }
+        else if (id >= 1 + NC && id <= 2 * NC && role == 0) { a = q_t[id - 1 - NC]; lay = &qn; }
+        else if (id == 1 + 2 * NC) { float* r[5] = {log_alpha, nullptr, al_m, al_v, nullptr}; a = r[role]; }
+        if (!a) return false;
+        if (lay) *pv = mlp_view(*lay, a);
+        else *pv = {a, 4, 1, [](const float* in, float* ref) { ref[0] = in[0]; }, [](const float* ref, float* in) { in[0] = ref[0]; }};   // log_alpha: one value
+        return true;
     }
-    uint64_t param_count(int which) override
+    // SyncModel ships only `pi` (sac/base.rs:377-386); the caller (a parameter exchange) enqueues work on `stream` the flags know nothing about
+    void arena_handed_out(int) override { main_ahead = true; }
+    void checkpoint_files(std::vector<CheckpointFile>& files) override   // sac/base.rs:313-328: qnet_{i}, qnet_tgt_{i}, pi, ent_coef
     {
-        Slot s = slot(which);
-        if (!s.p) return 0;
-        return s.lay ? s.lay->ref_total : 1;
-    }
-    int32_t get_params(int which, float* out, uint64_t n) override
-    {
-        Slot s = slot(which);
-        BDR_REQUIRE(s.p, "unknown SAC model %d", which);
-        BDR_REQUIRE(n == param_count(which), "parameter count mismatch (%llu vs %llu)", (unsigned long long)n, (unsigned long long)param_count(which));
-        std::vector<float> in(s.n);
-        BDR_HIP(hipMemcpyAsync(in.data(), s.p, s.n * 4, hipMemcpyDeviceToHost, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        if (s.lay) mlp_to_reference(*s.lay, 0, in.data(), out); else out[0] = in[0];
-        return BDR_OK;
-    }
-    int32_t set_params(int which, const float* inp, uint64_t n) override
-    {
-        Slot s = slot(which);
-        BDR_REQUIRE(s.p, "unknown SAC model %d", which);
-        BDR_REQUIRE(n == param_count(which), "parameter count mismatch");
-        std::vector<float> in(s.n, 0.f);
-        if (s.lay) mlp_to_internal(*s.lay, 0, inp, in.data()); else in[0] = inp[0];
-        BDR_HIP(hipMemcpyAsync(s.p, in.data(), s.n * 4, hipMemcpyHostToDevice, stream));
-        BDR_HIP(hipStreamSynchronize(stream));
-        return BDR_OK;
-    }
-    // SyncModel ships only `pi` (sac/base.rs:377-386)
-    float* arena(int which, size_t* n) override
-    {
-        main_ahead = true;   // the caller (a parameter exchange) enqueues work on `stream` the flags know nothing about
-        Slot s = slot(which); if (n) *n = s.n; return s.p;
-    }
-
-    std::vector<NamedTensor> pi_meta() const
-    {
-        std::vector<NamedTensor> mt;
-        for (int i = 0; i < n_trunk; ++i) {
-            mt.push_back({"mlp.al" + std::to_string(i) + ".weight", {(uint64_t)pi.L[i].out, (uint64_t)pi.L[i].in}});
-            mt.push_back({"mlp.al" + std::to_string(i) + ".bias", {(uint64_t)pi.L[i].out}});
-        }
+        std::vector<NamedTensor> mt, qt;
+        mlp_tensors(pi, "mlp.al", mt, 0, n_trunk);
         const auto& h = pi.L[n_trunk];
-        mt.push_back({"ml.weight", {(uint64_t)h.out, (uint64_t)h.in}}); mt.push_back({"ml.bias", {(uint64_t)h.out}});
-        mt.push_back({"sl.weight", {(uint64_t)h.out, (uint64_t)h.in}}); mt.push_back({"sl.bias", {(uint64_t)h.out}});
-        return mt;
-    }
-    std::vector<NamedTensor> q_meta() const
-    {
-        std::vector<NamedTensor> mt;
-        for (size_t i = 0; i < qn.L.size(); ++i) {
-            mt.push_back({"mlp.ln" + std::to_string(i) + ".weight", {(uint64_t)qn.L[i].out, (uint64_t)qn.L[i].in}});
-            mt.push_back({"mlp.ln" + std::to_string(i) + ".bias", {(uint64_t)qn.L[i].out}});
-        }
-        return mt;
-    }
-    int32_t save(const char* dir) override   // sac/base.rs:313-328: qnet_{i}, qnet_tgt_{i}, pi, ent_coef
-    {
-        std::vector<float> v(pi.ref_total);
-        BDR_TRY(get_params(0, v.data(), v.size()));
-        BDR_TRY(save_named(ckpt_save_path(this, dir, "pi"), pi_meta(), v.data(), v.size()));
-        v.resize(qn.ref_total);
+        for (const char* hd : {"ml", "sl"}) { mt.push_back({std::string(hd) + ".weight", {(uint64_t)h.out, (uint64_t)h.in}}); mt.push_back({std::string(hd) + ".bias", {(uint64_t)h.out}}); }
+        mlp_tensors(qn, "mlp.ln", qt);
+        files = {{"pi", mt, {0}, {0}}};
         for (int i = 0; i < NC; ++i) {
-            BDR_TRY(get_params(1 + i, v.data(), v.size()));
-            BDR_TRY(save_named(ckpt_save_path(this, dir, "qnet_" + std::to_string(i)), q_meta(), v.data(), v.size()));
-            BDR_TRY(get_params(1 + NC + i, v.data(), v.size()));
-            BDR_TRY(save_named(ckpt_save_path(this, dir, "qnet_tgt_" + std::to_string(i)), q_meta(), v.data(), v.size()));
+            files.push_back({"qnet_" + std::to_string(i), qt, {1 + i}, {1 + i}});
+            files.push_back({"qnet_tgt_" + std::to_string(i), qt, {1 + NC + i}, {1 + NC + i}});
         }
-        float la = 0;
-        BDR_TRY(get_params(1 + 2 * NC, &la, 1));
-        return save_named(ckpt_save_path(this, dir, "ent_coef"), {{"log_alpha", {1}}}, &la, 1);
-    }
-    int32_t load(const char* dir) override
-    {
-        std::vector<float> v(pi.ref_total);
-        BDR_TRY(load_named(ckpt_load_path(this, dir, "pi"), pi_meta(), v.data(), v.size()));
-        BDR_TRY(set_params(0, v.data(), v.size()));
-        v.resize(qn.ref_total);
-        for (int i = 0; i < NC; ++i) {
-            BDR_TRY(load_named(ckpt_load_path(this, dir, "qnet_" + std::to_string(i)), q_meta(), v.data(), v.size()));
-            BDR_TRY(set_params(1 + i, v.data(), v.size()));
-            BDR_TRY(load_named(ckpt_load_path(this, dir, "qnet_tgt_" + std::to_string(i)), q_meta(), v.data(), v.size()));
-            BDR_TRY(set_params(1 + NC + i, v.data(), v.size()));
-        }
-        float la = 0;
-        BDR_TRY(load_named(ckpt_load_path(this, dir, "ent_coef"), {{"log_alpha", {1}}}, &la, 1));
-        return set_params(1 + 2 * NC, &la, 1);
+        files.push_back({"ent_coef", {{"log_alpha", {1}}}, {1 + 2 * NC}, {1 + 2 * NC}});
     }
 };
 

@@ -12,14 +12,13 @@ All arithmetic runs in the HIP library; there is no CPU fallback here.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass, field
 from typing import Optional, Tuple
 
 import numpy as np
 
 from . import _lib
-from .replay import SimpleReplayBuffer
+from .handle import AgentHandle, _p, draw_noise, opt_with_named_record, record_keys  # noqa: F401  (the helpers: importable from here as before)
 
 
 @dataclass
@@ -146,82 +145,82 @@ class DqnConfig:
         return c
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+def _sample_info(info) -> dict:
+    return {"eps": info.eps, "is_random": bool(info.is_random), "n_samples_act": info.n_samples_act, "n_samples_best_act": info.n_samples_best_act}
 
 
-def record_keys(handle) -> list:
-    names = C.create_string_buffer(8192)
-    n = C.c_int32()
-    _lib.check(_lib.lib().bdr_agent_record_keys(handle, names, 8192, C.byref(n)))
-    return names.value.decode().split("\n")[:n.value]
+class TchValueAgent(AgentHandle):
+    """What the handles of the tch Dqn and Iqn share on AgentHandle: their arenas are MODELS 0..5 named by WHICH (no roles), their files
+    are `<stem>.pt.tch` archives, and Policy::sample returns int64 actions from the library's exploration stream."""
+    CKPT_EXTS = {"tch": ".pt.tch", "safetensors": ".safetensors"}
+
+    def param_count(self) -> int:
+        n = C.c_uint64()
+        _lib.check(_lib.lib().bdr_agent_param_count(self._h, C.byref(n)))
+        return n.value
+
+    def get_params(self, which) -> np.ndarray:
+        out = np.empty(self.param_count(), np.float32)
+        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.WHICH[which], _p(out), out.size))
+        return out
+
+    def set_params(self, params: np.ndarray, which) -> None:
+        p = np.ascontiguousarray(params, dtype=np.float32)
+        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.WHICH[which], _p(p), p.size))
+
+    def set_explorer(self, explorer: "Softmax | EpsilonGreedy", seed: int = 0) -> None:
+        """DqnConfig::explorer (dqn/config.rs:45), IqnConfig::explorer (iqn/config.rs:35; default Softmax); `seed` seeds the library's
+        exploration stream."""
+        _lib.check(_lib.lib().bdr_agent_set_explorer(self._h, C.byref(explorer.to_c(seed))))
+
+    def sample(self, obs, return_info: bool = False):
+        """Policy::sample (dqn/base.rs:211-242, iqn/base.rs:204-228): forward on the device + the configured exploration (train) /
+        argmax (eval).  obs: [n_procs, ...] rows as stored in the replay buffer; returns int64 actions [n_procs]."""
+        obs = np.ascontiguousarray(obs)
+        a = np.empty(obs.shape[0], np.int64)
+        info = _lib.SampleInfoC()
+        _lib.check(_lib.lib().bdr_agent_sample(self._h, obs.shape[0], _p(obs), _p(a), C.byref(info)))
+        return (a, _sample_info(info)) if return_info else a
+
+    def sample_device(self, obs_dev: int, n: int, row_stride: int, return_info: bool = False):
+        """Policy::sample for observation rows already in HBM (`bdr_agent_sample_device`): row i at obs_dev + i * row_stride bytes."""
+        a = np.empty(n, np.int64)
+        info = _lib.SampleInfoC()
+        _lib.check(_lib.lib().bdr_agent_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(a), C.byref(info)))
+        return (a, _sample_info(info)) if return_info else a
+
+    def qvalues_device(self, obs_dev: int, n: int, row_stride: int) -> np.ndarray:
+        q = np.empty((n, self.n_actions), np.float32)
+        _lib.check(_lib.lib().bdr_agent_qvalues_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(q), None))
+        return q
 
 
-def opt_with_named_record(handle, buffer) -> dict:
-    """bdr_agent_opt_with_scalars + bdr_agent_record_keys: the reference's Record of one opt_with_record call."""
-    out = np.zeros(128, np.float32)
-    n = C.c_int32()
-    _lib.check(_lib.lib().bdr_agent_opt_with_scalars(handle, buffer.handle, _p(out), 128, C.byref(n)))
-    return {k: float(v) for k, v in zip(record_keys(handle), out[:n.value])}
-
-
-def draw_noise(handle, n: int) -> np.ndarray:
-    out = np.empty(n, np.float32)
-    _lib.check(_lib.lib().bdr_agent_draw_noise(handle, n, _p(out)))
-    return out
-
-
-class Dqn:
-    """Dqn<E, Q, R> (dqn/base.rs:22-48)."""
+class Dqn(TchValueAgent):
+    """Dqn<E, Q, R> (dqn/base.rs:22-48); Configurable::build (:252-286); checkpoints qnet, qnet_tgt (:348-356); SyncModel ships
+    qnet (:377-402)."""
+    KIND = "dqn"
+    CKPT_STEMS = ("qnet", "qnet_tgt")
+    SYNC_MODEL = "qnet"
+    WHICH = {"qnet": 0, "qnet_tgt": 1, "exp_avg": 2, "exp_avg_sq": 3, "grad": 4, "max_exp_avg_sq": 5}
 
     def __init__(self, config: DqnConfig):
-        self.config = config
-        h = C.c_void_p()
-        c = config.to_c()
-        _lib.check(_lib.lib().bdr_dqn_create(C.byref(c), C.byref(h)))
-        self._h = h
+        super().__init__(config)
         self.n_actions = config.model_config.q_config.out_dim
-
-    @classmethod
-    def build(cls, config: DqnConfig) -> "Dqn":   # Configurable::build (dqn/base.rs:252-286)
-        return cls(config)
 
     def close(self):
         if getattr(self, "_h", None):
             _lib.check(_lib.lib().bdr_agent_destroy(self._h))   # (refused for a member of a live DqnGroup: the group owns it)
             self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    # the parameter views under this class's own signatures: `qnet` is the literal default
+    def arena_device_ptr(self, which="qnet"):
+        return super().arena_device_ptr(which)
 
-    @property
-    def handle(self):
-        return self._h
+    def get_params(self, which="qnet") -> np.ndarray:
+        return super().get_params(which)
 
-    # Agent ----------------------------------------------------------------------------------
-    def train(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 1))
-
-    def eval(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 0))
-
-    def is_train(self) -> bool:
-        v = C.c_int32()
-        _lib.check(_lib.lib().bdr_agent_is_train(self._h, C.byref(v)))
-        return bool(v.value)
-
-    def opt(self, buffer: SimpleReplayBuffer) -> None:
-        """Agent::opt -- enqueue one optimisation step; does not synchronise."""
-        _lib.check(_lib.lib().bdr_agent_opt(self._h, buffer.handle))
-
-    def opt_with_record(self, buffer: SimpleReplayBuffer) -> dict:
-        """Agent::opt_with_record (dqn/base.rs:316-342): the Record as a dict - "loss"; with record_verbose_level >= 2 also
-        pred_mean / reward_mean / tgt_mean / tgt_minus_pred_mean, `<var>_mean` / `<var>_std` of every qnet variable
-        (param_stats, util.rs:64-80) and ratio_best_act (which resets the sample counters)."""
-        return opt_with_named_record(self._h, buffer)
+    def set_params(self, params: np.ndarray, which="qnet") -> None:
+        super().set_params(params, which)
 
     @staticmethod
     def _record(r) -> dict:
@@ -267,68 +266,11 @@ class Dqn:
         """The optimizer step on the gradient arena + opt_'s bookkeeping (soft update counter, n_opts)."""
         _lib.check(_lib.lib().bdr_agent_apply_grads(self._h))
 
-    def sync(self):
-        _lib.check(_lib.lib().bdr_agent_sync(self._h))
-
-    @property
-    def n_opts(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
-        return n.value
-
-    def set_checkpoint_format(self, fmt: str) -> None:
-        """"tch" (default): `<stem>.pt.tch` libtorch archives, the reference's files; "safetensors": `<stem>.safetensors`."""
-        from .checkpoint import FORMATS
-        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
-        self._ckpt_ext = {"tch": ".pt.tch", "safetensors": ".safetensors"}[fmt]
-
-    def save_params(self, path: str):
-        os.makedirs(path, exist_ok=True)
-        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
-        ext = getattr(self, "_ckpt_ext", ".pt.tch")
-        return [os.path.join(path, stem + ext) for stem in ["qnet", "qnet_tgt"]]
-
-    def load_params(self, path: str):
-        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))
-
-    # Policy ----------------------------------------------------------------------------------------
-    def set_explorer(self, explorer: "Softmax | EpsilonGreedy", seed: int = 0) -> None:
-        """DqnConfig::explorer (dqn/config.rs:45); `seed` seeds the library's exploration stream."""
-        _lib.check(_lib.lib().bdr_agent_set_explorer(self._h, C.byref(explorer.to_c(seed))))
-
     def explorer_state(self) -> dict:
         e = _lib.ExplorerConfigC()
         _lib.check(_lib.lib().bdr_agent_get_explorer(self._h, C.byref(e)))
         return {"kind": "softmax" if e.kind == 0 else "eps_greedy", "eps_start": e.eps_start, "eps_final": e.eps_final,
                 "final_step": e.final_step, "n_opts": e.n_calls}
-
-    def sample(self, obs, return_info: bool = False):
-        """Policy::sample (dqn/base.rs:211-242): forward on the device + the configured exploration.
-        obs: [n_procs, ...] rows as stored in the replay buffer; returns int64 actions [n_procs]."""
-        obs = np.ascontiguousarray(obs)
-        n = obs.shape[0]
-        a = np.empty(n, np.int64)
-        info = _lib.SampleInfoC()
-        _lib.check(_lib.lib().bdr_agent_sample(self._h, n, _p(obs), _p(a), C.byref(info)))
-        if return_info:
-            return a, {"eps": info.eps, "is_random": bool(info.is_random), "n_samples_act": info.n_samples_act,
-                       "n_samples_best_act": info.n_samples_best_act}
-        return a
-
-    def sample_device(self, obs_dev: int, n: int, row_stride: int, return_info: bool = False):
-        """Policy::sample for observation rows already in HBM (`bdr_agent_sample_device`): row i at obs_dev + i * row_stride bytes."""
-        a = np.empty(n, np.int64)
-        info = _lib.SampleInfoC()
-        _lib.check(_lib.lib().bdr_agent_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(a), C.byref(info)))
-        if return_info:
-            return a, {"eps": info.eps, "is_random": bool(info.is_random), "n_samples_act": info.n_samples_act,
-                       "n_samples_best_act": info.n_samples_best_act}
-        return a
-
-    def qvalues_device(self, obs_dev: int, n: int, row_stride: int) -> np.ndarray:
-        q = np.empty((n, self.n_actions), np.float32)
-        _lib.check(_lib.lib().bdr_agent_qvalues_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(q), None))
-        return q
 
     def qvalues(self, obs) -> np.ndarray:
         obs = np.ascontiguousarray(obs)
@@ -344,42 +286,10 @@ class Dqn:
         _lib.check(_lib.lib().bdr_agent_qvalues(self._h, n, _p(obs), None, _p(a)))
         return a
 
-    # SyncModel / parameter access --------------------------------------------------------------
-    WHICH = {"qnet": 0, "qnet_tgt": 1, "exp_avg": 2, "exp_avg_sq": 3, "grad": 4, "max_exp_avg_sq": 5}
-
-    def arena_device_ptr(self, which="qnet"):
-        """(device pointer, float count) of the flat parameter arena in the kernels' internal layout."""
-        ptr, n = C.c_void_p(), C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
-        return ptr.value, n.value
-
     def arena_release(self, which="qnet") -> None:
         """hands an arena back after arena_device_ptr: the library's derived copies (bf16 weight planes) are trusted again"""
         _lib.check(_lib.lib().bdr_agent_arena_release(self._h, self.WHICH[which]))
 
-    def param_count(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_param_count(self._h, C.byref(n)))
-        return n.value
-
-    def get_params(self, which="qnet") -> np.ndarray:
-        out = np.empty(self.param_count(), np.float32)
-        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.WHICH[which], _p(out), out.size))
-        return out
-
-    def set_params(self, params: np.ndarray, which="qnet") -> None:
-        p = np.ascontiguousarray(params, dtype=np.float32)
-        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.WHICH[which], _p(p), p.size))
-
-    def model_info(self):
-        """SyncModel::model_info (dqn/base.rs:377-389): (n_opts, qnet parameters)."""
-        return self.n_opts, self.get_params("qnet")
-
-    def sync_model(self, model_info) -> None:
-        """SyncModel::sync_model (dqn/base.rs:391-402)."""
-        self.set_params(model_info, "qnet")
-
-    # probes / profiling ----------------------------------------------------------------------
     def probe(self, what: str, n: int) -> np.ndarray:
         idx = {"q_pred_all": 0, "q_next_all": 1, "pred": 2, "tgt": 3, "loss": 4, "act_conv1": 5, "act_conv2": 6, "act_conv3": 7,
                "h1": 8, "dq": 9, "dh1": 10, "dy3": 11, "dy2": 12, "dy1": 13}[what]   # 8-13 AtariCnn only: the backward pass's inputs and intermediates
@@ -387,13 +297,6 @@ class Dqn:
         _lib.check(_lib.lib().bdr_dqn_probe(self._h, idx, _p(out), n))
         return out
 
-    def profile_enable(self, on: bool = True):
-        _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
-
     def profile_read(self) -> dict:
-        cnt = C.c_uint64(256)
-        names = C.create_string_buffer(8192)
-        ms = np.zeros(256, np.float32)
-        _lib.check(_lib.lib().bdr_agent_profile_read(self._h, names, 8192, _p(ms), C.byref(cnt)))
-        labels = names.value.decode().split("\n")[:cnt.value]
-        return {l: float(ms[i]) for i, l in enumerate(labels)}
+        """{bracket name: mean milliseconds} (AgentHandle.profile_read as a dict)"""
+        return dict(super().profile_read())

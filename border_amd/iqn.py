@@ -8,15 +8,14 @@
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass, field
 from typing import Optional, Tuple
 
 import numpy as np
 
 from . import _lib
-from .dqn import AtariCnnConfig, MlpConfig, OptimizerConfig
-from .replay import SimpleReplayBuffer
+from .dqn import AtariCnnConfig, MlpConfig, OptimizerConfig, TchValueAgent
+from .handle import _p
 
 IQN_SAMPLE = {"Const10": 0, "Const32": 1, "Uniform10": 2, "Uniform8": 3, "Uniform32": 4, "Uniform64": 5, "Median": 6}
 
@@ -70,65 +69,26 @@ class IqnConfig:
         return c
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class Iqn:
+class Iqn(TchValueAgent):
+    """iqn/base.rs; checkpoints iqn, iqn_tgt; the models are named as the tch Dqn names them ("qnet" is "iqn")."""
+    KIND = "iqn"
+    CKPT_STEMS = ("iqn", "iqn_tgt")
+    SYNC_MODEL = "iqn"
     WHICH = {"qnet": 0, "iqn": 0, "iqn_tgt": 1, "exp_avg": 2, "exp_avg_sq": 3, "grad": 4, "max_exp_avg_sq": 5}
 
-    def arena_device_ptr(self, which="iqn"):
-        """(device pointer, float count) of a flat parameter arena in the kernels' internal layout."""
-        ptr, n = C.c_void_p(), C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
-        return ptr.value, n.value
-
     def __init__(self, config: IqnConfig):
-        self.config = config
-        h = C.c_void_p()
-        c = config.to_c()
-        _lib.check(_lib.lib().bdr_iqn_create(C.byref(c), C.byref(h)))
-        self._h = h
+        super().__init__(config)
+        self.n_actions = config.n_actions
 
-    @classmethod
-    def build(cls, config: IqnConfig) -> "Iqn":
-        return cls(config)
+    # the parameter views under this class's own signatures: `iqn` is the literal default
+    def arena_device_ptr(self, which="iqn"):
+        return super().arena_device_ptr(which)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().bdr_agent_destroy(self._h)
-            self._h = None
+    def get_params(self, which="iqn") -> np.ndarray:
+        return super().get_params(which)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    def train(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 1))
-
-    def eval(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 0))
-
-    def opt(self, buffer: SimpleReplayBuffer) -> None:
-        _lib.check(_lib.lib().bdr_agent_opt(self._h, buffer.handle))
-
-    def opt_with_record(self, buffer: SimpleReplayBuffer) -> dict:
-        from .dqn import opt_with_named_record
-        return opt_with_named_record(self._h, buffer)
-
-    def profile_enable(self, on: bool = True):
-        _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
-
-    def draw_noise(self, n: int) -> np.ndarray:
-        """n draws of the agent's device noise stream (test helper, bdr_agent_draw_noise)."""
-        from .dqn import draw_noise
-        return draw_noise(self._h, n)
+    def set_params(self, params, which="iqn") -> None:
+        super().set_params(params, which)
 
     def update_on_batch(self, obs, act, next_obs, reward, is_terminated, tau_pred, tau_tgt) -> dict:
         reward = np.ascontiguousarray(reward, dtype=np.float32)
@@ -174,77 +134,8 @@ class Iqn:
         _lib.check(_lib.lib().bdr_iqn_probe(self._h, self.PROBE[what] + (i if self.PROBE[what] >= 16 else 0), _p(out), out.size))
         return out
 
-    def sample_device(self, obs_dev: int, n: int, row_stride: int, return_info: bool = False):
-        """Policy::sample for observation rows already in HBM (`bdr_agent_sample_device`): row i at obs_dev + i * row_stride bytes."""
-        a = np.empty(n, np.int64)
-        info = _lib.SampleInfoC()
-        _lib.check(_lib.lib().bdr_agent_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(a), C.byref(info)))
-        if return_info:
-            return a, {"eps": info.eps, "is_random": bool(info.is_random), "n_samples_act": info.n_samples_act,
-                       "n_samples_best_act": info.n_samples_best_act}
-        return a
-
-    def qvalues_device(self, obs_dev: int, n: int, row_stride: int) -> np.ndarray:
-        q = np.empty((n, self.config.n_actions), np.float32)
-        _lib.check(_lib.lib().bdr_agent_qvalues_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(q), None))
-        return q
-
     def qvalues(self, obs) -> np.ndarray:
         obs = np.ascontiguousarray(obs)
         q = np.empty((obs.shape[0], self.config.n_actions), np.float32)
         _lib.check(_lib.lib().bdr_iqn_qvalues(self._h, obs.shape[0], _p(obs), _p(q), None))
         return q
-
-    def set_explorer(self, explorer, seed: int = 0) -> None:
-        """IqnConfig::explorer (iqn/config.rs:35; default Softmax, :62)."""
-        _lib.check(_lib.lib().bdr_agent_set_explorer(self._h, C.byref(explorer.to_c(seed))))
-
-    def sample(self, obs, return_info: bool = False):
-        """Policy::sample (iqn/base.rs:204-228): quantile-averaged action values + exploration (train) / argmax (eval)."""
-        obs = np.ascontiguousarray(obs)
-        n = obs.shape[0]
-        a = np.empty(n, np.int64)
-        info = _lib.SampleInfoC()
-        _lib.check(_lib.lib().bdr_agent_sample(self._h, n, _p(obs), _p(a), C.byref(info)))
-        if return_info:
-            return a, {"eps": info.eps, "is_random": bool(info.is_random), "n_samples_act": info.n_samples_act,
-                       "n_samples_best_act": info.n_samples_best_act}
-        return a
-
-    def sync(self):
-        _lib.check(_lib.lib().bdr_agent_sync(self._h))
-
-    @property
-    def n_opts(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
-        return n.value
-
-    def param_count(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_param_count(self._h, C.byref(n)))
-        return n.value
-
-    def get_params(self, which="iqn") -> np.ndarray:
-        out = np.empty(self.param_count(), np.float32)
-        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.WHICH[which], _p(out), out.size))
-        return out
-
-    def set_params(self, params, which="iqn") -> None:
-        p = np.ascontiguousarray(params, dtype=np.float32)
-        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.WHICH[which], _p(p), p.size))
-
-    def set_checkpoint_format(self, fmt: str) -> None:
-        """"tch" (default): `<stem>.pt.tch` libtorch archives, the reference's files; "safetensors": `<stem>.safetensors`."""
-        from .checkpoint import FORMATS
-        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
-        self._ckpt_ext = {"tch": ".pt.tch", "safetensors": ".safetensors"}[fmt]
-
-    def save_params(self, path: str):
-        os.makedirs(path, exist_ok=True)
-        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
-        ext = getattr(self, "_ckpt_ext", ".pt.tch")
-        return [os.path.join(path, stem + ext) for stem in ["iqn", "iqn_tgt"]]
-
-    def load_params(self, path: str):
-        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))

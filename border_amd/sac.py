@@ -7,7 +7,6 @@
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -15,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .dqn import OptimizerConfig
-from .replay import SimpleReplayBuffer
+from .handle import ROLES, AgentHandle, _p
 
 
 @dataclass
@@ -71,77 +70,42 @@ class SacConfig:
         return c
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class Sac:
-    def __init__(self, config: SacConfig):
-        self.config = config
-        h = C.c_void_p()
-        c = config.to_c()
-        _lib.check(_lib.lib().bdr_sac_create(C.byref(c), C.byref(h)))
-        self._h = h
-
-    @classmethod
-    def build(cls, config: SacConfig) -> "Sac":
-        return cls(config)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().bdr_agent_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class Sac(AgentHandle):
+    """sac/base.rs; SyncModel ships only the policy network `pi` (:377-386)."""
+    KIND = "sac"
+    SYNC_MODEL = "pi"
+    WHICH = {"qnet": 0, "pi": 0}   # ParamExchange / ModelMailbox: SyncModel ships `pi` == model 0
+    CKPT_EXTS = {"tch": ".pt.tch", "safetensors": ".safetensors"}
+    ROLES = {**ROLES, "max_exp_avg_sq": 400}   # AdamW{amsgrad}
 
     @property
-    def handle(self):
-        return self._h
+    def CKPT_STEMS(self):   # sac/base.rs:313-334 order
+        return [s for i in range(self.config.n_critics) for s in (f"qnet_{i}", f"qnet_tgt_{i}")] + ["pi", "ent_coef"]
 
-    # model ids (bdr_agent_get_params `which`)
-    def which(self, name: str, role: str = "param") -> int:
+    def _model_id(self, name: str) -> int:
+        """pi 0, qnet_i 1 + i, qnet_tgt_i 1 + n_critics + i, log_alpha 1 + 2 n_critics"""
         nc = self.config.n_critics
-        base = {"pi": 0, "log_alpha": 1 + 2 * nc}
         if name.startswith("qnet_tgt_"):
-            i = 1 + nc + int(name[len("qnet_tgt_"):])
-        elif name.startswith("qnet_"):
-            i = 1 + int(name[len("qnet_"):])
-        else:
-            i = base[name]
-        return i + {"param": 0, "grad": 100, "exp_avg": 200, "exp_avg_sq": 300, "max_exp_avg_sq": 400}[role]
+            return 1 + nc + int(name[len("qnet_tgt_"):])
+        if name.startswith("qnet_"):
+            return 1 + int(name[len("qnet_"):])
+        return {"pi": 0, "log_alpha": 1 + 2 * nc}[name]
 
-    WHICH = {"qnet": 0, "pi": 0}   # ParamExchange / ModelMailbox: SyncModel ships `pi` (sac/base.rs:377-386) == model 0
+    # AgentHandle's parameter views under this class's own signatures: `pi` is the literal default, `which` needs a name
+    def which(self, name: str, role: str = "param") -> int:
+        return super().which(name, role)
 
     def arena_device_ptr(self, which="pi"):
-        """(device pointer, float count) of a flat parameter arena in the kernels' internal layout."""
-        ptr, n = C.c_void_p(), C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_arena_device_ptr(self._h, self.WHICH[which], C.byref(ptr), C.byref(n)))
-        return ptr.value, n.value
+        return super().arena_device_ptr(which)
 
-    def train(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 1))
+    def param_count(self, name="pi") -> int:
+        return super().param_count(name)
 
-    def eval(self):
-        _lib.check(_lib.lib().bdr_agent_set_train(self._h, 0))
+    def get_params(self, name="pi", role="param") -> np.ndarray:
+        return super().get_params(name, role)
 
-    def opt(self, buffer: SimpleReplayBuffer) -> None:
-        _lib.check(_lib.lib().bdr_agent_opt(self._h, buffer.handle))
-
-    def opt_with_record(self, buffer: SimpleReplayBuffer) -> dict:
-        from .dqn import opt_with_named_record
-        return opt_with_named_record(self._h, buffer)
-
-    def profile_enable(self, on: bool = True):
-        _lib.check(_lib.lib().bdr_agent_profile_enable(self._h, int(on)))
-
-    def draw_noise(self, n: int) -> np.ndarray:
-        """n draws of the agent's device noise stream (test helper, bdr_agent_draw_noise)."""
-        from .dqn import draw_noise
-        return draw_noise(self._h, n)
+    def set_params(self, params, name="pi", role="param") -> None:
+        super().set_params(params, name, role)
 
     def update_on_batch(self, obs, act, next_obs, reward, is_terminated, z_actor, z_next) -> dict:
         f = lambda x: np.ascontiguousarray(x, dtype=np.float32)
@@ -174,50 +138,3 @@ class Sac:
         out = np.empty((n, self.config.act_dim), np.float32)
         _lib.check(_lib.lib().bdr_sac_sample_device(self._h, n, C.c_void_p(obs_dev), row_stride, _p(out)))
         return out
-
-    def sync(self):
-        _lib.check(_lib.lib().bdr_agent_sync(self._h))
-
-    @property
-    def n_opts(self) -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_n_opts(self._h, C.byref(n)))
-        return n.value
-
-    def param_count(self, name="pi") -> int:
-        n = C.c_uint64()
-        _lib.check(_lib.lib().bdr_agent_param_count_of(self._h, self.which(name), C.byref(n)))
-        return n.value
-
-    def get_params(self, name="pi", role="param") -> np.ndarray:
-        out = np.empty(self.param_count(name), np.float32)
-        _lib.check(_lib.lib().bdr_agent_get_params(self._h, self.which(name, role), _p(out), out.size))
-        return out
-
-    def set_params(self, params, name="pi", role="param") -> None:
-        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
-        _lib.check(_lib.lib().bdr_agent_set_params(self._h, self.which(name, role), _p(p), p.size))
-
-    def model_info(self):
-        """SyncModel::model_info (sac/base.rs:377-383): only the policy network."""
-        return self.n_opts, self.get_params("pi")
-
-    def sync_model(self, model_info) -> None:
-        self.set_params(model_info, "pi")
-
-    def set_checkpoint_format(self, fmt: str) -> None:
-        """"tch" (default): `<stem>.pt.tch` libtorch archives, the reference's files; "safetensors": `<stem>.safetensors`."""
-        from .checkpoint import FORMATS
-        _lib.check(_lib.lib().bdr_agent_set_checkpoint_format(self._h, FORMATS[fmt]))
-        self._ckpt_ext = {"tch": ".pt.tch", "safetensors": ".safetensors"}[fmt]
-
-    def save_params(self, path: str):
-        os.makedirs(path, exist_ok=True)
-        _lib.check(_lib.lib().bdr_agent_save_params(self._h, path.encode()))
-        nc = self.config.n_critics
-        ext = getattr(self, "_ckpt_ext", ".pt.tch")
-        stems = [s for i in range(nc) for s in (f"qnet_{i}", f"qnet_tgt_{i}")] + ["pi", "ent_coef"]   # sac/base.rs:313-334 order
-        return [os.path.join(path, stem + ext) for stem in stems]
-
-    def load_params(self, path: str):
-        _lib.check(_lib.lib().bdr_agent_load_params(self._h, path.encode()))
