@@ -272,6 +272,7 @@ ABI_SYMBOLS = [
     "bdr_agent_profile_enable", "bdr_agent_profile_read",
     "bdr_iqn_config_default", "bdr_iqn_create", "bdr_iqn_update_on_batch", "bdr_iqn_forward", "bdr_iqn_qvalues", "bdr_iqn_probe",
     "bdr_sac_config_default", "bdr_sac_create", "bdr_sac_update_on_batch", "bdr_sac_sample", "bdr_sac_sample_device",
+    "bdr_sac_keep_layers", "bdr_sac_layer_probe",
     "bdr_iql_config_default", "bdr_iql_create", "bdr_iql_update_on_batch", "bdr_iql_probe", "bdr_iql_sample", "bdr_iql_sample_device",
     "bdr_awac_config_default", "bdr_awac_create", "bdr_awac_update_on_batch", "bdr_awac_probe", "bdr_awac_sample", "bdr_awac_sample_device",
     "bdr_candle_sac_config_default", "bdr_candle_sac_create", "bdr_candle_sac_update_on_batch", "bdr_candle_sac_probe", "bdr_candle_sac_sample",
@@ -406,6 +407,8 @@ def lib() -> C.CDLL:
     L.bdr_sac_update_on_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.bdr_sac_sample.argtypes = [vp, u64, vp, vp]
     L.bdr_sac_probe.argtypes = [vp, i32, vp, u64]
+    L.bdr_sac_keep_layers.argtypes = [vp, i32]
+    L.bdr_sac_layer_probe.argtypes = [vp, i32, i32, i32, i32, vp, u64]
     L.bdr_iql_config_default.restype = None
     L.bdr_iql_config_default.argtypes = [C.POINTER(IqlConfigC)]
     L.bdr_iql_create.argtypes = [C.POINTER(IqlConfigC), C.POINTER(vp)]

@@ -333,6 +333,9 @@ struct Sac : bdr_agent, SacBatch {
     // update_on_batch only (probe_copy; never inside a captured step)
     bool probe_copy = false; int probe_B = 0; int last_B = 0;
     float* pr_qpi[4] = {nullptr}; float* pr_logp = nullptr;
+    // bdr_sac_layer_probe: with keep_layers on, update_on_batch copies everything the actor phase produced into `keep` (a third buffer
+    // set) behind the actor's Adam launch - the critic phase reuses those buffers.  live_B: rows of the last update / acting call.
+    bool keep_layers = false; SacBatch keep; int keep_cap = 0, keep_B = 0, live_B = 0; bool live_acting = false; float* keep_log_alpha = nullptr;
     StepGraph graph; StepGraphPolicy graph_policy;   // step_graph.hpp
     bool gather_in_pack = true;               // BDR_NO_STEP_GATHER=1: separate gather launch
     bool fuse_rows = true;                    // BDR_NO_SAC_FUSE=1: the narrow layers as launches of their own (sac_fused.hpp)
@@ -378,7 +381,7 @@ struct Sac : bdr_agent, SacBatch {
         (void)hipFree(u_obs); (void)hipFree(u_next); (void)hipFree(u_act); (void)hipFree(u_rew); (void)hipFree(u_term);
         for (int i = 0; i < 4; ++i) (void)hipFree(pr_qpi[i]);
         (void)hipFree(tickets); (void)hipFree(applied); (void)hipFree(head_tickets);
-        (void)hipFree(pr_logp);
+        (void)hipFree(pr_logp); (void)hipFree(keep_log_alpha);
     }
     static void free_set(SacBatch& b)
     {
@@ -397,7 +400,8 @@ struct Sac : bdr_agent, SacBatch {
     }
     void free_batch()
     {
-        free_set(*this); free_set(other);
+        free_set(*this); free_set(other); free_set(keep);
+        keep_cap = 0; keep_B = 0;
         float** singles[] = {&pi_part, &q_part, &lrow};
         for (auto p : singles) { (void)hipFree(*p); *p = nullptr; }
     }
@@ -604,6 +608,9 @@ struct Sac : bdr_agent, SacBatch {
     {
         return adam_scalars_for(o.opt_kind == BDR_OPT_ADAMW, lr, o.beta1, o.beta2, o.eps, o.weight_decay, step);
     }
+    // row chunks a weight-gradient launch of Bn rows uses of the `planned` ones (ensure_batch plans for the buffers' capacity): the one
+    // place the grouped dW launches, the reduce and bdr_sac_layer_probe take it from
+    int chunks_launched(int planned, int Bn) const { return std::min(planned, std::max(1, Bn / (small_gemm ? 256 : 64))); }
     // partial sums of a grouped dW launch -> gradient arena, Adam, (tracking) for `ninst` networks of one layout
     int32_t reduce_adam(const MlpLayout& net, const std::vector<size_t>& off, const std::vector<int>& chunks, int Bn, const float* part,
                         size_t inst_stride, int ninst, float* const* p, float* const* g, float* const* m, float* const* v,
@@ -614,7 +621,7 @@ struct Sac : bdr_agent, SacBatch {
         for (size_t l = 0; l < net.L.size(); ++l) {
             const DenseLayer& L = net.L[l];
             const size_t nfl = (size_t)L.Kp * L.Np + L.Np;
-            ra.seg[l] = DenseReduceSeg{part + off[l], nfl, std::min(chunks[l], std::max(1, Bn / (small_gemm ? 256 : 64))), (unsigned)(L.w / 4), (unsigned)(nfl / 4)};
+            ra.seg[l] = DenseReduceSeg{part + off[l], nfl, chunks_launched(chunks[l], Bn), (unsigned)(L.w / 4), (unsigned)(nfl / 4)};
         }
         for (int i = 0; i < ninst; ++i) { ra.p[i] = p[i]; ra.g[i] = g[i]; ra.m[i] = m[i]; ra.v[i] = v[i]; ra.tgt[i] = tgt_p ? tgt_p[i] : nullptr; ra.s[i] = sc[i]; ra.vmax[i] = vmax ? vmax[i] : nullptr; }
         ra.n4 = (unsigned)(net.total / 4); ra.track = tgt_p ? 1 : 0; ra.tau = (float)cfg.tau; ra.omt = (float)(1.0 - cfg.tau);
@@ -755,7 +762,7 @@ struct Sac : bdr_agent, SacBatch {
         }
         {   // input gradients down the trunk first, then every weight gradient of the actor in one grouped launch
             DenseDwJob jobs[RA_SEGS];
-            auto chunks_rt = [&](int c) { return std::min(c, std::max(1, Bn / (small_gemm ? 256 : 64))); };
+            auto chunks_rt = [&](int c) { return chunks_launched(c, Bn); };
             const DenseSrc hin = n_trunk ? DenseSrc{t_act[n_trunk - 1], pi.L[n_trunk - 1].Np} : DenseSrc{x_o, pi.L[0].Kp};
             if (n_trunk) {
                 float* dh = t_dy[n_trunk - 1];
@@ -776,6 +783,8 @@ struct Sac : bdr_agent, SacBatch {
             Bracket br(a, "adam_pi");
             BDR_TRY(reduce_adam(pi, pi_off, pi_chunks, Bn, pi_part, 0, 1, &pi_p, &pi_g, &pi_m, &pi_v, nullptr, &sc, AP_PI, step_pi, &pi_vmax));
         }
+
+        if (probe_copy && keep_layers) BDR_TRY(keep_snapshot(Bn));   // bdr_sac_layer_probe, phase ACTOR (update_on_batch only)
 
         // ---------------- update_critic (sac/base.rs:107-149) ----------------
         // the UPDATED actor; its first launch starts when the actor's Adam step is complete and says so (flag PI)
@@ -821,7 +830,7 @@ struct Sac : bdr_agent, SacBatch {
             for (int i = 0; i < NC; ++i)
                 for (int l = 0; l < L; ++l)
                     jobs.push_back(DenseDwJob{&qn.L[l], l == 0 ? DenseSrc{xq_c, Kq} : DenseSrc{c2_act[i][l - 1], qn.L[l - 1].Np}, c_dy[i][l],
-                                              q_part + (size_t)i * q_part_stride + q_off[l], std::min(q_chunks[l], std::max(1, Bn / (small_gemm ? 256 : 64)))});
+                                              q_part + (size_t)i * q_part_stride + q_off[l], chunks_launched(q_chunks[l], Bn)});
             { Bracket br(a, "q_dw"); BDR_TRY(small_gemm ? dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn) : dense_dw_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
             AdamScalars sc[4];
             for (int i = 0; i < NC; ++i) { step_q[i] += 1; sc[i] = opt_scalars(cfg.opt_critic, cfg.lr_critic, step_q[i]); }
@@ -829,7 +838,115 @@ struct Sac : bdr_agent, SacBatch {
             BDR_TRY(reduce_adam(qn, q_off, q_chunks, Bn, q_part, q_part_stride, NC, q_p, q_g, q_m, q_v, q_t, sc, AP_Q, step_q[0], q_vmax));
         }
         n_opts += 1;
-        last_B = Bn;
+        last_B = Bn; live_B = Bn; live_acting = false;
+        return BDR_OK;
+    }
+
+    // What the actor phase produced, of the current set -> `keep`, in order on `stream` (ordered device-to-device copies, no kernel).
+    // x_no, xq_n, xq_c, tgt (and dxq on the fused path) are not the actor phase's: not copied, and refused in phase ACTOR.
+    int32_t keep_snapshot(int Bn)
+    {
+        if (keep_cap < Bn) {
+            free_set(keep); keep_cap = 0; keep_B = 0;
+            BDR_TRY(alloc_set(keep, Bn));
+            keep_cap = Bn;
+        }
+        if (!keep_log_alpha) BDR_TRY(alloc_f(&keep_log_alpha, 4));
+        auto cp = [&](float* d, const float* s, size_t n) -> int32_t {
+            BDR_HIP(hipMemcpyAsync(d, s, n * 4, hipMemcpyDeviceToDevice, stream));
+            return BDR_OK;
+        };
+        const size_t R = (size_t)Bn, Kp = pi.L[0].Kp, Ap = pi.L[n_trunk].Np, Kq = qn.L[0].Kp;
+        BDR_TRY(cp(keep.x_o, x_o, R * Kp));
+        for (int i = 0; i < n_trunk; ++i) { BDR_TRY(cp(keep.t_act[i], t_act[i], R * pi.L[i].Np)); BDR_TRY(cp(keep.t_dy[i], t_dy[i], R * pi.L[i].Np)); }
+        float* const dst[] = {keep.mean, keep.e, keep.a_s, keep.s_s, keep.sd_s, keep.gmean, keep.ge};
+        const float* const src[] = {mean, e, a_s, s_s, sd_s, gmean, ge};
+        for (int k = 0; k < 7; ++k) BDR_TRY(cp(dst[k], src[k], R * Ap));
+        BDR_TRY(cp(keep.xq_a, xq_a, R * Kq));
+        for (int i = 0; i < NC; ++i) {
+            for (size_t l = 0; l < qn.L.size(); ++l) {
+                const size_t n = R * qn.L[l].Np;
+                BDR_TRY(cp(keep.c_act[i][l], c_act[i][l], n)); BDR_TRY(cp(keep.c2_act[i][l], c2_act[i][l], n)); BDR_TRY(cp(keep.c_dy[i][l], c_dy[i][l], n));
+            }
+            if (!fused()) BDR_TRY(cp(keep.dxq[i], dxq[i], R * Kq));   // (the fused path never forms it)
+        }
+        BDR_TRY(cp(keep.logp, logp, R));
+        BDR_TRY(cp(keep.z_a, z_a, 2 * R * A));
+        BDR_TRY(cp(keep_log_alpha, log_alpha, 1));
+        keep_B = Bn;
+        return BDR_OK;
+    }
+    // bdr_sac_layer_probe: the raw buffer, rows x padded leading dimension
+    int32_t layer_probe(int32_t phase, int32_t buf, int32_t ci, int32_t l, float* out, uint64_t n)
+    {
+        BDR_REQUIRE(phase == BDR_SAC_PHASE_ACTOR || phase == BDR_SAC_PHASE_CRITIC, "unknown SAC probe phase %d", phase);
+        const bool snap = phase == BDR_SAC_PHASE_ACTOR;
+        BDR_REQUIRE(live_B > 0, "nothing to probe yet (no update has run)");
+        BDR_REQUIRE(!snap || keep_B > 0, "no actor-phase snapshot: bdr_sac_keep_layers(1), then bdr_sac_update_on_batch");
+        if (snap) {
+            const bool critic_only = buf == BDR_SAC_BUF_X_NO || buf == BDR_SAC_BUF_XQ_N || buf == BDR_SAC_BUF_XQ_C || buf == BDR_SAC_BUF_TGT ||
+                                     (buf == BDR_SAC_BUF_DXQ && fused());
+            BDR_REQUIRE(!critic_only, "SAC probe buffer %d is not the actor phase's: read it in phase CRITIC", buf);
+        } else if (live_acting) {   // after bdr_sac_sample: only what action_logp wrote for the acting rows
+            const bool acting = buf == BDR_SAC_BUF_X_O || buf == BDR_SAC_BUF_T_ACT || buf == BDR_SAC_BUF_MEAN || buf == BDR_SAC_BUF_E || buf == BDR_SAC_BUF_A_S ||
+                                buf == BDR_SAC_BUF_S_S || buf == BDR_SAC_BUF_SD_S || buf == BDR_SAC_BUF_LOGP || buf == BDR_SAC_BUF_XQ_A;
+            BDR_REQUIRE(acting, "SAC probe buffer %d was not written by the acting call that ran last", buf);
+        }
+        const SacBatch& s = snap ? keep : static_cast<const SacBatch&>(*this);
+        const size_t R = (size_t)(snap ? keep_B : live_B), Kp = pi.L[0].Kp, Ap = pi.L[n_trunk].Np, Kq = qn.L[0].Kp;
+        const int Lq = (int)qn.L.size(), Lpi = (int)pi.L.size();
+        auto need = [&](bool ok) -> int32_t { BDR_REQUIRE(ok, "SAC probe buffer %d: critic %d / layer %d out of range", buf, ci, l); return BDR_OK; };
+        auto no_index = [&]() { return need(ci == 0 && l == 0); };
+        auto chunks_rt = [&](int c) { return chunks_launched(c, last_B); };
+        const float* src = nullptr; size_t want = 0;
+        switch (buf) {
+            case BDR_SAC_BUF_X_O: BDR_TRY(no_index()); src = s.x_o; want = R * Kp; break;
+            case BDR_SAC_BUF_X_NO: BDR_TRY(no_index()); src = s.x_no; want = R * Kp; break;
+            case BDR_SAC_BUF_XQ_A: BDR_TRY(no_index()); src = s.xq_a; want = R * Kq; break;
+            case BDR_SAC_BUF_XQ_N: BDR_TRY(no_index()); src = s.xq_n; want = R * Kq; break;
+            case BDR_SAC_BUF_XQ_C: BDR_TRY(no_index()); src = s.xq_c; want = R * Kq; break;
+            case BDR_SAC_BUF_Z: BDR_TRY(no_index()); src = s.z_a; want = 2 * R * A; break;
+            case BDR_SAC_BUF_T_ACT: BDR_TRY(need(ci == 0 && l >= 0 && l < n_trunk)); src = s.t_act[l]; want = R * pi.L[l].Np; break;
+            case BDR_SAC_BUF_T_DY: BDR_TRY(need(ci == 0 && l >= 0 && l < n_trunk)); src = s.t_dy[l]; want = R * pi.L[l].Np; break;
+            case BDR_SAC_BUF_MEAN: BDR_TRY(no_index()); src = s.mean; want = R * Ap; break;
+            case BDR_SAC_BUF_E: BDR_TRY(no_index()); src = s.e; want = R * Ap; break;
+            case BDR_SAC_BUF_A_S: BDR_TRY(no_index()); src = s.a_s; want = R * Ap; break;
+            case BDR_SAC_BUF_S_S: BDR_TRY(no_index()); src = s.s_s; want = R * Ap; break;
+            case BDR_SAC_BUF_SD_S: BDR_TRY(no_index()); src = s.sd_s; want = R * Ap; break;
+            case BDR_SAC_BUF_GMEAN: BDR_TRY(no_index()); src = s.gmean; want = R * Ap; break;
+            case BDR_SAC_BUF_GE: BDR_TRY(no_index()); src = s.ge; want = R * Ap; break;
+            case BDR_SAC_BUF_LOGP: BDR_TRY(no_index()); src = s.logp; want = R; break;
+            case BDR_SAC_BUF_TGT: BDR_TRY(no_index()); src = s.tgt; want = R; break;
+            case BDR_SAC_BUF_C_ACT: BDR_TRY(need(ci >= 0 && ci < NC && l >= 0 && l < Lq)); src = s.c_act[ci][l]; want = R * qn.L[l].Np; break;
+            case BDR_SAC_BUF_C2_ACT: BDR_TRY(need(ci >= 0 && ci < NC && l >= 0 && l < Lq)); src = s.c2_act[ci][l]; want = R * qn.L[l].Np; break;
+            case BDR_SAC_BUF_C_DY: BDR_TRY(need(ci >= 0 && ci < NC && l >= 0 && l < Lq)); src = s.c_dy[ci][l]; want = R * qn.L[l].Np; break;
+            case BDR_SAC_BUF_DXQ: BDR_TRY(need(ci >= 0 && ci < NC && l == 0)); src = s.dxq[ci]; want = R * Kq; break;
+            // what the step does not reuse between its phases: the same memory in either phase (of the last UPDATE: last_B rows)
+            case BDR_SAC_BUF_LROW: BDR_TRY(no_index()); src = lrow; want = (size_t)(3 + NC) * ((last_B + 31) / 32); break;
+            case BDR_SAC_BUF_SCAL: BDR_TRY(no_index()); src = scal; want = 4; break;
+            case BDR_SAC_BUF_LOG_ALPHA: BDR_TRY(no_index()); src = snap ? keep_log_alpha : log_alpha; want = 1; break;
+            case BDR_SAC_BUF_PI_GRAD: BDR_TRY(no_index()); src = pi_g; want = pi.total; break;
+            case BDR_SAC_BUF_Q_GRAD: BDR_TRY(need(ci >= 0 && ci < NC && l == 0)); src = q_g[ci]; want = qn.total; break;
+            case BDR_SAC_BUF_PI_PART: case BDR_SAC_BUF_PI_CHUNKS: {
+                BDR_TRY(need(ci == 0 && l >= 0 && l < Lpi));
+                const int c = chunks_rt(pi_chunks[l]);
+                if (buf == BDR_SAC_BUF_PI_CHUNKS) { BDR_REQUIRE(n == 1, "a chunk count is 1 float, not %llu", (unsigned long long)n); out[0] = (float)c; return BDR_OK; }
+                src = pi_part + pi_off[l]; want = (size_t)c * ((size_t)pi.L[l].Kp * pi.L[l].Np + pi.L[l].Np);
+                break;
+            }
+            case BDR_SAC_BUF_Q_PART: case BDR_SAC_BUF_Q_CHUNKS: {
+                BDR_TRY(need(ci >= 0 && ci < NC && l >= 0 && l < Lq));
+                const int c = chunks_rt(q_chunks[l]);
+                if (buf == BDR_SAC_BUF_Q_CHUNKS) { BDR_REQUIRE(n == 1, "a chunk count is 1 float, not %llu", (unsigned long long)n); out[0] = (float)c; return BDR_OK; }
+                src = q_part + (size_t)ci * q_part_stride + q_off[l]; want = (size_t)c * ((size_t)qn.L[l].Kp * qn.L[l].Np + qn.L[l].Np);
+                break;
+            }
+            default: return fail(BDR_ERR_INVALID, "unknown SAC probe buffer %d", buf);
+        }
+        BDR_REQUIRE(src, "SAC probe buffer %d is not allocated", buf);
+        BDR_REQUIRE(n == want, "SAC probe buffer %d holds %llu floats, not %llu", buf, (unsigned long long)want, (unsigned long long)n);
+        BDR_HIP(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, stream));
+        BDR_HIP(hipStreamSynchronize(stream));
         return BDR_OK;
     }
 
@@ -1180,6 +1297,24 @@ int32_t bdr_sac_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
     }
 }
 
+// Layer probes (see include/border_amd.h): the snapshot switch, and one raw buffer to the host
+int32_t bdr_sac_keep_layers(bdr_agent* base, int32_t on)
+{
+    BDR_REQUIRE(base, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "sac"), "not a SAC agent");
+    static_cast<Sac*>(base)->keep_layers = on != 0;
+    return BDR_OK;
+}
+
+int32_t bdr_sac_layer_probe(bdr_agent* base, int32_t phase, int32_t buf, int32_t critic, int32_t layer, float* out, uint64_t n)
+{
+    BDR_REQUIRE(base && out, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "sac"), "not a SAC agent");
+    Sac* a = static_cast<Sac*>(base);
+    BDR_HIP(hipSetDevice(a->device));
+    return a->layer_probe(phase, buf, critic, layer, out, n);
+}
+
 // Policy::sample (sac/base.rs:215-225): tanh(mean) in eval mode, tanh(sigma*z + mean) in train mode
 // (z from the device generator); out: [n][act_dim]
 int32_t bdr_sac_sample(bdr_agent* base, uint64_t n, const float* obs, float* act_out)
@@ -1197,6 +1332,7 @@ int32_t bdr_sac_sample(bdr_agent* base, uint64_t n, const float* obs, float* act
         else { hipError_t e = hipMemsetAsync(a->z_a, 0, n * a->A * 4, a->stream); if (e != hipSuccess) st = fail(BDR_ERR_HIP, "memset failed"); }
     }
     if (st == BDR_OK) st = a->action_logp(a->x_o, a->z_a, (int)n, true, a->xq_a, a->stream);
+    if (st == BDR_OK) { a->live_B = (int)n; a->live_acting = true; }   // bdr_sac_layer_probe, phase CRITIC: the acting pass's rows (bdr_sac_sample_device comes through here too)
     const int Ap = a->pi.L[a->n_trunk].Np;
     std::vector<float> tmp(n * Ap);
     if (st == BDR_OK) st = a->rows_to_host(a->a_s, tmp.data(), tmp.size());

@@ -127,6 +127,62 @@ class Sac(AgentHandle):
         _lib.check(_lib.lib().bdr_sac_probe(self._h, self.PROBES[what], _p(out), out.size))
         return out
 
+    def keep_layers(self, on: bool = True) -> None:
+        """bdr_sac_keep_layers: update_on_batch also keeps the actor phase's buffers aside (phase "actor" of `layer`).  Off by default."""
+        _lib.check(_lib.lib().bdr_sac_keep_layers(self._h, int(bool(on))))
+
+    PHASES = {"actor": 0, "critic": 1}   # BDR_SAC_PHASE_*
+    BUFS = {"x_o": 0, "x_no": 1, "xq_a": 2, "xq_n": 3, "xq_c": 4, "z": 5, "t_act": 6, "t_dy": 7, "mean": 8, "e": 9, "a_s": 10, "s_s": 11,
+            "sd_s": 12, "logp": 13, "gmean": 14, "ge": 15, "c_act": 16, "c2_act": 17, "c_dy": 18, "dxq": 19, "tgt": 20, "lrow": 21,
+            "scal": 22, "log_alpha": 23, "pi_part": 24, "q_part": 25, "pi_grad": 26, "q_grad": 27, "pi_chunks": 28, "q_chunks": 29}   # BDR_SAC_BUF_*
+
+    def layout(self, net: str):
+        """Padded layers of `pi` (trunk, then the heads ml, sl) or `q`: a list of (in, out, Kp, Np, w, b) - sizes padded to 64, W [Kp][Np]
+        at float offset w of the arena, bias [Np] at b (csrc/dense.hpp make_mlp)."""
+        c, pad = self.config, lambda x: (x + 63) // 64 * 64
+        if net == "pi":
+            dims = [(i, o) for i, o in zip((c.obs_dim,) + tuple(c.pi_units[:-1]), c.pi_units)] + [(c.pi_units[-1], c.act_dim)] * 2
+        else:
+            dims = [(i, o) for i, o in zip((c.obs_dim + c.act_dim,) + tuple(c.q_units), tuple(c.q_units) + (1,))]
+        out, o = [], 0
+        for i, n in dims:
+            kp, np_ = pad(i), pad(n)
+            out.append((i, n, kp, np_, o, o + kp * np_))
+            o += kp * np_ + np_
+        return out
+
+    def layer(self, buf: str, rows: int, phase: str = "critic", critic: int = 0, layer: int = 0) -> np.ndarray:
+        """bdr_sac_layer_probe: one raw device buffer of the last update_on_batch (phase "critic" also: of the last `sample`), padding
+        included; `rows` = the batch of that call.  Matrices come back [rows][ld]; z [2][rows][act_dim]; lrow [3 + n_critics][blocks];
+        pi_part / q_part [chunks][Kp * Np + Np]; pi_grad / q_grad the flat padded arena; pi_chunks / q_chunks an int."""
+        c = self.config
+        pi, q = self.layout("pi"), self.layout("q")
+        nt = len(c.pi_units)
+        if buf in ("pi_chunks", "q_chunks"):
+            out = np.zeros(1, np.float32)
+            _lib.check(_lib.lib().bdr_sac_layer_probe(self._h, self.PHASES[phase], self.BUFS[buf], critic, layer, _p(out), 1))
+            return int(out[0])
+        if buf in ("x_o", "x_no"): shape = (rows, pi[0][2])
+        elif buf in ("xq_a", "xq_n", "xq_c", "dxq"): shape = (rows, q[0][2])
+        elif buf == "z": shape = (2, rows, c.act_dim)
+        elif buf in ("t_act", "t_dy"): shape = (rows, pi[layer][3])
+        elif buf in ("mean", "e", "a_s", "s_s", "sd_s", "gmean", "ge"): shape = (rows, pi[nt][3])
+        elif buf in ("logp", "tgt"): shape = (rows,)
+        elif buf in ("c_act", "c2_act", "c_dy"): shape = (rows, q[layer][3])
+        elif buf == "lrow": shape = (3 + c.n_critics, (rows + 31) // 32)
+        elif buf == "scal": shape = (4,)
+        elif buf == "log_alpha": shape = (1,)
+        elif buf == "pi_grad": shape = (pi[-1][5] + pi[-1][3],)
+        elif buf == "q_grad": shape = (q[-1][5] + q[-1][3],)
+        elif buf in ("pi_part", "q_part"):
+            ly = (pi if buf == "pi_part" else q)[layer]
+            shape = (self.layer(buf.replace("part", "chunks"), rows, phase, critic, layer), ly[2] * ly[3] + ly[3])
+        else:
+            raise KeyError(buf)
+        out = np.empty(shape, np.float32)
+        _lib.check(_lib.lib().bdr_sac_layer_probe(self._h, self.PHASES[phase], self.BUFS[buf], critic, layer, _p(out), out.size))
+        return out
+
     def sample(self, obs) -> np.ndarray:
         obs = np.ascontiguousarray(obs, dtype=np.float32)
         out = np.empty((obs.shape[0], self.config.act_dim), np.float32)

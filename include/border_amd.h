@@ -906,6 +906,31 @@ BDR_API int32_t bdr_sac_update_on_batch(bdr_agent* a, uint64_t n, const float* o
  *   5 q_pi [n_critics][B]     Q_i(obs, a_pi) of update_actor (:157-158)      6 log_p [B]  log p(a_pi | obs) (:156)
  * 5 and 6 are overwritten by the critic phase and therefore kept aside by bdr_sac_update_on_batch only. */
 BDR_API int32_t bdr_sac_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* Layer probes: ONE raw device buffer of the last bdr_sac_update_on_batch (or, phase CRITIC, of the last bdr_sac_sample) to the host,
+ * rows x padded leading dimension, padding columns included (they must be exactly 0).  The step reuses its buffers, hence two phases:
+ *   BDR_SAC_PHASE_ACTOR   a snapshot taken behind the actor's Adam launch, before the updated actor's pass on next_obs.  Opt-in
+ *                         (bdr_sac_keep_layers), taken by bdr_sac_update_on_batch only: ordered device-to-device copies on the
+ *                         agent's stream, never inside opt(), a captured step or the two-queue sequence.
+ *   BDR_SAC_PHASE_CRITIC  the buffers as the step (or the acting call) left them.
+ * buf (critic i / layer l where the buffer has them, 0 otherwise), floats; B = rows, Kp / Np = sizes padded to 64:
+ *   X_O, X_NO [B][Kp_pi]; XQ_A, XQ_N, XQ_C, DXQ(i) [B][Kp_q]; Z [2][B][act_dim]; T_ACT(l), T_DY(l) [B][Np_l] (trunk layer l);
+ *   MEAN, E, A_S, S_S, SD_S, GMEAN, GE [B][Np_head]; LOGP, TGT [B]; C_ACT(i, l), C2_ACT(i, l), C_DY(i, l) [B][Np_l];
+ *   LROW [3 + n_critics][ceil(B / 32)] block partials (log_p + target, log_p, qmin, loss of critic 0..); SCAL [4]: loss_critic, loss_actor;
+ *   LOG_ALPHA [1]; PI_CHUNKS(l), Q_CHUNKS(l) [1]: the row chunks the weight-gradient launch used for layer l (actor: heads are layers
+ *   n_trunk, n_trunk + 1); PI_PART(l), Q_PART(i, l) [chunks][Kp * Np + Np] the partials; PI_GRAD, Q_GRAD(i): the whole padded gradient arena.
+ * Phase ACTOR holds what the actor phase produced: X_NO, XQ_N, XQ_C, TGT (and DXQ where the row-block kernels run, which never form
+ * it) are refused there.  After bdr_sac_sample / bdr_sac_sample_device phase CRITIC serves only what the acting pass wrote (X_O, T_ACT,
+ * MEAN, E, A_S, S_S, SD_S, LOGP, XQ_A) until the next update.
+ * BDR_ERR_INVALID for an unknown phase or buffer, an index out of range, a wrong float count, and when there is nothing to read yet. */
+enum { BDR_SAC_PHASE_ACTOR = 0, BDR_SAC_PHASE_CRITIC = 1 };
+enum { BDR_SAC_BUF_X_O = 0, BDR_SAC_BUF_X_NO = 1, BDR_SAC_BUF_XQ_A = 2, BDR_SAC_BUF_XQ_N = 3, BDR_SAC_BUF_XQ_C = 4, BDR_SAC_BUF_Z = 5,
+       BDR_SAC_BUF_T_ACT = 6, BDR_SAC_BUF_T_DY = 7, BDR_SAC_BUF_MEAN = 8, BDR_SAC_BUF_E = 9, BDR_SAC_BUF_A_S = 10, BDR_SAC_BUF_S_S = 11,
+       BDR_SAC_BUF_SD_S = 12, BDR_SAC_BUF_LOGP = 13, BDR_SAC_BUF_GMEAN = 14, BDR_SAC_BUF_GE = 15, BDR_SAC_BUF_C_ACT = 16,
+       BDR_SAC_BUF_C2_ACT = 17, BDR_SAC_BUF_C_DY = 18, BDR_SAC_BUF_DXQ = 19, BDR_SAC_BUF_TGT = 20, BDR_SAC_BUF_LROW = 21,
+       BDR_SAC_BUF_SCAL = 22, BDR_SAC_BUF_LOG_ALPHA = 23, BDR_SAC_BUF_PI_PART = 24, BDR_SAC_BUF_Q_PART = 25, BDR_SAC_BUF_PI_GRAD = 26,
+       BDR_SAC_BUF_Q_GRAD = 27, BDR_SAC_BUF_PI_CHUNKS = 28, BDR_SAC_BUF_Q_CHUNKS = 29 };
+BDR_API int32_t bdr_sac_keep_layers(bdr_agent* a, int32_t on);
+BDR_API int32_t bdr_sac_layer_probe(bdr_agent* a, int32_t phase, int32_t buf, int32_t critic, int32_t layer, float* out, uint64_t n);
 /* Policy::sample (sac/base.rs:215-225). */
 BDR_API int32_t bdr_sac_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out);
 /* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */

@@ -40,6 +40,38 @@ pub const BDR_IQN_PROBE_F_ACT: i32 = 16;
 pub const BDR_IQN_PROBE_F_DY: i32 = 32;
 pub const BDR_IQN_PROBE_PSI_ACT: i32 = 48;
 pub const BDR_IQN_PROBE_PSI_DY: i32 = 64;
+pub const BDR_SAC_PHASE_ACTOR: i32 = 0;
+pub const BDR_SAC_PHASE_CRITIC: i32 = 1;
+pub const BDR_SAC_BUF_X_O: i32 = 0;
+pub const BDR_SAC_BUF_X_NO: i32 = 1;
+pub const BDR_SAC_BUF_XQ_A: i32 = 2;
+pub const BDR_SAC_BUF_XQ_N: i32 = 3;
+pub const BDR_SAC_BUF_XQ_C: i32 = 4;
+pub const BDR_SAC_BUF_Z: i32 = 5;
+pub const BDR_SAC_BUF_T_ACT: i32 = 6;
+pub const BDR_SAC_BUF_T_DY: i32 = 7;
+pub const BDR_SAC_BUF_MEAN: i32 = 8;
+pub const BDR_SAC_BUF_E: i32 = 9;
+pub const BDR_SAC_BUF_A_S: i32 = 10;
+pub const BDR_SAC_BUF_S_S: i32 = 11;
+pub const BDR_SAC_BUF_SD_S: i32 = 12;
+pub const BDR_SAC_BUF_LOGP: i32 = 13;
+pub const BDR_SAC_BUF_GMEAN: i32 = 14;
+pub const BDR_SAC_BUF_GE: i32 = 15;
+pub const BDR_SAC_BUF_C_ACT: i32 = 16;
+pub const BDR_SAC_BUF_C2_ACT: i32 = 17;
+pub const BDR_SAC_BUF_C_DY: i32 = 18;
+pub const BDR_SAC_BUF_DXQ: i32 = 19;
+pub const BDR_SAC_BUF_TGT: i32 = 20;
+pub const BDR_SAC_BUF_LROW: i32 = 21;
+pub const BDR_SAC_BUF_SCAL: i32 = 22;
+pub const BDR_SAC_BUF_LOG_ALPHA: i32 = 23;
+pub const BDR_SAC_BUF_PI_PART: i32 = 24;
+pub const BDR_SAC_BUF_Q_PART: i32 = 25;
+pub const BDR_SAC_BUF_PI_GRAD: i32 = 26;
+pub const BDR_SAC_BUF_Q_GRAD: i32 = 27;
+pub const BDR_SAC_BUF_PI_CHUNKS: i32 = 28;
+pub const BDR_SAC_BUF_Q_CHUNKS: i32 = 29;
 pub const BDR_ARITH_BF16X3_6: i32 = 0;
 pub const BDR_ARITH_F32_EXACT: i32 = 1;
 pub const BDR_ACTIVATION_NONE: i32 = 0;
@@ -1047,6 +1079,8 @@ extern "C" {
         z_next: *const f32,
         rec3: *mut f32,
     ) -> i32;
+    pub fn bdr_sac_keep_layers(a: *mut bdr_agent, on: i32) -> i32;
+    pub fn bdr_sac_layer_probe(a: *mut bdr_agent, phase: i32, buf: i32, critic: i32, layer: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_sac_sample(a: *mut bdr_agent, n: u64, obs: *const f32, act_out: *mut f32) -> i32;
     pub fn bdr_sac_sample_device(a: *mut bdr_agent, n: u64, obs_dev: *const c_void, row_stride: u64, act_out: *mut f32) -> i32;
 
