@@ -206,6 +206,22 @@ SAMPLE_RAW_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_v
 SAVE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_char_p)
 
 
+# bdr_group_trainer_ops: the function table of bdr_trainer_train_group (one group, its members' buffers)
+G_SET_TRAIN_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32)
+G_SAMPLE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
+G_PUSH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                        C.POINTER(C.c_float), C.POINTER(C.c_int8), C.POINTER(C.c_int8))
+G_OPT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_void_p))
+G_OPT_REC_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32))
+GROUP_OBSERVER_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(C.c_float), C.c_int32)
+
+
+class GroupTrainerOps(C.Structure):
+    _fields_ = [("group", C.c_void_p), ("buffers", C.POINTER(C.c_void_p)), ("n_members", C.c_uint32), ("reserved", C.c_uint32),
+                ("set_train", G_SET_TRAIN_FN), ("sample", G_SAMPLE_FN), ("push", G_PUSH_FN), ("opt", G_OPT_FN),
+                ("opt_with_record", G_OPT_REC_FN)]
+
+
 class EvalEnvVtable(C.Structure):
     _fields_ = [("ctx", C.c_void_p), ("reset_with_index", EVAL_RESET_FN), ("step", EVAL_STEP_FN), ("obs_on_device", C.c_int32), ("device", C.c_int32)]
 
@@ -291,6 +307,7 @@ ABI_SYMBOLS = [
     "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default", "bdr_async_train",
     "bdr_agent_group_create", "bdr_agent_group_destroy", "bdr_agent_group_size", "bdr_agent_group_member", "bdr_agent_group_opt",
     "bdr_agent_group_opt_with_scalars", "bdr_agent_group_qvalues", "bdr_agent_group_sample", "bdr_agent_group_sync",
+    "bdr_agent_group_push", "bdr_group_trainer_ops_default", "bdr_trainer_train_group",
 ]
 
 _lib = None
@@ -317,7 +334,8 @@ def lib() -> C.CDLL:
                         "bdr_awac_config_default", "bdr_bc_config_default", "bdr_candle_sac_config_default", "bdr_candle_dqn_config_default",
                         "bdr_candle_dqn_cnn_config_default",
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
-                        "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default"):
+                        "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default",
+                        "bdr_group_trainer_ops_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -464,6 +482,11 @@ def lib() -> C.CDLL:
     L.bdr_agent_group_qvalues.argtypes = [vp, vp, vp]
     L.bdr_agent_group_sample.argtypes = [vp, vp, vp, vp]
     L.bdr_agent_group_sync.argtypes = [vp]
+    L.bdr_agent_group_push.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.bdr_group_trainer_ops_default.restype = None
+    L.bdr_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
+    L.bdr_trainer_train_group.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(C.c_uint64), C.POINTER(GroupTrainerOps), C.POINTER(EnvVtable),
+                                          GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     _lib = L
     return L
 

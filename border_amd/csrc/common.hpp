@@ -95,6 +95,7 @@ struct bdr_replay {
     hipStream_t read_stream = nullptr;
     uint64_t written_gen = 1;           // bumped with every record of `written`
     bool written_lazy = false;          // the newest write has not recorded `written` yet (wait_for_writer does it on the writer's stream)
+    hipStream_t writer_stream = nullptr; // the stream of that newest write: `stream`, or a group's stream after a grouped push (bdr_agent_group_push)
     std::vector<std::pair<hipStream_t, uint64_t>> waited;   // consumer stream -> generation of `written` it has waited for
     // pinned staging for push
     uint8_t* stage = nullptr;
@@ -188,6 +189,12 @@ struct GatherArgs {
 };
 int32_t replay_sample_plan(bdr_replay* r, uint64_t n, hipStream_t stream, GatherArgs* out);
 int32_t replay_ensure_batch_capacity(bdr_replay* r, uint64_t n);
+// A kernel on `stream` - not necessarily the ring's own - is about to write `n` rows at the head (a grouped push): begin orders
+// `stream` behind the last gather (WAR) and behind every earlier write (WAW) and costs nothing when both were on `stream`; end, once
+// the kernel is enqueued, makes `stream` the ring's last writer and advances head and size as one push of n rows does.  A later
+// sample on `stream` is ordered by the queue; every other stream orders itself through `written`, recorded on `stream` on demand.
+int32_t replay_begin_write_on_stream(bdr_replay* r, hipStream_t stream);
+void replay_end_write_on_stream(bdr_replay* r, hipStream_t stream, uint64_t n);
 // Consumer streams a replay buffer may have to record an event on later (lazy ordering): registered when they first sample,
 // retired by their owner after synchronising and before hipStreamDestroy, so that a buffer never touches a dead handle.
 void stream_register(hipStream_t s);

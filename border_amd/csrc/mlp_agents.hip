@@ -749,7 +749,54 @@ struct bdr_agent_group {
     float* obs_pin = nullptr; float* obs_pin_dev = nullptr;
     float* act_pin = nullptr; float* act_pin_dev = nullptr; unsigned act_seq = 0;
     std::vector<float> qrow;
+    // push (bdr_agent_group_push): PUSH_SLOTS slots of [GroupPushDesc[P] | the P packed records], pinned and mapped; k_group_push reads a
+    // slot in place.  Push launches take their numbers from `launches` like the steps do, so one sequence word serves both rings: a
+    // slot is rewritten once the launch that read it last (push_slot_launch) has published.
+    enum { PUSH_SLOTS = 8 };
+    uint8_t* push_host = nullptr; uint8_t* push_dev = nullptr; size_t push_slot_bytes = 0;
+    uint64_t push_slot_launch[PUSH_SLOTS] = {0}; uint64_t pushes = 0;
+    std::vector<bdr_replay*> last_push_buffers;                         // the buffers of the last accepted push (distinctness checked once)
 };
+
+// ---- bdr_agent_group_push: one transition per member, one launch ------------------------------------------------------------------
+// Member p's record sits in the slot exactly as bdr_replay_push lays it out for that ring (obs | next_obs | act | reward, flags at the
+// ring's own offsets), 16-byte aligned like its destination `ring + head * stride`, so source and destination of every field share
+// their alignment.  One wave per member - a CartPole record is 46 bytes in four fields, a quarter of one wave's 16-byte lanes - and
+// four members per workgroup.  Exactly the bytes a standalone push defines are written: the two rows, act_bytes, reward and two flags.
+struct GroupPushDesc { uint8_t* dst; uint32_t src_off, obs_bytes, next_off, act_off, tail_off, act_bytes; };
+static_assert(sizeof(GroupPushDesc) == 32, "GroupPushDesc is read as two 16-byte halves");
+
+// n bytes by one wave: 16-byte lanes, then 4-byte lanes over what is left, then single bytes (rows of 12 and 24 bytes take the 4-byte lanes)
+__device__ __forceinline__ void gp_copy(uint8_t* dst, const uint8_t* src, uint32_t n, int lane)
+{
+    uint32_t done = 0;
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+        const uint32_t nv = n / 16;
+        for (uint32_t i = lane; i < nv; i += 64) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+        done = nv * 16;
+    }
+    if ((((uintptr_t)src | (uintptr_t)dst) & 3) == 0) {
+        const uint32_t nw = (n - done) / 4;
+        for (uint32_t i = lane; i < nw; i += 64) reinterpret_cast<uint32_t*>(dst + done)[i] = reinterpret_cast<const uint32_t*>(src + done)[i];
+        done += nw * 4;
+    }
+    for (uint32_t i = done + lane; i < n; i += 64) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(256) void k_group_push(const uint8_t* __restrict__ slot, unsigned P, unsigned* ticket, unsigned* seq_host, unsigned seq)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned p = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p < P) {
+        const GroupPushDesc d = reinterpret_cast<const GroupPushDesc*>(slot)[p];
+        const uint8_t* rec = slot + d.src_off;
+        gp_copy(d.dst, rec, d.obs_bytes, lane);
+        gp_copy(d.dst + d.next_off, rec + d.next_off, d.obs_bytes, lane);
+        gp_copy(d.dst + d.act_off, rec + d.act_off, d.act_bytes, lane);
+        gp_copy(d.dst + d.tail_off, rec + d.tail_off, 6, lane);   // reward f32, is_terminated, is_truncated
+    }
+    mf_group_done(ticket, seq_host, seq);   // every wave's loads of the slot have returned: their data went into the stores above
+}
 
 namespace {
 
@@ -917,6 +964,82 @@ int32_t group_act(bdr_agent_group* g, const void* const* obs)
     return BDR_OK;
 }
 
+// every refusal of a grouped push, before anything moves
+int32_t group_check_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* const* obs, const void* const* next_obs)
+{
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {
+        const DqnMlp* m = g->members[p];
+        const bdr_replay* r = buffers[p];
+        BDR_REQUIRE(r, "member %u: null buffer", p);
+        BDR_REQUIRE(obs[p] && next_obs[p], "member %u: null observation row", p);
+        BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
+        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot take a grouped push (its sum tree is updated by bdr_replay_push)", p);
+        BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot take a grouped push", p);
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->net.in_dim * 4, "member %u: replay obs rows (%llu B) do not match the Mlp input (%d f32)", p,
+                    (unsigned long long)r->obs_bytes, m->net.in_dim);
+        BDR_REQUIRE(r->act_bytes == 8, "member %u: a grouped push stores one i64 action per row (act_row_bytes %llu)", p, (unsigned long long)r->act_bytes);
+    }
+    if (g->last_push_buffers.size() != P || memcmp(g->last_push_buffers.data(), buffers, P * sizeof(bdr_replay*)) != 0) {
+        std::vector<const bdr_replay*> s(buffers, buffers + P);   // waves run side by side, and every ring's head moves by one
+        std::sort(s.begin(), s.end());
+        BDR_REQUIRE(std::adjacent_find(s.begin(), s.end()) == s.end(), "two members share one replay buffer: every member needs its own");
+        g->last_push_buffers.clear();   // (set again once the push is enqueued)
+    }
+    return BDR_OK;
+}
+
+int32_t group_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* const* obs, const int64_t* act, const void* const* next_obs,
+                   const float* reward, const int8_t* term, const int8_t* trunc)
+{
+    BDR_HIP(hipSetDevice(g->device));
+    BDR_TRY(group_check_push(g, buffers, obs, next_obs));
+    const uint32_t P = (uint32_t)g->members.size();
+    // the slot: descriptors, then the records (each a multiple of 16 bytes)
+    size_t need = (size_t)P * sizeof(GroupPushDesc);
+    for (uint32_t p = 0; p < P; ++p) need += (size_t)round_up(buffers[p]->tail_off + 8, 16);
+    if (need > g->push_slot_bytes) {   // first push, or wider rings than before: rare, behind everything the stream still holds
+        BDR_HIP(hipStreamSynchronize(g->stream));
+        if (g->push_host) (void)hipHostFree(g->push_host);
+        g->push_host = nullptr; g->push_dev = nullptr; g->push_slot_bytes = 0;
+        const size_t bytes = (size_t)round_up((uint64_t)need, 256);
+        BDR_HIP(hipHostMalloc((void**)&g->push_host, bdr_agent_group::PUSH_SLOTS * bytes, hipHostMallocMapped));
+        memset(g->push_host, 0, bdr_agent_group::PUSH_SLOTS * bytes);
+        BDR_HIP(hipHostGetDevicePointer((void**)&g->push_dev, g->push_host, 0));
+        g->push_slot_bytes = bytes;
+        for (uint64_t& l : g->push_slot_launch) l = 0;
+    }
+    const int slot = (int)(g->pushes % bdr_agent_group::PUSH_SLOTS);
+    if (g->push_slot_launch[slot]) BDR_TRY(group_wait_seq(g, (unsigned)g->push_slot_launch[slot]));   // the launch that read this slot last
+    // order the group's stream behind each ring's last reader and writer: nothing to do when both were this stream
+    for (uint32_t p = 0; p < P; ++p) BDR_TRY(replay_begin_write_on_stream(buffers[p], g->stream));
+    uint8_t* base = g->push_host + (size_t)slot * g->push_slot_bytes;
+    GroupPushDesc* desc = reinterpret_cast<GroupPushDesc*>(base);
+    size_t off = (size_t)P * sizeof(GroupPushDesc);
+    for (uint32_t p = 0; p < P; ++p) {
+        const bdr_replay* r = buffers[p];
+        uint8_t* rec = base + off;
+        memcpy(rec, obs[p], r->obs_bytes);
+        memcpy(rec + r->next_off, next_obs[p], r->obs_bytes);
+        memcpy(rec + r->act_off, &act[p], 8);
+        memcpy(rec + r->tail_off, &reward[p], 4);
+        rec[r->tail_off + 4] = (uint8_t)term[p];
+        rec[r->tail_off + 5] = (uint8_t)trunc[p];
+        desc[p] = GroupPushDesc{r->ring + r->i * r->stride, (uint32_t)off, (uint32_t)r->obs_bytes, (uint32_t)r->next_off, (uint32_t)r->act_off,
+                                (uint32_t)r->tail_off, 8u};
+        off += (size_t)round_up(r->tail_off + 8, 16);
+    }
+    std::atomic_thread_fence(std::memory_order_release);
+    const uint64_t k = g->launches + 1;
+    hipLaunchKernelGGL(k_group_push, dim3((P + 3) / 4), dim3(256), 0, g->stream, (const uint8_t*)(g->push_dev + (size_t)slot * g->push_slot_bytes), P,
+                       g->ticket, g->seq_dev, (unsigned)k);
+    BDR_HIP(hipGetLastError());
+    g->launches = k; g->push_slot_launch[slot] = k; g->pushes += 1;
+    for (uint32_t p = 0; p < P; ++p) replay_end_write_on_stream(buffers[p], g->stream, 1);
+    g->last_push_buffers.assign(buffers, buffers + P);
+    return BDR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1012,6 +1135,7 @@ int32_t bdr_agent_group_destroy(bdr_agent_group* g)
     (void)hipStreamDestroy(g->stream);
     (void)hipFree(g->d_args); (void)hipFree(g->d_act); (void)hipFree(g->d_err_refs); (void)hipFree(g->ticket);
     (void)hipHostFree(g->steps_host); (void)hipHostFree(g->seq_host); (void)hipHostFree(g->obs_pin); (void)hipHostFree(g->act_pin);
+    if (g->push_host) (void)hipHostFree(g->push_host);
     delete g;
     return BDR_OK;
 }
@@ -1035,6 +1159,13 @@ int32_t bdr_agent_group_opt(bdr_agent_group* g, bdr_replay* const* buffers)
 {
     BDR_REQUIRE(g && buffers, "null argument");
     return group_opt(g, buffers);
+}
+
+int32_t bdr_agent_group_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* const* obs, const int64_t* act, const void* const* next_obs,
+                             const float* reward, const int8_t* is_terminated, const int8_t* is_truncated)
+{
+    BDR_REQUIRE(g && buffers && obs && act && next_obs && reward && is_terminated && is_truncated, "null argument");
+    return group_push(g, buffers, obs, act, next_obs, reward, is_terminated, is_truncated);
 }
 
 int32_t bdr_agent_group_opt_with_scalars(bdr_agent_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out)

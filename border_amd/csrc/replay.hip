@@ -324,6 +324,8 @@ int32_t replay_per_check(uint64_t uid, bool* alive)
 
 // `written` was just recorded on some stream: consumers have to wait for it again
 static void mark_written(bdr_replay* r) { r->written_gen += 1; }
+// a write was enqueued on `s` and left the record of `written` to the first consumer on another stream (wait_for_writer)
+static void mark_written_lazy(bdr_replay* r, hipStream_t s) { r->written_lazy = true; r->writer_stream = s; mark_written(r); }
 
 // WAR / WAW against the last gather: the stream `s` is about to overwrite ring rows or the batch buffers
 static int32_t wait_for_reader(bdr_replay* r, hipStream_t s)
@@ -342,25 +344,65 @@ static int32_t wait_for_reader(bdr_replay* r, hipStream_t s)
     return BDR_OK;
 }
 
-// RAW against pushes / fills / tree updates: once per consumer stream and generation of `written`
-static int32_t wait_for_writer(bdr_replay* r, hipStream_t s)
+// `s` is ordered behind generation written_gen: true when it already was
+static bool note_waited(bdr_replay* r, hipStream_t s)
 {
-    if (r->written_lazy) {   // a small device push left the record of `written` to its first consumer: on the writer's stream now, it covers that push
-        r->written_lazy = false;
-        BDR_HIP(hipEventRecord(r->written, r->stream));
-    }
     for (auto& w : r->waited)
         if (w.first == s) {
-            if (w.second == r->written_gen) return BDR_OK;
+            if (w.second == r->written_gen) return true;
             w.second = r->written_gen;
-            BDR_HIP(hipStreamWaitEvent(s, r->written, 0));
-            return BDR_OK;
+            return false;
         }
     if (r->waited.size() >= 16) r->waited.erase(r->waited.begin());
     r->waited.emplace_back(s, r->written_gen);
+    return false;
+}
+
+// RAW against pushes / fills / tree updates: once per consumer stream and generation of `written`.  Every writer orders itself behind
+// the writes before it (WAW), so being ordered behind the newest write is being ordered behind all of them.
+static int32_t wait_for_writer(bdr_replay* r, hipStream_t s)
+{
+    if (r->written_lazy) {   // the newest write left the record of `written` to its first consumer
+        hipStream_t w = r->writer_stream ? r->writer_stream : r->stream;
+        if (w == s && w != r->stream) { (void)note_waited(r, s); return BDR_OK; }   // a group's stream reading what it wrote: the queue orders it, no event
+        r->written_lazy = false;
+        // on the writer's stream now, the record covers that write (a retired stream was synchronised by its owner: its write is complete)
+        if (w == r->stream || stream_alive(w)) BDR_HIP(hipEventRecord(r->written, w));
+    }
+    if (note_waited(r, s)) return BDR_OK;
     BDR_HIP(hipStreamWaitEvent(s, r->written, 0));
     return BDR_OK;
 }
+
+// the ring's own stream is about to write or read ring rows: behind a grouped push on another stream (WAW / RAW)
+static int32_t order_behind_foreign_writer(bdr_replay* r)
+{
+    if (!r->written_lazy || !r->writer_stream || r->writer_stream == r->stream) return BDR_OK;
+    return wait_for_writer(r, r->stream);
+}
+
+// head of every write on the ring's own stream
+static int32_t begin_write(bdr_replay* r)
+{
+    BDR_TRY(order_behind_foreign_writer(r));
+    return wait_for_reader(r, r->stream);   // WAR: do not overwrite rows a consumer's gather may still be reading
+}
+
+namespace bdr {
+int32_t replay_begin_write_on_stream(bdr_replay* r, hipStream_t stream)
+{
+    if (stream != r->stream) stream_register(stream);
+    BDR_TRY(wait_for_writer(r, stream));
+    return wait_for_reader(r, stream);
+}
+void replay_end_write_on_stream(bdr_replay* r, hipStream_t stream, uint64_t n)
+{
+    mark_written_lazy(r, stream);
+    (void)note_waited(r, stream);
+    r->i = (r->i + n) % r->capacity;   // base.rs:308-312
+    r->size = std::min(r->size + n, r->capacity);
+}
+}  // namespace bdr
 
 // the packed record of the transition frame_share_step placed last: [u32 slot x 2k | act | reward | flags], as common.hpp describes it
 static void stage_frame_record(const bdr_replay* r, uint8_t* rec, const uint8_t* act, float reward, int8_t term, int8_t trunc)
@@ -614,7 +656,7 @@ int32_t bdr_replay_push(bdr_replay* r, uint64_t n, const void* obs, const void* 
     if (n == 0) return BDR_OK;
     BDR_REQUIRE(obs && act && next_obs && reward && term && trunc, "null transition field");
     BDR_HIP(hipSetDevice(r->device));
-    BDR_TRY(wait_for_reader(r, r->stream));  // WAR: do not overwrite rows a consumer's gather may still be reading
+    BDR_TRY(begin_write(r));   // WAR against the last gather, WAW against a grouped push
     const uint8_t* o = (const uint8_t*)obs; const uint8_t* a = (const uint8_t*)act; const uint8_t* x = (const uint8_t*)next_obs;
     if (r->frame_stack) return push_frames(r, n, o, a, x, reward, term, trunc);
     uint64_t done = 0;
@@ -642,7 +684,7 @@ int32_t bdr_replay_push(bdr_replay* r, uint64_t n, const void* obs, const void* 
         BDR_TRY(per_push(r->per, r->i, n, r->stream));
         BDR_HIP(hipEventRecord(r->written, r->stream)); mark_written(r);
     } else {
-        r->written_lazy = true; mark_written(r);   // `written` is recorded when a consumer on another stream asks for it (wait_for_writer)
+        mark_written_lazy(r, r->stream);   // `written` is recorded when a consumer on another stream asks for it (wait_for_writer)
     }
     // The caller's rows are in the pinned staging buffer: its buffers are free.  The copy to the ring is in flight on the buffer's stream;
     // whoever touches the staging buffer next waits for it first (the synchronisation at the head of every staging loop), consumers of the
@@ -746,7 +788,7 @@ int32_t bdr_replay_push_device(bdr_replay* r, uint64_t n, const void* obs_dev, u
                                  "buffer with frame_stack > 0");
     BDR_HIP(hipSetDevice(r->device));
     BDR_TRY(require_device_rows(r, obs_dev, next_obs_dev));
-    BDR_TRY(wait_for_reader(r, r->stream));  // WAR: do not overwrite rows a consumer's gather may still be reading
+    BDR_TRY(begin_write(r));   // WAR against the last gather, WAW against a grouped push
     if (n <= (uint64_t)PUSH_SMALL_N && r->act_bytes + 8 <= (uint64_t)PUSH_SMALL_TAIL && !r->per) {
         PushDevSmallArgs sa{};
         sa.a = PushDevArgs{r->ring, r->stride, r->obs_bytes, r->act_bytes, r->next_off, r->act_off, r->tail_off, r->i,
@@ -769,7 +811,7 @@ int32_t bdr_replay_push_device(bdr_replay* r, uint64_t n, const void* obs_dev, u
         sa.ticket = r->done_ticket; sa.done = r->done_dev; sa.seq = ++r->done_seq;
         hipLaunchKernelGGL(k_push_device_small, dim3((uint32_t)n), dim3(256), 0, r->stream, sa);
         BDR_HIP(hipGetLastError());
-        r->written_lazy = true; mark_written(r);   // `written` is recorded when a consumer on another stream asks for it (wait_for_writer)
+        mark_written_lazy(r, r->stream);   // `written` is recorded when a consumer on another stream asks for it (wait_for_writer)
         // the caller's device rows may be overwritten by its next environment step: wait until the kernel has read them
         {
             const volatile unsigned* done = reinterpret_cast<const volatile unsigned*>(r->done_host);
@@ -907,7 +949,7 @@ int32_t bdr_replay_push_device_frames(bdr_replay* r, uint64_t n, const void* obs
     BDR_REQUIRE(n <= 0xFFFFFFFFull, "too many transitions in one push");
     BDR_HIP(hipSetDevice(r->device));
     BDR_TRY(require_device_rows(r, obs_dev, next_obs_dev));
-    BDR_TRY(wait_for_reader(r, r->stream));  // WAR: do not overwrite frames or records a consumer's gather may still be reading
+    BDR_TRY(begin_write(r));   // WAR against the last gather, WAW against a grouped push
     const int k = r->frame_stack, Q = frame_q_count(k);
     FrameShare& f = r->fs;
     // a run of m transitions stages m * Q flags and <= 2k * m jobs in the pinned frame staging area, and m records in `stage`
@@ -1058,7 +1100,7 @@ int32_t bdr_replay_push_episode(bdr_replay* r, uint64_t T, const void* observati
         BDR_HIP(hipMalloc((void**)&r->d_ep, 2 * r->ep_half));
         for (hipEvent_t& ev : r->ep_free) BDR_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    BDR_TRY(wait_for_reader(r, r->stream));  // WAR: do not overwrite rows a consumer's gather may still be reading
+    BDR_TRY(begin_write(r));   // WAR against the last gather, WAW against a grouped push
     // a pass of m records stages round_up((m + 1) * rb, 16) + 16 bytes of rows and m * tw bytes of small fields
     const uint64_t fit = (r->ep_half - rb - 32) / (rb + tw);
     const uint8_t* o = (const uint8_t*)observations; const uint8_t* a = (const uint8_t*)act;
@@ -1095,7 +1137,7 @@ int32_t bdr_replay_push_episode(bdr_replay* r, uint64_t T, const void* observati
         BDR_TRY(per_push(r->per, r->i, T, r->stream));
         BDR_HIP(hipEventRecord(r->written, r->stream)); mark_written(r);
     } else {
-        r->written_lazy = true; mark_written(r);   // `written` is recorded when a consumer on another stream asks for it (wait_for_writer)
+        mark_written_lazy(r, r->stream);   // `written` is recorded when a consumer on another stream asks for it (wait_for_writer)
     }
     // as bdr_replay_push: the caller's arrays are in the pinned staging area, the copies and kernels are in flight on the buffer's stream
     r->i = (r->i + T) % r->capacity;
@@ -1127,6 +1169,7 @@ int32_t bdr_replay_summarize(bdr_replay* r, bdr_replay_summary* out)
     const uint64_t n = r->size;
     if (n == 0) return BDR_OK;
     BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(order_behind_foreign_writer(r));
     uint8_t* d = nullptr;
     BDR_HIP(hipMalloc((void**)&d, n * 6));
     std::vector<uint8_t> hbuf(n * 6);
@@ -1158,7 +1201,7 @@ int32_t bdr_replay_fill_synthetic(bdr_replay* r, uint64_t n, uint64_t seed, int3
     BDR_REQUIRE(n <= r->capacity, "fill count exceeds capacity");
     BDR_REQUIRE(!r->per || r->size == 0, "synthetic fill with PER needs an empty buffer");   // before anything is overwritten
     BDR_HIP(hipSetDevice(r->device));
-    BDR_TRY(wait_for_reader(r, r->stream));
+    BDR_TRY(begin_write(r));   // WAR against the last gather, WAW against a grouped push
     if (r->frame_stack) {   // one continuous episode of n transitions over n + k frames (see k_fill_frames)
         BDR_REQUIRE(kind == 0 && n_actions > 0, "the single-frame store is filled with Atari-like rows (kind 0, discrete actions)");
         BDR_REQUIRE(r->size == 0 && r->fs.frame_seq == 0, "synthetic fill of the single-frame store needs an empty buffer");
@@ -1201,6 +1244,7 @@ int32_t bdr_replay_read_rows(bdr_replay* r, uint64_t first, uint64_t n, void* ob
     BDR_REQUIRE(r, "null replay handle");
     BDR_REQUIRE(first + n <= r->capacity, "row range out of bounds");
     BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(order_behind_foreign_writer(r));
     BDR_HIP(hipStreamSynchronize(r->stream));
     std::vector<uint8_t> tmp(r->stride);
     if (r->frame_stack) {

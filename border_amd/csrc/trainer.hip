@@ -15,6 +15,7 @@
 #include <cfloat>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -165,6 +166,47 @@ int32_t step_and_records(State& s, const bdr_trainer_post* post, bdr_trainer_obs
     *stop = s.opt_steps == s.c->max_opts;   // trainer.rs:323-325
     return BDR_OK;
 }
+
+// ---- the group loop: bdr_trainer_ops over a group, so that State / train_step / cost_record serve it unchanged ---------------------
+// `agent` is this adapter: opt is one group opt, opt_with_record one group opt_with_record whose Records stay here per member
+struct GroupAdapter {
+    const bdr_group_trainer_ops* g;
+    std::vector<float> scalars;      // [n_members][128]
+    std::vector<int32_t> n_scalars;  // [n_members]
+};
+int32_t ga_set_train(void* a, int32_t on) { const auto* ga = (GroupAdapter*)a; return ga->g->set_train(ga->g->group, on); }
+int32_t ga_opt(void* a, void*) { const auto* ga = (GroupAdapter*)a; return ga->g->opt(ga->g->group, ga->g->buffers); }
+int32_t ga_opt_rec(void* a, void*, float* out, int32_t cap, int32_t* n)
+{
+    auto* ga = (GroupAdapter*)a;
+    BDR_TRY(ga->g->opt_with_record(ga->g->group, ga->g->buffers, ga->scalars.data(), 128, ga->n_scalars.data()));
+    *n = std::min(ga->n_scalars[0], cap);   // (State::scalars mirrors member 0's; the loop hands every member its own)
+    memcpy(out, ga->scalars.data(), (size_t)*n * sizeof(float));
+    return BDR_OK;
+}
+// defaults: the library's own group
+int32_t dg_set_train(void* g, int32_t on)
+{
+    uint32_t n = 0;
+    BDR_TRY(bdr_agent_group_size((bdr_agent_group*)g, &n));
+    for (uint32_t i = 0; i < n; ++i) {
+        bdr_agent* m = nullptr;
+        BDR_TRY(bdr_agent_group_member((bdr_agent_group*)g, i, &m));
+        BDR_TRY(bdr_agent_set_train(m, on));
+    }
+    return BDR_OK;
+}
+int32_t dg_sample(void* g, const void* const* obs, int64_t* act) { return bdr_agent_group_sample((bdr_agent_group*)g, obs, act, nullptr); }
+int32_t dg_push(void* g, void* const* b, const void* const* obs, const int64_t* act, const void* const* next_obs, const float* rew, const int8_t* term,
+                const int8_t* trunc)
+{
+    return bdr_agent_group_push((bdr_agent_group*)g, (bdr_replay* const*)b, obs, act, next_obs, rew, term, trunc);
+}
+int32_t dg_opt(void* g, void* const* b) { return bdr_agent_group_opt((bdr_agent_group*)g, (bdr_replay* const*)b); }
+int32_t dg_opt_rec(void* g, void* const* b, float* out, int32_t cap, int32_t* n)
+{
+    return bdr_agent_group_opt_with_scalars((bdr_agent_group*)g, (bdr_replay* const*)b, out, cap, n);
+}
 }  // namespace
 
 namespace bdr {
@@ -301,6 +343,87 @@ int32_t bdr_trainer_train_post(const bdr_trainer_config* c, const bdr_trainer_op
         if (stop) break;
     }
     fill_stats(s, out);
+    return BDR_OK;
+}
+
+void bdr_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_agent_group* group, bdr_replay* const* buffers)
+{
+    if (!ops) return;
+    memset(ops, 0, sizeof *ops);
+    ops->group = group; ops->buffers = (void* const*)buffers;
+    if (group) (void)bdr_agent_group_size(group, &ops->n_members);
+    ops->set_train = dg_set_train; ops->sample = dg_sample; ops->push = dg_push; ops->opt = dg_opt; ops->opt_with_record = dg_opt_rec;
+}
+
+int32_t bdr_trainer_train_group(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const bdr_group_trainer_ops* ops, const bdr_env_vtable* envs,
+                                void (*obs)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars,
+                                            int32_t n_scalars),
+                                void* obs_ctx, bdr_trainer_stats* out)
+{
+    BDR_REQUIRE(c && ops && envs && obs_row_bytes, "null argument");
+    BDR_REQUIRE(c->max_opts >= 1, "max_opts must be >= 1");
+    BDR_REQUIRE(c->opt_interval >= 1, "opt_interval must be >= 1");
+    BDR_REQUIRE(ops->set_train && ops->sample && ops->push && ops->opt && ops->opt_with_record, "group function table is incomplete");
+    const uint32_t P = ops->n_members;
+    BDR_REQUIRE(P >= 1 && ops->buffers, "the group function table names no members or no buffers");
+    BDR_REQUIRE(c->act_row_bytes == 8, "a group acts with one i64 action per member: act_row_bytes must be 8");
+    for (uint32_t p = 0; p < P; ++p) {
+        BDR_REQUIRE(envs[p].reset && envs[p].step_with_reset, "member %u: environment function table is incomplete", p);
+        BDR_REQUIRE(!envs[p].obs_on_device, "member %u: the group loop takes host observations (obs_on_device environments are not supported)", p);
+        BDR_REQUIRE(obs_row_bytes[p] > 0, "member %u: obs_row_bytes must be set", p);
+    }
+    GroupAdapter ga{ops, std::vector<float>((size_t)P * 128), std::vector<int32_t>(P, 0)};
+    bdr_trainer_ops t{};
+    t.agent = &ga; t.agent_set_train = ga_set_train; t.agent_opt = ga_opt; t.agent_opt_with_record = ga_opt_rec;
+    State s; s.c = c; s.ops = &t;
+    // per member: the Sampler's / SimpleStepProcessor's prev_obs, the step's obs and init_obs (bdr_trainer_train's three rows)
+    std::vector<std::vector<uint8_t>> prev(P), obs_new(P), init_obs(P);
+    std::vector<const void*> prev_p(P), new_p(P);
+    for (uint32_t p = 0; p < P; ++p) { prev[p].resize(obs_row_bytes[p]); obs_new[p].resize(obs_row_bytes[p]); init_obs[p].resize(obs_row_bytes[p]); }
+    std::vector<int64_t> act(P);
+    std::vector<float> reward(P);
+    std::vector<int8_t> term(P), trunc(P);
+    std::vector<uint64_t> n_episodes(P, 0);
+    bool have_prev = false;
+    BDR_TRY(t.agent_set_train(t.agent, 1));   // trainer.rs:283
+    for (;;) {
+        const auto t0 = Clock::now();
+        // ---- Sampler::sample_and_push (sampler.rs:99-144) of every member
+        if (!have_prev) {
+            for (uint32_t p = 0; p < P; ++p) BDR_TRY(envs[p].reset(envs[p].ctx, prev[p].data()));
+            have_prev = true;
+        }
+        for (uint32_t p = 0; p < P; ++p) { prev_p[p] = prev[p].data(); new_p[p] = obs_new[p].data(); }
+        BDR_TRY(ops->sample(ops->group, prev_p.data(), act.data()));
+        for (uint32_t p = 0; p < P; ++p) {
+            reward[p] = 0; term[p] = 0; trunc[p] = 0;
+            BDR_TRY(envs[p].step_with_reset(envs[p].ctx, &act[p], obs_new[p].data(), &reward[p], &term[p], &trunc[p], init_obs[p].data()));
+        }
+        BDR_TRY(ops->push(ops->group, ops->buffers, prev_p.data(), act.data(), new_p.data(), reward.data(), term.data(), trunc.data()));
+        for (uint32_t p = 0; p < P; ++p) {
+            const bool is_done = term[p] == 1 || trunc[p] == 1;   // step.rs:136-138
+            prev[p].swap(is_done ? init_obs[p] : obs_new[p]);     // prev_obs = init_obs / obs (sampler.rs:137-141, step_proc.rs:131-135)
+            if (is_done) n_episodes[p] += 1;
+        }
+        const double dt = std::chrono::duration<double>(Clock::now() - t0).count();
+        s.timer_for_samples += dt; s.total_sample += dt;
+        s.samples_counter += 1;
+        s.env_steps += 1;
+        // ---- train_step, once for all members; every member's event; the cost record
+        bool is_opt = false, with_record = false;
+        BDR_TRY(train_step(s, &is_opt, &with_record));
+        const int32_t event = is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP;
+        if (obs)
+            for (uint32_t p = 0; p < P; ++p) obs(obs_ctx, p, s.env_steps, s.opt_steps, event, ga.scalars.data() + (size_t)p * 128, with_record ? ga.n_scalars[p] : 0);
+        struct Fan { decltype(obs) obs; void* ctx; uint32_t P; } fan{obs, obs_ctx, P};
+        cost_record(s, obs ? +[](void* f, uint64_t es, uint64_t os, int32_t ev, const float* sc, int32_t n) {
+            const Fan* fn = (const Fan*)f;
+            for (uint32_t p = 0; p < fn->P; ++p) fn->obs(fn->ctx, p, es, os, ev, sc, n);
+        } : nullptr, &fan);
+        if (s.opt_steps == c->max_opts) break;   // trainer.rs:323-325
+    }
+    if (out)
+        for (uint32_t p = 0; p < P; ++p) { fill_stats(s, out + p); out[p].n_episodes = n_episodes[p]; }
     return BDR_OK;
 }
 

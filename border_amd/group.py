@@ -1,4 +1,5 @@
-"""DqnGroup: a set of small Mlp DQN agents whose Agent::opt runs as ONE launch, one workgroup per member (bdr_agent_group_*).
+"""DqnGroup: a set of small Mlp DQN agents whose Agent::opt runs as ONE launch, one workgroup per member (bdr_agent_group_*); so do
+acting (`sample`) and pushing one transition per member (`push`), and `train` drives the three from a compiled online loop.
 
 A launch grouping, not an agent kind: the members are ordinary `Dqn` objects (every `Dqn` method keeps working on a member and
 means what it meant) that the group owns - `DqnGroup.close()` closes them, `member.close()` on a live group is refused.  Results
@@ -16,6 +17,7 @@ from .dqn import Dqn, DqnConfig, record_keys
 
 class DqnGroup:
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/mlp_agents.hip bdr_agent_group::STEP_SLOTS)
+    PUSH_STAGING_DEPTH = 8   # slots of the push staging ring (bdr_agent_group::PUSH_SLOTS)
 
     def __init__(self, agents):
         """Adopts already built `Dqn` agents (they must be Mlp agents that take the one-workgroup step; see bdr_agent_group_create)."""
@@ -116,6 +118,32 @@ class DqnGroup:
             return act, [{"eps": i.eps, "is_random": bool(i.is_random), "n_samples_act": i.n_samples_act,
                           "n_samples_best_act": i.n_samples_best_act} for i in info]
         return act
+
+    def push(self, obs, act, next_obs, reward, is_terminated, is_truncated, buffers=None) -> None:
+        """ExperienceBufferBase::push of one transition per member into the member's own buffer, one launch; does not synchronise.
+        obs / next_obs: one row per member, or a float32 array [n, in_dim] when every member has the same in_dim; act [n] (or [n, 1])
+        int64, reward [n] float32, the flags [n] int8.  `buffers=None`: the buffers named last (as opt())."""
+        bufs = self._buffers(buffers)
+        n = len(self._members)
+        _o, optrs, _ko = self._rows(obs)
+        _x, xptrs, _kx = self._rows(next_obs)
+        act = np.ascontiguousarray(act, np.int64).reshape(-1)
+        reward = np.ascontiguousarray(reward, np.float32).reshape(-1)
+        term = np.ascontiguousarray(is_terminated, np.int8).reshape(-1)
+        trunc = np.ascontiguousarray(is_truncated, np.int8).reshape(-1)
+        for name, a in (("act", act), ("reward", reward), ("is_terminated", term), ("is_truncated", trunc)):
+            if a.size != n:
+                raise ValueError(f"{n} members need {n} values of {name}, got {a.size}")
+        _lib.check(_lib.lib().bdr_agent_group_push(self._g, bufs, optrs, act.ctypes.data_as(C.c_void_p), xptrs, reward.ctypes.data_as(C.c_void_p),
+                                                   term.ctypes.data_as(C.c_void_p), trunc.ctypes.data_as(C.c_void_p)))
+
+    def train(self, envs, buffers, trainer_config, on_event=None) -> list:
+        """The compiled online loop over the group (bdr_trainer_train_group): member i on envs[i] and buffers[i], one group sample,
+        one group push and at most one group opt per iteration.  on_event(member, env_steps, opt_steps, event, scalars); returns one
+        statistics dict per member."""
+        from .trainer import NativeTrainer
+        self._buffers(buffers)   # (opt() / push() without buffers go on with these)
+        return NativeTrainer(trainer_config).train_group(envs, self, list(buffers), on_event=on_event)
 
     def sync(self) -> None:
         _lib.check(_lib.lib().bdr_agent_group_sync(self._g))

@@ -305,6 +305,64 @@ class NativeTrainer:
             (evaluator._raise if hasattr(evaluator, "_raise") else _lib.check)(rc)
         return self._finish(st)
 
+    def train_group(self, envs, group, buffers, on_event=None):
+        """bdr_trainer_train_group: Trainer::train for the members of a `DqnGroup` in lockstep, member i on envs[i] (each as `train`'s
+        env: reset(None) -> obs[1, in_dim], step_with_reset(act[1] int64) -> Step) and buffers[i].  One group sample, one group push
+        and at most one group opt per iteration.  on_event(member, env_steps, opt_steps, event, scalars); returns (and keeps in
+        .stats) one statistics dict per member.  An exception raised by an environment ends the loop and is raised again here."""
+        n = len(envs)
+        if n != len(group) or n != len(buffers):
+            raise ValueError(f"{len(group)} members need {len(group)} environments and buffers, got {n} and {len(buffers)}")
+        rows = [4 * a.config.model_config.q_config.in_dim for a in group.members]
+        failure = []
+        keep = []
+
+        def callbacks(env, row):
+            def write(ptr, arr):
+                a = np.ascontiguousarray(arr, np.float32)
+                if a.nbytes != row:
+                    raise ValueError(f"an observation of {row} bytes, got {a.nbytes}")
+                C.memmove(ptr, a.ctypes.data, row)
+
+            def reset(_ctx, obs_out):
+                try:
+                    write(obs_out, env.reset(None))
+                    return 0
+                except Exception as e:  # noqa: BLE001  (raised again once the loop has returned)
+                    failure.append(e)
+                    return 1
+
+            def step(_ctx, act, obs_out, reward, term, trunc, init_out):
+                try:
+                    st = env.step_with_reset(np.array([C.c_int64.from_address(act).value], np.int64))
+                    write(obs_out, st.obs)
+                    reward[0], term[0], trunc[0] = float(st.reward[0]), int(st.is_terminated[0]), int(st.is_truncated[0])
+                    if st.is_done():
+                        write(init_out, st.init_obs)
+                    return 0
+                except Exception as e:  # noqa: BLE001
+                    failure.append(e)
+                    return 1
+            fns = (_lib.ENV_RESET_FN(reset), _lib.ENV_STEP_FN(step))
+            keep.append(fns)
+            return _lib.EnvVtable(None, fns[0], fns[1])
+
+        vts = (_lib.EnvVtable * n)(*[callbacks(e, r) for e, r in zip(envs, rows)])
+        ops = _lib.GroupTrainerOps()
+        handles = (C.c_void_p * n)(*[b.handle for b in buffers])
+        _lib.lib().bdr_group_trainer_ops_default(C.byref(ops), group.handle, handles)
+
+        def cb(_ctx, member, env_steps, opt_steps, event, scalars, k):
+            if on_event is not None:
+                on_event(member, env_steps, opt_steps, NativeTrainer.EVENTS[event], [scalars[i] for i in range(k)])
+        c, st, obs = self._config(0, 8), (_lib.TrainerStatsC * n)(), _lib.GROUP_OBSERVER_FN(cb)
+        rc = _lib.lib().bdr_trainer_train_group(C.byref(c), (C.c_uint64 * n)(*rows), C.byref(ops), vts, obs, None, st)
+        if failure:
+            raise failure[0]
+        _lib.check(rc)
+        self.stats = [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
+        return self.stats
+
 
 class ParamExchange:
     """Parameter averaging across one-replica-per-GPU ranks over the library's own communicator (csrc/comm.hip): ncclAllReduce on the

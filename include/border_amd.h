@@ -491,6 +491,18 @@ BDR_API int32_t bdr_agent_group_qvalues(bdr_agent_group* g, const void* const* o
 /* Policy::sample (dqn/base.rs:211-242) of every member on one observation row each: one launch, then each member's own
  * exploration stream and counters exactly as bdr_agent_sample(member i, 1, obs[i]) advances them.  act_out[n]; info[n] or NULL. */
 BDR_API int32_t bdr_agent_group_sample(bdr_agent_group* g, const void* const* obs, int64_t* act_out, bdr_sample_info* info);
+/* ExperienceBufferBase::push (generic_replay_buffer/base.rs:287-313) of ONE transition per member, member i's into buffers[i] at its
+ * head: one launch on the group's stream and no copy command, whatever n is.  obs[i] / next_obs[i] are host rows of the member's
+ * input width; act[n] (i64), reward[n] and the flags [n] are host arrays, free again when the call returns.  Each ring ends up
+ * exactly as bdr_replay_push(buffers[i], 1, ...) leaves it: the same bytes in the same row, the head advanced by one, the size
+ * saturating at capacity.  The group's own later calls (opt, a member's bdr_agent_opt) are ordered behind the push by their queue;
+ * calls on a ring's own stream (bdr_replay_push, _batch, _read_rows, _summarize) order themselves behind it through the ring's event.
+ * Refused with BDR_ERR_INVALID before anything moves - every ring's head, size and index stream stay where they were - when a buffer
+ * or a row pointer is NULL, a ring lives on another device, is prioritized (its sum tree is updated by bdr_replay_push) or a
+ * single-frame store, its row width differs from the member's in_dim, act_row_bytes != 8, or two members share one ring. */
+BDR_API int32_t bdr_agent_group_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* const* obs, const int64_t* act,
+                                     const void* const* next_obs, const float* reward, const int8_t* is_terminated,
+                                     const int8_t* is_truncated);
 /* bdr_agent_sync for the group's stream; reports every member's device-side error flags. */
 BDR_API int32_t bdr_agent_group_sync(bdr_agent_group* g);
 
@@ -603,6 +615,36 @@ BDR_API int32_t bdr_trainer_train(const bdr_trainer_config* c, const bdr_trainer
                                   bdr_trainer_observer observer, void* observer_ctx, bdr_trainer_stats* out);
 BDR_API int32_t bdr_trainer_train_offline(const bdr_trainer_config* c, const bdr_trainer_ops* ops, bdr_trainer_observer observer,
                                           void* observer_ctx, bdr_trainer_stats* out);
+
+/* Trainer::train (trainer.rs:267-327) for the n members of a group in lockstep, member i on its own environment envs[i] and its own
+ * buffer.  Per iteration: ONE group sample on the members' prev_obs rows, step_with_reset of every environment in member order, ONE
+ * group push of (prev_obs, act, obs, reward, flags), prev_obs = init_obs / obs per member, then train_step's rule once - the members
+ * share env_steps, so warm-up, opt_interval, opt vs opt_with_record and the stop at max_opts are one decision - ending in one opt /
+ * opt_with_record of the group.  Member i sees exactly the calls bdr_trainer_train makes for a lone agent on envs[i].
+ * c->obs_row_bytes is ignored: obs_row_bytes[i] is member i's row size; c->act_row_bytes must be 8 (one i64 action).  Environments
+ * with obs_on_device are refused (BDR_ERR_INVALID); the *_post entries (Evaluator, best model) have no group form.  The observer
+ * (bdr_trainer_observer with the member index after ctx; may be NULL) receives every member's event of an iteration in member order (scalars: that member's Record on OPT_RECORD); out[n] receives
+ * per-member statistics (env_steps, opt_steps and n_records are shared, n_episodes is the member's own). */
+typedef struct bdr_group_trainer_ops {
+    void* group;
+    void* const* buffers;                   /* [n_members] */
+    uint32_t n_members;
+    uint32_t reserved;
+    int32_t (*set_train)(void* group, int32_t train);                                             /* Agent::train of every member */
+    int32_t (*sample)(void* group, const void* const* obs, int64_t* act_out);                     /* Policy::sample, one row per member */
+    int32_t (*push)(void* group, void* const* buffers, const void* const* obs, const int64_t* act, const void* const* next_obs,
+                    const float* reward, const int8_t* is_terminated, const int8_t* is_truncated);
+    int32_t (*opt)(void* group, void* const* buffers);                                            /* Agent::opt of every member */
+    /* member i's Record scalars in scalars[i * cap_per_member ...], their count in n_scalars[i] */
+    int32_t (*opt_with_record)(void* group, void* const* buffers, float* scalars, int32_t cap_per_member, int32_t* n_scalars);
+} bdr_group_trainer_ops;
+/* the bdr_agent_group_* entries on a group and its members' rings (`buffers` must stay alive while `ops` is used) */
+BDR_API void bdr_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_agent_group* group, bdr_replay* const* buffers);
+BDR_API int32_t bdr_trainer_train_group(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const bdr_group_trainer_ops* ops,
+                                        const bdr_env_vtable* envs,
+                                        void (*observer)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps,
+                                                         int32_t event, const float* scalars, int32_t n_scalars),
+                                        void* observer_ctx, bdr_trainer_stats* out);
 
 /* ---- Evaluator (border-core/src/evaluator/default_evaluator.rs:64-88, border-minari/src/evaluator.rs:25-62) and
  * Trainer::post_process (trainer.rs:231-264) ---------------------------------------------------------------------------------

@@ -437,6 +437,33 @@ pub struct bdr_trainer_post {
     pub save_params: Option<unsafe extern "C" fn(agent: *mut c_void, dir: *const c_char) -> i32>,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_group_trainer_ops {
+    pub group: *mut c_void,
+    pub buffers: *mut *const c_void,
+    pub n_members: u32,
+    pub reserved: u32,
+    pub set_train: Option<unsafe extern "C" fn(group: *mut c_void, train: i32) -> i32>,
+    pub sample: Option<unsafe extern "C" fn(group: *mut c_void, obs: *mut *const c_void, act_out: *mut i64) -> i32>,
+    pub push: Option<
+        unsafe extern "C" fn(
+            group: *mut c_void,
+            buffers: *mut *const c_void,
+            obs: *mut *const c_void,
+            act: *const i64,
+            next_obs: *mut *const c_void,
+            reward: *const f32,
+            is_terminated: *const i8,
+            is_truncated: *const i8,
+        ) -> i32,
+    >,
+    pub opt: Option<unsafe extern "C" fn(group: *mut c_void, buffers: *mut *const c_void) -> i32>,
+    pub opt_with_record: Option<
+        unsafe extern "C" fn(group: *mut c_void, buffers: *mut *const c_void, scalars: *mut f32, cap_per_member: i32, n_scalars: *mut i32) -> i32,
+    >,
+}
+
 pub type bdr_trainer_observer =
     Option<unsafe extern "C" fn(ctx: *mut c_void, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32)>;
 
@@ -936,6 +963,16 @@ extern "C" {
     pub fn bdr_agent_group_qvalues(g: *mut bdr_agent_group, obs: *mut *const c_void, q_out: *mut *const f32) -> i32;
     pub fn bdr_agent_group_sample(g: *mut bdr_agent_group, obs: *mut *const c_void, act_out: *mut i64, info: *mut bdr_sample_info) -> i32;
     pub fn bdr_agent_group_sync(g: *mut bdr_agent_group) -> i32;
+    pub fn bdr_agent_group_push(
+        g: *mut bdr_agent_group,
+        buffers: *mut *const bdr_replay,
+        obs: *mut *const c_void,
+        act: *const i64,
+        next_obs: *mut *const c_void,
+        reward: *const f32,
+        is_terminated: *const i8,
+        is_truncated: *const i8,
+    ) -> i32;
     pub fn bdr_agent_param_count(a: *const bdr_agent, n: *mut u64) -> i32;
     pub fn bdr_agent_param_count_of(a: *mut bdr_agent, which: i32, n: *mut u64) -> i32;
     pub fn bdr_agent_get_params(a: *mut bdr_agent, which: i32, out: *mut f32, n: u64) -> i32;
@@ -954,6 +991,18 @@ extern "C" {
         ops: *const bdr_trainer_ops,
         env: *const bdr_env_vtable,
         observer: bdr_trainer_observer,
+        observer_ctx: *mut c_void,
+        out: *mut bdr_trainer_stats,
+    ) -> i32;
+    pub fn bdr_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_agent_group, buffers: *mut *const bdr_replay);
+    pub fn bdr_trainer_train_group(
+        c: *const bdr_trainer_config,
+        obs_row_bytes: *const u64,
+        ops: *const bdr_group_trainer_ops,
+        envs: *const bdr_env_vtable,
+        observer: Option<
+            unsafe extern "C" fn(ctx: *mut c_void, member: u32, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32),
+        >,
         observer_ctx: *mut c_void,
         out: *mut bdr_trainer_stats,
     ) -> i32;

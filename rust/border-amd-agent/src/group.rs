@@ -1,11 +1,12 @@
 //! A group of small `Mlp` DQN agents whose `Agent::opt` runs as ONE kernel launch, one workgroup per member
-//! (`bdr_agent_group_*` of `include/border_amd.h`).
+//! (`bdr_agent_group_*` of `include/border_amd.h`); acting, pushing one transition per member and the compiled online loop
+//! (`bdr_trainer_train_group`) are one launch / one loop for all members too.
 //!
 //! A launch grouping, not an agent kind: the members are ordinary [`AmdDqn`] agents - every trait method keeps working on a
 //! member ([`AmdDqnGroup::member_mut`]) and means what it meant - that enqueue on the group's stream, so member calls and group
 //! calls stay ordered and may be mixed freely.  Results are bit for bit those of stepping the same agents one after the other.
 use crate::{
-    bytes::RowBatch,
+    bytes::{DiscreteAct, ObsRows, RowBatch},
     config::DqnConfig,
     dqn::AmdDqn,
     error::{check, expect},
@@ -141,10 +142,151 @@ where
         Ok(q)
     }
 
+    /// `ExperienceBufferBase::push` of ONE transition per member, member `i`'s into `buffers[i]` at its head: one launch, no copy
+    /// command.  `obs[i]` / `next_obs[i]`: the `in_dim` floats of member `i`; `act`, `reward` and the flags: one value per member.
+    /// Each ring ends up exactly as its own `push` of that one transition leaves it.  A refused call (a prioritized ring, a
+    /// single-frame store, a row width other than the member's, two members on one ring) moves nothing.
+    pub fn push(
+        &mut self,
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        obs: &[&[f32]],
+        act: &[i64],
+        next_obs: &[&[f32]],
+        reward: &[f32],
+        is_terminated: &[i8],
+        is_truncated: &[i8],
+    ) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut o = self.row_pointers(obs)?;
+        let mut x = self.row_pointers(next_obs)?;
+        let n = self.members.len();
+        if act.len() != n || reward.len() != n || is_terminated.len() != n || is_truncated.len() != n {
+            return Err(anyhow!("{} members need {} actions, rewards and flags", n, n));
+        }
+        check(unsafe {
+            ffi::bdr_agent_group_push(
+                self.g,
+                hs.as_mut_ptr(),
+                o.as_mut_ptr(),
+                act.as_ptr(),
+                x.as_mut_ptr(),
+                reward.as_ptr(),
+                is_terminated.as_ptr(),
+                is_truncated.as_ptr(),
+            )
+        })
+    }
+
+    /// `Trainer::train` (`trainer.rs:267-327`) for all members in lockstep, member `i` on `envs[i]` and `buffers[i]`, in the
+    /// compiled loop `bdr_trainer_train_group`: one group sample, one group push and at most one group opt per iteration.
+    /// `config.obs_row_bytes` is ignored (member `i`'s row is `obs_row_bytes[i]`); `config.act_row_bytes` must be 8.
+    /// Returns one statistics block per member.
+    pub fn train(
+        &mut self,
+        envs: &mut [E],
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        obs_row_bytes: &[u64],
+        config: &ffi::bdr_trainer_config,
+    ) -> Result<Vec<ffi::bdr_trainer_stats>>
+    where
+        E::Obs: ObsRows,
+        E::Act: DiscreteAct,
+    {
+        let n = self.members.len();
+        if envs.len() != n || obs_row_bytes.len() != n {
+            return Err(anyhow!("{} members need {} environments and row sizes", n, n));
+        }
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut ctxs: Vec<GroupEnvCtx<E>> =
+            envs.iter_mut().zip(obs_row_bytes).map(|(e, &b)| GroupEnvCtx { env: e as *mut E, obs_row_bytes: b as usize }).collect();
+        let vts: Vec<ffi::bdr_env_vtable> = ctxs
+            .iter_mut()
+            .map(|c| ffi::bdr_env_vtable {
+                ctx: c as *mut GroupEnvCtx<E> as *mut c_void,
+                reset: Some(group_env_reset::<E>),
+                step_with_reset: Some(group_env_step::<E>),
+                obs_on_device: 0,
+                device: 0,
+            })
+            .collect();
+        let mut ops: ffi::bdr_group_trainer_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_group_trainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
+        let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
+        check(unsafe {
+            ffi::bdr_trainer_train_group(config, obs_row_bytes.as_ptr(), &ops, vts.as_ptr(), None, std::ptr::null_mut(), stats.as_mut_ptr())
+        })?;
+        Ok(stats)
+    }
+
     /// Blocks until the group's stream is idle; device-side errors of any member surface here.
     pub fn sync(&mut self) -> Result<()> {
         check(unsafe { ffi::bdr_agent_group_sync(self.g) })
     }
+}
+
+// ---- a member's Env behind bdr_env_vtable (the callbacks of async_trainer.rs on an environment that already exists) ------------
+struct GroupEnvCtx<E: Env> {
+    env: *mut E,
+    obs_row_bytes: usize,
+}
+
+fn write_row<Ob: ObsRows>(obs: &Ob, out: *mut c_void, row_bytes: usize) -> i32 {
+    let b = obs.as_bytes();
+    if obs.n_procs() != 1 || b.len() != row_bytes {
+        return ffi::BDR_ERR_INVALID;
+    }
+    // SAFETY: the compiled loop hands a buffer of obs_row_bytes bytes.
+    unsafe { std::ptr::copy_nonoverlapping(b.as_ptr(), out as *mut u8, row_bytes) };
+    ffi::BDR_OK
+}
+
+unsafe extern "C" fn group_env_reset<E>(ctx: *mut c_void, obs_out: *mut c_void) -> i32
+where
+    E: Env,
+    E::Obs: ObsRows,
+{
+    let ctx = &mut *(ctx as *mut GroupEnvCtx<E>);
+    let r = std::panic::catch_unwind(std::panic::AssertUnwindSafe(|| match (*ctx.env).reset(None) {
+        Ok(obs) => write_row(&obs, obs_out, ctx.obs_row_bytes),
+        Err(_) => 90,
+    }));
+    r.unwrap_or(90) // a panic must not unwind into C
+}
+
+unsafe extern "C" fn group_env_step<E>(
+    ctx: *mut c_void,
+    act: *const c_void,
+    obs_out: *mut c_void,
+    reward: *mut f32,
+    is_terminated: *mut i8,
+    is_truncated: *mut i8,
+    init_obs_out: *mut c_void,
+) -> i32
+where
+    E: Env,
+    E::Obs: ObsRows,
+    E::Act: DiscreteAct,
+{
+    let ctx = &mut *(ctx as *mut GroupEnvCtx<E>);
+    let r = std::panic::catch_unwind(std::panic::AssertUnwindSafe(|| {
+        let a = <E::Act as crate::bytes::ActFromRows<i64>>::from_rows(vec![*(act as *const i64)], 1);
+        let (step, _record) = (*ctx.env).step_with_reset(&a);
+        let rc = write_row(&step.obs, obs_out, ctx.obs_row_bytes);
+        if rc != ffi::BDR_OK {
+            return rc;
+        }
+        *reward = step.reward[0];
+        *is_terminated = step.is_terminated[0];
+        *is_truncated = step.is_truncated[0];
+        if step.is_done() {
+            match &step.init_obs {
+                Some(o) => return write_row(o, init_obs_out, ctx.obs_row_bytes),
+                None => return 91,
+            }
+        }
+        ffi::BDR_OK
+    }));
+    r.unwrap_or(91)
 }
 
 impl<E, O, A> Drop for AmdDqnGroup<E, O, A>

@@ -3,7 +3,13 @@ agents stepped in a loop by Agent::opt, and group.sample against P sample calls 
 ring pre-filled) at P in {1, 8, 64, 256}, both sides in one process.
 
 Protocol: warm-up, one window of K = 300 steps per side, then five legs of 0.3 s per side, the two sides alternating; the figure
-is the median of the legs, the spread their min / max.  Writes one JSON document (default profiles/bench_dqn_group.json)."""
+is the median of the legs, the spread their min / max.  Writes one JSON document (default profiles/bench_dqn_group.json).
+
+--online measures the online loop over a group instead (default profiles/bench_dqn_group_online.json), same protocol, host rows:
+  push   group.push (one launch for P transitions) against a loop of P rb.push of one row, member-pushes/s
+  iter   one online iteration group.sample -> group.push -> group.opt against the same iteration with the P rb.push calls in
+         the middle (what an online loop over a group had to be before group.push), member-iterations/s
+and states for every P whether the worst grouped leg beats the best leg of the loop form by more than the legs' min-max spread."""
 import argparse
 import json
 import os
@@ -64,14 +70,58 @@ def measure(a_step, a_sync, b_step, b_sync, per_step, K, n_legs, leg_s):
     return {k: (round(v, 2) if isinstance(v, float) else [round(x, 1) for x in v]) for k, v in res.items()}
 
 
+def online(args, rows):
+    doc = {"bench": "dqn_group_online", "shape": "Mlp[64,64] in 4 A 2, batch 32, ring 5000 / 10000, host rows", "window_steps": args.window,
+           "legs": args.legs, "leg_seconds": args.leg_seconds, "unit_push": "member-pushes/s (median of the legs)",
+           "unit_iter": "member-iterations/s (median of the legs); one iteration = sample, push, opt of every member",
+           "bar": "group_min - loop_max > max(group_max - group_min, loop_max - loop_min)", "push": {}, "iter": {}}
+    for P in [int(x) for x in args.sizes.split(",")]:
+        ga, gb = B.DqnGroup.build([c1(i) for i in range(P)]), B.DqnGroup.build([c1(i) for i in range(P)])
+        a_rings, b_rings = [ring(100 + i, rows) for i in range(P)], [ring(100 + i, rows) for i in range(P)]
+        pa_rings, pb_rings = [ring(300 + i, rows) for i in range(P)], [ring(300 + i, rows) for i in range(P)]   # the push-only pair
+        cols = tuple(np.ascontiguousarray(c[:P]) for c in rows)
+        obs = cols[0]
+        one = [tuple(c[i:i + 1] for c in cols) for i in range(P)]
+        ga.opt(a_rings); gb.opt(b_rings)              # names the buffers; opt() / push() then go on with them
+        gp = B.DqnGroup.build([c1(i) for i in range(P)])
+        gp.push(*cols, buffers=pa_rings)
+
+        def loop_push():
+            for r, t in zip(pb_rings, one): r.push(*t)
+
+        def loop_push_sync():
+            for r in pb_rings: r.read_rows(0, 0)      # (synchronises the ring's stream)
+
+        def iter_group():
+            ga.sample(obs); ga.push(*cols); ga.opt()
+
+        def iter_loop():
+            gb.sample(obs)
+            for r, t in zip(b_rings, one): r.push(*t)
+            gb.opt()
+
+        for key, m in (("push", measure(lambda: gp.push(*cols), gp.sync, loop_push, loop_push_sync, P, args.window, args.legs, args.leg_seconds)),
+                       ("iter", measure(iter_group, ga.sync, iter_loop, gb.sync, P, args.window, args.legs, args.leg_seconds))):
+            (g0, g1), (l0, l1) = m["group_min_max"], m["loop_min_max"]
+            m["bar_met"] = bool(g0 - l1 > max(g1 - g0, l1 - l0))
+            doc[key][str(P)] = m
+            print(P, key, m, flush=True)
+        for g in (ga, gb, gp): g.close()
+        for r in a_rings + b_rings + pa_rings + pb_rings: r.close()
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--online", action="store_true", help="measure group.push and the online iteration instead of opt / sample")
     ap.add_argument("--sizes", default="1,8,64,256")
     ap.add_argument("--window", type=int, default=300)
     ap.add_argument("--legs", type=int, default=5)
     ap.add_argument("--leg-seconds", type=float, default=0.3)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_dqn_group.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/bench_dqn_group.json, with --online profiles/bench_dqn_group_online.json")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_dqn_group_online.json" if args.online else "bench_dqn_group.json")
     rng = np.random.default_rng(0)
     n = 5000
     rows = (rng.standard_normal((n, 4)).astype(np.float32), rng.integers(0, 2, (n, 1)).astype(np.int64),
@@ -79,7 +129,9 @@ def main():
     doc = {"bench": "dqn_group", "shape": "Mlp[64,64] in 4 A 2, batch 32, ring 5000 / 10000", "window_steps": args.window, "legs": args.legs,
            "leg_seconds": args.leg_seconds, "unit_opt": "member-updates/s (median of the legs)", "unit_sample": "member-actions/s (median of the legs)",
            "opt": {}, "sample": {}}
-    for P in [int(x) for x in args.sizes.split(",")]:
+    if args.online:
+        doc = online(args, rows)
+    for P in [] if args.online else [int(x) for x in args.sizes.split(",")]:
         g = B.DqnGroup.build([c1(i) for i in range(P)])
         g_rings = [ring(100 + i, rows) for i in range(P)]
         solo = [B.Dqn.build(c1(i)) for i in range(P)]
