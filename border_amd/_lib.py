@@ -307,7 +307,7 @@ ABI_SYMBOLS = [
     "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default", "bdr_async_train",
     "bdr_agent_group_create", "bdr_agent_group_destroy", "bdr_agent_group_size", "bdr_agent_group_member", "bdr_agent_group_opt",
     "bdr_agent_group_opt_with_scalars", "bdr_agent_group_qvalues", "bdr_agent_group_sample", "bdr_agent_group_sync",
-    "bdr_agent_group_push", "bdr_group_trainer_ops_default", "bdr_trainer_train_group",
+    "bdr_agent_group_push", "bdr_group_trainer_ops_default", "bdr_trainer_train_group", "bdr_agent_group_set_prioritized",
 ]
 
 _lib = None
@@ -478,6 +478,7 @@ def lib() -> C.CDLL:
     L.bdr_agent_group_size.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.bdr_agent_group_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.bdr_agent_group_opt.argtypes = [vp, vp]
+    L.bdr_agent_group_set_prioritized.argtypes = [vp, C.c_int32]
     L.bdr_agent_group_opt_with_scalars.argtypes = [vp, vp, vp, i32, vp]
     L.bdr_agent_group_qvalues.argtypes = [vp, vp, vp]
     L.bdr_agent_group_sample.argtypes = [vp, vp, vp, vp]

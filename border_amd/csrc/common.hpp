@@ -225,4 +225,32 @@ int32_t per_check(bdr_per* p);   // non-finite priorities flagged by the update 
 // an agent enqueues after its backward pass (device arrays, the agent's stream)
 inline const float* replay_batch_weights(const bdr_replay* r) { return r->per ? per_weights(r->per) : nullptr; }
 int32_t replay_update_priority_on_stream(bdr_replay* r, uint64_t n, const float* td_dev, hipStream_t stream);
+
+// ---- per.hip: the prioritized members of an agent group (bdr_agent_group, mlp_agents.hip) -----------------------------------------
+// Every kernel below serves ALL prioritized members of a group in one launch on the group's stream.  The static descriptor of a member
+// sits in a device array (rewritten behind a synchronise when a buffer changes), the words of one step or push in a pinned slot the
+// kernels read in place.  The per_group_*_advance calls move the host state exactly as per_sample / per_update / per_push do.
+struct PerGroupMember {
+    float* tree; unsigned* mm; float* w;                    // sum tree, {min, max, NaN flag} words, weights of the batch [>= n]
+    const float* td; uint64_t* ixs;                         // |TD error| of the step [n], sampled indices [n] (the ring's b_ixs)
+    uint32_t capacity; int32_t maxdepth; float alpha, eps; int32_t normalize, n;
+    const uint8_t* ring; uint32_t stride, obs_bytes, act_bytes, next_off, act_off, tail_off;   // ring layout (obs_bytes % 4 == 0)
+    uint8_t *b_obs, *b_next, *b_act; float* b_reward; int8_t *b_term, *b_trunc;               // the ring's batch arrays [>= n rows]
+    ChaChaKey key;
+};
+struct PerGroupWords { uint32_t n_samples, need_mm, head, pad0; float beta; uint32_t pad1; uint64_t word_pos; };
+static_assert(sizeof(PerGroupWords) == 32, "PerGroupWords is laid out in pinned slots");
+// seq != 0: the launch publishes `seq` to the group's pinned sequence word once its last workgroup is through (mf_group_done's protocol)
+struct PerGroupPublish { unsigned* ticket; unsigned* seq_host; unsigned seq; };
+int32_t per_group_describe(bdr_per* p, uint64_t n, PerGroupMember* out);   // tree, mm, w (allocated for n), capacity, maxdepth, alpha, eps, normalize
+uint64_t per_capacity(const bdr_per* p);
+bool per_normalizes_all(const bdr_per* p);
+PerGroupWords per_group_sample_advance(bdr_per* p);       // n_samples, need_mm, beta; mm_valid as after per_sample
+void per_group_update_advance(bdr_per* p);                // mm_valid, n_opts as after per_update
+PerGroupWords per_group_push_advance(bdr_per* p);         // n_samples (before the push), need_mm; mm_valid, n_samples as after per_push of one row
+// post == 0: members whose words say need_mm; post == 1: members normalised over `All` (the minimum the next batch needs)
+int32_t per_group_minmax(hipStream_t st, const PerGroupMember* d, const PerGroupWords* words, uint32_t n, uint64_t max_capacity, int post, PerGroupPublish pub);
+int32_t per_group_sample(hipStream_t st, const PerGroupMember* d, const PerGroupWords* words, uint32_t n);
+int32_t per_group_update(hipStream_t st, const PerGroupMember* d, uint32_t n, PerGroupPublish pub);
+int32_t per_group_push(hipStream_t st, const PerGroupMember* d, const PerGroupWords* words, uint32_t n, PerGroupPublish pub);
 }  // namespace bdr

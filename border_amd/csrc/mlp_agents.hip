@@ -734,7 +734,8 @@ struct bdr_agent_group {
     std::vector<DqnMlp*> members;
     uint64_t n_updates = 1;
     // opt
-    struct StaticKey { bool valid = false; uint64_t batch_gen = 0; const void* td_abs = nullptr; uint64_t r_uid = 0, r_batch_gen = 0; };
+    struct StaticKey { bool valid = false; uint64_t batch_gen = 0; const void* td_abs = nullptr; uint64_t r_uid = 0, r_batch_gen = 0;
+                       const void* weight = nullptr; int per_j = -1; };   // (prioritized ring: its weight array, its place in d_per)
     std::vector<StaticKey> keys;
     std::vector<MlpFusedArgs> h_args; MlpFusedArgs* d_args = nullptr;
     std::vector<size_t> lds_bytes; size_t lds_attr = 0;
@@ -756,6 +757,16 @@ struct bdr_agent_group {
     uint8_t* push_host = nullptr; uint8_t* push_dev = nullptr; size_t push_slot_bytes = 0;
     uint64_t push_slot_launch[PUSH_SLOTS] = {0}; uint64_t pushes = 0;
     std::vector<bdr_replay*> last_push_buffers;                         // the buffers of the last accepted push (distinctness checked once)
+    // prioritized rings (bdr_agent_group_set_prioritized; per.hip k_per_*_group).  Member p on a prioritized ring is entry keys[p].per_j
+    // of d_per (static descriptors, rewritten with d_args) and of a slot of per_words (STEP_SLOTS slots of P entries, pinned): a round
+    // takes slot per_rounds % STEP_SLOTS and its LAST tree kernel publishes a launch number of its own (per_slot_launch), so the slot
+    // is rewritten only once every kernel that read it is through.  A push carries its words in the push slot, behind the records.
+    bool prioritized = false;
+    std::vector<PerGroupMember> h_per; PerGroupMember* d_per = nullptr;
+    PerGroupWords* per_words_host = nullptr; PerGroupWords* per_words_dev = nullptr;
+    uint64_t per_slot_launch[STEP_SLOTS] = {0}; uint64_t per_rounds = 0;
+    std::vector<PerGroupMember> h_per_push; PerGroupMember* d_per_push = nullptr;
+    std::vector<uint64_t> per_push_uids;                                // uid of every prioritized ring of the last push, in member order
 };
 
 // ---- bdr_agent_group_push: one transition per member, one launch ------------------------------------------------------------------
@@ -813,6 +824,16 @@ int32_t group_wait_seq(bdr_agent_group* g, unsigned seq)
     return BDR_OK;
 }
 
+// a member's deferred report (its error words, its ring's NaN flag) under the member's number; the deferred mark stays
+int32_t group_name_member(int32_t st, uint32_t p)
+{
+    const int deferred = bdr::g_err_deferred;
+    const std::string msg = bdr::g_err;
+    (void)fail(st, "member %u: %s", p, msg.c_str());
+    bdr::g_err_deferred = deferred;
+    return st;
+}
+
 // why `a` cannot be a member (nullptr: it can)
 const char* group_ineligible(const bdr_agent* a, const DqnMlp** out)
 {
@@ -842,7 +863,7 @@ int32_t group_check_buffers(bdr_agent_group* g, bdr_replay* const* buffers)
                     (unsigned long long)r->obs_bytes, m->net.in_dim);
         BDR_REQUIRE(r->act_bytes >= 8, "member %u: discrete actions are stored as i64", p);
         BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
-        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot be stepped by a group (the in-step sample covers the uniform ring)", p);
+        BDR_REQUIRE(!r->per || g->prioritized, "member %u: a prioritized buffer cannot be stepped by a group (the in-step sample covers the uniform ring)", p);
         BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by a group", p);
         BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: the in-step sample draws the StdRng index stream only", p);
         if (r->size == 0) return fail(BDR_ERR_EMPTY, "member %u: batch() on an empty replay buffer", p);
@@ -865,7 +886,18 @@ int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_ro
     const int slot = (int)(k % bdr_agent_group::STEP_SLOTS);
     if (k > bdr_agent_group::STEP_SLOTS) BDR_TRY(group_wait_seq(g, (unsigned)(k - bdr_agent_group::STEP_SLOTS)));   // the launch that read this slot last
     MfStep* steps = g->steps_host + (size_t)slot * P;
-    bool dirty = false;
+    // prioritized rings (accepted by group_check_buffers only when the group is switched on): their words go into a slot of their own
+    uint32_t n_per = 0;
+    for (uint32_t p = 0; p < P; ++p) n_per += buffers[p]->per ? 1u : 0u;
+    const int per_slot = (int)(g->per_rounds % bdr_agent_group::STEP_SLOTS);
+    PerGroupWords* per_words = nullptr;
+    if (n_per) {
+        if (g->per_slot_launch[per_slot]) BDR_TRY(group_wait_seq(g, (unsigned)g->per_slot_launch[per_slot]));   // the last kernel that read this slot
+        per_words = g->per_words_host + (size_t)per_slot * P;
+    }
+    bool dirty = false, per_need_mm = false, per_any_all = false;
+    uint64_t per_max_capacity = 0;
+    uint32_t j = 0;
     for (uint32_t p = 0; p < P; ++p) {
         DqnMlp* m = g->members[p];
         bdr_replay* r = buffers[p];
@@ -873,21 +905,59 @@ int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_ro
         BDR_TRY(m->ensure_batch(bs));
         BDR_TRY(m->td_buffer(bs));
         GatherArgs plan{};
-        BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));
+        PerGroupMember pm{};
+        if (r->per) {   // the head of replay_sample_on_stream; the sample itself is k_per_sample_group's
+            BDR_TRY(replay_prepare_sample(r, bs, g->stream));
+            BDR_TRY(per_group_describe(r->per, bs, &pm));
+        } else {
+            BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));
+        }
         m->last_reward = r->b_reward; m->last_B = bs;
         m->defer_adam = false;
         m->track_with_next = last_round && m->soft_update_counter + 1 == m->cfg.soft_update_interval;
         bdr_agent_group::StaticKey& key = g->keys[p];
-        if (!key.valid || key.batch_gen != m->batch_gen || key.td_abs != m->td_abs || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
-            g->lds_bytes[p] = m->fused_static(g->h_args[p], bs, r->b_obs, r->b_next, r->b_act, (int)r->act_bytes, r->b_reward, r->b_term, nullptr, &plan);
+        const int per_j = r->per ? (int)j : -1;
+        if (!key.valid || key.batch_gen != m->batch_gen || key.td_abs != m->td_abs || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen ||
+            key.weight != (const void*)pm.w || key.per_j != per_j) {
+            // a prioritized member takes the step as update_critic_fused gives it standalone: no in-step sample, weight and td_abs set
+            g->lds_bytes[p] = m->fused_static(g->h_args[p], bs, r->b_obs, r->b_next, r->b_act, (int)r->act_bytes, r->b_reward, r->b_term, pm.w,
+                                              r->per ? nullptr : &plan);
+            if (r->per) {
+                pm.td = m->td_abs; pm.ixs = r->b_ixs;
+                pm.ring = r->ring; pm.stride = (uint32_t)r->stride; pm.obs_bytes = (uint32_t)r->obs_bytes; pm.act_bytes = (uint32_t)r->act_bytes;
+                pm.next_off = (uint32_t)r->next_off; pm.act_off = (uint32_t)r->act_off; pm.tail_off = (uint32_t)r->tail_off;
+                pm.b_obs = r->b_obs; pm.b_next = r->b_next; pm.b_act = r->b_act; pm.b_reward = r->b_reward; pm.b_term = r->b_term; pm.b_trunc = r->b_trunc;
+                memcpy(pm.key.k, r->key, sizeof pm.key.k);
+                g->h_per[j] = pm;
+            }
             key.valid = true; key.batch_gen = m->batch_gen; key.td_abs = m->td_abs; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
+            key.weight = pm.w; key.per_j = per_j;
             dirty = true;
         }
-        steps[p] = m->fused_step_advance(&plan);
+        if (r->per) {   // what replay_sample_on_stream advances, with per_sample's state
+            PerGroupWords w = per_group_sample_advance(r->per);
+            w.word_pos = r->word_pos;
+            r->word_pos += (uint64_t)bs;   // one next_u32() per index
+            r->read_pending = true; r->read_stream = g->stream;
+            r->batch_n = (uint64_t)bs;
+            per_words[j] = w;
+            per_need_mm = per_need_mm || w.need_mm != 0;
+            per_any_all = per_any_all || per_normalizes_all(r->per);
+            per_max_capacity = std::max(per_max_capacity, per_capacity(r->per));
+            ++j;
+        }
+        steps[p] = m->fused_step_advance(r->per ? nullptr : &plan);
     }
     if (dirty) {   // rare (first step, a reallocation, another ring): behind everything the stream still holds
         BDR_HIP(hipStreamSynchronize(g->stream));
         BDR_HIP(hipMemcpy(g->d_args, g->h_args.data(), P * sizeof(MlpFusedArgs), hipMemcpyHostToDevice));
+        if (n_per) BDR_HIP(hipMemcpy(g->d_per, g->h_per.data(), n_per * sizeof(PerGroupMember), hipMemcpyHostToDevice));
+    }
+    const PerGroupWords* per_words_dev = g->per_words_dev + (size_t)per_slot * P;
+    if (n_per) {   // every prioritized member's sample, weights and rows: one launch (two when a minimum has to be recomputed first)
+        std::atomic_thread_fence(std::memory_order_release);
+        if (per_need_mm) BDR_TRY(per_group_minmax(g->stream, g->d_per, per_words_dev, n_per, per_max_capacity, 0, PerGroupPublish{nullptr, nullptr, 0u}));
+        BDR_TRY(per_group_sample(g->stream, g->d_per, per_words_dev, n_per));
     }
     // the LDS form only when every member has a plan: otherwise all take the global-memory form (same bits)
     size_t lds = 0;
@@ -906,6 +976,17 @@ int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_ro
     }
     g->launches = k;
     BDR_HIP(hipGetLastError());
+    if (n_per) {   // update_priority of every prioritized member (and the minimum the next `All` batch needs): the last of them publishes
+        const PerGroupPublish pub{g->ticket, g->seq_dev, (unsigned)(k + 1)}, none{nullptr, nullptr, 0u};
+        BDR_TRY(per_group_update(g->stream, g->d_per, n_per, per_any_all ? none : pub));
+        if (per_any_all) BDR_TRY(per_group_minmax(g->stream, g->d_per, per_words_dev, n_per, per_max_capacity, 1, pub));
+        g->launches = k + 1; g->per_slot_launch[per_slot] = k + 1; g->per_rounds += 1;
+        for (uint32_t p = 0; p < P; ++p) {
+            if (!buffers[p]->per) continue;
+            per_group_update_advance(buffers[p]->per);
+            replay_end_write_on_stream(buffers[p], g->stream, 0);   // a tree update is a write of the ring: the group's stream is its last writer
+        }
+    }
     return BDR_OK;
 }
 
@@ -974,7 +1055,7 @@ int32_t group_check_push(bdr_agent_group* g, bdr_replay* const* buffers, const v
         BDR_REQUIRE(r, "member %u: null buffer", p);
         BDR_REQUIRE(obs[p] && next_obs[p], "member %u: null observation row", p);
         BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
-        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot take a grouped push (its sum tree is updated by bdr_replay_push)", p);
+        BDR_REQUIRE(!r->per || g->prioritized, "member %u: a prioritized buffer cannot take a grouped push (its sum tree is updated by bdr_replay_push)", p);
         BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot take a grouped push", p);
         BDR_REQUIRE(r->obs_bytes == (uint64_t)m->net.in_dim * 4, "member %u: replay obs rows (%llu B) do not match the Mlp input (%d f32)", p,
                     (unsigned long long)r->obs_bytes, m->net.in_dim);
@@ -998,6 +1079,10 @@ int32_t group_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* c
     // the slot: descriptors, then the records (each a multiple of 16 bytes)
     size_t need = (size_t)P * sizeof(GroupPushDesc);
     for (uint32_t p = 0; p < P; ++p) need += (size_t)round_up(buffers[p]->tail_off + 8, 16);
+    uint32_t n_per = 0;   // prioritized rings: their words follow the records
+    for (uint32_t p = 0; p < P; ++p) n_per += buffers[p]->per ? 1u : 0u;
+    const size_t words_off = need;
+    need += (size_t)n_per * sizeof(PerGroupWords);
     if (need > g->push_slot_bytes) {   // first push, or wider rings than before: rare, behind everything the stream still holds
         BDR_HIP(hipStreamSynchronize(g->stream));
         if (g->push_host) (void)hipHostFree(g->push_host);
@@ -1029,12 +1114,49 @@ int32_t group_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* c
                                 (uint32_t)r->tail_off, 8u};
         off += (size_t)round_up(r->tail_off + 8, 16);
     }
+    bool per_need_mm = false;
+    uint64_t per_max_capacity = 0;
+    if (n_per) {   // set_priority(1) of every prioritized ring (base.rs:227-235): the tree descriptors, then this push's words
+        bool same = g->per_push_uids.size() == n_per;
+        uint32_t j = 0;
+        for (uint32_t p = 0; p < P && same; ++p) if (buffers[p]->per) same = g->per_push_uids[j++] == buffers[p]->uid;
+        if (!same) {   // rare (first push, other rings): behind everything the stream still holds
+            g->per_push_uids.clear();
+            j = 0;
+            for (uint32_t p = 0; p < P; ++p) {
+                if (!buffers[p]->per) continue;
+                PerGroupMember pm{};
+                BDR_TRY(per_group_describe(buffers[p]->per, 1, &pm));
+                g->h_per_push[j++] = pm;
+            }
+            BDR_HIP(hipStreamSynchronize(g->stream));
+            BDR_HIP(hipMemcpy(g->d_per_push, g->h_per_push.data(), n_per * sizeof(PerGroupMember), hipMemcpyHostToDevice));
+            for (uint32_t p = 0; p < P; ++p) if (buffers[p]->per) g->per_push_uids.push_back(buffers[p]->uid);
+        }
+        PerGroupWords* words = reinterpret_cast<PerGroupWords*>(base + words_off);
+        j = 0;
+        for (uint32_t p = 0; p < P; ++p) {
+            bdr_replay* r = buffers[p];
+            if (!r->per) continue;
+            PerGroupWords w = per_group_push_advance(r->per);
+            w.head = (uint32_t)r->i;
+            words[j++] = w;
+            per_need_mm = per_need_mm || w.need_mm != 0;
+            per_max_capacity = std::max(per_max_capacity, per_capacity(r->per));
+        }
+    }
     std::atomic_thread_fence(std::memory_order_release);
     const uint64_t k = g->launches + 1;
     hipLaunchKernelGGL(k_group_push, dim3((P + 3) / 4), dim3(256), 0, g->stream, (const uint8_t*)(g->push_dev + (size_t)slot * g->push_slot_bytes), P,
                        g->ticket, g->seq_dev, (unsigned)k);
     BDR_HIP(hipGetLastError());
     g->launches = k; g->push_slot_launch[slot] = k; g->pushes += 1;
+    if (n_per) {   // the tree kernels read the slot too: the last of them publishes, under a launch number of its own
+        const PerGroupWords* words_dev = reinterpret_cast<const PerGroupWords*>(g->push_dev + (size_t)slot * g->push_slot_bytes + words_off);
+        if (per_need_mm) BDR_TRY(per_group_minmax(g->stream, g->d_per_push, words_dev, n_per, per_max_capacity, 0, PerGroupPublish{nullptr, nullptr, 0u}));
+        BDR_TRY(per_group_push(g->stream, g->d_per_push, words_dev, n_per, PerGroupPublish{g->ticket, g->seq_dev, (unsigned)(k + 1)}));
+        g->launches = k + 1; g->push_slot_launch[slot] = k + 1;
+    }
     for (uint32_t p = 0; p < P; ++p) replay_end_write_on_stream(buffers[p], g->stream, 1);
     g->last_push_buffers.assign(buffers, buffers + P);
     return BDR_OK;
@@ -1136,6 +1258,8 @@ int32_t bdr_agent_group_destroy(bdr_agent_group* g)
     (void)hipFree(g->d_args); (void)hipFree(g->d_act); (void)hipFree(g->d_err_refs); (void)hipFree(g->ticket);
     (void)hipHostFree(g->steps_host); (void)hipHostFree(g->seq_host); (void)hipHostFree(g->obs_pin); (void)hipHostFree(g->act_pin);
     if (g->push_host) (void)hipHostFree(g->push_host);
+    (void)hipFree(g->d_per); (void)hipFree(g->d_per_push);
+    if (g->per_words_host) (void)hipHostFree(g->per_words_host);
     delete g;
     return BDR_OK;
 }
@@ -1152,6 +1276,32 @@ int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr_agent**
     BDR_REQUIRE(g && out, "null argument");
     BDR_REQUIRE(i < g->members.size(), "member %u of a group of %u", i, (unsigned)g->members.size());
     *out = g->members[i];
+    return BDR_OK;
+}
+
+int32_t bdr_agent_group_set_prioritized(bdr_agent_group* g, int32_t on)
+{
+    BDR_REQUIRE(g, "null group");
+    BDR_REQUIRE(on == 0 || on == 1, "on must be 0 or 1 (got %d)", on);
+    if (on && !g->d_per) {   // the arrays of the tree kernels, once
+        BDR_HIP(hipSetDevice(g->device));
+        const size_t P = g->members.size();
+        PerGroupMember *d = nullptr, *dp = nullptr;
+        PerGroupWords* wh = nullptr;
+        hipError_t e = hipMalloc((void**)&d, P * sizeof(PerGroupMember));
+        if (e == hipSuccess) e = hipMalloc((void**)&dp, P * sizeof(PerGroupMember));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&wh, bdr_agent_group::STEP_SLOTS * P * sizeof(PerGroupWords), hipHostMallocMapped);
+        PerGroupWords* wd = nullptr;
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&wd, wh, 0);
+        if (e != hipSuccess) {
+            (void)hipFree(d); (void)hipFree(dp); if (wh) (void)hipHostFree(wh);
+            return fail(BDR_ERR_HIP, "allocating the group's prioritized-replay arrays failed: %s", hipGetErrorString(e));
+        }
+        memset(wh, 0, bdr_agent_group::STEP_SLOTS * P * sizeof(PerGroupWords));
+        g->d_per = d; g->d_per_push = dp; g->per_words_host = wh; g->per_words_dev = wd;
+        g->h_per.resize(P); g->h_per_push.resize(P);
+    }
+    g->prioritized = on != 0;
     return BDR_OK;
 }
 
@@ -1214,7 +1364,7 @@ int32_t bdr_agent_group_sample(bdr_agent_group* g, const void* const* obs, int64
         bool alive = false;
         const int32_t st = replay_per_check(m->last_replay_uid, &alive);
         if (!alive) m->last_replay_uid = 0;
-        BDR_TRY(st);
+        if (st != BDR_OK) return g->prioritized ? group_name_member(st, p) : st;
     }
     for (uint32_t p = 0; p < P; ++p) {
         DqnMlp* m = g->members[p];
@@ -1228,7 +1378,12 @@ int32_t bdr_agent_group_sync(bdr_agent_group* g)
     BDR_REQUIRE(g, "null group");
     BDR_HIP(hipSetDevice(g->device));
     BDR_HIP(hipStreamSynchronize(g->stream));
-    for (DqnMlp* m : g->members) { BDR_TRY(m->after_sync()); BDR_TRY(m->err_check()); }
+    for (size_t p = 0; p < g->members.size(); ++p) {
+        DqnMlp* m = g->members[p];
+        BDR_TRY(m->after_sync());
+        const int32_t st = m->err_check();
+        if (st != BDR_OK) return g->prioritized ? group_name_member(st, (uint32_t)p) : st;
+    }
     return BDR_OK;
 }
 

@@ -1508,6 +1508,7 @@ int32_t bdr_replay_update_priority(bdr_replay* r, uint64_t n, const uint64_t* ix
     BDR_REQUIRE(ixs && td_errs, "ixs and td_errs must be given when PER is enabled");   // the reference's expect()s
     BDR_REQUIRE(n > 0 && n <= (1ull << 20), "update size out of range");
     BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(order_behind_foreign_writer(r));   // (a group's tree update on its own stream)
     for (uint64_t k = 0; k < n; ++k) BDR_REQUIRE(ixs[k] < r->capacity, "index %llu out of range", (unsigned long long)ixs[k]);
     uint64_t* d_ix = nullptr; float* d_td = nullptr;
     BDR_HIP(hipMalloc((void**)&d_ix, n * 8));
@@ -1528,6 +1529,7 @@ int32_t bdr_replay_batch_weights(bdr_replay* r, uint64_t n, float* w_out)
     BDR_REQUIRE(r->per, "PER is not enabled on this buffer (weight: None)");
     BDR_REQUIRE(r->batch_n > 0 && n <= r->batch_n, "no batch of that size has been drawn");
     BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(order_behind_foreign_writer(r));
     BDR_HIP(hipMemcpyAsync(w_out, per_weights(r->per), n * 4, hipMemcpyDeviceToHost, r->stream));
     BDR_HIP(hipStreamSynchronize(r->stream));
     return BDR_OK;
@@ -1538,6 +1540,7 @@ int32_t bdr_replay_per_info(bdr_replay* r, bdr_per_info* out)
     BDR_REQUIRE(r && out, "null argument");
     BDR_REQUIRE(r->per, "PER is not enabled on this buffer");
     BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(order_behind_foreign_writer(r));
     per_info(r->per, out);
     float total = 0.f, mm[2];
     BDR_TRY(per_read(r->per, 0, &total, 1, r->stream));
@@ -1551,6 +1554,7 @@ int32_t bdr_replay_per_read(bdr_replay* r, int32_t what, float* out, uint64_t n)
     BDR_REQUIRE(r && out, "null argument");
     BDR_REQUIRE(r->per, "PER is not enabled on this buffer");
     BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(order_behind_foreign_writer(r));
     return per_read(r->per, what, out, n, r->stream);
 }
 
@@ -1559,6 +1563,7 @@ int32_t bdr_replay_per_get(bdr_replay* r, float s, uint64_t* ix)
     BDR_REQUIRE(r && ix, "null argument");
     BDR_REQUIRE(r->per, "PER is not enabled on this buffer");
     BDR_HIP(hipSetDevice(r->device));
+    BDR_TRY(order_behind_foreign_writer(r));
     return per_get(r->per, s, ix, r->stream);
 }
 

@@ -19,8 +19,10 @@ class DqnGroup:
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/mlp_agents.hip bdr_agent_group::STEP_SLOTS)
     PUSH_STAGING_DEPTH = 8   # slots of the push staging ring (bdr_agent_group::PUSH_SLOTS)
 
-    def __init__(self, agents):
-        """Adopts already built `Dqn` agents (they must be Mlp agents that take the one-workgroup step; see bdr_agent_group_create)."""
+    def __init__(self, agents, prioritized: bool = False):
+        """Adopts already built `Dqn` agents (they must be Mlp agents that take the one-workgroup step; see bdr_agent_group_create).
+        `prioritized=True`: opt / opt_with_record / push / train also accept buffers built with a `PerConfig`
+        (bdr_agent_group_set_prioritized); by default a prioritized buffer is refused."""
         agents = list(agents)
         hs = (C.c_void_p * len(agents))(*[a.handle for a in agents])
         g = C.c_void_p()
@@ -31,15 +33,25 @@ class DqnGroup:
         self._bound = None   # the handle array of the buffers passed last (opt() without an argument steps on them again)
         dims = {a.config.model_config.q_config.in_dim for a in agents}
         self._in_dim = dims.pop() if len(dims) == 1 else None   # one input width for all: sample / qvalues also take a [n, in_dim] array
+        self._prioritized = False
+        if prioritized:
+            try:
+                self.set_prioritized(True)
+            except Exception:
+                _lib.lib().bdr_agent_group_destroy(g)   # (destroys the adopted members)
+                self._g = None
+                for a in agents:
+                    a._h = None
+                raise
 
     @classmethod
-    def build(cls, configs) -> "DqnGroup":
+    def build(cls, configs, prioritized: bool = False) -> "DqnGroup":
         """One `Dqn` per DqnConfig, grouped.  Nothing is left behind when a config is refused."""
         agents = []
         try:
             for c in configs:
                 agents.append(Dqn.build(c))
-            return cls(agents)
+            return cls(agents, prioritized=prioritized)
         except Exception:
             for a in agents:
                 a.close()
@@ -51,6 +63,16 @@ class DqnGroup:
 
     def __len__(self):
         return len(self._members)
+
+    @property
+    def prioritized(self) -> bool:
+        return self._prioritized
+
+    def set_prioritized(self, on: bool) -> None:
+        """Switches prioritized replay under the group on or off (bdr_agent_group_set_prioritized): on, the prioritized members' tree
+        sampling, weights and priority updates run as a fixed number of launches per round, bit for bit what their own calls give."""
+        _lib.check(_lib.lib().bdr_agent_group_set_prioritized(self._g, 1 if on else 0))
+        self._prioritized = bool(on)
 
     @property
     def handle(self):

@@ -476,10 +476,21 @@ BDR_API int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr
 BDR_API int32_t bdr_agent_group_destroy(bdr_agent_group* g);
 BDR_API int32_t bdr_agent_group_size(const bdr_agent_group* g, uint32_t* n);
 BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr_agent** out);
+/* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
+ * switched on steps and feeds rings with bdr_replay_enable_per: every prioritized member's SumTree::sample, importance weights and
+ * row gather are one launch for all of them ahead of the step, update_priority one launch behind it, and set_priority of a grouped
+ * push one launch behind the push - a fixed number of launches per round and per push whatever n is, no copy command, no
+ * synchronisation.  Members may be mixed; a uniform member keeps the in-step sample.  Every ring ends up bit for bit as the
+ * standalone calls leave it: rows, head, size, index stream, weights, the whole f32 sum tree, n_samples, n_opts, beta.  A NaN TD
+ * error does what it does standalone (the update is dropped) and is reported, naming the member, as a deferred BDR_ERR_INVALID by
+ * bdr_agent_group_sync / _sample.  A group switched on that is given uniform rings only enqueues exactly what the default one does. */
+BDR_API int32_t bdr_agent_group_set_prioritized(bdr_agent_group* g, int32_t on);
 /* Agent::opt of every member, member i on buffers[i] (n distinct buffers): n_updates_per_opt launches in all, asynchronous.
  * Every buffer must be what the one-launch step samples itself - a uniform (non-prioritized) ring with the StdRng index stream,
- * no single-frame store, f32 rows of the member's input width, on the group's device, not empty.  All buffers are checked BEFORE
- * anything advances or is enqueued: a refused call leaves every member and every ring exactly where it was. */
+ * no single-frame store, f32 rows of the member's input width, on the group's device, not empty - or, once
+ * bdr_agent_group_set_prioritized(g, 1) was called, a prioritized ring of that shape (at most four more launches per update round,
+ * see there).  All buffers are checked BEFORE anything advances or is enqueued: a refused call leaves every member and every ring
+ * exactly where it was. */
 BDR_API int32_t bdr_agent_group_opt(bdr_agent_group* g, bdr_replay* const* buffers);
 /* Agent::opt_with_record (dqn/base.rs:311-343) of every member: the same step, ONE synchronisation, then member i's Record scalars
  * (bdr_agent_opt_with_scalars' order) in out[i * cap_per_member ...] and their count in n_out[i]. */
@@ -498,7 +509,9 @@ BDR_API int32_t bdr_agent_group_sample(bdr_agent_group* g, const void* const* ob
  * saturating at capacity.  The group's own later calls (opt, a member's bdr_agent_opt) are ordered behind the push by their queue;
  * calls on a ring's own stream (bdr_replay_push, _batch, _read_rows, _summarize) order themselves behind it through the ring's event.
  * Refused with BDR_ERR_INVALID before anything moves - every ring's head, size and index stream stay where they were - when a buffer
- * or a row pointer is NULL, a ring lives on another device, is prioritized (its sum tree is updated by bdr_replay_push) or a
+ * or a row pointer is NULL, a ring lives on another device, is prioritized (its sum tree is updated by bdr_replay_push) and the
+ * group was not switched on by bdr_agent_group_set_prioritized (switched on: set_priority(1) of every prioritized ring - the
+ * current maximum priority at the head row - rides behind the push, one or two launches for all of them), is a
  * single-frame store, its row width differs from the member's in_dim, act_row_bytes != 8, or two members share one ring. */
 BDR_API int32_t bdr_agent_group_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* const* obs, const int64_t* act,
                                      const void* const* next_obs, const float* reward, const int8_t* is_terminated,

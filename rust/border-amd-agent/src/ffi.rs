@@ -958,6 +958,7 @@ extern "C" {
     pub fn bdr_agent_group_destroy(g: *mut bdr_agent_group) -> i32;
     pub fn bdr_agent_group_size(g: *const bdr_agent_group, n: *mut u32) -> i32;
     pub fn bdr_agent_group_member(g: *const bdr_agent_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_agent_group_set_prioritized(g: *mut bdr_agent_group, on: i32) -> i32;
     pub fn bdr_agent_group_opt(g: *mut bdr_agent_group, buffers: *mut *const bdr_replay) -> i32;
     pub fn bdr_agent_group_opt_with_scalars(g: *mut bdr_agent_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
     pub fn bdr_agent_group_qvalues(g: *mut bdr_agent_group, obs: *mut *const c_void, q_out: *mut *const f32) -> i32;

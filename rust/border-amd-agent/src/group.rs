@@ -80,6 +80,14 @@ where
         &mut self.members[i]
     }
 
+    /// Prioritized replay under the group (`bdr_agent_group_set_prioritized`): switched on, `opt`, `opt_with_record`, `push` and
+    /// `train` accept buffers built with a `PerConfig` - sampling, importance weights and `update_priority` of all prioritized
+    /// members run as a fixed number of launches per round, bit for bit what the members' own calls give.  Off (the default), a
+    /// prioritized buffer is refused.
+    pub fn set_prioritized(&mut self, on: bool) -> Result<()> {
+        check(unsafe { ffi::bdr_agent_group_set_prioritized(self.g, on as i32) })
+    }
+
     fn buffer_handles(&self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<*const ffi::bdr_replay>> {
         if buffers.len() != self.members.len() {
             return Err(anyhow!("{} members need {} buffers, got {}", self.members.len(), self.members.len(), buffers.len()));

@@ -9,7 +9,13 @@ is the median of the legs, the spread their min / max.  Writes one JSON document
   push   group.push (one launch for P transitions) against a loop of P rb.push of one row, member-pushes/s
   iter   one online iteration group.sample -> group.push -> group.opt against the same iteration with the P rb.push calls in
          the middle (what an online loop over a group had to be before group.push), member-iterations/s
-and states for every P whether the worst grouped leg beats the best leg of the loop form by more than the legs' min-max spread."""
+and states for every P whether the worst grouped leg beats the best leg of the loop form by more than the legs' min-max spread.
+
+--per measures prioritized replay under a group (default profiles/bench_dqn_group_per.json): rings of 10 000 with PerConfig() defaults,
+same protocol and bar:
+  opt    group.opt of a group switched on (DqnGroup(prioritized=True)) against a loop of Agent::opt on the same kind of rings,
+         member-updates/s
+  iter   group.sample -> group.push -> group.opt against the same iteration with P rb.push calls in the middle, member-iterations/s"""
 import argparse
 import json
 import os
@@ -23,9 +29,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import border_amd as B  # noqa: E402
 
 
-def c1(seed):
+def c1(seed, gamma=0.99):
     return B.DqnConfig(model_config=B.DqnModelConfig(q_config=B.MlpConfig(in_dim=4, units=(64, 64), out_dim=2), opt_config=B.OptimizerConfig.Adam(1e-3)),
-                       soft_update_interval=1, batch_size=32, tau=0.01, critic_loss="Mse", device=0, param_seed=seed, train=True)
+                       soft_update_interval=1, batch_size=32, tau=0.01, critic_loss="Mse", discount_factor=gamma, device=0, param_seed=seed, train=True)
 
 
 def ring(seed, rows):
@@ -111,17 +117,77 @@ def online(args, rows):
     return doc
 
 
+def per_ring(seed, rows):
+    rb = B.SimpleReplayBuffer(B.SimpleReplayBufferConfig(capacity=10000, seed=seed, per_config=B.PerConfig()), (4,), np.float32)
+    # FULL rings: a uniform of exactly 0 (word 840 702 of seed 100's stream, update 26 271) descends to the leftmost leaf; in a part-filled
+    # ring that leaf was never set, its weight is infinite - in the reference too - and the run ends in NaN priorities
+    rb.push(*rows); rb.push(*rows)
+    return rb
+
+
+def prioritized(args, rows):
+    doc = {"bench": "dqn_group_per", "shape": "Mlp[64,64] in 4 A 2, batch 32, prioritized rings 10000 / 10000 (PerConfig defaults: alpha 0.6, All), gamma 0, host rows",
+           "window_steps": args.window, "legs": args.legs, "leg_seconds": args.leg_seconds, "unit_opt": "member-updates/s (median of the legs)",
+           "unit_iter": "member-iterations/s (median of the legs); one iteration = sample, push, opt of every member",
+           "bar": "group_min - loop_max > max(group_max - group_min, loop_max - loop_min); P = 1 is reported without a bar",
+           "launches_per_round": "4 in the steady loop (k_per_sample_group, the step, k_per_update_group, k_per_minmax_group), 5 behind a push "
+                                 "(k_per_minmax_group first); enqueued by group_round whatever P is",
+           "launches_per_push": "3 (k_group_push, k_per_minmax_group, k_per_push_group), 2 when no ring needs its maximum recomputed; whatever P is",
+           "opt": {}, "iter": {}}
+    # gamma = 0: tens of thousands of bootstrapped updates on random rows can diverge, and a prioritized ring - unlike a uniform one -
+    # reports the NaN priority that follows; the work per update is the same
+    for P in [int(x) for x in args.sizes.split(",")]:
+        g = B.DqnGroup.build([c1(i, 0.0) for i in range(P)], prioritized=True)
+        g_rings = [per_ring(100 + i, rows) for i in range(P)]
+        solo = [B.Dqn.build(c1(i, 0.0)) for i in range(P)]
+        s_rings = [per_ring(100 + i, rows) for i in range(P)]
+        ga, gb = B.DqnGroup.build([c1(i, 0.0) for i in range(P)], prioritized=True), B.DqnGroup.build([c1(i, 0.0) for i in range(P)], prioritized=True)
+        a_rings, b_rings = [per_ring(300 + i, rows) for i in range(P)], [per_ring(300 + i, rows) for i in range(P)]
+        cols = tuple(np.ascontiguousarray(c[:P]) for c in rows)
+        obs = cols[0]
+        one = [tuple(c[i:i + 1] for c in cols) for i in range(P)]
+        g.opt(g_rings); ga.opt(a_rings); gb.opt(b_rings)   # names the buffers; opt() / push() then go on with them
+
+        def loop_opt():
+            for a, r in zip(solo, s_rings): a.opt(r)
+
+        def loop_sync():
+            for a in solo: a.sync()
+
+        def iter_group():
+            ga.sample(obs); ga.push(*cols); ga.opt()
+
+        def iter_loop():
+            gb.sample(obs)
+            for r, t in zip(b_rings, one): r.push(*t)
+            gb.opt()
+
+        for key, m in (("opt", measure(g.opt, g.sync, loop_opt, loop_sync, P, args.window, args.legs, args.leg_seconds)),
+                       ("iter", measure(iter_group, ga.sync, iter_loop, gb.sync, P, args.window, args.legs, args.leg_seconds))):
+            (g0, g1), (l0, l1) = m["group_min_max"], m["loop_min_max"]
+            m["bar_met"] = bool(g0 - l1 > max(g1 - g0, l1 - l0)) if P > 1 else None
+            doc[key][str(P)] = m
+            print(P, key, m, flush=True)
+        for x in (g, ga, gb): x.close()
+        for a in solo: a.close()
+        for r in g_rings + s_rings + a_rings + b_rings: r.close()
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--per", action="store_true", help="measure prioritized rings under a group: opt and the online iteration")
     ap.add_argument("--online", action="store_true", help="measure group.push and the online iteration instead of opt / sample")
     ap.add_argument("--sizes", default="1,8,64,256")
     ap.add_argument("--window", type=int, default=300)
     ap.add_argument("--legs", type=int, default=5)
     ap.add_argument("--leg-seconds", type=float, default=0.3)
-    ap.add_argument("--out", default=None, help="default: profiles/bench_dqn_group.json, with --online profiles/bench_dqn_group_online.json")
+    ap.add_argument("--out", default=None, help="default: profiles/bench_dqn_group.json, with --online profiles/bench_dqn_group_online.json, "
+                                                "with --per profiles/bench_dqn_group_per.json")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_dqn_group_online.json" if args.online else "bench_dqn_group.json")
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                "bench_dqn_group_per.json" if args.per else "bench_dqn_group_online.json" if args.online else "bench_dqn_group.json")
     rng = np.random.default_rng(0)
     n = 5000
     rows = (rng.standard_normal((n, 4)).astype(np.float32), rng.integers(0, 2, (n, 1)).astype(np.int64),
@@ -129,9 +195,11 @@ def main():
     doc = {"bench": "dqn_group", "shape": "Mlp[64,64] in 4 A 2, batch 32, ring 5000 / 10000", "window_steps": args.window, "legs": args.legs,
            "leg_seconds": args.leg_seconds, "unit_opt": "member-updates/s (median of the legs)", "unit_sample": "member-actions/s (median of the legs)",
            "opt": {}, "sample": {}}
-    if args.online:
+    if args.per:
+        doc = prioritized(args, rows)
+    elif args.online:
         doc = online(args, rows)
-    for P in [] if args.online else [int(x) for x in args.sizes.split(",")]:
+    for P in [] if args.online or args.per else [int(x) for x in args.sizes.split(",")]:
         g = B.DqnGroup.build([c1(i) for i in range(P)])
         g_rings = [ring(100 + i, rows) for i in range(P)]
         solo = [B.Dqn.build(c1(i)) for i in range(P)]
