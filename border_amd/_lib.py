@@ -241,6 +241,20 @@ class TrainerPostC(C.Structure):
                 ("save_params", SAVE_FN)]
 
 
+# bdr_group_eval_ops / bdr_group_trainer_post: the lockstep evaluator of a group and Trainer::post_process in the group loop
+G_SAMPLE_MEMBERS_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
+G_SAVE_MEMBER_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_uint32, C.c_char_p)
+
+
+class GroupEvalOps(C.Structure):
+    _fields_ = [("group", C.c_void_p), ("n_members", C.c_uint32), ("reserved", C.c_uint32), ("sample_members", G_SAMPLE_MEMBERS_FN)]
+
+
+class GroupTrainerPostC(C.Structure):
+    _fields_ = [("eval_interval", C.c_uint64), ("save_interval", C.c_uint64), ("evaluators", C.POINTER(EvaluatorC)),
+                ("model_dirs", C.POINTER(C.c_char_p)), ("eval_ops", GroupEvalOps), ("save_member", G_SAVE_MEMBER_FN)]
+
+
 BDR_ACT_PATH_DEFAULT, BDR_ACT_PATH_LAYERS, BDR_ACT_PATH_FUSED = 0, 1, 2
 BDR_TRAINER_EVENT_EVAL = 4
 
@@ -308,6 +322,8 @@ ABI_SYMBOLS = [
     "bdr_agent_group_create", "bdr_agent_group_destroy", "bdr_agent_group_size", "bdr_agent_group_member", "bdr_agent_group_opt",
     "bdr_agent_group_opt_with_scalars", "bdr_agent_group_qvalues", "bdr_agent_group_sample", "bdr_agent_group_sync",
     "bdr_agent_group_push", "bdr_group_trainer_ops_default", "bdr_trainer_train_group", "bdr_agent_group_set_prioritized",
+    "bdr_agent_group_sample_members", "bdr_group_eval_ops_default", "bdr_evaluate_group", "bdr_group_trainer_post_default",
+    "bdr_trainer_train_group_post",
 ]
 
 _lib = None
@@ -335,7 +351,7 @@ def lib() -> C.CDLL:
                         "bdr_candle_dqn_cnn_config_default",
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
                         "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default",
-                        "bdr_group_trainer_ops_default"):
+                        "bdr_group_trainer_ops_default", "bdr_group_eval_ops_default", "bdr_group_trainer_post_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -488,6 +504,14 @@ def lib() -> C.CDLL:
     L.bdr_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
     L.bdr_trainer_train_group.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(C.c_uint64), C.POINTER(GroupTrainerOps), C.POINTER(EnvVtable),
                                           GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
+    L.bdr_agent_group_sample_members.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
+    L.bdr_group_eval_ops_default.restype = None
+    L.bdr_group_eval_ops_default.argtypes = [C.POINTER(GroupEvalOps), vp]
+    L.bdr_evaluate_group.argtypes = [C.POINTER(EvaluatorC), C.POINTER(GroupEvalOps), C.POINTER(EvalResultC)]
+    L.bdr_group_trainer_post_default.restype = None
+    L.bdr_group_trainer_post_default.argtypes = [C.POINTER(GroupTrainerPostC), vp]
+    L.bdr_trainer_train_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(C.c_uint64), C.POINTER(GroupTrainerOps), C.POINTER(EnvVtable),
+                                               C.POINTER(GroupTrainerPostC), GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     _lib = L
     return L
 

@@ -749,6 +749,10 @@ struct bdr_agent_group {
     MfActArgs* d_act = nullptr; std::vector<unsigned> obs_off; unsigned obs_floats = 0;
     float* obs_pin = nullptr; float* obs_pin_dev = nullptr;
     float* act_pin = nullptr; float* act_pin_dev = nullptr; unsigned act_seq = 0;
+    // acting for a subset (k_dqn_mlp_act_group_sel): the selected member indices, pinned and mapped, read in place by the launch.  ONE
+    // buffer, no staging ring: group_act returns only after every launched member's sequence word has arrived, so no launch is in
+    // flight when the host writes the next selection.
+    unsigned* sel_pin = nullptr; unsigned* sel_pin_dev = nullptr;
     std::vector<float> qrow;
     // push (bdr_agent_group_push): PUSH_SLOTS slots of [GroupPushDesc[P] | the P packed records], pinned and mapped; k_group_push reads a
     // slot in place.  Push launches take their numbers from `launches` like the steps do, so one sequence word serves both rings: a
@@ -1013,21 +1017,38 @@ int32_t group_opt(bdr_agent_group* g, bdr_replay* const* buffers)
     return BDR_OK;
 }
 
-// one observation row per member -> the members' action values in the pinned result area (and each member's view of its error words)
-int32_t group_act(bdr_agent_group* g, const void* const* obs)
+// one observation row per selected member -> those members' action values in the pinned result area (and each one's view of its error
+// words).  members == nullptr: all of them, through the full entry; otherwise members[0..n) (checked by the caller: strictly
+// ascending, every index < P, rows not NULL) - a full list takes the full entry too, so the default path enqueues what it always did.
+int32_t group_act(bdr_agent_group* g, const void* const* obs, const uint32_t* members = nullptr, uint32_t n = 0)
 {
     BDR_HIP(hipSetDevice(g->device));
     const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {
+    if (members && n == P) members = nullptr;   // strictly ascending and n == P: every member
+    const uint32_t N = members ? n : P;
+    auto member = [&](uint32_t b) { return members ? members[b] : b; };
+    for (uint32_t b = 0; b < N; ++b) {
+        const uint32_t p = member(b);
+        BDR_REQUIRE(p < P, "member %u of a group of %u", p, P);   // (the kernel indexes the members' arrays with it)
         BDR_REQUIRE(obs[p], "member %u: null observation row", p);
+    }
+    for (uint32_t b = 0; b < N; ++b) {
+        const uint32_t p = member(b);
         memcpy(g->obs_pin + g->obs_off[p], obs[p], (size_t)g->members[p]->net.in_dim * 4);
+        if (members) g->sel_pin[b] = p;
     }
     const unsigned seq = ++g->act_seq;
-    hipLaunchKernelGGL(k_dqn_mlp_act_group, dim3(P), dim3(512), 0, g->stream, (const MF_CONST_AS MfActArgs*)g->d_act, (const float*)g->obs_pin_dev, g->act_pin_dev, seq);
+    if (members) {
+        std::atomic_thread_fence(std::memory_order_release);
+        hipLaunchKernelGGL(k_dqn_mlp_act_group_sel, dim3(N), dim3(512), 0, g->stream, (const MF_CONST_AS MfActArgs*)g->d_act,
+                           (const MF_CONST_AS unsigned*)g->sel_pin_dev, (const float*)g->obs_pin_dev, g->act_pin_dev, seq);
+    } else {
+        hipLaunchKernelGGL(k_dqn_mlp_act_group, dim3(P), dim3(512), 0, g->stream, (const MF_CONST_AS MfActArgs*)g->d_act, (const float*)g->obs_pin_dev, g->act_pin_dev, seq);
+    }
     BDR_HIP(hipGetLastError());
     const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t p = 0; p < P; ++p) {
-        const volatile unsigned* done = reinterpret_cast<const volatile unsigned*>(g->act_pin + (size_t)p * MF_ACT_SLOT);
+    for (uint32_t b = 0; b < N; ++b) {
+        const volatile unsigned* done = reinterpret_cast<const volatile unsigned*>(g->act_pin + (size_t)member(b) * MF_ACT_SLOT);
         for (unsigned spins = 0; (int)(*done - seq) < 0; ++spins) {
             if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
                 BDR_HIP(hipStreamSynchronize(g->stream));
@@ -1037,10 +1058,33 @@ int32_t group_act(bdr_agent_group* g, const void* const* obs)
         }
     }
     std::atomic_thread_fence(std::memory_order_acquire);
-    for (uint32_t p = 0; p < P; ++p) {
-        DqnMlp* m = g->members[p];
-        const unsigned* words = reinterpret_cast<const unsigned*>(g->act_pin + (size_t)p * MF_ACT_SLOT);
+    for (uint32_t b = 0; b < N; ++b) {
+        DqnMlp* m = g->members[member(b)];
+        const unsigned* words = reinterpret_cast<const unsigned*>(g->act_pin + (size_t)member(b) * MF_ACT_SLOT);
         for (int i = 0; i < bdr_agent::ERR_WORDS; ++i) reinterpret_cast<volatile unsigned*>(m->host_err)[i] = words[4 + i];
+    }
+    return BDR_OK;
+}
+
+// the per-member tail of Policy::sample behind group_act, for the members members[0..n) (nullptr: all), in member order
+int32_t group_sample_tail(bdr_agent_group* g, const uint32_t* members, uint32_t n, int64_t* act_out, bdr_sample_info* info)
+{
+    const uint32_t N = members ? n : (uint32_t)g->members.size();
+    for (uint32_t b = 0; b < N; ++b) {   // the forward brought each member's error words along: report from them, as bdr_agent_sample does
+        const uint32_t p = members ? members[b] : b;
+        DqnMlp* m = g->members[p];
+        unsigned w[bdr_agent::ERR_WORDS];
+        for (int i = 0; i < bdr_agent::ERR_WORDS; ++i) w[i] = reinterpret_cast<volatile unsigned*>(m->host_err)[i];
+        BDR_TRY(m->err_report(w));
+        bool alive = false;
+        const int32_t st = replay_per_check(m->last_replay_uid, &alive);
+        if (!alive) m->last_replay_uid = 0;
+        if (st != BDR_OK) return g->prioritized ? group_name_member(st, p) : st;
+    }
+    for (uint32_t b = 0; b < N; ++b) {
+        const uint32_t p = members ? members[b] : b;
+        DqnMlp* m = g->members[p];
+        BDR_TRY(bdr::explore_actions(m, 1, g->act_pin + (size_t)p * MF_ACT_SLOT + 16, m->net.out_dim, act_out + p, info ? info + p : nullptr));
     }
     return BDR_OK;
 }
@@ -1207,7 +1251,7 @@ int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr_agent_g
     struct Guard { bdr_agent_group* g; bool armed = true; ~Guard() { if (armed) {
         (void)hipFree(g->d_args); (void)hipFree(g->d_act); (void)hipFree(g->d_err_refs); (void)hipFree(g->ticket);
         if (g->steps_host) (void)hipHostFree(g->steps_host); if (g->seq_host) (void)hipHostFree(g->seq_host);
-        if (g->obs_pin) (void)hipHostFree(g->obs_pin); if (g->act_pin) (void)hipHostFree(g->act_pin);
+        if (g->obs_pin) (void)hipHostFree(g->obs_pin); if (g->act_pin) (void)hipHostFree(g->act_pin); if (g->sel_pin) (void)hipHostFree(g->sel_pin);
         if (g->stream) (void)hipStreamDestroy(g->stream); } } } guard{g.get()};
     BDR_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     BDR_HIP(hipMalloc((void**)&g->d_args, P * sizeof(MlpFusedArgs)));
@@ -1229,6 +1273,9 @@ int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr_agent_g
     BDR_HIP(hipHostMalloc((void**)&g->act_pin, P * MF_ACT_SLOT * sizeof(float), hipHostMallocMapped));
     memset(g->act_pin, 0, P * MF_ACT_SLOT * sizeof(float));
     BDR_HIP(hipHostGetDevicePointer((void**)&g->act_pin_dev, g->act_pin, 0));
+    BDR_HIP(hipHostMalloc((void**)&g->sel_pin, P * sizeof(unsigned), hipHostMallocMapped));
+    memset(g->sel_pin, 0, P * sizeof(unsigned));
+    BDR_HIP(hipHostGetDevicePointer((void**)&g->sel_pin_dev, g->sel_pin, 0));
     g->keys.resize(P); g->h_args.resize(P); g->lds_bytes.assign(P, 0);
     // adopt: the member's own stream is drained, retired and destroyed; the member enqueues on the group's stream from now on
     for (size_t p = 0; p < P; ++p) BDR_HIP(hipStreamSynchronize(ms[p]->stream));
@@ -1257,6 +1304,7 @@ int32_t bdr_agent_group_destroy(bdr_agent_group* g)
     (void)hipStreamDestroy(g->stream);
     (void)hipFree(g->d_args); (void)hipFree(g->d_act); (void)hipFree(g->d_err_refs); (void)hipFree(g->ticket);
     (void)hipHostFree(g->steps_host); (void)hipHostFree(g->seq_host); (void)hipHostFree(g->obs_pin); (void)hipHostFree(g->act_pin);
+    (void)hipHostFree(g->sel_pin);
     if (g->push_host) (void)hipHostFree(g->push_host);
     (void)hipFree(g->d_per); (void)hipFree(g->d_per_push);
     if (g->per_words_host) (void)hipHostFree(g->per_words_host);
@@ -1355,22 +1403,22 @@ int32_t bdr_agent_group_sample(bdr_agent_group* g, const void* const* obs, int64
 {
     BDR_REQUIRE(g && obs && act_out, "null argument");
     BDR_TRY(group_act(g, obs));
+    return group_sample_tail(g, nullptr, 0, act_out, info);
+}
+
+int32_t bdr_agent_group_sample_members(bdr_agent_group* g, const uint32_t* members, uint32_t n, const void* const* obs, int64_t* act_out,
+                                       bdr_sample_info* info)
+{
+    BDR_REQUIRE(g && members && obs && act_out, "null argument");
     const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {   // the forward brought each member's error words along: report from them, as bdr_agent_sample does
-        DqnMlp* m = g->members[p];
-        unsigned w[bdr_agent::ERR_WORDS];
-        for (int i = 0; i < bdr_agent::ERR_WORDS; ++i) w[i] = reinterpret_cast<volatile unsigned*>(m->host_err)[i];
-        BDR_TRY(m->err_report(w));
-        bool alive = false;
-        const int32_t st = replay_per_check(m->last_replay_uid, &alive);
-        if (!alive) m->last_replay_uid = 0;
-        if (st != BDR_OK) return g->prioritized ? group_name_member(st, p) : st;
+    BDR_REQUIRE(n >= 1, "an empty member list");
+    for (uint32_t b = 0; b < n; ++b) {   // everything is refused before anything moves
+        BDR_REQUIRE(members[b] < P, "member %u of a group of %u", members[b], P);
+        BDR_REQUIRE(b == 0 || members[b] > members[b - 1], "the member list must be strictly ascending (%u follows %u)", members[b], members[b - 1]);
+        BDR_REQUIRE(obs[members[b]], "member %u: null observation row", members[b]);
     }
-    for (uint32_t p = 0; p < P; ++p) {
-        DqnMlp* m = g->members[p];
-        BDR_TRY(bdr::explore_actions(m, 1, g->act_pin + (size_t)p * MF_ACT_SLOT + 16, m->net.out_dim, act_out + p, info ? info + p : nullptr));
-    }
-    return BDR_OK;
+    BDR_TRY(group_act(g, obs, members, n));
+    return group_sample_tail(g, members, n, act_out, info);
 }
 
 int32_t bdr_agent_group_sync(bdr_agent_group* g)

@@ -815,10 +815,10 @@ struct MfActArgs {
     unsigned obs_off;          // the member's row in the pinned observation area, in floats
 };
 constexpr int MF_ACT_SLOT = 128;   // floats per member of the result area: [0] sequence word, [4, 8) error words, [16, 16 + A) values
-__global__ __launch_bounds__(512) void k_dqn_mlp_act_group(const MF_CONST_AS MfActArgs* args, const float* obs_host, float* out_host, unsigned seq)
+// one body, two entries: `a` is the member's arguments (read in place), `slot` its slot of the result area
+__device__ __forceinline__ void mf_act_body(const MF_CONST_AS MfActArgs& a, const float* obs_host, float* slot, unsigned seq)
 {
     __shared__ __attribute__((aligned(16))) float xs[2][256 + 4];   // (fused_ok: no layer wider than 256)
-    const MF_CONST_AS MfActArgs& a = args[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int c = tid; c < a.Kp[0]; c += 512) xs[0][c] = c < a.in_dim ? obs_host[a.obs_off + c] : 0.f;
     __syncthreads();
@@ -844,12 +844,23 @@ __global__ __launch_bounds__(512) void k_dqn_mlp_act_group(const MF_CONST_AS MfA
         }
         __syncthreads();
     }
-    float* slot = out_host + (size_t)blockIdx.x * MF_ACT_SLOT;
     if (tid < a.A) slot[16 + tid] = xs[a.L & 1][tid];
     if (tid < (int)bdr_agent::ERR_WORDS) reinterpret_cast<unsigned*>(slot)[4 + tid] = a.dev_err[tid];
     __threadfence_system();
     __syncthreads();
     if (tid == 0) __hip_atomic_store(reinterpret_cast<unsigned*>(slot), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__global__ __launch_bounds__(512) void k_dqn_mlp_act_group(const MF_CONST_AS MfActArgs* args, const float* obs_host, float* out_host, unsigned seq)
+{
+    mf_act_body(args[blockIdx.x], obs_host, out_host + (size_t)blockIdx.x * MF_ACT_SLOT, seq);
+}
+// a subset of the members: workgroup b runs member sel[b] (n_sel workgroups; the host has checked every sel[b] < P).  `sel` is a
+// pinned host array read in place like the MfStep slots: sel[blockIdx.x] is uniform, so the member's fields stay scalar loads.
+__global__ __launch_bounds__(512) void k_dqn_mlp_act_group_sel(const MF_CONST_AS MfActArgs* args, const MF_CONST_AS unsigned* sel, const float* obs_host,
+                                                               float* out_host, unsigned seq)
+{
+    const unsigned p = sel[blockIdx.x];
+    mf_act_body(args[p], obs_host, out_host + (size_t)p * MF_ACT_SLOT, seq);
 }
 // every member's error words -> its pinned mirror (k_err_mirror for a whole group, one launch)
 struct MfErrRef { const unsigned* dev_err; unsigned* host_err; };

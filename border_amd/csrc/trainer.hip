@@ -207,6 +207,79 @@ int32_t dg_opt_rec(void* g, void* const* b, float* out, int32_t cap, int32_t* n)
 {
     return bdr_agent_group_opt_with_scalars((bdr_agent_group*)g, (bdr_replay* const*)b, out, cap, n);
 }
+int32_t dg_sample_members(void* g, const uint32_t* members, uint32_t n, const void* const* obs, int64_t* act)
+{
+    return bdr_agent_group_sample_members((bdr_agent_group*)g, members, n, obs, act, nullptr);
+}
+int32_t dg_save_member(void* g, uint32_t member, const char* dir)
+{
+    bdr_agent* m = nullptr;
+    BDR_TRY(bdr_agent_group_member((bdr_agent_group*)g, member, &m));
+    return d_save(m, dir);
+}
+
+// every refusal of bdr_evaluate_group, naming the member: the group acts on host f32 rows and writes one i64 action
+int32_t check_group_eval(const bdr_evaluator* evs, const bdr_group_eval_ops* ops)
+{
+    BDR_REQUIRE(evs && ops, "null argument");
+    BDR_REQUIRE(ops->sample_members, "the group evaluation function table is incomplete");
+    BDR_REQUIRE(ops->n_members >= 1, "the group evaluation function table names no members");
+    for (uint32_t p = 0; p < ops->n_members; ++p) {
+        const bdr_evaluator& ev = evs[p];
+        BDR_REQUIRE(ev.env.reset_with_index && ev.env.step, "member %u: the evaluator's environment function table is incomplete", p);
+        BDR_REQUIRE(ev.n_episodes >= 1, "member %u: n_episodes must be >= 1", p);
+        BDR_REQUIRE(ev.obs_row_bytes > 0, "member %u: obs_row_bytes must be set", p);
+        BDR_REQUIRE(ev.act_row_bytes == 8, "member %u: a group acts with one i64 action per member: act_row_bytes must be 8", p);
+        BDR_REQUIRE(ev.obs_dtype == BDR_DTYPE_F32, "member %u: a group acts on float32 rows (obs_dtype must be BDR_DTYPE_F32)", p);
+        BDR_REQUIRE(!ev.norm, "member %u: a group acts on the rows as they are (norm must be NULL)", p);
+        BDR_REQUIRE(!ev.env.obs_on_device, "member %u: a group acts on host rows (obs_on_device environments are not supported)", p);
+    }
+    return BDR_OK;
+}
+
+int32_t check_group_post(const bdr_group_trainer_post* post, uint32_t P)
+{
+    if (!post) return BDR_OK;
+    BDR_REQUIRE(!post->eval_interval || post->evaluators, "eval_interval is set: post-processing needs one evaluator per member");
+    BDR_REQUIRE(!(post->eval_interval || post->save_interval) || post->model_dirs, "post-processing saves models: model_dirs must be set");
+    if (post->eval_interval || post->save_interval)
+        for (uint32_t p = 0; p < P; ++p) BDR_REQUIRE(post->model_dirs[p], "member %u: null model directory", p);
+    if (post->eval_interval) {
+        BDR_REQUIRE(post->eval_ops.n_members == P, "the evaluation function table names %u members, the loop %u", post->eval_ops.n_members, P);
+        BDR_TRY(check_group_eval(post->evaluators, &post->eval_ops));
+    }
+    return BDR_OK;
+}
+
+typedef void (*GroupObserver)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars, int32_t n_scalars);
+
+// trainer.rs:231-264 for every member, after an iteration that took an opt step; max_eval_reward[p] is member p's own
+int32_t group_post_process(State& s, const bdr_group_trainer_ops* ops, const bdr_group_trainer_post* post, std::vector<float>& max_eval_reward,
+                           GroupObserver obs, void* ctx)
+{
+    if (!post) return BDR_OK;
+    const uint32_t P = ops->n_members;
+    const auto save = post->save_member ? post->save_member : dg_save_member;
+    if (post->eval_interval && s.opt_steps % post->eval_interval == 0) {
+        BDR_TRY(ops->set_train(ops->group, 0));
+        std::vector<bdr_eval_result> r(P);
+        BDR_TRY(bdr_evaluate_group(post->evaluators, &post->eval_ops, r.data()));
+        BDR_TRY(ops->set_train(ops->group, 1));
+        if (obs)
+            for (uint32_t p = 0; p < P; ++p) {
+                const float sc[2] = {r[p].score, r[p].normalized};
+                obs(ctx, p, s.env_steps, s.opt_steps, BDR_TRAINER_EVENT_EVAL, sc, r[p].has_normalized ? 2 : 1);
+            }
+        for (uint32_t p = 0; p < P; ++p) {
+            if (!(r[p].score > max_eval_reward[p])) continue;
+            max_eval_reward[p] = r[p].score;
+            BDR_TRY(save(ops->group, p, (std::string(post->model_dirs[p]) + "/best").c_str()));
+        }
+    }
+    if (post->save_interval > 0 && s.opt_steps % post->save_interval == 0)
+        for (uint32_t p = 0; p < P; ++p) BDR_TRY(save(ops->group, p, (std::string(post->model_dirs[p]) + "/" + std::to_string(s.opt_steps)).c_str()));
+    return BDR_OK;
+}
 }  // namespace
 
 namespace bdr {
@@ -355,10 +428,84 @@ void bdr_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_agent_group* 
     ops->set_train = dg_set_train; ops->sample = dg_sample; ops->push = dg_push; ops->opt = dg_opt; ops->opt_with_record = dg_opt_rec;
 }
 
+void bdr_group_eval_ops_default(bdr_group_eval_ops* ops, bdr_agent_group* group)
+{
+    if (!ops) return;
+    memset(ops, 0, sizeof *ops);
+    ops->group = group;
+    if (group) (void)bdr_agent_group_size(group, &ops->n_members);
+    ops->sample_members = dg_sample_members;
+}
+
+void bdr_group_trainer_post_default(bdr_group_trainer_post* post, bdr_agent_group* group)
+{
+    if (!post) return;
+    memset(post, 0, sizeof *post);
+    bdr_group_eval_ops_default(&post->eval_ops, group);
+    post->save_member = dg_save_member;
+}
+
+// default_evaluator.rs:64-88 for every member in lockstep: member p sees exactly the calls bdr_evaluate(&evs[p], member p) makes
+int32_t bdr_evaluate_group(const bdr_evaluator* evs, const bdr_group_eval_ops* ops, bdr_eval_result* out)
+{
+    BDR_REQUIRE(evs && ops && out, "null argument");
+    BDR_TRY(check_group_eval(evs, ops));
+    const uint32_t P = ops->n_members;
+    std::vector<std::vector<uint8_t>> prev(P), next(P);
+    for (uint32_t p = 0; p < P; ++p) { prev[p].resize(evs[p].obs_row_bytes); next[p].resize(evs[p].obs_row_bytes); }
+    std::vector<const void*> rows(P);
+    std::vector<int64_t> act(P);
+    std::vector<float> r_total(P, 0.f), reward(P);
+    std::vector<int8_t> term(P), trunc(P), open(P, 0);
+    std::vector<uint64_t> ix(P, 0), n_steps(P, 0);
+    std::vector<uint32_t> sel;
+    sel.reserve(P);
+    for (;;) {
+        sel.clear();
+        for (uint32_t p = 0; p < P; ++p) {   // a member with episodes left and none open starts its next one
+            if (!open[p] && ix[p] < evs[p].n_episodes) {
+                BDR_TRY(evs[p].env.reset_with_index(evs[p].env.ctx, ix[p], prev[p].data()));
+                open[p] = 1;
+            }
+            if (open[p]) sel.push_back(p);
+            rows[p] = prev[p].data();
+        }
+        if (sel.empty()) break;   // ix == n_episodes for everybody
+        BDR_TRY(ops->sample_members(ops->group, sel.data(), (uint32_t)sel.size(), rows.data(), act.data()));
+        for (const uint32_t p : sel) {
+            reward[p] = 0; term[p] = 0; trunc[p] = 0;
+            BDR_TRY(evs[p].env.step(evs[p].env.ctx, &act[p], next[p].data(), &reward[p], &term[p], &trunc[p]));
+        }
+        for (const uint32_t p : sel) {
+            r_total[p] += reward[p];
+            n_steps[p] += 1;
+            if (term[p] == 1 || trunc[p] == 1) { open[p] = 0; ix[p] += 1; }   // step.rs:136-138
+            else prev[p].swap(next[p]);                                      // prev_obs = step.obs
+        }
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        const bdr_evaluator& ev = evs[p];
+        out[p].score = r_total[p] / (float)ev.n_episodes;
+        out[p].has_normalized = ev.has_ref_scores ? 1 : 0;
+        out[p].normalized = ev.has_ref_scores ? (out[p].score - ev.ref_min_score) / (ev.ref_max_score - ev.ref_min_score) : 0.f;   // border-minari/src/env.rs:162-168
+        out[p].n_steps = n_steps[p]; out[p].n_episodes = ev.n_episodes;
+    }
+    return BDR_OK;
+}
+
 int32_t bdr_trainer_train_group(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const bdr_group_trainer_ops* ops, const bdr_env_vtable* envs,
                                 void (*obs)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars,
                                             int32_t n_scalars),
                                 void* obs_ctx, bdr_trainer_stats* out)
+{
+    return bdr_trainer_train_group_post(c, obs_row_bytes, ops, envs, nullptr, obs, obs_ctx, out);
+}
+
+int32_t bdr_trainer_train_group_post(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const bdr_group_trainer_ops* ops, const bdr_env_vtable* envs,
+                                     const bdr_group_trainer_post* post,
+                                     void (*obs)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars,
+                                                 int32_t n_scalars),
+                                     void* obs_ctx, bdr_trainer_stats* out)
 {
     BDR_REQUIRE(c && ops && envs && obs_row_bytes, "null argument");
     BDR_REQUIRE(c->max_opts >= 1, "max_opts must be >= 1");
@@ -372,6 +519,8 @@ int32_t bdr_trainer_train_group(const bdr_trainer_config* c, const uint64_t* obs
         BDR_REQUIRE(!envs[p].obs_on_device, "member %u: the group loop takes host observations (obs_on_device environments are not supported)", p);
         BDR_REQUIRE(obs_row_bytes[p] > 0, "member %u: obs_row_bytes must be set", p);
     }
+    BDR_TRY(check_group_post(post, P));
+    std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member
     GroupAdapter ga{ops, std::vector<float>((size_t)P * 128), std::vector<int32_t>(P, 0)};
     bdr_trainer_ops t{};
     t.agent = &ga; t.agent_set_train = ga_set_train; t.agent_opt = ga_opt; t.agent_opt_with_record = ga_opt_rec;
@@ -415,6 +564,7 @@ int32_t bdr_trainer_train_group(const bdr_trainer_config* c, const uint64_t* obs
         const int32_t event = is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP;
         if (obs)
             for (uint32_t p = 0; p < P; ++p) obs(obs_ctx, p, s.env_steps, s.opt_steps, event, ga.scalars.data() + (size_t)p * 128, with_record ? ga.n_scalars[p] : 0);
+        if (is_opt) BDR_TRY(group_post_process(s, ops, post, max_eval_reward, obs, obs_ctx));
         struct Fan { decltype(obs) obs; void* ctx; uint32_t P; } fan{obs, obs_ctx, P};
         cost_record(s, obs ? +[](void* f, uint64_t es, uint64_t os, int32_t ev, const float* sc, int32_t n) {
             const Fan* fn = (const Fan*)f;

@@ -15,6 +15,15 @@ from . import _lib
 from .dqn import Dqn, DqnConfig, record_keys
 
 
+def raise_first(evaluators, status: int) -> None:
+    """Evaluator._raise over the evaluators of a group call: an environment's exception (status 99) is raised again, else the status is checked."""
+    if status == 99:
+        for e in evaluators:
+            if e.error is not None:
+                e._raise(status)
+    _lib.check(status)
+
+
 class DqnGroup:
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/mlp_agents.hip bdr_agent_group::STEP_SLOTS)
     PUSH_STAGING_DEPTH = 8   # slots of the push staging ring (bdr_agent_group::PUSH_SLOTS)
@@ -128,18 +137,44 @@ class DqnGroup:
         _lib.check(_lib.lib().bdr_agent_group_qvalues(self._g, ptrs, outs))
         return qs
 
-    def sample(self, rows, return_info: bool = False):
+    def sample(self, rows, return_info: bool = False, members=None):
         """Policy::sample of every member on one observation row each, one launch: int64 actions [n] (and the per-member info).
-        rows: one row per member, or - when every member has the same in_dim - a float32 array [n, in_dim]."""
+        rows: one row per member, or - when every member has the same in_dim - a float32 array [n, in_dim].
+        members: a strictly ascending list of member indices (bdr_agent_group_sample_members): only those act, in one launch of
+        len(members) workgroups; `rows` is still one row per member and the results still have one entry per member, of which only
+        the selected ones are written.  A member that is not selected is not touched: its exploration stream and counters stay."""
         rows, ptrs, _keep = self._rows(rows)
         n = len(rows)
-        act = np.empty(n, np.int64)
+        act = np.zeros(n, np.int64) if members is not None else np.empty(n, np.int64)
         info = (_lib.SampleInfoC * n)()
-        _lib.check(_lib.lib().bdr_agent_group_sample(self._g, ptrs, act.ctypes.data_as(C.c_void_p), info))
+        if members is None:
+            _lib.check(_lib.lib().bdr_agent_group_sample(self._g, ptrs, act.ctypes.data_as(C.c_void_p), info))
+        else:
+            sel = np.ascontiguousarray(members, np.uint32).reshape(-1)
+            _lib.check(_lib.lib().bdr_agent_group_sample_members(self._g, sel.ctypes.data_as(C.c_void_p), sel.size, ptrs,
+                                                                 act.ctypes.data_as(C.c_void_p), info))
         if return_info:
             return act, [{"eps": i.eps, "is_random": bool(i.is_random), "n_samples_act": i.n_samples_act,
                           "n_samples_best_act": i.n_samples_best_act} for i in info]
         return act
+
+    def evaluate(self, evaluators) -> list:
+        """The Evaluator of every member in lockstep (bdr_evaluate_group): member i on evaluators[i] (a border_amd.evaluator.Evaluator
+        built with act_dtype=np.int64; environment, n_episodes and reference scores may differ per member), one acting launch per
+        round over the members that still have an episode open.  Each EvalResult is what evaluators[i].evaluate(member i) gives;
+        the members stay in the mode they are in.  An exception raised by an environment is raised again here."""
+        from .evaluator import EvalResult
+        evaluators = list(evaluators)
+        n = len(self._members)
+        if len(evaluators) != n:
+            raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
+        evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
+        ops = _lib.GroupEvalOps()
+        _lib.lib().bdr_group_eval_ops_default(C.byref(ops), self._g)
+        out = (_lib.EvalResultC * n)()
+        rc = _lib.lib().bdr_evaluate_group(evs, C.byref(ops), out)
+        raise_first(evaluators, rc)
+        return [EvalResult(np.float32(o.score), np.float32(o.normalized) if o.has_normalized else None, o.n_steps, o.n_episodes) for o in out]
 
     def push(self, obs, act, next_obs, reward, is_terminated, is_truncated, buffers=None) -> None:
         """ExperienceBufferBase::push of one transition per member into the member's own buffer, one launch; does not synchronise.
@@ -159,13 +194,17 @@ class DqnGroup:
         _lib.check(_lib.lib().bdr_agent_group_push(self._g, bufs, optrs, act.ctypes.data_as(C.c_void_p), xptrs, reward.ctypes.data_as(C.c_void_p),
                                                    term.ctypes.data_as(C.c_void_p), trunc.ctypes.data_as(C.c_void_p)))
 
-    def train(self, envs, buffers, trainer_config, on_event=None) -> list:
+    def train(self, envs, buffers, trainer_config, on_event=None, evaluators=None, eval_interval=0, save_interval=0, model_dirs=None) -> list:
         """The compiled online loop over the group (bdr_trainer_train_group): member i on envs[i] and buffers[i], one group sample,
         one group push and at most one group opt per iteration.  on_event(member, env_steps, opt_steps, event, scalars); returns one
-        statistics dict per member."""
+        statistics dict per member.  evaluators / eval_interval / save_interval / model_dirs (one Evaluator and one directory per
+        member): Trainer::post_process after every opt step (bdr_trainer_train_group_post) - a lockstep evaluation every
+        eval_interval opt steps with an "eval" event per member, each member's best model in model_dirs[i]/best, every member in
+        model_dirs[i]/<opt_steps> every save_interval opt steps."""
         from .trainer import NativeTrainer
         self._buffers(buffers)   # (opt() / push() without buffers go on with these)
-        return NativeTrainer(trainer_config).train_group(envs, self, list(buffers), on_event=on_event)
+        return NativeTrainer(trainer_config).train_group(envs, self, list(buffers), on_event=on_event, evaluators=evaluators,
+                                                         eval_interval=eval_interval, save_interval=save_interval, model_dirs=model_dirs)
 
     def sync(self) -> None:
         _lib.check(_lib.lib().bdr_agent_group_sync(self._g))

@@ -305,11 +305,14 @@ class NativeTrainer:
             (evaluator._raise if hasattr(evaluator, "_raise") else _lib.check)(rc)
         return self._finish(st)
 
-    def train_group(self, envs, group, buffers, on_event=None):
+    def train_group(self, envs, group, buffers, on_event=None, evaluators=None, eval_interval=0, save_interval=0, model_dirs=None, save_member=None):
         """bdr_trainer_train_group: Trainer::train for the members of a `DqnGroup` in lockstep, member i on envs[i] (each as `train`'s
         env: reset(None) -> obs[1, in_dim], step_with_reset(act[1] int64) -> Step) and buffers[i].  One group sample, one group push
         and at most one group opt per iteration.  on_event(member, env_steps, opt_steps, event, scalars); returns (and keeps in
-        .stats) one statistics dict per member.  An exception raised by an environment ends the loop and is raised again here."""
+        .stats) one statistics dict per member.  An exception raised by an environment ends the loop and is raised again here.
+        evaluators / eval_interval / save_interval / model_dirs: Trainer::post_process per member (bdr_trainer_train_group_post; one
+        Evaluator with act_dtype=np.int64 and one directory per member); the observer then also gets "eval" events with [score] or
+        [score, normalized].  Leaving them out gives bdr_trainer_train_group."""
         n = len(envs)
         if n != len(group) or n != len(buffers):
             raise ValueError(f"{len(group)} members need {len(group)} environments and buffers, got {n} and {len(buffers)}")
@@ -356,9 +359,31 @@ class NativeTrainer:
             if on_event is not None:
                 on_event(member, env_steps, opt_steps, NativeTrainer.EVENTS[event], [scalars[i] for i in range(k)])
         c, st, obs = self._config(0, 8), (_lib.TrainerStatsC * n)(), _lib.GROUP_OBSERVER_FN(cb)
-        rc = _lib.lib().bdr_trainer_train_group(C.byref(c), (C.c_uint64 * n)(*rows), C.byref(ops), vts, obs, None, st)
+        if evaluators is None and not eval_interval and not save_interval and model_dirs is None:
+            rc = _lib.lib().bdr_trainer_train_group(C.byref(c), (C.c_uint64 * n)(*rows), C.byref(ops), vts, obs, None, st)
+        else:
+            post = _lib.GroupTrainerPostC()
+            _lib.lib().bdr_group_trainer_post_default(C.byref(post), group.handle)
+            post.eval_interval, post.save_interval = int(eval_interval or 0), int(save_interval or 0)
+            evaluators = list(evaluators) if evaluators is not None else []
+            if evaluators:
+                if len(evaluators) != n:
+                    raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
+                evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
+                post.evaluators = evs
+            if model_dirs is not None:
+                if len(model_dirs) != n:
+                    raise ValueError(f"{n} members need {n} model directories, got {len(model_dirs)}")
+                dirs = (C.c_char_p * n)(*[None if d is None else str(d).encode() for d in model_dirs])
+                post.model_dirs = dirs
+            if save_member is not None:
+                post.save_member = save_member
+            rc = _lib.lib().bdr_trainer_train_group_post(C.byref(c), (C.c_uint64 * n)(*rows), C.byref(ops), vts, C.byref(post), obs, None, st)
         if failure:
             raise failure[0]
+        if evaluators:
+            from .group import raise_first
+            raise_first(evaluators, rc)
         _lib.check(rc)
         self.stats = [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
         return self.stats

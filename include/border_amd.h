@@ -502,6 +502,14 @@ BDR_API int32_t bdr_agent_group_qvalues(bdr_agent_group* g, const void* const* o
 /* Policy::sample (dqn/base.rs:211-242) of every member on one observation row each: one launch, then each member's own
  * exploration stream and counters exactly as bdr_agent_sample(member i, 1, obs[i]) advances them.  act_out[n]; info[n] or NULL. */
 BDR_API int32_t bdr_agent_group_sample(bdr_agent_group* g, const void* const* obs, int64_t* act_out, bdr_sample_info* info);
+/* Policy::sample of the members members[0..n) (strictly ascending indices) on one observation row each: one launch of n
+ * workgroups.  obs / act_out / info are indexed by MEMBER ([group size]); only the selected entries are read / written.
+ * A member that is not selected is not touched at all: its explorer stream, n_samples_act / n_samples_best_act, pinned error
+ * mirror and last_replay_uid stay where they were.  For a selected member the call is bdr_agent_group_sample's, bit for bit.
+ * Refused with BDR_ERR_INVALID before anything moves when n == 0, an index is >= the group's size, the list is not strictly
+ * ascending, or a selected member's row is NULL.  With every member selected it enqueues what bdr_agent_group_sample enqueues. */
+BDR_API int32_t bdr_agent_group_sample_members(bdr_agent_group* g, const uint32_t* members, uint32_t n, const void* const* obs,
+                                               int64_t* act_out, bdr_sample_info* info);
 /* ExperienceBufferBase::push (generic_replay_buffer/base.rs:287-313) of ONE transition per member, member i's into buffers[i] at its
  * head: one launch on the group's stream and no copy command, whatever n is.  obs[i] / next_obs[i] are host rows of the member's
  * input width; act[n] (i64), reward[n] and the flags [n] are host arrays, free again when the call returns.  Each ring ends up
@@ -635,7 +643,7 @@ BDR_API int32_t bdr_trainer_train_offline(const bdr_trainer_config* c, const bdr
  * share env_steps, so warm-up, opt_interval, opt vs opt_with_record and the stop at max_opts are one decision - ending in one opt /
  * opt_with_record of the group.  Member i sees exactly the calls bdr_trainer_train makes for a lone agent on envs[i].
  * c->obs_row_bytes is ignored: obs_row_bytes[i] is member i's row size; c->act_row_bytes must be 8 (one i64 action).  Environments
- * with obs_on_device are refused (BDR_ERR_INVALID); the *_post entries (Evaluator, best model) have no group form.  The observer
+ * with obs_on_device are refused (BDR_ERR_INVALID); Trainer::post_process is bdr_trainer_train_group_post below.  The observer
  * (bdr_trainer_observer with the member index after ctx; may be NULL) receives every member's event of an iteration in member order (scalars: that member's Record on OPT_RECORD); out[n] receives
  * per-member statistics (env_steps, opt_steps and n_records are shared, n_episodes is the member's own). */
 typedef struct bdr_group_trainer_ops {
@@ -725,6 +733,52 @@ BDR_API int32_t bdr_trainer_train_post(const bdr_trainer_config* c, const bdr_tr
                                        bdr_trainer_stats* out);
 BDR_API int32_t bdr_trainer_train_offline_post(const bdr_trainer_config* c, const bdr_trainer_ops* ops, const bdr_trainer_post* post,
                                                bdr_trainer_observer observer, void* observer_ctx, bdr_trainer_stats* out);
+
+/* ---- The Evaluator and Trainer::post_process for a group ---------------------------------------------------------------------
+ * bdr_evaluate_group is default_evaluator.rs:64-88 for every member of a group in lockstep, member i on evs[i] (its own
+ * environment, n_episodes, obs_row_bytes and reference scores).  Per round: every member that has episodes left and no open episode
+ * gets reset_with_index(ix_i), in member order; ONE sample_members over the members with an open episode; step of each of those
+ * environments in member order; then per member r_total_i += reward, n_steps_i += 1, and on is_terminated | is_truncated the episode
+ * closes and ix_i += 1.  A member whose ix_i == n_episodes leaves the selection - it does not act any more, so its explorer stream
+ * and counters end where a lone bdr_evaluate leaves them - and the loop ends when nobody is left.  Member i sees exactly the calls
+ * bdr_evaluate(&evs[i], member i) makes: the same indices, the same actions, one f32 accumulator in call order, the same score
+ * and normalised score.  It does not touch the train / eval mode.  evs[i].agent_sample* are not used.  Refused with
+ * BDR_ERR_INVALID naming the member: an incomplete environment table, n_episodes == 0, obs_row_bytes == 0, act_row_bytes != 8,
+ * obs_dtype != BDR_DTYPE_F32, norm != NULL, env.obs_on_device != 0 (the group acts on host f32 rows).  A failing environment call or
+ * a failing sample_members returns its status at once. */
+typedef struct bdr_group_eval_ops {
+    void* group;
+    uint32_t n_members;
+    uint32_t reserved;
+    /* Policy::sample of members[0..n) (strictly ascending); obs and act_out are indexed by member (bdr_agent_group_sample_members) */
+    int32_t (*sample_members)(void* group, const uint32_t* members, uint32_t n, const void* const* obs, int64_t* act_out);
+} bdr_group_eval_ops;
+BDR_API void bdr_group_eval_ops_default(bdr_group_eval_ops* ops, bdr_agent_group* group);
+BDR_API int32_t bdr_evaluate_group(const bdr_evaluator* evs, const bdr_group_eval_ops* ops, bdr_eval_result* out);
+
+/* Trainer::post_process (trainer.rs:231-264) in the group loop.  After an iteration that took an opt step, behind the members'
+ * OPT / OPT_RECORD events and ahead of the cost record: when opt_steps % eval_interval == 0, set_train(0), bdr_evaluate_group,
+ * set_train(1) - unconditionally, as trainer.rs:246-248 - then every member's BDR_TRAINER_EVENT_EVAL in member order, and member i
+ * is saved to model_dirs[i]/best when its score > its own max_eval_reward (each starts at -FLT_MAX = f32::MIN; a strict >).  When
+ * save_interval > 0 and opt_steps % save_interval == 0 every member is saved to model_dirs[i]/<opt_steps>.  An interval of 0 means
+ * never.  The evaluator's time is in neither Trainer timer.  Member i's observer sees the event sequence bdr_trainer_train_post gives
+ * a lone agent.  Refused before anything runs: eval_interval without evaluators (or evaluators bdr_evaluate_group refuses),
+ * something to save without model_dirs, a NULL model_dirs[i] (naming the member). */
+typedef struct bdr_group_trainer_post {
+    uint64_t eval_interval;                 /* 0 = never */
+    uint64_t save_interval;                 /* 0 = never */
+    const bdr_evaluator* evaluators;        /* [n_members]; needed when eval_interval > 0 */
+    const char* const* model_dirs;          /* [n_members]; needed when something is saved */
+    bdr_group_eval_ops eval_ops;
+    int32_t (*save_member)(void* group, uint32_t member, const char* dir);   /* NULL: mkdir -p + bdr_agent_save_params of the member */
+} bdr_group_trainer_post;
+BDR_API void bdr_group_trainer_post_default(bdr_group_trainer_post* post, bdr_agent_group* group);
+/* bdr_trainer_train_group plus post_process; with post == NULL it is that function (one loop body). */
+BDR_API int32_t bdr_trainer_train_group_post(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const bdr_group_trainer_ops* ops,
+                                             const bdr_env_vtable* envs, const bdr_group_trainer_post* post,
+                                             void (*observer)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps,
+                                                              int32_t event, const float* scalars, int32_t n_scalars),
+                                             void* observer_ctx, bdr_trainer_stats* out);
 
 /* ---- border-async-trainer (border-async-trainer/src) -----------------------------------------------------------------------
  * The reference runs one learner thread (AsyncTrainer::train, async_trainer/base.rs:299-388) and n actor threads (Actor::run,

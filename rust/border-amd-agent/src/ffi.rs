@@ -464,6 +464,27 @@ pub struct bdr_group_trainer_ops {
     >,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_group_eval_ops {
+    pub group: *mut c_void,
+    pub n_members: u32,
+    pub reserved: u32,
+    pub sample_members:
+        Option<unsafe extern "C" fn(group: *mut c_void, members: *const u32, n: u32, obs: *mut *const c_void, act_out: *mut i64) -> i32>,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_group_trainer_post {
+    pub eval_interval: u64,
+    pub save_interval: u64,
+    pub evaluators: *const bdr_evaluator,
+    pub model_dirs: *mut *const c_char,
+    pub eval_ops: bdr_group_eval_ops,
+    pub save_member: Option<unsafe extern "C" fn(group: *mut c_void, member: u32, dir: *const c_char) -> i32>,
+}
+
 pub type bdr_trainer_observer =
     Option<unsafe extern "C" fn(ctx: *mut c_void, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32)>;
 
@@ -963,6 +984,14 @@ extern "C" {
     pub fn bdr_agent_group_opt_with_scalars(g: *mut bdr_agent_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
     pub fn bdr_agent_group_qvalues(g: *mut bdr_agent_group, obs: *mut *const c_void, q_out: *mut *const f32) -> i32;
     pub fn bdr_agent_group_sample(g: *mut bdr_agent_group, obs: *mut *const c_void, act_out: *mut i64, info: *mut bdr_sample_info) -> i32;
+    pub fn bdr_agent_group_sample_members(
+        g: *mut bdr_agent_group,
+        members: *const u32,
+        n: u32,
+        obs: *mut *const c_void,
+        act_out: *mut i64,
+        info: *mut bdr_sample_info,
+    ) -> i32;
     pub fn bdr_agent_group_sync(g: *mut bdr_agent_group) -> i32;
     pub fn bdr_agent_group_push(
         g: *mut bdr_agent_group,
@@ -1001,6 +1030,21 @@ extern "C" {
         obs_row_bytes: *const u64,
         ops: *const bdr_group_trainer_ops,
         envs: *const bdr_env_vtable,
+        observer: Option<
+            unsafe extern "C" fn(ctx: *mut c_void, member: u32, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32),
+        >,
+        observer_ctx: *mut c_void,
+        out: *mut bdr_trainer_stats,
+    ) -> i32;
+    pub fn bdr_group_eval_ops_default(ops: *mut bdr_group_eval_ops, group: *mut bdr_agent_group);
+    pub fn bdr_evaluate_group(evs: *const bdr_evaluator, ops: *const bdr_group_eval_ops, out: *mut bdr_eval_result) -> i32;
+    pub fn bdr_group_trainer_post_default(post: *mut bdr_group_trainer_post, group: *mut bdr_agent_group);
+    pub fn bdr_trainer_train_group_post(
+        c: *const bdr_trainer_config,
+        obs_row_bytes: *const u64,
+        ops: *const bdr_group_trainer_ops,
+        envs: *const bdr_env_vtable,
+        post: *const bdr_group_trainer_post,
         observer: Option<
             unsafe extern "C" fn(ctx: *mut c_void, member: u32, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32),
         >,

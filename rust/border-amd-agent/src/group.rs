@@ -10,6 +10,7 @@ use crate::{
     config::DqnConfig,
     dqn::AmdDqn,
     error::{check, expect},
+    evaluator::EvalResult,
     ffi,
     replay::AmdReplayBuffer,
 };
@@ -18,7 +19,9 @@ use border_core::{
     record::{Record, RecordValue},
     Configurable, Env,
 };
-use std::os::raw::c_void;
+use std::ffi::CString;
+use std::os::raw::{c_char, c_void};
+use std::path::Path;
 
 /// Owns its members: dropping the group destroys them (`bdr_agent_group_destroy`).
 pub struct AmdDqnGroup<E, O, A>
@@ -138,6 +141,19 @@ where
         Ok(act)
     }
 
+    /// `Policy::sample` of the members `members` (strictly ascending indices) only, one launch of `members.len()` workgroups
+    /// (`bdr_agent_group_sample_members`).  `rows` is still one row per member and the result has one entry per member, of which
+    /// only the selected ones are written (the others are 0).  A member that is not selected is not touched: its exploration
+    /// stream and counters stay where they were.
+    pub fn sample_members(&mut self, members: &[u32], rows: &[&[f32]]) -> Result<Vec<i64>> {
+        let mut ptrs = self.row_pointers(rows)?;
+        let mut act = vec![0i64; rows.len()];
+        check(unsafe {
+            ffi::bdr_agent_group_sample_members(self.g, members.as_ptr(), members.len() as u32, ptrs.as_mut_ptr(), act.as_mut_ptr(), std::ptr::null_mut())
+        })?;
+        Ok(act)
+    }
+
     /// `qnet.forward` of one observation row per member, one launch: member `i`'s action values.
     pub fn qvalues(&mut self, rows: &[&[f32]], n_actions: &[usize]) -> Result<Vec<Vec<f32>>> {
         let mut ptrs = self.row_pointers(rows)?;
@@ -207,16 +223,7 @@ where
         let mut hs = self.buffer_handles(buffers)?;
         let mut ctxs: Vec<GroupEnvCtx<E>> =
             envs.iter_mut().zip(obs_row_bytes).map(|(e, &b)| GroupEnvCtx { env: e as *mut E, obs_row_bytes: b as usize }).collect();
-        let vts: Vec<ffi::bdr_env_vtable> = ctxs
-            .iter_mut()
-            .map(|c| ffi::bdr_env_vtable {
-                ctx: c as *mut GroupEnvCtx<E> as *mut c_void,
-                reset: Some(group_env_reset::<E>),
-                step_with_reset: Some(group_env_step::<E>),
-                obs_on_device: 0,
-                device: 0,
-            })
-            .collect();
+        let vts = Self::env_vtables(&mut ctxs);
         let mut ops: ffi::bdr_group_trainer_ops = unsafe { std::mem::zeroed() };
         unsafe { ffi::bdr_group_trainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
         let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
@@ -226,10 +233,210 @@ where
         Ok(stats)
     }
 
+    fn env_vtables(ctxs: &mut [GroupEnvCtx<E>]) -> Vec<ffi::bdr_env_vtable>
+    where
+        E::Obs: ObsRows,
+        E::Act: DiscreteAct,
+    {
+        ctxs.iter_mut()
+            .map(|c| ffi::bdr_env_vtable {
+                ctx: c as *mut GroupEnvCtx<E> as *mut c_void,
+                reset: Some(group_env_reset::<E>),
+                step_with_reset: Some(group_env_step::<E>),
+                obs_on_device: 0,
+                device: 0,
+            })
+            .collect()
+    }
+
+    /// The Evaluator of every member in lockstep (`bdr_evaluate_group`): member `i` on `evaluators[i]`, one acting launch per round
+    /// over the members that still have an episode open.  Each result is what a lone `bdr_evaluate` of that member gives; the
+    /// members stay in the mode they are in.
+    pub fn evaluate(&mut self, evaluators: &mut [GroupEvaluator<E>]) -> Result<Vec<EvalResult>>
+    where
+        E::Obs: ObsRows,
+        E::Act: DiscreteAct,
+    {
+        let n = self.members.len();
+        if evaluators.len() != n {
+            return Err(anyhow!("{} members need {} evaluators, got {}", n, n, evaluators.len()));
+        }
+        let evs: Vec<ffi::bdr_evaluator> = evaluators.iter().map(|e| e.c).collect();
+        // SAFETY: bdr_group_eval_ops_default fills every field.
+        let mut ops: ffi::bdr_group_eval_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_group_eval_ops_default(&mut ops, self.g) };
+        let mut out = vec![ffi::bdr_eval_result::default(); n];
+        check(unsafe { ffi::bdr_evaluate_group(evs.as_ptr(), &ops, out.as_mut_ptr()) })?;
+        Ok(out.iter().map(eval_result).collect())
+    }
+
+    /// [`AmdDqnGroup::train`] plus `Trainer::post_process` per member (`bdr_trainer_train_group_post`): every `eval_interval` opt
+    /// steps a lockstep evaluation on `evaluators`, member `i`'s best model in `model_dirs[i]/best`, and every `save_interval` opt
+    /// steps every member in `model_dirs[i]/<opt_steps>`.  An interval of 0 means never.
+    #[allow(clippy::too_many_arguments)]
+    pub fn train_post(
+        &mut self,
+        envs: &mut [E],
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        obs_row_bytes: &[u64],
+        config: &ffi::bdr_trainer_config,
+        evaluators: &mut [GroupEvaluator<E>],
+        eval_interval: usize,
+        save_interval: usize,
+        model_dirs: &[&Path],
+    ) -> Result<Vec<ffi::bdr_trainer_stats>>
+    where
+        E::Obs: ObsRows,
+        E::Act: DiscreteAct,
+    {
+        let n = self.members.len();
+        if envs.len() != n || obs_row_bytes.len() != n || model_dirs.len() != n {
+            return Err(anyhow!("{} members need {} environments, row sizes and model directories", n, n));
+        }
+        if eval_interval > 0 && evaluators.len() != n {
+            return Err(anyhow!("{} members need {} evaluators, got {}", n, n, evaluators.len()));
+        }
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut ctxs: Vec<GroupEnvCtx<E>> =
+            envs.iter_mut().zip(obs_row_bytes).map(|(e, &b)| GroupEnvCtx { env: e as *mut E, obs_row_bytes: b as usize }).collect();
+        let vts = Self::env_vtables(&mut ctxs);
+        let mut ops: ffi::bdr_group_trainer_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_group_trainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
+        let evs: Vec<ffi::bdr_evaluator> = evaluators.iter().map(|e| e.c).collect();
+        let mut dirs = Vec::with_capacity(n);
+        for d in model_dirs {
+            dirs.push(CString::new(d.to_string_lossy().as_bytes())?);
+        }
+        let mut dir_ptrs: Vec<*const c_char> = dirs.iter().map(|d| d.as_ptr()).collect();
+        // SAFETY: bdr_group_trainer_post_default fills every field.
+        let mut post: ffi::bdr_group_trainer_post = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_group_trainer_post_default(&mut post, self.g) };
+        post.eval_interval = eval_interval as u64;
+        post.save_interval = save_interval as u64;
+        post.evaluators = if evs.is_empty() { std::ptr::null() } else { evs.as_ptr() };
+        post.model_dirs = dir_ptrs.as_mut_ptr();
+        let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
+        check(unsafe {
+            ffi::bdr_trainer_train_group_post(
+                config,
+                obs_row_bytes.as_ptr(),
+                &ops,
+                vts.as_ptr(),
+                &post,
+                None,
+                std::ptr::null_mut(),
+                stats.as_mut_ptr(),
+            )
+        })?;
+        Ok(stats)
+    }
+
     /// Blocks until the group's stream is idle; device-side errors of any member surface here.
     pub fn sync(&mut self) -> Result<()> {
         check(unsafe { ffi::bdr_agent_group_sync(self.g) })
     }
+}
+
+fn eval_result(o: &ffi::bdr_eval_result) -> EvalResult {
+    EvalResult {
+        score: o.score,
+        normalized: if o.has_normalized != 0 { Some(o.normalized) } else { None },
+        n_steps: o.n_steps as usize,
+        n_episodes: o.n_episodes as usize,
+    }
+}
+
+// ---- a member's evaluation Env behind bdr_eval_env_vtable: f32 observation rows, one i64 action -----------------------------------
+struct GroupEvalCtx<E: Env> {
+    env: E,
+    obs_row_bytes: usize,
+}
+
+/// One member's evaluator for [`AmdDqnGroup::evaluate`] / [`AmdDqnGroup::train_post`]: `DefaultEvaluator<E>`
+/// (`default_evaluator.rs:64-88`) on an environment of its own with f32 observation rows of `obs_dim` elements and discrete actions.
+pub struct GroupEvaluator<E: Env> {
+    ctx: Box<GroupEvalCtx<E>>,
+    c: ffi::bdr_evaluator,
+}
+
+impl<E> GroupEvaluator<E>
+where
+    E: Env,
+    E::Obs: ObsRows,
+    E::Act: DiscreteAct,
+{
+    pub fn new(env: E, n_episodes: usize, obs_dim: usize) -> Self {
+        let obs_row_bytes = obs_dim * 4;
+        let mut ctx = Box::new(GroupEvalCtx { env, obs_row_bytes });
+        // SAFETY: bdr_evaluator_default fills every field of the struct it is handed.
+        let mut c: ffi::bdr_evaluator = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_evaluator_default(&mut c, std::ptr::null_mut()) };
+        c.n_episodes = n_episodes as u64;
+        c.obs_row_bytes = obs_row_bytes as u64;
+        c.act_row_bytes = 8;
+        c.env = ffi::bdr_eval_env_vtable {
+            ctx: &mut *ctx as *mut GroupEvalCtx<E> as *mut c_void,
+            reset_with_index: Some(group_eval_reset::<E>),
+            step: Some(group_eval_step::<E>),
+            obs_on_device: 0,
+            device: 0,
+        };
+        Self { ctx, c }
+    }
+
+    /// `ref_min_score` / `ref_max_score` of a Minari dataset (`border-minari/src/env.rs:162-168`).
+    pub fn with_ref_scores(mut self, min: f32, max: f32) -> Self {
+        self.c.has_ref_scores = 1;
+        self.c.ref_min_score = min;
+        self.c.ref_max_score = max;
+        self
+    }
+
+    pub fn env_mut(&mut self) -> &mut E {
+        &mut self.ctx.env
+    }
+}
+
+unsafe extern "C" fn group_eval_reset<E>(ctx: *mut c_void, ix: u64, obs_out: *mut c_void) -> i32
+where
+    E: Env,
+    E::Obs: ObsRows,
+{
+    let ctx = &mut *(ctx as *mut GroupEvalCtx<E>);
+    let r = std::panic::catch_unwind(std::panic::AssertUnwindSafe(|| match ctx.env.reset_with_index(ix as usize) {
+        Ok(obs) => write_row(&obs, obs_out, ctx.obs_row_bytes),
+        Err(_) => 90,
+    }));
+    r.unwrap_or(90) // a panic must not unwind into C
+}
+
+unsafe extern "C" fn group_eval_step<E>(
+    ctx: *mut c_void,
+    act: *const c_void,
+    obs_out: *mut c_void,
+    reward: *mut f32,
+    is_terminated: *mut i8,
+    is_truncated: *mut i8,
+) -> i32
+where
+    E: Env,
+    E::Obs: ObsRows,
+    E::Act: DiscreteAct,
+{
+    let ctx = &mut *(ctx as *mut GroupEvalCtx<E>);
+    let r = std::panic::catch_unwind(std::panic::AssertUnwindSafe(|| {
+        let a = <E::Act as crate::bytes::ActFromRows<i64>>::from_rows(vec![*(act as *const i64)], 1);
+        let (step, _record) = ctx.env.step(&a);
+        let rc = write_row(&step.obs, obs_out, ctx.obs_row_bytes);
+        if rc != ffi::BDR_OK {
+            return rc;
+        }
+        *reward = step.reward[0];
+        *is_terminated = step.is_terminated[0];
+        *is_truncated = step.is_truncated[0];
+        ffi::BDR_OK
+    }));
+    r.unwrap_or(91)
 }
 
 // ---- a member's Env behind bdr_env_vtable (the callbacks of async_trainer.rs on an environment that already exists) ------------

@@ -11,7 +11,8 @@
 //! * [`AmdDqn`], [`AmdIqn`], [`AmdSac`] - `border-tch-agent/src/{dqn,iqn,sac}/base.rs`; configs keep the reference's field names
 //!   and serde layout ([`config`]), so the example YAML files load unchanged.
 //! * [`AmdDqnGroup`] - a set of small `Mlp` [`AmdDqn`] agents whose `Agent::opt` runs as one kernel launch, one workgroup per member
-//!   (`bdr_agent_group_*`); the members stay ordinary agents.
+//!   (`bdr_agent_group_*`); the members stay ordinary agents.  [`GroupEvaluator`]: one member's evaluator for the lockstep
+//!   `AmdDqnGroup::evaluate` / `train_post` (`bdr_evaluate_group`, `bdr_trainer_train_group_post`).
 //! * [`AmdIql`] - `border-candle-agent/src/iql/base.rs` (offline RL; [`IqlConfig`] deserialises the candle YAML names).
 //! * [`AmdAwac`] - `border-candle-agent/src/awac/base.rs` (offline and online RL; [`AwacConfig`] likewise).
 //! * [`AmdCandleSac`] - `border-candle-agent/src/sac/base.rs` (the candle SAC with its `Mlp2` Gaussian actor; [`CandleSacConfig`]
@@ -63,7 +64,7 @@ pub use candle_dqn::AmdCandleDqn;
 pub use candle_sac::AmdCandleSac;
 pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;
-pub use group::AmdDqnGroup;
+pub use group::{AmdDqnGroup, GroupEvaluator};
 pub use evaluator::{ActPath, AmdEvaluator, EvalResult, SampleRaw, TrainerPost};
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;

@@ -15,7 +15,15 @@ and states for every P whether the worst grouped leg beats the best leg of the l
 same protocol and bar:
   opt    group.opt of a group switched on (DqnGroup(prioritized=True)) against a loop of Agent::opt on the same kind of rings,
          member-updates/s
-  iter   group.sample -> group.push -> group.opt against the same iteration with P rb.push calls in the middle, member-iterations/s"""
+  iter   group.sample -> group.push -> group.opt against the same iteration with P rb.push calls in the middle, member-iterations/s
+
+--eval measures the lockstep evaluator (default profiles/bench_dqn_group_eval.json): members in eval mode, a trivial environment with
+episodes of a fixed length, n_episodes = 4, five alternating legs of 0.3 s per side (a leg is at least one call):
+  eval    group.evaluate (one acting launch per round) against Evaluator.evaluate(member) for each member of the same group, one
+          after the other, member-evaluations/s; the same bar for P >= 8, P = 1 reported without one
+  subset  group.sample(members=[0]) against group.sample() of all at P = 64 and 256, us per call (reported, no bar)
+--sample-full prints one line with the us per call of group.sample of all members at P = 64 (three runs of this commit and of the
+parent alternating show that the default path did not move); it writes no file."""
 import argparse
 import json
 import os
@@ -117,6 +125,86 @@ def online(args, rows):
     return doc
 
 
+class FixedEnv:
+    """the evaluator's trivial environment: episodes of `length` steps, a constant row, reward 1"""
+    def __init__(self, length=10):
+        self.length, self.t, self.row = length, 0, np.zeros(4, np.float32)
+
+    def reset_with_index(self, ix):
+        self.t = 0
+        return self.row
+
+    def step(self, act):
+        self.t += 1
+        return self.row, 1.0, self.t == self.length, False
+
+
+def alternating(a_step, b_step, n_legs, leg_s):
+    """calls/s of n_legs legs per side, the sides alternating; a leg runs whole calls until leg_s seconds are up (at least one)"""
+    a_step(); b_step()
+    out = ([], [])
+    for _ in range(n_legs):
+        for side, step in enumerate((a_step, b_step)):
+            n, t0 = 0, time.perf_counter()
+            while n == 0 or time.perf_counter() - t0 < leg_s:
+                step(); n += 1
+            out[side].append(n / (time.perf_counter() - t0))
+    return out
+
+
+def evaluation(args, rows):
+    from border_amd.evaluator import Evaluator
+    doc = {"bench": "dqn_group_eval", "shape": "Mlp[64,64] in 4 A 2, members in eval mode, n_episodes 4, episodes of 10 steps, host rows",
+           "legs": args.legs, "leg_seconds": args.leg_seconds, "unit_eval": "member-evaluations/s (median of the legs)",
+           "unit_subset": "us per call (median of the legs)",
+           "bar": "group_min - loop_max > max(group_max - group_min, loop_max - loop_min) for P >= 8; P = 1 is reported without a bar",
+           "eval": {}, "subset": {}}
+    for P in [int(x) for x in args.sizes.split(",")]:
+        g = B.DqnGroup.build([c1(i) for i in range(P)])
+        for m in g.members: m.eval()
+        evs = [Evaluator(FixedEnv(), 4, obs_dim=4, act_dim=1, act_dtype=np.int64) for _ in range(P)]
+        members = g.members
+
+        def loop_eval():
+            for e, m in zip(evs, members): e.evaluate(m)
+
+        la, lb = alternating(lambda: g.evaluate(evs), loop_eval, args.legs, args.leg_seconds)
+        la, lb = [x * P for x in la], [x * P for x in lb]
+        m = {"group": statistics.median(la), "group_min_max": [min(la), max(la)], "loop": statistics.median(lb), "loop_min_max": [min(lb), max(lb)]}
+        m["ratio"] = m["group"] / m["loop"]; m["ratio_worst_case"] = min(la) / max(lb)
+        m = {k: (round(v, 2) if isinstance(v, float) else [round(x, 1) for x in v]) for k, v in m.items()}
+        (g0, g1), (l0, l1) = m["group_min_max"], m["loop_min_max"]
+        m["bar_met"] = bool(g0 - l1 > max(g1 - g0, l1 - l0)) if P >= 8 else None
+        doc["eval"][str(P)] = m
+        print(P, "eval", m, flush=True)
+        if P in (64, 256):
+            obs = np.ascontiguousarray(rows[0][:P])
+            one, full = alternating(lambda: g.sample(obs, members=[0]), lambda: g.sample(obs), args.legs, args.leg_seconds)
+            one, full = [1e6 / x for x in one], [1e6 / x for x in full]
+            doc["subset"][str(P)] = {"one_member_us": round(statistics.median(one), 2), "one_member_min_max": [round(min(one), 2), round(max(one), 2)],
+                                     "all_members_us": round(statistics.median(full), 2), "all_members_min_max": [round(min(full), 2), round(max(full), 2)]}
+            print(P, "subset", doc["subset"][str(P)], flush=True)
+        g.close()
+    return doc
+
+
+def sample_full(args, rows):
+    P = 64
+    g = B.DqnGroup.build([c1(i) for i in range(P)])
+    for m in g.members: m.eval()
+    obs = np.ascontiguousarray(rows[0][:P])
+    for _ in range(200): g.sample(obs)
+    us = []
+    for _ in range(args.legs):
+        n, t0 = 0, time.perf_counter()
+        while time.perf_counter() - t0 < args.leg_seconds:
+            for _ in range(20): g.sample(obs)
+            n += 20
+        us.append(1e6 * (time.perf_counter() - t0) / n)
+    g.close()
+    print(json.dumps({"sample_full_P64_us": round(statistics.median(us), 2), "min_max": [round(min(us), 2), round(max(us), 2)]}))
+
+
 def per_ring(seed, rows):
     rb = B.SimpleReplayBuffer(B.SimpleReplayBufferConfig(capacity=10000, seed=seed, per_config=B.PerConfig()), (4,), np.float32)
     # FULL rings: a uniform of exactly 0 (word 840 702 of seed 100's stream, update 26 271) descends to the leftmost leaf; in a part-filled
@@ -176,6 +264,8 @@ def prioritized(args, rows):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--eval", action="store_true", help="measure the lockstep evaluator against a loop of Evaluator.evaluate, and the subset launch")
+    ap.add_argument("--sample-full", action="store_true", help="print the us per call of group.sample of all members at P = 64 and exit")
     ap.add_argument("--per", action="store_true", help="measure prioritized rings under a group: opt and the online iteration")
     ap.add_argument("--online", action="store_true", help="measure group.push and the online iteration instead of opt / sample")
     ap.add_argument("--sizes", default="1,8,64,256")
@@ -183,11 +273,12 @@ def main():
     ap.add_argument("--legs", type=int, default=5)
     ap.add_argument("--leg-seconds", type=float, default=0.3)
     ap.add_argument("--out", default=None, help="default: profiles/bench_dqn_group.json, with --online profiles/bench_dqn_group_online.json, "
-                                                "with --per profiles/bench_dqn_group_per.json")
+                                                "with --per profiles/bench_dqn_group_per.json, "
+                                                "with --eval profiles/bench_dqn_group_eval.json")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
-                                "bench_dqn_group_per.json" if args.per else "bench_dqn_group_online.json" if args.online else "bench_dqn_group.json")
+                                "bench_dqn_group_eval.json" if args.eval else "bench_dqn_group_per.json" if args.per else "bench_dqn_group_online.json" if args.online else "bench_dqn_group.json")
     rng = np.random.default_rng(0)
     n = 5000
     rows = (rng.standard_normal((n, 4)).astype(np.float32), rng.integers(0, 2, (n, 1)).astype(np.int64),
@@ -195,11 +286,15 @@ def main():
     doc = {"bench": "dqn_group", "shape": "Mlp[64,64] in 4 A 2, batch 32, ring 5000 / 10000", "window_steps": args.window, "legs": args.legs,
            "leg_seconds": args.leg_seconds, "unit_opt": "member-updates/s (median of the legs)", "unit_sample": "member-actions/s (median of the legs)",
            "opt": {}, "sample": {}}
-    if args.per:
+    if args.sample_full:
+        return sample_full(args, rows)
+    if args.eval:
+        doc = evaluation(args, rows)
+    elif args.per:
         doc = prioritized(args, rows)
     elif args.online:
         doc = online(args, rows)
-    for P in [] if args.online or args.per else [int(x) for x in args.sizes.split(",")]:
+    for P in [] if args.online or args.per or args.eval else [int(x) for x in args.sizes.split(",")]:
         g = B.DqnGroup.build([c1(i) for i in range(P)])
         g_rings = [ring(100 + i, rows) for i in range(P)]
         solo = [B.Dqn.build(c1(i)) for i in range(P)]
