@@ -270,7 +270,7 @@ int32_t bdr_agent::err_poll()
 {
     if (!dev_err) return BDR_OK;
     unsigned w[ERR_WORDS];
-    for (int i = 0; i < ERR_WORDS; ++i) w[i] = reinterpret_cast<volatile unsigned*>(host_err)[i];
+    err_mirror_read(w);
     BDR_TRY(err_report(w));
     if (++err_poll_count % ERR_POLL_INTERVAL == 0) {
         if (!host_err_dev) BDR_HIP(hipHostGetDevicePointer((void**)&host_err_dev, host_err, 0));

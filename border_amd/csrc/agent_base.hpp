@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "igemm.hpp"
 #include "param_table.hpp"
+#include "slot_ring.hpp"
 #include "step_graph.hpp"
 
 // DqnExplorer / IqnExplorer state (dqn/explorer.rs:8-120, iqn/explorer.rs:9-108).  The reference draws from
@@ -89,10 +90,25 @@ static __global__ __launch_bounds__(256) void k_publish_rows(const float* src, f
     if (threadIdx.x == 0) __hip_atomic_store(seq_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// Spins until the pinned sequence word `done` has reached `seq` (k_publish_rows' protocol).  After 20 s, counted from t0, a kernel is
+// taken for lost: the stream is synchronised, so that it reports what it has to report, and the word is looked at once more.
+// *arrived: whether the word got there; what a missing word means is the caller's to say.
+inline int32_t wait_seq_word(const volatile unsigned* done, unsigned seq, hipStream_t stream, std::chrono::steady_clock::time_point t0, bool* arrived)
+{
+    for (unsigned spins = 0; !bdr::seq_reached(*done, seq); ++spins) {
+        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+            BDR_HIP(hipStreamSynchronize(stream));
+            break;
+        }
+    }
+    *arrived = bdr::seq_reached(*done, seq);
+    return BDR_OK;
+}
+
 struct bdr_agent : bdr::ParamTable {
     int32_t device = 0;
     hipStream_t stream = nullptr;
-    void* group = nullptr;          // the live bdr_agent_group that adopted this agent (`stream` is then the group's; mlp_agents.hip)
+    void* group = nullptr;          // the live bdr_agent_group that adopted this agent (`stream` is then the group's; agent_group.hpp)
     bool train = false;
     uint64_t n_opts = 0;
     int32_t ckpt_format = BDR_CKPT_TCH;
@@ -158,6 +174,9 @@ struct bdr_agent : bdr::ParamTable {
     int32_t err_report(const unsigned* w);
     int32_t err_check();   // the stream has just been synchronised: read, report, clear
     int32_t err_poll();    // no synchronisation: look at the last asynchronous read-back, enqueue the next one when due
+    // the pinned mirror as it stands (kernels write it: volatile reads), and the words a pinned result slot brought along into it
+    void err_mirror_read(unsigned* w) const { for (int i = 0; i < ERR_WORDS; ++i) w[i] = reinterpret_cast<const volatile unsigned*>(host_err)[i]; }
+    void err_adopt(const volatile unsigned* words) { for (int i = 0; i < ERR_WORDS; ++i) reinterpret_cast<volatile unsigned*>(host_err)[i] = words[i]; }
     // Result rows of an ACTING call (Policy::sample: a handful of floats once per environment step) -> host.  Up to ROWS_PINNED_MAX_FLOATS
     // go through pinned host memory: a one-workgroup kernel behind the forward pass stores the rows, the error words and then a sequence
     // number there, and this thread waits for the number - instead of a copy command plus a stream synchronisation (~25 us of host
@@ -191,18 +210,13 @@ struct bdr_agent : bdr::ParamTable {
     int32_t rows_wait(unsigned seq, float* out, size_t n_floats)
     {
         const volatile unsigned* done = reinterpret_cast<const volatile unsigned*>(rows_host);
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0; (int)(*done - seq) < 0; ++spins) {
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {   // a lost kernel: let the stream report
-                BDR_HIP(hipStreamSynchronize(stream));
-                if ((int)(*done - seq) < 0) return ::bdr::fail(BDR_ERR_HIP, "the result rows of an acting call never arrived in host memory");
-                break;
-            }
-        }
+        bool arrived = false;
+        BDR_TRY(wait_seq_word(done, seq, stream, std::chrono::steady_clock::now(), &arrived));
+        if (!arrived) return ::bdr::fail(BDR_ERR_HIP, "the result rows of an acting call never arrived in host memory");
         std::atomic_thread_fence(std::memory_order_acquire);
         memcpy(out, rows_host + 16, n_floats * sizeof(float));
         if (dev_err && host_err) {   // this call's view of the error words: the caller polls them instead of copying them once more
-            for (int i = 0; i < ERR_WORDS; ++i) reinterpret_cast<volatile unsigned*>(host_err)[i] = reinterpret_cast<const volatile unsigned*>(rows_host)[4 + i];
+            err_adopt(done + 4);
             err_fresh = true;
         }
         return BDR_OK;

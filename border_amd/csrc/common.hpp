@@ -226,7 +226,7 @@ int32_t per_check(bdr_per* p);   // non-finite priorities flagged by the update 
 inline const float* replay_batch_weights(const bdr_replay* r) { return r->per ? per_weights(r->per) : nullptr; }
 int32_t replay_update_priority_on_stream(bdr_replay* r, uint64_t n, const float* td_dev, hipStream_t stream);
 
-// ---- per.hip: the prioritized members of an agent group (bdr_agent_group, mlp_agents.hip) -----------------------------------------
+// ---- per.hip: the prioritized members of an agent group (bdr_agent_group, agent_group.hpp) ----------------------------------------
 // Every kernel below serves ALL prioritized members of a group in one launch on the group's stream.  The static descriptor of a member
 // sits in a device array (rewritten behind a synchronise when a buffer changes), the words of one step or push in a pinned slot the
 // kernels read in place.  The per_group_*_advance calls move the host state exactly as per_sample / per_update / per_push do.

@@ -25,7 +25,7 @@ def raise_first(evaluators, status: int) -> None:
 
 
 class DqnGroup:
-    STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/mlp_agents.hip bdr_agent_group::STEP_SLOTS)
+    STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/agent_group.hpp bdr_agent_group::STEP_SLOTS)
     PUSH_STAGING_DEPTH = 8   # slots of the push staging ring (bdr_agent_group::PUSH_SLOTS)
 
     def __init__(self, agents, prioritized: bool = False):

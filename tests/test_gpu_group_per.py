@@ -228,6 +228,40 @@ def test_grouped_push_on_prioritized_rings(B, monkeypatch):
     for r in rings: r.rb.close()
 
 
+def test_push_and_opt_alternating_on_prioritized_rings(B, monkeypatch):
+    """40 iterations of (one grouped push of one row, one group opt), no synchronise and no acting call in between, on prioritized rings
+    of capacity 5, 33 and 33 that start part filled and wrap: the step words, the prioritized words and the push records each go round
+    their staging ring five times by their own use count, every round and every push taking two launch numbers of the one counter"""
+    clean_env(monkeypatch)
+    assert 40 >= 4 * max(B.DqnGroup.STAGING_DEPTH, B.DqnGroup.PUSH_STAGING_DEPTH)
+    members = hetero(B, 1)[:3]
+    pers = [(5, 1.0, "All"), (33, 0.6, "Batch"), (33, 0.6, "All")]
+    want = []
+    for (c, seed), per in zip(members, pers):
+        a, ring = B.Dqn.build(c), PRing(B, c, seed, per)
+        cols = draw(ring.rng, ring.in_dim, ring.A, 40)
+        for k in range(40):
+            ring.rb.push(*row(cols, k))
+            a.opt(ring.rb)
+        want.append(pstate(a, ring, []))
+        a.close(); ring.rb.close()
+    g = B.DqnGroup.build([c for c, _ in members], prioritized=True)
+    rings = [PRing(B, c, seed, per) for (c, seed), per in zip(members, pers)]
+    bufs = [r.rb for r in rings]
+    cols = [draw(r.rng, r.in_dim, r.A, 40) for r in rings]
+    for k in range(40):
+        group_push(g, cols, k, bufs)
+        g.opt(bufs)
+    g.sync()
+    for i, (m, r) in enumerate(zip(g.members, rings)):
+        got = pstate(m, r, [])
+        assert_psame(got, want[i], f"member {i}")
+        assert got["n_opts"] == 40 and got["info"]["n_opts"] == 40 and got["info"]["n_samples"] == pers[i][0]
+        assert got["ring"]["len"] == pers[i][0] and got["ring"]["head"] == (pers[i][0] - 3 + 40) % pers[i][0]
+    g.close()
+    for r in rings: r.rb.close()
+
+
 def test_group_loop_on_prioritized_rings_equals_three_single_loops(B, monkeypatch):
     """DqnGroup.train over three members on prioritized rings against three Trainer runs on twins"""
     from border_amd.trainer import NativeTrainer, TrainerConfig

@@ -112,6 +112,38 @@ def test_staging_slots_are_reused_safely(B, monkeypatch):
     for rb in bufs: rb.close()
 
 
+def test_push_and_opt_alternating_without_a_synchronise(B, monkeypatch):
+    """40 iterations of (one grouped push of one row, one group opt) with no synchronise and no acting call in between: pushes and steps
+    draw their launch numbers from one counter in turn, so each staging ring is rewritten five times by its own use count while the
+    launches of BOTH are still queued; a slot rewritten early is a wrong row or a wrong Adam step"""
+    clean_env(monkeypatch)
+    assert 40 >= 4 * max(B.DqnGroup.STAGING_DEPTH, B.DqnGroup.PUSH_STAGING_DEPTH)
+    members = hetero(B, 1)[:3]
+    want = []
+    for c, seed in members:
+        a, ring = B.Dqn.build(c), Ring(B, c, seed)
+        cols = draw(ring.rng, ring.in_dim, ring.A, 40)
+        for k in range(40):
+            ring.rb.push(*row(cols, k))
+            a.opt(ring.rb)
+        want.append((state(a, ring, []), ring_state(ring.rb)))
+        a.close(); ring.rb.close()
+    g = B.DqnGroup.build([c for c, _ in members])
+    rings = [Ring(B, c, seed) for c, seed in members]
+    bufs = [r.rb for r in rings]
+    cols = [draw(r.rng, r.in_dim, r.A, 40) for r in rings]
+    for k in range(40):
+        group_push(g, cols, k, bufs)
+        g.opt(bufs)
+    g.sync()
+    for i, (m, r) in enumerate(zip(g.members, rings)):
+        assert_same(state(m, r, []), want[i][0], f"member {i}")
+        assert_same_ring(ring_state(r.rb), want[i][1], f"member {i}")
+        assert m.n_opts == 40 and r.rb.len() == 340
+    g.close()
+    for r in rings: r.rb.close()
+
+
 def test_ordering_against_the_groups_own_reads(B, monkeypatch):
     """the schedule of twelve_opts with its 50 rows pushed one by one: g.push between g.opt / g.opt_with_record against twins
     stepped by opt and fed by rb.push"""
