@@ -206,6 +206,15 @@ SAMPLE_RAW_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_v
 SAVE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_char_p)
 
 
+# bdr_group_info (bdr_agent_group_info): the form of a group and its launch counts
+GROUP_FORM_ONE_WORKGROUP, GROUP_FORM_LAYERS = 0, 1
+
+
+class GroupInfoC(C.Structure):
+    _fields_ = [("form", C.c_int32), ("n_members", C.c_uint32), ("launches_per_round", C.c_uint32), ("reserved", C.c_uint32),
+                ("kernel_launches", C.c_uint64)]
+
+
 # bdr_group_trainer_ops: the function table of bdr_trainer_train_group (one group, its members' buffers)
 G_SET_TRAIN_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32)
 G_SAMPLE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
@@ -323,7 +332,7 @@ ABI_SYMBOLS = [
     "bdr_agent_group_opt_with_scalars", "bdr_agent_group_qvalues", "bdr_agent_group_sample", "bdr_agent_group_sync",
     "bdr_agent_group_push", "bdr_group_trainer_ops_default", "bdr_trainer_train_group", "bdr_agent_group_set_prioritized",
     "bdr_agent_group_sample_members", "bdr_group_eval_ops_default", "bdr_evaluate_group", "bdr_group_trainer_post_default",
-    "bdr_trainer_train_group_post",
+    "bdr_trainer_train_group_post", "bdr_agent_group_info",
 ]
 
 _lib = None
@@ -494,6 +503,7 @@ def lib() -> C.CDLL:
     L.bdr_agent_group_size.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.bdr_agent_group_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.bdr_agent_group_opt.argtypes = [vp, vp]
+    L.bdr_agent_group_info.argtypes = [vp, C.POINTER(GroupInfoC)]
     L.bdr_agent_group_set_prioritized.argtypes = [vp, C.c_int32]
     L.bdr_agent_group_opt_with_scalars.argtypes = [vp, vp, vp, i32, vp]
     L.bdr_agent_group_qvalues.argtypes = [vp, vp, vp]

@@ -8,6 +8,8 @@
 //   per launch         three pinned, device-mapped staging rings the kernels read in place: MfStep[P] per step, PerGroupWords[P] per
 //                      round with prioritized members, [GroupPushDesc[P] | P records | words] per push
 // so one group step is one launch per update round and no copy command, whatever P is.
+// A group whose members do NOT take the one-workgroup step (one shape for all, Mlp[256, 256] at batch 64 among them) takes the layer
+// form instead: group_layers.hpp - the layer path's launches of one member, each serving all members, on the same rings and rule.
 // The one rule of the three rings (slot_ring.hpp): every launch that ends with mf_group_done / per_group_done takes the next number of
 // `launches` and publishes it to the pinned word `seq`; a ring takes its slots in turn by its own use count, records per slot the
 // number published by the last kernel that reads it - a step or a push its own number k, the words of a prioritized round and a push
@@ -47,6 +49,8 @@ template <class T> hipError_t pinned_array(PinnedArray<T>& out, size_t n)
 
 }  // namespace bdr
 
+#include "group_layers.hpp"
+
 struct bdr_agent_group {
     enum { STEP_SLOTS = 8, PUSH_SLOTS = 8 };
     using StepRing = SlotRing<STEP_SLOTS>;
@@ -58,6 +62,10 @@ struct bdr_agent_group {
     ~bdr_agent_group() { if (stream) { stream_retire(stream); (void)hipStreamDestroy(stream); } }
     std::vector<DqnMlp*> members;
     uint64_t n_updates = 1;
+    // the form: every member takes the one-workgroup step (layers == nullptr, everything below as it always was), or none does and all
+    // have one shape on the latency-shaped layer path (group_layers.hpp: its device arrays; `keys`, `steps`, `seq`, `ticket` are shared)
+    std::unique_ptr<GroupLayers> layers;
+    uint64_t kernel_launches = 0;                                       // every kernel launch the group's own calls have enqueued (bdr_agent_group_info)
     // opt
     struct StaticKey { bool valid = false; uint64_t batch_gen = 0; const void* td_abs = nullptr; uint64_t r_uid = 0, r_batch_gen = 0;
                        const void* weight = nullptr; int per_j = -1; };   // (prioritized ring: its weight array, its place in d_per)
@@ -166,16 +174,31 @@ int32_t group_name_member(int32_t st, uint32_t p)
     return st;
 }
 
+// The form follows member 0: the layer form when it is an Mlp DQN agent whose one-workgroup step is ON and whose network / batch size
+// does not take it; every other member 0 is judged by the one-workgroup rules, with their messages, as before.
+bool group_takes_layer_form(const bdr_agent* a)
+{
+    if (strcmp(a->kind(), "dqn_mlp") != 0) return false;
+    const DqnMlp* m = static_cast<const DqnMlp*>(a);
+    return m->fused && m->gather_in_step && !m->fused_ok((int)m->cfg.batch_size);
+}
+
 // why `a` cannot be a member (nullptr: it can)
-const char* group_ineligible(const bdr_agent* a, const DqnMlp** out)
+// layer_form: the group takes the layer form (group_takes_layer_form of member 0)
+const char* group_ineligible(const bdr_agent* a, const DqnMlp** out, bool layer_form)
 {
     if (strcmp(a->kind(), "dqn_mlp") != 0) return "not an Mlp DQN agent (kind dqn_mlp)";
     const DqnMlp* m = static_cast<const DqnMlp*>(a);
     *out = m;
     if (m->group) return "already a member of a group";
-    if (!m->fused) return "the one-workgroup step is switched off (BDR_NO_MLP_FUSED)";
-    if (!m->gather_in_step) return "the in-step sample is switched off (BDR_NO_STEP_GATHER)";
-    if (!m->fused_ok((int)m->cfg.batch_size)) return "its network / batch size does not take the one-workgroup step (at most 4 layers up to 256 wide, batch <= 128, at most 8 32x32 blocks per phase)";
+    if (layer_form) {   // (member 0 does not take the one-workgroup step: the layer form, one shape for all)
+        if (m->fused_ok((int)m->cfg.batch_size)) return "it takes the one-workgroup step, member 0 the layer path: one form per group";
+        if (const char* why = gl_layers_ineligible(m->gl_shape((int)m->cfg.batch_size))) return why;
+    } else {
+        if (!m->fused) return "the one-workgroup step is switched off (BDR_NO_MLP_FUSED)";
+        if (!m->gather_in_step) return "the in-step sample is switched off (BDR_NO_STEP_GATHER)";
+        if (!m->fused_ok((int)m->cfg.batch_size)) return "its network / batch size does not take the one-workgroup step (at most 4 layers up to 256 wide, batch <= 128, at most 8 32x32 blocks per phase)";
+    }
     if (m->amsgrad) return "amsgrad";
     if (m->grad_comm) return "a gradient communicator is installed";
     if (m->prof) return "profiling is on";
@@ -195,6 +218,7 @@ int32_t group_check_buffers(bdr_agent_group* g, bdr_replay* const* buffers)
                     (unsigned long long)r->obs_bytes, m->net.in_dim);
         BDR_REQUIRE(r->act_bytes >= 8, "member %u: discrete actions are stored as i64", p);
         BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
+        BDR_REQUIRE(!r->per || !g->layers, "member %u: a prioritized buffer cannot be stepped by a layer-form group (prioritized replay under the layer form is not built)", p);
         BDR_REQUIRE(!r->per || g->prioritized, "member %u: a prioritized buffer cannot be stepped by a group (the in-step sample covers the uniform ring)", p);
         BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by a group", p);
         BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: the in-step sample draws the StdRng index stream only", p);
@@ -286,6 +310,7 @@ int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_ro
         std::atomic_thread_fence(std::memory_order_release);
         if (per_need_mm) BDR_TRY(per_group_minmax(g->stream, d_per, per_words_dev, n_per, per_max_capacity, 0, PerGroupPublish{nullptr, nullptr, 0u}));
         BDR_TRY(per_group_sample(g->stream, d_per, per_words_dev, n_per));
+        g->kernel_launches += per_need_mm ? 2 : 1;
     }
     // the LDS form only when every member has a plan: otherwise all take the global-memory form (same bits)
     size_t lds = 0;
@@ -304,10 +329,12 @@ int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_ro
     }
     g->launches = k; g->step_ring.record(k);
     BDR_HIP(hipGetLastError());
+    g->kernel_launches += 1;
     if (n_per) {   // update_priority of every prioritized member (and the minimum the next `All` batch needs): the last of them publishes
         const PerGroupPublish pub{ticket, g->seq.dev, (unsigned)(k + 1)}, none{nullptr, nullptr, 0u};
         BDR_TRY(per_group_update(g->stream, d_per, n_per, per_any_all ? none : pub));
         if (per_any_all) BDR_TRY(per_group_minmax(g->stream, d_per, per_words_dev, n_per, per_max_capacity, 1, pub));
+        g->kernel_launches += per_any_all ? 2 : 1;
         g->launches = k + 1; g->per_ring.record(k + 1);
         for (uint32_t p = 0; p < P; ++p) {
             if (!buffers[p]->per) continue;
@@ -315,6 +342,53 @@ int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_ro
             replay_end_write_on_stream(buffers[p], g->stream, 0);   // a tree update is a write of the ring: the group's stream is its last writer
         }
     }
+    return BDR_OK;
+}
+
+// group_round for the layer form: per member what DqnMlp::opt_enqueue / update_critic do on the host for one update on the layer
+// path, then the round's launches (GroupLayers::launch), the last of which publishes the round's number
+int32_t group_round_layers(bdr_agent_group* g, bdr_replay* const* buffers, bool last_round)
+{
+    GroupLayers& gl = *g->layers;
+    const uint32_t P = (uint32_t)g->members.size();
+    const uint64_t k = g->launches + 1;
+    const auto step_slot = g->step_ring.next();
+    BDR_TRY(group_wait_seq(g, step_slot.wait));
+    MfStep* steps = g->steps.host.get() + (size_t)step_slot.slot * P;
+    bool dirty = false;
+    for (uint32_t p = 0; p < P; ++p) {
+        DqnMlp* m = g->members[p];
+        bdr_replay* r = buffers[p];
+        const int bs = (int)m->cfg.batch_size;
+        BDR_TRY(m->ensure_batch(bs));
+        BDR_TRY(m->td_buffer(bs));
+        GatherArgs plan{};
+        BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));   // the host half of replay_sample_on_stream; the rows are k_gather_group's
+        m->last_reward = r->b_reward; m->last_B = bs;
+        m->defer_adam = false;
+        m->head_fused = gl.head != 0;
+        m->track_with_next = last_round && m->soft_update_counter + 1 == m->cfg.soft_update_interval;
+        bdr_agent_group::StaticKey& key = g->keys[p];
+        if (!key.valid || key.batch_gen != m->batch_gen || key.td_abs != m->td_abs || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
+            GlMemberArgs o;
+            gl_member_static(m, bs, r, plan, o);
+            BDR_REQUIRE(o.dw_grid == (int)gl.plan[gl.n_launches - 2].gx, "member %u: the weight-gradient grid (%d) differs from the plan's (%u)", p, o.dw_grid,
+                        gl.plan[gl.n_launches - 2].gx);
+            gl.stage(p, P, o);
+            key.valid = true; key.batch_gen = m->batch_gen; key.td_abs = m->td_abs; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
+            dirty = true;
+        }
+        steps[p] = m->fused_step_advance(&plan);   // word_pos / size, adam_step and its scalars, the soft update riding on this round
+    }
+    if (dirty) {   // rare (first step, a reallocation, another ring): behind everything the stream still holds
+        BDR_HIP(hipStreamSynchronize(g->stream));
+        BDR_HIP(gl.upload(P));
+    }
+    std::atomic_thread_fence(std::memory_order_release);
+    // (should a launch fail, k is the number of whatever the group launches next - later than every reader of the slot)
+    g->launches = k; g->step_ring.record(k);
+    BDR_TRY(gl.launch(g->stream, P, g->steps.dev + (size_t)step_slot.slot * P, g->ticket.get(), g->seq.dev, (unsigned)k));
+    g->kernel_launches += (uint64_t)gl.n_launches;
     return BDR_OK;
 }
 
@@ -333,9 +407,10 @@ int32_t group_opt(bdr_agent_group* g, bdr_replay* const* buffers)
     if (++g->poll_count % bdr_agent::ERR_POLL_INTERVAL == 0) {   // every member's error words -> its pinned mirror, one launch
         hipLaunchKernelGGL(k_group_err_mirror, dim3(P), dim3(64), 0, g->stream, (const MfErrRef*)g->d_err_refs.get(), (int)bdr_agent::ERR_WORDS);
         BDR_HIP(hipGetLastError());
+        g->kernel_launches += 1;
     }
     for (uint32_t p = 0; p < P; ++p) g->members[p]->last_replay_uid = buffers[p]->uid;
-    for (uint64_t u = 0; u < g->n_updates; ++u) BDR_TRY(group_round(g, buffers, u + 1 == g->n_updates));
+    for (uint64_t u = 0; u < g->n_updates; ++u) BDR_TRY(g->layers ? group_round_layers(g, buffers, u + 1 == g->n_updates) : group_round(g, buffers, u + 1 == g->n_updates));
     for (uint32_t p = 0; p < P; ++p) BDR_TRY(g->members[p]->after_updates());   // (the soft update rode on the last round's launch: nothing is enqueued here)
     g->last_buffers.assign(buffers, buffers + P);
     return BDR_OK;
@@ -370,6 +445,7 @@ int32_t group_act(bdr_agent_group* g, const void* const* obs, const uint32_t* me
         hipLaunchKernelGGL(k_dqn_mlp_act_group, dim3(P), dim3(512), 0, g->stream, act_args, (const float*)g->obs_pin.dev, g->act_pin.dev, seq);
     }
     BDR_HIP(hipGetLastError());
+    g->kernel_launches += 1;
     const auto slot_words = [&](uint32_t b) { return reinterpret_cast<const volatile unsigned*>(g->act_pin.host.get() + (size_t)group_member_at(members, b) * MF_ACT_SLOT); };
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t b = 0; b < N; ++b) {
@@ -415,6 +491,7 @@ int32_t group_check_push(bdr_agent_group* g, bdr_replay* const* buffers, const v
         BDR_REQUIRE(r, "member %u: null buffer", p);
         BDR_REQUIRE(obs[p] && next_obs[p], "member %u: null observation row", p);
         BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
+        BDR_REQUIRE(!r->per || !g->layers, "member %u: a prioritized buffer cannot take the push of a layer-form group (prioritized replay under the layer form is not built)", p);
         BDR_REQUIRE(!r->per || g->prioritized, "member %u: a prioritized buffer cannot take a grouped push (its sum tree is updated by bdr_replay_push)", p);
         BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot take a grouped push", p);
         BDR_REQUIRE(r->obs_bytes == (uint64_t)m->net.in_dim * 4, "member %u: replay obs rows (%llu B) do not match the Mlp input (%d f32)", p,
@@ -503,12 +580,14 @@ int32_t group_push(bdr_agent_group* g, bdr_replay* const* buffers, const void* c
     BDR_HIP(hipGetLastError());
     // the tree kernels read the slot too: the last of them publishes, under a launch number of its own.  (Should one of them fail to
     // launch, k + 1 is the number of whatever the group launches next - later than every reader of the slot.)
+    g->kernel_launches += 1;
     g->launches = k; g->push_ring.record(n_per ? k + 1 : k);
     if (n_per) {
         const PerGroupWords* words_dev = reinterpret_cast<const PerGroupWords*>(g->push.dev + slot_off + words_off);
         PerGroupMember* const d_per_push = g->d_per_push.get();
         if (per_need_mm) BDR_TRY(per_group_minmax(g->stream, d_per_push, words_dev, n_per, per_max_capacity, 0, PerGroupPublish{nullptr, nullptr, 0u}));
         BDR_TRY(per_group_push(g->stream, d_per_push, words_dev, n_per, PerGroupPublish{g->ticket.get(), g->seq.dev, (unsigned)(k + 1)}));
+        g->kernel_launches += per_need_mm ? 2 : 1;
         g->launches = k + 1;
     }
     for (uint32_t p = 0; p < P; ++p) replay_end_write_on_stream(buffers[p], g->stream, 1);
@@ -525,11 +604,18 @@ int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr_agent_g
     BDR_REQUIRE(agents && out, "null argument");
     BDR_REQUIRE(n >= 1 && n <= 65535, "a group has 1 .. 65535 members");
     std::vector<DqnMlp*> ms;
+    BDR_REQUIRE(agents[0], "member 0: null agent");
+    const bool layer_form = group_takes_layer_form(agents[0]);
     for (uint32_t p = 0; p < n; ++p) {
         BDR_REQUIRE(agents[p], "member %u: null agent", p);
         const DqnMlp* m = nullptr;
-        const char* why = group_ineligible(agents[p], &m);
+        const char* why = group_ineligible(agents[p], &m, layer_form);
         BDR_REQUIRE(!why, "member %u cannot join a group: %s", p, why);
+        if (layer_form) {
+            const DqnMlp* m0 = static_cast<const DqnMlp*>(agents[0]);
+            BDR_REQUIRE(gl_same_shape(m->gl_shape((int)m->cfg.batch_size), m0->gl_shape((int)m0->cfg.batch_size)),
+                        "member %u cannot join a group: its shape (in_dim, units, out_dim, activation_out, batch_size, double_dqn) differs from member 0's - one shape per layer-form group", p);
+        }
         BDR_REQUIRE(m->device == agents[0]->device, "member %u lives on device %d, member 0 on device %d", p, m->device, agents[0]->device);
         BDR_REQUIRE(m->cfg.n_updates_per_opt == static_cast<const DqnMlp*>(agents[0])->cfg.n_updates_per_opt,
                     "member %u has n_updates_per_opt %llu, member 0 has %llu: one value per group", p, (unsigned long long)m->cfg.n_updates_per_opt,
@@ -559,7 +645,15 @@ int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr_agent_g
     }
     // (a failure below leaves nothing adopted: the partially built group releases what it holds)
     BDR_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    BDR_HIP(device_array(g->d_args, P));
+    if (layer_form) {   // the layer form's argument arrays instead of d_args
+        g->layers.reset(new GroupLayers());
+        BDR_HIP(g->layers->allocate(ms[0]->gl_shape((int)ms[0]->cfg.batch_size), P));
+        BDR_REQUIRE(g->layers->n_launches >= 3, "the layer-form launch plan is empty");
+        for (int i = 0; i < g->layers->n_launches; ++i)
+            BDR_REQUIRE(gl_grid_ok(g->layers->plan[i]), "%u members of this shape: the grid of %s exceeds the launch limits", n, gl_kernel_name(g->layers->plan[i].kernel));
+    } else {
+        BDR_HIP(device_array(g->d_args, P));
+    }
     BDR_HIP(device_array(g->d_act, P));
     BDR_HIP(device_array(g->d_err_refs, P));
     BDR_HIP(device_array(g->ticket, 1));
@@ -613,10 +707,22 @@ int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr_agent**
     return BDR_OK;
 }
 
+int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out)
+{
+    BDR_REQUIRE(g && out, "null argument");
+    memset(out, 0, sizeof *out);
+    out->form = g->layers ? BDR_GROUP_FORM_LAYERS : BDR_GROUP_FORM_ONE_WORKGROUP;
+    out->n_members = (uint32_t)g->members.size();
+    out->launches_per_round = g->layers ? (uint32_t)g->layers->n_launches : 1u;
+    out->kernel_launches = g->kernel_launches;
+    return BDR_OK;
+}
+
 int32_t bdr_agent_group_set_prioritized(bdr_agent_group* g, int32_t on)
 {
     BDR_REQUIRE(g, "null group");
     BDR_REQUIRE(on == 0 || on == 1, "on must be 0 or 1 (got %d)", on);
+    BDR_REQUIRE(!on || !g->layers, "prioritized replay under a layer-form group is not built: its members step prioritized rings standalone");
     if (on && !g->d_per) {   // the arrays of the tree kernels, once
         BDR_HIP(hipSetDevice(g->device));
         const size_t P = g->members.size();

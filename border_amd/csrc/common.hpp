@@ -188,6 +188,13 @@ struct GatherArgs {
     uint32_t given;       // 1: ixs[] was produced by the PER sampler, gather those rows
 };
 int32_t replay_sample_plan(bdr_replay* r, uint64_t n, hipStream_t stream, GatherArgs* out);
+// The plans of P members gathered by ONE launch of k_gather's body (a layer-form agent group, group_layers.hpp): the descriptors sit
+// in a device array, each member's stream position and ring size of this step at the start of its entry of a pinned staging slot.
+// Arguments a kernel reads in place from memory go through the constant address space: uniform indices make them scalar loads.
+#define BDR_CONST_AS __attribute__((address_space(4)))
+struct GatherStepWords { unsigned long long word_pos, size; };
+void replay_gather_shape(uint64_t obs_bytes, uint32_t* chunks, uint32_t* vec_per_chunk);
+int32_t replay_gather_group(hipStream_t stream, const GatherArgs* d_args, const void* words, uint32_t word_stride, uint32_t P, uint64_t n, uint64_t obs_bytes);
 int32_t replay_ensure_batch_capacity(bdr_replay* r, uint64_t n);
 // A kernel on `stream` - not necessarily the ring's own - is about to write `n` rows at the head (a grouped push): begin orders
 // `stream` behind the last gather (WAR) and behind every earlier write (WAW) and costs nothing when both were on `stream`; end, once

@@ -436,9 +436,10 @@ __device__ __forceinline__ bool last_workgroup(unsigned* ticket, unsigned n_wg, 
 
 struct HeadRef { const float* w; const float* bias; int relu; };   // a narrow layer handed to a row-block kernel
 
-// (the body as a function: sac.hip's k_dense_small_dx_tail runs it beside one more workgroup)
-template <bool DX>
-__device__ __forceinline__ void dense_small_body(const DenseArgs& a, float (*red)[32][33])
+// (the body as a function: sac.hip's k_dense_small_dx_tail runs it beside one more workgroup; Args is DenseArgs in the kernel-argument
+// segment, or an entry of a device array read in place - group_layers.hpp)
+template <bool DX, class Args>
+__device__ __forceinline__ void dense_small_body(const Args& a, float (*red)[32][33])
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int NT = a.ncols / 32;
@@ -682,7 +683,9 @@ inline int32_t dense_dw_group(hipStream_t st, const DenseDwJob* jobs, int n, int
 // k_igemm_red_group walks 2-6 row blocks with a barrier each and there are few of them; here 450-770 workgroups run 16-32 MFMAs
 // per wave.  Partials have k_igemm_red's layout ([Kp*Np] weights then [Np] bias per chunk): k_dense_reduce_adam is unchanged.
 struct DenseDwSmallGroup { DenseDwArgs a[DW_GROUP]; int first[DW_GROUP + 1]; int chunks[DW_GROUP]; int n; };
-__global__ __launch_bounds__(256) void k_dense_dw_small_group(DenseDwSmallGroup g)
+// (the body over its argument struct G: the kernel argument, or a member's entry of a device array read in place - group_layers.hpp)
+template <class G>
+__device__ __forceinline__ void dense_dw_small_group_body(const G& g)
 {
     __shared__ float red[4][32][33];
     __shared__ float bred[4][32];
@@ -691,7 +694,7 @@ __global__ __launch_bounds__(256) void k_dense_dw_small_group(DenseDwSmallGroup 
     int z = 0;
 #pragma unroll
     for (int k = 1; k < DW_GROUP; ++k) z += (k < g.n && b >= g.first[k]) ? 1 : 0;
-    const DenseDwArgs& a = g.a[z];
+    const auto& a = g.a[z];
     const int nch = g.chunks[z], local = b - g.first[z];
     const int tile = local / nch, chunk = local % nch;
     const int NT = a.Np / 32, kt = tile / NT, nt = tile % NT;
@@ -761,20 +764,27 @@ __global__ __launch_bounds__(256) void k_dense_dw_small_group(DenseDwSmallGroup 
     *reinterpret_cast<f32x4*>(part + (size_t)(kt * 32 + r) * a.Np + nt * 32 + c4) = v;
     if (kt == 0 && tid < 32) part[(size_t)a.Kp * a.Np + nt * 32 + tid] = ((bred[0][tid] + bred[1][tid]) + bred[2][tid]) + bred[3][tid];
 }
+__global__ __launch_bounds__(256) void k_dense_dw_small_group(DenseDwSmallGroup g) { dense_dw_small_group_body(g); }
+// the group of one backward pass as the launch takes it (jobs [0, n), n <= DW_GROUP); returns the workgroups
+inline int dense_dw_small_group_fill(DenseDwSmallGroup& g, const DenseDwJob* jobs, int n, int M)
+{
+    g = DenseDwSmallGroup{};
+    int first = 0;
+    for (int j = 0; j < n; ++j) {
+        const DenseDwJob& q = jobs[j];
+        g.a[j] = DenseDwArgs{q.x, q.dy, q.part, (size_t)q.l->Kp * q.l->Np + q.l->Np, M, q.l->Kp, q.l->Np, nullptr, 0, 1};
+        g.first[j] = first; g.chunks[j] = q.chunks;
+        first += (q.l->Kp / 32) * (q.l->Np / 32) * q.chunks;
+    }
+    for (int j = n; j <= DW_GROUP; ++j) g.first[j] = first;
+    g.n = n;
+    return first;
+}
 inline int32_t dense_dw_small_group(hipStream_t st, const DenseDwJob* jobs, int n, int M)
 {
     for (int j0 = 0; j0 < n; j0 += DW_GROUP) {
-        DenseDwSmallGroup g{};
-        const int nj = std::min(DW_GROUP, n - j0);
-        int first = 0;
-        for (int j = 0; j < nj; ++j) {
-            const DenseDwJob& q = jobs[j0 + j];
-            g.a[j] = DenseDwArgs{q.x, q.dy, q.part, (size_t)q.l->Kp * q.l->Np + q.l->Np, M, q.l->Kp, q.l->Np, nullptr, 0, 1};
-            g.first[j] = first; g.chunks[j] = q.chunks;
-            first += (q.l->Kp / 32) * (q.l->Np / 32) * q.chunks;
-        }
-        for (int j = nj; j <= DW_GROUP; ++j) g.first[j] = first;
-        g.n = nj;
+        DenseDwSmallGroup g;
+        const int first = dense_dw_small_group_fill(g, jobs + j0, std::min(DW_GROUP, n - j0), M);
         BDR_HIP(step_launch(st, false, k_dense_dw_small_group, dim3(first), dim3(256), g));
     }
     return BDR_OK;
@@ -791,16 +801,20 @@ struct ReduceAdamArgs {
     const unsigned* poison;   // optional: a cross-queue wait of the step timed out (queue_flags.hpp) - the inputs may be incomplete, leave everything alone
     unsigned long long* applied; unsigned long long step;   // optional: *applied = step by a pass that was not skipped (the host rolls its step counter back to it)
 };
-__global__ __launch_bounds__(256) void k_dense_reduce_adam(ReduceAdamArgs a)
+// (the body over its argument struct: the kernel argument, or a member's entry of a device array read in place - group_layers.hpp,
+// where this step's optimizer scalars and its two switches come from the member's staging slot instead of the static arguments.
+// z: the instance, s / track / grads_only: a.s[z], a.track, a.grads_only of the existing entry.  No barrier inside: a caller may
+// follow it with one, every thread returns to it.)
+template <class Args>
+__device__ __forceinline__ void dense_reduce_adam_body(const Args& a, int z, const AdamScalars& s, int track, int grads_only)
 {
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
-    const int z = blockIdx.y;
     if (i >= a.n4) return;
     if (a.poison && *a.poison) return;
-    if (a.applied && i == 0 && z == 0 && !a.grads_only) *a.applied = a.step;
+    if (a.applied && i == 0 && z == 0 && !grads_only) *a.applied = a.step;
     int k = 0;
     for (int q = 1; q < a.nseg; ++q) k += i >= a.seg[q].off4 ? 1 : 0;
-    const DenseReduceSeg sg = a.seg[k];
+    const DenseReduceSeg sg{a.seg[k].part, a.seg[k].stride, a.seg[k].chunks, a.seg[k].off4, a.seg[k].n4};
     f32x4 gg = f32x4{0.f, 0.f, 0.f, 0.f};
     if (i < sg.off4 + sg.n4) {   // (arena slack past the last layer keeps a zero gradient)
         const float* part = sg.part + (size_t)z * a.inst_part_stride + (size_t)(i - sg.off4) * 4;
@@ -815,9 +829,8 @@ __global__ __launch_bounds__(256) void k_dense_reduce_adam(ReduceAdamArgs a)
         gg = ((s4[0] + s4[1]) + s4[2]) + s4[3];
     }
     reinterpret_cast<f32x4*>(a.g[z])[i] = gg;
-    if (a.grads_only) return;
+    if (grads_only) return;
     f32x4 pp = reinterpret_cast<f32x4*>(a.p[z])[i], mm = reinterpret_cast<f32x4*>(a.m[z])[i], vv = reinterpret_cast<f32x4*>(a.v[z])[i];
-    const AdamScalars s = a.s[z];
     if (a.vmax[z]) {   // (uniform per launch row z)
         f32x4 xx = reinterpret_cast<f32x4*>(a.vmax[z])[i];
 #pragma unroll
@@ -838,13 +851,14 @@ __global__ __launch_bounds__(256) void k_dense_reduce_adam(ReduceAdamArgs a)
     reinterpret_cast<f32x4*>(a.p[z])[i] = pp;
     reinterpret_cast<f32x4*>(a.m[z])[i] = mm;
     reinterpret_cast<f32x4*>(a.v[z])[i] = vv;
-    if (a.track) {
+    if (track) {
         f32x4 d = reinterpret_cast<f32x4*>(a.tgt[z])[i];
 #pragma unroll
         for (int j = 0; j < 4; ++j) d[j] = track_element(pp[j], d[j], a.tau, a.omt);
         reinterpret_cast<f32x4*>(a.tgt[z])[i] = d;
     }
 }
+__global__ __launch_bounds__(256) void k_dense_reduce_adam(ReduceAdamArgs a) { dense_reduce_adam_body(a, (int)blockIdx.y, a.s[blockIdx.y], a.track, a.grads_only); }
 
 inline int32_t pack_rows(hipStream_t st, const float* src, int src_ld, int cols, float* dst, int ld, int col0, int B)
 {

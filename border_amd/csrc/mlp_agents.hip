@@ -8,6 +8,7 @@
 
 #include "dense.hpp"
 #include "mlp_fused.hpp"
+#include "group_layers_plan.hpp"
 
 using namespace bdr;
 
@@ -28,7 +29,10 @@ struct TdDenseArgs {
     unsigned* err;    // bdr_agent::dev_err
     int relu_out;     // MlpConfig::activation_out (mlp/base.rs:36): the Q rows are post-ReLU, dL/dz = dL/dQ * [Q > 0]
 };
-__global__ __launch_bounds__(256) void k_td_dense(TdDenseArgs a)
+// (every body below is a function over its argument struct: the existing entry runs it on its kernel argument, the entries of a
+// layer-form agent group - group_layers.hpp - on a member's entry of a device array read in place)
+template <class Args>
+__device__ __forceinline__ void td_dense_body(const Args& a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
@@ -59,9 +63,10 @@ __global__ __launch_bounds__(256) void k_td_dense(TdDenseArgs a)
     if (lane == 0) { a.pred[row] = pred; a.tgt[row] = tgt; a.loss_row[row] = lossb; if (a.td_abs) a.td_abs[row] = td; }
     for (int c = lane; c < a.ld; c += 64) a.dq_rows[(size_t)row * a.ld + c] = c == act ? dq : 0.f;
 }
+__global__ __launch_bounds__(256) void k_td_dense(TdDenseArgs a) { td_dense_body(a); }
 
 // loss = mean(loss_row): fixed-order tree
-__global__ __launch_bounds__(256) void k_mean_rows(const float* __restrict__ x, int n, float* __restrict__ out, float scale)
+__device__ __forceinline__ void mean_rows_body(const float* __restrict__ x, int n, float* __restrict__ out, float scale)
 {
     __shared__ float red[256];
     float s = 0.f;
@@ -74,6 +79,7 @@ __global__ __launch_bounds__(256) void k_mean_rows(const float* __restrict__ x, 
     }
     if (threadIdx.x == 0) out[0] = red[0] * scale;
 }
+__global__ __launch_bounds__(256) void k_mean_rows(const float* __restrict__ x, int n, float* __restrict__ out, float scale) { mean_rows_body(x, n, out, scale); }
 
 // Row-block head of the layer-by-layer step (the SAC step's sac_fused.hpp pattern): the last layer (hidden -> A actions, narrower than
 // one 32-column tile) of every network instance, the TD step of the rows (k_td_dense), the loss mean (k_mean_rows, by the last
@@ -88,7 +94,8 @@ struct MlpHeadTdArgs {
     const float* w_last; float* dh;                                      // online last-layer weights, gradient w.r.t. hin[0] [B][ldh]
     unsigned* ticket; float* loss; float scale;
 };
-__global__ __launch_bounds__(512) void k_mlp_head_td(MlpHeadTdArgs p)
+template <class Args>
+__device__ __forceinline__ void mlp_head_td_body(const Args& p)
 {
     __shared__ float red[2][4][32][33];
     __shared__ float qv[MAXZ][32][33];
@@ -100,7 +107,7 @@ __global__ __launch_bounds__(512) void k_mlp_head_td(MlpHeadTdArgs p)
     const int team = wave >> 2, w4 = wave & 3;
     const int m0 = (int)blockIdx.x * 32, c0 = (int)blockIdx.y * 64;
     const bool writer = blockIdx.y == 0;
-    const TdDenseArgs& a = p.t;
+    const auto& a = p.t;
     for (int z0 = 0; z0 < p.nz; z0 += 2) {
         const int z = z0 + team;
         if (z < p.nz) {   // team-uniform
@@ -179,16 +186,19 @@ __global__ __launch_bounds__(512) void k_mlp_head_td(MlpHeadTdArgs p)
     }
     if (tid == 0) p.loss[0] = mred[0] * p.scale;
 }
+__global__ __launch_bounds__(512) void k_mlp_head_td(MlpHeadTdArgs p) { mlp_head_td_body(p); }
 
 // [B][in_dim] f32 rows of up to MAXZ network instances into their zero-padded [B][Kp0] input matrices, one launch
 struct MlpPackArgs { const float* rows[MAXZ]; float* x[MAXZ]; int nz, B, in_dim, Kp0; };
-__global__ void k_mlp_pack_z(MlpPackArgs p)
+template <class Args>
+__device__ __forceinline__ void mlp_pack_z_body(const Args& p)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x, per = p.B * p.in_dim;
     if (t >= p.nz * per) return;
     const int z = t / per, e = t % per, b = e / p.in_dim, c = e % p.in_dim;
     p.x[z][(size_t)b * p.Kp0 + c] = p.rows[z][e];
 }
+__global__ void k_mlp_pack_z(MlpPackArgs p) { mlp_pack_z_body(p); }
 
 }  // namespace
 
@@ -287,17 +297,20 @@ struct DqnMlp : bdr_agent {
         return BDR_OK;
     }
 
-    bool fused_ok(int Bn) const
+    // what the step rules of group_layers_plan.hpp read of this agent, for a batch of Bn rows
+    GlShape gl_shape(int Bn) const
     {
-        if (!fused || net.L.size() > MF_MAXL || Bn > 128 || net.out_dim > 64) return false;
-        for (const auto& l : net.L) if (l.Kp > 256 || l.Np > 256) return false;
-        // One workgroup wins while every phase is a single pass of its eight waves over the phase's 32x32 blocks; beyond that the
-        // layer-by-layer path, which spreads a layer over the chip, is faster (tools/probes/mlp_sizes.py: Mlp[256,256] at B = 64 -
-        // the reference's own CartPole example - 4.1 k opt-steps/s in one workgroup, 11.7 k layer by layer).
-        const int nz = cfg.double_dqn ? 3 : 2, RB = (Bn + 31) / 32;
-        for (const auto& l : net.L) if (nz * RB * (l.Np / 32) > 8 || RB * (l.Kp / 32) * (l.Np / 32) > 8) return false;
-        return true;
+        GlShape s{};
+        s.in_dim = net.in_dim; s.n_layers = (int)net.L.size();
+        for (int i = 0; i < s.n_layers && i < GL_SHAPE_LAYERS; ++i) { s.Kp[i] = net.L[i].Kp; s.Np[i] = net.L[i].Np; }
+        s.out_dim = net.out_dim; s.batch = Bn; s.double_dqn = cfg.double_dqn ? 1 : 0; s.activation_out = net.L.back().relu;
+        s.fused = fused; s.small_gemm = small_gemm; s.head_fuse = head_fuse; s.head_fuse_wide = head_fuse_wide;
+        return s;
     }
+    // One workgroup wins while every phase is a single pass of its eight waves over the phase's 32x32 blocks; beyond that the
+    // layer-by-layer path, which spreads a layer over the chip, is faster (tools/probes/mlp_sizes.py: Mlp[256,256] at B = 64 -
+    // the reference's own CartPole example - 4.1 k opt-steps/s in one workgroup, 11.7 k layer by layer).  The rule: gl_fused_ok.
+    bool fused_ok(int Bn) const { return gl_fused_ok(gl_shape(Bn)); }
     // ---- the one-launch step (mlp_fused.hpp) in three parts, so that a group (DqnGroup below) can fill every member's arguments and
     // launch once: fused_static = everything that changes only when buffers are reallocated; fused_step_advance = this step's words,
     // advancing the host state (adam_step, track_with_next / track_done); the launch.

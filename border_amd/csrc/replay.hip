@@ -87,12 +87,14 @@ __global__ void k_xo_indices(uint64_t* __restrict__ st, uint64_t size, uint32_t 
 // ------------------------------------------------------------------------------------------------
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-template <typename V>
-__global__ __launch_bounds__(256) void k_gather(GatherArgs a)
+// (the body as a function over its arguments: k_gather runs it on its kernel argument, k_gather_group on a member's entry of a device
+// array with the stream position and ring size of this step from the member's staging slot)
+template <typename V, class Args>
+__device__ __forceinline__ void gather_body(const Args& a, const ChaChaKey& key, uint64_t word_pos, uint64_t size)
 {
     const uint32_t sample = blockIdx.x / a.chunks, chunk = blockIdx.x % a.chunks;
     // ixs[k] = (StdRng::next_u32() as usize) % size   (base.rs:386): word k of this batch's key stream
-    const uint64_t row = a.given ? a.ixs[sample] : (uint64_t)chacha12_word(a.key, a.word_pos + sample) % a.size;
+    const uint64_t row = a.given ? a.ixs[sample] : (uint64_t)chacha12_word(key, word_pos + sample) % size;
     if (!a.given && chunk == 0 && threadIdx.x == 0) a.ixs[sample] = row;
     const uint8_t* rec = a.ring + row * a.stride;
     const uint64_t nvec = a.obs_bytes / sizeof(V);
@@ -136,6 +138,24 @@ __global__ __launch_bounds__(256) void k_gather(GatherArgs a)
             a.b_act[(uint64_t)sample * a.act_bytes + t] = rec[a.act_off + t];
         if (threadIdx.x == 0) { a.b_reward[sample] = t_rew; a.b_term[sample] = t_term; a.b_trunc[sample] = t_trunc; }
     }
+}
+template <typename V>
+__global__ __launch_bounds__(256) void k_gather(GatherArgs a)
+{
+    gather_body<V>(a, a.key, a.word_pos, a.size);
+}
+// The gather of every member of a layer-form agent group (group_layers.hpp) in one launch: grid (n * chunks, P), member = blockIdx.y.
+// The member's static descriptor is read in place from a device array through the constant address space (blockIdx.y is uniform:
+// scalar loads); word_pos and size of this step come from the member's entry of a pinned staging slot (`words` + member * stride).
+template <typename V>
+__global__ __launch_bounds__(256) void k_gather_group(const BDR_CONST_AS GatherArgs* args, const BDR_CONST_AS uint8_t* words, uint32_t word_stride)
+{
+    const BDR_CONST_AS GatherArgs& a = args[blockIdx.y];
+    const BDR_CONST_AS GatherStepWords& w = *reinterpret_cast<const BDR_CONST_AS GatherStepWords*>(words + (size_t)blockIdx.y * word_stride);
+    ChaChaKey key;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) key.k[i] = a.key.k[i];
+    gather_body<V>(a, key, w.word_pos, w.size);
 }
 
 // K2 for the single-frame store: the record of a sampled transition names 2k frame slots; workgroup (sample, half) copies the
@@ -1363,6 +1383,18 @@ int32_t replay_prepare_sample(bdr_replay* r, uint64_t n, hipStream_t stream)
     return BDR_OK;
 }
 
+// k_gather's workgroups per sample and vectors (16 bytes, or 4 when the row is no multiple of 16) per workgroup for rows of obs_bytes
+void replay_gather_shape(uint64_t obs_bytes, uint32_t* chunks, uint32_t* vec_per_chunk)
+{
+    const bool v16 = obs_bytes % 16 == 0;
+    const uint64_t nvec = obs_bytes / (v16 ? 16 : 4);
+    // up to 4 vectors per thread per section and pass: 2 workgroups per sample for Atari rows (1764 vectors)
+    uint32_t c = (uint32_t)std::max<uint64_t>(1, (nvec + 1023) / 1024);
+    if (v16) { static const int forced = getenv("BDR_GATHER_CHUNKS") ? atoi(getenv("BDR_GATHER_CHUNKS")) : 0; if (forced > 0) c = (uint32_t)forced; }   // diagnostics
+    *chunks = c;
+    *vec_per_chunk = (uint32_t)((nvec + c - 1) / c);
+}
+
 int32_t replay_sample_on_stream(bdr_replay* r, uint64_t n, hipStream_t stream)
 {
     BDR_TRY(replay_prepare_sample(r, n, stream));
@@ -1389,16 +1421,10 @@ int32_t replay_sample_on_stream(bdr_replay* r, uint64_t n, hipStream_t stream)
         g.given = a.given;
         BDR_HIP(step_launch(stream, true, k_gather_frames, dim3((uint32_t)(n * 2)), dim3(256), g));
     } else if (r->obs_bytes % 16 == 0) {
-        const uint64_t nvec = r->obs_bytes / 16;
-        // up to 4 vectors per thread per section and pass: 2 workgroups per sample for Atari rows (1764 vectors)
-        a.chunks = (uint32_t)std::max<uint64_t>(1, (nvec + 1023) / 1024);
-        { static const int forced = getenv("BDR_GATHER_CHUNKS") ? atoi(getenv("BDR_GATHER_CHUNKS")) : 0; if (forced > 0) a.chunks = (uint32_t)forced; }   // diagnostics
-        a.vec_per_chunk = (uint32_t)((nvec + a.chunks - 1) / a.chunks);
+        replay_gather_shape(r->obs_bytes, &a.chunks, &a.vec_per_chunk);
         BDR_HIP(step_launch(stream, true, k_gather<u32x4>, dim3((uint32_t)(n * a.chunks)), dim3(256), a));
     } else {
-        const uint64_t nvec = r->obs_bytes / 4;
-        a.chunks = (uint32_t)std::max<uint64_t>(1, (nvec + 1023) / 1024);
-        a.vec_per_chunk = (uint32_t)((nvec + a.chunks - 1) / a.chunks);
+        replay_gather_shape(r->obs_bytes, &a.chunks, &a.vec_per_chunk);
         BDR_HIP(step_launch(stream, true, k_gather<uint32_t>, dim3((uint32_t)(n * a.chunks)), dim3(256), a));
     }
     r->read_pending = true; r->read_stream = stream;   // recorded only if somebody has to wait for it (wait_for_reader)
@@ -1424,6 +1450,22 @@ int32_t replay_sample_plan(bdr_replay* r, uint64_t n, hipStream_t stream, Gather
     r->read_pending = true; r->read_stream = stream;
     r->batch_n = n;
     *out = a;
+    return BDR_OK;
+}
+
+// One launch for the plans of P members (replay_sample_plan each; rows of one width): d_args[P] on the device, `words` the device address
+// of the members' step words in a pinned slot (GatherStepWords at the start of every `word_stride` bytes).  The same chunking as
+// replay_sample_on_stream, so every member's rows are copied by the workgroups that copy them standalone.
+int32_t replay_gather_group(hipStream_t stream, const GatherArgs* d_args, const void* words, uint32_t word_stride, uint32_t P, uint64_t n, uint64_t obs_bytes)
+{
+    BDR_REQUIRE(P >= 1 && P <= 65535 && n >= 1 && n < (1ull << 24), "grouped gather: %u members, %llu rows", P, (unsigned long long)n);
+    const auto* a = (const BDR_CONST_AS GatherArgs*)d_args;
+    const auto* w = (const BDR_CONST_AS uint8_t*)words;
+    uint32_t chunks = 1, vec_per_chunk = 0;
+    replay_gather_shape(obs_bytes, &chunks, &vec_per_chunk);   // (every d_args[p] carries these two: replay_gather_shape of the same width)
+    if (obs_bytes % 16 == 0) hipLaunchKernelGGL(k_gather_group<u32x4>, dim3((uint32_t)(n * chunks), P), dim3(256), 0, stream, a, w, word_stride);
+    else hipLaunchKernelGGL(k_gather_group<uint32_t>, dim3((uint32_t)(n * chunks), P), dim3(256), 0, stream, a, w, word_stride);
+    BDR_HIP(hipGetLastError());
     return BDR_OK;
 }
 

@@ -1,5 +1,7 @@
 """DqnGroup: a set of small Mlp DQN agents whose Agent::opt runs as ONE launch, one workgroup per member (bdr_agent_group_*); so do
 acting (`sample`) and pushing one transition per member (`push`), and `train` drives the three from a compiled online loop.
+Members of one shape beyond the one-workgroup step (Mlp[256, 256] at batch 64, the reference's dqn_cartpole) form a group too: its
+update round is the layer path's launch sequence of one member, each launch serving all members (`form`, `launches_per_round`).
 
 A launch grouping, not an agent kind: the members are ordinary `Dqn` objects (every `Dqn` method keeps working on a member and
 means what it meant) that the group owns - `DqnGroup.close()` closes them, `member.close()` on a live group is refused.  Results
@@ -29,7 +31,8 @@ class DqnGroup:
     PUSH_STAGING_DEPTH = 8   # slots of the push staging ring (bdr_agent_group::PUSH_SLOTS)
 
     def __init__(self, agents, prioritized: bool = False):
-        """Adopts already built `Dqn` agents (they must be Mlp agents that take the one-workgroup step; see bdr_agent_group_create).
+        """Adopts already built `Dqn` agents: Mlp agents that all take the one-workgroup step, or - the layer form - that all have one
+        shape beyond it (at most 4 layers up to 256 wide; see bdr_agent_group_create and `form`).
         `prioritized=True`: opt / opt_with_record / push / train also accept buffers built with a `PerConfig`
         (bdr_agent_group_set_prioritized); by default a prioritized buffer is refused."""
         agents = list(agents)
@@ -73,6 +76,30 @@ class DqnGroup:
     def __len__(self):
         return len(self._members)
 
+    def info(self) -> dict:
+        """bdr_agent_group_info: {"form": "one_workgroup" | "layers", "n_members", "launches_per_round", "kernel_launches"}."""
+        i = _lib.GroupInfoC()
+        _lib.check(_lib.lib().bdr_agent_group_info(self._g, C.byref(i)))
+        return {"form": "layers" if i.form == _lib.GROUP_FORM_LAYERS else "one_workgroup", "n_members": i.n_members,
+                "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
+
+    @property
+    def form(self) -> str:
+        """"one_workgroup": every member takes the one-workgroup step, one launch per update round.  "layers": members of one shape
+        beyond it (Mlp[256, 256] at batch 64 and every net down to Mlp[64, 64] past batch 64) on the layer path's launch sequence of
+        one member, each launch serving all of them."""
+        return self.info()["form"]
+
+    @property
+    def launches_per_round(self) -> int:
+        """kernel launches of one update round on uniform rings, whatever the number of members"""
+        return self.info()["launches_per_round"]
+
+    @property
+    def kernel_launches(self) -> int:
+        """kernel launches the group's own calls have enqueued since it was built"""
+        return self.info()["kernel_launches"]
+
     @property
     def prioritized(self) -> bool:
         return self._prioritized
@@ -99,7 +126,8 @@ class DqnGroup:
         return self._bound
 
     def opt(self, buffers=None) -> None:
-        """Agent::opt of every member on its own buffer: n_updates_per_opt launches in all; does not synchronise.
+        """Agent::opt of every member on its own buffer: n_updates_per_opt * launches_per_round launches in all (one per round in the
+        one-workgroup form); does not synchronise.
         `buffers=None`: the buffers of the last opt / opt_with_record call (they must still be open)."""
         _lib.check(_lib.lib().bdr_agent_group_opt(self._g, self._buffers(buffers)))
 

@@ -476,6 +476,27 @@ BDR_API int32_t bdr_agent_group_create(bdr_agent* const* agents, uint32_t n, bdr
 BDR_API int32_t bdr_agent_group_destroy(bdr_agent_group* g);
 BDR_API int32_t bdr_agent_group_size(const bdr_agent_group* g, uint32_t* n);
 BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr_agent** out);
+/* The two forms of a group.  bdr_agent_group_create takes the form of member 0:
+ *   BDR_GROUP_FORM_ONE_WORKGROUP  every member takes the one-workgroup step (the rules above): one launch per update round;
+ *   BDR_GROUP_FORM_LAYERS         NO member takes it and every member steps on the latency-shaped layer path (Mlp[256, 256] at batch
+ *                                 64 - the reference's dqn_cartpole - and every net between it and Mlp[64, 64]): one update round is
+ *                                 the launch sequence Dqn::update_critic (dqn/base.rs:60-160) takes for ONE such member - gather, pack,
+ *                                 the forward layers, TD + loss, the input gradients, the grouped weight gradient, reduce + Adam with
+ *                                 the soft update - each launch serving all members (11 launches for dqn_cartpole, whatever n is).
+ * Layer form, further conditions (otherwise BDR_ERR_INVALID naming the member and the reason, before anybody is adopted): no layer
+ * wider than 256 (padded), at most 4 layers, the layer path switched on (no BDR_NO_SMALL_GEMM), no amsgrad, no gradient
+ * communicator, profiling off, one n_updates_per_opt, and ONE shape for all members: in_dim, units, out_dim, activation_out,
+ * batch_size, double_dqn.  Optimizer and its scalars, loss, clip_td_err, gamma, tau, soft_update_interval and the seeds may differ.
+ * A group mixing the two forms is refused, naming the first member whose form differs from member 0's.  Prioritized rings under a
+ * layer-form group are refused: bdr_agent_group_set_prioritized(g, 1) on it, and a prioritized buffer handed to _opt / _push.
+ * Every result is bit for bit what bdr_agent_opt on the same agents standalone gives, in both forms.
+ * bdr_agent_group_info (no trait method: the launch grouping is this library's, Agent::opt - border-core/src/base/agent.rs:62-64 - is
+ * what it groups): the form, the kernel launches one update round enqueues on uniform rings, and a running count of the kernel
+ * launches the group's own calls (opt, push, sample, qvalues, evaluate, the compiled loop) have enqueued since it was created. */
+#define BDR_GROUP_FORM_ONE_WORKGROUP 0
+#define BDR_GROUP_FORM_LAYERS 1
+typedef struct { int32_t form; uint32_t n_members; uint32_t launches_per_round; uint32_t reserved; uint64_t kernel_launches; } bdr_group_info;
+BDR_API int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out);
 /* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
  * switched on steps and feeds rings with bdr_replay_enable_per: every prioritized member's SumTree::sample, importance weights and
  * row gather are one launch for all of them ahead of the step, update_priority one launch behind it, and set_priority of a grouped

@@ -95,6 +95,8 @@ pub const BDR_EXPLORER_SOFTMAX: i32 = 0;
 pub const BDR_EXPLORER_EPS_GREEDY: i32 = 1;
 pub const BDR_CKPT_TCH: i32 = 0;
 pub const BDR_CKPT_SAFETENSORS: i32 = 1;
+pub const BDR_GROUP_FORM_ONE_WORKGROUP: i32 = 0;
+pub const BDR_GROUP_FORM_LAYERS: i32 = 1;
 pub const BDR_IQN_CONST10: i32 = 0;
 pub const BDR_IQN_CONST32: i32 = 1;
 pub const BDR_IQN_UNIFORM10: i32 = 2;
@@ -192,6 +194,16 @@ pub struct bdr_per_config {
     pub n_opts_final: u64,
     pub normalize: i32,
     pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bdr_group_info {
+    pub form: i32,
+    pub n_members: u32,
+    pub launches_per_round: u32,
+    pub reserved: u32,
+    pub kernel_launches: u64,
 }
 
 #[repr(C)]
@@ -979,6 +991,7 @@ extern "C" {
     pub fn bdr_agent_group_destroy(g: *mut bdr_agent_group) -> i32;
     pub fn bdr_agent_group_size(g: *const bdr_agent_group, n: *mut u32) -> i32;
     pub fn bdr_agent_group_member(g: *const bdr_agent_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_agent_group_info(g: *const bdr_agent_group, out: *mut bdr_group_info) -> i32;
     pub fn bdr_agent_group_set_prioritized(g: *mut bdr_agent_group, on: i32) -> i32;
     pub fn bdr_agent_group_opt(g: *mut bdr_agent_group, buffers: *mut *const bdr_replay) -> i32;
     pub fn bdr_agent_group_opt_with_scalars(g: *mut bdr_agent_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;

@@ -83,6 +83,17 @@ where
         &mut self.members[i]
     }
 
+    /// The group's form and launch counts (`bdr_agent_group_info`): `form` is `ffi::BDR_GROUP_FORM_ONE_WORKGROUP` (every member takes
+    /// the one-workgroup step: one launch per update round) or `ffi::BDR_GROUP_FORM_LAYERS` (members of one shape beyond it, such
+    /// as Mlp[256, 256] at batch 64: the layer path's launch sequence of one member, each launch serving all members);
+    /// `launches_per_round` the kernel launches of one update round on uniform rings, `kernel_launches` those the group's own
+    /// calls have enqueued since it was created.
+    pub fn info(&self) -> Result<ffi::bdr_group_info> {
+        let mut out = ffi::bdr_group_info::default();
+        check(unsafe { ffi::bdr_agent_group_info(self.g, &mut out) })?;
+        Ok(out)
+    }
+
     /// Prioritized replay under the group (`bdr_agent_group_set_prioritized`): switched on, `opt`, `opt_with_record`, `push` and
     /// `train` accept buffers built with a `PerConfig` - sampling, importance weights and `update_priority` of all prioritized
     /// members run as a fixed number of launches per round, bit for bit what the members' own calls give.  Off (the default), a

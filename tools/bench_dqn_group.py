@@ -22,6 +22,11 @@ episodes of a fixed length, n_episodes = 4, five alternating legs of 0.3 s per s
   eval    group.evaluate (one acting launch per round) against Evaluator.evaluate(member) for each member of the same group, one
           after the other, member-evaluations/s; the same bar for P >= 8, P = 1 reported without one
   subset  group.sample(members=[0]) against group.sample() of all at P = 64 and 256, us per call (reported, no bar)
+--wide measures the layer form of a group (default profiles/bench_dqn_group_wide.json): the reference's dqn_cartpole shape - Mlp[256, 256],
+in 4, 2 actions, batch 64, Adam - on full uniform rings of 10 000, same protocol:
+  opt    group.opt (11 launches per round whatever P is) against a loop of Agent::opt over the same P agents standalone in their default
+         configuration (graph replay included), member-updates/s, the ratio, worst grouped leg over best loop leg, us per group round;
+         the bar at P = 8 and 64, P = 1 and 256 reported without one
 --sample-full prints one line with the us per call of group.sample of all members at P = 64 (three runs of this commit and of the
 parent alternating show that the default path did not move); it writes no file."""
 import argparse
@@ -262,8 +267,59 @@ def prioritized(args, rows):
     return doc
 
 
+def wide_cfg(seed):
+    return B.DqnConfig(model_config=B.DqnModelConfig(q_config=B.MlpConfig(in_dim=4, units=(256, 256), out_dim=2), opt_config=B.OptimizerConfig.Adam(1e-3)),
+                       soft_update_interval=1, batch_size=64, tau=0.01, critic_loss="Mse", discount_factor=0.99, device=0, param_seed=seed, train=True)
+
+
+def full_ring(seed, rows):
+    rb = B.SimpleReplayBuffer(B.SimpleReplayBufferConfig(capacity=10000, seed=seed), (4,), np.float32)
+    rb.push(*rows); rb.push(*rows)
+    return rb
+
+
+def source_stamp():
+    """the hash bench.py ties committed measurements to (kernel sources + the header), so a stale profile can be told from a current one"""
+    import bench
+    return {"kernel_source_sha16": bench.kernel_source_hash()}
+
+
+def wide(args, rows):
+    doc = {"bench": "dqn_group_wide", "_source": source_stamp(),
+           "shape": "dqn_cartpole: Mlp[256,256] in 4 A 2, batch 64, Adam 1e-3, full uniform rings 10000 / 10000", "window_steps": args.window,
+           "legs": args.legs, "leg_seconds": args.leg_seconds, "unit_opt": "member-updates/s (median of the legs)",
+           "sides": "group.opt of a layer-form DqnGroup against a loop of Agent::opt over the same P agents standalone, default configuration (graph replay included), one process",
+           "bar": "at P = 8 and 64: group_min - loop_max > max(group_max - group_min, loop_max - loop_min); P = 1 and 256 are reported without a bar",
+           "opt": {}}
+    for P in [int(x) for x in args.sizes.split(",")]:
+        g = B.DqnGroup.build([wide_cfg(i) for i in range(P)])
+        assert g.form == "layers"
+        doc["launches_per_round"] = g.launches_per_round
+        g_rings = [full_ring(100 + i, rows) for i in range(P)]
+        solo = [B.Dqn.build(wide_cfg(i)) for i in range(P)]
+        s_rings = [full_ring(100 + i, rows) for i in range(P)]
+        g.opt(g_rings)
+
+        def loop_opt():
+            for a, r in zip(solo, s_rings): a.opt(r)
+
+        def loop_sync():
+            for a in solo: a.sync()
+
+        m = measure(g.opt, g.sync, loop_opt, loop_sync, P, args.window, args.legs, args.leg_seconds)
+        (g0, g1), (l0, l1) = m["group_min_max"], m["loop_min_max"]
+        m["bar_met"] = bool(g0 - l1 > max(g1 - g0, l1 - l0)) if P in (8, 64) else None
+        doc["opt"][str(P)] = m
+        print(P, "opt", m, flush=True)
+        g.close()
+        for a in solo: a.close()
+        for r in g_rings + s_rings: r.close()
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--wide", action="store_true", help="measure the layer form: dqn_cartpole (Mlp[256, 256], batch 64) group opt against a loop of Agent::opt")
     ap.add_argument("--eval", action="store_true", help="measure the lockstep evaluator against a loop of Evaluator.evaluate, and the subset launch")
     ap.add_argument("--sample-full", action="store_true", help="print the us per call of group.sample of all members at P = 64 and exit")
     ap.add_argument("--per", action="store_true", help="measure prioritized rings under a group: opt and the online iteration")
@@ -274,11 +330,11 @@ def main():
     ap.add_argument("--leg-seconds", type=float, default=0.3)
     ap.add_argument("--out", default=None, help="default: profiles/bench_dqn_group.json, with --online profiles/bench_dqn_group_online.json, "
                                                 "with --per profiles/bench_dqn_group_per.json, "
-                                                "with --eval profiles/bench_dqn_group_eval.json")
+                                                "with --eval profiles/bench_dqn_group_eval.json, with --wide profiles/bench_dqn_group_wide.json")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
-                                "bench_dqn_group_eval.json" if args.eval else "bench_dqn_group_per.json" if args.per else "bench_dqn_group_online.json" if args.online else "bench_dqn_group.json")
+                                "bench_dqn_group_wide.json" if args.wide else "bench_dqn_group_eval.json" if args.eval else "bench_dqn_group_per.json" if args.per else "bench_dqn_group_online.json" if args.online else "bench_dqn_group.json")
     rng = np.random.default_rng(0)
     n = 5000
     rows = (rng.standard_normal((n, 4)).astype(np.float32), rng.integers(0, 2, (n, 1)).astype(np.int64),
@@ -288,13 +344,15 @@ def main():
            "opt": {}, "sample": {}}
     if args.sample_full:
         return sample_full(args, rows)
-    if args.eval:
+    if args.wide:
+        doc = wide(args, rows)
+    elif args.eval:
         doc = evaluation(args, rows)
     elif args.per:
         doc = prioritized(args, rows)
     elif args.online:
         doc = online(args, rows)
-    for P in [] if args.online or args.per or args.eval else [int(x) for x in args.sizes.split(",")]:
+    for P in [] if args.online or args.per or args.eval or args.wide else [int(x) for x in args.sizes.split(",")]:
         g = B.DqnGroup.build([c1(i) for i in range(P)])
         g_rings = [ring(100 + i, rows) for i in range(P)]
         solo = [B.Dqn.build(c1(i)) for i in range(P)]
