@@ -307,7 +307,7 @@ ABI_SYMBOLS = [
     "bdr_explorer_config_default", "bdr_agent_set_explorer", "bdr_agent_get_explorer", "bdr_agent_sample", "bdr_agent_sample_device", "bdr_agent_qvalues_device",
     "bdr_agent_sync", "bdr_agent_n_opts", "bdr_agent_param_count", "bdr_agent_get_params",
     "bdr_agent_set_params", "bdr_agent_arena_device_ptr", "bdr_agent_arena_release", "bdr_agent_save_params", "bdr_agent_load_params", "bdr_agent_set_checkpoint_format",
-    "bdr_checkpoint_write", "bdr_checkpoint_read", "bdr_dqn_probe",
+    "bdr_checkpoint_write", "bdr_checkpoint_read", "bdr_dqn_probe", "bdr_dqn_mlp_layer_probe",
     "bdr_agent_profile_enable", "bdr_agent_profile_read",
     "bdr_iqn_config_default", "bdr_iqn_create", "bdr_iqn_update_on_batch", "bdr_iqn_forward", "bdr_iqn_qvalues", "bdr_iqn_probe",
     "bdr_sac_config_default", "bdr_sac_create", "bdr_sac_update_on_batch", "bdr_sac_sample", "bdr_sac_sample_device",
@@ -437,6 +437,7 @@ def lib() -> C.CDLL:
     L.bdr_agent_save_params.argtypes = [vp, C.c_char_p]
     L.bdr_agent_load_params.argtypes = [vp, C.c_char_p]
     L.bdr_dqn_probe.argtypes = [vp, i32, vp, u64]
+    L.bdr_dqn_mlp_layer_probe.argtypes = [vp, i32, i32, i32, vp, u64]
     L.bdr_agent_profile_enable.argtypes = [vp, i32]
     L.bdr_agent_profile_read.argtypes = [vp, vp, u64, vp, C.POINTER(u64)]
     L.bdr_iqn_config_default.argtypes = [C.POINTER(IqnConfigC)]

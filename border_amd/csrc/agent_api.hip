@@ -24,6 +24,7 @@ int32_t dqn_cnn_qvalues(bdr_agent* a, uint64_t n, const void* obs, float* q_out)
 int32_t dqn_mlp_qvalues(bdr_agent* a, uint64_t n, const void* obs, float* q_out);
 int32_t dqn_cnn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
 int32_t dqn_mlp_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+int32_t dqn_mlp_layer_probe(bdr_agent* a, int32_t buf, int32_t z, int32_t layer, float* out, uint64_t n);
 
 // Checkpoint containers, chosen by the file name exactly as tch's VarStore::save / load choose:
 //  * "*.safetensors": 8-byte little-endian header length, JSON header
@@ -789,6 +790,15 @@ int32_t bdr_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n)
     BDR_REQUIRE(is_dqn(a), "not a DQN agent");
     BDR_HIP(hipSetDevice(a->device));
     return !strcmp(a->kind(), "dqn_cnn") ? dqn_cnn_probe(a, what, out, n) : dqn_mlp_probe(a, what, out, n);
+}
+
+// Layer probes of the Mlp DQN agent (see include/border_amd.h): one raw buffer of the last update to the host
+int32_t bdr_dqn_mlp_layer_probe(bdr_agent* a, int32_t buf, int32_t z, int32_t layer, float* out, uint64_t n)
+{
+    BDR_REQUIRE(a && out, "null argument");
+    BDR_REQUIRE(!strcmp(a->kind(), "dqn_mlp"), "not an Mlp DQN agent");
+    BDR_HIP(hipSetDevice(a->device));
+    return dqn_mlp_layer_probe(a, buf, z, layer, out, n);
 }
 
 int32_t bdr_agent_set_act_path(bdr_agent* a, int32_t path)

@@ -316,6 +316,7 @@ int32_t group_round(bdr_agent_group* g, bdr_replay* const* buffers, bool last_ro
     size_t lds = 0;
     bool all_lds = true;
     for (uint32_t p = 0; p < P; ++p) { all_lds = all_lds && g->lds_bytes[p] != 0; lds = std::max(lds, g->lds_bytes[p]); }
+    for (uint32_t p = 0; p < P; ++p) { g->members[p]->probe_form = all_lds ? BDR_DQN_MLP_FORM_LDS : BDR_DQN_MLP_FORM_GLOBAL; g->members[p]->probe_chunks = 0; }   // bdr_dqn_mlp_layer_probe
     const auto* args = (const MF_CONST_AS MlpFusedArgs*)g->d_args.get();
     const auto* st = (const MF_CONST_AS MfStep*)(g->steps.dev + (size_t)step_slot.slot * P);
     if (all_lds) {
@@ -367,6 +368,8 @@ int32_t group_round_layers(bdr_agent_group* g, bdr_replay* const* buffers, bool 
         m->last_reward = r->b_reward; m->last_B = bs;
         m->defer_adam = false;
         m->head_fused = gl.head != 0;
+        m->probe_form = gl.head ? BDR_DQN_MLP_FORM_LAYERS_HEAD : BDR_DQN_MLP_FORM_LAYERS_TD;   // bdr_dqn_mlp_layer_probe
+        m->probe_chunks = std::min(m->dw_chunks_l[0], std::max(1, bs / 256));
         m->track_with_next = last_round && m->soft_update_counter + 1 == m->cfg.soft_update_interval;
         bdr_agent_group::StaticKey& key = g->keys[p];
         if (!key.valid || key.batch_gen != m->batch_gen || key.td_abs != m->td_abs || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {

@@ -171,7 +171,9 @@ __device__ __forceinline__ void mlp_head_td_body(const Args& p)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int e = tid + 512 * u, r = e >> 6, k = c0 + (e & 63);
-            if (m0 + r < a.B) p.dh[(size_t)(m0 + r) * p.ldh + k] = hv[u] > 0.f ? s_dq[r] * wv[u] : 0.f;
+            // (+ 0.f: a row whose dq is 0 - a clamped Q under activation_out - gives +0 for a negative weight too, as the dX launch's
+            //  accumulation from +0 does: the two forms leave the same bits, signs of zeros included)
+            if (m0 + r < a.B) p.dh[(size_t)(m0 + r) * p.ldh + k] = hv[u] > 0.f ? s_dq[r] * wv[u] + 0.f : 0.f;
         }
     }
     if (!last_workgroup(p.ticket, gridDim.x * gridDim.y, &s_last)) return;
@@ -228,6 +230,7 @@ struct DqnMlp : bdr_agent {
     float* dw_part = nullptr; std::vector<size_t> dw_off; std::vector<int> dw_chunks_l;   // row-chunk partials of the grouped dW launch
     bool fused = true;         // one-workgroup step for nets that fit a CU (mlp_fused.hpp; BDR_NO_MLP_FUSED=1: generic path)
     bool track_with_next = false, track_done = false;   // opt(): the soft update rides on the fused kernel of the last update
+    int probe_form = -1, probe_chunks = 0;   // bdr_dqn_mlp_layer_probe: the step the last update took (BDR_DQN_MLP_FORM_*, -1: none yet), its dW row chunks (0: no partials)
 
     ~DqnMlp() override
     {
@@ -260,7 +263,10 @@ struct DqnMlp : bdr_agent {
             for (const auto& l : net.L) {
                 float* p = nullptr;
                 BDR_TRY(alloc_f(&p, (size_t)Bn * l.Np));
+                // the row-block head (k_mlp_head_td) stores the 32 columns of its one tile: the Q rows' padding columns 32..63 are
+                // zeros from here on, as every other form writes them (probes read whole rows)
                 acts[z].push_back(p);
+                BDR_HIP(hipMemsetAsync(p, 0, (size_t)Bn * l.Np * 4, stream));
             }
         }
         for (const auto& l : net.L) {
@@ -360,6 +366,7 @@ struct DqnMlp : bdr_agent {
         const size_t lds_bytes = fused_static(f, Bn, obs, next_obs, act, act_bytes, reward, term, weight, gather);
         const MfStep d = fused_step_advance(gather);
         f.g.word_pos = d.word_pos; f.g.size = d.size; f.adam = d.adam; f.do_adam = d.do_adam; f.do_track = d.do_track;
+        probe_form = lds_bytes ? BDR_DQN_MLP_FORM_LDS : BDR_DQN_MLP_FORM_GLOBAL; probe_chunks = 0;
         Bracket br(this, "mlp_step");
         if (lds_bytes) {   // activations and gradients resident in LDS (mlp_fused.hpp)
             if (lds_bytes > lds_attr) {
@@ -425,6 +432,8 @@ struct DqnMlp : bdr_agent {
         t.weight = weight; t.td_abs = td_abs;
         t.has_clip = cfg.has_clip_td_err; t.clip_min = (float)cfg.clip_td_err_min; t.clip_max = (float)cfg.clip_td_err_max;
         t.err = dev_err; t.relu_out = net.L[L - 1].relu;
+        probe_form = !lat ? BDR_DQN_MLP_FORM_TILES : head_fused ? BDR_DQN_MLP_FORM_LAYERS_HEAD : BDR_DQN_MLP_FORM_LAYERS_TD;
+        probe_chunks = lat ? std::min(dw_chunks_l[0], std::max(1, Bn / 256)) : 0;
         if (lat && head_fused) {
             const DenseLayer& ll = net.L[L - 1];
             const int nz = cfg.double_dqn ? 3 : 2;
@@ -716,8 +725,10 @@ int32_t dqn_mlp_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
     DqnMlp* a = static_cast<DqnMlp*>(base);
     const int L = (int)a->net.L.size(), ld = a->net.L[L - 1].Np, A = a->net.out_dim;
     BDR_HIP(hipStreamSynchronize(a->stream));
+    // (nothing is read past the rows the batch buffers were allocated for)
     if (what == 0 || what == 1) {   // [B][A] from the padded rows
         const uint64_t rows = n / A;
+        BDR_REQUIRE(rows <= (uint64_t)a->B, "probe %d: %llu rows asked, the batch buffers hold %d", what, (unsigned long long)rows, a->B);
         std::vector<float> tmp(rows * ld);
         BDR_HIP(hipMemcpy(tmp.data(), a->acts[what][L - 1], tmp.size() * 4, hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < rows; ++i) for (int k = 0; k < A; ++k) out[i * A + k] = tmp[i * ld + k];
@@ -725,6 +736,59 @@ int32_t dqn_mlp_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
     }
     const float* src = what == 2 ? a->pred : what == 3 ? a->tgt : what == 4 ? a->loss : nullptr;
     BDR_REQUIRE(src, "unknown probe %d", what);
+    BDR_REQUIRE(n <= (what == 4 ? (uint64_t)1 : (uint64_t)a->B), "probe %d: %llu floats asked, the buffer holds %d", what, (unsigned long long)n, what == 4 ? 1 : a->B);
+    BDR_HIP(hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost));
+    return BDR_OK;
+}
+
+// bdr_dqn_mlp_layer_probe: the raw buffer, rows of the last update x padded leading dimension.  Every argument is checked before the
+// stream is touched; the copy is the only thing enqueued, and only here - update_critic and opt record two integers, nothing more.
+int32_t dqn_mlp_layer_probe(bdr_agent* base, int32_t buf, int32_t z, int32_t l, float* out, uint64_t n)
+{
+    DqnMlp* a = static_cast<DqnMlp*>(base);
+    BDR_REQUIRE(a->probe_form >= 0 && a->last_B > 0 && a->last_B <= a->B, "nothing to probe yet (no update has run)");
+    const int L = (int)a->net.L.size(), nz = a->cfg.double_dqn ? 3 : 2;
+    const size_t R = (size_t)a->last_B;
+    auto need = [&](bool ok) -> int32_t { BDR_REQUIRE(ok, "Mlp DQN probe buffer %d: instance %d / layer %d out of range", buf, z, l); return BDR_OK; };
+    auto no_index = [&]() { return need(z == 0 && l == 0); };
+    const float* src = nullptr; size_t want = 0;
+    switch (buf) {
+        case BDR_DQN_MLP_BUF_X_IN: BDR_TRY(need(z >= 0 && z < nz && l == 0)); src = a->x_in[z]; want = R * a->net.L[0].Kp; break;
+        case BDR_DQN_MLP_BUF_ACT: BDR_TRY(need(z >= 0 && z < nz && l >= 0 && l < L)); src = a->acts[z][l]; want = R * a->net.L[l].Np; break;
+        case BDR_DQN_MLP_BUF_DY: BDR_TRY(need(z == 0 && l >= 0 && l < L)); src = a->dys[l]; want = R * a->net.L[l].Np; break;
+        case BDR_DQN_MLP_BUF_PRED: BDR_TRY(no_index()); src = a->pred; want = R; break;
+        case BDR_DQN_MLP_BUF_TGT: BDR_TRY(no_index()); src = a->tgt; want = R; break;
+        case BDR_DQN_MLP_BUF_LOSS_ROW: BDR_TRY(no_index()); src = a->loss_row; want = R; break;
+        case BDR_DQN_MLP_BUF_TD_ABS: BDR_TRY(no_index()); BDR_REQUIRE(a->td_cap >= R, "no TD buffer of %llu rows", (unsigned long long)R); src = a->td_abs; want = R; break;
+        case BDR_DQN_MLP_BUF_LOSS: BDR_TRY(no_index()); src = a->loss; want = 1; break;
+        case BDR_DQN_MLP_BUF_DW_PART: case BDR_DQN_MLP_BUF_CHUNKS: {
+            BDR_REQUIRE(a->probe_chunks > 0, "the last update formed no weight-gradient partials (step form %d)", a->probe_form);
+            if (buf == BDR_DQN_MLP_BUF_CHUNKS) {
+                BDR_TRY(no_index());
+                BDR_REQUIRE(n == 1, "a chunk count is 1 float, not %llu", (unsigned long long)n);
+                out[0] = (float)a->probe_chunks;
+                return BDR_OK;
+            }
+            BDR_TRY(need(z == 0 && l >= 0 && l < L));
+            BDR_REQUIRE(a->probe_chunks <= a->dw_chunks_l[l], "more chunks than the partial buffer was laid out for");
+            src = a->dw_part + a->dw_off[l]; want = (size_t)a->probe_chunks * ((size_t)a->net.L[l].Kp * a->net.L[l].Np + a->net.L[l].Np);
+            break;
+        }
+        case BDR_DQN_MLP_BUF_Q: BDR_TRY(no_index()); src = a->q; want = a->net.total; break;
+        case BDR_DQN_MLP_BUF_Q_TGT: BDR_TRY(no_index()); src = a->q_tgt; want = a->net.total; break;
+        case BDR_DQN_MLP_BUF_GRAD: BDR_TRY(no_index()); src = a->grad; want = a->net.total; break;
+        case BDR_DQN_MLP_BUF_M: BDR_TRY(no_index()); src = a->m; want = a->net.total; break;
+        case BDR_DQN_MLP_BUF_V: BDR_TRY(no_index()); src = a->v; want = a->net.total; break;
+        case BDR_DQN_MLP_BUF_FORM:
+            BDR_TRY(no_index());
+            BDR_REQUIRE(n == 1, "a step form is 1 float, not %llu", (unsigned long long)n);
+            out[0] = (float)a->probe_form;
+            return BDR_OK;
+        default: return fail(BDR_ERR_INVALID, "unknown Mlp DQN probe buffer %d", buf);
+    }
+    BDR_REQUIRE(src, "Mlp DQN probe buffer %d is not allocated", buf);
+    BDR_REQUIRE(n == want, "Mlp DQN probe buffer %d holds %llu floats, not %llu", buf, (unsigned long long)want, (unsigned long long)n);
+    BDR_HIP(hipStreamSynchronize(a->stream));
     BDR_HIP(hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost));
     return BDR_OK;
 }

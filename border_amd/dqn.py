@@ -297,6 +297,42 @@ class Dqn(TchValueAgent):
         _lib.check(_lib.lib().bdr_dqn_probe(self._h, idx, _p(out), n))
         return out
 
+    BUFS = {"x_in": 0, "act": 1, "dy": 2, "pred": 3, "tgt": 4, "loss_row": 5, "td_abs": 6, "loss": 7, "dw_part": 8, "q": 9, "q_tgt": 10,
+            "grad": 11, "m": 12, "v": 13, "chunks": 14, "form": 15}   # BDR_DQN_MLP_BUF_*
+    FORMS = ("lds", "global", "layers_head", "layers_td", "tiles")     # BDR_DQN_MLP_FORM_*
+
+    def layer(self, buf: str, rows: int, z: int = 0, layer: int = 0):
+        """bdr_dqn_mlp_layer_probe (Mlp Q-network only): one raw device buffer of the last update, padding included.  `rows` is that
+        update's batch size; the library refuses any other float count.  x_in, act, dy: [rows][padded width]; pred, tgt, loss_row,
+        td_abs: [rows]; loss: [1]; dw_part: [chunks][Kp * Np + Np]; q, q_tgt, grad, m, v: the whole padded arena; chunks: int."""
+        q = self.config.model_config.q_config
+        if not isinstance(q, MlpConfig):
+            raise TypeError("Dqn.layer reads the buffers of an Mlp Q-network")
+        pad = lambda x: (x + 63) // 64 * 64
+        widths = (q.in_dim,) + tuple(q.units) + (q.out_dim,)
+        Kp, Np = [pad(w) for w in widths[:-1]], [pad(w) for w in widths[1:]]
+        if buf in ("chunks", "form"):
+            out = np.empty(1, np.float32)
+            _lib.check(_lib.lib().bdr_dqn_mlp_layer_probe(self._h, self.BUFS[buf], z, layer, _p(out), 1))
+            return int(out[0])
+        if buf in ("act", "dy", "dw_part") and not 0 <= layer < len(Np):
+            raise IndexError("layer %d of %d" % (layer, len(Np)))
+        total = sum(k * n + n for k, n in zip(Kp, Np))
+        if buf == "dw_part":
+            shape = (self.layer("chunks", rows), Kp[layer] * Np[layer] + Np[layer])
+        else:
+            shape = {"x_in": (rows, Kp[0]), "act": (rows, Np[layer]), "dy": (rows, Np[layer]), "pred": (rows,), "tgt": (rows,),
+                     "loss_row": (rows,), "td_abs": (rows,), "loss": (1,), "q": (total,), "q_tgt": (total,), "grad": (total,),
+                     "m": (total,), "v": (total,)}[buf]
+        out = np.empty(shape, np.float32)
+        _lib.check(_lib.lib().bdr_dqn_mlp_layer_probe(self._h, self.BUFS[buf], z, layer, _p(out), out.size))
+        return out
+
+    @property
+    def step_form(self) -> str:
+        """the step the last update took: one of FORMS"""
+        return self.FORMS[self.layer("form", 0)]
+
     def profile_read(self) -> dict:
         """{bracket name: mean milliseconds} (AgentHandle.profile_read as a dict)"""
         return dict(super().profile_read())

@@ -935,6 +935,26 @@ BDR_API int32_t bdr_checkpoint_read(const char* path, const bdr_named_tensor* me
  * AtariCnn only, the backward pass: 8 h1 [B][512] (online instance on `obs`), 9 dq [B] (dL/dQ(s,a)), 10 dh1 [B][512], and the gradients
  * w.r.t. the conv layers' pre-activations, position-major: 11 dy3 [B*49][64], 12 dy2 [B*81][64], 13 dy1 [B*400][32]. */
 BDR_API int32_t bdr_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
+/* Layer probes of the Mlp DQN agent: ONE raw device buffer of the last update (bdr_dqn_update_on_batch*, opt, a group's round) to the
+ * host after synchronising the agent's stream, rows x padded leading dimension, padding included.  B = rows of that update, Kp / Np =
+ * sizes padded to 64, z = network instance (0 online on obs, 1 target on next_obs, 2 online on next_obs under double DQN), l = layer:
+ *   X_IN(z) [B][Kp_0]; ACT(z, l) [B][Np_l]; DY(l) [B][Np_l]; PRED, TGT, LOSS_ROW, TD_ABS [B]; LOSS [1];
+ *   DW_PART(l) [chunks][Kp_l * Np_l + Np_l] the row-chunk partials of the grouped weight gradient;
+ *   Q, Q_TGT, GRAD, M, V: the whole padded arena (weights [Kp_l][Np_l], bias [Np_l] per layer);
+ *   CHUNKS [1]: the row chunks the last grouped weight-gradient launch used; FORM [1]: the step the last update took (BDR_DQN_MLP_FORM_*).
+ * z and l are 0 where the buffer has none.  BDR_ERR_INVALID, without reading anything, before any update, for a float count that is not
+ * exactly the buffer's, an index out of range (z >= instances of the update) or given where the buffer has none, DW_PART / CHUNKS after
+ * a step that formed no partials (the one-workgroup forms, 64x64 tiles), an unknown buffer, and a handle that is not an Mlp DQN agent. */
+enum { BDR_DQN_MLP_BUF_X_IN = 0, BDR_DQN_MLP_BUF_ACT = 1, BDR_DQN_MLP_BUF_DY = 2, BDR_DQN_MLP_BUF_PRED = 3, BDR_DQN_MLP_BUF_TGT = 4,
+       BDR_DQN_MLP_BUF_LOSS_ROW = 5, BDR_DQN_MLP_BUF_TD_ABS = 6, BDR_DQN_MLP_BUF_LOSS = 7, BDR_DQN_MLP_BUF_DW_PART = 8, BDR_DQN_MLP_BUF_Q = 9,
+       BDR_DQN_MLP_BUF_Q_TGT = 10, BDR_DQN_MLP_BUF_GRAD = 11, BDR_DQN_MLP_BUF_M = 12, BDR_DQN_MLP_BUF_V = 13, BDR_DQN_MLP_BUF_CHUNKS = 14,
+       BDR_DQN_MLP_BUF_FORM = 15 };
+enum { BDR_DQN_MLP_FORM_LDS = 0,          /* one workgroup, matrices resident in LDS (k_dqn_mlp_step_lds) */
+       BDR_DQN_MLP_FORM_GLOBAL = 1,       /* one workgroup through global memory (k_dqn_mlp_step) */
+       BDR_DQN_MLP_FORM_LAYERS_HEAD = 2,  /* layer by layer, row-block head (k_mlp_head_td) */
+       BDR_DQN_MLP_FORM_LAYERS_TD = 3,    /* layer by layer, k_td_dense + k_mean_rows */
+       BDR_DQN_MLP_FORM_TILES = 4 };      /* 64x64 tiles, one launch per tensor (BDR_NO_SMALL_GEMM=1) */
+BDR_API int32_t bdr_dqn_mlp_layer_probe(bdr_agent* a, int32_t buf, int32_t z, int32_t layer, float* out, uint64_t n);
 
 /* Per-kernel device timing of the opt step (bench.py roofline leg): when enabled the step is
  * bracketed kernel by kernel with HIP events on the agent's stream. */

@@ -72,6 +72,27 @@ pub const BDR_SAC_BUF_PI_GRAD: i32 = 26;
 pub const BDR_SAC_BUF_Q_GRAD: i32 = 27;
 pub const BDR_SAC_BUF_PI_CHUNKS: i32 = 28;
 pub const BDR_SAC_BUF_Q_CHUNKS: i32 = 29;
+pub const BDR_DQN_MLP_BUF_X_IN: i32 = 0;
+pub const BDR_DQN_MLP_BUF_ACT: i32 = 1;
+pub const BDR_DQN_MLP_BUF_DY: i32 = 2;
+pub const BDR_DQN_MLP_BUF_PRED: i32 = 3;
+pub const BDR_DQN_MLP_BUF_TGT: i32 = 4;
+pub const BDR_DQN_MLP_BUF_LOSS_ROW: i32 = 5;
+pub const BDR_DQN_MLP_BUF_TD_ABS: i32 = 6;
+pub const BDR_DQN_MLP_BUF_LOSS: i32 = 7;
+pub const BDR_DQN_MLP_BUF_DW_PART: i32 = 8;
+pub const BDR_DQN_MLP_BUF_Q: i32 = 9;
+pub const BDR_DQN_MLP_BUF_Q_TGT: i32 = 10;
+pub const BDR_DQN_MLP_BUF_GRAD: i32 = 11;
+pub const BDR_DQN_MLP_BUF_M: i32 = 12;
+pub const BDR_DQN_MLP_BUF_V: i32 = 13;
+pub const BDR_DQN_MLP_BUF_CHUNKS: i32 = 14;
+pub const BDR_DQN_MLP_BUF_FORM: i32 = 15;
+pub const BDR_DQN_MLP_FORM_LDS: i32 = 0;
+pub const BDR_DQN_MLP_FORM_GLOBAL: i32 = 1;
+pub const BDR_DQN_MLP_FORM_LAYERS_HEAD: i32 = 2;
+pub const BDR_DQN_MLP_FORM_LAYERS_TD: i32 = 3;
+pub const BDR_DQN_MLP_FORM_TILES: i32 = 4;
 pub const BDR_ARITH_BF16X3_6: i32 = 0;
 pub const BDR_ARITH_F32_EXACT: i32 = 1;
 pub const BDR_ACTIVATION_NONE: i32 = 0;
@@ -1146,6 +1167,7 @@ extern "C" {
     pub fn bdr_checkpoint_write(path: *const c_char, meta: *const bdr_named_tensor, n_tensors: u32, data: *const f32, n: u64) -> i32;
     pub fn bdr_checkpoint_read(path: *const c_char, meta: *const bdr_named_tensor, n_tensors: u32, data: *mut f32, n: u64) -> i32;
     pub fn bdr_dqn_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
+    pub fn bdr_dqn_mlp_layer_probe(a: *mut bdr_agent, buf: i32, z: i32, layer: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_sac_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_agent_profile_enable(a: *mut bdr_agent, on: i32) -> i32;
     pub fn bdr_agent_profile_read(a: *mut bdr_agent, names_out: *mut c_char, names_cap: u64, ms_out: *mut f32, count_inout: *mut u64) -> i32;
