@@ -76,6 +76,11 @@ class Bc(DenseHandle):
     WHICH = {"policy": 0, "actor": 0, "pi": 0, "qnet": 0}   # ParamExchange / ModelMailbox: SyncModel ships the policy == model 0
     PROBES = {"pred": 0, "dz": 1}
 
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.check(_lib.lib().bdr_agent_destroy(self._h))   # (refused for a member of a live BcGroup: the group owns it)
+            self._h = None
+
     def update_on_batch(self, obs, act) -> dict:
         """One Bc::opt_ (bc/base.rs:167-198) on host rows; the record's one key is "loss"."""
         obs = np.ascontiguousarray(obs, dtype=np.float32)

@@ -18,10 +18,13 @@
 // differences added in column order; then candle_actor.hpp's batch order (rows in blocks of 32, a butterfly per block, the block
 // partials added in block order), formed by the launch's last workgroup from per-row sums - no workgroup waits for another, and no
 // float atomics.  The two forms form the last layer's dot products in different orders and need not agree bitwise.
+// k_bc_loss, k_bc_head_mfma (and dense.hpp's k_pack_rows) are bodies over their argument structs with the entries calling them: bc_group.hpp
+// (included below) runs the same bodies for P agents of one shape per launch, the member index in grid dimension y.
 #include <algorithm>
 #include <cstdlib>
 
 #include "candle_actor.hpp"
+#include "bc_group_plan.hpp"
 
 using namespace bdr;
 
@@ -69,7 +72,10 @@ struct BcLossArgs {
     const float* z; int ld; const float* act; int A, B, kind;
     float* pred; float* dz; float* rowsq; unsigned* ticket; float* scal; int accumulate; float inv_n;
 };
-__global__ __launch_bounds__(256) void k_bc_loss(BcLossArgs p)
+// (the body over its argument struct: the kernel argument, or a member's entry of a device array read in place - bc_group.hpp, where
+// gridDim.x is still the member's own workgroup count and the ticket the member's own)
+template <class Args>
+__device__ __forceinline__ void bc_loss_body(const Args& p)
 {
     __shared__ float sq[32 * 257];
     __shared__ float red8[8];
@@ -90,6 +96,7 @@ __global__ __launch_bounds__(256) void k_bc_loss(BcLossArgs p)
     }
     if (last_workgroup(p.ticket, gridDim.x, &s_flag)) bc_finish_loss(p.rowsq, p.B, p.scal, p.accumulate, p.inv_n, red8);
 }
+__global__ __launch_bounds__(256) void k_bc_loss(BcLossArgs p) { bc_loss_body(p); }
 
 // ---- fused form -------------------------------------------------------------------------------------------------------------------
 // h [B][K] the last hidden activation (post-ReLU, K = its padded width), w [K][64] + bias [64] the last layer (out_dim <= 64).
@@ -104,10 +111,7 @@ struct BcHeadArgs {
     float* pred; float* dz; float* dx; float* rowsq; unsigned* ticket; float* scal; int accumulate; float inv_n;
 };
 constexpr int BC_HEAD_ROWS_DEFAULT = 8;   // measured at the bc_pen shape: 8 rows 22.9k updates/s, 16 rows 21.1k, 32 rows 17.1k (profiles/bench_bc_pen.json)
-// BDR_BC_KERNEL_DEFAULT: the MFMA head where it applies and the update is launch-bound.  Measured at the bc_pen shape (B = 256,
-// profiles/bench_bc_pen.json): 23 200-23 600 updates/s against 21 800-22 000 (general) and 22 600-23 000 (k_bc_head, 8 rows) in five
-// alternating rounds.  Nothing was measured above a few hundred rows, where the launches stop being the bound: the general form there.
-inline int bc_default_form(int batch, bool can_mfma) { return can_mfma && batch <= 1024 ? BDR_BC_KERNEL_FUSED_MFMA : BDR_BC_KERNEL_GENERAL; }
+// (BDR_BC_KERNEL_DEFAULT and the MFMA head's conditions: bc_resolve_form / bc_can_mfma, bc_group_plan.hpp - the group reads the same rule)
 inline size_t bc_head_lds(int K, int R) { return ((size_t)K * 65 + (size_t)R * K + 64 * (size_t)R + (size_t)R * 65 + 8 + 4) * sizeof(float) + 64; }
 template <int R>
 __global__ __launch_bounds__(256) void k_bc_head(BcHeadArgs p)
@@ -192,8 +196,9 @@ __global__ __launch_bounds__(256) void k_bc_head(BcHeadArgs p)
 // gradient: wave w owns the 32-column tiles w, w + 4, ... of the hidden layer; A = dz rows from LDS, B = weight rows (contiguous
 // in n), reduced over n ascending in quads, the two lane halves taking alternate quads.
 // Bounds: rows clamped to B - 1 when loaded, stored for b < B only; k < K (K % 64 == 0); n < 32 NT <= 64.
-template <int NT>
-__global__ __launch_bounds__(256) void k_bc_head_mfma(BcHeadArgs p)
+// (the body over its argument struct, as bc_loss_body)
+template <int NT, class Args>
+__device__ __forceinline__ void bc_head_mfma_body(const Args& p)
 {
     constexpr int NC = NT * 32;
     __shared__ float red[4][32][33];
@@ -262,6 +267,8 @@ __global__ __launch_bounds__(256) void k_bc_head_mfma(BcHeadArgs p)
     }
     if (ticket_last(&s_flag)) bc_finish_loss(p.rowsq, p.B, p.scal, p.accumulate, p.inv_n, red8);
 }
+template <int NT>
+__global__ __launch_bounds__(256) void k_bc_head_mfma(BcHeadArgs p) { bc_head_mfma_body<NT>(p); }
 
 // Policy::sample (bc/base.rs:49-59) from the last layer's pre-activation z [n][ld].  Continuous: out [n][A] = act_out(z).  Discrete:
 // idx [n] = argmax_j act_out(z[b][j]), the lowest index among equal values (candle's tie order is not pinned by anything that can be
@@ -292,7 +299,7 @@ struct Bc : DenseAgent {
     uint64_t step = 0;
     int form = BDR_BC_KERNEL_GENERAL; bool head_attr = false; int head_rows = 0; size_t head_lds = 0;
     // batch buffers
-    int B = 0;
+    int B = 0; uint64_t batch_gen = 0;          // batch_gen: bumped whenever the batch buffers are re-allocated (bc_group.hpp keys its static arguments on it)
     float* x0 = nullptr;                        // [B][Kp] padded observations
     std::vector<float*> act, dy;                // activations (the last: z) and gradients per layer
     float *pred = nullptr, *rowsq = nullptr, *part = nullptr, *samp = nullptr; long long* samp_idx = nullptr;
@@ -315,7 +322,7 @@ struct Bc : DenseAgent {
         BDR_TRY(alloc(&part, plan(net, Bn, off), BATCH));
         BDR_TRY(alloc(&samp, (size_t)Bn * A, BATCH));
         BDR_TRY(alloc(&samp_idx, Bn, BATCH));
-        B = Bn;
+        B = Bn; batch_gen += 1;
         return BDR_OK;
     }
     // layers [0, upto) of Bn rows of x0
@@ -501,6 +508,8 @@ int32_t bc_check(const bdr_bc_config& c)
 
 }  // namespace
 
+#include "bc_group.hpp"
+
 extern "C" {
 
 void bdr_bc_config_default(bdr_bc_config* c)
@@ -529,14 +538,14 @@ int32_t bdr_bc_create(const bdr_bc_config* cfg, bdr_agent** out)
                 "the fused BC head needs act_dim <= 64, a hidden layer, and the last layer's weights plus %d rows within 160 KB of LDS "
                 "(act_dim %d, %d hidden layers, last hidden width %d): use BDR_BC_KERNEL_GENERAL", R, c.act_dim, c.policy.n_units,
                 c.policy.n_units ? c.policy.units[c.policy.n_units - 1] : 0);
-    const bool can_mfma = c.act_dim <= 64 && c.policy.n_units >= 1;
+    const bool can_mfma = bc_can_mfma(c.act_dim, c.policy.n_units);
     BDR_REQUIRE(c.kernel_form != BDR_BC_KERNEL_FUSED_MFMA || can_mfma,
                 "the fused BC head needs act_dim <= 64 and a hidden layer (act_dim %d, %d hidden layers): use BDR_BC_KERNEL_GENERAL", c.act_dim, c.policy.n_units);
     BDR_TRY(ensure_device(c.device));
     Bc* a = new Bc();
     a->cfg = c; a->device = c.device; a->train = false;
     a->O = c.obs_dim; a->A = c.act_dim; a->net = net;
-    a->form = c.kernel_form != BDR_BC_KERNEL_DEFAULT ? c.kernel_form : bc_default_form((int)c.batch_size, can_mfma);
+    a->form = bc_resolve_form(c.kernel_form, (int)c.batch_size, c.act_dim, c.policy.n_units);
     a->head_rows = R; a->head_lds = bc_head_lds(net.L.back().Kp, R);
     const int32_t st = [&]() -> int32_t {
         BDR_HIP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));

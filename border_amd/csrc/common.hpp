@@ -85,6 +85,9 @@ struct bdr_replay {
     uint32_t key[8] = {0};     // ChaCha12 key = seed_from_u64(seed)
     uint64_t word_pos = 0;     // next u32 word of the key stream (host-tracked, passed by value)
     uint8_t* ring = nullptr;   // capacity * stride bytes in HBM
+    // views (bdr_replay_view_create, replay.hip): a view borrows its owner's rows - `ring` is the owner's - and is read-only
+    bdr_replay* view_of = nullptr;   // the owner of the rows (nullptr: this handle owns its ring)
+    uint32_t n_views = 0;            // live views of this ring: pushes, fill, enable_per and destroy are refused meanwhile
     hipStream_t stream = nullptr;
     hipEvent_t written = nullptr;  // recorded after the last push/fill on `stream`
     hipEvent_t read = nullptr;     // recorded by the consumer after the last gather

@@ -288,13 +288,19 @@ __global__ __launch_bounds__(256) void k_dense_reduce(const float* __restrict__ 
 
 // copy the logical columns of row-major host-layout rows into a zero-padded [B][ld] matrix:
 // dst[b][col0 + c] = src[b*src_ld + c], c < cols
-__global__ void k_pack_rows(const float* __restrict__ src, int src_ld, int cols, float* __restrict__ dst, int ld, int col0, int B)
+// (the body as a function: the kernel's own arguments, or the fields of a member's PackRowsArgs read in place - bc_group.hpp)
+__device__ __forceinline__ void pack_rows_body(const float* __restrict__ src, int src_ld, int cols, float* __restrict__ dst, int ld, int col0, int B)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * cols) return;
     const int b = i / cols, c = i % cols;
     dst[(size_t)b * ld + col0 + c] = src[(size_t)b * src_ld + c];
 }
+__global__ void k_pack_rows(const float* __restrict__ src, int src_ld, int cols, float* __restrict__ dst, int ld, int col0, int B)
+{
+    pack_rows_body(src, src_ld, cols, dst, ld, col0, B);
+}
+struct PackRowsArgs { const float* src; int src_ld, cols; float* dst; int ld, col0, B; };
 
 // ---- small layers: one 32x32 output tile per workgroup, the reduction split over its four waves ---------
 // A 64x64 tile of k_igemm keeps one CU busy for kred/2 * 64 cycles however its waves are arranged (the CU's four matrix pipes

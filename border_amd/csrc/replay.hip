@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 #include <unordered_set>
@@ -342,6 +343,15 @@ int32_t replay_per_check(uint64_t uid, bool* alive)
 }
 }  // namespace bdr
 
+// Views (bdr_replay_view_create): a view borrows its owner's rows and is read-only; while an owner has live views its rows, its
+// `size` and its layout are frozen.  Every call that writes ring rows asks here first.
+static int32_t refuse_frozen(const bdr_replay* r, const char* what)
+{
+    BDR_REQUIRE(!r->view_of, "%s on a view: a view is read-only (it borrows its owner's rows)", what);
+    BDR_REQUIRE(r->n_views == 0, "%s on a ring with %u live view(s): its rows stay as they are until the views are destroyed", what, r->n_views);
+    return BDR_OK;
+}
+
 // `written` was just recorded on some stream: consumers have to wait for it again
 static void mark_written(bdr_replay* r) { r->written_gen += 1; }
 // a write was enqueued on `s` and left the record of `written` to the first consumer on another stream (wait_for_writer)
@@ -411,6 +421,7 @@ static int32_t begin_write(bdr_replay* r)
 namespace bdr {
 int32_t replay_begin_write_on_stream(bdr_replay* r, hipStream_t stream)
 {
+    BDR_TRY(refuse_frozen(r, "a grouped push"));
     if (stream != r->stream) stream_register(stream);
     BDR_TRY(wait_for_writer(r, stream));
     return wait_for_reader(r, stream);
@@ -621,6 +632,8 @@ int32_t bdr_replay_create(const bdr_replay_config* cfg, bdr_replay** out)
 int32_t bdr_replay_destroy(bdr_replay* r)
 {
     if (!r) return BDR_OK;
+    BDR_REQUIRE(r->n_views == 0, "bdr_replay_destroy on a ring with %u live view(s): destroy the views first (they read its rows)", r->n_views);
+    if (r->view_of) { r->view_of->n_views -= 1; r->ring = nullptr; }   // a view owns no ring memory: nothing of the owner's is freed below
     replay_retire(r);   // agents that last sampled from this buffer find no handle for its uid from here on
     (void)hipSetDevice(r->device);
     (void)hipDeviceSynchronize();
@@ -643,6 +656,50 @@ int32_t bdr_replay_destroy(bdr_replay* r)
     (void)hipEventDestroy(r->written); (void)hipEventDestroy(r->read);
     (void)hipStreamDestroy(r->stream);
     delete r;
+    return BDR_OK;
+}
+
+// A read-only bdr_replay over the rows of `owner`: its own ChaCha key (seed_from_u64(seed), as bdr_replay_create derives it), stream
+// position, stream, events and batch buffers; `ring` is the owner's.  capacity, size, head and the layout are the owner's at this moment
+// and stay: while a view lives the owner refuses every write (refuse_frozen) and its destroy.  Every sample of a view therefore runs
+// the code of a sample on a separate ring of that seed holding the same rows, on the same values: the same bits.
+int32_t bdr_replay_view_create(bdr_replay* owner, uint64_t seed, bdr_replay** out)
+{
+    BDR_REQUIRE(owner && out, "null argument");
+    BDR_REQUIRE(!owner->view_of, "a view of a view: create it on the owner");
+    BDR_REQUIRE(!owner->per, "views cover uniform rings: a prioritized ring samples through its sum tree, which its pushes and priority updates rewrite");
+    BDR_REQUIRE(!owner->frame_stack, "views cover plain rings: a single-frame store is not shared");
+    BDR_REQUIRE(owner->index_rng == BDR_RNG_STDRNG, "views draw the StdRng index stream: the owner's index_rng must be BDR_RNG_STDRNG");
+    if (owner->size == 0) return fail(BDR_ERR_EMPTY, "a view of an empty replay buffer");
+    BDR_HIP(hipSetDevice(owner->device));
+    // once: every write of the owner so far is complete, whichever stream enqueued it (its own, or a group's after a grouped push)
+    if (owner->written_lazy && owner->writer_stream && owner->writer_stream != owner->stream && stream_alive(owner->writer_stream))
+        BDR_HIP(hipStreamSynchronize(owner->writer_stream));
+    BDR_HIP(hipStreamSynchronize(owner->stream));
+    std::unique_ptr<bdr_replay> v(new bdr_replay());
+    { static std::atomic<uint64_t> next_view_uid{1ull << 40}; v->uid = next_view_uid.fetch_add(1); }   // (ring uids count from 1: the two never meet)
+    v->device = owner->device;
+    v->capacity = owner->capacity; v->i = owner->i; v->size = owner->size;
+    v->obs_bytes = owner->obs_bytes; v->act_bytes = owner->act_bytes;
+    v->next_off = owner->next_off; v->act_off = owner->act_off; v->tail_off = owner->tail_off; v->stride = owner->stride;
+    v->index_rng = BDR_RNG_STDRNG;
+    seed_from_u64(seed, v->key);
+    v->ring = owner->ring;
+    hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->written, hipEventDisableTiming | hipEventDisableSystemFence);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->read, hipEventDisableTiming | hipEventDisableSystemFence);
+    if (e == hipSuccess) e = hipEventRecord(v->written, v->stream);   // (nothing is ever written through a view: consumers wait for this once)
+    if (e != hipSuccess) {
+        if (v->written) (void)hipEventDestroy(v->written);
+        if (v->read) (void)hipEventDestroy(v->read);
+        if (v->stream) (void)hipStreamDestroy(v->stream);
+        return fail(BDR_ERR_HIP, "creating a view's stream and events failed: %s", hipGetErrorString(e));
+    }
+    mark_written(v.get());
+    v->view_of = owner;
+    owner->n_views += 1;
+    replay_register(v.get());
+    *out = v.release();
     return BDR_OK;
 }
 
@@ -673,6 +730,7 @@ int32_t bdr_replay_push(bdr_replay* r, uint64_t n, const void* obs, const void* 
                         const float* reward, const int8_t* term, const int8_t* trunc)
 {
     BDR_REQUIRE(r, "null replay handle");
+    BDR_TRY(refuse_frozen(r, "bdr_replay_push"));
     if (n == 0) return BDR_OK;
     BDR_REQUIRE(obs && act && next_obs && reward && term && trunc, "null transition field");
     BDR_HIP(hipSetDevice(r->device));
@@ -801,6 +859,7 @@ int32_t bdr_replay_push_device(bdr_replay* r, uint64_t n, const void* obs_dev, u
                                uint64_t next_obs_stride, const float* reward, const int8_t* term, const int8_t* trunc)
 {
     BDR_REQUIRE(r, "null replay handle");
+    BDR_TRY(refuse_frozen(r, "bdr_replay_push_device"));
     if (n == 0) return BDR_OK;
     BDR_REQUIRE(obs_dev && act && next_obs_dev && reward && term && trunc, "null transition field");
     BDR_REQUIRE(obs_stride >= r->obs_bytes && next_obs_stride >= r->obs_bytes, "row strides must be >= the observation row size");
@@ -960,6 +1019,7 @@ int32_t bdr_replay_push_device_frames(bdr_replay* r, uint64_t n, const void* obs
                                       uint64_t next_obs_stride, const float* reward, const int8_t* term, const int8_t* trunc)
 {
     BDR_REQUIRE(r, "null replay handle");
+    BDR_TRY(refuse_frozen(r, "bdr_replay_push_device_frames"));
     if (n == 0) return BDR_OK;
     BDR_REQUIRE(obs_dev && act && next_obs_dev && reward && term && trunc, "null transition field");
     BDR_REQUIRE(r->frame_stack > 0, "not a single-frame store (bdr_replay_config::frame_stack == 0): push device rows into a plain ring with bdr_replay_push_device");
@@ -1101,6 +1161,7 @@ int32_t bdr_replay_push_episode(bdr_replay* r, uint64_t T, const void* observati
                                 const int8_t* term, const int8_t* trunc, const bdr_obs_norm* norm)
 {
     BDR_REQUIRE(r, "null replay handle");
+    BDR_TRY(refuse_frozen(r, "bdr_replay_push_episode"));
     BDR_REQUIRE(obs_dtype == BDR_DTYPE_F32 || obs_dtype == BDR_DTYPE_F64, "obs_dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64");
     BDR_REQUIRE(!r->frame_stack, "bdr_replay_push_episode writes f32 rows: not for a buffer with frame_stack > 0 (push stacked host rows with bdr_replay_push)");
     const uint64_t dim = r->obs_bytes / 4;
@@ -1214,6 +1275,7 @@ int32_t bdr_replay_summarize(bdr_replay* r, bdr_replay_summary* out)
 int32_t bdr_replay_fill_synthetic(bdr_replay* r, uint64_t n, uint64_t seed, int32_t kind, int32_t n_actions)
 {
     BDR_REQUIRE(r, "null replay handle");
+    BDR_TRY(refuse_frozen(r, "bdr_replay_fill_synthetic"));
     BDR_REQUIRE(kind == 0 || kind == 1, "kind must be 0 or 1");
     BDR_REQUIRE(n_actions >= 0, "n_actions must be >= 0");
     BDR_REQUIRE(n_actions == 0 || r->act_bytes == 8, "discrete actions are one i64 per row");
@@ -1534,6 +1596,7 @@ void bdr_per_config_default(bdr_per_config* c)   // config.rs:67-83
 int32_t bdr_replay_enable_per(bdr_replay* r, const bdr_per_config* c)
 {
     BDR_REQUIRE(r && c, "null argument");
+    BDR_TRY(refuse_frozen(r, "bdr_replay_enable_per"));
     BDR_REQUIRE(!r->per, "PER is already enabled");
     BDR_REQUIRE(r->size == 0 && r->i == 0, "PER must be enabled on an empty buffer");
     BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "prioritized sampling draws from the StdRng stream (base.rs:377-383): index_rng must be BDR_RNG_STDRNG");

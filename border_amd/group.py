@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .bc import Bc
 from .dqn import Dqn, DqnConfig, record_keys
 
 
@@ -240,6 +241,126 @@ class DqnGroup:
     def close(self) -> None:
         if getattr(self, "_g", None):
             _lib.check(_lib.lib().bdr_agent_group_destroy(self._g))   # destroys the members
+            self._g = None
+            for a in self._members:
+                a._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BcGroup:
+    """A set of BC agents of one shape whose Agent::opt runs as the launch sequence of ONE member, every launch serving all members
+    (bdr_bc_group_*): 2L + 4 launches per round for L layers in the "general" kernel form, 2L + 2 with the MFMA head, whatever the
+    number of members.  The members may differ in seed, learning rate and optimizer; their buffers are uniform buffers of their own
+    or views of one (`SimpleReplayBuffer.view`), so that P members hold one copy of a dataset.
+
+    A launch grouping, not an agent kind: the members are ordinary `Bc` objects (every `Bc` method keeps working on a member and
+    means what it meant) that the group owns - `BcGroup.close()` closes them, `member.close()` on a live group is refused.  Results
+    are bit for bit those of stepping the same agents one after the other."""
+    STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/bc_group.hpp bdr_bc_group::STEP_SLOTS)
+
+    def __init__(self, agents):
+        agents = list(agents)
+        hs = (C.c_void_p * len(agents))(*[a.handle for a in agents])
+        g = C.c_void_p()
+        _lib.check(_lib.lib().bdr_bc_group_create(hs, len(agents), C.byref(g)))
+        self._g = g
+        self._members = agents
+        self._bound = None   # the handle array of the buffers passed last (opt() without an argument steps on them again)
+
+    @classmethod
+    def build(cls, configs) -> "BcGroup":
+        """One `Bc` per BcConfig, grouped.  Nothing is left behind when a config is refused."""
+        agents = []
+        try:
+            for c in configs:
+                agents.append(Bc.build(c))
+            return cls(agents)
+        except Exception:
+            for a in agents:
+                a.close()
+            raise
+
+    @property
+    def members(self):
+        return list(self._members)
+
+    def __len__(self):
+        return len(self._members)
+
+    @property
+    def handle(self):
+        return self._g
+
+    def info(self) -> dict:
+        """bdr_bc_group_info: {"form": "bc_layers", "n_members", "launches_per_round", "kernel_launches"}."""
+        i = _lib.GroupInfoC()
+        _lib.check(_lib.lib().bdr_bc_group_info(self._g, C.byref(i)))
+        form = {_lib.GROUP_FORM_BC_LAYERS: "bc_layers", _lib.GROUP_FORM_LAYERS: "layers", _lib.GROUP_FORM_ONE_WORKGROUP: "one_workgroup"}[i.form]
+        return {"form": form, "n_members": i.n_members, "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
+
+    @property
+    def form(self) -> str:
+        return self.info()["form"]
+
+    @property
+    def launches_per_round(self) -> int:
+        """kernel launches of one update round, whatever the number of members"""
+        return self.info()["launches_per_round"]
+
+    @property
+    def kernel_launches(self) -> int:
+        """kernel launches the group's own calls have enqueued since it was built"""
+        return self.info()["kernel_launches"]
+
+    def _buffers(self, buffers):
+        if buffers is None:
+            if self._bound is None:
+                raise ValueError("opt() without buffers needs an earlier call that named them")
+            return self._bound
+        buffers = list(buffers)
+        if len(buffers) != len(self._members):
+            raise ValueError(f"{len(self._members)} members need {len(self._members)} buffers, got {len(buffers)}")
+        self._bound = (C.c_void_p * len(buffers))(*[b.handle for b in buffers])
+        return self._bound
+
+    def opt(self, buffers=None) -> None:
+        """Agent::opt of every member on its own buffer: launches_per_round launches in all; does not synchronise.
+        `buffers=None`: the buffers of the last opt / opt_with_record call (they must still be open)."""
+        _lib.check(_lib.lib().bdr_bc_group_opt(self._g, self._buffers(buffers)))
+
+    def opt_with_record(self, buffers=None) -> list:
+        """Agent::opt_with_record of every member (one synchronisation): a list of Record dicts ({"loss": ..}) in member order."""
+        n, cap = len(self._members), 8
+        out = np.zeros((n, cap), np.float32)
+        cnt = np.zeros(n, np.int32)
+        _lib.check(_lib.lib().bdr_bc_group_opt_with_scalars(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap,
+                                                            cnt.ctypes.data_as(C.c_void_p)))
+        return [{k: float(v) for k, v in zip(("loss",), out[i, :cnt[i]])} for i in range(n)]
+
+    def train_offline(self, buffers, max_opts: int, record_interval: int = 0, on_record=None) -> None:
+        """max_opts update rounds on `buffers`; every record_interval-th one is an opt_with_record whose records go to
+        on_record(opt_step, records).  A plain loop over opt / opt_with_record, synchronised at its end."""
+        self._buffers(buffers)
+        for k in range(1, max_opts + 1):
+            if record_interval and k % record_interval == 0:
+                rec = self.opt_with_record()
+                if on_record is not None:
+                    on_record(k, rec)
+            else:
+                self.opt()
+        self.sync()
+
+    def sync(self) -> None:
+        _lib.check(_lib.lib().bdr_bc_group_sync(self._g))
+
+    def close(self) -> None:
+        if getattr(self, "_g", None):
+            _lib.check(_lib.lib().bdr_bc_group_destroy(self._g))   # destroys the members
             self._g = None
             for a in self._members:
                 a._h = None

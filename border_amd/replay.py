@@ -104,9 +104,26 @@ class SimpleReplayBuffer:
     def build(cls, config: SimpleReplayBufferConfig, **kw) -> "SimpleReplayBuffer":
         return cls(config, **kw)
 
+    def view(self, seed: int) -> "SimpleReplayBuffer":
+        """A read-only buffer over THIS buffer's rows with an index stream of its own (`bdr_replay_view_create`): its `batch`,
+        `sample_indices` and an agent's `opt` on it give bit for bit what they give on a separate buffer built with `seed` and
+        holding the same rows, and it holds no copy of them.  The rows are those present now: while a view is open, pushes,
+        `fill_synthetic` and `close` of this buffer are refused (and every push on the view); close the views first.
+        Uniform "StdRng" buffers without a frame store that are not empty."""
+        h = C.c_void_p()
+        _lib.check(_lib.lib().bdr_replay_view_create(self._h, seed, C.byref(h)))
+        v = object.__new__(SimpleReplayBuffer)
+        v.config = SimpleReplayBufferConfig(capacity=self.config.capacity, seed=seed)
+        v.device = self.device
+        v.obs_shape, v.obs_dtype, v.act_shape, v.act_dtype = self.obs_shape, self.obs_dtype, self.act_shape, self.act_dtype
+        v.obs_bytes, v.act_bytes = self.obs_bytes, self.act_bytes
+        v._h = h
+        v._owner = self   # (the owner outlives its views)
+        return v
+
     def close(self):
         if getattr(self, "_h", None):
-            _lib.lib().bdr_replay_destroy(self._h)
+            _lib.check(_lib.lib().bdr_replay_destroy(self._h))   # (refused while views of this buffer are open)
             self._h = None
 
     def __del__(self):

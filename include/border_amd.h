@@ -96,6 +96,16 @@ typedef struct {
  * transition: [obs | next_obs | act | reward f32 | is_terminated i8 | is_truncated i8 | pad]. */
 BDR_API int32_t bdr_replay_create(const bdr_replay_config* cfg, bdr_replay** out);
 BDR_API int32_t bdr_replay_destroy(bdr_replay* r);
+/* A VIEW of a ring: a read-only bdr_replay that borrows `owner`'s rows and carries its own ChaCha key - seed_from_u64(seed), as
+ * bdr_replay_create derives it - stream position and batch buffers, so that P consumers of one dataset (a BC group's members, seeds of a
+ * sweep) hold P index streams over ONE copy of the rows in HBM.  Creation synchronises the owner's stream once and takes capacity, size
+ * and the layout as they are then; the view owns no ring memory and bdr_replay_destroy of a view frees none.
+ * Owners: uniform StdRng rings without a frame store that are not empty; anything else is BDR_ERR_INVALID (BDR_ERR_EMPTY: an empty ring).
+ * On a view every push, bdr_replay_fill_synthetic and bdr_replay_enable_per are BDR_ERR_INVALID; on the owner, while it has live views,
+ * so are every push, fill, enable_per and bdr_replay_destroy, each naming the number of live views.  Without a view nothing about a
+ * ring changes.  bdr_replay_batch, bdr_replay_sample_indices and an agent's opt on a view give bit for bit what they give on a separate
+ * ring created with that seed and holding the same rows. */
+BDR_API int32_t bdr_replay_view_create(bdr_replay* owner, uint64_t seed, bdr_replay** out);
 
 /* ExperienceBufferBase::push (base.rs:295-316): n transitions, rows written at
  * (i+k) % capacity, i = (i+n) % capacity, size = min(size+n, capacity). Host pointers.  The call returns when the
@@ -495,6 +505,7 @@ BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr
  * launches the group's own calls (opt, push, sample, qvalues, evaluate, the compiled loop) have enqueued since it was created. */
 #define BDR_GROUP_FORM_ONE_WORKGROUP 0
 #define BDR_GROUP_FORM_LAYERS 1
+#define BDR_GROUP_FORM_BC_LAYERS 2   /* a bdr_bc_group (below): BC's launch sequence of one member, every launch serving all members */
 typedef struct { int32_t form; uint32_t n_members; uint32_t launches_per_round; uint32_t reserved; uint64_t kernel_launches; } bdr_group_info;
 BDR_API int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out);
 /* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
@@ -1338,6 +1349,32 @@ BDR_API int32_t bdr_bc_probe(bdr_agent* a, int32_t what, float* out, uint64_t n)
 BDR_API int32_t bdr_bc_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out, int64_t* idx_out);
 /* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
 BDR_API int32_t bdr_bc_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out, int64_t* idx_out);
+
+/* A GROUP of BC agents over uniform rings (or views of one ring, bdr_replay_view_create): Agent::opt of every member in 2L + 4
+ * launches (general form; gather, pack, L forwards, loss, L - 1 input gradients, the grouped weight gradient, reduce + Adam) or 2L + 2
+ * (the MFMA head) for L layers, whatever the number of members - the launch sequence of one member, the member index one more grid
+ * dimension - bit for bit what bdr_agent_opt of the members one after the other gives.  The calls carry the semantics of their
+ * bdr_agent_group_* namesakes: create adopts the members onto one stream and owns them from then on (bdr_agent_destroy of a member is
+ * refused; bdr_bc_group_destroy destroys them), every bdr_agent_* / bdr_bc_* call on a member keeps its meaning and is ordered with the
+ * group's calls.
+ * One value for all members: obs_dim, units, act_dim, activation_out, batch_size, the resolved kernel form, action_type Continuous.
+ * Free per member: optimizer kind and scalars, learning rate, seed.  Refused (BDR_ERR_INVALID, naming the first member concerned): another
+ * shape, the LDS head (BDR_BC_KERNEL_FUSED), a Discrete agent, profiling or a gradient communicator switched on, another device, the
+ * same agent twice, an agent that is in a group already; more than 65535 members or a launch beyond the grid limits.
+ * buffers[p] is member p's: a uniform StdRng ring of f32 rows on the group's device, or a view of one.  A prioritized ring, a frame store,
+ * the xoshiro stream, an empty ring (BDR_ERR_EMPTY) and one bdr_replay for two members are refused, naming the member, and a refused
+ * call leaves every member's step, n_opts and stream position where they were.  _opt does not synchronise; _opt_with_scalars
+ * synchronises once and returns every member's record (one key, loss) at out + p * cap_per_member.  _info fills bdr_group_info with
+ * form = BDR_GROUP_FORM_BC_LAYERS. */
+typedef struct bdr_bc_group bdr_bc_group;
+BDR_API int32_t bdr_bc_group_create(bdr_agent* const* agents, uint32_t n, bdr_bc_group** out);
+BDR_API int32_t bdr_bc_group_destroy(bdr_bc_group* g);
+BDR_API int32_t bdr_bc_group_size(const bdr_bc_group* g, uint32_t* n);
+BDR_API int32_t bdr_bc_group_member(const bdr_bc_group* g, uint32_t i, bdr_agent** out);
+BDR_API int32_t bdr_bc_group_info(const bdr_bc_group* g, bdr_group_info* out);
+BDR_API int32_t bdr_bc_group_opt(bdr_bc_group* g, bdr_replay* const* buffers);
+BDR_API int32_t bdr_bc_group_opt_with_scalars(bdr_bc_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);
+BDR_API int32_t bdr_bc_group_sync(bdr_bc_group* g);
 
 /* ------------------------------------------------------------------------------------------
  * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)

@@ -118,6 +118,7 @@ pub const BDR_CKPT_TCH: i32 = 0;
 pub const BDR_CKPT_SAFETENSORS: i32 = 1;
 pub const BDR_GROUP_FORM_ONE_WORKGROUP: i32 = 0;
 pub const BDR_GROUP_FORM_LAYERS: i32 = 1;
+pub const BDR_GROUP_FORM_BC_LAYERS: i32 = 2;
 pub const BDR_IQN_CONST10: i32 = 0;
 pub const BDR_IQN_CONST32: i32 = 1;
 pub const BDR_IQN_UNIFORM10: i32 = 2;
@@ -145,6 +146,8 @@ pub const BDR_ACT_PATH_FUSED: i32 = 2;
 // opaque handles
 /// `bdr_agent_group` (a launch grouping of Mlp DQN agents): only ever behind a pointer.
 pub enum bdr_agent_group {}
+/// `bdr_bc_group` (a launch grouping of BC agents): only ever behind a pointer.
+pub enum bdr_bc_group {}
 #[repr(C)]
 pub struct bdr_replay {
     _private: [u8; 0],
@@ -853,6 +856,7 @@ extern "C" {
     // ---- SimpleReplayBuffer
     pub fn bdr_replay_create(cfg: *const bdr_replay_config, out: *mut *mut bdr_replay) -> i32;
     pub fn bdr_replay_destroy(r: *mut bdr_replay) -> i32;
+    pub fn bdr_replay_view_create(owner: *mut bdr_replay, seed: u64, out: *mut *mut bdr_replay) -> i32;
     pub fn bdr_replay_push(
         r: *mut bdr_replay,
         n: u64,
@@ -1027,6 +1031,14 @@ extern "C" {
         info: *mut bdr_sample_info,
     ) -> i32;
     pub fn bdr_agent_group_sync(g: *mut bdr_agent_group) -> i32;
+    pub fn bdr_bc_group_create(agents: *mut *const bdr_agent, n: u32, out: *mut *mut bdr_bc_group) -> i32;
+    pub fn bdr_bc_group_destroy(g: *mut bdr_bc_group) -> i32;
+    pub fn bdr_bc_group_size(g: *const bdr_bc_group, n: *mut u32) -> i32;
+    pub fn bdr_bc_group_member(g: *const bdr_bc_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_bc_group_info(g: *const bdr_bc_group, out: *mut bdr_group_info) -> i32;
+    pub fn bdr_bc_group_opt(g: *mut bdr_bc_group, buffers: *mut *const bdr_replay) -> i32;
+    pub fn bdr_bc_group_opt_with_scalars(g: *mut bdr_bc_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
+    pub fn bdr_bc_group_sync(g: *mut bdr_bc_group) -> i32;
     pub fn bdr_agent_group_push(
         g: *mut bdr_agent_group,
         buffers: *mut *const bdr_replay,

@@ -313,6 +313,23 @@ where
     }
 }
 
+impl<O, A> AmdReplayBuffer<O, A>
+where
+    O: RowBatch,
+    A: RowBatch,
+{
+    /// A read-only buffer over THIS buffer's rows with an index stream of its own (`bdr_replay_view_create`): its `batch` and an
+    /// agent's `opt` on it give bit for bit what they give on a separate buffer built with `seed` and holding the same rows, and it
+    /// holds no copy of them.  While a view lives, every push into this buffer is refused (and every push into the view); the
+    /// views must be dropped before this buffer is (the library refuses to destroy a buffer with live views, and its rows stay
+    /// allocated).  Uniform `StdRng` buffers without a frame store that are not empty.
+    pub fn view(&mut self, seed: u64) -> anyhow::Result<Self> {
+        let mut h = std::ptr::null_mut();
+        crate::error::check(unsafe { ffi::bdr_replay_view_create(self.h, seed, &mut h) })?;
+        Ok(Self { h, capacity: self.capacity, per: false, phantom: PhantomData })
+    }
+}
+
 impl<O, A> Drop for AmdReplayBuffer<O, A>
 where
     O: RowBatch,
