@@ -264,6 +264,20 @@ class GroupTrainerPostC(C.Structure):
                 ("model_dirs", C.POINTER(C.c_char_p)), ("eval_ops", GroupEvalOps), ("save_member", G_SAVE_MEMBER_FN)]
 
 
+# bdr_bc_group_eval_ops / bdr_bc_group_trainer_post: the lockstep evaluator of a BC group and post_process in its offline loop
+BG_SAMPLE_MEMBERS_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_void_p))
+
+
+class BcGroupEvalOps(C.Structure):
+    _fields_ = [("group", C.c_void_p), ("n_members", C.c_uint32), ("reserved", C.c_uint32), ("sample_members", BG_SAMPLE_MEMBERS_FN)]
+
+
+class BcGroupTrainerPostC(C.Structure):
+    _fields_ = [("eval_interval", C.c_uint64), ("save_interval", C.c_uint64), ("evaluators", C.POINTER(EvaluatorC)),
+                ("model_dirs", C.POINTER(C.c_char_p)), ("eval_ops", BcGroupEvalOps), ("save_member", G_SAVE_MEMBER_FN)]
+
+
 BDR_ACT_PATH_DEFAULT, BDR_ACT_PATH_LAYERS, BDR_ACT_PATH_FUSED = 0, 1, 2
 BDR_TRAINER_EVENT_EVAL = 4
 
@@ -335,6 +349,8 @@ ABI_SYMBOLS = [
     "bdr_trainer_train_group_post", "bdr_agent_group_info",
     "bdr_replay_view_create", "bdr_bc_group_create", "bdr_bc_group_destroy", "bdr_bc_group_size", "bdr_bc_group_member", "bdr_bc_group_info",
     "bdr_bc_group_opt", "bdr_bc_group_opt_with_scalars", "bdr_bc_group_sync",
+    "bdr_bc_group_sample", "bdr_bc_group_sample_members", "bdr_bc_group_eval_ops_default", "bdr_evaluate_bc_group",
+    "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default", "bdr_trainer_train_offline_group_post",
 ]
 
 _lib = None
@@ -362,7 +378,8 @@ def lib() -> C.CDLL:
                         "bdr_candle_dqn_cnn_config_default",
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
                         "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default",
-                        "bdr_group_trainer_ops_default", "bdr_group_eval_ops_default", "bdr_group_trainer_post_default"):
+                        "bdr_group_trainer_ops_default", "bdr_group_eval_ops_default", "bdr_group_trainer_post_default",
+                        "bdr_bc_group_eval_ops_default", "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -534,6 +551,17 @@ def lib() -> C.CDLL:
     L.bdr_group_trainer_post_default.argtypes = [C.POINTER(GroupTrainerPostC), vp]
     L.bdr_trainer_train_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(C.c_uint64), C.POINTER(GroupTrainerOps), C.POINTER(EnvVtable),
                                                C.POINTER(GroupTrainerPostC), GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
+    L.bdr_bc_group_sample.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.bdr_bc_group_sample_members.argtypes = [vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
+    L.bdr_bc_group_eval_ops_default.restype = None
+    L.bdr_bc_group_eval_ops_default.argtypes = [C.POINTER(BcGroupEvalOps), vp]
+    L.bdr_evaluate_bc_group.argtypes = [C.POINTER(EvaluatorC), C.POINTER(BcGroupEvalOps), C.POINTER(EvalResultC)]
+    L.bdr_bc_group_trainer_ops_default.restype = None
+    L.bdr_bc_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
+    L.bdr_bc_group_trainer_post_default.restype = None
+    L.bdr_bc_group_trainer_post_default.argtypes = [C.POINTER(BcGroupTrainerPostC), vp]
+    L.bdr_trainer_train_offline_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(GroupTrainerOps), C.POINTER(BcGroupTrainerPostC),
+                                                       GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     _lib = L
     return L
 

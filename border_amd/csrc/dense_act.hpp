@@ -24,6 +24,9 @@
 //   Bounds.  rows: block row r is read from memory only for m0 + r < n and column c < O, and stored (out / idx) only for
 //   m0 + r < n; LDS rows r >= n - m0 are zero.  LDS: r < 32, c < Kp or Np <= W.  Weights: k < Kp, column < Np of the layer
 //   (t < Np / 32).  out: (m0 + r) * A + j < n * A; idx: m0 + r < n.  mean / std: c < O = the normaliser's dim (checked by the host).
+//   A group.  The body is a function, dense_act_body: k_dense_act runs it on its argument struct, k_bc_act_group (bc_group.hpp) on
+//   args[member] and calls[member] of a BC group with the member as grid dimension y - P members with a row each are P workgroups on
+//   P CUs in one launch, the form this kernel has anyway.
 #pragma once
 
 namespace bdr {
@@ -129,10 +132,15 @@ __device__ __forceinline__ void dense_act_land(const f32x4 (&v)[8], const f32x4&
     asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(b));
 }
 
-template <int TEAMS>
-__global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
+// The body of k_dense_act and of the group entry k_bc_act_group (bc_group.hpp).  `a`: the network and the epilogue (layers, widths,
+// mode, kind, A, O, W); `call`: the words of this call (rows, row_stride, f64, n, mean, std, out, idx).  The standalone kernel passes
+// its one argument struct as both; the group entry passes a member's entries of two arrays it reads in place through the constant
+// address space, so Args and Call are template parameters and a layer is copied field by field (a struct copy would have to bind a
+// generic reference to the constant address space).  BC_ONLY: the caller has refused every mode but DA_BC - the other epilogues,
+// which leave the kernel early or take a SampleElem by reference, are not instantiated and every thread returns to the entry.
+template <int TEAMS, bool BC_ONLY, class Args, class Call>
+__device__ __forceinline__ void dense_act_body(const Args& a, const Call& call, float* da_lds)
 {
-    extern __shared__ __attribute__((aligned(16))) float da_lds[];
     constexpr int NTHR = 256 * TEAMS;
     const int S = 32 * (a.W + 4);
     float* cur = da_lds;
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), team = wv >> 2, wave = wv & 3;
     float (*red)[32][33] = reinterpret_cast<float (*)[32][33]>(da_lds + 2 * (size_t)S + (size_t)team * 4 * 32 * 33);
     const int m0 = (int)blockIdx.x * 32;
-    const int rows_here = min(32, a.n - m0);
+    const int rows_here = min(32, call.n - m0);
     const int r = (tid & 255) >> 3, c4 = (tid & 7) * 4;   // the thread's element quad of its team's tile (dense_small_body's)
 
     // the first round's weights and bias: they depend on nothing, issued before the rows are read
@@ -149,7 +157,7 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
 #pragma unroll
     for (int q = 0; q < 8; ++q) { bv[q] = f32x4{0.f, 0.f, 0.f, 0.f}; bvn[q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     {
-        const DenseActLayer& l0 = a.L[0];
+        const auto& l0 = a.L[0];
         if (team * 32 < l0.Np) {
             bias = *reinterpret_cast<const f32x4*>(l0.b + team * 32 + c4);
             if (l0.Kp <= 256) dense_small_load_b<false>(l0.w, l0.Np, team * 32, l0.Kp, wave, lane, bv);
@@ -162,9 +170,9 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
             const int rr = e / Kp0, c = e % Kp0;
             float x = 0.f;
             if (rr < rows_here && c < a.O) {
-                const uint8_t* row = a.rows + (size_t)(m0 + rr) * a.row_stride;
-                x = a.f64 ? (float)reinterpret_cast<const double*>(row)[c] : reinterpret_cast<const float*>(row)[c];
-                if (a.mean) x = obs_norm_z(x, a.mean[c], a.std[c]);
+                const uint8_t* row = call.rows + (size_t)(m0 + rr) * call.row_stride;
+                x = call.f64 ? (float)reinterpret_cast<const double*>(row)[c] : reinterpret_cast<const float*>(row)[c];
+                if (call.mean) x = obs_norm_z(x, call.mean[c], call.std[c]);
             }
             cur[rr * ld0 + c] = x;
         }
@@ -173,7 +181,8 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
 
     // ---- the layers: TEAMS tiles per round
     for (int l = 0; l < a.nl; ++l) {
-        const DenseActLayer ly = a.L[l];
+        DenseActLayer ly;
+        ly.w = a.L[l].w; ly.b = a.L[l].b; ly.Kp = a.L[l].Kp; ly.Np = a.L[l].Np; ly.relu = a.L[l].relu;
         const int ldi = ly.Kp + 4, ldo = ly.Np + 4, NT = ly.Np / 32;
         const float* arow = cur + (lane & 31) * ldi;
         const bool pre = ly.Kp <= 256;
@@ -186,7 +195,7 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
                 if (tn >= NT) { ln = l + 1; tn = 0; }
                 tn += team;
                 if (ln < a.nl) {
-                    const DenseActLayer& lx = a.L[ln];
+                    const auto& lx = a.L[ln];
                     if (tn * 32 < lx.Np) {
                         biasn = *reinterpret_cast<const f32x4*>(lx.b + tn * 32 + c4);
                         if (lx.Kp <= 256) dense_small_load_b<false>(lx.w, lx.Np, tn * 32, lx.Kp, wave, lane, bvn);
@@ -216,24 +225,34 @@ __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
 
     // ---- epilogue: the last layer's rows [32][Np + 4] in cur -> actions
     const int ldz = a.L[a.nl - 1].Np + 4;
-    if (a.mode == DA_BC_DISCRETE) {
-        if (tid < rows_here) a.idx[m0 + tid] = bc_argmax(a.kind, cur + tid * ldz, a.A);
-        return;
-    }
-    if (a.mode == DA_DQN) {   // the candle DQN (dqn/base.rs:203): the Q rows themselves and each row's first maximum (dqn_q_argmax)
-        for (int e = tid; e < rows_here * a.A; e += NTHR) {
-            const int rr = e / a.A, j = e % a.A;
-            a.out[(size_t)(m0 + rr) * a.A + j] = cur[rr * ldz + j];
+    if constexpr (!BC_ONLY) {
+        if (a.mode == DA_BC_DISCRETE) {
+            if (tid < rows_here) call.idx[m0 + tid] = bc_argmax(a.kind, cur + tid * ldz, a.A);
+            return;
         }
-        if (tid < rows_here) a.idx[m0 + tid] = dqn_q_argmax(cur + tid * ldz, a.A);
-        return;
+        if (a.mode == DA_DQN) {   // the candle DQN (dqn/base.rs:203): the Q rows themselves and each row's first maximum (dqn_q_argmax)
+            for (int e = tid; e < rows_here * a.A; e += NTHR) {
+                const int rr = e / a.A, j = e % a.A;
+                call.out[(size_t)(m0 + rr) * a.A + j] = cur[rr * ldz + j];
+            }
+            if (tid < rows_here) call.idx[m0 + tid] = dqn_q_argmax(cur + tid * ldz, a.A);
+            return;
+        }
     }
     for (int e = tid; e < rows_here * a.A; e += NTHR) {
         const int rr = e / a.A, j = e % a.A;
         const size_t t = (size_t)(m0 + rr) * a.A + j;
         const float z = cur[rr * ldz + j];
-        a.out[t] = a.mode == DA_CANDLE ? candle_sample_elem(a.e, z, j, t, a.e.mlp2 ? cur[rr * ldz + a.A + j] : 0.f) : bc_act_out(a.kind, z);
+        if constexpr (BC_ONLY) call.out[t] = bc_act_out(a.kind, z);
+        else call.out[t] = a.mode == DA_CANDLE ? candle_sample_elem(a.e, z, j, t, a.e.mlp2 ? cur[rr * ldz + a.A + j] : 0.f) : bc_act_out(a.kind, z);
     }
+}
+
+template <int TEAMS>
+__global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float da_lds[];
+    dense_act_body<TEAMS, false>(a, a, da_lds);
 }
 
 }  // namespace

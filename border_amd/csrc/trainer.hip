@@ -24,6 +24,10 @@
 
 using namespace bdr;
 
+namespace bdr {
+int bc_group_act_dim(const void* group, uint32_t member);   // bc.hip (bc_group.hpp)
+}
+
 namespace {
 using Clock = std::chrono::steady_clock;
 
@@ -237,7 +241,115 @@ int32_t check_group_eval(const bdr_evaluator* evs, const bdr_group_eval_ops* ops
     return BDR_OK;
 }
 
-int32_t check_group_post(const bdr_group_trainer_post* post, uint32_t P)
+// the BC group's entries behind the function tables (bdr_bc_group_trainer_ops_default, bdr_bc_group_eval_ops_default)
+int32_t dbg_set_train(void* g, int32_t on)
+{
+    uint32_t n = 0;
+    BDR_TRY(bdr_bc_group_size((bdr_bc_group*)g, &n));
+    for (uint32_t i = 0; i < n; ++i) {
+        bdr_agent* m = nullptr;
+        BDR_TRY(bdr_bc_group_member((bdr_bc_group*)g, i, &m));
+        BDR_TRY(bdr_agent_set_train(m, on));
+    }
+    return BDR_OK;
+}
+int32_t dbg_opt(void* g, void* const* b) { return bdr_bc_group_opt((bdr_bc_group*)g, (bdr_replay* const*)b); }
+int32_t dbg_opt_rec(void* g, void* const* b, float* out, int32_t cap, int32_t* n)
+{
+    return bdr_bc_group_opt_with_scalars((bdr_bc_group*)g, (bdr_replay* const*)b, out, cap, n);
+}
+int32_t dbg_sample_members(void* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, const void* const* rows, const int32_t* dtypes,
+                           float* const* act_out)
+{
+    return bdr_bc_group_sample_members((bdr_bc_group*)g, members, n_sel, norms, 1, rows, dtypes, act_out);
+}
+int32_t dbg_save_member(void* g, uint32_t member, const char* dir)
+{
+    bdr_agent* m = nullptr;
+    BDR_TRY(bdr_bc_group_member((bdr_bc_group*)g, member, &m));
+    return d_save(m, dir);
+}
+
+// every refusal of bdr_evaluate_bc_group, naming the member: the group acts on host rows, f32 or float64, and writes one f32 action row
+int32_t check_bc_group_eval(const bdr_evaluator* evs, const bdr_bc_group_eval_ops* ops)
+{
+    BDR_REQUIRE(evs && ops, "null argument");
+    BDR_REQUIRE(ops->sample_members, "the group evaluation function table is incomplete");
+    BDR_REQUIRE(ops->n_members >= 1, "the group evaluation function table names no members");
+    for (uint32_t p = 0; p < ops->n_members; ++p) {
+        const bdr_evaluator& ev = evs[p];
+        BDR_REQUIRE(ev.env.reset_with_index && ev.env.step, "member %u: the evaluator's environment function table is incomplete", p);
+        BDR_REQUIRE(ev.n_episodes >= 1, "member %u: n_episodes must be >= 1", p);
+        BDR_REQUIRE(ev.obs_row_bytes > 0, "member %u: obs_row_bytes must be set", p);
+        if (ops->sample_members == dbg_sample_members) {
+            const int A = bc_group_act_dim(ops->group, p);
+            BDR_REQUIRE(A > 0, "member %u: the group has no such member", p);
+            BDR_REQUIRE(ev.act_row_bytes == (uint64_t)A * 4, "member %u: a BC group acts with one f32 action row per member: act_row_bytes must be 4 * act_dim = %d", p, A * 4);
+        } else {
+            BDR_REQUIRE(ev.act_row_bytes > 0 && ev.act_row_bytes % 4 == 0, "member %u: a BC group acts with f32 action rows: act_row_bytes must be a positive multiple of 4", p);
+        }
+        BDR_REQUIRE(ev.obs_dtype == BDR_DTYPE_F32 || ev.obs_dtype == BDR_DTYPE_F64, "member %u: obs_dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64", p);
+        BDR_REQUIRE(!ev.env.obs_on_device, "member %u: a group acts on host rows (obs_on_device environments are not supported)", p);
+    }
+    return BDR_OK;
+}
+
+// default_evaluator.rs:64-88 for every member in lockstep, the one loop of bdr_evaluate_group and bdr_evaluate_bc_group: member p sees
+// exactly the calls bdr_evaluate(&evs[p], member p) makes.  act(sel, n_sel, rows, act_rows): ONE acting call over the members with an
+// open episode; rows[p] is member p's observation row and act_rows[p] its action row of evs[p].act_row_bytes (16-byte aligned, the
+// rows of all members contiguous in member order when they have one size).
+template <class Act>
+int32_t evaluate_lockstep(const bdr_evaluator* evs, uint32_t P, Act&& act, bdr_eval_result* out)
+{
+    std::vector<std::vector<uint8_t>> prev(P), next(P);
+    for (uint32_t p = 0; p < P; ++p) { prev[p].resize(evs[p].obs_row_bytes); next[p].resize(evs[p].obs_row_bytes); }
+    std::vector<const void*> rows(P);
+    size_t act_bytes = 0;
+    for (uint32_t p = 0; p < P; ++p) act_bytes += evs[p].act_row_bytes;
+    std::vector<uint64_t> act_store((act_bytes + 7) / 8 + 1);   // (u64 words: aligned for i64 and f32 rows alike)
+    std::vector<uint8_t*> act_rows(P);
+    for (uint32_t p = 0, off = 0; p < P; off += (uint32_t)evs[p].act_row_bytes, ++p) act_rows[p] = reinterpret_cast<uint8_t*>(act_store.data()) + off;
+    std::vector<float> r_total(P, 0.f), reward(P);
+    std::vector<int8_t> term(P), trunc(P), open(P, 0);
+    std::vector<uint64_t> ix(P, 0), n_steps(P, 0);
+    std::vector<uint32_t> sel;
+    sel.reserve(P);
+    for (;;) {
+        sel.clear();
+        for (uint32_t p = 0; p < P; ++p) {   // a member with episodes left and none open starts its next one
+            if (!open[p] && ix[p] < evs[p].n_episodes) {
+                BDR_TRY(evs[p].env.reset_with_index(evs[p].env.ctx, ix[p], prev[p].data()));
+                open[p] = 1;
+            }
+            if (open[p]) sel.push_back(p);
+            rows[p] = prev[p].data();
+        }
+        if (sel.empty()) break;   // ix == n_episodes for everybody
+        BDR_TRY(act(sel.data(), (uint32_t)sel.size(), rows.data(), act_rows.data()));
+        for (const uint32_t p : sel) {
+            reward[p] = 0; term[p] = 0; trunc[p] = 0;
+            BDR_TRY(evs[p].env.step(evs[p].env.ctx, act_rows[p], next[p].data(), &reward[p], &term[p], &trunc[p]));
+        }
+        for (const uint32_t p : sel) {
+            r_total[p] += reward[p];
+            n_steps[p] += 1;
+            if (term[p] == 1 || trunc[p] == 1) { open[p] = 0; ix[p] += 1; }   // step.rs:136-138
+            else prev[p].swap(next[p]);                                      // prev_obs = step.obs
+        }
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        const bdr_evaluator& ev = evs[p];
+        out[p].score = r_total[p] / (float)ev.n_episodes;
+        out[p].has_normalized = ev.has_ref_scores ? 1 : 0;
+        out[p].normalized = ev.has_ref_scores ? (out[p].score - ev.ref_min_score) / (ev.ref_max_score - ev.ref_min_score) : 0.f;   // border-minari/src/env.rs:162-168
+        out[p].n_steps = n_steps[p]; out[p].n_episodes = ev.n_episodes;
+    }
+    return BDR_OK;
+}
+
+// (Post: bdr_group_trainer_post or bdr_bc_group_trainer_post; check_eval: check_group_eval or check_bc_group_eval)
+template <class Post, class CheckEval>
+int32_t check_group_post(const Post* post, uint32_t P, CheckEval&& check_eval)
 {
     if (!post) return BDR_OK;
     BDR_REQUIRE(!post->eval_interval || post->evaluators, "eval_interval is set: post-processing needs one evaluator per member");
@@ -246,24 +358,26 @@ int32_t check_group_post(const bdr_group_trainer_post* post, uint32_t P)
         for (uint32_t p = 0; p < P; ++p) BDR_REQUIRE(post->model_dirs[p], "member %u: null model directory", p);
     if (post->eval_interval) {
         BDR_REQUIRE(post->eval_ops.n_members == P, "the evaluation function table names %u members, the loop %u", post->eval_ops.n_members, P);
-        BDR_TRY(check_group_eval(post->evaluators, &post->eval_ops));
+        BDR_TRY(check_eval(post->evaluators, &post->eval_ops));
     }
     return BDR_OK;
 }
 
 typedef void (*GroupObserver)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars, int32_t n_scalars);
 
-// trainer.rs:231-264 for every member, after an iteration that took an opt step; max_eval_reward[p] is member p's own
-int32_t group_post_process(State& s, const bdr_group_trainer_ops* ops, const bdr_group_trainer_post* post, std::vector<float>& max_eval_reward,
-                           GroupObserver obs, void* ctx)
+// trainer.rs:231-264 for every member, after an iteration that took an opt step; max_eval_reward[p] is member p's own.
+// evaluate: bdr_evaluate_group or bdr_evaluate_bc_group; save_default: the group kind's own save of a member
+template <class Post, class Evaluate>
+int32_t group_post_process(State& s, const bdr_group_trainer_ops* ops, const Post* post, Evaluate&& evaluate, int32_t (*save_default)(void*, uint32_t, const char*),
+                           std::vector<float>& max_eval_reward, GroupObserver obs, void* ctx)
 {
     if (!post) return BDR_OK;
     const uint32_t P = ops->n_members;
-    const auto save = post->save_member ? post->save_member : dg_save_member;
+    const auto save = post->save_member ? post->save_member : save_default;
     if (post->eval_interval && s.opt_steps % post->eval_interval == 0) {
         BDR_TRY(ops->set_train(ops->group, 0));
         std::vector<bdr_eval_result> r(P);
-        BDR_TRY(bdr_evaluate_group(post->evaluators, &post->eval_ops, r.data()));
+        BDR_TRY(evaluate(post->evaluators, &post->eval_ops, r.data()));
         BDR_TRY(ops->set_train(ops->group, 1));
         if (obs)
             for (uint32_t p = 0; p < P; ++p) {
@@ -279,6 +393,16 @@ int32_t group_post_process(State& s, const bdr_group_trainer_ops* ops, const bdr
     if (post->save_interval > 0 && s.opt_steps % post->save_interval == 0)
         for (uint32_t p = 0; p < P; ++p) BDR_TRY(save(ops->group, p, (std::string(post->model_dirs[p]) + "/" + std::to_string(s.opt_steps)).c_str()));
     return BDR_OK;
+}
+
+// cost_record once for the group: every member's observer receives the one COST event, in member order
+void group_cost_record(State& s, GroupObserver obs, void* obs_ctx, uint32_t P)
+{
+    struct Fan { GroupObserver obs; void* ctx; uint32_t P; } fan{obs, obs_ctx, P};
+    cost_record(s, obs ? +[](void* f, uint64_t es, uint64_t os, int32_t ev, const float* sc, int32_t n) {
+        const Fan* fn = (const Fan*)f;
+        for (uint32_t p = 0; p < fn->P; ++p) fn->obs(fn->ctx, p, es, os, ev, sc, n);
+    } : nullptr, &fan);
 }
 }  // namespace
 
@@ -450,46 +574,88 @@ int32_t bdr_evaluate_group(const bdr_evaluator* evs, const bdr_group_eval_ops* o
 {
     BDR_REQUIRE(evs && ops && out, "null argument");
     BDR_TRY(check_group_eval(evs, ops));
+    // (act_row_bytes == 8 for every member: the action rows are one i64 array indexed by member)
+    return evaluate_lockstep(evs, ops->n_members, [&](const uint32_t* sel, uint32_t n_sel, const void* const* rows, uint8_t* const* act_rows) {
+        return ops->sample_members(ops->group, sel, n_sel, rows, reinterpret_cast<int64_t*>(act_rows[0]));
+    }, out);
+}
+
+void bdr_bc_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_bc_group* group)
+{
+    if (!ops) return;
+    memset(ops, 0, sizeof *ops);
+    ops->group = group;
+    if (group) (void)bdr_bc_group_size(group, &ops->n_members);
+    ops->sample_members = dbg_sample_members;
+}
+
+// the same loop for a BC group: f32 action rows, f32 or float64 observation rows, a normaliser per member
+int32_t bdr_evaluate_bc_group(const bdr_evaluator* evs, const bdr_bc_group_eval_ops* ops, bdr_eval_result* out)
+{
+    BDR_REQUIRE(evs && ops && out, "null argument");
+    BDR_TRY(check_bc_group_eval(evs, ops));
     const uint32_t P = ops->n_members;
-    std::vector<std::vector<uint8_t>> prev(P), next(P);
-    for (uint32_t p = 0; p < P; ++p) { prev[p].resize(evs[p].obs_row_bytes); next[p].resize(evs[p].obs_row_bytes); }
-    std::vector<const void*> rows(P);
-    std::vector<int64_t> act(P);
-    std::vector<float> r_total(P, 0.f), reward(P);
-    std::vector<int8_t> term(P), trunc(P), open(P, 0);
-    std::vector<uint64_t> ix(P, 0), n_steps(P, 0);
-    std::vector<uint32_t> sel;
-    sel.reserve(P);
+    std::vector<const bdr_obs_norm*> norms(P);
+    std::vector<int32_t> dtypes(P);
+    std::vector<float*> act_out(P);
+    for (uint32_t p = 0; p < P; ++p) { norms[p] = evs[p].norm; dtypes[p] = evs[p].obs_dtype; }
+    return evaluate_lockstep(evs, P, [&](const uint32_t* sel, uint32_t n_sel, const void* const* rows, uint8_t* const* act_rows) {
+        for (uint32_t p = 0; p < P; ++p) act_out[p] = reinterpret_cast<float*>(act_rows[p]);
+        return ops->sample_members(ops->group, sel, n_sel, norms.data(), rows, dtypes.data(), act_out.data());
+    }, out);
+}
+
+void bdr_bc_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_bc_group* group, bdr_replay* const* buffers)
+{
+    if (!ops) return;
+    memset(ops, 0, sizeof *ops);
+    ops->group = group; ops->buffers = (void* const*)buffers;
+    if (group) (void)bdr_bc_group_size(group, &ops->n_members);
+    ops->set_train = dbg_set_train; ops->opt = dbg_opt; ops->opt_with_record = dbg_opt_rec;
+}
+
+void bdr_bc_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_bc_group* group)
+{
+    if (!post) return;
+    memset(post, 0, sizeof *post);
+    bdr_bc_group_eval_ops_default(&post->eval_ops, group);
+    post->save_member = dbg_save_member;
+}
+
+// Trainer::train_offline (trainer.rs:330-384) with post_process for every member of a group in lockstep
+int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, const bdr_group_trainer_ops* ops, const bdr_bc_group_trainer_post* post,
+                                             void (*obs)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars,
+                                                         int32_t n_scalars),
+                                             void* obs_ctx, bdr_trainer_stats* out)
+{
+    BDR_REQUIRE(c_in && ops, "null argument");
+    BDR_REQUIRE(c_in->max_opts >= 1, "max_opts must be >= 1");
+    BDR_REQUIRE(ops->set_train && ops->opt && ops->opt_with_record, "group function table is incomplete");
+    const uint32_t P = ops->n_members;
+    BDR_REQUIRE(P >= 1 && ops->buffers, "the group function table names no members or no buffers");
+    BDR_TRY(check_group_post(post, P, check_bc_group_eval));
+    bdr_trainer_config c = *c_in;
+    c.warmup_period = 0; c.opt_interval = 1;            // trainer.rs:345-346
+    std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member
+    GroupAdapter ga{ops, std::vector<float>((size_t)P * 128), std::vector<int32_t>(P, 0)};
+    bdr_trainer_ops t{};
+    t.agent = &ga; t.agent_set_train = ga_set_train; t.agent_opt = ga_opt; t.agent_opt_with_record = ga_opt_rec;
+    State s; s.c = &c; s.ops = &t;
+    BDR_TRY(t.agent_set_train(t.agent, 1));
     for (;;) {
-        sel.clear();
-        for (uint32_t p = 0; p < P; ++p) {   // a member with episodes left and none open starts its next one
-            if (!open[p] && ix[p] < evs[p].n_episodes) {
-                BDR_TRY(evs[p].env.reset_with_index(evs[p].env.ctx, ix[p], prev[p].data()));
-                open[p] = 1;
-            }
-            if (open[p]) sel.push_back(p);
-            rows[p] = prev[p].data();
-        }
-        if (sel.empty()) break;   // ix == n_episodes for everybody
-        BDR_TRY(ops->sample_members(ops->group, sel.data(), (uint32_t)sel.size(), rows.data(), act.data()));
-        for (const uint32_t p : sel) {
-            reward[p] = 0; term[p] = 0; trunc[p] = 0;
-            BDR_TRY(evs[p].env.step(evs[p].env.ctx, &act[p], next[p].data(), &reward[p], &term[p], &trunc[p]));
-        }
-        for (const uint32_t p : sel) {
-            r_total[p] += reward[p];
-            n_steps[p] += 1;
-            if (term[p] == 1 || trunc[p] == 1) { open[p] = 0; ix[p] += 1; }   // step.rs:136-138
-            else prev[p].swap(next[p]);                                      // prev_obs = step.obs
-        }
+        s.env_steps += 1;
+        // ---- train_step, once for all members; every member's event; post_process; the cost record
+        bool is_opt = false, with_record = false;
+        BDR_TRY(train_step(s, &is_opt, &with_record));
+        const int32_t event = with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT;
+        if (obs)
+            for (uint32_t p = 0; p < P; ++p) obs(obs_ctx, p, s.env_steps, s.opt_steps, event, ga.scalars.data() + (size_t)p * 128, with_record ? ga.n_scalars[p] : 0);
+        BDR_TRY(group_post_process(s, ops, post, bdr_evaluate_bc_group, dbg_save_member, max_eval_reward, obs, obs_ctx));
+        group_cost_record(s, obs, obs_ctx, P);
+        if (s.opt_steps == c.max_opts) break;   // trainer.rs:323-325
     }
-    for (uint32_t p = 0; p < P; ++p) {
-        const bdr_evaluator& ev = evs[p];
-        out[p].score = r_total[p] / (float)ev.n_episodes;
-        out[p].has_normalized = ev.has_ref_scores ? 1 : 0;
-        out[p].normalized = ev.has_ref_scores ? (out[p].score - ev.ref_min_score) / (ev.ref_max_score - ev.ref_min_score) : 0.f;   // border-minari/src/env.rs:162-168
-        out[p].n_steps = n_steps[p]; out[p].n_episodes = ev.n_episodes;
-    }
+    if (out)
+        for (uint32_t p = 0; p < P; ++p) fill_stats(s, out + p);
     return BDR_OK;
 }
 
@@ -519,7 +685,7 @@ int32_t bdr_trainer_train_group_post(const bdr_trainer_config* c, const uint64_t
         BDR_REQUIRE(!envs[p].obs_on_device, "member %u: the group loop takes host observations (obs_on_device environments are not supported)", p);
         BDR_REQUIRE(obs_row_bytes[p] > 0, "member %u: obs_row_bytes must be set", p);
     }
-    BDR_TRY(check_group_post(post, P));
+    BDR_TRY(check_group_post(post, P, check_group_eval));
     std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member
     GroupAdapter ga{ops, std::vector<float>((size_t)P * 128), std::vector<int32_t>(P, 0)};
     bdr_trainer_ops t{};
@@ -564,12 +730,8 @@ int32_t bdr_trainer_train_group_post(const bdr_trainer_config* c, const uint64_t
         const int32_t event = is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP;
         if (obs)
             for (uint32_t p = 0; p < P; ++p) obs(obs_ctx, p, s.env_steps, s.opt_steps, event, ga.scalars.data() + (size_t)p * 128, with_record ? ga.n_scalars[p] : 0);
-        if (is_opt) BDR_TRY(group_post_process(s, ops, post, max_eval_reward, obs, obs_ctx));
-        struct Fan { decltype(obs) obs; void* ctx; uint32_t P; } fan{obs, obs_ctx, P};
-        cost_record(s, obs ? +[](void* f, uint64_t es, uint64_t os, int32_t ev, const float* sc, int32_t n) {
-            const Fan* fn = (const Fan*)f;
-            for (uint32_t p = 0; p < fn->P; ++p) fn->obs(fn->ctx, p, es, os, ev, sc, n);
-        } : nullptr, &fan);
+        if (is_opt) BDR_TRY(group_post_process(s, ops, post, bdr_evaluate_group, dg_save_member, max_eval_reward, obs, obs_ctx));
+        group_cost_record(s, obs, obs_ctx, P);
         if (s.opt_steps == c->max_opts) break;   // trainer.rs:323-325
     }
     if (out)

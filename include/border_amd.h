@@ -1376,6 +1376,66 @@ BDR_API int32_t bdr_bc_group_opt(bdr_bc_group* g, bdr_replay* const* buffers);
 BDR_API int32_t bdr_bc_group_opt_with_scalars(bdr_bc_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);
 BDR_API int32_t bdr_bc_group_sync(bdr_bc_group* g);
 
+/* Policy::sample of the members of a BC group in ONE launch: the one-launch acting kernel (bdr_agent_set_act_path, BDR_ACT_PATH_FUSED)
+ * with the member as one more grid dimension, one workgroup per member and block of 32 rows.  Every array is indexed by MEMBER:
+ * rows[i] = n host rows of obs_dim elements of dtypes[i] (BDR_DTYPE_F32 / BDR_DTYPE_F64), norms[i] = the
+ * normaliser applied to member i's rows (norms or any entry may be NULL), act_out[i] receives [n][act_dim] f32: the bits of
+ * bdr_agent_sample_raw(member i, norms[i], n, rows[i], dtypes[i], 0, 0, act_out[i], NULL) on either act path.  The same n, 1 <= n <=
+ * 65536, holds for every member; two members may name the same rows.  The call is synchronous and counts as one launch of the group
+ * (bdr_group_info::kernel_launches); n_opts does not move.  _sample_members: only members[0..n_sel) act (strictly ascending); a member
+ * that is not selected sees nothing of the call - its entries of the arrays are not read and nothing of it is written.  With every
+ * member selected it enqueues what _sample enqueues.
+ * Refused with BDR_ERR_INVALID before anything is enqueued, naming the member: a NULL rows[i] / act_out[i] of a selected member; an
+ * empty, not strictly ascending or out-of-range member list; a normaliser that is not ready, has another dim or lives on another
+ * device; an unknown dtype; a network whose widest padded layer exceeds 512 (such members keep acting standalone); rows or actions of
+ * one call beyond 64 MiB (split the call). */
+BDR_API int32_t bdr_bc_group_sample(bdr_bc_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
+                                    const int32_t* dtypes, float* const* act_out);
+BDR_API int32_t bdr_bc_group_sample_members(bdr_bc_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms,
+                                            uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out);
+
+/* bdr_evaluate_group's rule, word for word, for a BC group: resets in member order, ONE acting call per round over the members with
+ * an open episode, steps in member order, one f32 accumulator per member in call order; a member that has finished its episodes
+ * leaves the selection; score and normalised score as bdr_evaluate.  Member i sees exactly the calls bdr_evaluate(&evs[i], member i)
+ * makes.  The differences: actions are f32 rows - act_row_bytes must be 4 * act_dim (checked against the member by the default
+ * table; a positive multiple of 4 with another table) -, obs_dtype may be BDR_DTYPE_F32 or BDR_DTYPE_F64 and norm may be set, per
+ * member.  env.obs_on_device is still refused.  The hook receives the rows as the environments wrote them and the evaluators' norm
+ * and obs_dtype, all indexed by member, and writes member i's action row to act_out[i]. */
+typedef struct bdr_bc_group_eval_ops {
+    void* group;
+    uint32_t n_members;
+    uint32_t reserved;
+    /* bdr_bc_group_sample_members with n = 1 */
+    int32_t (*sample_members)(void* group, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, const void* const* rows,
+                              const int32_t* dtypes, float* const* act_out);
+} bdr_bc_group_eval_ops;
+BDR_API void bdr_bc_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_bc_group* group);
+BDR_API int32_t bdr_evaluate_bc_group(const bdr_evaluator* evs, const bdr_bc_group_eval_ops* ops, bdr_eval_result* out);
+
+/* Trainer::train_offline (trainer.rs:330-384) with Trainer::post_process (:231-264) for the members of a group in lockstep.
+ * set_train(1) once; per iteration env_steps += 1, ONE group opt - opt_with_record when (opt_steps + 1) %
+ * record_agent_info_interval == 0 -, the members' OPT / OPT_RECORD events in member order, post_process as bdr_group_trainer_post
+ * describes it (bdr_evaluate_bc_group in place of bdr_evaluate_group), the COST event (average_opt_time only: the offline loop
+ * samples nothing), stop at max_opts.  An interval of 0 means never; the timer wraps opt* only.  Member i's observer sees the event
+ * sequence bdr_trainer_train_offline_post gives a lone agent.  ops->sample and ops->push are not read and may be NULL; post may be
+ * NULL.  Refused before anything runs: what bdr_trainer_train_group_post refuses of c, ops and post. */
+typedef struct bdr_bc_group_trainer_post {
+    uint64_t eval_interval;                 /* 0 = never */
+    uint64_t save_interval;                 /* 0 = never */
+    const bdr_evaluator* evaluators;        /* [n_members]; needed when eval_interval > 0 */
+    const char* const* model_dirs;          /* [n_members]; needed when something is saved */
+    bdr_bc_group_eval_ops eval_ops;
+    int32_t (*save_member)(void* group, uint32_t member, const char* dir);   /* NULL: mkdir -p + bdr_agent_save_params of the member */
+} bdr_bc_group_trainer_post;
+/* set_train over the members, opt = bdr_bc_group_opt, opt_with_record = bdr_bc_group_opt_with_scalars; sample and push stay NULL */
+BDR_API void bdr_bc_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_bc_group* group, bdr_replay* const* buffers);
+BDR_API void bdr_bc_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_bc_group* group);
+BDR_API int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c, const bdr_group_trainer_ops* ops,
+                                                     const bdr_bc_group_trainer_post* post,
+                                                     void (*observer)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps,
+                                                                      int32_t event, const float* scalars, int32_t n_scalars),
+                                                     void* observer_ctx, bdr_trainer_stats* out);
+
 /* ------------------------------------------------------------------------------------------
  * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)
  * Not the bdr_dqn_* agent above, which restates border-tch-agent/src/dqn.  Q-network = Mlp (mlp/base.rs, mlp.rs:14-24): ReLU after

@@ -521,6 +521,36 @@ pub struct bdr_group_trainer_post {
     pub save_member: Option<unsafe extern "C" fn(group: *mut c_void, member: u32, dir: *const c_char) -> i32>,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_bc_group_eval_ops {
+    pub group: *mut c_void,
+    pub n_members: u32,
+    pub reserved: u32,
+    pub sample_members: Option<
+        unsafe extern "C" fn(
+            group: *mut c_void,
+            members: *const u32,
+            n_sel: u32,
+            norms: *mut *const bdr_obs_norm,
+            rows: *mut *const c_void,
+            dtypes: *const i32,
+            act_out: *mut *const f32,
+        ) -> i32,
+    >,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct bdr_bc_group_trainer_post {
+    pub eval_interval: u64,
+    pub save_interval: u64,
+    pub evaluators: *const bdr_evaluator,
+    pub model_dirs: *mut *const c_char,
+    pub eval_ops: bdr_bc_group_eval_ops,
+    pub save_member: Option<unsafe extern "C" fn(group: *mut c_void, member: u32, dir: *const c_char) -> i32>,
+}
+
 pub type bdr_trainer_observer =
     Option<unsafe extern "C" fn(ctx: *mut c_void, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32)>;
 
@@ -1039,6 +1069,38 @@ extern "C" {
     pub fn bdr_bc_group_opt(g: *mut bdr_bc_group, buffers: *mut *const bdr_replay) -> i32;
     pub fn bdr_bc_group_opt_with_scalars(g: *mut bdr_bc_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
     pub fn bdr_bc_group_sync(g: *mut bdr_bc_group) -> i32;
+    pub fn bdr_bc_group_sample(
+        g: *mut bdr_bc_group,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const f32,
+    ) -> i32;
+    pub fn bdr_bc_group_sample_members(
+        g: *mut bdr_bc_group,
+        members: *const u32,
+        n_sel: u32,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const f32,
+    ) -> i32;
+    pub fn bdr_bc_group_eval_ops_default(ops: *mut bdr_bc_group_eval_ops, group: *mut bdr_bc_group);
+    pub fn bdr_evaluate_bc_group(evs: *const bdr_evaluator, ops: *const bdr_bc_group_eval_ops, out: *mut bdr_eval_result) -> i32;
+    pub fn bdr_bc_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_bc_group, buffers: *mut *const bdr_replay);
+    pub fn bdr_bc_group_trainer_post_default(post: *mut bdr_bc_group_trainer_post, group: *mut bdr_bc_group);
+    pub fn bdr_trainer_train_offline_group_post(
+        c: *const bdr_trainer_config,
+        ops: *const bdr_group_trainer_ops,
+        post: *const bdr_bc_group_trainer_post,
+        observer: Option<
+            unsafe extern "C" fn(ctx: *mut c_void, member: u32, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32),
+        >,
+        observer_ctx: *mut c_void,
+        out: *mut bdr_trainer_stats,
+    ) -> i32;
     pub fn bdr_agent_group_push(
         g: *mut bdr_agent_group,
         buffers: *mut *const bdr_replay,
