@@ -207,7 +207,7 @@ SAVE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_char_p)
 
 
 # bdr_group_info (bdr_agent_group_info): the form of a group and its launch counts
-GROUP_FORM_ONE_WORKGROUP, GROUP_FORM_LAYERS, GROUP_FORM_BC_LAYERS = 0, 1, 2
+GROUP_FORM_ONE_WORKGROUP, GROUP_FORM_LAYERS, GROUP_FORM_BC_LAYERS, GROUP_FORM_IQL_LAYERS = 0, 1, 2, 3
 
 
 class GroupInfoC(C.Structure):
@@ -351,6 +351,8 @@ ABI_SYMBOLS = [
     "bdr_bc_group_opt", "bdr_bc_group_opt_with_scalars", "bdr_bc_group_sync",
     "bdr_bc_group_sample", "bdr_bc_group_sample_members", "bdr_bc_group_eval_ops_default", "bdr_evaluate_bc_group",
     "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default", "bdr_trainer_train_offline_group_post",
+    "bdr_iql_group_create", "bdr_iql_group_destroy", "bdr_iql_group_size", "bdr_iql_group_member", "bdr_iql_group_info",
+    "bdr_iql_group_opt", "bdr_iql_group_opt_with_scalars", "bdr_iql_group_sync",
 ]
 
 _lib = None
@@ -539,6 +541,14 @@ def lib() -> C.CDLL:
     L.bdr_bc_group_opt.argtypes = [vp, vp]
     L.bdr_bc_group_opt_with_scalars.argtypes = [vp, vp, vp, i32, vp]
     L.bdr_bc_group_sync.argtypes = [vp]
+    L.bdr_iql_group_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_iql_group_destroy.argtypes = [vp]
+    L.bdr_iql_group_size.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.bdr_iql_group_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_iql_group_info.argtypes = [vp, C.POINTER(GroupInfoC)]
+    L.bdr_iql_group_opt.argtypes = [vp, vp]
+    L.bdr_iql_group_opt_with_scalars.argtypes = [vp, vp, vp, i32, vp]
+    L.bdr_iql_group_sync.argtypes = [vp]
     L.bdr_group_trainer_ops_default.restype = None
     L.bdr_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
     L.bdr_trainer_train_group.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(C.c_uint64), C.POINTER(GroupTrainerOps), C.POINTER(EnvVtable),

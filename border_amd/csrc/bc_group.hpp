@@ -23,6 +23,7 @@
 #pragma once
 #include "slot_ring.hpp"
 #include "device_arrays.hpp"
+#include "group_done.hpp"
 #include "bc_group_plan.hpp"
 
 static_assert(BG_FORM_DEFAULT == BDR_BC_KERNEL_DEFAULT && BG_FORM_GENERAL == BDR_BC_KERNEL_GENERAL && BG_FORM_FUSED == BDR_BC_KERNEL_FUSED &&
@@ -37,15 +38,8 @@ static_assert(offsetof(BcStep, word_pos) == offsetof(GatherStepWords, word_pos) 
 
 namespace {
 
-// gl_group_done's rule (group_layers.hpp): every workgroup of the launch counts, behind a barrier every thread reaches
-__device__ __forceinline__ void bg_group_done(unsigned* ticket, unsigned* seq_host, unsigned seq)
-{
-    __syncthreads();
-    if (threadIdx.x == 0 && atomicAdd(ticket, 1u) == gridDim.x * gridDim.y * gridDim.z - 1) {
-        atomicExch(ticket, 0u);   // (the next launch is behind this one in the stream)
-        __hip_atomic_store(seq_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
+// (bg_group_done - gl_group_done's rule, group_layers.hpp: every workgroup of the launch counts, behind a barrier every thread reaches -
+// lives in group_done.hpp, which the IQL group shares)
 
 // ---- the group entries: grid dimension y is the member -------------------------------------------------------------------------------
 __global__ void k_pack_rows_group(const BDR_CONST_AS PackRowsArgs* args)

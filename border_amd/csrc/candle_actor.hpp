@@ -128,7 +128,7 @@ struct CandleAgent : DenseAgent {
     uint64_t step_pi = 0, step_q = 0;
     uint64_t noise_counter = 0;
     // batch buffers (ensure_batch)
-    int B = 0;
+    int B = 0; uint64_t batch_gen = 0;   // batch_gen: bumped whenever the batch buffers are re-allocated (iql_group.hpp keys its static arguments on it)
     float *x_o = nullptr, *x_no = nullptr, *xq = nullptr;    // actor inputs [B][Kp] (obs, next_obs), critic input [B][Kq] (obs | act)
     std::vector<float*> p_act, p_dy;                         // actor on obs, its gradients
     std::vector<float*> c_act[4], t_act[4], c_dy[4];         // online critics, target critics, critic gradients
@@ -160,7 +160,7 @@ struct CandleAgent : DenseAgent {
         BDR_TRY(alloc(&h2_part, (size_t)pad64(A), BATCH));
         BDR_TRY(alloc(&samp, (size_t)Bn * A, BATCH));
         BDR_TRY(self().alloc_batch(Bn));
-        B = Bn;
+        B = Bn; batch_gen += 1;
         return BDR_OK;
     }
 

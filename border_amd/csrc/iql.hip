@@ -19,7 +19,10 @@ namespace {
 
 // obs / next_obs / act rows -> the zero-padded inputs of the value + actor ([B][Kp], obs and next_obs) and of the critics ([B][Kq], obs | act)
 struct IqlPackArgs { const float* obs; const float* next; const float* act; int O, A, B; float* x_o; float* x_no; int ldp; float* xq; int ldq; };
-__global__ __launch_bounds__(256) void k_iql_pack(IqlPackArgs p)
+// (the bodies of the four kernels below are functions over their argument struct: the kernel argument, or a member's entry of a device
+// array read in place - iql_group.hpp, where blockIdx.y is the member; `red` is the kernel's own 32 floats of LDS)
+template <class Args>
+__device__ __forceinline__ void iql_pack_body(const Args& p)
 {
     const int W = p.O + p.A;
     const size_t n = (size_t)p.B * W;
@@ -35,6 +38,7 @@ __global__ __launch_bounds__(256) void k_iql_pack(IqlPackArgs p)
         }
     }
 }
+__global__ __launch_bounds__(256) void k_iql_pack(IqlPackArgs p) { iql_pack_body(p); }
 
 // (a) update_value (iql/base.rs:75-86): q = min_i Qtgt_i(obs, act), u = q - V(obs), loss = mean(|tau - 1[u < 0]| u^2) (util.rs:262-266),
 // dL/dV = -2 |tau - 1[u < 0]| u / B (masked by the output ReLU when the value Mlp has one).  Column 0 of dv only: the padding columns
@@ -46,9 +50,9 @@ struct IqlValueArgs {
     float* q_min; float* v_out; float* u_out;   // probes [B]
     float* loss; int accumulate; int B;
 };
-__global__ __launch_bounds__(1024) void k_iql_value_loss(IqlValueArgs p)
+template <class Args>
+__device__ __forceinline__ void iql_value_loss_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     const float invB = 1.0f / (float)p.B;
     const float s = candle::row_sum(p.B, [&](int b) {
 #pragma clang fp contract(off)
@@ -68,6 +72,11 @@ __global__ __launch_bounds__(1024) void k_iql_value_loss(IqlValueArgs p)
     }, red);
     if (threadIdx.x == 0) p.loss[0] = candle::acc(p.accumulate ? p.loss[0] : 0.f, s, invB);
 }
+__global__ __launch_bounds__(1024) void k_iql_value_loss(IqlValueArgs p)
+{
+    __shared__ float red[32];
+    iql_value_loss_body(p, red);
+}
 
 // (b) update_critic (iql/base.rs:88-121): tgt = r + gamma_not_done * V'(next_obs), gamma_not_done = (1 - (term | trunc)) * gamma in f32
 // (util.rs:235-255); loss = mean_i mean_b loss(Q_i - tgt), MSE or smooth L1 (util.rs:144-152); dL/dQ_i = loss'(Q_i - tgt) / (NC * B)
@@ -78,9 +87,9 @@ struct IqlCriticArgs {
     float* tgt; float* v_next;   // [B]
     int loss_kind; float* loss; int accumulate; int B;
 };
-__global__ __launch_bounds__(1024) void k_iql_critic_loss(IqlCriticArgs p)
+template <class Args>
+__device__ __forceinline__ void iql_critic_loss_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     for (int b = threadIdx.x; b < p.B; b += 1024) {
 #pragma clang fp contract(off)
         const float vn = p.vn[(size_t)b * p.ldv];
@@ -108,6 +117,11 @@ __global__ __launch_bounds__(1024) void k_iql_critic_loss(IqlCriticArgs p)
     }
     if (threadIdx.x == 0) p.loss[0] = total;
 }
+__global__ __launch_bounds__(1024) void k_iql_critic_loss(IqlCriticArgs p)
+{
+    __shared__ float red[32];
+    iql_critic_loss_body(p, red);
+}
 
 // (c) + (d) update_actor (iql/base.rs:123-155): adv = min_i Qtgt_i(obs, act) - V'(obs); w = clamp(exp(inv_lambda adv), 0, exp_adv_max) or
 // softmax(inv_lambda adv) over the batch (one batch-wide max and sum); logp of the batch actions under N(mean, std^2), std =
@@ -124,7 +138,8 @@ struct IqlActorArgs {
     float* gmean; float* gh2;              // [B][ldm], [A]
     float* loss; int accumulate; int B;
 };
-__device__ __forceinline__ float iql_x(const IqlActorArgs& p, float a)
+template <class Args>
+__device__ __forceinline__ float iql_x(const Args& p, float a)
 {
 #pragma clang fp contract(off)
     if (!p.tanh_limit) return a;
@@ -132,9 +147,9 @@ __device__ __forceinline__ float iql_x(const IqlActorArgs& p, float a)
     const float r = (1.0f + t) / (1.0f - t);
     return 0.5f * logf(r);
 }
-__global__ __launch_bounds__(1024) void k_iql_actor_loss(IqlActorArgs p)
+template <class Args>
+__device__ __forceinline__ void iql_actor_loss_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     const float invB = 1.0f / (float)p.B;
     for (int b = threadIdx.x; b < p.B; b += 1024) {
 #pragma clang fp contract(off)
@@ -190,6 +205,11 @@ __global__ __launch_bounds__(1024) void k_iql_actor_loss(IqlActorArgs p)
         }, red);
         if (threadIdx.x == 0) p.gh2[j] = (h >= p.lo && h <= p.hi) ? s : 0.f;
     }
+}
+__global__ __launch_bounds__(1024) void k_iql_actor_loss(IqlActorArgs p)
+{
+    __shared__ float red[32];
+    iql_actor_loss_body(p, red);
 }
 
 }  // namespace
@@ -412,3 +432,7 @@ int32_t bdr_iql_sample_device(bdr_agent* base, uint64_t n, const void* obs_dev, 
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// the launch grouping of IQL agents (bdr_iql_group_*): it needs Iql and the kernel bodies above
+#include "iql_group.hpp"

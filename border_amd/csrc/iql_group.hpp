@@ -1,0 +1,596 @@
+// ================================================================================================
+// A group of IQL agents: Iql::opt_ (iql/base.rs:157-188) of every member in the launch sequence Iql::update enqueues for ONE member -
+// gather, pack, the critics', actor's and value's forwards, the value loss and step, V'(obs) | V'(next_obs), the critic loss and the
+// critics' step with the soft update riding on it, the target critics again, the actor loss and the actor's step - with every launch
+// serving ALL members: the member index is grid dimension y, the network instance (where the standalone launch has one) stays grid
+// dimension z, x stays the member's own grid (iql_group_plan.hpp has the rule and the grids).  A launch grouping, not an agent kind:
+// the members stay ordinary IQL agents on the group's stream.  A part of iql.hip's translation unit (it needs Iql and the bodies of
+// IQL's kernels), included where the code stands.
+// Each entry runs the body of the kernel it groups (iql.hip, dense.hpp, replay.hip) on the member's entry of a device array, read in
+// place through the constant address space: member and instance come from blockIdx, so they are uniform and the entry's fields are
+// scalar loads, as they are from the kernel-argument segment of the standalone kernel.  Same bodies, same bits.  The three loss kernels
+// are one workgroup per member: candle::row_sum / row_max run inside that workgroup, in their block order, over the member's rows only.
+//   static arguments   one device array per kernel family, rewritten only when a member's batch buffers or its ring change (`keys`:
+//                      CandleAgent::batch_gen, the ring's uid and batch_gen), synchronously, behind a stream synchronise: rare
+//   per step           IqlStep[P] in a slot of the pinned, device-mapped step ring: the gather reads word_pos and size of the member's
+//                      entry (GatherStepWords at its start), the three reduce + Adam launches its three AdamScalars
+// The slot rule (slot_ring.hpp): the ACTOR's reduce + Adam is the LAST launch of a round that reads the slot, so it alone ends with the
+// ticket and publishes the round's launch number (bg_group_done - all workgroups of its three-dimensional grid counted, behind a
+// barrier every thread reaches: dense_reduce_adam_body returns early for threads past the arena, to the entry, not out of the kernel).
+// The host rewrites a slot only once the pinned word has reached the number recorded for it: no copy command, event or synchronise in
+// the steady loop.
+// Bounds of every new index:
+//   member = blockIdx.y < gridDim.y = P = the length of d_gather, d_pack, d_vloss, d_closs, d_aloss and of a step slot;
+//   z = blockIdx.z < gridDim.z = nz <= 4 = the instances of a DenseGroupEntry and of a ReduceAdamArgs (2 n_critics <= 4 is a condition
+//   of the group);
+//   the i-th forward / dX launch of the round (stream order) is handed d_dense + i * P and reads entry i * P + member, i < ndense =
+//   ig_dense_launches: the array holds ndense * P entries; the weight-gradient and reduce + Adam launches of network n (value 0,
+//   critic 1, actor 2) are handed d_dw + n * P / d_ra + n * P: 3 P entries each; NET < 3 = the AdamScalars of an IqlStep;
+//   inside a member every index is the body's own, with the bounds of the standalone kernel.
+#pragma once
+#include <atomic>
+#include <memory>
+
+#include "slot_ring.hpp"
+#include "device_arrays.hpp"
+#include "dense_group.hpp"
+#include "iql_group_plan.hpp"
+
+static_assert(IG_DW_GROUP == DW_GROUP && IG_RA_SEGS == RA_SEGS && IG_MAXZ == DG_MAXZ && IG_SHAPE_LAYERS >= BDR_MAX_UNITS + 1, "iql_group_plan.hpp restates these limits");
+
+// the per-step words of one member: the gather's, then the optimizer scalars of value, critics and actor (IgNetId's order)
+struct IqlStep { unsigned long long word_pos, size; AdamScalars adam[3]; };
+static_assert(offsetof(IqlStep, word_pos) == offsetof(GatherStepWords, word_pos) && offsetof(IqlStep, size) == offsetof(GatherStepWords, size),
+              "the grouped gather reads the first two words of a member's IqlStep");
+static_assert(IG_NET_VALUE == 0 && IG_NET_CRITIC == 1 && IG_NET_ACTOR == 2, "IqlStep::adam and the dW / reduce argument arrays are indexed by IgNetId");
+
+namespace {
+
+// ---- the group entries: grid dimension y is the member -------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_iql_pack_group(const BDR_CONST_AS IqlPackArgs* args) { iql_pack_body(args[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_iql_value_loss_group(const BDR_CONST_AS IqlValueArgs* args)
+{
+    __shared__ float red[32];
+    iql_value_loss_body(args[blockIdx.y], red);
+}
+__global__ __launch_bounds__(1024) void k_iql_critic_loss_group(const BDR_CONST_AS IqlCriticArgs* args)
+{
+    __shared__ float red[32];
+    iql_critic_loss_body(args[blockIdx.y], red);
+}
+__global__ __launch_bounds__(1024) void k_iql_actor_loss_group(const BDR_CONST_AS IqlActorArgs* args)
+{
+    __shared__ float red[32];
+    iql_actor_loss_body(args[blockIdx.y], red);
+}
+// reduce + Adam of network NET of every member, instance z = blockIdx.z: the optimizer scalars of this step come from the member's
+// staging slot; the critics track their targets at the member's own tau (a.tau / a.omt of its entry); the actor's is the last reader of
+// the slot and publishes
+template <int NET>
+__global__ __launch_bounds__(256) void k_iql_reduce_adam_group(const BDR_CONST_AS ReduceAdamArgs* args, const BDR_CONST_AS IqlStep* steps, unsigned* ticket,
+                                                               unsigned* seq_host, unsigned seq)
+{
+    const BDR_CONST_AS AdamScalars& s = steps[blockIdx.y].adam[NET];
+    AdamScalars d;   // field by field: static indices, registers
+    d.b1 = s.b1; d.omb1 = s.omb1; d.b2 = s.b2; d.omb2 = s.omb2; d.sqrt_bc2 = s.sqrt_bc2; d.eps = s.eps; d.neg_step = s.neg_step; d.wd_mul = s.wd_mul;
+    dense_reduce_adam_body(args[blockIdx.y], (int)blockIdx.z, d, NET == IG_NET_CRITIC ? 1 : 0, 0);
+    if constexpr (NET == IG_NET_ACTOR) bg_group_done(ticket, seq_host, seq);
+}
+
+IgNet iql_net_shape(const MlpLayout& net, int activation_out)
+{
+    IgNet s{};
+    s.n_layers = (int)net.L.size(); s.activation_out = activation_out;
+    for (int i = 0; i < s.n_layers && i < IG_SHAPE_LAYERS; ++i) { s.Kp[i] = net.L[i].Kp; s.Np[i] = net.L[i].Np; s.out[i] = net.L[i].out; }
+    return s;
+}
+IgShape iql_shape(const Iql* m)
+{
+    IgShape s{};
+    s.obs_dim = m->O; s.act_dim = m->A; s.batch = (int)m->cfg.batch_size; s.n_critics = m->NC;
+    s.value = iql_net_shape(m->vn, m->cfg.value.activation_out);
+    s.critic = iql_net_shape(m->qn, m->cfg.critic.activation_out);
+    s.actor = iql_net_shape(m->pn, m->cfg.actor.activation_out);
+    return s;
+}
+
+// ---- host: one member's static arguments, exactly what Iql::update hands its launches ---------------------------------------------------
+struct IqlMemberArgs {
+    GatherArgs gather; IqlPackArgs pack;
+    std::vector<DenseGroupEntry> dense;   // the forward and dX launches in stream order
+    IqlValueArgs vloss; IqlCriticArgs closs; IqlActorArgs aloss;
+    DenseDwSmallGroup dw[3]; int dw_grid[3];   // by IgNetId
+    ReduceAdamArgs ra[3];
+};
+
+DenseArgs iql_fwd_args(const DenseLayer& l, const float* par, DenseSrc in, float* out, int bs)   // dense_forward_z
+{
+    DenseArgs d{};
+    d.x = in; d.w = par + l.w; d.bias = par + l.b; d.out = out; d.ldo = l.Np;
+    d.M = bs; d.ncols = l.Np; d.kred = l.Kp; d.relu = l.relu; d.w_ld = l.Np;
+    return d;
+}
+DenseArgs iql_dx_args(const DenseLayer& l, const float* par, const float* dy, float* dx, const float* mask, int bs)   // dense_dx_z
+{
+    DenseArgs d{};
+    d.x = DenseSrc{dy, l.Np}; d.w = par + l.w; d.out = dx; d.ldo = l.Kp; d.mask = mask; d.ldm = l.Kp;
+    d.M = bs; d.ncols = l.Kp; d.kred = l.Np; d.w_ld = l.Np;
+    return d;
+}
+// mlp_forward of nz (parameters, input, activations) triples of one architecture: one entry per layer
+void iql_fwd_entries(std::vector<DenseGroupEntry>& out, const MlpLayout& net, int nz, const float* const* par, const float* const* x,
+                     std::vector<float*>* const* acts, int bs)
+{
+    for (size_t l = 0; l < net.L.size(); ++l) {
+        DenseGroupEntry e{};
+        for (int z = 0; z < nz; ++z)
+            e.a[z] = iql_fwd_args(net.L[l], par[z], l == 0 ? DenseSrc{x[z], net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*acts[z])[l], bs);
+        out.push_back(e);
+    }
+}
+// mlp_backward_step of nz networks of one architecture: the dX entries from the last layer down, the grouped dW, the reduce segments
+void iql_step_entries(IqlMemberArgs& o, int id, const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
+                      const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
+                      const std::vector<size_t>& off, int bs, size_t total, double tau, const DenseReduceSeg* extra)
+{
+    const int L = (int)net.L.size();
+    for (int l = L - 1; l >= 1; --l) {
+        DenseGroupEntry e{};
+        for (int z = 0; z < nz; ++z) e.a[z] = iql_dx_args(net.L[l], p[z], (*dys[z])[l], (*dys[z])[l - 1], (*acts[z])[l - 1], bs);
+        o.dense.push_back(e);
+    }
+    DenseDwJob jobs[DW_GROUP];
+    const int c = DenseAgent::chunks_for(bs);
+    int nj = 0;
+    for (int z = 0; z < nz; ++z)
+        for (int l = 0; l < L; ++l)
+            jobs[nj++] = DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*dys[z])[l],
+                                    part + (size_t)z * part_stride + off[l], c};
+    o.dw_grid[id] = dense_dw_small_group_fill(o.dw[id], jobs, nj, bs);
+    ReduceAdamArgs& ra = o.ra[id];
+    ra = ReduceAdamArgs{};
+    ra.nseg = L; ra.inst_part_stride = part_stride;
+    for (int l = 0; l < L; ++l) {
+        const DenseLayer& ly = net.L[l];
+        const size_t nfl = (size_t)ly.Kp * ly.Np + ly.Np;
+        ra.seg[l] = DenseReduceSeg{part + off[l], nfl, c, (unsigned)(ly.w / 4), (unsigned)(nfl / 4)};
+    }
+    if (extra) ra.seg[ra.nseg++] = *extra;
+    for (int z = 0; z < nz; ++z) { ra.p[z] = p[z]; ra.g[z] = g[z]; ra.m[z] = m[z]; ra.v[z] = v[z]; ra.tgt[z] = tgt ? tgt[z] : nullptr; ra.vmax[z] = nullptr; }
+    // (s[z], track and grads_only are the entry's: this step's IqlStep, the network, 0)
+    ra.n4 = (unsigned)(total / 4); ra.track = tgt ? 1 : 0; ra.tau = (float)tau; ra.omt = (float)(1.0 - tau);
+}
+
+// (bs: the batch size; r: the member's ring or view; plan: replay_sample_plan's descriptor of this step)
+void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& plan, IqlMemberArgs& o)
+{
+    const bdr_iql_config& cfg = m->cfg;
+    const int NC = m->NC, O = m->O, A = m->A;
+    const MlpLayout &qn = m->qn, &vn = m->vn, &pn = m->pn;
+    const int Lq = (int)qn.L.size(), Lv = (int)vn.L.size(), Lp = (int)pn.L.size();
+    const int ldq = qn.L[Lq - 1].Np, ldv = vn.L[Lv - 1].Np;
+    const float* obs = reinterpret_cast<const float*>(r->b_obs);
+    const float* next_obs = reinterpret_cast<const float*>(r->b_next);
+    const float* act = reinterpret_cast<const float*>(r->b_act);
+    o.dense.clear();
+    // the gather: k_gather's arguments as replay_sample_on_stream sets them (word_pos and size are this step's, read from the slot)
+    o.gather = plan;
+    replay_gather_shape(r->obs_bytes, &o.gather.chunks, &o.gather.vec_per_chunk);
+    o.gather.word_pos = 0; o.gather.size = 0;
+    o.pack = IqlPackArgs{obs, next_obs, act, O, A, bs, m->x_o, m->x_no, vn.L[0].Kp, m->xq, qn.L[0].Kp};
+    // target and online critics: one forward of 2 NC networks
+    {
+        const float* params[4]; const float* x[4]; std::vector<float*>* acts[4];
+        for (int i = 0; i < NC; ++i) { params[i] = m->q_t[i]; x[i] = m->xq; acts[i] = &m->t_act[i]; params[NC + i] = m->q_p[i]; x[NC + i] = m->xq; acts[NC + i] = &m->c_act[i]; }
+        iql_fwd_entries(o.dense, qn, 2 * NC, params, x, acts, bs);
+    }
+    { const float* pp[1] = {m->pi_p}; const float* x[1] = {m->x_o}; std::vector<float*>* acts[1] = {&m->p_act}; iql_fwd_entries(o.dense, pn, 1, pp, x, acts, bs); }
+    // ---- update_value
+    { const float* pp[1] = {m->v_p}; const float* x[1] = {m->x_o}; std::vector<float*>* acts[1] = {&m->v_act}; iql_fwd_entries(o.dense, vn, 1, pp, x, acts, bs); }
+    {
+        IqlValueArgs& p = o.vloss;
+        p = IqlValueArgs{};
+        for (int i = 0; i < NC; ++i) p.qt[i] = m->t_act[i][Lq - 1];
+        p.ldq = ldq; p.NC = NC; p.v = m->v_act[Lv - 1]; p.dv = m->v_dy[Lv - 1]; p.ldv = ldv; p.relu_out = vn.L[Lv - 1].relu;
+        p.tau = (float)cfg.tau_iql; p.q_min = m->pr_qmin1; p.v_out = m->pr_v; p.u_out = m->pr_u; p.loss = m->scal; p.accumulate = 0; p.B = bs;
+    }
+    {
+        std::vector<float*>* acts[1] = {&m->v_act}; std::vector<float*>* dys[1] = {&m->v_dy};
+        iql_step_entries(o, IG_NET_VALUE, vn, 1, &m->v_p, &m->v_g, &m->v_m, &m->v_v, nullptr, m->x_o, acts, dys, m->v_part, 0, m->v_off, bs, vn.total, cfg.critic_tau, nullptr);
+    }
+    // ---- update_critic
+    {
+        const float* pp[2] = {m->v_p, m->v_p}; const float* x[2] = {m->x_o, m->x_no}; std::vector<float*>* acts[2] = {&m->vo_act, &m->vn_act};
+        iql_fwd_entries(o.dense, vn, 2, pp, x, acts, bs);
+    }
+    {
+        IqlCriticArgs& p = o.closs;
+        p = IqlCriticArgs{};
+        for (int i = 0; i < NC; ++i) { p.q[i] = m->c_act[i][Lq - 1]; p.dq[i] = m->c_dy[i][Lq - 1]; }
+        p.ldq = ldq; p.NC = NC; p.relu_out = qn.L[Lq - 1].relu; p.vn = m->vn_act[Lv - 1]; p.ldv = ldv;
+        p.reward = r->b_reward; p.term = r->b_term; p.trunc = r->b_trunc; p.gamma = (float)cfg.gamma; p.tgt = m->pr_tgt; p.v_next = m->pr_vnext;
+        p.loss_kind = cfg.critic_loss; p.loss = m->scal + 1; p.accumulate = 0; p.B = bs;
+    }
+    {
+        std::vector<float*>* acts[4]; std::vector<float*>* dys[4];
+        for (int i = 0; i < NC; ++i) { acts[i] = &m->c_act[i]; dys[i] = &m->c_dy[i]; }
+        iql_step_entries(o, IG_NET_CRITIC, qn, NC, m->q_p, m->q_g, m->q_m, m->q_v, m->q_t, m->xq, acts, dys, m->q_part, m->q_part_stride, m->q_off, bs, qn.total,
+                         cfg.critic_tau, nullptr);
+    }
+    // ---- update_actor
+    {
+        const float* params[4]; const float* x[4]; std::vector<float*>* acts[4];
+        for (int i = 0; i < NC; ++i) { params[i] = m->q_t[i]; x[i] = m->xq; acts[i] = &m->t_act[i]; }
+        iql_fwd_entries(o.dense, qn, NC, params, x, acts, bs);
+    }
+    {
+        IqlActorArgs& p = o.aloss;
+        p = IqlActorArgs{};
+        for (int i = 0; i < NC; ++i) p.qt[i] = m->t_act[i][Lq - 1];
+        p.ldq = ldq; p.NC = NC; p.vo = m->vo_act[Lv - 1]; p.ldv = ldv;
+        p.mean = m->p_act[Lp - 1]; p.ldm = pn.L[Lp - 1].Np; p.head2 = m->pi_p + m->h2_off; p.act = act; p.A = A;
+        p.lo = (float)cfg.min_log_std; p.hi = (float)cfg.max_log_std; p.tanh_limit = cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
+        p.scale = (float)cfg.action_scale; p.inv_lambda = (float)cfg.inv_lambda; p.exp_adv_max = (float)cfg.exp_adv_max; p.softmax = cfg.adv_softmax ? 1 : 0;
+        p.q_min = m->pr_qmin3; p.w = m->pr_w; p.logp = m->pr_logp; p.gmean = m->p_dy[Lp - 1]; p.gh2 = m->h2_part;
+        p.loss = m->scal + 2; p.accumulate = 0; p.B = bs;
+    }
+    {
+        std::vector<float*>* acts[1] = {&m->p_act}; std::vector<float*>* dys[1] = {&m->p_dy};
+        const DenseReduceSeg h2seg{m->h2_part, (size_t)pad64(A), 1, (unsigned)(m->h2_off / 4), (unsigned)(pad64(A) / 4)};
+        iql_step_entries(o, IG_NET_ACTOR, pn, 1, &m->pi_p, &m->pi_g, &m->pi_m, &m->pi_v, nullptr, m->x_o, acts, dys, m->pi_part, 0, m->pi_off, bs, m->pi_total,
+                         cfg.critic_tau, &h2seg);
+    }
+}
+
+}  // namespace
+
+struct bdr_iql_group {
+    enum { STEP_SLOTS = 8 };
+    int32_t device = 0;
+    hipStream_t stream = nullptr;
+    // (bdr_iql_group_destroy has synchronised the stream and destroyed the members; a failed create has adopted nobody.)  The stream
+    // goes first, the buffers - the members below - after it.
+    ~bdr_iql_group() { if (stream) { stream_retire(stream); (void)hipStreamDestroy(stream); } }
+    std::vector<Iql*> members;
+    IgShape shape{};                 // the one shape of all members
+    IgLaunch plan[IG_MAX_LAUNCHES]; int n_launches = 0;
+    int ndense = 0;                  // forward and dX launches of a round
+    uint64_t kernel_launches = 0;    // every kernel launch the group's own calls have enqueued (bdr_iql_group_info)
+    struct StaticKey { bool valid = false; uint64_t batch_gen = 0, r_uid = 0, r_batch_gen = 0; };
+    std::vector<StaticKey> keys;
+    std::vector<GatherArgs> h_gather; DeviceArray<GatherArgs> d_gather;
+    std::vector<IqlPackArgs> h_pack; DeviceArray<IqlPackArgs> d_pack;
+    std::vector<DenseGroupEntry> h_dense; DeviceArray<DenseGroupEntry> d_dense;   // [ndense][P] (launch order)
+    std::vector<IqlValueArgs> h_vloss; DeviceArray<IqlValueArgs> d_vloss;
+    std::vector<IqlCriticArgs> h_closs; DeviceArray<IqlCriticArgs> d_closs;
+    std::vector<IqlActorArgs> h_aloss; DeviceArray<IqlActorArgs> d_aloss;
+    std::vector<DenseDwSmallGroup> h_dw; DeviceArray<DenseDwSmallGroup> d_dw;     // [3][P] by IgNetId
+    std::vector<ReduceAdamArgs> h_ra; DeviceArray<ReduceAdamArgs> d_ra;           // [3][P] by IgNetId
+    PinnedArray<IqlStep> steps; SlotRing<STEP_SLOTS> step_ring;                   // [STEP_SLOTS][P]
+    PinnedArray<unsigned> seq;                                                    // pinned word: the launch number published last
+    DeviceArray<unsigned> ticket;
+    uint64_t launches = 0;                                                        // launch numbers given out so far (1-based)
+    std::vector<bdr_replay*> last_buffers;                                        // the buffers of the last accepted opt (distinctness checked once)
+
+    hipError_t allocate(size_t P)
+    {
+        ndense = ig_dense_launches(shape.value.n_layers, shape.critic.n_layers, shape.actor.n_layers);
+        h_gather.resize(P); h_pack.resize(P); h_dense.resize((size_t)ndense * P); h_vloss.resize(P); h_closs.resize(P); h_aloss.resize(P);
+        h_dw.resize(3 * P); h_ra.resize(3 * P);
+        keys.resize(P);
+        hipError_t e = device_array(d_gather, P);
+        if (e == hipSuccess) e = device_array(d_pack, P);
+        if (e == hipSuccess) e = device_array(d_dense, h_dense.size());
+        if (e == hipSuccess) e = device_array(d_vloss, P);
+        if (e == hipSuccess) e = device_array(d_closs, P);
+        if (e == hipSuccess) e = device_array(d_aloss, P);
+        if (e == hipSuccess) e = device_array(d_dw, 3 * P);
+        if (e == hipSuccess) e = device_array(d_ra, 3 * P);
+        if (e == hipSuccess) e = device_array(ticket, 1);
+        if (e == hipSuccess) e = hipMemset(ticket.get(), 0, sizeof(unsigned));
+        if (e == hipSuccess) e = pinned_array(steps, (size_t)STEP_SLOTS * P);
+        if (e == hipSuccess) e = pinned_array(seq, 16);   // (one word, a cache line of its own)
+        return e;
+    }
+    // member p's arguments into the staging arrays
+    void stage(size_t p, size_t P, const IqlMemberArgs& o)
+    {
+        h_gather[p] = o.gather; h_pack[p] = o.pack; h_vloss[p] = o.vloss; h_closs[p] = o.closs; h_aloss[p] = o.aloss;
+        for (int i = 0; i < ndense; ++i) h_dense[(size_t)i * P + p] = o.dense[i];
+        for (int n = 0; n < 3; ++n) { h_dw[(size_t)n * P + p] = o.dw[n]; h_ra[(size_t)n * P + p] = o.ra[n]; }
+    }
+    hipError_t upload(size_t P)
+    {
+        hipError_t e = hipMemcpy(d_gather.get(), h_gather.data(), P * sizeof(GatherArgs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_pack.get(), h_pack.data(), P * sizeof(IqlPackArgs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_dense.get(), h_dense.data(), h_dense.size() * sizeof(DenseGroupEntry), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_vloss.get(), h_vloss.data(), P * sizeof(IqlValueArgs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_closs.get(), h_closs.data(), P * sizeof(IqlCriticArgs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_aloss.get(), h_aloss.data(), P * sizeof(IqlActorArgs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_dw.get(), h_dw.data(), 3 * P * sizeof(DenseDwSmallGroup), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_ra.get(), h_ra.data(), 3 * P * sizeof(ReduceAdamArgs), hipMemcpyHostToDevice);
+        return e;
+    }
+    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
+    int32_t launch(size_t P, const IqlStep* steps_dev, unsigned seq_no)
+    {
+        int dense = 0;
+        for (int n = 0; n < n_launches; ++n) {
+            const IgLaunch& l = plan[n];
+            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
+            const auto* st = (const BDR_CONST_AS IqlStep*)steps_dev;
+            switch (l.kernel) {
+            case IG_K_GATHER:
+                BDR_TRY(replay_gather_group(stream, d_gather.get(), steps_dev, (uint32_t)sizeof(IqlStep), (uint32_t)P, (uint64_t)shape.batch, (uint64_t)shape.obs_dim * 4));
+                break;
+            case IG_K_PACK: hipLaunchKernelGGL(k_iql_pack_group, grid, block, 0, stream, (const BDR_CONST_AS IqlPackArgs*)d_pack.get()); break;
+            case IG_K_FWD:
+                BDR_REQUIRE(dense < ndense, "IQL group round: more dense launches in the plan than argument entries");
+                hipLaunchKernelGGL(k_dense_small_members_z<false>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(d_dense.get() + (size_t)dense++ * P));
+                break;
+            case IG_K_DX:
+                BDR_REQUIRE(dense < ndense, "IQL group round: more dense launches in the plan than argument entries");
+                hipLaunchKernelGGL(k_dense_small_members_z<true>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(d_dense.get() + (size_t)dense++ * P));
+                break;
+            case IG_K_VALUE_LOSS: hipLaunchKernelGGL(k_iql_value_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlValueArgs*)d_vloss.get()); break;
+            case IG_K_CRITIC_LOSS: hipLaunchKernelGGL(k_iql_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlCriticArgs*)d_closs.get()); break;
+            case IG_K_ACTOR_LOSS: hipLaunchKernelGGL(k_iql_actor_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlActorArgs*)d_aloss.get()); break;
+            case IG_K_DW:
+                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
+                hipLaunchKernelGGL(k_dense_dw_small_members, grid, block, 0, stream, (const BDR_CONST_AS DenseDwSmallGroup*)(d_dw.get() + (size_t)l.net * P));
+                break;
+            case IG_K_REDUCE_ADAM: {
+                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
+                const auto* ra = (const BDR_CONST_AS ReduceAdamArgs*)(d_ra.get() + (size_t)l.net * P);
+                if (l.net == IG_NET_VALUE) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_VALUE>, grid, block, 0, stream, ra, st, ticket.get(), seq.dev, seq_no);
+                else if (l.net == IG_NET_CRITIC) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_CRITIC>, grid, block, 0, stream, ra, st, ticket.get(), seq.dev, seq_no);
+                else hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_ACTOR>, grid, block, 0, stream, ra, st, ticket.get(), seq.dev, seq_no);
+                break;
+            }
+            default: return fail(BDR_ERR_INVALID, "IQL group round: launch %d of the plan names no kernel", n);
+            }
+            BDR_HIP(hipGetLastError());
+        }
+        return BDR_OK;
+    }
+};
+
+namespace {
+
+// every refusal of a grouped opt, before anything moves: CandleAgent::opt's checks (check_replay), and what the grouped gather covers
+int32_t iql_group_check_buffers(bdr_iql_group* g, bdr_replay* const* buffers)
+{
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {
+        const Iql* m = g->members[p];
+        const bdr_replay* r = buffers[p];
+        BDR_REQUIRE(r, "member %u: null buffer", p);
+        BDR_REQUIRE(!m->prof && !m->grad_comm, "member %u: profiling or a gradient communicator was switched on after the group was created", p);
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == (uint64_t)m->A * 4, "member %u: replay rows do not match IQL obs/act dims (f32 rows)", p);
+        BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
+        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot be stepped by an IQL group (the grouped gather covers the uniform ring)", p);
+        BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by an IQL group", p);
+        BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: the grouped gather draws the StdRng index stream only", p);
+        if (r->size == 0) return fail(BDR_ERR_EMPTY, "member %u: batch() on an empty replay buffer", p);
+    }
+    if (g->last_buffers.size() == P && memcmp(g->last_buffers.data(), buffers, P * sizeof(bdr_replay*)) == 0) return BDR_OK;
+    std::vector<const bdr_replay*> s(buffers, buffers + P);   // workgroups run side by side: one bdr_replay (its batch arrays, its stream position) per member
+    std::sort(s.begin(), s.end());
+    const auto dup = std::adjacent_find(s.begin(), s.end());
+    if (dup != s.end()) {
+        uint32_t second = 0;
+        for (uint32_t p = 0, seen = 0; p < P; ++p) if (buffers[p] == *dup && seen++ == 1) { second = p; break; }
+        return fail(BDR_ERR_INVALID, "member %u: it shares its replay buffer with an earlier member: every member needs a bdr_replay of its own (a view of one ring will do)", second);
+    }
+    g->last_buffers.clear();
+    return BDR_OK;
+}
+
+// one update round: per member what CandleAgent::opt / Iql::update do on the host, in their order, then the round's launches, the last of
+// which publishes its number
+int32_t iql_group_round(bdr_iql_group* g, bdr_replay* const* buffers)
+{
+    const uint32_t P = (uint32_t)g->members.size();
+    const uint64_t k = g->launches + 1;
+    const auto slot = g->step_ring.next();
+    if (slot.wait) {   // the slot's last reader has published (bounded: wait_seq_word)
+        bool arrived = false;
+        BDR_TRY(wait_seq_word(g->seq.host.get(), (unsigned)slot.wait, g->stream, std::chrono::steady_clock::now(), &arrived));
+    }
+    IqlStep* steps = g->steps.host.get() + (size_t)slot.slot * P;
+    bool dirty = false;
+    IqlMemberArgs o;
+    for (uint32_t p = 0; p < P; ++p) {
+        Iql* m = g->members[p];
+        bdr_replay* r = buffers[p];
+        const int bs = (int)m->cfg.batch_size;
+        BDR_TRY(m->ensure_batch(bs));
+        GatherArgs plan{};
+        BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));   // the host half of replay_sample_on_stream; the rows are k_gather_group's
+        IqlStep st{};
+        st.word_pos = plan.word_pos; st.size = plan.size;
+        m->step_v += 1;
+        st.adam[IG_NET_VALUE] = DenseAgent::opt_scalars(m->cfg.opt_value, m->cfg.lr_value, m->step_v);
+        m->step_q += 1;
+        st.adam[IG_NET_CRITIC] = DenseAgent::opt_scalars(m->cfg.opt_critic, m->cfg.lr_critic, m->step_q);
+        m->step_pi += 1;
+        st.adam[IG_NET_ACTOR] = DenseAgent::opt_scalars(m->cfg.opt_actor, m->cfg.lr_actor, m->step_pi);
+        m->n_opts += 1;
+        m->last_B = bs;
+        bdr_iql_group::StaticKey& key = g->keys[p];
+        if (!key.valid || key.batch_gen != m->batch_gen || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
+            iql_member_static(m, bs, r, plan, o);
+            BDR_REQUIRE((int)o.dense.size() == g->ndense, "member %u: %d dense launches, the plan has %d", p, (int)o.dense.size(), g->ndense);
+            for (int n = 0; n < g->n_launches; ++n)
+                if (g->plan[n].kernel == IG_K_DW) {
+                    const int id = g->plan[n].net;
+                    BDR_REQUIRE(o.dw_grid[id] == (int)g->plan[n].gx, "member %u: the weight-gradient grid of network %d (%d) differs from the plan's (%u)", p, id,
+                                o.dw_grid[id], g->plan[n].gx);
+                }
+            g->stage(p, P, o);
+            key.valid = true; key.batch_gen = m->batch_gen; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
+            dirty = true;
+        }
+        steps[p] = st;
+    }
+    if (dirty) {   // rare (first step, a reallocation, another ring): behind everything the stream still holds
+        BDR_HIP(hipStreamSynchronize(g->stream));
+        BDR_HIP(g->upload(P));
+    }
+    std::atomic_thread_fence(std::memory_order_release);
+    // (should a launch fail, k is the number of whatever the group launches next - later than every reader of the slot)
+    g->launches = k; g->step_ring.record(k);
+    BDR_TRY(g->launch(P, g->steps.dev + (size_t)slot.slot * P, (unsigned)k));
+    g->kernel_launches += (uint64_t)g->n_launches;
+    return BDR_OK;
+}
+
+// what bdr_agent_opt does around opt(), for every member, then the round
+int32_t iql_group_opt(bdr_iql_group* g, bdr_replay* const* buffers)
+{
+    BDR_HIP(hipSetDevice(g->device));
+    BDR_TRY(iql_group_check_buffers(g, buffers));
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {   // asynchronous: what an earlier synchronising call of the member read back surfaces here
+        Iql* m = g->members[p];
+        unsigned w[bdr_agent::ERR_WORDS];
+        m->err_mirror_read(w);
+        BDR_TRY(m->err_report(w));
+    }
+    for (uint32_t p = 0; p < P; ++p) g->members[p]->last_replay_uid = buffers[p]->uid;
+    BDR_TRY(iql_group_round(g, buffers));
+    g->last_buffers.assign(buffers, buffers + P);
+    return BDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t bdr_iql_group_create(bdr_agent* const* agents, uint32_t n, bdr_iql_group** out)
+{
+    BDR_REQUIRE(agents && out, "null argument");
+    BDR_REQUIRE(n >= 1 && n <= IG_MAX_MEMBERS, "a group has 1 .. 65535 members");
+    std::vector<Iql*> ms;
+    std::vector<IgMember> desc;
+    for (uint32_t p = 0; p < n; ++p) {
+        BDR_REQUIRE(agents[p], "member %u: null agent", p);
+        BDR_REQUIRE(!strcmp(agents[p]->kind(), "iql"), "member %u cannot join an IQL group: not an IQL agent (kind %s)", p, agents[p]->kind());
+        BDR_REQUIRE(!agents[p]->group, "member %u cannot join an IQL group: already a member of a group", p);
+        Iql* m = static_cast<Iql*>(agents[p]);
+        ms.push_back(m);
+        desc.push_back(IgMember{iql_shape(m), 1, m->cfg.n_updates_per_opt, m->device, m->prof ? 1 : 0, m->grad_comm ? 1 : 0, m});
+    }
+    const char* why = nullptr;
+    int kernel = -1;
+    const int who = ig_group_refusal(desc.data(), n, &why, &kernel);
+    if (who == IG_NO_MEMBER) return kernel >= 0 ? fail(BDR_ERR_INVALID, "%u members of this shape: %s (%s)", n, why, ig_kernel_name(kernel)) : fail(BDR_ERR_INVALID, "%s", why);
+    BDR_REQUIRE(who == IG_OK, "member %d cannot join an IQL group: %s", who, why);
+    std::unique_ptr<bdr_iql_group> g(new bdr_iql_group());
+    g->device = ms[0]->device;
+    BDR_HIP(hipSetDevice(g->device));
+    g->shape = desc[0].shape;
+    g->n_launches = ig_round_plan(g->shape, n, g->plan);
+    BDR_REQUIRE(g->n_launches == ig_launch_count(g->shape.value.n_layers, g->shape.critic.n_layers, g->shape.actor.n_layers), "the IQL group launch plan is incomplete");
+    {   // the gather's grid is replay_gather_group's own: it must be the one the plan has checked against the limits
+        uint32_t chunks = 1, vec_per_chunk = 0;
+        replay_gather_shape((uint64_t)g->shape.obs_dim * 4, &chunks, &vec_per_chunk);
+        BDR_REQUIRE((unsigned)g->shape.batch * chunks == g->plan[0].gx && g->plan[0].kernel == IG_K_GATHER,
+                    "the gather's grid (%u workgroups per row) differs from the plan's (is BDR_GATHER_CHUNKS set?): no IQL group", chunks);
+    }
+    // (a failure below leaves nothing adopted: the partially built group releases what it holds)
+    BDR_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    BDR_HIP(g->allocate(n));
+    // adopt: the member's own stream is drained, retired and destroyed; the member enqueues on the group's stream from now on
+    for (Iql* m : ms) BDR_HIP(hipStreamSynchronize(m->stream));
+    for (Iql* m : ms) {
+        hipStream_t old = m->stream;
+        m->stream = g->stream; m->group = g.get();
+        if (old) { stream_retire(old); (void)hipStreamDestroy(old); }
+    }
+    g->members = std::move(ms);
+    *out = g.release();
+    return BDR_OK;
+}
+
+int32_t bdr_iql_group_destroy(bdr_iql_group* g)
+{
+    if (!g) return BDR_OK;
+    (void)hipSetDevice(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    for (Iql* m : g->members) {   // the group owns its members; their stream is the group's, destroyed once below
+        m->group = nullptr; m->stream = nullptr;
+        (void)bdr_agent_destroy(m);
+    }
+    delete g;   // retires and destroys the stream, then releases the buffers
+    return BDR_OK;
+}
+
+int32_t bdr_iql_group_size(const bdr_iql_group* g, uint32_t* n)
+{
+    BDR_REQUIRE(g && n, "null argument");
+    *n = (uint32_t)g->members.size();
+    return BDR_OK;
+}
+
+int32_t bdr_iql_group_member(const bdr_iql_group* g, uint32_t i, bdr_agent** out)
+{
+    BDR_REQUIRE(g && out, "null argument");
+    BDR_REQUIRE(i < g->members.size(), "member %u of a group of %u", i, (unsigned)g->members.size());
+    *out = g->members[i];
+    return BDR_OK;
+}
+
+int32_t bdr_iql_group_info(const bdr_iql_group* g, bdr_group_info* out)
+{
+    BDR_REQUIRE(g && out, "null argument");
+    memset(out, 0, sizeof *out);
+    out->form = BDR_GROUP_FORM_IQL_LAYERS;
+    out->n_members = (uint32_t)g->members.size();
+    out->launches_per_round = (uint32_t)g->n_launches;
+    out->kernel_launches = g->kernel_launches;
+    return BDR_OK;
+}
+
+int32_t bdr_iql_group_opt(bdr_iql_group* g, bdr_replay* const* buffers)
+{
+    BDR_REQUIRE(g && buffers, "null argument");
+    return iql_group_opt(g, buffers);
+}
+
+int32_t bdr_iql_group_opt_with_scalars(bdr_iql_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out)
+{
+    BDR_REQUIRE(g && buffers && out && n_out, "null argument");
+    BDR_REQUIRE(cap_per_member >= Iql::N_RECORD, "cap_per_member must hold the three keys of an IQL record");
+    BDR_TRY(iql_group_opt(g, buffers));
+    BDR_HIP(hipStreamSynchronize(g->stream));   // the one synchronisation: every record() below finds the stream idle
+    const uint32_t P = (uint32_t)g->members.size();
+    for (uint32_t p = 0; p < P; ++p) {
+        Iql* m = g->members[p];
+        int n = 0;
+        m->rec_opt = true;
+        const int32_t st = m->record(out + (size_t)p * cap_per_member, cap_per_member, &n);
+        m->rec_opt = false;
+        BDR_TRY(st);
+        n_out[p] = n;
+    }
+    for (uint32_t p = 0; p < P; ++p) {   // the records are complete whatever the error words say about the step that produced them
+        const int32_t st = g->members[p]->err_check();
+        if (st != BDR_OK) { if (bdr::g_err_deferred) bdr::g_err_deferred = 2; return st; }
+    }
+    return BDR_OK;
+}
+
+int32_t bdr_iql_group_sync(bdr_iql_group* g)
+{
+    BDR_REQUIRE(g, "null group");
+    BDR_HIP(hipSetDevice(g->device));
+    BDR_HIP(hipStreamSynchronize(g->stream));
+    for (Iql* m : g->members) {
+        BDR_TRY(m->after_sync());
+        BDR_TRY(m->err_check());
+    }
+    return BDR_OK;
+}
+
+}  // extern "C"

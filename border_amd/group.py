@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from .bc import Bc
 from .dqn import Dqn, DqnConfig, record_keys
+from .iql import Iql
 
 
 def raise_first(evaluators, status: int) -> None:
@@ -25,6 +26,10 @@ def raise_first(evaluators, status: int) -> None:
             if e.error is not None:
                 e._raise(status)
     _lib.check(status)
+
+
+GROUP_FORMS = {_lib.GROUP_FORM_ONE_WORKGROUP: "one_workgroup", _lib.GROUP_FORM_LAYERS: "layers", _lib.GROUP_FORM_BC_LAYERS: "bc_layers",
+               _lib.GROUP_FORM_IQL_LAYERS: "iql_layers"}
 
 
 class DqnGroup:
@@ -301,7 +306,7 @@ class BcGroup:
         """bdr_bc_group_info: {"form": "bc_layers", "n_members", "launches_per_round", "kernel_launches"}."""
         i = _lib.GroupInfoC()
         _lib.check(_lib.lib().bdr_bc_group_info(self._g, C.byref(i)))
-        form = {_lib.GROUP_FORM_BC_LAYERS: "bc_layers", _lib.GROUP_FORM_LAYERS: "layers", _lib.GROUP_FORM_ONE_WORKGROUP: "one_workgroup"}[i.form]
+        form = GROUP_FORMS[i.form]
         return {"form": form, "n_members": i.n_members, "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
 
     @property
@@ -471,6 +476,120 @@ class BcGroup:
     def close(self) -> None:
         if getattr(self, "_g", None):
             _lib.check(_lib.lib().bdr_bc_group_destroy(self._g))   # destroys the members
+            self._g = None
+            for a in self._members:
+                a._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IqlGroup:
+    """A set of IQL agents of one shape whose Agent::opt (Iql::opt_, iql/base.rs:157-188) runs as the launch sequence of ONE member,
+    every launch serving all members (bdr_iql_group_*): 3 (Lq + Lv) + 2 Lp + 8 launches per round for Lv, Lq, Lp layers of value,
+    critic and actor, whatever the number of members.  The members may differ in seed, tau_iql, inv_lambda, exp_adv_max, gamma, the
+    critics' tau, adv_softmax, critic_loss, the action limit, the log-std clamps, learning rates and optimizers; their buffers are
+    uniform buffers of their own or views of one (`SimpleReplayBuffer.view`), so that P members hold one copy of a dataset.
+
+    A launch grouping, not an agent kind: the members are ordinary `Iql` objects (every `Iql` method keeps working on a member and
+    means what it meant) that the group owns - `IqlGroup.close()` closes them, `member.close()` on a live group is refused.  Results
+    are bit for bit those of stepping the same agents one after the other."""
+    STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/iql_group.hpp bdr_iql_group::STEP_SLOTS)
+    RECORD_KEYS = ("loss_value", "loss_critic", "loss_actor")
+
+    def __init__(self, agents):
+        agents = list(agents)
+        hs = (C.c_void_p * len(agents))(*[a.handle for a in agents])
+        g = C.c_void_p()
+        _lib.check(_lib.lib().bdr_iql_group_create(hs, len(agents), C.byref(g)))
+        self._g = g
+        self._members = agents
+        self._bound = None   # the handle array of the buffers passed last (opt() without an argument steps on them again)
+        self._bound_buffers = None   # ... and the buffers themselves: kept alive, and checked to be open, while opt() may step on them
+
+    @classmethod
+    def build(cls, configs) -> "IqlGroup":
+        """One `Iql` per IqlConfig, grouped.  Nothing is left behind when a config is refused."""
+        agents = []
+        try:
+            for c in configs:
+                agents.append(Iql.build(c))
+            return cls(agents)
+        except Exception:
+            for a in agents:
+                a.close()
+            raise
+
+    @property
+    def members(self):
+        return list(self._members)
+
+    def __len__(self):
+        return len(self._members)
+
+    @property
+    def handle(self):
+        return self._g
+
+    def info(self) -> dict:
+        """bdr_iql_group_info: {"form": "iql_layers", "n_members", "launches_per_round", "kernel_launches"}."""
+        i = _lib.GroupInfoC()
+        _lib.check(_lib.lib().bdr_iql_group_info(self._g, C.byref(i)))
+        return {"form": GROUP_FORMS[i.form], "n_members": i.n_members, "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
+
+    @property
+    def form(self) -> str:
+        return self.info()["form"]
+
+    @property
+    def launches_per_round(self) -> int:
+        """kernel launches of one update round, whatever the number of members"""
+        return self.info()["launches_per_round"]
+
+    @property
+    def kernel_launches(self) -> int:
+        """kernel launches the group's own calls have enqueued since it was built"""
+        return self.info()["kernel_launches"]
+
+    def _buffers(self, buffers):
+        if buffers is None:
+            if self._bound is None:
+                raise ValueError("opt() without buffers needs an earlier call that named them")
+            for i, b in enumerate(self._bound_buffers):
+                if b is not None and not b.handle:
+                    raise ValueError(f"member {i}: its buffer of the last call has been closed: name the buffers again")
+            return self._bound
+        buffers = list(buffers)
+        if len(buffers) != len(self._members):
+            raise ValueError(f"{len(self._members)} members need {len(self._members)} buffers, got {len(buffers)}")
+        self._bound = (C.c_void_p * len(buffers))(*[None if b is None else b.handle for b in buffers])
+        self._bound_buffers = buffers
+        return self._bound
+
+    def opt(self, buffers=None) -> None:
+        """Agent::opt of every member on its own buffer: launches_per_round launches in all; does not synchronise.
+        `buffers=None`: the buffers of the last opt / opt_with_record call (they must still be open)."""
+        _lib.check(_lib.lib().bdr_iql_group_opt(self._g, self._buffers(buffers)))
+
+    def opt_with_record(self, buffers=None) -> list:
+        """Agent::opt_with_record of every member (one synchronisation): a list of Record dicts (loss_value, loss_critic, loss_actor)
+        in member order."""
+        n, cap = len(self._members), 8
+        out = np.zeros((n, cap), np.float32)
+        cnt = np.zeros(n, np.int32)
+        _lib.check(_lib.lib().bdr_iql_group_opt_with_scalars(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap,
+                                                             cnt.ctypes.data_as(C.c_void_p)))
+        return [{k: float(v) for k, v in zip(self.RECORD_KEYS, out[i, :cnt[i]])} for i in range(n)]
+
+    def sync(self) -> None:
+        _lib.check(_lib.lib().bdr_iql_group_sync(self._g))
+
+    def close(self) -> None:
+        if getattr(self, "_g", None):
+            _lib.check(_lib.lib().bdr_iql_group_destroy(self._g))   # destroys the members
             self._g = None
             for a in self._members:
                 a._h = None

@@ -132,6 +132,11 @@ class Iql(CandleAgent):
     def _model_id(self, name: str) -> int:
         return 1 + 2 * self.n_critics if name == "value" else super()._model_id(name)
 
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.check(_lib.lib().bdr_agent_destroy(self._h))   # (refused for a member of a live IqlGroup: the group owns it)
+            self._h = None
+
     def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated) -> dict:
         f = lambda x: np.ascontiguousarray(x, dtype=np.float32)
         obs, act, next_obs, reward = map(f, (obs, act, next_obs, reward))

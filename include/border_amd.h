@@ -506,6 +506,7 @@ BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr
 #define BDR_GROUP_FORM_ONE_WORKGROUP 0
 #define BDR_GROUP_FORM_LAYERS 1
 #define BDR_GROUP_FORM_BC_LAYERS 2   /* a bdr_bc_group (below): BC's launch sequence of one member, every launch serving all members */
+#define BDR_GROUP_FORM_IQL_LAYERS 3  /* a bdr_iql_group (below): IQL's launch sequence of one member, every launch serving all members */
 typedef struct { int32_t form; uint32_t n_members; uint32_t launches_per_round; uint32_t reserved; uint64_t kernel_launches; } bdr_group_info;
 BDR_API int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out);
 /* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
@@ -1163,6 +1164,35 @@ BDR_API int32_t bdr_iql_probe(bdr_agent* a, int32_t what, float* out, uint64_t n
 BDR_API int32_t bdr_iql_sample(bdr_agent* a, uint64_t n, const float* obs, float* act_out);
 /* the same for observation rows in HBM (row i at obs_dev + i * row_stride bytes), see bdr_agent_sample_device */
 BDR_API int32_t bdr_iql_sample_device(bdr_agent* a, uint64_t n, const void* obs_dev, uint64_t row_stride, float* act_out);
+
+/* A GROUP of IQL agents over uniform rings (or views of one ring, bdr_replay_view_create): Iql::opt_ (iql/base.rs:157-188) of every
+ * member in the launch sequence of ONE member - gather, pack, the critics', actor's and value's forwards, update_value, V'(obs) |
+ * V'(next_obs), update_critic with the soft update, the target critics again, update_actor: 3 (Lq + Lv) + 2 Lp + 8 launches for Lv, Lq,
+ * Lp layers (n_units + 1) of value, critic and actor, whatever the number of members; the member index is one more grid dimension -
+ * bit for bit what bdr_agent_opt of the members one after the other gives.  The calls carry the semantics of their bdr_bc_group_*
+ * namesakes: create adopts the members onto one stream and owns them from then on (bdr_agent_destroy of a member is refused;
+ * bdr_iql_group_destroy destroys them), every bdr_agent_* / bdr_iql_* call on a member (update_on_batch, sample, probe, parameter views,
+ * checkpoints) keeps its meaning and is ordered with the group's calls.
+ * One value for all members: obs_dim, act_dim, the three networks' units and activation_out, n_critics, batch_size, the device.  Free
+ * per member: seed, tau_iql, inv_lambda, exp_adv_max, gamma, critic_tau, adv_softmax, critic_loss, the action limit and its scale, the
+ * log-std clamps, the three learning rates, optimizer kinds and scalars.  Refused (BDR_ERR_INVALID, naming the first member concerned):
+ * a non-IQL agent, another shape, n_critics > 2, n_critics x critic layers > 16, more than 12 reduce segments, n_updates_per_opt != 1,
+ * profiling or a gradient communicator switched on, another device, the same agent twice, an agent that is in a group already; more
+ * than 65535 members or a launch beyond the grid limits (naming the kernel).
+ * buffers[p] is member p's: a uniform StdRng ring of f32 rows on the group's device, or a view of one.  A prioritized ring, a frame store,
+ * the xoshiro stream, an empty ring (BDR_ERR_EMPTY), a NULL and one bdr_replay for two members are refused, naming the member, and a
+ * refused call leaves every member's three step counters, n_opts and stream position where they were.  _opt does not synchronise;
+ * _opt_with_scalars synchronises once and returns every member's record (three keys: loss_value, loss_critic, loss_actor; cap_per_member
+ * >= 3) at out + p * cap_per_member.  _info fills bdr_group_info with form = BDR_GROUP_FORM_IQL_LAYERS. */
+typedef struct bdr_iql_group bdr_iql_group;
+BDR_API int32_t bdr_iql_group_create(bdr_agent* const* agents, uint32_t n, bdr_iql_group** out);   /* iql/base.rs:157-188 (opt_ of every member) */
+BDR_API int32_t bdr_iql_group_destroy(bdr_iql_group* g);                                           /* iql/base.rs:157-188 */
+BDR_API int32_t bdr_iql_group_size(const bdr_iql_group* g, uint32_t* n);                           /* iql/base.rs:157-188 */
+BDR_API int32_t bdr_iql_group_member(const bdr_iql_group* g, uint32_t i, bdr_agent** out);         /* iql/base.rs:157-188 */
+BDR_API int32_t bdr_iql_group_info(const bdr_iql_group* g, bdr_group_info* out);                   /* iql/base.rs:157-188 */
+BDR_API int32_t bdr_iql_group_opt(bdr_iql_group* g, bdr_replay* const* buffers);                   /* iql/base.rs:157-188 */
+BDR_API int32_t bdr_iql_group_opt_with_scalars(bdr_iql_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);   /* iql/base.rs:157-188, record :177-185 */
+BDR_API int32_t bdr_iql_group_sync(bdr_iql_group* g);                                              /* iql/base.rs:157-188 */
 
 /* ------------------------------------------------------------------------------------------
  * AWAC agent  (border-candle-agent/src/awac/{base.rs,config.rs}; offline and online RL)

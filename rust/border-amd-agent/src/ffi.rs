@@ -119,6 +119,7 @@ pub const BDR_CKPT_SAFETENSORS: i32 = 1;
 pub const BDR_GROUP_FORM_ONE_WORKGROUP: i32 = 0;
 pub const BDR_GROUP_FORM_LAYERS: i32 = 1;
 pub const BDR_GROUP_FORM_BC_LAYERS: i32 = 2;
+pub const BDR_GROUP_FORM_IQL_LAYERS: i32 = 3;
 pub const BDR_IQN_CONST10: i32 = 0;
 pub const BDR_IQN_CONST32: i32 = 1;
 pub const BDR_IQN_UNIFORM10: i32 = 2;
@@ -148,6 +149,8 @@ pub const BDR_ACT_PATH_FUSED: i32 = 2;
 pub enum bdr_agent_group {}
 /// `bdr_bc_group` (a launch grouping of BC agents): only ever behind a pointer.
 pub enum bdr_bc_group {}
+/// `bdr_iql_group` (a launch grouping of IQL agents): only ever behind a pointer.
+pub enum bdr_iql_group {}
 #[repr(C)]
 pub struct bdr_replay {
     _private: [u8; 0],
@@ -1069,6 +1072,14 @@ extern "C" {
     pub fn bdr_bc_group_opt(g: *mut bdr_bc_group, buffers: *mut *const bdr_replay) -> i32;
     pub fn bdr_bc_group_opt_with_scalars(g: *mut bdr_bc_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
     pub fn bdr_bc_group_sync(g: *mut bdr_bc_group) -> i32;
+    pub fn bdr_iql_group_create(agents: *mut *const bdr_agent, n: u32, out: *mut *mut bdr_iql_group) -> i32;
+    pub fn bdr_iql_group_destroy(g: *mut bdr_iql_group) -> i32;
+    pub fn bdr_iql_group_size(g: *const bdr_iql_group, n: *mut u32) -> i32;
+    pub fn bdr_iql_group_member(g: *const bdr_iql_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_iql_group_info(g: *const bdr_iql_group, out: *mut bdr_group_info) -> i32;
+    pub fn bdr_iql_group_opt(g: *mut bdr_iql_group, buffers: *mut *const bdr_replay) -> i32;
+    pub fn bdr_iql_group_opt_with_scalars(g: *mut bdr_iql_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
+    pub fn bdr_iql_group_sync(g: *mut bdr_iql_group) -> i32;
     pub fn bdr_bc_group_sample(
         g: *mut bdr_bc_group,
         norms: *mut *const bdr_obs_norm,

@@ -13,6 +13,7 @@ use crate::{
     error::{check, expect},
     evaluator::EvalResult,
     ffi,
+    iql::AmdIql,
     replay::AmdReplayBuffer,
 };
 use anyhow::{anyhow, Result};
@@ -752,6 +753,131 @@ where
 {
     fn drop(&mut self) {
         expect(unsafe { ffi::bdr_bc_group_destroy(self.g) }, "bdr_bc_group_destroy");
+        for m in self.members.iter_mut() {
+            m.a.h = std::ptr::null_mut(); // destroyed with the group; bdr_agent_destroy(NULL) in the member's own drop is a no-op
+        }
+    }
+}
+
+/// A group of IQL agents of one shape whose `Agent::opt` (`Iql::opt_`, iql/base.rs:157-188) runs as the launch sequence of ONE member,
+/// every launch serving all members (`bdr_iql_group_*`): 3 (Lq + Lv) + 2 Lp + 8 launches per round for Lv, Lq, Lp layers of value,
+/// critic and actor, whatever the number of members.  The members may differ in seed, expectile, temperature, discount, the
+/// critics' tau, advantage form, critic loss, action limit, learning rates and optimizers; member `i` steps on `buffers[i]`, a
+/// uniform buffer of its own or a view of one ([`AmdReplayBuffer::view`]), so that P members hold one copy of a dataset.
+///
+/// A launch grouping, not an agent kind: the members are ordinary [`AmdIql`] agents ([`AmdIqlGroup::member_mut`]) on the group's
+/// stream.  Results are bit for bit those of stepping the same agents one after the other.  Owns its members: dropping the group
+/// destroys them (`bdr_iql_group_destroy`).
+pub struct AmdIqlGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    g: *mut ffi::bdr_iql_group,
+    members: Vec<AmdIql<E, O, A>>,
+}
+
+// SAFETY: as `AgentHandle` - one HIP stream for the group and its members, all device work behind `&mut`.
+unsafe impl<E: Env, O: RowBatch, A: RowBatch> Send for AmdIqlGroup<E, O, A> {}
+
+impl<E, O, A> AmdIqlGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    /// Groups agents that already exist.  Fails, naming the first member concerned and the reason, unless all members are IQL
+    /// agents of one shape (obs and act dims, the three networks, at most two critics, batch size) with `n_updates_per_opt == 1`
+    /// on one device; the agents are then dropped as ordinary agents.
+    pub fn adopt(members: Vec<AmdIql<E, O, A>>) -> Result<Self> {
+        if members.is_empty() {
+            return Err(anyhow!("a group needs at least one member"));
+        }
+        let mut hs: Vec<*const ffi::bdr_agent> = members.iter().map(|m| m.a.h as *const ffi::bdr_agent).collect();
+        let mut g = std::ptr::null_mut();
+        check(unsafe { ffi::bdr_iql_group_create(hs.as_mut_ptr(), hs.len() as u32, &mut g) })?;
+        Ok(Self { g, members })
+    }
+
+    pub fn handle(&self) -> *mut ffi::bdr_iql_group {
+        self.g
+    }
+
+    pub fn len(&self) -> usize {
+        self.members.len()
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.members.is_empty()
+    }
+
+    pub fn member(&self, i: usize) -> &AmdIql<E, O, A> {
+        &self.members[i]
+    }
+
+    /// A member as the ordinary agent it is (`Agent`, `Policy`, `SyncModel`, `save_params` ...).
+    pub fn member_mut(&mut self, i: usize) -> &mut AmdIql<E, O, A> {
+        &mut self.members[i]
+    }
+
+    /// `bdr_iql_group_info`: `form` is `ffi::BDR_GROUP_FORM_IQL_LAYERS`, `launches_per_round` the kernel launches of one update
+    /// round, `kernel_launches` those the group's own calls have enqueued since it was created.
+    pub fn info(&self) -> Result<ffi::bdr_group_info> {
+        let mut out = ffi::bdr_group_info::default();
+        check(unsafe { ffi::bdr_iql_group_info(self.g, &mut out) })?;
+        Ok(out)
+    }
+
+    fn buffer_handles(&self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<*const ffi::bdr_replay>> {
+        if buffers.len() != self.members.len() {
+            return Err(anyhow!("{} members need {} buffers, got {}", self.members.len(), self.members.len(), buffers.len()));
+        }
+        Ok(buffers.iter().map(|b| b.h as *const ffi::bdr_replay).collect())
+    }
+
+    /// `Agent::opt` of every member, member `i` on `buffers[i]`; only enqueues.  A refused call (a prioritized, empty, mismatched
+    /// or shared buffer) leaves every member and every buffer where it was.
+    pub fn opt(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        check(unsafe { ffi::bdr_iql_group_opt(self.g, hs.as_mut_ptr()) })
+    }
+
+    /// `Agent::opt_with_record` of every member: the same round, one synchronisation, the members' `Record`s (`loss_value`,
+    /// `loss_critic`, `loss_actor`) in member order.
+    pub fn opt_with_record(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<Record>> {
+        const CAP: usize = 8;
+        let mut hs = self.buffer_handles(buffers)?;
+        let n = self.members.len();
+        let mut vals = vec![0f32; n * CAP];
+        let mut counts = vec![0i32; n];
+        check(unsafe { ffi::bdr_iql_group_opt_with_scalars(self.g, hs.as_mut_ptr(), vals.as_mut_ptr(), CAP as i32, counts.as_mut_ptr()) })?;
+        let mut out = Vec::with_capacity(n);
+        for (i, m) in self.members.iter_mut().enumerate() {
+            let keys = m.a.record_keys().to_vec();
+            let mut record = Record::empty();
+            for (k, v) in keys.iter().zip(vals[i * CAP..].iter().take(counts[i] as usize)) {
+                record.insert(k.clone(), RecordValue::Scalar(*v));
+            }
+            out.push(record);
+        }
+        Ok(out)
+    }
+
+    /// Waits for everything the group and its members have enqueued (`bdr_iql_group_sync`).
+    pub fn sync(&mut self) -> Result<()> {
+        check(unsafe { ffi::bdr_iql_group_sync(self.g) })
+    }
+}
+
+impl<E, O, A> Drop for AmdIqlGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    fn drop(&mut self) {
+        expect(unsafe { ffi::bdr_iql_group_destroy(self.g) }, "bdr_iql_group_destroy");
         for m in self.members.iter_mut() {
             m.a.h = std::ptr::null_mut(); // destroyed with the group; bdr_agent_destroy(NULL) in the member's own drop is a no-op
         }
