@@ -264,7 +264,7 @@ class GroupTrainerPostC(C.Structure):
                 ("model_dirs", C.POINTER(C.c_char_p)), ("eval_ops", GroupEvalOps), ("save_member", G_SAVE_MEMBER_FN)]
 
 
-# bdr_bc_group_eval_ops / bdr_bc_group_trainer_post: the lockstep evaluator of a BC group and post_process in its offline loop
+# bdr_bc_group_eval_ops / bdr_bc_group_trainer_post: the lockstep evaluator of a BC or IQL group and post_process in its offline loop
 BG_SAMPLE_MEMBERS_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_void_p))
 
@@ -353,6 +353,8 @@ ABI_SYMBOLS = [
     "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default", "bdr_trainer_train_offline_group_post",
     "bdr_iql_group_create", "bdr_iql_group_destroy", "bdr_iql_group_size", "bdr_iql_group_member", "bdr_iql_group_info",
     "bdr_iql_group_opt", "bdr_iql_group_opt_with_scalars", "bdr_iql_group_sync",
+    "bdr_iql_group_sample", "bdr_iql_group_sample_members", "bdr_iql_group_eval_ops_default", "bdr_iql_group_trainer_ops_default",
+    "bdr_iql_group_trainer_post_default",
 ]
 
 _lib = None
@@ -381,7 +383,8 @@ def lib() -> C.CDLL:
                         "bdr_explorer_config_default", "bdr_per_config_default", "bdr_atari_clip_reward", "bdr_trainer_config_default",
                         "bdr_trainer_ops_default", "bdr_evaluator_default", "bdr_trainer_post_default", "bdr_async_trainer_config_default", "bdr_learner_ops_default", "bdr_actor_ops_default",
                         "bdr_group_trainer_ops_default", "bdr_group_eval_ops_default", "bdr_group_trainer_post_default",
-                        "bdr_bc_group_eval_ops_default", "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default"):
+                        "bdr_bc_group_eval_ops_default", "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default",
+                        "bdr_iql_group_eval_ops_default", "bdr_iql_group_trainer_ops_default", "bdr_iql_group_trainer_post_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -570,6 +573,14 @@ def lib() -> C.CDLL:
     L.bdr_bc_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
     L.bdr_bc_group_trainer_post_default.restype = None
     L.bdr_bc_group_trainer_post_default.argtypes = [C.POINTER(BcGroupTrainerPostC), vp]
+    L.bdr_iql_group_sample.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.bdr_iql_group_sample_members.argtypes = [vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
+    L.bdr_iql_group_eval_ops_default.restype = None
+    L.bdr_iql_group_eval_ops_default.argtypes = [C.POINTER(BcGroupEvalOps), vp]
+    L.bdr_iql_group_trainer_ops_default.restype = None
+    L.bdr_iql_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
+    L.bdr_iql_group_trainer_post_default.restype = None
+    L.bdr_iql_group_trainer_post_default.argtypes = [C.POINTER(BcGroupTrainerPostC), vp]
     L.bdr_trainer_train_offline_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(GroupTrainerOps), C.POINTER(BcGroupTrainerPostC),
                                                        GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     _lib = L

@@ -24,6 +24,7 @@
 #include "slot_ring.hpp"
 #include "device_arrays.hpp"
 #include "group_done.hpp"
+#include "group_act.hpp"
 #include "bc_group_plan.hpp"
 
 static_assert(BG_FORM_DEFAULT == BDR_BC_KERNEL_DEFAULT && BG_FORM_GENERAL == BDR_BC_KERNEL_GENERAL && BG_FORM_FUSED == BDR_BC_KERNEL_FUSED &&
@@ -83,8 +84,9 @@ __global__ __launch_bounds__(256) void k_bc_reduce_adam_group(const BDR_CONST_AS
 //   (checked by the host before anything is enqueued).  Inside a member every index is the body's own, with the standalone kernel's
 //   bounds: rows are read for m0 + r < n and c < O from the member's staged block of n * O elements, out is written at
 //   (m0 + r) * A + j < n * A inside the member's block of n * A floats.
+// (the host half of an acting call - the member list, the checks, the staging areas, the launch number, the copy out - is
+// group_act.hpp's, shared with the IQL group)
 struct BcActCall { const uint8_t* rows; unsigned long long row_stride; const float* mean; const float* std; float* out; long long* idx; int n, f64; };
-constexpr size_t BG_ACT_STAGE_MAX = (size_t)64 << 20;   // staged rows (and results) of one call
 
 template <int TEAMS>
 __global__ __launch_bounds__(256 * TEAMS) void k_bc_act_group(const BDR_CONST_AS DenseActArgs* args, const BDR_CONST_AS BcActCall* calls, const BDR_CONST_AS unsigned* sel,
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(256 * TEAMS) void k_bc_act_group(const BDR_CONST_AS
 {
     extern __shared__ __attribute__((aligned(16))) float da_lds[];
     const unsigned member = sel[blockIdx.y];
-    dense_act_body<TEAMS, true>(args[member], calls[member], da_lds);
+    dense_act_body<TEAMS, DA_EPI_BC>(args[member], calls[member], da_lds);
     __threadfence_system();   // this thread's result rows are in host memory before its workgroup counts
     bg_group_done(ticket, seq_host, seq);
 }
@@ -195,15 +197,7 @@ struct bdr_bc_group {
     DeviceArray<unsigned> ticket;
     uint64_t launches = 0;                                              // launch numbers given out so far (1-based)
     std::vector<bdr_replay*> last_buffers;                              // the buffers of the last accepted opt (distinctness checked once)
-    // group acting (bc_group_sample).  Static per member: d_act, rewritten when the member's parameter arena has moved (act_keys), behind a
-    // stream synchronise.  Per call: calls / sel and the staged rows and results, ONE area each - an acting call is synchronous, so
-    // the areas are free again whenever the next call fills them; rows and results grow on demand behind a stream synchronise.
-    int act_W = 0, act_teams = 0; bool act_attr = false;
-    std::vector<const float*> act_keys;                                 // [P] the arena d_act[p] was written for (null: not yet)
-    std::vector<DenseActArgs> h_act; DeviceArray<DenseActArgs> d_act;   // [P]
-    PinnedArray<BcActCall> act_calls; PinnedArray<unsigned> act_sel;    // [P], [P]
-    PinnedArray<uint8_t> act_rows; size_t act_rows_cap = 0;             // bytes
-    PinnedArray<float> act_res; size_t act_res_cap = 0;                 // floats
+    GroupAct<BcActCall> act;                                            // group acting (group_act.hpp): static arguments, call words, staging areas
 
     size_t fwd_at(int i, size_t P) const { return (size_t)i * P; }
     size_t dx_at(int j, size_t P) const { return (size_t)(nfwd + j) * P; }   // j-th dX launch of the round
@@ -380,125 +374,35 @@ int32_t bc_group_opt(bdr_bc_group* g, bdr_replay* const* buffers)
     return BDR_OK;
 }
 
-// Policy::sample of the selected members (members == nullptr: all of them) on n host rows each, ONE launch.  Everything is checked
-// before anything is staged or enqueued; every refusal names the member.
+// Policy::sample of the selected members (members == nullptr: all of them) on n host rows each, ONE launch: group_act.hpp's call with
+// what is BC's - the policy net on the member's arena, bc_act_out of its activation_out, no words beyond the common ones
+struct BcActKind {
+    using Call = BcActCall;
+    const float* arena(const Bc* m) const { return m->p; }
+    void write_static(const Bc* m, DenseActArgs& a) const
+    {
+        a.nl = (int)m->net.L.size();
+        for (int l = 0; l < a.nl; ++l) a.L[l] = DenseActLayer{m->p + m->net.L[l].w, m->p + m->net.L[l].b, m->net.L[l].Kp, m->net.L[l].Np, m->net.L[l].relu};
+        a.mode = DA_BC; a.kind = m->cfg.policy.activation_out;
+    }
+    void noise(const Bc*, int*, uint64_t*) const {}   // (no noise stream: nothing draws)
+    void call_words(Bc*, BcActCall&, int, uint64_t, uint64_t) const {}
+    hipError_t set_lds_attr(int teams) const
+    {
+        return teams == 2 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bc_act_group<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX)
+                          : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bc_act_group<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX);
+    }
+    void launch(int teams, dim3 grid, size_t lds, hipStream_t stream, const BDR_CONST_AS DenseActArgs* args, const BDR_CONST_AS BcActCall* calls,
+                const BDR_CONST_AS unsigned* sel, unsigned* ticket, unsigned* seq_host, unsigned seq) const
+    {
+        if (teams == 2) hipLaunchKernelGGL(k_bc_act_group<2>, grid, dim3(512), lds, stream, args, calls, sel, ticket, seq_host, seq);
+        else hipLaunchKernelGGL(k_bc_act_group<1>, grid, dim3(256), lds, stream, args, calls, sel, ticket, seq_host, seq);
+    }
+};
 int32_t bc_group_sample(bdr_bc_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
                         const int32_t* dtypes, float* const* act_out)
 {
-    const uint32_t P = (uint32_t)g->members.size();
-    BDR_REQUIRE(n_sel >= 1, "the member list is empty");
-    for (uint32_t b = 0; members && b < n_sel; ++b) {
-        BDR_REQUIRE(members[b] < P, "member %u (entry %u of the member list) of a group of %u", members[b], b, P);
-        BDR_REQUIRE(b == 0 || members[b] > members[b - 1], "member %u (entry %u of the member list): the list must be strictly ascending", members[b], b);
-    }
-    BDR_REQUIRE(members || n_sel == P, "%u rows for a group of %u", n_sel, P);
-    const auto at = [&](uint32_t b) { return members ? members[b] : b; };
-    BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
-    const int O = g->shape.obs_dim, A = g->shape.act_dim;
-    if (!g->act_W) {
-        g->act_W = g->members[0]->act_width();
-        g->act_teams = dense_act_lds(g->act_W, 2) <= DA_LDS_MAX ? 2 : 1;
-    }
-    size_t staged = 0;
-    for (uint32_t b = 0; b < n_sel; ++b) {
-        const uint32_t p = at(b);
-        BDR_REQUIRE(rows[p], "member %u: null observation rows", p);
-        BDR_REQUIRE(act_out[p], "member %u: null act_out", p);
-        const int32_t dt = dtypes[p];
-        BDR_REQUIRE(dt == BDR_DTYPE_F32 || dt == BDR_DTYPE_F64, "member %u: dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64", p);
-        if (const bdr_obs_norm* nm = norms ? norms[p] : nullptr) {
-            BDR_REQUIRE(nm->ready, "member %u: the normaliser has no statistics yet (bdr_obs_norm_finish / bdr_obs_norm_set)", p);
-            BDR_REQUIRE(nm->dim == (uint64_t)O, "member %u: the normaliser's dim (%llu) is not the agent's obs dim (%d)", p, (unsigned long long)nm->dim, O);
-            BDR_REQUIRE(nm->device == g->device, "member %u: agent and normaliser live on different devices", p);
-        }
-        BDR_REQUIRE(g->act_W <= DA_MAX_W && dense_act_lds(g->act_W, 1) <= DA_LDS_MAX,
-                    "member %u: the group acting kernel keeps two [32][W + 4] activation buffers in LDS: W <= %d, this member's widest padded layer is %d: "
-                    "such members keep acting standalone (bdr_agent_sample_raw)", p, DA_MAX_W, g->act_W);
-        staged += ((size_t)n * O * (dt == BDR_DTYPE_F64 ? 8 : 4) + 15) / 16 * 16;
-    }
-    const size_t res_floats = (size_t)n_sel * n * A;
-    BDR_REQUIRE(staged <= BG_ACT_STAGE_MAX && res_floats * 4 <= BG_ACT_STAGE_MAX,
-                "member %u .. %u: %zu bytes of rows and %zu bytes of actions in one group acting call, more than the staging area's %zu: split the call",
-                at(0), at(n_sel - 1), staged, res_floats * 4, BG_ACT_STAGE_MAX);
-    BDR_HIP(hipSetDevice(g->device));
-    // ---- the areas (first call, growth) and the static arguments (first call, a moved arena): rare, behind whatever the stream holds
-    if (!g->d_act) {   // (d_act last: a failure before it leaves the first call to be made again)
-        BDR_HIP(pinned_array(g->act_calls, P));
-        BDR_HIP(pinned_array(g->act_sel, P));
-        g->h_act.assign(P, DenseActArgs{});
-        g->act_keys.assign(P, nullptr);
-        BDR_HIP(device_array(g->d_act, P));
-    }
-    if (staged > g->act_rows_cap) {
-        BDR_HIP(hipStreamSynchronize(g->stream));
-        const size_t cap = std::max(staged, (size_t)64 * 1024);
-        g->act_rows_cap = 0;
-        BDR_HIP(pinned_array(g->act_rows, cap));
-        g->act_rows_cap = cap;
-    }
-    if (res_floats > g->act_res_cap) {
-        BDR_HIP(hipStreamSynchronize(g->stream));
-        const size_t cap = std::max(res_floats, (size_t)16 * 1024);
-        g->act_res_cap = 0;
-        BDR_HIP(pinned_array(g->act_res, cap));
-        g->act_res_cap = cap;
-    }
-    bool dirty = false;
-    for (uint32_t b = 0; b < n_sel; ++b) {
-        const uint32_t p = at(b);
-        const Bc* m = g->members[p];
-        if (g->act_keys[p] == m->p) continue;
-        DenseActArgs& a = g->h_act[p];
-        a = DenseActArgs{};
-        a.O = O; a.A = A; a.nl = (int)m->net.L.size(); a.W = g->act_W;
-        for (int l = 0; l < a.nl; ++l) a.L[l] = DenseActLayer{m->p + m->net.L[l].w, m->p + m->net.L[l].b, m->net.L[l].Kp, m->net.L[l].Np, m->net.L[l].relu};
-        a.mode = DA_BC; a.kind = m->cfg.policy.activation_out;
-        g->act_keys[p] = m->p;
-        dirty = true;
-    }
-    if (dirty) {
-        hipError_t e = hipStreamSynchronize(g->stream);
-        if (e == hipSuccess) e = hipMemcpy(g->d_act.get(), g->h_act.data(), (size_t)P * sizeof(DenseActArgs), hipMemcpyHostToDevice);
-        if (e != hipSuccess) g->act_keys.assign(P, nullptr);   // (nothing is known to be on the device: the next call writes it again)
-        BDR_HIP(e);
-    }
-    if (!g->act_attr) {   // more than 64 KB of dynamic LDS has to be asked for, once per group (and so per device)
-        BDR_HIP(g->act_teams == 2 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bc_act_group<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX)
-                                  : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bc_act_group<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX));
-        g->act_attr = true;
-    }
-    // ---- this call's words, rows and selection
-    size_t off = 0;
-    for (uint32_t b = 0; b < n_sel; ++b) {
-        const uint32_t p = at(b);
-        const bool f64 = dtypes[p] == BDR_DTYPE_F64;
-        const size_t row = (size_t)O * (f64 ? 8 : 4), bytes = (size_t)n * row;
-        memcpy(g->act_rows.host.get() + off, rows[p], bytes);
-        const bdr_obs_norm* nm = norms ? norms[p] : nullptr;
-        g->act_calls.host.get()[p] = BcActCall{g->act_rows.dev + off, row, nm ? nm->d_meanf : nullptr, nm ? nm->d_stdf : nullptr,
-                                               g->act_res.dev + (size_t)b * n * A, nullptr, (int)n, f64 ? 1 : 0};
-        g->act_sel.host.get()[b] = p;
-        off += (bytes + 15) / 16 * 16;
-    }
-    std::atomic_thread_fence(std::memory_order_release);
-    // the launch takes the next number of the group's one counter: opt rounds and acting calls are ordered on the group's stream
-    const uint64_t k = g->launches + 1;
-    g->launches = k;
-    const dim3 grid((unsigned)((n + 31) / 32), n_sel);
-    const size_t lds = dense_act_lds(g->act_W, g->act_teams);
-    const auto* d_args = (const BDR_CONST_AS DenseActArgs*)g->d_act.get();
-    const auto* d_calls = (const BDR_CONST_AS BcActCall*)g->act_calls.dev;
-    const auto* d_sel = (const BDR_CONST_AS unsigned*)g->act_sel.dev;
-    if (g->act_teams == 2) hipLaunchKernelGGL(k_bc_act_group<2>, grid, dim3(512), lds, g->stream, d_args, d_calls, d_sel, g->ticket.get(), g->seq.dev, (unsigned)k);
-    else hipLaunchKernelGGL(k_bc_act_group<1>, grid, dim3(256), lds, g->stream, d_args, d_calls, d_sel, g->ticket.get(), g->seq.dev, (unsigned)k);
-    BDR_HIP(hipGetLastError());
-    g->kernel_launches += 1;
-    bool arrived = false;
-    BDR_TRY(wait_seq_word(g->seq.host.get(), (unsigned)k, g->stream, std::chrono::steady_clock::now(), &arrived));
-    if (!arrived) return fail(BDR_ERR_HIP, "the actions of a group acting call never arrived in host memory");
-    std::atomic_thread_fence(std::memory_order_acquire);
-    for (uint32_t b = 0; b < n_sel; ++b) memcpy(act_out[at(b)], g->act_res.host.get() + (size_t)b * n * A, (size_t)n * A * sizeof(float));
-    return BDR_OK;
+    return group_act_sample(g, BcActKind{}, members, n_sel, norms, n, rows, dtypes, act_out);
 }
 
 }  // namespace

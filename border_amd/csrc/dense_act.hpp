@@ -24,9 +24,9 @@
 //   Bounds.  rows: block row r is read from memory only for m0 + r < n and column c < O, and stored (out / idx) only for
 //   m0 + r < n; LDS rows r >= n - m0 are zero.  LDS: r < 32, c < Kp or Np <= W.  Weights: k < Kp, column < Np of the layer
 //   (t < Np / 32).  out: (m0 + r) * A + j < n * A; idx: m0 + r < n.  mean / std: c < O = the normaliser's dim (checked by the host).
-//   A group.  The body is a function, dense_act_body: k_dense_act runs it on its argument struct, k_bc_act_group (bc_group.hpp) on
-//   args[member] and calls[member] of a BC group with the member as grid dimension y - P members with a row each are P workgroups on
-//   P CUs in one launch, the form this kernel has anyway.
+//   A group.  The body is a function, dense_act_body: k_dense_act runs it on its argument struct, k_bc_act_group (bc_group.hpp) and
+//   k_candle_act_group (candle_act_group.hpp) on args[member] and calls[member] of a group with the member as grid dimension y - P
+//   members with a row each are P workgroups on P CUs in one launch, the form this kernel has anyway.
 #pragma once
 
 namespace bdr {
@@ -136,9 +136,15 @@ __device__ __forceinline__ void dense_act_land(const f32x4 (&v)[8], const f32x4&
 // mode, kind, A, O, W); `call`: the words of this call (rows, row_stride, f64, n, mean, std, out, idx).  The standalone kernel passes
 // its one argument struct as both; the group entry passes a member's entries of two arrays it reads in place through the constant
 // address space, so Args and Call are template parameters and a layer is copied field by field (a struct copy would have to bind a
-// generic reference to the constant address space).  BC_ONLY: the caller has refused every mode but DA_BC - the other epilogues,
-// which leave the kernel early or take a SampleElem by reference, are not instantiated and every thread returns to the entry.
-template <int TEAMS, bool BC_ONLY, class Args, class Call>
+// generic reference to the constant address space).  EPI: the epilogues the entry instantiates.
+//   DA_EPI_ALL     k_dense_act: every mode; DA_BC_DISCRETE and DA_DQN leave the kernel early, DA_CANDLE reads a.e as it stands.
+//   DA_EPI_BC      the caller has refused every mode but DA_BC: bc_act_out alone, every thread returns to the entry.
+//   DA_EPI_CANDLE  the caller has refused every mode but DA_CANDLE: candle_sample_elem on a SampleElem built in registers, field by
+//                  field - the static words (head2, the clamps, the limit, seed, mlp2) from a.e, the words of this call (train,
+//                  counter) from `call`, z null: the draw of element t = (m0 + rr) * A + j of the member's own call is counter + t,
+//                  the one the member's own kernel takes.  Every thread returns to the entry.
+enum { DA_EPI_ALL = 0, DA_EPI_BC = 1, DA_EPI_CANDLE = 2 };
+template <int TEAMS, int EPI, class Args, class Call>
 __device__ __forceinline__ void dense_act_body(const Args& a, const Call& call, float* da_lds)
 {
     constexpr int NTHR = 256 * TEAMS;
@@ -225,7 +231,7 @@ __device__ __forceinline__ void dense_act_body(const Args& a, const Call& call, 
 
     // ---- epilogue: the last layer's rows [32][Np + 4] in cur -> actions
     const int ldz = a.L[a.nl - 1].Np + 4;
-    if constexpr (!BC_ONLY) {
+    if constexpr (EPI == DA_EPI_ALL) {
         if (a.mode == DA_BC_DISCRETE) {
             if (tid < rows_here) call.idx[m0 + tid] = bc_argmax(a.kind, cur + tid * ldz, a.A);
             return;
@@ -239,12 +245,25 @@ __device__ __forceinline__ void dense_act_body(const Args& a, const Call& call, 
             return;
         }
     }
-    for (int e = tid; e < rows_here * a.A; e += NTHR) {
-        const int rr = e / a.A, j = e % a.A;
-        const size_t t = (size_t)(m0 + rr) * a.A + j;
-        const float z = cur[rr * ldz + j];
-        if constexpr (BC_ONLY) call.out[t] = bc_act_out(a.kind, z);
-        else call.out[t] = a.mode == DA_CANDLE ? candle_sample_elem(a.e, z, j, t, a.e.mlp2 ? cur[rr * ldz + a.A + j] : 0.f) : bc_act_out(a.kind, z);
+    if constexpr (EPI == DA_EPI_CANDLE) {
+        SampleElem se;   // field by field: static indices, registers
+        se.head2 = a.e.head2; se.lo = a.e.lo; se.hi = a.e.hi; se.tanh_limit = a.e.tanh_limit; se.amin = a.e.amin; se.amax = a.e.amax; se.scale = a.e.scale;
+        se.seed = a.e.seed; se.mlp2 = a.e.mlp2;
+        se.train = call.train; se.counter = call.counter; se.z = nullptr;
+        for (int e = tid; e < rows_here * a.A; e += NTHR) {
+            const int rr = e / a.A, j = e % a.A;
+            const size_t t = (size_t)(m0 + rr) * a.A + j;
+            const float z = cur[rr * ldz + j];
+            call.out[t] = candle_sample_elem(se, z, j, t, se.mlp2 ? cur[rr * ldz + a.A + j] : 0.f);
+        }
+    } else {
+        for (int e = tid; e < rows_here * a.A; e += NTHR) {
+            const int rr = e / a.A, j = e % a.A;
+            const size_t t = (size_t)(m0 + rr) * a.A + j;
+            const float z = cur[rr * ldz + j];
+            if constexpr (EPI == DA_EPI_BC) call.out[t] = bc_act_out(a.kind, z);
+            else call.out[t] = a.mode == DA_CANDLE ? candle_sample_elem(a.e, z, j, t, a.e.mlp2 ? cur[rr * ldz + a.A + j] : 0.f) : bc_act_out(a.kind, z);
+        }
     }
 }
 
@@ -252,7 +271,7 @@ template <int TEAMS>
 __global__ __launch_bounds__(256 * TEAMS) void k_dense_act(DenseActArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float da_lds[];
-    dense_act_body<TEAMS, false>(a, a, da_lds);
+    dense_act_body<TEAMS, DA_EPI_ALL>(a, a, da_lds);
 }
 
 }  // namespace

@@ -27,6 +27,9 @@
 //   ig_dense_launches: the array holds ndense * P entries; the weight-gradient and reduce + Adam launches of network n (value 0,
 //   critic 1, actor 2) are handed d_dw + n * P / d_ra + n * P: 3 P entries each; NET < 3 = the AdamScalars of an IqlStep;
 //   inside a member every index is the body's own, with the bounds of the standalone kernel.
+// Acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp, which states the bounds of
+// its indices; included by this translation unit only) through group_act.hpp, the host half BC's group shares; IqlActKind below says
+// what is IQL's.
 #pragma once
 #include <atomic>
 #include <memory>
@@ -34,6 +37,8 @@
 #include "slot_ring.hpp"
 #include "device_arrays.hpp"
 #include "dense_group.hpp"
+#include "candle_act_group.hpp"
+#include "group_act.hpp"
 #include "iql_group_plan.hpp"
 
 static_assert(IG_DW_GROUP == DW_GROUP && IG_RA_SEGS == RA_SEGS && IG_MAXZ == DG_MAXZ && IG_SHAPE_LAYERS >= BDR_MAX_UNITS + 1, "iql_group_plan.hpp restates these limits");
@@ -271,6 +276,7 @@ struct bdr_iql_group {
     DeviceArray<unsigned> ticket;
     uint64_t launches = 0;                                                        // launch numbers given out so far (1-based)
     std::vector<bdr_replay*> last_buffers;                                        // the buffers of the last accepted opt (distinctness checked once)
+    GroupAct<CandleActCall> act;                                                  // group acting (group_act.hpp): static arguments, call words, staging areas
 
     hipError_t allocate(size_t P)
     {
@@ -463,7 +469,61 @@ int32_t iql_group_opt(bdr_iql_group* g, bdr_replay* const* buffers)
     return BDR_OK;
 }
 
+// ---- group acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp) -----------------
+// group_act.hpp's call with what is IQL's.  Static, keyed on the actor arena: the actor net pn on pi_p, DA_CANDLE, and the static half of
+// CandleAgent::sample_elem from the member's config (IQL has no Mlp2 actor: mlp2 = 0).  Per call: the member's mode, read now
+// (bdr_agent_set_train), and in train mode its noise counter, which advances by the n * A draws the call takes - sample_elem's rule, so
+// group calls, the member's own sample / sample_raw on either act path and bdr_agent_noise continue one stream in any interleaving.  The
+// call does not go through ensure_batch and does not touch a member's samp: results go to the group's pinned area.
+struct IqlActKind {
+    using Call = CandleActCall;
+    const float* arena(const Iql* m) const { return m->pi_p; }
+    void write_static(const Iql* m, DenseActArgs& a) const
+    {
+        const MlpLayout& pn = m->pn;
+        a.nl = (int)pn.L.size();
+        for (int l = 0; l < a.nl; ++l) a.L[l] = DenseActLayer{m->pi_p + pn.L[l].w, m->pi_p + pn.L[l].b, pn.L[l].Kp, pn.L[l].Np, pn.L[l].relu};
+        a.mode = DA_CANDLE;
+        SampleElem& e = a.e;   // train, counter and z are the call's
+        e.head2 = m->pi_p + m->h2_off; e.mlp2 = 0;
+        e.lo = (float)m->cfg.min_log_std; e.hi = (float)m->cfg.max_log_std; e.tanh_limit = m->cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
+        e.amin = (float)m->cfg.action_min; e.amax = (float)m->cfg.action_max; e.scale = (float)m->cfg.action_scale;
+        e.seed = m->cfg.seed;
+    }
+    void noise(const Iql* m, int* train, uint64_t* counter) const { *train = m->train ? 1 : 0; *counter = m->noise_counter; }
+    void call_words(Iql* m, CandleActCall& c, int train, uint64_t start, uint64_t counter) const
+    {
+        c.train = train; c.counter = train ? start : 0;
+        m->noise_counter = counter;
+    }
+    hipError_t set_lds_attr(int teams) const
+    {
+        return teams == 2 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_candle_act_group<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX)
+                          : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_candle_act_group<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX);
+    }
+    void launch(int teams, dim3 grid, size_t lds, hipStream_t stream, const BDR_CONST_AS DenseActArgs* args, const BDR_CONST_AS CandleActCall* calls,
+                const BDR_CONST_AS unsigned* sel, unsigned* ticket, unsigned* seq_host, unsigned seq) const
+    {
+        if (teams == 2) hipLaunchKernelGGL(k_candle_act_group<2>, grid, dim3(512), lds, stream, args, calls, sel, ticket, seq_host, seq);
+        else hipLaunchKernelGGL(k_candle_act_group<1>, grid, dim3(256), lds, stream, args, calls, sel, ticket, seq_host, seq);
+    }
+};
+int32_t iql_group_sample(bdr_iql_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
+                         const int32_t* dtypes, float* const* act_out)
+{
+    return group_act_sample(g, IqlActKind{}, members, n_sel, norms, n, rows, dtypes, act_out);
+}
+
 }  // namespace
+
+namespace bdr {
+// the action width of a member, for the group evaluator's check of act_row_bytes (trainer.hip); 0: no such member
+int iql_group_act_dim(const void* group, uint32_t member)
+{
+    const auto* g = static_cast<const bdr_iql_group*>(group);
+    return g && member < g->members.size() ? g->members[member]->A : 0;
+}
+}  // namespace bdr
 
 extern "C" {
 
@@ -579,6 +639,19 @@ int32_t bdr_iql_group_opt_with_scalars(bdr_iql_group* g, bdr_replay* const* buff
         if (st != BDR_OK) { if (bdr::g_err_deferred) bdr::g_err_deferred = 2; return st; }
     }
     return BDR_OK;
+}
+
+int32_t bdr_iql_group_sample(bdr_iql_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out)
+{
+    BDR_REQUIRE(g && rows && dtypes && act_out, "null argument");
+    return iql_group_sample(g, nullptr, (uint32_t)g->members.size(), norms, n, rows, dtypes, act_out);
+}
+
+int32_t bdr_iql_group_sample_members(bdr_iql_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n,
+                                     const void* const* rows, const int32_t* dtypes, float* const* act_out)
+{
+    BDR_REQUIRE(g && members && rows && dtypes && act_out, "null argument");
+    return iql_group_sample(g, members, n_sel, norms, n, rows, dtypes, act_out);
 }
 
 int32_t bdr_iql_group_sync(bdr_iql_group* g)

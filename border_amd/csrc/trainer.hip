@@ -25,7 +25,8 @@
 using namespace bdr;
 
 namespace bdr {
-int bc_group_act_dim(const void* group, uint32_t member);   // bc.hip (bc_group.hpp)
+int bc_group_act_dim(const void* group, uint32_t member);    // bc.hip (bc_group.hpp)
+int iql_group_act_dim(const void* group, uint32_t member);   // iql.hip (iql_group.hpp)
 }
 
 namespace {
@@ -270,7 +271,36 @@ int32_t dbg_save_member(void* g, uint32_t member, const char* dir)
     return d_save(m, dir);
 }
 
-// every refusal of bdr_evaluate_bc_group, naming the member: the group acts on host rows, f32 or float64, and writes one f32 action row
+// the IQL group's entries behind the same tables (bdr_iql_group_trainer_ops_default, bdr_iql_group_eval_ops_default)
+int32_t dig_set_train(void* g, int32_t on)
+{
+    uint32_t n = 0;
+    BDR_TRY(bdr_iql_group_size((bdr_iql_group*)g, &n));
+    for (uint32_t i = 0; i < n; ++i) {
+        bdr_agent* m = nullptr;
+        BDR_TRY(bdr_iql_group_member((bdr_iql_group*)g, i, &m));
+        BDR_TRY(bdr_agent_set_train(m, on));
+    }
+    return BDR_OK;
+}
+int32_t dig_opt(void* g, void* const* b) { return bdr_iql_group_opt((bdr_iql_group*)g, (bdr_replay* const*)b); }
+int32_t dig_opt_rec(void* g, void* const* b, float* out, int32_t cap, int32_t* n)
+{
+    return bdr_iql_group_opt_with_scalars((bdr_iql_group*)g, (bdr_replay* const*)b, out, cap, n);
+}
+int32_t dig_sample_members(void* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, const void* const* rows, const int32_t* dtypes,
+                           float* const* act_out)
+{
+    return bdr_iql_group_sample_members((bdr_iql_group*)g, members, n_sel, norms, 1, rows, dtypes, act_out);
+}
+int32_t dig_save_member(void* g, uint32_t member, const char* dir)
+{
+    bdr_agent* m = nullptr;
+    BDR_TRY(bdr_iql_group_member((bdr_iql_group*)g, member, &m));
+    return d_save(m, dir);
+}
+
+// every refusal of bdr_evaluate_bc_group (a BC or an IQL group behind the table), naming the member: the group acts on host rows, f32 or float64, and writes one f32 action row
 int32_t check_bc_group_eval(const bdr_evaluator* evs, const bdr_bc_group_eval_ops* ops)
 {
     BDR_REQUIRE(evs && ops, "null argument");
@@ -285,6 +315,10 @@ int32_t check_bc_group_eval(const bdr_evaluator* evs, const bdr_bc_group_eval_op
             const int A = bc_group_act_dim(ops->group, p);
             BDR_REQUIRE(A > 0, "member %u: the group has no such member", p);
             BDR_REQUIRE(ev.act_row_bytes == (uint64_t)A * 4, "member %u: a BC group acts with one f32 action row per member: act_row_bytes must be 4 * act_dim = %d", p, A * 4);
+        } else if (ops->sample_members == dig_sample_members) {
+            const int A = iql_group_act_dim(ops->group, p);
+            BDR_REQUIRE(A > 0, "member %u: the group has no such member", p);
+            BDR_REQUIRE(ev.act_row_bytes == (uint64_t)A * 4, "member %u: an IQL group acts with one f32 action row per member: act_row_bytes must be 4 * act_dim = %d", p, A * 4);
         } else {
             BDR_REQUIRE(ev.act_row_bytes > 0 && ev.act_row_bytes % 4 == 0, "member %u: a BC group acts with f32 action rows: act_row_bytes must be a positive multiple of 4", p);
         }
@@ -589,7 +623,16 @@ void bdr_bc_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_bc_group* gro
     ops->sample_members = dbg_sample_members;
 }
 
-// the same loop for a BC group: f32 action rows, f32 or float64 observation rows, a normaliser per member
+void bdr_iql_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_iql_group* group)
+{
+    if (!ops) return;
+    memset(ops, 0, sizeof *ops);
+    ops->group = group;
+    if (group) (void)bdr_iql_group_size(group, &ops->n_members);
+    ops->sample_members = dig_sample_members;
+}
+
+// the same loop for a BC or an IQL group: f32 action rows, f32 or float64 observation rows, a normaliser per member
 int32_t bdr_evaluate_bc_group(const bdr_evaluator* evs, const bdr_bc_group_eval_ops* ops, bdr_eval_result* out)
 {
     BDR_REQUIRE(evs && ops && out, "null argument");
@@ -622,7 +665,24 @@ void bdr_bc_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_bc_g
     post->save_member = dbg_save_member;
 }
 
-// Trainer::train_offline (trainer.rs:330-384) with post_process for every member of a group in lockstep
+void bdr_iql_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_iql_group* group, bdr_replay* const* buffers)
+{
+    if (!ops) return;
+    memset(ops, 0, sizeof *ops);
+    ops->group = group; ops->buffers = (void* const*)buffers;
+    if (group) (void)bdr_iql_group_size(group, &ops->n_members);
+    ops->set_train = dig_set_train; ops->opt = dig_opt; ops->opt_with_record = dig_opt_rec;
+}
+
+void bdr_iql_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_iql_group* group)
+{
+    if (!post) return;
+    memset(post, 0, sizeof *post);
+    bdr_iql_group_eval_ops_default(&post->eval_ops, group);
+    post->save_member = dig_save_member;
+}
+
+// Trainer::train_offline (trainer.rs:330-384) with post_process for every member of a group (BC or IQL) in lockstep
 int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, const bdr_group_trainer_ops* ops, const bdr_bc_group_trainer_post* post,
                                              void (*obs)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars,
                                                          int32_t n_scalars),
@@ -634,6 +694,8 @@ int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, con
     const uint32_t P = ops->n_members;
     BDR_REQUIRE(P >= 1 && ops->buffers, "the group function table names no members or no buffers");
     BDR_TRY(check_group_post(post, P, check_bc_group_eval));
+    // a NULL save_member: the save of the group kind the evaluation table names - IQL's default table: an IQL member, anything else: a BC member
+    const auto save_default = post && post->eval_ops.sample_members == dig_sample_members ? dig_save_member : dbg_save_member;
     bdr_trainer_config c = *c_in;
     c.warmup_period = 0; c.opt_interval = 1;            // trainer.rs:345-346
     std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member
@@ -650,7 +712,7 @@ int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, con
         const int32_t event = with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT;
         if (obs)
             for (uint32_t p = 0; p < P; ++p) obs(obs_ctx, p, s.env_steps, s.opt_steps, event, ga.scalars.data() + (size_t)p * 128, with_record ? ga.n_scalars[p] : 0);
-        BDR_TRY(group_post_process(s, ops, post, bdr_evaluate_bc_group, dbg_save_member, max_eval_reward, obs, obs_ctx));
+        BDR_TRY(group_post_process(s, ops, post, bdr_evaluate_bc_group, save_default, max_eval_reward, obs, obs_ctx));
         group_cost_record(s, obs, obs_ctx, P);
         if (s.opt_steps == c.max_opts) break;   // trainer.rs:323-325
     }

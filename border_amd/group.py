@@ -257,6 +257,119 @@ class DqnGroup:
             pass
 
 
+# ---- acting, evaluation and the offline loop of a BcGroup or an IqlGroup: one implementation over the group's C prefix ------------------
+def _group_norms(group, norm):
+    n = len(group._members)
+    if norm is None:
+        return None, None
+    norms = list(norm) if isinstance(norm, (list, tuple)) else [norm] * n
+    if len(norms) != n:
+        raise ValueError(f"{n} members need {n} normalisers (or None), got {len(norms)}")
+    return (C.c_void_p * n)(*[None if x is None else x.handle for x in norms]), norms
+
+
+def _group_sample(group, fn: str, rows, norm, members) -> list:
+    """`fn` / `fn`_members (bdr_bc_group_sample, bdr_iql_group_sample) on one row array per member"""
+    P = len(group._members)
+    od, ad = group._members[0].config.obs_dim, group._members[0].config.act_dim
+    if isinstance(rows, np.ndarray):
+        rows = [rows] * P
+    rows = list(rows)
+    if len(rows) != P:
+        raise ValueError(f"{P} members need {P} row arrays, got {len(rows)}")
+    sel = list(range(P)) if members is None else [int(i) for i in members]
+    staged, ptrs, codes, outs, n = {}, (C.c_void_p * P)(), (C.c_int32 * P)(), [None] * P, None
+    for i in sel:
+        if not 0 <= i < P or rows[i] is None:
+            continue   # (the library refuses it, naming the member)
+        r = rows[i]
+        key = id(r)
+        if key not in staged:   # one host array for several members stays one host pointer
+            a = np.asarray(r)
+            if a.dtype != np.float32:
+                a = a.astype(np.float64, copy=False)
+            staged[key] = np.ascontiguousarray(a).reshape(-1, od)
+        a = staged[key]
+        if n is None:
+            n = a.shape[0]
+        elif a.shape[0] != n:
+            raise ValueError(f"member {i}: {a.shape[0]} rows, the members before it {n}: one n for every member")
+        ptrs[i], codes[i] = a.ctypes.data, _lib.BDR_DTYPE_F32 if a.dtype == np.float32 else _lib.BDR_DTYPE_F64
+        outs[i] = np.empty((n, ad), np.float32)
+    n = 1 if n is None else n
+    out_ptrs = (C.c_void_p * P)(*[None if o is None else o.ctypes.data for o in outs])
+    norms, _keep = _group_norms(group, norm)
+    if members is None:
+        _lib.check(getattr(_lib.lib(), fn)(group._g, norms, n, ptrs, codes, out_ptrs))
+    else:
+        s = np.ascontiguousarray(sel, np.uint32).reshape(-1)
+        _lib.check(getattr(_lib.lib(), fn + "_members")(group._g, s.ctypes.data_as(C.c_void_p), s.size, norms, n, ptrs, codes, out_ptrs))
+    return outs
+
+
+def _group_evaluate(group, prefix: str, evaluators) -> list:
+    """bdr_evaluate_bc_group behind `prefix`_eval_ops_default (bdr_bc_group, bdr_iql_group)"""
+    from .evaluator import EvalResult
+    evaluators = list(evaluators)
+    n = len(group._members)
+    if len(evaluators) != n:
+        raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
+    evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
+    ops = _lib.BcGroupEvalOps()
+    getattr(_lib.lib(), prefix + "_eval_ops_default")(C.byref(ops), group._g)
+    out = (_lib.EvalResultC * n)()
+    rc = _lib.lib().bdr_evaluate_bc_group(evs, C.byref(ops), out)
+    raise_first(evaluators, rc)
+    return [EvalResult(np.float32(o.score), np.float32(o.normalized) if o.has_normalized else None, o.n_steps, o.n_episodes) for o in out]
+
+
+def _group_train_offline(group, prefix: str, record_keys, buffers, max_opts, record_interval, on_record, evaluators, eval_interval, save_interval,
+                         model_dirs, on_event) -> list:
+    """bdr_trainer_train_offline_group_post behind `prefix`_trainer_ops_default / _trainer_post_default; records carry record_keys"""
+    from .trainer import NativeTrainer
+    n = len(group._members)
+    ops = _lib.GroupTrainerOps()
+    getattr(_lib.lib(), prefix + "_trainer_ops_default")(C.byref(ops), group._g, group._buffers(buffers))
+    c = _lib.TrainerConfigC()
+    _lib.lib().bdr_trainer_config_default(C.byref(c))
+    c.max_opts, c.record_agent_info_interval = int(max_opts), int(record_interval or 0)
+    failure, recs = [], [None] * n
+
+    def cb(_ctx, member, env_steps, opt_steps, event, scalars, k):
+        try:
+            name = NativeTrainer.EVENTS[event]
+            vals = [scalars[i] for i in range(k)]
+            if on_event is not None:
+                on_event(member, env_steps, opt_steps, name, vals)
+            if name == "opt_record":
+                recs[member] = {key: float(v) for key, v in zip(record_keys, vals)}
+                if member == n - 1 and on_record is not None:
+                    on_record(opt_steps, list(recs))
+        except BaseException as e:  # noqa: BLE001  (an exception cannot cross the C frame: raised again below)
+            failure.append(e)
+    obs, st = _lib.GROUP_OBSERVER_FN(cb), (_lib.TrainerStatsC * n)()
+    post = _lib.BcGroupTrainerPostC()
+    getattr(_lib.lib(), prefix + "_trainer_post_default")(C.byref(post), group._g)
+    post.eval_interval, post.save_interval = int(eval_interval or 0), int(save_interval or 0)
+    evaluators = list(evaluators) if evaluators is not None else []
+    if evaluators:
+        if len(evaluators) != n:
+            raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
+        evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
+        post.evaluators = evs
+    if model_dirs is not None:
+        if len(model_dirs) != n:
+            raise ValueError(f"{n} members need {n} model directories, got {len(model_dirs)}")
+        dirs = (C.c_char_p * n)(*[None if d is None else str(d).encode() for d in model_dirs])
+        post.model_dirs = dirs
+    rc = _lib.lib().bdr_trainer_train_offline_group_post(C.byref(c), C.byref(ops), C.byref(post), obs, None, st)
+    if failure:
+        raise failure[0]
+    raise_first(evaluators, rc)
+    group.sync()
+    return [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
+
+
 class BcGroup:
     """A set of BC agents of one shape whose Agent::opt runs as the launch sequence of ONE member, every launch serving all members
     (bdr_bc_group_*): 2L + 4 launches per round for L layers in the "general" kernel form, 2L + 2 with the MFMA head, whatever the
@@ -348,15 +461,6 @@ class BcGroup:
                                                             cnt.ctypes.data_as(C.c_void_p)))
         return [{k: float(v) for k, v in zip(("loss",), out[i, :cnt[i]])} for i in range(n)]
 
-    def _norms(self, norm):
-        n = len(self._members)
-        if norm is None:
-            return None, None
-        norms = list(norm) if isinstance(norm, (list, tuple)) else [norm] * n
-        if len(norms) != n:
-            raise ValueError(f"{n} members need {n} normalisers (or None), got {len(norms)}")
-        return (C.c_void_p * n)(*[None if x is None else x.handle for x in norms]), norms
-
     def sample(self, rows, norm=None, members=None) -> list:
         """Policy::sample of the members in ONE launch (bdr_bc_group_sample): a list of float32 arrays [n, act_dim] in member order,
         each with the bits of that member's own `sample_raw(rows[i], norm[i])` on either act path.
@@ -364,59 +468,14 @@ class BcGroup:
         array for all members (an ensemble on one observation batch).  norm: an ObsNormalizer for all members, a list of them /
         None per member, or None.  members: a strictly ascending list of member indices (bdr_bc_group_sample_members): only those
         act; the result still has one entry per member and the entries of members that were not selected are None."""
-        P = len(self._members)
-        od, ad = self._members[0].config.obs_dim, self._members[0].config.act_dim
-        if isinstance(rows, np.ndarray):
-            rows = [rows] * P
-        rows = list(rows)
-        if len(rows) != P:
-            raise ValueError(f"{P} members need {P} row arrays, got {len(rows)}")
-        sel = list(range(P)) if members is None else [int(i) for i in members]
-        staged, ptrs, codes, outs, n = {}, (C.c_void_p * P)(), (C.c_int32 * P)(), [None] * P, None
-        for i in sel:
-            if not 0 <= i < P or rows[i] is None:
-                continue   # (the library refuses it, naming the member)
-            r = rows[i]
-            key = id(r)
-            if key not in staged:   # one host array for several members stays one host pointer
-                a = np.asarray(r)
-                if a.dtype != np.float32:
-                    a = a.astype(np.float64, copy=False)
-                staged[key] = np.ascontiguousarray(a).reshape(-1, od)
-            a = staged[key]
-            if n is None:
-                n = a.shape[0]
-            elif a.shape[0] != n:
-                raise ValueError(f"member {i}: {a.shape[0]} rows, the members before it {n}: one n for every member")
-            ptrs[i], codes[i] = a.ctypes.data, _lib.BDR_DTYPE_F32 if a.dtype == np.float32 else _lib.BDR_DTYPE_F64
-            outs[i] = np.empty((n, ad), np.float32)
-        n = 1 if n is None else n
-        out_ptrs = (C.c_void_p * P)(*[None if o is None else o.ctypes.data for o in outs])
-        norms, _keep = self._norms(norm)
-        if members is None:
-            _lib.check(_lib.lib().bdr_bc_group_sample(self._g, norms, n, ptrs, codes, out_ptrs))
-        else:
-            s = np.ascontiguousarray(sel, np.uint32).reshape(-1)
-            _lib.check(_lib.lib().bdr_bc_group_sample_members(self._g, s.ctypes.data_as(C.c_void_p), s.size, norms, n, ptrs, codes, out_ptrs))
-        return outs
+        return _group_sample(self, "bdr_bc_group_sample", rows, norm, members)
 
     def evaluate(self, evaluators) -> list:
         """The Evaluator of every member in lockstep (bdr_evaluate_bc_group): member i on evaluators[i] (a
         border_amd.evaluator.Evaluator with act_dim = the members' act_dim; environment, n_episodes, obs_dtype, normaliser and
         reference scores may differ per member), ONE acting launch per round over the members that still have an episode open.
         Each EvalResult is what evaluators[i].evaluate(member i) gives.  An exception raised by an environment is raised again here."""
-        from .evaluator import EvalResult
-        evaluators = list(evaluators)
-        n = len(self._members)
-        if len(evaluators) != n:
-            raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
-        evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
-        ops = _lib.BcGroupEvalOps()
-        _lib.lib().bdr_bc_group_eval_ops_default(C.byref(ops), self._g)
-        out = (_lib.EvalResultC * n)()
-        rc = _lib.lib().bdr_evaluate_bc_group(evs, C.byref(ops), out)
-        raise_first(evaluators, rc)
-        return [EvalResult(np.float32(o.score), np.float32(o.normalized) if o.has_normalized else None, o.n_steps, o.n_episodes) for o in out]
+        return _group_evaluate(self, "bdr_bc_group", evaluators)
 
     def train_offline(self, buffers, max_opts: int, record_interval: int = 0, on_record=None, evaluators=None, eval_interval: int = 0,
                       save_interval: int = 0, model_dirs=None, on_event=None) -> list:
@@ -427,48 +486,8 @@ class BcGroup:
         every member in model_dirs[i]/<opt_steps> every save_interval opt steps.  on_event(member, env_steps, opt_steps, event,
         scalars) sees every event ("opt", "opt_record", "eval", "cost").  Synchronised at its end; returns one statistics dict per
         member."""
-        from .trainer import NativeTrainer
-        n = len(self._members)
-        ops = _lib.GroupTrainerOps()
-        _lib.lib().bdr_bc_group_trainer_ops_default(C.byref(ops), self._g, self._buffers(buffers))
-        c = _lib.TrainerConfigC()
-        _lib.lib().bdr_trainer_config_default(C.byref(c))
-        c.max_opts, c.record_agent_info_interval = int(max_opts), int(record_interval or 0)
-        failure, recs = [], [None] * n
-
-        def cb(_ctx, member, env_steps, opt_steps, event, scalars, k):
-            try:
-                name = NativeTrainer.EVENTS[event]
-                vals = [scalars[i] for i in range(k)]
-                if on_event is not None:
-                    on_event(member, env_steps, opt_steps, name, vals)
-                if name == "opt_record":
-                    recs[member] = {key: float(v) for key, v in zip(("loss",), vals)}
-                    if member == n - 1 and on_record is not None:
-                        on_record(opt_steps, list(recs))
-            except BaseException as e:  # noqa: BLE001  (an exception cannot cross the C frame: raised again below)
-                failure.append(e)
-        obs, st = _lib.GROUP_OBSERVER_FN(cb), (_lib.TrainerStatsC * n)()
-        post = _lib.BcGroupTrainerPostC()
-        _lib.lib().bdr_bc_group_trainer_post_default(C.byref(post), self._g)
-        post.eval_interval, post.save_interval = int(eval_interval or 0), int(save_interval or 0)
-        evaluators = list(evaluators) if evaluators is not None else []
-        if evaluators:
-            if len(evaluators) != n:
-                raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
-            evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
-            post.evaluators = evs
-        if model_dirs is not None:
-            if len(model_dirs) != n:
-                raise ValueError(f"{n} members need {n} model directories, got {len(model_dirs)}")
-            dirs = (C.c_char_p * n)(*[None if d is None else str(d).encode() for d in model_dirs])
-            post.model_dirs = dirs
-        rc = _lib.lib().bdr_trainer_train_offline_group_post(C.byref(c), C.byref(ops), C.byref(post), obs, None, st)
-        if failure:
-            raise failure[0]
-        raise_first(evaluators, rc)
-        self.sync()
-        return [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
+        return _group_train_offline(self, "bdr_bc_group", ("loss",), buffers, max_opts, record_interval, on_record, evaluators, eval_interval,
+                                    save_interval, model_dirs, on_event)
 
     def sync(self) -> None:
         _lib.check(_lib.lib().bdr_bc_group_sync(self._g))
@@ -583,6 +602,36 @@ class IqlGroup:
         _lib.check(_lib.lib().bdr_iql_group_opt_with_scalars(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap,
                                                              cnt.ctypes.data_as(C.c_void_p)))
         return [{k: float(v) for k, v in zip(self.RECORD_KEYS, out[i, :cnt[i]])} for i in range(n)]
+
+    def sample(self, rows, norm=None, members=None) -> list:
+        """Policy::sample of the members in ONE launch (bdr_iql_group_sample): a list of float32 arrays [n, act_dim] in member order,
+        each with the bits of that member's own `sample_raw(rows[i], norm[i])` on either act path, in the mode the member is in
+        (`set_train`) and at its own noise counter: a member in train mode takes n * act_dim draws of its noise stream, a member in
+        eval mode none, so group calls and the member's own calls continue one stream.
+        rows: one array per member - float32 or float64, [n, obs_dim] (or [obs_dim]: n = 1), the same n for every member - or ONE
+        array for all members (an ensemble on one observation batch).  norm: an ObsNormalizer for all members, a list of them /
+        None per member, or None.  members: a strictly ascending list of member indices (bdr_iql_group_sample_members): only those
+        act; the result still has one entry per member and the entries of members that were not selected are None."""
+        return _group_sample(self, "bdr_iql_group_sample", rows, norm, members)
+
+    def evaluate(self, evaluators) -> list:
+        """The Evaluator of every member in lockstep (bdr_evaluate_bc_group behind IQL's table): member i on evaluators[i] (a
+        border_amd.evaluator.Evaluator with act_dim = the members' act_dim; environment, n_episodes, obs_dtype, normaliser and
+        reference scores may differ per member), ONE acting launch per round over the members that still have an episode open.
+        Each EvalResult is what evaluators[i].evaluate(member i) gives.  An exception raised by an environment is raised again here."""
+        return _group_evaluate(self, "bdr_iql_group", evaluators)
+
+    def train_offline(self, buffers, max_opts: int, record_interval: int = 0, on_record=None, evaluators=None, eval_interval: int = 0,
+                      save_interval: int = 0, model_dirs=None, on_event=None) -> list:
+        """Trainer::train_offline over the group in compiled code (bdr_trainer_train_offline_group_post): max_opts update rounds on
+        `buffers`; every record_interval-th one is an opt_with_record whose records (RECORD_KEYS) go to on_record(opt_step, records).
+        evaluators / eval_interval / save_interval / model_dirs (one Evaluator and one directory per member): Trainer::post_process
+        after every opt step - a lockstep evaluation every eval_interval opt steps, each member's best model in model_dirs[i]/best,
+        every member in model_dirs[i]/<opt_steps> every save_interval opt steps.  on_event(member, env_steps, opt_steps, event,
+        scalars) sees every event ("opt", "opt_record", "eval", "cost").  Synchronised at its end; returns one statistics dict per
+        member."""
+        return _group_train_offline(self, "bdr_iql_group", self.RECORD_KEYS, buffers, max_opts, record_interval, on_record, evaluators,
+                                    eval_interval, save_interval, model_dirs, on_event)
 
     def sync(self) -> None:
         _lib.check(_lib.lib().bdr_iql_group_sync(self._g))

@@ -1424,7 +1424,10 @@ BDR_API int32_t bdr_bc_group_sample(bdr_bc_group* g, const bdr_obs_norm* const* 
 BDR_API int32_t bdr_bc_group_sample_members(bdr_bc_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms,
                                             uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out);
 
-/* bdr_evaluate_group's rule, word for word, for a BC group: resets in member order, ONE acting call per round over the members with
+/* (bdr_bc_group_eval_ops, bdr_evaluate_bc_group, bdr_bc_group_trainer_post and bdr_trainer_train_offline_group_post below serve BC
+ * groups AND IQL groups: the structs hold a void* group and hooks, and the bdr_iql_group_*_default fillers further down fill them for
+ * an IQL group.  Where the text says "a BC group", an IQL group behind its default table is served the same way.)
+ * bdr_evaluate_group's rule, word for word, for a BC group: resets in member order, ONE acting call per round over the members with
  * an open episode, steps in member order, one f32 accumulator per member in call order; a member that has finished its episodes
  * leaves the selection; score and normalised score as bdr_evaluate.  Member i sees exactly the calls bdr_evaluate(&evs[i], member i)
  * makes.  The differences: actions are f32 rows - act_row_bytes must be 4 * act_dim (checked against the member by the default
@@ -1455,7 +1458,8 @@ typedef struct bdr_bc_group_trainer_post {
     const bdr_evaluator* evaluators;        /* [n_members]; needed when eval_interval > 0 */
     const char* const* model_dirs;          /* [n_members]; needed when something is saved */
     bdr_bc_group_eval_ops eval_ops;
-    int32_t (*save_member)(void* group, uint32_t member, const char* dir);   /* NULL: mkdir -p + bdr_agent_save_params of the member */
+    int32_t (*save_member)(void* group, uint32_t member, const char* dir);   /* NULL: mkdir -p + bdr_agent_save_params of the member (of an
+                                                                              * IQL group when eval_ops is IQL's default table, else of a BC group) */
 } bdr_bc_group_trainer_post;
 /* set_train over the members, opt = bdr_bc_group_opt, opt_with_record = bdr_bc_group_opt_with_scalars; sample and push stay NULL */
 BDR_API void bdr_bc_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_bc_group* group, bdr_replay* const* buffers);
@@ -1465,6 +1469,39 @@ BDR_API int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c
                                                      void (*observer)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps,
                                                                       int32_t event, const float* scalars, int32_t n_scalars),
                                                      void* observer_ctx, bdr_trainer_stats* out);
+
+/* Policy::sample of the members of an IQL group (bdr_iql_group, above) in ONE launch: the one-launch acting kernel (bdr_agent_set_act_path,
+ * BDR_ACT_PATH_FUSED) with the member as one more grid dimension, one workgroup per member and block of 32 rows.  Every array is indexed by
+ * MEMBER: rows[i] = n host rows of obs_dim elements of dtypes[i] (BDR_DTYPE_F32 / BDR_DTYPE_F64), norms[i] = the
+ * normaliser applied to member i's rows (norms or any entry may be NULL), act_out[i] receives [n][act_dim] f32: the bits of
+ * bdr_agent_sample_raw(member i, norms[i], n, rows[i], dtypes[i], 0, 0, act_out[i], NULL) on either act path - the bits of the member's
+ * own bdr_agent_sample_raw in its current mode at its current noise counter.  The same n, 1 <= n <=
+ * 65536, holds for every member; two members may name the same rows.  The call is synchronous and counts as one launch of the group
+ * (bdr_group_info::kernel_launches); n_opts and the three step counters do not move.  _sample_members: only members[0..n_sel) act
+ * (strictly ascending); a member that is not selected sees nothing of the call - its entries of the arrays are not read and nothing of it
+ * is written or advanced.  With every member selected it enqueues what _sample enqueues.
+ * Train and eval mode: each selected member's mode (bdr_agent_set_train) is read at call time, and members of one call may be in
+ * different modes.  A selected member in train mode takes n * act_dim draws at its own noise counter, which then advances by n *
+ * act_dim; in eval mode the counter does not move.  Group calls, the member's own sample / sample_raw on either act path and
+ * bdr_agent_draw_noise therefore continue ONE stream, in any interleaving.  The call touches no member's batch buffers.
+ * Refused with BDR_ERR_INVALID before anything is enqueued and before any counter moves, naming the member: a NULL rows[i] / act_out[i]
+ * of a selected member; an empty, not strictly ascending or out-of-range member list; a normaliser that is not ready, has another dim
+ * or lives on another device; an unknown dtype; an actor whose widest padded layer exceeds 512 (refused at the first acting call, not
+ * at creation: such groups keep stepping and their members keep acting standalone); rows or actions of one call beyond 64 MiB (split
+ * the call). */
+BDR_API int32_t bdr_iql_group_sample(bdr_iql_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
+                                     const int32_t* dtypes, float* const* act_out);   /* util/actor.rs:226-241 */
+BDR_API int32_t bdr_iql_group_sample_members(bdr_iql_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms,
+                                             uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out);   /* util/actor.rs:226-241 */
+/* The tables of bdr_evaluate_bc_group and bdr_trainer_train_offline_group_post for an IQL group: sample_members =
+ * bdr_iql_group_sample_members with n = 1 (act_row_bytes is checked against the member: 4 * act_dim); set_train over the members, opt
+ * = bdr_iql_group_opt, opt_with_record = bdr_iql_group_opt_with_scalars (three keys), sample and push stay NULL; save_member = mkdir -p
+ * + bdr_agent_save_params of the IQL member (actor, critic, critic.tgt, value).  Evaluation runs in eval mode inside the offline loop
+ * (post_process sets it); bdr_evaluate_bc_group called directly acts in whatever mode each member is in, and a member that has
+ * finished its episodes takes no draws. */
+BDR_API void bdr_iql_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_iql_group* group);                                   /* evaluator/default_evaluator.rs:64-88 */
+BDR_API void bdr_iql_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_iql_group* group, bdr_replay* const* buffers);    /* trainer.rs:330-384 */
+BDR_API void bdr_iql_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_iql_group* group);                          /* trainer.rs:231-264 */
 
 /* ------------------------------------------------------------------------------------------
  * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)

@@ -1080,6 +1080,27 @@ extern "C" {
     pub fn bdr_iql_group_opt(g: *mut bdr_iql_group, buffers: *mut *const bdr_replay) -> i32;
     pub fn bdr_iql_group_opt_with_scalars(g: *mut bdr_iql_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
     pub fn bdr_iql_group_sync(g: *mut bdr_iql_group) -> i32;
+    pub fn bdr_iql_group_sample(
+        g: *mut bdr_iql_group,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const f32,
+    ) -> i32;
+    pub fn bdr_iql_group_sample_members(
+        g: *mut bdr_iql_group,
+        members: *const u32,
+        n_sel: u32,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const f32,
+    ) -> i32;
+    pub fn bdr_iql_group_eval_ops_default(ops: *mut bdr_bc_group_eval_ops, group: *mut bdr_iql_group);
+    pub fn bdr_iql_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_iql_group, buffers: *mut *const bdr_replay);
+    pub fn bdr_iql_group_trainer_post_default(post: *mut bdr_bc_group_trainer_post, group: *mut bdr_iql_group);
     pub fn bdr_bc_group_sample(
         g: *mut bdr_bc_group,
         norms: *mut *const bdr_obs_norm,

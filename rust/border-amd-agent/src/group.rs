@@ -864,6 +864,113 @@ where
         Ok(out)
     }
 
+    /// `Policy::sample` of every member in ONE launch (`bdr_iql_group_sample`): member `i` acts on the `n` rows of `rows[i]`
+    /// (`n * obs_dim` f32 values, the same `n` for every member; two members may name the same slice) and gets `n * act_dim`
+    /// actions, the bits of its own `bdr_agent_sample_raw` in its current mode at its current noise counter: a member in train mode
+    /// takes `n * act_dim` draws of its noise stream, a member in eval mode none.  `norms[i]`: the normaliser of member `i`'s rows,
+    /// or null; an empty slice means none for anybody.
+    pub fn sample(&mut self, n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<f32>>> {
+        self.sample_with(None, n, rows, norms)
+    }
+
+    /// The same for the members `members` (strictly ascending indices) only (`bdr_iql_group_sample_members`).  `rows` and the result
+    /// still have one entry per member; the entries of members that are not selected are not read and stay empty, and their noise
+    /// counters stay where they were.
+    pub fn sample_members(&mut self, members: &[u32], n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<f32>>> {
+        self.sample_with(Some(members), n, rows, norms)
+    }
+
+    fn sample_with(&mut self, members: Option<&[u32]>, n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<f32>>> {
+        let p = self.members.len();
+        if rows.len() != p || !(norms.is_empty() || norms.len() == p) {
+            return Err(anyhow!("{} members need {} row slices and {} normalisers (or none), got {} and {}", p, p, p, rows.len(), norms.len()));
+        }
+        let act_dim = self.members[0].act_dim();
+        let selected = |i: usize| members.map_or(true, |m| m.contains(&(i as u32)));
+        let mut out: Vec<Vec<f32>> = (0..p).map(|i| if selected(i) { vec![0f32; n * act_dim] } else { Vec::new() }).collect();
+        for i in (0..p).filter(|&i| selected(i)) {
+            if n == 0 || rows[i].is_empty() || rows[i].len() % n != 0 {
+                return Err(anyhow!("member {}: {} values are not {} rows of one width", i, rows[i].len(), n));
+            }
+        }
+        let mut row_ptrs: Vec<*const c_void> = rows.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut out_ptrs: Vec<*const f32> = out.iter_mut().map(|v| if v.is_empty() { std::ptr::null() } else { v.as_mut_ptr() as *const f32 }).collect();
+        let mut norm_ptrs: Vec<*const ffi::bdr_obs_norm> = norms.to_vec();
+        let norms_arg = if norm_ptrs.is_empty() { std::ptr::null_mut() } else { norm_ptrs.as_mut_ptr() };
+        let dtypes = vec![ffi::BDR_DTYPE_F32; p];
+        check(match members {
+            None => unsafe { ffi::bdr_iql_group_sample(self.g, norms_arg, n as u64, row_ptrs.as_mut_ptr(), dtypes.as_ptr(), out_ptrs.as_mut_ptr()) },
+            Some(m) => unsafe {
+                ffi::bdr_iql_group_sample_members(
+                    self.g,
+                    m.as_ptr(),
+                    m.len() as u32,
+                    norms_arg,
+                    n as u64,
+                    row_ptrs.as_mut_ptr(),
+                    dtypes.as_ptr(),
+                    out_ptrs.as_mut_ptr(),
+                )
+            },
+        })?;
+        Ok(out)
+    }
+
+    /// `DefaultEvaluator` of every member in lockstep (`bdr_evaluate_bc_group` behind IQL's table): member `i` on `evaluators[i]` -
+    /// the C view of an evaluator of this crate with `act_row_bytes = 4 * act_dim`; f32 or float64 rows and a normaliser per member
+    /// are allowed - with ONE acting launch per round over the members that still have an episode open.
+    pub fn evaluate(&mut self, evaluators: &[ffi::bdr_evaluator]) -> Result<Vec<EvalResult>> {
+        let n = self.members.len();
+        if evaluators.len() != n {
+            return Err(anyhow!("{} members need {} evaluators, got {}", n, n, evaluators.len()));
+        }
+        // SAFETY: bdr_iql_group_eval_ops_default fills every field.
+        let mut ops: ffi::bdr_bc_group_eval_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_iql_group_eval_ops_default(&mut ops, self.g) };
+        let mut out = vec![ffi::bdr_eval_result::default(); n];
+        check(unsafe { ffi::bdr_evaluate_bc_group(evaluators.as_ptr(), &ops, out.as_mut_ptr()) })?;
+        Ok(out.iter().map(eval_result).collect())
+    }
+
+    /// `Trainer::train_offline` with `Trainer::post_process` for the group in compiled code
+    /// (`bdr_trainer_train_offline_group_post`): `config.max_opts` update rounds, member `i` on `buffers[i]`; every `eval_interval`
+    /// opt steps a lockstep evaluation on `evaluators`, member `i`'s best model in `model_dirs[i]/best`, every `save_interval` opt
+    /// steps every member in `model_dirs[i]/<opt_steps>`.  An interval of 0 means never; with both 0, `evaluators` and `model_dirs`
+    /// may be empty.
+    pub fn train_offline(
+        &mut self,
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        config: &ffi::bdr_trainer_config,
+        evaluators: &[ffi::bdr_evaluator],
+        eval_interval: usize,
+        save_interval: usize,
+        model_dirs: &[&Path],
+    ) -> Result<Vec<ffi::bdr_trainer_stats>> {
+        let n = self.members.len();
+        if (eval_interval > 0 && evaluators.len() != n) || ((eval_interval > 0 || save_interval > 0) && model_dirs.len() != n) {
+            return Err(anyhow!("{} members need {} evaluators and model directories", n, n));
+        }
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut ops: ffi::bdr_group_trainer_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_iql_group_trainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
+        let mut dirs = Vec::with_capacity(n);
+        for d in model_dirs {
+            dirs.push(CString::new(d.to_string_lossy().as_bytes())?);
+        }
+        let mut dir_ptrs: Vec<*const c_char> = dirs.iter().map(|d| d.as_ptr()).collect();
+        // SAFETY: bdr_iql_group_trainer_post_default fills every field.
+        let mut post: ffi::bdr_bc_group_trainer_post = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_iql_group_trainer_post_default(&mut post, self.g) };
+        post.eval_interval = eval_interval as u64;
+        post.save_interval = save_interval as u64;
+        post.evaluators = if evaluators.is_empty() { std::ptr::null() } else { evaluators.as_ptr() };
+        post.model_dirs = if dir_ptrs.is_empty() { std::ptr::null_mut() } else { dir_ptrs.as_mut_ptr() };
+        let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
+        check(unsafe { ffi::bdr_trainer_train_offline_group_post(config, &ops, &post, None, std::ptr::null_mut(), stats.as_mut_ptr()) })?;
+        self.sync()?;
+        Ok(stats)
+    }
+
     /// Waits for everything the group and its members have enqueued (`bdr_iql_group_sync`).
     pub fn sync(&mut self) -> Result<()> {
         check(unsafe { ffi::bdr_iql_group_sync(self.g) })
