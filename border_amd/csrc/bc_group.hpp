@@ -8,23 +8,17 @@
 // array through the constant address space: the member index comes from blockIdx, so it is uniform and the member's fields are scalar
 // loads, as they are from the kernel-argument segment of the existing entry.  Same bodies, same bits.  The loss and the head count
 // gridDim.x workgroups on the member's OWN ticket: x stays the member's own grid.
-//   static arguments   one device array per kernel family, rewritten only when a member's buffers or ring change (`keys`),
-//                      synchronously, behind a stream synchronise: rare
-//   per step           BcStep[P] in a slot of the pinned, device-mapped step ring: the gather reads word_pos and size of the member's
-//                      entry (GatherStepWords at its start), reduce + Adam its AdamScalars
-// The slot rule (slot_ring.hpp): reduce + Adam is the LAST launch of a round that reads the slot, so it ends with the ticket and
-// publishes the round's launch number (bg_group_done - all workgroups of its two-dimensional grid counted, behind a barrier every
-// thread reaches: dense_reduce_adam_body returns early for threads past the arena, to the entry, not out of the kernel).  The host
-// rewrites a slot only once the pinned word has reached the number recorded for it: no copy command, event or synchronise in the
-// steady loop.
+// The host half - the members' adoption, the static argument arrays and their keys, the step ring and its slot rule, the round, records,
+// sync - is group_core.hpp's, shared with the IQL group; BcGroupKind below says what is BC's.  Per step a member has a BcStep: the
+// gather reads word_pos and size (GatherStepWords at its start), reduce + Adam its AdamScalars.  Reduce + Adam is the LAST launch of a
+// round that reads the slot, so it ends with the ticket and publishes the round's launch number (bg_group_done - all workgroups of its
+// two-dimensional grid counted, behind a barrier every thread reaches: dense_reduce_adam_body returns early for threads past the arena,
+// to the entry, not out of the kernel).
 // Bounds of every new index: member = blockIdx.y < P = the length of every argument array and of a slot; forward launch i reads
 // d_dense[i * P + member], i < nfwd; input-gradient launch j reads d_dense[(nfwd + j) * P + member], j < ndx; the array holds
 // (nfwd + ndx) * P entries.  Inside a member every index is the body's own, with the bounds of the standalone kernel.
 #pragma once
-#include "slot_ring.hpp"
-#include "device_arrays.hpp"
-#include "group_done.hpp"
-#include "group_act.hpp"
+#include "group_core.hpp"
 #include "bc_group_plan.hpp"
 
 static_assert(BG_FORM_DEFAULT == BDR_BC_KERNEL_DEFAULT && BG_FORM_GENERAL == BDR_BC_KERNEL_GENERAL && BG_FORM_FUSED == BDR_BC_KERNEL_FUSED &&
@@ -169,215 +163,9 @@ void bc_member_static(Bc* m, int bs, const bdr_replay* r, const GatherArgs& plan
     ra.tau = 0.f; ra.omt = 1.f;   // (no target: track == 0; s[0] is this step's: BcStep)
 }
 
-}  // namespace
-
-struct bdr_bc_group {
-    enum { STEP_SLOTS = 8 };
-    int32_t device = 0;
-    hipStream_t stream = nullptr;
-    // (bdr_bc_group_destroy has synchronised the stream and destroyed the members; a failed create has adopted nobody.)  The stream
-    // goes first, the buffers - the members below - after it.
-    ~bdr_bc_group() { if (stream) { stream_retire(stream); (void)hipStreamDestroy(stream); } }
-    std::vector<Bc*> members;
-    BgShape shape{};                 // the one shape of all members
-    BgLaunch plan[BG_MAX_LAUNCHES]; int n_launches = 0;
-    int nfwd = 0, ndx = 0, head = 0;
-    uint64_t kernel_launches = 0;    // every kernel launch the group's own calls have enqueued (bdr_bc_group_info)
-    struct StaticKey { bool valid = false; uint64_t batch_gen = 0, r_uid = 0, r_batch_gen = 0; };
-    std::vector<StaticKey> keys;
-    std::vector<GatherArgs> h_gather; DeviceArray<GatherArgs> d_gather;
-    std::vector<PackRowsArgs> h_pack; DeviceArray<PackRowsArgs> d_pack;
-    std::vector<DenseArgs> h_dense; DeviceArray<DenseArgs> d_dense;     // [nfwd][P] then [ndx][P] (launch order)
-    std::vector<BcLossArgs> h_loss; DeviceArray<BcLossArgs> d_loss;
-    std::vector<BcHeadArgs> h_head; DeviceArray<BcHeadArgs> d_head;
-    std::vector<DenseDwSmallGroup> h_dw; DeviceArray<DenseDwSmallGroup> d_dw;
-    std::vector<ReduceAdamArgs> h_ra; DeviceArray<ReduceAdamArgs> d_ra;
-    PinnedArray<BcStep> steps; SlotRing<STEP_SLOTS> step_ring;          // [STEP_SLOTS][P]
-    PinnedArray<unsigned> seq;                                          // pinned word: the launch number published last
-    DeviceArray<unsigned> ticket;
-    uint64_t launches = 0;                                              // launch numbers given out so far (1-based)
-    std::vector<bdr_replay*> last_buffers;                              // the buffers of the last accepted opt (distinctness checked once)
-    GroupAct<BcActCall> act;                                            // group acting (group_act.hpp): static arguments, call words, staging areas
-
-    size_t fwd_at(int i, size_t P) const { return (size_t)i * P; }
-    size_t dx_at(int j, size_t P) const { return (size_t)(nfwd + j) * P; }   // j-th dX launch of the round
-
-    hipError_t allocate(size_t P)
-    {
-        const int L = shape.n_layers;
-        head = shape.form == BG_FORM_FUSED_MFMA ? 1 : 0;
-        nfwd = head ? L - 1 : L;
-        ndx = head ? L - 2 : L - 1;
-        h_gather.resize(P); h_pack.resize(P); h_dense.resize((size_t)(nfwd + ndx) * P); h_loss.resize(P); h_head.resize(P); h_dw.resize(P); h_ra.resize(P);
-        keys.resize(P);
-        hipError_t e = device_array(d_gather, P);
-        if (e == hipSuccess) e = device_array(d_pack, P);
-        if (e == hipSuccess) e = device_array(d_dense, std::max<size_t>(h_dense.size(), 1));
-        if (e == hipSuccess) e = device_array(d_loss, P);
-        if (e == hipSuccess) e = device_array(d_head, P);
-        if (e == hipSuccess) e = device_array(d_dw, P);
-        if (e == hipSuccess) e = device_array(d_ra, P);
-        if (e == hipSuccess) e = device_array(ticket, 1);
-        if (e == hipSuccess) e = hipMemset(ticket.get(), 0, sizeof(unsigned));
-        if (e == hipSuccess) e = pinned_array(steps, (size_t)STEP_SLOTS * P);
-        if (e == hipSuccess) e = pinned_array(seq, 16);   // (one word, a cache line of its own)
-        return e;
-    }
-    // member p's arguments into the staging arrays
-    void stage(size_t p, size_t P, const BcMemberArgs& o)
-    {
-        const int L = shape.n_layers;
-        h_gather[p] = o.gather; h_pack[p] = o.pack; h_loss[p] = o.loss; h_head[p] = o.head; h_dw[p] = o.dw; h_ra[p] = o.ra;
-        for (int i = 0; i < nfwd; ++i) h_dense[fwd_at(i, P) + p] = o.fwd[i];
-        for (int j = 0; j < ndx; ++j) h_dense[dx_at(j, P) + p] = o.dx[(head ? L - 2 : L - 1) - j];
-    }
-    hipError_t upload(size_t P)
-    {
-        hipError_t e = hipMemcpy(d_gather.get(), h_gather.data(), P * sizeof(GatherArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_pack.get(), h_pack.data(), P * sizeof(PackRowsArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !h_dense.empty()) e = hipMemcpy(d_dense.get(), h_dense.data(), h_dense.size() * sizeof(DenseArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_loss.get(), h_loss.data(), P * sizeof(BcLossArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_head.get(), h_head.data(), P * sizeof(BcHeadArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_dw.get(), h_dw.data(), P * sizeof(DenseDwSmallGroup), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_ra.get(), h_ra.data(), P * sizeof(ReduceAdamArgs), hipMemcpyHostToDevice);
-        return e;
-    }
-    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
-    int32_t launch(size_t P, const BcStep* steps_dev, unsigned seq_no)
-    {
-        int fwd = 0, dx = 0;
-        for (int n = 0; n < n_launches; ++n) {
-            const BgLaunch& l = plan[n];
-            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
-            switch (l.kernel) {
-            case BG_K_GATHER:
-                BDR_TRY(replay_gather_group(stream, d_gather.get(), steps_dev, (uint32_t)sizeof(BcStep), (uint32_t)P, (uint64_t)shape.batch, (uint64_t)shape.obs_dim * 4));
-                break;
-            case BG_K_PACK: hipLaunchKernelGGL(k_pack_rows_group, grid, block, 0, stream, (const BDR_CONST_AS PackRowsArgs*)d_pack.get()); break;
-            case BG_K_FWD:
-                hipLaunchKernelGGL(k_bc_dense_small_group<false>, grid, block, 0, stream, (const BDR_CONST_AS DenseArgs*)(d_dense.get() + fwd_at(fwd++, P)));
-                break;
-            case BG_K_LOSS: hipLaunchKernelGGL(k_bc_loss_group, grid, block, 0, stream, (const BDR_CONST_AS BcLossArgs*)d_loss.get()); break;
-            case BG_K_HEAD:
-                if (shape.act_dim <= 32) hipLaunchKernelGGL(k_bc_head_mfma_group<1>, grid, block, 0, stream, (const BDR_CONST_AS BcHeadArgs*)d_head.get());
-                else hipLaunchKernelGGL(k_bc_head_mfma_group<2>, grid, block, 0, stream, (const BDR_CONST_AS BcHeadArgs*)d_head.get());
-                break;
-            case BG_K_DX:
-                hipLaunchKernelGGL(k_bc_dense_small_group<true>, grid, block, 0, stream, (const BDR_CONST_AS DenseArgs*)(d_dense.get() + dx_at(dx++, P)));
-                break;
-            case BG_K_DW: hipLaunchKernelGGL(k_bc_dense_dw_small_group, grid, block, 0, stream, (const BDR_CONST_AS DenseDwSmallGroup*)d_dw.get()); break;
-            case BG_K_REDUCE_ADAM:
-                hipLaunchKernelGGL(k_bc_reduce_adam_group, grid, block, 0, stream, (const BDR_CONST_AS ReduceAdamArgs*)d_ra.get(), (const BDR_CONST_AS BcStep*)steps_dev,
-                                   ticket.get(), seq.dev, seq_no);
-                break;
-            default: return fail(BDR_ERR_INVALID, "BC group round: launch %d of the plan names no kernel", n);
-            }
-            BDR_HIP(hipGetLastError());
-        }
-        return BDR_OK;
-    }
-};
-
-namespace {
-
-// every refusal of a grouped opt, before anything moves: Bc::opt's checks, and what the grouped gather covers
-int32_t bc_group_check_buffers(bdr_bc_group* g, bdr_replay* const* buffers)
-{
-    const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {
-        const Bc* m = g->members[p];
-        const bdr_replay* r = buffers[p];
-        BDR_REQUIRE(r, "member %u: null buffer", p);
-        BDR_REQUIRE(!m->prof && !m->grad_comm, "member %u: profiling or a gradient communicator was switched on after the group was created", p);
-        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == (uint64_t)m->A * 4, "member %u: replay rows do not match BC obs/act dims (f32 rows)", p);
-        BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
-        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot be stepped by a BC group (the grouped gather covers the uniform ring)", p);
-        BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by a BC group", p);
-        BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: the grouped gather draws the StdRng index stream only", p);
-        if (r->size == 0) return fail(BDR_ERR_EMPTY, "member %u: batch() on an empty replay buffer", p);
-    }
-    if (g->last_buffers.size() == P && memcmp(g->last_buffers.data(), buffers, P * sizeof(bdr_replay*)) == 0) return BDR_OK;
-    std::vector<const bdr_replay*> s(buffers, buffers + P);   // workgroups run side by side: one bdr_replay (its batch arrays, its stream position) per member
-    std::sort(s.begin(), s.end());
-    const auto dup = std::adjacent_find(s.begin(), s.end());
-    if (dup != s.end()) {
-        uint32_t second = 0;
-        for (uint32_t p = 0, seen = 0; p < P; ++p) if (buffers[p] == *dup && seen++ == 1) { second = p; break; }
-        return fail(BDR_ERR_INVALID, "member %u: it shares its replay buffer with an earlier member: every member needs a bdr_replay of its own (a view of one ring will do)", second);
-    }
-    g->last_buffers.clear();
-    return BDR_OK;
-}
-
-// one update round: per member what Bc::opt / Bc::update do on the host, then the round's launches, the last of which publishes its number
-int32_t bc_group_round(bdr_bc_group* g, bdr_replay* const* buffers)
-{
-    const uint32_t P = (uint32_t)g->members.size();
-    const uint64_t k = g->launches + 1;
-    const auto slot = g->step_ring.next();
-    if (slot.wait) {   // the slot's last reader has published (bounded: wait_seq_word)
-        bool arrived = false;
-        BDR_TRY(wait_seq_word(g->seq.host.get(), (unsigned)slot.wait, g->stream, std::chrono::steady_clock::now(), &arrived));
-    }
-    BcStep* steps = g->steps.host.get() + (size_t)slot.slot * P;
-    bool dirty = false;
-    for (uint32_t p = 0; p < P; ++p) {
-        Bc* m = g->members[p];
-        bdr_replay* r = buffers[p];
-        const int bs = (int)m->cfg.batch_size;
-        BDR_TRY(m->ensure_batch(bs));
-        GatherArgs plan{};
-        BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));   // the host half of replay_sample_on_stream; the rows are k_gather_group's
-        m->step += 1;
-        const AdamScalars sc = DenseAgent::opt_scalars(m->cfg.opt, m->cfg.lr, m->step);
-        m->n_opts += 1;
-        m->last_B = bs;
-        bdr_bc_group::StaticKey& key = g->keys[p];
-        if (!key.valid || key.batch_gen != m->batch_gen || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
-            BcMemberArgs o;
-            bc_member_static(m, bs, r, plan, o);
-            BDR_REQUIRE(o.dw_grid == (int)g->plan[g->n_launches - 2].gx, "member %u: the weight-gradient grid (%d) differs from the plan's (%u)", p, o.dw_grid,
-                        g->plan[g->n_launches - 2].gx);
-            g->stage(p, P, o);
-            key.valid = true; key.batch_gen = m->batch_gen; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
-            dirty = true;
-        }
-        steps[p] = BcStep{plan.word_pos, plan.size, sc};
-    }
-    if (dirty) {   // rare (first step, a reallocation, another ring): behind everything the stream still holds
-        BDR_HIP(hipStreamSynchronize(g->stream));
-        BDR_HIP(g->upload(P));
-    }
-    std::atomic_thread_fence(std::memory_order_release);
-    // (should a launch fail, k is the number of whatever the group launches next - later than every reader of the slot)
-    g->launches = k; g->step_ring.record(k);
-    BDR_TRY(g->launch(P, g->steps.dev + (size_t)slot.slot * P, (unsigned)k));
-    g->kernel_launches += (uint64_t)g->n_launches;
-    return BDR_OK;
-}
-
-// what bdr_agent_opt does around opt(), for every member, then the round
-int32_t bc_group_opt(bdr_bc_group* g, bdr_replay* const* buffers)
-{
-    BDR_HIP(hipSetDevice(g->device));
-    BDR_TRY(bc_group_check_buffers(g, buffers));
-    const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {   // asynchronous: what an earlier synchronising call of the member read back surfaces here
-        Bc* m = g->members[p];
-        unsigned w[bdr_agent::ERR_WORDS];
-        m->err_mirror_read(w);
-        BDR_TRY(m->err_report(w));
-    }
-    for (uint32_t p = 0; p < P; ++p) g->members[p]->last_replay_uid = buffers[p]->uid;
-    BDR_TRY(bc_group_round(g, buffers));
-    g->last_buffers.assign(buffers, buffers + P);
-    return BDR_OK;
-}
-
-// Policy::sample of the selected members (members == nullptr: all of them) on n host rows each, ONE launch: group_act.hpp's call with
-// what is BC's - the policy net on the member's arena, bc_act_out of its activation_out, no words beyond the common ones
-struct BcActKind {
-    using Call = BcActCall;
+// ---- what is BC's of the group core (group_core.hpp) -------------------------------------------------------------------------------------
+// group acting: the policy net on the member's arena, bc_act_out of its activation_out, no words beyond the common ones
+struct BcActKind : GroupActEntry<BcActCall, k_bc_act_group<1>, k_bc_act_group<2>> {
     const float* arena(const Bc* m) const { return m->p; }
     void write_static(const Bc* m, DenseActArgs& a) const
     {
@@ -387,168 +175,121 @@ struct BcActKind {
     }
     void noise(const Bc*, int*, uint64_t*) const {}   // (no noise stream: nothing draws)
     void call_words(Bc*, BcActCall&, int, uint64_t, uint64_t) const {}
-    hipError_t set_lds_attr(int teams) const
+};
+
+struct BcGroupKind {
+    using Member = Bc; using Shape = BgShape; using Launch = BgLaunch; using Step = BcStep; using MemberArgs = BcMemberArgs; using PlanMember = BgMember;
+    using Act = BcActKind;
+    static constexpr const char *KIND = "bc", *A = "a BC", *NAME = "BC", *CAP_MSG = "cap_per_member must be positive";
+    static constexpr int MAX_LAUNCHES = BG_MAX_LAUNCHES, K_GATHER = BG_K_GATHER, FORM = BDR_GROUP_FORM_BC_LAYERS, MIN_CAP = 1;
+    static BgMember describe(const Bc* m) { return BgMember{bc_shape(m), m->device, m->prof ? 1 : 0, m->grad_comm ? 1 : 0, m}; }
+    static int refusal(const BgMember* m, unsigned n, const char** why, int* kernel) { return bg_group_refusal(m, n, why, kernel); }
+    static const char* kernel_name(int k) { return bg_kernel_name(k); }
+    static int round_plan(const BgShape& s, unsigned P, BgLaunch* out) { return bg_round_plan(s, P, out); }
+    static int launch_count(const BgShape& s) { return bg_launch_count(s.n_layers, s.form); }
+    // Bc::opt / Bc::update on the host
+    static BcStep fill_step(Bc* m, int bs, const GatherArgs& plan)
     {
-        return teams == 2 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bc_act_group<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX)
-                          : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bc_act_group<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX);
+        m->step += 1;
+        const AdamScalars sc = DenseAgent::opt_scalars(m->cfg.opt, m->cfg.lr, m->step);
+        m->n_opts += 1;
+        m->last_B = bs;
+        return BcStep{plan.word_pos, plan.size, sc};
     }
-    void launch(int teams, dim3 grid, size_t lds, hipStream_t stream, const BDR_CONST_AS DenseActArgs* args, const BDR_CONST_AS BcActCall* calls,
-                const BDR_CONST_AS unsigned* sel, unsigned* ticket, unsigned* seq_host, unsigned seq) const
+    static void member_static(Bc* m, int bs, const bdr_replay* r, const GatherArgs& plan, BcMemberArgs& o) { bc_member_static(m, bs, r, plan, o); }
+
+    int L = 0, nfwd = 0, ndx = 0, head = 0;
+    StagedArray<GatherArgs> gather; StagedArray<PackRowsArgs> pack; StagedArray<BcLossArgs> loss; StagedArray<BcHeadArgs> hd;
+    StagedArray<DenseDwSmallGroup> dw; StagedArray<ReduceAdamArgs> ra;
+    StagedArray<DenseArgs> dense;   // [nfwd][P] then [ndx][P] (launch order)
+    hipError_t allocate(const BgShape& s, size_t P)
     {
-        if (teams == 2) hipLaunchKernelGGL(k_bc_act_group<2>, grid, dim3(512), lds, stream, args, calls, sel, ticket, seq_host, seq);
-        else hipLaunchKernelGGL(k_bc_act_group<1>, grid, dim3(256), lds, stream, args, calls, sel, ticket, seq_host, seq);
+        L = s.n_layers;
+        head = s.form == BG_FORM_FUSED_MFMA ? 1 : 0;
+        nfwd = head ? L - 1 : L;
+        ndx = head ? L - 2 : L - 1;
+        hipError_t e = staged_resize(P, gather, pack);   // (in this order: where the arrays lie in device memory shows in the round time, LAB.md)
+        if (e == hipSuccess) e = dense.resize((size_t)(nfwd + ndx) * P);
+        return e == hipSuccess ? staged_resize(P, loss, hd, dw, ra) : e;
+    }
+    // member p's arguments into the staging arrays
+    void stage(size_t p, size_t P, const BcMemberArgs& o)
+    {
+        gather[p] = o.gather; pack[p] = o.pack; loss[p] = o.loss; hd[p] = o.head; dw[p] = o.dw; ra[p] = o.ra;
+        for (int i = 0; i < nfwd; ++i) dense[(size_t)i * P + p] = o.fwd[i];
+        for (int j = 0; j < ndx; ++j) dense[(size_t)(nfwd + j) * P + p] = o.dx[(head ? L - 2 : L - 1) - j];   // j-th dX launch of the round
+    }
+    hipError_t upload() { return staged_upload(gather, pack, dense, loss, hd, dw, ra); }
+    int32_t check_static(const BgLaunch* plan, int n, const BcMemberArgs& o, uint32_t p) const
+    {
+        BDR_REQUIRE(o.dw_grid == (int)plan[n - 2].gx, "member %u: the weight-gradient grid (%d) differs from the plan's (%u)", p, o.dw_grid, plan[n - 2].gx);
+        return BDR_OK;
+    }
+    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
+    int32_t launch(const GroupCore<BcGroupKind>& g, size_t P, const BcStep* steps_dev, unsigned seq_no) const
+    {
+        int fwd = 0, dx = 0;
+        for (int n = 0; n < g.n_launches; ++n) {
+            const BgLaunch& l = g.plan[n];
+            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
+            switch (l.kernel) {
+            case BG_K_GATHER:
+                BDR_TRY(replay_gather_group(g.stream, gather.d.get(), steps_dev, (uint32_t)sizeof(BcStep), (uint32_t)P, (uint64_t)g.shape.batch, (uint64_t)g.shape.obs_dim * 4));
+                break;
+            case BG_K_PACK: hipLaunchKernelGGL(k_pack_rows_group, grid, block, 0, g.stream, (const BDR_CONST_AS PackRowsArgs*)pack.d.get()); break;
+            case BG_K_FWD:
+                hipLaunchKernelGGL(k_bc_dense_small_group<false>, grid, block, 0, g.stream, (const BDR_CONST_AS DenseArgs*)(dense.d.get() + (size_t)fwd++ * P));
+                break;
+            case BG_K_LOSS: hipLaunchKernelGGL(k_bc_loss_group, grid, block, 0, g.stream, (const BDR_CONST_AS BcLossArgs*)loss.d.get()); break;
+            case BG_K_HEAD:
+                if (g.shape.act_dim <= 32) hipLaunchKernelGGL(k_bc_head_mfma_group<1>, grid, block, 0, g.stream, (const BDR_CONST_AS BcHeadArgs*)hd.d.get());
+                else hipLaunchKernelGGL(k_bc_head_mfma_group<2>, grid, block, 0, g.stream, (const BDR_CONST_AS BcHeadArgs*)hd.d.get());
+                break;
+            case BG_K_DX:
+                hipLaunchKernelGGL(k_bc_dense_small_group<true>, grid, block, 0, g.stream, (const BDR_CONST_AS DenseArgs*)(dense.d.get() + (size_t)(nfwd + dx++) * P));
+                break;
+            case BG_K_DW: hipLaunchKernelGGL(k_bc_dense_dw_small_group, grid, block, 0, g.stream, (const BDR_CONST_AS DenseDwSmallGroup*)dw.d.get()); break;
+            case BG_K_REDUCE_ADAM:
+                hipLaunchKernelGGL(k_bc_reduce_adam_group, grid, block, 0, g.stream, (const BDR_CONST_AS ReduceAdamArgs*)ra.d.get(), (const BDR_CONST_AS BcStep*)steps_dev,
+                                   g.ticket.get(), g.seq.dev, seq_no);
+                break;
+            default: return fail(BDR_ERR_INVALID, "BC group round: launch %d of the plan names no kernel", n);
+            }
+            BDR_HIP(hipGetLastError());
+        }
+        return BDR_OK;
     }
 };
-int32_t bc_group_sample(bdr_bc_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
-                        const int32_t* dtypes, float* const* act_out)
-{
-    return group_act_sample(g, BcActKind{}, members, n_sel, norms, n, rows, dtypes, act_out);
-}
 
 }  // namespace
 
+struct bdr_bc_group : GroupCore<BcGroupKind> {};
+
 namespace bdr {
-// the action width of a member, for the BC group evaluator's check of act_row_bytes (trainer.hip); 0: no such member
-int bc_group_act_dim(const void* group, uint32_t member)
-{
-    const auto* g = static_cast<const bdr_bc_group*>(group);
-    return g && member < g->members.size() ? g->members[member]->A : 0;
-}
+int bc_group_act_dim(const void* group, uint32_t member) { return group_act_dim<bdr_bc_group>(group, member); }   // (trainer.hip)
 }  // namespace bdr
 
 extern "C" {
 
-int32_t bdr_bc_group_create(bdr_agent* const* agents, uint32_t n, bdr_bc_group** out)
-{
-    BDR_REQUIRE(agents && out, "null argument");
-    BDR_REQUIRE(n >= 1 && n <= BG_MAX_MEMBERS, "a group has 1 .. 65535 members");
-    std::vector<Bc*> ms;
-    std::vector<BgMember> desc;
-    for (uint32_t p = 0; p < n; ++p) {
-        BDR_REQUIRE(agents[p], "member %u: null agent", p);
-        BDR_REQUIRE(!strcmp(agents[p]->kind(), "bc"), "member %u cannot join a BC group: not a BC agent (kind %s)", p, agents[p]->kind());
-        BDR_REQUIRE(!agents[p]->group, "member %u cannot join a BC group: already a member of a group", p);
-        Bc* m = static_cast<Bc*>(agents[p]);
-        ms.push_back(m);
-        desc.push_back(BgMember{bc_shape(m), m->device, m->prof ? 1 : 0, m->grad_comm ? 1 : 0, m});
-    }
-    const char* why = nullptr;
-    int kernel = -1;
-    const int who = bg_group_refusal(desc.data(), n, &why, &kernel);
-    if (who == BG_NO_MEMBER) return kernel >= 0 ? fail(BDR_ERR_INVALID, "%u members of this shape: %s (%s)", n, why, bg_kernel_name(kernel)) : fail(BDR_ERR_INVALID, "%s", why);
-    BDR_REQUIRE(who == BG_OK, "member %d cannot join a BC group: %s", who, why);
-    std::unique_ptr<bdr_bc_group> g(new bdr_bc_group());
-    g->device = ms[0]->device;
-    BDR_HIP(hipSetDevice(g->device));
-    g->shape = desc[0].shape;
-    g->n_launches = bg_round_plan(g->shape, n, g->plan);
-    BDR_REQUIRE(g->n_launches == bg_launch_count(g->shape.n_layers, g->shape.form), "the BC group launch plan is incomplete");
-    // (a failure below leaves nothing adopted: the partially built group releases what it holds)
-    BDR_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    BDR_HIP(g->allocate(n));
-    // adopt: the member's own stream is drained, retired and destroyed; the member enqueues on the group's stream from now on
-    for (Bc* m : ms) BDR_HIP(hipStreamSynchronize(m->stream));
-    for (Bc* m : ms) {
-        hipStream_t old = m->stream;
-        m->stream = g->stream; m->group = g.get();
-        if (old) { stream_retire(old); (void)hipStreamDestroy(old); }
-    }
-    g->members = std::move(ms);
-    *out = g.release();
-    return BDR_OK;
-}
-
-int32_t bdr_bc_group_destroy(bdr_bc_group* g)
-{
-    if (!g) return BDR_OK;
-    (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->stream);
-    for (Bc* m : g->members) {   // the group owns its members; their stream is the group's, destroyed once below
-        m->group = nullptr; m->stream = nullptr;
-        (void)bdr_agent_destroy(m);
-    }
-    delete g;   // retires and destroys the stream, then releases the buffers
-    return BDR_OK;
-}
-
-int32_t bdr_bc_group_size(const bdr_bc_group* g, uint32_t* n)
-{
-    BDR_REQUIRE(g && n, "null argument");
-    *n = (uint32_t)g->members.size();
-    return BDR_OK;
-}
-
-int32_t bdr_bc_group_member(const bdr_bc_group* g, uint32_t i, bdr_agent** out)
-{
-    BDR_REQUIRE(g && out, "null argument");
-    BDR_REQUIRE(i < g->members.size(), "member %u of a group of %u", i, (unsigned)g->members.size());
-    *out = g->members[i];
-    return BDR_OK;
-}
-
-int32_t bdr_bc_group_info(const bdr_bc_group* g, bdr_group_info* out)
-{
-    BDR_REQUIRE(g && out, "null argument");
-    memset(out, 0, sizeof *out);
-    out->form = BDR_GROUP_FORM_BC_LAYERS;
-    out->n_members = (uint32_t)g->members.size();
-    out->launches_per_round = (uint32_t)g->n_launches;
-    out->kernel_launches = g->kernel_launches;
-    return BDR_OK;
-}
-
-int32_t bdr_bc_group_opt(bdr_bc_group* g, bdr_replay* const* buffers)
-{
-    BDR_REQUIRE(g && buffers, "null argument");
-    return bc_group_opt(g, buffers);
-}
-
+int32_t bdr_bc_group_create(bdr_agent* const* agents, uint32_t n, bdr_bc_group** out) { return group_create(agents, n, out); }
+int32_t bdr_bc_group_destroy(bdr_bc_group* g) { return group_destroy(g); }
+int32_t bdr_bc_group_size(const bdr_bc_group* g, uint32_t* n) { return group_size(g, n); }
+int32_t bdr_bc_group_member(const bdr_bc_group* g, uint32_t i, bdr_agent** out) { return group_member(g, i, out); }
+int32_t bdr_bc_group_info(const bdr_bc_group* g, bdr_group_info* out) { return group_info(g, out); }
+int32_t bdr_bc_group_opt(bdr_bc_group* g, bdr_replay* const* buffers) { return group_opt(g, buffers); }
 int32_t bdr_bc_group_opt_with_scalars(bdr_bc_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out)
 {
-    BDR_REQUIRE(g && buffers && out && n_out, "null argument");
-    BDR_REQUIRE(cap_per_member >= 1, "cap_per_member must be positive");
-    BDR_TRY(bc_group_opt(g, buffers));
-    BDR_HIP(hipStreamSynchronize(g->stream));   // the one synchronisation: every record() below finds the stream idle
-    const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {
-        Bc* m = g->members[p];
-        int n = 0;
-        m->rec_opt = true;
-        const int32_t st = m->record(out + (size_t)p * cap_per_member, cap_per_member, &n);
-        m->rec_opt = false;
-        BDR_TRY(st);
-        n_out[p] = n;
-    }
-    for (uint32_t p = 0; p < P; ++p) {   // the records are complete whatever the error words say about the step that produced them
-        const int32_t st = g->members[p]->err_check();
-        if (st != BDR_OK) { if (bdr::g_err_deferred) bdr::g_err_deferred = 2; return st; }
-    }
-    return BDR_OK;
+    return group_opt_with_scalars(g, buffers, out, cap_per_member, n_out);
 }
-
 int32_t bdr_bc_group_sample(bdr_bc_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out)
 {
-    BDR_REQUIRE(g && rows && dtypes && act_out, "null argument");
-    return bc_group_sample(g, nullptr, (uint32_t)g->members.size(), norms, n, rows, dtypes, act_out);
+    return group_sample(g, norms, n, rows, dtypes, act_out);
 }
-
 int32_t bdr_bc_group_sample_members(bdr_bc_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n,
                                     const void* const* rows, const int32_t* dtypes, float* const* act_out)
 {
-    BDR_REQUIRE(g && members && rows && dtypes && act_out, "null argument");
-    return bc_group_sample(g, members, n_sel, norms, n, rows, dtypes, act_out);
+    return group_sample_members(g, members, n_sel, norms, n, rows, dtypes, act_out);
 }
-
-int32_t bdr_bc_group_sync(bdr_bc_group* g)
-{
-    BDR_REQUIRE(g, "null group");
-    BDR_HIP(hipSetDevice(g->device));
-    BDR_HIP(hipStreamSynchronize(g->stream));
-    for (Bc* m : g->members) {
-        BDR_TRY(m->after_sync());
-        BDR_TRY(m->err_check());
-    }
-    return BDR_OK;
-}
+int32_t bdr_bc_group_sync(bdr_bc_group* g) { return group_sync(g); }
 
 }  // extern "C"

@@ -8,12 +8,14 @@
 #pragma once
 #include <cstdint>
 
+#include "group_plan_common.hpp"
+
 namespace bdr {
 
 constexpr int BG_SHAPE_LAYERS = 16;
 constexpr int BG_DW_GROUP = 16;     // jobs of one grouped weight-gradient launch (dense.hpp DW_GROUP)
 constexpr int BG_RA_SEGS = 12;      // segments of k_dense_reduce_adam (dense.hpp RA_SEGS)
-constexpr unsigned BG_MAX_MEMBERS = 65535;   // the member index is grid dimension y
+constexpr unsigned BG_MAX_MEMBERS = GP_MAX_MEMBERS;
 // the kernel forms and action types of include/border_amd.h (bc_group.hpp checks that they are the same numbers)
 enum BgForm { BG_FORM_DEFAULT = 0, BG_FORM_GENERAL = 1, BG_FORM_FUSED = 2, BG_FORM_FUSED_MFMA = 3 };
 enum BgAction { BG_ACTION_DISCRETE = 0, BG_ACTION_CONTINUOUS = 1 };
@@ -75,15 +77,9 @@ constexpr int BG_MAX_LAUNCHES = 2 * BG_SHAPE_LAYERS + 4;
 
 // launches of one round, whatever P is: 2L + 4 (general), 2L + 2 (MFMA head)
 inline int bg_launch_count(int n_layers, int form) { return form == BG_FORM_GENERAL ? 2 * n_layers + 4 : 2 * n_layers + 2; }
-// row chunks of the grouped weight gradient (DenseAgent::chunks_for): 256 batch rows per workgroup, at most 16
-inline int bg_dw_chunks(int batch) { const int c = batch / 256; return c < 1 ? 1 : (c > 16 ? 16 : c); }
-// workgroups per sampled row of the gather (replay_gather_shape)
-inline unsigned bg_gather_chunks(uint64_t obs_bytes)
-{
-    const uint64_t nvec = obs_bytes % 16 == 0 ? obs_bytes / 16 : obs_bytes / 4;
-    const uint64_t c = (nvec + 1023) / 1024;
-    return (unsigned)(c < 1 ? 1 : c);
-}
+// (the rules every plan shares: group_plan_common.hpp)
+inline int bg_dw_chunks(int batch) { return gp_dw_chunks(batch); }
+inline unsigned bg_gather_chunks(uint64_t obs_bytes) { return gp_gather_chunks(obs_bytes); }
 inline uint64_t bg_arena_floats(const BgShape& s)
 {
     uint64_t total = 0;
@@ -112,41 +108,20 @@ inline int bg_round_plan(const BgShape& s, unsigned P, BgLaunch* out)
     return n;
 }
 
-// hardware limits of a launch: 2^31 - 1 workgroups along x, 65535 along y and z, and (HIP) fewer than 2^32 threads in all
-inline bool bg_grid_ok(const BgLaunch& l)
-{
-    if (l.gx < 1 || l.gy < 1 || l.gz < 1 || l.gx > 0x7fffffffu || l.gy > 65535u || l.gz > 65535u) return false;
-    return (uint64_t)l.gx * l.gy * l.gz * l.threads < (1ull << 32);
-}
+inline bool bg_grid_ok(const BgLaunch& l) { return gp_grid_ok(l); }
 
 // May these n agents form a group?  BG_OK: yes.  Otherwise *why says so; the return value is the first member the reason names,
 // or BG_NO_MEMBER where it concerns the group as a whole (its size, a launch beyond the limits: *kernel names that launch).
-constexpr int BG_OK = -1, BG_NO_MEMBER = -2;
+constexpr int BG_OK = GP_OK, BG_NO_MEMBER = GP_NO_MEMBER;
 inline int bg_group_refusal(const BgMember* m, unsigned n, const char** why, int* kernel = nullptr)
 {
-    if (kernel) *kernel = -1;
-    if (n < 1 || n > BG_MAX_MEMBERS) { *why = "a group has 1 .. 65535 members"; return BG_NO_MEMBER; }
-    for (unsigned p = 0; p < n; ++p) {
-        if (const char* w = bg_shape_ineligible(m[p].shape)) { *why = w; return (int)p; }
-        if (!bg_same_shape(m[p].shape, m[0].shape)) {
-            *why = "its shape (obs_dim, units, act_dim, activation_out, batch_size, resolved kernel form) differs from member 0's: one shape per group";
-            return (int)p;
-        }
-        if (m[p].prof) { *why = "profiling is on"; return (int)p; }
-        if (m[p].grad_comm) { *why = "a gradient communicator is installed"; return (int)p; }
-        if (m[p].device != m[0].device) { *why = "it lives on another device than member 0"; return (int)p; }
-        for (unsigned o = 0; o < p; ++o)
-            if (m[o].agent == m[p].agent) { *why = "the same agent is an earlier member already"; return (int)p; }
-    }
-    BgLaunch plan[BG_MAX_LAUNCHES];
-    const int nl = bg_round_plan(m[0].shape, n, plan);
-    for (int i = 0; i < nl; ++i)
-        if (!bg_grid_ok(plan[i])) {
-            *why = "a launch of the round exceeds 2^31 - 1 / 65535 / 65535 workgroups or 2^32 threads";
-            if (kernel) *kernel = plan[i].kernel;
-            return BG_NO_MEMBER;
-        }
-    return BG_OK;
+    const auto own = [&](const BgMember& x) -> const char* {
+        if (const char* w = bg_shape_ineligible(x.shape)) return w;
+        if (!bg_same_shape(x.shape, m[0].shape))
+            return "its shape (obs_dim, units, act_dim, activation_out, batch_size, resolved kernel form) differs from member 0's: one shape per group";
+        return nullptr;
+    };
+    return gp_group_refusal<BgLaunch, BG_MAX_LAUNCHES>(m, n, why, kernel, own, [&](BgLaunch* out) { return bg_round_plan(m[0].shape, n, out); });
 }
 
 }  // namespace bdr

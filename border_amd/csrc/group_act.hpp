@@ -2,7 +2,7 @@
 // Group acting, the host half, once: Policy::sample of the selected members of a group on n host rows each in ONE launch of a group
 // entry over dense_act_body (k_bc_act_group, bc_group.hpp: BC; k_candle_act_group, candle_act_group.hpp: Gaussian actors).  The rule
 // without HIP in it - selection, the staged offsets, the cap, the draws - is group_act_plan.hpp's; this header adds the state and the
-// call.  A group (bdr_bc_group, bdr_iql_group) holds a GroupAct<Call> as `act` beside device, stream, members, shape (obs_dim,
+// call.  A group (group_core.hpp: bdr_bc_group, bdr_iql_group) holds a GroupAct<Call> as `act` beside device, stream, members, shape (obs_dim,
 // act_dim), ticket, seq, launches and kernel_launches, and hands group_act_sample a Kind that says what differs:
 //   Kind::Call                          the words of one member's call (BcActCall, CandleActCall: the common words by name)
 //   Kind::arena(m)                      the parameter arena the member acts with: the key of its static arguments
@@ -10,7 +10,8 @@
 //   Kind::noise(m, &train, &counter)    the member's mode and noise counter, for the draws rule of group_act_plan.hpp (BC: no stream)
 //   Kind::call_words(m, c, train, start, counter)   what the call struct holds beyond the common words (train, and the counter the
 //                                       call draws at) and the member's counter after the call; runs after every refusal, once per call
-//   Kind::set_lds_attr(teams), launch(teams, grid, lds, stream, args, calls, sel, ticket, seq_host, seq)
+//   Kind::set_lds_attr(teams), launch(teams, grid, lds, stream, args, calls, sel, ticket, seq_host, seq)   GroupActEntry's, over the
+//                                       one-team and the two-team instantiation of the kind's entry
 //   static per member   d_act, rewritten when the member's arena has moved (keys), behind a stream synchronise
 //   per call            calls / sel and the staged rows and results, ONE pinned, device-mapped area each - an acting call is
 //                       synchronous, so the areas are free again whenever the next call fills them; rows and results grow on demand
@@ -40,6 +41,23 @@ struct GroupAct {
     PinnedArray<Call> calls; PinnedArray<unsigned> sel;             // [P], [P]
     PinnedArray<uint8_t> rows; size_t rows_cap = 0;                 // bytes
     PinnedArray<float> res; size_t res_cap = 0;                     // floats
+};
+
+// the attribute and launch halves of a Kind: K1 / K2 are its entry with one team of 256 threads / two teams
+template <class C> using GroupActKernel = void (*)(const BDR_CONST_AS DenseActArgs*, const BDR_CONST_AS C*, const BDR_CONST_AS unsigned*, unsigned*, unsigned*, unsigned);
+template <class C, GroupActKernel<C> K1, GroupActKernel<C> K2>
+struct GroupActEntry {
+    using Call = C;
+    hipError_t set_lds_attr(int teams) const
+    {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(teams == 2 ? K2 : K1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX);
+    }
+    void launch(int teams, dim3 grid, size_t lds, hipStream_t stream, const BDR_CONST_AS DenseActArgs* args, const BDR_CONST_AS C* calls,
+                const BDR_CONST_AS unsigned* sel, unsigned* ticket, unsigned* seq_host, unsigned seq) const
+    {
+        if (teams == 2) hipLaunchKernelGGL(K2, grid, dim3(512), lds, stream, args, calls, sel, ticket, seq_host, seq);
+        else hipLaunchKernelGGL(K1, grid, dim3(256), lds, stream, args, calls, sel, ticket, seq_host, seq);
+    }
 };
 
 // Policy::sample of the selected members (members == nullptr: all of them) on n host rows each, ONE launch

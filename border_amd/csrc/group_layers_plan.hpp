@@ -7,6 +7,8 @@
 #pragma once
 #include <cstdint>
 
+#include "group_plan_common.hpp"
+
 namespace bdr {
 
 constexpr int GL_MAXL = 4;        // layers the acting kernel covers (mlp_fused.hpp MF_MAXL)
@@ -71,16 +73,9 @@ inline const char* gl_kernel_name(int k)
 struct GlLaunch { int kernel, layer; unsigned gx, gy, gz, threads; };   // layer: the layer a forward / dX launch serves, else -1
 constexpr int GL_MAX_LAUNCHES = 2 + GL_MAXL + 2 + GL_MAXL + 2;
 
-// row chunks of the grouped weight gradient (DqnMlp::ensure_batch / update_critic): 256 batch rows per workgroup, at most 16
-inline int gl_dw_chunks(int batch) { const int c = batch / 256; return c < 1 ? 1 : (c > 16 ? 16 : c); }
-
-// workgroups of one member's gather: replay_sample_on_stream's chunking of a row of obs_bytes
-inline unsigned gl_gather_chunks(uint64_t obs_bytes)
-{
-    const uint64_t nvec = obs_bytes % 16 == 0 ? obs_bytes / 16 : obs_bytes / 4;
-    const uint64_t c = (nvec + 1023) / 1024;
-    return (unsigned)(c < 1 ? 1 : c);
-}
+// (the rules every plan shares: group_plan_common.hpp)
+inline int gl_dw_chunks(int batch) { return gp_dw_chunks(batch); }
+inline unsigned gl_gather_chunks(uint64_t obs_bytes) { return gp_gather_chunks(obs_bytes); }
 
 // The launches of one update round of P members of shape `s` on uniform rings, in stream order; returns their number (0: a member of
 // that shape does not take the layer form).  The member index is grid y everywhere but in the two kernels that already use y or z:
@@ -111,11 +106,6 @@ inline int gl_round_plan(const GlShape& s, unsigned P, GlLaunch* out)
     return n;
 }
 
-// hardware limits of a launch: 2^31 - 1 workgroups along x, 65535 along y and z, and (HIP) fewer than 2^32 threads in all
-inline bool gl_grid_ok(const GlLaunch& l)
-{
-    if (l.gx < 1 || l.gy < 1 || l.gz < 1 || l.gx > 0x7fffffffu || l.gy > 65535u || l.gz > 65535u) return false;
-    return (uint64_t)l.gx * l.gy * l.gz * l.threads < (1ull << 32);
-}
+inline bool gl_grid_ok(const GlLaunch& l) { return gp_grid_ok(l); }
 
 }  // namespace bdr

@@ -10,35 +10,27 @@
 // place through the constant address space: member and instance come from blockIdx, so they are uniform and the entry's fields are
 // scalar loads, as they are from the kernel-argument segment of the standalone kernel.  Same bodies, same bits.  The three loss kernels
 // are one workgroup per member: candle::row_sum / row_max run inside that workgroup, in their block order, over the member's rows only.
-//   static arguments   one device array per kernel family, rewritten only when a member's batch buffers or its ring change (`keys`:
-//                      CandleAgent::batch_gen, the ring's uid and batch_gen), synchronously, behind a stream synchronise: rare
-//   per step           IqlStep[P] in a slot of the pinned, device-mapped step ring: the gather reads word_pos and size of the member's
-//                      entry (GatherStepWords at its start), the three reduce + Adam launches its three AdamScalars
-// The slot rule (slot_ring.hpp): the ACTOR's reduce + Adam is the LAST launch of a round that reads the slot, so it alone ends with the
-// ticket and publishes the round's launch number (bg_group_done - all workgroups of its three-dimensional grid counted, behind a
-// barrier every thread reaches: dense_reduce_adam_body returns early for threads past the arena, to the entry, not out of the kernel).
-// The host rewrites a slot only once the pinned word has reached the number recorded for it: no copy command, event or synchronise in
-// the steady loop.
+// The host half - the members' adoption, the static argument arrays and their keys, the step ring and its slot rule, the round, records,
+// sync - is group_core.hpp's, shared with the BC group; IqlGroupKind below says what is IQL's.  Per step a member has an IqlStep: the
+// gather reads word_pos and size (GatherStepWords at its start), the three reduce + Adam launches its three AdamScalars.  The ACTOR's
+// reduce + Adam is the LAST launch of a round that reads the slot, so it alone ends with the ticket and publishes the round's launch
+// number (bg_group_done - all workgroups of its three-dimensional grid counted, behind a barrier every thread reaches:
+// dense_reduce_adam_body returns early for threads past the arena, to the entry, not out of the kernel).
 // Bounds of every new index:
-//   member = blockIdx.y < gridDim.y = P = the length of d_gather, d_pack, d_vloss, d_closs, d_aloss and of a step slot;
+//   member = blockIdx.y < gridDim.y = P = the length of gather, pack, vloss, closs, aloss and of a step slot;
 //   z = blockIdx.z < gridDim.z = nz <= 4 = the instances of a DenseGroupEntry and of a ReduceAdamArgs (2 n_critics <= 4 is a condition
 //   of the group);
-//   the i-th forward / dX launch of the round (stream order) is handed d_dense + i * P and reads entry i * P + member, i < ndense =
+//   the i-th forward / dX launch of the round (stream order) is handed dense + i * P and reads entry i * P + member, i < ndense =
 //   ig_dense_launches: the array holds ndense * P entries; the weight-gradient and reduce + Adam launches of network n (value 0,
-//   critic 1, actor 2) are handed d_dw + n * P / d_ra + n * P: 3 P entries each; NET < 3 = the AdamScalars of an IqlStep;
+//   critic 1, actor 2) are handed dw + n * P / ra + n * P: 3 P entries each; NET < 3 = the AdamScalars of an IqlStep;
 //   inside a member every index is the body's own, with the bounds of the standalone kernel.
 // Acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp, which states the bounds of
 // its indices; included by this translation unit only) through group_act.hpp, the host half BC's group shares; IqlActKind below says
 // what is IQL's.
 #pragma once
-#include <atomic>
-#include <memory>
-
-#include "slot_ring.hpp"
-#include "device_arrays.hpp"
 #include "dense_group.hpp"
 #include "candle_act_group.hpp"
-#include "group_act.hpp"
+#include "group_core.hpp"
 #include "iql_group_plan.hpp"
 
 static_assert(IG_DW_GROUP == DW_GROUP && IG_RA_SEGS == RA_SEGS && IG_MAXZ == DG_MAXZ && IG_SHAPE_LAYERS >= BDR_MAX_UNITS + 1, "iql_group_plan.hpp restates these limits");
@@ -247,236 +239,13 @@ void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& pl
     }
 }
 
-}  // namespace
-
-struct bdr_iql_group {
-    enum { STEP_SLOTS = 8 };
-    int32_t device = 0;
-    hipStream_t stream = nullptr;
-    // (bdr_iql_group_destroy has synchronised the stream and destroyed the members; a failed create has adopted nobody.)  The stream
-    // goes first, the buffers - the members below - after it.
-    ~bdr_iql_group() { if (stream) { stream_retire(stream); (void)hipStreamDestroy(stream); } }
-    std::vector<Iql*> members;
-    IgShape shape{};                 // the one shape of all members
-    IgLaunch plan[IG_MAX_LAUNCHES]; int n_launches = 0;
-    int ndense = 0;                  // forward and dX launches of a round
-    uint64_t kernel_launches = 0;    // every kernel launch the group's own calls have enqueued (bdr_iql_group_info)
-    struct StaticKey { bool valid = false; uint64_t batch_gen = 0, r_uid = 0, r_batch_gen = 0; };
-    std::vector<StaticKey> keys;
-    std::vector<GatherArgs> h_gather; DeviceArray<GatherArgs> d_gather;
-    std::vector<IqlPackArgs> h_pack; DeviceArray<IqlPackArgs> d_pack;
-    std::vector<DenseGroupEntry> h_dense; DeviceArray<DenseGroupEntry> d_dense;   // [ndense][P] (launch order)
-    std::vector<IqlValueArgs> h_vloss; DeviceArray<IqlValueArgs> d_vloss;
-    std::vector<IqlCriticArgs> h_closs; DeviceArray<IqlCriticArgs> d_closs;
-    std::vector<IqlActorArgs> h_aloss; DeviceArray<IqlActorArgs> d_aloss;
-    std::vector<DenseDwSmallGroup> h_dw; DeviceArray<DenseDwSmallGroup> d_dw;     // [3][P] by IgNetId
-    std::vector<ReduceAdamArgs> h_ra; DeviceArray<ReduceAdamArgs> d_ra;           // [3][P] by IgNetId
-    PinnedArray<IqlStep> steps; SlotRing<STEP_SLOTS> step_ring;                   // [STEP_SLOTS][P]
-    PinnedArray<unsigned> seq;                                                    // pinned word: the launch number published last
-    DeviceArray<unsigned> ticket;
-    uint64_t launches = 0;                                                        // launch numbers given out so far (1-based)
-    std::vector<bdr_replay*> last_buffers;                                        // the buffers of the last accepted opt (distinctness checked once)
-    GroupAct<CandleActCall> act;                                                  // group acting (group_act.hpp): static arguments, call words, staging areas
-
-    hipError_t allocate(size_t P)
-    {
-        ndense = ig_dense_launches(shape.value.n_layers, shape.critic.n_layers, shape.actor.n_layers);
-        h_gather.resize(P); h_pack.resize(P); h_dense.resize((size_t)ndense * P); h_vloss.resize(P); h_closs.resize(P); h_aloss.resize(P);
-        h_dw.resize(3 * P); h_ra.resize(3 * P);
-        keys.resize(P);
-        hipError_t e = device_array(d_gather, P);
-        if (e == hipSuccess) e = device_array(d_pack, P);
-        if (e == hipSuccess) e = device_array(d_dense, h_dense.size());
-        if (e == hipSuccess) e = device_array(d_vloss, P);
-        if (e == hipSuccess) e = device_array(d_closs, P);
-        if (e == hipSuccess) e = device_array(d_aloss, P);
-        if (e == hipSuccess) e = device_array(d_dw, 3 * P);
-        if (e == hipSuccess) e = device_array(d_ra, 3 * P);
-        if (e == hipSuccess) e = device_array(ticket, 1);
-        if (e == hipSuccess) e = hipMemset(ticket.get(), 0, sizeof(unsigned));
-        if (e == hipSuccess) e = pinned_array(steps, (size_t)STEP_SLOTS * P);
-        if (e == hipSuccess) e = pinned_array(seq, 16);   // (one word, a cache line of its own)
-        return e;
-    }
-    // member p's arguments into the staging arrays
-    void stage(size_t p, size_t P, const IqlMemberArgs& o)
-    {
-        h_gather[p] = o.gather; h_pack[p] = o.pack; h_vloss[p] = o.vloss; h_closs[p] = o.closs; h_aloss[p] = o.aloss;
-        for (int i = 0; i < ndense; ++i) h_dense[(size_t)i * P + p] = o.dense[i];
-        for (int n = 0; n < 3; ++n) { h_dw[(size_t)n * P + p] = o.dw[n]; h_ra[(size_t)n * P + p] = o.ra[n]; }
-    }
-    hipError_t upload(size_t P)
-    {
-        hipError_t e = hipMemcpy(d_gather.get(), h_gather.data(), P * sizeof(GatherArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_pack.get(), h_pack.data(), P * sizeof(IqlPackArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_dense.get(), h_dense.data(), h_dense.size() * sizeof(DenseGroupEntry), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_vloss.get(), h_vloss.data(), P * sizeof(IqlValueArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_closs.get(), h_closs.data(), P * sizeof(IqlCriticArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_aloss.get(), h_aloss.data(), P * sizeof(IqlActorArgs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_dw.get(), h_dw.data(), 3 * P * sizeof(DenseDwSmallGroup), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_ra.get(), h_ra.data(), 3 * P * sizeof(ReduceAdamArgs), hipMemcpyHostToDevice);
-        return e;
-    }
-    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
-    int32_t launch(size_t P, const IqlStep* steps_dev, unsigned seq_no)
-    {
-        int dense = 0;
-        for (int n = 0; n < n_launches; ++n) {
-            const IgLaunch& l = plan[n];
-            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
-            const auto* st = (const BDR_CONST_AS IqlStep*)steps_dev;
-            switch (l.kernel) {
-            case IG_K_GATHER:
-                BDR_TRY(replay_gather_group(stream, d_gather.get(), steps_dev, (uint32_t)sizeof(IqlStep), (uint32_t)P, (uint64_t)shape.batch, (uint64_t)shape.obs_dim * 4));
-                break;
-            case IG_K_PACK: hipLaunchKernelGGL(k_iql_pack_group, grid, block, 0, stream, (const BDR_CONST_AS IqlPackArgs*)d_pack.get()); break;
-            case IG_K_FWD:
-                BDR_REQUIRE(dense < ndense, "IQL group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<false>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(d_dense.get() + (size_t)dense++ * P));
-                break;
-            case IG_K_DX:
-                BDR_REQUIRE(dense < ndense, "IQL group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<true>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(d_dense.get() + (size_t)dense++ * P));
-                break;
-            case IG_K_VALUE_LOSS: hipLaunchKernelGGL(k_iql_value_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlValueArgs*)d_vloss.get()); break;
-            case IG_K_CRITIC_LOSS: hipLaunchKernelGGL(k_iql_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlCriticArgs*)d_closs.get()); break;
-            case IG_K_ACTOR_LOSS: hipLaunchKernelGGL(k_iql_actor_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlActorArgs*)d_aloss.get()); break;
-            case IG_K_DW:
-                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
-                hipLaunchKernelGGL(k_dense_dw_small_members, grid, block, 0, stream, (const BDR_CONST_AS DenseDwSmallGroup*)(d_dw.get() + (size_t)l.net * P));
-                break;
-            case IG_K_REDUCE_ADAM: {
-                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
-                const auto* ra = (const BDR_CONST_AS ReduceAdamArgs*)(d_ra.get() + (size_t)l.net * P);
-                if (l.net == IG_NET_VALUE) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_VALUE>, grid, block, 0, stream, ra, st, ticket.get(), seq.dev, seq_no);
-                else if (l.net == IG_NET_CRITIC) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_CRITIC>, grid, block, 0, stream, ra, st, ticket.get(), seq.dev, seq_no);
-                else hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_ACTOR>, grid, block, 0, stream, ra, st, ticket.get(), seq.dev, seq_no);
-                break;
-            }
-            default: return fail(BDR_ERR_INVALID, "IQL group round: launch %d of the plan names no kernel", n);
-            }
-            BDR_HIP(hipGetLastError());
-        }
-        return BDR_OK;
-    }
-};
-
-namespace {
-
-// every refusal of a grouped opt, before anything moves: CandleAgent::opt's checks (check_replay), and what the grouped gather covers
-int32_t iql_group_check_buffers(bdr_iql_group* g, bdr_replay* const* buffers)
-{
-    const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {
-        const Iql* m = g->members[p];
-        const bdr_replay* r = buffers[p];
-        BDR_REQUIRE(r, "member %u: null buffer", p);
-        BDR_REQUIRE(!m->prof && !m->grad_comm, "member %u: profiling or a gradient communicator was switched on after the group was created", p);
-        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == (uint64_t)m->A * 4, "member %u: replay rows do not match IQL obs/act dims (f32 rows)", p);
-        BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
-        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot be stepped by an IQL group (the grouped gather covers the uniform ring)", p);
-        BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by an IQL group", p);
-        BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: the grouped gather draws the StdRng index stream only", p);
-        if (r->size == 0) return fail(BDR_ERR_EMPTY, "member %u: batch() on an empty replay buffer", p);
-    }
-    if (g->last_buffers.size() == P && memcmp(g->last_buffers.data(), buffers, P * sizeof(bdr_replay*)) == 0) return BDR_OK;
-    std::vector<const bdr_replay*> s(buffers, buffers + P);   // workgroups run side by side: one bdr_replay (its batch arrays, its stream position) per member
-    std::sort(s.begin(), s.end());
-    const auto dup = std::adjacent_find(s.begin(), s.end());
-    if (dup != s.end()) {
-        uint32_t second = 0;
-        for (uint32_t p = 0, seen = 0; p < P; ++p) if (buffers[p] == *dup && seen++ == 1) { second = p; break; }
-        return fail(BDR_ERR_INVALID, "member %u: it shares its replay buffer with an earlier member: every member needs a bdr_replay of its own (a view of one ring will do)", second);
-    }
-    g->last_buffers.clear();
-    return BDR_OK;
-}
-
-// one update round: per member what CandleAgent::opt / Iql::update do on the host, in their order, then the round's launches, the last of
-// which publishes its number
-int32_t iql_group_round(bdr_iql_group* g, bdr_replay* const* buffers)
-{
-    const uint32_t P = (uint32_t)g->members.size();
-    const uint64_t k = g->launches + 1;
-    const auto slot = g->step_ring.next();
-    if (slot.wait) {   // the slot's last reader has published (bounded: wait_seq_word)
-        bool arrived = false;
-        BDR_TRY(wait_seq_word(g->seq.host.get(), (unsigned)slot.wait, g->stream, std::chrono::steady_clock::now(), &arrived));
-    }
-    IqlStep* steps = g->steps.host.get() + (size_t)slot.slot * P;
-    bool dirty = false;
-    IqlMemberArgs o;
-    for (uint32_t p = 0; p < P; ++p) {
-        Iql* m = g->members[p];
-        bdr_replay* r = buffers[p];
-        const int bs = (int)m->cfg.batch_size;
-        BDR_TRY(m->ensure_batch(bs));
-        GatherArgs plan{};
-        BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));   // the host half of replay_sample_on_stream; the rows are k_gather_group's
-        IqlStep st{};
-        st.word_pos = plan.word_pos; st.size = plan.size;
-        m->step_v += 1;
-        st.adam[IG_NET_VALUE] = DenseAgent::opt_scalars(m->cfg.opt_value, m->cfg.lr_value, m->step_v);
-        m->step_q += 1;
-        st.adam[IG_NET_CRITIC] = DenseAgent::opt_scalars(m->cfg.opt_critic, m->cfg.lr_critic, m->step_q);
-        m->step_pi += 1;
-        st.adam[IG_NET_ACTOR] = DenseAgent::opt_scalars(m->cfg.opt_actor, m->cfg.lr_actor, m->step_pi);
-        m->n_opts += 1;
-        m->last_B = bs;
-        bdr_iql_group::StaticKey& key = g->keys[p];
-        if (!key.valid || key.batch_gen != m->batch_gen || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
-            iql_member_static(m, bs, r, plan, o);
-            BDR_REQUIRE((int)o.dense.size() == g->ndense, "member %u: %d dense launches, the plan has %d", p, (int)o.dense.size(), g->ndense);
-            for (int n = 0; n < g->n_launches; ++n)
-                if (g->plan[n].kernel == IG_K_DW) {
-                    const int id = g->plan[n].net;
-                    BDR_REQUIRE(o.dw_grid[id] == (int)g->plan[n].gx, "member %u: the weight-gradient grid of network %d (%d) differs from the plan's (%u)", p, id,
-                                o.dw_grid[id], g->plan[n].gx);
-                }
-            g->stage(p, P, o);
-            key.valid = true; key.batch_gen = m->batch_gen; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
-            dirty = true;
-        }
-        steps[p] = st;
-    }
-    if (dirty) {   // rare (first step, a reallocation, another ring): behind everything the stream still holds
-        BDR_HIP(hipStreamSynchronize(g->stream));
-        BDR_HIP(g->upload(P));
-    }
-    std::atomic_thread_fence(std::memory_order_release);
-    // (should a launch fail, k is the number of whatever the group launches next - later than every reader of the slot)
-    g->launches = k; g->step_ring.record(k);
-    BDR_TRY(g->launch(P, g->steps.dev + (size_t)slot.slot * P, (unsigned)k));
-    g->kernel_launches += (uint64_t)g->n_launches;
-    return BDR_OK;
-}
-
-// what bdr_agent_opt does around opt(), for every member, then the round
-int32_t iql_group_opt(bdr_iql_group* g, bdr_replay* const* buffers)
-{
-    BDR_HIP(hipSetDevice(g->device));
-    BDR_TRY(iql_group_check_buffers(g, buffers));
-    const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {   // asynchronous: what an earlier synchronising call of the member read back surfaces here
-        Iql* m = g->members[p];
-        unsigned w[bdr_agent::ERR_WORDS];
-        m->err_mirror_read(w);
-        BDR_TRY(m->err_report(w));
-    }
-    for (uint32_t p = 0; p < P; ++p) g->members[p]->last_replay_uid = buffers[p]->uid;
-    BDR_TRY(iql_group_round(g, buffers));
-    g->last_buffers.assign(buffers, buffers + P);
-    return BDR_OK;
-}
-
 // ---- group acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp) -----------------
 // group_act.hpp's call with what is IQL's.  Static, keyed on the actor arena: the actor net pn on pi_p, DA_CANDLE, and the static half of
 // CandleAgent::sample_elem from the member's config (IQL has no Mlp2 actor: mlp2 = 0).  Per call: the member's mode, read now
 // (bdr_agent_set_train), and in train mode its noise counter, which advances by the n * A draws the call takes - sample_elem's rule, so
 // group calls, the member's own sample / sample_raw on either act path and bdr_agent_noise continue one stream in any interleaving.  The
 // call does not go through ensure_batch and does not touch a member's samp: results go to the group's pinned area.
-struct IqlActKind {
-    using Call = CandleActCall;
+struct IqlActKind : GroupActEntry<CandleActCall, k_candle_act_group<1>, k_candle_act_group<2>> {
     const float* arena(const Iql* m) const { return m->pi_p; }
     void write_static(const Iql* m, DenseActArgs& a) const
     {
@@ -496,174 +265,141 @@ struct IqlActKind {
         c.train = train; c.counter = train ? start : 0;
         m->noise_counter = counter;
     }
-    hipError_t set_lds_attr(int teams) const
+};
+
+// ---- what is IQL's of the group core (group_core.hpp) ----------------------------------------------------------------------------------
+struct IqlGroupKind {
+    using Member = Iql; using Shape = IgShape; using Launch = IgLaunch; using Step = IqlStep; using MemberArgs = IqlMemberArgs; using PlanMember = IgMember;
+    using Act = IqlActKind;
+    static constexpr const char *KIND = "iql", *A = "an IQL", *NAME = "IQL", *CAP_MSG = "cap_per_member must hold the three keys of an IQL record";
+    static constexpr int MAX_LAUNCHES = IG_MAX_LAUNCHES, K_GATHER = IG_K_GATHER, FORM = BDR_GROUP_FORM_IQL_LAYERS, MIN_CAP = Iql::N_RECORD;
+    static IgMember describe(const Iql* m) { return IgMember{iql_shape(m), 1, m->cfg.n_updates_per_opt, m->device, m->prof ? 1 : 0, m->grad_comm ? 1 : 0, m}; }
+    static int refusal(const IgMember* m, unsigned n, const char** why, int* kernel) { return ig_group_refusal(m, n, why, kernel); }
+    static const char* kernel_name(int k) { return ig_kernel_name(k); }
+    static int round_plan(const IgShape& s, unsigned P, IgLaunch* out) { return ig_round_plan(s, P, out); }
+    static int launch_count(const IgShape& s) { return ig_launch_count(s.value.n_layers, s.critic.n_layers, s.actor.n_layers); }
+    // CandleAgent::opt / Iql::update on the host, in their order
+    static IqlStep fill_step(Iql* m, int bs, const GatherArgs& plan)
     {
-        return teams == 2 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_candle_act_group<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX)
-                          : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_candle_act_group<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX);
+        IqlStep st{};
+        st.word_pos = plan.word_pos; st.size = plan.size;
+        m->step_v += 1;
+        st.adam[IG_NET_VALUE] = DenseAgent::opt_scalars(m->cfg.opt_value, m->cfg.lr_value, m->step_v);
+        m->step_q += 1;
+        st.adam[IG_NET_CRITIC] = DenseAgent::opt_scalars(m->cfg.opt_critic, m->cfg.lr_critic, m->step_q);
+        m->step_pi += 1;
+        st.adam[IG_NET_ACTOR] = DenseAgent::opt_scalars(m->cfg.opt_actor, m->cfg.lr_actor, m->step_pi);
+        m->n_opts += 1;
+        m->last_B = bs;
+        return st;
     }
-    void launch(int teams, dim3 grid, size_t lds, hipStream_t stream, const BDR_CONST_AS DenseActArgs* args, const BDR_CONST_AS CandleActCall* calls,
-                const BDR_CONST_AS unsigned* sel, unsigned* ticket, unsigned* seq_host, unsigned seq) const
+    static void member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& plan, IqlMemberArgs& o) { iql_member_static(m, bs, r, plan, o); }
+
+    int ndense = 0;   // forward and dX launches of a round
+    StagedArray<GatherArgs> gather; StagedArray<IqlPackArgs> pack; StagedArray<IqlValueArgs> vloss; StagedArray<IqlCriticArgs> closs; StagedArray<IqlActorArgs> aloss;
+    StagedArray<DenseGroupEntry> dense;                                   // [ndense][P] (launch order)
+    StagedArray<DenseDwSmallGroup> dw; StagedArray<ReduceAdamArgs> ra;   // [3][P] by IgNetId
+    hipError_t allocate(const IgShape& s, size_t P)
     {
-        if (teams == 2) hipLaunchKernelGGL(k_candle_act_group<2>, grid, dim3(512), lds, stream, args, calls, sel, ticket, seq_host, seq);
-        else hipLaunchKernelGGL(k_candle_act_group<1>, grid, dim3(256), lds, stream, args, calls, sel, ticket, seq_host, seq);
+        ndense = ig_dense_launches(s.value.n_layers, s.critic.n_layers, s.actor.n_layers);
+        hipError_t e = staged_resize(P, gather, pack);   // (in this order: where the arrays lie in device memory shows in the round time, LAB.md)
+        if (e == hipSuccess) e = dense.resize((size_t)ndense * P);
+        if (e == hipSuccess) e = staged_resize(P, vloss, closs, aloss);
+        return e == hipSuccess ? staged_resize(3 * P, dw, ra) : e;
+    }
+    // member p's arguments into the staging arrays
+    void stage(size_t p, size_t P, const IqlMemberArgs& o)
+    {
+        gather[p] = o.gather; pack[p] = o.pack; vloss[p] = o.vloss; closs[p] = o.closs; aloss[p] = o.aloss;
+        for (int i = 0; i < ndense; ++i) dense[(size_t)i * P + p] = o.dense[i];
+        for (int n = 0; n < 3; ++n) { dw[(size_t)n * P + p] = o.dw[n]; ra[(size_t)n * P + p] = o.ra[n]; }
+    }
+    hipError_t upload() { return staged_upload(gather, pack, dense, vloss, closs, aloss, dw, ra); }
+    int32_t check_static(const IgLaunch* plan, int n_launches, const IqlMemberArgs& o, uint32_t p) const
+    {
+        BDR_REQUIRE((int)o.dense.size() == ndense, "member %u: %d dense launches, the plan has %d", p, (int)o.dense.size(), ndense);
+        for (int n = 0; n < n_launches; ++n)
+            if (plan[n].kernel == IG_K_DW) {
+                const int id = plan[n].net;
+                BDR_REQUIRE(o.dw_grid[id] == (int)plan[n].gx, "member %u: the weight-gradient grid of network %d (%d) differs from the plan's (%u)", p, id, o.dw_grid[id],
+                            plan[n].gx);
+            }
+        return BDR_OK;
+    }
+    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
+    int32_t launch(const GroupCore<IqlGroupKind>& g, size_t P, const IqlStep* steps_dev, unsigned seq_no) const
+    {
+        int nd = 0;
+        hipStream_t stream = g.stream;
+        for (int n = 0; n < g.n_launches; ++n) {
+            const IgLaunch& l = g.plan[n];
+            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
+            const auto* st = (const BDR_CONST_AS IqlStep*)steps_dev;
+            switch (l.kernel) {
+            case IG_K_GATHER:
+                BDR_TRY(replay_gather_group(stream, gather.d.get(), steps_dev, (uint32_t)sizeof(IqlStep), (uint32_t)P, (uint64_t)g.shape.batch, (uint64_t)g.shape.obs_dim * 4));
+                break;
+            case IG_K_PACK: hipLaunchKernelGGL(k_iql_pack_group, grid, block, 0, stream, (const BDR_CONST_AS IqlPackArgs*)pack.d.get()); break;
+            case IG_K_FWD:
+                BDR_REQUIRE(nd < ndense, "IQL group round: more dense launches in the plan than argument entries");
+                hipLaunchKernelGGL(k_dense_small_members_z<false>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
+                break;
+            case IG_K_DX:
+                BDR_REQUIRE(nd < ndense, "IQL group round: more dense launches in the plan than argument entries");
+                hipLaunchKernelGGL(k_dense_small_members_z<true>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
+                break;
+            case IG_K_VALUE_LOSS: hipLaunchKernelGGL(k_iql_value_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlValueArgs*)vloss.d.get()); break;
+            case IG_K_CRITIC_LOSS: hipLaunchKernelGGL(k_iql_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlCriticArgs*)closs.d.get()); break;
+            case IG_K_ACTOR_LOSS: hipLaunchKernelGGL(k_iql_actor_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlActorArgs*)aloss.d.get()); break;
+            case IG_K_DW:
+                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
+                hipLaunchKernelGGL(k_dense_dw_small_members, grid, block, 0, stream, (const BDR_CONST_AS DenseDwSmallGroup*)(dw.d.get() + (size_t)l.net * P));
+                break;
+            case IG_K_REDUCE_ADAM: {
+                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
+                const auto* a = (const BDR_CONST_AS ReduceAdamArgs*)(ra.d.get() + (size_t)l.net * P);
+                if (l.net == IG_NET_VALUE) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_VALUE>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
+                else if (l.net == IG_NET_CRITIC) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_CRITIC>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
+                else hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_ACTOR>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
+                break;
+            }
+            default: return fail(BDR_ERR_INVALID, "IQL group round: launch %d of the plan names no kernel", n);
+            }
+            BDR_HIP(hipGetLastError());
+        }
+        return BDR_OK;
     }
 };
-int32_t iql_group_sample(bdr_iql_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
-                         const int32_t* dtypes, float* const* act_out)
-{
-    return group_act_sample(g, IqlActKind{}, members, n_sel, norms, n, rows, dtypes, act_out);
-}
 
 }  // namespace
 
+struct bdr_iql_group : GroupCore<IqlGroupKind> {};
+
 namespace bdr {
-// the action width of a member, for the group evaluator's check of act_row_bytes (trainer.hip); 0: no such member
-int iql_group_act_dim(const void* group, uint32_t member)
-{
-    const auto* g = static_cast<const bdr_iql_group*>(group);
-    return g && member < g->members.size() ? g->members[member]->A : 0;
-}
+int iql_group_act_dim(const void* group, uint32_t member) { return group_act_dim<bdr_iql_group>(group, member); }   // (trainer.hip)
 }  // namespace bdr
 
 extern "C" {
 
-int32_t bdr_iql_group_create(bdr_agent* const* agents, uint32_t n, bdr_iql_group** out)
-{
-    BDR_REQUIRE(agents && out, "null argument");
-    BDR_REQUIRE(n >= 1 && n <= IG_MAX_MEMBERS, "a group has 1 .. 65535 members");
-    std::vector<Iql*> ms;
-    std::vector<IgMember> desc;
-    for (uint32_t p = 0; p < n; ++p) {
-        BDR_REQUIRE(agents[p], "member %u: null agent", p);
-        BDR_REQUIRE(!strcmp(agents[p]->kind(), "iql"), "member %u cannot join an IQL group: not an IQL agent (kind %s)", p, agents[p]->kind());
-        BDR_REQUIRE(!agents[p]->group, "member %u cannot join an IQL group: already a member of a group", p);
-        Iql* m = static_cast<Iql*>(agents[p]);
-        ms.push_back(m);
-        desc.push_back(IgMember{iql_shape(m), 1, m->cfg.n_updates_per_opt, m->device, m->prof ? 1 : 0, m->grad_comm ? 1 : 0, m});
-    }
-    const char* why = nullptr;
-    int kernel = -1;
-    const int who = ig_group_refusal(desc.data(), n, &why, &kernel);
-    if (who == IG_NO_MEMBER) return kernel >= 0 ? fail(BDR_ERR_INVALID, "%u members of this shape: %s (%s)", n, why, ig_kernel_name(kernel)) : fail(BDR_ERR_INVALID, "%s", why);
-    BDR_REQUIRE(who == IG_OK, "member %d cannot join an IQL group: %s", who, why);
-    std::unique_ptr<bdr_iql_group> g(new bdr_iql_group());
-    g->device = ms[0]->device;
-    BDR_HIP(hipSetDevice(g->device));
-    g->shape = desc[0].shape;
-    g->n_launches = ig_round_plan(g->shape, n, g->plan);
-    BDR_REQUIRE(g->n_launches == ig_launch_count(g->shape.value.n_layers, g->shape.critic.n_layers, g->shape.actor.n_layers), "the IQL group launch plan is incomplete");
-    {   // the gather's grid is replay_gather_group's own: it must be the one the plan has checked against the limits
-        uint32_t chunks = 1, vec_per_chunk = 0;
-        replay_gather_shape((uint64_t)g->shape.obs_dim * 4, &chunks, &vec_per_chunk);
-        BDR_REQUIRE((unsigned)g->shape.batch * chunks == g->plan[0].gx && g->plan[0].kernel == IG_K_GATHER,
-                    "the gather's grid (%u workgroups per row) differs from the plan's (is BDR_GATHER_CHUNKS set?): no IQL group", chunks);
-    }
-    // (a failure below leaves nothing adopted: the partially built group releases what it holds)
-    BDR_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    BDR_HIP(g->allocate(n));
-    // adopt: the member's own stream is drained, retired and destroyed; the member enqueues on the group's stream from now on
-    for (Iql* m : ms) BDR_HIP(hipStreamSynchronize(m->stream));
-    for (Iql* m : ms) {
-        hipStream_t old = m->stream;
-        m->stream = g->stream; m->group = g.get();
-        if (old) { stream_retire(old); (void)hipStreamDestroy(old); }
-    }
-    g->members = std::move(ms);
-    *out = g.release();
-    return BDR_OK;
-}
-
-int32_t bdr_iql_group_destroy(bdr_iql_group* g)
-{
-    if (!g) return BDR_OK;
-    (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->stream);
-    for (Iql* m : g->members) {   // the group owns its members; their stream is the group's, destroyed once below
-        m->group = nullptr; m->stream = nullptr;
-        (void)bdr_agent_destroy(m);
-    }
-    delete g;   // retires and destroys the stream, then releases the buffers
-    return BDR_OK;
-}
-
-int32_t bdr_iql_group_size(const bdr_iql_group* g, uint32_t* n)
-{
-    BDR_REQUIRE(g && n, "null argument");
-    *n = (uint32_t)g->members.size();
-    return BDR_OK;
-}
-
-int32_t bdr_iql_group_member(const bdr_iql_group* g, uint32_t i, bdr_agent** out)
-{
-    BDR_REQUIRE(g && out, "null argument");
-    BDR_REQUIRE(i < g->members.size(), "member %u of a group of %u", i, (unsigned)g->members.size());
-    *out = g->members[i];
-    return BDR_OK;
-}
-
-int32_t bdr_iql_group_info(const bdr_iql_group* g, bdr_group_info* out)
-{
-    BDR_REQUIRE(g && out, "null argument");
-    memset(out, 0, sizeof *out);
-    out->form = BDR_GROUP_FORM_IQL_LAYERS;
-    out->n_members = (uint32_t)g->members.size();
-    out->launches_per_round = (uint32_t)g->n_launches;
-    out->kernel_launches = g->kernel_launches;
-    return BDR_OK;
-}
-
-int32_t bdr_iql_group_opt(bdr_iql_group* g, bdr_replay* const* buffers)
-{
-    BDR_REQUIRE(g && buffers, "null argument");
-    return iql_group_opt(g, buffers);
-}
-
+int32_t bdr_iql_group_create(bdr_agent* const* agents, uint32_t n, bdr_iql_group** out) { return group_create(agents, n, out); }
+int32_t bdr_iql_group_destroy(bdr_iql_group* g) { return group_destroy(g); }
+int32_t bdr_iql_group_size(const bdr_iql_group* g, uint32_t* n) { return group_size(g, n); }
+int32_t bdr_iql_group_member(const bdr_iql_group* g, uint32_t i, bdr_agent** out) { return group_member(g, i, out); }
+int32_t bdr_iql_group_info(const bdr_iql_group* g, bdr_group_info* out) { return group_info(g, out); }
+int32_t bdr_iql_group_opt(bdr_iql_group* g, bdr_replay* const* buffers) { return group_opt(g, buffers); }
 int32_t bdr_iql_group_opt_with_scalars(bdr_iql_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out)
 {
-    BDR_REQUIRE(g && buffers && out && n_out, "null argument");
-    BDR_REQUIRE(cap_per_member >= Iql::N_RECORD, "cap_per_member must hold the three keys of an IQL record");
-    BDR_TRY(iql_group_opt(g, buffers));
-    BDR_HIP(hipStreamSynchronize(g->stream));   // the one synchronisation: every record() below finds the stream idle
-    const uint32_t P = (uint32_t)g->members.size();
-    for (uint32_t p = 0; p < P; ++p) {
-        Iql* m = g->members[p];
-        int n = 0;
-        m->rec_opt = true;
-        const int32_t st = m->record(out + (size_t)p * cap_per_member, cap_per_member, &n);
-        m->rec_opt = false;
-        BDR_TRY(st);
-        n_out[p] = n;
-    }
-    for (uint32_t p = 0; p < P; ++p) {   // the records are complete whatever the error words say about the step that produced them
-        const int32_t st = g->members[p]->err_check();
-        if (st != BDR_OK) { if (bdr::g_err_deferred) bdr::g_err_deferred = 2; return st; }
-    }
-    return BDR_OK;
+    return group_opt_with_scalars(g, buffers, out, cap_per_member, n_out);
 }
-
 int32_t bdr_iql_group_sample(bdr_iql_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out)
 {
-    BDR_REQUIRE(g && rows && dtypes && act_out, "null argument");
-    return iql_group_sample(g, nullptr, (uint32_t)g->members.size(), norms, n, rows, dtypes, act_out);
+    return group_sample(g, norms, n, rows, dtypes, act_out);
 }
-
 int32_t bdr_iql_group_sample_members(bdr_iql_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n,
                                      const void* const* rows, const int32_t* dtypes, float* const* act_out)
 {
-    BDR_REQUIRE(g && members && rows && dtypes && act_out, "null argument");
-    return iql_group_sample(g, members, n_sel, norms, n, rows, dtypes, act_out);
+    return group_sample_members(g, members, n_sel, norms, n, rows, dtypes, act_out);
 }
-
-int32_t bdr_iql_group_sync(bdr_iql_group* g)
-{
-    BDR_REQUIRE(g, "null group");
-    BDR_HIP(hipSetDevice(g->device));
-    BDR_HIP(hipStreamSynchronize(g->stream));
-    for (Iql* m : g->members) {
-        BDR_TRY(m->after_sync());
-        BDR_TRY(m->err_check());
-    }
-    return BDR_OK;
-}
+int32_t bdr_iql_group_sync(bdr_iql_group* g) { return group_sync(g); }
 
 }  // extern "C"

@@ -8,10 +8,9 @@
 // actor's step - with the member index as grid dimension y of every launch and the network instance, where the standalone launch has
 // one, as grid dimension z.  With Lv, Lq, Lp the layer counts: 3 (Lq + Lv) + 2 Lp + 8 launches whatever P is.
 #pragma once
-#include <algorithm>
 #include <cstdint>
-#include <utility>
-#include <vector>
+
+#include "group_plan_common.hpp"
 
 namespace bdr {
 
@@ -19,7 +18,7 @@ constexpr int IG_SHAPE_LAYERS = 16;
 constexpr int IG_DW_GROUP = 16;     // jobs of one grouped weight-gradient launch (dense.hpp DW_GROUP)
 constexpr int IG_RA_SEGS = 12;      // segments of k_dense_reduce_adam (dense.hpp RA_SEGS)
 constexpr int IG_MAXZ = 4;          // instances of one dense launch (dense.hpp DenseArgsZ, RA_INST)
-constexpr unsigned IG_MAX_MEMBERS = 65535;   // the member index is grid dimension y
+constexpr unsigned IG_MAX_MEMBERS = GP_MAX_MEMBERS;
 
 // ---- what the rule reads of a member ------------------------------------------------------------------------------------------------
 // padded sizes (multiples of 64: make_mlp) and logical output width of every layer of one network, and whether its output has a ReLU
@@ -73,17 +72,9 @@ constexpr int IG_MAX_LAUNCHES = 8 * IG_SHAPE_LAYERS + 8;
 inline int ig_launch_count(int Lv, int Lq, int Lp) { return 3 * (Lq + Lv) + 2 * Lp + 8; }
 // forward and dX launches of one round: the entries of the dense argument array are (this) x P
 inline int ig_dense_launches(int Lv, int Lq, int Lp) { return 3 * (Lq + Lv) + 2 * Lp - 3; }
-// row chunks of the grouped weight gradient (DenseAgent::chunks_for): 256 batch rows per workgroup, at most 16
-inline int ig_dw_chunks(int batch) { const int c = batch / 256; return c < 1 ? 1 : (c > 16 ? 16 : c); }
-// workgroups per sampled row of the gather: replay_gather_shape's rule (replay.hip) without its diagnostics override BDR_GATHER_CHUNKS -
-// bdr_iql_group_create compares the two and refuses a group while the override makes them differ, so the grid replay_gather_group
-// launches is always the grid checked against the limits here
-inline unsigned ig_gather_chunks(uint64_t obs_bytes)
-{
-    const uint64_t nvec = obs_bytes % 16 == 0 ? obs_bytes / 16 : obs_bytes / 4;
-    const uint64_t c = (nvec + 1023) / 1024;
-    return (unsigned)(c < 1 ? 1 : c);
-}
+// (the rules every plan shares: group_plan_common.hpp)
+inline int ig_dw_chunks(int batch) { return gp_dw_chunks(batch); }
+inline unsigned ig_gather_chunks(uint64_t obs_bytes) { return gp_gather_chunks(obs_bytes); }
 inline uint64_t ig_arena_floats(const IgNet& n)
 {
     uint64_t total = 0;
@@ -136,54 +127,22 @@ inline int ig_round_plan(const IgShape& s, unsigned P, IgLaunch* out)
     return n;
 }
 
-// hardware limits of a launch: 2^31 - 1 workgroups along x, 65535 along y and z, and (HIP) fewer than 2^32 threads in all
-inline bool ig_grid_ok(const IgLaunch& l)
-{
-    if (l.gx < 1 || l.gy < 1 || l.gz < 1 || l.gx > 0x7fffffffu || l.gy > 65535u || l.gz > 65535u) return false;
-    return (uint64_t)l.gx * l.gy * l.gz * l.threads < (1ull << 32);
-}
-
-// the first member that is the same agent as an earlier member (n: there is none); a sort, not n^2 / 2 comparisons at 65535 members
-inline unsigned ig_first_duplicate(const IgMember* m, unsigned n)
-{
-    std::vector<std::pair<const void*, unsigned>> v(n);
-    for (unsigned p = 0; p < n; ++p) v[p] = {m[p].agent, p};
-    std::sort(v.begin(), v.end());   // (equal agents in member order)
-    unsigned first = n;
-    for (unsigned i = 1; i < n; ++i) if (v[i].first == v[i - 1].first) first = std::min(first, v[i].second);
-    return first;
-}
+inline bool ig_grid_ok(const IgLaunch& l) { return gp_grid_ok(l); }
 
 // May these n agents form a group?  IG_OK: yes.  Otherwise *why says so; the return value is the first member the reason names,
 // or IG_NO_MEMBER where it concerns the group as a whole (its size, a launch beyond the limits: *kernel names that launch).
-constexpr int IG_OK = -1, IG_NO_MEMBER = -2;
+constexpr int IG_OK = GP_OK, IG_NO_MEMBER = GP_NO_MEMBER;
 inline int ig_group_refusal(const IgMember* m, unsigned n, const char** why, int* kernel = nullptr)
 {
-    if (kernel) *kernel = -1;
-    if (n < 1 || n > IG_MAX_MEMBERS) { *why = "a group has 1 .. 65535 members"; return IG_NO_MEMBER; }
-    const unsigned dup = ig_first_duplicate(m, n);
-    for (unsigned p = 0; p < n; ++p) {
-        if (!m[p].kind_iql) { *why = "not an IQL agent"; return (int)p; }
-        if (const char* w = ig_shape_ineligible(m[p].shape)) { *why = w; return (int)p; }
-        if (!ig_same_shape(m[p].shape, m[0].shape)) {
-            *why = "its shape (obs_dim, act_dim, the three networks' units and activation_out, n_critics, batch_size) differs from member 0's: one shape per group";
-            return (int)p;
-        }
-        if (m[p].n_updates != 1) { *why = "n_updates_per_opt != 1 is not built for a group"; return (int)p; }
-        if (m[p].prof) { *why = "profiling is on"; return (int)p; }
-        if (m[p].grad_comm) { *why = "a gradient communicator is installed"; return (int)p; }
-        if (m[p].device != m[0].device) { *why = "it lives on another device than member 0"; return (int)p; }
-        if (p == dup) { *why = "the same agent is an earlier member already"; return (int)p; }
-    }
-    IgLaunch plan[IG_MAX_LAUNCHES];
-    const int nl = ig_round_plan(m[0].shape, n, plan);
-    for (int i = 0; i < nl; ++i)
-        if (!ig_grid_ok(plan[i])) {
-            *why = "a launch of the round exceeds 2^31 - 1 / 65535 / 65535 workgroups or 2^32 threads";
-            if (kernel) *kernel = plan[i].kernel;
-            return IG_NO_MEMBER;
-        }
-    return IG_OK;
+    const auto own = [&](const IgMember& x) -> const char* {
+        if (!x.kind_iql) return "not an IQL agent";
+        if (const char* w = ig_shape_ineligible(x.shape)) return w;
+        if (!ig_same_shape(x.shape, m[0].shape))
+            return "its shape (obs_dim, act_dim, the three networks' units and activation_out, n_critics, batch_size) differs from member 0's: one shape per group";
+        if (x.n_updates != 1) return "n_updates_per_opt != 1 is not built for a group";
+        return nullptr;
+    };
+    return gp_group_refusal<IgLaunch, IG_MAX_LAUNCHES>(m, n, why, kernel, own, [&](IgLaunch* out) { return ig_round_plan(m[0].shape, n, out); });
 }
 
 }  // namespace bdr

@@ -25,8 +25,8 @@
 using namespace bdr;
 
 namespace bdr {
-int bc_group_act_dim(const void* group, uint32_t member);    // bc.hip (bc_group.hpp)
-int iql_group_act_dim(const void* group, uint32_t member);   // iql.hip (iql_group.hpp)
+int bc_group_act_dim(const void* group, uint32_t member);    // bc.hip (bc_group.hpp), iql.hip (iql_group.hpp): group_core.hpp's group_act_dim of the kind
+int iql_group_act_dim(const void* group, uint32_t member);
 }
 
 namespace {
@@ -242,62 +242,75 @@ int32_t check_group_eval(const bdr_evaluator* evs, const bdr_group_eval_ops* ops
     return BDR_OK;
 }
 
-// the BC group's entries behind the function tables (bdr_bc_group_trainer_ops_default, bdr_bc_group_eval_ops_default)
-int32_t dbg_set_train(void* g, int32_t on)
-{
-    uint32_t n = 0;
-    BDR_TRY(bdr_bc_group_size((bdr_bc_group*)g, &n));
-    for (uint32_t i = 0; i < n; ++i) {
-        bdr_agent* m = nullptr;
-        BDR_TRY(bdr_bc_group_member((bdr_bc_group*)g, i, &m));
-        BDR_TRY(bdr_agent_set_train(m, on));
+// a BC or an IQL group's entries behind the function tables (bdr_*_group_trainer_ops_default, bdr_*_group_eval_ops_default), over the kind's
+// C functions
+template <class G, auto Size, auto Member, auto Opt, auto OptRec, auto Sample>
+struct GroupEntries {
+    static int32_t set_train(void* g, int32_t on)
+    {
+        uint32_t n = 0;
+        BDR_TRY(Size((G*)g, &n));
+        for (uint32_t i = 0; i < n; ++i) {
+            bdr_agent* m = nullptr;
+            BDR_TRY(Member((G*)g, i, &m));
+            BDR_TRY(bdr_agent_set_train(m, on));
+        }
+        return BDR_OK;
     }
-    return BDR_OK;
-}
-int32_t dbg_opt(void* g, void* const* b) { return bdr_bc_group_opt((bdr_bc_group*)g, (bdr_replay* const*)b); }
-int32_t dbg_opt_rec(void* g, void* const* b, float* out, int32_t cap, int32_t* n)
-{
-    return bdr_bc_group_opt_with_scalars((bdr_bc_group*)g, (bdr_replay* const*)b, out, cap, n);
-}
-int32_t dbg_sample_members(void* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, const void* const* rows, const int32_t* dtypes,
-                           float* const* act_out)
-{
-    return bdr_bc_group_sample_members((bdr_bc_group*)g, members, n_sel, norms, 1, rows, dtypes, act_out);
-}
-int32_t dbg_save_member(void* g, uint32_t member, const char* dir)
-{
-    bdr_agent* m = nullptr;
-    BDR_TRY(bdr_bc_group_member((bdr_bc_group*)g, member, &m));
-    return d_save(m, dir);
-}
-
-// the IQL group's entries behind the same tables (bdr_iql_group_trainer_ops_default, bdr_iql_group_eval_ops_default)
-int32_t dig_set_train(void* g, int32_t on)
-{
-    uint32_t n = 0;
-    BDR_TRY(bdr_iql_group_size((bdr_iql_group*)g, &n));
-    for (uint32_t i = 0; i < n; ++i) {
-        bdr_agent* m = nullptr;
-        BDR_TRY(bdr_iql_group_member((bdr_iql_group*)g, i, &m));
-        BDR_TRY(bdr_agent_set_train(m, on));
+    static int32_t opt(void* g, void* const* b) { return Opt((G*)g, (bdr_replay* const*)b); }
+    static int32_t opt_rec(void* g, void* const* b, float* out, int32_t cap, int32_t* n) { return OptRec((G*)g, (bdr_replay* const*)b, out, cap, n); }
+    static int32_t sample_members(void* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, const void* const* rows, const int32_t* dtypes,
+                                  float* const* act_out)
+    {
+        return Sample((G*)g, members, n_sel, norms, 1, rows, dtypes, act_out);
     }
-    return BDR_OK;
-}
-int32_t dig_opt(void* g, void* const* b) { return bdr_iql_group_opt((bdr_iql_group*)g, (bdr_replay* const*)b); }
-int32_t dig_opt_rec(void* g, void* const* b, float* out, int32_t cap, int32_t* n)
+    static int32_t save_member(void* g, uint32_t member, const char* dir)
+    {
+        bdr_agent* m = nullptr;
+        BDR_TRY(Member((G*)g, member, &m));
+        return d_save(m, dir);
+    }
+    // the default tables of the kind
+    static void eval_ops(bdr_bc_group_eval_ops* ops, G* group)
+    {
+        if (!ops) return;
+        memset(ops, 0, sizeof *ops);
+        ops->group = group;
+        if (group) (void)Size(group, &ops->n_members);
+        ops->sample_members = sample_members;
+    }
+    static void trainer_ops(bdr_group_trainer_ops* ops, G* group, bdr_replay* const* buffers)
+    {
+        if (!ops) return;
+        memset(ops, 0, sizeof *ops);
+        ops->group = group; ops->buffers = (void* const*)buffers;
+        if (group) (void)Size(group, &ops->n_members);
+        ops->set_train = set_train; ops->opt = opt; ops->opt_with_record = opt_rec;
+    }
+    static void trainer_post(bdr_bc_group_trainer_post* post, G* group)
+    {
+        if (!post) return;
+        memset(post, 0, sizeof *post);
+        eval_ops(&post->eval_ops, group);
+        post->save_member = save_member;
+    }
+};
+using BcGroupEntries = GroupEntries<bdr_bc_group, bdr_bc_group_size, bdr_bc_group_member, bdr_bc_group_opt, bdr_bc_group_opt_with_scalars, bdr_bc_group_sample_members>;
+using IqlGroupEntries =
+    GroupEntries<bdr_iql_group, bdr_iql_group_size, bdr_iql_group_member, bdr_iql_group_opt, bdr_iql_group_opt_with_scalars, bdr_iql_group_sample_members>;
+// the kinds a default evaluation table can name: its acting entry, the action width of a member, the kind in messages, its save
+struct GroupKindRow {
+    decltype(bdr_bc_group_eval_ops::sample_members) sample_members;
+    int (*act_dim)(const void*, uint32_t);
+    const char* a;
+    int32_t (*save_member)(void*, uint32_t, const char*);
+};
+const GroupKindRow* group_kind_of(const bdr_bc_group_eval_ops* ops)
 {
-    return bdr_iql_group_opt_with_scalars((bdr_iql_group*)g, (bdr_replay* const*)b, out, cap, n);
-}
-int32_t dig_sample_members(void* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, const void* const* rows, const int32_t* dtypes,
-                           float* const* act_out)
-{
-    return bdr_iql_group_sample_members((bdr_iql_group*)g, members, n_sel, norms, 1, rows, dtypes, act_out);
-}
-int32_t dig_save_member(void* g, uint32_t member, const char* dir)
-{
-    bdr_agent* m = nullptr;
-    BDR_TRY(bdr_iql_group_member((bdr_iql_group*)g, member, &m));
-    return d_save(m, dir);
+    static const GroupKindRow kinds[] = {{BcGroupEntries::sample_members, bc_group_act_dim, "a BC", BcGroupEntries::save_member},
+                                         {IqlGroupEntries::sample_members, iql_group_act_dim, "an IQL", IqlGroupEntries::save_member}};
+    for (const GroupKindRow& k : kinds) if (ops && ops->sample_members == k.sample_members) return &k;
+    return nullptr;
 }
 
 // every refusal of bdr_evaluate_bc_group (a BC or an IQL group behind the table), naming the member: the group acts on host rows, f32 or float64, and writes one f32 action row
@@ -311,14 +324,10 @@ int32_t check_bc_group_eval(const bdr_evaluator* evs, const bdr_bc_group_eval_op
         BDR_REQUIRE(ev.env.reset_with_index && ev.env.step, "member %u: the evaluator's environment function table is incomplete", p);
         BDR_REQUIRE(ev.n_episodes >= 1, "member %u: n_episodes must be >= 1", p);
         BDR_REQUIRE(ev.obs_row_bytes > 0, "member %u: obs_row_bytes must be set", p);
-        if (ops->sample_members == dbg_sample_members) {
-            const int A = bc_group_act_dim(ops->group, p);
+        if (const GroupKindRow* k = group_kind_of(ops)) {
+            const int A = k->act_dim(ops->group, p);
             BDR_REQUIRE(A > 0, "member %u: the group has no such member", p);
-            BDR_REQUIRE(ev.act_row_bytes == (uint64_t)A * 4, "member %u: a BC group acts with one f32 action row per member: act_row_bytes must be 4 * act_dim = %d", p, A * 4);
-        } else if (ops->sample_members == dig_sample_members) {
-            const int A = iql_group_act_dim(ops->group, p);
-            BDR_REQUIRE(A > 0, "member %u: the group has no such member", p);
-            BDR_REQUIRE(ev.act_row_bytes == (uint64_t)A * 4, "member %u: an IQL group acts with one f32 action row per member: act_row_bytes must be 4 * act_dim = %d", p, A * 4);
+            BDR_REQUIRE(ev.act_row_bytes == (uint64_t)A * 4, "member %u: %s group acts with one f32 action row per member: act_row_bytes must be 4 * act_dim = %d", p, k->a, A * 4);
         } else {
             BDR_REQUIRE(ev.act_row_bytes > 0 && ev.act_row_bytes % 4 == 0, "member %u: a BC group acts with f32 action rows: act_row_bytes must be a positive multiple of 4", p);
         }
@@ -614,23 +623,8 @@ int32_t bdr_evaluate_group(const bdr_evaluator* evs, const bdr_group_eval_ops* o
     }, out);
 }
 
-void bdr_bc_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_bc_group* group)
-{
-    if (!ops) return;
-    memset(ops, 0, sizeof *ops);
-    ops->group = group;
-    if (group) (void)bdr_bc_group_size(group, &ops->n_members);
-    ops->sample_members = dbg_sample_members;
-}
-
-void bdr_iql_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_iql_group* group)
-{
-    if (!ops) return;
-    memset(ops, 0, sizeof *ops);
-    ops->group = group;
-    if (group) (void)bdr_iql_group_size(group, &ops->n_members);
-    ops->sample_members = dig_sample_members;
-}
+void bdr_bc_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_bc_group* group) { BcGroupEntries::eval_ops(ops, group); }
+void bdr_iql_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_iql_group* group) { IqlGroupEntries::eval_ops(ops, group); }
 
 // the same loop for a BC or an IQL group: f32 action rows, f32 or float64 observation rows, a normaliser per member
 int32_t bdr_evaluate_bc_group(const bdr_evaluator* evs, const bdr_bc_group_eval_ops* ops, bdr_eval_result* out)
@@ -650,37 +644,14 @@ int32_t bdr_evaluate_bc_group(const bdr_evaluator* evs, const bdr_bc_group_eval_
 
 void bdr_bc_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_bc_group* group, bdr_replay* const* buffers)
 {
-    if (!ops) return;
-    memset(ops, 0, sizeof *ops);
-    ops->group = group; ops->buffers = (void* const*)buffers;
-    if (group) (void)bdr_bc_group_size(group, &ops->n_members);
-    ops->set_train = dbg_set_train; ops->opt = dbg_opt; ops->opt_with_record = dbg_opt_rec;
+    BcGroupEntries::trainer_ops(ops, group, buffers);
 }
-
-void bdr_bc_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_bc_group* group)
-{
-    if (!post) return;
-    memset(post, 0, sizeof *post);
-    bdr_bc_group_eval_ops_default(&post->eval_ops, group);
-    post->save_member = dbg_save_member;
-}
-
+void bdr_bc_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_bc_group* group) { BcGroupEntries::trainer_post(post, group); }
 void bdr_iql_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_iql_group* group, bdr_replay* const* buffers)
 {
-    if (!ops) return;
-    memset(ops, 0, sizeof *ops);
-    ops->group = group; ops->buffers = (void* const*)buffers;
-    if (group) (void)bdr_iql_group_size(group, &ops->n_members);
-    ops->set_train = dig_set_train; ops->opt = dig_opt; ops->opt_with_record = dig_opt_rec;
+    IqlGroupEntries::trainer_ops(ops, group, buffers);
 }
-
-void bdr_iql_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_iql_group* group)
-{
-    if (!post) return;
-    memset(post, 0, sizeof *post);
-    bdr_iql_group_eval_ops_default(&post->eval_ops, group);
-    post->save_member = dig_save_member;
-}
+void bdr_iql_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_iql_group* group) { IqlGroupEntries::trainer_post(post, group); }
 
 // Trainer::train_offline (trainer.rs:330-384) with post_process for every member of a group (BC or IQL) in lockstep
 int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, const bdr_group_trainer_ops* ops, const bdr_bc_group_trainer_post* post,
@@ -695,7 +666,8 @@ int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, con
     BDR_REQUIRE(P >= 1 && ops->buffers, "the group function table names no members or no buffers");
     BDR_TRY(check_group_post(post, P, check_bc_group_eval));
     // a NULL save_member: the save of the group kind the evaluation table names - IQL's default table: an IQL member, anything else: a BC member
-    const auto save_default = post && post->eval_ops.sample_members == dig_sample_members ? dig_save_member : dbg_save_member;
+    const GroupKindRow* kind = post ? group_kind_of(&post->eval_ops) : nullptr;
+    const auto save_default = kind ? kind->save_member : BcGroupEntries::save_member;
     bdr_trainer_config c = *c_in;
     c.warmup_period = 0; c.opt_interval = 1;            // trainer.rs:345-346
     std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member

@@ -370,172 +370,34 @@ def _group_train_offline(group, prefix: str, record_keys, buffers, max_opts, rec
     return [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
 
 
-class BcGroup:
-    """A set of BC agents of one shape whose Agent::opt runs as the launch sequence of ONE member, every launch serving all members
-    (bdr_bc_group_*): 2L + 4 launches per round for L layers in the "general" kernel form, 2L + 2 with the MFMA head, whatever the
-    number of members.  The members may differ in seed, learning rate and optimizer; their buffers are uniform buffers of their own
-    or views of one (`SimpleReplayBuffer.view`), so that P members hold one copy of a dataset.  Acting (`sample`: one launch for the
-    selected members), the lockstep `evaluate` and the compiled `train_offline` with post-processing serve all members at once too.
+class _DenseGroup:
+    """What BcGroup and IqlGroup share: a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
+    member, every launch serving all members (csrc/group_core.hpp through the kind's bdr_<kind>_group_* functions).  A subclass names
+    the C prefix (_PREFIX), the member class (_MEMBER) and the keys of a member's Record (RECORD_KEYS)."""
+    STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/group_core.hpp GroupCore::STEP_SLOTS)
+    _PREFIX = _MEMBER = None
+    RECORD_KEYS = ()
 
-    A launch grouping, not an agent kind: the members are ordinary `Bc` objects (every `Bc` method keeps working on a member and
-    means what it meant) that the group owns - `BcGroup.close()` closes them, `member.close()` on a live group is refused.  Results
-    are bit for bit those of stepping the same agents one after the other."""
-    STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/bc_group.hpp bdr_bc_group::STEP_SLOTS)
-
-    def __init__(self, agents):
-        agents = list(agents)
-        hs = (C.c_void_p * len(agents))(*[a.handle for a in agents])
-        g = C.c_void_p()
-        _lib.check(_lib.lib().bdr_bc_group_create(hs, len(agents), C.byref(g)))
-        self._g = g
-        self._members = agents
-        self._bound = None   # the handle array of the buffers passed last (opt() without an argument steps on them again)
-
-    @classmethod
-    def build(cls, configs) -> "BcGroup":
-        """One `Bc` per BcConfig, grouped.  Nothing is left behind when a config is refused."""
-        agents = []
-        try:
-            for c in configs:
-                agents.append(Bc.build(c))
-            return cls(agents)
-        except Exception:
-            for a in agents:
-                a.close()
-            raise
-
-    @property
-    def members(self):
-        return list(self._members)
-
-    def __len__(self):
-        return len(self._members)
-
-    @property
-    def handle(self):
-        return self._g
-
-    def info(self) -> dict:
-        """bdr_bc_group_info: {"form": "bc_layers", "n_members", "launches_per_round", "kernel_launches"}."""
-        i = _lib.GroupInfoC()
-        _lib.check(_lib.lib().bdr_bc_group_info(self._g, C.byref(i)))
-        form = GROUP_FORMS[i.form]
-        return {"form": form, "n_members": i.n_members, "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
-
-    @property
-    def form(self) -> str:
-        return self.info()["form"]
-
-    @property
-    def launches_per_round(self) -> int:
-        """kernel launches of one update round, whatever the number of members"""
-        return self.info()["launches_per_round"]
-
-    @property
-    def kernel_launches(self) -> int:
-        """kernel launches the group's own calls have enqueued since it was built"""
-        return self.info()["kernel_launches"]
-
-    def _buffers(self, buffers):
-        if buffers is None:
-            if self._bound is None:
-                raise ValueError("opt() without buffers needs an earlier call that named them")
-            return self._bound
-        buffers = list(buffers)
-        if len(buffers) != len(self._members):
-            raise ValueError(f"{len(self._members)} members need {len(self._members)} buffers, got {len(buffers)}")
-        self._bound = (C.c_void_p * len(buffers))(*[b.handle for b in buffers])
-        return self._bound
-
-    def opt(self, buffers=None) -> None:
-        """Agent::opt of every member on its own buffer: launches_per_round launches in all; does not synchronise.
-        `buffers=None`: the buffers of the last opt / opt_with_record call (they must still be open)."""
-        _lib.check(_lib.lib().bdr_bc_group_opt(self._g, self._buffers(buffers)))
-
-    def opt_with_record(self, buffers=None) -> list:
-        """Agent::opt_with_record of every member (one synchronisation): a list of Record dicts ({"loss": ..}) in member order."""
-        n, cap = len(self._members), 8
-        out = np.zeros((n, cap), np.float32)
-        cnt = np.zeros(n, np.int32)
-        _lib.check(_lib.lib().bdr_bc_group_opt_with_scalars(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap,
-                                                            cnt.ctypes.data_as(C.c_void_p)))
-        return [{k: float(v) for k, v in zip(("loss",), out[i, :cnt[i]])} for i in range(n)]
-
-    def sample(self, rows, norm=None, members=None) -> list:
-        """Policy::sample of the members in ONE launch (bdr_bc_group_sample): a list of float32 arrays [n, act_dim] in member order,
-        each with the bits of that member's own `sample_raw(rows[i], norm[i])` on either act path.
-        rows: one array per member - float32 or float64, [n, obs_dim] (or [obs_dim]: n = 1), the same n for every member - or ONE
-        array for all members (an ensemble on one observation batch).  norm: an ObsNormalizer for all members, a list of them /
-        None per member, or None.  members: a strictly ascending list of member indices (bdr_bc_group_sample_members): only those
-        act; the result still has one entry per member and the entries of members that were not selected are None."""
-        return _group_sample(self, "bdr_bc_group_sample", rows, norm, members)
-
-    def evaluate(self, evaluators) -> list:
-        """The Evaluator of every member in lockstep (bdr_evaluate_bc_group): member i on evaluators[i] (a
-        border_amd.evaluator.Evaluator with act_dim = the members' act_dim; environment, n_episodes, obs_dtype, normaliser and
-        reference scores may differ per member), ONE acting launch per round over the members that still have an episode open.
-        Each EvalResult is what evaluators[i].evaluate(member i) gives.  An exception raised by an environment is raised again here."""
-        return _group_evaluate(self, "bdr_bc_group", evaluators)
-
-    def train_offline(self, buffers, max_opts: int, record_interval: int = 0, on_record=None, evaluators=None, eval_interval: int = 0,
-                      save_interval: int = 0, model_dirs=None, on_event=None) -> list:
-        """Trainer::train_offline over the group in compiled code (bdr_trainer_train_offline_group_post): max_opts update rounds on
-        `buffers`; every record_interval-th one is an opt_with_record whose records go to on_record(opt_step, records).
-        evaluators / eval_interval / save_interval / model_dirs (one Evaluator and one directory per member): Trainer::post_process
-        after every opt step - a lockstep evaluation every eval_interval opt steps, each member's best model in model_dirs[i]/best,
-        every member in model_dirs[i]/<opt_steps> every save_interval opt steps.  on_event(member, env_steps, opt_steps, event,
-        scalars) sees every event ("opt", "opt_record", "eval", "cost").  Synchronised at its end; returns one statistics dict per
-        member."""
-        return _group_train_offline(self, "bdr_bc_group", ("loss",), buffers, max_opts, record_interval, on_record, evaluators, eval_interval,
-                                    save_interval, model_dirs, on_event)
-
-    def sync(self) -> None:
-        _lib.check(_lib.lib().bdr_bc_group_sync(self._g))
-
-    def close(self) -> None:
-        if getattr(self, "_g", None):
-            _lib.check(_lib.lib().bdr_bc_group_destroy(self._g))   # destroys the members
-            self._g = None
-            for a in self._members:
-                a._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class IqlGroup:
-    """A set of IQL agents of one shape whose Agent::opt (Iql::opt_, iql/base.rs:157-188) runs as the launch sequence of ONE member,
-    every launch serving all members (bdr_iql_group_*): 3 (Lq + Lv) + 2 Lp + 8 launches per round for Lv, Lq, Lp layers of value,
-    critic and actor, whatever the number of members.  The members may differ in seed, tau_iql, inv_lambda, exp_adv_max, gamma, the
-    critics' tau, adv_softmax, critic_loss, the action limit, the log-std clamps, learning rates and optimizers; their buffers are
-    uniform buffers of their own or views of one (`SimpleReplayBuffer.view`), so that P members hold one copy of a dataset.
-
-    A launch grouping, not an agent kind: the members are ordinary `Iql` objects (every `Iql` method keeps working on a member and
-    means what it meant) that the group owns - `IqlGroup.close()` closes them, `member.close()` on a live group is refused.  Results
-    are bit for bit those of stepping the same agents one after the other."""
-    STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/iql_group.hpp bdr_iql_group::STEP_SLOTS)
-    RECORD_KEYS = ("loss_value", "loss_critic", "loss_actor")
+    def _c(self, name):
+        return getattr(_lib.lib(), f"{self._PREFIX}_{name}")
 
     def __init__(self, agents):
         agents = list(agents)
         hs = (C.c_void_p * len(agents))(*[a.handle for a in agents])
         g = C.c_void_p()
-        _lib.check(_lib.lib().bdr_iql_group_create(hs, len(agents), C.byref(g)))
+        _lib.check(self._c("create")(hs, len(agents), C.byref(g)))
         self._g = g
         self._members = agents
         self._bound = None   # the handle array of the buffers passed last (opt() without an argument steps on them again)
         self._bound_buffers = None   # ... and the buffers themselves: kept alive, and checked to be open, while opt() may step on them
 
     @classmethod
-    def build(cls, configs) -> "IqlGroup":
-        """One `Iql` per IqlConfig, grouped.  Nothing is left behind when a config is refused."""
+    def build(cls, configs):
+        """One member agent per config, grouped.  Nothing is left behind when a config is refused."""
         agents = []
         try:
             for c in configs:
-                agents.append(Iql.build(c))
+                agents.append(cls._MEMBER.build(c))
             return cls(agents)
         except Exception:
             for a in agents:
@@ -554,9 +416,9 @@ class IqlGroup:
         return self._g
 
     def info(self) -> dict:
-        """bdr_iql_group_info: {"form": "iql_layers", "n_members", "launches_per_round", "kernel_launches"}."""
+        """bdr_<kind>_group_info: {"form": "bc_layers" / "iql_layers", "n_members", "launches_per_round", "kernel_launches"}."""
         i = _lib.GroupInfoC()
-        _lib.check(_lib.lib().bdr_iql_group_info(self._g, C.byref(i)))
+        _lib.check(self._c("info")(self._g, C.byref(i)))
         return {"form": GROUP_FORMS[i.form], "n_members": i.n_members, "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
 
     @property
@@ -591,35 +453,33 @@ class IqlGroup:
     def opt(self, buffers=None) -> None:
         """Agent::opt of every member on its own buffer: launches_per_round launches in all; does not synchronise.
         `buffers=None`: the buffers of the last opt / opt_with_record call (they must still be open)."""
-        _lib.check(_lib.lib().bdr_iql_group_opt(self._g, self._buffers(buffers)))
+        _lib.check(self._c("opt")(self._g, self._buffers(buffers)))
 
     def opt_with_record(self, buffers=None) -> list:
-        """Agent::opt_with_record of every member (one synchronisation): a list of Record dicts (loss_value, loss_critic, loss_actor)
-        in member order."""
+        """Agent::opt_with_record of every member (one synchronisation): a list of Record dicts (RECORD_KEYS) in member order."""
         n, cap = len(self._members), 8
         out = np.zeros((n, cap), np.float32)
         cnt = np.zeros(n, np.int32)
-        _lib.check(_lib.lib().bdr_iql_group_opt_with_scalars(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap,
-                                                             cnt.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._c("opt_with_scalars")(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)))
         return [{k: float(v) for k, v in zip(self.RECORD_KEYS, out[i, :cnt[i]])} for i in range(n)]
 
     def sample(self, rows, norm=None, members=None) -> list:
-        """Policy::sample of the members in ONE launch (bdr_iql_group_sample): a list of float32 arrays [n, act_dim] in member order,
-        each with the bits of that member's own `sample_raw(rows[i], norm[i])` on either act path, in the mode the member is in
-        (`set_train`) and at its own noise counter: a member in train mode takes n * act_dim draws of its noise stream, a member in
+        """Policy::sample of the members in ONE launch (bdr_<kind>_group_sample): a list of float32 arrays [n, act_dim] in member
+        order, each with the bits of that member's own `sample_raw(rows[i], norm[i])` on either act path.  An IQL member acts in the
+        mode it is in (`set_train`) and at its own noise counter: in train mode it takes n * act_dim draws of its noise stream, in
         eval mode none, so group calls and the member's own calls continue one stream.
         rows: one array per member - float32 or float64, [n, obs_dim] (or [obs_dim]: n = 1), the same n for every member - or ONE
         array for all members (an ensemble on one observation batch).  norm: an ObsNormalizer for all members, a list of them /
-        None per member, or None.  members: a strictly ascending list of member indices (bdr_iql_group_sample_members): only those
+        None per member, or None.  members: a strictly ascending list of member indices (bdr_<kind>_group_sample_members): only those
         act; the result still has one entry per member and the entries of members that were not selected are None."""
-        return _group_sample(self, "bdr_iql_group_sample", rows, norm, members)
+        return _group_sample(self, self._PREFIX + "_sample", rows, norm, members)
 
     def evaluate(self, evaluators) -> list:
-        """The Evaluator of every member in lockstep (bdr_evaluate_bc_group behind IQL's table): member i on evaluators[i] (a
+        """The Evaluator of every member in lockstep (bdr_evaluate_bc_group behind the kind's table): member i on evaluators[i] (a
         border_amd.evaluator.Evaluator with act_dim = the members' act_dim; environment, n_episodes, obs_dtype, normaliser and
         reference scores may differ per member), ONE acting launch per round over the members that still have an episode open.
         Each EvalResult is what evaluators[i].evaluate(member i) gives.  An exception raised by an environment is raised again here."""
-        return _group_evaluate(self, "bdr_iql_group", evaluators)
+        return _group_evaluate(self, self._PREFIX, evaluators)
 
     def train_offline(self, buffers, max_opts: int, record_interval: int = 0, on_record=None, evaluators=None, eval_interval: int = 0,
                       save_interval: int = 0, model_dirs=None, on_event=None) -> list:
@@ -630,15 +490,15 @@ class IqlGroup:
         every member in model_dirs[i]/<opt_steps> every save_interval opt steps.  on_event(member, env_steps, opt_steps, event,
         scalars) sees every event ("opt", "opt_record", "eval", "cost").  Synchronised at its end; returns one statistics dict per
         member."""
-        return _group_train_offline(self, "bdr_iql_group", self.RECORD_KEYS, buffers, max_opts, record_interval, on_record, evaluators,
-                                    eval_interval, save_interval, model_dirs, on_event)
+        return _group_train_offline(self, self._PREFIX, self.RECORD_KEYS, buffers, max_opts, record_interval, on_record, evaluators, eval_interval,
+                                    save_interval, model_dirs, on_event)
 
     def sync(self) -> None:
-        _lib.check(_lib.lib().bdr_iql_group_sync(self._g))
+        _lib.check(self._c("sync")(self._g))
 
     def close(self) -> None:
         if getattr(self, "_g", None):
-            _lib.check(_lib.lib().bdr_iql_group_destroy(self._g))   # destroys the members
+            _lib.check(self._c("destroy")(self._g))   # destroys the members
             self._g = None
             for a in self._members:
                 a._h = None
@@ -648,3 +508,29 @@ class IqlGroup:
             self.close()
         except Exception:
             pass
+
+
+class BcGroup(_DenseGroup):
+    """A set of BC agents of one shape whose Agent::opt runs as the launch sequence of ONE member, every launch serving all members
+    (bdr_bc_group_*): 2L + 4 launches per round for L layers in the "general" kernel form, 2L + 2 with the MFMA head, whatever the
+    number of members.  The members may differ in seed, learning rate and optimizer; their buffers are uniform buffers of their own
+    or views of one (`SimpleReplayBuffer.view`), so that P members hold one copy of a dataset.  Acting (`sample`: one launch for the
+    selected members), the lockstep `evaluate` and the compiled `train_offline` with post-processing serve all members at once too.
+
+    A launch grouping, not an agent kind: the members are ordinary `Bc` objects (every `Bc` method keeps working on a member and
+    means what it meant) that the group owns - `BcGroup.close()` closes them, `member.close()` on a live group is refused.  Results
+    are bit for bit those of stepping the same agents one after the other."""
+    _PREFIX, _MEMBER, RECORD_KEYS = "bdr_bc_group", Bc, ("loss",)
+
+
+class IqlGroup(_DenseGroup):
+    """A set of IQL agents of one shape whose Agent::opt (Iql::opt_, iql/base.rs:157-188) runs as the launch sequence of ONE member,
+    every launch serving all members (bdr_iql_group_*): 3 (Lq + Lv) + 2 Lp + 8 launches per round for Lv, Lq, Lp layers of value,
+    critic and actor, whatever the number of members.  The members may differ in seed, tau_iql, inv_lambda, exp_adv_max, gamma, the
+    critics' tau, adv_softmax, critic_loss, the action limit, the log-std clamps, learning rates and optimizers; their buffers are
+    uniform buffers of their own or views of one (`SimpleReplayBuffer.view`), so that P members hold one copy of a dataset.
+
+    A launch grouping, not an agent kind: the members are ordinary `Iql` objects (every `Iql` method keeps working on a member and
+    means what it meant) that the group owns - `IqlGroup.close()` closes them, `member.close()` on a live group is refused.  Results
+    are bit for bit those of stepping the same agents one after the other."""
+    _PREFIX, _MEMBER, RECORD_KEYS = "bdr_iql_group", Iql, ("loss_value", "loss_critic", "loss_actor")

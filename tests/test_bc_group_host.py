@@ -228,6 +228,15 @@ def test_every_refusal_names_the_first_member_that_differs(prog):
     assert got["who"] == "0" and "act_dim <= 64" in got["why"]
 
 
+def test_of_two_duplicate_members_the_first_is_named(prog):
+    """the duplicate search is a sort over (agent, member): it still names the FIRST member that repeats an earlier one"""
+    s = SHAPES["partial_block"]
+    got = refusal(prog, [member(s, ident=i) for i in (1, 2, 3, 2, 1)])   # member 3 repeats member 1, member 4 repeats member 0
+    assert got["who"] == "3" and "earlier member already" in got["why"], got
+    got = refusal(prog, [member(s, ident=i) for i in (1, 2, 3, 1, 2)])   # the same with the lower agent id at the later member
+    assert got["who"] == "3" and "earlier member already" in got["why"], got
+
+
 def test_group_size_and_launch_limits(prog):
     s = SHAPES["partial_block"]
     assert run(prog, ["many", 65535] + shape_args(s))["who"] == "-1"

@@ -201,3 +201,30 @@ def test_train_offline_is_a_loop_over_opt_and_opt_with_record(B):
         a.close(); rb.close()
     g.close()
     for r in rings: r.close()
+
+
+# the smallest shape the host path of a round needs: obs 4, act 2, one hidden layer of 64, B = 33 (two row blocks, the last partial)
+TINY = (4, 2, (64,), "None", 33, ("general",))
+
+
+def test_a_buffer_closed_since_the_last_opt_and_a_null_buffer_are_refused_and_move_nothing(B):
+    """opt() without buffers steps on the buffers named last: one closed since is refused here, naming the member, before the library
+    sees its stale handle; a None buffer is the library's own refusal, not an AttributeError"""
+    g = B.BcGroup.build([config(B, TINY, "general", i) for i in range(2)])
+    rings = [ring(B, TINY, 100 + i) for i in range(2)]
+    g.opt(rings)
+    g.sync()
+    moved = lambda: [{r: m.get_params(role=r) for r in ROLES} for m in g.members]
+    before, launches = moved(), g.kernel_launches
+    rings[1].close()
+    for call in (g.opt, g.opt_with_record):
+        with pytest.raises(ValueError, match="member 1"):
+            call()
+    with pytest.raises(B.BdrError, match="member 0: null buffer"):
+        g.opt([None, rings[0]])
+    g.sync()
+    assert g.kernel_launches == launches and [m.n_opts for m in g.members] == [1, 1]
+    for got, want in zip(moved(), before):
+        assert_same(got, want, "closed buffer")
+    g.close()
+    rings[0].close()

@@ -274,3 +274,31 @@ def test_refused_buffers_name_the_member_and_move_nothing(B):
         assert_same(state(g.members[i], rings[i], shape), stepped_alone(B, shape, i, 2), i)
     g.close()
     for r in rings + [per, empty, other, xoshiro, store]: r.close()
+
+
+# the smallest shape the host path of a round needs: obs 4, act 2, one hidden layer of 64, B = 33 (two row blocks, the last partial)
+TINY = (4, 2, (64,), (64,), (64,), "None", 2, 33, ("Clamp", "Mse", False))
+
+
+def test_a_buffer_closed_since_the_last_opt_and_a_null_buffer_are_refused_and_move_nothing(B):
+    """opt() without buffers steps on the buffers named last: one closed since is refused here, naming the member, before the library
+    sees its stale handle; a None buffer is the library's own refusal, not an AttributeError"""
+    g = B.IqlGroup.build([config(B, TINY, i) for i in range(2)])
+    rings = [ring(B, TINY, 100 + i) for i in range(2)]
+    g.opt(rings)
+    g.sync()
+    trained, targets = models(TINY)
+    moved = lambda: [{**{(m, r): a.get_params(m, role=r) for m in trained for r in ROLES}, **{(m, "param"): a.get_params(m) for m in targets}} for a in g.members]
+    before, launches = moved(), g.kernel_launches
+    rings[1].close()
+    for call in (g.opt, g.opt_with_record):
+        with pytest.raises(ValueError, match="member 1"):
+            call()
+    with pytest.raises(B.BdrError, match="member 0: null buffer"):
+        g.opt([None, rings[0]])
+    g.sync()
+    assert g.kernel_launches == launches and [m.n_opts for m in g.members] == [1, 1]
+    for got, want in zip(moved(), before):
+        assert_same(got, want, "closed buffer")
+    g.close()
+    rings[0].close()
