@@ -110,6 +110,9 @@ struct bdr_agent : bdr::ParamTable {
     hipStream_t stream = nullptr;
     void* group = nullptr;          // the live bdr_agent_group that adopted this agent (`stream` is then the group's; agent_group.hpp)
     bool train = false;
+    // conv3's input gradient (dqn.hip and conv_trunk.hpp): DxC3PosL with the k loop's last step peeled (igemm.hpp: ADxS1PosLean, PEEL).
+    // BDR_DXC3_KLOOP=0, read when the agent is constructed: DxC3Pos with the plain loop, the form before them (same bits; A/B and tests)
+    bool dxc3_kloop = [] { const char* e = getenv("BDR_DXC3_KLOOP"); return !(e && e[0] == '0'); }();
     uint64_t n_opts = 0;
     int32_t ckpt_format = BDR_CKPT_TCH;
     // Policy::sample state (dqn/base.rs:211-242)

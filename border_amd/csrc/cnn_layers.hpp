@@ -204,10 +204,10 @@ static __device__ __constant__ unsigned char c3_pos_by_taps[81] = {
 #ifndef BDR_DXC3_SHAPE
 #define BDR_DXC3_SHAPE 2, 2, 1, 1
 #endif
-template <int WM_, int WN_, int TM_, int TN_>
+template <int WM_, int WN_, int TM_, int TN_, class A_ = ADxS1Pos<GeomC3>>
 struct DxC3PosP {
     using G = GeomC3;
-    using A = ADxS1Pos<G>;
+    using A = A_;
     using Args = DxArgs;          // M = B * 81
     static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_;
     static constexpr int RPI = 1, RPIP = 0;
@@ -250,6 +250,7 @@ struct DxC3PosP {
 };
 
 using DxC3Pos = DxC3PosP<BDR_DXC3_SHAPE>;
+using DxC3PosL = DxC3PosP<BDR_DXC3_SHAPE, ADxS1PosLean<GeomC3>>;   // the same tiles and taps with ADxS1PosLean's addressing
 template <class P> inline dim3 dxc3_pos_grid(int B) { return dim3((unsigned)((B + P::WM * P::TM * 32 - 1) / (P::WM * P::TM * 32)) * n_tiles<P>(), P::G::IH * P::G::IW, 1); }
 
 // conv2 (4x4, stride 2): blockIdx.y = parity class (ph,pw); rows (b, ih/2, iw/2); K' = 4 taps * 64

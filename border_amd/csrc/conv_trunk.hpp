@@ -50,7 +50,8 @@ inline int32_t trunk_backward(bdr_agent* a, const Arena& conv, const float* p, c
     {   // position-class tiles (cnn_layers.hpp DxC3PosP: only the taps that reach a valid output; bit-identical to the flat row tiles)
         DxArgs d{dy3, p + conv.w3, a2, dy2, Bn * 81, nullptr, 0};
         Bracket br(a, label("conv3_dx").c_str());
-        BDR_HIP((launch_igemm<DxC3Pos, 2>(a->stream, dxc3_pos_grid<DxC3Pos>(Bn), d)));
+        if (a->dxc3_kloop) BDR_HIP((launch_igemm<DxC3PosL, 2, true>(a->stream, dxc3_pos_grid<DxC3PosL>(Bn), d)));   // (igemm.hpp: ADxS1PosLean, PEEL; BDR_DXC3_KLOOP=0: the form before them)
+        else BDR_HIP((launch_igemm<DxC3Pos, 2>(a->stream, dxc3_pos_grid<DxC3Pos>(Bn), d)));
     }
     {
         const ConvDwLayer& l = pl.layer[1];

@@ -885,7 +885,9 @@ int32_t update_critic(DqnCnn* a, int B, const uint8_t* obs, const uint8_t* next_
     auto c3_dx = [&]() -> int32_t {
         DxArgs d{a->dy3, a->q + ar.w3, a->a2[0], a->dy2, B * 81, sigf(SIG_DXL1), epoch};
         Bracket br(a, "bwd_conv3_dx");
-        BDR_HIP((launch_igemm<DxC3Pos, TEAMS_DX_C3>(a->stream, dxc3_pos_grid<DxC3Pos>(B), d, 0, kev(2))));
+        // lean tap addressing + the k loop's last step peeled (igemm.hpp ADxS1PosLean, PEEL), or the form before them (BDR_DXC3_KLOOP=0): same grid, same bits
+        if (a->dxc3_kloop) BDR_HIP((launch_igemm<DxC3PosL, TEAMS_DX_C3, true>(a->stream, dxc3_pos_grid<DxC3PosL>(B), d, 0, kev(2))));
+        else BDR_HIP((launch_igemm<DxC3Pos, TEAMS_DX_C3>(a->stream, dxc3_pos_grid<DxC3Pos>(B), d, 0, kev(2))));
         return BDR_OK;
     };
     auto c2_dw = [&]() -> int32_t {

@@ -163,6 +163,45 @@ struct ADxS1Pos {
     __device__ static void load(const Row& r, int kt, int q, f32x4* v) { v[0] = *reinterpret_cast<const f32x4*>(chunk(r, kt, q)); }
 };
 
+// ADxS1Pos with the address of a load reduced to two multiply-adds and no branch.  ADxS1Pos spends about 150 VALU / SALU instructions
+// and a dozen branches per k-tile and thread on div_small, the tap's (kh, kw) and two clamps, beside 16 MFMAs: its kernel is as
+// busy computing addresses as multiplying.  The first valid tap (kh0, kw0) of a row reads output (ih - kh0, iw - kw0); the t-th,
+// (t / nw, t % nw) behind it, sits t * COUT + (t / nw) * (OW - nw) * COUT floats below that.  Rows of padding images get zero strides
+// (they re-read their first chunk), so nothing needs a clamp: a valid row's t-th valid tap is inside the tensor by construction, and
+// the k loop never asks for more than the position's taps (k_igemm's tile()).  Same loads, same values, same order.
+template <class G>
+struct ADxS1PosLean {
+    static constexpr int VEC = 4;
+    static constexpr int NKT = G::KH * G::KW * G::COUT / BK;
+    struct Row { const float* base; int step, wrap, mul; };
+    __device__ static void taps(int i, int n_out, int k, int& k0, int& n) { ADxS1Pos<G>::taps(i, n_out, k, k0, n); }
+    __device__ static int div_mul(int d) { return d == 1 ? 32 : (d == 2 ? 16 : 11); }   // t / d == (t * div_mul(d)) >> 5 for t < 16, d <= 3
+    __device__ static int div_small(int t, int d) { return (t * div_mul(d)) >> 5; }
+    __device__ static Row row(const float* dy, int m, int M)
+    {
+        Row r;
+        const bool ok = m < M;
+        const int mm = ok ? m : 0;
+        const int b = mm / (G::IH * G::IW), rem = mm % (G::IH * G::IW);
+        const int ih = rem / G::IW, iw = rem % G::IW;
+        int kh0, nh, kw0, nw;
+        taps(ih, G::OH, G::KH, kh0, nh);
+        taps(iw, G::OW, G::KW, kw0, nw);
+        r.base = dy + ((size_t)b * G::OH * G::OW + (ih - kh0) * G::OW + (iw - kw0)) * G::COUT;
+        r.step = ok ? G::COUT : 0;
+        r.wrap = ok ? (G::OW - nw) * G::COUT : 0;
+        r.mul = div_mul(nw);
+        return r;
+    }
+    __device__ static const float* chunk(const Row& r, int kt, int q)
+    {
+        constexpr int TPT = G::COUT / BK;
+        const int t = kt / TPT, c0 = (kt % TPT) * BK;
+        return r.base - (t * r.step + ((t * r.mul) >> 5) * r.wrap) + c0 + q * 4;
+    }
+    __device__ static void load(const Row& r, int kt, int q, f32x4* v) { v[0] = *reinterpret_cast<const f32x4*>(chunk(r, kt, q)); }
+};
+
 // Input gradient of a stride-2, 4x4 conv: the input grid splits into 4 parity classes (ih%2, iw%2);
 // class (ph,pw) only sees taps kh in {ph, ph+2}, kw in {pw, pw+2}, so K' = 4*COUT per class and no
 // MFMA work is spent on structurally-zero taps.  rows m' = (b, ih/2, iw/2) within a class.
@@ -416,7 +455,8 @@ __device__ inline bool vrow_of(const typename P::Args& a, int y, int mv, int& mr
     else return P::vrow(a, mv, mr);
 }
 
-template <class P, int TEAMS = 1>
+// PEEL (two teams): the last step of the k loop, the only one a team may have to sit out, is taken out of the loop (see the loop).
+template <class P, int TEAMS = 1, bool PEEL = false>
 __global__ __launch_bounds__(64 * P::WM * P::WN * TEAMS) void k_igemm(typename P::Args args)
 {
     if constexpr (has_start_signal<typename P::Args>::value) start_signal(args.sig_flag, args.sig_epoch);
@@ -606,8 +646,8 @@ __global__ __launch_bounds__(64 * P::WM * P::WN * TEAMS) void k_igemm(typename P
     }
     __syncthreads();
     int cur = 0;
-    auto step = [&](auto set, int it) {   // set = (it+1)&1: holds tile it+1; refilled with tile it+3
-        if (TEAMS == 1 || it < my_n) {    // team-uniform; one team: my_n == iters, and a branch here costs the compiler its knowledge of which loads are outstanding
+    auto step = [&](auto set, int it, auto every) {   // set = (it+1)&1: holds tile it+1; refilled with tile it+3.  every: a step that both teams take
+        if (TEAMS == 1 || decltype(every)::value || it < my_n) {    // team-uniform; one team: my_n == iters, and a branch here costs the compiler its knowledge of which loads are outstanding
             const float* As = smem + cur * STAGE;
             const int k3 = tile(it + 3);
             mfma_ktile<P::TM, P::TN, LDB, P::B_TR>(As, As + BM * LDA, wm * P::TM * 32, wn * P::TN * 32, lane, acc, [&](int u) {
@@ -622,13 +662,27 @@ __global__ __launch_bounds__(64 * P::WM * P::WN * TEAMS) void k_igemm(typename P
     // (pairs, then the odd tail: a conditional second step inside the loop gives the compiler a path "first step, straight back to the
     //  header" on which the set the header consumes is the most recently loaded one, and its s_waitcnt insertion then drains the loads of
     //  the previous step at every header - seen as vmcnt(3 .. 0) instead of vmcnt(7 .. 4) in the l1 forward kernel)
-    {
+    if constexpr (TEAMS == 2 && PEEL) {
+        // Two teams: the team-uniform `it < my_n` in front of every step is such a path too - a step that is skipped loads nothing - and
+        // conv3's dX waited vmcnt(3 .. 0) at every header: its global loads ran one k-tile ahead of their commit, not two.  Team 1 is
+        // short by at most one tile, so every step but the last runs without the test (vmcnt(7 .. 4) in the loop).
+        const int common = max(iters - 1, 0);
+        int it = 0;
+        for (; it + 1 < common; it += 2) {
+            step(Set1{}, it, std::true_type{});
+            step(Set0{}, it + 1, std::true_type{});
+        }
+        if (it < common) {
+            step(Set1{}, it, std::true_type{});
+            step(Set0{}, it + 1, std::false_type{});
+        } else if (iters > 0) step(Set1{}, it, std::false_type{});
+    } else {
         int it = 0;
         for (; it + 1 < iters; it += 2) {
-            step(Set1{}, it);
-            step(Set0{}, it + 1);
+            step(Set1{}, it, std::false_type{});
+            step(Set0{}, it + 1, std::false_type{});
         }
-        if (it < iters) step(Set1{}, it);
+        if (it < iters) step(Set1{}, it, std::false_type{});
     }
     if constexpr (TEAMS == 2) {   // acc(team 0) += acc(team 1), through team 1's (now idle) stages
         constexpr int PER_WAVE = P::TM * P::TN * 16 * 64;
@@ -671,10 +725,10 @@ __global__ __launch_bounds__(64 * P::WM * P::WN * TEAMS) void k_igemm(typename P
 // flags: 0, or hipExtAnyOrderLaunch (no barrier bit on the dispatch packet: the kernel may start while the packets queued
 // before it on the same stream are still running).  stop: event completed by this kernel's own dispatch packet (no separate
 // marker packet in the queue, unlike hipEventRecord)
-template <class P, int TEAMS>
+template <class P, int TEAMS, bool PEEL = false>
 inline hipError_t launch_igemm(hipStream_t st, dim3 grid, const typename P::Args& args, unsigned flags = 0, hipEvent_t stop = nullptr)
 {
-    hipExtLaunchKernelGGL((k_igemm<P, TEAMS>), grid, dim3(64 * P::WM * P::WN * TEAMS), 0, st, nullptr, stop, flags, args);
+    hipExtLaunchKernelGGL((k_igemm<P, TEAMS, PEEL>), grid, dim3(64 * P::WM * P::WN * TEAMS), 0, st, nullptr, stop, flags, args);
     return hipGetLastError();
 }
 

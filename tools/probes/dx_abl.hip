@@ -59,5 +59,38 @@ int main()
             hipExtLaunchKernelGGL((k_igemm<DxC3Pos, 2>), g, dim3(64 * DxC3Pos::WM * DxC3Pos::WN * 2), extra, 0, nullptr, nullptr, 0, d3);
             CK(hipGetLastError()); }));
     }
+    // conv3 dX back to back: the plain two-team loop, its last step peeled (k_igemm's PEEL), ADxS1PosLean's addressing, both (the product's
+    // launch), and one team (one chain over all k-tiles: other roundings than two teams); l1 dX with the peeled loop.  Every two-team form must give the first one's words.
+    auto same_bits = [&](float* out, size_t n, auto f_old, auto f_new) {
+        std::vector<unsigned> a(n), b(n);
+        CK(hipMemset(out, 0xff, n * 4)); f_old(); CK(hipMemcpy(a.data(), out, n * 4, hipMemcpyDeviceToHost));
+        CK(hipMemset(out, 0xff, n * 4)); f_new(); CK(hipMemcpy(b.data(), out, n * 4, hipMemcpyDeviceToHost));
+        size_t bad = 0;
+        for (size_t i = 0; i < n; ++i) bad += a[i] != b[i];
+        return bad;
+    };
+    const dim3 g3 = dxc3_pos_grid<DxC3Pos>(B);
+    auto c3_t2 = [&] { CK((launch_igemm<DxC3Pos, 2>(0, g3, d3))); };
+    auto c3_pl = [&] { CK((launch_igemm<DxC3Pos, 2, true>(0, g3, d3))); };
+    auto c3_ln = [&] { CK((launch_igemm<DxC3PosL, 2>(0, g3, d3))); };
+    auto c3_lp = [&] { CK((launch_igemm<DxC3PosL, 2, true>(0, g3, d3))); };
+    auto c3_t1 = [&] { CK((launch_igemm<DxC3Pos, 1>(0, g3, d3))); };
+    auto c3_l1 = [&] { CK((launch_igemm<DxC3PosL, 1>(0, g3, d3))); };
+    printf("  conv3 dX, 2 teams                                       : %7.2f us\n", time_us(c3_t2));
+    printf("  conv3 dX, 2 teams, last step peeled                     : %7.2f us   (%zu words differ)\n", time_us(c3_pl), same_bits(dx2, n2, c3_t2, c3_pl));
+    printf("  conv3 dX, 2 teams, lean addressing                      : %7.2f us   (%zu words differ)\n", time_us(c3_ln), same_bits(dx2, n2, c3_t2, c3_ln));
+    printf("  conv3 dX, 2 teams, last step peeled, lean addressing    : %7.2f us   (%zu words differ)\n", time_us(c3_lp), same_bits(dx2, n2, c3_t2, c3_lp));
+    printf("  conv3 dX, 1 team                                        : %7.2f us\n", time_us(c3_t1));
+    printf("  conv3 dX, 1 team, lean addressing                       : %7.2f us   (%zu words differ from 1 team)\n", time_us(c3_l1), same_bits(dx2, n2, c3_t1, c3_l1));
+    float* dh1 = dev_rand((size_t)B * 512, -1.f, 1.f, 10);
+    float* w4 = dev_rand((size_t)3136 * 512, -0.05f, 0.05f, 11);
+    float* mask3 = dev_rand(n3, -1.f, 1.f, 12);
+    float* dx3; CK(hipMalloc(&dx3, n3 * 4));
+    DxArgs d4{dh1, w4, mask3, dx3, B, nullptr, 0};
+    const dim3 g4((m_tiles<DxL1>(B) * n_tiles<DxL1>() + 7) / 8 * 8, 1, 1);
+    auto l1_t2 = [&] { CK((launch_igemm<DxL1, 2>(0, g4, d4))); };
+    auto l1_pl = [&] { CK((launch_igemm<DxL1, 2, true>(0, g4, d4))); };
+    printf("  l1 dX, 2 teams                                          : %7.2f us\n", time_us(l1_t2));
+    printf("  l1 dX, 2 teams, last step peeled                        : %7.2f us   (%zu words differ)\n", time_us(l1_pl), same_bits(dx3, n3, l1_t2, l1_pl));
     return 0;
 }
