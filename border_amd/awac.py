@@ -73,6 +73,11 @@ class Awac(CandleAgent):
     KIND = "awac"
     CKPT_STEMS = ("actor", "critic", "critic.tgt")
 
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.check(_lib.lib().bdr_agent_destroy(self._h))   # (refused for a member of a live AwacGroup: the group owns it)
+            self._h = None
+
     def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated, z_pi=None, z_next=None) -> dict:
         """One Awac::opt_ iteration.  z_pi / z_next: [n, act_dim] N(0,1) draws for act_ and next_act in train mode (None: the
         agent's device stream)."""

@@ -27,7 +27,10 @@ namespace {
 // obs / next_obs / act rows -> the zero-padded actor inputs ([B][Kp]: obs, next_obs) and the three critic inputs ([B][Kq]): (obs | act),
 // and the observation columns of (obs | act_) and (next_obs | next_act), whose action columns k_candle_sample fills
 struct AwacPackArgs { const float* obs; const float* next; const float* act; int O, A, B; float* x_o; float* x_no; int ldp; float* xq; float* xq_pi; float* xq_next; int ldq; };
-__global__ __launch_bounds__(256) void k_awac_pack(AwacPackArgs p)
+// (the bodies of the three kernels below are functions over their argument struct: the kernel argument, or a member's entry of a device
+// array read in place - awac_group.hpp, where blockIdx.y is the member; `red` is the kernel's own 32 floats of LDS)
+template <class Args>
+__device__ __forceinline__ void awac_pack_body(const Args& p)
 {
     const int W = p.O + p.A;
     const size_t n = (size_t)p.B * W;
@@ -45,6 +48,7 @@ __global__ __launch_bounds__(256) void k_awac_pack(AwacPackArgs p)
         }
     }
 }
+__global__ __launch_bounds__(256) void k_awac_pack(AwacPackArgs p) { awac_pack_body(p); }
 
 // update_actor (awac/base.rs:127-168): q = min_i Q_i(obs, act), v = min_i Q_i(obs, act_) (online critics, util/critic.rs:197-202),
 // adv = q - v; w = clamp(exp(inv_lambda adv), 0, exp_adv_max) or softmax(inv_lambda adv) over the batch; logp of the batch actions
@@ -63,7 +67,8 @@ struct AwacActorArgs {
     float* gmean; float* gh2;                                        // [B][ldm], [A]
     float* scal; int accumulate; int B;                              // scal[1] loss_actor, [3] adv_mean, [4] adv_abs_mean, [5] logp_mean
 };
-__device__ __forceinline__ float awac_x(const AwacActorArgs& p, float a)
+template <class Args>
+__device__ __forceinline__ float awac_x(const Args& p, float a)
 {
 #pragma clang fp contract(off)
     if (!p.tanh_limit) return a;
@@ -72,7 +77,8 @@ __device__ __forceinline__ float awac_x(const AwacActorArgs& p, float a)
     return 0.5f * logf(r);
 }
 struct AwacAdv { float q, v, adv, z; };
-__device__ __forceinline__ AwacAdv awac_adv(const AwacActorArgs& p, int b)
+template <class Args>
+__device__ __forceinline__ AwacAdv awac_adv(const Args& p, int b)
 {
 #pragma clang fp contract(off)
     AwacAdv r;
@@ -83,9 +89,9 @@ __device__ __forceinline__ AwacAdv awac_adv(const AwacActorArgs& p, int b)
     r.z = r.adv * p.inv_lambda;
     return r;
 }
-__global__ __launch_bounds__(1024) void k_awac_actor_loss(AwacActorArgs p)
+template <class Args>
+__device__ __forceinline__ void awac_actor_loss_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     const float invB = 1.0f / (float)p.B;
     // softmax(z, 0) = exp(z - max) / sum(exp(z - max)): one batch-wide max and sum per workgroup
     float mx = 0.f, se = 1.f;
@@ -146,6 +152,11 @@ __global__ __launch_bounds__(1024) void k_awac_actor_loss(AwacActorArgs p)
         p.scal[5] = candle::acc(acc ? p.scal[5] : 0.f, s_lp, invB);
     }
 }
+__global__ __launch_bounds__(1024) void k_awac_actor_loss(AwacActorArgs p)
+{
+    __shared__ float red[32];
+    awac_actor_loss_body(p, red);
+}
 
 // update_critic (awac/base.rs:66-125): next_q = min_i Qtgt_i(next_obs, next_act), tgt = r + gamma_not_done * next_q with
 // gamma_not_done = (1 - (term | trunc)) * gamma in f32 (util.rs:235-255); loss = sum_i mean_b loss(Q_i - tgt), MSE or smooth L1
@@ -157,9 +168,9 @@ struct AwacCriticArgs {
     float* tgt; float* next_q;   // [B]
     int loss_kind; float* scal; int accumulate; int B;
 };
-__global__ __launch_bounds__(1024) void k_awac_critic_loss(AwacCriticArgs p)
+template <class Args>
+__device__ __forceinline__ void awac_critic_loss_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     const float invB = 1.0f / (float)p.B;
     const float s_abs = candle::row_sum(p.B, [&](int b) {
 #pragma clang fp contract(off)
@@ -197,6 +208,11 @@ __global__ __launch_bounds__(1024) void k_awac_critic_loss(AwacCriticArgs p)
         p.scal[6] = candle::acc(acc ? p.scal[6] : 0.f, s_r, invB);
         p.scal[7] = candle::acc(acc ? p.scal[7] : 0.f, s_nq, invB);
     }
+}
+__global__ __launch_bounds__(1024) void k_awac_critic_loss(AwacCriticArgs p)
+{
+    __shared__ float red[32];
+    awac_critic_loss_body(p, red);
 }
 
 }  // namespace
@@ -400,3 +416,6 @@ int32_t bdr_awac_sample_device(bdr_agent* base, uint64_t n, const void* obs_dev,
 }
 
 }  // extern "C"
+
+// the launch grouping of AWAC agents (bdr_awac_group_*): it needs Awac and the kernel bodies above
+#include "awac_group.hpp"

@@ -21,8 +21,11 @@
 //   Inside a member every index is the body's own, with the standalone kernel's bounds: rows are read for m0 + r < n and c < O from the
 //   member's staged block of n * O elements, out is written at t = (m0 + r) * A + j < n * A inside the member's block of n * A floats,
 //   head2 is read at j < A of the member's actor arena, the draw index counter + t is a 64-bit sum.
+//   The host half.  CandleActKind<M> below is what group_act.hpp's call needs of a kind, written once over the CandleAgent member M
+//   (candle_actor.hpp: Iql, Awac).
 #pragma once
 #include "group_done.hpp"
+#include "group_act.hpp"
 
 namespace {
 
@@ -42,5 +45,34 @@ __global__ __launch_bounds__(256 * TEAMS) void k_candle_act_group(const BDR_CONS
     __threadfence_system();   // this thread's result rows are in host memory before its workgroup counts
     bg_group_done(ticket, seq_host, seq);
 }
+
+// ---- group acting of CandleAgent members: group_act.hpp's call with what is a Gaussian actor's ----------------------------------------
+// Static, keyed on the actor arena: the actor net pn on pi_p, DA_CANDLE, and the static half of CandleAgent::sample_elem from the
+// member's config (no group holds an Mlp2 actor: mlp2 = 0).  Per call: the member's mode, read now (bdr_agent_set_train), and in train
+// mode its noise counter, which advances by the n * A draws the call takes - sample_elem's rule, so group calls, group rounds that draw
+// (awac_group.hpp), the member's own sample / sample_raw on either act path and bdr_agent_noise continue one stream in any
+// interleaving.  The call does not go through ensure_batch and does not touch a member's samp: results go to the group's pinned area.
+template <class M>
+struct CandleActKind : GroupActEntry<CandleActCall, k_candle_act_group<1>, k_candle_act_group<2>> {
+    const float* arena(const M* m) const { return m->pi_p; }
+    void write_static(const M* m, DenseActArgs& a) const
+    {
+        const MlpLayout& pn = m->pn;
+        a.nl = (int)pn.L.size();
+        for (int l = 0; l < a.nl; ++l) a.L[l] = DenseActLayer{m->pi_p + pn.L[l].w, m->pi_p + pn.L[l].b, pn.L[l].Kp, pn.L[l].Np, pn.L[l].relu};
+        a.mode = DA_CANDLE;
+        SampleElem& e = a.e;   // train, counter and z are the call's
+        e.head2 = m->pi_p + m->h2_off; e.mlp2 = 0;
+        e.lo = (float)m->cfg.min_log_std; e.hi = (float)m->cfg.max_log_std; e.tanh_limit = m->cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
+        e.amin = (float)m->cfg.action_min; e.amax = (float)m->cfg.action_max; e.scale = (float)m->cfg.action_scale;
+        e.seed = m->cfg.seed;
+    }
+    void noise(const M* m, int* train, uint64_t* counter) const { *train = m->train ? 1 : 0; *counter = m->noise_counter; }
+    void call_words(M* m, CandleActCall& c, int train, uint64_t start, uint64_t counter) const
+    {
+        c.train = train; c.counter = train ? start : 0;
+        m->noise_counter = counter;
+    }
+};
 
 }  // namespace

@@ -90,16 +90,20 @@ struct CandleSampleArgs {
     SampleElem e;   // the element code and its operands (dense_act.hpp: shared with k_dense_act)
     float* out; float* xq; int ldq; int O;
 };
-__global__ __launch_bounds__(256) void k_candle_sample(CandleSampleArgs p)
+// (the body over its argument struct: the kernel argument, or a member's entry of a device array read in place - awac_group.hpp, where
+// blockIdx.y is the member and `e` is built in registers from the entry's static half and the member's step slot)
+template <class Args>
+__device__ __forceinline__ void candle_sample_body(const Args& p, const SampleElem& e)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.n * p.A) return;
     const int b = t / p.A, j = t % p.A;
     const float* row = p.mean + (size_t)b * p.ldm;
-    const float a = candle_sample_elem(p.e, row[j], j, (size_t)t, p.e.mlp2 ? row[p.A + j] : 0.f);
+    const float a = candle_sample_elem(e, row[j], j, (size_t)t, e.mlp2 ? row[p.A + j] : 0.f);
     p.out[t] = a;
     if (p.xq) p.xq[(size_t)b * p.ldq + p.O + j] = a;
 }
+__global__ __launch_bounds__(256) void k_candle_sample(CandleSampleArgs p) { candle_sample_body(p, p.e); }
 
 int32_t check_mlp(const bdr_mlp_config& m, const char* what, bool actor)
 {
@@ -128,7 +132,7 @@ struct CandleAgent : DenseAgent {
     uint64_t step_pi = 0, step_q = 0;
     uint64_t noise_counter = 0;
     // batch buffers (ensure_batch)
-    int B = 0; uint64_t batch_gen = 0;   // batch_gen: bumped whenever the batch buffers are re-allocated (iql_group.hpp keys its static arguments on it)
+    int B = 0; uint64_t batch_gen = 0;   // batch_gen: bumped whenever the batch buffers are re-allocated (iql_group.hpp and awac_group.hpp key their static arguments on it)
     float *x_o = nullptr, *x_no = nullptr, *xq = nullptr;    // actor inputs [B][Kp] (obs, next_obs), critic input [B][Kq] (obs | act)
     std::vector<float*> p_act, p_dy;                         // actor on obs, its gradients
     std::vector<float*> c_act[4], t_act[4], c_dy[4];         // online critics, target critics, critic gradients

@@ -2,7 +2,7 @@
 // Group acting, the host half, once: Policy::sample of the selected members of a group on n host rows each in ONE launch of a group
 // entry over dense_act_body (k_bc_act_group, bc_group.hpp: BC; k_candle_act_group, candle_act_group.hpp: Gaussian actors).  The rule
 // without HIP in it - selection, the staged offsets, the cap, the draws - is group_act_plan.hpp's; this header adds the state and the
-// call.  A group (group_core.hpp: bdr_bc_group, bdr_iql_group) holds a GroupAct<Call> as `act` beside device, stream, members, shape (obs_dim,
+// call.  A group (group_core.hpp: bdr_bc_group, bdr_iql_group, bdr_awac_group) holds a GroupAct<Call> as `act` beside device, stream, members, shape (obs_dim,
 // act_dim), ticket, seq, launches and kernel_launches, and hands group_act_sample a Kind that says what differs:
 //   Kind::Call                          the words of one member's call (BcActCall, CandleActCall: the common words by name)
 //   Kind::arena(m)                      the parameter arena the member acts with: the key of its static arguments

@@ -1,5 +1,5 @@
 // ================================================================================================
-// A launch grouping of dense agents, the host half, once (bc_group.hpp: BC; iql_group.hpp: IQL): Agent::opt of every member in the
+// A launch grouping of dense agents, the host half, once (bc_group.hpp: BC; iql_group.hpp: IQL; awac_group.hpp: AWAC): Agent::opt of every member in the
 // launch sequence the agent enqueues for ONE member, every launch serving ALL members - the member index is grid dimension y.  A launch
 // grouping, not an agent kind: the members stay ordinary agents on the group's stream.  The protocol: adopt the members onto one
 // stream, check the buffers, take a slot of the pinned step ring, re-stage the static arguments of the members whose key has moved,
@@ -22,7 +22,8 @@
 //   MAX_LAUNCHES, K_GATHER, FORM, MIN_CAP, CAP_MSG                  the plan's capacity and gather kernel, the bdr_group_info form, the
 //                                                                   least cap_per_member of opt_with_scalars and its message
 //   describe(m), refusal(..), kernel_name(k), round_plan(..), launch_count(shape)   the rule of its plan header
-//   fill_step(m, bs, plan)                                          this step's words; advances the member's step counters, n_opts, last_B
+//   fill_step(m, bs, plan)                                          this step's words; advances the member's step counters, n_opts, last_B (AWAC: and
+//                                                                   reads its mode and takes the round's draws of its noise counter)
 //   member_static(m, bs, r, plan, o)                                one member's static arguments
 //   allocate(shape, P), stage(p, P, o), upload()                    its StagedArrays
 //   check_static(plan, n, o, p)                                     the plan's weight-gradient grids against the member's

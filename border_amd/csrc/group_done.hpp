@@ -1,4 +1,4 @@
-// The end-of-round ticket of the launch groupings of dense agents (bc_group.hpp: BC; iql_group.hpp: IQL), gl_group_done's rule
+// The end-of-round ticket of the launch groupings of dense agents (bc_group.hpp: BC; iql_group.hpp: IQL; awac_group.hpp: AWAC), gl_group_done's rule
 // (group_layers.hpp): the last launch of a round that reads the step slot calls it as its last statement.
 #pragma once
 #include <hip/hip_runtime.h>

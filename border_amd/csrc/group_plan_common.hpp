@@ -1,7 +1,7 @@
 // ================================================================================================
-// What the launch plans of the agent groups share (bc_group_plan.hpp, iql_group_plan.hpp, group_layers_plan.hpp), without HIP in it:
+// What the launch plans of the agent groups share (bc_group_plan.hpp, iql_group_plan.hpp, awac_group_plan.hpp, group_layers_plan.hpp), without HIP in it:
 // the hardware limits of a launch, the row chunks of the grouped weight gradient, the gather's workgroups per row, and the refusals of
-// a group that do not depend on the kind of its members.  The plan headers keep their own names (bg_*, ig_*, gl_*) as forwarders.
+// a group that do not depend on the kind of its members.  The plan headers keep their own names (bg_*, ig_*, ag_*, gl_*) as forwarders.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -30,6 +30,30 @@ inline unsigned gp_gather_chunks(uint64_t obs_bytes)
     const uint64_t nvec = obs_bytes % 16 == 0 ? obs_bytes / 16 : obs_bytes / 4;
     const uint64_t c = (nvec + 1023) / 1024;
     return (unsigned)(c < 1 ? 1 : c);
+}
+
+// one Mlp as the plans of the candle-family groups (iql_group_plan.hpp, awac_group_plan.hpp) read it: padded sizes (multiples of 64:
+// make_mlp) and logical output width of every layer, and whether its output has a ReLU
+constexpr int GP_SHAPE_LAYERS = 16;
+struct GpNet { int n_layers; int Kp[GP_SHAPE_LAYERS], Np[GP_SHAPE_LAYERS], out[GP_SHAPE_LAYERS]; int activation_out; };
+inline bool gp_same_net(const GpNet& a, const GpNet& b)
+{
+    if (a.n_layers != b.n_layers || a.activation_out != b.activation_out) return false;
+    for (int i = 0; i < a.n_layers && i < GP_SHAPE_LAYERS; ++i) if (a.Kp[i] != b.Kp[i] || a.Np[i] != b.Np[i] || a.out[i] != b.out[i]) return false;
+    return true;
+}
+inline uint64_t gp_arena_floats(const GpNet& n)
+{
+    uint64_t total = 0;
+    for (int i = 0; i < n.n_layers; ++i) total += (uint64_t)n.Kp[i] * n.Np[i] + n.Np[i];
+    return total;
+}
+// tiles of the grouped weight gradient of one instance of the network
+inline unsigned gp_dw_tiles(const GpNet& n, int batch)
+{
+    unsigned dw = 0;
+    for (int i = 0; i < n.n_layers; ++i) dw += (unsigned)((n.Kp[i] / 32) * (n.Np[i] / 32) * gp_dw_chunks(batch));
+    return dw;
 }
 
 // the first member that is the same agent as an earlier member (n: there is none); a sort, not n^2 / 2 comparisons at 65535 members

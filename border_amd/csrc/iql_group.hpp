@@ -25,8 +25,7 @@
 //   critic 1, actor 2) are handed dw + n * P / ra + n * P: 3 P entries each; NET < 3 = the AdamScalars of an IqlStep;
 //   inside a member every index is the body's own, with the bounds of the standalone kernel.
 // Acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp, which states the bounds of
-// its indices; included by this translation unit only) through group_act.hpp, the host half BC's group shares; IqlActKind below says
-// what is IQL's.
+// its indices) through group_act.hpp, the host half BC's group shares; IqlActKind below is CandleActKind of an Iql.
 #pragma once
 #include "dense_group.hpp"
 #include "candle_act_group.hpp"
@@ -74,24 +73,18 @@ __global__ __launch_bounds__(256) void k_iql_reduce_adam_group(const BDR_CONST_A
     if constexpr (NET == IG_NET_ACTOR) bg_group_done(ticket, seq_host, seq);
 }
 
-IgNet iql_net_shape(const MlpLayout& net, int activation_out)
-{
-    IgNet s{};
-    s.n_layers = (int)net.L.size(); s.activation_out = activation_out;
-    for (int i = 0; i < s.n_layers && i < IG_SHAPE_LAYERS; ++i) { s.Kp[i] = net.L[i].Kp; s.Np[i] = net.L[i].Np; s.out[i] = net.L[i].out; }
-    return s;
-}
 IgShape iql_shape(const Iql* m)
 {
     IgShape s{};
     s.obs_dim = m->O; s.act_dim = m->A; s.batch = (int)m->cfg.batch_size; s.n_critics = m->NC;
-    s.value = iql_net_shape(m->vn, m->cfg.value.activation_out);
-    s.critic = iql_net_shape(m->qn, m->cfg.critic.activation_out);
-    s.actor = iql_net_shape(m->pn, m->cfg.actor.activation_out);
+    s.value = dg_net_shape(m->vn, m->cfg.value.activation_out);
+    s.critic = dg_net_shape(m->qn, m->cfg.critic.activation_out);
+    s.actor = dg_net_shape(m->pn, m->cfg.actor.activation_out);
     return s;
 }
 
-// ---- host: one member's static arguments, exactly what Iql::update hands its launches ---------------------------------------------------
+// ---- host: one member's static arguments, exactly what Iql::update hands its launches (the dense, dX, dW and reduce entries of a
+// network: dense_group.hpp's dg_fwd_entries / dg_step_entries) ---------------------------------------------------------------------------
 struct IqlMemberArgs {
     GatherArgs gather; IqlPackArgs pack;
     std::vector<DenseGroupEntry> dense;   // the forward and dX launches in stream order
@@ -99,64 +92,6 @@ struct IqlMemberArgs {
     DenseDwSmallGroup dw[3]; int dw_grid[3];   // by IgNetId
     ReduceAdamArgs ra[3];
 };
-
-DenseArgs iql_fwd_args(const DenseLayer& l, const float* par, DenseSrc in, float* out, int bs)   // dense_forward_z
-{
-    DenseArgs d{};
-    d.x = in; d.w = par + l.w; d.bias = par + l.b; d.out = out; d.ldo = l.Np;
-    d.M = bs; d.ncols = l.Np; d.kred = l.Kp; d.relu = l.relu; d.w_ld = l.Np;
-    return d;
-}
-DenseArgs iql_dx_args(const DenseLayer& l, const float* par, const float* dy, float* dx, const float* mask, int bs)   // dense_dx_z
-{
-    DenseArgs d{};
-    d.x = DenseSrc{dy, l.Np}; d.w = par + l.w; d.out = dx; d.ldo = l.Kp; d.mask = mask; d.ldm = l.Kp;
-    d.M = bs; d.ncols = l.Kp; d.kred = l.Np; d.w_ld = l.Np;
-    return d;
-}
-// mlp_forward of nz (parameters, input, activations) triples of one architecture: one entry per layer
-void iql_fwd_entries(std::vector<DenseGroupEntry>& out, const MlpLayout& net, int nz, const float* const* par, const float* const* x,
-                     std::vector<float*>* const* acts, int bs)
-{
-    for (size_t l = 0; l < net.L.size(); ++l) {
-        DenseGroupEntry e{};
-        for (int z = 0; z < nz; ++z)
-            e.a[z] = iql_fwd_args(net.L[l], par[z], l == 0 ? DenseSrc{x[z], net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*acts[z])[l], bs);
-        out.push_back(e);
-    }
-}
-// mlp_backward_step of nz networks of one architecture: the dX entries from the last layer down, the grouped dW, the reduce segments
-void iql_step_entries(IqlMemberArgs& o, int id, const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
-                      const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
-                      const std::vector<size_t>& off, int bs, size_t total, double tau, const DenseReduceSeg* extra)
-{
-    const int L = (int)net.L.size();
-    for (int l = L - 1; l >= 1; --l) {
-        DenseGroupEntry e{};
-        for (int z = 0; z < nz; ++z) e.a[z] = iql_dx_args(net.L[l], p[z], (*dys[z])[l], (*dys[z])[l - 1], (*acts[z])[l - 1], bs);
-        o.dense.push_back(e);
-    }
-    DenseDwJob jobs[DW_GROUP];
-    const int c = DenseAgent::chunks_for(bs);
-    int nj = 0;
-    for (int z = 0; z < nz; ++z)
-        for (int l = 0; l < L; ++l)
-            jobs[nj++] = DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*dys[z])[l],
-                                    part + (size_t)z * part_stride + off[l], c};
-    o.dw_grid[id] = dense_dw_small_group_fill(o.dw[id], jobs, nj, bs);
-    ReduceAdamArgs& ra = o.ra[id];
-    ra = ReduceAdamArgs{};
-    ra.nseg = L; ra.inst_part_stride = part_stride;
-    for (int l = 0; l < L; ++l) {
-        const DenseLayer& ly = net.L[l];
-        const size_t nfl = (size_t)ly.Kp * ly.Np + ly.Np;
-        ra.seg[l] = DenseReduceSeg{part + off[l], nfl, c, (unsigned)(ly.w / 4), (unsigned)(nfl / 4)};
-    }
-    if (extra) ra.seg[ra.nseg++] = *extra;
-    for (int z = 0; z < nz; ++z) { ra.p[z] = p[z]; ra.g[z] = g[z]; ra.m[z] = m[z]; ra.v[z] = v[z]; ra.tgt[z] = tgt ? tgt[z] : nullptr; ra.vmax[z] = nullptr; }
-    // (s[z], track and grads_only are the entry's: this step's IqlStep, the network, 0)
-    ra.n4 = (unsigned)(total / 4); ra.track = tgt ? 1 : 0; ra.tau = (float)tau; ra.omt = (float)(1.0 - tau);
-}
 
 // (bs: the batch size; r: the member's ring or view; plan: replay_sample_plan's descriptor of this step)
 void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& plan, IqlMemberArgs& o)
@@ -179,11 +114,11 @@ void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& pl
     {
         const float* params[4]; const float* x[4]; std::vector<float*>* acts[4];
         for (int i = 0; i < NC; ++i) { params[i] = m->q_t[i]; x[i] = m->xq; acts[i] = &m->t_act[i]; params[NC + i] = m->q_p[i]; x[NC + i] = m->xq; acts[NC + i] = &m->c_act[i]; }
-        iql_fwd_entries(o.dense, qn, 2 * NC, params, x, acts, bs);
+        dg_fwd_entries(o.dense, qn, 2 * NC, params, x, acts, bs);
     }
-    { const float* pp[1] = {m->pi_p}; const float* x[1] = {m->x_o}; std::vector<float*>* acts[1] = {&m->p_act}; iql_fwd_entries(o.dense, pn, 1, pp, x, acts, bs); }
+    { const float* pp[1] = {m->pi_p}; const float* x[1] = {m->x_o}; std::vector<float*>* acts[1] = {&m->p_act}; dg_fwd_entries(o.dense, pn, 1, pp, x, acts, bs); }
     // ---- update_value
-    { const float* pp[1] = {m->v_p}; const float* x[1] = {m->x_o}; std::vector<float*>* acts[1] = {&m->v_act}; iql_fwd_entries(o.dense, vn, 1, pp, x, acts, bs); }
+    { const float* pp[1] = {m->v_p}; const float* x[1] = {m->x_o}; std::vector<float*>* acts[1] = {&m->v_act}; dg_fwd_entries(o.dense, vn, 1, pp, x, acts, bs); }
     {
         IqlValueArgs& p = o.vloss;
         p = IqlValueArgs{};
@@ -193,12 +128,12 @@ void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& pl
     }
     {
         std::vector<float*>* acts[1] = {&m->v_act}; std::vector<float*>* dys[1] = {&m->v_dy};
-        iql_step_entries(o, IG_NET_VALUE, vn, 1, &m->v_p, &m->v_g, &m->v_m, &m->v_v, nullptr, m->x_o, acts, dys, m->v_part, 0, m->v_off, bs, vn.total, cfg.critic_tau, nullptr);
+        dg_step_entries(o, IG_NET_VALUE, vn, 1, &m->v_p, &m->v_g, &m->v_m, &m->v_v, nullptr, m->x_o, acts, dys, m->v_part, 0, m->v_off, bs, vn.total, cfg.critic_tau, nullptr);
     }
     // ---- update_critic
     {
         const float* pp[2] = {m->v_p, m->v_p}; const float* x[2] = {m->x_o, m->x_no}; std::vector<float*>* acts[2] = {&m->vo_act, &m->vn_act};
-        iql_fwd_entries(o.dense, vn, 2, pp, x, acts, bs);
+        dg_fwd_entries(o.dense, vn, 2, pp, x, acts, bs);
     }
     {
         IqlCriticArgs& p = o.closs;
@@ -211,14 +146,14 @@ void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& pl
     {
         std::vector<float*>* acts[4]; std::vector<float*>* dys[4];
         for (int i = 0; i < NC; ++i) { acts[i] = &m->c_act[i]; dys[i] = &m->c_dy[i]; }
-        iql_step_entries(o, IG_NET_CRITIC, qn, NC, m->q_p, m->q_g, m->q_m, m->q_v, m->q_t, m->xq, acts, dys, m->q_part, m->q_part_stride, m->q_off, bs, qn.total,
+        dg_step_entries(o, IG_NET_CRITIC, qn, NC, m->q_p, m->q_g, m->q_m, m->q_v, m->q_t, m->xq, acts, dys, m->q_part, m->q_part_stride, m->q_off, bs, qn.total,
                          cfg.critic_tau, nullptr);
     }
     // ---- update_actor
     {
         const float* params[4]; const float* x[4]; std::vector<float*>* acts[4];
         for (int i = 0; i < NC; ++i) { params[i] = m->q_t[i]; x[i] = m->xq; acts[i] = &m->t_act[i]; }
-        iql_fwd_entries(o.dense, qn, NC, params, x, acts, bs);
+        dg_fwd_entries(o.dense, qn, NC, params, x, acts, bs);
     }
     {
         IqlActorArgs& p = o.aloss;
@@ -234,38 +169,15 @@ void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& pl
     {
         std::vector<float*>* acts[1] = {&m->p_act}; std::vector<float*>* dys[1] = {&m->p_dy};
         const DenseReduceSeg h2seg{m->h2_part, (size_t)pad64(A), 1, (unsigned)(m->h2_off / 4), (unsigned)(pad64(A) / 4)};
-        iql_step_entries(o, IG_NET_ACTOR, pn, 1, &m->pi_p, &m->pi_g, &m->pi_m, &m->pi_v, nullptr, m->x_o, acts, dys, m->pi_part, 0, m->pi_off, bs, m->pi_total,
+        dg_step_entries(o, IG_NET_ACTOR, pn, 1, &m->pi_p, &m->pi_g, &m->pi_m, &m->pi_v, nullptr, m->x_o, acts, dys, m->pi_part, 0, m->pi_off, bs, m->pi_total,
                          cfg.critic_tau, &h2seg);
     }
 }
 
 // ---- group acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp) -----------------
-// group_act.hpp's call with what is IQL's.  Static, keyed on the actor arena: the actor net pn on pi_p, DA_CANDLE, and the static half of
-// CandleAgent::sample_elem from the member's config (IQL has no Mlp2 actor: mlp2 = 0).  Per call: the member's mode, read now
-// (bdr_agent_set_train), and in train mode its noise counter, which advances by the n * A draws the call takes - sample_elem's rule, so
-// group calls, the member's own sample / sample_raw on either act path and bdr_agent_noise continue one stream in any interleaving.  The
-// call does not go through ensure_batch and does not touch a member's samp: results go to the group's pinned area.
-struct IqlActKind : GroupActEntry<CandleActCall, k_candle_act_group<1>, k_candle_act_group<2>> {
-    const float* arena(const Iql* m) const { return m->pi_p; }
-    void write_static(const Iql* m, DenseActArgs& a) const
-    {
-        const MlpLayout& pn = m->pn;
-        a.nl = (int)pn.L.size();
-        for (int l = 0; l < a.nl; ++l) a.L[l] = DenseActLayer{m->pi_p + pn.L[l].w, m->pi_p + pn.L[l].b, pn.L[l].Kp, pn.L[l].Np, pn.L[l].relu};
-        a.mode = DA_CANDLE;
-        SampleElem& e = a.e;   // train, counter and z are the call's
-        e.head2 = m->pi_p + m->h2_off; e.mlp2 = 0;
-        e.lo = (float)m->cfg.min_log_std; e.hi = (float)m->cfg.max_log_std; e.tanh_limit = m->cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
-        e.amin = (float)m->cfg.action_min; e.amax = (float)m->cfg.action_max; e.scale = (float)m->cfg.action_scale;
-        e.seed = m->cfg.seed;
-    }
-    void noise(const Iql* m, int* train, uint64_t* counter) const { *train = m->train ? 1 : 0; *counter = m->noise_counter; }
-    void call_words(Iql* m, CandleActCall& c, int train, uint64_t start, uint64_t counter) const
-    {
-        c.train = train; c.counter = train ? start : 0;
-        m->noise_counter = counter;
-    }
-};
+// group_act.hpp's call with CandleActKind (candle_act_group.hpp), the acting kind of every CandleAgent member: the static half keyed on
+// the actor arena, the member's mode and noise counter per call.
+using IqlActKind = CandleActKind<Iql>;
 
 // ---- what is IQL's of the group core (group_core.hpp) ----------------------------------------------------------------------------------
 struct IqlGroupKind {

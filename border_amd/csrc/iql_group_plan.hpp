@@ -14,25 +14,20 @@
 
 namespace bdr {
 
-constexpr int IG_SHAPE_LAYERS = 16;
+constexpr int IG_SHAPE_LAYERS = GP_SHAPE_LAYERS;
 constexpr int IG_DW_GROUP = 16;     // jobs of one grouped weight-gradient launch (dense.hpp DW_GROUP)
 constexpr int IG_RA_SEGS = 12;      // segments of k_dense_reduce_adam (dense.hpp RA_SEGS)
 constexpr int IG_MAXZ = 4;          // instances of one dense launch (dense.hpp DenseArgsZ, RA_INST)
 constexpr unsigned IG_MAX_MEMBERS = GP_MAX_MEMBERS;
 
 // ---- what the rule reads of a member ------------------------------------------------------------------------------------------------
-// padded sizes (multiples of 64: make_mlp) and logical output width of every layer of one network, and whether its output has a ReLU
-struct IgNet { int n_layers; int Kp[IG_SHAPE_LAYERS], Np[IG_SHAPE_LAYERS], out[IG_SHAPE_LAYERS]; int activation_out; };
+// one network (group_plan_common.hpp, shared with awac_group_plan.hpp)
+using IgNet = GpNet;
 struct IgShape { int obs_dim, act_dim, batch, n_critics; IgNet value, critic, actor; };
 // kind_iql: the agent is an IQL agent; n_updates: its n_updates_per_opt
 struct IgMember { IgShape shape; int kind_iql; uint64_t n_updates; int device, prof, grad_comm; const void* agent; };
 
-inline bool ig_same_net(const IgNet& a, const IgNet& b)
-{
-    if (a.n_layers != b.n_layers || a.activation_out != b.activation_out) return false;
-    for (int i = 0; i < a.n_layers && i < IG_SHAPE_LAYERS; ++i) if (a.Kp[i] != b.Kp[i] || a.Np[i] != b.Np[i] || a.out[i] != b.out[i]) return false;
-    return true;
-}
+inline bool ig_same_net(const IgNet& a, const IgNet& b) { return gp_same_net(a, b); }
 inline bool ig_same_shape(const IgShape& a, const IgShape& b)
 {
     return a.obs_dim == b.obs_dim && a.act_dim == b.act_dim && a.batch == b.batch && a.n_critics == b.n_critics && ig_same_net(a.value, b.value) &&
@@ -75,18 +70,8 @@ inline int ig_dense_launches(int Lv, int Lq, int Lp) { return 3 * (Lq + Lv) + 2 
 // (the rules every plan shares: group_plan_common.hpp)
 inline int ig_dw_chunks(int batch) { return gp_dw_chunks(batch); }
 inline unsigned ig_gather_chunks(uint64_t obs_bytes) { return gp_gather_chunks(obs_bytes); }
-inline uint64_t ig_arena_floats(const IgNet& n)
-{
-    uint64_t total = 0;
-    for (int i = 0; i < n.n_layers; ++i) total += (uint64_t)n.Kp[i] * n.Np[i] + n.Np[i];
-    return total;
-}
-inline unsigned ig_dw_tiles(const IgNet& n, int batch)
-{
-    unsigned dw = 0;
-    for (int i = 0; i < n.n_layers; ++i) dw += (unsigned)((n.Kp[i] / 32) * (n.Np[i] / 32) * ig_dw_chunks(batch));
-    return dw;
-}
+inline uint64_t ig_arena_floats(const IgNet& n) { return gp_arena_floats(n); }
+inline unsigned ig_dw_tiles(const IgNet& n, int batch) { return gp_dw_tiles(n, batch); }
 // k_iql_pack's grid (Iql::update): one thread per element of [B][obs + act], at most 2048 workgroups (the body strides by the grid)
 inline unsigned ig_pack_grid(const IgShape& s)
 {

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .awac import Awac
 from .bc import Bc
 from .dqn import Dqn, DqnConfig, record_keys
 from .iql import Iql
@@ -29,7 +30,7 @@ def raise_first(evaluators, status: int) -> None:
 
 
 GROUP_FORMS = {_lib.GROUP_FORM_ONE_WORKGROUP: "one_workgroup", _lib.GROUP_FORM_LAYERS: "layers", _lib.GROUP_FORM_BC_LAYERS: "bc_layers",
-               _lib.GROUP_FORM_IQL_LAYERS: "iql_layers"}
+               _lib.GROUP_FORM_IQL_LAYERS: "iql_layers", _lib.GROUP_FORM_AWAC_LAYERS: "awac_layers"}
 
 
 class DqnGroup:
@@ -371,7 +372,7 @@ def _group_train_offline(group, prefix: str, record_keys, buffers, max_opts, rec
 
 
 class _DenseGroup:
-    """What BcGroup and IqlGroup share: a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
+    """What BcGroup, IqlGroup and AwacGroup share: a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
     member, every launch serving all members (csrc/group_core.hpp through the kind's bdr_<kind>_group_* functions).  A subclass names
     the C prefix (_PREFIX), the member class (_MEMBER) and the keys of a member's Record (RECORD_KEYS)."""
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/group_core.hpp GroupCore::STEP_SLOTS)
@@ -416,7 +417,7 @@ class _DenseGroup:
         return self._g
 
     def info(self) -> dict:
-        """bdr_<kind>_group_info: {"form": "bc_layers" / "iql_layers", "n_members", "launches_per_round", "kernel_launches"}."""
+        """bdr_<kind>_group_info: {"form": "bc_layers" / "iql_layers" / "awac_layers", "n_members", "launches_per_round", "kernel_launches"}."""
         i = _lib.GroupInfoC()
         _lib.check(self._c("info")(self._g, C.byref(i)))
         return {"form": GROUP_FORMS[i.form], "n_members": i.n_members, "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
@@ -465,7 +466,7 @@ class _DenseGroup:
 
     def sample(self, rows, norm=None, members=None) -> list:
         """Policy::sample of the members in ONE launch (bdr_<kind>_group_sample): a list of float32 arrays [n, act_dim] in member
-        order, each with the bits of that member's own `sample_raw(rows[i], norm[i])` on either act path.  An IQL member acts in the
+        order, each with the bits of that member's own `sample_raw(rows[i], norm[i])` on either act path.  An IQL or AWAC member acts in the
         mode it is in (`set_train`) and at its own noise counter: in train mode it takes n * act_dim draws of its noise stream, in
         eval mode none, so group calls and the member's own calls continue one stream.
         rows: one array per member - float32 or float64, [n, obs_dim] (or [obs_dim]: n = 1), the same n for every member - or ONE
@@ -534,3 +535,21 @@ class IqlGroup(_DenseGroup):
     means what it meant) that the group owns - `IqlGroup.close()` closes them, `member.close()` on a live group is refused.  Results
     are bit for bit those of stepping the same agents one after the other."""
     _PREFIX, _MEMBER, RECORD_KEYS = "bdr_iql_group", Iql, ("loss_value", "loss_critic", "loss_actor")
+
+
+class AwacGroup(_DenseGroup):
+    """A set of AWAC agents of one shape whose Agent::opt (Awac::opt_, awac/base.rs:170-215) runs as the launch sequence of ONE member,
+    every launch serving all members (bdr_awac_group_*): 3 (Lp + Lq) + 8 launches per round for Lp, Lq layers of actor and critic,
+    whatever the number of members.  The members may differ in seed, inv_lambda, exp_adv_max, gamma, the critics' tau, adv_softmax,
+    critic_loss, the action limit, the log-std clamps, learning rates, optimizers and train / eval mode; their buffers are uniform
+    buffers of their own or views of one (`SimpleReplayBuffer.view`), so that P members hold one copy of a dataset.
+
+    A round draws noise inside the round (act_ and next_act): each member's mode (`set_train`) is read when the round is enqueued,
+    and in train mode the member takes 2 * batch_size * act_dim draws at its own noise counter - rounds, `sample` of the group and
+    the member's own `sample` / `update_on_batch` continue one stream.
+
+    A launch grouping, not an agent kind: the members are ordinary `Awac` objects (every `Awac` method keeps working on a member and
+    means what it meant) that the group owns - `AwacGroup.close()` closes them, `member.close()` on a live group is refused.  Results
+    are bit for bit those of stepping the same agents one after the other."""
+    _PREFIX, _MEMBER = "bdr_awac_group", Awac
+    RECORD_KEYS = ("loss_critic", "loss_actor", "q_tgt_abs_mean", "adv_mean", "adv_abs_mean", "logp_mean", "reward_mean", "next_q_mean")

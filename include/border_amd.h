@@ -507,6 +507,7 @@ BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr
 #define BDR_GROUP_FORM_LAYERS 1
 #define BDR_GROUP_FORM_BC_LAYERS 2   /* a bdr_bc_group (below): BC's launch sequence of one member, every launch serving all members */
 #define BDR_GROUP_FORM_IQL_LAYERS 3  /* a bdr_iql_group (below): IQL's launch sequence of one member, every launch serving all members */
+#define BDR_GROUP_FORM_AWAC_LAYERS 4 /* a bdr_awac_group (below): AWAC's launch sequence of one member, every launch serving all members */
 typedef struct { int32_t form; uint32_t n_members; uint32_t launches_per_round; uint32_t reserved; uint64_t kernel_launches; } bdr_group_info;
 BDR_API int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out);
 /* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
@@ -1502,6 +1503,47 @@ BDR_API int32_t bdr_iql_group_sample_members(bdr_iql_group* g, const uint32_t* m
 BDR_API void bdr_iql_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_iql_group* group);                                   /* evaluator/default_evaluator.rs:64-88 */
 BDR_API void bdr_iql_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_iql_group* group, bdr_replay* const* buffers);    /* trainer.rs:330-384 */
 BDR_API void bdr_iql_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_iql_group* group);                          /* trainer.rs:231-264 */
+
+/* A GROUP of AWAC agents (bdr_awac_create, above) over uniform rings (or views of one ring, bdr_replay_view_create): Awac::opt_
+ * (awac/base.rs:170-215) of every member in the launch sequence of ONE member - gather, pack, the actor on obs, the sample of act_, the
+ * online critics on (obs | act) and (obs | act_), update_actor, the updated actor on next_obs, the sample of next_act, the target
+ * critics, update_critic with the soft update: 3 (Lp + Lq) + 8 launches for Lp, Lq layers (n_units + 1) of actor and critic, whatever
+ * the number of members; the member index is one more grid dimension - bit for bit what bdr_agent_opt of the members one after the
+ * other gives.  The calls carry the semantics of their bdr_iql_group_* namesakes (ownership, ordering with the members' own calls,
+ * acting, the tables of the evaluator and the offline loop).
+ * Noise: a round draws INSIDE the round.  Each member's mode (bdr_agent_set_train) is read when the round is enqueued; in train mode
+ * the member takes batch_size * act_dim draws at its own noise counter for act_, then as many for next_act, in eval mode none - the
+ * rule of bdr_agent_opt.  Rounds, the group's acting calls, the member's own sample / sample_raw / update_on_batch and
+ * bdr_agent_draw_noise continue ONE stream, in any interleaving; members of one group may be in different modes.
+ * One value for all members: obs_dim, act_dim, both networks' units and activation_out, n_critics, batch_size, the device.  Free per
+ * member: seed, inv_lambda, exp_adv_max, gamma, critic_tau, adv_softmax, critic_loss, the action limit with its bounds and scale, the
+ * log-std clamps, both learning rates, optimizer kinds and scalars, train / eval mode.  Refused (BDR_ERR_INVALID, naming the first
+ * member concerned): a non-AWAC agent, another shape, n_critics > 2, n_critics x critic layers > 16, more than 12 reduce segments
+ * (the actor's head2 is one), n_updates_per_opt != 1, profiling or a gradient communicator switched on, another device, the same agent
+ * twice, an agent that is in a group already; more than 65535 members or a launch beyond the grid limits (naming the kernel).
+ * buffers[p] is member p's, as for bdr_iql_group_opt, with the same refusals; a refused call leaves every member's two step counters,
+ * n_opts, noise counter and stream position where they were.  _opt_with_scalars returns every member's record (the eight keys of
+ * bdr_agent_record_keys; cap_per_member >= 8) at out + p * cap_per_member.  _info fills bdr_group_info with form =
+ * BDR_GROUP_FORM_AWAC_LAYERS.  Not built: pushes through the group (the online side), n_updates_per_opt > 1, n_critics > 2, Mlp2
+ * actors, host-supplied noise rows. */
+typedef struct bdr_awac_group bdr_awac_group;
+BDR_API int32_t bdr_awac_group_create(bdr_agent* const* agents, uint32_t n, bdr_awac_group** out);   /* awac/base.rs:170-215 (opt_ of every member) */
+BDR_API int32_t bdr_awac_group_destroy(bdr_awac_group* g);                                           /* awac/base.rs:170-215 */
+BDR_API int32_t bdr_awac_group_size(const bdr_awac_group* g, uint32_t* n);                           /* awac/base.rs:170-215 */
+BDR_API int32_t bdr_awac_group_member(const bdr_awac_group* g, uint32_t i, bdr_agent** out);         /* awac/base.rs:170-215 */
+BDR_API int32_t bdr_awac_group_info(const bdr_awac_group* g, bdr_group_info* out);                   /* awac/base.rs:170-215 */
+BDR_API int32_t bdr_awac_group_opt(bdr_awac_group* g, bdr_replay* const* buffers);                   /* awac/base.rs:170-215 */
+BDR_API int32_t bdr_awac_group_opt_with_scalars(bdr_awac_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);   /* awac/base.rs:170-215, record :190-212 */
+BDR_API int32_t bdr_awac_group_sync(bdr_awac_group* g);                                              /* awac/base.rs:170-215 */
+BDR_API int32_t bdr_awac_group_sample(bdr_awac_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
+                                      const int32_t* dtypes, float* const* act_out);   /* awac/base.rs:228-233, util/actor.rs:226-241 */
+BDR_API int32_t bdr_awac_group_sample_members(bdr_awac_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms,
+                                              uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out);   /* awac/base.rs:228-233, util/actor.rs:226-241 */
+/* the tables of bdr_evaluate_bc_group and bdr_trainer_train_offline_group_post for an AWAC group, as bdr_iql_group_*_default (eight
+ * record keys; save_member writes actor, critic, critic.tgt) */
+BDR_API void bdr_awac_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_awac_group* group);                                   /* awac/base.rs:228-233, evaluator/default_evaluator.rs:64-88 */
+BDR_API void bdr_awac_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_awac_group* group, bdr_replay* const* buffers);    /* awac/base.rs:170-215, trainer.rs:330-384 */
+BDR_API void bdr_awac_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_awac_group* group);                          /* awac/base.rs:311-319, trainer.rs:231-264 */
 
 /* ------------------------------------------------------------------------------------------
  * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)
