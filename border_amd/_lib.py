@@ -209,6 +209,7 @@ SAVE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_char_p)
 # bdr_group_info (bdr_agent_group_info): the form of a group and its launch counts
 GROUP_FORM_ONE_WORKGROUP, GROUP_FORM_LAYERS, GROUP_FORM_BC_LAYERS, GROUP_FORM_IQL_LAYERS = 0, 1, 2, 3
 GROUP_FORM_AWAC_LAYERS = 4
+GROUP_FORM_CANDLE_SAC_LAYERS = 5
 
 
 class GroupInfoC(C.Structure):
@@ -360,6 +361,10 @@ ABI_SYMBOLS = [
     "bdr_awac_group_opt", "bdr_awac_group_opt_with_scalars", "bdr_awac_group_sync",
     "bdr_awac_group_sample", "bdr_awac_group_sample_members", "bdr_awac_group_eval_ops_default", "bdr_awac_group_trainer_ops_default",
     "bdr_awac_group_trainer_post_default",
+    "bdr_candle_sac_group_create", "bdr_candle_sac_group_destroy", "bdr_candle_sac_group_size", "bdr_candle_sac_group_member", "bdr_candle_sac_group_info",
+    "bdr_candle_sac_group_opt", "bdr_candle_sac_group_opt_with_scalars", "bdr_candle_sac_group_sync",
+    "bdr_candle_sac_group_sample", "bdr_candle_sac_group_sample_members", "bdr_candle_sac_group_eval_ops_default", "bdr_candle_sac_group_trainer_ops_default",
+    "bdr_candle_sac_group_trainer_post_default",
 ]
 
 _lib = None
@@ -390,7 +395,8 @@ def lib() -> C.CDLL:
                         "bdr_group_trainer_ops_default", "bdr_group_eval_ops_default", "bdr_group_trainer_post_default",
                         "bdr_bc_group_eval_ops_default", "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default",
                         "bdr_iql_group_eval_ops_default", "bdr_iql_group_trainer_ops_default", "bdr_iql_group_trainer_post_default",
-                        "bdr_awac_group_eval_ops_default", "bdr_awac_group_trainer_ops_default", "bdr_awac_group_trainer_post_default"):
+                        "bdr_awac_group_eval_ops_default", "bdr_awac_group_trainer_ops_default", "bdr_awac_group_trainer_post_default",
+                        "bdr_candle_sac_group_eval_ops_default", "bdr_candle_sac_group_trainer_ops_default", "bdr_candle_sac_group_trainer_post_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -603,6 +609,22 @@ def lib() -> C.CDLL:
     L.bdr_awac_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
     L.bdr_awac_group_trainer_post_default.restype = None
     L.bdr_awac_group_trainer_post_default.argtypes = [C.POINTER(BcGroupTrainerPostC), vp]
+    L.bdr_candle_sac_group_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_candle_sac_group_destroy.argtypes = [vp]
+    L.bdr_candle_sac_group_size.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.bdr_candle_sac_group_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_candle_sac_group_info.argtypes = [vp, C.POINTER(GroupInfoC)]
+    L.bdr_candle_sac_group_opt.argtypes = [vp, vp]
+    L.bdr_candle_sac_group_opt_with_scalars.argtypes = [vp, vp, vp, i32, vp]
+    L.bdr_candle_sac_group_sync.argtypes = [vp]
+    L.bdr_candle_sac_group_sample.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.bdr_candle_sac_group_sample_members.argtypes = [vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
+    L.bdr_candle_sac_group_eval_ops_default.restype = None
+    L.bdr_candle_sac_group_eval_ops_default.argtypes = [C.POINTER(BcGroupEvalOps), vp]
+    L.bdr_candle_sac_group_trainer_ops_default.restype = None
+    L.bdr_candle_sac_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
+    L.bdr_candle_sac_group_trainer_post_default.restype = None
+    L.bdr_candle_sac_group_trainer_post_default.argtypes = [C.POINTER(BcGroupTrainerPostC), vp]
     L.bdr_trainer_train_offline_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(GroupTrainerOps), C.POINTER(BcGroupTrainerPostC),
                                                        GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     _lib = L

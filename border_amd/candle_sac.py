@@ -90,6 +90,11 @@ class CandleSac(CandleAgent):
     def _model_id(self, name: str) -> int:
         return 1 + 2 * self.n_critics if name == "log_alpha" else super()._model_id(name)
 
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.check(_lib.lib().bdr_agent_destroy(self._h))   # (refused for a member of a live CandleSacGroup: the group owns it)
+            self._h = None
+
     def update_on_batch(self, obs, act, next_obs, reward, is_terminated, is_truncated, z_pi=None, z_next=None) -> dict:
         """One Sac::opt_ iteration.  z_pi / z_next: [n, act_dim] N(0,1) draws for a and next_a in train mode (None: the agent's
         device stream)."""

@@ -86,11 +86,7 @@ template <int NET>
 __global__ __launch_bounds__(256) void k_awac_reduce_adam_group(const BDR_CONST_AS ReduceAdamArgs* args, const BDR_CONST_AS AwacStep* steps, unsigned* ticket,
                                                                 unsigned* seq_host, unsigned seq)
 {
-    const BDR_CONST_AS AdamScalars& s = steps[blockIdx.y].adam[NET];
-    AdamScalars d;   // field by field: static indices, registers
-    d.b1 = s.b1; d.omb1 = s.omb1; d.b2 = s.b2; d.omb2 = s.omb2; d.sqrt_bc2 = s.sqrt_bc2; d.eps = s.eps; d.neg_step = s.neg_step; d.wd_mul = s.wd_mul;
-    dense_reduce_adam_body(args[blockIdx.y], (int)blockIdx.z, d, NET == AG_NET_CRITIC ? 1 : 0, 0);
-    if constexpr (NET == AG_NET_CRITIC) bg_group_done(ticket, seq_host, seq);
+    dg_reduce_adam_step<NET, NET == AG_NET_CRITIC>(args, steps, ticket, seq_host, seq);   // (dense_group.hpp: shared with the candle SAC group)
 }
 
 AgShape awac_shape(const Awac* m)

@@ -10,8 +10,12 @@
 //   Bits.  Same body, same tile order, same element code as the member's own k_dense_act; element t = (m0 + rr) * A + j of the member's
 //   own call draws at counter + t, so with `counter` = the member's noise counter the actions are those of its own
 //   bdr_agent_sample_raw in the mode it is in, at the counter it is at.  Members of one call may be in different modes.
-//   Mlp2 actors.  The operand cur[rr * ldz + A + j] is the shared expression of the body; no group hands this entry an Mlp2 actor yet
-//   (the host writes mlp2 = 0), so that form is not reached under a group and nothing is claimed for it.
+//   Mlp2 actors (candle_sac_group.hpp hands this entry members whose actor is one: the host writes the member's own form, mlp2 = 1 and
+//   a null head2, which the element code does not read in that form).  The last layer is [mean | s] of logical width 2 A, padded to
+//   Np = pad64(2 A) >= 2 A, and the epilogue reads s at cur[rr * ldz + A + j] with rr < rows_here <= 32, j < A, so A + j < 2 A <= Np <
+//   ldz = Np + 4: inside row rr of the [32][Np + 4] buffer.  LDS is sized by W = the widest padded layer of the member (act_width:
+//   the maximum of every layer's Kp and Np, the last layer's pad64(2 A) included), two [32][W + 4] buffers, so ldz <= W + 4 and the
+//   rows fit; the host refuses W > DA_MAX_W before anything is enqueued.  IQL and AWAC members are Mlp3 actors and still get mlp2 = 0.
 //   The end.  An acting call is synchronous: every thread's result stores are fenced at system scope, then the launch counts its
 //   workgroups on the group's ticket and publishes its launch number (bg_group_done); the host waits for that number before it reads
 //   the results.  Stores are plain vector stores.
@@ -22,7 +26,7 @@
 //   member's staged block of n * O elements, out is written at t = (m0 + r) * A + j < n * A inside the member's block of n * A floats,
 //   head2 is read at j < A of the member's actor arena, the draw index counter + t is a 64-bit sum.
 //   The host half.  CandleActKind<M> below is what group_act.hpp's call needs of a kind, written once over the CandleAgent member M
-//   (candle_actor.hpp: Iql, Awac).
+//   (candle_actor.hpp: Iql, Awac, CandleSac).
 #pragma once
 #include "group_done.hpp"
 #include "group_act.hpp"
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(256 * TEAMS) void k_candle_act_group(const BDR_CONS
 
 // ---- group acting of CandleAgent members: group_act.hpp's call with what is a Gaussian actor's ----------------------------------------
 // Static, keyed on the actor arena: the actor net pn on pi_p, DA_CANDLE, and the static half of CandleAgent::sample_elem from the
-// member's config (no group holds an Mlp2 actor: mlp2 = 0).  Per call: the member's mode, read now (bdr_agent_set_train), and in train
+// member's config and actor form (Mlp3 for IQL and AWAC members: mlp2 = 0; a candle SAC member may be Mlp2).  Per call: the member's mode, read now (bdr_agent_set_train), and in train
 // mode its noise counter, which advances by the n * A draws the call takes - sample_elem's rule, so group calls, group rounds that draw
 // (awac_group.hpp), the member's own sample / sample_raw on either act path and bdr_agent_noise continue one stream in any
 // interleaving.  The call does not go through ensure_batch and does not touch a member's samp: results go to the group's pinned area.
@@ -62,7 +66,7 @@ struct CandleActKind : GroupActEntry<CandleActCall, k_candle_act_group<1>, k_can
         for (int l = 0; l < a.nl; ++l) a.L[l] = DenseActLayer{m->pi_p + pn.L[l].w, m->pi_p + pn.L[l].b, pn.L[l].Kp, pn.L[l].Np, pn.L[l].relu};
         a.mode = DA_CANDLE;
         SampleElem& e = a.e;   // train, counter and z are the call's
-        e.head2 = m->pi_p + m->h2_off; e.mlp2 = 0;
+        e.mlp2 = m->mlp2() ? 1 : 0; e.head2 = e.mlp2 ? nullptr : m->pi_p + m->h2_off;   // the member's actor form; Mlp2 has no head2
         e.lo = (float)m->cfg.min_log_std; e.hi = (float)m->cfg.max_log_std; e.tanh_limit = m->cfg.action_limit == BDR_ACTION_LIMIT_TANH ? 1 : 0;
         e.amin = (float)m->cfg.action_min; e.amax = (float)m->cfg.action_max; e.scale = (float)m->cfg.action_scale;
         e.seed = m->cfg.seed;

@@ -32,7 +32,10 @@ namespace {
 // the observation columns of (obs | a) and (next_obs | next_a), whose action columns k_csac_sample_logp fills.
 // Bounds: t < B (O + A); row b < B, column c < O + A <= ldq; c < O <= ldp for the actor inputs.
 struct CsacPackArgs { const float* obs; const float* next; const float* act; int O, A, B; float* x_o; float* x_no; int ldp; float* xq; float* xq_pi; float* xq_next; int ldq; };
-__global__ __launch_bounds__(256) void k_csac_pack(CsacPackArgs p)
+// (the bodies of the six kernels are functions over their argument struct: the kernel argument, or a member's entry of a device array
+// read in place - candle_sac_group.hpp, where blockIdx.y is the member; `red` is the kernel's own 32 floats of LDS)
+template <class Args>
+__device__ __forceinline__ void csac_pack_body(const Args& p)
 {
     const int W = p.O + p.A;
     const size_t n = (size_t)p.B * W;
@@ -50,6 +53,7 @@ __global__ __launch_bounds__(256) void k_csac_pack(CsacPackArgs p)
         }
     }
 }
+__global__ __launch_bounds__(256) void k_csac_pack(CsacPackArgs p) { csac_pack_body(p); }
 
 // GaussianActor::sample then ::logp of the sampled action (util/actor.rs:196-241).  A row belongs to a group of G lanes (G a power
 // of two <= 64, the smallest that holds A, chosen by the host): lane g of the group takes the columns g, g + G, ... in order, and the
@@ -72,7 +76,9 @@ struct CsacSampleArgs {
     float* logp;                                       // [B]
     float* g_lpm; float* g_lpl; float* g_am; float* g_al;   // [B][A], or all null
 };
-__global__ __launch_bounds__(256) void k_csac_sample_logp(CsacSampleArgs p)
+// (train, counter and z are handed in beside the struct: under a group they are the member's step words, z null)
+template <class Args>
+__device__ __forceinline__ void csac_sample_logp_body(const Args& p, int train, uint64_t counter, const float* zrows)
 {
 #pragma clang fp contract(off)
     const int b = blockIdx.x * (256 / p.G) + (int)threadIdx.x / p.G;
@@ -86,8 +92,8 @@ __global__ __launch_bounds__(256) void k_csac_sample_logp(CsacSampleArgs p)
         const float l = p.mlp2 ? expf(row[p.A + j]) : p.head2[j];
         const float sd = expf(fminf(fmaxf(l, p.lo), p.hi));
         float z = 0.f, u = m;
-        if (p.train) {
-            z = p.z ? p.z[t] : candle::randn_at(p.seed, p.counter, t);
+        if (train) {
+            z = zrows ? zrows[t] : candle::randn_at(p.seed, counter, t);
             const float e = sd * z;
             u = e + m;
         }
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(256) void k_csac_sample_logp(CsacSampleArgs p)
             const float e_m = d / var;                               // the explicit dN/dm
             const float e_sd = (d * d) / (var * sd) - 1.0f / sd;     // the explicit dN/dsd
             const float dlp_da = dlj_da - e_m * dx_da;
-            const float da_dsd = p.train ? da_du * z : 0.f;
+            const float da_dsd = train ? da_du * z : 0.f;
             const float cm = (l >= p.lo && l <= p.hi) ? 1.f : 0.f;   // the log-std clamp, closed range
             const float chain = p.mlp2 ? (sd * cm) * l : sd * cm;    // dsd / d(head2 | s)
             p.g_lpm[t] = e_m + dlp_da * da_du;
@@ -131,15 +137,17 @@ __global__ __launch_bounds__(256) void k_csac_sample_logp(CsacSampleArgs p)
     for (int off = p.G >> 1; off > 0; off >>= 1) { lp += __shfl_xor(lp, off); lj += __shfl_xor(lj, off); }
     if (live && g0 == 0) p.logp[b] = p.tanh_limit ? lp - lj : lp;
 }
+__global__ __launch_bounds__(256) void k_csac_sample_logp(CsacSampleArgs p) { csac_sample_logp_body(p, p.train, p.counter, p.z); }
 
 // EntCoef::update (sac/ent_coef.rs:71-84) and ::alpha (:59-61).  ent: [0] log_alpha, [1] its gradient, [2] exp_avg, [3] exp_avg_sq,
 // [4] alpha.  Auto: loss = mean_b(-log_alpha (logp_b + target_entropy)), so the gradient is -(1/B) sum_b (logp_b + target_entropy),
 // and one AdamW step (adam_element, the dense agents' formula).  Fix: log_alpha stays.  alpha = expf(log_alpha) in both.
 // One workgroup.  Bounds: b < B in row_sum; ent holds 8 floats.
 struct CsacAlphaArgs { const float* logp; int B; float target_entropy; int auto_mode; AdamScalars s; float* ent; };
-__global__ __launch_bounds__(1024) void k_csac_alpha(CsacAlphaArgs p)
+// (s: the AdamW scalars of this step - the struct's, or under a group the member's step words)
+template <class Args>
+__device__ __forceinline__ void csac_alpha_body(const Args& p, const AdamScalars& s, float* red)
 {
-    __shared__ float red[32];
     float sum = 0.f;
     if (p.auto_mode) sum = candle::row_sum(p.B, [&](int b) {
 #pragma clang fp contract(off)
@@ -150,17 +158,23 @@ __global__ __launch_bounds__(1024) void k_csac_alpha(CsacAlphaArgs p)
     if (p.auto_mode) {
         const float g = -(sum / (float)p.B);
         float m = p.ent[2], v = p.ent[3];
-        adam_element(la, g, m, v, p.s);
+        adam_element(la, g, m, v, s);
         p.ent[0] = la; p.ent[1] = g; p.ent[2] = m; p.ent[3] = v;
     }
     p.ent[4] = expf(la);
+}
+__global__ __launch_bounds__(1024) void k_csac_alpha(CsacAlphaArgs p)
+{
+    __shared__ float red[32];
+    csac_alpha_body(p, p.s, red);
 }
 
 // qvals_min (util/critic.rs:197-202) on (obs, a) and the output gradient of d(-q/B)/dQ_i: candle's reduce-min backward is an
 // equality mask, so EVERY critic whose value equals the minimum receives the gradient (identical critics: their sum), masked by
 // the output ReLU when the critic Mlp has one.  Bounds: b < B; column 0 of [B][ldq] rows.
 struct CsacQminArgs { const float* q[4]; float* dq[4]; int ldq; int NC; int relu_out; float* q_min; int B; };
-__global__ __launch_bounds__(256) void k_csac_qmin(CsacQminArgs p)
+template <class Args>
+__device__ __forceinline__ void csac_qmin_body(const Args& p)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= p.B) return;
@@ -173,6 +187,7 @@ __global__ __launch_bounds__(256) void k_csac_qmin(CsacQminArgs p)
         p.dq[i][(size_t)b * p.ldq] = (qi == mn && !(p.relu_out && !(qi > 0.f))) ? g : 0.f;
     }
 }
+__global__ __launch_bounds__(256) void k_csac_qmin(CsacQminArgs p) { csac_qmin_body(p); }
 
 // update_actor's loss and output gradient (sac/base.rs:104-122): L = mean_b(alpha logp_b - q_b).  With G_bj = sum_i d(-q/B)/da_bj
 // (the critics' input gradients dxa_i, action columns, added in critic order):
@@ -187,9 +202,9 @@ struct CsacActorArgs {
     float* gout; int ldm; float* gh2; float* dq_da;
     float* scal; int accumulate;
 };
-__global__ __launch_bounds__(1024) void k_csac_actor_grad(CsacActorArgs p)
+template <class Args>
+__device__ __forceinline__ void csac_actor_grad_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     const float invB = 1.0f / (float)p.B;
     const float alpha = p.ent[4];
     const int j = blockIdx.x;
@@ -217,6 +232,11 @@ __global__ __launch_bounds__(1024) void k_csac_actor_grad(CsacActorArgs p)
     }, red);
     if (threadIdx.x == 0) p.scal[1] = candle::acc(p.accumulate ? p.scal[1] : 0.f, s, invB);
 }
+__global__ __launch_bounds__(1024) void k_csac_actor_grad(CsacActorArgs p)
+{
+    __shared__ float red[32];
+    csac_actor_grad_body(p, red);
+}
 
 // update_critic (sac/base.rs:63-102): next_q = min_i Qtgt_i(next_obs, next_a) - alpha next_logp, tgt = r + gamma_not_done next_q with
 // gamma_not_done = (1 - is_terminated) gamma in f32 (is_truncated ignored); loss = mean_i mean_b loss(Q_i - tgt), MSE or smooth L1
@@ -227,9 +247,9 @@ struct CsacCriticArgs {
     const float* reward; const int8_t* term; float gamma; const float* ent; const float* next_logp;
     float* tgt; int loss_kind; float* scal; int accumulate; int B;
 };
-__global__ __launch_bounds__(1024) void k_csac_critic_loss(CsacCriticArgs p)
+template <class Args>
+__device__ __forceinline__ void csac_critic_loss_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     const float invB = 1.0f / (float)p.B, invNC = 1.0f / (float)p.NC;
     const float alpha = p.ent[4];
     float total = 0.f;
@@ -259,6 +279,11 @@ __global__ __launch_bounds__(1024) void k_csac_critic_loss(CsacCriticArgs p)
         p.scal[0] = (p.accumulate ? p.scal[0] : 0.f) + total * invNC;
         p.scal[2] = alpha;
     }
+}
+__global__ __launch_bounds__(1024) void k_csac_critic_loss(CsacCriticArgs p)
+{
+    __shared__ float red[32];
+    csac_critic_loss_body(p, red);
 }
 
 }  // namespace
@@ -537,3 +562,6 @@ int32_t bdr_candle_sac_sample_device(bdr_agent* base, uint64_t n, const void* ob
 }
 
 }  // extern "C"
+
+// the launch grouping of candle SAC agents (bdr_candle_sac_group_*): it needs CandleSac and the kernel bodies above
+#include "candle_sac_group.hpp"

@@ -33,7 +33,28 @@ __global__ __launch_bounds__(256) void k_dense_small_members_z(const BDR_CONST_A
 // the grouped weight gradient of every member: grid (the member's own dW tiles - all jobs of all its instances -, P)
 __global__ __launch_bounds__(256) void k_dense_dw_small_members(const BDR_CONST_AS DenseDwSmallGroup* args) { dense_dw_small_group_body(args[blockIdx.y]); }
 
-// ---- host: one member's entries of the launches of one network (iql_group.hpp, awac_group.hpp) -----------------------------------------
+// a member's optimizer scalars of this step out of its staging slot: field by field (static indices, registers)
+__device__ __forceinline__ AdamScalars dg_step_scalars(const BDR_CONST_AS AdamScalars& s)
+{
+    AdamScalars d;
+    d.b1 = s.b1; d.omb1 = s.omb1; d.b2 = s.b2; d.omb2 = s.omb2; d.sqrt_bc2 = s.sqrt_bc2; d.eps = s.eps; d.neg_step = s.neg_step; d.wd_mul = s.wd_mul;
+    return d;
+}
+// The body of a kind's reduce + Adam entry (awac_group.hpp, candle_sac_group.hpp), written once over the kind's per-step words: network
+// NET of every member, instance z = blockIdx.z, the optimizer scalars from adam[NET] of the member's slot.  TRACK_LAST: the network
+// tracks its targets at the member's own tau (a.tau / a.omt of its entry) and its launch is the last reader of the slot, which
+// publishes (bg_group_done, behind a barrier every thread reaches: dense_reduce_adam_body returns to here, not out of the kernel).
+// NET < the length of Step::adam is the kind's static_assert; member and z are bounded as above.
+template <int NET, bool TRACK_LAST, class Step>
+__device__ __forceinline__ void dg_reduce_adam_step(const BDR_CONST_AS ReduceAdamArgs* args, const BDR_CONST_AS Step* steps, unsigned* ticket, unsigned* seq_host,
+                                                    unsigned seq)
+{
+    const AdamScalars d = dg_step_scalars(steps[blockIdx.y].adam[NET]);
+    dense_reduce_adam_body(args[blockIdx.y], (int)blockIdx.z, d, TRACK_LAST ? 1 : 0, 0);
+    if constexpr (TRACK_LAST) bg_group_done(ticket, seq_host, seq);
+}
+
+// ---- host: one member's entries of the launches of one network (iql_group.hpp, awac_group.hpp, candle_sac_group.hpp) --------------------
 // a network as the kinds' plan headers read it (group_plan_common.hpp)
 inline GpNet dg_net_shape(const MlpLayout& net, int activation_out)
 {

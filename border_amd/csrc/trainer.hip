@@ -28,6 +28,7 @@ namespace bdr {
 int bc_group_act_dim(const void* group, uint32_t member);    // bc.hip (bc_group.hpp), iql.hip (iql_group.hpp): group_core.hpp's group_act_dim of the kind
 int iql_group_act_dim(const void* group, uint32_t member);
 int awac_group_act_dim(const void* group, uint32_t member);   // awac.hip (awac_group.hpp)
+int candle_sac_group_act_dim(const void* group, uint32_t member);   // candle_sac.hip (candle_sac_group.hpp)
 }
 
 namespace {
@@ -301,6 +302,8 @@ using IqlGroupEntries =
     GroupEntries<bdr_iql_group, bdr_iql_group_size, bdr_iql_group_member, bdr_iql_group_opt, bdr_iql_group_opt_with_scalars, bdr_iql_group_sample_members>;
 using AwacGroupEntries =
     GroupEntries<bdr_awac_group, bdr_awac_group_size, bdr_awac_group_member, bdr_awac_group_opt, bdr_awac_group_opt_with_scalars, bdr_awac_group_sample_members>;
+using CandleSacGroupEntries = GroupEntries<bdr_candle_sac_group, bdr_candle_sac_group_size, bdr_candle_sac_group_member, bdr_candle_sac_group_opt,
+                                           bdr_candle_sac_group_opt_with_scalars, bdr_candle_sac_group_sample_members>;
 // the kinds a default evaluation table can name: its acting entry, the action width of a member, the kind in messages, its save
 struct GroupKindRow {
     decltype(bdr_bc_group_eval_ops::sample_members) sample_members;
@@ -312,7 +315,8 @@ const GroupKindRow* group_kind_of(const bdr_bc_group_eval_ops* ops)
 {
     static const GroupKindRow kinds[] = {{BcGroupEntries::sample_members, bc_group_act_dim, "a BC", BcGroupEntries::save_member},
                                          {IqlGroupEntries::sample_members, iql_group_act_dim, "an IQL", IqlGroupEntries::save_member},
-                                         {AwacGroupEntries::sample_members, awac_group_act_dim, "an AWAC", AwacGroupEntries::save_member}};
+                                         {AwacGroupEntries::sample_members, awac_group_act_dim, "an AWAC", AwacGroupEntries::save_member},
+                                         {CandleSacGroupEntries::sample_members, candle_sac_group_act_dim, "a candle SAC", CandleSacGroupEntries::save_member}};
     for (const GroupKindRow& k : kinds) if (ops && ops->sample_members == k.sample_members) return &k;
     return nullptr;
 }
@@ -630,6 +634,7 @@ int32_t bdr_evaluate_group(const bdr_evaluator* evs, const bdr_group_eval_ops* o
 void bdr_bc_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_bc_group* group) { BcGroupEntries::eval_ops(ops, group); }
 void bdr_iql_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_iql_group* group) { IqlGroupEntries::eval_ops(ops, group); }
 void bdr_awac_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_awac_group* group) { AwacGroupEntries::eval_ops(ops, group); }
+void bdr_candle_sac_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_candle_sac_group* group) { CandleSacGroupEntries::eval_ops(ops, group); }
 
 // the same loop for a BC or an IQL group: f32 action rows, f32 or float64 observation rows, a normaliser per member
 int32_t bdr_evaluate_bc_group(const bdr_evaluator* evs, const bdr_bc_group_eval_ops* ops, bdr_eval_result* out)
@@ -662,6 +667,11 @@ void bdr_awac_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_awac_gro
     AwacGroupEntries::trainer_ops(ops, group, buffers);
 }
 void bdr_awac_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_awac_group* group) { AwacGroupEntries::trainer_post(post, group); }
+void bdr_candle_sac_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_candle_sac_group* group, bdr_replay* const* buffers)
+{
+    CandleSacGroupEntries::trainer_ops(ops, group, buffers);
+}
+void bdr_candle_sac_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_candle_sac_group* group) { CandleSacGroupEntries::trainer_post(post, group); }
 
 // Trainer::train_offline (trainer.rs:330-384) with post_process for every member of a group (BC or IQL) in lockstep
 int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, const bdr_group_trainer_ops* ops, const bdr_bc_group_trainer_post* post,

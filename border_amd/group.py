@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from .awac import Awac
 from .bc import Bc
+from .candle_sac import CandleSac
 from .dqn import Dqn, DqnConfig, record_keys
 from .iql import Iql
 
@@ -30,7 +31,8 @@ def raise_first(evaluators, status: int) -> None:
 
 
 GROUP_FORMS = {_lib.GROUP_FORM_ONE_WORKGROUP: "one_workgroup", _lib.GROUP_FORM_LAYERS: "layers", _lib.GROUP_FORM_BC_LAYERS: "bc_layers",
-               _lib.GROUP_FORM_IQL_LAYERS: "iql_layers", _lib.GROUP_FORM_AWAC_LAYERS: "awac_layers"}
+               _lib.GROUP_FORM_IQL_LAYERS: "iql_layers", _lib.GROUP_FORM_AWAC_LAYERS: "awac_layers",
+               _lib.GROUP_FORM_CANDLE_SAC_LAYERS: "candle_sac_layers"}
 
 
 class DqnGroup:
@@ -372,7 +374,7 @@ def _group_train_offline(group, prefix: str, record_keys, buffers, max_opts, rec
 
 
 class _DenseGroup:
-    """What BcGroup, IqlGroup and AwacGroup share: a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
+    """What BcGroup, IqlGroup, AwacGroup and CandleSacGroup share: a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
     member, every launch serving all members (csrc/group_core.hpp through the kind's bdr_<kind>_group_* functions).  A subclass names
     the C prefix (_PREFIX), the member class (_MEMBER) and the keys of a member's Record (RECORD_KEYS)."""
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/group_core.hpp GroupCore::STEP_SLOTS)
@@ -417,7 +419,7 @@ class _DenseGroup:
         return self._g
 
     def info(self) -> dict:
-        """bdr_<kind>_group_info: {"form": "bc_layers" / "iql_layers" / "awac_layers", "n_members", "launches_per_round", "kernel_launches"}."""
+        """bdr_<kind>_group_info: {"form": "bc_layers" / "iql_layers" / "awac_layers" / "candle_sac_layers", "n_members", "launches_per_round", "kernel_launches"}."""
         i = _lib.GroupInfoC()
         _lib.check(self._c("info")(self._g, C.byref(i)))
         return {"form": GROUP_FORMS[i.form], "n_members": i.n_members, "launches_per_round": i.launches_per_round, "kernel_launches": i.kernel_launches}
@@ -553,3 +555,24 @@ class AwacGroup(_DenseGroup):
     are bit for bit those of stepping the same agents one after the other."""
     _PREFIX, _MEMBER = "bdr_awac_group", Awac
     RECORD_KEYS = ("loss_critic", "loss_actor", "q_tgt_abs_mean", "adv_mean", "adv_abs_mean", "logp_mean", "reward_mean", "next_q_mean")
+
+
+class CandleSacGroup(_DenseGroup):
+    """A set of candle SAC agents of one shape whose Agent::opt (Sac::opt_, sac/base.rs:124-134) runs as the launch sequence of ONE
+    member, every launch serving all members (bdr_candle_sac_group_*): 3 Lp + 4 Lq + 10 launches per round for Lp, Lq layers of actor
+    and critic (31 at an Mlp2 [h, h] actor and twin [h, h] critics), whatever the number of members.  One value for all members:
+    obs_dim, act_dim, both networks' units and activation_out, the actor kind (Mlp2 or Mlp3), n_critics, batch_size.  The members may
+    differ in seed, gamma, the critics' tau, critic_loss, the entropy mode (Fix(alpha) or Auto(target_entropy, lr)), the action limit,
+    the log-std clamps, learning rates, optimizers and train / eval mode; their buffers are uniform buffers of their own or views of
+    one (`SimpleReplayBuffer.view`).
+
+    The members are online agents: each pushes into its own buffer (`rb.push`) between rounds; the ring may grow and wrap.  A round
+    draws noise inside the round (a and next_a): each member's mode (`set_train`) is read when the round is enqueued, and in train
+    mode the member takes 2 * batch_size * act_dim draws at its own noise counter - rounds, `sample` of the group and the member's own
+    `sample` / `update_on_batch` continue one stream.
+
+    A launch grouping, not an agent kind: the members are ordinary `CandleSac` objects (every `CandleSac` method keeps working on a
+    member and means what it meant) that the group owns - `CandleSacGroup.close()` closes them, `member.close()` on a live group is
+    refused.  Results are bit for bit those of stepping the same agents one after the other."""
+    _PREFIX, _MEMBER = "bdr_candle_sac_group", CandleSac
+    RECORD_KEYS = ("loss_critic", "loss_actor", "ent_coef")

@@ -508,6 +508,7 @@ BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr
 #define BDR_GROUP_FORM_BC_LAYERS 2   /* a bdr_bc_group (below): BC's launch sequence of one member, every launch serving all members */
 #define BDR_GROUP_FORM_IQL_LAYERS 3  /* a bdr_iql_group (below): IQL's launch sequence of one member, every launch serving all members */
 #define BDR_GROUP_FORM_AWAC_LAYERS 4 /* a bdr_awac_group (below): AWAC's launch sequence of one member, every launch serving all members */
+#define BDR_GROUP_FORM_CANDLE_SAC_LAYERS 5 /* a bdr_candle_sac_group (below): the candle SAC's launch sequence of one member, every launch serving all members */
 typedef struct { int32_t form; uint32_t n_members; uint32_t launches_per_round; uint32_t reserved; uint64_t kernel_launches; } bdr_group_info;
 BDR_API int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out);
 /* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
@@ -1544,6 +1545,48 @@ BDR_API int32_t bdr_awac_group_sample_members(bdr_awac_group* g, const uint32_t*
 BDR_API void bdr_awac_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_awac_group* group);                                   /* awac/base.rs:228-233, evaluator/default_evaluator.rs:64-88 */
 BDR_API void bdr_awac_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_awac_group* group, bdr_replay* const* buffers);    /* awac/base.rs:170-215, trainer.rs:330-384 */
 BDR_API void bdr_awac_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_awac_group* group);                          /* awac/base.rs:311-319, trainer.rs:231-264 */
+
+/* A GROUP of candle SAC agents (bdr_candle_sac_create, above) over uniform rings (or views of one ring, bdr_replay_view_create):
+ * Sac::opt_ (sac/base.rs:124-134) of every member in the launch sequence of ONE member - gather, pack, the actor on obs, sample + logp
+ * of a, the entropy coefficient's step, the online critics on (obs | act) and (obs | a), qmin, the critics' input gradients down to
+ * dq/da, update_actor, the updated actor on next_obs, sample + logp of next_a, the target critics, update_critic with the soft update:
+ * 3 Lp + 4 Lq + 10 launches for Lp, Lq layers (n_units + 1) of actor and critic, whatever the number of members; the member index is
+ * one more grid dimension - bit for bit what bdr_agent_opt of the members one after the other gives.  The calls carry the semantics
+ * of their bdr_iql_group_* namesakes (ownership, ordering with the members' own calls, acting, the tables of the evaluator and the
+ * offline loop).  The members are online agents: each pushes into its own ring (bdr_replay_push) between rounds.
+ * Noise: as for a bdr_awac_group - each member's mode is read when the round is enqueued; in train mode the member takes batch_size *
+ * act_dim draws at its own noise counter for a, then as many for next_a, in eval mode none.  Rounds, the group's acting calls, the
+ * member's own sample / sample_raw / update_on_batch and bdr_agent_draw_noise continue ONE stream, in any interleaving.
+ * One value for all members: obs_dim, act_dim, both networks' units and activation_out, actor_kind (Mlp2 or Mlp3), n_critics,
+ * batch_size, the device.  Free per member: seed, gamma, critic_tau, critic_loss, the entropy mode (Fix(alpha) or Auto(target_entropy,
+ * lr)), the action limit with its bounds and scale, the log-std clamps, both learning rates, optimizer kinds and scalars, train /
+ * eval mode.  Refused (BDR_ERR_INVALID, naming the first member concerned): a non-candle_sac agent, another shape or actor kind,
+ * n_critics > 2, n_critics x critic layers > 16, more than 12 reduce segments (an Mlp3 actor's head2 is one), n_updates_per_opt != 1,
+ * profiling or a gradient communicator switched on, another device, the same agent twice, an agent that is in a group already; more
+ * than 65535 members or a launch beyond the grid limits (naming the kernel).
+ * buffers[p] is member p's, as for bdr_iql_group_opt, with the same refusals; a refused call leaves every member's three step
+ * counters, n_opts, noise counter and stream position where they were.  _opt_with_scalars returns every member's record (the three
+ * keys of bdr_agent_record_keys; cap_per_member >= 3) at out + p * cap_per_member.  _info fills bdr_group_info with form =
+ * BDR_GROUP_FORM_CANDLE_SAC_LAYERS.  Not built: pushes through the group and a compiled online loop, n_updates_per_opt > 1,
+ * n_critics > 2, host-supplied noise rows, a captured graph of the round. */
+typedef struct bdr_candle_sac_group bdr_candle_sac_group;
+BDR_API int32_t bdr_candle_sac_group_create(bdr_agent* const* agents, uint32_t n, bdr_candle_sac_group** out);   /* sac/base.rs:124-134 (opt_ of every member) */
+BDR_API int32_t bdr_candle_sac_group_destroy(bdr_candle_sac_group* g);                                           /* sac/base.rs:124-134 */
+BDR_API int32_t bdr_candle_sac_group_size(const bdr_candle_sac_group* g, uint32_t* n);                           /* sac/base.rs:124-134 */
+BDR_API int32_t bdr_candle_sac_group_member(const bdr_candle_sac_group* g, uint32_t i, bdr_agent** out);         /* sac/base.rs:124-134 */
+BDR_API int32_t bdr_candle_sac_group_info(const bdr_candle_sac_group* g, bdr_group_info* out);                   /* sac/base.rs:124-134 */
+BDR_API int32_t bdr_candle_sac_group_opt(bdr_candle_sac_group* g, bdr_replay* const* buffers);                   /* sac/base.rs:124-134 */
+BDR_API int32_t bdr_candle_sac_group_opt_with_scalars(bdr_candle_sac_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);   /* sac/base.rs:124-134, record :136-146 */
+BDR_API int32_t bdr_candle_sac_group_sync(bdr_candle_sac_group* g);                                              /* sac/base.rs:124-134 */
+BDR_API int32_t bdr_candle_sac_group_sample(bdr_candle_sac_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
+                                            const int32_t* dtypes, float* const* act_out);   /* sac/base.rs:162-167, util/actor.rs:226-241 */
+BDR_API int32_t bdr_candle_sac_group_sample_members(bdr_candle_sac_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms,
+                                                    uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out);   /* sac/base.rs:162-167, util/actor.rs:226-241 */
+/* the tables of bdr_evaluate_bc_group and bdr_trainer_train_offline_group_post for a candle SAC group, as bdr_iql_group_*_default
+ * (three record keys; save_member writes actor, critic, critic.tgt, ent_coef) */
+BDR_API void bdr_candle_sac_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_candle_sac_group* group);                                   /* sac/base.rs:162-167, evaluator/default_evaluator.rs:64-88 */
+BDR_API void bdr_candle_sac_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_candle_sac_group* group, bdr_replay* const* buffers);    /* sac/base.rs:124-134, trainer.rs:330-384 */
+BDR_API void bdr_candle_sac_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_candle_sac_group* group);                          /* sac/base.rs:244-270, trainer.rs:231-264 */
 
 /* ------------------------------------------------------------------------------------------
  * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)

@@ -121,6 +121,7 @@ pub const BDR_GROUP_FORM_LAYERS: i32 = 1;
 pub const BDR_GROUP_FORM_BC_LAYERS: i32 = 2;
 pub const BDR_GROUP_FORM_IQL_LAYERS: i32 = 3;
 pub const BDR_GROUP_FORM_AWAC_LAYERS: i32 = 4;
+pub const BDR_GROUP_FORM_CANDLE_SAC_LAYERS: i32 = 5;
 pub const BDR_IQN_CONST10: i32 = 0;
 pub const BDR_IQN_CONST32: i32 = 1;
 pub const BDR_IQN_UNIFORM10: i32 = 2;
@@ -154,6 +155,8 @@ pub enum bdr_bc_group {}
 pub enum bdr_iql_group {}
 /// `bdr_awac_group` (a launch grouping of AWAC agents): only ever behind a pointer.
 pub enum bdr_awac_group {}
+/// `bdr_candle_sac_group` (a launch grouping of candle SAC agents): only ever behind a pointer.
+pub enum bdr_candle_sac_group {}
 #[repr(C)]
 pub struct bdr_replay {
     _private: [u8; 0],
@@ -1133,6 +1136,35 @@ extern "C" {
     pub fn bdr_awac_group_eval_ops_default(ops: *mut bdr_bc_group_eval_ops, group: *mut bdr_awac_group);
     pub fn bdr_awac_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_awac_group, buffers: *mut *const bdr_replay);
     pub fn bdr_awac_group_trainer_post_default(post: *mut bdr_bc_group_trainer_post, group: *mut bdr_awac_group);
+    pub fn bdr_candle_sac_group_create(agents: *mut *const bdr_agent, n: u32, out: *mut *mut bdr_candle_sac_group) -> i32;
+    pub fn bdr_candle_sac_group_destroy(g: *mut bdr_candle_sac_group) -> i32;
+    pub fn bdr_candle_sac_group_size(g: *const bdr_candle_sac_group, n: *mut u32) -> i32;
+    pub fn bdr_candle_sac_group_member(g: *const bdr_candle_sac_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_candle_sac_group_info(g: *const bdr_candle_sac_group, out: *mut bdr_group_info) -> i32;
+    pub fn bdr_candle_sac_group_opt(g: *mut bdr_candle_sac_group, buffers: *mut *const bdr_replay) -> i32;
+    pub fn bdr_candle_sac_group_opt_with_scalars(g: *mut bdr_candle_sac_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
+    pub fn bdr_candle_sac_group_sync(g: *mut bdr_candle_sac_group) -> i32;
+    pub fn bdr_candle_sac_group_sample(
+        g: *mut bdr_candle_sac_group,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const f32,
+    ) -> i32;
+    pub fn bdr_candle_sac_group_sample_members(
+        g: *mut bdr_candle_sac_group,
+        members: *const u32,
+        n_sel: u32,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const f32,
+    ) -> i32;
+    pub fn bdr_candle_sac_group_eval_ops_default(ops: *mut bdr_bc_group_eval_ops, group: *mut bdr_candle_sac_group);
+    pub fn bdr_candle_sac_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_candle_sac_group, buffers: *mut *const bdr_replay);
+    pub fn bdr_candle_sac_group_trainer_post_default(post: *mut bdr_bc_group_trainer_post, group: *mut bdr_candle_sac_group);
     pub fn bdr_bc_group_sample(
         g: *mut bdr_bc_group,
         norms: *mut *const bdr_obs_norm,

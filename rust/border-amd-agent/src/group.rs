@@ -9,6 +9,7 @@ use crate::{
     awac::AmdAwac,
     bc::AmdBc,
     bytes::{DiscreteAct, ObsRows, RowBatch},
+    candle_sac::AmdCandleSac,
     config::DqnConfig,
     dqn::AmdDqn,
     error::{check, expect},
@@ -1220,6 +1221,240 @@ where
 {
     fn drop(&mut self) {
         expect(unsafe { ffi::bdr_awac_group_destroy(self.g) }, "bdr_awac_group_destroy");
+        for m in self.members.iter_mut() {
+            m.a.h = std::ptr::null_mut(); // destroyed with the group; bdr_agent_destroy(NULL) in the member's own drop is a no-op
+        }
+    }
+}
+
+/// A group of candle SAC agents of one shape whose `Agent::opt` (`Sac::opt_`, sac/base.rs:124-134) runs as the launch sequence of ONE
+/// member, every launch serving all members (`bdr_candle_sac_group_*`): 3 Lp + 4 Lq + 10 launches per round for Lp, Lq layers of
+/// actor and critic, whatever the number of members.  The members may differ in seed, discount, the critics' tau, critic loss, the
+/// entropy mode (`Fix` or `Auto`), action limit, log-std clamps, learning rates, optimizers and train / eval mode; member `i` steps
+/// on `buffers[i]`, a uniform buffer of its own or a view of one ([`AmdReplayBuffer::view`]), and pushes into it between rounds as
+/// the online agent it is.  A round draws its noise inside the round: a member in train mode takes `2 * batch_size * act_dim` draws
+/// at its own noise counter, the stream its own `sample` and the group's `sample` continue.
+///
+/// A launch grouping, not an agent kind: the members are ordinary [`AmdCandleSac`] agents ([`AmdCandleSacGroup::member_mut`]) on the
+/// group's stream.  Results are bit for bit those of stepping the same agents one after the other.  Owns its members: dropping the
+/// group destroys them (`bdr_candle_sac_group_destroy`).
+pub struct AmdCandleSacGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    g: *mut ffi::bdr_candle_sac_group,
+    members: Vec<AmdCandleSac<E, O, A>>,
+}
+
+// SAFETY: as `AgentHandle` - one HIP stream for the group and its members, all device work behind `&mut`.
+unsafe impl<E: Env, O: RowBatch, A: RowBatch> Send for AmdCandleSacGroup<E, O, A> {}
+
+impl<E, O, A> AmdCandleSacGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    /// Groups agents that already exist.  Fails, naming the first member concerned and the reason, unless all members are candle
+    /// SAC agents of one shape (obs and act dims, both networks, the actor kind, at most two critics, batch size) with `n_updates_per_opt == 1`
+    /// on one device; the agents are then dropped as ordinary agents.
+    pub fn adopt(members: Vec<AmdCandleSac<E, O, A>>) -> Result<Self> {
+        if members.is_empty() {
+            return Err(anyhow!("a group needs at least one member"));
+        }
+        let mut hs: Vec<*const ffi::bdr_agent> = members.iter().map(|m| m.a.h as *const ffi::bdr_agent).collect();
+        let mut g = std::ptr::null_mut();
+        check(unsafe { ffi::bdr_candle_sac_group_create(hs.as_mut_ptr(), hs.len() as u32, &mut g) })?;
+        Ok(Self { g, members })
+    }
+
+    pub fn handle(&self) -> *mut ffi::bdr_candle_sac_group {
+        self.g
+    }
+
+    pub fn len(&self) -> usize {
+        self.members.len()
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.members.is_empty()
+    }
+
+    pub fn member(&self, i: usize) -> &AmdCandleSac<E, O, A> {
+        &self.members[i]
+    }
+
+    /// A member as the ordinary agent it is (`Agent`, `Policy`, `SyncModel`, `save_params` ...).
+    pub fn member_mut(&mut self, i: usize) -> &mut AmdCandleSac<E, O, A> {
+        &mut self.members[i]
+    }
+
+    /// `bdr_candle_sac_group_info`: `form` is `ffi::BDR_GROUP_FORM_CANDLE_SAC_LAYERS`, `launches_per_round` the kernel launches of one update
+    /// round, `kernel_launches` those the group's own calls have enqueued since it was created.
+    pub fn info(&self) -> Result<ffi::bdr_group_info> {
+        let mut out = ffi::bdr_group_info::default();
+        check(unsafe { ffi::bdr_candle_sac_group_info(self.g, &mut out) })?;
+        Ok(out)
+    }
+
+    fn buffer_handles(&self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<*const ffi::bdr_replay>> {
+        if buffers.len() != self.members.len() {
+            return Err(anyhow!("{} members need {} buffers, got {}", self.members.len(), self.members.len(), buffers.len()));
+        }
+        Ok(buffers.iter().map(|b| b.h as *const ffi::bdr_replay).collect())
+    }
+
+    /// `Agent::opt` of every member, member `i` on `buffers[i]`; only enqueues.  A refused call (a prioritized, empty, mismatched
+    /// or shared buffer) leaves every member and every buffer where it was.
+    pub fn opt(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        check(unsafe { ffi::bdr_candle_sac_group_opt(self.g, hs.as_mut_ptr()) })
+    }
+
+    /// `Agent::opt_with_record` of every member: the same round, one synchronisation, the members' `Record`s (the three
+    /// keys of a SAC record) in member order.
+    pub fn opt_with_record(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<Record>> {
+        const CAP: usize = 8;
+        let mut hs = self.buffer_handles(buffers)?;
+        let n = self.members.len();
+        let mut vals = vec![0f32; n * CAP];
+        let mut counts = vec![0i32; n];
+        check(unsafe { ffi::bdr_candle_sac_group_opt_with_scalars(self.g, hs.as_mut_ptr(), vals.as_mut_ptr(), CAP as i32, counts.as_mut_ptr()) })?;
+        let mut out = Vec::with_capacity(n);
+        for (i, m) in self.members.iter_mut().enumerate() {
+            let keys = m.a.record_keys().to_vec();
+            let mut record = Record::empty();
+            for (k, v) in keys.iter().zip(vals[i * CAP..].iter().take(counts[i] as usize)) {
+                record.insert(k.clone(), RecordValue::Scalar(*v));
+            }
+            out.push(record);
+        }
+        Ok(out)
+    }
+
+    /// `Policy::sample` of every member in ONE launch (`bdr_candle_sac_group_sample`): member `i` acts on the `n` rows of `rows[i]`
+    /// (`n * obs_dim` f32 values, the same `n` for every member; two members may name the same slice) and gets `n * act_dim`
+    /// actions, the bits of its own `bdr_agent_sample_raw` in its current mode at its current noise counter: a member in train mode
+    /// takes `n * act_dim` draws of its noise stream, a member in eval mode none.  `norms[i]`: the normaliser of member `i`'s rows,
+    /// or null; an empty slice means none for anybody.
+    pub fn sample(&mut self, n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<f32>>> {
+        self.sample_with(None, n, rows, norms)
+    }
+
+    /// The same for the members `members` (strictly ascending indices) only (`bdr_candle_sac_group_sample_members`).  `rows` and the result
+    /// still have one entry per member; the entries of members that are not selected are not read and stay empty, and their noise
+    /// counters stay where they were.
+    pub fn sample_members(&mut self, members: &[u32], n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<f32>>> {
+        self.sample_with(Some(members), n, rows, norms)
+    }
+
+    fn sample_with(&mut self, members: Option<&[u32]>, n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<f32>>> {
+        let p = self.members.len();
+        if rows.len() != p || !(norms.is_empty() || norms.len() == p) {
+            return Err(anyhow!("{} members need {} row slices and {} normalisers (or none), got {} and {}", p, p, p, rows.len(), norms.len()));
+        }
+        let act_dim = self.members[0].act_dim();
+        let selected = |i: usize| members.map_or(true, |m| m.contains(&(i as u32)));
+        let mut out: Vec<Vec<f32>> = (0..p).map(|i| if selected(i) { vec![0f32; n * act_dim] } else { Vec::new() }).collect();
+        for i in (0..p).filter(|&i| selected(i)) {
+            if n == 0 || rows[i].is_empty() || rows[i].len() % n != 0 {
+                return Err(anyhow!("member {}: {} values are not {} rows of one width", i, rows[i].len(), n));
+            }
+        }
+        let mut row_ptrs: Vec<*const c_void> = rows.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut out_ptrs: Vec<*const f32> = out.iter_mut().map(|v| if v.is_empty() { std::ptr::null() } else { v.as_mut_ptr() as *const f32 }).collect();
+        let mut norm_ptrs: Vec<*const ffi::bdr_obs_norm> = norms.to_vec();
+        let norms_arg = if norm_ptrs.is_empty() { std::ptr::null_mut() } else { norm_ptrs.as_mut_ptr() };
+        let dtypes = vec![ffi::BDR_DTYPE_F32; p];
+        check(match members {
+            None => unsafe { ffi::bdr_candle_sac_group_sample(self.g, norms_arg, n as u64, row_ptrs.as_mut_ptr(), dtypes.as_ptr(), out_ptrs.as_mut_ptr()) },
+            Some(m) => unsafe {
+                ffi::bdr_candle_sac_group_sample_members(
+                    self.g,
+                    m.as_ptr(),
+                    m.len() as u32,
+                    norms_arg,
+                    n as u64,
+                    row_ptrs.as_mut_ptr(),
+                    dtypes.as_ptr(),
+                    out_ptrs.as_mut_ptr(),
+                )
+            },
+        })?;
+        Ok(out)
+    }
+
+    /// `DefaultEvaluator` of every member in lockstep (`bdr_evaluate_bc_group` behind the candle SAC's table): member `i` on `evaluators[i]` -
+    /// the C view of an evaluator of this crate with `act_row_bytes = 4 * act_dim`; f32 or float64 rows and a normaliser per member
+    /// are allowed - with ONE acting launch per round over the members that still have an episode open.
+    pub fn evaluate(&mut self, evaluators: &[ffi::bdr_evaluator]) -> Result<Vec<EvalResult>> {
+        let n = self.members.len();
+        if evaluators.len() != n {
+            return Err(anyhow!("{} members need {} evaluators, got {}", n, n, evaluators.len()));
+        }
+        // SAFETY: bdr_candle_sac_group_eval_ops_default fills every field.
+        let mut ops: ffi::bdr_bc_group_eval_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_sac_group_eval_ops_default(&mut ops, self.g) };
+        let mut out = vec![ffi::bdr_eval_result::default(); n];
+        check(unsafe { ffi::bdr_evaluate_bc_group(evaluators.as_ptr(), &ops, out.as_mut_ptr()) })?;
+        Ok(out.iter().map(eval_result).collect())
+    }
+
+    /// `Trainer::train_offline` with `Trainer::post_process` for the group in compiled code
+    /// (`bdr_trainer_train_offline_group_post`): `config.max_opts` update rounds, member `i` on `buffers[i]`; every `eval_interval`
+    /// opt steps a lockstep evaluation on `evaluators`, member `i`'s best model in `model_dirs[i]/best`, every `save_interval` opt
+    /// steps every member in `model_dirs[i]/<opt_steps>`.  An interval of 0 means never; with both 0, `evaluators` and `model_dirs`
+    /// may be empty.
+    pub fn train_offline(
+        &mut self,
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        config: &ffi::bdr_trainer_config,
+        evaluators: &[ffi::bdr_evaluator],
+        eval_interval: usize,
+        save_interval: usize,
+        model_dirs: &[&Path],
+    ) -> Result<Vec<ffi::bdr_trainer_stats>> {
+        let n = self.members.len();
+        if (eval_interval > 0 && evaluators.len() != n) || ((eval_interval > 0 || save_interval > 0) && model_dirs.len() != n) {
+            return Err(anyhow!("{} members need {} evaluators and model directories", n, n));
+        }
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut ops: ffi::bdr_group_trainer_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_sac_group_trainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
+        let mut dirs = Vec::with_capacity(n);
+        for d in model_dirs {
+            dirs.push(CString::new(d.to_string_lossy().as_bytes())?);
+        }
+        let mut dir_ptrs: Vec<*const c_char> = dirs.iter().map(|d| d.as_ptr()).collect();
+        // SAFETY: bdr_candle_sac_group_trainer_post_default fills every field.
+        let mut post: ffi::bdr_bc_group_trainer_post = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_sac_group_trainer_post_default(&mut post, self.g) };
+        post.eval_interval = eval_interval as u64;
+        post.save_interval = save_interval as u64;
+        post.evaluators = if evaluators.is_empty() { std::ptr::null() } else { evaluators.as_ptr() };
+        post.model_dirs = if dir_ptrs.is_empty() { std::ptr::null_mut() } else { dir_ptrs.as_mut_ptr() };
+        let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
+        check(unsafe { ffi::bdr_trainer_train_offline_group_post(config, &ops, &post, None, std::ptr::null_mut(), stats.as_mut_ptr()) })?;
+        self.sync()?;
+        Ok(stats)
+    }
+
+    /// Waits for everything the group and its members have enqueued (`bdr_candle_sac_group_sync`).
+    pub fn sync(&mut self) -> Result<()> {
+        check(unsafe { ffi::bdr_candle_sac_group_sync(self.g) })
+    }
+}
+
+impl<E, O, A> Drop for AmdCandleSacGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    fn drop(&mut self) {
+        expect(unsafe { ffi::bdr_candle_sac_group_destroy(self.g) }, "bdr_candle_sac_group_destroy");
         for m in self.members.iter_mut() {
             m.a.h = std::ptr::null_mut(); // destroyed with the group; bdr_agent_destroy(NULL) in the member's own drop is a no-op
         }
