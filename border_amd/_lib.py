@@ -233,6 +233,18 @@ class GroupTrainerOps(C.Structure):
                 ("opt_with_record", G_OPT_REC_FN)]
 
 
+# bdr_cgroup_trainer_ops: the online loop's table of an AWAC or a candle SAC group (f32 action rows; every array indexed by member)
+CG_SAMPLE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p))
+CG_PUSH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p))
+
+
+class CGroupTrainerOps(C.Structure):
+    _fields_ = [("group", C.c_void_p), ("buffers", C.POINTER(C.c_void_p)), ("n_members", C.c_uint32), ("reserved", C.c_uint32),
+                ("set_train", G_SET_TRAIN_FN), ("sample", CG_SAMPLE_FN), ("push", CG_PUSH_FN), ("opt", G_OPT_FN),
+                ("opt_with_record", G_OPT_REC_FN)]
+
+
 class EvalEnvVtable(C.Structure):
     _fields_ = [("ctx", C.c_void_p), ("reset_with_index", EVAL_RESET_FN), ("step", EVAL_STEP_FN), ("obs_on_device", C.c_int32), ("device", C.c_int32)]
 
@@ -365,6 +377,8 @@ ABI_SYMBOLS = [
     "bdr_candle_sac_group_opt", "bdr_candle_sac_group_opt_with_scalars", "bdr_candle_sac_group_sync",
     "bdr_candle_sac_group_sample", "bdr_candle_sac_group_sample_members", "bdr_candle_sac_group_eval_ops_default", "bdr_candle_sac_group_trainer_ops_default",
     "bdr_candle_sac_group_trainer_post_default",
+    "bdr_awac_group_push", "bdr_awac_group_push_max_rows", "bdr_candle_sac_group_push", "bdr_candle_sac_group_push_max_rows",
+    "bdr_awac_group_ctrainer_ops_default", "bdr_candle_sac_group_ctrainer_ops_default", "bdr_trainer_train_cgroup_post",
 ]
 
 _lib = None
@@ -396,7 +410,8 @@ def lib() -> C.CDLL:
                         "bdr_bc_group_eval_ops_default", "bdr_bc_group_trainer_ops_default", "bdr_bc_group_trainer_post_default",
                         "bdr_iql_group_eval_ops_default", "bdr_iql_group_trainer_ops_default", "bdr_iql_group_trainer_post_default",
                         "bdr_awac_group_eval_ops_default", "bdr_awac_group_trainer_ops_default", "bdr_awac_group_trainer_post_default",
-                        "bdr_candle_sac_group_eval_ops_default", "bdr_candle_sac_group_trainer_ops_default", "bdr_candle_sac_group_trainer_post_default"):
+                        "bdr_candle_sac_group_eval_ops_default", "bdr_candle_sac_group_trainer_ops_default", "bdr_candle_sac_group_trainer_post_default",
+                        "bdr_awac_group_ctrainer_ops_default", "bdr_candle_sac_group_ctrainer_ops_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -627,6 +642,14 @@ def lib() -> C.CDLL:
     L.bdr_candle_sac_group_trainer_post_default.argtypes = [C.POINTER(BcGroupTrainerPostC), vp]
     L.bdr_trainer_train_offline_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(GroupTrainerOps), C.POINTER(BcGroupTrainerPostC),
                                                        GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
+    for kind in ("awac", "candle_sac"):
+        getattr(L, f"bdr_{kind}_group_push").argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"bdr_{kind}_group_push_max_rows").argtypes = [vp, vp, vp, C.POINTER(u64)]
+        fill = getattr(L, f"bdr_{kind}_group_ctrainer_ops_default")
+        fill.restype, fill.argtypes = None, [C.POINTER(CGroupTrainerOps), vp, vp]
+    L.bdr_trainer_train_cgroup_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(CGroupTrainerOps),
+                                                C.POINTER(EnvVtable), C.POINTER(BcGroupTrainerPostC), GROUP_OBSERVER_FN, C.c_void_p,
+                                                C.POINTER(TrainerStatsC)]
     _lib = L
     return L
 

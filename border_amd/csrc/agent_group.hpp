@@ -18,6 +18,7 @@
 #pragma once
 #include "slot_ring.hpp"
 #include "device_arrays.hpp"
+#include "gp_copy.hpp"
 
 #include "group_layers.hpp"
 
@@ -76,23 +77,6 @@ struct bdr_agent_group {
 // four members per workgroup.  Exactly the bytes a standalone push defines are written: the two rows, act_bytes, reward and two flags.
 struct GroupPushDesc { uint8_t* dst; uint32_t src_off, obs_bytes, next_off, act_off, tail_off, act_bytes; };
 static_assert(sizeof(GroupPushDesc) == 32, "GroupPushDesc is read as two 16-byte halves");
-
-// n bytes by one wave: 16-byte lanes, then 4-byte lanes over what is left, then single bytes (rows of 12 and 24 bytes take the 4-byte lanes)
-__device__ __forceinline__ void gp_copy(uint8_t* dst, const uint8_t* src, uint32_t n, int lane)
-{
-    uint32_t done = 0;
-    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
-        const uint32_t nv = n / 16;
-        for (uint32_t i = lane; i < nv; i += 64) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
-        done = nv * 16;
-    }
-    if ((((uintptr_t)src | (uintptr_t)dst) & 3) == 0) {
-        const uint32_t nw = (n - done) / 4;
-        for (uint32_t i = lane; i < nw; i += 64) reinterpret_cast<uint32_t*>(dst + done)[i] = reinterpret_cast<const uint32_t*>(src + done)[i];
-        done += nw * 4;
-    }
-    for (uint32_t i = done + lane; i < n; i += 64) dst[i] = src[i];
-}
 
 __global__ __launch_bounds__(256) void k_group_push(const uint8_t* __restrict__ slot, unsigned P, unsigned* ticket, unsigned* seq_host, unsigned seq)
 {

@@ -39,6 +39,8 @@
 // Memory traffic is plain vector stores, the existing agent-scope atomics of the ticket and st_agent / ld_agent: nothing new.
 // Acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp, which states the bounds of
 // its indices) through group_act.hpp; AwacActKind below is CandleActKind of an Awac.
+// Online: bdr_awac_group_push is group_core.hpp's group_push (n transitions per member into the member's own ring, ONE launch of
+// k_cgroup_push, group_push.hpp); the compiled online loop over the group is bdr_trainer_train_cgroup_post (trainer.hip).
 #pragma once
 #include "dense_group.hpp"
 #include "candle_act_group.hpp"
@@ -304,6 +306,7 @@ struct bdr_awac_group : GroupCore<AwacGroupKind> {};
 
 namespace bdr {
 int awac_group_act_dim(const void* group, uint32_t member) { return group_act_dim<bdr_awac_group>(group, member); }   // (trainer.hip)
+int awac_group_obs_dim(const void* group, uint32_t member) { return group_obs_dim<bdr_awac_group>(group, member); }   // (trainer.hip)
 }  // namespace bdr
 
 extern "C" {
@@ -328,5 +331,14 @@ int32_t bdr_awac_group_sample_members(bdr_awac_group* g, const uint32_t* members
     return group_sample_members(g, members, n_sel, norms, n, rows, dtypes, act_out);
 }
 int32_t bdr_awac_group_sync(bdr_awac_group* g) { return group_sync(g); }
+int32_t bdr_awac_group_push(bdr_awac_group* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs, const void* const* next_obs, const int32_t* obs_dtypes,
+        const float* const* act, const float* const* reward, const int8_t* const* is_terminated, const int8_t* const* is_truncated)
+{
+    return group_push(g, buffers, n, obs, next_obs, obs_dtypes, act, reward, is_terminated, is_truncated);
+}
+int32_t bdr_awac_group_push_max_rows(bdr_awac_group* g, bdr_replay* const* buffers, const int32_t* obs_dtypes, uint64_t* n_max)
+{
+    return group_push_max_rows(g, buffers, obs_dtypes, n_max);
+}
 
 }  // extern "C"

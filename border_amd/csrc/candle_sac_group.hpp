@@ -26,8 +26,9 @@
 // with nz = NC; its input-layer entry has a null mask (dense_small_body reads a.mask per entry and takes 1 where it is null, as
 // dense_dx_z's launch does today) and writes into dxa.  (3) Mlp2 actors: the last layer is [mean | s]; mlp2 is a static word of the
 // member's sample and actor-gradient entries, head2 / gh2 are not read in that form.  (4) Online members: a member's ring grows and
-// wraps between rounds through its own rb.push; word_pos and size are step words and the gather's static half is keyed on the ring, so
-// nothing is restaged for that.
+// wraps between rounds through the grouped push (bdr_candle_sac_group_push: group_core.hpp's group_push, ONE launch for all members)
+// or its own rb.push; word_pos and size are step words and the gather's static half is keyed on the ring, so nothing is restaged for
+// that.
 // The noise rule.  fill_step does per member what CandleAgent::opt and CandleSac::update do on the host, in their order: it reads the
 // member's mode NOW, and in train mode takes B A draws of the member's noise_counter for a, then B A for next_a (sample_elem's rule;
 // eval mode takes none), then advances step_al (Auto only), step_pi, step_q, n_opts and last_B.  Element t = b A + j of a sample +
@@ -361,6 +362,7 @@ struct bdr_candle_sac_group : GroupCore<CandleSacGroupKind> {};
 
 namespace bdr {
 int candle_sac_group_act_dim(const void* group, uint32_t member) { return group_act_dim<bdr_candle_sac_group>(group, member); }   // (trainer.hip)
+int candle_sac_group_obs_dim(const void* group, uint32_t member) { return group_obs_dim<bdr_candle_sac_group>(group, member); }   // (trainer.hip)
 }  // namespace bdr
 
 extern "C" {
@@ -386,5 +388,14 @@ int32_t bdr_candle_sac_group_sample_members(bdr_candle_sac_group* g, const uint3
     return group_sample_members(g, members, n_sel, norms, n, rows, dtypes, act_out);
 }
 int32_t bdr_candle_sac_group_sync(bdr_candle_sac_group* g) { return group_sync(g); }
+int32_t bdr_candle_sac_group_push(bdr_candle_sac_group* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs, const void* const* next_obs, const int32_t* obs_dtypes,
+        const float* const* act, const float* const* reward, const int8_t* const* is_terminated, const int8_t* const* is_truncated)
+{
+    return group_push(g, buffers, n, obs, next_obs, obs_dtypes, act, reward, is_terminated, is_truncated);
+}
+int32_t bdr_candle_sac_group_push_max_rows(bdr_candle_sac_group* g, bdr_replay* const* buffers, const int32_t* obs_dtypes, uint64_t* n_max)
+{
+    return group_push_max_rows(g, buffers, obs_dtypes, n_max);
+}
 
 }  // extern "C"

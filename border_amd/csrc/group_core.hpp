@@ -13,6 +13,9 @@
 // and publishes the round's launch number (bg_group_done, group_done.hpp - all workgroups of its grid counted, behind a barrier every
 // thread reaches).  The host rewrites a slot only once the pinned word has reached the number recorded for it: no copy command, event
 // or synchronise in the steady loop.  Acting calls (group_act.hpp) take their numbers from the same counter.
+// The grouped push of the online kinds (AWAC, candle SAC: group_push below, k_cgroup_push in group_push.hpp) has a pinned ring of its
+// own under the same rule - PUSH_SLOTS slots of PUSH_SLOT_BYTES, a slot = [CGroupPushDesc[P] | every member's n records] - and takes
+// its numbers from the same counter; the push kernel is the only reader of its slot and publishes its own number.
 // Bounds: a slot and every per-member argument array hold P = members.size() entries, the length of `keys` and of the buffer list of
 // an opt; slot.slot < STEP_SLOTS, and `steps` holds STEP_SLOTS * P entries.  The bounds of the indices a kind's launches add (its
 // dense, dW and reduce arrays) are stated in the kind's file.
@@ -38,6 +41,7 @@
 #include "device_arrays.hpp"
 #include "group_done.hpp"
 #include "group_act.hpp"
+#include "group_push.hpp"
 #include "group_plan_common.hpp"
 
 namespace {
@@ -45,7 +49,7 @@ namespace {
 template <class K>
 struct GroupCore {
     using Kind = K;
-    enum { STEP_SLOTS = 8 };
+    enum { STEP_SLOTS = 8, PUSH_SLOTS = 8, PUSH_SLOT_BYTES = 64 * 1024 };
     int32_t device = 0;
     hipStream_t stream = nullptr;
     // (group_destroy has synchronised the stream and destroyed the members; a failed create has adopted nobody.)  The stream goes
@@ -64,6 +68,10 @@ struct GroupCore {
     uint64_t launches = 0;                                              // launch numbers given out so far (1-based)
     std::vector<bdr_replay*> last_buffers;                              // the buffers of the last accepted opt (distinctness checked once)
     GroupAct<typename K::Act::Call> act;                                // group acting (group_act.hpp): static arguments, call words, staging areas
+    // push (group_push below): PUSH_SLOTS slots of PUSH_SLOT_BYTES, [CGroupPushDesc[P] | every member's n records]; allocated by the
+    // first push, read in place by k_cgroup_push (group_push.hpp)
+    PinnedArray<uint8_t> push; SlotRing<PUSH_SLOTS> push_ring;
+    std::vector<bdr_replay*> last_push_buffers;                         // the buffers of the last accepted push (distinctness checked once)
 
     hipError_t allocate(size_t P)
     {
@@ -175,6 +183,24 @@ int group_act_dim(const void* group, uint32_t member)
     const auto* g = static_cast<const G*>(group);
     return g && member < g->members.size() ? g->members[member]->A : 0;
 }
+// its observation width, for the online loop's check of obs_row_bytes (trainer.hip); 0: no such member
+template <class G>
+int group_obs_dim(const void* group, uint32_t member)
+{
+    const auto* g = static_cast<const G*>(group);
+    return g && member < g->members.size() ? g->members[member]->O : 0;
+}
+
+// the second of two members that name one bdr_replay (P: the P handles are all different)
+inline uint32_t group_shared_buffer(bdr_replay* const* buffers, uint32_t P)
+{
+    std::vector<const bdr_replay*> s(buffers, buffers + P);
+    std::sort(s.begin(), s.end());
+    const auto dup = std::adjacent_find(s.begin(), s.end());
+    if (dup == s.end()) return P;
+    for (uint32_t p = 0, seen = 0; p < P; ++p) if (buffers[p] == *dup && seen++ == 1) return p;
+    return P;
+}
 
 // every refusal of a grouped opt, before anything moves: the checks of the agent's own opt, and what the grouped gather covers
 template <class G>
@@ -195,14 +221,10 @@ int32_t group_check_buffers(G* g, bdr_replay* const* buffers)
         if (r->size == 0) return fail(BDR_ERR_EMPTY, "member %u: batch() on an empty replay buffer", p);
     }
     if (g->last_buffers.size() == P && memcmp(g->last_buffers.data(), buffers, P * sizeof(bdr_replay*)) == 0) return BDR_OK;
-    std::vector<const bdr_replay*> s(buffers, buffers + P);   // workgroups run side by side: one bdr_replay (its batch arrays, its stream position) per member
-    std::sort(s.begin(), s.end());
-    const auto dup = std::adjacent_find(s.begin(), s.end());
-    if (dup != s.end()) {
-        uint32_t second = 0;
-        for (uint32_t p = 0, seen = 0; p < P; ++p) if (buffers[p] == *dup && seen++ == 1) { second = p; break; }
+    // workgroups run side by side: one bdr_replay (its batch arrays, its stream position) per member
+    const uint32_t second = group_shared_buffer(buffers, P);
+    if (second != P)
         return fail(BDR_ERR_INVALID, "member %u: it shares its replay buffer with an earlier member: every member needs a bdr_replay of its own (a view of one ring will do)", second);
-    }
     g->last_buffers.clear();
     return BDR_OK;
 }
@@ -309,6 +331,138 @@ int32_t group_sample_members(G* g, const uint32_t* members, uint32_t n_sel, cons
 {
     BDR_REQUIRE(g && members && rows && dtypes && act_out, "null argument");
     return group_act_sample(g, typename G::Kind::Act{}, members, n_sel, norms, n, rows, dtypes, act_out);
+}
+
+// ---- the grouped push (group_push.hpp has the kernel and the slot's layout) -----------------------------------------------------------
+// the staged record of one transition of a ring, F32 or F64 observation rows
+struct GroupPushLayout { uint32_t s_next_off, s_act_off, s_tail_off, rec_bytes; };
+inline GroupPushLayout group_push_layout(const bdr_replay* r, bool f64)
+{
+    GroupPushLayout l{};
+    if (!f64) {   // the ring's own record
+        l.s_next_off = (uint32_t)r->next_off; l.s_act_off = (uint32_t)r->act_off; l.s_tail_off = (uint32_t)r->tail_off;
+    } else {      // two raw float64 rows, then act and the tail at the ring's offsets modulo 16
+        l.s_next_off = (uint32_t)round_up(2 * r->obs_bytes, 16);
+        l.s_act_off = 2 * l.s_next_off + (uint32_t)(r->act_off & 15);
+        l.s_tail_off = l.s_act_off + (uint32_t)(r->tail_off - r->act_off);
+    }
+    l.rec_bytes = (uint32_t)round_up((uint64_t)l.s_tail_off + 8, 16);
+    return l;
+}
+
+// every refusal of a grouped push, before anything moves; *need: the bytes of the slot the call fills
+template <class G>
+int32_t group_check_push(G* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs, const void* const* next_obs, const int32_t* dtypes,
+                         const float* const* act, const float* const* reward, const int8_t* const* term, const int8_t* const* trunc, uint64_t* need)
+{
+    using K = typename G::Kind;
+    const uint32_t P = (uint32_t)g->members.size();
+    BDR_REQUIRE(n >= 1, "a grouped push takes at least one row per member (n = 0)");
+    uint64_t bytes = (uint64_t)P * sizeof(CGroupPushDesc);
+    for (uint32_t p = 0; p < P; ++p) {
+        const auto* m = g->members[p];
+        const bdr_replay* r = buffers[p];
+        BDR_REQUIRE(r, "member %u: null buffer", p);
+        BDR_REQUIRE(obs[p] && next_obs[p], "member %u: null observation rows", p);
+        BDR_REQUIRE(act[p] && reward[p] && term[p] && trunc[p], "member %u: null act, reward or flag rows", p);
+        const int32_t dt = dtypes ? dtypes[p] : BDR_DTYPE_F32;
+        BDR_REQUIRE(dt == BDR_DTYPE_F32 || dt == BDR_DTYPE_F64, "member %u: dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64", p);
+        BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
+        BDR_REQUIRE(!r->view_of, "member %u: a grouped push on a view: a view is read-only (it borrows its owner's rows)", p);
+        BDR_REQUIRE(r->n_views == 0, "member %u: a grouped push on a ring with %u live view(s): its rows stay as they are until the views are destroyed", p, r->n_views);
+        BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot take the push of %s group (its sum tree is updated by bdr_replay_push)", p, K::A);
+        BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot take the push of %s group", p, K::A);
+        BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: %s group steps rings on the StdRng index stream only", p, K::A);
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == (uint64_t)m->A * 4, "member %u: replay rows do not match %s obs/act dims (f32 rows)", p, K::NAME);
+        bytes += n * (uint64_t)group_push_layout(r, dt == BDR_DTYPE_F64).rec_bytes;
+        BDR_REQUIRE(bytes <= (uint64_t)G::PUSH_SLOT_BYTES,
+                    "member %u: %llu rows per member do not fit one staging slot of %d bytes (descriptors and records of all members): split the call", p,
+                    (unsigned long long)n, (int)G::PUSH_SLOT_BYTES);
+    }
+    *need = bytes;
+    if (g->last_push_buffers.size() == P && memcmp(g->last_push_buffers.data(), buffers, P * sizeof(bdr_replay*)) == 0) return BDR_OK;
+    const uint32_t second = group_shared_buffer(buffers, P);   // waves run side by side, and every ring's head moves once
+    BDR_REQUIRE(second == P, "member %u: it shares its replay buffer with an earlier member: every member pushes into a ring of its own", second);
+    g->last_push_buffers.clear();
+    return BDR_OK;
+}
+
+// the largest n a grouped push of these rings and dtypes takes (0: not even one row fits)
+template <class G>
+int32_t group_push_max_rows(G* g, bdr_replay* const* buffers, const int32_t* dtypes, uint64_t* n_max)
+{
+    BDR_REQUIRE(g && buffers && n_max, "null argument");
+    const uint32_t P = (uint32_t)g->members.size();
+    uint64_t per_row = 0;
+    for (uint32_t p = 0; p < P; ++p) {
+        BDR_REQUIRE(buffers[p], "member %u: null buffer", p);
+        const int32_t dt = dtypes ? dtypes[p] : BDR_DTYPE_F32;
+        BDR_REQUIRE(dt == BDR_DTYPE_F32 || dt == BDR_DTYPE_F64, "member %u: dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64", p);
+        per_row += group_push_layout(buffers[p], dt == BDR_DTYPE_F64).rec_bytes;
+    }
+    const uint64_t head = (uint64_t)P * sizeof(CGroupPushDesc);
+    *n_max = head >= (uint64_t)G::PUSH_SLOT_BYTES ? 0 : ((uint64_t)G::PUSH_SLOT_BYTES - head) / per_row;
+    return BDR_OK;
+}
+
+// ExperienceBufferBase::push of n transitions per member, ONE launch; does not synchronise
+template <class G>
+int32_t group_push(G* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs, const void* const* next_obs, const int32_t* dtypes,
+                   const float* const* act, const float* const* reward, const int8_t* const* term, const int8_t* const* trunc)
+{
+    BDR_REQUIRE(g && buffers && obs && next_obs && act && reward && term && trunc, "null argument");
+    uint64_t need = 0;
+    BDR_TRY(group_check_push(g, buffers, n, obs, next_obs, dtypes, act, reward, term, trunc, &need));
+    BDR_HIP(hipSetDevice(g->device));
+    const uint32_t P = (uint32_t)g->members.size();
+    if (!g->push.host) BDR_HIP(pinned_array(g->push, (size_t)G::PUSH_SLOTS * G::PUSH_SLOT_BYTES));   // the first push
+    const auto slot = g->push_ring.next();
+    if (slot.wait) {   // the slot's last reader has published (bounded: wait_seq_word)
+        bool arrived = false;
+        BDR_TRY(wait_seq_word(g->seq.host.get(), (unsigned)slot.wait, g->stream, std::chrono::steady_clock::now(), &arrived));
+    }
+    // order the group's stream behind each ring's last reader and writer: nothing to do when both were this stream
+    for (uint32_t p = 0; p < P; ++p) BDR_TRY(replay_begin_write_on_stream(buffers[p], g->stream));
+    const size_t slot_off = (size_t)slot.slot * G::PUSH_SLOT_BYTES;
+    uint8_t* base = g->push.host.get() + slot_off;
+    CGroupPushDesc* desc = reinterpret_cast<CGroupPushDesc*>(base);
+    size_t off = (size_t)P * sizeof(CGroupPushDesc);
+    for (uint32_t p = 0; p < P; ++p) {
+        const bdr_replay* r = buffers[p];
+        const bool f64 = dtypes && dtypes[p] == BDR_DTYPE_F64;
+        const GroupPushLayout l = group_push_layout(r, f64);
+        const size_t row = (size_t)r->obs_bytes * (f64 ? 2 : 1);
+        const uint8_t* o = (const uint8_t*)obs[p]; const uint8_t* x = (const uint8_t*)next_obs[p]; const uint8_t* a = (const uint8_t*)act[p];
+        for (uint64_t j = 0; j < n; ++j) {
+            uint8_t* rec = base + off + (size_t)j * l.rec_bytes;
+            memcpy(rec, o + j * row, row);
+            memcpy(rec + l.s_next_off, x + j * row, row);
+            memcpy(rec + l.s_act_off, a + j * r->act_bytes, r->act_bytes);
+            memcpy(rec + l.s_tail_off, &reward[p][j], 4);
+            rec[l.s_tail_off + 4] = (uint8_t)term[p][j];
+            rec[l.s_tail_off + 5] = (uint8_t)trunc[p][j];
+        }
+        CGroupPushDesc d{};
+        d.ring = r->ring; d.head = r->i; d.capacity = r->capacity; d.stride = r->stride;
+        d.src_off = (uint32_t)off; d.rec_bytes = l.rec_bytes;
+        d.obs_bytes = (uint32_t)r->obs_bytes; d.act_bytes = (uint32_t)r->act_bytes;
+        d.next_off = (uint32_t)r->next_off; d.act_off = (uint32_t)r->act_off; d.tail_off = (uint32_t)r->tail_off;
+        d.s_next_off = l.s_next_off; d.s_act_off = l.s_act_off; d.s_tail_off = l.s_tail_off; d.f64 = f64 ? 1u : 0u;
+        desc[p] = d;
+        off += (size_t)n * l.rec_bytes;
+    }
+    std::atomic_thread_fence(std::memory_order_release);
+    // (should the launch fail, k is the number of whatever the group launches next - later than every reader of the slot)
+    const uint64_t k = g->launches + 1;
+    g->launches = k; g->push_ring.record(k);
+    const unsigned waves = P * (unsigned)n;
+    hipLaunchKernelGGL(k_cgroup_push, dim3((waves + 3) / 4), dim3(256), 0, g->stream, (const uint8_t*)(g->push.dev + slot_off), (unsigned)P, (unsigned)n,
+                       g->ticket.get(), g->seq.dev, (unsigned)k);
+    BDR_HIP(hipGetLastError());
+    g->kernel_launches += 1;
+    for (uint32_t p = 0; p < P; ++p) replay_end_write_on_stream(buffers[p], g->stream, n);
+    g->last_push_buffers.assign(buffers, buffers + P);
+    return BDR_OK;
 }
 
 template <class G>

@@ -29,6 +29,8 @@ int bc_group_act_dim(const void* group, uint32_t member);    // bc.hip (bc_group
 int iql_group_act_dim(const void* group, uint32_t member);
 int awac_group_act_dim(const void* group, uint32_t member);   // awac.hip (awac_group.hpp)
 int candle_sac_group_act_dim(const void* group, uint32_t member);   // candle_sac.hip (candle_sac_group.hpp)
+int awac_group_obs_dim(const void* group, uint32_t member);
+int candle_sac_group_obs_dim(const void* group, uint32_t member);
 }
 
 namespace {
@@ -176,17 +178,24 @@ int32_t step_and_records(State& s, const bdr_trainer_post* post, bdr_trainer_obs
 
 // ---- the group loop: bdr_trainer_ops over a group, so that State / train_step / cost_record serve it unchanged ---------------------
 // `agent` is this adapter: opt is one group opt, opt_with_record one group opt_with_record whose Records stay here per member
+// (the entries both group tables have - bdr_group_trainer_ops: i64 actions, bdr_cgroup_trainer_ops: f32 action rows - by value)
 struct GroupAdapter {
-    const bdr_group_trainer_ops* g;
+    void* group; void* const* buffers;
+    int32_t (*set_train)(void*, int32_t);
+    int32_t (*opt)(void*, void* const*);
+    int32_t (*opt_with_record)(void*, void* const*, float*, int32_t, int32_t*);
     std::vector<float> scalars;      // [n_members][128]
     std::vector<int32_t> n_scalars;  // [n_members]
+    template <class Ops>
+    GroupAdapter(const Ops* o, uint32_t P)
+        : group(o->group), buffers(o->buffers), set_train(o->set_train), opt(o->opt), opt_with_record(o->opt_with_record), scalars((size_t)P * 128), n_scalars(P, 0) {}
 };
-int32_t ga_set_train(void* a, int32_t on) { const auto* ga = (GroupAdapter*)a; return ga->g->set_train(ga->g->group, on); }
-int32_t ga_opt(void* a, void*) { const auto* ga = (GroupAdapter*)a; return ga->g->opt(ga->g->group, ga->g->buffers); }
+int32_t ga_set_train(void* a, int32_t on) { const auto* ga = (GroupAdapter*)a; return ga->set_train(ga->group, on); }
+int32_t ga_opt(void* a, void*) { const auto* ga = (GroupAdapter*)a; return ga->opt(ga->group, ga->buffers); }
 int32_t ga_opt_rec(void* a, void*, float* out, int32_t cap, int32_t* n)
 {
     auto* ga = (GroupAdapter*)a;
-    BDR_TRY(ga->g->opt_with_record(ga->g->group, ga->g->buffers, ga->scalars.data(), 128, ga->n_scalars.data()));
+    BDR_TRY(ga->opt_with_record(ga->group, ga->buffers, ga->scalars.data(), 128, ga->n_scalars.data()));
     *n = std::min(ga->n_scalars[0], cap);   // (State::scalars mirrors member 0's; the loop hands every member its own)
     memcpy(out, ga->scalars.data(), (size_t)*n * sizeof(float));
     return BDR_OK;
@@ -418,8 +427,8 @@ typedef void (*GroupObserver)(void* ctx, uint32_t member, uint64_t env_steps, ui
 
 // trainer.rs:231-264 for every member, after an iteration that took an opt step; max_eval_reward[p] is member p's own.
 // evaluate: bdr_evaluate_group or bdr_evaluate_bc_group; save_default: the group kind's own save of a member
-template <class Post, class Evaluate>
-int32_t group_post_process(State& s, const bdr_group_trainer_ops* ops, const Post* post, Evaluate&& evaluate, int32_t (*save_default)(void*, uint32_t, const char*),
+template <class Ops, class Post, class Evaluate>
+int32_t group_post_process(State& s, const Ops* ops, const Post* post, Evaluate&& evaluate, int32_t (*save_default)(void*, uint32_t, const char*),
                            std::vector<float>& max_eval_reward, GroupObserver obs, void* ctx)
 {
     if (!post) return BDR_OK;
@@ -454,6 +463,159 @@ void group_cost_record(State& s, GroupObserver obs, void* obs_ctx, uint32_t P)
         const Fan* fn = (const Fan*)f;
         for (uint32_t p = 0; p < fn->P; ++p) fn->obs(fn->ctx, p, es, os, ev, sc, n);
     } : nullptr, &fan);
+}
+
+// ---- the online group loop, once: bdr_trainer_train_group_post (one i64 action per member) and bdr_trainer_train_cgroup_post (f32
+// action rows, an observation dtype per member) share train_group_loop; an Actions type holds the members' action rows of an iteration
+// and makes the table's acting and push calls on them
+template <class Ops>
+int32_t check_group_loop(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const Ops* ops, const bdr_env_vtable* envs)
+{
+    BDR_REQUIRE(c->max_opts >= 1, "max_opts must be >= 1");
+    BDR_REQUIRE(c->opt_interval >= 1, "opt_interval must be >= 1");
+    BDR_REQUIRE(ops->set_train && ops->sample && ops->push && ops->opt && ops->opt_with_record, "group function table is incomplete");
+    const uint32_t P = ops->n_members;
+    BDR_REQUIRE(P >= 1 && ops->buffers, "the group function table names no members or no buffers");
+    for (uint32_t p = 0; p < P; ++p) {
+        BDR_REQUIRE(envs[p].reset && envs[p].step_with_reset, "member %u: environment function table is incomplete", p);
+        BDR_REQUIRE(!envs[p].obs_on_device, "member %u: the group loop takes host observations (obs_on_device environments are not supported)", p);
+        BDR_REQUIRE(obs_row_bytes[p] > 0, "member %u: obs_row_bytes must be set", p);
+    }
+    return BDR_OK;
+}
+
+struct I64Actions {   // bdr_group_trainer_ops: one i64 action per member, one array
+    const bdr_group_trainer_ops* ops;
+    std::vector<int64_t> act;
+    explicit I64Actions(const bdr_group_trainer_ops* o) : ops(o), act(o->n_members) {}
+    const void* row(uint32_t p) const { return &act[p]; }
+    int32_t sample(const void* const* rows) { return ops->sample(ops->group, rows, act.data()); }
+    int32_t push(const void* const* rows, const void* const* next_rows, const float* reward, const int8_t* term, const int8_t* trunc)
+    {
+        return ops->push(ops->group, ops->buffers, rows, act.data(), next_rows, reward, term, trunc);
+    }
+};
+
+struct F32Actions {   // bdr_cgroup_trainer_ops: one f32 action row per member; every array of a call is indexed by member
+    const bdr_cgroup_trainer_ops* ops;
+    std::vector<int32_t> dtypes;
+    std::vector<float> act;
+    std::vector<float*> act_p;
+    std::vector<const float*> reward_p; std::vector<const int8_t*> term_p, trunc_p;
+    F32Actions(const bdr_cgroup_trainer_ops* o, uint64_t act_row_bytes, const int32_t* obs_dtypes)
+        : ops(o), dtypes(o->n_members, BDR_DTYPE_F32), act((size_t)o->n_members * (act_row_bytes / 4)), act_p(o->n_members), reward_p(o->n_members),
+          term_p(o->n_members), trunc_p(o->n_members)
+    {
+        for (uint32_t p = 0; p < o->n_members; ++p) {
+            act_p[p] = act.data() + (size_t)p * (act_row_bytes / 4);
+            if (obs_dtypes) dtypes[p] = obs_dtypes[p];
+        }
+    }
+    const void* row(uint32_t p) const { return act_p[p]; }
+    int32_t sample(const void* const* rows) { return ops->sample(ops->group, rows, dtypes.data(), act_p.data()); }
+    int32_t push(const void* const* rows, const void* const* next_rows, const float* reward, const int8_t* term, const int8_t* trunc)
+    {
+        for (uint32_t p = 0; p < ops->n_members; ++p) { reward_p[p] = reward + p; term_p[p] = term + p; trunc_p[p] = trunc + p; }
+        return ops->push(ops->group, ops->buffers, rows, next_rows, dtypes.data(), act_p.data(), reward_p.data(), term_p.data(), trunc_p.data());
+    }
+};
+
+// Trainer::train (trainer.rs:267-327) with post_process for every member in lockstep; everything has been checked
+template <class Ops, class Post, class Actions, class Evaluate>
+int32_t train_group_loop(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const Ops* ops, const bdr_env_vtable* envs, const Post* post, Actions& actions,
+                         Evaluate&& evaluate, int32_t (*save_default)(void*, uint32_t, const char*), GroupObserver obs, void* obs_ctx, bdr_trainer_stats* out)
+{
+    const uint32_t P = ops->n_members;
+    std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member
+    GroupAdapter ga(ops, P);
+    bdr_trainer_ops t{};
+    t.agent = &ga; t.agent_set_train = ga_set_train; t.agent_opt = ga_opt; t.agent_opt_with_record = ga_opt_rec;
+    State s; s.c = c; s.ops = &t;
+    // per member: the Sampler's / SimpleStepProcessor's prev_obs, the step's obs and init_obs (bdr_trainer_train's three rows)
+    std::vector<std::vector<uint8_t>> prev(P), obs_new(P), init_obs(P);
+    std::vector<const void*> prev_p(P), new_p(P);
+    for (uint32_t p = 0; p < P; ++p) { prev[p].resize(obs_row_bytes[p]); obs_new[p].resize(obs_row_bytes[p]); init_obs[p].resize(obs_row_bytes[p]); }
+    std::vector<float> reward(P);
+    std::vector<int8_t> term(P), trunc(P);
+    std::vector<uint64_t> n_episodes(P, 0);
+    bool have_prev = false;
+    BDR_TRY(t.agent_set_train(t.agent, 1));   // trainer.rs:283
+    for (;;) {
+        const auto t0 = Clock::now();
+        // ---- Sampler::sample_and_push (sampler.rs:99-144) of every member
+        if (!have_prev) {
+            for (uint32_t p = 0; p < P; ++p) BDR_TRY(envs[p].reset(envs[p].ctx, prev[p].data()));
+            have_prev = true;
+        }
+        for (uint32_t p = 0; p < P; ++p) { prev_p[p] = prev[p].data(); new_p[p] = obs_new[p].data(); }
+        BDR_TRY(actions.sample(prev_p.data()));
+        for (uint32_t p = 0; p < P; ++p) {
+            reward[p] = 0; term[p] = 0; trunc[p] = 0;
+            BDR_TRY(envs[p].step_with_reset(envs[p].ctx, actions.row(p), obs_new[p].data(), &reward[p], &term[p], &trunc[p], init_obs[p].data()));
+        }
+        BDR_TRY(actions.push(prev_p.data(), new_p.data(), reward.data(), term.data(), trunc.data()));
+        for (uint32_t p = 0; p < P; ++p) {
+            const bool is_done = term[p] == 1 || trunc[p] == 1;   // step.rs:136-138
+            prev[p].swap(is_done ? init_obs[p] : obs_new[p]);     // prev_obs = init_obs / obs (sampler.rs:137-141, step_proc.rs:131-135)
+            if (is_done) n_episodes[p] += 1;
+        }
+        const double dt = std::chrono::duration<double>(Clock::now() - t0).count();
+        s.timer_for_samples += dt; s.total_sample += dt;
+        s.samples_counter += 1;
+        s.env_steps += 1;
+        // ---- train_step, once for all members; every member's event; the cost record
+        bool is_opt = false, with_record = false;
+        BDR_TRY(train_step(s, &is_opt, &with_record));
+        const int32_t event = is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP;
+        if (obs)
+            for (uint32_t p = 0; p < P; ++p) obs(obs_ctx, p, s.env_steps, s.opt_steps, event, ga.scalars.data() + (size_t)p * 128, with_record ? ga.n_scalars[p] : 0);
+        if (is_opt) BDR_TRY(group_post_process(s, ops, post, evaluate, save_default, max_eval_reward, obs, obs_ctx));
+        group_cost_record(s, obs, obs_ctx, P);
+        if (s.opt_steps == c->max_opts) break;   // trainer.rs:323-325
+    }
+    if (out)
+        for (uint32_t p = 0; p < P; ++p) { fill_stats(s, out + p); out[p].n_episodes = n_episodes[p]; }
+    return BDR_OK;
+}
+
+
+// an AWAC or a candle SAC group's online entries behind bdr_cgroup_trainer_ops (bdr_*_group_ctrainer_ops_default): the offline
+// table's set_train / opt / opt_with_record (Base), acting on one row per member and the grouped push of one transition per member
+template <class G, class Base, auto SampleAll, auto Push>
+struct CGroupEntries {
+    static int32_t sample(void* g, const void* const* rows, const int32_t* dtypes, float* const* act_out) { return SampleAll((G*)g, nullptr, 1, rows, dtypes, act_out); }
+    static int32_t push(void* g, void* const* b, const void* const* rows, const void* const* next_rows, const int32_t* dtypes, const float* const* act,
+                        const float* const* reward, const int8_t* const* term, const int8_t* const* trunc)
+    {
+        return Push((G*)g, (bdr_replay* const*)b, 1, rows, next_rows, dtypes, act, reward, term, trunc);
+    }
+    static void trainer_ops(bdr_cgroup_trainer_ops* ops, G* group, bdr_replay* const* buffers)
+    {
+        if (!ops) return;
+        bdr_group_trainer_ops t;
+        Base::trainer_ops(&t, group, buffers);
+        memset(ops, 0, sizeof *ops);
+        ops->group = t.group; ops->buffers = t.buffers; ops->n_members = t.n_members;
+        ops->set_train = t.set_train; ops->opt = t.opt; ops->opt_with_record = t.opt_with_record;
+        ops->sample = sample; ops->push = push;
+    }
+};
+using AwacGroupOnline = CGroupEntries<bdr_awac_group, AwacGroupEntries, bdr_awac_group_sample, bdr_awac_group_push>;
+using CandleSacGroupOnline = CGroupEntries<bdr_candle_sac_group, CandleSacGroupEntries, bdr_candle_sac_group_sample, bdr_candle_sac_group_push>;
+// the kinds a default online table can name: the widths of a member, the kind in messages, its save
+struct CGroupKindRow {
+    decltype(bdr_cgroup_trainer_ops::sample) sample;
+    int (*act_dim)(const void*, uint32_t);
+    int (*obs_dim)(const void*, uint32_t);
+    const char* a;
+    int32_t (*save_member)(void*, uint32_t, const char*);
+};
+const CGroupKindRow* cgroup_kind_of(const bdr_cgroup_trainer_ops* ops)
+{
+    static const CGroupKindRow kinds[] = {{AwacGroupOnline::sample, awac_group_act_dim, awac_group_obs_dim, "an AWAC", AwacGroupEntries::save_member},
+                                          {CandleSacGroupOnline::sample, candle_sac_group_act_dim, candle_sac_group_obs_dim, "a candle SAC", CandleSacGroupEntries::save_member}};
+    for (const CGroupKindRow& k : kinds) if (ops->sample == k.sample) return &k;
+    return nullptr;
 }
 }  // namespace
 
@@ -691,7 +853,7 @@ int32_t bdr_trainer_train_offline_group_post(const bdr_trainer_config* c_in, con
     bdr_trainer_config c = *c_in;
     c.warmup_period = 0; c.opt_interval = 1;            // trainer.rs:345-346
     std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member
-    GroupAdapter ga{ops, std::vector<float>((size_t)P * 128), std::vector<int32_t>(P, 0)};
+    GroupAdapter ga(ops, P);
     bdr_trainer_ops t{};
     t.agent = &ga; t.agent_set_train = ga_set_train; t.agent_opt = ga_opt; t.agent_opt_with_record = ga_opt_rec;
     State s; s.c = &c; s.ops = &t;
@@ -728,69 +890,48 @@ int32_t bdr_trainer_train_group_post(const bdr_trainer_config* c, const uint64_t
                                      void* obs_ctx, bdr_trainer_stats* out)
 {
     BDR_REQUIRE(c && ops && envs && obs_row_bytes, "null argument");
-    BDR_REQUIRE(c->max_opts >= 1, "max_opts must be >= 1");
-    BDR_REQUIRE(c->opt_interval >= 1, "opt_interval must be >= 1");
-    BDR_REQUIRE(ops->set_train && ops->sample && ops->push && ops->opt && ops->opt_with_record, "group function table is incomplete");
-    const uint32_t P = ops->n_members;
-    BDR_REQUIRE(P >= 1 && ops->buffers, "the group function table names no members or no buffers");
+    BDR_TRY(check_group_loop(c, obs_row_bytes, ops, envs));
     BDR_REQUIRE(c->act_row_bytes == 8, "a group acts with one i64 action per member: act_row_bytes must be 8");
+    BDR_TRY(check_group_post(post, ops->n_members, check_group_eval));
+    I64Actions actions(ops);
+    return train_group_loop(c, obs_row_bytes, ops, envs, post, actions, bdr_evaluate_group, dg_save_member, obs, obs_ctx, out);
+}
+
+void bdr_awac_group_ctrainer_ops_default(bdr_cgroup_trainer_ops* ops, bdr_awac_group* group, bdr_replay* const* buffers)
+{
+    AwacGroupOnline::trainer_ops(ops, group, buffers);
+}
+void bdr_candle_sac_group_ctrainer_ops_default(bdr_cgroup_trainer_ops* ops, bdr_candle_sac_group* group, bdr_replay* const* buffers)
+{
+    CandleSacGroupOnline::trainer_ops(ops, group, buffers);
+}
+
+// the same loop for an AWAC or a candle SAC group: f32 action rows, f32 or float64 observation rows, the grouped push of the group core
+int32_t bdr_trainer_train_cgroup_post(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const int32_t* obs_dtypes, const bdr_cgroup_trainer_ops* ops,
+                                      const bdr_env_vtable* envs, const bdr_bc_group_trainer_post* post,
+                                      void (*obs)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps, int32_t event, const float* scalars,
+                                                  int32_t n_scalars),
+                                      void* obs_ctx, bdr_trainer_stats* out)
+{
+    BDR_REQUIRE(c && ops && envs && obs_row_bytes, "null argument");
+    BDR_TRY(check_group_loop(c, obs_row_bytes, ops, envs));
+    const uint32_t P = ops->n_members;
+    BDR_REQUIRE(c->act_row_bytes > 0 && c->act_row_bytes % 4 == 0, "a continuous-action group acts with f32 action rows: act_row_bytes must be a positive multiple of 4");
+    const CGroupKindRow* online = cgroup_kind_of(ops);
     for (uint32_t p = 0; p < P; ++p) {
-        BDR_REQUIRE(envs[p].reset && envs[p].step_with_reset, "member %u: environment function table is incomplete", p);
-        BDR_REQUIRE(!envs[p].obs_on_device, "member %u: the group loop takes host observations (obs_on_device environments are not supported)", p);
-        BDR_REQUIRE(obs_row_bytes[p] > 0, "member %u: obs_row_bytes must be set", p);
+        const int32_t dt = obs_dtypes ? obs_dtypes[p] : BDR_DTYPE_F32;
+        BDR_REQUIRE(dt == BDR_DTYPE_F32 || dt == BDR_DTYPE_F64, "member %u: obs_dtype must be BDR_DTYPE_F32 or BDR_DTYPE_F64", p);
+        if (!online) continue;
+        const int A = online->act_dim(ops->group, p), O = online->obs_dim(ops->group, p);
+        BDR_REQUIRE(A > 0 && O > 0, "member %u: the group has no such member", p);
+        BDR_REQUIRE(c->act_row_bytes == (uint64_t)A * 4, "member %u: %s group acts with one f32 action row per member: act_row_bytes must be 4 * act_dim = %d", p, online->a, A * 4);
+        BDR_REQUIRE(obs_row_bytes[p] == (uint64_t)O * (dt == BDR_DTYPE_F64 ? 8 : 4), "member %u: obs_row_bytes must be obs_dim = %d elements of its obs_dtype", p, O);
     }
-    BDR_TRY(check_group_post(post, P, check_group_eval));
-    std::vector<float> max_eval_reward(P, -FLT_MAX);   // f32::MIN (trainer.rs: max_eval_reward), one per member
-    GroupAdapter ga{ops, std::vector<float>((size_t)P * 128), std::vector<int32_t>(P, 0)};
-    bdr_trainer_ops t{};
-    t.agent = &ga; t.agent_set_train = ga_set_train; t.agent_opt = ga_opt; t.agent_opt_with_record = ga_opt_rec;
-    State s; s.c = c; s.ops = &t;
-    // per member: the Sampler's / SimpleStepProcessor's prev_obs, the step's obs and init_obs (bdr_trainer_train's three rows)
-    std::vector<std::vector<uint8_t>> prev(P), obs_new(P), init_obs(P);
-    std::vector<const void*> prev_p(P), new_p(P);
-    for (uint32_t p = 0; p < P; ++p) { prev[p].resize(obs_row_bytes[p]); obs_new[p].resize(obs_row_bytes[p]); init_obs[p].resize(obs_row_bytes[p]); }
-    std::vector<int64_t> act(P);
-    std::vector<float> reward(P);
-    std::vector<int8_t> term(P), trunc(P);
-    std::vector<uint64_t> n_episodes(P, 0);
-    bool have_prev = false;
-    BDR_TRY(t.agent_set_train(t.agent, 1));   // trainer.rs:283
-    for (;;) {
-        const auto t0 = Clock::now();
-        // ---- Sampler::sample_and_push (sampler.rs:99-144) of every member
-        if (!have_prev) {
-            for (uint32_t p = 0; p < P; ++p) BDR_TRY(envs[p].reset(envs[p].ctx, prev[p].data()));
-            have_prev = true;
-        }
-        for (uint32_t p = 0; p < P; ++p) { prev_p[p] = prev[p].data(); new_p[p] = obs_new[p].data(); }
-        BDR_TRY(ops->sample(ops->group, prev_p.data(), act.data()));
-        for (uint32_t p = 0; p < P; ++p) {
-            reward[p] = 0; term[p] = 0; trunc[p] = 0;
-            BDR_TRY(envs[p].step_with_reset(envs[p].ctx, &act[p], obs_new[p].data(), &reward[p], &term[p], &trunc[p], init_obs[p].data()));
-        }
-        BDR_TRY(ops->push(ops->group, ops->buffers, prev_p.data(), act.data(), new_p.data(), reward.data(), term.data(), trunc.data()));
-        for (uint32_t p = 0; p < P; ++p) {
-            const bool is_done = term[p] == 1 || trunc[p] == 1;   // step.rs:136-138
-            prev[p].swap(is_done ? init_obs[p] : obs_new[p]);     // prev_obs = init_obs / obs (sampler.rs:137-141, step_proc.rs:131-135)
-            if (is_done) n_episodes[p] += 1;
-        }
-        const double dt = std::chrono::duration<double>(Clock::now() - t0).count();
-        s.timer_for_samples += dt; s.total_sample += dt;
-        s.samples_counter += 1;
-        s.env_steps += 1;
-        // ---- train_step, once for all members; every member's event; the cost record
-        bool is_opt = false, with_record = false;
-        BDR_TRY(train_step(s, &is_opt, &with_record));
-        const int32_t event = is_opt ? (with_record ? BDR_TRAINER_EVENT_OPT_RECORD : BDR_TRAINER_EVENT_OPT) : BDR_TRAINER_EVENT_SKIP;
-        if (obs)
-            for (uint32_t p = 0; p < P; ++p) obs(obs_ctx, p, s.env_steps, s.opt_steps, event, ga.scalars.data() + (size_t)p * 128, with_record ? ga.n_scalars[p] : 0);
-        if (is_opt) BDR_TRY(group_post_process(s, ops, post, bdr_evaluate_group, dg_save_member, max_eval_reward, obs, obs_ctx));
-        group_cost_record(s, obs, obs_ctx, P);
-        if (s.opt_steps == c->max_opts) break;   // trainer.rs:323-325
-    }
-    if (out)
-        for (uint32_t p = 0; p < P; ++p) { fill_stats(s, out + p); out[p].n_episodes = n_episodes[p]; }
-    return BDR_OK;
+    BDR_TRY(check_group_post(post, P, check_bc_group_eval));
+    const GroupKindRow* kind = post ? group_kind_of(&post->eval_ops) : nullptr;
+    const auto save_default = kind ? kind->save_member : (online ? online->save_member : BcGroupEntries::save_member);
+    F32Actions actions(ops, c->act_row_bytes, obs_dtypes);
+    return train_group_loop(c, obs_row_bytes, ops, envs, post, actions, bdr_evaluate_bc_group, save_default, obs, obs_ctx, out);
 }
 
 int32_t bdr_trainer_train_offline(const bdr_trainer_config* c_in, const bdr_trainer_ops* ops, bdr_trainer_observer obs, void* obs_ctx,

@@ -373,6 +373,104 @@ def _group_train_offline(group, prefix: str, record_keys, buffers, max_opts, rec
     return [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
 
 
+def _group_push_arrays(group, obs, act, next_obs, reward, is_terminated, is_truncated):
+    """The per-member arrays of a grouped push: (n, obs, next_obs, dtype codes, act, reward, is_terminated, is_truncated), each a list
+    of C-contiguous arrays in member order.  A field is one array per member (a list or tuple) or ONE ndarray that every member takes."""
+    P = len(group._members)
+    od, ad = group._members[0].config.obs_dim, group._members[0].config.act_dim
+
+    def per_member(name, x):
+        xs = [x] * P if isinstance(x, np.ndarray) else list(x)
+        if len(xs) != P:
+            raise ValueError(f"{P} members need {P} arrays of {name} (or one array for all), got {len(xs)}")
+        return xs
+
+    def rows(name, x):   # float64 stays float64, everything else becomes float32
+        out, seen = [], {}
+        for r in per_member(name, x):
+            if id(r) not in seen:
+                a = np.asarray(r)
+                seen[id(r)] = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32).reshape(-1, od)
+            out.append(seen[id(r)])
+        return out
+
+    def cols(name, x, dtype, width):
+        out, seen = [], {}
+        for r in per_member(name, x):
+            if id(r) not in seen:
+                seen[id(r)] = np.ascontiguousarray(r, dtype).reshape(-1, width) if width else np.ascontiguousarray(r, dtype).reshape(-1)
+            out.append(seen[id(r)])
+        return out
+    o, x = rows("obs", obs), rows("next_obs", next_obs)
+    a, r = cols("act", act, np.float32, ad), cols("reward", reward, np.float32, 0)
+    t, u = cols("is_terminated", is_terminated, np.int8, 0), cols("is_truncated", is_truncated, np.int8, 0)
+    n = o[0].shape[0]
+    for i in range(P):
+        if o[i].dtype != x[i].dtype:
+            raise ValueError(f"member {i}: obs is {o[i].dtype}, next_obs {x[i].dtype}: one dtype per member")
+        for name, arr in (("obs", o[i]), ("next_obs", x[i]), ("act", a[i]), ("reward", r[i]), ("is_terminated", t[i]), ("is_truncated", u[i])):
+            if arr.shape[0] != n:
+                raise ValueError(f"member {i}: {arr.shape[0]} rows of {name}, member 0 has {n} rows of obs: one n for every member and field")
+    codes = [_lib.BDR_DTYPE_F64 if v.dtype == np.float64 else _lib.BDR_DTYPE_F32 for v in o]
+    return n, o, x, codes, a, r, t, u
+
+
+def _group_push(group, prefix: str, obs, act, next_obs, reward, is_terminated, is_truncated, buffers) -> None:
+    """`prefix`_push (bdr_awac_group_push, bdr_candle_sac_group_push) of n transitions per member"""
+    bufs = group._buffers(buffers)
+    P = len(group._members)
+    n, o, x, codes, a, r, t, u = _group_push_arrays(group, obs, act, next_obs, reward, is_terminated, is_truncated)
+    ptrs = lambda arrs: (C.c_void_p * P)(*[v.ctypes.data for v in arrs])
+    _lib.check(getattr(_lib.lib(), prefix + "_push")(group._g, bufs, n, ptrs(o), ptrs(x), (C.c_int32 * P)(*codes), ptrs(a), ptrs(r), ptrs(t), ptrs(u)))
+
+
+def _group_push_max_rows(group, prefix: str, obs_dtypes, buffers) -> int:
+    bufs = group._buffers(buffers)
+    P = len(group._members)
+    dts = [obs_dtypes] * P if obs_dtypes is None or isinstance(obs_dtypes, (type, np.dtype, str)) else list(obs_dtypes)
+    codes = (C.c_int32 * P)(*[_lib.BDR_DTYPE_F64 if d is not None and np.dtype(d) == np.float64 else _lib.BDR_DTYPE_F32 for d in dts])
+    n = C.c_uint64(0)
+    _lib.check(getattr(_lib.lib(), prefix + "_push_max_rows")(group._g, bufs, codes, C.byref(n)))
+    return n.value
+
+
+class _OnlineGroup:
+    """The online half of an AwacGroup or a CandleSacGroup: the grouped push and the compiled online loop (csrc/group_core.hpp
+    group_push, csrc/trainer.hip bdr_trainer_train_cgroup_post), written once; the two classes take its methods.  BcGroup and
+    IqlGroup are offline kinds and do not have it."""
+    PUSH_STAGING_DEPTH = 8          # slots of the push staging ring (csrc/group_core.hpp GroupCore::PUSH_SLOTS)
+    PUSH_SLOT_BYTES = 64 * 1024     # ... and the bytes of one (GroupCore::PUSH_SLOT_BYTES): 80 per member plus every member's n records
+
+    def push(self, obs, act, next_obs, reward, is_terminated, is_truncated, buffers=None) -> None:
+        """ExperienceBufferBase::push of n transitions per member into the member's own buffer, ONE launch (bdr_<kind>_group_push);
+        does not synchronise.  Each field is one array per member (a list) or ONE ndarray that every member takes: obs / next_obs
+        [n, obs_dim] (or [obs_dim]: n = 1) - float64 arrays stay float64 and are converted on the device exactly as
+        `astype(np.float32)` does, everything else becomes float32 -, act [n, act_dim] float32, reward [n] float32, the flags [n]
+        int8; the same n for every member, 1 <= n <= push_max_rows().  Every ring ends up exactly as `rb.push` of the same rows as
+        float32 leaves it.  `buffers=None`: the buffers named last (as opt())."""
+        _group_push(self, self._PREFIX, obs, act, next_obs, reward, is_terminated, is_truncated, buffers)
+
+    def push_max_rows(self, obs_dtypes=None, buffers=None) -> int:
+        """The largest n one `push` takes for these buffers (bdr_<kind>_group_push_max_rows): the descriptors and the n records of
+        every member fit one staging slot of PUSH_SLOT_BYTES.  obs_dtypes: one dtype for all members or one per member
+        (np.float64 rows are staged raw and take twice the bytes); None: float32."""
+        return _group_push_max_rows(self, self._PREFIX, obs_dtypes, buffers)
+
+    def train(self, envs, buffers, trainer_config, obs_dtype=np.float32, on_event=None, evaluators=None, eval_interval=0, save_interval=0,
+              model_dirs=None) -> list:
+        """The compiled online loop over the group (bdr_trainer_train_cgroup_post): member i on envs[i] and buffers[i], one group
+        sample, one group push and at most one group opt per iteration; member i sees exactly the calls `NativeTrainer.train` makes
+        for a lone agent.  envs[i]: reset(None) -> obs[1, obs_dim], step_with_reset(act[1, act_dim] float32) -> Step.  obs_dtype:
+        np.float32 or np.float64, one for all members or one per member - the environments' rows are kept in that dtype, acted on
+        and pushed as they are.  on_event(member, env_steps, opt_steps, event, scalars); returns one statistics dict per member.
+        evaluators / eval_interval / save_interval / model_dirs (one Evaluator and one directory per member): Trainer::post_process
+        after every opt step, as `train_offline`.  An exception raised by an environment is raised again here."""
+        from .trainer import NativeTrainer
+        self._buffers(buffers)   # (opt() / push() without buffers go on with these)
+        return NativeTrainer(trainer_config).train_cgroup(envs, self, list(buffers), obs_dtype=obs_dtype, on_event=on_event, evaluators=evaluators,
+                                                          eval_interval=eval_interval, save_interval=save_interval, model_dirs=model_dirs)
+
+
 class _DenseGroup:
     """What BcGroup, IqlGroup, AwacGroup and CandleSacGroup share: a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
     member, every launch serving all members (csrc/group_core.hpp through the kind's bdr_<kind>_group_* functions).  A subclass names
@@ -548,13 +646,16 @@ class AwacGroup(_DenseGroup):
 
     A round draws noise inside the round (act_ and next_act): each member's mode (`set_train`) is read when the round is enqueued,
     and in train mode the member takes 2 * batch_size * act_dim draws at its own noise counter - rounds, `sample` of the group and
-    the member's own `sample` / `update_on_batch` continue one stream.
+    the member's own `sample` / `update_on_batch` continue one stream.  `push` stores n transitions per member in one launch and
+    `train` runs the compiled online loop (awac_pendulum runs Trainer::train).
 
     A launch grouping, not an agent kind: the members are ordinary `Awac` objects (every `Awac` method keeps working on a member and
     means what it meant) that the group owns - `AwacGroup.close()` closes them, `member.close()` on a live group is refused.  Results
     are bit for bit those of stepping the same agents one after the other."""
     _PREFIX, _MEMBER = "bdr_awac_group", Awac
     RECORD_KEYS = ("loss_critic", "loss_actor", "q_tgt_abs_mean", "adv_mean", "adv_abs_mean", "logp_mean", "reward_mean", "next_q_mean")
+    PUSH_STAGING_DEPTH, PUSH_SLOT_BYTES = _OnlineGroup.PUSH_STAGING_DEPTH, _OnlineGroup.PUSH_SLOT_BYTES
+    push, push_max_rows, train = _OnlineGroup.push, _OnlineGroup.push_max_rows, _OnlineGroup.train   # (the online half: BcGroup and IqlGroup do not have it)
 
 
 class CandleSacGroup(_DenseGroup):
@@ -566,7 +667,8 @@ class CandleSacGroup(_DenseGroup):
     the log-std clamps, learning rates, optimizers and train / eval mode; their buffers are uniform buffers of their own or views of
     one (`SimpleReplayBuffer.view`).
 
-    The members are online agents: each pushes into its own buffer (`rb.push`) between rounds; the ring may grow and wrap.  A round
+    The members are online agents: `push` stores n transitions per member in one launch and `train` runs the compiled online loop
+    (a member's own `rb.push` between rounds keeps working); the ring may grow and wrap.  A round
     draws noise inside the round (a and next_a): each member's mode (`set_train`) is read when the round is enqueued, and in train
     mode the member takes 2 * batch_size * act_dim draws at its own noise counter - rounds, `sample` of the group and the member's own
     `sample` / `update_on_batch` continue one stream.
@@ -576,3 +678,5 @@ class CandleSacGroup(_DenseGroup):
     refused.  Results are bit for bit those of stepping the same agents one after the other."""
     _PREFIX, _MEMBER = "bdr_candle_sac_group", CandleSac
     RECORD_KEYS = ("loss_critic", "loss_actor", "ent_coef")
+    PUSH_STAGING_DEPTH, PUSH_SLOT_BYTES = _OnlineGroup.PUSH_STAGING_DEPTH, _OnlineGroup.PUSH_SLOT_BYTES
+    push, push_max_rows, train = _OnlineGroup.push, _OnlineGroup.push_max_rows, _OnlineGroup.train   # (the online half: BcGroup and IqlGroup do not have it)

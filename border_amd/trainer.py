@@ -388,6 +388,90 @@ class NativeTrainer:
         self.stats = [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
         return self.stats
 
+    def train_cgroup(self, envs, group, buffers, obs_dtype=np.float32, on_event=None, evaluators=None, eval_interval=0, save_interval=0, model_dirs=None):
+        """bdr_trainer_train_cgroup_post: Trainer::train for the members of an `AwacGroup` or a `CandleSacGroup` in lockstep, member i
+        on envs[i] (reset(None) -> obs[1, obs_dim], step_with_reset(act[1, act_dim] float32) -> Step) and buffers[i].  obs_dtype:
+        np.float32 or np.float64, one for all members or a list per member.  Everything else as `train_group`; the evaluators are
+        built with act_dim = the members' act_dim."""
+        n = len(envs)
+        if n != len(group) or n != len(buffers):
+            raise ValueError(f"{len(group)} members need {len(group)} environments and buffers, got {n} and {len(buffers)}")
+        od, ad = group.members[0].config.obs_dim, group.members[0].config.act_dim
+        dts = [np.dtype(d) for d in (obs_dtype if isinstance(obs_dtype, (list, tuple)) else [obs_dtype] * n)]
+        if len(dts) != n or any(d not in (np.dtype(np.float32), np.dtype(np.float64)) for d in dts):
+            raise ValueError(f"obs_dtype: np.float32 or np.float64, one for all members or one per member ({n})")
+        rows = [od * d.itemsize for d in dts]
+        failure = []
+        keep = []
+
+        def callbacks(env, row, dt):
+            def write(ptr, arr):
+                a = np.ascontiguousarray(arr, dt)
+                if a.nbytes != row:
+                    raise ValueError(f"an observation of {row} bytes, got {a.nbytes}")
+                C.memmove(ptr, a.ctypes.data, row)
+
+            def reset(_ctx, obs_out):
+                try:
+                    write(obs_out, env.reset(None))
+                    return 0
+                except Exception as e:  # noqa: BLE001  (raised again once the loop has returned)
+                    failure.append(e)
+                    return 1
+
+            def step(_ctx, act, obs_out, reward, term, trunc, init_out):
+                try:
+                    st = env.step_with_reset(np.frombuffer((C.c_char * (4 * ad)).from_address(act), np.float32).copy())
+                    write(obs_out, st.obs)
+                    reward[0], term[0], trunc[0] = float(st.reward[0]), int(st.is_terminated[0]), int(st.is_truncated[0])
+                    if st.is_done():
+                        write(init_out, st.init_obs)
+                    return 0
+                except Exception as e:  # noqa: BLE001
+                    failure.append(e)
+                    return 1
+            fns = (_lib.ENV_RESET_FN(reset), _lib.ENV_STEP_FN(step))
+            keep.append(fns)
+            return _lib.EnvVtable(None, fns[0], fns[1])
+
+        vts = (_lib.EnvVtable * n)(*[callbacks(e, r, d) for e, r, d in zip(envs, rows, dts)])
+        ops = _lib.CGroupTrainerOps()
+        handles = (C.c_void_p * n)(*[b.handle for b in buffers])
+        getattr(_lib.lib(), group._PREFIX + "_ctrainer_ops_default")(C.byref(ops), group.handle, handles)
+
+        def cb(_ctx, member, env_steps, opt_steps, event, scalars, k):
+            if on_event is not None:
+                on_event(member, env_steps, opt_steps, NativeTrainer.EVENTS[event], [scalars[i] for i in range(k)])
+        c, st, obs = self._config(0, 4 * ad), (_lib.TrainerStatsC * n)(), _lib.GROUP_OBSERVER_FN(cb)
+        codes = (C.c_int32 * n)(*[_lib.BDR_DTYPE_F64 if d == np.dtype(np.float64) else _lib.BDR_DTYPE_F32 for d in dts])
+        post = None
+        evaluators = list(evaluators) if evaluators is not None else []
+        if evaluators or eval_interval or save_interval or model_dirs is not None:
+            post = _lib.BcGroupTrainerPostC()
+            getattr(_lib.lib(), group._PREFIX + "_trainer_post_default")(C.byref(post), group.handle)
+            post.eval_interval, post.save_interval = int(eval_interval or 0), int(save_interval or 0)
+            if evaluators:
+                if len(evaluators) != n:
+                    raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
+                evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
+                post.evaluators = evs
+            if model_dirs is not None:
+                if len(model_dirs) != n:
+                    raise ValueError(f"{n} members need {n} model directories, got {len(model_dirs)}")
+                dirs = (C.c_char_p * n)(*[None if d is None else str(d).encode() for d in model_dirs])
+                post.model_dirs = dirs
+        rc = _lib.lib().bdr_trainer_train_cgroup_post(C.byref(c), (C.c_uint64 * n)(*rows), codes, C.byref(ops), vts,
+                                                      C.byref(post) if post is not None else None, obs, None, st)
+        if failure:
+            raise failure[0]
+        if evaluators:
+            from .group import raise_first
+            raise_first(evaluators, rc)
+        _lib.check(rc)
+        group.sync()
+        self.stats = [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
+        return self.stats
+
 
 class ParamExchange:
     """Parameter averaging across one-replica-per-GPU ranks over the library's own communicator (csrc/comm.hip): ncclAllReduce on the

@@ -1525,8 +1525,8 @@ BDR_API void bdr_iql_group_trainer_post_default(bdr_bc_group_trainer_post* post,
  * buffers[p] is member p's, as for bdr_iql_group_opt, with the same refusals; a refused call leaves every member's two step counters,
  * n_opts, noise counter and stream position where they were.  _opt_with_scalars returns every member's record (the eight keys of
  * bdr_agent_record_keys; cap_per_member >= 8) at out + p * cap_per_member.  _info fills bdr_group_info with form =
- * BDR_GROUP_FORM_AWAC_LAYERS.  Not built: pushes through the group (the online side), n_updates_per_opt > 1, n_critics > 2, Mlp2
- * actors, host-supplied noise rows. */
+ * BDR_GROUP_FORM_AWAC_LAYERS.  Not built: n_updates_per_opt > 1, n_critics > 2, Mlp2 actors, host-supplied noise rows, prioritized
+ * rings under the group. */
 typedef struct bdr_awac_group bdr_awac_group;
 BDR_API int32_t bdr_awac_group_create(bdr_agent* const* agents, uint32_t n, bdr_awac_group** out);   /* awac/base.rs:170-215 (opt_ of every member) */
 BDR_API int32_t bdr_awac_group_destroy(bdr_awac_group* g);                                           /* awac/base.rs:170-215 */
@@ -1546,6 +1546,33 @@ BDR_API void bdr_awac_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_awa
 BDR_API void bdr_awac_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_awac_group* group, bdr_replay* const* buffers);    /* awac/base.rs:170-215, trainer.rs:330-384 */
 BDR_API void bdr_awac_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_awac_group* group);                          /* awac/base.rs:311-319, trainer.rs:231-264 */
 
+/* ExperienceBufferBase::push (generic_replay_buffer/base.rs:279-313) of n transitions per member of an AWAC group, member i's into
+ * buffers[i] at its head, in ONE launch and without a copy command whatever the number of members and n are.  Every array is indexed
+ * by member and holds n rows: obs[i] / next_obs[i] = n rows of obs_dim elements of obs_dtypes[i] (BDR_DTYPE_F32 / BDR_DTYPE_F64;
+ * obs_dtypes == NULL: all BDR_DTYPE_F32), act[i] = [n][act_dim] f32, reward[i] = [n] f32, the flags [n] i8.  Each ring ends up exactly
+ * as bdr_replay_push(buffers[i], n, ...) of the same rows as float32 leaves it: the same bytes in the same rows (row j at (head + j) %
+ * capacity: a push may cross the wrap), head advanced by n modulo capacity, size saturating at capacity, summary counters and index
+ * stream untouched in the same way.  float64 rows are converted on the device by one round-to-nearest-even cast per element - the
+ * bits of a C (float) cast / numpy astype(float32), and the cast bdr_awac_group_sample applies to the same rows with norms == NULL, so
+ * acting and storing agree; no normaliser is applied (the ring stores what the reference's step processor stores,
+ * generic_replay_buffer/step_proc.rs:103-137).
+ * The rows are staged in a slot of a pinned push ring of the group (8 slots of 64 KiB) that the kernel reads in place: the call
+ * returns once the caller's rows are staged - its arrays are free - and does not synchronise.  It runs on the group's stream: the
+ * group's later rounds and acting calls are ordered behind it by their queue, calls on a ring's own stream (bdr_replay_push,
+ * bdr_replay_batch, ...) order themselves through the ring's event.  It counts as one launch in bdr_group_info::kernel_launches.
+ * Bounds: 1 <= n, and 80 bytes per member plus the n records of every member fit one slot (a record is the ring's own record rounded
+ * up to 16 bytes; with float64 rows its two observation rows take twice their bytes); _push_max_rows returns the largest such n for
+ * these rings and dtypes.  A larger call is refused with a message that says to split it.
+ * Refused with BDR_ERR_INVALID before anything moves - every ring's head, size and rows, every slot and the launch counter stay where
+ * they were -, naming the member: a NULL buffer or row pointer; n outside its bounds; an unknown dtype; a ring on another device; a
+ * view, or a ring with live views; a prioritized ring, a single-frame store or an xoshiro256++ ring; observation rows that are not
+ * 4 * obs_dim bytes or action rows that are not 4 * act_dim bytes; two members naming one ring.
+ * Not built: acting on next_obs inside the push launch, a normaliser inside the push, prioritized rings. */
+BDR_API int32_t bdr_awac_group_push(bdr_awac_group* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs, const void* const* next_obs,
+                                    const int32_t* obs_dtypes, const float* const* act, const float* const* reward,
+                                    const int8_t* const* is_terminated, const int8_t* const* is_truncated);   /* generic_replay_buffer/base.rs:279-313 */
+BDR_API int32_t bdr_awac_group_push_max_rows(bdr_awac_group* g, bdr_replay* const* buffers, const int32_t* obs_dtypes, uint64_t* n_max);   /* generic_replay_buffer/base.rs:279-313 */
+
 /* A GROUP of candle SAC agents (bdr_candle_sac_create, above) over uniform rings (or views of one ring, bdr_replay_view_create):
  * Sac::opt_ (sac/base.rs:124-134) of every member in the launch sequence of ONE member - gather, pack, the actor on obs, sample + logp
  * of a, the entropy coefficient's step, the online critics on (obs | act) and (obs | a), qmin, the critics' input gradients down to
@@ -1553,7 +1580,8 @@ BDR_API void bdr_awac_group_trainer_post_default(bdr_bc_group_trainer_post* post
  * 3 Lp + 4 Lq + 10 launches for Lp, Lq layers (n_units + 1) of actor and critic, whatever the number of members; the member index is
  * one more grid dimension - bit for bit what bdr_agent_opt of the members one after the other gives.  The calls carry the semantics
  * of their bdr_iql_group_* namesakes (ownership, ordering with the members' own calls, acting, the tables of the evaluator and the
- * offline loop).  The members are online agents: each pushes into its own ring (bdr_replay_push) between rounds.
+ * offline loop).  The members are online agents: bdr_candle_sac_group_push (below) stores n transitions per member in one launch, and a
+ * member's own bdr_replay_push between rounds keeps working.
  * Noise: as for a bdr_awac_group - each member's mode is read when the round is enqueued; in train mode the member takes batch_size *
  * act_dim draws at its own noise counter for a, then as many for next_a, in eval mode none.  Rounds, the group's acting calls, the
  * member's own sample / sample_raw / update_on_batch and bdr_agent_draw_noise continue ONE stream, in any interleaving.
@@ -1567,8 +1595,8 @@ BDR_API void bdr_awac_group_trainer_post_default(bdr_bc_group_trainer_post* post
  * buffers[p] is member p's, as for bdr_iql_group_opt, with the same refusals; a refused call leaves every member's three step
  * counters, n_opts, noise counter and stream position where they were.  _opt_with_scalars returns every member's record (the three
  * keys of bdr_agent_record_keys; cap_per_member >= 3) at out + p * cap_per_member.  _info fills bdr_group_info with form =
- * BDR_GROUP_FORM_CANDLE_SAC_LAYERS.  Not built: pushes through the group and a compiled online loop, n_updates_per_opt > 1,
- * n_critics > 2, host-supplied noise rows, a captured graph of the round. */
+ * BDR_GROUP_FORM_CANDLE_SAC_LAYERS.  Not built: n_updates_per_opt > 1, n_critics > 2, host-supplied noise rows, a captured graph of
+ * the round, prioritized rings under the group. */
 typedef struct bdr_candle_sac_group bdr_candle_sac_group;
 BDR_API int32_t bdr_candle_sac_group_create(bdr_agent* const* agents, uint32_t n, bdr_candle_sac_group** out);   /* sac/base.rs:124-134 (opt_ of every member) */
 BDR_API int32_t bdr_candle_sac_group_destroy(bdr_candle_sac_group* g);                                           /* sac/base.rs:124-134 */
@@ -1587,6 +1615,50 @@ BDR_API int32_t bdr_candle_sac_group_sample_members(bdr_candle_sac_group* g, con
 BDR_API void bdr_candle_sac_group_eval_ops_default(bdr_bc_group_eval_ops* ops, bdr_candle_sac_group* group);                                   /* sac/base.rs:162-167, evaluator/default_evaluator.rs:64-88 */
 BDR_API void bdr_candle_sac_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_candle_sac_group* group, bdr_replay* const* buffers);    /* sac/base.rs:124-134, trainer.rs:330-384 */
 BDR_API void bdr_candle_sac_group_trainer_post_default(bdr_bc_group_trainer_post* post, bdr_candle_sac_group* group);                          /* sac/base.rs:244-270, trainer.rs:231-264 */
+/* bdr_awac_group_push / _push_max_rows for a candle SAC group: the same call, word for word */
+BDR_API int32_t bdr_candle_sac_group_push(bdr_candle_sac_group* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs,
+                                          const void* const* next_obs, const int32_t* obs_dtypes, const float* const* act, const float* const* reward,
+                                          const int8_t* const* is_terminated, const int8_t* const* is_truncated);   /* generic_replay_buffer/base.rs:279-313 */
+BDR_API int32_t bdr_candle_sac_group_push_max_rows(bdr_candle_sac_group* g, bdr_replay* const* buffers, const int32_t* obs_dtypes, uint64_t* n_max);   /* generic_replay_buffer/base.rs:279-313 */
+
+/* Trainer::train (trainer.rs:267-327) with Trainer::post_process (:231-264) for the members of an AWAC or a candle SAC group in
+ * lockstep: bdr_trainer_train_group_post's rule, word for word - ONE group sample on the members' prev_obs rows, step_with_reset of
+ * every environment in member order, ONE group push of (prev_obs, act, obs, reward, flags), prev_obs = init_obs / obs per member,
+ * train_step's rule once (env_steps, warm-up, opt_interval, opt vs opt_with_record and the stop at max_opts are shared decisions), the
+ * members' events in member order, post_process, the cost record - and the same loop body in the library.  Member i sees exactly the
+ * calls bdr_trainer_train_post makes for a lone agent on envs[i]: acting in train mode advances its noise counter by act_dim per
+ * iteration, the evaluation inside post_process runs in eval mode and returns to train mode.  The differences:
+ *   actions   are f32 rows: c->act_row_bytes must be a positive multiple of 4, and 4 * act_dim of the members with a default table;
+ *   dtypes    obs_dtypes[i] (BDR_DTYPE_F32 / BDR_DTYPE_F64; NULL: all F32) comes with obs_row_bytes[i]: the environments write rows
+ *             of that dtype (with a default table obs_row_bytes[i] must be obs_dim elements of it), and the same host rows go to the
+ *             group's acting call (n = 1, norms NULL) and to the grouped push (n = 1);
+ *   post      is a bdr_bc_group_trainer_post (bdr_evaluate_bc_group, save_member), filled by bdr_*_group_trainer_post_default; with
+ *             post == NULL it is the plain loop.
+ * Environments with obs_on_device are refused.  Not built: obs_on_device environments, n_updates_per_opt > 1. */
+typedef struct bdr_cgroup_trainer_ops {
+    void* group;
+    void* const* buffers;                   /* [n_members] */
+    uint32_t n_members;
+    uint32_t reserved;
+    int32_t (*set_train)(void* group, int32_t train);                                             /* Agent::train of every member */
+    /* Policy::sample, one row of dtypes[i] per member; act_out[i] receives member i's f32 action row */
+    int32_t (*sample)(void* group, const void* const* rows, const int32_t* dtypes, float* const* act_out);
+    /* one transition per member; every array is indexed by member */
+    int32_t (*push)(void* group, void* const* buffers, const void* const* rows, const void* const* next_rows, const int32_t* dtypes,
+                    const float* const* act, const float* const* reward, const int8_t* const* is_terminated, const int8_t* const* is_truncated);
+    int32_t (*opt)(void* group, void* const* buffers);                                            /* Agent::opt of every member */
+    /* member i's Record scalars in scalars[i * cap_per_member ...], their count in n_scalars[i] */
+    int32_t (*opt_with_record)(void* group, void* const* buffers, float* scalars, int32_t cap_per_member, int32_t* n_scalars);
+} bdr_cgroup_trainer_ops;
+/* the bdr_<kind>_group_* entries on a group and its members' rings (`buffers` must stay alive while `ops` is used): sample =
+ * _sample with n = 1 and norms NULL, push = _push with n = 1 */
+BDR_API void bdr_awac_group_ctrainer_ops_default(bdr_cgroup_trainer_ops* ops, bdr_awac_group* group, bdr_replay* const* buffers);               /* trainer.rs:267-327, trainer/sampler.rs:99-144 */
+BDR_API void bdr_candle_sac_group_ctrainer_ops_default(bdr_cgroup_trainer_ops* ops, bdr_candle_sac_group* group, bdr_replay* const* buffers);   /* trainer.rs:267-327, trainer/sampler.rs:99-144 */
+BDR_API int32_t bdr_trainer_train_cgroup_post(const bdr_trainer_config* c, const uint64_t* obs_row_bytes, const int32_t* obs_dtypes,
+                                              const bdr_cgroup_trainer_ops* ops, const bdr_env_vtable* envs, const bdr_bc_group_trainer_post* post,
+                                              void (*observer)(void* ctx, uint32_t member, uint64_t env_steps, uint64_t opt_steps,
+                                                               int32_t event, const float* scalars, int32_t n_scalars),
+                                              void* observer_ctx, bdr_trainer_stats* out);   /* trainer.rs:267-327, :231-264 */
 
 /* ------------------------------------------------------------------------------------------
  * DQN agent of border-candle-agent  (border-candle-agent/src/dqn/{base.rs,config.rs,explorer.rs,model.rs}; online RL)

@@ -28,6 +28,7 @@ where
     pub(crate) a: AgentHandle,
     train: bool,
     act_dim: usize,
+    obs_dim: usize,
     n_critics: usize,
     phantom: PhantomData<(E, O, A)>,
 }
@@ -65,6 +66,11 @@ where
     /// Width of one action row (`Policy::sample` on raw rows: [`crate::evaluator::SampleRaw`]).
     pub fn act_dim(&self) -> usize {
         self.act_dim
+    }
+
+    /// Width of one observation row.
+    pub fn obs_dim(&self) -> usize {
+        self.obs_dim
     }
 
     pub fn sync(&mut self) -> Result<()> {
@@ -115,7 +121,7 @@ where
         let c = config.to_c().expect("CandleSacConfig");
         let mut h = std::ptr::null_mut();
         expect(unsafe { ffi::bdr_candle_sac_create(&c, &mut h) }, "Sac::build");
-        Self { a: AgentHandle::new(h), train: config.train, act_dim: c.act_dim as usize, n_critics: c.n_critics as usize, phantom: PhantomData }
+        Self { a: AgentHandle::new(h), train: config.train, act_dim: c.act_dim as usize, obs_dim: c.obs_dim as usize, n_critics: c.n_critics as usize, phantom: PhantomData }
     }
 }
 

@@ -511,6 +511,34 @@ pub struct bdr_group_trainer_ops {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct bdr_cgroup_trainer_ops {
+    pub group: *mut c_void,
+    pub buffers: *mut *const c_void,
+    pub n_members: u32,
+    pub reserved: u32,
+    pub set_train: Option<unsafe extern "C" fn(group: *mut c_void, train: i32) -> i32>,
+    pub sample: Option<unsafe extern "C" fn(group: *mut c_void, rows: *mut *const c_void, dtypes: *const i32, act_out: *mut *const f32) -> i32>,
+    pub push: Option<
+        unsafe extern "C" fn(
+            group: *mut c_void,
+            buffers: *mut *const c_void,
+            rows: *mut *const c_void,
+            next_rows: *mut *const c_void,
+            dtypes: *const i32,
+            act: *mut *const f32,
+            reward: *mut *const f32,
+            is_terminated: *mut *const i8,
+            is_truncated: *mut *const i8,
+        ) -> i32,
+    >,
+    pub opt: Option<unsafe extern "C" fn(group: *mut c_void, buffers: *mut *const c_void) -> i32>,
+    pub opt_with_record: Option<
+        unsafe extern "C" fn(group: *mut c_void, buffers: *mut *const c_void, scalars: *mut f32, cap_per_member: i32, n_scalars: *mut i32) -> i32,
+    >,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct bdr_group_eval_ops {
     pub group: *mut c_void,
     pub n_members: u32,
@@ -1136,6 +1164,20 @@ extern "C" {
     pub fn bdr_awac_group_eval_ops_default(ops: *mut bdr_bc_group_eval_ops, group: *mut bdr_awac_group);
     pub fn bdr_awac_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_awac_group, buffers: *mut *const bdr_replay);
     pub fn bdr_awac_group_trainer_post_default(post: *mut bdr_bc_group_trainer_post, group: *mut bdr_awac_group);
+    pub fn bdr_awac_group_push(
+        g: *mut bdr_awac_group,
+        buffers: *mut *const bdr_replay,
+        n: u64,
+        obs: *mut *const c_void,
+        next_obs: *mut *const c_void,
+        obs_dtypes: *const i32,
+        act: *mut *const f32,
+        reward: *mut *const f32,
+        is_terminated: *mut *const i8,
+        is_truncated: *mut *const i8,
+    ) -> i32;
+    pub fn bdr_awac_group_push_max_rows(g: *mut bdr_awac_group, buffers: *mut *const bdr_replay, obs_dtypes: *const i32, n_max: *mut u64) -> i32;
+    pub fn bdr_awac_group_ctrainer_ops_default(ops: *mut bdr_cgroup_trainer_ops, group: *mut bdr_awac_group, buffers: *mut *const bdr_replay);
     pub fn bdr_candle_sac_group_create(agents: *mut *const bdr_agent, n: u32, out: *mut *mut bdr_candle_sac_group) -> i32;
     pub fn bdr_candle_sac_group_destroy(g: *mut bdr_candle_sac_group) -> i32;
     pub fn bdr_candle_sac_group_size(g: *const bdr_candle_sac_group, n: *mut u32) -> i32;
@@ -1165,6 +1207,33 @@ extern "C" {
     pub fn bdr_candle_sac_group_eval_ops_default(ops: *mut bdr_bc_group_eval_ops, group: *mut bdr_candle_sac_group);
     pub fn bdr_candle_sac_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_candle_sac_group, buffers: *mut *const bdr_replay);
     pub fn bdr_candle_sac_group_trainer_post_default(post: *mut bdr_bc_group_trainer_post, group: *mut bdr_candle_sac_group);
+    pub fn bdr_candle_sac_group_push(
+        g: *mut bdr_candle_sac_group,
+        buffers: *mut *const bdr_replay,
+        n: u64,
+        obs: *mut *const c_void,
+        next_obs: *mut *const c_void,
+        obs_dtypes: *const i32,
+        act: *mut *const f32,
+        reward: *mut *const f32,
+        is_terminated: *mut *const i8,
+        is_truncated: *mut *const i8,
+    ) -> i32;
+    pub fn bdr_candle_sac_group_push_max_rows(g: *mut bdr_candle_sac_group, buffers: *mut *const bdr_replay, obs_dtypes: *const i32, n_max: *mut u64) -> i32;
+    pub fn bdr_candle_sac_group_ctrainer_ops_default(ops: *mut bdr_cgroup_trainer_ops, group: *mut bdr_candle_sac_group, buffers: *mut *const bdr_replay);
+    pub fn bdr_trainer_train_cgroup_post(
+        c: *const bdr_trainer_config,
+        obs_row_bytes: *const u64,
+        obs_dtypes: *const i32,
+        ops: *const bdr_cgroup_trainer_ops,
+        envs: *const bdr_env_vtable,
+        post: *const bdr_bc_group_trainer_post,
+        observer: Option<
+            unsafe extern "C" fn(ctx: *mut c_void, member: u32, env_steps: u64, opt_steps: u64, event: i32, scalars: *const f32, n_scalars: i32),
+        >,
+        observer_ctx: *mut c_void,
+        out: *mut bdr_trainer_stats,
+    ) -> i32;
     pub fn bdr_bc_group_sample(
         g: *mut bdr_bc_group,
         norms: *mut *const bdr_obs_norm,

@@ -1207,6 +1207,127 @@ where
         Ok(stats)
     }
 
+    /// `ExperienceBufferBase::push` of `n` transitions per member, member `i`'s into `buffers[i]`, in ONE launch
+    /// (`bdr_awac_group_push`); only enqueues.  `obs[i]` / `next_obs[i]`: `n * obs_dim` f32 values, `act[i]`: `n * act_dim`,
+    /// `reward[i]`, `is_terminated[i]`, `is_truncated[i]`: `n` values.  Each ring ends up exactly as its own `push` of those rows
+    /// leaves it (a push may cross the wrap).  `n` is bounded by one staging slot ([`Self::push_max_rows`]); a refused call (a
+    /// view, a prioritized ring, a single-frame store, a row width other than the members', two members on one ring, too many
+    /// rows) moves nothing.  float64 rows go through `ffi::bdr_awac_group_push` with `BDR_DTYPE_F64`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn push(
+        &mut self,
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        n: usize,
+        obs: &[&[f32]],
+        act: &[&[f32]],
+        next_obs: &[&[f32]],
+        reward: &[&[f32]],
+        is_terminated: &[&[i8]],
+        is_truncated: &[&[i8]],
+    ) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        let p = self.members.len();
+        if obs.len() != p || act.len() != p || next_obs.len() != p || reward.len() != p || is_terminated.len() != p || is_truncated.len() != p {
+            return Err(anyhow!("{} members need {} slices of every field", p, p));
+        }
+        let (od, ad) = (self.members[0].obs_dim(), self.members[0].act_dim());
+        for i in 0..p {
+            if obs[i].len() != n * od || next_obs[i].len() != n * od || act[i].len() != n * ad {
+                return Err(anyhow!("member {}: {} rows need {} observation and {} action values", i, n, n * od, n * ad));
+            }
+            if reward[i].len() != n || is_terminated[i].len() != n || is_truncated[i].len() != n {
+                return Err(anyhow!("member {}: {} rows need {} rewards and flags", i, n, n));
+            }
+        }
+        let mut o: Vec<*const c_void> = obs.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut x: Vec<*const c_void> = next_obs.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut a: Vec<*const f32> = act.iter().map(|r| r.as_ptr()).collect();
+        let mut r: Vec<*const f32> = reward.iter().map(|r| r.as_ptr()).collect();
+        let mut t: Vec<*const i8> = is_terminated.iter().map(|r| r.as_ptr()).collect();
+        let mut u: Vec<*const i8> = is_truncated.iter().map(|r| r.as_ptr()).collect();
+        check(unsafe {
+            ffi::bdr_awac_group_push(
+                self.g,
+                hs.as_mut_ptr(),
+                n as u64,
+                o.as_mut_ptr(),
+                x.as_mut_ptr(),
+                std::ptr::null(),
+                a.as_mut_ptr(),
+                r.as_mut_ptr(),
+                t.as_mut_ptr(),
+                u.as_mut_ptr(),
+            )
+        })
+    }
+
+    /// The largest `n` one [`Self::push`] of f32 rows takes for these buffers (`bdr_awac_group_push_max_rows`).
+    pub fn push_max_rows(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<usize> {
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut n = 0u64;
+        check(unsafe { ffi::bdr_awac_group_push_max_rows(self.g, hs.as_mut_ptr(), std::ptr::null(), &mut n) })?;
+        Ok(n as usize)
+    }
+
+    /// `Trainer::train` (`trainer.rs:267-327`) with `Trainer::post_process` for all members in lockstep in the compiled loop
+    /// `bdr_trainer_train_cgroup_post`: member `i` on `envs[i]` - the C view of an environment that writes rows of
+    /// `obs_dtypes[i]` (`BDR_DTYPE_F32` / `BDR_DTYPE_F64`) and `obs_row_bytes[i]` bytes and reads one f32 action row - and
+    /// `buffers[i]`; one group sample, one group push and at most one group opt per iteration.  `config.act_row_bytes` must be
+    /// `4 * act_dim`.  Post-processing as [`Self::train_offline`]: with both intervals 0, `evaluators` and `model_dirs` may be empty.
+    #[allow(clippy::too_many_arguments)]
+    pub fn train(
+        &mut self,
+        envs: &[ffi::bdr_env_vtable],
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        obs_row_bytes: &[u64],
+        obs_dtypes: &[i32],
+        config: &ffi::bdr_trainer_config,
+        evaluators: &[ffi::bdr_evaluator],
+        eval_interval: usize,
+        save_interval: usize,
+        model_dirs: &[&Path],
+    ) -> Result<Vec<ffi::bdr_trainer_stats>> {
+        let n = self.members.len();
+        if envs.len() != n || obs_row_bytes.len() != n || obs_dtypes.len() != n {
+            return Err(anyhow!("{} members need {} environments, row sizes and dtypes", n, n));
+        }
+        if (eval_interval > 0 && evaluators.len() != n) || ((eval_interval > 0 || save_interval > 0) && model_dirs.len() != n) {
+            return Err(anyhow!("{} members need {} evaluators and model directories", n, n));
+        }
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut ops: ffi::bdr_cgroup_trainer_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_awac_group_ctrainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
+        let mut dirs = Vec::with_capacity(n);
+        for d in model_dirs {
+            dirs.push(CString::new(d.to_string_lossy().as_bytes())?);
+        }
+        let mut dir_ptrs: Vec<*const c_char> = dirs.iter().map(|d| d.as_ptr()).collect();
+        // SAFETY: bdr_awac_group_trainer_post_default fills every field.
+        let mut post: ffi::bdr_bc_group_trainer_post = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_awac_group_trainer_post_default(&mut post, self.g) };
+        post.eval_interval = eval_interval as u64;
+        post.save_interval = save_interval as u64;
+        post.evaluators = if evaluators.is_empty() { std::ptr::null() } else { evaluators.as_ptr() };
+        post.model_dirs = if dir_ptrs.is_empty() { std::ptr::null_mut() } else { dir_ptrs.as_mut_ptr() };
+        let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
+        check(unsafe {
+            ffi::bdr_trainer_train_cgroup_post(
+                config,
+                obs_row_bytes.as_ptr(),
+                obs_dtypes.as_ptr(),
+                &ops,
+                envs.as_ptr(),
+                &post,
+                None,
+                std::ptr::null_mut(),
+                stats.as_mut_ptr(),
+            )
+        })?;
+        self.sync()?;
+        Ok(stats)
+    }
+
+
     /// Waits for everything the group and its members have enqueued (`bdr_awac_group_sync`).
     pub fn sync(&mut self) -> Result<()> {
         check(unsafe { ffi::bdr_awac_group_sync(self.g) })
@@ -1440,6 +1561,127 @@ where
         self.sync()?;
         Ok(stats)
     }
+
+    /// `ExperienceBufferBase::push` of `n` transitions per member, member `i`'s into `buffers[i]`, in ONE launch
+    /// (`bdr_candle_sac_group_push`); only enqueues.  `obs[i]` / `next_obs[i]`: `n * obs_dim` f32 values, `act[i]`: `n * act_dim`,
+    /// `reward[i]`, `is_terminated[i]`, `is_truncated[i]`: `n` values.  Each ring ends up exactly as its own `push` of those rows
+    /// leaves it (a push may cross the wrap).  `n` is bounded by one staging slot ([`Self::push_max_rows`]); a refused call (a
+    /// view, a prioritized ring, a single-frame store, a row width other than the members', two members on one ring, too many
+    /// rows) moves nothing.  float64 rows go through `ffi::bdr_candle_sac_group_push` with `BDR_DTYPE_F64`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn push(
+        &mut self,
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        n: usize,
+        obs: &[&[f32]],
+        act: &[&[f32]],
+        next_obs: &[&[f32]],
+        reward: &[&[f32]],
+        is_terminated: &[&[i8]],
+        is_truncated: &[&[i8]],
+    ) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        let p = self.members.len();
+        if obs.len() != p || act.len() != p || next_obs.len() != p || reward.len() != p || is_terminated.len() != p || is_truncated.len() != p {
+            return Err(anyhow!("{} members need {} slices of every field", p, p));
+        }
+        let (od, ad) = (self.members[0].obs_dim(), self.members[0].act_dim());
+        for i in 0..p {
+            if obs[i].len() != n * od || next_obs[i].len() != n * od || act[i].len() != n * ad {
+                return Err(anyhow!("member {}: {} rows need {} observation and {} action values", i, n, n * od, n * ad));
+            }
+            if reward[i].len() != n || is_terminated[i].len() != n || is_truncated[i].len() != n {
+                return Err(anyhow!("member {}: {} rows need {} rewards and flags", i, n, n));
+            }
+        }
+        let mut o: Vec<*const c_void> = obs.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut x: Vec<*const c_void> = next_obs.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut a: Vec<*const f32> = act.iter().map(|r| r.as_ptr()).collect();
+        let mut r: Vec<*const f32> = reward.iter().map(|r| r.as_ptr()).collect();
+        let mut t: Vec<*const i8> = is_terminated.iter().map(|r| r.as_ptr()).collect();
+        let mut u: Vec<*const i8> = is_truncated.iter().map(|r| r.as_ptr()).collect();
+        check(unsafe {
+            ffi::bdr_candle_sac_group_push(
+                self.g,
+                hs.as_mut_ptr(),
+                n as u64,
+                o.as_mut_ptr(),
+                x.as_mut_ptr(),
+                std::ptr::null(),
+                a.as_mut_ptr(),
+                r.as_mut_ptr(),
+                t.as_mut_ptr(),
+                u.as_mut_ptr(),
+            )
+        })
+    }
+
+    /// The largest `n` one [`Self::push`] of f32 rows takes for these buffers (`bdr_candle_sac_group_push_max_rows`).
+    pub fn push_max_rows(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<usize> {
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut n = 0u64;
+        check(unsafe { ffi::bdr_candle_sac_group_push_max_rows(self.g, hs.as_mut_ptr(), std::ptr::null(), &mut n) })?;
+        Ok(n as usize)
+    }
+
+    /// `Trainer::train` (`trainer.rs:267-327`) with `Trainer::post_process` for all members in lockstep in the compiled loop
+    /// `bdr_trainer_train_cgroup_post`: member `i` on `envs[i]` - the C view of an environment that writes rows of
+    /// `obs_dtypes[i]` (`BDR_DTYPE_F32` / `BDR_DTYPE_F64`) and `obs_row_bytes[i]` bytes and reads one f32 action row - and
+    /// `buffers[i]`; one group sample, one group push and at most one group opt per iteration.  `config.act_row_bytes` must be
+    /// `4 * act_dim`.  Post-processing as [`Self::train_offline`]: with both intervals 0, `evaluators` and `model_dirs` may be empty.
+    #[allow(clippy::too_many_arguments)]
+    pub fn train(
+        &mut self,
+        envs: &[ffi::bdr_env_vtable],
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        obs_row_bytes: &[u64],
+        obs_dtypes: &[i32],
+        config: &ffi::bdr_trainer_config,
+        evaluators: &[ffi::bdr_evaluator],
+        eval_interval: usize,
+        save_interval: usize,
+        model_dirs: &[&Path],
+    ) -> Result<Vec<ffi::bdr_trainer_stats>> {
+        let n = self.members.len();
+        if envs.len() != n || obs_row_bytes.len() != n || obs_dtypes.len() != n {
+            return Err(anyhow!("{} members need {} environments, row sizes and dtypes", n, n));
+        }
+        if (eval_interval > 0 && evaluators.len() != n) || ((eval_interval > 0 || save_interval > 0) && model_dirs.len() != n) {
+            return Err(anyhow!("{} members need {} evaluators and model directories", n, n));
+        }
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut ops: ffi::bdr_cgroup_trainer_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_sac_group_ctrainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
+        let mut dirs = Vec::with_capacity(n);
+        for d in model_dirs {
+            dirs.push(CString::new(d.to_string_lossy().as_bytes())?);
+        }
+        let mut dir_ptrs: Vec<*const c_char> = dirs.iter().map(|d| d.as_ptr()).collect();
+        // SAFETY: bdr_candle_sac_group_trainer_post_default fills every field.
+        let mut post: ffi::bdr_bc_group_trainer_post = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_sac_group_trainer_post_default(&mut post, self.g) };
+        post.eval_interval = eval_interval as u64;
+        post.save_interval = save_interval as u64;
+        post.evaluators = if evaluators.is_empty() { std::ptr::null() } else { evaluators.as_ptr() };
+        post.model_dirs = if dir_ptrs.is_empty() { std::ptr::null_mut() } else { dir_ptrs.as_mut_ptr() };
+        let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
+        check(unsafe {
+            ffi::bdr_trainer_train_cgroup_post(
+                config,
+                obs_row_bytes.as_ptr(),
+                obs_dtypes.as_ptr(),
+                &ops,
+                envs.as_ptr(),
+                &post,
+                None,
+                std::ptr::null_mut(),
+                stats.as_mut_ptr(),
+            )
+        })?;
+        self.sync()?;
+        Ok(stats)
+    }
+
 
     /// Waits for everything the group and its members have enqueued (`bdr_candle_sac_group_sync`).
     pub fn sync(&mut self) -> Result<()> {

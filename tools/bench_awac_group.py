@@ -16,7 +16,10 @@ one.  Writes one JSON document (default profiles/bench_awac_group.json).
 --eval  AwacGroup.evaluate against Evaluator.evaluate member after member, 4 episodes of 10 steps per member on float64 rows with a
         normaliser (a scripted environment in Python on both sides): member-evaluations/s.
 Both follow tools/bench_bc_group.py's protocol for synchronous calls and the same bar at P = 8, and write
-profiles/bench_awac_group_act.json / profiles/bench_awac_group_eval.json."""
+profiles/bench_awac_group_act.json / profiles/bench_awac_group_eval.json.
+--online  the online iteration group sample -> push -> group opt with the grouped push (AwacGroup.push, one launch) against the same
+        iteration with P rb.push calls in the middle, and the push alone (tools/bench_cgroup_online.py has the protocol and the bar);
+        writes profiles/bench_awac_group_online.json."""
 import argparse
 import ctypes as C
 import json
@@ -134,6 +137,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--act", action="store_true", help="the group acting call against a loop of bdr_agent_sample_raw")
     ap.add_argument("--eval", action="store_true", help="AwacGroup.evaluate against Evaluator.evaluate member after member")
+    ap.add_argument("--online", action="store_true", help="the online iteration with the grouped push against P rb.push calls, and the push alone")
     ap.add_argument("--warm", type=int, default=50, help="warm-up calls per side of --act")
     ap.add_argument("--sizes", default="1,8,64")
     ap.add_argument("--window", type=int, default=300)
@@ -141,6 +145,16 @@ def main():
     ap.add_argument("--leg-seconds", type=float, default=0.3)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_awac_group.json"))
     args = ap.parse_args()
+    if args.online:
+        from bench_cgroup_online import online
+        out = os.path.join(os.path.dirname(os.path.abspath(args.out)), "bench_awac_group_online.json")
+        doc = online(args, "awac_group_online", SHAPE, "bdr_awac_group", B.AwacGroup, B.Awac, config, OBS, ACT)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        print("wrote", os.path.relpath(out))
+        return
     if args.act or args.eval:
         for on, run, name in ((args.act, act, "bench_awac_group_act.json"), (args.eval, evaluate, "bench_awac_group_eval.json")):
             if not on: continue
