@@ -12,25 +12,20 @@
 // loss keeps its A + 1 workgroups per member, the critic loss its one: candle::row_sum / row_max run inside a workgroup, in their block
 // order, over the member's rows only.
 // The host half - the members' adoption, the static argument arrays and their keys, the step ring and its slot rule, the round, records,
-// sync - is group_core.hpp's, shared with the BC and the IQL group; AwacGroupKind below says what is AWAC's.  Per step a member has an
-// AwacStep: the gather reads word_pos and size (GatherStepWords at its start), the two reduce + Adam launches its two AdamScalars, the
-// two sample launches its mode and their counter.  The CRITICS' reduce + Adam is the LAST launch of a round that reads the slot, so it
-// alone ends with the ticket and publishes the round's launch number (bg_group_done - all workgroups of its three-dimensional grid
-// counted, behind a barrier every thread reaches: dense_reduce_adam_body returns early for threads past the arena, to the entry, not
-// out of the kernel).
+// sync - is group_core.hpp's, shared with the other groups; the staging of the gather, dense, dW and reduce launches and the walk over
+// the plan are dense_group.hpp's, shared with the IQL and candle SAC groups, which also states the bounds of member, instance and the
+// shared argument arrays.  AwacGroupKind below says what is AWAC's.  Per step a member has an AwacStep: the gather reads word_pos and
+// size (GatherStepWords at its start), the two reduce + Adam launches its two AdamScalars (actor 0, critic 1), the two sample launches
+// its mode and their counter.  The CRITICS track their targets, and their reduce + Adam is the LAST launch of a round that reads the
+// slot, so it alone publishes.
 // The noise rule.  AWAC draws inside the round: act_ = actor.sample(obs) and next_act = actor.sample(next_obs).  fill_step does per
 // member what CandleAgent::opt and Awac::update do on the host, in their order: it reads the member's mode NOW, and in train mode takes
 // B A draws of the member's noise_counter for act_, then B A for next_act (sample_elem's rule; eval mode takes none), then advances
 // step_pi, step_q, n_opts and last_B.  Element t of a sample launch draws at its counter + t, as in k_candle_sample.  The counter is
 // the one the member's own sample / update_on_batch / bdr_agent_draw_noise and the group's acting calls advance: one stream in any
 // interleaving, and bdr_agent_set_train on a member between rounds takes effect in the next round without restaging.
-// Bounds of every new index:
-//   member = blockIdx.y < gridDim.y = P = the length of gather, pack, aloss, closs and of a step slot;
-//   z = blockIdx.z < gridDim.z = nz <= 4 = the instances of a DenseGroupEntry and of a ReduceAdamArgs (2 n_critics <= 4 is a condition
-//   of the group);
-//   the i-th forward / dX launch of the round (stream order) is handed dense + i * P and reads entry i * P + member, i < ndense =
-//   ag_dense_launches: the array holds ndense * P entries; the weight-gradient and reduce + Adam launches of network n (actor 0,
-//   critic 1) are handed dw + n * P / ra + n * P: 2 P entries each; NET < 2 = the AdamScalars of an AwacStep;
+// Bounds of AWAC's own indices:
+//   member = blockIdx.y < gridDim.y = P = the length of pack, aloss and closs;
 //   the sample launch of draw d (act_ 0, next_act 1) is handed sample + d * P: 2 P entries; d < 2 = the counters of an AwacStep; its
 //   t = blockIdx.x * 256 + threadIdx.x is used only where t < n A = B A, the elements of the member's out block ([B][A]) and of the
 //   action columns O .. O + A of its critic input ([B][ldq], O + A <= ldq); the draw index counter + t is a 64-bit sum;
@@ -46,8 +41,6 @@
 #include "candle_act_group.hpp"
 #include "group_core.hpp"
 #include "awac_group_plan.hpp"
-
-static_assert(AG_DW_GROUP == DW_GROUP && AG_RA_SEGS == RA_SEGS && AG_MAXZ == DG_MAXZ && AG_SHAPE_LAYERS >= BDR_MAX_UNITS + 1, "awac_group_plan.hpp restates these limits");
 
 // the per-step words of one member: the gather's, then the optimizer scalars of actor and critics (AgNetId's order), the mode, and the
 // noise counters of the act_ and the next_act launch
@@ -81,14 +74,13 @@ __global__ __launch_bounds__(256) void k_awac_sample_group(const BDR_CONST_AS Ca
     e.train = st.train; e.seed = a.e.seed; e.counter = d ? st.counter[1] : st.counter[0]; e.z = nullptr; e.mlp2 = a.e.mlp2;
     candle_sample_body(a, e);
 }
-// reduce + Adam of network NET of every member, instance z = blockIdx.z: the optimizer scalars of this step come from the member's
-// staging slot; the critics track their targets at the member's own tau (a.tau / a.omt of its entry), are the last reader of the slot
+// reduce + Adam of network NET of every member (dense_group.hpp): the critics track their targets, are the last reader of the slot
 // and publish
 template <int NET>
 __global__ __launch_bounds__(256) void k_awac_reduce_adam_group(const BDR_CONST_AS ReduceAdamArgs* args, const BDR_CONST_AS AwacStep* steps, unsigned* ticket,
                                                                 unsigned* seq_host, unsigned seq)
 {
-    dg_reduce_adam_step<NET, NET == AG_NET_CRITIC>(args, steps, ticket, seq_host, seq);   // (dense_group.hpp: shared with the candle SAC group)
+    dg_reduce_adam_step<NET, NET == AG_NET_CRITIC, NET == AG_NET_CRITIC>(args, steps, ticket, seq_host, seq);
 }
 
 AgShape awac_shape(const Awac* m)
@@ -101,13 +93,10 @@ AgShape awac_shape(const Awac* m)
 }
 
 // ---- host: one member's static arguments, exactly what Awac::update hands its launches --------------------------------------------------
-struct AwacMemberArgs {
-    GatherArgs gather; AwacPackArgs pack;
-    std::vector<DenseGroupEntry> dense;   // the forward and dX launches in stream order
+struct AwacMemberArgs : DenseMemberArgs<2> {   // (dw, dw_grid, ra by AgNetId)
+    AwacPackArgs pack;
     CandleSampleArgs sample[2];           // act_, next_act (train, counter and z are the step's)
     AwacActorArgs aloss; AwacCriticArgs closs;
-    DenseDwSmallGroup dw[2]; int dw_grid[2];   // by AgNetId
-    ReduceAdamArgs ra[2];
 };
 
 // (bs: the batch size; r: the member's ring or view; plan: replay_sample_plan's descriptor of this step)
@@ -122,10 +111,7 @@ void awac_member_static(Awac* m, int bs, const bdr_replay* r, const GatherArgs& 
     const float* next_obs = reinterpret_cast<const float*>(r->b_next);
     const float* act = reinterpret_cast<const float*>(r->b_act);
     o.dense.clear();
-    // the gather: k_gather's arguments as replay_sample_on_stream sets them (word_pos and size are this step's, read from the slot)
-    o.gather = plan;
-    replay_gather_shape(r->obs_bytes, &o.gather.chunks, &o.gather.vec_per_chunk);
-    o.gather.word_pos = 0; o.gather.size = 0;
+    o.gather = dg_gather_static(r, plan);
     o.pack = AwacPackArgs{obs, next_obs, act, O, A, bs, m->x_o, m->x_no, pn.L[0].Kp, m->xq, m->xq_pi, m->xq_next, qn.L[0].Kp};
     // CandleAgent::sample_pack with the static half of sample_elem (no host draws under a group: z null)
     const auto sample = [&](const float* mean, float* out, float* xqd) {
@@ -191,7 +177,7 @@ void awac_member_static(Awac* m, int bs, const bdr_replay* r, const GatherArgs& 
 using AwacActKind = CandleActKind<Awac>;   // group acting (candle_act_group.hpp)
 
 // ---- what is AWAC's of the group core (group_core.hpp) ---------------------------------------------------------------------------------
-struct AwacGroupKind {
+struct AwacGroupKind : DenseRound<2, AG_K_DW, AG_K_REDUCE_ADAM> {
     using Member = Awac; using Shape = AgShape; using Launch = AgLaunch; using Step = AwacStep; using MemberArgs = AwacMemberArgs; using PlanMember = AgMember;
     using Act = AwacActKind;
     static constexpr const char *KIND = "awac", *A = "an AWAC", *NAME = "AWAC", *CAP_MSG = "cap_per_member must hold the eight keys of an AWAC record";
@@ -220,81 +206,37 @@ struct AwacGroupKind {
     }
     static void member_static(Awac* m, int bs, const bdr_replay* r, const GatherArgs& plan, AwacMemberArgs& o) { awac_member_static(m, bs, r, plan, o); }
 
-    int ndense = 0;   // forward and dX launches of a round
-    StagedArray<GatherArgs> gather; StagedArray<AwacPackArgs> pack; StagedArray<AwacActorArgs> aloss; StagedArray<AwacCriticArgs> closs;
-    StagedArray<DenseGroupEntry> dense;                                   // [ndense][P] (launch order)
-    StagedArray<CandleSampleArgs> sample;                                 // [2][P]: act_, next_act
-    StagedArray<DenseDwSmallGroup> dw; StagedArray<ReduceAdamArgs> ra;   // [2][P] by AgNetId
+    static constexpr DgReduceEntry<AwacStep> RA[] = {k_awac_reduce_adam_group<AG_NET_ACTOR>, k_awac_reduce_adam_group<AG_NET_CRITIC>};
+    StagedArray<AwacPackArgs> pack; StagedArray<AwacActorArgs> aloss; StagedArray<AwacCriticArgs> closs;   // [P]
+    StagedArray<CandleSampleArgs> sample;                                                                  // [2][P]: act_, next_act
     hipError_t allocate(const AgShape& s, size_t P)
     {
-        ndense = ag_dense_launches(s.critic.n_layers, s.actor.n_layers);
-        hipError_t e = staged_resize(P, gather, pack);
-        if (e == hipSuccess) e = dense.resize((size_t)ndense * P);
-        if (e == hipSuccess) e = staged_resize(P, aloss, closs);
-        if (e == hipSuccess) e = sample.resize(2 * P);
-        return e == hipSuccess ? staged_resize(2 * P, dw, ra) : e;
+        return allocate_round(ag_dense_launches(s.critic.n_layers, s.actor.n_layers), P, pack, [&] {
+            const hipError_t e = staged_resize(P, aloss, closs);
+            return e == hipSuccess ? sample.resize(2 * P) : e;
+        });
     }
     // member p's arguments into the staging arrays
     void stage(size_t p, size_t P, const AwacMemberArgs& o)
     {
-        gather[p] = o.gather; pack[p] = o.pack; aloss[p] = o.aloss; closs[p] = o.closs;
-        for (int i = 0; i < ndense; ++i) dense[(size_t)i * P + p] = o.dense[i];
-        for (int n = 0; n < 2; ++n) { sample[(size_t)n * P + p] = o.sample[n]; dw[(size_t)n * P + p] = o.dw[n]; ra[(size_t)n * P + p] = o.ra[n]; }
+        stage_dense(p, P, o);
+        pack[p] = o.pack; aloss[p] = o.aloss; closs[p] = o.closs;
+        for (int d = 0; d < 2; ++d) sample[(size_t)d * P + p] = o.sample[d];
     }
     hipError_t upload() { return staged_upload(gather, pack, dense, sample, aloss, closs, dw, ra); }
-    int32_t check_static(const AgLaunch* plan, int n_launches, const AwacMemberArgs& o, uint32_t p) const
+    int32_t launch(const GroupCore<AwacGroupKind>& g, size_t P, const AwacStep* steps_dev, unsigned seq_no) const { return dg_round_launch(g, P, steps_dev, seq_no, *this); }
+    // AWAC's own launches of a round
+    int32_t launch_own(const AgLaunch& l, int n, size_t P, dim3 grid, dim3 block, const BDR_CONST_AS AwacStep* st, hipStream_t stream) const
     {
-        BDR_REQUIRE((int)o.dense.size() == ndense, "member %u: %d dense launches, the plan has %d", p, (int)o.dense.size(), ndense);
-        for (int n = 0; n < n_launches; ++n)
-            if (plan[n].kernel == AG_K_DW) {
-                const int id = plan[n].net;
-                BDR_REQUIRE(o.dw_grid[id] == (int)plan[n].gx, "member %u: the weight-gradient grid of network %d (%d) differs from the plan's (%u)", p, id, o.dw_grid[id],
-                            plan[n].gx);
-            }
-        return BDR_OK;
-    }
-    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
-    int32_t launch(const GroupCore<AwacGroupKind>& g, size_t P, const AwacStep* steps_dev, unsigned seq_no) const
-    {
-        int nd = 0;
-        hipStream_t stream = g.stream;
-        for (int n = 0; n < g.n_launches; ++n) {
-            const AgLaunch& l = g.plan[n];
-            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
-            const auto* st = (const BDR_CONST_AS AwacStep*)steps_dev;
-            switch (l.kernel) {
-            case AG_K_GATHER:
-                BDR_TRY(replay_gather_group(stream, gather.d.get(), steps_dev, (uint32_t)sizeof(AwacStep), (uint32_t)P, (uint64_t)g.shape.batch, (uint64_t)g.shape.obs_dim * 4));
-                break;
-            case AG_K_PACK: hipLaunchKernelGGL(k_awac_pack_group, grid, block, 0, stream, (const BDR_CONST_AS AwacPackArgs*)pack.d.get()); break;
-            case AG_K_FWD:
-                BDR_REQUIRE(nd < ndense, "AWAC group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<false>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
-                break;
-            case AG_K_DX:
-                BDR_REQUIRE(nd < ndense, "AWAC group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<true>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
-                break;
-            case AG_K_SAMPLE:
-                BDR_REQUIRE(l.layer == 0 || l.layer == 1, "AWAC group round: launch %d of the plan names no draw", n);
-                hipLaunchKernelGGL(k_awac_sample_group, grid, block, 0, stream, (const BDR_CONST_AS CandleSampleArgs*)(sample.d.get() + (size_t)l.layer * P), st, l.layer);
-                break;
-            case AG_K_ACTOR_LOSS: hipLaunchKernelGGL(k_awac_actor_loss_group, grid, block, 0, stream, (const BDR_CONST_AS AwacActorArgs*)aloss.d.get()); break;
-            case AG_K_CRITIC_LOSS: hipLaunchKernelGGL(k_awac_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS AwacCriticArgs*)closs.d.get()); break;
-            case AG_K_DW:
-                BDR_REQUIRE(l.net >= 0 && l.net < 2, "AWAC group round: launch %d of the plan names no network", n);
-                hipLaunchKernelGGL(k_dense_dw_small_members, grid, block, 0, stream, (const BDR_CONST_AS DenseDwSmallGroup*)(dw.d.get() + (size_t)l.net * P));
-                break;
-            case AG_K_REDUCE_ADAM: {
-                BDR_REQUIRE(l.net >= 0 && l.net < 2, "AWAC group round: launch %d of the plan names no network", n);
-                const auto* a = (const BDR_CONST_AS ReduceAdamArgs*)(ra.d.get() + (size_t)l.net * P);
-                if (l.net == AG_NET_ACTOR) hipLaunchKernelGGL(k_awac_reduce_adam_group<AG_NET_ACTOR>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
-                else hipLaunchKernelGGL(k_awac_reduce_adam_group<AG_NET_CRITIC>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
-                break;
-            }
-            default: return fail(BDR_ERR_INVALID, "AWAC group round: launch %d of the plan names no kernel", n);
-            }
-            BDR_HIP(hipGetLastError());
+        switch (l.kernel) {
+        case AG_K_PACK: hipLaunchKernelGGL(k_awac_pack_group, grid, block, 0, stream, (const BDR_CONST_AS AwacPackArgs*)pack.d.get()); break;
+        case AG_K_SAMPLE:
+            BDR_REQUIRE(l.layer == 0 || l.layer == 1, "AWAC group round: launch %d of the plan names no draw", n);
+            hipLaunchKernelGGL(k_awac_sample_group, grid, block, 0, stream, (const BDR_CONST_AS CandleSampleArgs*)(sample.d.get() + (size_t)l.layer * P), st, l.layer);
+            break;
+        case AG_K_ACTOR_LOSS: hipLaunchKernelGGL(k_awac_actor_loss_group, grid, block, 0, stream, (const BDR_CONST_AS AwacActorArgs*)aloss.d.get()); break;
+        case AG_K_CRITIC_LOSS: hipLaunchKernelGGL(k_awac_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS AwacCriticArgs*)closs.d.get()); break;
+        default: return fail(BDR_ERR_INVALID, "AWAC group round: launch %d of the plan names no kernel", n);
         }
         return BDR_OK;
     }

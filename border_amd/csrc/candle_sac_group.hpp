@@ -14,12 +14,12 @@
 // gradient keeps its A + 1 workgroups per member, alpha and the critic loss their one: candle::row_sum runs inside a workgroup, in its
 // block order, over the member's rows only; the butterfly of sample + logp stays inside the G lanes of one row of one member.
 // The host half - the members' adoption, the static argument arrays and their keys, the step ring and its slot rule, the round,
-// records, sync - is group_core.hpp's, shared with the BC, IQL and AWAC groups; CandleSacGroupKind below says what is SAC's.  Per step
-// a member has a CsacStep: the gather reads word_pos and size (GatherStepWords at its start), the two reduce + Adam launches and the
-// alpha launch their AdamScalars, the two sample + logp launches the mode and their counter.  The CRITICS' reduce + Adam is the LAST
-// launch of a round that reads the slot, so it alone ends with the ticket and publishes the round's launch number (bg_group_done - all
-// workgroups of its three-dimensional grid counted, behind a barrier every thread reaches: dense_reduce_adam_body returns early for
-// threads past the arena, to the entry, not out of the kernel).
+// records, sync - is group_core.hpp's, shared with the other groups; the staging of the gather, dense, dW and reduce launches and the
+// walk over the plan are dense_group.hpp's, shared with the IQL and AWAC groups, which also states the bounds of member, instance and
+// the shared argument arrays.  CandleSacGroupKind below says what is SAC's.  Per step a member has a CsacStep: the gather reads
+// word_pos and size (GatherStepWords at its start), the two reduce + Adam launches (actor 0, critic 1) and the alpha launch their
+// AdamScalars, the two sample + logp launches the mode and their counter.  The CRITICS track their targets, and their reduce + Adam
+// is the LAST launch of a round that reads the slot, so it alone publishes.
 // What a SAC round adds to the groups before it.  (1) A third optimizer: the entropy coefficient's AdamW step, per member Fix or Auto
 // (auto_mode and target_entropy are static words of the member's alpha entry; its AdamScalars are step words, written in Auto mode
 // only and read in Auto mode only).  (2) The action gradient: the critics' input-gradient chain runs through k_dense_small_members_z<dx>
@@ -35,14 +35,9 @@
 // logp launch draws at its counter + t, as in k_csac_sample_logp.  The counter is the one the member's own sample / update_on_batch /
 // bdr_agent_draw_noise and the group's acting calls advance: one stream in any interleaving, and bdr_agent_set_train on a member
 // between rounds takes effect in the next round without restaging.
-// Bounds of every new index:
-//   member = blockIdx.y < gridDim.y = P = the length of gather, pack, alpha, qmin, agrad, closs and of a step slot;
-//   z = blockIdx.z < gridDim.z = nz <= 4 = the instances of a DenseGroupEntry and of a ReduceAdamArgs (2 n_critics <= 4 is a condition
-//   of the group);
-//   the i-th forward / dX launch of the round (stream order) is handed dense + i * P and reads entry i * P + member, i < ndense =
-//   cs_dense_launches: the array holds ndense * P entries; the weight-gradient and reduce + Adam launches of network n (actor 0,
-//   critic 1) are handed dw + n * P / ra + n * P: 2 P entries each; NET < 2, and the alpha entry reads adam[2]: 3 = the AdamScalars of
-//   a CsacStep;
+// Bounds of SAC's own indices:
+//   member = blockIdx.y < gridDim.y = P = the length of pack, alpha, qmin, agrad and closs; the alpha entry reads adam[2] of the three
+//   AdamScalars of a CsacStep;
 //   the sample + logp launch of draw d (a 0, next_a 1) is handed sample + d * P: 2 P entries; d < 2 = the counters of a CsacStep; its
 //   row b = blockIdx.x * (256 / G) + threadIdx.x / G touches memory only where b < B, its column j = g0 + k G only where j < A: the
 //   elements of the member's out and g_* blocks ([B][A]), of logp ([B]), of the mean row ([B][ldm], A <= ldm; Mlp2: A + j < 2 A <= ldm)
@@ -55,8 +50,6 @@
 //   alpha: one workgroup, b < B in row_sum, ent holds 8 floats;  critic loss: one workgroup, b < B, column 0 of [B][ldq] rows;
 //   inside a member every other index is the body's own, with the bounds of the standalone kernel.
 // Memory traffic is plain vector stores, the existing agent-scope atomics of the ticket and st_agent / ld_agent: nothing new.
-// The reduce + Adam entry is awac_group.hpp's over another step type: its body is written once, dg_reduce_adam_step (dense_group.hpp),
-// a template over the step type that both kinds' entries call; AWAC's entries keep their names, register counts and bits.
 // Acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp, which states the bounds of
 // its indices, those of an Mlp2 last layer included) through group_act.hpp; CandleSacActKind below is CandleActKind of a CandleSac.
 #pragma once
@@ -65,8 +58,6 @@
 #include "group_core.hpp"
 #include "candle_sac_group_plan.hpp"
 
-static_assert(CS_DW_GROUP == DW_GROUP && CS_RA_SEGS == RA_SEGS && CS_MAXZ == DG_MAXZ && CS_SHAPE_LAYERS >= BDR_MAX_UNITS + 1,
-              "candle_sac_group_plan.hpp restates these limits");
 static_assert(CS_ACTOR_MLP3 == BDR_ACTOR_MLP3 && CS_ACTOR_MLP2 == BDR_ACTOR_MLP2, "candle_sac_group_plan.hpp restates the actor kinds");
 
 // the per-step words of one member: the gather's, then the optimizer scalars of actor, critics (CsNetId's order) and the entropy
@@ -107,14 +98,13 @@ __global__ __launch_bounds__(1024) void k_csac_critic_loss_group(const BDR_CONST
     __shared__ float red[32];
     csac_critic_loss_body(args[blockIdx.y], red);
 }
-// reduce + Adam of network NET of every member, instance z = blockIdx.z: the optimizer scalars of this step come from the member's
-// staging slot; the critics track their targets at the member's own tau (a.tau / a.omt of its entry), are the last reader of the slot
+// reduce + Adam of network NET of every member (dense_group.hpp): the critics track their targets, are the last reader of the slot
 // and publish
 template <int NET>
 __global__ __launch_bounds__(256) void k_csac_reduce_adam_group(const BDR_CONST_AS ReduceAdamArgs* args, const BDR_CONST_AS CsacStep* steps, unsigned* ticket,
                                                                 unsigned* seq_host, unsigned seq)
 {
-    dg_reduce_adam_step<NET, NET == CS_NET_CRITIC>(args, steps, ticket, seq_host, seq);   // (dense_group.hpp: shared with the AWAC group)
+    dg_reduce_adam_step<NET, NET == CS_NET_CRITIC, NET == CS_NET_CRITIC>(args, steps, ticket, seq_host, seq);
 }
 
 CsShape csac_shape(const CandleSac* m)
@@ -127,13 +117,10 @@ CsShape csac_shape(const CandleSac* m)
 }
 
 // ---- host: one member's static arguments, exactly what CandleSac::update hands its launches --------------------------------------------
-struct CsacMemberArgs {
-    GatherArgs gather; CsacPackArgs pack;
-    std::vector<DenseGroupEntry> dense;   // the forward and dX launches in stream order
+struct CsacMemberArgs : DenseMemberArgs<2> {   // (dw, dw_grid, ra by CsNetId)
+    CsacPackArgs pack;
     CsacSampleArgs sample[2];             // a (gradient form), next_a (train, counter and z are the step's)
     CsacAlphaArgs alpha; CsacQminArgs qmin; CsacActorArgs agrad; CsacCriticArgs closs;
-    DenseDwSmallGroup dw[2]; int dw_grid[2];   // by CsNetId
-    ReduceAdamArgs ra[2];
 };
 
 // (bs: the batch size; r: the member's ring or view; plan: replay_sample_plan's descriptor of this step)
@@ -149,10 +136,7 @@ void csac_member_static(CandleSac* m, int bs, const bdr_replay* r, const GatherA
     const float* next_obs = reinterpret_cast<const float*>(r->b_next);
     const float* act = reinterpret_cast<const float*>(r->b_act);
     o.dense.clear();
-    // the gather: k_gather's arguments as replay_sample_on_stream sets them (word_pos and size are this step's, read from the slot)
-    o.gather = plan;
-    replay_gather_shape(r->obs_bytes, &o.gather.chunks, &o.gather.vec_per_chunk);
-    o.gather.word_pos = 0; o.gather.size = 0;
+    o.gather = dg_gather_static(r, plan);
     o.pack = CsacPackArgs{obs, next_obs, act, O, A, bs, m->x_o, m->x_no, pn.L[0].Kp, m->xq, m->xq_pi, m->xq_next, qn.L[0].Kp};
     // CandleSac::sample_logp with the static half of sample_elem (no host draws under a group: z null)
     const auto sample = [&](const float* last, float* out, float* xqd, float* logp, bool grads) {
@@ -235,7 +219,7 @@ void csac_member_static(CandleSac* m, int bs, const bdr_replay* r, const GatherA
 using CandleSacActKind = CandleActKind<CandleSac>;   // group acting (candle_act_group.hpp)
 
 // ---- what is SAC's of the group core (group_core.hpp) ----------------------------------------------------------------------------------
-struct CandleSacGroupKind {
+struct CandleSacGroupKind : DenseRound<2, CS_K_DW, CS_K_REDUCE_ADAM> {
     using Member = CandleSac; using Shape = CsShape; using Launch = CsLaunch; using Step = CsacStep; using MemberArgs = CsacMemberArgs; using PlanMember = CsMember;
     using Act = CandleSacActKind;
     static constexpr const char *KIND = "candle_sac", *A = "a candle SAC", *NAME = "SAC (candle)", *CAP_MSG = "cap_per_member must hold the three keys of a SAC record";
@@ -268,89 +252,40 @@ struct CandleSacGroupKind {
     }
     static void member_static(CandleSac* m, int bs, const bdr_replay* r, const GatherArgs& plan, CsacMemberArgs& o) { csac_member_static(m, bs, r, plan, o); }
 
-    int ndense = 0;   // forward and dX launches of a round
-    StagedArray<GatherArgs> gather; StagedArray<CsacPackArgs> pack; StagedArray<CsacAlphaArgs> alpha; StagedArray<CsacQminArgs> qmin;
-    StagedArray<CsacActorArgs> agrad; StagedArray<CsacCriticArgs> closs;
-    StagedArray<DenseGroupEntry> dense;                                   // [ndense][P] (launch order)
-    StagedArray<CsacSampleArgs> sample;                                   // [2][P]: a, next_a
-    StagedArray<DenseDwSmallGroup> dw; StagedArray<ReduceAdamArgs> ra;   // [2][P] by CsNetId
+    static constexpr DgReduceEntry<CsacStep> RA[] = {k_csac_reduce_adam_group<CS_NET_ACTOR>, k_csac_reduce_adam_group<CS_NET_CRITIC>};
+    StagedArray<CsacPackArgs> pack; StagedArray<CsacAlphaArgs> alpha; StagedArray<CsacQminArgs> qmin; StagedArray<CsacActorArgs> agrad;   // [P]
+    StagedArray<CsacCriticArgs> closs;                                                                                                    // [P]
+    StagedArray<CsacSampleArgs> sample;                                                                                                   // [2][P]: a, next_a
     hipError_t allocate(const CsShape& s, size_t P)
     {
-        ndense = cs_dense_launches(s.critic.n_layers, s.actor.n_layers);
-        hipError_t e = staged_resize(P, gather, pack);
-        if (e == hipSuccess) e = dense.resize((size_t)ndense * P);
-        if (e == hipSuccess) e = staged_resize(P, alpha, qmin);
-        if (e == hipSuccess) e = staged_resize(P, agrad, closs);
-        if (e == hipSuccess) e = sample.resize(2 * P);
-        return e == hipSuccess ? staged_resize(2 * P, dw, ra) : e;
+        return allocate_round(cs_dense_launches(s.critic.n_layers, s.actor.n_layers), P, pack, [&] {
+            const hipError_t e = staged_resize(P, alpha, qmin, agrad, closs);
+            return e == hipSuccess ? sample.resize(2 * P) : e;
+        });
     }
     // member p's arguments into the staging arrays
     void stage(size_t p, size_t P, const CsacMemberArgs& o)
     {
-        gather[p] = o.gather; pack[p] = o.pack; alpha[p] = o.alpha; qmin[p] = o.qmin; agrad[p] = o.agrad; closs[p] = o.closs;
-        for (int i = 0; i < ndense; ++i) dense[(size_t)i * P + p] = o.dense[i];
-        for (int n = 0; n < 2; ++n) { sample[(size_t)n * P + p] = o.sample[n]; dw[(size_t)n * P + p] = o.dw[n]; ra[(size_t)n * P + p] = o.ra[n]; }
+        stage_dense(p, P, o);
+        pack[p] = o.pack; alpha[p] = o.alpha; qmin[p] = o.qmin; agrad[p] = o.agrad; closs[p] = o.closs;
+        for (int d = 0; d < 2; ++d) sample[(size_t)d * P + p] = o.sample[d];
     }
-    hipError_t upload()
+    hipError_t upload() { return staged_upload(gather, pack, dense, sample, alpha, qmin, agrad, closs, dw, ra); }
+    int32_t launch(const GroupCore<CandleSacGroupKind>& g, size_t P, const CsacStep* steps_dev, unsigned seq_no) const { return dg_round_launch(g, P, steps_dev, seq_no, *this); }
+    // SAC's own launches of a round
+    int32_t launch_own(const CsLaunch& l, int n, size_t P, dim3 grid, dim3 block, const BDR_CONST_AS CsacStep* st, hipStream_t stream) const
     {
-        const hipError_t e = staged_upload(gather, pack, dense, sample, alpha, qmin, agrad, closs);
-        return e == hipSuccess ? staged_upload(dw, ra) : e;
-    }
-    int32_t check_static(const CsLaunch* plan, int n_launches, const CsacMemberArgs& o, uint32_t p) const
-    {
-        BDR_REQUIRE((int)o.dense.size() == ndense, "member %u: %d dense launches, the plan has %d", p, (int)o.dense.size(), ndense);
-        for (int n = 0; n < n_launches; ++n)
-            if (plan[n].kernel == CS_K_DW) {
-                const int id = plan[n].net;
-                BDR_REQUIRE(o.dw_grid[id] == (int)plan[n].gx, "member %u: the weight-gradient grid of network %d (%d) differs from the plan's (%u)", p, id, o.dw_grid[id],
-                            plan[n].gx);
-            }
-        return BDR_OK;
-    }
-    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
-    int32_t launch(const GroupCore<CandleSacGroupKind>& g, size_t P, const CsacStep* steps_dev, unsigned seq_no) const
-    {
-        int nd = 0;
-        hipStream_t stream = g.stream;
-        for (int n = 0; n < g.n_launches; ++n) {
-            const CsLaunch& l = g.plan[n];
-            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
-            const auto* st = (const BDR_CONST_AS CsacStep*)steps_dev;
-            switch (l.kernel) {
-            case CS_K_GATHER:
-                BDR_TRY(replay_gather_group(stream, gather.d.get(), steps_dev, (uint32_t)sizeof(CsacStep), (uint32_t)P, (uint64_t)g.shape.batch, (uint64_t)g.shape.obs_dim * 4));
-                break;
-            case CS_K_PACK: hipLaunchKernelGGL(k_csac_pack_group, grid, block, 0, stream, (const BDR_CONST_AS CsacPackArgs*)pack.d.get()); break;
-            case CS_K_FWD:
-                BDR_REQUIRE(nd < ndense, "SAC group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<false>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
-                break;
-            case CS_K_DX:
-                BDR_REQUIRE(nd < ndense, "SAC group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<true>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
-                break;
-            case CS_K_SAMPLE_LOGP:
-                BDR_REQUIRE(l.layer == 0 || l.layer == 1, "SAC group round: launch %d of the plan names no draw", n);
-                hipLaunchKernelGGL(k_csac_sample_logp_group, grid, block, 0, stream, (const BDR_CONST_AS CsacSampleArgs*)(sample.d.get() + (size_t)l.layer * P), st, l.layer);
-                break;
-            case CS_K_ALPHA: hipLaunchKernelGGL(k_csac_alpha_group, grid, block, 0, stream, (const BDR_CONST_AS CsacAlphaArgs*)alpha.d.get(), st); break;
-            case CS_K_QMIN: hipLaunchKernelGGL(k_csac_qmin_group, grid, block, 0, stream, (const BDR_CONST_AS CsacQminArgs*)qmin.d.get()); break;
-            case CS_K_ACTOR_GRAD: hipLaunchKernelGGL(k_csac_actor_grad_group, grid, block, 0, stream, (const BDR_CONST_AS CsacActorArgs*)agrad.d.get()); break;
-            case CS_K_CRITIC_LOSS: hipLaunchKernelGGL(k_csac_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS CsacCriticArgs*)closs.d.get()); break;
-            case CS_K_DW:
-                BDR_REQUIRE(l.net >= 0 && l.net < 2, "SAC group round: launch %d of the plan names no network", n);
-                hipLaunchKernelGGL(k_dense_dw_small_members, grid, block, 0, stream, (const BDR_CONST_AS DenseDwSmallGroup*)(dw.d.get() + (size_t)l.net * P));
-                break;
-            case CS_K_REDUCE_ADAM: {
-                BDR_REQUIRE(l.net >= 0 && l.net < 2, "SAC group round: launch %d of the plan names no network", n);
-                const auto* a = (const BDR_CONST_AS ReduceAdamArgs*)(ra.d.get() + (size_t)l.net * P);
-                if (l.net == CS_NET_ACTOR) hipLaunchKernelGGL(k_csac_reduce_adam_group<CS_NET_ACTOR>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
-                else hipLaunchKernelGGL(k_csac_reduce_adam_group<CS_NET_CRITIC>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
-                break;
-            }
-            default: return fail(BDR_ERR_INVALID, "SAC group round: launch %d of the plan names no kernel", n);
-            }
-            BDR_HIP(hipGetLastError());
+        switch (l.kernel) {
+        case CS_K_PACK: hipLaunchKernelGGL(k_csac_pack_group, grid, block, 0, stream, (const BDR_CONST_AS CsacPackArgs*)pack.d.get()); break;
+        case CS_K_SAMPLE_LOGP:
+            BDR_REQUIRE(l.layer == 0 || l.layer == 1, "SAC group round: launch %d of the plan names no draw", n);
+            hipLaunchKernelGGL(k_csac_sample_logp_group, grid, block, 0, stream, (const BDR_CONST_AS CsacSampleArgs*)(sample.d.get() + (size_t)l.layer * P), st, l.layer);
+            break;
+        case CS_K_ALPHA: hipLaunchKernelGGL(k_csac_alpha_group, grid, block, 0, stream, (const BDR_CONST_AS CsacAlphaArgs*)alpha.d.get(), st); break;
+        case CS_K_QMIN: hipLaunchKernelGGL(k_csac_qmin_group, grid, block, 0, stream, (const BDR_CONST_AS CsacQminArgs*)qmin.d.get()); break;
+        case CS_K_ACTOR_GRAD: hipLaunchKernelGGL(k_csac_actor_grad_group, grid, block, 0, stream, (const BDR_CONST_AS CsacActorArgs*)agrad.d.get()); break;
+        case CS_K_CRITIC_LOSS: hipLaunchKernelGGL(k_csac_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS CsacCriticArgs*)closs.d.get()); break;
+        default: return fail(BDR_ERR_INVALID, "SAC group round: launch %d of the plan names no kernel", n);
         }
         return BDR_OK;
     }

@@ -17,11 +17,7 @@
 namespace bdr {
 
 constexpr int CS_SHAPE_LAYERS = GP_SHAPE_LAYERS;
-constexpr int CS_DW_GROUP = 16;     // jobs of one grouped weight-gradient launch (dense.hpp DW_GROUP)
-constexpr int CS_RA_SEGS = 12;      // segments of k_dense_reduce_adam (dense.hpp RA_SEGS)
-constexpr int CS_MAXZ = 4;          // instances of one dense launch (dense.hpp DenseArgsZ, RA_INST)
 constexpr int CS_ACTOR_MLP3 = 0, CS_ACTOR_MLP2 = 1;   // BDR_ACTOR_* (include/border_amd.h)
-constexpr unsigned CS_MAX_MEMBERS = GP_MAX_MEMBERS;
 
 // ---- what the rule reads of a member ------------------------------------------------------------------------------------------------
 using CsNet = GpNet;   // one network (group_plan_common.hpp)
@@ -41,24 +37,21 @@ inline int cs_actor_segs(const CsShape& s) { return s.actor.n_layers + (s.actor_
 // why a candle SAC agent of this shape cannot be a member of any group (nullptr: it can)
 inline const char* cs_shape_ineligible(const CsShape& s)
 {
-    for (const CsNet* n : {&s.critic, &s.actor})
-        if (n->n_layers < 1 || n->n_layers > CS_SHAPE_LAYERS) return "a network has no layer, or more than 16";
-    if (s.actor_kind != CS_ACTOR_MLP3 && s.actor_kind != CS_ACTOR_MLP2) return "unknown actor kind";
-    if (s.n_critics < 1) return "n_critics must be positive";
-    if (2 * s.n_critics > CS_MAXZ)
-        return "n_critics > 2: the online critics on (obs | act) and on (obs | a) run as the 2 n_critics instances of one launch per layer, and a launch holds four";
-    if (s.n_critics * s.critic.n_layers > CS_DW_GROUP) return "n_critics x critic layers beyond the 16 jobs of one grouped weight-gradient launch";
-    if (s.critic.n_layers > CS_RA_SEGS || cs_actor_segs(s) > CS_RA_SEGS)
-        return "more layers than one reduce + Adam launch has segments (12; an Mlp3 actor's head2 is one more)";
-    if (s.batch < 2 || s.batch > 65536) return "batch size out of range (SAC needs at least 2 rows)";
-    if (s.obs_dim < 1 || s.act_dim < 1) return "bad obs/act dims";
-    return nullptr;
+    GpShapeOwn own{};
+    if (s.actor_kind != CS_ACTOR_MLP3 && s.actor_kind != CS_ACTOR_MLP2) own.first = "unknown actor kind";
+    own.two_nc = "n_critics > 2: the online critics on (obs | act) and on (obs | a) run as the 2 n_critics instances of one launch per layer, and a launch holds four";
+    if (s.critic.n_layers > GP_RA_SEGS || cs_actor_segs(s) > GP_RA_SEGS)
+        own.segs = "more layers than one reduce + Adam launch has segments (12; an Mlp3 actor's head2 is one more)";
+    if (s.batch < 2 || s.batch > 65536) own.batch = "batch size out of range (SAC needs at least 2 rows)";
+    return gp_shape_ineligible({&s.critic, &s.actor}, s.n_critics, s.critic.n_layers, s.obs_dim, s.act_dim, own);
 }
 
+// gather .. dX under GpKernel's numbers, SAC's own behind them, the weight gradient and reduce + Adam last
 enum CsKernel {
-    CS_K_GATHER = 0, CS_K_PACK, CS_K_FWD, CS_K_DX, CS_K_SAMPLE_LOGP, CS_K_ALPHA, CS_K_QMIN, CS_K_ACTOR_GRAD, CS_K_CRITIC_LOSS, CS_K_DW, CS_K_REDUCE_ADAM, CS_K_COUNT
+    CS_K_GATHER = GP_K_GATHER, CS_K_PACK = GP_K_PACK, CS_K_FWD = GP_K_FWD, CS_K_DX = GP_K_DX,
+    CS_K_SAMPLE_LOGP = GP_K_OWN, CS_K_ALPHA, CS_K_QMIN, CS_K_ACTOR_GRAD, CS_K_CRITIC_LOSS, CS_K_DW, CS_K_REDUCE_ADAM, CS_K_COUNT
 };
-enum CsNetId { CS_NET_NONE = -1, CS_NET_ACTOR = 0, CS_NET_CRITIC = 1 };
+enum CsNetId { CS_NET_NONE = GP_NET_NONE, CS_NET_ACTOR = 0, CS_NET_CRITIC = 1 };
 inline const char* cs_kernel_name(int k)
 {
     static const char* const names[] = {"k_gather_group", "k_csac_pack_group", "k_dense_small_members_z<fwd>", "k_dense_small_members_z<dx>",
@@ -66,21 +59,13 @@ inline const char* cs_kernel_name(int k)
                                         "k_csac_critic_loss_group", "k_dense_dw_small_members", "k_csac_reduce_adam_group"};
     return k >= 0 && k < CS_K_COUNT ? names[k] : "?";
 }
-// net: the network a dense / dW / reduce / loss launch serves (CsNetId), layer: the layer a forward / dX launch serves, the draw (0: a,
-// 1: next_a) of a sample + logp launch, else -1; gz = the instances nz of the launch
-struct CsLaunch { int kernel, net, layer; unsigned gx, gy, gz, threads; };
+using CsLaunch = GpLaunch;   // net: CsNetId; layer of a sample + logp launch: the draw (0: a, 1: next_a)
 constexpr int CS_MAX_LAUNCHES = 7 * CS_SHAPE_LAYERS + 10;
 
 // launches of one round, whatever P is
 inline int cs_launch_count(int Lq, int Lp) { return 3 * Lp + 4 * Lq + 10; }
 // forward and dX launches of one round: the entries of the dense argument array are (this) x P
 inline int cs_dense_launches(int Lq, int Lp) { return 3 * Lp + 4 * Lq - 2; }
-// k_csac_pack's grid (CandleSac::update): one thread per element of [B][obs + act], at most 2048 workgroups (the body strides by the grid)
-inline unsigned cs_pack_grid(const CsShape& s)
-{
-    const uint64_t g = ((uint64_t)s.batch * (uint64_t)(s.obs_dim + s.act_dim) + 255) / 256;
-    return (unsigned)(g < 2048 ? g : 2048);
-}
 // lanes per row of k_csac_sample_logp (CandleSac::sample_logp): the smallest power of two that holds act_dim, at most 64
 inline int cs_sample_lanes(int act_dim)
 {
@@ -101,44 +86,29 @@ inline uint64_t cs_actor_arena(const CsShape& s)
 }
 
 // The launches of one update round of P members of shape `s`, in stream order; returns their number (0: no group of that shape).
-// x is the member's own grid everywhere, y the member, z the network instance.
 inline int cs_round_plan(const CsShape& s, unsigned P, CsLaunch* out)
 {
     if (cs_shape_ineligible(s) || P < 1) return 0;
-    const int B = s.batch, NC = s.n_critics;
-    const unsigned RB = (unsigned)((B + 31) / 32);
-    int n = 0;
-    const auto fwd = [&](const CsNet& net, int id, unsigned nz) {
-        for (int i = 0; i < net.n_layers; ++i) out[n++] = CsLaunch{CS_K_FWD, id, i, RB * (unsigned)(net.Np[i] / 32), P, nz, 256};
-    };
-    // the input gradients of layers hi .. lo, from the top
-    const auto dx = [&](const CsNet& net, int id, unsigned nz, int lo) {
-        for (int i = net.n_layers - 1; i >= lo; --i) out[n++] = CsLaunch{CS_K_DX, id, i, RB * (unsigned)(net.Kp[i] / 32), P, nz, 256};
-    };
-    // mlp_backward_step: the input gradients down to layer 1, the grouped weight gradient, reduce + Adam over `arena` floats
-    const auto step = [&](const CsNet& net, int id, unsigned nz, uint64_t arena) {
-        dx(net, id, nz, 1);
-        out[n++] = CsLaunch{CS_K_DW, id, -1, nz * gp_dw_tiles(net, B), P, 1, 256};
-        out[n++] = CsLaunch{CS_K_REDUCE_ADAM, id, -1, (unsigned)((arena / 4 + 255) / 256), P, nz, 256};
-    };
-    out[n++] = CsLaunch{CS_K_GATHER, CS_NET_NONE, -1, (unsigned)B * gp_gather_chunks((uint64_t)s.obs_dim * 4), P, 1, 256};
-    out[n++] = CsLaunch{CS_K_PACK, CS_NET_NONE, -1, cs_pack_grid(s), P, 1, 256};
+    const unsigned NC = (unsigned)s.n_critics;
+    GpPlan p{out, 0, s.batch, P, CS_K_DW, CS_K_REDUCE_ADAM};
+    p.gather(s.obs_dim);
+    p.pack(s.obs_dim + s.act_dim);
     // ---- update_actor
-    fwd(s.actor, CS_NET_ACTOR, 1);                                                              // the actor on obs
-    out[n++] = CsLaunch{CS_K_SAMPLE_LOGP, CS_NET_ACTOR, 0, cs_sample_grid(s), P, 1, 256};       // a, logp, the partials
-    out[n++] = CsLaunch{CS_K_ALPHA, CS_NET_NONE, -1, 1, P, 1, 1024};
-    fwd(s.critic, CS_NET_CRITIC, 2u * (unsigned)NC);                                            // the online critics on (obs | act) and (obs | a)
-    out[n++] = CsLaunch{CS_K_QMIN, CS_NET_CRITIC, -1, (unsigned)((B + 255) / 256), P, 1, 256};
-    dx(s.critic, CS_NET_CRITIC, (unsigned)NC, 0);                                               // dq/da: down to the input layer, which has no mask
-    out[n++] = CsLaunch{CS_K_ACTOR_GRAD, CS_NET_ACTOR, -1, (unsigned)s.act_dim + 1, P, 1, 1024};
-    step(s.actor, CS_NET_ACTOR, 1, cs_actor_arena(s));
+    p.fwd(s.actor, CS_NET_ACTOR, 1);                                              // the actor on obs
+    p.one(CS_K_SAMPLE_LOGP, CS_NET_ACTOR, 0, cs_sample_grid(s), 256);             // a, logp, the partials
+    p.one(CS_K_ALPHA, CS_NET_NONE, -1, 1, 1024);
+    p.fwd(s.critic, CS_NET_CRITIC, 2 * NC);                                       // the online critics on (obs | act) and (obs | a)
+    p.one(CS_K_QMIN, CS_NET_CRITIC, -1, (unsigned)((s.batch + 255) / 256), 256);
+    p.dx(s.critic, CS_NET_CRITIC, NC, 0);                                         // dq/da: down to the input layer, which has no mask
+    p.one(CS_K_ACTOR_GRAD, CS_NET_ACTOR, -1, (unsigned)s.act_dim + 1, 1024);
+    p.step(s.actor, CS_NET_ACTOR, 1, cs_actor_arena(s));
     // ---- update_critic
-    fwd(s.actor, CS_NET_ACTOR, 1);                                                              // the updated actor on next_obs
-    out[n++] = CsLaunch{CS_K_SAMPLE_LOGP, CS_NET_ACTOR, 1, cs_sample_grid(s), P, 1, 256};       // next_a, next_logp
-    fwd(s.critic, CS_NET_CRITIC, (unsigned)NC);                                                 // the target critics on (next_obs | next_a)
-    out[n++] = CsLaunch{CS_K_CRITIC_LOSS, CS_NET_CRITIC, -1, 1, P, 1, 1024};
-    step(s.critic, CS_NET_CRITIC, (unsigned)NC, gp_arena_floats(s.critic));                     // the last reader of the step slot
-    return n;
+    p.fwd(s.actor, CS_NET_ACTOR, 1);                                              // the updated actor on next_obs
+    p.one(CS_K_SAMPLE_LOGP, CS_NET_ACTOR, 1, cs_sample_grid(s), 256);             // next_a, next_logp
+    p.fwd(s.critic, CS_NET_CRITIC, NC);                                           // the target critics on (next_obs | next_a)
+    p.one(CS_K_CRITIC_LOSS, CS_NET_CRITIC, -1, 1, 1024);
+    p.step(s.critic, CS_NET_CRITIC, NC, gp_arena_floats(s.critic));               // the last reader of the step slot
+    return p.n;
 }
 
 inline bool cs_grid_ok(const CsLaunch& l) { return gp_grid_ok(l); }
@@ -148,15 +118,10 @@ inline bool cs_grid_ok(const CsLaunch& l) { return gp_grid_ok(l); }
 constexpr int CS_OK = GP_OK, CS_NO_MEMBER = GP_NO_MEMBER;
 inline int cs_group_refusal(const CsMember* m, unsigned n, const char** why, int* kernel = nullptr)
 {
-    const auto own = [&](const CsMember& x) -> const char* {
-        if (!x.kind_csac) return "not a candle SAC agent";
-        if (const char* w = cs_shape_ineligible(x.shape)) return w;
-        if (!cs_same_shape(x.shape, m[0].shape))
-            return "its shape (obs_dim, act_dim, both networks' units and activation_out, actor_kind, n_critics, batch_size) differs from member 0's: one shape per group";
-        if (x.n_updates != 1) return "n_updates_per_opt != 1 is not built for a group";
-        return nullptr;
-    };
-    return gp_group_refusal<CsLaunch, CS_MAX_LAUNCHES>(m, n, why, kernel, own, [&](CsLaunch* out) { return cs_round_plan(m[0].shape, n, out); });
+    return gp_dense_group_refusal<CS_MAX_LAUNCHES>(
+        m, n, why, kernel, &CsMember::kind_csac, "not a candle SAC agent",
+        "its shape (obs_dim, act_dim, both networks' units and activation_out, actor_kind, n_critics, batch_size) differs from member 0's: one shape per group",
+        cs_shape_ineligible, cs_same_shape, cs_round_plan);
 }
 
 }  // namespace bdr

@@ -18,7 +18,7 @@
 // its numbers from the same counter; the push kernel is the only reader of its slot and publishes its own number.
 // Bounds: a slot and every per-member argument array hold P = members.size() entries, the length of `keys` and of the buffer list of
 // an opt; slot.slot < STEP_SLOTS, and `steps` holds STEP_SLOTS * P entries.  The bounds of the indices a kind's launches add (its
-// dense, dW and reduce arrays) are stated in the kind's file.
+// dense, dW and reduce arrays) are stated in the kind's file, those of the kinds on dense_group.hpp once, there.
 // A Kind says what differs:
 //   Member, Shape, Launch, Step, MemberArgs, PlanMember, Act        the types (Act: the acting kind of group_act.hpp)
 //   KIND, A, NAME                                                   the member's kind() string and its name in messages ("a BC", "BC")
@@ -31,6 +31,7 @@
 //   allocate(shape, P), stage(p, P, o), upload()                    its StagedArrays
 //   check_static(plan, n, o, p)                                     the plan's weight-gradient grids against the member's
 //   launch(g, P, steps_dev, seq_no)                                 one round's launches (the switch over its own kernels)
+// For the kinds with network instances (IQL, AWAC, candle SAC) the dense half of the last four is written once: dense_group.hpp's DenseRound.
 #pragma once
 #include <algorithm>
 #include <atomic>

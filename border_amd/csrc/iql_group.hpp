@@ -11,19 +11,13 @@
 // scalar loads, as they are from the kernel-argument segment of the standalone kernel.  Same bodies, same bits.  The three loss kernels
 // are one workgroup per member: candle::row_sum / row_max run inside that workgroup, in their block order, over the member's rows only.
 // The host half - the members' adoption, the static argument arrays and their keys, the step ring and its slot rule, the round, records,
-// sync - is group_core.hpp's, shared with the BC group; IqlGroupKind below says what is IQL's.  Per step a member has an IqlStep: the
-// gather reads word_pos and size (GatherStepWords at its start), the three reduce + Adam launches its three AdamScalars.  The ACTOR's
-// reduce + Adam is the LAST launch of a round that reads the slot, so it alone ends with the ticket and publishes the round's launch
-// number (bg_group_done - all workgroups of its three-dimensional grid counted, behind a barrier every thread reaches:
-// dense_reduce_adam_body returns early for threads past the arena, to the entry, not out of the kernel).
-// Bounds of every new index:
-//   member = blockIdx.y < gridDim.y = P = the length of gather, pack, vloss, closs, aloss and of a step slot;
-//   z = blockIdx.z < gridDim.z = nz <= 4 = the instances of a DenseGroupEntry and of a ReduceAdamArgs (2 n_critics <= 4 is a condition
-//   of the group);
-//   the i-th forward / dX launch of the round (stream order) is handed dense + i * P and reads entry i * P + member, i < ndense =
-//   ig_dense_launches: the array holds ndense * P entries; the weight-gradient and reduce + Adam launches of network n (value 0,
-//   critic 1, actor 2) are handed dw + n * P / ra + n * P: 3 P entries each; NET < 3 = the AdamScalars of an IqlStep;
-//   inside a member every index is the body's own, with the bounds of the standalone kernel.
+// sync - is group_core.hpp's, shared with the other groups; the staging of the gather, dense, dW and reduce launches and the walk over
+// the plan are dense_group.hpp's, shared with the AWAC and candle SAC groups, which also states the bounds of member, instance and the
+// shared argument arrays.  IqlGroupKind below says what is IQL's.  Per step a member has an IqlStep: the gather reads word_pos and size
+// (GatherStepWords at its start), the three reduce + Adam launches its three AdamScalars (value 0, critic 1, actor 2).  The CRITICS
+// track their targets; the ACTOR's reduce + Adam is the LAST launch of a round that reads the slot, so it alone publishes.
+// Bounds of IQL's own indices: member = blockIdx.y < gridDim.y = P = the length of pack, vloss, closs and aloss; inside a member every
+// index is the body's own, with the bounds of the standalone kernel.
 // Acting: Policy::sample of the selected members in ONE launch of k_candle_act_group (candle_act_group.hpp, which states the bounds of
 // its indices) through group_act.hpp, the host half BC's group shares; IqlActKind below is CandleActKind of an Iql.
 #pragma once
@@ -31,8 +25,6 @@
 #include "candle_act_group.hpp"
 #include "group_core.hpp"
 #include "iql_group_plan.hpp"
-
-static_assert(IG_DW_GROUP == DW_GROUP && IG_RA_SEGS == RA_SEGS && IG_MAXZ == DG_MAXZ && IG_SHAPE_LAYERS >= BDR_MAX_UNITS + 1, "iql_group_plan.hpp restates these limits");
 
 // the per-step words of one member: the gather's, then the optimizer scalars of value, critics and actor (IgNetId's order)
 struct IqlStep { unsigned long long word_pos, size; AdamScalars adam[3]; };
@@ -59,18 +51,13 @@ __global__ __launch_bounds__(1024) void k_iql_actor_loss_group(const BDR_CONST_A
     __shared__ float red[32];
     iql_actor_loss_body(args[blockIdx.y], red);
 }
-// reduce + Adam of network NET of every member, instance z = blockIdx.z: the optimizer scalars of this step come from the member's
-// staging slot; the critics track their targets at the member's own tau (a.tau / a.omt of its entry); the actor's is the last reader of
+// reduce + Adam of network NET of every member (dense_group.hpp): the critics track their targets, the actor's is the last reader of
 // the slot and publishes
 template <int NET>
 __global__ __launch_bounds__(256) void k_iql_reduce_adam_group(const BDR_CONST_AS ReduceAdamArgs* args, const BDR_CONST_AS IqlStep* steps, unsigned* ticket,
                                                                unsigned* seq_host, unsigned seq)
 {
-    const BDR_CONST_AS AdamScalars& s = steps[blockIdx.y].adam[NET];
-    AdamScalars d;   // field by field: static indices, registers
-    d.b1 = s.b1; d.omb1 = s.omb1; d.b2 = s.b2; d.omb2 = s.omb2; d.sqrt_bc2 = s.sqrt_bc2; d.eps = s.eps; d.neg_step = s.neg_step; d.wd_mul = s.wd_mul;
-    dense_reduce_adam_body(args[blockIdx.y], (int)blockIdx.z, d, NET == IG_NET_CRITIC ? 1 : 0, 0);
-    if constexpr (NET == IG_NET_ACTOR) bg_group_done(ticket, seq_host, seq);
+    dg_reduce_adam_step<NET, NET == IG_NET_CRITIC, NET == IG_NET_ACTOR>(args, steps, ticket, seq_host, seq);
 }
 
 IgShape iql_shape(const Iql* m)
@@ -85,12 +72,8 @@ IgShape iql_shape(const Iql* m)
 
 // ---- host: one member's static arguments, exactly what Iql::update hands its launches (the dense, dX, dW and reduce entries of a
 // network: dense_group.hpp's dg_fwd_entries / dg_step_entries) ---------------------------------------------------------------------------
-struct IqlMemberArgs {
-    GatherArgs gather; IqlPackArgs pack;
-    std::vector<DenseGroupEntry> dense;   // the forward and dX launches in stream order
-    IqlValueArgs vloss; IqlCriticArgs closs; IqlActorArgs aloss;
-    DenseDwSmallGroup dw[3]; int dw_grid[3];   // by IgNetId
-    ReduceAdamArgs ra[3];
+struct IqlMemberArgs : DenseMemberArgs<3> {   // (dw, dw_grid, ra by IgNetId)
+    IqlPackArgs pack; IqlValueArgs vloss; IqlCriticArgs closs; IqlActorArgs aloss;
 };
 
 // (bs: the batch size; r: the member's ring or view; plan: replay_sample_plan's descriptor of this step)
@@ -105,10 +88,7 @@ void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& pl
     const float* next_obs = reinterpret_cast<const float*>(r->b_next);
     const float* act = reinterpret_cast<const float*>(r->b_act);
     o.dense.clear();
-    // the gather: k_gather's arguments as replay_sample_on_stream sets them (word_pos and size are this step's, read from the slot)
-    o.gather = plan;
-    replay_gather_shape(r->obs_bytes, &o.gather.chunks, &o.gather.vec_per_chunk);
-    o.gather.word_pos = 0; o.gather.size = 0;
+    o.gather = dg_gather_static(r, plan);
     o.pack = IqlPackArgs{obs, next_obs, act, O, A, bs, m->x_o, m->x_no, vn.L[0].Kp, m->xq, qn.L[0].Kp};
     // target and online critics: one forward of 2 NC networks
     {
@@ -180,7 +160,7 @@ void iql_member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& pl
 using IqlActKind = CandleActKind<Iql>;
 
 // ---- what is IQL's of the group core (group_core.hpp) ----------------------------------------------------------------------------------
-struct IqlGroupKind {
+struct IqlGroupKind : DenseRound<3, IG_K_DW, IG_K_REDUCE_ADAM> {
     using Member = Iql; using Shape = IgShape; using Launch = IgLaunch; using Step = IqlStep; using MemberArgs = IqlMemberArgs; using PlanMember = IgMember;
     using Act = IqlActKind;
     static constexpr const char *KIND = "iql", *A = "an IQL", *NAME = "IQL", *CAP_MSG = "cap_per_member must hold the three keys of an IQL record";
@@ -207,77 +187,29 @@ struct IqlGroupKind {
     }
     static void member_static(Iql* m, int bs, const bdr_replay* r, const GatherArgs& plan, IqlMemberArgs& o) { iql_member_static(m, bs, r, plan, o); }
 
-    int ndense = 0;   // forward and dX launches of a round
-    StagedArray<GatherArgs> gather; StagedArray<IqlPackArgs> pack; StagedArray<IqlValueArgs> vloss; StagedArray<IqlCriticArgs> closs; StagedArray<IqlActorArgs> aloss;
-    StagedArray<DenseGroupEntry> dense;                                   // [ndense][P] (launch order)
-    StagedArray<DenseDwSmallGroup> dw; StagedArray<ReduceAdamArgs> ra;   // [3][P] by IgNetId
+    static constexpr DgReduceEntry<IqlStep> RA[] = {k_iql_reduce_adam_group<IG_NET_VALUE>, k_iql_reduce_adam_group<IG_NET_CRITIC>, k_iql_reduce_adam_group<IG_NET_ACTOR>};
+    StagedArray<IqlPackArgs> pack; StagedArray<IqlValueArgs> vloss; StagedArray<IqlCriticArgs> closs; StagedArray<IqlActorArgs> aloss;   // [P]
     hipError_t allocate(const IgShape& s, size_t P)
     {
-        ndense = ig_dense_launches(s.value.n_layers, s.critic.n_layers, s.actor.n_layers);
-        hipError_t e = staged_resize(P, gather, pack);   // (in this order: where the arrays lie in device memory shows in the round time, LAB.md)
-        if (e == hipSuccess) e = dense.resize((size_t)ndense * P);
-        if (e == hipSuccess) e = staged_resize(P, vloss, closs, aloss);
-        return e == hipSuccess ? staged_resize(3 * P, dw, ra) : e;
+        return allocate_round(ig_dense_launches(s.value.n_layers, s.critic.n_layers, s.actor.n_layers), P, pack, [&] { return staged_resize(P, vloss, closs, aloss); });
     }
     // member p's arguments into the staging arrays
     void stage(size_t p, size_t P, const IqlMemberArgs& o)
     {
-        gather[p] = o.gather; pack[p] = o.pack; vloss[p] = o.vloss; closs[p] = o.closs; aloss[p] = o.aloss;
-        for (int i = 0; i < ndense; ++i) dense[(size_t)i * P + p] = o.dense[i];
-        for (int n = 0; n < 3; ++n) { dw[(size_t)n * P + p] = o.dw[n]; ra[(size_t)n * P + p] = o.ra[n]; }
+        stage_dense(p, P, o);
+        pack[p] = o.pack; vloss[p] = o.vloss; closs[p] = o.closs; aloss[p] = o.aloss;
     }
     hipError_t upload() { return staged_upload(gather, pack, dense, vloss, closs, aloss, dw, ra); }
-    int32_t check_static(const IgLaunch* plan, int n_launches, const IqlMemberArgs& o, uint32_t p) const
+    int32_t launch(const GroupCore<IqlGroupKind>& g, size_t P, const IqlStep* steps_dev, unsigned seq_no) const { return dg_round_launch(g, P, steps_dev, seq_no, *this); }
+    // IQL's own launches of a round
+    int32_t launch_own(const IgLaunch& l, int n, size_t, dim3 grid, dim3 block, const BDR_CONST_AS IqlStep*, hipStream_t stream) const
     {
-        BDR_REQUIRE((int)o.dense.size() == ndense, "member %u: %d dense launches, the plan has %d", p, (int)o.dense.size(), ndense);
-        for (int n = 0; n < n_launches; ++n)
-            if (plan[n].kernel == IG_K_DW) {
-                const int id = plan[n].net;
-                BDR_REQUIRE(o.dw_grid[id] == (int)plan[n].gx, "member %u: the weight-gradient grid of network %d (%d) differs from the plan's (%u)", p, id, o.dw_grid[id],
-                            plan[n].gx);
-            }
-        return BDR_OK;
-    }
-    // one round's launches on the group's stream, grids from the plan; the last one publishes `seq_no`
-    int32_t launch(const GroupCore<IqlGroupKind>& g, size_t P, const IqlStep* steps_dev, unsigned seq_no) const
-    {
-        int nd = 0;
-        hipStream_t stream = g.stream;
-        for (int n = 0; n < g.n_launches; ++n) {
-            const IgLaunch& l = g.plan[n];
-            const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
-            const auto* st = (const BDR_CONST_AS IqlStep*)steps_dev;
-            switch (l.kernel) {
-            case IG_K_GATHER:
-                BDR_TRY(replay_gather_group(stream, gather.d.get(), steps_dev, (uint32_t)sizeof(IqlStep), (uint32_t)P, (uint64_t)g.shape.batch, (uint64_t)g.shape.obs_dim * 4));
-                break;
-            case IG_K_PACK: hipLaunchKernelGGL(k_iql_pack_group, grid, block, 0, stream, (const BDR_CONST_AS IqlPackArgs*)pack.d.get()); break;
-            case IG_K_FWD:
-                BDR_REQUIRE(nd < ndense, "IQL group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<false>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
-                break;
-            case IG_K_DX:
-                BDR_REQUIRE(nd < ndense, "IQL group round: more dense launches in the plan than argument entries");
-                hipLaunchKernelGGL(k_dense_small_members_z<true>, grid, block, 0, stream, (const BDR_CONST_AS DenseGroupEntry*)(dense.d.get() + (size_t)nd++ * P));
-                break;
-            case IG_K_VALUE_LOSS: hipLaunchKernelGGL(k_iql_value_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlValueArgs*)vloss.d.get()); break;
-            case IG_K_CRITIC_LOSS: hipLaunchKernelGGL(k_iql_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlCriticArgs*)closs.d.get()); break;
-            case IG_K_ACTOR_LOSS: hipLaunchKernelGGL(k_iql_actor_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlActorArgs*)aloss.d.get()); break;
-            case IG_K_DW:
-                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
-                hipLaunchKernelGGL(k_dense_dw_small_members, grid, block, 0, stream, (const BDR_CONST_AS DenseDwSmallGroup*)(dw.d.get() + (size_t)l.net * P));
-                break;
-            case IG_K_REDUCE_ADAM: {
-                BDR_REQUIRE(l.net >= 0 && l.net < 3, "IQL group round: launch %d of the plan names no network", n);
-                const auto* a = (const BDR_CONST_AS ReduceAdamArgs*)(ra.d.get() + (size_t)l.net * P);
-                if (l.net == IG_NET_VALUE) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_VALUE>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
-                else if (l.net == IG_NET_CRITIC) hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_CRITIC>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
-                else hipLaunchKernelGGL(k_iql_reduce_adam_group<IG_NET_ACTOR>, grid, block, 0, stream, a, st, g.ticket.get(), g.seq.dev, seq_no);
-                break;
-            }
-            default: return fail(BDR_ERR_INVALID, "IQL group round: launch %d of the plan names no kernel", n);
-            }
-            BDR_HIP(hipGetLastError());
+        switch (l.kernel) {
+        case IG_K_PACK: hipLaunchKernelGGL(k_iql_pack_group, grid, block, 0, stream, (const BDR_CONST_AS IqlPackArgs*)pack.d.get()); break;
+        case IG_K_VALUE_LOSS: hipLaunchKernelGGL(k_iql_value_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlValueArgs*)vloss.d.get()); break;
+        case IG_K_CRITIC_LOSS: hipLaunchKernelGGL(k_iql_critic_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlCriticArgs*)closs.d.get()); break;
+        case IG_K_ACTOR_LOSS: hipLaunchKernelGGL(k_iql_actor_loss_group, grid, block, 0, stream, (const BDR_CONST_AS IqlActorArgs*)aloss.d.get()); break;
+        default: return fail(BDR_ERR_INVALID, "IQL group round: launch %d of the plan names no kernel", n);
         }
         return BDR_OK;
     }

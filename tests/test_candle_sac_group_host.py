@@ -317,6 +317,35 @@ def test_every_refusal_names_the_first_member_concerned(prog):
     assert got["who"] == "0" and "n_updates_per_opt" in got["why"]
 
 
+def test_the_shape_checks_all_dense_kinds_share_keep_their_texts_and_their_order(prog):
+    """gp_shape_ineligible (group_plan_common.hpp): the four texts that are the same for the IQL, AWAC and candle SAC groups, and where
+    the kind's own reasons rank among them - the layer counts, the actor kind, n_critics, the 2 n_critics launch, the weight-gradient
+    jobs, the reduce segments, the batch size, the dims"""
+    s = SHAPES["partial_block"]
+
+    def why(raw_kind=None, obs=None, **kw):
+        a = shape_args(s, **kw)
+        if obs is not None: a[0] = str(obs)
+        if raw_kind is not None: a[4] = str(raw_kind)
+        got = run(prog, ["plan", 2] + a)
+        assert ("why" in got) == (not got["launches"])   # a shape with a reason has no plan
+        return got.get("why")
+    deep, jobs, segs = dict(critic=(64,) * 16), dict(critic=(64,) * 8), dict(actor=(64,) * 12)   # 17 layers; 2 x 9 jobs; 13 segments
+    assert why() is None
+    assert why(**deep) == "a network has no layer, or more than 16"
+    assert why(nc=0) == "n_critics must be positive"
+    assert why(**jobs) == "n_critics x critic layers beyond the 16 jobs of one grouped weight-gradient launch"
+    assert why(obs=0) == "bad obs/act dims" and why(act=0) == "bad obs/act dims"
+    # two reasons at once: the earlier one is named
+    assert why(raw_kind=7, **deep) == "a network has no layer, or more than 16"
+    assert why(raw_kind=7, nc=0) == "unknown actor kind"
+    assert why(nc=0, **jobs) == "n_critics must be positive"
+    assert why(nc=3, **jobs).startswith("n_critics > 2")
+    assert "16 jobs" in why(**jobs, **segs)
+    assert "segments (12" in why(batch=1, **segs)
+    assert "at least 2 rows" in why(batch=1, obs=0)
+
+
 def test_group_size_and_launch_limits(prog):
     s = SHAPES["partial_block"]
     assert run(prog, ["many", 65535] + shape_args(s))["who"] == "-1"
