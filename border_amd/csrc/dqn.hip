@@ -1645,12 +1645,22 @@ int32_t dqn_cnn_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
         case 11: src = a->dy3; break;
         case 12: src = a->dy2; break;
         case 13: src = a->dy1; break;
+        // the other instances of the last update, layouts as 5-8 and 0: slot 1 = qnet_tgt(next_obs) (its Q rows are probe 1), slot 2 =
+        // qnet(next_obs), which only a double-DQN update runs
+        case 14: src = a->a1[1]; break;
+        case 15: src = a->a2[1]; break;
+        case 16: src = a->a3[1]; break;
+        case 17: src = a->h1[1]; break;
+        case 18: case 19: case 20: case 21: case 22:
+            BDR_REQUIRE(a->cfg.double_dqn, "probe %d reads the selector instance qnet(next_obs), which runs only with double DQN", what);
+            src = what == 18 ? a->a1[2] : what == 19 ? a->a2[2] : what == 20 ? a->a3[2] : what == 21 ? a->h1[2] : a->qv[2];
+            break;
         default: return fail(BDR_ERR_INVALID, "unknown probe %d", what);
     }
     BDR_REQUIRE(src, "nothing to probe yet (no update has run)");
     // Every probed buffer is written on, or ordered in front of, the agent's stream in every schedule: forward, head and the dX chain run
-    // on it, and with the split forward the target instance's Q values (probe 1) come from the other queue in front of k_head's wait on
-    // SIG_TGT.  Otherwise the other queue only reads them.  a1[0] is the buffer this update's conv2 dW read until the NEXT update swaps it
+    // on it, and with the split forward the target instance's buffers (probes 1 and 14-17: every kernel of its forward) come from the other
+    // queue in front of SIG_TGT, which k_head on the agent's stream waits for in-kernel.  Otherwise the other queue only reads them.  a1[0] is the buffer this update's conv2 dW read until the NEXT update swaps it
     // with a1_alt.  With the overlapped tail the last update's conv2 dW / conv optimizer pass may still be running on the other queue:
     // the copy goes behind its CONV23 flag, so a probe after opt() returns with that update complete, as one after update_on_batch does.
     BDR_TRY(a->join_conv23());

@@ -292,7 +292,10 @@ class Dqn(TchValueAgent):
 
     def probe(self, what: str, n: int) -> np.ndarray:
         idx = {"q_pred_all": 0, "q_next_all": 1, "pred": 2, "tgt": 3, "loss": 4, "act_conv1": 5, "act_conv2": 6, "act_conv3": 7,
-               "h1": 8, "dq": 9, "dh1": 10, "dy3": 11, "dy2": 12, "dy1": 13}[what]   # 8-13 AtariCnn only: the backward pass's inputs and intermediates
+               "h1": 8, "dq": 9, "dh1": 10, "dy3": 11, "dy2": 12, "dy1": 13,   # 8-13 AtariCnn only: the backward pass's inputs and intermediates
+               # AtariCnn only: qnet_tgt(next_obs) (its Q rows: q_next_all) and, with double DQN, qnet(next_obs)
+               "tgt_conv1": 14, "tgt_conv2": 15, "tgt_conv3": 16, "tgt_h1": 17,
+               "sel_conv1": 18, "sel_conv2": 19, "sel_conv3": 20, "sel_h1": 21, "q_sel_all": 22}[what]
         out = np.empty(n, np.float32)
         _lib.check(_lib.lib().bdr_dqn_probe(self._h, idx, _p(out), n))
         return out

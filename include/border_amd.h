@@ -947,7 +947,10 @@ BDR_API int32_t bdr_checkpoint_read(const char* path, const bdr_named_tensor* me
  * what: 0 q_pred_all [B][A], 1 q_next_all [B][A], 2 pred [B], 3 tgt [B], 4 loss [1];
  * AtariCnn only, the online network's activations on `obs`, position-major (NHWC): 5 conv1 [B][400][32], 6 conv2 [B][81][64], 7 conv3 [B][49][64];
  * AtariCnn only, the backward pass: 8 h1 [B][512] (online instance on `obs`), 9 dq [B] (dL/dQ(s,a)), 10 dh1 [B][512], and the gradients
- * w.r.t. the conv layers' pre-activations, position-major: 11 dy3 [B*49][64], 12 dy2 [B*81][64], 13 dy1 [B*400][32]. */
+ * w.r.t. the conv layers' pre-activations, position-major: 11 dy3 [B*49][64], 12 dy2 [B*81][64], 13 dy1 [B*400][32];
+ * AtariCnn only, the other network instances of the update, layouts as 5-8 and 0: qnet_tgt(next_obs) 14 conv1, 15 conv2, 16 conv3, 17 h1
+ * (its Q rows are 1); qnet(next_obs), which runs with double DQN only (BDR_ERR_INVALID without it): 18 conv1, 19 conv2, 20 conv3, 21 h1,
+ * 22 Q rows [B][A]. */
 BDR_API int32_t bdr_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
 /* Layer probes of the Mlp DQN agent: ONE raw device buffer of the last update (bdr_dqn_update_on_batch*, opt, a group's round) to the
  * host after synchronising the agent's stream, rows x padded leading dimension, padding included.  B = rows of that update, Kp / Np =
