@@ -16,6 +16,7 @@ from .candle_sac import CandleSac, CandleSacConfig, EntCoefMode  # noqa: F401
 from .bc import Bc, BcActionType, BcConfig, BcModelConfig  # noqa: F401
 from .candle_dqn import CandleDqn, CandleDqnConfig, CandleDqnModelConfig  # noqa: F401
 from . import checkpoint  # noqa: F401
+from . import pbt  # noqa: F401
 from .atari import AtariDeviceEnv, AtariPreprocessor  # noqa: F401
 from .trainer import (NativeTrainer, ParamExchange, Sampler, SimpleStepProcessor, Step, SyntheticEnv, Trainer, TrainerConfig,  # noqa: F401
                       shard_seed)

@@ -379,7 +379,38 @@ ABI_SYMBOLS = [
     "bdr_candle_sac_group_trainer_post_default",
     "bdr_awac_group_push", "bdr_awac_group_push_max_rows", "bdr_candle_sac_group_push", "bdr_candle_sac_group_push_max_rows",
     "bdr_awac_group_ctrainer_ops_default", "bdr_candle_sac_group_ctrainer_ops_default", "bdr_trainer_train_cgroup_post",
+    "bdr_agent_hyper_get", "bdr_agent_hyper_set", "bdr_bc_group_copy_members", "bdr_iql_group_copy_members", "bdr_awac_group_copy_members",
+    "bdr_candle_sac_group_copy_members",
 ]
+
+# BDR_HYPER_* (include/border_amd.h): the settable scalar fields of a BC, IQL, AWAC or candle SAC agent, by name
+HYPER_IDS = {
+    "lr": 0, "beta1": 1, "beta2": 2, "eps": 3, "weight_decay": 4,
+    "lr_actor": 10, "actor_beta1": 11, "actor_beta2": 12, "actor_eps": 13, "actor_weight_decay": 14,
+    "lr_critic": 20, "critic_beta1": 21, "critic_beta2": 22, "critic_eps": 23, "critic_weight_decay": 24,
+    "lr_value": 30, "value_beta1": 31, "value_beta2": 32, "value_eps": 33, "value_weight_decay": 34,
+    "gamma": 40, "critic_tau": 41, "tau_iql": 42, "inv_lambda": 43, "exp_adv_max": 44, "ent_coef_lr": 45, "target_entropy": 46,
+}
+BDR_COPY_HYPER = 1
+
+
+def hyper_id(name) -> int:
+    """BDR_HYPER_* of a name of HYPER_IDS (an int passes through)"""
+    if isinstance(name, str):
+        if name not in HYPER_IDS:
+            raise ValueError(f"unknown hyperparameter {name!r}: one of {sorted(HYPER_IDS)}")
+        return HYPER_IDS[name]
+    return int(name)
+
+
+def agent_get_hyper(handle, name) -> float:
+    v = C.c_double(0.0)
+    check(lib().bdr_agent_hyper_get(handle, hyper_id(name), C.byref(v)))
+    return v.value
+
+
+def agent_set_hyper(handle, name, value) -> None:
+    check(lib().bdr_agent_hyper_set(handle, hyper_id(name), float(value)))
 
 _lib = None
 
@@ -430,6 +461,10 @@ def lib() -> C.CDLL:
     L.bdr_trainer_train_offline_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(TrainerOps), C.POINTER(TrainerPostC), OBSERVER_FN, C.c_void_p,
                                                  C.POINTER(TrainerStatsC)]
     L.bdr_agent_set_act_path.argtypes = [C.c_void_p, C.c_int32]
+    L.bdr_agent_hyper_get.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+    L.bdr_agent_hyper_set.argtypes = [C.c_void_p, C.c_int32, C.c_double]
+    for k in ("bc", "iql", "awac", "candle_sac"):
+        getattr(L, f"bdr_{k}_group_copy_members").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.bdr_agent_sample_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.bdr_atari_clip_reward.restype = C.c_float
     L.bdr_atari_clip_reward.argtypes = [C.c_float, C.c_int32]

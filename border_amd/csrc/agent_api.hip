@@ -807,6 +807,18 @@ int32_t bdr_agent_set_act_path(bdr_agent* a, int32_t path)
     return a->set_act_path(path);
 }
 
+int32_t bdr_agent_hyper_get(bdr_agent* a, int32_t id, double* out)
+{
+    BDR_REQUIRE(a && out, "null argument");
+    return a->hyper(id, false, out);
+}
+
+int32_t bdr_agent_hyper_set(bdr_agent* a, int32_t id, double v)
+{
+    BDR_REQUIRE(a, "null agent");
+    return a->hyper(id, true, &v);
+}
+
 int32_t bdr_agent_sample_raw(bdr_agent* a, const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype, int32_t on_device, uint64_t row_stride,
                              float* act_out, int64_t* idx_out)
 {

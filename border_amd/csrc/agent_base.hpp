@@ -351,6 +351,11 @@ struct bdr_agent : bdr::ParamTable {
         if (path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS) return BDR_OK;
         return ::bdr::fail(BDR_ERR_INVALID, path == BDR_ACT_PATH_FUSED ? "this agent kind has no fused acting kernel (IQL, AWAC, BC and the candle SAC and DQN have one)" : "unknown act path");
     }
+    // bdr_agent_hyper_get / _set: hyperparameter `id` (BDR_HYPER_*) into *v, or *v into it; the DenseAgent agents implement them
+    virtual int32_t hyper(int32_t id, bool /*set*/, double* /*v*/)
+    {
+        return ::bdr::fail(BDR_ERR_INVALID, "%s agent has no settable hyperparameter %d (BC, IQL, AWAC and the candle SAC have some)", kind(), id);
+    }
     virtual int32_t sample_raw(const bdr_obs_norm*, uint64_t, const void*, int32_t, bool, uint64_t, float*, int64_t*)
     {
         return ::bdr::fail(BDR_ERR_INVALID, "bdr_agent_sample_raw serves IQL, AWAC and BC agents (the others sample through their own entry points)");

@@ -242,6 +242,7 @@ struct Awac : CandleAgent<Awac, bdr_awac_config> {
         return BDR_OK;
     }
     int32_t alloc_staging(uint64_t n) { return alloc(&u_z, 2 * n * A, STAGING, false); }
+    double* own_hyper(int32_t id) { return id == BDR_HYPER_INV_LAMBDA ? &cfg.inv_lambda : id == BDR_HYPER_EXP_ADV_MAX ? &cfg.exp_adv_max : nullptr; }
 
     // One iteration of the Awac::opt_ loop on device-resident rows (f32 obs / next_obs / act).  z_pi / z_next: device N(0,1) rows or null.
     int32_t update(int Bn, const float* obs, const float* act, const float* next_obs, const float* reward, const int8_t* term,

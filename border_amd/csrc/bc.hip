@@ -477,6 +477,10 @@ struct Bc : DenseAgent {
         *pv = mlp_view(net, r[which / 100]);
         return true;
     }
+    // ---- group copies and hyperparameters (dense_agent.hpp) ----
+    void state_arenas(std::vector<StateArena>& out) override { out = {{p, net.total}, {g, net.total}, {m, net.total}, {v, net.total}}; }
+    void adopt_steps(const DenseAgent& src) override { step = static_cast<const Bc&>(src).step; }
+    double* hyper_field(int32_t id) override { return id <= BDR_HYPER_WEIGHT_DECAY ? opt_field(cfg.opt, cfg.lr, id) : nullptr; }
     // ---- checkpoint: policy_model.pt (bc/base.rs:138-153), variables mlp.ln{i}.weight / .bias from the VarMap's root (bc/model.rs:130-133)
     void checkpoint_files(std::vector<CheckpointFile>& files) override
     {

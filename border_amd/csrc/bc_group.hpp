@@ -291,5 +291,9 @@ int32_t bdr_bc_group_sample_members(bdr_bc_group* g, const uint32_t* members, ui
     return group_sample_members(g, members, n_sel, norms, n, rows, dtypes, act_out);
 }
 int32_t bdr_bc_group_sync(bdr_bc_group* g) { return group_sync(g); }
+int32_t bdr_bc_group_copy_members(bdr_bc_group* g, const uint32_t* src, const uint32_t* dst, uint32_t n, uint32_t flags)
+{
+    return group_copy_members(g, src, dst, n, flags);
+}
 
 }  // extern "C"

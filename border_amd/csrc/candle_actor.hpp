@@ -397,11 +397,37 @@ struct CandleAgent : DenseAgent {
         self().own_files(files);
     }
 
+    // ---- group copies and hyperparameters (dense_agent.hpp): the actor's and critics', then the agent's own (own_arenas, own_steps, own_hyper) ----
+    void state_arenas(std::vector<StateArena>& out) override
+    {
+        out = {{pi_p, pi_total}, {pi_g, pi_total}, {pi_m, pi_total}, {pi_v, pi_total}};
+        for (int i = 0; i < NC; ++i)
+            for (float* a : {q_p[i], q_t[i], q_g[i], q_m[i], q_v[i]}) out.push_back({a, qn.total});
+        self().own_arenas(out);
+    }
+    void adopt_steps(const DenseAgent& src) override
+    {
+        const Self& s = static_cast<const Self&>(src);
+        step_pi = s.step_pi; step_q = s.step_q;
+        self().own_steps(s);
+    }
+    double* hyper_field(int32_t id) override
+    {
+        if (id >= BDR_HYPER_LR_ACTOR && id <= BDR_HYPER_ACTOR_WEIGHT_DECAY) return opt_field(cfg.opt_actor, cfg.lr_actor, id - BDR_HYPER_LR_ACTOR);
+        if (id >= BDR_HYPER_LR_CRITIC && id <= BDR_HYPER_CRITIC_WEIGHT_DECAY) return opt_field(cfg.opt_critic, cfg.lr_critic, id - BDR_HYPER_LR_CRITIC);
+        if (id == BDR_HYPER_GAMMA) return &cfg.gamma;
+        if (id == BDR_HYPER_CRITIC_TAU) return &cfg.critic_tau;
+        return self().own_hyper(id);
+    }
+
     // ---- hooks an agent may replace ----
     int32_t init_own() { return BDR_OK; }                       // create: the agent's own models, after the actor's and critics'
     int32_t alloc_staging(uint64_t) { return BDR_OK; }          // stage_batch: the agent's own staging rows (alloc(..., STAGING))
     bool own_view(int /*k*/, int /*role*/, ParamView*) { return false; }   // model 1 + 2NC + k
     void own_files(std::vector<CheckpointFile>&) {}             // checkpoint files behind the core's three
+    void own_arenas(std::vector<StateArena>&) {}                // state_arenas: the arenas of the agent's own models
+    void own_steps(const Self&) {}                              // adopt_steps: the step counters of the agent's own models
+    double* own_hyper(int32_t) { return nullptr; }              // hyper_field: the agent's own hyperparameters
 
     // bdr_*_create after its null check: the checks in their order, the device, then the agent with its initial parameters.
     // value / opt_value: IQL's value model, checked before the actor's; one_row: why a one-row batch is refused (AWAC), null where one

@@ -320,6 +320,15 @@ struct CandleSac : CandleAgent<CandleSac, bdr_candle_sac_config> {
         return BDR_OK;
     }
     int32_t alloc_staging(uint64_t n) { return alloc(&u_z, 2 * n * A, STAGING, false); }
+    // the entropy block as one arena: log_alpha, its gradient and moments, and alpha - the copy params_written derives, with the bits
+    // the source's k_csac_alpha wrote
+    void own_arenas(std::vector<StateArena>& out) { out.push_back({ent, 8}); }
+    void own_steps(const CandleSac& s) { step_al = s.step_al; }
+    double* own_hyper(int32_t id)
+    {
+        if (cfg.ent_coef_mode != BDR_ENT_COEF_AUTO) return nullptr;
+        return id == BDR_HYPER_ENT_COEF_LR ? &cfg.ent_coef_lr : id == BDR_HYPER_TARGET_ENTROPY ? &cfg.target_entropy : nullptr;
+    }
     int32_t init_own()
     {
         BDR_TRY(alloc(&ent, 8, AGENT));

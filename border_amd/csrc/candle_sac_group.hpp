@@ -323,6 +323,10 @@ int32_t bdr_candle_sac_group_sample_members(bdr_candle_sac_group* g, const uint3
     return group_sample_members(g, members, n_sel, norms, n, rows, dtypes, act_out);
 }
 int32_t bdr_candle_sac_group_sync(bdr_candle_sac_group* g) { return group_sync(g); }
+int32_t bdr_candle_sac_group_copy_members(bdr_candle_sac_group* g, const uint32_t* src, const uint32_t* dst, uint32_t n, uint32_t flags)
+{
+    return group_copy_members(g, src, dst, n, flags);
+}
 int32_t bdr_candle_sac_group_push(bdr_candle_sac_group* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs, const void* const* next_obs, const int32_t* obs_dtypes,
         const float* const* act, const float* const* reward, const int8_t* const* is_terminated, const int8_t* const* is_truncated)
 {

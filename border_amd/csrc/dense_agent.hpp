@@ -168,6 +168,59 @@ struct DenseAgent : bdr_agent {
         return BDR_OK;
     }
 
+    // ---- training state as a group copy moves it (group_copy.hpp) ----
+    // state_arenas: every arena the agent's model table serves, each once, in one order for every agent of a kind and shape (an
+    // agent lists its allocations, not its views: the candle SAC's one-float views share a block).  state_adopt: the host half of a
+    // copy from `src`, an agent of the same kind and shape - the optimizer step counters, and with `hypers` every settable
+    // hyperparameter both have; seed, noise counter, mode, act path, n_opts and everything about buffers stay this agent's.
+    struct StateArena { float* p; size_t n; };
+    virtual void state_arenas(std::vector<StateArena>& out) { out.clear(); }   // (the candle DQN joins none of these groups)
+    virtual void adopt_steps(const DenseAgent&) {}
+    void state_adopt(const DenseAgent& src, bool hypers)
+    {
+        adopt_steps(src);
+        if (hypers)
+            for (int32_t id = 0; id <= HYPER_ID_MAX; ++id) {
+                double* d = hyper_field(id);
+                const double* s = const_cast<DenseAgent&>(src).hyper_field(id);
+                if (d && s && *d != *s) { *d = *s; hyper_gen += 1; }
+            }
+    }
+
+    // ---- hyperparameters by id (bdr_agent_hyper_get / _set) ----
+    // hyper_field: the config field behind BDR_HYPER_* `id`, null where the kind (or the agent's entropy mode) has none.  hyper_gen
+    // moves with every change: the groups key their staged static arguments on it (group_core.hpp), the per-step words and the
+    // agent's own update read the config afresh.
+    static constexpr int32_t HYPER_ID_MAX = BDR_HYPER_TARGET_ENTROPY;
+    uint64_t hyper_gen = 0;
+    virtual double* hyper_field(int32_t) { return nullptr; }
+    static double* opt_field(bdr_adamw_config& o, double& lr, int k)   // k: BDR_HYPER_LR .. BDR_HYPER_WEIGHT_DECAY
+    {
+        double* f[5] = {&lr, &o.beta1, &o.beta2, &o.eps, &o.weight_decay};
+        return k >= 0 && k < 5 ? f[k] : nullptr;
+    }
+    static int32_t hyper_check(int32_t id, double v)
+    {
+        const int k = id < BDR_HYPER_GAMMA ? id % 10 : -1;
+        BDR_REQUIRE(std::isfinite(v), "hyperparameter %d: %g is not finite", id, v);
+        if (k == BDR_HYPER_LR || id == BDR_HYPER_ENT_COEF_LR) BDR_REQUIRE(v >= 0.0, "hyperparameter %d: a learning rate is >= 0, got %g", id, v);
+        else if (k == BDR_HYPER_BETA1 || k == BDR_HYPER_BETA2) BDR_REQUIRE(v >= 0.0 && v < 1.0, "hyperparameter %d: a beta lies in [0, 1), got %g", id, v);
+        else if (k == BDR_HYPER_EPS || k == BDR_HYPER_WEIGHT_DECAY) BDR_REQUIRE(v >= 0.0, "hyperparameter %d: eps and weight decay are >= 0, got %g", id, v);
+        else if (id == BDR_HYPER_GAMMA || id == BDR_HYPER_CRITIC_TAU) BDR_REQUIRE(v >= 0.0 && v <= 1.0, "hyperparameter %d: gamma and critic_tau lie in [0, 1], got %g", id, v);
+        else if (id == BDR_HYPER_TAU_IQL) BDR_REQUIRE(v > 0.0 && v < 1.0, "hyperparameter %d: tau_iql lies in (0, 1), got %g", id, v);
+        else if (id == BDR_HYPER_INV_LAMBDA || id == BDR_HYPER_EXP_ADV_MAX) BDR_REQUIRE(v >= 0.0, "hyperparameter %d: inv_lambda and exp_adv_max are >= 0, got %g", id, v);
+        return BDR_OK;
+    }
+    int32_t hyper(int32_t id, bool set, double* v) override
+    {
+        double* f = id >= 0 && id <= HYPER_ID_MAX ? hyper_field(id) : nullptr;
+        BDR_REQUIRE(f, "%s agent has no hyperparameter %d (include/border_amd.h, BDR_HYPER_*)", kind(), id);
+        if (!set) { *v = *f; return BDR_OK; }
+        BDR_TRY(hyper_check(id, *v));
+        if (*f != *v) { *f = *v; hyper_gen += 1; }
+        return BDR_OK;
+    }
+
     // ---- acting calls (Policy::sample) ----
     // n observation rows (host rows, or device rows inside with_device_rows) -> the zero-padded first-layer input x [n][Kp].  On an
     // error the profile's slot cursor is reset, as the caller does when the call ends, and the status returned.

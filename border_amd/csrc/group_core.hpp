@@ -5,8 +5,8 @@
 // stream, check the buffers, take a slot of the pinned step ring, re-stage the static arguments of the members whose key has moved,
 // walk the launch plan, publish the launch number, collect records, sync, destroy.
 //   static arguments   one device array per kernel family (the Kind's StagedArrays), rewritten only when a member's batch buffers or
-//                      its ring change (`keys`: the member's batch_gen, the ring's uid and batch_gen), synchronously, behind a stream
-//                      synchronise: rare
+//                      its ring change, or a hyperparameter of it is set (`keys`: the member's batch_gen and hyper_gen, the ring's uid
+//                      and batch_gen), synchronously, behind a stream synchronise: rare
 //   per step           Kind::Step[P] in a slot of the pinned, device-mapped step ring: the gather reads word_pos and size of the
 //                      member's entry (GatherStepWords at its start), the reduce + Adam launches its AdamScalars
 // The slot rule (slot_ring.hpp): the LAST launch of a round that reads the slot - the kind's final reduce + Adam - ends with the ticket
@@ -16,6 +16,8 @@
 // The grouped push of the online kinds (AWAC, candle SAC: group_push below, k_cgroup_push in group_push.hpp) has a pinned ring of its
 // own under the same rule - PUSH_SLOTS slots of PUSH_SLOT_BYTES, a slot = [CGroupPushDesc[P] | every member's n records] - and takes
 // its numbers from the same counter; the push kernel is the only reader of its slot and publishes its own number.
+// Copies of training state between members (group_copy.hpp: group_copy_members, k_group_copy) have a third ring under the same rule -
+// GC_SLOTS slots of segment tables - and take their numbers from the same counter.
 // Bounds: a slot and every per-member argument array hold P = members.size() entries, the length of `keys` and of the buffer list of
 // an opt; slot.slot < STEP_SLOTS, and `steps` holds STEP_SLOTS * P entries.  The bounds of the indices a kind's launches add (its
 // dense, dW and reduce arrays) are stated in the kind's file, those of the kinds on dense_group.hpp once, there.
@@ -43,6 +45,7 @@
 #include "group_done.hpp"
 #include "group_act.hpp"
 #include "group_push.hpp"
+#include "group_copy.hpp"
 #include "group_plan_common.hpp"
 
 namespace {
@@ -60,7 +63,7 @@ struct GroupCore {
     typename K::Shape shape{};       // the one shape of all members
     typename K::Launch plan[K::MAX_LAUNCHES]; int n_launches = 0;
     uint64_t kernel_launches = 0;    // every kernel launch the group's own calls have enqueued (bdr_*_group_info)
-    struct StaticKey { bool valid = false; uint64_t batch_gen = 0, r_uid = 0, r_batch_gen = 0; };
+    struct StaticKey { bool valid = false; uint64_t batch_gen = 0, hyper_gen = 0, r_uid = 0, r_batch_gen = 0; };
     std::vector<StaticKey> keys;
     K kind;                                                             // the static arguments of its kernel families
     PinnedArray<typename K::Step> steps; SlotRing<STEP_SLOTS> step_ring;   // [STEP_SLOTS][P]
@@ -73,6 +76,9 @@ struct GroupCore {
     // first push, read in place by k_cgroup_push (group_push.hpp)
     PinnedArray<uint8_t> push; SlotRing<PUSH_SLOTS> push_ring;
     std::vector<bdr_replay*> last_push_buffers;                         // the buffers of the last accepted push (distinctness checked once)
+    // copies between members (group_copy.hpp): GC_SLOTS slots of min(65535, (P - 1) x arenas) segments; allocated by the first copy,
+    // read in place by k_group_copy
+    PinnedArray<GroupCopySeg> copy; SlotRing<GC_SLOTS> copy_ring;
 
     hipError_t allocate(size_t P)
     {
@@ -255,11 +261,11 @@ int32_t group_round(G* g, bdr_replay* const* buffers)
         BDR_TRY(replay_sample_plan(r, bs, g->stream, &plan));   // the host half of replay_sample_on_stream; the rows are k_gather_group's
         const typename K::Step st = K::fill_step(m, bs, plan);
         auto& key = g->keys[p];
-        if (!key.valid || key.batch_gen != m->batch_gen || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
+        if (!key.valid || key.batch_gen != m->batch_gen || key.hyper_gen != m->hyper_gen || key.r_uid != r->uid || key.r_batch_gen != r->batch_gen) {
             K::member_static(m, bs, r, plan, o);
             BDR_TRY(g->kind.check_static(g->plan, g->n_launches, o, p));
             g->kind.stage(p, P, o);
-            key.valid = true; key.batch_gen = m->batch_gen; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
+            key.valid = true; key.batch_gen = m->batch_gen; key.hyper_gen = m->hyper_gen; key.r_uid = r->uid; key.r_batch_gen = r->batch_gen;
             dirty = true;
         }
         steps[p] = st;

@@ -249,6 +249,13 @@ struct Iql : CandleAgent<Iql, bdr_iql_config> {
         mlp_meta(vn, "value.", mt);
         files.push_back({"value", mt, {1 + 2 * NC}, {1 + 2 * NC}});
     }
+    void own_arenas(std::vector<StateArena>& out) { for (float* a : {v_p, v_g, v_m, v_v}) out.push_back({a, vn.total}); }
+    void own_steps(const Iql& s) { step_v = s.step_v; }
+    double* own_hyper(int32_t id)
+    {
+        if (id >= BDR_HYPER_LR_VALUE && id <= BDR_HYPER_VALUE_WEIGHT_DECAY) return opt_field(cfg.opt_value, cfg.lr_value, id - BDR_HYPER_LR_VALUE);
+        return id == BDR_HYPER_TAU_IQL ? &cfg.tau_iql : id == BDR_HYPER_INV_LAMBDA ? &cfg.inv_lambda : id == BDR_HYPER_EXP_ADV_MAX ? &cfg.exp_adv_max : nullptr;
+    }
     int32_t alloc_batch(int Bn)
     {
         for (auto* vec : {&v_act, &vo_act, &vn_act, &v_dy}) BDR_TRY(layer_bufs(vn, Bn, *vec));

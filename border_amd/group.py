@@ -476,6 +476,7 @@ class _DenseGroup:
     member, every launch serving all members (csrc/group_core.hpp through the kind's bdr_<kind>_group_* functions).  A subclass names
     the C prefix (_PREFIX), the member class (_MEMBER) and the keys of a member's Record (RECORD_KEYS)."""
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/group_core.hpp GroupCore::STEP_SLOTS)
+    COPY_STAGING_DEPTH = 8   # slots of the segment ring of copy_members (csrc/group_copy.hpp GC_SLOTS)
     _PREFIX = _MEMBER = None
     RECORD_KEYS = ()
 
@@ -593,6 +594,32 @@ class _DenseGroup:
         member."""
         return _group_train_offline(self, self._PREFIX, self.RECORD_KEYS, buffers, max_opts, record_interval, on_record, evaluators, eval_interval,
                                     save_interval, model_dirs, on_event)
+
+    def copy_members(self, pairs, hyper: bool = True) -> None:
+        """Member dst becomes a copy of member src for every (src, dst) of `pairs`, ONE launch whatever their number
+        (bdr_<kind>_group_copy_members); does not synchronise.  Every arena of the model table moves (networks and targets, the last
+        gradient, exp_avg, exp_avg_sq) with the optimizer step counters, and with hyper=True every settable hyperparameter; the
+        destination keeps its seed, noise counter, mode, act path, buffer and index stream, n_opts and best-model bookkeeping.
+        Refused (BdrError naming the pair) before anything moves: an index out of range, src == dst, a destination listed twice, a
+        member that is a destination in one pair and a source in another.  An empty list does nothing."""
+        pairs = [(int(s), int(d)) for s, d in pairs]
+        if not pairs:
+            return
+        for s, d in pairs:
+            if s < 0 or d < 0:
+                raise ValueError(f"pair ({s} -> {d}): a member index is not negative")
+        src = np.ascontiguousarray([s for s, _ in pairs], np.uint32)
+        dst = np.ascontiguousarray([d for _, d in pairs], np.uint32)
+        _lib.check(self._c("copy_members")(self._g, src.ctypes.data_as(C.c_void_p), dst.ctypes.data_as(C.c_void_p), len(pairs),
+                                           _lib.BDR_COPY_HYPER if hyper else 0))
+
+    def get_hyper(self, member: int, name) -> float:
+        """`members[member].get_hyper(name)`"""
+        return self._members[member].get_hyper(name)
+
+    def set_hyper(self, member: int, name, value: float) -> None:
+        """`members[member].set_hyper(name, value)`: in force from the next round"""
+        self._members[member].set_hyper(name, value)
 
     def sync(self) -> None:
         _lib.check(self._c("sync")(self._g))

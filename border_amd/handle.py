@@ -184,6 +184,17 @@ class DenseHandle(AgentHandle):
         raw rows to the action; same bits) or "default".  "fused" on a network it does not cover raises BdrError."""
         _lib.check(_lib.lib().bdr_agent_set_act_path(self._h, self.ACT_PATHS[path]))
 
+    def get_hyper(self, name) -> float:
+        """One settable hyperparameter (bdr_agent_hyper_get): a name of _lib.HYPER_IDS - "lr" and "beta1" ... of BC; "lr_actor",
+        "lr_critic", "lr_value", "actor_beta1" ..., "gamma", "critic_tau", "tau_iql", "inv_lambda", "exp_adv_max", "ent_coef_lr",
+        "target_entropy" of the others - or its BDR_HYPER_* id.  A name the agent's kind does not have raises BdrError."""
+        return _lib.agent_get_hyper(self._h, name)
+
+    def set_hyper(self, name, value: float) -> None:
+        """Set it (bdr_agent_hyper_set): in force from the agent's next update, standalone or as a group member.  A value outside
+        the field's range raises BdrError.  (`config` keeps what the agent was built with.)"""
+        _lib.agent_set_hyper(self._h, name, value)
+
     def _raw_out(self, n: int):
         """(result array, is it an index array) of a sample of n rows"""
         return np.empty((n, self.config.act_dim), np.float32), False

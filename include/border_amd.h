@@ -1793,6 +1793,57 @@ BDR_API int32_t bdr_agent_set_act_path(bdr_agent* a, int32_t path);
 BDR_API int32_t bdr_agent_sample_raw(bdr_agent* a, const bdr_obs_norm* norm, uint64_t n, const void* rows, int32_t dtype,
                                      int32_t on_device, uint64_t row_stride, float* act_out, int64_t* idx_out);
 
+/* ---- hyperparameters by id, and copies of training state between the members of a group (BC, IQL, AWAC, the candle SAC) ----------------
+ * The two steps of population-based training (explore, exploit), of successive halving and of a learning-rate schedule.
+ * bdr_agent_hyper_get / _set read and write ONE scalar field of the agent's config - the fields the group comments above list as
+ * "free per member" - on a standalone agent or a group member.  Nothing about shape, loss form or optimizer kind is settable.
+ *   BC          LR, BETA1, BETA2, EPS, WEIGHT_DECAY (bdr_bc_config::lr, ::opt)
+ *   IQL         LR_VALUE, LR_CRITIC, LR_ACTOR and the VALUE_ / CRITIC_ / ACTOR_ scalars of their optimizers, GAMMA, CRITIC_TAU, TAU_IQL,
+ *               INV_LAMBDA, EXP_ADV_MAX
+ *   AWAC        LR_ACTOR, LR_CRITIC and their optimizers' scalars, GAMMA, CRITIC_TAU, INV_LAMBDA, EXP_ADV_MAX
+ *   candle SAC  LR_ACTOR, LR_CRITIC and their optimizers' scalars, GAMMA, CRITIC_TAU; with EntCoefMode::Auto also ENT_COEF_LR and
+ *               TARGET_ENTROPY
+ * (BETA1, BETA2, EPS and WEIGHT_DECAY are read by BDR_OPT_ADAMW only, as at creation: BDR_OPT_ADAM keeps PyTorch's defaults.)
+ * BDR_ERR_INVALID: an id the kind does not have (every agent kind but these four has none), and a value outside the id's range - a
+ * learning rate, eps or weight decay that is negative or not finite; a beta outside [0, 1); GAMMA or CRITIC_TAU outside [0, 1];
+ * TAU_IQL outside (0, 1); INV_LAMBDA or EXP_ADV_MAX negative or not finite; a TARGET_ENTROPY that is not finite.  (The constructors
+ * check none of these scalars; the setter refuses what no update defines.)
+ * A set takes effect in the member's next update, a group round or its own bdr_agent_opt / update_on_batch: the learning rates and
+ * optimizer scalars are recomputed from the config every update; the values a group keeps in staged static arguments (GAMMA,
+ * CRITIC_TAU, TAU_IQL, INV_LAMBDA, EXP_ADV_MAX, TARGET_ENTROPY) are part of the member's static key, so the next round restages them.
+ * These agent kinds replay no captured step graph, so there is no graph to patch or drop.  Setting a value to what it is changes nothing. */
+enum {
+    BDR_HYPER_LR = 0, BDR_HYPER_BETA1 = 1, BDR_HYPER_BETA2 = 2, BDR_HYPER_EPS = 3, BDR_HYPER_WEIGHT_DECAY = 4,
+    BDR_HYPER_LR_ACTOR = 10, BDR_HYPER_ACTOR_BETA1 = 11, BDR_HYPER_ACTOR_BETA2 = 12, BDR_HYPER_ACTOR_EPS = 13, BDR_HYPER_ACTOR_WEIGHT_DECAY = 14,
+    BDR_HYPER_LR_CRITIC = 20, BDR_HYPER_CRITIC_BETA1 = 21, BDR_HYPER_CRITIC_BETA2 = 22, BDR_HYPER_CRITIC_EPS = 23, BDR_HYPER_CRITIC_WEIGHT_DECAY = 24,
+    BDR_HYPER_LR_VALUE = 30, BDR_HYPER_VALUE_BETA1 = 31, BDR_HYPER_VALUE_BETA2 = 32, BDR_HYPER_VALUE_EPS = 33, BDR_HYPER_VALUE_WEIGHT_DECAY = 34,
+    BDR_HYPER_GAMMA = 40, BDR_HYPER_CRITIC_TAU = 41, BDR_HYPER_TAU_IQL = 42, BDR_HYPER_INV_LAMBDA = 43, BDR_HYPER_EXP_ADV_MAX = 44,
+    BDR_HYPER_ENT_COEF_LR = 45, BDR_HYPER_TARGET_ENTROPY = 46
+};
+BDR_API int32_t bdr_agent_hyper_get(bdr_agent* a, int32_t id, double* out);
+BDR_API int32_t bdr_agent_hyper_set(bdr_agent* a, int32_t id, double v);
+
+/* bdr_<kind>_group_copy_members: member dst[i] becomes a copy of member src[i], i < n, in ONE launch whatever n and the number of
+ * models are - no copy command, no event, no synchronise; the call counts as one launch in bdr_group_info::kernel_launches and
+ * launches_per_round stays what it is.
+ * What moves, on the device: every arena the member's model table serves (bdr_agent_get_params: online and target networks, +100 the
+ * last gradient, +200 exp_avg, +300 exp_avg_sq; the candle SAC's log_alpha with its gradient and moments, and alpha).  On the host: the
+ * optimizer step counters that become Adam's bias corrections, so the destination continues exactly as its source would; with
+ * flags & BDR_COPY_HYPER every hyperparameter above that both members have.
+ * What stays the destination's: its seed and noise counter, train / eval mode, act path, its buffer or view with its index stream,
+ * n_opts, the record of its last update, and the evaluator's best-model bookkeeping - exploration stays independent.  Every derived
+ * copy of the destination's parameters follows as after bdr_agent_set_params (the candle SAC's alpha is carried by the copy itself:
+ * it keeps the bits its source's update wrote).
+ * Refused with BDR_ERR_INVALID before anything moves, naming the pair: n == 0; an index >= the group's size; src[i] == dst[i]; a
+ * destination listed twice; a member that is a destination in one pair and a source in another (so no member is read and written by
+ * one call); unknown flags; more than 65535 segments - n x the member's arenas (BC 4, AWAC 4 + 5 n_critics, IQL 8 + 5 n_critics, the
+ * candle SAC 5 + 5 n_critics), the extent of a grid dimension: split the call. */
+#define BDR_COPY_HYPER 1
+BDR_API int32_t bdr_bc_group_copy_members(bdr_bc_group* g, const uint32_t* src, const uint32_t* dst, uint32_t n, uint32_t flags);
+BDR_API int32_t bdr_iql_group_copy_members(bdr_iql_group* g, const uint32_t* src, const uint32_t* dst, uint32_t n, uint32_t flags);
+BDR_API int32_t bdr_awac_group_copy_members(bdr_awac_group* g, const uint32_t* src, const uint32_t* dst, uint32_t n, uint32_t flags);
+BDR_API int32_t bdr_candle_sac_group_copy_members(bdr_candle_sac_group* g, const uint32_t* src, const uint32_t* dst, uint32_t n, uint32_t flags);
+
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU parameter exchange (replaces the learner->actors NamedTensors channel of
  * border-async-trainer/src/async_trainer/base.rs:268-272 with RCCL over xGMI).

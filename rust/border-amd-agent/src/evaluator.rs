@@ -48,10 +48,91 @@ impl ActPath {
     }
 }
 
+/// A settable hyperparameter of a BC, IQL, AWAC or candle SAC agent (`BDR_HYPER_*`): BC has `Lr` .. `WeightDecay`; the others the
+/// learning rate and optimizer scalars of each of their models, `Gamma`, `CriticTau` and what their loss reads (`TauIql`, `InvLambda`,
+/// `ExpAdvMax`; with `EntCoefMode::Auto` `EntCoefLr`, `TargetEntropy`).  An id the agent's kind does not have is an error.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Hyper {
+    Lr,
+    Beta1,
+    Beta2,
+    Eps,
+    WeightDecay,
+    LrActor,
+    ActorBeta1,
+    ActorBeta2,
+    ActorEps,
+    ActorWeightDecay,
+    LrCritic,
+    CriticBeta1,
+    CriticBeta2,
+    CriticEps,
+    CriticWeightDecay,
+    LrValue,
+    ValueBeta1,
+    ValueBeta2,
+    ValueEps,
+    ValueWeightDecay,
+    Gamma,
+    CriticTau,
+    TauIql,
+    InvLambda,
+    ExpAdvMax,
+    EntCoefLr,
+    TargetEntropy,
+}
+
+impl Hyper {
+    pub fn code(self) -> i32 {
+        match self {
+            Hyper::Lr => ffi::BDR_HYPER_LR,
+            Hyper::Beta1 => ffi::BDR_HYPER_BETA1,
+            Hyper::Beta2 => ffi::BDR_HYPER_BETA2,
+            Hyper::Eps => ffi::BDR_HYPER_EPS,
+            Hyper::WeightDecay => ffi::BDR_HYPER_WEIGHT_DECAY,
+            Hyper::LrActor => ffi::BDR_HYPER_LR_ACTOR,
+            Hyper::ActorBeta1 => ffi::BDR_HYPER_ACTOR_BETA1,
+            Hyper::ActorBeta2 => ffi::BDR_HYPER_ACTOR_BETA2,
+            Hyper::ActorEps => ffi::BDR_HYPER_ACTOR_EPS,
+            Hyper::ActorWeightDecay => ffi::BDR_HYPER_ACTOR_WEIGHT_DECAY,
+            Hyper::LrCritic => ffi::BDR_HYPER_LR_CRITIC,
+            Hyper::CriticBeta1 => ffi::BDR_HYPER_CRITIC_BETA1,
+            Hyper::CriticBeta2 => ffi::BDR_HYPER_CRITIC_BETA2,
+            Hyper::CriticEps => ffi::BDR_HYPER_CRITIC_EPS,
+            Hyper::CriticWeightDecay => ffi::BDR_HYPER_CRITIC_WEIGHT_DECAY,
+            Hyper::LrValue => ffi::BDR_HYPER_LR_VALUE,
+            Hyper::ValueBeta1 => ffi::BDR_HYPER_VALUE_BETA1,
+            Hyper::ValueBeta2 => ffi::BDR_HYPER_VALUE_BETA2,
+            Hyper::ValueEps => ffi::BDR_HYPER_VALUE_EPS,
+            Hyper::ValueWeightDecay => ffi::BDR_HYPER_VALUE_WEIGHT_DECAY,
+            Hyper::Gamma => ffi::BDR_HYPER_GAMMA,
+            Hyper::CriticTau => ffi::BDR_HYPER_CRITIC_TAU,
+            Hyper::TauIql => ffi::BDR_HYPER_TAU_IQL,
+            Hyper::InvLambda => ffi::BDR_HYPER_INV_LAMBDA,
+            Hyper::ExpAdvMax => ffi::BDR_HYPER_EXP_ADV_MAX,
+            Hyper::EntCoefLr => ffi::BDR_HYPER_ENT_COEF_LR,
+            Hyper::TargetEntropy => ffi::BDR_HYPER_TARGET_ENTROPY,
+        }
+    }
+}
+
 /// `Policy::sample` on raw environment rows (`bdr_agent_sample_raw`) and the choice of the acting path.
 pub trait SampleRaw {
     fn raw_handle(&self) -> *mut ffi::bdr_agent;
     fn raw_act_dim(&self) -> usize;
+
+    /// The value of one settable hyperparameter (`bdr_agent_hyper_get`).
+    fn hyper(&self, id: Hyper) -> Result<f64> {
+        let mut v = 0f64;
+        check(unsafe { ffi::bdr_agent_hyper_get(self.raw_handle(), id.code(), &mut v) })?;
+        Ok(v)
+    }
+
+    /// Sets it (`bdr_agent_hyper_set`): in force from the agent's next update, standalone or as a group member.  A value outside
+    /// the field's range is an error and changes nothing.
+    fn set_hyper(&mut self, id: Hyper, v: f64) -> Result<()> {
+        check(unsafe { ffi::bdr_agent_hyper_set(self.raw_handle(), id.code(), v) })
+    }
 
     /// `ActPath::Fused` on a network the kernel does not cover (a padded layer wider than 512) is an error with the reason.
     fn set_act_path(&mut self, path: ActPath) -> Result<()> {

@@ -145,6 +145,36 @@ pub const BDR_TRAINER_EVENT_EVAL: i32 = 4;
 pub const BDR_ACT_PATH_DEFAULT: i32 = 0;
 pub const BDR_ACT_PATH_LAYERS: i32 = 1;
 pub const BDR_ACT_PATH_FUSED: i32 = 2;
+// BDR_HYPER_*: the settable scalar fields of a BC, IQL, AWAC or candle SAC agent (bdr_agent_hyper_get / _set)
+pub const BDR_HYPER_LR: i32 = 0;
+pub const BDR_HYPER_BETA1: i32 = 1;
+pub const BDR_HYPER_BETA2: i32 = 2;
+pub const BDR_HYPER_EPS: i32 = 3;
+pub const BDR_HYPER_WEIGHT_DECAY: i32 = 4;
+pub const BDR_HYPER_LR_ACTOR: i32 = 10;
+pub const BDR_HYPER_ACTOR_BETA1: i32 = 11;
+pub const BDR_HYPER_ACTOR_BETA2: i32 = 12;
+pub const BDR_HYPER_ACTOR_EPS: i32 = 13;
+pub const BDR_HYPER_ACTOR_WEIGHT_DECAY: i32 = 14;
+pub const BDR_HYPER_LR_CRITIC: i32 = 20;
+pub const BDR_HYPER_CRITIC_BETA1: i32 = 21;
+pub const BDR_HYPER_CRITIC_BETA2: i32 = 22;
+pub const BDR_HYPER_CRITIC_EPS: i32 = 23;
+pub const BDR_HYPER_CRITIC_WEIGHT_DECAY: i32 = 24;
+pub const BDR_HYPER_LR_VALUE: i32 = 30;
+pub const BDR_HYPER_VALUE_BETA1: i32 = 31;
+pub const BDR_HYPER_VALUE_BETA2: i32 = 32;
+pub const BDR_HYPER_VALUE_EPS: i32 = 33;
+pub const BDR_HYPER_VALUE_WEIGHT_DECAY: i32 = 34;
+pub const BDR_HYPER_GAMMA: i32 = 40;
+pub const BDR_HYPER_CRITIC_TAU: i32 = 41;
+pub const BDR_HYPER_TAU_IQL: i32 = 42;
+pub const BDR_HYPER_INV_LAMBDA: i32 = 43;
+pub const BDR_HYPER_EXP_ADV_MAX: i32 = 44;
+pub const BDR_HYPER_ENT_COEF_LR: i32 = 45;
+pub const BDR_HYPER_TARGET_ENTROPY: i32 = 46;
+/// `bdr_*_group_copy_members` flag: the destination also takes the source's settable hyperparameters
+pub const BDR_COPY_HYPER: u32 = 1;
 
 // opaque handles
 /// `bdr_agent_group` (a launch grouping of Mlp DQN agents): only ever behind a pointer.
@@ -1345,6 +1375,12 @@ extern "C" {
         out: *mut bdr_trainer_stats,
     ) -> i32;
     pub fn bdr_agent_set_act_path(a: *mut bdr_agent, path: i32) -> i32;
+    pub fn bdr_agent_hyper_get(a: *mut bdr_agent, id: i32, out: *mut f64) -> i32;
+    pub fn bdr_agent_hyper_set(a: *mut bdr_agent, id: i32, v: f64) -> i32;
+    pub fn bdr_bc_group_copy_members(g: *mut bdr_bc_group, src: *const u32, dst: *const u32, n: u32, flags: u32) -> i32;
+    pub fn bdr_iql_group_copy_members(g: *mut bdr_iql_group, src: *const u32, dst: *const u32, n: u32, flags: u32) -> i32;
+    pub fn bdr_awac_group_copy_members(g: *mut bdr_awac_group, src: *const u32, dst: *const u32, n: u32, flags: u32) -> i32;
+    pub fn bdr_candle_sac_group_copy_members(g: *mut bdr_candle_sac_group, src: *const u32, dst: *const u32, n: u32, flags: u32) -> i32;
     pub fn bdr_agent_sample_raw(
         a: *mut bdr_agent,
         norm: *const bdr_obs_norm,

@@ -741,6 +741,22 @@ where
         Ok(stats)
     }
 
+    /// Member `dst` becomes a copy of member `src` for every `(src, dst)` of `pairs`, ONE launch whatever their number
+    /// (`bdr_bc_group_copy_members`); does not synchronise.  Every arena of the model table moves (networks and targets, the last
+    /// gradient, exp_avg, exp_avg_sq) with the optimizer step counters, and with `hyper` every settable hyperparameter; the
+    /// destination keeps its seed, noise counter, mode, act path, buffer and index stream, n_opts and best-model bookkeeping.
+    /// Refused, naming the pair, before anything moves: an index out of range, `src == dst`, a destination listed twice, a member
+    /// that is a destination in one pair and a source in another.  An empty list does nothing.
+    pub fn copy_members(&mut self, pairs: &[(u32, u32)], hyper: bool) -> Result<()> {
+        if pairs.is_empty() {
+            return Ok(());
+        }
+        let src: Vec<u32> = pairs.iter().map(|p| p.0).collect();
+        let dst: Vec<u32> = pairs.iter().map(|p| p.1).collect();
+        let flags = if hyper { ffi::BDR_COPY_HYPER } else { 0 };
+        check(unsafe { ffi::bdr_bc_group_copy_members(self.g, src.as_ptr(), dst.as_ptr(), pairs.len() as u32, flags) })
+    }
+
     /// Waits for everything the group and its members have enqueued (`bdr_bc_group_sync`).
     pub fn sync(&mut self) -> Result<()> {
         check(unsafe { ffi::bdr_bc_group_sync(self.g) })
@@ -971,6 +987,22 @@ where
         check(unsafe { ffi::bdr_trainer_train_offline_group_post(config, &ops, &post, None, std::ptr::null_mut(), stats.as_mut_ptr()) })?;
         self.sync()?;
         Ok(stats)
+    }
+
+    /// Member `dst` becomes a copy of member `src` for every `(src, dst)` of `pairs`, ONE launch whatever their number
+    /// (`bdr_iql_group_copy_members`); does not synchronise.  Every arena of the model table moves (networks and targets, the last
+    /// gradient, exp_avg, exp_avg_sq) with the optimizer step counters, and with `hyper` every settable hyperparameter; the
+    /// destination keeps its seed, noise counter, mode, act path, buffer and index stream, n_opts and best-model bookkeeping.
+    /// Refused, naming the pair, before anything moves: an index out of range, `src == dst`, a destination listed twice, a member
+    /// that is a destination in one pair and a source in another.  An empty list does nothing.
+    pub fn copy_members(&mut self, pairs: &[(u32, u32)], hyper: bool) -> Result<()> {
+        if pairs.is_empty() {
+            return Ok(());
+        }
+        let src: Vec<u32> = pairs.iter().map(|p| p.0).collect();
+        let dst: Vec<u32> = pairs.iter().map(|p| p.1).collect();
+        let flags = if hyper { ffi::BDR_COPY_HYPER } else { 0 };
+        check(unsafe { ffi::bdr_iql_group_copy_members(self.g, src.as_ptr(), dst.as_ptr(), pairs.len() as u32, flags) })
     }
 
     /// Waits for everything the group and its members have enqueued (`bdr_iql_group_sync`).
@@ -1328,6 +1360,22 @@ where
     }
 
 
+    /// Member `dst` becomes a copy of member `src` for every `(src, dst)` of `pairs`, ONE launch whatever their number
+    /// (`bdr_awac_group_copy_members`); does not synchronise.  Every arena of the model table moves (networks and targets, the last
+    /// gradient, exp_avg, exp_avg_sq) with the optimizer step counters, and with `hyper` every settable hyperparameter; the
+    /// destination keeps its seed, noise counter, mode, act path, buffer and index stream, n_opts and best-model bookkeeping.
+    /// Refused, naming the pair, before anything moves: an index out of range, `src == dst`, a destination listed twice, a member
+    /// that is a destination in one pair and a source in another.  An empty list does nothing.
+    pub fn copy_members(&mut self, pairs: &[(u32, u32)], hyper: bool) -> Result<()> {
+        if pairs.is_empty() {
+            return Ok(());
+        }
+        let src: Vec<u32> = pairs.iter().map(|p| p.0).collect();
+        let dst: Vec<u32> = pairs.iter().map(|p| p.1).collect();
+        let flags = if hyper { ffi::BDR_COPY_HYPER } else { 0 };
+        check(unsafe { ffi::bdr_awac_group_copy_members(self.g, src.as_ptr(), dst.as_ptr(), pairs.len() as u32, flags) })
+    }
+
     /// Waits for everything the group and its members have enqueued (`bdr_awac_group_sync`).
     pub fn sync(&mut self) -> Result<()> {
         check(unsafe { ffi::bdr_awac_group_sync(self.g) })
@@ -1682,6 +1730,22 @@ where
         Ok(stats)
     }
 
+
+    /// Member `dst` becomes a copy of member `src` for every `(src, dst)` of `pairs`, ONE launch whatever their number
+    /// (`bdr_candle_sac_group_copy_members`); does not synchronise.  Every arena of the model table moves (networks and targets, the last
+    /// gradient, exp_avg, exp_avg_sq) with the optimizer step counters, and with `hyper` every settable hyperparameter; the
+    /// destination keeps its seed, noise counter, mode, act path, buffer and index stream, n_opts and best-model bookkeeping.
+    /// Refused, naming the pair, before anything moves: an index out of range, `src == dst`, a destination listed twice, a member
+    /// that is a destination in one pair and a source in another.  An empty list does nothing.
+    pub fn copy_members(&mut self, pairs: &[(u32, u32)], hyper: bool) -> Result<()> {
+        if pairs.is_empty() {
+            return Ok(());
+        }
+        let src: Vec<u32> = pairs.iter().map(|p| p.0).collect();
+        let dst: Vec<u32> = pairs.iter().map(|p| p.1).collect();
+        let flags = if hyper { ffi::BDR_COPY_HYPER } else { 0 };
+        check(unsafe { ffi::bdr_candle_sac_group_copy_members(self.g, src.as_ptr(), dst.as_ptr(), pairs.len() as u32, flags) })
+    }
 
     /// Waits for everything the group and its members have enqueued (`bdr_candle_sac_group_sync`).
     pub fn sync(&mut self) -> Result<()> {

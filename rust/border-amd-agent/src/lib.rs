@@ -65,7 +65,7 @@ pub use candle_sac::AmdCandleSac;
 pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;
 pub use group::{AmdAwacGroup, AmdBcGroup, AmdCandleSacGroup, AmdDqnGroup, AmdIqlGroup, GroupEvaluator};
-pub use evaluator::{ActPath, AmdEvaluator, EvalResult, SampleRaw, TrainerPost};
+pub use evaluator::{ActPath, AmdEvaluator, EvalResult, Hyper, SampleRaw, TrainerPost};
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;
 pub use replay::AmdReplayBuffer;
