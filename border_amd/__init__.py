@@ -7,7 +7,7 @@ from ._lib import BdrError, device_count  # noqa: F401
 from .replay import GenericTransitionBatch, PerConfig, SimpleReplayBuffer, SimpleReplayBufferConfig  # noqa: F401
 from .dataset import ObsNormalizer, create_replay_buffer  # noqa: F401
 from .dqn import AtariCnnConfig, Dqn, DqnConfig, DqnModelConfig, EpsilonGreedy, MlpConfig, OptimizerConfig, Softmax  # noqa: F401
-from .group import AwacGroup, BcGroup, CandleSacGroup, DqnGroup, IqlGroup  # noqa: F401
+from .group import AwacGroup, BcGroup, CandleDqnGroup, CandleSacGroup, DqnGroup, IqlGroup  # noqa: F401
 from .sac import Sac, SacConfig  # noqa: F401
 from .iqn import Iqn, IqnConfig  # noqa: F401
 from .iql import ActionLimit, CandleMlpConfig, GaussianActorConfig, Iql, IqlConfig, MultiCriticConfig, ValueConfig  # noqa: F401

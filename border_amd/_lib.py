@@ -210,6 +210,7 @@ SAVE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_char_p)
 GROUP_FORM_ONE_WORKGROUP, GROUP_FORM_LAYERS, GROUP_FORM_BC_LAYERS, GROUP_FORM_IQL_LAYERS = 0, 1, 2, 3
 GROUP_FORM_AWAC_LAYERS = 4
 GROUP_FORM_CANDLE_SAC_LAYERS = 5
+GROUP_FORM_CANDLE_DQN_LAYERS = 6
 
 
 class GroupInfoC(C.Structure):
@@ -381,6 +382,11 @@ ABI_SYMBOLS = [
     "bdr_awac_group_ctrainer_ops_default", "bdr_candle_sac_group_ctrainer_ops_default", "bdr_trainer_train_cgroup_post",
     "bdr_agent_hyper_get", "bdr_agent_hyper_set", "bdr_bc_group_copy_members", "bdr_iql_group_copy_members", "bdr_awac_group_copy_members",
     "bdr_candle_sac_group_copy_members",
+    "bdr_candle_dqn_group_create", "bdr_candle_dqn_group_destroy", "bdr_candle_dqn_group_size", "bdr_candle_dqn_group_member", "bdr_candle_dqn_group_info",
+    "bdr_candle_dqn_group_opt", "bdr_candle_dqn_group_opt_with_scalars", "bdr_candle_dqn_group_sync",
+    "bdr_candle_dqn_group_sample", "bdr_candle_dqn_group_sample_members", "bdr_candle_dqn_group_last_q",
+    "bdr_candle_dqn_group_push", "bdr_candle_dqn_group_push_max_rows",
+    "bdr_candle_dqn_group_trainer_ops_default", "bdr_candle_dqn_group_eval_ops_default", "bdr_candle_dqn_group_trainer_post_default",
 ]
 
 # BDR_HYPER_* (include/border_amd.h): the settable scalar fields of a BC, IQL, AWAC or candle SAC agent, by name
@@ -442,7 +448,8 @@ def lib() -> C.CDLL:
                         "bdr_iql_group_eval_ops_default", "bdr_iql_group_trainer_ops_default", "bdr_iql_group_trainer_post_default",
                         "bdr_awac_group_eval_ops_default", "bdr_awac_group_trainer_ops_default", "bdr_awac_group_trainer_post_default",
                         "bdr_candle_sac_group_eval_ops_default", "bdr_candle_sac_group_trainer_ops_default", "bdr_candle_sac_group_trainer_post_default",
-                        "bdr_awac_group_ctrainer_ops_default", "bdr_candle_sac_group_ctrainer_ops_default"):
+                        "bdr_awac_group_ctrainer_ops_default", "bdr_candle_sac_group_ctrainer_ops_default",
+                        "bdr_candle_dqn_group_trainer_ops_default", "bdr_candle_dqn_group_eval_ops_default", "bdr_candle_dqn_group_trainer_post_default"):
             fn.restype = C.c_int32
     L.bdr_trainer_config_default.restype = None
     L.bdr_trainer_ops_default.restype = None
@@ -675,6 +682,25 @@ def lib() -> C.CDLL:
     L.bdr_candle_sac_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
     L.bdr_candle_sac_group_trainer_post_default.restype = None
     L.bdr_candle_sac_group_trainer_post_default.argtypes = [C.POINTER(BcGroupTrainerPostC), vp]
+    L.bdr_candle_dqn_group_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_candle_dqn_group_destroy.argtypes = [vp]
+    L.bdr_candle_dqn_group_size.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.bdr_candle_dqn_group_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_candle_dqn_group_info.argtypes = [vp, C.POINTER(GroupInfoC)]
+    L.bdr_candle_dqn_group_opt.argtypes = [vp, vp]
+    L.bdr_candle_dqn_group_opt_with_scalars.argtypes = [vp, vp, vp, i32, vp]
+    L.bdr_candle_dqn_group_sync.argtypes = [vp]
+    L.bdr_candle_dqn_group_sample.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.bdr_candle_dqn_group_sample_members.argtypes = [vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
+    L.bdr_candle_dqn_group_last_q.argtypes = [vp, C.c_uint32, vp, u64]
+    L.bdr_candle_dqn_group_push.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.bdr_candle_dqn_group_push_max_rows.argtypes = [vp, vp, vp, C.POINTER(u64)]
+    L.bdr_candle_dqn_group_trainer_ops_default.restype = None
+    L.bdr_candle_dqn_group_trainer_ops_default.argtypes = [C.POINTER(GroupTrainerOps), vp, vp]
+    L.bdr_candle_dqn_group_eval_ops_default.restype = None
+    L.bdr_candle_dqn_group_eval_ops_default.argtypes = [C.POINTER(GroupEvalOps), vp]
+    L.bdr_candle_dqn_group_trainer_post_default.restype = None
+    L.bdr_candle_dqn_group_trainer_post_default.argtypes = [C.POINTER(GroupTrainerPostC), vp]
     L.bdr_trainer_train_offline_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(GroupTrainerOps), C.POINTER(BcGroupTrainerPostC),
                                                        GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     for kind in ("awac", "candle_sac"):

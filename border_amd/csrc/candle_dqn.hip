@@ -21,6 +21,7 @@
 
 #include "candle_actor.hpp"
 #include "conv_trunk.hpp"
+#include "candle_dqn_group_plan.hpp"
 
 using namespace bdr;
 
@@ -28,14 +29,20 @@ namespace {
 
 // obs, next_obs [B][O] -> the zero-padded first-layer inputs x_o, x_no [B][Kp] in one launch (the padding columns were zeroed when
 // the buffers were allocated and are never written).  Bounds: t < B O; row b < B, column c < O <= Kp.
-__global__ __launch_bounds__(256) void k_cdqn_pack(const float* __restrict__ obs, const float* __restrict__ next_obs, int O, int Kp, int B,
-                                                   float* __restrict__ x_o, float* __restrict__ x_no)
+// (the body over its operands: the kernel's arguments, or a member's entry of a group's device array - candle_dqn_group.hpp)
+__device__ __forceinline__ void cdqn_pack_body(const float* __restrict__ obs, const float* __restrict__ next_obs, int O, int Kp, int B,
+                                               float* __restrict__ x_o, float* __restrict__ x_no)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= B * O) return;
     const size_t d = (size_t)(t / O) * Kp + t % O;
     x_o[d] = obs[t];
     x_no[d] = next_obs[t];
+}
+__global__ __launch_bounds__(256) void k_cdqn_pack(const float* __restrict__ obs, const float* __restrict__ next_obs, int O, int Kp, int B,
+                                                   float* __restrict__ x_o, float* __restrict__ x_no)
+{
+    cdqn_pack_body(obs, next_obs, O, Kp, B, x_o, x_no);
 }
 
 // ---- k_cdqn_td --------------------------------------------------------------------------------------------------------------------
@@ -66,16 +73,19 @@ struct CdqnTdArgs {
     float *pred, *q_next, *y, *tgt, *dpred, *lrow;                  // [B]
     float* scal; unsigned* err;
 };
-__device__ __forceinline__ long long cdqn_action(const CdqnTdArgs& p, int b, bool* bad)
+template <class Args>
+__device__ __forceinline__ long long cdqn_action(const Args& p, int b, bool* bad)
 {
     long long a = *reinterpret_cast<const long long*>(p.act + (size_t)b * p.act_bytes);
     *bad = a < 0 || a >= p.A;
     if (*bad) a = a < 0 ? 0 : p.A - 1;
     return a;
 }
-__global__ __launch_bounds__(1024) void k_cdqn_td(CdqnTdArgs p)
+// (the body over its argument struct: the kernel argument, or a member's entry of a group's device array read in place through the
+// constant address space - k_cdqn_td_group, candle_dqn_group.hpp; red: the workgroup's float[32])
+template <class Args>
+__device__ __forceinline__ void cdqn_td_body(const Args& p, float* red)
 {
-    __shared__ float red[32];
     const float invB = 1.0f / (float)p.B;
     for (int b = threadIdx.x; b < p.B; b += 1024) {
 #pragma clang fp contract(off)
@@ -118,6 +128,11 @@ __global__ __launch_bounds__(1024) void k_cdqn_td(CdqnTdArgs p)
         p.scal[1] = candle::acc(0.f, sp, invB); p.scal[2] = candle::acc(0.f, sr, invB);
         p.scal[3] = candle::acc(0.f, st, invB); p.scal[4] = candle::acc(0.f, sd, invB);
     }
+}
+__global__ __launch_bounds__(1024) void k_cdqn_td(CdqnTdArgs p)
+{
+    __shared__ float red[32];
+    cdqn_td_body(p, red);
 }
 
 // Policy::sample's device part on the layer path (dqn/base.rs:203, :226) from the last layer's output z [n][ld]: q [n][A] = the
@@ -280,7 +295,7 @@ struct CandleDqn : DenseAgent {
     unsigned long long* applied = nullptr;   // device: the Adam step number of the last reduce + Adam launch that was not skipped
     SmallRng rng;
     // batch buffers
-    int B = 0;
+    int B = 0; uint64_t batch_gen = 0;   // batch_gen: bumped whenever the batch buffers are re-allocated (candle_dqn_group.hpp keys its static arguments on it)
     float *x_o = nullptr, *x_no = nullptr;                 // [B][Kp] padded obs, next_obs
     std::vector<float*> a_on, a_tg, a_onn, dy;             // activations of (p, obs), (p_tgt, next_obs), (p, next_obs); gradients
     float *pr_pred = nullptr, *pr_qn = nullptr, *pr_y = nullptr, *pr_tgt = nullptr, *pr_dpred = nullptr, *lrow = nullptr;   // [B]
@@ -318,7 +333,7 @@ struct CandleDqn : DenseAgent {
         BDR_TRY(alloc(&part, plan(net, Bn, off), BATCH));
         BDR_TRY(alloc(&samp, (size_t)Bn * A, BATCH));
         BDR_TRY(alloc(&samp_idx, Bn, BATCH));
-        B = Bn;
+        B = Bn; batch_gen += 1;
         return BDR_OK;
     }
 
@@ -789,9 +804,9 @@ int32_t cdqn_check(const bdr_candle_dqn_config& c)
 {
     BDR_REQUIRE(c.device >= 0, "No device is given for DQN agent");   // dqn/base.rs:245-248
     BDR_REQUIRE(c.obs_dim >= 1 && c.obs_dim <= 4096, "bad obs dim");
-    BDR_REQUIRE(c.n_actions >= 1 && c.n_actions <= 4096, "n_actions must be in [1, 4096], got %d", c.n_actions);
+    BDR_REQUIRE(c.n_actions >= 1 && c.n_actions <= CQ_MAX_ACTIONS, "n_actions must be in [1, %d], got %d", CQ_MAX_ACTIONS, c.n_actions);
     BDR_TRY(check_mlp(c.qnet, "qnet", false));
-    BDR_REQUIRE(c.batch_size >= 1 && c.batch_size <= 65536, "bad batch size");
+    BDR_REQUIRE(c.batch_size >= 1 && c.batch_size <= (uint64_t)CQ_MAX_BATCH, "bad batch size");   // (candle_dqn_group_plan.hpp: the limits the TD launch indexes)
     BDR_REQUIRE(c.soft_update_interval >= 1 && c.n_updates_per_opt >= 1, "intervals must be >= 1");
     BDR_REQUIRE(c.critic_loss == BDR_LOSS_MSE || c.critic_loss == BDR_LOSS_SMOOTH_L1, "unknown critic loss %d", c.critic_loss);
     BDR_TRY(check_opt(c.opt, "qnet"));
@@ -826,6 +841,8 @@ int32_t cdqn_cnn_check(const bdr_candle_dqn_cnn_config& c, bdr_candle_dqn_config
 }
 
 }  // namespace
+
+#include "candle_dqn_group.hpp"   // the launch grouping of Mlp-form agents: needs CandleDqn and the bodies above
 
 extern "C" {
 

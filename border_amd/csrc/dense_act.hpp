@@ -132,6 +132,19 @@ __device__ __forceinline__ void dense_act_land(const f32x4 (&v)[8], const f32x4&
     asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(b));
 }
 
+// the candle DQN's epilogue (dqn/base.rs:203), once for DA_EPI_ALL's DA_DQN branch and for DA_EPI_DQN: the Q rows themselves - the
+// last layer's rows in LDS without their padding - and each row's first maximum (dqn_q_argmax).  Bounds: rr < rows_here <= 32,
+// j < A <= ld - 4; out at (m0 + rr) * A + j, idx at m0 + tid, both below the call's n rows.
+template <int NTHR>
+__device__ __forceinline__ void dense_act_dqn_rows(const float* cur, int ld, int A, int m0, int rows_here, int tid, float* out, long long* idx)
+{
+    for (int e = tid; e < rows_here * A; e += NTHR) {
+        const int rr = e / A, j = e % A;
+        out[(size_t)(m0 + rr) * A + j] = cur[rr * ld + j];
+    }
+    if (tid < rows_here) idx[m0 + tid] = dqn_q_argmax(cur + tid * ld, A);
+}
+
 // The body of k_dense_act and of the group entry k_bc_act_group (bc_group.hpp).  `a`: the network and the epilogue (layers, widths,
 // mode, kind, A, O, W); `call`: the words of this call (rows, row_stride, f64, n, mean, std, out, idx).  The standalone kernel passes
 // its one argument struct as both; the group entry passes a member's entries of two arrays it reads in place through the constant
@@ -143,7 +156,9 @@ __device__ __forceinline__ void dense_act_land(const f32x4 (&v)[8], const f32x4&
 //                  field - the static words (head2, the clamps, the limit, seed, mlp2) from a.e, the words of this call (train,
 //                  counter) from `call`, z null: the draw of element t = (m0 + rr) * A + j of the member's own call is counter + t,
 //                  the one the member's own kernel takes.  Every thread returns to the entry.
-enum { DA_EPI_ALL = 0, DA_EPI_BC = 1, DA_EPI_CANDLE = 2 };
+//   DA_EPI_DQN     the caller has refused every mode but DA_DQN (k_cdqn_act_group, candle_dqn_group.hpp): the Q rows and each row's
+//                  first maximum, as DA_EPI_ALL's DA_DQN branch writes them; every thread returns to the entry.
+enum { DA_EPI_ALL = 0, DA_EPI_BC = 1, DA_EPI_CANDLE = 2, DA_EPI_DQN = 3 };
 template <int TEAMS, int EPI, class Args, class Call>
 __device__ __forceinline__ void dense_act_body(const Args& a, const Call& call, float* da_lds)
 {
@@ -236,16 +251,14 @@ __device__ __forceinline__ void dense_act_body(const Args& a, const Call& call, 
             if (tid < rows_here) call.idx[m0 + tid] = bc_argmax(a.kind, cur + tid * ldz, a.A);
             return;
         }
-        if (a.mode == DA_DQN) {   // the candle DQN (dqn/base.rs:203): the Q rows themselves and each row's first maximum (dqn_q_argmax)
-            for (int e = tid; e < rows_here * a.A; e += NTHR) {
-                const int rr = e / a.A, j = e % a.A;
-                call.out[(size_t)(m0 + rr) * a.A + j] = cur[rr * ldz + j];
-            }
-            if (tid < rows_here) call.idx[m0 + tid] = dqn_q_argmax(cur + tid * ldz, a.A);
+        if (a.mode == DA_DQN) {
+            dense_act_dqn_rows<NTHR>(cur, ldz, a.A, m0, rows_here, tid, call.out, call.idx);
             return;
         }
     }
-    if constexpr (EPI == DA_EPI_CANDLE) {
+    if constexpr (EPI == DA_EPI_DQN) {
+        dense_act_dqn_rows<NTHR>(cur, ldz, a.A, m0, rows_here, tid, call.out, call.idx);
+    } else if constexpr (EPI == DA_EPI_CANDLE) {
         SampleElem se;   // field by field: static indices, registers
         se.head2 = a.e.head2; se.lo = a.e.lo; se.hi = a.e.hi; se.tanh_limit = a.e.tanh_limit; se.amin = a.e.amin; se.amax = a.e.amax; se.scale = a.e.scale;
         se.seed = a.e.seed; se.mlp2 = a.e.mlp2;

@@ -174,7 +174,7 @@ struct DenseAgent : bdr_agent {
     // copy from `src`, an agent of the same kind and shape - the optimizer step counters, and with `hypers` every settable
     // hyperparameter both have; seed, noise counter, mode, act path, n_opts and everything about buffers stay this agent's.
     struct StateArena { float* p; size_t n; };
-    virtual void state_arenas(std::vector<StateArena>& out) { out.clear(); }   // (the candle DQN joins none of these groups)
+    virtual void state_arenas(std::vector<StateArena>& out) { out.clear(); }   // (the candle DQN's group, candle_dqn_group.hpp, has no copy between members: it lists none)
     virtual void adopt_steps(const DenseAgent&) {}
     void state_adopt(const DenseAgent& src, bool hypers)
     {

@@ -48,6 +48,18 @@ template <class C> using GroupActKernel = void (*)(const BDR_CONST_AS DenseActAr
 template <class C, GroupActKernel<C> K1, GroupActKernel<C> K2>
 struct GroupActEntry {
     using Call = C;
+    // The result step of a call, what the four float-action kinds do; a kind whose members act otherwise (the candle DQN:
+    // candle_dqn_group.hpp) shadows these.  Out: the element of act_out; act_cols(shape): the action width A; res_cols(A): the floats
+    // a member's result block holds per row; result(m, block, n, A, out): the member's block -> its act_out rows, after the launch
+    // has arrived, in selection order.
+    using Out = float;
+    template <class Shape> int act_cols(const Shape& s) const { return s.act_dim; }
+    int res_cols(int A) const { return A; }
+    template <class M> int32_t result(M*, const float* block, uint64_t n, int A, float* out) const
+    {
+        memcpy(out, block, (size_t)n * A * sizeof(float));
+        return BDR_OK;
+    }
     hipError_t set_lds_attr(int teams) const
     {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(teams == 2 ? K2 : K1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DA_LDS_MAX);
@@ -63,7 +75,7 @@ struct GroupActEntry {
 // Policy::sample of the selected members (members == nullptr: all of them) on n host rows each, ONE launch
 template <class Group, class Kind>
 int32_t group_act_sample(Group* g, Kind kind, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
-                         const int32_t* dtypes, float* const* act_out)
+                         const int32_t* dtypes, typename Kind::Out* const* act_out)
 {
     using Call = typename Kind::Call;
     auto& s = g->act;
@@ -75,7 +87,7 @@ int32_t group_act_sample(Group* g, Kind kind, const uint32_t* members, uint32_t 
     BDR_REQUIRE(pick.refusal != GA_COUNT, "%u rows for a group of %u", n_sel, P);
     const auto at = [&](uint32_t b) { return ga_member_at(members, b); };
     BDR_REQUIRE(n >= 1 && n <= GA_MAX_ROWS, "batch size out of range");
-    const int O = g->shape.obs_dim, A = g->shape.act_dim;
+    const int O = g->shape.obs_dim, A = kind.act_cols(g->shape), RC = kind.res_cols(A);
     if (!s.W) {
         s.W = g->members[0]->act_width();
         s.teams = dense_act_lds(s.W, 2) <= DA_LDS_MAX ? 2 : 1;
@@ -97,7 +109,7 @@ int32_t group_act_sample(Group* g, Kind kind, const uint32_t* members, uint32_t 
                     "such members keep acting standalone (bdr_agent_sample_raw)", p, DA_MAX_W, s.W);
         f64[p] = dt == BDR_DTYPE_F64 ? 1 : 0;
     }
-    const GaPlan plan = ga_plan(members, n_sel, P, n, O, A, f64.data());
+    const GaPlan plan = ga_plan(members, n_sel, P, n, O, RC, f64.data());   // (RC = A for every kind but the candle DQN)
     const size_t staged = plan.staged, res_floats = plan.res_floats;
     BDR_REQUIRE(plan.refusal == GA_OK,
                 "member %u .. %u: %zu bytes of rows and %zu bytes of actions in one group acting call, more than the staging area's %zu: split the call",
@@ -179,7 +191,7 @@ int32_t group_act_sample(Group* g, Kind kind, const uint32_t* members, uint32_t 
     BDR_TRY(wait_seq_word(g->seq.host.get(), (unsigned)k, g->stream, std::chrono::steady_clock::now(), &arrived));
     if (!arrived) return fail(BDR_ERR_HIP, "the actions of a group acting call never arrived in host memory");
     std::atomic_thread_fence(std::memory_order_acquire);
-    for (uint32_t b = 0; b < n_sel; ++b) memcpy(act_out[at(b)], s.res.host.get() + plan.res_off[b], (size_t)n * A * sizeof(float));
+    for (uint32_t b = 0; b < n_sel; ++b) BDR_TRY(kind.result(g->members[at(b)], s.res.host.get() + plan.res_off[b], n, A, act_out[at(b)]));
     return BDR_OK;
 }
 

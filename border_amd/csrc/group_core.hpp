@@ -198,6 +198,10 @@ int group_obs_dim(const void* group, uint32_t member)
     return g && member < g->members.size() ? g->members[member]->O : 0;
 }
 
+// the bytes of one action row of a member's ring: A f32 values, unless the kind says otherwise (K::act_row_bytes - the candle DQN: one i64)
+template <class K, class M> auto group_act_row_bytes(const M* m, int) -> decltype(K::act_row_bytes(m)) { return K::act_row_bytes(m); }
+template <class K, class M> uint64_t group_act_row_bytes(const M* m, long) { return (uint64_t)m->A * 4; }
+
 // the second of two members that name one bdr_replay (P: the P handles are all different)
 inline uint32_t group_shared_buffer(bdr_replay* const* buffers, uint32_t P)
 {
@@ -220,7 +224,7 @@ int32_t group_check_buffers(G* g, bdr_replay* const* buffers)
         const bdr_replay* r = buffers[p];
         BDR_REQUIRE(r, "member %u: null buffer", p);
         BDR_REQUIRE(!m->prof && !m->grad_comm, "member %u: profiling or a gradient communicator was switched on after the group was created", p);
-        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == (uint64_t)m->A * 4, "member %u: replay rows do not match %s obs/act dims (f32 rows)", p, K::NAME);
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == group_act_row_bytes<K>(m, 0), "member %u: replay rows do not match %s obs/act dims (f32 rows)", p, K::NAME);
         BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
         BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot be stepped by %s group (the grouped gather covers the uniform ring)", p, K::A);
         BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by %s group", p, K::A);
@@ -327,14 +331,14 @@ int32_t group_opt_with_scalars(G* g, bdr_replay* const* buffers, float* out, int
 
 // Policy::sample of the selected members (members == nullptr: all of them) on n host rows each, ONE launch (group_act.hpp)
 template <class G>
-int32_t group_sample(G* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows, const int32_t* dtypes, float* const* act_out)
+int32_t group_sample(G* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows, const int32_t* dtypes, typename G::Kind::Act::Out* const* act_out)
 {
     BDR_REQUIRE(g && rows && dtypes && act_out, "null argument");
     return group_act_sample(g, typename G::Kind::Act{}, nullptr, (uint32_t)g->members.size(), norms, n, rows, dtypes, act_out);
 }
 template <class G>
 int32_t group_sample_members(G* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
-                             const int32_t* dtypes, float* const* act_out)
+                             const int32_t* dtypes, typename G::Kind::Act::Out* const* act_out)
 {
     BDR_REQUIRE(g && members && rows && dtypes && act_out, "null argument");
     return group_act_sample(g, typename G::Kind::Act{}, members, n_sel, norms, n, rows, dtypes, act_out);
@@ -380,7 +384,7 @@ int32_t group_check_push(G* g, bdr_replay* const* buffers, uint64_t n, const voi
         BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot take the push of %s group (its sum tree is updated by bdr_replay_push)", p, K::A);
         BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot take the push of %s group", p, K::A);
         BDR_REQUIRE(r->index_rng == BDR_RNG_STDRNG, "member %u: %s group steps rings on the StdRng index stream only", p, K::A);
-        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == (uint64_t)m->A * 4, "member %u: replay rows do not match %s obs/act dims (f32 rows)", p, K::NAME);
+        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == group_act_row_bytes<K>(m, 0), "member %u: replay rows do not match %s obs/act dims (f32 rows)", p, K::NAME);
         bytes += n * (uint64_t)group_push_layout(r, dt == BDR_DTYPE_F64).rec_bytes;
         BDR_REQUIRE(bytes <= (uint64_t)G::PUSH_SLOT_BYTES,
                     "member %u: %llu rows per member do not fit one staging slot of %d bytes (descriptors and records of all members): split the call", p,

@@ -897,6 +897,69 @@ int32_t bdr_trainer_train_group_post(const bdr_trainer_config* c, const uint64_t
     return train_group_loop(c, obs_row_bytes, ops, envs, post, actions, bdr_evaluate_group, dg_save_member, obs, obs_ctx, out);
 }
 
+// ---- a candle DQN group behind the i64-action tables (bdr_group_trainer_ops, bdr_group_eval_ops): one float32 row and one i64 action
+// per member, over the group's own C functions
+namespace {
+using CandleDqnGroupEntries = GroupEntries<bdr_candle_dqn_group, bdr_candle_dqn_group_size, bdr_candle_dqn_group_member, bdr_candle_dqn_group_opt,
+                                           bdr_candle_dqn_group_opt_with_scalars, bdr_candle_dqn_group_sample_members>;
+// the per-member pointer arrays of a table call: their sizes are fixed per group, so they are kept from call to call (one set per
+// thread: a compiled loop runs on the thread that called it) instead of being allocated on every environment step
+struct CdqGroupScratch {
+    std::vector<int32_t> dtypes; std::vector<int64_t*> out; std::vector<const int64_t*> act; std::vector<const float*> rew; std::vector<const int8_t*> term, trunc;
+    void size(uint32_t P)
+    {
+        if (dtypes.size() == P) return;
+        dtypes.assign(P, BDR_DTYPE_F32); out.resize(P); act.resize(P); rew.resize(P); term.resize(P); trunc.resize(P);
+    }
+};
+CdqGroupScratch* cdq_scratch(void* g, uint32_t* P)
+{
+    static thread_local CdqGroupScratch s;
+    *P = 0;
+    if (bdr_candle_dqn_group_size((bdr_candle_dqn_group*)g, P) == BDR_OK) s.size(*P);
+    return &s;
+}
+int32_t cdq_group_sample_members(void* g, const uint32_t* members, uint32_t n_sel, const void* const* obs, int64_t* act)
+{
+    uint32_t P = 0;
+    CdqGroupScratch& s = *cdq_scratch(g, &P);
+    BDR_REQUIRE(P >= 1, "null group");
+    for (uint32_t p = 0; p < P; ++p) s.out[p] = act + p;
+    return members ? bdr_candle_dqn_group_sample_members((bdr_candle_dqn_group*)g, members, n_sel, nullptr, 1, obs, s.dtypes.data(), s.out.data())
+                   : bdr_candle_dqn_group_sample((bdr_candle_dqn_group*)g, nullptr, 1, obs, s.dtypes.data(), s.out.data());
+}
+int32_t cdq_group_sample(void* g, const void* const* obs, int64_t* act) { return cdq_group_sample_members(g, nullptr, 0, obs, act); }
+int32_t cdq_group_push(void* g, void* const* b, const void* const* obs, const int64_t* act, const void* const* next_obs, const float* rew, const int8_t* term,
+                       const int8_t* trunc)
+{
+    uint32_t P = 0;
+    CdqGroupScratch& s = *cdq_scratch(g, &P);
+    BDR_REQUIRE(P >= 1, "null group");
+    for (uint32_t p = 0; p < P; ++p) { s.act[p] = act + p; s.rew[p] = rew + p; s.term[p] = term + p; s.trunc[p] = trunc + p; }
+    return bdr_candle_dqn_group_push((bdr_candle_dqn_group*)g, (bdr_replay* const*)b, 1, obs, next_obs, nullptr, s.act.data(), s.rew.data(), s.term.data(), s.trunc.data());
+}
+}  // namespace
+void bdr_candle_dqn_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_candle_dqn_group* group, bdr_replay* const* buffers)
+{
+    CandleDqnGroupEntries::trainer_ops(ops, group, buffers);
+    if (ops) { ops->sample = cdq_group_sample; ops->push = cdq_group_push; }
+}
+void bdr_candle_dqn_group_eval_ops_default(bdr_group_eval_ops* ops, bdr_candle_dqn_group* group)
+{
+    if (!ops) return;
+    memset(ops, 0, sizeof *ops);
+    ops->group = group;
+    if (group) (void)bdr_candle_dqn_group_size(group, &ops->n_members);
+    ops->sample_members = cdq_group_sample_members;
+}
+void bdr_candle_dqn_group_trainer_post_default(bdr_group_trainer_post* post, bdr_candle_dqn_group* group)
+{
+    if (!post) return;
+    memset(post, 0, sizeof *post);
+    bdr_candle_dqn_group_eval_ops_default(&post->eval_ops, group);
+    post->save_member = CandleDqnGroupEntries::save_member;
+}
+
 void bdr_awac_group_ctrainer_ops_default(bdr_cgroup_trainer_ops* ops, bdr_awac_group* group, bdr_replay* const* buffers)
 {
     AwacGroupOnline::trainer_ops(ops, group, buffers);

@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from .awac import Awac
 from .bc import Bc
+from .candle_dqn import CandleDqn
 from .candle_sac import CandleSac
 from .dqn import Dqn, DqnConfig, record_keys
 from .iql import Iql
@@ -32,12 +33,17 @@ def raise_first(evaluators, status: int) -> None:
 
 GROUP_FORMS = {_lib.GROUP_FORM_ONE_WORKGROUP: "one_workgroup", _lib.GROUP_FORM_LAYERS: "layers", _lib.GROUP_FORM_BC_LAYERS: "bc_layers",
                _lib.GROUP_FORM_IQL_LAYERS: "iql_layers", _lib.GROUP_FORM_AWAC_LAYERS: "awac_layers",
-               _lib.GROUP_FORM_CANDLE_SAC_LAYERS: "candle_sac_layers"}
+               _lib.GROUP_FORM_CANDLE_SAC_LAYERS: "candle_sac_layers", _lib.GROUP_FORM_CANDLE_DQN_LAYERS: "candle_dqn_layers"}
 
 
 class DqnGroup:
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/agent_group.hpp bdr_agent_group::STEP_SLOTS)
     PUSH_STAGING_DEPTH = 8   # slots of the push staging ring (bdr_agent_group::PUSH_SLOTS)
+    _TRAINER_PREFIX = "bdr_group"   # NativeTrainer.train_group: bdr_group_trainer_ops_default / bdr_group_trainer_post_default
+
+    def obs_row_bytes(self) -> list:
+        """bytes of one float32 observation row of every member (NativeTrainer.train_group)"""
+        return [4 * a.config.model_config.q_config.in_dim for a in self._members]
 
     def __init__(self, agents, prioritized: bool = False):
         """Adopts already built `Dqn` agents: Mlp agents that all take the one-workgroup step, or - the layer form - that all have one
@@ -373,7 +379,7 @@ def _group_train_offline(group, prefix: str, record_keys, buffers, max_opts, rec
     return [{k: getattr(s, k) for k, _ in _lib.TrainerStatsC._fields_} for s in st]
 
 
-def _group_push_arrays(group, obs, act, next_obs, reward, is_terminated, is_truncated):
+def _group_push_arrays(group, obs, act, next_obs, reward, is_terminated, is_truncated, act_dtype=np.float32):
     """The per-member arrays of a grouped push: (n, obs, next_obs, dtype codes, act, reward, is_terminated, is_truncated), each a list
     of C-contiguous arrays in member order.  A field is one array per member (a list or tuple) or ONE ndarray that every member takes."""
     P = len(group._members)
@@ -402,7 +408,7 @@ def _group_push_arrays(group, obs, act, next_obs, reward, is_terminated, is_trun
             out.append(seen[id(r)])
         return out
     o, x = rows("obs", obs), rows("next_obs", next_obs)
-    a, r = cols("act", act, np.float32, ad), cols("reward", reward, np.float32, 0)
+    a, r = cols("act", act, act_dtype, ad), cols("reward", reward, np.float32, 0)   # (act_dtype: float32 rows, or the candle DQN's one int64)
     t, u = cols("is_terminated", is_terminated, np.int8, 0), cols("is_truncated", is_truncated, np.int8, 0)
     n = o[0].shape[0]
     for i in range(P):
@@ -471,12 +477,11 @@ class _OnlineGroup:
                                                           eval_interval=eval_interval, save_interval=save_interval, model_dirs=model_dirs)
 
 
-class _DenseGroup:
-    """What BcGroup, IqlGroup, AwacGroup and CandleSacGroup share: a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
+class _GroupBase:
+    """What every group on csrc/group_core.hpp shares (BcGroup, IqlGroup, AwacGroup, CandleSacGroup through _DenseGroup; CandleDqnGroup): a set of agents of one kind and shape whose Agent::opt runs as the launch sequence of ONE
     member, every launch serving all members (csrc/group_core.hpp through the kind's bdr_<kind>_group_* functions).  A subclass names
     the C prefix (_PREFIX), the member class (_MEMBER) and the keys of a member's Record (RECORD_KEYS)."""
     STAGING_DEPTH = 8   # slots of the per-step staging ring (csrc/group_core.hpp GroupCore::STEP_SLOTS)
-    COPY_STAGING_DEPTH = 8   # slots of the segment ring of copy_members (csrc/group_copy.hpp GC_SLOTS)
     _PREFIX = _MEMBER = None
     RECORD_KEYS = ()
 
@@ -583,6 +588,28 @@ class _DenseGroup:
         Each EvalResult is what evaluators[i].evaluate(member i) gives.  An exception raised by an environment is raised again here."""
         return _group_evaluate(self, self._PREFIX, evaluators)
 
+    def sync(self) -> None:
+        _lib.check(self._c("sync")(self._g))
+
+    def close(self) -> None:
+        if getattr(self, "_g", None):
+            _lib.check(self._c("destroy")(self._g))   # destroys the members
+            self._g = None
+            for a in self._members:
+                a._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DenseGroup(_GroupBase):
+    """_GroupBase plus what the four float-action kinds have and the candle DQN group has not: the compiled offline loop, copies
+    between members and the hyperparameters by id."""
+    COPY_STAGING_DEPTH = 8   # slots of the segment ring of copy_members (csrc/group_copy.hpp GC_SLOTS)
+
     def train_offline(self, buffers, max_opts: int, record_interval: int = 0, on_record=None, evaluators=None, eval_interval: int = 0,
                       save_interval: int = 0, model_dirs=None, on_event=None) -> list:
         """Trainer::train_offline over the group in compiled code (bdr_trainer_train_offline_group_post): max_opts update rounds on
@@ -620,22 +647,6 @@ class _DenseGroup:
     def set_hyper(self, member: int, name, value: float) -> None:
         """`members[member].set_hyper(name, value)`: in force from the next round"""
         self._members[member].set_hyper(name, value)
-
-    def sync(self) -> None:
-        _lib.check(self._c("sync")(self._g))
-
-    def close(self) -> None:
-        if getattr(self, "_g", None):
-            _lib.check(self._c("destroy")(self._g))   # destroys the members
-            self._g = None
-            for a in self._members:
-                a._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class BcGroup(_DenseGroup):
@@ -707,3 +718,128 @@ class CandleSacGroup(_DenseGroup):
     RECORD_KEYS = ("loss_critic", "loss_actor", "ent_coef")
     PUSH_STAGING_DEPTH, PUSH_SLOT_BYTES = _OnlineGroup.PUSH_STAGING_DEPTH, _OnlineGroup.PUSH_SLOT_BYTES
     push, push_max_rows, train = _OnlineGroup.push, _OnlineGroup.push_max_rows, _OnlineGroup.train   # (the online half: BcGroup and IqlGroup do not have it)
+
+
+class CandleDqnGroup(_GroupBase):
+    """A set of candle DQN agents (Mlp Q-network) of one shape whose Agent::opt (Dqn::opt_, dqn/base.rs:172-189) runs as the launch
+    sequence of ONE member, every launch serving all members (bdr_candle_dqn_group_*): 2 L + 4 launches per round for L layers (10 at
+    the dqn_cartpole shape), whatever the number of members.  One value for all members: obs_dim, n_actions, the Q-network's units and
+    activation_out, batch_size, double_dqn.  The members may differ in seed, explorer and its parameters, train / eval mode, optimizer,
+    learning rate, discount_factor, tau, soft_update_interval, critic_loss, record_verbose_level and act path; their buffers are
+    uniform buffers with int64 actions of their own or views of one (`SimpleReplayBuffer.view`).
+
+    The members are online agents: `sample` acts for the selected members in one launch and then runs each member's own explorer on
+    the host (one SmallRng stream per member across group calls, the member's own calls and rounds), `push` stores n transitions per
+    member in one launch, `evaluate` and `train` run the compiled lockstep loops.  A member whose batch holds an out-of-range action
+    is skipped on the device and reported by `sync` / `opt_with_record` as "member <i>: ..."; the others step.
+
+    A launch grouping, not an agent kind: the members are ordinary `CandleDqn` objects (every `CandleDqn` method keeps working on a
+    member and means what it meant) that the group owns - `CandleDqnGroup.close()` closes them, `member.close()` on a live group is
+    refused.  Results are bit for bit those of stepping the same agents one after the other.  Not built: copy_members and the
+    hyperparameter setters, the AtariCnn form, n_updates_per_opt > 1."""
+    _PREFIX, _MEMBER = "bdr_candle_dqn_group", CandleDqn
+    _TRAINER_PREFIX = "bdr_candle_dqn_group"   # NativeTrainer.train_group: the kind's default tables
+    PUSH_STAGING_DEPTH, PUSH_SLOT_BYTES = _OnlineGroup.PUSH_STAGING_DEPTH, _OnlineGroup.PUSH_SLOT_BYTES
+    push_max_rows = _OnlineGroup.push_max_rows
+
+    def obs_row_bytes(self) -> list:
+        return [4 * m.config.obs_dim for m in self._members]
+
+    def record_keys(self, member: int = 0) -> list:
+        """The keys of a member's opt_with_record record (bdr_agent_record_keys)."""
+        from .handle import record_keys
+        return record_keys(self._members[member].handle)
+
+    def opt_with_record(self, buffers=None) -> list:
+        """Agent::opt_with_record of every member (one synchronisation): a list of Record dicts in member order - loss, at
+        record_verbose_level >= 2 the four means and the parameter statistics, then ratio_best_act."""
+        n = len(self._members)
+        keys = [self.record_keys(i) for i in range(n)]
+        cap = max(8, max(len(k) for k in keys))   # (verbosity >= 2 adds the parameter statistics)
+        out = np.zeros((n, cap), np.float32)
+        cnt = np.zeros(n, np.int32)
+        _lib.check(self._c("opt_with_scalars")(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)))
+        return [{k: np.float32(v) for k, v in zip(keys[i], out[i, :cnt[i]])} for i in range(n)]
+
+    def sample(self, rows, norm=None, members=None) -> list:
+        """Policy::sample of the members in ONE launch (bdr_candle_dqn_group_sample / _sample_members): a list of int64 arrays [n] in
+        member order, each what that member's own `sample_raw(rows[i], norm[i])` gives at this point of its explorer stream.  rows,
+        norm and members as for the other dense groups; the entries of members that were not selected are None (they draw nothing)."""
+        P = len(self._members)
+        od = self._members[0].config.obs_dim
+        if isinstance(rows, np.ndarray):
+            rows = [rows] * P
+        rows = list(rows)
+        if len(rows) != P:
+            raise ValueError(f"{P} members need {P} row arrays, got {len(rows)}")
+        sel = list(range(P)) if members is None else [int(i) for i in members]
+        staged, ptrs, codes, outs, n = {}, (C.c_void_p * P)(), (C.c_int32 * P)(), [None] * P, None
+        for i in sel:
+            if not 0 <= i < P or rows[i] is None:
+                continue   # (the library refuses it, naming the member)
+            r = rows[i]
+            if id(r) not in staged:
+                a = np.asarray(r)
+                if a.dtype != np.float32:
+                    a = a.astype(np.float64, copy=False)
+                staged[id(r)] = np.ascontiguousarray(a).reshape(-1, od)
+            a = staged[id(r)]
+            if n is None:
+                n = a.shape[0]
+            elif a.shape[0] != n:
+                raise ValueError(f"member {i}: {a.shape[0]} rows, the members before it {n}: one n for every member")
+            ptrs[i], codes[i] = a.ctypes.data, _lib.BDR_DTYPE_F32 if a.dtype == np.float32 else _lib.BDR_DTYPE_F64
+            outs[i] = np.empty(n, np.int64)
+        n = 1 if n is None else n
+        out_ptrs = (C.c_void_p * P)(*[None if o is None else o.ctypes.data for o in outs])
+        norms, _keep = _group_norms(self, norm)
+        if members is None:
+            _lib.check(self._c("sample")(self._g, norms, n, ptrs, codes, out_ptrs))
+        else:
+            s = np.ascontiguousarray(sel, np.uint32).reshape(-1)
+            _lib.check(self._c("sample_members")(self._g, s.ctypes.data_as(C.c_void_p), s.size, norms, n, ptrs, codes, out_ptrs))
+        return outs
+
+    def last_q(self, member: int, n: int) -> np.ndarray:
+        """The action values [n, n_actions] the last group `sample` that selected `member` brought back for it."""
+        q = np.empty((n, self._members[member].n_actions), np.float32)
+        _lib.check(self._c("last_q")(self._g, int(member), q.ctypes.data_as(C.c_void_p), q.size))
+        return q
+
+    def push(self, obs, act, next_obs, reward, is_terminated, is_truncated, buffers=None) -> None:
+        """ExperienceBufferBase::push of n transitions per member into the member's own buffer, ONE launch
+        (bdr_candle_dqn_group_push); does not synchronise.  As `CandleSacGroup.push`, with act [n] int64 per member."""
+        bufs = self._buffers(buffers)
+        P = len(self._members)
+        acts = [act] * P if isinstance(act, np.ndarray) else list(act)
+        if len(acts) != P:
+            raise ValueError(f"{P} members need {P} arrays of act (or one array for all), got {len(acts)}")
+        a = [np.ascontiguousarray(v, np.int64).reshape(-1) for v in acts]
+        n, o, x, codes, a, r, t, u = _group_push_arrays(self, obs, a, next_obs, reward, is_terminated, is_truncated, act_dtype=np.int64)
+        ptrs = lambda arrs: (C.c_void_p * P)(*[v.ctypes.data for v in arrs])
+        _lib.check(self._c("push")(self._g, bufs, n, ptrs(o), ptrs(x), (C.c_int32 * P)(*codes), ptrs(a), ptrs(r), ptrs(t), ptrs(u)))
+
+    def evaluate(self, evaluators) -> list:
+        """The Evaluator of every member in lockstep (bdr_evaluate_group behind bdr_candle_dqn_group_eval_ops_default): member i on
+        evaluators[i] (an Evaluator built with act_dtype=np.int64), ONE acting launch per round over the members that still have an
+        episode open.  Each EvalResult is what evaluators[i].evaluate(member i) gives; the members stay in the mode they are in."""
+        from .evaluator import EvalResult
+        evaluators = list(evaluators)
+        n = len(self._members)
+        if len(evaluators) != n:
+            raise ValueError(f"{n} members need {n} evaluators, got {len(evaluators)}")
+        evs = (_lib.EvaluatorC * n)(*[e.c_struct() for e in evaluators])
+        ops = _lib.GroupEvalOps()
+        self._c("eval_ops_default")(C.byref(ops), self._g)
+        out = (_lib.EvalResultC * n)()
+        rc = _lib.lib().bdr_evaluate_group(evs, C.byref(ops), out)
+        raise_first(evaluators, rc)
+        return [EvalResult(np.float32(o.score), np.float32(o.normalized) if o.has_normalized else None, o.n_steps, o.n_episodes) for o in out]
+
+    def train(self, envs, buffers, trainer_config, on_event=None, evaluators=None, eval_interval=0, save_interval=0, model_dirs=None) -> list:
+        """The compiled online loop over the group (bdr_trainer_train_group / _post behind the kind's tables): as `DqnGroup.train`;
+        models are saved as qnet.pt / qnet_tgt.pt in model_dirs[i]/best and model_dirs[i]/<opt_steps>."""
+        from .trainer import NativeTrainer
+        self._buffers(buffers)   # (opt() / push() without buffers go on with these)
+        return NativeTrainer(trainer_config).train_group(envs, self, list(buffers), on_event=on_event, evaluators=evaluators,
+                                                         eval_interval=eval_interval, save_interval=save_interval, model_dirs=model_dirs)

@@ -316,7 +316,7 @@ class NativeTrainer:
         n = len(envs)
         if n != len(group) or n != len(buffers):
             raise ValueError(f"{len(group)} members need {len(group)} environments and buffers, got {n} and {len(buffers)}")
-        rows = [4 * a.config.model_config.q_config.in_dim for a in group.members]
+        rows, tables = group.obs_row_bytes(), group._TRAINER_PREFIX   # (DqnGroup, CandleDqnGroup: the row sizes and the kind's default tables)
         failure = []
         keep = []
 
@@ -353,7 +353,7 @@ class NativeTrainer:
         vts = (_lib.EnvVtable * n)(*[callbacks(e, r) for e, r in zip(envs, rows)])
         ops = _lib.GroupTrainerOps()
         handles = (C.c_void_p * n)(*[b.handle for b in buffers])
-        _lib.lib().bdr_group_trainer_ops_default(C.byref(ops), group.handle, handles)
+        getattr(_lib.lib(), tables + "_trainer_ops_default")(C.byref(ops), group.handle, handles)
 
         def cb(_ctx, member, env_steps, opt_steps, event, scalars, k):
             if on_event is not None:
@@ -363,7 +363,7 @@ class NativeTrainer:
             rc = _lib.lib().bdr_trainer_train_group(C.byref(c), (C.c_uint64 * n)(*rows), C.byref(ops), vts, obs, None, st)
         else:
             post = _lib.GroupTrainerPostC()
-            _lib.lib().bdr_group_trainer_post_default(C.byref(post), group.handle)
+            getattr(_lib.lib(), tables + "_trainer_post_default")(C.byref(post), group.handle)
             post.eval_interval, post.save_interval = int(eval_interval or 0), int(save_interval or 0)
             evaluators = list(evaluators) if evaluators is not None else []
             if evaluators:

@@ -509,6 +509,7 @@ BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr
 #define BDR_GROUP_FORM_IQL_LAYERS 3  /* a bdr_iql_group (below): IQL's launch sequence of one member, every launch serving all members */
 #define BDR_GROUP_FORM_AWAC_LAYERS 4 /* a bdr_awac_group (below): AWAC's launch sequence of one member, every launch serving all members */
 #define BDR_GROUP_FORM_CANDLE_SAC_LAYERS 5 /* a bdr_candle_sac_group (below): the candle SAC's launch sequence of one member, every launch serving all members */
+#define BDR_GROUP_FORM_CANDLE_DQN_LAYERS 6 /* a bdr_candle_dqn_group (below): the candle DQN's launch sequence of one member, every launch serving all members */
 typedef struct { int32_t form; uint32_t n_members; uint32_t launches_per_round; uint32_t reserved; uint64_t kernel_launches; } bdr_group_info;
 BDR_API int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out);
 /* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
@@ -1775,6 +1776,71 @@ BDR_API int32_t bdr_candle_dqn_cnn_update_on_batch(bdr_agent* a, uint64_t n, con
  *                                              gen::<u64>() % A; n_samples_best_act counts only with record_verbose_level >= 2
  *   eval (dqn/base.rs:221-227):                gen::<f32>() < 0.01 ? ONE gen_range(0..A), written to every row : argmax per row
  * bdr_agent_set_explorer rewinds the stream to its seed. */
+
+/* A GROUP of candle DQN agents in the Mlp form (bdr_candle_dqn_create, above) over uniform rings with 8-byte action rows (or views of
+ * one ring, bdr_replay_view_create): Dqn::opt_ (dqn/base.rs:172-189) of every member in the launch sequence of ONE member - gather,
+ * pack, the L forward layers (the passes (qnet, obs), (qnet_tgt, next_obs) and - double_dqn - (qnet, next_obs) are the 2 or 3
+ * instances of one launch per layer), update_critic's TD launch (dqn/base.rs:59-170), the L - 1 input gradients, the grouped weight
+ * gradient, reduce + Adam with the soft update on the rounds a member tracks (:180-184): 2 L + 4 launches for L = n_units + 1 layers,
+ * whatever the number of members; the member index is one more grid dimension - bit for bit what bdr_agent_opt of the members one
+ * after the other gives: parameters, target, moments, records, probes, actions, explorer stream, counters, ring bytes, saved files.
+ * The calls carry the semantics of their bdr_candle_sac_group_* namesakes (ownership, ordering with the members' own calls, the slot
+ * rule, the grouped push).
+ * One value for all members: obs_dim, n_actions, the Q-network's units and activation_out, batch_size, double_dqn, the device.  Free
+ * per member: seed, explorer and its parameters, train / eval mode, optimizer kind and scalars, learning rate, discount_factor, tau,
+ * soft_update_interval, critic_loss, record_verbose_level, act path.  Refused (BDR_ERR_INVALID, naming the first member concerned):
+ * an agent that is not a candle_dqn, the AtariCnn form, n_updates_per_opt != 1, another shape, more layers than one grouped
+ * weight-gradient launch (16) or one reduce + Adam launch (12 segments) holds, profiling or a gradient communicator switched on,
+ * another device, the same agent twice, an agent that is in a group already; more than 65535 members or a launch beyond the grid
+ * limits (naming the kernel).
+ * buffers[p] is member p's: a uniform f32 ring or view with 4 * obs_dim byte observation rows and 8-byte action rows on the group's
+ * device; a prioritized ring, a frame-stack store, a ring on another device or one listed twice is refused before anything moves,
+ * naming the member, and leaves every member's step, n_opts, soft_update_counter and stream position where they were.
+ * An out-of-range action in a member's batch (dqn/base.rs:80-86: the reference's gather raises) is clamped on the device and skips
+ * THAT member's optimizer step and soft update; the other members step.  _sync, _opt_with_scalars and a member's own synchronising
+ * calls put the member's step, n_opts and soft_update_counter back, as the lone agent's do, and report it as "member <p>: ..." with
+ * the lone agent's status.  _opt_with_scalars returns every member's opt_with_record record (dqn/base.rs:307-331: loss, at
+ * record_verbose_level >= 2 the four means and the parameter statistics, then ratio_best_act and the reset of both counters) at
+ * out + p * cap_per_member.  _info fills bdr_group_info with form = BDR_GROUP_FORM_CANDLE_DQN_LAYERS.
+ * Not built: the AtariCnn form, n_updates_per_opt > 1, bdr_*_group_copy_members and bdr_agent_hyper_* for this kind, a captured graph
+ * of the round, an explorer on the device, prioritized rings under the group. */
+typedef struct bdr_candle_dqn_group bdr_candle_dqn_group;
+BDR_API int32_t bdr_candle_dqn_group_create(bdr_agent* const* agents, uint32_t n, bdr_candle_dqn_group** out);   /* dqn/base.rs:172-189 (opt_ of every member) */
+BDR_API int32_t bdr_candle_dqn_group_destroy(bdr_candle_dqn_group* g);                                           /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_group_size(const bdr_candle_dqn_group* g, uint32_t* n);                           /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_group_member(const bdr_candle_dqn_group* g, uint32_t i, bdr_agent** out);         /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_group_info(const bdr_candle_dqn_group* g, bdr_group_info* out);                   /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_group_opt(bdr_candle_dqn_group* g, bdr_replay* const* buffers);                   /* dqn/base.rs:172-189, :59-170 */
+BDR_API int32_t bdr_candle_dqn_group_opt_with_scalars(bdr_candle_dqn_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);   /* dqn/base.rs:307-331 */
+BDR_API int32_t bdr_candle_dqn_group_sync(bdr_candle_dqn_group* g);                                              /* dqn/base.rs:172-189 */
+/* Policy::sample (dqn/base.rs:202-230) of every member (_sample) or of the members of a strictly ascending list (_sample_members)
+ * on n host rows each (float32 or float64 per member, an optional normaliser per member) in ONE launch: the Q rows and each row's
+ * first maximum come back, then every selected member's own explorer (dqn/explorer.rs:31-40, :79-133; eval: dqn/base.rs:221-227)
+ * runs on the host in member order, exactly as after the member's own bdr_agent_sample_raw: the Softmax explorer reads the Q rows,
+ * epsilon-greedy and eval mode the indices; n_samples_act, n_samples_best_act and the epsilon counter move as they do alone.  A member
+ * that is not selected draws nothing.  act_out[p]: member p's n explored i64 actions.  Group calls, rounds and a member's own
+ * bdr_agent_sample* calls continue ONE explorer stream.  One difference from a lone member's call: bdr_agent_sample_raw reads the
+ * member's device error words between the forward pass and the explorer, so a pending error (an action clamped in an earlier round)
+ * stops the lone call before it draws; a group acting call does not read them - P synchronising reads would undo the one launch -
+ * and draws; the error surfaces at the next _sync, _opt_with_scalars or call of the member's own, as it does for rounds.
+ * _last_q is a test and diagnostic helper, not part of the reference's surface: it copies the n * n_actions action values the last
+ * group call that selected `member` brought back for it (the rows its explorer read). */
+BDR_API int32_t bdr_candle_dqn_group_sample(bdr_candle_dqn_group* g, const bdr_obs_norm* const* norms, uint64_t n, const void* const* rows,
+                                            const int32_t* dtypes, int64_t* const* act_out);   /* dqn/base.rs:202-230, dqn/explorer.rs:31-40, :79-133 */
+BDR_API int32_t bdr_candle_dqn_group_sample_members(bdr_candle_dqn_group* g, const uint32_t* members, uint32_t n_sel, const bdr_obs_norm* const* norms,
+                                                    uint64_t n, const void* const* rows, const int32_t* dtypes, int64_t* const* act_out);   /* dqn/base.rs:202-230, dqn/explorer.rs:31-40, :79-133 */
+BDR_API int32_t bdr_candle_dqn_group_last_q(const bdr_candle_dqn_group* g, uint32_t member, float* q_out, uint64_t n_floats);   /* dqn/base.rs:203 */
+/* bdr_awac_group_push / _push_max_rows for a candle DQN group: the same call, with ONE i64 action per row (act[p]: n indices) */
+BDR_API int32_t bdr_candle_dqn_group_push(bdr_candle_dqn_group* g, bdr_replay* const* buffers, uint64_t n, const void* const* obs,
+                                          const void* const* next_obs, const int32_t* obs_dtypes, const int64_t* const* act, const float* const* reward,
+                                          const int8_t* const* is_terminated, const int8_t* const* is_truncated);   /* generic_replay_buffer/base.rs:279-313 */
+BDR_API int32_t bdr_candle_dqn_group_push_max_rows(bdr_candle_dqn_group* g, bdr_replay* const* buffers, const int32_t* obs_dtypes, uint64_t* n_max);   /* generic_replay_buffer/base.rs:279-313 */
+/* the i64-action tables of bdr_evaluate_group, bdr_trainer_train_group and bdr_trainer_train_group_post over a candle DQN group:
+ * sample = _sample with n = 1 float32 row per member and norms NULL, push = _push with n = 1; _trainer_post_default fills eval_ops
+ * and save_member (mkdir -p + bdr_agent_save_params of the member: qnet.pt, qnet_tgt.pt, dqn/base.rs:337-351) */
+BDR_API void bdr_candle_dqn_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_candle_dqn_group* group, bdr_replay* const* buffers);   /* trainer.rs:267-327, trainer/sampler.rs:99-144 */
+BDR_API void bdr_candle_dqn_group_eval_ops_default(bdr_group_eval_ops* ops, bdr_candle_dqn_group* group);                                     /* evaluator/default_evaluator.rs:64-88 */
+BDR_API void bdr_candle_dqn_group_trainer_post_default(bdr_group_trainer_post* post, bdr_candle_dqn_group* group);                            /* dqn/base.rs:337-351, trainer.rs:231-264 */
 
 /* ---- acting of the dense-agent agents (IQL, AWAC, the candle SAC, BC, the candle DQN) ----------------------------------------------------------------------
  * Their Policy::sample has two forms that produce the same bits: the layer-by-layer path (pack, one launch per layer, the sample

@@ -122,6 +122,7 @@ pub const BDR_GROUP_FORM_BC_LAYERS: i32 = 2;
 pub const BDR_GROUP_FORM_IQL_LAYERS: i32 = 3;
 pub const BDR_GROUP_FORM_AWAC_LAYERS: i32 = 4;
 pub const BDR_GROUP_FORM_CANDLE_SAC_LAYERS: i32 = 5;
+pub const BDR_GROUP_FORM_CANDLE_DQN_LAYERS: i32 = 6;
 pub const BDR_IQN_CONST10: i32 = 0;
 pub const BDR_IQN_CONST32: i32 = 1;
 pub const BDR_IQN_UNIFORM10: i32 = 2;
@@ -187,6 +188,8 @@ pub enum bdr_iql_group {}
 pub enum bdr_awac_group {}
 /// `bdr_candle_sac_group` (a launch grouping of candle SAC agents): only ever behind a pointer.
 pub enum bdr_candle_sac_group {}
+/// `bdr_candle_dqn_group` (a launch grouping of candle DQN agents in the Mlp form): only ever behind a pointer.
+pub enum bdr_candle_dqn_group {}
 #[repr(C)]
 pub struct bdr_replay {
     _private: [u8; 0],
@@ -1381,6 +1384,49 @@ extern "C" {
     pub fn bdr_iql_group_copy_members(g: *mut bdr_iql_group, src: *const u32, dst: *const u32, n: u32, flags: u32) -> i32;
     pub fn bdr_awac_group_copy_members(g: *mut bdr_awac_group, src: *const u32, dst: *const u32, n: u32, flags: u32) -> i32;
     pub fn bdr_candle_sac_group_copy_members(g: *mut bdr_candle_sac_group, src: *const u32, dst: *const u32, n: u32, flags: u32) -> i32;
+    pub fn bdr_candle_dqn_group_create(agents: *mut *const bdr_agent, n: u32, out: *mut *mut bdr_candle_dqn_group) -> i32;
+    pub fn bdr_candle_dqn_group_destroy(g: *mut bdr_candle_dqn_group) -> i32;
+    pub fn bdr_candle_dqn_group_size(g: *const bdr_candle_dqn_group, n: *mut u32) -> i32;
+    pub fn bdr_candle_dqn_group_member(g: *const bdr_candle_dqn_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_candle_dqn_group_info(g: *const bdr_candle_dqn_group, out: *mut bdr_group_info) -> i32;
+    pub fn bdr_candle_dqn_group_opt(g: *mut bdr_candle_dqn_group, buffers: *mut *const bdr_replay) -> i32;
+    pub fn bdr_candle_dqn_group_opt_with_scalars(g: *mut bdr_candle_dqn_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
+    pub fn bdr_candle_dqn_group_sync(g: *mut bdr_candle_dqn_group) -> i32;
+    pub fn bdr_candle_dqn_group_sample(
+        g: *mut bdr_candle_dqn_group,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const i64,
+    ) -> i32;
+    pub fn bdr_candle_dqn_group_sample_members(
+        g: *mut bdr_candle_dqn_group,
+        members: *const u32,
+        n_sel: u32,
+        norms: *mut *const bdr_obs_norm,
+        n: u64,
+        rows: *mut *const c_void,
+        dtypes: *const i32,
+        act_out: *mut *const i64,
+    ) -> i32;
+    pub fn bdr_candle_dqn_group_last_q(g: *const bdr_candle_dqn_group, member: u32, q_out: *mut f32, n_floats: u64) -> i32;
+    pub fn bdr_candle_dqn_group_push(
+        g: *mut bdr_candle_dqn_group,
+        buffers: *mut *const bdr_replay,
+        n: u64,
+        obs: *mut *const c_void,
+        next_obs: *mut *const c_void,
+        obs_dtypes: *const i32,
+        act: *mut *const i64,
+        reward: *mut *const f32,
+        is_terminated: *mut *const i8,
+        is_truncated: *mut *const i8,
+    ) -> i32;
+    pub fn bdr_candle_dqn_group_push_max_rows(g: *mut bdr_candle_dqn_group, buffers: *mut *const bdr_replay, obs_dtypes: *const i32, n_max: *mut u64) -> i32;
+    pub fn bdr_candle_dqn_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_candle_dqn_group, buffers: *mut *const bdr_replay);
+    pub fn bdr_candle_dqn_group_eval_ops_default(ops: *mut bdr_group_eval_ops, group: *mut bdr_candle_dqn_group);
+    pub fn bdr_candle_dqn_group_trainer_post_default(post: *mut bdr_group_trainer_post, group: *mut bdr_candle_dqn_group);
     pub fn bdr_agent_sample_raw(
         a: *mut bdr_agent,
         norm: *const bdr_obs_norm,

@@ -9,6 +9,7 @@ use crate::{
     awac::AmdAwac,
     bc::AmdBc,
     bytes::{DiscreteAct, ObsRows, RowBatch},
+    candle_dqn::AmdCandleDqn,
     candle_sac::AmdCandleSac,
     config::DqnConfig,
     dqn::AmdDqn,
@@ -1761,6 +1762,314 @@ where
 {
     fn drop(&mut self) {
         expect(unsafe { ffi::bdr_candle_sac_group_destroy(self.g) }, "bdr_candle_sac_group_destroy");
+        for m in self.members.iter_mut() {
+            m.a.h = std::ptr::null_mut(); // destroyed with the group; bdr_agent_destroy(NULL) in the member's own drop is a no-op
+        }
+    }
+}
+
+/// A group of candle DQN agents (`Mlp` Q-network) of one shape whose `Agent::opt` (`Dqn::opt_`, dqn/base.rs:172-189) runs as the launch
+/// sequence of ONE member, every launch serving all members (`bdr_candle_dqn_group_*`): 2 L + 4 launches per round for L layers (10
+/// at the dqn_cartpole shape), whatever the number of members.  The members may differ in seed, explorer, train / eval mode,
+/// optimizer, learning rate, discount, tau, soft-update interval, critic loss, record verbosity and act path; member `i` steps on
+/// `buffers[i]`, a uniform buffer with i64 actions of its own or a view of one ([`AmdReplayBuffer::view`]), and pushes into it between
+/// rounds as the online agent it is.  Acting runs the members' networks in one launch and then each selected member's own explorer
+/// on the host: one `SmallRng` stream per member across group calls, the member's own calls and rounds.
+///
+/// A launch grouping, not an agent kind: the members are ordinary [`AmdCandleDqn`] agents ([`AmdCandleDqnGroup::member_mut`]) on the
+/// group's stream.  Results are bit for bit those of stepping the same agents one after the other.  Owns its members: dropping the
+/// group destroys them (`bdr_candle_dqn_group_destroy`).  Not built: copies between members and the hyperparameter setters.
+pub struct AmdCandleDqnGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    g: *mut ffi::bdr_candle_dqn_group,
+    members: Vec<AmdCandleDqn<E, O, A>>,
+}
+
+// SAFETY: as `AgentHandle` - one HIP stream for the group and its members, all device work behind `&mut`.
+unsafe impl<E: Env, O: RowBatch, A: RowBatch> Send for AmdCandleDqnGroup<E, O, A> {}
+
+impl<E, O, A> AmdCandleDqnGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    /// Groups agents that already exist.  Fails, naming the first member concerned and the reason, unless all members are candle
+    /// DQN agents in the Mlp form of one shape (obs dim, number of actions, the Q-network, batch size, double_dqn) with
+    /// `n_updates_per_opt == 1` on one device; the agents are then dropped as ordinary agents.
+    pub fn adopt(members: Vec<AmdCandleDqn<E, O, A>>) -> Result<Self> {
+        if members.is_empty() {
+            return Err(anyhow!("a group needs at least one member"));
+        }
+        let mut hs: Vec<*const ffi::bdr_agent> = members.iter().map(|m| m.a.h as *const ffi::bdr_agent).collect();
+        let mut g = std::ptr::null_mut();
+        check(unsafe { ffi::bdr_candle_dqn_group_create(hs.as_mut_ptr(), hs.len() as u32, &mut g) })?;
+        Ok(Self { g, members })
+    }
+
+    pub fn handle(&self) -> *mut ffi::bdr_candle_dqn_group {
+        self.g
+    }
+
+    pub fn len(&self) -> usize {
+        self.members.len()
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.members.is_empty()
+    }
+
+    pub fn member(&self, i: usize) -> &AmdCandleDqn<E, O, A> {
+        &self.members[i]
+    }
+
+    /// A member as the ordinary agent it is (`Agent`, `Policy`, `SyncModel`, `save_params` ...).
+    pub fn member_mut(&mut self, i: usize) -> &mut AmdCandleDqn<E, O, A> {
+        &mut self.members[i]
+    }
+
+    /// `bdr_candle_dqn_group_info`: `form` is `ffi::BDR_GROUP_FORM_CANDLE_DQN_LAYERS`, `launches_per_round` the kernel launches of one
+    /// update round, `kernel_launches` those the group's own calls have enqueued since it was created.
+    pub fn info(&self) -> Result<ffi::bdr_group_info> {
+        let mut out = ffi::bdr_group_info::default();
+        check(unsafe { ffi::bdr_candle_dqn_group_info(self.g, &mut out) })?;
+        Ok(out)
+    }
+
+    fn buffer_handles(&self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<*const ffi::bdr_replay>> {
+        if buffers.len() != self.members.len() {
+            return Err(anyhow!("{} members need {} buffers, got {}", self.members.len(), self.members.len(), buffers.len()));
+        }
+        Ok(buffers.iter().map(|b| b.h as *const ffi::bdr_replay).collect())
+    }
+
+    /// `Agent::opt` of every member, member `i` on `buffers[i]`; only enqueues.  A refused call (a prioritized, empty, mismatched
+    /// or shared buffer) leaves every member and every buffer where it was.
+    pub fn opt(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        check(unsafe { ffi::bdr_candle_dqn_group_opt(self.g, hs.as_mut_ptr()) })
+    }
+
+    /// `Agent::opt_with_record` of every member (dqn/base.rs:307-331): the same round, one synchronisation, the members' `Record`s
+    /// in member order.  A member skipped for an out-of-range action is reported as "member <i>: ...".
+    pub fn opt_with_record(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<Record>> {
+        const CAP: usize = 128;
+        let mut hs = self.buffer_handles(buffers)?;
+        let n = self.members.len();
+        let mut vals = vec![0f32; n * CAP];
+        let mut counts = vec![0i32; n];
+        check(unsafe { ffi::bdr_candle_dqn_group_opt_with_scalars(self.g, hs.as_mut_ptr(), vals.as_mut_ptr(), CAP as i32, counts.as_mut_ptr()) })?;
+        let mut out = Vec::with_capacity(n);
+        for (i, m) in self.members.iter_mut().enumerate() {
+            let keys = m.a.record_keys().to_vec();
+            let mut record = Record::empty();
+            for (k, v) in keys.iter().zip(vals[i * CAP..].iter().take(counts[i] as usize)) {
+                record.insert(k.clone(), RecordValue::Scalar(*v));
+            }
+            out.push(record);
+        }
+        Ok(out)
+    }
+
+    /// `Policy::sample` of every member in ONE launch (`bdr_candle_dqn_group_sample`): member `i` acts on the `n` rows of `rows[i]`
+    /// (`n * obs_dim` f32 values, the same `n` for every member) and gets `n` explored i64 actions, what its own
+    /// `bdr_agent_sample_raw` gives at this point of its explorer stream.  `norms[i]`: the normaliser of member `i`'s rows, or null;
+    /// an empty slice means none for anybody.
+    pub fn sample(&mut self, n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<i64>>> {
+        self.sample_with(None, n, rows, norms)
+    }
+
+    /// The same for the members `members` (strictly ascending indices) only (`bdr_candle_dqn_group_sample_members`).  `rows` and the
+    /// result still have one entry per member; the entries of members that are not selected are not read and stay empty, and those
+    /// members draw nothing.
+    pub fn sample_members(&mut self, members: &[u32], n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<i64>>> {
+        self.sample_with(Some(members), n, rows, norms)
+    }
+
+    fn sample_with(&mut self, members: Option<&[u32]>, n: usize, rows: &[&[f32]], norms: &[*const ffi::bdr_obs_norm]) -> Result<Vec<Vec<i64>>> {
+        let p = self.members.len();
+        if rows.len() != p || !(norms.is_empty() || norms.len() == p) {
+            return Err(anyhow!("{} members need {} row slices and {} normalisers (or none), got {} and {}", p, p, p, rows.len(), norms.len()));
+        }
+        let selected = |i: usize| members.map_or(true, |m| m.contains(&(i as u32)));
+        let mut out: Vec<Vec<i64>> = (0..p).map(|i| if selected(i) { vec![0i64; n] } else { Vec::new() }).collect();
+        for i in (0..p).filter(|&i| selected(i)) {
+            if n == 0 || rows[i].is_empty() || rows[i].len() % n != 0 {
+                return Err(anyhow!("member {}: {} values are not {} rows of one width", i, rows[i].len(), n));
+            }
+        }
+        let mut row_ptrs: Vec<*const c_void> = rows.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut out_ptrs: Vec<*const i64> = out.iter_mut().map(|v| if v.is_empty() { std::ptr::null() } else { v.as_mut_ptr() as *const i64 }).collect();
+        let mut norm_ptrs: Vec<*const ffi::bdr_obs_norm> = norms.to_vec();
+        let norms_arg = if norm_ptrs.is_empty() { std::ptr::null_mut() } else { norm_ptrs.as_mut_ptr() };
+        let dtypes = vec![ffi::BDR_DTYPE_F32; p];
+        check(match members {
+            None => unsafe { ffi::bdr_candle_dqn_group_sample(self.g, norms_arg, n as u64, row_ptrs.as_mut_ptr(), dtypes.as_ptr(), out_ptrs.as_mut_ptr()) },
+            Some(m) => unsafe {
+                ffi::bdr_candle_dqn_group_sample_members(
+                    self.g,
+                    m.as_ptr(),
+                    m.len() as u32,
+                    norms_arg,
+                    n as u64,
+                    row_ptrs.as_mut_ptr(),
+                    dtypes.as_ptr(),
+                    out_ptrs.as_mut_ptr(),
+                )
+            },
+        })?;
+        Ok(out)
+    }
+
+    /// The action values `[n][n_actions]` the last group acting call that selected `member` brought back for it.
+    pub fn last_q(&self, member: usize, n: usize) -> Result<Vec<f32>> {
+        let mut q = vec![0f32; n * self.members[member].n_actions()];
+        check(unsafe { ffi::bdr_candle_dqn_group_last_q(self.g, member as u32, q.as_mut_ptr(), q.len() as u64) })?;
+        Ok(q)
+    }
+
+    /// `ExperienceBufferBase::push` of `n` transitions per member, member `i`'s into `buffers[i]`, in ONE launch
+    /// (`bdr_candle_dqn_group_push`); only enqueues.  `obs[i]` / `next_obs[i]`: `n * obs_dim` f32 values, `act[i]`: `n` i64 indices,
+    /// `reward[i]`, `is_terminated[i]`, `is_truncated[i]`: `n` values.  Each ring ends up exactly as its own `push` of those rows
+    /// leaves it (a push may cross the wrap).
+    #[allow(clippy::too_many_arguments)]
+    pub fn push(
+        &mut self,
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        n: usize,
+        obs: &[&[f32]],
+        act: &[&[i64]],
+        next_obs: &[&[f32]],
+        reward: &[&[f32]],
+        is_terminated: &[&[i8]],
+        is_truncated: &[&[i8]],
+    ) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        let p = self.members.len();
+        if obs.len() != p || act.len() != p || next_obs.len() != p || reward.len() != p || is_terminated.len() != p || is_truncated.len() != p {
+            return Err(anyhow!("{} members need {} slices of every field", p, p));
+        }
+        for i in 0..p {
+            if n == 0 || obs[i].len() % n != 0 || next_obs[i].len() != obs[i].len() || act[i].len() != n {
+                return Err(anyhow!("member {}: {} rows need {} actions and as many observation as next-observation values", i, n, n));
+            }
+            if reward[i].len() != n || is_terminated[i].len() != n || is_truncated[i].len() != n {
+                return Err(anyhow!("member {}: {} rows need {} rewards and flags", i, n, n));
+            }
+        }
+        let mut o: Vec<*const c_void> = obs.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut x: Vec<*const c_void> = next_obs.iter().map(|r| r.as_ptr() as *const c_void).collect();
+        let mut a: Vec<*const i64> = act.iter().map(|r| r.as_ptr()).collect();
+        let mut r: Vec<*const f32> = reward.iter().map(|r| r.as_ptr()).collect();
+        let mut t: Vec<*const i8> = is_terminated.iter().map(|r| r.as_ptr()).collect();
+        let mut u: Vec<*const i8> = is_truncated.iter().map(|r| r.as_ptr()).collect();
+        check(unsafe {
+            ffi::bdr_candle_dqn_group_push(
+                self.g,
+                hs.as_mut_ptr(),
+                n as u64,
+                o.as_mut_ptr(),
+                x.as_mut_ptr(),
+                std::ptr::null(),
+                a.as_mut_ptr(),
+                r.as_mut_ptr(),
+                t.as_mut_ptr(),
+                u.as_mut_ptr(),
+            )
+        })
+    }
+
+    /// The largest `n` one [`Self::push`] of f32 rows takes for these buffers (`bdr_candle_dqn_group_push_max_rows`).
+    pub fn push_max_rows(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<usize> {
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut n = 0u64;
+        check(unsafe { ffi::bdr_candle_dqn_group_push_max_rows(self.g, hs.as_mut_ptr(), std::ptr::null(), &mut n) })?;
+        Ok(n as usize)
+    }
+
+    /// `DefaultEvaluator` of every member in lockstep (`bdr_evaluate_group` behind `bdr_candle_dqn_group_eval_ops_default`): member
+    /// `i` on `evaluators[i]` - the C view of an evaluator with `act_row_bytes = 8` and f32 rows - with ONE acting launch per round
+    /// over the members that still have an episode open.
+    pub fn evaluate(&mut self, evaluators: &[ffi::bdr_evaluator]) -> Result<Vec<EvalResult>> {
+        let n = self.members.len();
+        if evaluators.len() != n {
+            return Err(anyhow!("{} members need {} evaluators, got {}", n, n, evaluators.len()));
+        }
+        // SAFETY: bdr_candle_dqn_group_eval_ops_default fills every field.
+        let mut ops: ffi::bdr_group_eval_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_dqn_group_eval_ops_default(&mut ops, self.g) };
+        let mut out = vec![ffi::bdr_eval_result::default(); n];
+        check(unsafe { ffi::bdr_evaluate_group(evaluators.as_ptr(), &ops, out.as_mut_ptr()) })?;
+        Ok(out.iter().map(eval_result).collect())
+    }
+
+    /// `Trainer::train` (`trainer.rs:267-327`) with `Trainer::post_process` for all members in lockstep in the compiled loop
+    /// `bdr_trainer_train_group_post`: member `i` on `envs[i]` - the C view of an environment that writes f32 rows of
+    /// `obs_row_bytes[i]` bytes and reads one i64 action - and `buffers[i]`; one group sample, one group push and at most one group
+    /// opt per iteration.  `config.act_row_bytes` must be 8.  Every `eval_interval` opt steps a lockstep evaluation on `evaluators`,
+    /// member `i`'s best model in `model_dirs[i]/best` (qnet.pt, qnet_tgt.pt), every `save_interval` opt steps every member in
+    /// `model_dirs[i]/<opt_steps>`; with both intervals 0, `evaluators` and `model_dirs` may be empty.
+    #[allow(clippy::too_many_arguments)]
+    pub fn train(
+        &mut self,
+        envs: &[ffi::bdr_env_vtable],
+        buffers: &mut [AmdReplayBuffer<O, A>],
+        obs_row_bytes: &[u64],
+        config: &ffi::bdr_trainer_config,
+        evaluators: &[ffi::bdr_evaluator],
+        eval_interval: usize,
+        save_interval: usize,
+        model_dirs: &[&Path],
+    ) -> Result<Vec<ffi::bdr_trainer_stats>> {
+        let n = self.members.len();
+        if envs.len() != n || obs_row_bytes.len() != n {
+            return Err(anyhow!("{} members need {} environments and row sizes", n, n));
+        }
+        if (eval_interval > 0 && evaluators.len() != n) || ((eval_interval > 0 || save_interval > 0) && model_dirs.len() != n) {
+            return Err(anyhow!("{} members need {} evaluators and model directories", n, n));
+        }
+        let mut hs = self.buffer_handles(buffers)?;
+        let mut ops: ffi::bdr_group_trainer_ops = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_dqn_group_trainer_ops_default(&mut ops, self.g, hs.as_mut_ptr()) };
+        let mut dirs = Vec::with_capacity(n);
+        for d in model_dirs {
+            dirs.push(CString::new(d.to_string_lossy().as_bytes())?);
+        }
+        let mut dir_ptrs: Vec<*const c_char> = dirs.iter().map(|d| d.as_ptr()).collect();
+        // SAFETY: bdr_candle_dqn_group_trainer_post_default fills every field.
+        let mut post: ffi::bdr_group_trainer_post = unsafe { std::mem::zeroed() };
+        unsafe { ffi::bdr_candle_dqn_group_trainer_post_default(&mut post, self.g) };
+        post.eval_interval = eval_interval as u64;
+        post.save_interval = save_interval as u64;
+        post.evaluators = if evaluators.is_empty() { std::ptr::null() } else { evaluators.as_ptr() };
+        post.model_dirs = if dir_ptrs.is_empty() { std::ptr::null_mut() } else { dir_ptrs.as_mut_ptr() };
+        let mut stats = vec![ffi::bdr_trainer_stats::default(); n];
+        check(unsafe {
+            ffi::bdr_trainer_train_group_post(config, obs_row_bytes.as_ptr(), &ops, envs.as_ptr(), &post, None, std::ptr::null_mut(), stats.as_mut_ptr())
+        })?;
+        self.sync()?;
+        Ok(stats)
+    }
+
+    /// Waits for everything the group and its members have enqueued (`bdr_candle_dqn_group_sync`); every member settles, and a
+    /// member whose update was skipped for an out-of-range action is reported as "member <i>: ...".
+    pub fn sync(&mut self) -> Result<()> {
+        check(unsafe { ffi::bdr_candle_dqn_group_sync(self.g) })
+    }
+}
+
+impl<E, O, A> Drop for AmdCandleDqnGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    fn drop(&mut self) {
+        expect(unsafe { ffi::bdr_candle_dqn_group_destroy(self.g) }, "bdr_candle_dqn_group_destroy");
         for m in self.members.iter_mut() {
             m.a.h = std::ptr::null_mut(); // destroyed with the group; bdr_agent_destroy(NULL) in the member's own drop is a no-op
         }

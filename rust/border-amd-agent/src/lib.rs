@@ -64,7 +64,7 @@ pub use candle_dqn::AmdCandleDqn;
 pub use candle_sac::AmdCandleSac;
 pub use dataset::{AmdObsNorm, ObsElem};
 pub use dqn::AmdDqn;
-pub use group::{AmdAwacGroup, AmdBcGroup, AmdCandleSacGroup, AmdDqnGroup, AmdIqlGroup, GroupEvaluator};
+pub use group::{AmdAwacGroup, AmdBcGroup, AmdCandleDqnGroup, AmdCandleSacGroup, AmdDqnGroup, AmdIqlGroup, GroupEvaluator};
 pub use evaluator::{ActPath, AmdEvaluator, EvalResult, Hyper, SampleRaw, TrainerPost};
 pub use iql::AmdIql;
 pub use iqn::AmdIqn;
