@@ -293,7 +293,7 @@ class BcGroupTrainerPostC(C.Structure):
                 ("model_dirs", C.POINTER(C.c_char_p)), ("eval_ops", BcGroupEvalOps), ("save_member", G_SAVE_MEMBER_FN)]
 
 
-BDR_ACT_PATH_DEFAULT, BDR_ACT_PATH_LAYERS, BDR_ACT_PATH_FUSED = 0, 1, 2
+BDR_ACT_PATH_DEFAULT, BDR_ACT_PATH_LAYERS, BDR_ACT_PATH_FUSED, BDR_ACT_PATH_IMAGE = 0, 1, 2, 3
 BDR_TRAINER_EVENT_EVAL = 4
 
 

@@ -12,7 +12,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libborder_amd.so")
-SOURCES = ["replay.hip", "dataset.hip", "per.hip", "agent_api.hip", "dqn.hip", "mlp_agents.hip", "sac.hip", "iql.hip", "awac.hip", "candle_sac.hip", "candle_dqn.hip", "bc.hip", "iqn.hip", "comm.hip", "atari_prep.hip", "trainer.hip", "async_trainer.hip"]  # missing files are skipped
+SOURCES = ["replay.hip", "dataset.hip", "per.hip", "agent_api.hip", "dqn.hip", "mlp_agents.hip", "sac.hip", "iql.hip", "awac.hip", "candle_sac.hip", "candle_dqn.hip", "cnn_act_img.hip", "bc.hip", "iqn.hip", "comm.hip", "atari_prep.hip", "trainer.hip", "async_trainer.hip"]  # missing files are skipped
+# per-source switches: the packed-f32 instructions are off in the acting kernels of cnn_act_img.hip (scalar f32 forms only)
+EXTRA_FLAGS = {"cnn_act_img.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))) + ["../../include/border_amd.h"]
 
 
@@ -38,7 +40,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
                 os.path.getmtime(path), *[os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS
                                           if os.path.exists(os.path.join(CSRC, h))]):
             cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
-                   "-Wall", "-Wno-unused-function", "-c", path, "-o", obj]
+                   "-Wall", "-Wno-unused-function"] + EXTRA_FLAGS.get(src, []) + ["-c", path, "-o", obj]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             jobs.append(cmd)

@@ -349,6 +349,9 @@ struct bdr_agent : bdr::ParamTable {
     virtual int32_t set_act_path(int32_t path)
     {
         if (path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS) return BDR_OK;
+        if (path == BDR_ACT_PATH_IMAGE)
+            return ::bdr::fail(BDR_ERR_INVALID, "BDR_ACT_PATH_IMAGE is the acting path of the DQN (candle) agent with the AtariCnn Q-network: this %s agent acts "
+                                                "through BDR_ACT_PATH_LAYERS", kind());
         return ::bdr::fail(BDR_ERR_INVALID, path == BDR_ACT_PATH_FUSED ? "this agent kind has no fused acting kernel (IQL, AWAC, BC and the candle SAC and DQN have one)" : "unknown act path");
     }
     // bdr_agent_hyper_get / _set: hyperparameter `id` (BDR_HYPER_*) into *v, or *v into it; the DenseAgent agents implement them

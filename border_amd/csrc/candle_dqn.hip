@@ -21,6 +21,7 @@
 
 #include "candle_actor.hpp"
 #include "conv_trunk.hpp"
+#include "cnn_act_img.hpp"
 #include "candle_dqn_group_plan.hpp"
 
 using namespace bdr;
@@ -733,10 +734,52 @@ struct CandleDqnCnn : CandleDqn {
                 {"c3.weight", {64, 64, 3, 3}}, {"c3.bias", {64}}, {"l1.weight", {512, 3136}}, {"l1.bias", {512}},
                 {"l2.weight", {(uint64_t)A, 512}}, {"l2.bias", {(uint64_t)A}}};
     }
-    // Policy::sample's forward: u8 rows (host rows, or device rows inside a DeviceRowsScope) through the batch forward of the update
+    // BDR_ACT_PATH_IMAGE (cnn_act_img.hpp): n <= CAI_MAX_ROWS rows in two launches, k_cnn_act_trunk (one workgroup per frame stack,
+    // read where it lies: the pinned host rows, or device rows at their stride) and k_cnn_act_head, into samp / samp_idx
+    float *img_feat = nullptr, *img_part = nullptr; unsigned* img_counters = nullptr;   // allocated on the path's first call
+    int32_t run_image(uint64_t n, const float* obs)
+    {
+        BDR_HIP(hipSetDevice(device));
+        BDR_TRY(ensure_batch((int)n));
+        if (!img_feat) {
+            BDR_TRY(alloc(&img_feat, (size_t)CAI_MAX_ROWS * 3136, AGENT));
+            BDR_TRY(alloc(&img_part, CAI_PART_FLOATS + CAI_COUNTERS, AGENT));   // (zeroed: the counters start at zero and every launch leaves them so)
+            img_counters = reinterpret_cast<unsigned*>(img_part + CAI_PART_FLOATS);
+        }
+        const uint8_t* d = static_cast<const uint8_t*>(static_cast<const void*>(obs));
+        size_t stride = row_bytes();
+        int32_t st = BDR_OK;
+        if (obs_rows_on_device) {
+            stride = obs_row_stride;
+            if (stride < row_bytes())
+                st = fail(BDR_ERR_INVALID, "row_stride (%llu bytes) is smaller than the agent's observation row (%llu bytes)", (unsigned long long)stride,
+                          (unsigned long long)row_bytes());
+        } else st = acting_rows(obs, row_bytes(), n, &d);
+        const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
+        const float* hp = head(p);
+        if (st == BDR_OK) {
+            CnnActTrunkArgs t{d, stride, conv.ns, ((uintptr_t)d | stride) % 16 == 0 ? 1 : 0, p + conv.w1, p + conv.b1, p + conv.w2, p + conv.b2, p + conv.w3, p + conv.b3, img_feat};
+            Bracket br(this, "act_trunk");
+            const hipError_t e = launch_cnn_act_trunk(stream, (int)n, t);
+            if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_cnn_act_trunk: %s", hipGetErrorString(e));
+        }
+        if (st == BDR_OK) {
+            CnnActHeadArgs h{img_feat, hp + l1.w, hp + l1.b, hp + l2.w, hp + l2.b, l2.Np, img_part, img_counters, (int)n, A, samp, samp_idx};
+            Bracket br(this, "act_head");
+            const hipError_t e = launch_cnn_act_head(stream, h);
+            if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_cnn_act_head: %s", hipGetErrorString(e));
+        }
+        if (st == BDR_OK) st = results_to_host(n);
+        if (st == BDR_OK) prof_collect(this);
+        slot_cursor = 0;
+        return st;
+    }
+    // Policy::sample's forward: u8 rows (host rows, or device rows inside a DeviceRowsScope) through the batch forward of the update,
+    // or - BDR_ACT_PATH_IMAGE, up to CAI_MAX_ROWS rows - through the two acting launches above
     int32_t run_net(uint64_t n, const float* obs) override
     {
         BDR_REQUIRE(n >= 1 && n <= 65536, "batch size out of range");
+        if (act_path == BDR_ACT_PATH_IMAGE && n <= (uint64_t)CAI_MAX_ROWS) return run_image(n, obs);
         BDR_HIP(hipSetDevice(device));
         BDR_TRY(ensure_batch((int)n));
         const uint8_t* d = nullptr;
@@ -759,9 +802,10 @@ struct CandleDqnCnn : CandleDqn {
     }
     int32_t set_act_path(int32_t path) override
     {
-        BDR_REQUIRE(path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS || path == BDR_ACT_PATH_FUSED, "unknown act path %d", path);
+        BDR_REQUIRE(path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS || path == BDR_ACT_PATH_FUSED || path == BDR_ACT_PATH_IMAGE, "unknown act path %d", path);
         BDR_REQUIRE(path != BDR_ACT_PATH_FUSED, "the fused acting kernel runs Mlp networks on f32 rows: the AtariCnn Q-network of this DQN (candle) agent acts "
                                                 "through its layer launches (BDR_ACT_PATH_LAYERS)");
+        act_path = path;
         return BDR_OK;
     }
     int32_t sample_raw(const bdr_obs_norm*, uint64_t, const void*, int32_t, bool, uint64_t, float*, int64_t*) override

@@ -1,0 +1,400 @@
+// Policy::sample of the candle DQN's AtariCnn Q-network on a handful of frame stacks (dqn/base.rs:202-230 is called once per
+// environment step): BDR_ACT_PATH_IMAGE, two launches for n <= CAI_MAX_ROWS rows instead of the update's six batch-tiled ones.
+//
+//   k_cnn_act_trunk   one workgroup of four waves per observation row (grid = n): conv1, conv2 and conv3 of ONE image with every
+//                     activation in LDS; the output a3 goes to feat [n][3136] in (h, w, c) order, l1's internal input layout.
+//   k_cnn_act_head    l1 (3136 -> 512, ReLU) cut as act_small.hpp cuts it - 16 column tiles x CAI_L1_KS k-slices, one partial
+//                     32 x 32 tile per workgroup (dense_small_tile), a counter per column tile, the last arriver adds the partials in
+//                     slice order - and, in the workgroup that completes the last column tile, l2 and dqn_q_argmax into the
+//                     buffers k_cdqn_act writes (samp, samp_idx).
+// No workgroup waits for another one: a counter is taken once, behind the workgroup's own stores (dense.hpp last_workgroup: agent-scope
+// stores, s_waitcnt, barrier, agent-scope fetch-add), and whoever takes the last ticket goes on; the grid need not be co-resident.
+//
+// Arithmetic.  conv1 under conv1_bf16_img.hpp's operand rule: u8 pixels are exact in bf16, an f32 weight is split exactly into three
+// bf16 terms, the products are exact, the MFMA accumulates in f32 (planes lo, mid, hi per k-step), 1/255 once in the epilogue, then
+// bias and ReLU.  conv2, conv3, l1, l2: f32 x f32 on v_mfma_f32_32x32x2_f32, exact products (BDR_ARITH_F32_EXACT).  The ORDER of the
+// additions differs from the batch forward (k-quarters and slices here, k-tiles there): Q agrees with the layer path to rounding, not
+// bit for bit.
+//
+// The trunk's work split (lane = (i, h), i = lane & 31, h = lane >> 5; an MFMA tile is 32 x 32, lane (i, h) holds column i, rows
+// (r & 3) + 8 (r >> 2) + 4 h of its 16 accumulators r):
+//   conv1  400 positions x 32 channels, K = 64 n_stack.  Rows of the MFMA = channels, columns = 32 positions (a "unit"): 13 units,
+//          wave w takes units w, w + 4, w + 8 (and 12: wave 0) and keeps their accumulators while the k-steps go by ONCE, so a
+//          weight fragment is fetched and split once per wave.  Weights of a whole channel (4 k-steps) are in flight one channel ahead.
+//   conv2  81 x 64, K = 512 = (kh, kw, c): 3 x 2 tiles do not divide over four waves, so the REDUCTION is split: wave w owns kernel
+//          row kh = w (k in [128 w, 128 w + 128)) of all six tiles; the quarters meet in LDS - wave 0 writes a2 itself, waves 1 ... 3 the
+//          reduction area - and every element is summed as ((q0 + q1) + q2) + q3, then bias and ReLU.
+//   conv3  49 x 64, K = 576: 2 x 2 tiles, one per wave; one tap (64 k) of weights in flight ahead of the tap being multiplied.
+//   A operands are gathered from LDS patches (16-byte reads), B operands (weights) go from L2 straight into registers: 312 KB of conv
+//   weights is not staged.  Every weight address is a function of the thread index and the loop counters alone; the first weights of
+//   conv1, conv2 AND conv3 and the biases of conv1 and conv3 are requested before the frames are staged.
+//   Rows >= 400 / 81 / 49 of a ragged tile read the layer's last valid row (index clamped) and are not stored.
+//
+// LDS of the trunk, floats unless said otherwise (static, 141 840 bytes of the CU's 160 KB):
+//   s_u   [15 552]        first the frames as u8 [n_stack][84][84] (7 056 n_stack <= 56 448 bytes), overlaid once conv1 is done
+//                         (barrier) by conv2's reduction area red [3][81][64] (62 208 bytes)
+//   s_a1  [400][36]       conv1's output; rows padded by 4 floats (57 600 bytes)
+//   s_a2  [81][68]        conv2's output, padded alike (22 032 bytes)
+// Index bounds.
+//   frames: staged as dwords (or 16-byte vectors) t < 1 764 n_stack; conv1 reads two dwords at byte c 7056 + (4 oh + kh) 84 + 4 ow,
+//           c < n_stack, oh, ow <= 19 (position index clamped to 399), kh <= 7: row <= 83, last byte column 4 * 19 + 7 = 83.
+//   W1:     row 64 c + 16 sl + 8 h + j < 64 n_stack, column i < 32.   s_a1 writes: position m < 400, channels 8 q + 4 h + e < 32.
+//   conv2:  position m <= 80 (clamped), a1 row (2 oh + w) 20 + 2 ow + kw <= 19 * 20 + 19 = 399, channels (s & 3) 8 + 4 h + e < 32;
+//           W2 row 128 w + 8 s + 4 h + q < 512, column 32 nt + i < 64; red / s_a2 writes at m < 81 only, column < 64.
+//   conv3:  position m <= 48 (clamped), a2 row (oh + kh) 9 + ow + kw <= 8 * 9 + 8 = 80, channels 8 s + 4 h + e < 64;
+//           W3 row 64 tap + 8 s + 4 h + q < 576; feat writes at m < 49: row blockIdx.x < n, element m 64 + column < 3 136.
+// The head: feat rows min(i, n - 1) < n, k < 3 136; W1 (l1) rows < 3 136, columns < 512; part [KS][32][512] at rows m < n, then
+// h1 [32][512]; counters [17]; l2: hs rows < 32 (rows >= n hold a copy of row n - 1), W2 rows < 512, columns 32 t + i < ld2 for the
+// tiles t with 32 t < A; q at m < n, column < A; idx at m < n.
+// The kernels are compiled in a translation unit of their own (cnn_act_img.hip defines BDR_CNN_ACT_IMG_KERNELS; build.py compiles it
+// with the packed-f32 instructions switched off); candle_dqn.hip sees the argument structs and the two launchers.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <hip/hip_runtime.h>
+
+namespace bdr {
+
+constexpr int CAI_MAX_ROWS = 32;          // rows per call served by this path: one 32-row tile of l1
+constexpr int CAI_A1_LD = 36, CAI_A2_LD = 68;
+constexpr int CAI_RED = 81 * 64;          // floats of one k-quarter of conv2
+constexpr int CAI_L1_KS = 7;              // k-slices of l1: 448 k each (act_small.hpp: 49 slices of one round trip each were slower)
+constexpr size_t CAI_PART_FLOATS = (size_t)(CAI_L1_KS + 1) * 32 * 512;   // the partial tiles, then h1 [32][512]
+constexpr int CAI_COUNTERS = 17;          // one per column tile of l1, one for the layer
+
+struct CnnActTrunkArgs {
+    const uint8_t* rows; size_t row_stride;   // n frame stacks [n_stack][84][84] u8, row_stride bytes apart (a multiple of 4)
+    int ns, vec16;                            // vec16: base and stride are multiples of 16 bytes
+    const float *w1, *b1, *w2, *b2, *w3, *b3; // conv_layout.hpp's internal layouts
+    float* feat;                              // [n][3136]
+};
+
+struct CnnActHeadArgs {
+    const float* feat;                 // [n][3136]
+    const float *w1, *b1;              // l1: [3136][512], [512]
+    const float *w2, *b2; int ld2;     // l2: [512][ld2], [A]
+    float* part;                       // CAI_PART_FLOATS: [CAI_L1_KS][32][512] partial tiles, then h1 [32][512]
+    unsigned* counters;                // [CAI_COUNTERS], zero between launches
+    int n, A;
+    float* q; long long* idx;          // [n][A], [n]
+};
+
+hipError_t launch_cnn_act_trunk(hipStream_t st, int n, const CnnActTrunkArgs& a);   // grid n
+hipError_t launch_cnn_act_head(hipStream_t st, const CnnActHeadArgs& a);            // grid (16, CAI_L1_KS)
+
+}  // namespace bdr
+
+#ifdef BDR_CNN_ACT_IMG_KERNELS
+#include "conv1_bf16.hpp"
+#include "dense.hpp"
+#include "dense_act.hpp"
+
+namespace bdr {
+
+// n elements src -> dst, eight loads of a thread in flight at a time (index clamped for the load, predicated for the store)
+template <class V>
+__device__ __forceinline__ void cai_stage(const V* __restrict__ src, V* dst, int n, int tid)
+{
+    for (int t0 = 0; t0 < n; t0 += 256 * 8) {
+        V v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const int t = t0 + 256 * k + tid; v[k] = src[t < n ? t : n - 1]; }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const int t = t0 + 256 * k + tid; if (t < n) dst[t] = v[k]; }
+    }
+}
+
+static __global__ __launch_bounds__(256) void k_cnn_act_trunk(CnnActTrunkArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float s_u[3 * CAI_RED];
+    __shared__ __attribute__((aligned(16))) float s_a1[400 * CAI_A1_LD];
+    __shared__ __attribute__((aligned(16))) float s_a2[81 * CAI_A2_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, h = lane >> 5;
+
+    // ---- every first operand, requested before anything is waited for
+    // conv1: the fragment rows of channel c for this lane (output channel i, k half h): W1[64 c + 16 sl + 8 h + j][i]
+    auto load_w1 = [&](int c, float (&w)[4][8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) w[sl][j] = a.w1[(size_t)(64 * c + 16 * sl + 8 * h + j) * 32 + i];
+    };
+    // conv2: chunk ch = k-steps 2 ch, 2 ch + 1 of this wave's quarter, both column tiles: W2[128 w + 8 s + 4 h + q][32 nt + i]
+    auto load_w2 = [&](int ch, float (&w)[2][2][4]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[u][nt][q] = a.w2[(size_t)(128 * wave + 8 * (2 * ch + u) + 4 * h + q) * 64 + 32 * nt + i];
+    };
+    // conv3: one tap of this wave's column tile: W3[64 tap + 8 s + 4 h + q][32 (w & 1) + i]
+    auto load_w3 = [&](int tap, float (&w)[8][4]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < 8; ++s)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) w[s][q] = a.w3[(size_t)(64 * tap + 8 * s + 4 * h + q) * 64 + 32 * (wave & 1) + i];
+    };
+    float w1n[4][8], w2n[2][2][4], w3n[8][4];
+    load_w1(0, w1n);
+    f32x4 bq1[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bq1[q] = *reinterpret_cast<const f32x4*>(a.b1 + 8 * q + 4 * h);
+    load_w2(0, w2n);
+    load_w3(0, w3n);
+    const float b3v = a.b3[32 * (wave & 1) + i];
+
+    // ---- the frame stack -> LDS, as it is (u8)
+    {
+        const uint8_t* src = a.rows + (size_t)blockIdx.x * a.row_stride;
+        if (a.vec16) cai_stage(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(s_u), a.ns * 441, tid);
+        else cai_stage(reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(s_u), a.ns * 1764, tid);
+    }
+    __syncthreads();
+
+    // ---- conv1
+    {
+        const int nu = wave == 0 ? 4 : 3;
+        const uint8_t* frb = reinterpret_cast<const uint8_t*>(s_u);
+        int poff[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int m = min((wave + 4 * t) * 32 + i, 399), oh = m / 20, ow = m - oh * 20;
+            poff[t] = (oh * 4 + h) * 84 + ow * 4;
+        }
+        f32x16 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        for (int c = 0; c < a.ns; ++c) {
+            float wc[4][8];
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) wc[sl][j] = w1n[sl][j];
+            if (c + 1 < a.ns) load_w1(c + 1, w1n);
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl) {
+                uint32_t hi[8], mid[8], lo[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    hi[j] = __float_as_uint(wc[sl][j]) & 0xffff0000u;
+                    const float r1 = wc[sl][j] - __uint_as_float(hi[j]);    // exact
+                    mid[j] = __float_as_uint(r1) & 0xffff0000u;
+                    const float r2 = r1 - __uint_as_float(mid[j]);          // exact, <= 8 significant bits
+                    lo[j] = __float_as_uint(r2) & 0xffff0000u;
+                }
+                bf16x8 wp[3];
+                wp[0] = __builtin_bit_cast(bf16x8, uint4{(hi[0] >> 16) | hi[1], (hi[2] >> 16) | hi[3], (hi[4] >> 16) | hi[5], (hi[6] >> 16) | hi[7]});
+                wp[1] = __builtin_bit_cast(bf16x8, uint4{(mid[0] >> 16) | mid[1], (mid[2] >> 16) | mid[3], (mid[4] >> 16) | mid[5], (mid[6] >> 16) | mid[7]});
+                wp[2] = __builtin_bit_cast(bf16x8, uint4{(lo[0] >> 16) | lo[1], (lo[2] >> 16) | lo[3], (lo[4] >> 16) | lo[5], (lo[6] >> 16) | lo[7]});
+                // k-step sl of channel c: patch rows 2 sl + h, eight pixels of the row per lane
+                const int so = c * 7056 + (2 * sl) * 84;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    if (t < nu) {   // wave-uniform
+                        const uint32_t* px = reinterpret_cast<const uint32_t*>(frb + poff[t] + so);
+                        const bf16x8 fa = u8x8_to_bf16(px[0], px[1]);
+#pragma unroll
+                        for (int pl = 2; pl >= 0; --pl) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[pl], fa, acc[t], 0, 0, 0);   // small terms first
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int m = (wave + 4 * t) * 32 + i;
+            if (t < nu && m < 400) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const float x = acc[t][4 * q + e] * (1.0f / 255.0f) + bq1[q][e]; v[e] = x > 0.f ? x : 0.f; }
+                    *reinterpret_cast<f32x4*>(s_a1 + m * CAI_A1_LD + 8 * q + 4 * h) = v;
+                }
+            }
+        }
+    }
+    __syncthreads();   // a1 is whole; nobody reads the frames any more
+
+    // ---- conv2: this wave's k-quarter (kernel row kh = wave) of all six tiles
+    {
+        int ab[3];
+#pragma unroll
+        for (int mt = 0; mt < 3; ++mt) {
+            const int m = min(32 * mt + i, 80), oh = m / 9, ow = m - oh * 9;
+            ab[mt] = ((2 * oh + wave) * 20 + 2 * ow) * CAI_A1_LD + 4 * h;
+        }
+        f32x16 acc[3][2];
+#pragma unroll
+        for (int mt = 0; mt < 3; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+        for (int ch = 0; ch < 8; ++ch) {
+            float wc[2][2][4];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) wc[u][nt][q] = w2n[u][nt][q];
+            if (ch + 1 < 8) load_w2(ch + 1, w2n);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int s = 2 * ch + u, ko = (s >> 2) * CAI_A1_LD + (s & 3) * 8;   // k = 8 s + 4 h: kw = s >> 2, channels (s & 3) 8 + 4 h ...
+                f32x4 av[3];
+#pragma unroll
+                for (int mt = 0; mt < 3; ++mt) av[mt] = *reinterpret_cast<const f32x4*>(s_a1 + ab[mt] + ko);
+#pragma unroll
+                for (int mt = 0; mt < 3; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt][q], wc[u][nt][q], acc[mt][nt], 0, 0, 0);
+            }
+        }
+        // the quarters meet: wave 0 in a2 itself, waves 1 ... 3 in red (over the frames)
+        float* dst = wave == 0 ? s_a2 : s_u + (wave - 1) * CAI_RED;
+        const int ld = wave == 0 ? CAI_A2_LD : 64;
+#pragma unroll
+        for (int mt = 0; mt < 3; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    if (m < 81) dst[m * ld + 32 * nt + i] = acc[mt][nt][r];
+                }
+    }
+    __syncthreads();
+    for (int e = tid; e < CAI_RED; e += 256) {   // one thread per element: ((q0 + q1) + q2) + q3, bias, ReLU
+        const int m = e >> 6, n = e & 63;
+        float v = ((s_a2[m * CAI_A2_LD + n] + s_u[e]) + s_u[CAI_RED + e]) + s_u[2 * CAI_RED + e];
+        v += a.b2[n];
+        s_a2[m * CAI_A2_LD + n] = v > 0.f ? v : 0.f;
+    }
+    __syncthreads();
+
+    // ---- conv3: tile (wave >> 1, wave & 1)
+    {
+        const int mt = wave >> 1, nt = wave & 1;
+        const int mc = min(32 * mt + i, 48), oh = mc / 7, ow = mc - oh * 7;
+        const int ab = (oh * 9 + ow) * CAI_A2_LD + 4 * h;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int tap = 0; tap < 9; ++tap) {
+            float wc[8][4];
+#pragma unroll
+            for (int s = 0; s < 8; ++s)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wc[s][q] = w3n[s][q];
+            if (tap + 1 < 9) load_w3(tap + 1, w3n);
+            const int kh = tap / 3, kw = tap - kh * 3, to = ab + (kh * 9 + kw) * CAI_A2_LD;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const f32x4 av = *reinterpret_cast<const f32x4*>(s_a2 + to + 8 * s);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q], wc[s][q], acc, 0, 0, 0);
+            }
+        }
+        float* out = a.feat + (size_t)blockIdx.x * 3136 + 32 * nt + i;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const float v = acc[r] + b3v;
+            if (m < 49) out[m * 64] = v > 0.f ? v : 0.f;
+        }
+    }
+}
+
+// grid (16, CAI_L1_KS)
+static __global__ __launch_bounds__(256) void k_cnn_act_head(CnnActHeadArgs a)
+{
+    __shared__ float red[4][32][33];
+    __shared__ __attribute__((aligned(16))) float hs[32][516];
+    __shared__ unsigned s_last;
+    constexpr int KSL = 3136 / CAI_L1_KS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nt = blockIdx.x, ks = blockIdx.y, n0 = nt * 32, k0 = ks * KSL;
+    const float* arow = a.feat + (size_t)min(lane & 31, a.n - 1) * 3136 + k0;   // rows >= n alias the last row (never stored)
+    const int r = tid >> 3, c4 = (tid & 7) * 4, col = n0 + c4;
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b1 + col);   // the epilogue's operand, requested beside the tile operands
+    dense_small_tile<false>([&](int k) { return *reinterpret_cast<const f32x4*>(arow + k); }, a.w1 + (size_t)k0 * 512, 512, n0, KSL, wave, lane, red);
+    __syncthreads();
+    f32x4 v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = dense_small_sum(red, r, c4 + q);
+    if (r < a.n) {
+        float* p = a.part + ((size_t)ks * 32 + r) * 512 + col;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) st_agent(p + q, v[q]);
+    }
+    if (!last_workgroup(a.counters + nt, (unsigned)CAI_L1_KS, &s_last)) return;
+    // the column tile's partials in slice order whoever arrives last (act_small.hpp: 16-byte loads served by the coherent level, all
+    // in flight before the one wait)
+    float* h1 = a.part + (size_t)CAI_L1_KS * 32 * 512;
+    if (r < a.n) {
+        const float* p0 = a.part + (size_t)r * 512 + col;
+        f32x4 t[CAI_L1_KS];
+#pragma unroll
+        for (int e = 0; e < CAI_L1_KS; ++e) {
+            const float* ps = p0 + (size_t)e * 32 * 512;
+            asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(t[e]) : "v"(ps) : "memory");
+        }
+        static_assert(CAI_L1_KS == 7, "the wait below names seven destinations");
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]) :: "memory");
+        v = t[0];
+#pragma unroll
+        for (int e = 1; e < CAI_L1_KS; ++e) v += t[e];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float x = v[q] + bv[q];
+            st_agent(h1 + (size_t)r * 512 + col + q, x > 0.f ? x : 0.f);   // read by the workgroup below, possibly on another XCD
+        }
+    }
+    if (!last_workgroup(a.counters + 16, 16u, &s_last)) return;
+
+    // ---- l2 and the first maximum, by the workgroup that completed l1's last column tile: h1 -> LDS (rows >= n: a copy of row n - 1)
+    for (int e0 = 0; e0 < 16; e0 += 8) {
+        f32x4 t[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int x = tid + 256 * (e0 + e);   // 16-byte vector x of hs: row x >> 7, floats 4 (x & 127) ...
+            const float* ps = h1 + (size_t)min(x >> 7, a.n - 1) * 512 + 4 * (x & 127);
+            asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(t[e]) : "v"(ps) : "memory");
+        }
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]) :: "memory");
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const int x = tid + 256 * (e0 + e); *reinterpret_cast<f32x4*>(&hs[x >> 7][4 * (x & 127)]) = t[e]; }
+    }
+    __syncthreads();
+    const float* hrow = hs[lane & 31];
+    for (int t0 = 0; t0 < a.A; t0 += 32) {
+        dense_small_tile<false>([&](int k) { return *reinterpret_cast<const f32x4*>(hrow + k); }, a.w2, a.ld2, t0, 512, wave, lane, red);
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = t0 + c4 + q;
+            if (r < a.n && j < a.A) a.q[(size_t)r * a.A + j] = dense_small_sum(red, r, c4 + q) + a.b2[j];
+        }
+        __syncthreads();   // red is free again; the Q stores of this workgroup are visible to it
+    }
+    if (tid < a.n) a.idx[tid] = dqn_q_argmax(a.q + (size_t)tid * a.A, a.A);
+}
+
+hipError_t launch_cnn_act_trunk(hipStream_t st, int n, const CnnActTrunkArgs& a)
+{
+    return step_launch(st, false, k_cnn_act_trunk, dim3((unsigned)n), dim3(256), a);
+}
+hipError_t launch_cnn_act_head(hipStream_t st, const CnnActHeadArgs& a)
+{
+    return step_launch(st, false, k_cnn_act_head, dim3(16, CAI_L1_KS), dim3(256), a);
+}
+
+}  // namespace bdr
+#endif  // BDR_CNN_ACT_IMG_KERNELS

@@ -269,6 +269,8 @@ struct DenseAgent : bdr_agent {
     bool act_fused_on() const { return act_path == BDR_ACT_PATH_FUSED; }
     int32_t set_act_path(int32_t path) override
     {
+        BDR_REQUIRE(path != BDR_ACT_PATH_IMAGE, "BDR_ACT_PATH_IMAGE is the acting path of the DQN (candle) agent with the AtariCnn Q-network: this %s agent acts "
+                                                "on f32 rows through BDR_ACT_PATH_LAYERS or BDR_ACT_PATH_FUSED", kind());
         BDR_REQUIRE(path == BDR_ACT_PATH_DEFAULT || path == BDR_ACT_PATH_LAYERS || path == BDR_ACT_PATH_FUSED, "unknown act path %d", path);
         const int W = act_width();
         BDR_REQUIRE(path != BDR_ACT_PATH_FUSED || (W <= DA_MAX_W && dense_act_lds(W, 1) <= DA_LDS_MAX),

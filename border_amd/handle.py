@@ -177,11 +177,13 @@ class AgentHandle:
 class DenseHandle(AgentHandle):
     """On AgentHandle, what the library serves for the agents of the dense-agent core (IQL, AWAC, BC, the candle SAC and DQN): the
     acting path and Policy::sample on raw rows; their configs carry obs_dim and act_dim."""
-    ACT_PATHS = {"default": 0, "layers": 1, "fused": 2}   # BDR_ACT_PATH_*
+    ACT_PATHS = {"default": 0, "layers": 1, "fused": 2, "image": 3}   # BDR_ACT_PATH_*
 
     def set_act_path(self, path: str) -> None:
         """How Policy::sample runs: "layers" (pack, one launch per layer, the sample kernel), "fused" (k_dense_act: one launch from the
-        raw rows to the action; same bits) or "default".  "fused" on a network it does not cover raises BdrError."""
+        raw rows to the action; same bits) or "default".  "fused" on a network it does not cover raises BdrError.  "image": the
+        two-launch acting path of the candle DQN with the AtariCnn Q-network, up to 32 rows per call (csrc/cnn_act_img.hpp; the
+        action values agree with the layer path's to rounding); every other agent raises BdrError."""
         _lib.check(_lib.lib().bdr_agent_set_act_path(self._h, self.ACT_PATHS[path]))
 
     def get_hyper(self, name) -> float:

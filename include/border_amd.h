@@ -1735,7 +1735,8 @@ BDR_API int32_t bdr_candle_dqn_probe(bdr_agent* a, int32_t what, float* out, uin
  * out-of-range action rule (no parameter of the update steps, conv layers included), checkpoints.  bdr_agent_opt reads a u8 ring
  * (obs_bytes = 84 * 84 * n_stack, act_bytes = 8; a frame-stack store is accepted); an f32 ring, another row size, another device or
  * a prioritized ring returns BDR_ERR_INVALID.  bdr_agent_sample / _qvalues take u8 host rows, the _device forms rows such as
- * bdr_atari_prep_device_stacks'; BDR_ACT_PATH_FUSED and bdr_agent_sample_raw return BDR_ERR_INVALID for this network. */
+ * bdr_atari_prep_device_stacks'; BDR_ACT_PATH_FUSED and bdr_agent_sample_raw return BDR_ERR_INVALID for this network;
+ * BDR_ACT_PATH_IMAGE (below) is its two-launch acting path. */
 typedef struct {
     int32_t n_stack;                /* AtariCnnConfig.n_stack: 1 ... 8 */
     int32_t out_dim;                /* AtariCnnConfig.out_dim = the number of actions */
@@ -1846,10 +1847,17 @@ BDR_API void bdr_candle_dqn_group_trainer_post_default(bdr_group_trainer_post* p
  * Their Policy::sample has two forms that produce the same bits: the layer-by-layer path (pack, one launch per layer, the sample
  * kernel) and k_dense_act (csrc/dense_act.hpp), one launch from the raw rows to the action.  bdr_{iql,awac,bc}_sample[_device] and
  * bdr_agent_sample_raw obey the setting.  FUSED on an agent kind or a network it does not cover (a padded layer wider than 512)
- * returns BDR_ERR_INVALID with the reason.  DEFAULT is the layer path. */
+ * returns BDR_ERR_INVALID with the reason.  DEFAULT is the layer path.
+ * IMAGE is the latency-shaped acting path of the candle DQN with the AtariCnn Q-network (bdr_candle_dqn_cnn_create) and of no other
+ * agent (they return BDR_ERR_INVALID and name their own paths): bdr_agent_sample, _sample_device and _qvalues of up to 32 rows take
+ * two launches (csrc/cnn_act_img.hpp: the conv trunk of one frame stack per workgroup with its activations in LDS, then l1, l2 and
+ * the first maximum) instead of the update's batch forward; a call with more rows takes the layer launches, bit for bit.  It is
+ * opt-in.  Its sums run in another order than the batch forward's (k-quarters and slices, not k-tiles), so its action values agree
+ * with the layer path's to rounding, not bit for bit: "acting equals the update's forward" is a property of LAYERS / DEFAULT. */
 #define BDR_ACT_PATH_DEFAULT 0
 #define BDR_ACT_PATH_LAYERS 1
 #define BDR_ACT_PATH_FUSED 2
+#define BDR_ACT_PATH_IMAGE 3
 BDR_API int32_t bdr_agent_set_act_path(bdr_agent* a, int32_t path);
 /* Policy::sample on n raw environment rows of `dtype` (BDR_DTYPE_F32 / _F64): host rows, contiguous, or (on_device != 0) device rows
  * row_stride bytes apart.  float64 is rounded to f32; with a normaliser (finished or set, dim = the agent's obs dim, on the agent's

@@ -36,6 +36,9 @@ pub enum ActPath {
     Layers,
     /// `k_dense_act`: one launch from the raw rows to the action
     Fused,
+    /// the AtariCnn candle DQN only: the conv trunk of one frame stack per workgroup, then l1 / l2 - two launches for up to 32 rows;
+    /// action values agree with `Layers` to rounding, not bit for bit
+    Image,
 }
 
 impl ActPath {
@@ -44,6 +47,7 @@ impl ActPath {
             ActPath::Default => ffi::BDR_ACT_PATH_DEFAULT,
             ActPath::Layers => ffi::BDR_ACT_PATH_LAYERS,
             ActPath::Fused => ffi::BDR_ACT_PATH_FUSED,
+            ActPath::Image => ffi::BDR_ACT_PATH_IMAGE,
         }
     }
 }

@@ -146,6 +146,7 @@ pub const BDR_TRAINER_EVENT_EVAL: i32 = 4;
 pub const BDR_ACT_PATH_DEFAULT: i32 = 0;
 pub const BDR_ACT_PATH_LAYERS: i32 = 1;
 pub const BDR_ACT_PATH_FUSED: i32 = 2;
+pub const BDR_ACT_PATH_IMAGE: i32 = 3;
 // BDR_HYPER_*: the settable scalar fields of a BC, IQL, AWAC or candle SAC agent (bdr_agent_hyper_get / _set)
 pub const BDR_HYPER_LR: i32 = 0;
 pub const BDR_HYPER_BETA1: i32 = 1;

@@ -12,6 +12,12 @@ device, for comparison.  Prints ONE JSON line and writes it to profiles/bench_ca
 u8 ring, against the tch Dqn CNN agent built with arithmetic = "f32_exact" (the same products), legs alternating in the same
 process; writes profiles/bench_candle_dqn_cnn.json (B = 32) or profiles/bench_candle_dqn_cnn_b256.json.  --no-tch runs the candle
 agent alone (the kernel-trace run).
+
+--cnn --act: per-call latency of `sample` on host frame stacks (the call of the online loop: rows to the device, the forward, the
+action back) at n = 1 and n = 8 on the act paths "layers" and "image" (csrc/cnn_act_img.hpp), ONE agent, the paths alternating in
+one process: after a warm-up of both, five rounds of 1 000 calls per path; median and spread of the rounds, and the per-launch times
+of one call from the profile brackets.  Writes profiles/bench_candle_dqn_cnn_act.json.  The bar: at n = 1 the worst "image" round is
+not slower than the best "layers" round of the same run.
 """
 from __future__ import annotations
 
@@ -95,10 +101,13 @@ def main():
     ap.add_argument("--cnn", action="store_true")
     ap.add_argument("--batch", type=int, default=32, help="--cnn: 32 (dqn_atari) or 256 (the C2 batch)")
     ap.add_argument("--no-tch", action="store_true")
+    ap.add_argument("--act", action="store_true", help="--cnn: the acting-call latency of the act paths instead of the update rate")
     args = ap.parse_args()
     if args.out is None:
         stem = "bench_candle_dqn" if not args.cnn else "bench_candle_dqn_cnn" + ("" if args.batch == 32 else f"_b{args.batch}")
         args.out = os.path.join(ROOT, "profiles", stem + ".json")
+    if args.cnn and args.act:
+        return main_cnn_act(args)
     if args.cnn:
         return main_cnn(args)
 
@@ -174,6 +183,59 @@ def main_cnn(args):
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(line + "\n")
+    print(line)
+
+
+def main_cnn_act(args, rounds=5, calls=1000):
+    import border_amd as B
+    import candle_dqn_cnn_restatement as RC
+    from bench import read_profile
+    NS, NA, PATHS = 4, 6, ("layers", "image")
+    spec = RC.CandleDqnCnnSpec(NS, NA, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01))
+    build = lambda: B.CandleDqn.build(spec.to_config(B, 32, device=0, seed=1, train=True, explorer=B.EpsilonGreedy(eps_start=0.02, eps_final=0.02, final_step=1)))
+    a = build()
+    res = {}
+    for n in (1, 8):
+        obs = np.random.default_rng(n).integers(0, 256, (n, 84 * 84 * NS), dtype=np.uint8)
+        us = {p: [] for p in PATHS}
+        for p in PATHS:   # warm-up of both paths: code objects, the path's buffers
+            a.set_act_path(p)
+            for _ in range(200):
+                a.sample(obs)
+        for _ in range(rounds):
+            for p in PATHS:
+                a.set_act_path(p)
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    a.sample(obs)   # (returns with the actions on the host: the call is synchronous)
+                us[p].append(1e6 * (time.perf_counter() - t0) / calls)
+        r = {}
+        for p in PATHS:
+            v = sorted(us[p])
+            b = build()   # (an agent of its own per path: profile slots keep the names of their first use)
+            b.set_act_path(p)
+            for _ in range(20):
+                b.sample(obs)
+            b.profile_enable(True)
+            for _ in range(100):
+                b.sample(obs)
+            slots = read_profile(b)
+            b.profile_enable(False)
+            b.close()
+            r[p] = {"us_per_call_rounds": [round(x, 2) for x in us[p]], "median_us": round(v[len(v) // 2], 2),
+                    "spread_pct": round(100.0 * (v[-1] - v[0]) / v[len(v) // 2], 2), "best_us": round(v[0], 2), "worst_us": round(v[-1], 2),
+                    "profile_brackets_us": [[l, round(1e3 * ms, 2)] for l, ms in slots if l != "_null"]}
+        r["image_over_layers_median"] = round(r["image"]["median_us"] / r["layers"]["median_us"], 4)
+        r["worst_image_not_slower_than_best_layers"] = bool(r["image"]["worst_us"] <= r["layers"]["best_us"])
+        res[f"n{n}"] = r
+    a.close()
+    out = {"metric": "dqn_atari_candle_sample_us_per_call", "shape": {"n_stack": NS, "n_actions": NA, "rows": "host u8"}, "rounds": rounds,
+           "calls_per_round": calls, "value": res["n1"]["image"]["median_us"], **res}
+    line = json.dumps(out)
+    path = os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_act.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(line + "\n")
     print(line)
 
 
