@@ -211,6 +211,7 @@ GROUP_FORM_ONE_WORKGROUP, GROUP_FORM_LAYERS, GROUP_FORM_BC_LAYERS, GROUP_FORM_IQ
 GROUP_FORM_AWAC_LAYERS = 4
 GROUP_FORM_CANDLE_SAC_LAYERS = 5
 GROUP_FORM_CANDLE_DQN_LAYERS = 6
+GROUP_FORM_CANDLE_DQN_CNN_LAYERS = 7
 
 
 class GroupInfoC(C.Structure):
@@ -387,6 +388,8 @@ ABI_SYMBOLS = [
     "bdr_candle_dqn_group_sample", "bdr_candle_dqn_group_sample_members", "bdr_candle_dqn_group_last_q",
     "bdr_candle_dqn_group_push", "bdr_candle_dqn_group_push_max_rows",
     "bdr_candle_dqn_group_trainer_ops_default", "bdr_candle_dqn_group_eval_ops_default", "bdr_candle_dqn_group_trainer_post_default",
+    "bdr_candle_dqn_cnn_group_create", "bdr_candle_dqn_cnn_group_destroy", "bdr_candle_dqn_cnn_group_size", "bdr_candle_dqn_cnn_group_member",
+    "bdr_candle_dqn_cnn_group_info", "bdr_candle_dqn_cnn_group_opt", "bdr_candle_dqn_cnn_group_opt_with_record", "bdr_candle_dqn_cnn_group_sync",
 ]
 
 # BDR_HYPER_* (include/border_amd.h): the settable scalar fields of a BC, IQL, AWAC or candle SAC agent, by name
@@ -701,6 +704,14 @@ def lib() -> C.CDLL:
     L.bdr_candle_dqn_group_eval_ops_default.argtypes = [C.POINTER(GroupEvalOps), vp]
     L.bdr_candle_dqn_group_trainer_post_default.restype = None
     L.bdr_candle_dqn_group_trainer_post_default.argtypes = [C.POINTER(GroupTrainerPostC), vp]
+    L.bdr_candle_dqn_cnn_group_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_candle_dqn_cnn_group_destroy.argtypes = [vp]
+    L.bdr_candle_dqn_cnn_group_size.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.bdr_candle_dqn_cnn_group_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.bdr_candle_dqn_cnn_group_info.argtypes = [vp, C.POINTER(GroupInfoC)]
+    L.bdr_candle_dqn_cnn_group_opt.argtypes = [vp, vp]
+    L.bdr_candle_dqn_cnn_group_opt_with_record.argtypes = [vp, vp, vp, i32, vp]
+    L.bdr_candle_dqn_cnn_group_sync.argtypes = [vp]
     L.bdr_trainer_train_offline_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(GroupTrainerOps), C.POINTER(BcGroupTrainerPostC),
                                                        GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     for kind in ("awac", "candle_sac"):

@@ -172,37 +172,46 @@ struct CdqnConvAdamArgs {
     AdamScalars s; unsigned n4; float tau, omt; int track;
     const unsigned* poison; unsigned long long* applied; unsigned long long step;
 };
-__global__ __launch_bounds__(256) void k_cdqn_conv_reduce_adam(CdqnConvAdamArgs a)
+// (the body over its segments and arenas `a` - the kernel argument, or a member's entry of a group's device array read in place through
+// the constant address space: k_cdqn_conv_reduce_adam_group, candle_dqn_cnn_group.hpp - and this step's words; every thread of the
+// workgroup calls it: the barrier is inside)
+template <class Args>
+__device__ __forceinline__ void cdqn_conv_reduce_adam_body(const Args& a, const AdamScalars& s, int track, unsigned long long* applied, unsigned long long step,
+                                                           f32x4 (&red)[8][32])
 {
 #pragma clang fp contract(off)
-    __shared__ f32x4 red[8][32];
-    if (*a.poison) return;   // (the whole grid reads the same word: no thread of a workgroup is left at the barrier)
     const unsigned i = blockIdx.x * 32 + (threadIdx.x & 31);
     const int k = (i >= a.seg[1].off4 ? 1 : 0) + (i >= a.seg[2].off4 ? 1 : 0);
-    const CdqnConvSeg sg = a.seg[k];
+    const CdqnConvSeg sg{a.seg[k].part, a.seg[k].stride, a.seg[k].chunks, a.seg[k].off4, a.seg[k].n4, a.seg[k].nw4, a.seg[k].wscale};
     const unsigned j = i - sg.off4;
     reduce_partials_8x32(red, sg, j, i < a.n4, [&](f32x4 gg) {
 #pragma clang fp contract(off)
-        if (i == 0) *a.applied = a.step;
+        if (i == 0) *applied = step;
         if (j < sg.nw4) gg *= sg.wscale;
         reinterpret_cast<f32x4*>(a.g)[i] = gg;
         f32x4 pp = reinterpret_cast<f32x4*>(a.p)[i], mm = reinterpret_cast<f32x4*>(a.m)[i], vv = reinterpret_cast<f32x4*>(a.v)[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float pe = pp[e], me = mm[e], ve = vv[e];
-            adam_element(pe, gg[e], me, ve, a.s);
+            adam_element(pe, gg[e], me, ve, s);
             pp[e] = pe; mm[e] = me; vv[e] = ve;
         }
         reinterpret_cast<f32x4*>(a.p)[i] = pp;
         reinterpret_cast<f32x4*>(a.m)[i] = mm;
         reinterpret_cast<f32x4*>(a.v)[i] = vv;
-        if (a.track) {
+        if (track) {
             f32x4 d = reinterpret_cast<f32x4*>(a.tgt)[i];
 #pragma unroll
             for (int e = 0; e < 4; ++e) d[e] = track_element(pp[e], d[e], a.tau, a.omt);
             reinterpret_cast<f32x4*>(a.tgt)[i] = d;
         }
     });
+}
+__global__ __launch_bounds__(256) void k_cdqn_conv_reduce_adam(CdqnConvAdamArgs a)
+{
+    __shared__ f32x4 red[8][32];
+    if (*a.poison) return;   // (the whole grid reads the same word: no thread of a workgroup is left at the barrier)
+    cdqn_conv_reduce_adam_body(a, a.s, a.track, a.applied, a.step, red);
 }
 
 // ---- the exploration stream -------------------------------------------------------------------------------------------------------
@@ -886,7 +895,8 @@ int32_t cdqn_cnn_check(const bdr_candle_dqn_cnn_config& c, bdr_candle_dqn_config
 
 }  // namespace
 
-#include "candle_dqn_group.hpp"   // the launch grouping of Mlp-form agents: needs CandleDqn and the bodies above
+#include "candle_dqn_group.hpp"       // the launch grouping of Mlp-form agents: needs CandleDqn and the bodies above
+#include "candle_dqn_cnn_group.hpp"   // the launch grouping of AtariCnn-form agents (the update round): conv_group.hpp's trunk entries on top of it
 
 extern "C" {
 

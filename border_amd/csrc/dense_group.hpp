@@ -118,16 +118,22 @@ inline void dg_fwd_entries(std::vector<DenseGroupEntry>& out, const MlpLayout& n
     }
 }
 // mlp_backward_step of the nz instances of network `id` (the kind's network id: the index of o.dw, o.dw_grid and o.ra): the dX entries
-// from the last layer down, the grouped dW, the reduce segments
+// from the last layer down (and, with dx0 / mask0, the one below layer 0), the grouped dW, the reduce segments
 template <int NNET>
 void dg_step_entries(DenseMemberArgs<NNET>& o, int id, const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
                      const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
-                     const std::vector<size_t>& off, int bs, size_t total, double tau, const DenseReduceSeg* extra)
+                     const std::vector<size_t>& off, int bs, size_t total, double tau, const DenseReduceSeg* extra, float* const* dx0 = nullptr,
+                     const float* const* mask0 = nullptr)
 {
     const int L = (int)net.L.size();
     for (int l = L - 1; l >= 1; --l) {
         DenseGroupEntry e{};
         for (int z = 0; z < nz; ++z) e.a[z] = dg_dx_args(net.L[l], p[z], (*dys[z])[l], (*dys[z])[l - 1], (*acts[z])[l - 1], bs);
+        o.dense.push_back(e);
+    }
+    if (dx0) {   // mlp_backward_step's dx0 / mask0: one more input gradient below layer 0, masked by the activation that produced x0
+        DenseGroupEntry e{};
+        for (int z = 0; z < nz; ++z) e.a[z] = dg_dx_args(net.L[0], p[z], (*dys[z])[0], dx0[z], mask0 ? mask0[z] : nullptr, bs);
         o.dense.push_back(e);
     }
     DenseDwJob jobs[DW_GROUP];

@@ -202,6 +202,11 @@ int group_obs_dim(const void* group, uint32_t member)
 template <class K, class M> auto group_act_row_bytes(const M* m, int) -> decltype(K::act_row_bytes(m)) { return K::act_row_bytes(m); }
 template <class K, class M> uint64_t group_act_row_bytes(const M* m, long) { return (uint64_t)m->A * 4; }
 
+// the bytes of one observation row of a member's ring: O f32 values, unless the kind says otherwise (K::obs_row_bytes - the candle DQN
+// CNN group: u8 rows of 84 * 84 * n_stack bytes)
+template <class K, class M> auto group_obs_row_bytes(const M* m, int) -> decltype(K::obs_row_bytes(m)) { return K::obs_row_bytes(m); }
+template <class K, class M> uint64_t group_obs_row_bytes(const M* m, long) { return (uint64_t)m->O * 4; }
+
 // the second of two members that name one bdr_replay (P: the P handles are all different)
 inline uint32_t group_shared_buffer(bdr_replay* const* buffers, uint32_t P)
 {
@@ -224,7 +229,7 @@ int32_t group_check_buffers(G* g, bdr_replay* const* buffers)
         const bdr_replay* r = buffers[p];
         BDR_REQUIRE(r, "member %u: null buffer", p);
         BDR_REQUIRE(!m->prof && !m->grad_comm, "member %u: profiling or a gradient communicator was switched on after the group was created", p);
-        BDR_REQUIRE(r->obs_bytes == (uint64_t)m->O * 4 && r->act_bytes == group_act_row_bytes<K>(m, 0), "member %u: replay rows do not match %s obs/act dims (f32 rows)", p, K::NAME);
+        BDR_REQUIRE(r->obs_bytes == group_obs_row_bytes<K>(m, 0) && r->act_bytes == group_act_row_bytes<K>(m, 0), "member %u: replay rows do not match %s obs/act dims (f32 rows)", p, K::NAME);
         BDR_REQUIRE(r->device == g->device, "member %u: its replay buffer lives on another device", p);
         BDR_REQUIRE(!r->per, "member %u: a prioritized buffer cannot be stepped by %s group (the grouped gather covers the uniform ring)", p, K::A);
         BDR_REQUIRE(!r->frame_stack, "member %u: a single-frame store cannot be stepped by %s group", p, K::A);

@@ -33,7 +33,8 @@ def raise_first(evaluators, status: int) -> None:
 
 GROUP_FORMS = {_lib.GROUP_FORM_ONE_WORKGROUP: "one_workgroup", _lib.GROUP_FORM_LAYERS: "layers", _lib.GROUP_FORM_BC_LAYERS: "bc_layers",
                _lib.GROUP_FORM_IQL_LAYERS: "iql_layers", _lib.GROUP_FORM_AWAC_LAYERS: "awac_layers",
-               _lib.GROUP_FORM_CANDLE_SAC_LAYERS: "candle_sac_layers", _lib.GROUP_FORM_CANDLE_DQN_LAYERS: "candle_dqn_layers"}
+               _lib.GROUP_FORM_CANDLE_SAC_LAYERS: "candle_sac_layers", _lib.GROUP_FORM_CANDLE_DQN_LAYERS: "candle_dqn_layers",
+               _lib.GROUP_FORM_CANDLE_DQN_CNN_LAYERS: "candle_dqn_cnn_layers"}
 
 
 class DqnGroup:
@@ -843,3 +844,36 @@ class CandleDqnGroup(_GroupBase):
         self._buffers(buffers)   # (opt() / push() without buffers go on with these)
         return NativeTrainer(trainer_config).train_group(envs, self, list(buffers), on_event=on_event, evaluators=evaluators,
                                                          eval_interval=eval_interval, save_interval=save_interval, model_dirs=model_dirs)
+
+
+class CandleDqnCnnGroup(_GroupBase):
+    """A set of candle DQN agents with the AtariCnn Q-network (`CandleDqn.build` of a config whose q_config is an AtariCnnConfig) of
+    one shape whose Agent::opt (Dqn::opt_, dqn/base.rs:172-189) runs as the launch sequence of ONE member, every launch serving all
+    members (bdr_candle_dqn_cnn_group_*): 17 launches per round whatever the number of members, each member bit for bit what it is
+    stepped alone.  One value for all members: n_stack (<= 6), the number of actions, batch_size, double_dqn, n_updates_per_opt = 1.
+    The members may differ in seed, parameters, optimizer and learning rate, discount_factor, tau, soft_update_interval, critic_loss
+    and record_verbose_level; their buffers are uniform uint8 buffers of their own or views of one (`SimpleReplayBuffer.view`) - a
+    frame-stack store or a prioritized buffer is refused by member.
+
+    The group covers the update round only: `opt`, `opt_with_record`, `sync`.  Acting, push, evaluation, the compiled online loop and
+    copy_members are not built for CNN members; the members are ordinary `CandleDqn` objects the group owns, and their own `sample`,
+    `qvalues`, `set_hyper` and checkpoint calls keep working between rounds.  A member whose batch holds an out-of-range action is
+    skipped on the device and reported by `sync` / `opt_with_record` as "member <i>: ..."; the others step."""
+    _PREFIX, _MEMBER = "bdr_candle_dqn_cnn_group", CandleDqn
+    record_keys = CandleDqnGroup.record_keys
+
+    def opt_with_record(self, buffers=None) -> list:
+        """Agent::opt_with_record of every member (one synchronisation): a list of Record dicts in member order."""
+        n = len(self._members)
+        keys = [self.record_keys(i) for i in range(n)]
+        cap = max(8, max(len(k) for k in keys))
+        out = np.zeros((n, cap), np.float32)
+        cnt = np.zeros(n, np.int32)
+        _lib.check(self._c("opt_with_record")(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)))
+        return [{k: np.float32(v) for k, v in zip(keys[i], out[i, :cnt[i]])} for i in range(n)]
+
+    def sample(self, *a, **k):
+        raise NotImplementedError("a candle DQN CNN group steps the update round only: act through the members' own sample()")
+    evaluate = sample
+
+

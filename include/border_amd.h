@@ -510,6 +510,7 @@ BDR_API int32_t bdr_agent_group_member(const bdr_agent_group* g, uint32_t i, bdr
 #define BDR_GROUP_FORM_AWAC_LAYERS 4 /* a bdr_awac_group (below): AWAC's launch sequence of one member, every launch serving all members */
 #define BDR_GROUP_FORM_CANDLE_SAC_LAYERS 5 /* a bdr_candle_sac_group (below): the candle SAC's launch sequence of one member, every launch serving all members */
 #define BDR_GROUP_FORM_CANDLE_DQN_LAYERS 6 /* a bdr_candle_dqn_group (below): the candle DQN's launch sequence of one member, every launch serving all members */
+#define BDR_GROUP_FORM_CANDLE_DQN_CNN_LAYERS 7 /* a bdr_candle_dqn_cnn_group (below): the AtariCnn candle DQN's 17 launches of one member's update, every launch serving all members */
 typedef struct { int32_t form; uint32_t n_members; uint32_t launches_per_round; uint32_t reserved; uint64_t kernel_launches; } bdr_group_info;
 BDR_API int32_t bdr_agent_group_info(const bdr_agent_group* g, bdr_group_info* out);
 /* Prioritized replay under the group (on = 1; 0, the default, refuses every prioritized ring in _opt and _push as before).  A group
@@ -1803,7 +1804,7 @@ BDR_API int32_t bdr_candle_dqn_cnn_update_on_batch(bdr_agent* a, uint64_t n, con
  * the lone agent's status.  _opt_with_scalars returns every member's opt_with_record record (dqn/base.rs:307-331: loss, at
  * record_verbose_level >= 2 the four means and the parameter statistics, then ratio_best_act and the reset of both counters) at
  * out + p * cap_per_member.  _info fills bdr_group_info with form = BDR_GROUP_FORM_CANDLE_DQN_LAYERS.
- * Not built: the AtariCnn form, n_updates_per_opt > 1, bdr_*_group_copy_members and bdr_agent_hyper_* for this kind, a captured graph
+ * Not built: the AtariCnn form (it has a group kind of its own: bdr_candle_dqn_cnn_group below), n_updates_per_opt > 1, bdr_*_group_copy_members and bdr_agent_hyper_* for this kind, a captured graph
  * of the round, an explorer on the device, prioritized rings under the group. */
 typedef struct bdr_candle_dqn_group bdr_candle_dqn_group;
 BDR_API int32_t bdr_candle_dqn_group_create(bdr_agent* const* agents, uint32_t n, bdr_candle_dqn_group** out);   /* dqn/base.rs:172-189 (opt_ of every member) */
@@ -1842,6 +1843,34 @@ BDR_API int32_t bdr_candle_dqn_group_push_max_rows(bdr_candle_dqn_group* g, bdr_
 BDR_API void bdr_candle_dqn_group_trainer_ops_default(bdr_group_trainer_ops* ops, bdr_candle_dqn_group* group, bdr_replay* const* buffers);   /* trainer.rs:267-327, trainer/sampler.rs:99-144 */
 BDR_API void bdr_candle_dqn_group_eval_ops_default(bdr_group_eval_ops* ops, bdr_candle_dqn_group* group);                                     /* evaluator/default_evaluator.rs:64-88 */
 BDR_API void bdr_candle_dqn_group_trainer_post_default(bdr_group_trainer_post* post, bdr_candle_dqn_group* group);                            /* dqn/base.rs:337-351, trainer.rs:231-264 */
+
+/* ---- a group of candle DQN agents with the AtariCnn Q-network: the update round ----------------------------------------------------------------------
+ * Dqn::opt_ (dqn/base.rs:172-189) of every member in the launch sequence bdr_agent_opt enqueues for ONE bdr_candle_dqn_cnn_create agent -
+ * the gather of u8 rows, conv1 / conv2 / conv3 and l1 / l2 forward (the passes (p, obs), (p_tgt, next_obs) and - double_dqn - (p, next_obs)
+ * are the instances of one launch per layer), the TD launch, the head's two input gradients, its grouped weight gradient and reduce +
+ * Adam, conv3 dW, conv3 dX, conv2 dW, conv2 dX, conv1 dW, the conv reduce + Adam - with every launch serving ALL members (the member
+ * is grid dimension y): 17 launches per round whatever the number of members, and every member bit-identical to being stepped alone.
+ * The group covers the UPDATE ROUND ONLY: acting, push, evaluation, the compiled online loop and copies between members are not built
+ * for CNN members.  The members stay ordinary agents (on the group's stream, destroyed with the group): their own bdr_agent_sample,
+ * bdr_agent_qvalues, bdr_agent_hyper_set and checkpoint calls keep working between rounds.
+ * _create: every agent a bdr_candle_dqn_cnn_create agent, one shape per group (n_stack <= 6, n_actions, batch_size, double_dqn),
+ * n_updates_per_opt == 1, one device, no profiling, no gradient communicator, one value of dxc3_kloop; a refusal names the first member
+ * concerned and adopts nobody (an Mlp-form candle DQN agent is refused by name: it joins a bdr_candle_dqn_group).
+ * buffers[p] is member p's: a uniform u8 ring, or a view of one, with rows of 84 * 84 * n_stack bytes and 8-byte action rows on the
+ * group's device; a frame-stack store, a prioritized ring, a ring on another device or one listed twice is refused before anything is
+ * enqueued, naming the member.  An out-of-range action in a member's batch skips THAT member's optimizer step and soft update (head and
+ * conv parameters alike); _sync, _opt_with_record and the member's own synchronising calls put its step, n_opts and soft_update_counter
+ * back and report it as "member <p>: ...".  _opt_with_record returns every member's opt_with_record record (dqn/base.rs:307-331) at
+ * out + p * cap_per_member.  _info fills bdr_group_info with form = BDR_GROUP_FORM_CANDLE_DQN_CNN_LAYERS. */
+typedef struct bdr_candle_dqn_cnn_group bdr_candle_dqn_cnn_group;
+BDR_API int32_t bdr_candle_dqn_cnn_group_create(bdr_agent* const* agents, uint32_t n, bdr_candle_dqn_cnn_group** out);   /* dqn/base.rs:172-189 (opt_ of every member) */
+BDR_API int32_t bdr_candle_dqn_cnn_group_destroy(bdr_candle_dqn_cnn_group* g);                                           /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_size(const bdr_candle_dqn_cnn_group* g, uint32_t* n);                           /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_member(const bdr_candle_dqn_cnn_group* g, uint32_t i, bdr_agent** out);         /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_info(const bdr_candle_dqn_cnn_group* g, bdr_group_info* out);                   /* dqn/base.rs:172-189 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_opt(bdr_candle_dqn_cnn_group* g, bdr_replay* const* buffers);                   /* dqn/base.rs:172-189, :59-170 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_opt_with_record(bdr_candle_dqn_cnn_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);   /* dqn/base.rs:307-331 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_sync(bdr_candle_dqn_cnn_group* g);                                              /* dqn/base.rs:172-189 */
 
 /* ---- acting of the dense-agent agents (IQL, AWAC, the candle SAC, BC, the candle DQN) ----------------------------------------------------------------------
  * Their Policy::sample has two forms that produce the same bits: the layer-by-layer path (pack, one launch per layer, the sample

@@ -123,6 +123,7 @@ pub const BDR_GROUP_FORM_IQL_LAYERS: i32 = 3;
 pub const BDR_GROUP_FORM_AWAC_LAYERS: i32 = 4;
 pub const BDR_GROUP_FORM_CANDLE_SAC_LAYERS: i32 = 5;
 pub const BDR_GROUP_FORM_CANDLE_DQN_LAYERS: i32 = 6;
+pub const BDR_GROUP_FORM_CANDLE_DQN_CNN_LAYERS: i32 = 7;
 pub const BDR_IQN_CONST10: i32 = 0;
 pub const BDR_IQN_CONST32: i32 = 1;
 pub const BDR_IQN_UNIFORM10: i32 = 2;
@@ -191,6 +192,8 @@ pub enum bdr_awac_group {}
 pub enum bdr_candle_sac_group {}
 /// `bdr_candle_dqn_group` (a launch grouping of candle DQN agents in the Mlp form): only ever behind a pointer.
 pub enum bdr_candle_dqn_group {}
+/// `bdr_candle_dqn_cnn_group` (a launch grouping of candle DQN agents in the AtariCnn form, the update round): only ever behind a pointer.
+pub enum bdr_candle_dqn_cnn_group {}
 #[repr(C)]
 pub struct bdr_replay {
     _private: [u8; 0],
@@ -1428,6 +1431,14 @@ extern "C" {
     pub fn bdr_candle_dqn_group_trainer_ops_default(ops: *mut bdr_group_trainer_ops, group: *mut bdr_candle_dqn_group, buffers: *mut *const bdr_replay);
     pub fn bdr_candle_dqn_group_eval_ops_default(ops: *mut bdr_group_eval_ops, group: *mut bdr_candle_dqn_group);
     pub fn bdr_candle_dqn_group_trainer_post_default(post: *mut bdr_group_trainer_post, group: *mut bdr_candle_dqn_group);
+    pub fn bdr_candle_dqn_cnn_group_create(agents: *mut *const bdr_agent, n: u32, out: *mut *mut bdr_candle_dqn_cnn_group) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_destroy(g: *mut bdr_candle_dqn_cnn_group) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_size(g: *const bdr_candle_dqn_cnn_group, n: *mut u32) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_member(g: *const bdr_candle_dqn_cnn_group, i: u32, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_info(g: *const bdr_candle_dqn_cnn_group, out: *mut bdr_group_info) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_opt(g: *mut bdr_candle_dqn_cnn_group, buffers: *mut *const bdr_replay) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_opt_with_record(g: *mut bdr_candle_dqn_cnn_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_sync(g: *mut bdr_candle_dqn_cnn_group) -> i32;
     pub fn bdr_agent_sample_raw(
         a: *mut bdr_agent,
         norm: *const bdr_obs_norm,

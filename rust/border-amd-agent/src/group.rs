@@ -2075,3 +2075,126 @@ where
         }
     }
 }
+
+/// A group of candle DQN agents with the `AtariCnn` Q-network of one shape (n_stack <= 6, number of actions, batch size, double_dqn)
+/// whose `Agent::opt` (`Dqn::opt_`, dqn/base.rs:172-189) runs as the launch sequence of ONE member, every launch serving all members
+/// (`bdr_candle_dqn_cnn_group_*`): 17 launches per round whatever the number of members, every member bit for bit what it is stepped
+/// alone.  Member `i` steps on `buffers[i]`, a uniform u8 buffer of its own or a view of one ([`AmdReplayBuffer::view`]).
+///
+/// The group covers the update round only - acting, push, evaluation, the compiled online loop and copies between members are not
+/// built for CNN members; the members are ordinary [`AmdCandleDqn`] agents ([`AmdCandleDqnCnnGroup::member_mut`]) whose own calls keep
+/// working between rounds.  Owns its members: dropping the group destroys them (`bdr_candle_dqn_cnn_group_destroy`).
+pub struct AmdCandleDqnCnnGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    g: *mut ffi::bdr_candle_dqn_cnn_group,
+    members: Vec<AmdCandleDqn<E, O, A>>,
+}
+
+// SAFETY: as `AgentHandle` - one HIP stream for the group and its members, all device work behind `&mut`.
+unsafe impl<E: Env, O: RowBatch, A: RowBatch> Send for AmdCandleDqnCnnGroup<E, O, A> {}
+
+impl<E, O, A> AmdCandleDqnCnnGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    /// Groups agents that already exist.  Fails, naming the first member concerned and the reason, unless all members are candle DQN
+    /// agents in the AtariCnn form of one shape with `n_updates_per_opt == 1` on one device.
+    pub fn adopt(members: Vec<AmdCandleDqn<E, O, A>>) -> Result<Self> {
+        if members.is_empty() {
+            return Err(anyhow!("a group needs at least one member"));
+        }
+        let mut hs: Vec<*const ffi::bdr_agent> = members.iter().map(|m| m.a.h as *const ffi::bdr_agent).collect();
+        let mut g = std::ptr::null_mut();
+        check(unsafe { ffi::bdr_candle_dqn_cnn_group_create(hs.as_mut_ptr(), hs.len() as u32, &mut g) })?;
+        Ok(Self { g, members })
+    }
+
+    pub fn handle(&self) -> *mut ffi::bdr_candle_dqn_cnn_group {
+        self.g
+    }
+
+    pub fn len(&self) -> usize {
+        self.members.len()
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.members.is_empty()
+    }
+
+    pub fn member(&self, i: usize) -> &AmdCandleDqn<E, O, A> {
+        &self.members[i]
+    }
+
+    /// A member as the ordinary agent it is (`Agent`, `Policy`, `SyncModel`, `save_params` ...).
+    pub fn member_mut(&mut self, i: usize) -> &mut AmdCandleDqn<E, O, A> {
+        &mut self.members[i]
+    }
+
+    /// `bdr_candle_dqn_cnn_group_info`: `form` is `ffi::BDR_GROUP_FORM_CANDLE_DQN_CNN_LAYERS`, `launches_per_round` is 17.
+    pub fn info(&self) -> Result<ffi::bdr_group_info> {
+        let mut out = ffi::bdr_group_info::default();
+        check(unsafe { ffi::bdr_candle_dqn_cnn_group_info(self.g, &mut out) })?;
+        Ok(out)
+    }
+
+    fn buffer_handles(&self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<*const ffi::bdr_replay>> {
+        if buffers.len() != self.members.len() {
+            return Err(anyhow!("{} members need {} buffers, got {}", self.members.len(), self.members.len(), buffers.len()));
+        }
+        Ok(buffers.iter().map(|b| b.h as *const ffi::bdr_replay).collect())
+    }
+
+    /// `Agent::opt` of every member, member `i` on `buffers[i]`; only enqueues.  A refused call (a frame-stack store, a prioritized,
+    /// empty, mismatched or shared buffer) leaves every member and every buffer where it was.
+    pub fn opt(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<()> {
+        let mut hs = self.buffer_handles(buffers)?;
+        check(unsafe { ffi::bdr_candle_dqn_cnn_group_opt(self.g, hs.as_mut_ptr()) })
+    }
+
+    /// `Agent::opt_with_record` of every member (dqn/base.rs:307-331): the same round, one synchronisation, the members' `Record`s
+    /// in member order.  A member skipped for an out-of-range action is reported as "member <i>: ...".
+    pub fn opt_with_record(&mut self, buffers: &mut [AmdReplayBuffer<O, A>]) -> Result<Vec<Record>> {
+        const CAP: usize = 128;
+        let mut hs = self.buffer_handles(buffers)?;
+        let n = self.members.len();
+        let mut vals = vec![0f32; n * CAP];
+        let mut counts = vec![0i32; n];
+        check(unsafe { ffi::bdr_candle_dqn_cnn_group_opt_with_record(self.g, hs.as_mut_ptr(), vals.as_mut_ptr(), CAP as i32, counts.as_mut_ptr()) })?;
+        let mut out = Vec::with_capacity(n);
+        for (i, m) in self.members.iter_mut().enumerate() {
+            let keys = m.a.record_keys().to_vec();
+            let mut record = Record::empty();
+            for (k, v) in keys.iter().zip(vals[i * CAP..].iter().take(counts[i] as usize)) {
+                record.insert(k.clone(), RecordValue::Scalar(*v));
+            }
+            out.push(record);
+        }
+        Ok(out)
+    }
+
+    /// Waits for everything the group and its members have enqueued (`bdr_candle_dqn_cnn_group_sync`); every member settles, and a
+    /// member whose update was skipped for an out-of-range action is reported as "member <i>: ...".
+    pub fn sync(&mut self) -> Result<()> {
+        check(unsafe { ffi::bdr_candle_dqn_cnn_group_sync(self.g) })
+    }
+}
+
+impl<E, O, A> Drop for AmdCandleDqnCnnGroup<E, O, A>
+where
+    E: Env,
+    O: RowBatch,
+    A: RowBatch,
+{
+    fn drop(&mut self) {
+        expect(unsafe { ffi::bdr_candle_dqn_cnn_group_destroy(self.g) }, "bdr_candle_dqn_cnn_group_destroy");
+        for m in self.members.iter_mut() {
+            m.a.h = std::ptr::null_mut(); // destroyed with the group; bdr_agent_destroy(NULL) in the member's own drop is a no-op
+        }
+    }
+}
