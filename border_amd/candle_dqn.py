@@ -6,7 +6,8 @@
   CandleDqnModelConfig  dqn/model.rs (q_config: the Mlp's MlpConfig, opt_config: OptimizerConfig::default() = AdamW)
                         q_config = AtariCnnConfig(n_stack, out_dim) (atari_cnn/config.rs) builds the AtariCnn form instead: u8 rows of
                         84 * 84 * n_stack bytes, variables c1.weight ... l2.bias; CandleDqnConfig(q_config=AtariCnnConfig(...)) is the
-                        short spelling.  `arithmetic` must stay "f32_exact" for it.
+                        short spelling.  `arithmetic` must stay "f32_exact" for it: the split-operand forward of conv2 / conv3
+                        is switched on on the built agent, `CandleDqn.set_arithmetic("bf16x3_6")` (DqnConfig's naming).
   Softmax, EpsilonGreedy  dqn/explorer.rs (the classes of border_amd.dqn); explorer_seed is the seed of the agent's SmallRng, 42 in
                         the reference (dqn/base.rs:274)
   CandleDqn             dqn/base.rs (Agent, Policy::sample -> int64 action indices)
@@ -53,7 +54,8 @@ class CandleDqnConfig:
     ckpt_format: str = "tch"                              # "tch": qnet.pt / qnet_tgt.pt; "safetensors": *.safetensors
     seed: int = 0
     q_config: Optional[AtariCnnConfig] = None             # the AtariCnn form: replaces model_config.q_config
-    arithmetic: str = "f32_exact"                         # AtariCnn form only; "bf16x3_6" is refused by the library
+    arithmetic: str = "f32_exact"                         # AtariCnn form only.  It takes ONE value: the library builds "f32_exact" and refuses
+                                                          # "bf16x3_6" here, naming CandleDqn.set_arithmetic("bf16x3_6"), the switch on the built agent
 
     def __post_init__(self):
         if self.q_config is not None:
@@ -115,6 +117,7 @@ class CandleDqn(DenseHandle):
     # bdr_agent_get_params `which`: the tch Dqn's numbers
     WHICH = {"qnet": 0, "qnet_tgt": 1, "exp_avg": 2, "exp_avg_sq": 3, "grad": 4}
     PROBES = {"pred": 0, "q_next": 1, "y": 2, "tgt": 3, "dpred": 4}
+    LAYER_PROBES = {"a1": (5, (20, 20, 32)), "a2": (6, (9, 9, 64)), "a3": (7, (7, 7, 64))}   # AtariCnn form: the trunk of the last forward
 
     def __init__(self, config: CandleDqnConfig):
         self.cnn = config.cnn
@@ -152,10 +155,25 @@ class CandleDqn(DenseHandle):
         return out
 
     def probe(self, what: str, batch: int) -> np.ndarray:
-        """Intermediates of the last update (bdr_candle_dqn_probe), each [B]: pred, q_next, y (the argmax index), tgt, dpred."""
+        """Intermediates of the last update (bdr_candle_dqn_probe), each [B]: pred, q_next, y (the argmax index), tgt, dpred.
+        AtariCnn form: a1, a2, a3 of instance 0 of the last forward (an update or an acting call of `batch` rows), [batch][H][W][C]."""
+        if what in self.LAYER_PROBES:
+            code, shape = self.LAYER_PROBES[what]
+            out = np.empty((batch,) + shape, np.float32)
+            _lib.check(_lib.lib().bdr_candle_dqn_probe(self._h, code, _p(out), out.size))
+            return out
         out = np.empty(batch, np.float32)
         _lib.check(_lib.lib().bdr_candle_dqn_probe(self._h, self.PROBES[what], _p(out), out.size))
         return out.astype(np.int64) if what == "y" else out
+
+    def set_arithmetic(self, arithmetic: str) -> None:
+        """bdr_candle_dqn_cnn_set_arithmetic (AtariCnn form): "bf16x3_6" - conv2 / conv3 forward with split operands on the bf16
+        matrix cores, in the update and on both acting paths.  One way: a split agent stays split."""
+        _lib.check(_lib.lib().bdr_candle_dqn_cnn_set_arithmetic(self._h, _lib.ARITHMETIC[arithmetic]))
+
+    def keep_layers(self, on: bool = True) -> None:
+        """bdr_candle_dqn_cnn_keep_layers: the image-path trunk of a "bf16x3_6" agent also stores a1 and a2 for probe()."""
+        _lib.check(_lib.lib().bdr_candle_dqn_cnn_keep_layers(self._h, int(on)))
 
     # ---- Policy::sample (dqn/base.rs:202-230) ----
     def set_explorer(self, explorer: Union[Softmax, EpsilonGreedy], seed: int = 42) -> None:

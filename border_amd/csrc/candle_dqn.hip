@@ -26,6 +26,8 @@
 
 using namespace bdr;
 
+#include "fwd_c23_b3.hpp"   // BDR_ARITH_BF16X3_6 of the AtariCnn form: the weight planes, k_conv_planes and the fused conv2 + conv3 launch
+
 namespace {
 
 // obs, next_obs [B][O] -> the zero-padded first-layer inputs x_o, x_no [B][Kp] in one launch (the padding columns were zeroed when
@@ -175,9 +177,13 @@ struct CdqnConvAdamArgs {
 // (the body over its segments and arenas `a` - the kernel argument, or a member's entry of a group's device array read in place through
 // the constant address space: k_cdqn_conv_reduce_adam_group, candle_dqn_cnn_group.hpp - and this step's words; every thread of the
 // workgroup calls it: the barrier is inside)
-template <class Args>
+// PLANES (BDR_ARITH_BF16X3_6): the W2 / W3 elements just stepped - segments 1 and 2, float4 j < nw4, element 4 j + e = k 64 + n of the
+// layer - are split again (split3_rn) and their three terms stored into the set's planes cpl (fwd_c23_b3.hpp conv_plane_store:
+// cpl_index(k, n) < K 64 of each plane), and on the opts that track the target's elements into cpl_tgt behind track_element: the
+// planes of both sets stay equal to their f32 weights without a launch of their own.
+template <bool PLANES = false, class Args>
 __device__ __forceinline__ void cdqn_conv_reduce_adam_body(const Args& a, const AdamScalars& s, int track, unsigned long long* applied, unsigned long long step,
-                                                           f32x4 (&red)[8][32])
+                                                           f32x4 (&red)[8][32], uint16_t* cpl = nullptr, uint16_t* cpl_tgt = nullptr)
 {
 #pragma clang fp contract(off)
     const unsigned i = blockIdx.x * 32 + (threadIdx.x & 31);
@@ -199,11 +205,22 @@ __device__ __forceinline__ void cdqn_conv_reduce_adam_body(const Args& a, const 
         reinterpret_cast<f32x4*>(a.p)[i] = pp;
         reinterpret_cast<f32x4*>(a.m)[i] = mm;
         reinterpret_cast<f32x4*>(a.v)[i] = vv;
+        [[maybe_unused]] const bool w23 = PLANES && k >= 1 && j < sg.nw4;
+        if constexpr (PLANES) {
+            if (w23)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) conv_plane_store(cpl, k - 1, (int)(4 * j + e), pp[e]);
+        }
         if (track) {
             f32x4 d = reinterpret_cast<f32x4*>(a.tgt)[i];
 #pragma unroll
             for (int e = 0; e < 4; ++e) d[e] = track_element(pp[e], d[e], a.tau, a.omt);
             reinterpret_cast<f32x4*>(a.tgt)[i] = d;
+            if constexpr (PLANES) {
+                if (w23)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) conv_plane_store(cpl_tgt, k - 1, (int)(4 * j + e), d[e]);
+            }
         }
     });
 }
@@ -212,6 +229,12 @@ __global__ __launch_bounds__(256) void k_cdqn_conv_reduce_adam(CdqnConvAdamArgs 
     __shared__ f32x4 red[8][32];
     if (*a.poison) return;   // (the whole grid reads the same word: no thread of a workgroup is left at the barrier)
     cdqn_conv_reduce_adam_body(a, a.s, a.track, a.applied, a.step, red);
+}
+__global__ __launch_bounds__(256) void k_cdqn_conv_reduce_adam_planes(CdqnConvAdamArgs a, uint16_t* cpl, uint16_t* cpl_tgt)
+{
+    __shared__ f32x4 red[8][32];
+    if (*a.poison) return;
+    cdqn_conv_reduce_adam_body<true>(a, a.s, a.track, a.applied, a.step, red, cpl, cpl_tgt);
 }
 
 // ---- the exploration stream -------------------------------------------------------------------------------------------------------
@@ -641,12 +664,55 @@ struct CandleDqn : DenseAgent {
 //   2 head forwards, k_cdqn_td, 2 head input gradients (l2, then d(features) under conv3's ReLU mask), the grouped dW of l1 and l2,
 //   the head's reduce + Adam, conv3 dW, conv3 dX, conv2 dW, conv2 dX, conv1 dW, k_cdqn_conv_reduce_adam
 // = 16 launches plus the ring's gather.  The head steps before the trunk's backward runs; nothing behind it reads l1 or l2.
+// BDR_ARITH_BF16X3_6 (opt-in, bdr_candle_dqn_cnn_set_arithmetic): conv2 + conv3 forward of all instances are ONE launch of k_fwd_c23_b3 (fwd_c23_b3.hpp) from the bf16
+// planes kept beside p and p_tgt (cpl below) - 15 launches - and the conv optimizer launch is k_cdqn_conv_reduce_adam_planes; on
+// BDR_ACT_PATH_IMAGE the trunk is k_cnn_act_trunk_b3 (cnn_act_img.hpp).  Everything else is the exact agent's.
 struct CandleDqnCnn : CandleDqn {
     bdr_candle_dqn_cnn_config ccfg;
     Arena conv;                      // offsets of W1 ... b3 (w4 = the conv floats = where net's arena begins)
     float *a1[3] = {}, *a2[3] = {}, *a3[3] = {};    // trunk activations of the three passes
     float *dy3 = nullptr, *dy2 = nullptr, *dy1 = nullptr, *part_conv = nullptr;
     uint8_t *u_obs8 = nullptr, *u_next8 = nullptr; uint64_t u_cap8 = 0;
+
+    // BDR_ARITH_BF16X3_6 (bdr_candle_dqn_cnn_set_arithmetic on a built agent; the constructor builds BDR_ARITH_F32_EXACT): the bf16 planes of W2 / W3 beside p (set 0) and p_tgt (set 1), fwd_c23_b3.hpp's layout.  The PLANES form of
+    // the conv optimizer launch keeps them equal to the weights it steps; every other writer of conv parameters (set_params, a
+    // checkpoint load, an arena handed out; the switch itself, which finds whatever the constructor or anyone else wrote) marks the set stale and the next
+    // forward runs k_conv_planes on it first - one extra launch, only after such a write.  A set whose raw arena pointer left the
+    // library is re-split before every forward until the arena is released.
+    uint16_t* cpl[2] = {nullptr, nullptr};
+    bool cpl_fresh[2] = {false, false}, cpl_escaped[2] = {false, false};
+    bool b3() const { return ccfg.arithmetic == BDR_ARITH_BF16X3_6; }
+    int32_t set_arithmetic(int32_t arith)
+    {
+        BDR_REQUIRE(arith == BDR_ARITH_F32_EXACT || arith == BDR_ARITH_BF16X3_6, "DQN (candle, AtariCnn): unknown arithmetic %d (BDR_ARITH_F32_EXACT or BDR_ARITH_BF16X3_6)", arith);
+        if (arith == ccfg.arithmetic) return BDR_OK;
+        // one way: exact -> split.  (The way back would leave planes nobody keeps and a second set of transitions to hold right.)
+        BDR_REQUIRE(arith == BDR_ARITH_BF16X3_6, "this agent's arithmetic is BDR_ARITH_BF16X3_6 and stays so: build another agent for BDR_ARITH_F32_EXACT");
+        BDR_REQUIRE(!group, "this agent is a member of a group: the grouped round is built for BDR_ARITH_F32_EXACT members, and a member's arithmetic is fixed");
+        BDR_HIP(hipSetDevice(device));
+        for (auto& pl : cpl) BDR_TRY(alloc(&pl, CPL_U16, AGENT));
+        cpl_fresh[0] = cpl_fresh[1] = false;   // (nothing kept the planes while the exact kernels ran)
+        ccfg.arithmetic = arith;
+        return BDR_OK;
+    }
+    void planes_stale(int set) { if (set == 0 || set == 1) cpl_fresh[set] = false; }
+    int32_t params_written(int which) override { planes_stale(which); return CandleDqn::params_written(which); }
+    void arena_handed_out(int which) override { planes_stale(which); CandleDqn::arena_handed_out(which); }
+    void arena_escaped(int which) override { if (which == 0 || which == 1) cpl_escaped[which] = true; }
+    void arena_released(int which) override { if (which == 0 || which == 1) { cpl_escaped[which] = false; cpl_fresh[which] = false; } }
+    int32_t planes_ready(int set)
+    {
+        if (cpl_fresh[set] && !cpl_escaped[set]) return BDR_OK;
+        const float* w = set ? p_tgt : p;
+        Bracket br(this, "conv_planes");
+        BDR_HIP(step_launch(stream, false, k_conv_planes, dim3((512 * 64 + 576 * 64 + 255) / 256), dim3(256), w + conv.w2, w + conv.w3, cpl[set]));
+        cpl_fresh[set] = true;
+        return BDR_OK;
+    }
+    // the probes of the trunk (bdr_candle_dqn_probe 5 ... 7): the rows of the last forward, where its a3 lies, and whether a1 / a2 of
+    // instance 0 hold it (the image trunk stores them only under keep_layers)
+    bool keep_layers = false;
+    int fwd_rows = 0; const float* fwd_a3 = nullptr; bool fwd_a12 = false;
 
     bool cnn_form() const override { return true; }
     size_t conv_floats() const { return conv.w4; }
@@ -664,10 +730,26 @@ struct CandleDqnCnn : CandleDqn {
         return alloc(&part_conv, conv_dw_plan(conv, Bn).total, BATCH);
     }
     // the trunk of nz (parameters, u8 rows) pairs into a1 / a2 / a3 [0, nz): one launch per layer
+    // (BDR_ARITH_BF16X3_6: conv2 + conv3 of every instance in ONE launch of k_fwd_c23_b3, grid (Bn, 1, nz), from the sets' planes)
     int32_t trunk_forward(int nz, const float* const* pp, const uint8_t* const* rows, int Bn, const char* name)
     {
+        fwd_rows = 0;   // (the probes' state names this forward only once all of it is enqueued)
+        if (!b3()) {
+            BDR_TRY(trunk_conv1(this, conv, nz, pp, rows, a1, Bn, name));
+            BDR_TRY(trunk_conv23(this, conv, nz, pp, a1, a2, a3, Bn, name, name));
+            fwd_rows = Bn; fwd_a3 = a3[0]; fwd_a12 = true;
+            return BDR_OK;
+        }
+        for (int z = 0; z < nz; ++z) BDR_TRY(planes_ready(pp[z] == p ? 0 : 1));
         BDR_TRY(trunk_conv1(this, conv, nz, pp, rows, a1, Bn, name));
-        return trunk_conv23(this, conv, nz, pp, a1, a2, a3, Bn, name, name);
+        FwdC23Args c{};
+        for (int z = 0; z < nz; ++z) {
+            c.a1[z] = a1[z]; c.cpl[z] = cpl[pp[z] == p ? 0 : 1]; c.b2[z] = pp[z] + conv.b2; c.b3[z] = pp[z] + conv.b3; c.a2[z] = a2[z]; c.a3[z] = a3[z];
+        }
+        Bracket br(this, name);
+        BDR_HIP(launch_fwd_c23_b3(stream, Bn, nz, c));
+        fwd_rows = Bn; fwd_a3 = a3[0]; fwd_a12 = true;
+        return BDR_OK;
     }
     int32_t update_cnn(int Bn, const uint8_t* obs, const uint8_t* act, int act_bytes, const uint8_t* next_obs, const float* reward, const int8_t* term, bool track)
     {
@@ -712,7 +794,8 @@ struct CandleDqnCnn : CandleDqn {
             ra.track = track ? 1 : 0; ra.tau = (float)cfg.tau; ra.omt = (float)(1.0 - cfg.tau);
             ra.poison = dev_err + ERR_ACTION; ra.applied = applied; ra.step = step;
             Bracket br(this, "conv_reduce_adam");
-            BDR_HIP(step_launch(stream, true, k_cdqn_conv_reduce_adam, dim3((ra.n4 + 31) / 32), dim3(256), ra));
+            if (b3()) BDR_HIP(step_launch(stream, true, k_cdqn_conv_reduce_adam_planes, dim3((ra.n4 + 31) / 32), dim3(256), ra, cpl[0], cpl[1]));
+            else BDR_HIP(step_launch(stream, true, k_cdqn_conv_reduce_adam, dim3((ra.n4 + 31) / 32), dim3(256), ra));
         }
         last_B = Bn;
         return BDR_OK;
@@ -766,12 +849,21 @@ struct CandleDqnCnn : CandleDqn {
         } else st = acting_rows(obs, row_bytes(), n, &d);
         const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
         const float* hp = head(p);
-        if (st == BDR_OK) {
+        if (st == BDR_OK && b3()) st = planes_ready(0);
+        if (st == BDR_OK && b3()) {
+            CnnActTrunkB3Args t{d, stride, conv.ns, ((uintptr_t)d | stride) % 16 == 0 ? 1 : 0, p + conv.w1, p + conv.b1, cpl[0] + CPL_W2, p + conv.b2, cpl[0] + CPL_W3, p + conv.b3,
+                                img_feat, keep_layers ? a1[0] : nullptr, keep_layers ? a2[0] : nullptr};
+            Bracket br(this, "act_trunk");
+            const hipError_t e = launch_cnn_act_trunk_b3(stream, (int)n, t);
+            if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_cnn_act_trunk_b3: %s", hipGetErrorString(e));
+        } else if (st == BDR_OK) {
             CnnActTrunkArgs t{d, stride, conv.ns, ((uintptr_t)d | stride) % 16 == 0 ? 1 : 0, p + conv.w1, p + conv.b1, p + conv.w2, p + conv.b2, p + conv.w3, p + conv.b3, img_feat};
             Bracket br(this, "act_trunk");
             const hipError_t e = launch_cnn_act_trunk(stream, (int)n, t);
             if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_cnn_act_trunk: %s", hipGetErrorString(e));
         }
+        fwd_rows = 0;
+        if (st == BDR_OK) { fwd_rows = (int)n; fwd_a3 = img_feat; fwd_a12 = b3() && keep_layers; }
         if (st == BDR_OK) {
             CnnActHeadArgs h{img_feat, hp + l1.w, hp + l1.b, hp + l2.w, hp + l2.b, l2.Np, img_part, img_counters, (int)n, A, samp, samp_idx};
             Bracket br(this, "act_head");
@@ -873,8 +965,8 @@ int32_t cdqn_check(const bdr_candle_dqn_config& c)
 int32_t cdqn_cnn_check(const bdr_candle_dqn_cnn_config& c, bdr_candle_dqn_config* out)
 {
     BDR_REQUIRE(c.skip_linear == 0, "AtariCnnConfig::skip_linear = true leaves the 3136 features of conv3 as the output: Dqn needs out_dim action values (l1, l2)");
-    BDR_REQUIRE(c.arithmetic == BDR_ARITH_F32_EXACT, "DQN (candle, AtariCnn) computes exact f32 products in conv2 / conv3 (BDR_ARITH_F32_EXACT): the split-operand "
-                                                     "forward (BDR_ARITH_BF16X3_6) is the tch agent's (bdr_dqn_config)");
+    BDR_REQUIRE(c.arithmetic == BDR_ARITH_F32_EXACT, "DQN (candle, AtariCnn) is built with exact f32 products in conv2 / conv3 (BDR_ARITH_F32_EXACT): the split-operand "
+                                                     "forward (BDR_ARITH_BF16X3_6) is switched on on the built agent, bdr_candle_dqn_cnn_set_arithmetic");
     BDR_REQUIRE(c.n_stack >= 1 && c.n_stack <= bdr::C1_MAX_STACK, "AtariCnnConfig::n_stack must be in [1, %d] (conv1's kernels are instantiated per depth), got %d",
                 bdr::C1_MAX_STACK, c.n_stack);
     bdr_candle_dqn_config d;
@@ -1081,6 +1173,21 @@ int32_t bdr_candle_dqn_update_on_batch(bdr_agent* base, uint64_t n, const float*
     return a->err_check();
 }
 
+int32_t bdr_candle_dqn_cnn_set_arithmetic(bdr_agent* base, int32_t arithmetic)
+{
+    BDR_REQUIRE(base, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn") && static_cast<CandleDqn*>(base)->cnn_form(), "not a DQN (candle) agent with the AtariCnn Q-network");
+    return static_cast<CandleDqnCnn*>(base)->set_arithmetic(arithmetic);
+}
+
+int32_t bdr_candle_dqn_cnn_keep_layers(bdr_agent* base, int32_t on)
+{
+    BDR_REQUIRE(base, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn") && static_cast<CandleDqn*>(base)->cnn_form(), "not a DQN (candle) agent with the AtariCnn Q-network");
+    static_cast<CandleDqnCnn*>(base)->keep_layers = on != 0;
+    return BDR_OK;
+}
+
 // Parity probes of the LAST update (see include/border_amd.h)
 int32_t bdr_candle_dqn_probe(bdr_agent* base, int32_t what, float* out, uint64_t n)
 {
@@ -1088,8 +1195,21 @@ int32_t bdr_candle_dqn_probe(bdr_agent* base, int32_t what, float* out, uint64_t
     BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn"), "not a DQN (candle) agent");
     CandleDqn* a = static_cast<CandleDqn*>(base);
     BDR_HIP(hipSetDevice(a->device));
+    BDR_REQUIRE(what >= 0 && what <= 7, "unknown DQN (candle) probe %d", what);
+    if (what >= 5) {   // the trunk of the last forward, instance 0: a1, a2, a3
+        BDR_REQUIRE(a->cnn_form(), "probes 5 ... 7 are the conv activations of the AtariCnn Q-network: this agent has an Mlp");
+        CandleDqnCnn* c = static_cast<CandleDqnCnn*>(a);
+        BDR_REQUIRE(c->fwd_rows > 0, "no forward has run yet");
+        BDR_REQUIRE(what == 7 || c->fwd_a12, "the last forward was the image path's, which keeps a1 and a2 in LDS: bdr_candle_dqn_cnn_keep_layers(agent, 1) "
+                                             "(BDR_ARITH_BF16X3_6) makes its trunk store them");
+        const size_t row[3] = {CONV_A1_ROW, CONV_A2_ROW, CONV_A3_ROW};
+        const float* src3[3] = {c->a1[0], c->a2[0], c->fwd_a3};
+        BDR_REQUIRE(n == (uint64_t)c->fwd_rows * row[what - 5], "probe %d holds %d rows of %llu floats", what, c->fwd_rows, (unsigned long long)row[what - 5]);
+        BDR_HIP(hipStreamSynchronize(a->stream));
+        BDR_HIP(hipMemcpy(out, src3[what - 5], n * 4, hipMemcpyDeviceToHost));
+        return BDR_OK;
+    }
     BDR_REQUIRE(a->last_B > 0, "no update has run yet");
-    BDR_REQUIRE(what >= 0 && what <= 4, "unknown DQN (candle) probe %d", what);
     BDR_REQUIRE(n == (uint64_t)a->last_B, "this probe holds batch values");
     const float* src[5] = {a->pr_pred, a->pr_qn, a->pr_y, a->pr_tgt, a->pr_dpred};
     BDR_HIP(hipStreamSynchronize(a->stream));

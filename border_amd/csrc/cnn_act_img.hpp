@@ -3,6 +3,8 @@
 //
 //   k_cnn_act_trunk   one workgroup of four waves per observation row (grid = n): conv1, conv2 and conv3 of ONE image with every
 //                     activation in LDS; the output a3 goes to feat [n][3136] in (h, w, c) order, l1's internal input layout.
+//   k_cnn_act_trunk_b3  the trunk of BDR_ARITH_BF16X3_6 agents: conv2 / conv3 on the bf16 matrix cores with split operands (its own
+//                     header comment, below); same grid, same feat, same head.
 //   k_cnn_act_head    l1 (3136 -> 512, ReLU) cut as act_small.hpp cuts it - 16 column tiles x CAI_L1_KS k-slices, one partial
 //                     32 x 32 tile per workgroup (dense_small_tile), a counter per column tile, the last arriver adds the partials in
 //                     slice order - and, in the workgroup that completes the last column tile, l2 and dqn_q_argmax into the
@@ -79,7 +81,19 @@ struct CnnActHeadArgs {
     float* q; long long* idx;          // [n][A], [n]
 };
 
+// k_cnn_act_trunk_b3 (BDR_ARITH_BF16X3_6): W2 / W3 come as the parameter set's bf16 planes (fwd_c23_b3.hpp: CPL_W2, CPL_W3)
+struct CnnActTrunkB3Args {
+    const uint8_t* rows; size_t row_stride;
+    int ns, vec16;
+    const float *w1, *b1;
+    const uint16_t* pl2; const float* b2;     // [3][16][64][32]
+    const uint16_t* pl3; const float* b3;     // [3][18][64][32]
+    float* feat;                              // [n][3136]
+    float *keep_a1, *keep_a2;                 // null, or [n][20][20][32] and [n][9][9][64]: the probes' copies of a1 and a2
+};
+
 hipError_t launch_cnn_act_trunk(hipStream_t st, int n, const CnnActTrunkArgs& a);   // grid n
+hipError_t launch_cnn_act_trunk_b3(hipStream_t st, int n, const CnnActTrunkB3Args& a);   // grid n
 hipError_t launch_cnn_act_head(hipStream_t st, const CnnActHeadArgs& a);            // grid (16, CAI_L1_KS)
 
 }  // namespace bdr
@@ -88,6 +102,7 @@ hipError_t launch_cnn_act_head(hipStream_t st, const CnnActHeadArgs& a);        
 #include "conv1_bf16.hpp"
 #include "dense.hpp"
 #include "dense_act.hpp"
+#include "fwd_c23_b3.hpp"   // k_cnn_act_trunk_b3: the plane layouts (cpl_index, c23_a1_off, c23_a2_off) and split3_f32x4
 
 namespace bdr {
 
@@ -312,6 +327,275 @@ static __global__ __launch_bounds__(256) void k_cnn_act_trunk(CnnActTrunkArgs a)
     }
 }
 
+
+// ---- k_cnn_act_trunk_b3 -----------------------------------------------------------------------------------------------------------
+// The trunk of BDR_ARITH_BF16X3_6 agents: conv2 and conv3 on v_mfma_f32_32x32x16_bf16 with both operands split into three bf16 terms
+// (igemm_b3.hpp split3_rn / split3_f32x4) and six of the nine partial products kept.  One workgroup of four waves per frame stack, as
+// k_cnn_act_trunk; the data path is its own:
+//   conv1  k_cnn_act_trunk's (same units, same operand rule, same sums).  Its epilogue splits every run of four channels ONCE and
+//          leaves a1 in LDS as three bf16 planes in k_fwd_c23_b3's layout: four parity blocks (ih & 1, iw & 1) of [10][10] pixels of
+//          64 bytes, the four 16-byte chunks of pixel P at chunk ^ ((P >> 2) & 3) (c23_a1_off), so that the 16 lanes of a
+//          ds_read_b128 group read 16 different 16-byte slots.
+//   conv2  rows of the MFMA = 32 output channels, columns = 32 positions, column v = 10 oh + ow (ow = 9 is a hole: 89 columns in three
+//          tiles).  Six products per 16 k cost 192 matrix cycles where the FP32 MFMA costs 512, so the six tiles need NO k split:
+//          the waves take 2 / 2 / 1 / 1 tiles - wave 0 and wave 1 position tile 0 / 1 with both channel tiles, waves 2 and 3 position
+//          tile 2 with channel tile 0 / 1 - and the reduction area of the exact trunk is gone.  The epilogue (bias, ReLU) splits a2
+//          once into three planes [84 pixels][64] (chunk ^ ((P >> 1) & 7): c23_a2_off) that OVERLAY the frames, dead since conv1.
+//   conv3  2 x 2 tiles, one per wave: column v = 9 oh + ow (ow = 7, 8 and oh = 7 are holes: 63 columns in two tiles); a3 -> feat.
+//   A fragments (activations) are 16-byte LDS reads of the planes; B fragments (weights) go from the pre-split planes in L2 straight
+//   into registers as 16-byte pieces, in chunks (a k-tile of 32 = two MFMA steps) held in a ring of four (conv2) / three (conv3):
+//   a chunk's slot is refilled as soon as it has been multiplied, so three / two chunks are in flight ahead of the one in use (one
+//   chunk ahead left every chunk's ~0.3 us of matrix work waiting for a load from L2: 55 us against 41 us for the trunk at n = 1).
+//   Chunk 0 of conv2 AND of conv3, conv1's first channel and all three biases are requested before the frames are staged.
+// Summation order: every output element of conv2 / conv3 is ONE f32 accumulator that sees k ascending in steps of 16 in (kh, kw, c)
+// order, lane half h holding k = 8 h ... 8 h + 7 of a step, and per step the products (activation term, weight term) =
+// (2,0) (0,2) (1,1) (1,0) (0,1) (0,0) - ORD9[3..8] of k_igemm_b3, smallest first.  That is k_fwd_c23_b3's order: a2 is what the
+// layer path computes from the same a1, bit for bit, and a3 from the same a2.  (a1 itself differs from the layer path's in the
+// order of conv1's sums, as in the exact trunk.)
+// Registers: 254 VGPRs + 112 AGPRs, no scratch.  The 2-tile waves' conv2 ring alone is 4 chunks x 48 = 192 registers and the
+// allocator stops at 256 VGPRs, so there is no headroom: if a compiler change makes this kernel spill, a ring of three chunks for
+// conv2 (16 k-tiles: peel the last one) is the fallback, at some of the latency cover.
+// Hole columns read real or padding pixels (never written: any bit pattern) and are never stored; an MFMA column depends on its own
+// column of the operand only.
+// LDS (static, 139 392 bytes of the CU's 160 KB, whatever n_stack <= 8 is):
+//   s_fr  [56 448 bytes]  the frames as u8 [n_stack][84][84]; behind conv1's barrier a2's planes [3][84][64] bf16 (32 256 bytes)
+//   s_p1  [3][432][32]    a1's planes, bf16 (82 944 bytes)
+// Index bounds.
+//   frames, W1, conv1's units: k_cnn_act_trunk's.   s_p1 writes: position m < 400 = (ih, iw), pixel P = ((ih & 1) 2 + (iw & 1)) 108 +
+//           10 (ih >> 1) + (iw >> 1) <= 3 * 108 + 99, chunk q < 4, half h: u16 offset < 432 * 32 per plane.
+//   conv2:  column v = 32 pt + i <= 95, pixel v + 10 (kh >> 1) + (kw >> 1) <= 95 + 11 = 106 < 108 of block (kh & 1, kw & 1), chunk
+//           2 s + h < 4;  plane index cpl_index(32 kt + 16 s + 8 h, 32 ct + i) + 7 <= (15 * 64 + 63) 32 + 31 < 64 * 512;
+//           s_p2 writes at oh, ow < 9 only: pixel m <= 80, chunk 4 ct + q < 8;  keep_a2 row blockIdx.x < n, element m 64 + channel < 5 184.
+//   conv3:  column v = 32 pt + i <= 63, pixel v + 9 kh + kw <= 63 + 20 = 83 < 84, chunk 4 (kt & 1) + 2 s + h < 8;
+//           plane index <= (17 * 64 + 63) 32 + 31 < 64 * 576;  feat writes at oh, ow < 7: row blockIdx.x < n, element (7 oh + ow) 64 +
+//           32 ct + 8 q + 4 h + 3 < 3 136.   keep_a1 row blockIdx.x < n, element m 32 + channel < 12 800.
+constexpr int CAB_FRAME_BYTES = 7056 * C1_MAX_STACK;
+static_assert(3 * C23_PL_A2 * 2 <= CAB_FRAME_BYTES, "a2's planes overlay the frames");
+static_assert(CAB_FRAME_BYTES + 3 * C23_PL_A1 * 2 <= 160 * 1024, "one workgroup per CU");
+
+static __global__ __launch_bounds__(256) void k_cnn_act_trunk_b3(CnnActTrunkB3Args a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_fr[CAB_FRAME_BYTES / 4];
+    __shared__ __attribute__((aligned(16))) uint16_t s_p1[3 * C23_PL_A1];
+    uint16_t* const s_p2 = reinterpret_cast<uint16_t*>(s_fr);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 31, h = lane >> 5;
+    constexpr int ORD[6][2] = {{2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};   // (activation term, weight term)
+    // conv2: position tile pt2 and channel tiles ct2(0 ... nt2 - 1) of this wave; conv3: tile (pt3, ct3)
+    const int pt2 = min(wave, 2), nt2 = wave < 2 ? 2 : 1, ct2_0 = wave < 2 ? 0 : wave - 2;
+    const int pt3 = wave >> 1, ct3 = wave & 1;
+
+    // ---- every first operand, requested before anything is waited for
+    auto load_w1 = [&](int c, float (&w)[4][8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) w[sl][j] = a.w1[(size_t)(64 * c + 16 * sl + 8 * h + j) * 32 + i];
+    };
+    // chunk kt of conv2: the fragments of its two k-steps, this wave's channel tiles, three planes: 8 bf16 at cpl_index(32 kt + 16 s + 8 h, n)
+    auto load_w2 = [&](int kt, bf16x8_t (&w)[2][2][3]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+                if (tn < nt2)   // wave-uniform
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl)
+                        w[s][tn][pl] = *reinterpret_cast<const bf16x8_t*>(a.pl2 + (size_t)pl * (64 * 512) + cpl_index(32 * kt + 16 * s + 8 * h, 32 * (ct2_0 + tn) + i));
+    };
+    auto load_w3 = [&](int kt, bf16x8_t (&w)[2][3]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+                w[s][pl] = *reinterpret_cast<const bf16x8_t*>(a.pl3 + (size_t)pl * (64 * 576) + cpl_index(32 * kt + 16 * s + 8 * h, 32 * ct3 + i));
+    };
+    float w1n[4][8];
+    bf16x8_t w2b[4][2][2][3], w3b[3][2][3];   // rings of four / three chunks: a chunk is requested three / two chunks before it is multiplied
+    load_w1(0, w1n);
+    f32x4 bq1[4], bq2[2][4], bq3[4];   // the bias of this lane's channel runs [8 q + 4 h, + 4) of each of its tiles
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bq1[q] = *reinterpret_cast<const f32x4*>(a.b1 + 8 * q + 4 * h);
+    load_w2(0, w2b[0]);
+    load_w3(0, w3b[0]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+            if (tn < nt2) bq2[tn][q] = *reinterpret_cast<const f32x4*>(a.b2 + 32 * (ct2_0 + tn) + 8 * q + 4 * h);
+        bq3[q] = *reinterpret_cast<const f32x4*>(a.b3 + 32 * ct3 + 8 * q + 4 * h);
+    }
+
+    // ---- the frame stack -> LDS, as it is (u8)
+    {
+        const uint8_t* src = a.rows + (size_t)blockIdx.x * a.row_stride;
+        if (a.vec16) cai_stage(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(s_fr), a.ns * 441, tid);
+        else cai_stage(reinterpret_cast<const uint32_t*>(src), s_fr, a.ns * 1764, tid);
+    }
+    __syncthreads();
+
+    // ---- conv1 (k_cnn_act_trunk's k loop); the epilogue leaves a1 split in s_p1
+    {
+        const int nu = wave == 0 ? 4 : 3;
+        const uint8_t* frb = reinterpret_cast<const uint8_t*>(s_fr);
+        int poff[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int m = min((wave + 4 * t) * 32 + i, 399), oh = m / 20, ow = m - oh * 20;
+            poff[t] = (oh * 4 + h) * 84 + ow * 4;
+        }
+        f32x16 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        for (int c = 0; c < a.ns; ++c) {
+            float wc[4][8];
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) wc[sl][j] = w1n[sl][j];
+            if (c + 1 < a.ns) load_w1(c + 1, w1n);
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl) {
+                uint32_t hi[8], mid[8], lo[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    hi[j] = __float_as_uint(wc[sl][j]) & 0xffff0000u;
+                    const float r1 = wc[sl][j] - __uint_as_float(hi[j]);    // exact
+                    mid[j] = __float_as_uint(r1) & 0xffff0000u;
+                    const float r2 = r1 - __uint_as_float(mid[j]);          // exact, <= 8 significant bits
+                    lo[j] = __float_as_uint(r2) & 0xffff0000u;
+                }
+                bf16x8 wp[3];
+                wp[0] = __builtin_bit_cast(bf16x8, uint4{(hi[0] >> 16) | hi[1], (hi[2] >> 16) | hi[3], (hi[4] >> 16) | hi[5], (hi[6] >> 16) | hi[7]});
+                wp[1] = __builtin_bit_cast(bf16x8, uint4{(mid[0] >> 16) | mid[1], (mid[2] >> 16) | mid[3], (mid[4] >> 16) | mid[5], (mid[6] >> 16) | mid[7]});
+                wp[2] = __builtin_bit_cast(bf16x8, uint4{(lo[0] >> 16) | lo[1], (lo[2] >> 16) | lo[3], (lo[4] >> 16) | lo[5], (lo[6] >> 16) | lo[7]});
+                const int so = c * 7056 + (2 * sl) * 84;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    if (t < nu) {   // wave-uniform
+                        const uint32_t* px = reinterpret_cast<const uint32_t*>(frb + poff[t] + so);
+                        const bf16x8 fa = u8x8_to_bf16(px[0], px[1]);
+#pragma unroll
+                        for (int pl = 2; pl >= 0; --pl) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[pl], fa, acc[t], 0, 0, 0);   // small terms first
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int m = (wave + 4 * t) * 32 + i;
+            if (t < nu && m < 400) {
+                const int ih = m / 20, iw = m - ih * 20;
+                const int P = ((ih & 1) * 2 + (iw & 1)) * C23_A1_BLK + (ih >> 1) * 10 + (iw >> 1);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const float x = acc[t][4 * q + e] * (1.0f / 255.0f) + bq1[q][e]; v[e] = x > 0.f ? x : 0.f; }
+                    u32x2_t sp[3];
+                    split3_f32x4(v, sp);
+                    const int o = c23_a1_off(P, q) + 4 * h;
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x2_t*>(&s_p1[pl * C23_PL_A1 + o]) = sp[pl];
+                    if (a.keep_a1) *reinterpret_cast<f32x4*>(a.keep_a1 + ((size_t)blockIdx.x * 400 + m) * 32 + 8 * q + 4 * h) = v;   // workgroup-uniform
+                }
+            }
+        }
+    }
+    __syncthreads();   // a1's planes are whole; nobody reads the frames any more: a2's planes may overlay them
+
+    // ---- conv2: position tile pt2, channel tiles ct2_0 ... of this wave, all 16 k-tiles (taps) in order
+    {
+        const int v = pt2 * 32 + i;
+        f32x16 acc[2];
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tn][r] = 0.f;
+#pragma unroll
+        for (int u = 1; u < 4; ++u) load_w2(u, w2b[u]);
+        for (int kt0 = 0; kt0 < 16; kt0 += 4) {   // kernel row kh = kt0 >> 2; ring slot u = kw
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int kh = kt0 >> 2, kw = u;
+                const int P = ((kh & 1) * 2 + (kw & 1)) * C23_A1_BLK + v + 10 * (kh >> 1) + (kw >> 1);
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    bf16x8_t fx[3];
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) fx[pl] = *reinterpret_cast<const bf16x8_t*>(&s_p1[pl * C23_PL_A1 + c23_a1_off(P, 2 * s + h)]);
+#pragma unroll
+                    for (int t = 0; t < 6; ++t)
+#pragma unroll
+                        for (int tn = 0; tn < 2; ++tn)
+                            if (tn < nt2) acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2b[u][s][tn][ORD[t][1]], fx[ORD[t][0]], acc[tn], 0, 0, 0);
+                }
+                if (kt0 + 4 < 16) load_w2(kt0 + 4 + u, w2b[u]);   // (kt0 + 4 + u <= 15)
+            }
+        }
+#pragma unroll
+        for (int u = 1; u < 3; ++u) load_w3(u, w3b[u]);   // in flight across the epilogue and the barrier
+        const int oh = v / 10, ow = v - 10 * oh;
+        if (oh < 9 && ow < 9) {
+            const int m = oh * 9 + ow;
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+                if (tn < nt2) {
+                    const int ct = ct2_0 + tn;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        f32x4 y;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { const float t = acc[tn][4 * q + e] + bq2[tn][q][e]; y[e] = t > 0.f ? t : 0.f; }
+                        u32x2_t sp[3];
+                        split3_f32x4(y, sp);
+                        const int o = c23_a2_off(m, 4 * ct + q) + 4 * h;
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x2_t*>(&s_p2[pl * C23_PL_A2 + o]) = sp[pl];
+                        if (a.keep_a2) *reinterpret_cast<f32x4*>(a.keep_a2 + ((size_t)blockIdx.x * 81 + m) * 64 + 32 * ct + 8 * q + 4 * h) = y;
+                    }
+                }
+        }
+    }
+    __syncthreads();   // a2's planes are whole
+
+    // ---- conv3: tile (pt3, ct3), all 18 k-tiles (half taps) in order
+    {
+        const int v = pt3 * 32 + i;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int kt0 = 0; kt0 < 18; kt0 += 3) {
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                const int kt = kt0 + u, tap = kt >> 1, kh = tap / 3, kw = tap - 3 * kh, P = v + 9 * kh + kw;
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    bf16x8_t fx[3];
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) fx[pl] = *reinterpret_cast<const bf16x8_t*>(&s_p2[pl * C23_PL_A2 + c23_a2_off(P, (kt & 1) * 4 + 2 * s + h)]);
+#pragma unroll
+                    for (int t = 0; t < 6; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w3b[u][s][ORD[t][1]], fx[ORD[t][0]], acc, 0, 0, 0);
+                }
+                if (kt0 + 3 < 18) load_w3(kt + 3, w3b[u]);   // (kt + 3 <= 17)
+            }
+        }
+        const int oh = v / 9, ow = v - 9 * oh;
+        if (oh < 7 && ow < 7) {
+            float* out = a.feat + (size_t)blockIdx.x * 3136 + (oh * 7 + ow) * 64 + 32 * ct3 + 4 * h;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                f32x4 y;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { const float t = acc[4 * q + e] + bq3[q][e]; y[e] = t > 0.f ? t : 0.f; }
+                *reinterpret_cast<f32x4*>(out + 8 * q) = y;
+            }
+        }
+    }
+}
+
 // grid (16, CAI_L1_KS)
 static __global__ __launch_bounds__(256) void k_cnn_act_head(CnnActHeadArgs a)
 {
@@ -390,6 +674,10 @@ static __global__ __launch_bounds__(256) void k_cnn_act_head(CnnActHeadArgs a)
 hipError_t launch_cnn_act_trunk(hipStream_t st, int n, const CnnActTrunkArgs& a)
 {
     return step_launch(st, false, k_cnn_act_trunk, dim3((unsigned)n), dim3(256), a);
+}
+hipError_t launch_cnn_act_trunk_b3(hipStream_t st, int n, const CnnActTrunkB3Args& a)
+{
+    return step_launch(st, false, k_cnn_act_trunk_b3, dim3((unsigned)n), dim3(256), a);
 }
 hipError_t launch_cnn_act_head(hipStream_t st, const CnnActHeadArgs& a)
 {

@@ -1721,7 +1721,12 @@ BDR_API int32_t bdr_candle_dqn_update_on_batch(bdr_agent* a, uint64_t n, const f
 /* Parity probes: intermediates of the LAST update, to the host, each [B] floats.  what:
  *   0 pred   Q(obs)[act] (:80-86)                    1 q_next  the gathered target value (:101-111)
  *   2 y      the argmax index as a float (:103, :108)  3 tgt   the TD target (:113)
- *   4 dpred  dLoss / dpred, 1/B included (the gradient of the output itself: an output ReLU's mask is applied behind it) */
+ *   4 dpred  dLoss / dpred, 1/B included (the gradient of the output itself: an output ReLU's mask is applied behind it)
+ * AtariCnn form only, the trunk of instance 0 (qnet on obs) of the LAST FORWARD that ran - an update, or an acting call; n is then the
+ * number of floats, rows x the row below, rows = the batch of that update or the rows of that call:
+ *   5 a1 [rows][20][20][32]      6 a2 [rows][9][9][64]      7 a3 [rows][7][7][64]
+ * After an acting call on BDR_ACT_PATH_IMAGE, 7 is that path's feature rows; 5 and 6 exist only for a BDR_ARITH_BF16X3_6 agent under
+ * bdr_candle_dqn_cnn_keep_layers (the exact image trunk keeps a1 and a2 in LDS): BDR_ERR_INVALID otherwise. */
 BDR_API int32_t bdr_candle_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
 /* ---- the same agent with the candle crate's AtariCnn Q-network (border-candle-agent/src/atari_cnn/base.rs:31-45) ----
  * conv1 8x8/4 (n_stack -> 32), conv2 4x4/2 (-> 64), conv3 3x3/1 (-> 64), ReLU after each, flatten (c, h, w), l1 3136 -> 512, ReLU,
@@ -1731,8 +1736,8 @@ BDR_API int32_t bdr_candle_dqn_probe(bdr_agent* a, int32_t what, float* out, uin
  * l2.bias - also the order of the parameter models (0 qnet, 1 qnet_tgt, 2 exp_avg, 3 exp_avg_sq, 4 gradient; +100 / +200 / +300).
  * The fields are those of bdr_candle_dqn_config with AtariCnnConfig's n_stack / out_dim / skip_linear in place of obs_dim / qnet.
  * skip_linear != 0 is refused (Dqn needs out_dim action values).  arithmetic: BDR_ARITH_F32_EXACT only (conv1 on the bf16 MFMA with
- * exact u8 operands, every other product f32 x f32); BDR_ARITH_BF16X3_6 is refused - the split-operand forward belongs to the tch
- * agent.  Everything said about bdr_candle_dqn_config's agent holds: update order, records, explorers on the SmallRng, the
+ * exact u8 operands, every other product f32 x f32); BDR_ARITH_BF16X3_6 is refused HERE - an agent is built exact, and
+ * bdr_candle_dqn_cnn_set_arithmetic (below) switches a built agent to the split-operand forward.  Everything said about bdr_candle_dqn_config's agent holds: update order, records, explorers on the SmallRng, the
  * out-of-range action rule (no parameter of the update steps, conv layers included), checkpoints.  bdr_agent_opt reads a u8 ring
  * (obs_bytes = 84 * 84 * n_stack, act_bytes = 8; a frame-stack store is accepted); an f32 ring, another row size, another device or
  * a prioritized ring returns BDR_ERR_INVALID.  bdr_agent_sample / _qvalues take u8 host rows, the _device forms rows such as
@@ -1742,7 +1747,7 @@ typedef struct {
     int32_t n_stack;                /* AtariCnnConfig.n_stack: 1 ... 8 */
     int32_t out_dim;                /* AtariCnnConfig.out_dim = the number of actions */
     int32_t skip_linear;            /* AtariCnnConfig.skip_linear: must be 0 */
-    int32_t arithmetic;             /* BDR_ARITH_F32_EXACT */
+    int32_t arithmetic;             /* BDR_ARITH_F32_EXACT; the split-operand forward: bdr_candle_dqn_cnn_set_arithmetic */
     bdr_adamw_config opt;           /* DqnModelConfig.opt_config */
     double lr;
     uint64_t soft_update_interval;  /* 1 */
@@ -1770,6 +1775,20 @@ BDR_API int32_t bdr_candle_dqn_cnn_create(const bdr_candle_dqn_cnn_config* cfg, 
 BDR_API int32_t bdr_candle_dqn_cnn_update_on_batch(bdr_agent* a, uint64_t n, const uint8_t* obs, const int64_t* act, const uint8_t* next_obs,
                                                    const float* reward, const int8_t* is_terminated, const int8_t* is_truncated,
                                                    bdr_dqn_record* rec);
+/* The arithmetic of conv2 / conv3 FORWARD of a built agent: BDR_ARITH_F32_EXACT (what bdr_candle_dqn_cnn_create builds) or
+ * BDR_ARITH_BF16X3_6 - both operands split into three bf16 terms, six of the nine products kept, on v_mfma_f32_32x32x16_bf16: in the
+ * update (conv2 + conv3 of all instances in one launch, 15 launches per update), on the layer acting path (the same kernel) and on
+ * BDR_ACT_PATH_IMAGE (k_cnn_act_trunk_b3).  conv1, the head, every backward kernel and the optimizer arithmetic stay the exact
+ * agent's.  The agent then keeps bf16 planes of W2 / W3 beside qnet and qnet_tgt: the conv optimizer launch re-splits what it steps,
+ * every other writer of conv parameters marks the set stale and the next forward re-splits it (one extra launch, only then).  May be
+ * called at any time between calls and goes ONE way, exact -> split (the value the agent already has is accepted and does nothing;
+ * BDR_ARITH_F32_EXACT on a split agent is BDR_ERR_INVALID); any other value, an Mlp-form agent and a member of a live group return
+ * BDR_ERR_INVALID (an agent of BDR_ARITH_BF16X3_6 joins no bdr_candle_dqn_cnn_group). */
+BDR_API int32_t bdr_candle_dqn_cnn_set_arithmetic(bdr_agent* a, int32_t arithmetic);
+/* on != 0: the image-path trunk of a BDR_ARITH_BF16X3_6 agent (BDR_ACT_PATH_IMAGE) also stores a1 and a2 of every row to the buffers
+ * probes 5 and 6 read, behind a workgroup-uniform branch; off (the default) it stores nothing extra.  Accepted and without effect on a
+ * BDR_ARITH_F32_EXACT agent.  (bdr_sac_keep_layers is the precedent.) */
+BDR_API int32_t bdr_candle_dqn_cnn_keep_layers(bdr_agent* a, int32_t on);
 /* Policy::sample (dqn/base.rs:202-230) goes through bdr_agent_sample / _sample_device / _sample_raw (idx_out) and the action values
  * through bdr_agent_qvalues / _qvalues_device.  The exploration stream of this kind is the reference's SmallRng (xoshiro256++ seeded
  * by rand_core's seed_from_u64; DESIGN.md 17 states the rules, which nothing here can pin against rand itself):

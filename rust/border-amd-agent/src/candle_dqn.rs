@@ -67,6 +67,12 @@ where
         self.a.sync()
     }
 
+    /// `bdr_candle_dqn_cnn_set_arithmetic` (AtariCnn form): `Arithmetic::Bf16x3` switches the built agent to the split-operand
+    /// conv2 / conv3 forward on the bf16 matrix cores, in the update and when acting.  One way: a split agent stays split.
+    pub fn set_arithmetic(&mut self, arithmetic: crate::config::Arithmetic) -> Result<()> {
+        crate::error::check(unsafe { ffi::bdr_candle_dqn_cnn_set_arithmetic(self.a.h, arithmetic.code()) })
+    }
+
     /// `<stem>.safetensors` instead of the reference's `<stem>.pt` (both hold safetensors).
     pub fn set_checkpoint_format(&mut self, safetensors: bool) -> Result<()> {
         self.a.set_checkpoint_format(safetensors)

@@ -1684,12 +1684,21 @@ pub struct CandleDqnAtariCnnConfig {
     pub out_dim: i64,
     #[serde(default)]
     pub skip_linear: bool,
+    /// `bdr_candle_dqn_cnn_config::arithmetic` (not a reference field; absent in a reference YAML -> `F32Exact`).  As in the Python
+    /// binding it takes ONE value: the library builds every agent exact and refuses `Bf16x3` here, naming the switch on the built
+    /// agent, `AmdCandleDqn::set_arithmetic(Arithmetic::Bf16x3)`.
+    #[serde(default = "candle_cnn_arithmetic")]
+    pub arithmetic: Arithmetic,
     pub dqn: CandleDqnConfig,
+}
+
+fn candle_cnn_arithmetic() -> Arithmetic {
+    Arithmetic::F32Exact
 }
 
 impl Default for CandleDqnAtariCnnConfig {
     fn default() -> Self {
-        Self { n_stack: 4, out_dim: 0, skip_linear: false, dqn: Default::default() }
+        Self { n_stack: 4, out_dim: 0, skip_linear: false, arithmetic: candle_cnn_arithmetic(), dqn: Default::default() }
     }
 }
 
@@ -1697,6 +1706,7 @@ impl CandleDqnAtariCnnConfig {
     setter!(n_stack, i64);
     setter!(out_dim, i64);
     setter!(skip_linear, bool);
+    setter!(arithmetic, Arithmetic);
     setter!(dqn, CandleDqnConfig);
     yaml_io!();
 
@@ -1707,6 +1717,7 @@ impl CandleDqnAtariCnnConfig {
         c.n_stack = self.n_stack as i32;
         c.out_dim = self.out_dim as i32;
         c.skip_linear = self.skip_linear as i32;
+        c.arithmetic = self.arithmetic.code();
         c.lr = d.model_config.opt_config.lr();
         d.model_config.opt_config.fill(&mut c.opt);
         c.soft_update_interval = d.soft_update_interval as u64;

@@ -1621,6 +1621,8 @@ extern "C" {
     pub fn bdr_candle_dqn_probe(a: *mut bdr_agent, what: i32, out: *mut f32, n: u64) -> i32;
     pub fn bdr_candle_dqn_cnn_config_default(cfg: *mut bdr_candle_dqn_cnn_config);
     pub fn bdr_candle_dqn_cnn_create(cfg: *const bdr_candle_dqn_cnn_config, out: *mut *mut bdr_agent) -> i32;
+    pub fn bdr_candle_dqn_cnn_set_arithmetic(a: *mut bdr_agent, arithmetic: i32) -> i32;
+    pub fn bdr_candle_dqn_cnn_keep_layers(a: *mut bdr_agent, on: i32) -> i32;
     pub fn bdr_candle_dqn_cnn_update_on_batch(
         a: *mut bdr_agent,
         n: u64,

@@ -18,6 +18,11 @@ action back) at n = 1 and n = 8 on the act paths "layers" and "image" (csrc/cnn_
 one process: after a warm-up of both, five rounds of 1 000 calls per path; median and spread of the rounds, and the per-launch times
 of one call from the profile brackets.  Writes profiles/bench_candle_dqn_cnn_act.json.  The bar: at n = 1 the worst "image" round is
 not slower than the best "layers" round of the same run.
+
+--cnn --arithmetic both: the candle agent as built ("f32_exact") and after set_arithmetic("bf16x3_6"), legs alternating in one process, no tch agent,
+at B = 32 and B = 256; writes profiles/bench_candle_dqn_cnn_b3.json and says whether the worst split leg beats the best exact leg.
+With --act: exact layers, exact image, split layers, split image alternating at n = 1 and 8 (profiles/bench_candle_dqn_cnn_act_b3.json).
+--arithmetic f32_exact | bf16x3_6 alone sets that arithmetic on the candle agent of the other runs.  No speed bar.
 """
 from __future__ import annotations
 
@@ -102,12 +107,15 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="--cnn: 32 (dqn_atari) or 256 (the C2 batch)")
     ap.add_argument("--no-tch", action="store_true")
     ap.add_argument("--act", action="store_true", help="--cnn: the acting-call latency of the act paths instead of the update rate")
+    ap.add_argument("--arithmetic", choices=("f32_exact", "bf16x3_6", "both"), default="f32_exact", help="--cnn: the candle agent's arithmetic; both: exact against split")
     args = ap.parse_args()
     if args.out is None:
         stem = "bench_candle_dqn" if not args.cnn else "bench_candle_dqn_cnn" + ("" if args.batch == 32 else f"_b{args.batch}")
         args.out = os.path.join(ROOT, "profiles", stem + ".json")
     if args.cnn and args.act:
         return main_cnn_act(args)
+    if args.cnn and args.arithmetic == "both":
+        return main_cnn_both(args)
     if args.cnn:
         return main_cnn(args)
 
@@ -152,6 +160,8 @@ def main_cnn(args):
     NS, NA = 4, 6
     spec = RC.CandleDqnCnnSpec(NS, NA, lr=1e-3, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01), double_dqn=args.double_dqn)
     pairs = [("candle_dqn_cnn", B.CandleDqn.build(spec.to_config(B, args.batch, device=0, seed=1)), ring_u8(B, NS))]
+    if args.arithmetic != "f32_exact":   # (the exact line is an agent nobody touched)
+        pairs[0][1].set_arithmetic(args.arithmetic)
     if not args.no_tch:
         tch = B.Dqn.build(B.DqnConfig(model_config=B.DqnModelConfig(B.AtariCnnConfig(NS, NA), B.OptimizerConfig.AdamW(1e-3, wd=0.01)),
                                       batch_size=args.batch, double_dqn=args.double_dqn, device=0, param_seed=1, arithmetic="f32_exact"))
@@ -186,13 +196,50 @@ def main_cnn(args):
     print(line)
 
 
+def main_cnn_both(args):
+    import border_amd as B
+    import candle_dqn_cnn_restatement as RC
+    NS, NA, ARITH = 4, 6, ("f32_exact", "bf16x3_6")
+    spec = RC.CandleDqnCnnSpec(NS, NA, lr=1e-3, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01), double_dqn=args.double_dqn)
+    out = {"metric": "dqn_atari_candle_updates_per_s_by_arithmetic", "shape": {"n_stack": NS, "n_actions": NA, "opt": "AdamW", "loss": "Mse",
+                                                                                "double_dqn": bool(args.double_dqn)}, "warmup": args.warmup, "steps": args.steps}
+    for bsz in (32, 256):
+        pairs = [(ar, B.CandleDqn.build(spec.to_config(B, bsz, device=0, seed=1)), ring_u8(B, NS)) for ar in ARITH]
+        pairs[1][1].set_arithmetic(ARITH[1])
+        res = {ar: {"value": round(window(agent, rb, args.warmup, args.steps), 1)} for ar, agent, rb in pairs}
+        legs = {ar: [] for ar in ARITH}
+        for _ in range(args.legs):
+            for ar, agent, rb in pairs:
+                legs[ar].append(leg(agent, rb))
+        for ar, agent, rb in pairs:
+            v = sorted(legs[ar])
+            res[ar].update(ms_per_update=round(1e3 / res[ar]["value"], 4), steady_legs_updates_per_s=[round(x, 1) for x in legs[ar]],
+                           steady_median=round(v[len(v) // 2], 1), steady_spread_pct=round(100.0 * (v[-1] - v[0]) / v[len(v) // 2], 2), **launches(agent, rb))
+            agent.close(); rb.close()
+        res["split_over_exact_steady_median"] = round(res["bf16x3_6"]["steady_median"] / res["f32_exact"]["steady_median"], 4)
+        res["worst_split_leg_beats_best_exact_leg"] = bool(min(legs["bf16x3_6"]) > max(legs["f32_exact"]))
+        out[f"b{bsz}"] = res
+    out["value"] = out["b32"]["bf16x3_6"]["value"]
+    line = json.dumps(out)
+    path = os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_b3.json")
+    with open(path, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main_cnn_act(args, rounds=5, calls=1000):
     import border_amd as B
     import candle_dqn_cnn_restatement as RC
     from bench import read_profile
     NS, NA, PATHS = 4, 6, ("layers", "image")
     spec = RC.CandleDqnCnnSpec(NS, NA, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01))
-    build = lambda: B.CandleDqn.build(spec.to_config(B, 32, device=0, seed=1, train=True, explorer=B.EpsilonGreedy(eps_start=0.02, eps_final=0.02, final_step=1)))
+    if args.arithmetic == "both":
+        return main_cnn_act_both(args, spec, rounds, calls)
+    def build():
+        a = B.CandleDqn.build(spec.to_config(B, 32, device=0, seed=1, train=True, explorer=B.EpsilonGreedy(eps_start=0.02, eps_final=0.02, final_step=1)))
+        if args.arithmetic != "f32_exact":
+            a.set_arithmetic(args.arithmetic)
+        return a
     a = build()
     res = {}
     for n in (1, 8):
@@ -235,6 +282,63 @@ def main_cnn_act(args, rounds=5, calls=1000):
     path = os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_act.json")
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+def main_cnn_act_both(args, spec, rounds, calls):
+    """exact layers, exact image, split layers, split image: one agent per arithmetic, the four forms alternating round by round"""
+    import border_amd as B
+    from bench import read_profile
+    NS, NA = spec.n_stack, spec.n_actions
+    FORMS = [(ar, p) for ar in ("f32_exact", "bf16x3_6") for p in ("layers", "image")]
+    def build(ar):
+        a = B.CandleDqn.build(spec.to_config(B, 32, device=0, seed=1, train=True, explorer=B.EpsilonGreedy(eps_start=0.02, eps_final=0.02, final_step=1)))
+        if ar != "f32_exact":
+            a.set_arithmetic(ar)
+        return a
+    agents = {ar: build(ar) for ar in ("f32_exact", "bf16x3_6")}
+    res = {}
+    for n in (1, 8):
+        obs = np.random.default_rng(n).integers(0, 256, (n, 84 * 84 * NS), dtype=np.uint8)
+        us = {f: [] for f in FORMS}
+        for ar, p in FORMS:
+            agents[ar].set_act_path(p)
+            for _ in range(200):
+                agents[ar].sample(obs)
+        for _ in range(rounds):
+            for ar, p in FORMS:
+                agents[ar].set_act_path(p)
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    agents[ar].sample(obs)
+                us[(ar, p)].append(1e6 * (time.perf_counter() - t0) / calls)
+        r = {}
+        for ar, p in FORMS:
+            v = sorted(us[(ar, p)])
+            b = build(ar)
+            b.set_act_path(p)
+            for _ in range(20):
+                b.sample(obs)
+            b.profile_enable(True)
+            for _ in range(100):
+                b.sample(obs)
+            slots = read_profile(b)
+            b.profile_enable(False)
+            b.close()
+            r[f"{ar}_{p}"] = {"us_per_call_rounds": [round(x, 2) for x in us[(ar, p)]], "median_us": round(v[len(v) // 2], 2),
+                              "spread_pct": round(100.0 * (v[-1] - v[0]) / v[len(v) // 2], 2), "best_us": round(v[0], 2), "worst_us": round(v[-1], 2),
+                              "profile_brackets_us": [[l, round(1e3 * ms, 2)] for l, ms in slots if l != "_null"]}
+        for p in ("layers", "image"):
+            r[f"worst_split_{p}_beats_best_exact_{p}"] = bool(r[f"bf16x3_6_{p}"]["worst_us"] < r[f"f32_exact_{p}"]["best_us"])
+        r["worst_split_image_beats_best_split_layers"] = bool(r["bf16x3_6_image"]["worst_us"] < r["bf16x3_6_layers"]["best_us"])
+        res[f"n{n}"] = r
+    for a in agents.values():
+        a.close()
+    out = {"metric": "dqn_atari_candle_sample_us_per_call_by_arithmetic", "shape": {"n_stack": NS, "n_actions": NA, "rows": "host u8"}, "rounds": rounds,
+           "calls_per_round": calls, "value": res["n1"]["bf16x3_6_image"]["median_us"], **res}
+    line = json.dumps(out)
+    with open(os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_act_b3.json"), "w") as f:
         f.write(line + "\n")
     print(line)
 
