@@ -156,7 +156,12 @@ class CandleDqn(DenseHandle):
 
     def probe(self, what: str, batch: int) -> np.ndarray:
         """Intermediates of the last update (bdr_candle_dqn_probe), each [B]: pred, q_next, y (the argmax index), tgt, dpred.
-        AtariCnn form: a1, a2, a3 of instance 0 of the last forward (an update or an acting call of `batch` rows), [batch][H][W][C]."""
+        AtariCnn form: a1, a2, a3 of instance 0 of the last forward (an update or an acting call of `batch` rows), [batch][H][W][C],
+        and its head under either head form: h1 [batch][512], q [batch][n_actions]."""
+        if what in ("h1", "q"):
+            out = np.empty((batch, 512 if what == "h1" else self.n_actions), np.float32)
+            _lib.check(_lib.lib().bdr_candle_dqn_probe(self._h, 8 if what == "h1" else 9, _p(out), out.size))
+            return out
         if what in self.LAYER_PROBES:
             code, shape = self.LAYER_PROBES[what]
             out = np.empty((batch,) + shape, np.float32)
@@ -170,6 +175,11 @@ class CandleDqn(DenseHandle):
         """bdr_candle_dqn_cnn_set_arithmetic (AtariCnn form): "bf16x3_6" - conv2 / conv3 forward with split operands on the bf16
         matrix cores, in the update and on both acting paths.  One way: a split agent stays split."""
         _lib.check(_lib.lib().bdr_candle_dqn_cnn_set_arithmetic(self._h, _lib.ARITHMETIC[arithmetic]))
+
+    def set_head_form(self, form: str) -> None:
+        """bdr_candle_dqn_cnn_set_head_form (AtariCnn form): "splitk" - l1 + l2 of every instance in one split-k launch, in the update
+        and on the layer acting path: the small-batch form; "layers" - one launch per layer, what an agent is built with.  Both ways."""
+        _lib.check(_lib.lib().bdr_candle_dqn_cnn_set_head_form(self._h, _lib.HEAD_FORM[form]))
 
     def keep_layers(self, on: bool = True) -> None:
         """bdr_candle_dqn_cnn_keep_layers: the image-path trunk of a "bf16x3_6" agent also stores a1 and a2 for probe()."""

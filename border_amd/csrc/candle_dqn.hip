@@ -22,6 +22,7 @@
 #include "candle_actor.hpp"
 #include "conv_trunk.hpp"
 #include "cnn_act_img.hpp"
+#include "cdqn_head_fwd.hpp"
 #include "candle_dqn_group_plan.hpp"
 
 using namespace bdr;
@@ -713,6 +714,50 @@ struct CandleDqnCnn : CandleDqn {
     // instance 0 hold it (the image trunk stores them only under keep_layers)
     bool keep_layers = false;
     int fwd_rows = 0; const float* fwd_a3 = nullptr; bool fwd_a12 = false;
+    bool fwd_head = false;   // probes 8 / 9: a_on holds h1 and q of the last forward (the image path's head keeps them in its own buffers)
+
+    // BDR_HEAD_FORM_SPLITK (bdr_candle_dqn_cnn_set_head_form on a built agent; the constructor builds BDR_HEAD_FORM_LAYERS): l1 + l2 of
+    // every instance in ONE launch of k_cdqn_head_fwd (cdqn_head_fwd.hpp) in the update and on the layer acting path.  No state belongs
+    // to a form: the switch goes both ways.  The partial tiles and the counters live as long as the batch buffers and are allocated by
+    // the first forward that needs them (zeroed: the counters start at zero and every launch leaves them so).
+    int head_form = BDR_HEAD_FORM_LAYERS;
+    float* hf_part = nullptr; unsigned* hf_counters = nullptr;
+    int32_t set_head_form(int32_t form)
+    {
+        BDR_REQUIRE(form == BDR_HEAD_FORM_LAYERS || form == BDR_HEAD_FORM_SPLITK, "DQN (candle, AtariCnn): unknown head form %d (BDR_HEAD_FORM_LAYERS or BDR_HEAD_FORM_SPLITK)", form);
+        if (form == head_form) return BDR_OK;
+        BDR_REQUIRE(!group, "this agent is a member of a group: the grouped round is built for BDR_HEAD_FORM_LAYERS members, and a member's head form is fixed");
+        head_form = form;
+        return BDR_OK;
+    }
+    // l1 and l2 of nz (head parameters, feature rows) pairs into (*as[z])[0] and (*as[z])[1]: the two k_dense_small launches
+    // (brackets `name`), or - BDR_HEAD_FORM_SPLITK - the one launch (bracket "fwd_head")
+    int32_t head_forward(int nz, const float* const* hp, const float* const* xs, std::vector<float*>* const* as, int Bn, const char* name)
+    {
+        fwd_head = false;
+        if (head_form == BDR_HEAD_FORM_LAYERS) {
+            BDR_TRY(mlp_forward(net, nz, hp, xs, as, Bn, name));
+            fwd_head = true;
+            return BDR_OK;
+        }
+        const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
+        BDR_REQUIRE(nz >= 1 && nz <= CHF_MAX_Z && Bn >= 1 && Bn <= B && l1.Kp == 3136 && l1.Np == 512 && l2.Kp == 512 && l2.Np % 64 == 0,
+                    "k_cdqn_head_fwd runs [3136 -> 512 -> A] for up to %d instances of at most the allocated batch", CHF_MAX_Z);
+        if (!hf_part) {   // for the allocated batch B >= Bn and three instances: every later call fits
+            BDR_TRY(alloc(&hf_part, chf_part_floats(CHF_MAX_Z, B), BATCH, false));   // (every partial element read was written by the same launch)
+            BDR_TRY(alloc(&hf_counters, chf_counter_words(CHF_MAX_Z, B), BATCH));
+        }
+        CdqnHeadFwdArgs h{};
+        for (int z = 0; z < nz; ++z) {
+            h.x[z] = xs[z]; h.w1[z] = hp[z] + l1.w; h.b1[z] = hp[z] + l1.b; h.w2[z] = hp[z] + l2.w; h.b2[z] = hp[z] + l2.b;
+            h.h1[z] = (*as[z])[0]; h.q[z] = (*as[z])[1];
+        }
+        h.part = hf_part; h.counters = hf_counters; h.B = Bn; h.ld2 = l2.Np; h.row_tiles = chf_row_tiles(Bn);
+        Bracket br(this, "fwd_head");
+        BDR_HIP(launch_cdqn_head_fwd(stream, nz, h));
+        fwd_head = true;
+        return BDR_OK;
+    }
 
     bool cnn_form() const override { return true; }
     size_t conv_floats() const { return conv.w4; }
@@ -723,6 +768,7 @@ struct CandleDqnCnn : CandleDqn {
 
     int32_t alloc_inputs(int Bn) override
     {
+        hf_part = nullptr; hf_counters = nullptr;   // (released with the batch buffers: the next split-k head forward allocates them again)
         for (int z = 0; z < 3; ++z) {
             BDR_TRY(alloc(&a1[z], Bn * CONV_A1_ROW, BATCH)); BDR_TRY(alloc(&a2[z], Bn * CONV_A2_ROW, BATCH)); BDR_TRY(alloc(&a3[z], Bn * CONV_A3_ROW, BATCH));
         }
@@ -760,7 +806,7 @@ struct CandleDqnCnn : CandleDqn {
             const float* pp[3] = {p, p_tgt, p}; const uint8_t* rows[3] = {obs, next_obs, next_obs};
             BDR_TRY(trunk_forward(nz, pp, rows, Bn, "fwd_conv"));
             const float* hp[3] = {head(p), head(p_tgt), head(p)}; const float* xs[3] = {a3[0], a3[1], a3[2]}; std::vector<float*>* as[3] = {&a_on, &a_tg, &a_onn};
-            BDR_TRY(mlp_forward(net, nz, hp, xs, as, Bn, "fwd"));
+            BDR_TRY(head_forward(nz, hp, xs, as, Bn, "fwd"));
         }
         {
             CdqnTdArgs t{};
@@ -862,7 +908,7 @@ struct CandleDqnCnn : CandleDqn {
             const hipError_t e = launch_cnn_act_trunk(stream, (int)n, t);
             if (e != hipSuccess) st = fail(BDR_ERR_HIP, "k_cnn_act_trunk: %s", hipGetErrorString(e));
         }
-        fwd_rows = 0;
+        fwd_rows = 0; fwd_head = false;
         if (st == BDR_OK) { fwd_rows = (int)n; fwd_a3 = img_feat; fwd_a12 = b3() && keep_layers; }
         if (st == BDR_OK) {
             CnnActHeadArgs h{img_feat, hp + l1.w, hp + l1.b, hp + l2.w, hp + l2.b, l2.Np, img_part, img_counters, (int)n, A, samp, samp_idx};
@@ -888,7 +934,7 @@ struct CandleDqnCnn : CandleDqn {
         if (st == BDR_OK) { const float* pp[1] = {p}; const uint8_t* rows[1] = {d}; st = trunk_forward(1, pp, rows, (int)n, "sample_conv"); }
         if (st == BDR_OK) {
             const float* hp[1] = {head(p)}; const float* xs[1] = {a3[0]}; std::vector<float*>* as[1] = {&a_on};
-            st = mlp_forward(net, 1, hp, xs, as, (int)n, "sample_fwd");
+            st = head_forward(1, hp, xs, as, (int)n, "sample_fwd");
         }
         if (st == BDR_OK) {
             CdqnActArgs a{a_on.back(), net.L.back().Np, A, (int)n, samp, samp_idx};
@@ -1180,6 +1226,13 @@ int32_t bdr_candle_dqn_cnn_set_arithmetic(bdr_agent* base, int32_t arithmetic)
     return static_cast<CandleDqnCnn*>(base)->set_arithmetic(arithmetic);
 }
 
+int32_t bdr_candle_dqn_cnn_set_head_form(bdr_agent* base, int32_t form)
+{
+    BDR_REQUIRE(base, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn") && static_cast<CandleDqn*>(base)->cnn_form(), "not a DQN (candle) agent with the AtariCnn Q-network");
+    return static_cast<CandleDqnCnn*>(base)->set_head_form(form);
+}
+
 int32_t bdr_candle_dqn_cnn_keep_layers(bdr_agent* base, int32_t on)
 {
     BDR_REQUIRE(base, "null argument");
@@ -1195,7 +1248,19 @@ int32_t bdr_candle_dqn_probe(bdr_agent* base, int32_t what, float* out, uint64_t
     BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn"), "not a DQN (candle) agent");
     CandleDqn* a = static_cast<CandleDqn*>(base);
     BDR_HIP(hipSetDevice(a->device));
-    BDR_REQUIRE(what >= 0 && what <= 7, "unknown DQN (candle) probe %d", what);
+    BDR_REQUIRE(what >= 0 && what <= 9, "unknown DQN (candle) probe %d", what);
+    if (what >= 8) {   // the head of the last forward, instance 0: h1 [rows][512], q [rows][A], from the activation buffers of either head form
+        BDR_REQUIRE(a->cnn_form(), "probes 8 and 9 are the head activations of the AtariCnn Q-network: this agent has an Mlp");
+        CandleDqnCnn* c = static_cast<CandleDqnCnn*>(a);
+        BDR_REQUIRE(c->fwd_rows > 0, "no forward has run yet");
+        BDR_REQUIRE(c->fwd_head, "the last forward was the image path's, whose head keeps h1 and q in its own buffers: probes 8 and 9 follow an update or a "
+                                 "layer-path acting call (BDR_ACT_PATH_LAYERS, or more than %d rows)", CAI_MAX_ROWS);
+        const int l = what - 8, w = l == 0 ? 512 : a->A, ld = a->net.L[l].Np;
+        BDR_REQUIRE(n == (uint64_t)c->fwd_rows * w, "probe %d holds %d rows of %d floats", what, c->fwd_rows, w);
+        BDR_HIP(hipStreamSynchronize(a->stream));
+        BDR_HIP(hipMemcpy2D(out, (size_t)w * 4, a->a_on[l], (size_t)ld * 4, (size_t)w * 4, (size_t)c->fwd_rows, hipMemcpyDeviceToHost));
+        return BDR_OK;
+    }
     if (what >= 5) {   // the trunk of the last forward, instance 0: a1, a2, a3
         BDR_REQUIRE(a->cnn_form(), "probes 5 ... 7 are the conv activations of the AtariCnn Q-network: this agent has an Mlp");
         CandleDqnCnn* c = static_cast<CandleDqnCnn*>(a);

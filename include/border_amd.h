@@ -1726,7 +1726,10 @@ BDR_API int32_t bdr_candle_dqn_update_on_batch(bdr_agent* a, uint64_t n, const f
  * number of floats, rows x the row below, rows = the batch of that update or the rows of that call:
  *   5 a1 [rows][20][20][32]      6 a2 [rows][9][9][64]      7 a3 [rows][7][7][64]
  * After an acting call on BDR_ACT_PATH_IMAGE, 7 is that path's feature rows; 5 and 6 exist only for a BDR_ARITH_BF16X3_6 agent under
- * bdr_candle_dqn_cnn_keep_layers (the exact image trunk keeps a1 and a2 in LDS): BDR_ERR_INVALID otherwise. */
+ * bdr_candle_dqn_cnn_keep_layers (the exact image trunk keeps a1 and a2 in LDS): BDR_ERR_INVALID otherwise.
+ *   8 h1 [rows][512]             9 q [rows][n_actions]      the head of the same forward under either head form
+ * (bdr_candle_dqn_cnn_set_head_form); after an acting call that took BDR_ACT_PATH_IMAGE (at most 32 rows) BDR_ERR_INVALID: that
+ * path's head keeps them in buffers of its own. */
 BDR_API int32_t bdr_candle_dqn_probe(bdr_agent* a, int32_t what, float* out, uint64_t n);
 /* ---- the same agent with the candle crate's AtariCnn Q-network (border-candle-agent/src/atari_cnn/base.rs:31-45) ----
  * conv1 8x8/4 (n_stack -> 32), conv2 4x4/2 (-> 64), conv3 3x3/1 (-> 64), ReLU after each, flatten (c, h, w), l1 3136 -> 512, ReLU,
@@ -1785,6 +1788,19 @@ BDR_API int32_t bdr_candle_dqn_cnn_update_on_batch(bdr_agent* a, uint64_t n, con
  * BDR_ARITH_F32_EXACT on a split agent is BDR_ERR_INVALID); any other value, an Mlp-form agent and a member of a live group return
  * BDR_ERR_INVALID (an agent of BDR_ARITH_BF16X3_6 joins no bdr_candle_dqn_cnn_group). */
 BDR_API int32_t bdr_candle_dqn_cnn_set_arithmetic(bdr_agent* a, int32_t arithmetic);
+/* The form of the HEAD FORWARD (l1 3136 -> 512 + ReLU, l2 512 -> out_dim) of a built agent: BDR_HEAD_FORM_LAYERS (what
+ * bdr_candle_dqn_cnn_create builds: one launch per layer for all instances) or BDR_HEAD_FORM_SPLITK - l1 cut into 16 column tiles x 7
+ * k-slices per 32-row tile and instance, the slices added in slice order by the last arriver of each column tile, l2 by the last
+ * arriver of each row tile, ALL in one launch (k_cdqn_head_fwd): in the update (15 launches, 14 under BDR_ARITH_BF16X3_6) and on the
+ * layer acting path at any number of rows (bdr_agent_sample / _sample_device / _qvalues, and rows beyond 32 on BDR_ACT_PATH_IMAGE).
+ * It is the small-batch form: at batch 32 the layer form leaves l1 32 workgroups on a 256-CU device.  The cut is the same for every
+ * batch size, row and instance, so an acting call gives a row the bits the update's forward gives it; against the layer form h1 and
+ * Q differ in rounding.  Everything behind the forward is the agent's as it was, and the switch composes with both arithmetics and
+ * with double_dqn.  No state belongs to a form: it may be called at any time between calls and goes both ways; the work buffers
+ * are allocated by the first forward that needs them.  An unknown value, an Mlp-form agent and a member of a live group return
+ * BDR_ERR_INVALID (an agent of BDR_HEAD_FORM_SPLITK joins no bdr_candle_dqn_cnn_group). */
+enum { BDR_HEAD_FORM_LAYERS = 0, BDR_HEAD_FORM_SPLITK = 1 };
+BDR_API int32_t bdr_candle_dqn_cnn_set_head_form(bdr_agent* a, int32_t form);
 /* on != 0: the image-path trunk of a BDR_ARITH_BF16X3_6 agent (BDR_ACT_PATH_IMAGE) also stores a1 and a2 of every row to the buffers
  * probes 5 and 6 read, behind a workgroup-uniform branch; off (the default) it stores nothing extra.  Accepted and without effect on a
  * BDR_ARITH_F32_EXACT agent.  (bdr_sac_keep_layers is the precedent.) */

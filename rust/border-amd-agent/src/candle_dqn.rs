@@ -73,6 +73,13 @@ where
         crate::error::check(unsafe { ffi::bdr_candle_dqn_cnn_set_arithmetic(self.a.h, arithmetic.code()) })
     }
 
+    /// `bdr_candle_dqn_cnn_set_head_form` (AtariCnn form): `splitk = true` runs l1 + l2 of every instance as ONE split-k launch in the
+    /// update and on the layer acting path (the small-batch form), `false` goes back to one launch per layer.  Both ways, at any time.
+    pub fn set_head_form(&mut self, splitk: bool) -> Result<()> {
+        let form = if splitk { ffi::BDR_HEAD_FORM_SPLITK } else { ffi::BDR_HEAD_FORM_LAYERS };
+        crate::error::check(unsafe { ffi::bdr_candle_dqn_cnn_set_head_form(self.a.h, form) })
+    }
+
     /// `<stem>.safetensors` instead of the reference's `<stem>.pt` (both hold safetensors).
     pub fn set_checkpoint_format(&mut self, safetensors: bool) -> Result<()> {
         self.a.set_checkpoint_format(safetensors)

@@ -23,6 +23,12 @@ not slower than the best "layers" round of the same run.
 at B = 32 and B = 256; writes profiles/bench_candle_dqn_cnn_b3.json and says whether the worst split leg beats the best exact leg.
 With --act: exact layers, exact image, split layers, split image alternating at n = 1 and 8 (profiles/bench_candle_dqn_cnn_act_b3.json).
 --arithmetic f32_exact | bf16x3_6 alone sets that arithmetic on the candle agent of the other runs.  No speed bar.
+
+--cnn --head-form both: the candle agent as built ("layers") and after set_head_form("splitk") (csrc/cdqn_head_fwd.hpp), legs alternating
+in one process, no tch agent, at B = 32 and B = 256; writes profiles/bench_candle_dqn_cnn_headform.json.  The bar, at B = 32 only: the
+worst "splitk" leg is not below the best "layers" leg.  With --act: `sample` on the layer act path under both head forms alternating
+at n = 1 and 8 (profiles/bench_candle_dqn_cnn_act_headform.json).  --head-form splitk alone sets the form on the candle agent of
+--cnn and --cnn --act.
 """
 from __future__ import annotations
 
@@ -108,10 +114,13 @@ def main():
     ap.add_argument("--no-tch", action="store_true")
     ap.add_argument("--act", action="store_true", help="--cnn: the acting-call latency of the act paths instead of the update rate")
     ap.add_argument("--arithmetic", choices=("f32_exact", "bf16x3_6", "both"), default="f32_exact", help="--cnn: the candle agent's arithmetic; both: exact against split")
+    ap.add_argument("--head-form", choices=("layers", "splitk", "both"), default="layers", help="--cnn: the candle agent's head forward; both: layers against splitk")
     args = ap.parse_args()
     if args.out is None:
         stem = "bench_candle_dqn" if not args.cnn else "bench_candle_dqn_cnn" + ("" if args.batch == 32 else f"_b{args.batch}")
         args.out = os.path.join(ROOT, "profiles", stem + ".json")
+    if args.cnn and args.head_form == "both":
+        return main_cnn_act_headform(args) if args.act else main_cnn_headform(args)
     if args.cnn and args.act:
         return main_cnn_act(args)
     if args.cnn and args.arithmetic == "both":
@@ -162,6 +171,7 @@ def main_cnn(args):
     pairs = [("candle_dqn_cnn", B.CandleDqn.build(spec.to_config(B, args.batch, device=0, seed=1)), ring_u8(B, NS))]
     if args.arithmetic != "f32_exact":   # (the exact line is an agent nobody touched)
         pairs[0][1].set_arithmetic(args.arithmetic)
+    pairs[0][1].set_head_form(args.head_form)
     if not args.no_tch:
         tch = B.Dqn.build(B.DqnConfig(model_config=B.DqnModelConfig(B.AtariCnnConfig(NS, NA), B.OptimizerConfig.AdamW(1e-3, wd=0.01)),
                                       batch_size=args.batch, double_dqn=args.double_dqn, device=0, param_seed=1, arithmetic="f32_exact"))
@@ -227,6 +237,99 @@ def main_cnn_both(args):
     print(line)
 
 
+def main_cnn_headform(args):
+    """layers against splitk: one agent per head form (both of --arithmetic, "both" excepted), legs alternating, B = 32 and 256"""
+    import border_amd as B
+    import candle_dqn_cnn_restatement as RC
+    NS, NA, FORMS = 4, 6, ("layers", "splitk")
+    spec = RC.CandleDqnCnnSpec(NS, NA, lr=1e-3, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01), double_dqn=args.double_dqn)
+    arith = "f32_exact" if args.arithmetic == "both" else args.arithmetic
+    out = {"metric": "dqn_atari_candle_updates_per_s_by_head_form", "shape": {"n_stack": NS, "n_actions": NA, "opt": "AdamW", "loss": "Mse", "arithmetic": arith,
+                                                                               "double_dqn": bool(args.double_dqn)}, "warmup": args.warmup, "steps": args.steps}
+    for bsz in (32, 256):
+        pairs = [(hf, B.CandleDqn.build(spec.to_config(B, bsz, device=0, seed=1)), ring_u8(B, NS)) for hf in FORMS]
+        for hf, agent, _ in pairs:
+            if arith != "f32_exact":
+                agent.set_arithmetic(arith)
+            agent.set_head_form(hf)
+        res = {hf: {"value": round(window(agent, rb, args.warmup, args.steps), 1)} for hf, agent, rb in pairs}
+        legs = {hf: [] for hf in FORMS}
+        for _ in range(args.legs):
+            for hf, agent, rb in pairs:
+                legs[hf].append(leg(agent, rb))
+        for hf, agent, rb in pairs:
+            v = sorted(legs[hf])
+            res[hf].update(ms_per_update=round(1e3 / res[hf]["value"], 4), steady_legs_updates_per_s=[round(x, 1) for x in legs[hf]],
+                           steady_median=round(v[len(v) // 2], 1), steady_spread_pct=round(100.0 * (v[-1] - v[0]) / v[len(v) // 2], 2), **launches(agent, rb))
+            agent.close(); rb.close()
+        res["splitk_over_layers_steady_median"] = round(res["splitk"]["steady_median"] / res["layers"]["steady_median"], 4)
+        res["worst_splitk_leg_not_below_best_layers_leg"] = bool(min(legs["splitk"]) >= max(legs["layers"]))
+        out[f"b{bsz}"] = res
+    out["value"] = out["b32"]["splitk"]["value"]
+    line = json.dumps(out)
+    with open(os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_headform.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+def main_cnn_act_headform(args, rounds=5, calls=1000):
+    """`sample` on the layer act path, head form layers against splitk: one agent per form, alternating round by round, n = 1 and 8"""
+    import border_amd as B
+    import candle_dqn_cnn_restatement as RC
+    from bench import read_profile
+    NS, NA, FORMS = 4, 6, ("layers", "splitk")
+    spec = RC.CandleDqnCnnSpec(NS, NA, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01))
+    arith = "f32_exact" if args.arithmetic == "both" else args.arithmetic
+    def build(hf):
+        a = B.CandleDqn.build(spec.to_config(B, 32, device=0, seed=1, train=True, explorer=B.EpsilonGreedy(eps_start=0.02, eps_final=0.02, final_step=1)))
+        if arith != "f32_exact":
+            a.set_arithmetic(arith)
+        a.set_act_path("layers")
+        a.set_head_form(hf)
+        return a
+    agents = {hf: build(hf) for hf in FORMS}
+    res = {}
+    for n in (1, 8):
+        obs = np.random.default_rng(n).integers(0, 256, (n, 84 * 84 * NS), dtype=np.uint8)
+        us = {hf: [] for hf in FORMS}
+        for hf in FORMS:
+            for _ in range(200):
+                agents[hf].sample(obs)
+        for _ in range(rounds):
+            for hf in FORMS:
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    agents[hf].sample(obs)
+                us[hf].append(1e6 * (time.perf_counter() - t0) / calls)
+        r = {}
+        for hf in FORMS:
+            v = sorted(us[hf])
+            b = build(hf)   # (an agent of its own: profile slots keep the names of their first use)
+            for _ in range(20):
+                b.sample(obs)
+            b.profile_enable(True)
+            for _ in range(100):
+                b.sample(obs)
+            slots = read_profile(b)
+            b.profile_enable(False)
+            b.close()
+            r[hf] = {"us_per_call_rounds": [round(x, 2) for x in us[hf]], "median_us": round(v[len(v) // 2], 2),
+                     "spread_pct": round(100.0 * (v[-1] - v[0]) / v[len(v) // 2], 2), "best_us": round(v[0], 2), "worst_us": round(v[-1], 2),
+                     "profile_brackets_us": [[l, round(1e3 * ms, 2)] for l, ms in slots if l != "_null"]}
+        r["splitk_over_layers_median"] = round(r["splitk"]["median_us"] / r["layers"]["median_us"], 4)
+        r["worst_splitk_not_slower_than_best_layers"] = bool(r["splitk"]["worst_us"] <= r["layers"]["best_us"])
+        res[f"n{n}"] = r
+    for a in agents.values():
+        a.close()
+    out = {"metric": "dqn_atari_candle_sample_us_per_call_by_head_form", "shape": {"n_stack": NS, "n_actions": NA, "rows": "host u8", "act_path": "layers",
+                                                                                    "arithmetic": arith}, "rounds": rounds,
+           "calls_per_round": calls, "value": res["n1"]["splitk"]["median_us"], **res}
+    line = json.dumps(out)
+    with open(os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_act_headform.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main_cnn_act(args, rounds=5, calls=1000):
     import border_amd as B
     import candle_dqn_cnn_restatement as RC
@@ -239,6 +342,7 @@ def main_cnn_act(args, rounds=5, calls=1000):
         a = B.CandleDqn.build(spec.to_config(B, 32, device=0, seed=1, train=True, explorer=B.EpsilonGreedy(eps_start=0.02, eps_final=0.02, final_step=1)))
         if args.arithmetic != "f32_exact":
             a.set_arithmetic(args.arithmetic)
+        a.set_head_form(args.head_form)
         return a
     a = build()
     res = {}
