@@ -391,6 +391,7 @@ ABI_SYMBOLS = [
     "bdr_candle_dqn_group_trainer_ops_default", "bdr_candle_dqn_group_eval_ops_default", "bdr_candle_dqn_group_trainer_post_default",
     "bdr_candle_dqn_cnn_group_create", "bdr_candle_dqn_cnn_group_destroy", "bdr_candle_dqn_cnn_group_size", "bdr_candle_dqn_cnn_group_member",
     "bdr_candle_dqn_cnn_group_info", "bdr_candle_dqn_cnn_group_opt", "bdr_candle_dqn_cnn_group_opt_with_record", "bdr_candle_dqn_cnn_group_sync",
+    "bdr_candle_dqn_cnn_group_sample", "bdr_candle_dqn_cnn_group_sample_members", "bdr_candle_dqn_cnn_group_last_q",
 ]
 
 # BDR_HYPER_* (include/border_amd.h): the settable scalar fields of a BC, IQL, AWAC or candle SAC agent, by name
@@ -716,6 +717,9 @@ def lib() -> C.CDLL:
     L.bdr_candle_dqn_cnn_group_opt.argtypes = [vp, vp]
     L.bdr_candle_dqn_cnn_group_opt_with_record.argtypes = [vp, vp, vp, i32, vp]
     L.bdr_candle_dqn_cnn_group_sync.argtypes = [vp]
+    L.bdr_candle_dqn_cnn_group_sample.argtypes = [vp, u64, vp, vp]
+    L.bdr_candle_dqn_cnn_group_sample_members.argtypes = [vp, vp, C.c_uint32, u64, vp, vp]
+    L.bdr_candle_dqn_cnn_group_last_q.argtypes = [vp, C.c_uint32, vp, u64]
     L.bdr_trainer_train_offline_group_post.argtypes = [C.POINTER(TrainerConfigC), C.POINTER(GroupTrainerOps), C.POINTER(BcGroupTrainerPostC),
                                                        GROUP_OBSERVER_FN, C.c_void_p, C.POINTER(TrainerStatsC)]
     for kind in ("awac", "candle_sac"):

@@ -2,7 +2,7 @@
 // A group of candle DQN agents in the AtariCnn form: Dqn::opt_ (dqn/base.rs:172-189) of every member in the launch sequence
 // CandleDqnCnn::opt / update_cnn enqueue for ONE member, every launch serving ALL members - 17 launches whatever P is
 // (candle_dqn_cnn_group_plan.hpp has the rule, the order and the grids): the member index is grid dimension y of every launch.
-// A launch grouping, not an agent kind.  It covers the UPDATE ROUND only: acting, push, evaluation, the compiled online loop and
+// A launch grouping, not an agent kind.  It covers the update round and ACTING (below); push, evaluation, the compiled online loop and
 // copies between members are not built for CNN members.  The members stay ordinary agents on the group's stream - their own sample,
 // qvalues, set_hyper and checkpoint calls keep working between rounds.  A part of candle_dqn.hip's translation unit.
 //   trunk forward, dX, dW       conv_group.hpp's entries (k_conv1_img_members, k_igemm_members, k_igemm_red_members, k_conv1_dw_members),
@@ -27,6 +27,24 @@
 // host, in their order - opt_tracks(), step += 1 and the Mark, opt_scalars, n_opts, last_B -; every synchronising call of the group
 // or of a member settle()s the member: a member whose reduce + Adam launches were skipped gets step, n_opts and soft_update_counter
 // back, is reported by member index, and the other members' rounds stay counted.
+// Acting.  Policy::sample (dqn/base.rs:202-230) of the selected members, each on its own n <= CAI_MAX_ROWS host frame stacks, in TWO
+// launches whatever P is: k_cnn_act_trunk_group, grid (n, n_sel), and k_cnn_act_head_group, grid (16, CAI_L1_KS, n_sel)
+// (cnn_act_img.hpp has the kernels and their bounds) - the members' own image acting path with the member as a grid dimension, same
+// sums, same bits.  The host half is cdqn_cnn_group_act below:
+//   static per member   a CnnActTrunkArgs and a CnnActHeadArgs in two device arrays [P], keyed on the member's parameter arena and
+//                       rewritten when it has moved, behind a stream synchronise (group_act.hpp's rule); feat [P][32][3136] and, per
+//                       member, partial tiles, h1, Q rows [32][A] and 17 counters (zeroed once; every launch leaves them zero) are
+//                       the group's own device memory: a member's own img_feat, samp and probes are not touched.
+//   per call            calls [P], sel [P], the staged rows and the results, ONE pinned, device-mapped area each; the selection, the
+//                       offsets and the cap are group_act_plan.hpp's with a row of 7056 n_stack bytes (1764 n_stack words: every
+//                       member's block is 16-byte aligned, the trunk stages 16-byte vectors) and a result row of A + 1 floats: the
+//                       member's block is Q [n][A], then its n first-maximum indices as int32.
+// The head launch takes the next number of the group's one counter - rounds and acting calls are ordered on the group's stream -
+// and ends with the group's ticket; the host waits for that number (wait_seq_word), then runs every selected member's own explorer
+// (CandleDqn::explore) in member order on what came back: Softmax reads the Q rows, epsilon-greedy and eval mode the indices;
+// n_samples_act, n_samples_best_act and the epsilon counter move as they do alone, and group calls, rounds and the member's own
+// bdr_agent_sample* calls continue ONE explorer stream.  Pending device error words are not read (candle_dqn_group.hpp's rule).
+// Everything is checked before anything is staged, enqueued or drawn.
 #pragma once
 #include "candle_dqn_group.hpp"
 #include "conv_group.hpp"
@@ -114,8 +132,19 @@ void cdqn_cnn_member_static(CandleDqnCnn* m, int bs, const bdr_replay* r, const 
     }
 }
 
-// no acting for CNN members: the core's acting state stays empty
+// CNN members do not act through group_act.hpp's one launch over dense_act_body: the core's acting state stays empty
 struct CdqnCnnNoAct { using Call = CdqnActCall; using Out = int64_t; };
+// the state of cdqn_cnn_group_act
+struct CdqnCnnGroupAct {
+    std::vector<const float*> keys;                                                 // [P] the arena the static entries were written for (null: not yet)
+    std::vector<CnnActTrunkArgs> h_trunk; DeviceArray<CnnActTrunkArgs> d_trunk;     // [P]
+    std::vector<CnnActHeadArgs> h_head; DeviceArray<CnnActHeadArgs> d_head;         // [P]
+    DeviceArray<float> feat;                                                        // [P][32][3136]
+    DeviceArray<float> work;                                                        // [P][CAI_PART_FLOATS + 32 A] floats, then [P][CAI_COUNTERS] words
+    PinnedArray<CnnActGroupCall> calls; PinnedArray<unsigned> sel;                  // [P], [P]
+    PinnedArray<uint8_t> rows; size_t rows_cap = 0;                                 // bytes
+    PinnedArray<float> res; size_t res_cap = 0;                                     // floats
+};
 
 // ---- what is this kind's of the group core (group_core.hpp) ----------------------------------------------------------------------------
 struct CandleDqnCnnGroupKind : DenseRound<1, CQC_K_DW, CQC_K_REDUCE_ADAM> {
@@ -153,6 +182,7 @@ struct CandleDqnCnnGroupKind : DenseRound<1, CQC_K_DW, CQC_K_REDUCE_ADAM> {
     StagedArray<CdqnTdArgs> td; StagedArray<CdqnConvAdamArgs> cra; ConvRound conv;   // [P]
     unsigned* done_ticket = nullptr; unsigned* done_seq = nullptr; unsigned done_no = 0;   // the round in flight: what the last launch publishes
     CqcShape sh{};                                                                         // the group's one shape: which trunk entries a round launches
+    CdqnCnnGroupAct img;                                                                   // group acting (cdqn_cnn_group_act)
     hipError_t allocate(const CqcShape& s, size_t P)
     {
         sh = s;
@@ -235,6 +265,111 @@ int32_t cdqn_cnn_group_check_rings(const bdr_candle_dqn_cnn_group* g, bdr_replay
     return BDR_OK;
 }
 
+
+// Policy::sample of the selected members (members == nullptr: all of them) on n host frame stacks each: two launches, then the explorers
+int32_t cdqn_cnn_group_act(bdr_candle_dqn_cnn_group* g, const uint32_t* members, uint32_t n_sel, uint64_t n, const uint8_t* const* rows, int64_t* const* act_out)
+{
+    CdqnCnnGroupAct& s = g->kind.img;
+    const uint32_t P = (uint32_t)g->members.size();
+    const GaSelect pick = ga_select(members, n_sel, P);
+    BDR_REQUIRE(pick.refusal != GA_EMPTY, "the member list is empty");
+    BDR_REQUIRE(pick.refusal != GA_RANGE, "member %u (entry %u of the member list) of a group of %u", members[pick.entry], pick.entry, P);
+    BDR_REQUIRE(pick.refusal != GA_ORDER, "member %u (entry %u of the member list): the list must be strictly ascending", members[pick.entry], pick.entry);
+    BDR_REQUIRE(pick.refusal != GA_COUNT, "%u rows for a group of %u", n_sel, P);
+    const auto at = [&](uint32_t b) { return ga_member_at(members, b); };
+    BDR_REQUIRE(n >= 1, "batch size out of range: a group acting call takes 1 .. %d frame stacks per member", CAI_MAX_ROWS);
+    BDR_REQUIRE(n <= (uint64_t)CAI_MAX_ROWS, "%llu frame stacks per member: the grouped acting kernels serve one tile of %d rows per member; larger batches go "
+                "through the members' own sample (bdr_agent_sample)", (unsigned long long)n, CAI_MAX_ROWS);
+    for (uint32_t b = 0; b < n_sel; ++b) {
+        BDR_REQUIRE(rows[at(b)], "member %u: null observation rows", at(b));
+        BDR_REQUIRE(act_out[at(b)], "member %u: null act_out", at(b));
+    }
+    const int A = g->shape.n_actions, RC = A + 1, O = g->shape.obs_dim;   // (obs_dim: the u8 row in 4-byte words)
+    const size_t row = ga_row_bytes(O, false);
+    const std::vector<int> f64(P, 0);
+    const GaPlan plan = ga_plan(members, n_sel, P, n, O, RC, f64.data());
+    BDR_REQUIRE(plan.refusal == GA_OK, "member %u .. %u: %zu bytes of rows in one group acting call, more than the staging area's %zu: split the call", at(0),
+                at(n_sel - 1), plan.staged, GA_STAGE_MAX);
+    BDR_HIP(hipSetDevice(g->device));
+    // ---- the areas (first call, growth) and the static arguments (first call, a moved arena): rare, behind whatever the stream holds
+    const size_t W = CAI_PART_FLOATS + (size_t)32 * A;
+    if (!s.d_head) {   // (d_head last: a failure before it leaves the first call to be made again)
+        BDR_HIP(pinned_array(s.calls, P));
+        BDR_HIP(pinned_array(s.sel, P));
+        BDR_HIP(device_array(s.feat, (size_t)P * CAI_MAX_ROWS * 3136));
+        BDR_HIP(device_array(s.work, P * W + (size_t)P * CAI_COUNTERS));
+        BDR_HIP(hipMemset(s.work.get(), 0, (P * W + (size_t)P * CAI_COUNTERS) * 4));   // the counters start at zero and every launch leaves them so
+        BDR_HIP(hipStreamSynchronize(nullptr));                                        // (the memset ran on the null stream, the kernels will not)
+        s.h_trunk.assign(P, CnnActTrunkArgs{}); s.h_head.assign(P, CnnActHeadArgs{});
+        s.keys.assign(P, nullptr);
+        BDR_HIP(device_array(s.d_trunk, P));
+        BDR_HIP(device_array(s.d_head, P));
+    }
+    if (plan.staged > s.rows_cap) {
+        BDR_HIP(hipStreamSynchronize(g->stream));
+        s.rows_cap = 0;
+        BDR_HIP(pinned_array(s.rows, plan.staged));
+        s.rows_cap = plan.staged;
+    }
+    if (plan.res_floats > s.res_cap) {
+        BDR_HIP(hipStreamSynchronize(g->stream));
+        s.res_cap = 0;
+        BDR_HIP(pinned_array(s.res, plan.res_floats));
+        s.res_cap = plan.res_floats;
+    }
+    bool dirty = false;
+    for (uint32_t b = 0; b < n_sel; ++b) {
+        const uint32_t p = at(b);
+        const CandleDqnCnn* m = cdqn_cnn(g->members[p]);
+        if (s.keys[p] == m->p) continue;
+        const Arena& cv = m->conv;
+        const DenseLayer &l1 = m->net.L[0], &l2 = m->net.L[1];
+        const float* hp = m->head(m->p);
+        float* work = s.work.get() + p * W;
+        s.h_trunk[p] = CnnActTrunkArgs{nullptr, row, cv.ns, 1, m->p + cv.w1, m->p + cv.b1, m->p + cv.w2, m->p + cv.b2, m->p + cv.w3, m->p + cv.b3, s.feat.get()};
+        s.h_head[p] = CnnActHeadArgs{s.feat.get(), hp + l1.w, hp + l1.b, hp + l2.w, hp + l2.b, l2.Np, work,
+                                     reinterpret_cast<unsigned*>(s.work.get() + P * W) + (size_t)p * CAI_COUNTERS, 0, A, work + CAI_PART_FLOATS, nullptr};
+        s.keys[p] = m->p;
+        dirty = true;
+    }
+    if (dirty) {
+        hipError_t e = hipStreamSynchronize(g->stream);
+        if (e == hipSuccess) e = hipMemcpy(s.d_trunk.get(), s.h_trunk.data(), (size_t)P * sizeof(CnnActTrunkArgs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(s.d_head.get(), s.h_head.data(), (size_t)P * sizeof(CnnActHeadArgs), hipMemcpyHostToDevice);
+        if (e != hipSuccess) s.keys.assign(P, nullptr);   // (nothing is known to be on the device: the next call writes it again)
+        BDR_HIP(e);
+    }
+    // ---- this call's words, rows and selection
+    for (uint32_t b = 0; b < n_sel; ++b) {
+        const uint32_t p = at(b);
+        memcpy(s.rows.host.get() + plan.row_off[b], rows[p], (size_t)n * row);
+        s.calls.host.get()[p] = CnnActGroupCall{s.rows.dev + plan.row_off[b], s.res.dev + plan.res_off[b]};
+        s.sel.host.get()[b] = p;
+    }
+    std::atomic_thread_fence(std::memory_order_release);
+    // the head launch takes the next number of the group's one counter: opt rounds and acting calls are ordered on the group's stream
+    const uint64_t k = g->launches + 1;
+    g->launches = k;
+    BDR_HIP(launch_cnn_act_trunk_group(g->stream, (int)n, n_sel, s.d_trunk.get(), s.calls.dev, s.sel.dev));
+    g->kernel_launches += 1;
+    BDR_HIP(launch_cnn_act_head_group(g->stream, (int)n, n_sel, s.d_head.get(), s.calls.dev, s.sel.dev, CnnActGroupDone{g->ticket.get(), g->seq.dev, (unsigned)k}));
+    g->kernel_launches += 1;
+    bool arrived = false;
+    BDR_TRY(wait_seq_word(g->seq.host.get(), (unsigned)k, g->stream, std::chrono::steady_clock::now(), &arrived));
+    if (!arrived) return fail(BDR_ERR_HIP, "the actions of a group acting call never arrived in host memory");
+    std::atomic_thread_fence(std::memory_order_acquire);
+    // what came back -> the member's h_q / h_idx, then its own explorer, as its sample ends
+    for (uint32_t b = 0; b < n_sel; ++b) {
+        CandleDqn* m = g->members[at(b)];
+        const float* block = s.res.host.get() + plan.res_off[b];
+        const int32_t* idx = reinterpret_cast<const int32_t*>(block + (size_t)n * A);
+        m->h_q.assign(block, block + (size_t)n * A);
+        m->h_idx.assign(idx, idx + n);
+        BDR_TRY(m->explore(n, act_out[at(b)], nullptr));
+    }
+    return BDR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -277,6 +412,31 @@ int32_t bdr_candle_dqn_cnn_group_sync(bdr_candle_dqn_cnn_group* g)
     BDR_HIP(hipSetDevice(g->device));
     BDR_HIP(hipStreamSynchronize(g->stream));
     return cdqn_cnn_group_settle_and_check(g);
+}
+
+// Policy::sample (dqn/base.rs:202-230) of every member / of the members `members` on n host u8 frame stacks each: two launches
+int32_t bdr_candle_dqn_cnn_group_sample(bdr_candle_dqn_cnn_group* g, uint64_t n, const uint8_t* const* rows, int64_t* const* act_out)
+{
+    BDR_REQUIRE(g && rows && act_out, "null argument");
+    return cdqn_cnn_group_act(g, nullptr, (uint32_t)g->members.size(), n, rows, act_out);
+}
+int32_t bdr_candle_dqn_cnn_group_sample_members(bdr_candle_dqn_cnn_group* g, const uint32_t* members, uint32_t n_sel, uint64_t n, const uint8_t* const* rows,
+                                                int64_t* const* act_out)
+{
+    BDR_REQUIRE(g && members && rows && act_out, "null argument");
+    return cdqn_cnn_group_act(g, members, n_sel, n, rows, act_out);
+}
+// a test and diagnostic helper: the Q rows [n][A] the last acting call of the group that selected `member` brought back for it -
+// the member's h_q, which its own sample / qvalues calls overwrite: valid until the member acts alone
+int32_t bdr_candle_dqn_cnn_group_last_q(const bdr_candle_dqn_cnn_group* g, uint32_t member, float* q_out, uint64_t n_floats)
+{
+    BDR_REQUIRE(g && q_out, "null argument");
+    BDR_REQUIRE(member < g->members.size(), "member %u of a group of %u", member, (unsigned)g->members.size());
+    const CandleDqn* m = g->members[member];
+    BDR_REQUIRE(n_floats == m->h_q.size() && n_floats > 0, "member %u holds %llu action values of its last acting call, not %llu", member,
+                (unsigned long long)m->h_q.size(), (unsigned long long)n_floats);
+    std::copy(m->h_q.begin(), m->h_q.end(), q_out);
+    return BDR_OK;
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@
 //                     32 x 32 tile per workgroup (dense_small_tile), a counter per column tile, the last arriver adds the partials in
 //                     slice order - and, in the workgroup that completes the last column tile, l2 and dqn_q_argmax into the
 //                     buffers k_cdqn_act writes (samp, samp_idx).
+//   k_cnn_act_trunk_group, k_cnn_act_head_group   the same two launches for the selected members of a candle DQN CNN group, the
+//                     member as a grid dimension (their own header comment, below; the host half: candle_dqn_cnn_group.hpp).
 // No workgroup waits for another one: a counter is taken once, behind the workgroup's own stores (dense.hpp last_workgroup: agent-scope
 // stores, s_waitcnt, barrier, agent-scope fetch-add), and whoever takes the last ticket goes on; the grid need not be co-resident.
 //
@@ -96,6 +98,22 @@ hipError_t launch_cnn_act_trunk(hipStream_t st, int n, const CnnActTrunkArgs& a)
 hipError_t launch_cnn_act_trunk_b3(hipStream_t st, int n, const CnnActTrunkB3Args& a);   // grid n
 hipError_t launch_cnn_act_head(hipStream_t st, const CnnActHeadArgs& a);            // grid (16, CAI_L1_KS)
 
+// ---- the group entries (candle_dqn_cnn_group.hpp): Policy::sample of the selected members of a group, the member = sel[blockIdx.y]
+// (trunk) / sel[blockIdx.z] (head).  `trunk` and `head` are device arrays [P] of the members' STATIC words, read in place through the
+// constant address space: the member is uniform, so its fields stay scalar loads.  A static trunk entry holds the weights, ns,
+// row_stride = 7056 ns, vec16 = 1 and feat = the group's feature area [n_sel][32][3136] (rows: null - the call's); a static head entry
+// the weights, ld2, A, feat = the same area, the member's OWN part / counters and q = the member's own device rows [32][A] (n, idx:
+// unused - the call's).  `calls` [P] and `sel` [n_sel] are this call's, in pinned device-mapped memory.
+struct CnnActGroupCall {
+    const uint8_t* rows;   // the member's n staged frame stacks, 16-byte aligned, 7056 ns bytes apart
+    float* res;            // the member's result block in pinned memory: Q [n][A] floats, then the n first-maximum indices as int32
+};
+struct CnnActGroupDone { unsigned* ticket; unsigned* seq_host; unsigned seq; };   // the group's ticket (group_done.hpp) and this launch's number
+hipError_t launch_cnn_act_trunk_group(hipStream_t st, int n, unsigned n_sel, const CnnActTrunkArgs* trunk, const CnnActGroupCall* calls,
+                                      const unsigned* sel);   // grid (n, n_sel)
+hipError_t launch_cnn_act_head_group(hipStream_t st, int n, unsigned n_sel, const CnnActHeadArgs* head, const CnnActGroupCall* calls,
+                                     const unsigned* sel, const CnnActGroupDone& done);   // grid (16, CAI_L1_KS, n_sel)
+
 }  // namespace bdr
 
 #ifdef BDR_CNN_ACT_IMG_KERNELS
@@ -103,6 +121,7 @@ hipError_t launch_cnn_act_head(hipStream_t st, const CnnActHeadArgs& a);        
 #include "dense.hpp"
 #include "dense_act.hpp"
 #include "fwd_c23_b3.hpp"   // k_cnn_act_trunk_b3: the plane layouts (cpl_index, c23_a1_off, c23_a2_off) and split3_f32x4
+#include "group_done.hpp"   // the group entries end with the group's ticket
 
 namespace bdr {
 
@@ -121,210 +140,7 @@ __device__ __forceinline__ void cai_stage(const V* __restrict__ src, V* dst, int
 
 static __global__ __launch_bounds__(256) void k_cnn_act_trunk(CnnActTrunkArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float s_u[3 * CAI_RED];
-    __shared__ __attribute__((aligned(16))) float s_a1[400 * CAI_A1_LD];
-    __shared__ __attribute__((aligned(16))) float s_a2[81 * CAI_A2_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, h = lane >> 5;
-
-    // ---- every first operand, requested before anything is waited for
-    // conv1: the fragment rows of channel c for this lane (output channel i, k half h): W1[64 c + 16 sl + 8 h + j][i]
-    auto load_w1 = [&](int c, float (&w)[4][8]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int sl = 0; sl < 4; ++sl)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) w[sl][j] = a.w1[(size_t)(64 * c + 16 * sl + 8 * h + j) * 32 + i];
-    };
-    // conv2: chunk ch = k-steps 2 ch, 2 ch + 1 of this wave's quarter, both column tiles: W2[128 w + 8 s + 4 h + q][32 nt + i]
-    auto load_w2 = [&](int ch, float (&w)[2][2][4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w[u][nt][q] = a.w2[(size_t)(128 * wave + 8 * (2 * ch + u) + 4 * h + q) * 64 + 32 * nt + i];
-    };
-    // conv3: one tap of this wave's column tile: W3[64 tap + 8 s + 4 h + q][32 (w & 1) + i]
-    auto load_w3 = [&](int tap, float (&w)[8][4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[s][q] = a.w3[(size_t)(64 * tap + 8 * s + 4 * h + q) * 64 + 32 * (wave & 1) + i];
-    };
-    float w1n[4][8], w2n[2][2][4], w3n[8][4];
-    load_w1(0, w1n);
-    f32x4 bq1[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bq1[q] = *reinterpret_cast<const f32x4*>(a.b1 + 8 * q + 4 * h);
-    load_w2(0, w2n);
-    load_w3(0, w3n);
-    const float b3v = a.b3[32 * (wave & 1) + i];
-
-    // ---- the frame stack -> LDS, as it is (u8)
-    {
-        const uint8_t* src = a.rows + (size_t)blockIdx.x * a.row_stride;
-        if (a.vec16) cai_stage(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(s_u), a.ns * 441, tid);
-        else cai_stage(reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(s_u), a.ns * 1764, tid);
-    }
-    __syncthreads();
-
-    // ---- conv1
-    {
-        const int nu = wave == 0 ? 4 : 3;
-        const uint8_t* frb = reinterpret_cast<const uint8_t*>(s_u);
-        int poff[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int m = min((wave + 4 * t) * 32 + i, 399), oh = m / 20, ow = m - oh * 20;
-            poff[t] = (oh * 4 + h) * 84 + ow * 4;
-        }
-        f32x16 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        for (int c = 0; c < a.ns; ++c) {
-            float wc[4][8];
-#pragma unroll
-            for (int sl = 0; sl < 4; ++sl)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) wc[sl][j] = w1n[sl][j];
-            if (c + 1 < a.ns) load_w1(c + 1, w1n);
-#pragma unroll
-            for (int sl = 0; sl < 4; ++sl) {
-                uint32_t hi[8], mid[8], lo[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    hi[j] = __float_as_uint(wc[sl][j]) & 0xffff0000u;
-                    const float r1 = wc[sl][j] - __uint_as_float(hi[j]);    // exact
-                    mid[j] = __float_as_uint(r1) & 0xffff0000u;
-                    const float r2 = r1 - __uint_as_float(mid[j]);          // exact, <= 8 significant bits
-                    lo[j] = __float_as_uint(r2) & 0xffff0000u;
-                }
-                bf16x8 wp[3];
-                wp[0] = __builtin_bit_cast(bf16x8, uint4{(hi[0] >> 16) | hi[1], (hi[2] >> 16) | hi[3], (hi[4] >> 16) | hi[5], (hi[6] >> 16) | hi[7]});
-                wp[1] = __builtin_bit_cast(bf16x8, uint4{(mid[0] >> 16) | mid[1], (mid[2] >> 16) | mid[3], (mid[4] >> 16) | mid[5], (mid[6] >> 16) | mid[7]});
-                wp[2] = __builtin_bit_cast(bf16x8, uint4{(lo[0] >> 16) | lo[1], (lo[2] >> 16) | lo[3], (lo[4] >> 16) | lo[5], (lo[6] >> 16) | lo[7]});
-                // k-step sl of channel c: patch rows 2 sl + h, eight pixels of the row per lane
-                const int so = c * 7056 + (2 * sl) * 84;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    if (t < nu) {   // wave-uniform
-                        const uint32_t* px = reinterpret_cast<const uint32_t*>(frb + poff[t] + so);
-                        const bf16x8 fa = u8x8_to_bf16(px[0], px[1]);
-#pragma unroll
-                        for (int pl = 2; pl >= 0; --pl) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[pl], fa, acc[t], 0, 0, 0);   // small terms first
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int m = (wave + 4 * t) * 32 + i;
-            if (t < nu && m < 400) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float x = acc[t][4 * q + e] * (1.0f / 255.0f) + bq1[q][e]; v[e] = x > 0.f ? x : 0.f; }
-                    *reinterpret_cast<f32x4*>(s_a1 + m * CAI_A1_LD + 8 * q + 4 * h) = v;
-                }
-            }
-        }
-    }
-    __syncthreads();   // a1 is whole; nobody reads the frames any more
-
-    // ---- conv2: this wave's k-quarter (kernel row kh = wave) of all six tiles
-    {
-        int ab[3];
-#pragma unroll
-        for (int mt = 0; mt < 3; ++mt) {
-            const int m = min(32 * mt + i, 80), oh = m / 9, ow = m - oh * 9;
-            ab[mt] = ((2 * oh + wave) * 20 + 2 * ow) * CAI_A1_LD + 4 * h;
-        }
-        f32x16 acc[3][2];
-#pragma unroll
-        for (int mt = 0; mt < 3; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-        for (int ch = 0; ch < 8; ++ch) {
-            float wc[2][2][4];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) wc[u][nt][q] = w2n[u][nt][q];
-            if (ch + 1 < 8) load_w2(ch + 1, w2n);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int s = 2 * ch + u, ko = (s >> 2) * CAI_A1_LD + (s & 3) * 8;   // k = 8 s + 4 h: kw = s >> 2, channels (s & 3) 8 + 4 h ...
-                f32x4 av[3];
-#pragma unroll
-                for (int mt = 0; mt < 3; ++mt) av[mt] = *reinterpret_cast<const f32x4*>(s_a1 + ab[mt] + ko);
-#pragma unroll
-                for (int mt = 0; mt < 3; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt][q], wc[u][nt][q], acc[mt][nt], 0, 0, 0);
-            }
-        }
-        // the quarters meet: wave 0 in a2 itself, waves 1 ... 3 in red (over the frames)
-        float* dst = wave == 0 ? s_a2 : s_u + (wave - 1) * CAI_RED;
-        const int ld = wave == 0 ? CAI_A2_LD : 64;
-#pragma unroll
-        for (int mt = 0; mt < 3; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (m < 81) dst[m * ld + 32 * nt + i] = acc[mt][nt][r];
-                }
-    }
-    __syncthreads();
-    for (int e = tid; e < CAI_RED; e += 256) {   // one thread per element: ((q0 + q1) + q2) + q3, bias, ReLU
-        const int m = e >> 6, n = e & 63;
-        float v = ((s_a2[m * CAI_A2_LD + n] + s_u[e]) + s_u[CAI_RED + e]) + s_u[2 * CAI_RED + e];
-        v += a.b2[n];
-        s_a2[m * CAI_A2_LD + n] = v > 0.f ? v : 0.f;
-    }
-    __syncthreads();
-
-    // ---- conv3: tile (wave >> 1, wave & 1)
-    {
-        const int mt = wave >> 1, nt = wave & 1;
-        const int mc = min(32 * mt + i, 48), oh = mc / 7, ow = mc - oh * 7;
-        const int ab = (oh * 9 + ow) * CAI_A2_LD + 4 * h;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        for (int tap = 0; tap < 9; ++tap) {
-            float wc[8][4];
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) wc[s][q] = w3n[s][q];
-            if (tap + 1 < 9) load_w3(tap + 1, w3n);
-            const int kh = tap / 3, kw = tap - kh * 3, to = ab + (kh * 9 + kw) * CAI_A2_LD;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(s_a2 + to + 8 * s);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q], wc[s][q], acc, 0, 0, 0);
-            }
-        }
-        float* out = a.feat + (size_t)blockIdx.x * 3136 + 32 * nt + i;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float v = acc[r] + b3v;
-            if (m < 49) out[m * 64] = v > 0.f ? v : 0.f;
-        }
-    }
+#include "cnn_act_trunk_body_inc.hpp"
 }
 
 
@@ -669,6 +485,137 @@ static __global__ __launch_bounds__(256) void k_cnn_act_head(CnnActHeadArgs a)
         __syncthreads();   // red is free again; the Q stores of this workgroup are visible to it
     }
     if (tid < a.n) a.idx[tid] = dqn_q_argmax(a.q + (size_t)tid * a.A, a.A);
+}
+
+// ---- the group entries ---------------------------------------------------------------------------------------------------------------
+// k_cnn_act_trunk_group   grid (n, n_sel): one workgroup of four waves per (frame stack, selected member) runs k_cnn_act_trunk's body -
+//   the same text (cnn_act_trunk_body_inc.hpp): conv1's units per wave on the bf16 MFMA with split weights, conv2's k-quarters meeting in
+//   LDS as ((q0 + q1) + q2) + q3, conv3 one tile per wave, weights from L2 straight into registers one step ahead - on a CnnActTrunkArgs
+//   gathered in registers from the member's static entry (scalar loads), the member's rows of this call and the block of 32 feature
+//   rows of the SELECTION index y.  Same sums, same bits as the member's own k_cnn_act_trunk.
+// k_cnn_act_head_group    grid (16 column tiles, CAI_L1_KS k-slices, n_sel): k_cnn_act_head's tiles and sums per member - one partial
+//   32 x 32 tile per workgroup (dense_small_tile), the member's own counter per column tile, the last arriver adds the partials in
+//   slice order, and the workgroup that completes the member's last column tile runs l2 and dqn_q_argmax - with a body of its own,
+//   because every workgroup has to reach the group's ticket: the two early returns of the standalone head are nested conditions here.
+//   Q goes to the member's device rows q (the argmax reads them back, as the standalone head reads samp) AND to the member's block of
+//   the pinned result area; the indices go to the block only.  Every thread fences its result stores at system scope before its
+//   workgroup counts on the ticket (candle_act_group.hpp's rule); the last workgroup of the launch publishes the launch number.
+//   A member's counters are zero between launches: whoever takes the last ticket of a counter re-arms it (dense.hpp ticket_take).
+// No workgroup waits for another one; the grids need not be co-resident.
+// Bounds of every new index.  y (z) = blockIdx.y (.z) < gridDim.y (.z) = n_sel = the length of `sel` the host has written; member =
+// sel[y] < P = the length of `trunk`, `head` and `calls` (checked by the host before anything is enqueued).  The trunk reads frame stack
+// blockIdx.x < n of the member's n staged rows and writes feature row y * 32 + blockIdx.x < n_sel * 32 of feat [n_sel][32][3136]
+// (n <= CAI_MAX_ROWS = 32).  The head reads feature rows y * 32 + min(i, n - 1); part, counters and q are the member's own
+// (CAI_PART_FLOATS floats, CAI_COUNTERS words, 32 * A floats), indexed inside as k_cnn_act_head indexes them: part at rows r < n, h1
+// likewise, counters nt < 16 and 16.  Result stores go only to rows r < n: res[r * A + j], j < A, and int32 index n * A + tid, tid < n,
+// inside the member's block of n * (A + 1) floats.
+static __global__ __launch_bounds__(256) void k_cnn_act_trunk_group(const BDR_CONST_AS CnnActTrunkArgs* args, const BDR_CONST_AS CnnActGroupCall* calls,
+                                                                    const BDR_CONST_AS unsigned* sel)
+{
+    const unsigned member = sel[blockIdx.y];
+    const BDR_CONST_AS CnnActTrunkArgs& e = args[member];
+    const CnnActTrunkArgs a{calls[member].rows, e.row_stride, e.ns, e.vec16, e.w1, e.b1, e.w2, e.b2, e.w3, e.b3, e.feat + (size_t)blockIdx.y * (CAI_MAX_ROWS * 3136)};
+#include "cnn_act_trunk_body_inc.hpp"
+}
+
+static __global__ __launch_bounds__(256) void k_cnn_act_head_group(const BDR_CONST_AS CnnActHeadArgs* args, const BDR_CONST_AS CnnActGroupCall* calls,
+                                                                   const BDR_CONST_AS unsigned* sel, int n, CnnActGroupDone done)
+{
+    __shared__ float red[4][32][33];
+    __shared__ __attribute__((aligned(16))) float hs[32][516];
+    __shared__ unsigned s_last;
+    constexpr int KSL = 3136 / CAI_L1_KS;
+    const unsigned member = sel[blockIdx.z];
+    const BDR_CONST_AS CnnActHeadArgs& a = args[member];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nt = blockIdx.x, ks = blockIdx.y, n0 = nt * 32, k0 = ks * KSL;
+    const int A = a.A, ld2 = a.ld2;
+    float* const part = a.part;
+    unsigned* const counters = a.counters;
+    const float* arow = a.feat + ((size_t)blockIdx.z * CAI_MAX_ROWS + min(lane & 31, n - 1)) * 3136 + k0;   // rows >= n alias the last row (never stored)
+    const int r = tid >> 3, c4 = (tid & 7) * 4, col = n0 + c4;
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b1 + col);
+    dense_small_tile<false>([&](int k) { return *reinterpret_cast<const f32x4*>(arow + k); }, a.w1 + (size_t)k0 * 512, 512, n0, KSL, wave, lane, red);
+    __syncthreads();
+    f32x4 v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = dense_small_sum(red, r, c4 + q);
+    if (r < n) {
+        float* p = part + ((size_t)ks * 32 + r) * 512 + col;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) st_agent(p + q, v[q]);
+    }
+    if (last_workgroup(counters + nt, (unsigned)CAI_L1_KS, &s_last)) {
+        // the column tile's partials in slice order whoever arrives last (k_cnn_act_head's loads and sums)
+        float* h1 = part + (size_t)CAI_L1_KS * 32 * 512;
+        if (r < n) {
+            const float* p0 = part + (size_t)r * 512 + col;
+            f32x4 t[CAI_L1_KS];
+#pragma unroll
+            for (int e = 0; e < CAI_L1_KS; ++e) {
+                const float* ps = p0 + (size_t)e * 32 * 512;
+                asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(t[e]) : "v"(ps) : "memory");
+            }
+            static_assert(CAI_L1_KS == 7, "the wait below names seven destinations");
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]) :: "memory");
+            v = t[0];
+#pragma unroll
+            for (int e = 1; e < CAI_L1_KS; ++e) v += t[e];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float x = v[q] + bv[q];
+                st_agent(h1 + (size_t)r * 512 + col + q, x > 0.f ? x : 0.f);   // read by the workgroup below, possibly on another XCD
+            }
+        }
+        if (last_workgroup(counters + 16, 16u, &s_last)) {
+            // ---- l2 and the first maximum, by the workgroup that completed the member's last column tile
+            for (int e0 = 0; e0 < 16; e0 += 8) {
+                f32x4 t[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int x = tid + 256 * (e0 + e);   // 16-byte vector x of hs: row x >> 7, floats 4 (x & 127) ...
+                    const float* ps = h1 + (size_t)min(x >> 7, n - 1) * 512 + 4 * (x & 127);
+                    asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(t[e]) : "v"(ps) : "memory");
+                }
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]) :: "memory");
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const int x = tid + 256 * (e0 + e); *reinterpret_cast<f32x4*>(&hs[x >> 7][4 * (x & 127)]) = t[e]; }
+            }
+            __syncthreads();
+            const float* hrow = hs[lane & 31];
+            float* const qd = a.q;                  // the member's device rows [32][A]
+            float* const res = calls[member].res;   // its block of the pinned result area
+            for (int t0 = 0; t0 < A; t0 += 32) {
+                dense_small_tile<false>([&](int k) { return *reinterpret_cast<const f32x4*>(hrow + k); }, a.w2, ld2, t0, 512, wave, lane, red);
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int j = t0 + c4 + q;
+                    if (r < n && j < A) {
+                        const float x = dense_small_sum(red, r, c4 + q) + a.b2[j];
+                        qd[(size_t)r * A + j] = x;
+                        res[(size_t)r * A + j] = x;
+                    }
+                }
+                __syncthreads();   // red is free again; the Q stores of this workgroup are visible to it
+            }
+            if (tid < n) reinterpret_cast<int*>(res + (size_t)n * A)[tid] = dqn_q_argmax(qd + (size_t)tid * A, A);
+        }
+    }
+    __threadfence_system();   // this thread's result rows are in host memory before its workgroup counts
+    bg_group_done(done.ticket, done.seq_host, done.seq);
+}
+
+hipError_t launch_cnn_act_trunk_group(hipStream_t st, int n, unsigned n_sel, const CnnActTrunkArgs* trunk, const CnnActGroupCall* calls, const unsigned* sel)
+{
+    return step_launch(st, false, k_cnn_act_trunk_group, dim3((unsigned)n, n_sel), dim3(256), (const BDR_CONST_AS CnnActTrunkArgs*)trunk,
+                       (const BDR_CONST_AS CnnActGroupCall*)calls, (const BDR_CONST_AS unsigned*)sel);
+}
+hipError_t launch_cnn_act_head_group(hipStream_t st, int n, unsigned n_sel, const CnnActHeadArgs* head, const CnnActGroupCall* calls, const unsigned* sel,
+                                     const CnnActGroupDone& done)
+{
+    return step_launch(st, false, k_cnn_act_head_group, dim3(16, CAI_L1_KS, n_sel), dim3(256), (const BDR_CONST_AS CnnActHeadArgs*)head,
+                       (const BDR_CONST_AS CnnActGroupCall*)calls, (const BDR_CONST_AS unsigned*)sel, n, done);
 }
 
 hipError_t launch_cnn_act_trunk(hipStream_t st, int n, const CnnActTrunkArgs& a)

@@ -855,10 +855,13 @@ class CandleDqnCnnGroup(_GroupBase):
     and record_verbose_level; their buffers are uniform uint8 buffers of their own or views of one (`SimpleReplayBuffer.view`) - a
     frame-stack store or a prioritized buffer is refused by member.
 
-    The group covers the update round only: `opt`, `opt_with_record`, `sync`.  Acting, push, evaluation, the compiled online loop and
-    copy_members are not built for CNN members; the members are ordinary `CandleDqn` objects the group owns, and their own `sample`,
-    `qvalues`, `set_hyper` and checkpoint calls keep working between rounds.  A member whose batch holds an out-of-range action is
-    skipped on the device and reported by `sync` / `opt_with_record` as "member <i>: ..."; the others step."""
+    The group covers the update round - `opt`, `opt_with_record`, `sync` - and acting: `sample` acts for the selected members on up
+    to 32 frame stacks each in TWO launches whatever the number of members, then runs each member's own explorer on the host (one
+    SmallRng stream per member across group calls, the member's own calls and rounds); `last_q` reads back the action values.  Push,
+    evaluation, the compiled online loop and copy_members are not built for CNN members; the members are ordinary `CandleDqn` objects
+    the group owns, and their own `sample`, `qvalues`, `set_hyper` and checkpoint calls keep working between rounds.  A member whose
+    batch holds an out-of-range action is skipped on the device and reported by `sync` / `opt_with_record` as "member <i>: ..."; the
+    others step."""
     _PREFIX, _MEMBER = "bdr_candle_dqn_cnn_group", CandleDqn
     record_keys = CandleDqnGroup.record_keys
 
@@ -872,8 +875,45 @@ class CandleDqnCnnGroup(_GroupBase):
         _lib.check(self._c("opt_with_record")(self._g, self._buffers(buffers), out.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)))
         return [{k: np.float32(v) for k, v in zip(keys[i], out[i, :cnt[i]])} for i in range(n)]
 
-    def sample(self, *a, **k):
-        raise NotImplementedError("a candle DQN CNN group steps the update round only: act through the members' own sample()")
-    evaluate = sample
+    def sample(self, rows, members=None) -> list:
+        """Policy::sample of the members in TWO launches (bdr_candle_dqn_cnn_group_sample / _sample_members): a list of int64 arrays
+        [n] in member order, each what that member's own `sample(rows[i])` on the image act path gives at this point of its explorer
+        stream.  rows: one uint8 array per member, [n, n_stack, 84, 84] (or [n_stack, 84, 84]: n = 1) with 1 <= n <= 32, the same n
+        for every member - or ONE array for all members.  members: a strictly ascending list of member indices: only those act; the
+        entries of members that were not selected are None (they draw nothing)."""
+        P = len(self._members)
+        if isinstance(rows, np.ndarray):
+            rows = [rows] * P
+        rows = list(rows)
+        if len(rows) != P:
+            raise ValueError(f"{P} members need {P} row arrays, got {len(rows)}")
+        rb = self._members[0].config.obs_dim   # (the uint8 row: 84 * 84 * n_stack bytes)
+        sel = list(range(P)) if members is None else [int(i) for i in members]
+        staged, ptrs, outs, n = {}, (C.c_void_p * P)(), [None] * P, None
+        for i in sel:
+            if not 0 <= i < P or rows[i] is None:
+                continue   # (the library refuses it, naming the member)
+            if id(rows[i]) not in staged:
+                staged[id(rows[i])] = np.ascontiguousarray(rows[i], np.uint8).reshape(-1, rb)
+            a = staged[id(rows[i])]
+            if n is None:
+                n = a.shape[0]
+            elif a.shape[0] != n:
+                raise ValueError(f"member {i}: {a.shape[0]} rows, the members before it {n}: one n for every member")
+            ptrs[i] = a.ctypes.data
+            outs[i] = np.empty(n, np.int64)
+        n = 1 if n is None else n
+        out_ptrs = (C.c_void_p * P)(*[None if o is None else o.ctypes.data for o in outs])
+        if members is None:
+            _lib.check(self._c("sample")(self._g, n, ptrs, out_ptrs))
+        else:
+            s = np.ascontiguousarray(sel, np.uint32).reshape(-1)
+            _lib.check(self._c("sample_members")(self._g, s.ctypes.data_as(C.c_void_p), s.size, n, ptrs, out_ptrs))
+        return outs
+
+    last_q = CandleDqnGroup.last_q   # (the member's own copy of its last action values: its own sample / qvalues overwrite it)
+
+    def evaluate(self, *a, **k):
+        raise NotImplementedError("a candle DQN CNN group has no lockstep evaluator: evaluate through the members' own sample()")
 
 

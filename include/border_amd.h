@@ -1885,8 +1885,8 @@ BDR_API void bdr_candle_dqn_group_trainer_post_default(bdr_group_trainer_post* p
  * are the instances of one launch per layer), the TD launch, the head's two input gradients, its grouped weight gradient and reduce +
  * Adam, conv3 dW, conv3 dX, conv2 dW, conv2 dX, conv1 dW, the conv reduce + Adam - with every launch serving ALL members (the member
  * is grid dimension y): 17 launches per round whatever the number of members, and every member bit-identical to being stepped alone.
- * The group covers the UPDATE ROUND ONLY: acting, push, evaluation, the compiled online loop and copies between members are not built
- * for CNN members.  The members stay ordinary agents (on the group's stream, destroyed with the group): their own bdr_agent_sample,
+ * The group covers the update round and acting (below): push, evaluation, the compiled online loop and copies between members are
+ * not built for CNN members.  The members stay ordinary agents (on the group's stream, destroyed with the group): their own bdr_agent_sample,
  * bdr_agent_qvalues, bdr_agent_hyper_set and checkpoint calls keep working between rounds.
  * _create: every agent a bdr_candle_dqn_cnn_create agent, one shape per group (n_stack <= 6, n_actions, batch_size, double_dqn),
  * n_updates_per_opt == 1, one device, no profiling, no gradient communicator, one value of dxc3_kloop; a refusal names the first member
@@ -1906,6 +1906,21 @@ BDR_API int32_t bdr_candle_dqn_cnn_group_info(const bdr_candle_dqn_cnn_group* g,
 BDR_API int32_t bdr_candle_dqn_cnn_group_opt(bdr_candle_dqn_cnn_group* g, bdr_replay* const* buffers);                   /* dqn/base.rs:172-189, :59-170 */
 BDR_API int32_t bdr_candle_dqn_cnn_group_opt_with_record(bdr_candle_dqn_cnn_group* g, bdr_replay* const* buffers, float* out, int32_t cap_per_member, int32_t* n_out);   /* dqn/base.rs:307-331 */
 BDR_API int32_t bdr_candle_dqn_cnn_group_sync(bdr_candle_dqn_cnn_group* g);                                              /* dqn/base.rs:172-189 */
+/* Acting.  Policy::sample (dqn/base.rs:202-230) of every member (_sample) or of the members `members` (_sample_members: strictly
+ * ascending, every entry < P) in TWO launches whatever the number of members (csrc/cnn_act_img.hpp: the members' image acting path
+ * with the member as a grid dimension, bit-identical to the member's own BDR_ACT_PATH_IMAGE call), followed by each selected member's
+ * own explorer on the host, in member order.  rows[p]: member p's n host frame stacks [n][n_stack][84][84] u8, 1 <= n <= 32 (more rows
+ * go through the members' own bdr_agent_sample); act_out[p]: its n actions.  rows and act_out are indexed by MEMBER; entries of members
+ * that are not selected are not read.  A selected member's explorer state, n_samples_act, n_samples_best_act and the epsilon counter
+ * move as in its own bdr_agent_sample; a member that is not selected draws nothing.  Pending device error words are not read, as in
+ * bdr_candle_dqn_group_sample.  Every refusal comes before anything is staged, enqueued or drawn and names the member.
+ * _last_q: the Q rows [n][A] the last acting call that selected `member` brought back for it (a test and diagnostic helper).  They
+ * are the member's own host copy of its last action values: a bdr_agent_sample or bdr_agent_qvalues of the member's own after the
+ * group call overwrites them, and _last_q then returns those (bdr_candle_dqn_group_last_q has the same property). */
+BDR_API int32_t bdr_candle_dqn_cnn_group_sample(bdr_candle_dqn_cnn_group* g, uint64_t n, const uint8_t* const* rows, int64_t* const* act_out);   /* dqn/base.rs:202-230 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_sample_members(bdr_candle_dqn_cnn_group* g, const uint32_t* members, uint32_t n_sel, uint64_t n,
+                                                        const uint8_t* const* rows, int64_t* const* act_out);                                     /* dqn/base.rs:202-230 */
+BDR_API int32_t bdr_candle_dqn_cnn_group_last_q(const bdr_candle_dqn_cnn_group* g, uint32_t member, float* q_out, uint64_t n_floats);            /* dqn/base.rs:203 */
 
 /* ---- acting of the dense-agent agents (IQL, AWAC, the candle SAC, BC, the candle DQN) ----------------------------------------------------------------------
  * Their Policy::sample has two forms that produce the same bits: the layer-by-layer path (pack, one launch per layer, the sample

@@ -30,6 +30,7 @@ where
     pub(crate) a: AgentHandle,
     train: bool,
     n_actions: usize,
+    n_stack: usize, // the AtariCnn form's frames per observation; 0 in the Mlp form
     phantom: PhantomData<(E, O, A)>,
 }
 
@@ -56,6 +57,11 @@ where
 
     pub fn n_actions(&self) -> usize {
         self.n_actions
+    }
+
+    /// Frames per observation of the AtariCnn form (a row is `84 * 84 * n_stack` bytes); 0 for an Mlp Q-network.
+    pub fn n_stack(&self) -> usize {
+        self.n_stack
     }
 
     /// Width of one action row in elements ([`crate::evaluator::SampleRaw`]): one i64 index.
@@ -139,7 +145,7 @@ where
         let c = config.to_c().expect("CandleDqnConfig");
         let mut h = std::ptr::null_mut();
         expect(unsafe { ffi::bdr_candle_dqn_create(&c, &mut h) }, "Dqn::build");
-        Self { a: AgentHandle::new(h), train: config.train, n_actions: c.n_actions as usize, phantom: PhantomData }
+        Self { a: AgentHandle::new(h), train: config.train, n_actions: c.n_actions as usize, n_stack: 0, phantom: PhantomData }
     }
 }
 
@@ -155,7 +161,7 @@ where
         let c = config.to_c().expect("CandleDqnAtariCnnConfig");
         let mut h = std::ptr::null_mut();
         expect(unsafe { ffi::bdr_candle_dqn_cnn_create(&c, &mut h) }, "Dqn::build");
-        Self { a: AgentHandle::new(h), train: config.dqn.train, n_actions: c.out_dim as usize, phantom: PhantomData }
+        Self { a: AgentHandle::new(h), train: config.dqn.train, n_actions: c.out_dim as usize, n_stack: c.n_stack as usize, phantom: PhantomData }
     }
 }
 

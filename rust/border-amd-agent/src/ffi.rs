@@ -1441,6 +1441,16 @@ extern "C" {
     pub fn bdr_candle_dqn_cnn_group_opt(g: *mut bdr_candle_dqn_cnn_group, buffers: *mut *const bdr_replay) -> i32;
     pub fn bdr_candle_dqn_cnn_group_opt_with_record(g: *mut bdr_candle_dqn_cnn_group, buffers: *mut *const bdr_replay, out: *mut f32, cap_per_member: i32, n_out: *mut i32) -> i32;
     pub fn bdr_candle_dqn_cnn_group_sync(g: *mut bdr_candle_dqn_cnn_group) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_sample(g: *mut bdr_candle_dqn_cnn_group, n: u64, rows: *mut *const u8, act_out: *mut *const i64) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_sample_members(
+        g: *mut bdr_candle_dqn_cnn_group,
+        members: *const u32,
+        n_sel: u32,
+        n: u64,
+        rows: *mut *const u8,
+        act_out: *mut *const i64,
+    ) -> i32;
+    pub fn bdr_candle_dqn_cnn_group_last_q(g: *const bdr_candle_dqn_cnn_group, member: u32, q_out: *mut f32, n_floats: u64) -> i32;
     pub fn bdr_agent_sample_raw(
         a: *mut bdr_agent,
         norm: *const bdr_obs_norm,

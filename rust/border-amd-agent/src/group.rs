@@ -2183,6 +2183,42 @@ where
     pub fn sync(&mut self) -> Result<()> {
         check(unsafe { ffi::bdr_candle_dqn_cnn_group_sync(self.g) })
     }
+
+    /// `Policy::sample` of every member (`members: None`, `bdr_candle_dqn_cnn_group_sample`) or of the strictly ascending `members`
+    /// (`bdr_candle_dqn_cnn_group_sample_members`) in TWO launches: member `i` acts on the `n <= 32` u8 frame stacks of `rows[i]`
+    /// (`n * 84 * 84 * n_stack` bytes, the same `n` for every member) and gets `n` explored i64 actions, what its own `sample` on the
+    /// image act path gives at this point of its explorer stream.  `rows` and the result have one entry per member; the entries of
+    /// members that are not selected are not read and stay empty, and those members draw nothing.
+    pub fn sample(&mut self, members: Option<&[u32]>, n: usize, rows: &[&[u8]]) -> Result<Vec<Vec<i64>>> {
+        let p = self.members.len();
+        if rows.len() != p {
+            return Err(anyhow!("{} members need {} row slices, got {}", p, p, rows.len()));
+        }
+        let selected = |i: usize| members.map_or(true, |m| m.contains(&(i as u32)));
+        let mut out: Vec<Vec<i64>> = (0..p).map(|i| if selected(i) { vec![0i64; n] } else { Vec::new() }).collect();
+        for i in (0..p).filter(|&i| selected(i)) {
+            let want = n * 7056 * self.members[i].n_stack();
+            if n == 0 || rows[i].len() != want {
+                return Err(anyhow!("member {}: {} bytes are not {} frame stacks of 84 x 84 x {} bytes", i, rows[i].len(), n, self.members[i].n_stack()));
+            }
+        }
+        let mut row_ptrs: Vec<*const u8> = (0..p).map(|i| if selected(i) { rows[i].as_ptr() } else { std::ptr::null() }).collect();
+        let mut out_ptrs: Vec<*const i64> = out.iter_mut().map(|v| if v.is_empty() { std::ptr::null() } else { v.as_mut_ptr() as *const i64 }).collect();
+        check(match members {
+            None => unsafe { ffi::bdr_candle_dqn_cnn_group_sample(self.g, n as u64, row_ptrs.as_mut_ptr(), out_ptrs.as_mut_ptr()) },
+            Some(m) => unsafe {
+                ffi::bdr_candle_dqn_cnn_group_sample_members(self.g, m.as_ptr(), m.len() as u32, n as u64, row_ptrs.as_mut_ptr(), out_ptrs.as_mut_ptr())
+            },
+        })?;
+        Ok(out)
+    }
+
+    /// The action values `[n][n_actions]` the last group acting call that selected `member` brought back for it.
+    pub fn last_q(&self, member: usize, n: usize) -> Result<Vec<f32>> {
+        let mut q = vec![0f32; n * self.members[member].n_actions()];
+        check(unsafe { ffi::bdr_candle_dqn_cnn_group_last_q(self.g, member as u32, q.as_mut_ptr(), q.len() as u64) })?;
+        Ok(q)
+    }
 }
 
 impl<E, O, A> Drop for AmdCandleDqnCnnGroup<E, O, A>

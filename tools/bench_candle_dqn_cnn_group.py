@@ -5,7 +5,11 @@ P in {1, 8, 32}.  The data of both sides are VIEWS of one u8 ring (SimpleReplayB
 Protocol (tools/bench_candle_dqn_group.py): warm-up, one window of K rounds per side, then five legs of 0.3 s per side, the two sides
 alternating, a synchronise per leg; the figure is the median of the legs, the spread their min / max.  The bar, at P = 8 and P = 32:
 the group's worst leg is not below the loop's best leg; P = 1 (the cost of a group of one against the agent alone) is reported without
-one.  Writes one JSON document (default profiles/bench_candle_dqn_cnn_group.json)."""
+one.  Writes one JSON document (default profiles/bench_candle_dqn_cnn_group.json).
+
+--act    ONE group acting call (CandleDqnCnnGroup.sample: two launches whatever P is) of one host frame stack per member in eval
+mode against a loop of the same P agents' own sample() on the image act path, their faster path; member-actions/s, the same protocol
+and bar.  Writes profiles/bench_candle_dqn_cnn_group_act.json."""
 import argparse
 import json
 import os
@@ -31,14 +35,44 @@ def config(i):
                              seed=i, device=0)
 
 
+def act(args):
+    rng = np.random.default_rng(0)
+    doc = {"bench": "candle_dqn_cnn_group_act", "shape": SHAPE + "; one host frame stack per member, eval mode", "window_steps": args.window, "legs": args.legs,
+           "leg_seconds": args.leg_seconds,
+           "unit": "member-actions/s (median of the legs); loop = sample() of the same P agents standalone on the image act path, one after the other",
+           "bar": "at P = 8 and P = 32: group_min >= loop_max", "act": {}}
+    for P in [int(x) for x in args.sizes.split(",")]:
+        g = B.CandleDqnCnnGroup.build([config(i) for i in range(P)])
+        solo = [B.CandleDqn.build(config(i)) for i in range(P)]
+        for a in solo: a.set_act_path("image")
+        rows = [rng.integers(0, 256, (1, ROW), dtype=np.uint8) for _ in range(P)]
+
+        def loop():
+            for a, r in zip(solo, rows): a.sample(r)
+
+        m = measure(lambda: g.sample(rows), g.sync, loop, lambda: None, P, args.window, args.legs, args.leg_seconds)   # (both sides' calls are synchronous)
+        if P > 1:
+            m["bar_met"] = bool(m["group_min_max"][0] >= m["loop_min_max"][1])
+        doc["act"][str(P)] = m
+        print(P, m, flush=True)
+        g.close()
+        for a in solo: a.close()
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--act", action="store_true")
     ap.add_argument("--sizes", default="1,8,32")
     ap.add_argument("--window", type=int, default=100)
     ap.add_argument("--legs", type=int, default=5)
     ap.add_argument("--leg-seconds", type=float, default=0.3)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_candle_dqn_cnn_group.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                        "bench_candle_dqn_cnn_group_act.json" if args.act else "bench_candle_dqn_cnn_group.json")
+    if args.act:
+        return write(args, act(args))
     rng = np.random.default_rng(0)
     owner = B.SimpleReplayBuffer(B.SimpleReplayBufferConfig(capacity=ROWS, seed=1), (ROW,), np.uint8, (1,), np.int64, device=0)
     for _ in range(ROWS // 512):
@@ -71,6 +105,10 @@ def main():
         for a in solo: a.close()
         for v in gv + sv: v.close()
     owner.close()
+    write(args, doc)
+
+
+def write(args, doc):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
