@@ -47,6 +47,7 @@ class AdamWConfigC(C.Structure):
 
 ARITHMETIC = {"bf16x3_6": 0, "f32_exact": 1}   # BDR_ARITH_*
 HEAD_FORM = {"layers": 0, "splitk": 1}         # BDR_HEAD_FORM_*
+HEAD_BWD_FORM = {"layers": 0, "fused": 1}      # BDR_HEAD_BWD_*
 
 
 class DqnConfigC(C.Structure):
@@ -349,7 +350,7 @@ ABI_SYMBOLS = [
     "bdr_candle_sac_sample_device",
     "bdr_bc_config_default", "bdr_bc_create", "bdr_bc_update_on_batch", "bdr_bc_probe", "bdr_bc_sample", "bdr_bc_sample_device",
     "bdr_candle_dqn_config_default", "bdr_candle_dqn_create", "bdr_candle_dqn_update_on_batch", "bdr_candle_dqn_probe",
-    "bdr_candle_dqn_cnn_config_default", "bdr_candle_dqn_cnn_create", "bdr_candle_dqn_cnn_update_on_batch", "bdr_candle_dqn_cnn_keep_layers", "bdr_candle_dqn_cnn_set_arithmetic", "bdr_candle_dqn_cnn_set_head_form",
+    "bdr_candle_dqn_cnn_config_default", "bdr_candle_dqn_cnn_create", "bdr_candle_dqn_cnn_update_on_batch", "bdr_candle_dqn_cnn_keep_layers", "bdr_candle_dqn_cnn_set_arithmetic", "bdr_candle_dqn_cnn_set_head_form", "bdr_candle_dqn_cnn_set_head_bwd_form",
     "bdr_comm_get_unique_id", "bdr_comm_init_rank", "bdr_comm_destroy", "bdr_comm_agree", "bdr_sac_probe", "bdr_agent_allreduce_params",
     "bdr_agent_broadcast_params", "bdr_agent_set_grad_comm", "bdr_dqn_grads_on_batch", "bdr_agent_apply_grads",
     "bdr_atari_prep_create", "bdr_atari_prep_destroy", "bdr_atari_prep_reset", "bdr_atari_prep_step", "bdr_atari_prep_obs",
@@ -584,6 +585,7 @@ def lib() -> C.CDLL:
     L.bdr_candle_dqn_cnn_keep_layers.argtypes = [vp, i32]
     L.bdr_candle_dqn_cnn_set_arithmetic.argtypes = [vp, i32]
     L.bdr_candle_dqn_cnn_set_head_form.argtypes = [vp, i32]
+    L.bdr_candle_dqn_cnn_set_head_bwd_form.argtypes = [vp, i32]
     L.bdr_bc_config_default.restype = None
     L.bdr_bc_config_default.argtypes = [C.POINTER(BcConfigC)]
     L.bdr_bc_create.argtypes = [C.POINTER(BcConfigC), C.POINTER(vp)]

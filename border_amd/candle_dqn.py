@@ -181,6 +181,11 @@ class CandleDqn(DenseHandle):
         and on the layer acting path: the small-batch form; "layers" - one launch per layer, what an agent is built with.  Both ways."""
         _lib.check(_lib.lib().bdr_candle_dqn_cnn_set_head_form(self._h, _lib.HEAD_FORM[form]))
 
+    def set_head_bwd_form(self, form: str) -> None:
+        """bdr_candle_dqn_cnn_set_head_bwd_form (AtariCnn form): "fused" - the head's two input gradients and its weight gradients in
+        one launch for batches of at most 256 rows; "layers" - the three launches an agent is built with.  Both ways."""
+        _lib.check(_lib.lib().bdr_candle_dqn_cnn_set_head_bwd_form(self._h, _lib.HEAD_BWD_FORM[form]))
+
     def keep_layers(self, on: bool = True) -> None:
         """bdr_candle_dqn_cnn_keep_layers: the image-path trunk of a "bf16x3_6" agent also stores a1 and a2 for probe()."""
         _lib.check(_lib.lib().bdr_candle_dqn_cnn_keep_layers(self._h, int(on)))

@@ -23,6 +23,7 @@
 #include "conv_trunk.hpp"
 #include "cnn_act_img.hpp"
 #include "cdqn_head_fwd.hpp"
+#include "cdqn_head_bwd.hpp"
 #include "candle_dqn_group_plan.hpp"
 
 using namespace bdr;
@@ -759,6 +760,34 @@ struct CandleDqnCnn : CandleDqn {
         return BDR_OK;
     }
 
+    // BDR_HEAD_BWD_FUSED (bdr_candle_dqn_cnn_set_head_bwd_form on a built agent; the constructor builds BDR_HEAD_BWD_LAYERS): the head's
+    // two input-gradient launches and its grouped dW launch are ONE launch of k_cdqn_head_bwd (cdqn_head_bwd.hpp) into the same
+    // buffers, for batches of one dW chunk and at most CHB_MAX_B rows; above that the layer launches run.  No state belongs to a form.
+    int head_bwd_form = BDR_HEAD_BWD_LAYERS;
+    int32_t set_head_bwd_form(int32_t form)
+    {
+        BDR_REQUIRE(form == BDR_HEAD_BWD_LAYERS || form == BDR_HEAD_BWD_FUSED, "DQN (candle, AtariCnn): unknown head backward form %d (BDR_HEAD_BWD_LAYERS or BDR_HEAD_BWD_FUSED)", form);
+        if (form == head_bwd_form) return BDR_OK;
+        BDR_REQUIRE(!group, "this agent is a member of a group: the grouped round is built for BDR_HEAD_BWD_LAYERS members, and a member's head backward form is fixed");
+        if (form == BDR_HEAD_BWD_FUSED) {
+            BDR_REQUIRE(net.L.size() == 2 && net.L[0].Kp == 3136 && net.L[0].Np == 512 && net.L[1].Kp == 512, "BDR_HEAD_BWD_FUSED: k_cdqn_head_bwd runs the head [3136 -> 512 -> A]");
+            BDR_REQUIRE(A <= CHB_MAX_A, "BDR_HEAD_BWD_FUSED: k_cdqn_head_bwd stages W2's columns in LDS and runs at most %d actions, this agent has %d", CHB_MAX_A, A);
+        }
+        head_bwd_form = form;
+        return BDR_OK;
+    }
+    bool head_bwd_fused(int Bn) const { return head_bwd_form == BDR_HEAD_BWD_FUSED && Bn <= CHB_MAX_B && chunks_for(Bn) == 1; }
+    // dy[L - 1], h1 and a3 of instance 0 -> dy[0], dy3 and chunk 0 of the head's dW partials (bracket "bwd_head")
+    int32_t head_backward_fused(int Bn)
+    {
+        const DenseLayer &l1 = net.L[0], &l2 = net.L[1];
+        const float* hp = head(p);
+        const CdqnHeadBwdArgs h{dy[1], a_on[0], a3[0], hp + l1.w, hp + l2.w, dy[0], dy3, part + off[0], part + off[1], Bn, l2.Np, A, (Bn + 31) / 32};
+        Bracket br(this, "bwd_head");
+        BDR_HIP(launch_cdqn_head_bwd(stream, h));
+        return BDR_OK;
+    }
+
     bool cnn_form() const override { return true; }
     size_t conv_floats() const { return conv.w4; }
     size_t row_bytes() const { return (size_t)7056 * conv.ns; }
@@ -826,8 +855,10 @@ struct CandleDqnCnn : CandleDqn {
             std::vector<float*>* acts[1] = {&a_on}; std::vector<float*>* dys[1] = {&dy};
             float *hp = head(p), *hg = head(g), *hm = head(m), *hv = head(v), *ht[1] = {head(p_tgt)};
             float* dx0[1] = {dy3}; const float* mask0[1] = {a3[0]};
+            const bool fused = head_bwd_fused(Bn);   // BDR_HEAD_BWD_FUSED: the three launches as one, then the reduce + Adam launch alone
+            if (fused) BDR_TRY(head_backward_fused(Bn));
             BDR_TRY(mlp_backward_step(net, 1, &hp, &hg, &hm, &hv, track ? ht : nullptr, a3[0], acts, dys, part, 0, off, &sc, Bn, {"dx", "dw", "reduce_adam"}, net.total,
-                                      cfg.tau, L - 1, nullptr, dev_err + ERR_ACTION, applied, step, dx0, mask0));
+                                      cfg.tau, L - 1, nullptr, dev_err + ERR_ACTION, applied, step, dx0, mask0, fused));
         }
         CdqnConvAdamArgs ra{};
         int k = 3;   // the hook runs for conv3, conv2, conv1; the segments are in arena order
@@ -1231,6 +1262,13 @@ int32_t bdr_candle_dqn_cnn_set_head_form(bdr_agent* base, int32_t form)
     BDR_REQUIRE(base, "null argument");
     BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn") && static_cast<CandleDqn*>(base)->cnn_form(), "not a DQN (candle) agent with the AtariCnn Q-network");
     return static_cast<CandleDqnCnn*>(base)->set_head_form(form);
+}
+
+int32_t bdr_candle_dqn_cnn_set_head_bwd_form(bdr_agent* base, int32_t form)
+{
+    BDR_REQUIRE(base, "null argument");
+    BDR_REQUIRE(!strcmp(base->kind(), "candle_dqn") && static_cast<CandleDqn*>(base)->cnn_form(), "not a DQN (candle) agent with the AtariCnn Q-network");
+    return static_cast<CandleDqnCnn*>(base)->set_head_bwd_form(form);
 }
 
 int32_t bdr_candle_dqn_cnn_keep_layers(bdr_agent* base, int32_t on)

@@ -162,6 +162,7 @@ struct CandleDqnCnnGroupKind : DenseRound<1, CQC_K_DW, CQC_K_REDUCE_ADAM> {
         const CandleDqnCnn* c = cdqn_cnn(m);
         d.split_arith = c->b3() ? 1 : 0;
         d.head_splitk = c->head_form == BDR_HEAD_FORM_SPLITK ? 1 : 0;
+        d.head_bwd_fused = c->head_bwd_form == BDR_HEAD_BWD_FUSED ? 1 : 0;
         CqcShape& s = d.shape;
         s.n_stack = c->conv.ns; s.obs_dim = (int)(c->row_bytes() / 4); s.n_actions = m->A; s.batch = (int)m->cfg.batch_size; s.double_dqn = m->cfg.double_dqn ? 1 : 0;
         s.dxc3_kloop = m->dxc3_kloop ? 1 : 0;

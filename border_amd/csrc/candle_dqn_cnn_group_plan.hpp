@@ -29,7 +29,8 @@ struct CqcShape { int obs_dim, n_stack, n_actions, batch, double_dqn, dxc3_kloop
 // kind_cdqn_cnn: the agent is a candle DQN agent with the AtariCnn Q-network; n_updates: its n_updates_per_opt
 // split_arith: it was switched to BDR_ARITH_BF16X3_6 (bdr_candle_dqn_cnn_set_arithmetic)
 // head_splitk: it was switched to BDR_HEAD_FORM_SPLITK (bdr_candle_dqn_cnn_set_head_form)
-struct CqcMember { CqcShape shape; int kind_cdqn_cnn; uint64_t n_updates; int device, prof, grad_comm; const void* agent; int split_arith, head_splitk; };
+// head_bwd_fused: it was switched to BDR_HEAD_BWD_FUSED (bdr_candle_dqn_cnn_set_head_bwd_form)
+struct CqcMember { CqcShape shape; int kind_cdqn_cnn; uint64_t n_updates; int device, prof, grad_comm; const void* agent; int split_arith, head_splitk, head_bwd_fused; };
 
 inline bool cqc_same_shape(const CqcShape& a, const CqcShape& b)
 {
@@ -124,6 +125,7 @@ inline int cqc_group_refusal(const CqcMember* m, unsigned n, const char** why, i
         if (!x.kind_cdqn_cnn) return "not a candle DQN agent with the AtariCnn Q-network (agents in the Mlp form make a candle DQN group)";
         if (x.split_arith) return "its arithmetic is BDR_ARITH_BF16X3_6: the grouped round is built for BDR_ARITH_F32_EXACT members (conv2 / conv3 on the FP32 MFMA)";
         if (x.head_splitk) return "its head form is BDR_HEAD_FORM_SPLITK: the grouped round is built for BDR_HEAD_FORM_LAYERS members (l1 and l2 as two grouped launches)";
+        if (x.head_bwd_fused) return "its head backward form is BDR_HEAD_BWD_FUSED: the grouped round is built for BDR_HEAD_BWD_LAYERS members (the head's dX and dW as grouped launches)";
         if (const char* w = cqc_shape_ineligible(x.shape)) return w;
         if (!cqc_same_shape(x.shape, m[0].shape)) return "its shape (n_stack, n_actions, batch_size, double_dqn) differs from member 0's: one shape per group";
         if (x.n_updates != 1) return "n_updates_per_opt != 1 is not built for a group";

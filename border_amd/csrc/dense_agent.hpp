@@ -116,20 +116,22 @@ struct DenseAgent : bdr_agent {
     // out-of-range action flag); applied / step: *applied = step by a launch that was not skipped.
     // dx0 / mask0 (optional): one more input-gradient launch below layer 0, d(x0) of network z into dx0[z] ([Bn][Kp of layer 0]),
     // zero where mask0[z] - the post-ReLU activation that produced x0 - is not positive (the candle DQN's conv trunk feeds layer 0).
+    // tail_only: the caller's own launch has written every input gradient and chunk 0 of every dW partial (the candle DQN's fused head
+    // backward, cdqn_head_bwd.hpp): only the reduce + Adam launch is enqueued, with the arguments it always had.
     int32_t mlp_backward_step(const MlpLayout& net, int nz, float* const* p, float* const* g, float* const* m, float* const* v, float* const* tgt,
                               const float* x0, std::vector<float*>* const* acts, std::vector<float*>* const* dys, float* part, size_t part_stride,
                               const std::vector<size_t>& off, const AdamScalars* sc, int Bn, const StepNames& names, size_t total, double tau, int lo,
                               const DenseReduceSeg* extra = nullptr, const unsigned* poison = nullptr, unsigned long long* applied = nullptr,
-                              unsigned long long step = 0, float* const* dx0 = nullptr, const float* const* mask0 = nullptr)
+                              unsigned long long step = 0, float* const* dx0 = nullptr, const float* const* mask0 = nullptr, bool tail_only = false)
     {
         const int L = (int)net.L.size();
-        for (int l = lo; l >= 1; --l) {
+        for (int l = tail_only ? 0 : lo; l >= 1; --l) {
             const float* pb[4]; const float* dy[4]; float* dx[4]; const float* mask[4];
             for (int z = 0; z < nz; ++z) { pb[z] = p[z]; dy[z] = (*dys[z])[l]; dx[z] = (*dys[z])[l - 1]; mask[z] = (*acts[z])[l - 1]; }
             Bracket br(this, names.dx);
             BDR_TRY(dense_dx_z(stream, net.L[l], nz, pb, dy, dx, mask, Bn, true));
         }
-        if (dx0) {
+        if (dx0 && !tail_only) {
             const float* pb[4]; const float* dy[4];
             for (int z = 0; z < nz; ++z) { pb[z] = p[z]; dy[z] = (*dys[z])[0]; }
             Bracket br(this, names.dx);
@@ -137,11 +139,11 @@ struct DenseAgent : bdr_agent {
         }
         std::vector<DenseDwJob> jobs;
         const int c = chunks_for(Bn);
-        for (int z = 0; z < nz; ++z)
+        for (int z = 0; z < nz && !tail_only; ++z)
             for (int l = 0; l < L; ++l)
                 jobs.push_back(DenseDwJob{&net.L[l], l == 0 ? DenseSrc{x0, net.L[0].Kp} : DenseSrc{(*acts[z])[l - 1], net.L[l - 1].Np}, (*dys[z])[l],
                                           part + (size_t)z * part_stride + off[l], c});
-        { Bracket br(this, names.dw); BDR_TRY(dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
+        if (!tail_only) { Bracket br(this, names.dw); BDR_TRY(dense_dw_small_group(stream, jobs.data(), (int)jobs.size(), Bn)); }
         ReduceAdamArgs ra{};
         ra.nseg = L; ra.inst_part_stride = part_stride;
         for (int l = 0; l < L; ++l) {

@@ -1801,6 +1801,20 @@ BDR_API int32_t bdr_candle_dqn_cnn_set_arithmetic(bdr_agent* a, int32_t arithmet
  * BDR_ERR_INVALID (an agent of BDR_HEAD_FORM_SPLITK joins no bdr_candle_dqn_cnn_group). */
 enum { BDR_HEAD_FORM_LAYERS = 0, BDR_HEAD_FORM_SPLITK = 1 };
 BDR_API int32_t bdr_candle_dqn_cnn_set_head_form(bdr_agent* a, int32_t form);
+/* The form of the HEAD BACKWARD of a built agent's update: BDR_HEAD_BWD_LAYERS (what bdr_candle_dqn_cnn_create builds: l2's input
+ * gradient, l1's input gradient under conv3's ReLU mask and the grouped weight gradient as three launches) or BDR_HEAD_BWD_FUSED - the
+ * same outputs from ONE launch (k_cdqn_head_bwd): a workgroup per 32 feature rows of W1 forms l2's input gradient itself (at most 32
+ * terms per element) and from it both its rows of l1's weight gradient, accumulated in registers over the whole batch, and its columns
+ * of l1's input gradient; a few more workgroups form l2's weight gradient.  No partial sums through memory, no counters.  It writes
+ * every element the three launches write, so the reduce + Adam launch and the conv trunk's backward follow unchanged (14 launches per
+ * update with BDR_HEAD_FORM_LAYERS, 13 with BDR_HEAD_FORM_SPLITK, one fewer under BDR_ARITH_BF16X3_6).  It serves batches of at most
+ * 256 rows; a larger batch runs the three layer launches, bit for bit as under BDR_HEAD_BWD_LAYERS.  Gradients agree with the layer
+ * form's to rounding (the summation order over the batch differs; it is a function of the batch size alone, so two runs give the
+ * same bits).  No state belongs to a form: it may be called at any time between calls and goes both ways, and composes with either
+ * head forward form and either arithmetic.  An unknown value, an Mlp-form agent, a member of a live group and BDR_HEAD_BWD_FUSED on an
+ * agent with more than 32 actions return BDR_ERR_INVALID (an agent of BDR_HEAD_BWD_FUSED joins no bdr_candle_dqn_cnn_group). */
+enum { BDR_HEAD_BWD_LAYERS = 0, BDR_HEAD_BWD_FUSED = 1 };
+BDR_API int32_t bdr_candle_dqn_cnn_set_head_bwd_form(bdr_agent* a, int32_t form);
 /* on != 0: the image-path trunk of a BDR_ARITH_BF16X3_6 agent (BDR_ACT_PATH_IMAGE) also stores a1 and a2 of every row to the buffers
  * probes 5 and 6 read, behind a workgroup-uniform branch; off (the default) it stores nothing extra.  Accepted and without effect on a
  * BDR_ARITH_F32_EXACT agent.  (bdr_sac_keep_layers is the precedent.) */

@@ -86,6 +86,13 @@ where
         crate::error::check(unsafe { ffi::bdr_candle_dqn_cnn_set_head_form(self.a.h, form) })
     }
 
+    /// `bdr_candle_dqn_cnn_set_head_bwd_form` (AtariCnn form): `fused = true` runs the head's two input gradients and its weight
+    /// gradients as ONE launch for batches of at most 256 rows, `false` goes back to the three layer launches.  Both ways, at any time.
+    pub fn set_head_bwd_form(&mut self, fused: bool) -> Result<()> {
+        let form = if fused { ffi::BDR_HEAD_BWD_FUSED } else { ffi::BDR_HEAD_BWD_LAYERS };
+        crate::error::check(unsafe { ffi::bdr_candle_dqn_cnn_set_head_bwd_form(self.a.h, form) })
+    }
+
     /// `<stem>.safetensors` instead of the reference's `<stem>.pt` (both hold safetensors).
     pub fn set_checkpoint_format(&mut self, safetensors: bool) -> Result<()> {
         self.a.set_checkpoint_format(safetensors)

@@ -97,6 +97,8 @@ pub const BDR_ARITH_BF16X3_6: i32 = 0;
 pub const BDR_ARITH_F32_EXACT: i32 = 1;
 pub const BDR_HEAD_FORM_LAYERS: i32 = 0;
 pub const BDR_HEAD_FORM_SPLITK: i32 = 1;
+pub const BDR_HEAD_BWD_LAYERS: i32 = 0;
+pub const BDR_HEAD_BWD_FUSED: i32 = 1;
 pub const BDR_ACTIVATION_NONE: i32 = 0;
 pub const BDR_ACTIVATION_RELU: i32 = 1;
 pub const BDR_ACTIVATION_TANH: i32 = 2;
@@ -1635,6 +1637,7 @@ extern "C" {
     pub fn bdr_candle_dqn_cnn_create(cfg: *const bdr_candle_dqn_cnn_config, out: *mut *mut bdr_agent) -> i32;
     pub fn bdr_candle_dqn_cnn_set_arithmetic(a: *mut bdr_agent, arithmetic: i32) -> i32;
     pub fn bdr_candle_dqn_cnn_set_head_form(a: *mut bdr_agent, form: i32) -> i32;
+    pub fn bdr_candle_dqn_cnn_set_head_bwd_form(a: *mut bdr_agent, form: i32) -> i32;
     pub fn bdr_candle_dqn_cnn_keep_layers(a: *mut bdr_agent, on: i32) -> i32;
     pub fn bdr_candle_dqn_cnn_update_on_batch(
         a: *mut bdr_agent,

@@ -29,6 +29,13 @@ in one process, no tch agent, at B = 32 and B = 256; writes profiles/bench_candl
 worst "splitk" leg is not below the best "layers" leg.  With --act: `sample` on the layer act path under both head forms alternating
 at n = 1 and 8 (profiles/bench_candle_dqn_cnn_act_headform.json).  --head-form splitk alone sets the form on the candle agent of
 --cnn and --cnn --act.
+
+--cnn --head-bwd both: the candle agent as built ("layers") and after set_head_bwd_form("fused") (csrc/cdqn_head_bwd.hpp), legs
+alternating in one process, no tch agent, at B = 32 and B = 256; writes --out, by default profiles/bench_candle_dqn_cnn_headbwd.json
+(..._headbwd_splitk.json with --head-form splitk).  No speed bar.  --head-bwd fused alone sets the form on the candle agent of --cnn;
+--head-form and --arithmetic (not "both") apply to both agents.  --against-parent PARENT_DIR TREE_DIR merges the b32.json / b256.json
+that `--cnn --no-tch --batch 32 | 256 > <dir>/b<batch>.json` of a parent checkout and of this tree left into
+profiles/bench_candle_dqn_cnn_headbwd_parent.json (needs no device).
 """
 from __future__ import annotations
 
@@ -115,7 +122,16 @@ def main():
     ap.add_argument("--act", action="store_true", help="--cnn: the acting-call latency of the act paths instead of the update rate")
     ap.add_argument("--arithmetic", choices=("f32_exact", "bf16x3_6", "both"), default="f32_exact", help="--cnn: the candle agent's arithmetic; both: exact against split")
     ap.add_argument("--head-form", choices=("layers", "splitk", "both"), default="layers", help="--cnn: the candle agent's head forward; both: layers against splitk")
+    ap.add_argument("--head-bwd", choices=("layers", "fused", "both"), default="layers", help="--cnn: the candle agent's head backward; both: layers against fused")
+    ap.add_argument("--against-parent", nargs=2, metavar=("PARENT_DIR", "TREE_DIR"), default=None,
+                    help="merge <dir>/b32.json and <dir>/b256.json (the output of --cnn --no-tch --batch 32 | 256 of a parent checkout and of this tree) into one record")
     args = ap.parse_args()
+    if args.against_parent:
+        return merge_against_parent(args)
+    if args.cnn and args.head_bwd == "both":
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_headbwd" + ("_splitk" if args.head_form == "splitk" else "") + ".json")
+        return main_cnn_headbwd(args)
     if args.out is None:
         stem = "bench_candle_dqn" if not args.cnn else "bench_candle_dqn_cnn" + ("" if args.batch == 32 else f"_b{args.batch}")
         args.out = os.path.join(ROOT, "profiles", stem + ".json")
@@ -172,6 +188,8 @@ def main_cnn(args):
     if args.arithmetic != "f32_exact":   # (the exact line is an agent nobody touched)
         pairs[0][1].set_arithmetic(args.arithmetic)
     pairs[0][1].set_head_form(args.head_form)
+    if args.head_bwd != "layers":        # (the layers line is an agent nobody touched)
+        pairs[0][1].set_head_bwd_form(args.head_bwd)
     if not args.no_tch:
         tch = B.Dqn.build(B.DqnConfig(model_config=B.DqnModelConfig(B.AtariCnnConfig(NS, NA), B.OptimizerConfig.AdamW(1e-3, wd=0.01)),
                                       batch_size=args.batch, double_dqn=args.double_dqn, device=0, param_seed=1, arithmetic="f32_exact"))
@@ -268,6 +286,60 @@ def main_cnn_headform(args):
     out["value"] = out["b32"]["splitk"]["value"]
     line = json.dumps(out)
     with open(os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_headform.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+def main_cnn_headbwd(args):
+    """head backward layers against fused: one agent per form (both of --arithmetic and --head-form, "both" excepted), legs alternating, B = 32 and 256"""
+    import border_amd as B
+    import candle_dqn_cnn_restatement as RC
+    NS, NA, FORMS = 4, 6, ("layers", "fused")
+    spec = RC.CandleDqnCnnSpec(NS, NA, lr=1e-3, adamw=dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01), double_dqn=args.double_dqn)
+    arith = "f32_exact" if args.arithmetic == "both" else args.arithmetic
+    head = "layers" if args.head_form == "both" else args.head_form
+    out = {"metric": "dqn_atari_candle_updates_per_s_by_head_bwd_form", "shape": {"n_stack": NS, "n_actions": NA, "opt": "AdamW", "loss": "Mse", "arithmetic": arith,
+                                                                                   "head_form": head, "double_dqn": bool(args.double_dqn)},
+           "warmup": args.warmup, "steps": args.steps}
+    for bsz in (32, 256):
+        pairs = [(hb, B.CandleDqn.build(spec.to_config(B, bsz, device=0, seed=1)), ring_u8(B, NS)) for hb in FORMS]
+        for hb, agent, _ in pairs:
+            if arith != "f32_exact":
+                agent.set_arithmetic(arith)
+            agent.set_head_form(head)
+            agent.set_head_bwd_form(hb)
+        res = {hb: {"value": round(window(agent, rb, args.warmup, args.steps), 1)} for hb, agent, rb in pairs}
+        legs = {hb: [] for hb in FORMS}
+        for _ in range(args.legs):
+            for hb, agent, rb in pairs:
+                legs[hb].append(leg(agent, rb))
+        for hb, agent, rb in pairs:
+            v = sorted(legs[hb])
+            res[hb].update(ms_per_update=round(1e3 / res[hb]["value"], 4), steady_legs_updates_per_s=[round(x, 1) for x in legs[hb]],
+                           steady_median=round(v[len(v) // 2], 1), steady_spread_pct=round(100.0 * (v[-1] - v[0]) / v[len(v) // 2], 2), **launches(agent, rb))
+            agent.close(); rb.close()
+        res["fused_over_layers_steady_median"] = round(res["fused"]["steady_median"] / res["layers"]["steady_median"], 4)
+        res["worst_fused_leg_not_below_best_layers_leg"] = bool(min(legs["fused"]) >= max(legs["layers"]))
+        out[f"b{bsz}"] = res
+    out["value"] = out["b32"]["fused"]["value"]
+    line = json.dumps(out)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+def merge_against_parent(args):
+    """the layers agent of a parent checkout against this tree's: the output of four runs `--cnn --no-tch --batch b > <dir>/b<b>.json`,
+    taken alternating in one sitting, as one record (--out, or profiles/bench_candle_dqn_cnn_headbwd_parent.json)"""
+    out = {"metric": "dqn_atari_candle_updates_per_s_layers_agent_parent_against_tree",
+           "note": "tools/bench_candle_dqn.py --cnn --no-tch of the parent commit and of this tree, alternating in one sitting on one MI355X"}
+    for b in (32, 256):
+        for who, d in zip(("parent", "tree"), args.against_parent):
+            with open(os.path.join(d, f"b{b}.json")) as f:
+                out[f"{who}_b{b}"] = json.loads(next(l for l in f if l.startswith("{")))["candle_dqn_cnn"]
+        out[f"tree_over_parent_steady_median_b{b}"] = round(out[f"tree_b{b}"]["steady_median"] / out[f"parent_b{b}"]["steady_median"], 4)
+    line = json.dumps(out)
+    with open(args.out or os.path.join(ROOT, "profiles", "bench_candle_dqn_cnn_headbwd_parent.json"), "w") as f:
         f.write(line + "\n")
     print(line)
 
